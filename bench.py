@@ -13,6 +13,11 @@ skipped or cached between epochs.  The graph (232 965 vertices, ~114.6 M directe
 edges, symmetrised, self loops removed, seed 42) is partitioned in contiguous
 blocks over the N ranks (strong scaling: the total work is fixed).  Inputs are
 resident in HBM before the timed region.  One JSON line is printed by rank 0.
+
+A plain run does only what the headline needs: setup, W warm-up steps, K timed steps and the line (ms_per_step = one
+timed step).  --full adds everything else the line can carry: the CPU baseline, the transform-first and cached-ah0
+epochs and the other single-GPU configurations.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -224,6 +229,42 @@ def spmm_algorithmic_bytes(N, G, E, F):
     return E * 8 + 8 * (N + 1) + 4 * N + 4 * F * (N + G) + 4 * F * N
 
 
+DUMP_WEIGHTS = {"gcn": ("w",), "gat": ("w", "a_i"), "gatmh": ("w", "a_l", "a_r")}
+DUMP_ROW_BYTES = 48 << 20      # budget of the row-sampled activations; weights and statistics are a few MB at most
+
+
+def dump_outputs(ctx, g, gnn, out_dir):
+    """--dump-outputs: what one timed epoch hands its caller, read back after the last one.  Every layer's weights after its
+    Adam step (W<l>, plus a_i<l> / a_l<l> / a_r<l> for the GAT forms) and their gradients (dW<l>, ...), the training
+    statistics (train_stat: accuracy sum, loss sum, validation rows) and the activations the epoch leaves behind: hidden
+    outputs h<l> and the last layer's logits.  Activations are row-sampled: a fixed seeded subset of the local rows, the same
+    for every tensor and every run with the same arguments, within DUMP_ROW_BYTES; rows.npy holds their global vertex ids.
+    float32 as computed, except rows and train_stat (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    L = ctx.L
+    out = {}
+    for l in range(L):
+        for name in DUMP_WEIGHTS[gnn]:
+            tag = "W" if name == "w" else name
+            out[f"{tag}{l}"] = ctx.weight_get(l, name)
+            out[f"d{tag}{l}"] = ctx.weight_grad_get(l, name)
+    a, lo, n = ctx.train_stat()
+    out["train_stat"] = np.array([a, lo, n], np.float64)
+    if gnn == "gcn":
+        acts = [(f"h{l}", l, "h") for l in range(L - 1)] + [("logits", L - 1, "z")]
+    else:
+        acts = [(f"h{l}", l, "h") for l in range(1, L)] + [("logits", L - 1, "ah" if gnn == "gat" else "logits")]
+    N = int(g["localVtxCnt"])
+    cols = sum(ctx.info(l, t)[1] for _, l, t in acts)
+    k = min(N, max(1, DUMP_ROW_BYTES // (4 * cols)))
+    rows = np.arange(N) if k == N else np.sort(np.random.default_rng(0).choice(N, k, replace=False))
+    out["rows"] = np.asarray(g["localToGlobal"])[rows].astype(np.float64)
+    for key, l, t in acts:
+        out[key] = np.ascontiguousarray(ctx.download(l, t)[rows])
+    for key, arr in out.items():
+        np.save(os.path.join(out_dir, key + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -248,8 +289,18 @@ def main():
                          "dory_comm_set_host_transport over gloo (several ranks on ONE GPU: --device 0); diagnostic, not the metric")
     ap.add_argument("--device", type=int, default=-1, help="HIP device of this rank (default: LOCAL_RANK)")
     ap.add_argument("--with-friendster", action="store_true",
-                    help="also time BASELINE config 5 as rank 0 of 8 holds it (key friendster_rank0of8: ~2 min of setup, 58 GB of ghost rows)")
+                    help="with --full: also time BASELINE config 5 as rank 0 of 8 holds it (key friendster_rank0of8: ~2 min of setup, "
+                         "58 GB of ghost rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline, the transform-first and cached-ah0 epochs and "
+                         "the other single-GPU configurations (gat, gatmh, rmat, community, amazon_rank0of8); without it their keys "
+                         "are null or absent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (weights, weight gradients, training statistics, "
+                         "a fixed seeded row sample of the hidden and output activations) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -407,6 +458,9 @@ def main():
     else:
         E_in, E_out = nnz_in, nnz_out
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        run_stage["name"] = "writing the last timed step's outputs"
+        dump_outputs(ctx, g, args.gnn, args.dump_outputs)
     run_stage["name"] = "bookkeeping after the timed region"
     nl = len(DIMS) - 1
     edges_per_epoch = nl * E_in + (nl - 1) * E_out           # L forward (CSC) + L-1 backward (CSR) aggregations
@@ -481,12 +535,12 @@ def main():
 
     # ---- CPU baseline: the oracle (port of the reference CPU path) on this box's cores ----------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not gat and not args.emulate and args.workload == "reddit":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not gat and not args.emulate and args.workload == "reddit":
         cpu = cpu_baseline(ctx, g, args.cpu_rows)
 
     # ---- the same epoch in the transform-first order of layer 0 (opt-in mode, reported beside the headline) ----
     alt = None
-    if world == 1 and not gat and not tf_mode and not args.emulate and not args.opt and not args.no_alt:
+    if args.full and world == 1 and not gat and not tf_mode and not args.emulate and not args.opt and not args.no_alt:
         ctx.set_option("gcn_transform_first", 2)
         if ctx.transform_first_active():
             ctx.timing_enable(False)
@@ -501,7 +555,7 @@ def main():
 
     # ---- the same epoch with the layer-0 aggregate kept across epochs (opt-in gcn_cache_ah0, reported beside the headline) ----
     cached = None
-    if world == 1 and not gat and not tf_mode and not args.emulate and not args.opt and not args.no_alt:
+    if args.full and world == 1 and not gat and not tf_mode and not args.emulate and not args.opt and not args.no_alt:
         ctx.set_option("gcn_cache_ah0", 1)
         ctx.timing_enable(False)
         eng.run(max(1, args.warmup))          # (computes ah@0 once)
@@ -597,7 +651,7 @@ def main():
     eng.close()
     ctx.close()
     # ---- the other single-GPU configurations, each timed the same way (extra keys beside the headline) ----
-    if rank == 0 and world == 1 and not gat and not tf_mode and not args.emulate and not args.opt and not args.no_alt \
+    if args.full and rank == 0 and world == 1 and not gat and not tf_mode and not args.emulate and not args.opt and not args.no_alt \
             and args.workload == "reddit" and args.graph == "uniform" and args.scale == 1.0:
         steps_x, warm_x = max(2, min(args.steps, 5)), 1
         out["gatmh"] = extra_epoch(da, part, g, "gatmh", V, steps_x, warm_x,

@@ -89,6 +89,29 @@ def gen_partition_fixtures():
         print("partition fixture", name, sorted(os.listdir(d)))
 
 
+def gen_random_partition_fixtures(exe=os.path.join(HERE, "_ref", "ref_preprocess")):
+    """the random graphs of tests/test_oracle_partition.py::test_oracle_matches_live_reference (seeds 0-3), with the
+    graph.<id>.bin bytes the reference's DataLoader wrote for them: tests/golden/ref_random/seed<k>, same layout as parts_*"""
+    for seed in range(4):
+        rng = np.random.default_rng(seed)
+        V = int(rng.integers(5, 300))
+        E = int(rng.integers(0, 4000))
+        P = int(rng.integers(1, 6))
+        und = int(seed % 2)
+        src, dst = rng.integers(0, V, E), rng.integers(0, V, E)
+        parts = rng.integers(0, P, V)
+        d = os.path.join(GOLD, "ref_random", f"seed{seed}")
+        shutil.rmtree(d, ignore_errors=True)
+        os.makedirs(d)
+        po.write_bsnap_edges(os.path.join(d, "graph.bsnap.edges"), V, src, dst)
+        po.write_parts(os.path.join(d, "graph.bsnap.parts"), parts)
+        with open(os.path.join(d, "meta.txt"), "w") as f:
+            f.write(f"V={V} E={E} P={P} undirected={und}\n")
+        for nid in range(P):
+            subprocess.run([exe, d + "/", str(nid), str(P), str(und)], check=True, capture_output=True)
+        print("random partition fixture", f"seed{seed}", sorted(os.listdir(d)))
+
+
 def gen_numpy_gnn_fixture():
     """One epoch of the reference's numpy GCN (miscs/numpy-gnn) on a toy graph."""
     sys.path.insert(0, os.path.join(REF, "miscs", "numpy-gnn"))
@@ -222,6 +245,7 @@ if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     gen_wire_fixture()
     gen_partition_fixtures()
+    gen_random_partition_fixtures()
     gen_numpy_gnn_fixture()
     gen_numpy_gnn_large("numpy_gnn_reddit_dims", [602, 128, 41])            # BASELINE config 2 widths
     gen_numpy_gnn_large("numpy_gnn_amazon_dims", [300, 64, 64, 25], seed=29)  # config 4: 3 layers

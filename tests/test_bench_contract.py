@@ -1,5 +1,6 @@
 """bench.py's output contract (the driver parses this line): one JSON object on the last stdout line with the
-metric fields, the roofline and cpu_baseline objects; without a GPU the script must refuse, not fall back."""
+metric fields, the roofline and (with --full) cpu_baseline objects; without a GPU the script must refuse, not fall back.
+A plain run carries the headline only, and --dump-outputs writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def test_bench_refuses_without_gpu():
 @pytest.mark.gpu
 def test_bench_json_line_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--scale", "0.02", "--cpu-rows", "2000"], capture_output=True, text=True, timeout=900)
+                        "--scale", "0.02", "--cpu-rows", "2000", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines            # stdout carries the JSON line and nothing else
@@ -76,3 +77,82 @@ def test_stdout_is_shielded_while_communicators_are_created():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     assert r.stdout.strip() == '{"json": 1}' and "noise from a library" in r.stderr
+
+
+def _bench(args, timeout=600):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """without --full nothing beside the headline runs; --dump-outputs writes the same arrays for the same arguments"""
+    from helpers import rel_err
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    runs = [_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--scale", "0.02", "--dump-outputs", str(d)]) for d in dirs]
+    for d in runs:
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "edges/s" and d["dtype"] == "f32"
+        assert d["higher_is_better"] is True and d["value"] > 0 and "GCN" in d["metric"]
+        assert d["cpu_baseline"] is None and d["transform_first"] is None and d["cached_ah0"] is None
+        for k in ("gat", "gatmh", "rmat", "community", "amazon_rank0of8", "friendster_rank0of8"):
+            assert k not in d, k
+    names = sorted(f.name for f in dirs[0].iterdir())
+    assert names == sorted(["W0.npy", "W1.npy", "dW0.npy", "dW1.npy", "train_stat.npy", "rows.npy", "h0.npy", "logits.npy"]), names
+    assert sum(f.stat().st_size for f in dirs[0].iterdir()) <= 64 << 20
+    a = {n[:-4]: np.load(dirs[0] / n) for n in names}
+    b = {n[:-4]: np.load(dirs[1] / n) for n in names}
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and np.isfinite(a[n]).all(), n
+        assert a[n].shape == b[n].shape, n
+    assert a["W0"].shape == (602, 128) and a["W1"].shape == (128, 41)
+    assert a["h0"].shape == (a["rows"].size, 128) and a["logits"].shape == (a["rows"].size, 41)
+    assert np.array_equal(a["rows"], b["rows"]) and a["train_stat"][2] > 0
+    for n in a:
+        assert rel_err(b[n], a[n]) < 1e-4, (n, rel_err(b[n], a[n]))
+
+
+def test_dump_outputs_without_a_gpu(tmp_path):
+    """dump_outputs against a stand-in context: names, dtypes, the seeded row sample and the size budget"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+
+    class Ctx:
+        L = 2
+        shapes = {(0, "h"): 128, (1, "z"): 41}
+
+        def weight_get(self, l, name):
+            return np.full((602, 128) if l == 0 else (128, 41), l + 1.0, np.float32)
+
+        def weight_grad_get(self, l, name):
+            return -self.weight_get(l, name)
+
+        def train_stat(self):
+            return 7.0, 3.5, 100
+
+        def info(self, l, name):
+            return N, self.shapes[(l, name)], 0, 0
+
+        def download(self, l, name):
+            return np.arange(N * self.shapes[(l, name)], dtype=np.float32).reshape(N, -1)
+
+    N = 200000
+    g = {"localVtxCnt": N, "localToGlobal": np.arange(N, dtype=np.uint32)[::-1] + 5}
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(Ctx(), g, "gcn", str(d))
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == sorted(["W0.npy", "W1.npy", "dW0.npy", "dW1.npy", "train_stat.npy", "rows.npy", "h0.npy", "logits.npy"])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    h0, lg = np.load(tmp_path / "a" / "h0.npy"), np.load(tmp_path / "a" / "logits.npy")
+    assert rows.dtype == np.float64 and h0.dtype == np.float32 and 1000 < rows.size < N
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))         # the sample is fixed
+    local = (N + 4 - rows).astype(np.int64)                                    # back from the global ids above
+    assert np.all(np.diff(local) > 0) and h0.shape == (rows.size, 128) and lg.shape == (rows.size, 41)
+    assert np.array_equal(h0[:, 0], local * 128.0) and np.array_equal(lg[:, 0], local * 41.0)
+    assert np.array_equal(np.load(tmp_path / "a" / "train_stat.npy"), [7.0, 3.5, 100.0])
+    assert np.array_equal(np.load(tmp_path / "a" / "dW1.npy"), -np.load(tmp_path / "a" / "W1.npy"))

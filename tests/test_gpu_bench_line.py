@@ -1,4 +1,4 @@
-"""The one JSON line the driver reads: `python bench.py` with its defaults (fewer steps here) must print exactly one line
+"""The one JSON line the driver reads: `python bench.py --full` with its defaults (fewer steps here) must print exactly one line
 with the contract's keys, the BASELINE metric's workload, a roofline whose numbers follow from each other, and the extra
 keys the reviews asked for (R-MAT, community, GAT, 8-head GAT, config 4 as one rank of 8 with its own roofline)."""
 import json
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(900)
 def test_default_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-rows", "4000"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-rows", "4000", "--full"],
                        capture_output=True, text=True, timeout=850, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

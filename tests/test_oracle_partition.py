@@ -1,6 +1,6 @@
 """Oracle pin #1: the numpy restatement of DataLoader::preprocess reproduces, byte
 for byte, the graph.<id>.bin files written by the reference's own DataLoader
-(oracle/_ref/ref_preprocess; fixtures committed under tests/golden/parts_*)."""
+(oracle/_ref/ref_preprocess; fixtures committed under tests/golden/parts_* and tests/golden/ref_random)."""
 import glob
 import os
 import subprocess
@@ -37,24 +37,29 @@ def test_oracle_matches_reference_bins(d):
 
 
 REF_EXE = os.path.join(ROOT, "oracle", "_ref", "ref_preprocess")
+RANDOM = os.path.join(ROOT, "tests", "golden", "ref_random")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_EXE), reason="oracle/_ref not built")
 @pytest.mark.parametrize("seed", range(4))
 def test_oracle_matches_live_reference(seed):
-    """Random graphs through the live reference binary (when present)."""
-    rng = np.random.default_rng(seed)
-    V = int(rng.integers(5, 300))
-    E = int(rng.integers(0, 4000))
-    P = int(rng.integers(1, 6))
-    und = bool(seed % 2)
-    src, dst = rng.integers(0, V, E), rng.integers(0, V, E)
-    parts = rng.integers(0, P, V)
-    with tempfile.TemporaryDirectory() as d:
-        d += "/"
-        po.write_bsnap_edges(d + "graph.bsnap.edges", V, src, dst)
-        po.write_parts(d + "graph.bsnap.parts", parts)
+    """Random graphs (oracle/gen_golden.py gen_random_partition_fixtures: seeded V, E, P, direction and parts) against the
+    bytes the reference's DataLoader wrote for them (tests/golden/ref_random/seed<k>); where oracle/_ref is built, the live
+    reference binary is run on the same inputs as well and must write those bytes again."""
+    d = os.path.join(RANDOM, f"seed{seed}")
+    P, und = _meta(d)
+    assert und == bool(seed % 2)
+    V, src, dst = po.read_bsnap_edges(os.path.join(d, "graph.bsnap.edges"))
+    parts = np.loadtxt(os.path.join(d, "graph.bsnap.parts"), dtype=np.int64, ndmin=1)
+    assert parts.size == V and 5 <= V < 300 and src.size < 4000 and 1 <= P < 6
+    for nid in range(P):
+        ref = open(os.path.join(d, f"graph.{nid}.bin"), "rb").read()
+        assert po.dump_bytes(po.preprocess(src, dst, parts, nid, P, und)) == ref
+    if not os.path.exists(REF_EXE):
+        return
+    with tempfile.TemporaryDirectory() as t:
+        t += "/"
+        po.write_bsnap_edges(t + "graph.bsnap.edges", V, src, dst)
+        po.write_parts(t + "graph.bsnap.parts", parts)
         for nid in range(P):
-            subprocess.run([REF_EXE, d, str(nid), str(P), str(int(und))], check=True, capture_output=True)
-            ref = open(d + f"graph.{nid}.bin", "rb").read()
-            assert po.dump_bytes(po.preprocess(src, dst, parts, nid, P, und)) == ref
+            subprocess.run([REF_EXE, t, str(nid), str(P), str(int(und))], check=True, capture_output=True)
+            assert open(t + f"graph.{nid}.bin", "rb").read() == open(os.path.join(d, f"graph.{nid}.bin"), "rb").read()

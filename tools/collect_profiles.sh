@@ -9,7 +9,7 @@ R=$PWD
 OUT=$R/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+python bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d /tmp/prof_${TAG}_k -o k -- python "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-alt > /tmp/prof_${TAG}_k.log 2>&1
 python "$R/tools/rocprof_summary.py" "$(find /tmp/prof_${TAG}_k -name '*.db' | head -1)" > "$OUT/${TAG}_bench_kernel_stats.txt" 2>&1

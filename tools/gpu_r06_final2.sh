@@ -10,7 +10,7 @@ done
 cd $R
 python bench.py --gnn gat --steps 3 --warmup 1 --no-cpu-baseline > $OUT/r06_bench_gat.json 2>/dev/null
 python bench.py --gnn gatmh --steps 3 --warmup 1 --no-cpu-baseline > $OUT/r06_bench_gatmh.json 2>/dev/null
-python bench.py > $OUT/r06_bench.json 2> $OUT/r06_bench.err
+python bench.py --full > $OUT/r06_bench.json 2> $OUT/r06_bench.err
 python - <<PY
 import json
 d=json.load(open('$OUT/r06_bench.json')); print(d['ms_per_step'], d['gat']['ms_per_step'], d['gatmh']['ms_per_step'], d['roofline']['traffic'], d['gatmh']['roofline']['traffic'])
