@@ -109,14 +109,44 @@ int blk_group_for(dory_ctx *c, uint32_t ld) {
     return group;
 }
 
+// Option gcn_bf16_gather: the rows of one aggregation rounded to bf16 into the context's shadow buffer, [N local rows ;
+// ghost rows], every call (nothing is kept: a caller may write x / h / fg through a raw pointer between two calls).  The
+// buffer only grows, outside a recording.
+static int bf16_shadow(dory_ctx *c, uint64_t rows, uint32_t ld) {
+    const size_t need = (size_t)rows * ld * sizeof(uint16_t);
+    if (need <= c->bf16_rows_bytes) return DORY_OK;
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the bf16 rows of gcn_bf16_gather would have to grow while recording");
+    if (c->bf16_rows) {
+        HIPCK(c, hipStreamSynchronize(c->compute));
+        (void)hipFree(c->bf16_rows);
+        c->bf16_rows = nullptr;
+        c->bf16_rows_bytes = 0;
+        epoch_graph_drop_locked(c);   // (a recorded epoch would read the freed buffer)
+    }
+    HIPCK(c, hipMalloc((void **)&c->bf16_rows, need));
+    c->bf16_rows_bytes = need;
+    return DORY_OK;
+}
+static int bf16_convert(dory_ctx *c, const Tensor &t, uint64_t first_row) {
+    if (!t.rows) return DORY_OK;
+    Timed tc(c, "bf16_convert", c->compute);
+    HIPCK(c, launch_bf16_rows(t.d, c->bf16_rows + first_row * t.ld, t.rows * t.ld, c->compute));
+    return DORY_OK;
+}
+
 // One aggregation.  Edge weights come from `val` (any per-edge array, K1), or -- when
 // `val` is the adjacency's own static array -- from the source-blocked copy (K1b), or are
 // 1 with a per-destination factor `row_scale` (K1b, unit mode; the reference GAT's edge
 // scores depend on the destination only, CPU_comm.cpp:299-319).
+// bf16 (option gcn_bf16_gather, GCN only): every row read -- self row, local and ghost rows -- is rounded to bf16 first;
+// edge values, norm, the sums and `out` stay fp32, the sums in the order of the fp32 path.  K1s and K1 have bf16 forms,
+// K1b has none: where fp32 would take K1b, bf16 takes K1.
 static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &xl, Tensor *xg, Tensor &out,
-                uint32_t F, int accumulate, const float *row_scale = nullptr) {
+                uint32_t F, int accumulate, const float *row_scale = nullptr, bool bf16 = false) {
     if (xl.ld != out.ld || (xg && xg->rows && xg->ld != xl.ld) || xl.cols != F)
         return fail(c, DORY_ERR_ARG, "spmm: tensor shapes disagree (F=%u ld %u/%u)", F, xl.ld, out.ld);
+    if (bf16 && (row_scale || xl.rows < c->N))
+        return fail(c, DORY_ERR_ARG, "spmm: bf16 rows need edge weights and N rows");
     c->last_spmm_unit = false;
     SpmmArgs a{};
     a.N = c->N; a.F = F; a.ld = xl.ld;
@@ -126,6 +156,23 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
     a.self_scale = c->norm;
     a.self_mode = self_mode;
     a.xl = xl.d; a.xg = (xg && xg->rows) ? xg->d : nullptr; a.out = out.d;   // nullptr: no ghost rows (the blocked kernel then skips the select)
+    const uint64_t ghost_rows = a.xg ? xg->rows : 0;
+    if (bf16) {
+        // the kernels' xl / xg point at bf16 rows from here on; the local rows are converted now, the ghost rows only once
+        // the exchange that writes them has landed (halo() below, at every wait_halo of this function)
+        Tensor local = xl;
+        local.rows = c->N;
+        int rc = bf16_shadow(c, (uint64_t)c->N + ghost_rows, a.ld);
+        if (!rc) rc = bf16_convert(c, local, 0);
+        if (rc) return rc;
+        a.xl = reinterpret_cast<const float *>(c->bf16_rows);
+        a.xg = ghost_rows ? reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * a.ld) : nullptr;
+    }
+    auto halo = [&]() -> int {
+        int rc = wait_halo(c);
+        if (!rc && bf16 && ghost_rows) rc = bf16_convert(c, *xg, c->N);
+        return rc;
+    };
     a.accumulate = accumulate;
     a.order = (c->opt["spmm_order"] >= 2 || (c->opt["spmm_order"] == 1 && (csc ? c->skewIn : c->skewOut))) ? (csc ? c->orderIn : c->orderOut) : nullptr;
     const bool static_vals = val == (csc ? c->cscVal : c->csrVal) && !(c->gnn == DORY_GAT && csc);  // GAT rewrites cscVal
@@ -173,11 +220,11 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
                     Timed tp(c, "spmm_xcd_probe", c->compute);
                     for (auto &x : ev.e) HIPCK(c, hipEventCreate(&x));
                     const uint32_t hi = two ? S.nb_local : S.nb;
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags | 8u, c->scratch));   // (warm: layout, code)
+                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags | 8u, c->scratch, 0, bf16));   // (warm: layout, code)
                     HIPCK(c, hipEventRecord(ev.e[0], c->compute));
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags, c->scratch));
+                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags, c->scratch, 0, bf16));
                     HIPCK(c, hipEventRecord(ev.e[1], c->compute));
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags | 8u, c->scratch));
+                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags | 8u, c->scratch, 0, bf16));
                     HIPCK(c, hipEventRecord(ev.e[2], c->compute));
                     HIPCK(c, hipEventSynchronize(ev.e[2]));
                     (void)hipEventElapsedTime(&c->xcd_gated_ms, ev.e[0], ev.e[1]);
@@ -187,27 +234,28 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
                 sflags |= c->xcd_policy == 0 ? 0u : 8u;      // undecided (recording, accumulating caller): ungated, never a timeout
             }
             Timed t(c, "spmm", c->compute);
+            if (bf16) c->bf16_gathers_k1s++;
             if (two) {
                 // under an exchange in flight the RCCL kernels need CUs of their own
                 const uint32_t reserve = c->halo_pending ? (uint32_t)c->opt["spmm_sweep_reserve_cus"] : 0u;
                 {
                     Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, S.nb_local, done, c->compute, ctl, sflags, c->scratch, reserve));
+                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, S.nb_local, done, c->compute, ctl, sflags, c->scratch, reserve, bf16));
                 }
-                if ((rc = wait_halo(c))) return rc;
+                if ((rc = halo())) return rc;
                 SpmmArgs a2 = a;
                 a2.self_mode = 0;
                 a2.accumulate = 1;
-                HIPCK(c, launch_spmm_sweep(a2, S, group, row_scale, G, S.nb_local, S.nb, done, c->compute, ctl, sflags | 2u, c->scratch));
+                HIPCK(c, launch_spmm_sweep(a2, S, group, row_scale, G, S.nb_local, S.nb, done, c->compute, ctl, sflags | 2u, c->scratch, 0, bf16));
             } else {
-                if ((rc = wait_halo(c))) return rc;
-                HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, S.nb, done, c->compute, ctl, sflags, c->scratch));
+                if ((rc = halo())) return rc;
+                HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, S.nb, done, c->compute, ctl, sflags, c->scratch, 0, bf16));
             }
-            HIPCK(c, launch_spmm_sweep_combine(a, S, row_scale, c->scratch, c->compute));
+            HIPCK(c, launch_spmm_sweep_combine(a, S, row_scale, c->scratch, c->compute, bf16));
             return DORY_OK;
         }
     }
-    if (c->opt["spmm_variant"] >= 1 && (static_vals || row_scale) && c->N > 0 && a.ld >= 32) {
+    if (c->opt["spmm_variant"] >= 1 && !bf16 && (static_vals || row_scale) && c->N > 0 && a.ld >= 32) {
         const int group = blk_group_for(c, a.ld);
         int rc = ensure_blocked(c, csc, group);
         if (rc) return rc;
@@ -249,6 +297,7 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
         }
     }
     if (!val) return fail(c, DORY_ERR_ARG, "spmm: no edge values");
+    if (bf16) c->bf16_gathers_k1++;
     const LongRowsDev &longRows = csc ? c->longIn : c->longOut;
     if (longRows.nchunks) {   // hubs: K1 stops after LONG_ROW_CLAMP edges of a row, workgroup-per-chunk kernels do the rest
         int rc = ensure_scratch(c, (size_t)longRows.nchunks * a.ld * sizeof(float));
@@ -274,9 +323,9 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
             p1.ptr_end = es.mid;
             {
                 Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
-                HIPCK(c, launch_spmm(p1, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute));
+                HIPCK(c, launch_spmm(p1, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
             }
-            int rc = wait_halo(c);
+            int rc = halo();
             if (rc) return rc;
             SpmmArgs p2 = a;
             p2.ptr = es.mid;
@@ -284,12 +333,12 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
             p2.self_mode = 0;
             p2.accumulate = 2;
             if (split && nInt < c->N) { p2.order = split + nInt; p2.rows = c->N - nInt; }   // rows without a ghost source are done
-            if (!split || nInt < c->N) HIPCK(c, launch_spmm(p2, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute));
+            if (!split || nInt < c->N) HIPCK(c, launch_spmm(p2, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
             return DORY_OK;
         }
-        int rc = wait_halo(c);
+        int rc = halo();
         if (rc) return rc;
-        HIPCK(c, launch_spmm(a, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute));
+        HIPCK(c, launch_spmm(a, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
         return DORY_OK;
     }
     // (other cases -- GAT's per-epoch edge values, hub rows: the rows whose sources are all local run first, the rows that read
@@ -303,21 +352,21 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
         part.rows = nInt;
         {
             Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
-            HIPCK(c, launch_spmm(part, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute));
+            HIPCK(c, launch_spmm(part, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
         }
-        int rc = wait_halo(c);
+        int rc = halo();
         if (rc) return rc;
         part.order = split + nInt;
         part.rows = c->N - nInt;
-        HIPCK(c, launch_spmm(part, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute));
+        HIPCK(c, launch_spmm(part, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
         return DORY_OK;
     }
     {
-        int rc = wait_halo(c);
+        int rc = halo();
         if (rc) return rc;
     }
-    HIPCK(c, launch_spmm(a, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute));
-    if (longRows.nchunks) HIPCK(c, launch_spmm_long_rows(a, longRows, c->scratch, c->compute));
+    HIPCK(c, launch_spmm(a, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
+    if (longRows.nchunks) HIPCK(c, launch_spmm_long_rows(a, longRows, c->scratch, c->compute, bf16));
     return DORY_OK;
 }
 
@@ -332,6 +381,13 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
     CHECK_CTX(c);
     if (!c->prealloc) return fail(c, DORY_ERR_ARG, "aggregate: preallocate first");
     if (c->gnn == DORY_GCN) {  // Engine::aggregateGCN (gcn_ops.cpp:130-191)
+        // opt-in "gcn_bf16_gather" (no reference counterpart): 1 = the forward aggregations read bf16 rows, 2 = the backward
+        // ones too (spmm(): fp32 sums, same order).  K1b has no bf16 form: an explicit spmm_variant = 1 is refused
+        const int64_t bfm = c->opt["gcn_bf16_gather"];
+        if (bfm && c->opt["spmm_variant"] == 1)
+            return fail(c, DORY_ERR_ARG, "aggregate: gcn_bf16_gather = %lld with spmm_variant = 1 (K1b has no bf16 form: spmm_variant 0 or 2)",
+                        (long long)bfm);
+        const bool bf_fwd = bfm >= 1, bf_bwd = bfm >= 2;
         if (dir == DORY_FORWARD) {
             if (layer >= c->L) return fail(c, DORY_ERR_ARG, "aggregate: layer %u out of range", layer);
             Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
@@ -346,7 +402,7 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
                     if (!rc && c->Gsrc) rc = gemm(c, 0, 0, c->Gsrc, c->dims[1], c->dims[0], *fg, W, *fgxw);
                     if (rc) return rc;
                 }   // deeper layers: apply_vertex(l-1) left xw@l, the forward exchange of layer l its ghost rows
-                return spmm(c, true, c->cscVal, 1, *xw, fgxw, *z, c->dims[layer + 1], 0);
+                return spmm(c, true, c->cscVal, 1, *xw, fgxw, *z, c->dims[layer + 1], 0, nullptr, bf_fwd);
             }
             // Opt-in "gcn_cache_ah0" (no reference counterpart; the reference recomputes it every epoch and so does the
             // default here): in full-graph training ah@0 = A_hat [x ; fg@0] is a constant of the run -- x and fg@0 come
@@ -355,14 +411,14 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
             if (layer == 0 && c->opt["gcn_cache_ah0"] && !c->capturing) {
                 if (c->ah0_valid) { c->ah0_skips++; return DORY_OK; }
                 c->agg_static_ghosts = true;
-                int rc = spmm(c, true, c->cscVal, 1, *in, fg, *ah, c->dims[layer], 0);
+                int rc = spmm(c, true, c->cscVal, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd);
                 c->agg_static_ghosts = false;
                 c->ah0_valid = rc == DORY_OK;
                 return rc;
             }
             if (layer == 0) c->ah0_valid = false;
             c->agg_static_ghosts = layer == 0;
-            const int src_ = spmm(c, true, c->cscVal, 1, *in, fg, *ah, c->dims[layer], 0);
+            const int src_ = spmm(c, true, c->cscVal, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd);
             c->agg_static_ghosts = false;
             return src_;
         }
@@ -371,7 +427,7 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
             Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
             if (!in) return fail(c, DORY_ERR_ARG, "aggregate: input tensor missing");
             const uint32_t Fin = c->dims[layer], Fout = c->dims[layer + 1];
-            int rc = spmm(c, false, c->csrVal, 1, *g, bgg, *u, Fout, 0);
+            int rc = spmm(c, false, c->csrVal, 1, *g, bgg, *u, Fout, 0, nullptr, bf_bwd);
             if (rc) return rc;
             if ((rc = gemm(c, 1, 0, Fin, Fout, c->N, *in, *u, c->wgrads[layer]["w"]))) return rc;
             if (layer == 0) return DORY_OK;
@@ -382,7 +438,7 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
         NEED(grad, layer, "grad");
         NEED(bg, layer - 1, "bg");
         NEED(aTg, layer - 1, "aTg");
-        return spmm(c, false, c->csrVal, 1, *grad, bg, *aTg, c->dims[layer], 0);
+        return spmm(c, false, c->csrVal, 1, *grad, bg, *aTg, c->dims[layer], 0, nullptr, bf_bwd);
     }
     // Engine::aggregateGAT (gat_ops.cpp:173-243): tensors live at layer-1
     if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "aggregate GAT: layer %u out of range", layer);

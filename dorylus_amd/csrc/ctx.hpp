@@ -183,6 +183,11 @@ struct dory_ctx {
     bool prealloc = false;
     bool ah0_valid = false;      // option gcn_cache_ah0: ah@0 holds the aggregate of the current x / fg@0 / adjacency
     uint64_t ah0_skips = 0;      // layer-0 aggregations answered from it
+    // option gcn_bf16_gather: the bf16 copy of the rows an aggregation reads ((N + ghosts) x ld, rewritten by every
+    // aggregation that uses it, never kept across calls), and the aggregations that ran on it per kernel family
+    uint16_t *bf16_rows = nullptr;
+    size_t bf16_rows_bytes = 0;
+    uint64_t bf16_gathers_k1s = 0, bf16_gathers_k1 = 0;
     std::vector<std::map<std::string, dory::Tensor>> tensors;   // [layer][name]
     std::vector<std::map<std::string, dory::Tensor>> weights;   // "w", "a_i"
     std::vector<std::map<std::string, dory::Tensor>> wgrads;    // same names
@@ -269,10 +274,11 @@ struct SpmmArgs {
     const uint32_t *order;  // optional row schedule (longest first) or nullptr
     const uint64_t *ptr_end;// K1: end of every row's edge range (nullptr: ptr[v + 1]); with accumulate == 2 the sum STARTS from out[v]
 };
-hipError_t launch_spmm(const SpmmArgs &a, int variant, int slab, hipStream_t s);
+// bf16: xl / xg point at bf16 rows of ld elements (launch_bf16_rows; option gcn_bf16_gather), the sums stay fp32
+hipError_t launch_spmm(const SpmmArgs &a, int variant, int slab, hipStream_t s, bool bf16 = false);
 
 void plan_long_rows(const uint64_t *ptr, uint32_t N, LongRowsHost *out);
-hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float *partial /*nchunks x ld*/, hipStream_t s);
+hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float *partial /*nchunks x ld*/, hipStream_t s, bool bf16 = false);
 
 hipError_t build_blocked(const uint64_t *ptr, const uint32_t *idx, const float *val, uint32_t N, uint32_t NG,
                          uint64_t nnz, uint32_t want_nb /*0 = auto*/, uint32_t row_bytes, BlockedAdj *out,
@@ -310,9 +316,13 @@ size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t
 hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, const float *row_scale, uint32_t cus_per_xcd,
                              uint32_t b_lo, uint32_t b_hi, uint32_t *done /* sweep_scratch_bytes() */, hipStream_t s,
                              const SweepCtl &ctl, uint32_t flags = 0, float *split_partial = nullptr /* B.nslots x ld floats */,
-                             uint32_t reserve_cus = 0 /* CUs per XCD left to concurrent kernels */);
+                             uint32_t reserve_cus = 0 /* CUs per XCD left to concurrent kernels */,
+                             bool bf16 = false /* bf16 source rows (launch_spmm), no row_scale */);
 hipError_t launch_spmm_sweep_combine(const SpmmArgs &a, const BlockedAdj &B, const float *row_scale, const float *split_partial,
-                                     hipStream_t s);
+                                     hipStream_t s, bool bf16 = false);
+// fp32 -> bf16 (round to nearest even) of n elements, n a multiple of 4: the rows an aggregation reads under option
+// gcn_bf16_gather (elementwise.hip)
+hipError_t launch_bf16_rows(const float *x, uint16_t *y, uint64_t n, hipStream_t s);
 hipError_t launch_occupy_cus(uint32_t workgroups, uint64_t usec, hipStream_t s);   // diagnostic (dory_debug_occupy_cus)
 hipError_t launch_xcd_probe(uint32_t *xcc /*grid words*/, uint32_t grid, hipStream_t s);   // HW_REG_XCC_ID of every probe workgroup
 size_t blocked_partial_bytes(const SpmmArgs &a, const BlockedAdj &B);

@@ -335,6 +335,28 @@ hipError_t launch_row_axpy(float *out, const float *S, const float *rs, const fl
     return hipGetLastError();
 }
 
+// option gcn_bf16_gather: the rows an aggregation reads, rounded to bf16 (nearest even; v_cvt_pk_bf16_f32), into the
+// context's shadow buffer -- every element of an ld-wide row, so that padding columns stay 0
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 p = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(uint32_t, p);
+}
+__global__ __launch_bounds__(256) void bf16_rows_kernel(const float4 *x, uint2 *y, uint64_t n4) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * blockDim.x) {
+        const float4 v = x[i];
+        y[i] = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+    }
+}
+hipError_t launch_bf16_rows(const float *x, uint16_t *y, uint64_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n & 3) return hipErrorInvalidValue;
+    const uint64_t n4 = n >> 2;
+    hipLaunchKernelGGL(bf16_rows_kernel, dim3((uint32_t)std::min<uint64_t>(8192, (n4 + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(x), reinterpret_cast<uint2 *>(y), n4);
+    return hipGetLastError();
+}
+
 hipError_t launch_pad_copy(float *dst, uint32_t ldd, const float *src, uint32_t lds, uint64_t rows,
                            uint32_t cols, hipStream_t s) {
     if (rows == 0 || ldd == 0) return hipSuccess;

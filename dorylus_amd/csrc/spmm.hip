@@ -32,8 +32,10 @@
 
 namespace dory {
 
-template <int GROUP, int CHUNKS>
-__global__ __launch_bounds__(256) void spmm_rows_kernel(SpmmArgs a) {
+// BF16: xl / xg hold bf16 rows of ld elements (option gcn_bf16_gather; spmm_rows_bf16_kernel); the sums stay fp32
+template <int GROUP, int CHUNKS, bool BF16>
+__device__ __forceinline__ void spmm_rows_body(SpmmArgs a) {
+    typedef RowChunk<BF16> RC;
     constexpr int RPW = 64 / GROUP;      // rows per wave
     constexpr int RPB = 4 * RPW;         // rows per 256-thread block
     const int lane = threadIdx.x & 63;
@@ -64,15 +66,15 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(SpmmArgs a) {
             if (act[k]) acc[k] = o4[(size_t)v * nchunk + col[k]];
     }
 
-    const float4 *xl4 = reinterpret_cast<const float4 *>(a.xl);
-    const float4 *xg4 = reinterpret_cast<const float4 *>(a.xg);
+    const RC *xl4 = reinterpret_cast<const RC *>(a.xl);
+    const RC *xg4 = reinterpret_cast<const RC *>(a.xg);
 
     if (a.self_mode != 0) {
         const float sc = (a.self_mode == 1 && row_ok) ? a.self_scale[v] : 1.f;
 #pragma unroll
         for (int k = 0; k < CHUNKS; ++k)
             if (act[k]) {
-                float4 x = xl4[(size_t)v * nchunk + col[k]];
+                float4 x = row_chunk(xl4[(size_t)v * nchunk + col[k]]);
                 acc[k] = make_float4(x.x * sc, x.y * sc, x.z * sc, x.w * sc);
             }
     }
@@ -97,11 +99,11 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(SpmmArgs a) {
             for (int u = 0; u < 4; ++u) {
                 const uint32_t s = bcast_u32<GROUP>(my_idx, j + u);
                 w[u] = bcast_f32<GROUP>(my_val, j + u);
-                const float4 *row = s < a.N ? xl4 + (size_t)s * nchunk
-                                            : xg4 + (size_t)(s - a.N) * nchunk;
+                const RC *row = s < a.N ? xl4 + (size_t)s * nchunk
+                                        : xg4 + (size_t)(s - a.N) * nchunk;
 #pragma unroll
                 for (int k = 0; k < CHUNKS; ++k)
-                    x[u][k] = row[col[k]];
+                    x[u][k] = row_chunk(row[col[k]]);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -111,11 +113,11 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(SpmmArgs a) {
         for (; j < n; ++j) {
             const uint32_t s = bcast_u32<GROUP>(my_idx, j);
             const float w = bcast_f32<GROUP>(my_val, j);
-            const float4 *row = s < a.N ? xl4 + (size_t)s * nchunk
-                                        : xg4 + (size_t)(s - a.N) * nchunk;
+            const RC *row = s < a.N ? xl4 + (size_t)s * nchunk
+                                    : xg4 + (size_t)(s - a.N) * nchunk;
 #pragma unroll
             for (int k = 0; k < CHUNKS; ++k)
-                acc[k] = fma4(w, row[col[k]], acc[k]);
+                acc[k] = fma4(w, row_chunk(row[col[k]]), acc[k]);
         }
         e += n;
     }
@@ -134,13 +136,19 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(SpmmArgs a) {
 }
 
 template <int GROUP, int CHUNKS>
-static hipError_t launch_t(const SpmmArgs &a, hipStream_t s) {
+__global__ __launch_bounds__(256) void spmm_rows_kernel(SpmmArgs a) { spmm_rows_body<GROUP, CHUNKS, false>(a); }
+template <int GROUP, int CHUNKS>
+__global__ __launch_bounds__(256) void spmm_rows_bf16_kernel(SpmmArgs a) { spmm_rows_body<GROUP, CHUNKS, true>(a); }
+
+template <int GROUP, int CHUNKS>
+static hipError_t launch_t(const SpmmArgs &a, hipStream_t s, bool bf16) {
     constexpr int RPB = 4 * (64 / GROUP);
     const uint32_t nchunk = a.ld >> 2;
     const uint32_t rows = a.rows ? a.rows : a.N;
     dim3 grid((rows + RPB - 1) / RPB, (nchunk + GROUP * CHUNKS - 1) / (GROUP * CHUNKS));
     if (rows == 0 || nchunk == 0) return hipSuccess;
-    hipLaunchKernelGGL((spmm_rows_kernel<GROUP, CHUNKS>), grid, dim3(256), 0, s, a);
+    if (bf16) hipLaunchKernelGGL((spmm_rows_bf16_kernel<GROUP, CHUNKS>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((spmm_rows_kernel<GROUP, CHUNKS>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -152,13 +160,15 @@ static hipError_t launch_t(const SpmmArgs &a, hipStream_t s) {
 // LDS), and a last kernel adds a row's chunk sums to `out` in chunk order -- deterministic, no atomics.
 struct LongChunk { uint32_t row; uint32_t pad; uint64_t e0, e1; };
 
-__global__ __launch_bounds__(256) void spmm_longrow_kernel(SpmmArgs a, const LongChunk *chunks, float *partial) {
+template <bool BF16>
+__device__ __forceinline__ void spmm_longrow_body(SpmmArgs a, const LongChunk *chunks, float *partial) {
+    typedef RowChunk<BF16> RC;
     extern __shared__ float4 lds4[];                    // [4][nchunk]
     const LongChunk ch = chunks[blockIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t nchunk = a.ld >> 2;
-    const float4 *xl4 = reinterpret_cast<const float4 *>(a.xl);
-    const float4 *xg4 = reinterpret_cast<const float4 *>(a.xg);
+    const RC *xl4 = reinterpret_cast<const RC *>(a.xl);
+    const RC *xg4 = reinterpret_cast<const RC *>(a.xg);
     const uint64_t len = ch.e1 - ch.e0, q = (len + 3) / 4;
     const uint64_t wb = ch.e0 + (uint64_t)wave * q, we = wb + q < ch.e1 ? wb + q : ch.e1;
     for (uint32_t c0 = 0; c0 < nchunk; c0 += 64) {      // 256 floats of the row per pass
@@ -174,14 +184,14 @@ __global__ __launch_bounds__(256) void spmm_longrow_kernel(SpmmArgs a, const Lon
             for (int u = 0; u < 4; ++u) {
                 const uint32_t s = a.idx[e + u];        // wave-uniform
                 w[u] = a.val[e + u];
-                x[u] = (s < a.N ? xl4 + (size_t)s * nchunk : xg4 + (size_t)(s - a.N) * nchunk)[cc];
+                x[u] = row_chunk((s < a.N ? xl4 + (size_t)s * nchunk : xg4 + (size_t)(s - a.N) * nchunk)[cc]);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc = fma4(w[u], x[u], acc);
         }
         for (; e < we; ++e) {
             const uint32_t s = a.idx[e];
-            acc = fma4(a.val[e], (s < a.N ? xl4 + (size_t)s * nchunk : xg4 + (size_t)(s - a.N) * nchunk)[cc], acc);
+            acc = fma4(a.val[e], row_chunk((s < a.N ? xl4 + (size_t)s * nchunk : xg4 + (size_t)(s - a.N) * nchunk)[cc]), acc);
         }
         if (act) lds4[(size_t)wave * nchunk + col] = acc;
     }
@@ -195,6 +205,12 @@ __global__ __launch_bounds__(256) void spmm_longrow_kernel(SpmmArgs a, const Lon
         }
         p4[col] = r;
     }
+}
+__global__ __launch_bounds__(256) void spmm_longrow_kernel(SpmmArgs a, const LongChunk *chunks, float *partial) {
+    spmm_longrow_body<false>(a, chunks, partial);
+}
+__global__ __launch_bounds__(256) void spmm_longrow_bf16_kernel(SpmmArgs a, const LongChunk *chunks, float *partial) {
+    spmm_longrow_body<true>(a, chunks, partial);
 }
 
 // out[row,:] += sum of the row's chunk partials, in chunk order (one workgroup per long row)
@@ -231,10 +247,10 @@ void plan_long_rows(const uint64_t *ptr, uint32_t N, LongRowsHost *out) {
     }
 }
 
-hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float *partial, hipStream_t s) {
+hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float *partial, hipStream_t s, bool bf16) {
     if (L.nchunks == 0 || a.ld == 0) return hipSuccess;
     const uint32_t nchunk = a.ld >> 2;
-    hipLaunchKernelGGL(spmm_longrow_kernel, dim3(L.nchunks), dim3(256), (size_t)4 * nchunk * sizeof(float4), s, a,
+    hipLaunchKernelGGL(bf16 ? spmm_longrow_bf16_kernel : spmm_longrow_kernel, dim3(L.nchunks), dim3(256), (size_t)4 * nchunk * sizeof(float4), s, a,
                        reinterpret_cast<const LongChunk *>(L.chunks), partial);
     hipLaunchKernelGGL(spmm_longrow_reduce_kernel, dim3(L.nrows), dim3(256), 0, s, a, L.rows, L.row_chunk_ptr, partial);
     return hipGetLastError();
@@ -242,20 +258,20 @@ hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float 
 
 // variant 0 = auto.  slab = floats per feature slab (0 = whole row in one pass
 // where it fits 4 chunks per lane).
-hipError_t launch_spmm(const SpmmArgs &a, int variant, int slab, hipStream_t s) {
+hipError_t launch_spmm(const SpmmArgs &a, int variant, int slab, hipStream_t s, bool bf16) {
     (void)variant;
     if (a.ld & 3) return hipErrorInvalidValue;
     uint32_t width = a.ld;                  // floats handled by one block pass
     if (slab > 0 && (uint32_t)slab < width) width = (uint32_t)slab;
     const uint32_t ch = (width + 3) / 4;    // float4 chunks per row pass
-    if (ch <= 8) return launch_t<8, 1>(a, s);
-    if (ch <= 16) return launch_t<16, 1>(a, s);
-    if (ch <= 32) return launch_t<32, 1>(a, s);
-    if (ch <= 64) return launch_t<64, 1>(a, s);
-    if (ch <= 96) return launch_t<32, 3>(a, s);   // e.g. 300 -> 320 floats (Amazon): 80 of 96 lanes-chunks busy instead of 80 of 128
-    if (ch <= 128) return launch_t<64, 2>(a, s);
-    if (ch <= 192) return launch_t<64, 3>(a, s);
-    return launch_t<64, 4>(a, s);           // wider rows: gridDim.y slabs of 1024 floats
+    if (ch <= 8) return launch_t<8, 1>(a, s, bf16);
+    if (ch <= 16) return launch_t<16, 1>(a, s, bf16);
+    if (ch <= 32) return launch_t<32, 1>(a, s, bf16);
+    if (ch <= 64) return launch_t<64, 1>(a, s, bf16);
+    if (ch <= 96) return launch_t<32, 3>(a, s, bf16);   // e.g. 300 -> 320 floats (Amazon): 80 of 96 lanes-chunks busy instead of 80 of 128
+    if (ch <= 128) return launch_t<64, 2>(a, s, bf16);
+    if (ch <= 192) return launch_t<64, 3>(a, s, bf16);
+    return launch_t<64, 4>(a, s, bf16);           // wider rows: gridDim.y slabs of 1024 floats
 }
 
 void free_blocked(BlockedAdj *B) {
@@ -304,9 +320,10 @@ void free_blocked(BlockedAdj *B) {
 // 2.9 ms (3.9).  Hub (block,row) segments (B.nchunks != 0) keep K1b.
 // =======================================================================================
 // The skeleton (gates, loader wave, staging, batches of gathers) is sweep_core.hpp; the plain SpMM is this OP on it.
-template <bool UNIT>
+template <bool UNIT, bool BF16 = false>
 struct SweepPlainOp {
     static constexpr bool PLAIN = true, UNIT_W = UNIT, PROLOGUE = false, AUX_BATCH = false;
+    static constexpr bool BF16_ROWS = BF16;     // source rows (and the self row) are bf16: spmm_sweep_bf16_kernel
 #ifndef K1S_BATCH
 #define K1S_BATCH SWEEP_U   // 3 / 4 / 5 / 6 gathers per batch = 18.60 / 18.10 / 18.64 / 19.58 ms per epoch (round 5, re-measured on the final kernel)
 #endif
@@ -338,7 +355,8 @@ struct SweepPlainOp {
         float4 xs = make_float4(0.f, 0.f, 0.f, 0.f);
         if (a.self_mode != 0 && !piece) {
             sc = a.self_mode == 1 ? a.self_scale[v] : 1.f;
-            xs = xl4[(size_t)v * nchunk];
+            if constexpr (BF16) xs = row_chunk(reinterpret_cast<const uint2 *>(a.xl)[(size_t)v * nchunk + col]);
+            else xs = xl4[(size_t)v * nchunk];
         }
         float4 o4 = make_float4(r.acc.x * rs, r.acc.y * rs, r.acc.z * rs, r.acc.w * rs);
         o4 = fma4(sc, xs, o4);
@@ -356,19 +374,27 @@ __global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_kernel(SpmmArgs a, Blocke
     SweepPlainOp<UNIT> op{row_scale};
     sweep_run<GROUP, R, PAIR, LOADER>(a, B, w, op);
 }
+// the same sweep over bf16 source rows (option gcn_bf16_gather): 8-byte gathers, fp32 sums in the same order
+template <int GROUP, int R, bool UNIT, bool PAIR, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16_kernel(SpmmArgs a, BlockedAdj B, const float *row_scale,
+                                                                   SweepArgs w) {
+    SweepPlainOp<UNIT, true> op{row_scale};
+    sweep_run<GROUP, R, PAIR, LOADER>(a, B, w, op);
+}
 
 // out[row] (+)= self + (row_scale *) sum of the row's pieces, in piece order.  TPR threads per split row (a float4
 // column each), several rows per workgroup on narrow tensors; eight pieces are requested at a time so that the loads of
 // a hub row's hundreds of pieces overlap -- the adds stay in piece order.
-__global__ __launch_bounds__(320) void spmm_sweep_combine_kernel(SpmmArgs a, BlockedAdj B, const float *row_scale,
-                                                                 const float *split_partial, uint32_t tpr) {
+template <bool BF16>
+__device__ __forceinline__ void spmm_sweep_combine_body(const SpmmArgs &a, const BlockedAdj &B, const float *row_scale,
+                                                        const float *split_partial, uint32_t tpr) {
     const uint32_t nchunk = a.ld >> 2;
     const uint32_t rpb = blockDim.x / tpr;
     const uint32_t sr = blockIdx.x * rpb + threadIdx.x / tpr;
     if (sr >= B.nsplit) return;
     const uint32_t v = B.split_rows[3 * sr], s0 = B.split_rows[3 * sr + 1], K = B.split_rows[3 * sr + 2];
     const float4 *p4 = reinterpret_cast<const float4 *>(split_partial) + (size_t)s0 * nchunk;
-    const float4 *xl4 = reinterpret_cast<const float4 *>(a.xl);
+    const RowChunk<BF16> *xl4 = reinterpret_cast<const RowChunk<BF16> *>(a.xl);
     float4 *out4 = reinterpret_cast<float4 *>(a.out) + (size_t)v * nchunk;
     for (uint32_t col = threadIdx.x % tpr; col < nchunk; col += tpr) {
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -390,7 +416,7 @@ __global__ __launch_bounds__(320) void spmm_sweep_combine_kernel(SpmmArgs a, Blo
         }
         if (a.self_mode != 0) {
             const float sc = a.self_mode == 1 ? a.self_scale[v] : 1.f;
-            acc = fma4(sc, xl4[(size_t)v * nchunk + col], acc);
+            acc = fma4(sc, row_chunk(xl4[(size_t)v * nchunk + col]), acc);
         }
         if (a.accumulate) {
             const float4 p = out4[col];
@@ -399,15 +425,23 @@ __global__ __launch_bounds__(320) void spmm_sweep_combine_kernel(SpmmArgs a, Blo
         out4[col] = acc;
     }
 }
+__global__ __launch_bounds__(320) void spmm_sweep_combine_kernel(SpmmArgs a, BlockedAdj B, const float *row_scale,
+                                                                 const float *split_partial, uint32_t tpr) {
+    spmm_sweep_combine_body<false>(a, B, row_scale, split_partial, tpr);
+}
+__global__ __launch_bounds__(320) void spmm_sweep_combine_bf16_kernel(SpmmArgs a, BlockedAdj B, const float *row_scale,
+                                                                      const float *split_partial, uint32_t tpr) {
+    spmm_sweep_combine_body<true>(a, B, row_scale, split_partial, tpr);
+}
 
 hipError_t launch_spmm_sweep_combine(const SpmmArgs &a, const BlockedAdj &B, const float *row_scale, const float *split_partial,
-                                     hipStream_t s) {
+                                     hipStream_t s, bool bf16) {
     if (!B.nsplit || a.ld == 0) return hipSuccess;
     const uint32_t nchunk = a.ld >> 2;
     const uint32_t tpr = std::min<uint32_t>(256u, (nchunk + 31u) & ~31u);      // threads per row: whole half-waves
     const uint32_t rpb = std::max<uint32_t>(1u, 320u / tpr);
-    hipLaunchKernelGGL(spmm_sweep_combine_kernel, dim3((B.nsplit + rpb - 1) / rpb), dim3(tpr * rpb), 0, s, a, B, row_scale,
-                       split_partial, tpr);
+    hipLaunchKernelGGL(bf16 ? spmm_sweep_combine_bf16_kernel : spmm_sweep_combine_kernel, dim3((B.nsplit + rpb - 1) / rpb),
+                       dim3(tpr * rpb), 0, s, a, B, row_scale, split_partial, tpr);
     return hipGetLastError();
 }
 
@@ -631,8 +665,9 @@ size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t
 // out (+)= self + (row_scale *) sum over source blocks [b_lo, b_hi); `done` = sweep_scratch_bytes() of device memory
 hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, const float *row_scale, uint32_t cus,
                              uint32_t b_lo, uint32_t b_hi, uint32_t *done, hipStream_t s, const SweepCtl &ctl, uint32_t flags,
-                             float *split_partial, uint32_t reserve) {
+                             float *split_partial, uint32_t reserve, bool bf16) {
     if (a.N == 0 || a.ld == 0 || b_lo >= b_hi) return hipSuccess;
+    if (bf16 && row_scale) return hipErrorInvalidValue;   // bf16 rows: the GCN aggregations (edge weights) only
     if (!sweep_supported(a, B, group) || b_hi > B.nb || cus == 0 || cus > 32 || !ctl.stat) return hipErrorInvalidValue;
     if (b_lo < B.nb_local && b_hi > B.nb_local) return hipErrorInvalidValue;   // one source array per launch
     if (b_lo >= B.nb_local && !a.xg) return hipErrorInvalidValue;
@@ -665,7 +700,9 @@ hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, 
     const bool pair = (R & 1) ? false : (ctl.pair < 0 ? slabs >= 3 : ctl.pair != 0);   // (odd R: 16-lane launches on a 6- or 10-row layout)
 #define SWEEP_LAUNCH_L(GRP, RR, LD)                                                                                    \
     do {                                                                                                               \
-        if (unit) { if (pair) hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, true, true, LD>), gr, bl, 0, s, a, B, row_scale, w);   \
+        if (bf16) { if (pair) hipLaunchKernelGGL((spmm_sweep_bf16_kernel<GRP, RR, false, true, LD>), gr, bl, 0, s, a, B, row_scale, w); \
+                    else hipLaunchKernelGGL((spmm_sweep_bf16_kernel<GRP, RR, false, false, LD>), gr, bl, 0, s, a, B, row_scale, w); } \
+        else if (unit) { if (pair) hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, true, true, LD>), gr, bl, 0, s, a, B, row_scale, w);   \
                     else hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, true, false, LD>), gr, bl, 0, s, a, B, row_scale, w); }   \
         else { if (pair) hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, false, true, LD>), gr, bl, 0, s, a, B, row_scale, w);       \
                else hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, false, false, LD>), gr, bl, 0, s, a, B, row_scale, w); }       \

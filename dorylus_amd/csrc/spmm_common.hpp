@@ -3,6 +3,8 @@
 // build_blocked) and by K1s's (spmm.hip: build_blocked_sweep).  Header-only (static kernels: one copy per translation unit).
 #ifndef DORY_SPMM_COMMON_HPP
 #define DORY_SPMM_COMMON_HPP
+#include <type_traits>
+
 #include "ctx.hpp"
 
 namespace dory {
@@ -33,6 +35,17 @@ __device__ __forceinline__ float4 fma4(float w, float4 x, float4 a) {
 }
 
 typedef float v4f __attribute__((ext_vector_type(4)));  // native vector for nontemporal ld/st
+
+// four bf16 (option gcn_bf16_gather: source rows rounded to bf16 by launch_bf16_rows) -> float4, exactly: a bf16 is the
+// high half of the fp32 with the same value.  lo holds elements 0 (low 16 bits) and 1, hi elements 2 and 3.
+__device__ __forceinline__ float4 bf16x4_to_float4(uint32_t lo, uint32_t hi) {
+    return make_float4(__uint_as_float(lo << 16), __uint_as_float(lo & 0xFFFF0000u), __uint_as_float(hi << 16),
+                       __uint_as_float(hi & 0xFFFF0000u));
+}
+__device__ __forceinline__ float4 row_chunk(const float4 &x) { return x; }
+__device__ __forceinline__ float4 row_chunk(const uint2 &x) { return bf16x4_to_float4(x.x, x.y); }
+// one row chunk of four features as the kernels load it: a float4, or four bf16 in a uint2
+template <bool BF16> using RowChunk = typename std::conditional<BF16, uint2, float4>::type;
 
 // `perm` (optional): position -> row (0xFFFFFFFF = empty position); `sblk` (optional): source row -> block.  Without
 // them position = row and block = source / SB (K1b's layout); with them the K1s layout of build_blocked_sweep.

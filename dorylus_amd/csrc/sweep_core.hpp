@@ -114,12 +114,19 @@ __device__ __forceinline__ void sweep_arrive(uint32_t sb, uint32_t t, uint32_t *
 // wave: taken by one wave (whose lane groups the layout deals fewer rows: option spmm_sweep_loader_relief,
 // host/sweep_deal.cpp) it is off the path of the other fifteen, which issue nothing but gathers.
 
+// OP trait BF16_ROWS (default false: the GAT OPs): the source rows are bf16 (option gcn_bf16_gather) -- the gathers read
+// 8 bytes per lane (four features) through the same buffer resource and expand them to a float4 by shifts and masks;
+// lane mapping, slabs, layout, gates and loader wave are those of the fp32 rows
+template <class OP, class = void> struct sweep_bf16_rows : std::false_type {};
+template <class OP> struct sweep_bf16_rows<OP, std::void_t<decltype(OP::BF16_ROWS)>> : std::integral_constant<bool, OP::BF16_ROWS> {};
+
 #ifndef SWEEP_DMA_AUX
 #define SWEEP_DMA_AUX 2   // cache policy of the loader's copies: nt (the entry stream is read once: it must not push the window out of L2)
 #endif
 template <int GROUP, int R, bool PAIR, bool LOADER, class OP>
 __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B, const SweepArgs &w, OP &op) {
     constexpr bool UNIT = OP::UNIT_W;
+    constexpr bool BF16 = sweep_bf16_rows<OP>::value;
     static_assert(!PAIR || OP::PLAIN, "rows in pairs: the plain SpMM only");
     constexpr int GPW = 64 / GROUP;
     constexpr int NGRP = SWEEP_NT / GROUP;
@@ -190,17 +197,23 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
     // an absent slot of a tail is an out-of-range offset -- reads zeros, no memory access, no branch.  A launch covers
     // local-source blocks or ghost blocks, never both: one base.
     const bool ghost_launch = w.b_lo >= B.nb_local;
-    const uint32_t row_b = a.ld * 4u;
+    const uint32_t row_b = a.ld * (BF16 ? 2u : 4u);
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(ghost_launch ? a.xg : a.xl), 0, (ghost_launch ? B.nghost : a.N) * row_b, 0x00020000);
     // a lane without a column (the last slab of a row narrower than the slabs) multiplies by 0 and adds -1: always out of range,
     // at no instruction
-    const uint32_t lane_b = col_ok ? ccol * 16u - (ghost_launch ? a.N : 0u) * row_b : 0xFFFFFFFFu;   // (mod 2^32) + idx * row_b = byte offset
+    const uint32_t lane_b = col_ok ? ccol * (BF16 ? 8u : 16u) - (ghost_launch ? a.N : 0u) * row_b : 0xFFFFFFFFu;   // (mod 2^32) + idx * row_b = byte offset
     const uint32_t lane_m = col_ok ? row_b : 0u;
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
     auto gather = [&](uint32_t sidx, bool on) -> float4 {
-        const u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, on ? __umul24(sidx, lane_m) + lane_b : 0xFFFFFFFFu, 0, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        if constexpr (BF16) {
+            const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, on ? __umul24(sidx, lane_m) + lane_b : 0xFFFFFFFFu, 0, 0);
+            return bf16x4_to_float4(v.x, v.y);
+        } else {
+            const u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, on ? __umul24(sidx, lane_m) + lane_b : 0xFFFFFFFFu, 0, 0);
+            return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        }
     };
     // a pass of a step's entries: [cs, min(cs + CE, o_R)) of this group.  (idx, val) pairs are interleaved in the blocked
     // copy and travel two per lane and load (the addresser spends as long on a 4-byte load as on a 16-byte one); the

@@ -293,6 +293,20 @@ int dory_transform_first_layer(dory_ctx *ctx, uint32_t layer);
  * same kernel produced the kept tensor.  Not combined with a recorded epoch (the recording always contains the
  * aggregation).  dory_get_option "gcn_cache_ah0_skips" counts the aggregations answered from the kept tensor. */
 
+/* bf16 row gathers (option "gcn_bf16_gather", default 0; GCN contexts only, no reference counterpart).  1: every forward
+ * GCN aggregation reads its source rows as bf16 -- "x"/"fg"@0, "h"@(l-1)/"fg"@l, and in the transform-first order
+ * "xw"/"fgxw"; 2: as 1, and the backward aggregations too ("grad"/"bg" -> "aTg", transform-first "g"/"bgg" -> "u").
+ * Every row an aggregation reads -- the self row norm[v]*x[v], local rows and ghost rows -- is rounded to bf16, round to
+ * nearest even (fp32 subnormals stay bf16 subnormals); the edge values, norm, the sums (in the order of the fp32 path) and
+ * the output stay fp32: the result is bit for bit the fp32 path's on the rounded rows.  The stored tensors stay fp32; the
+ * bf16 rows are a per-call copy inside the library (ghost rows are converted only once their exchange has landed), never
+ * kept across calls.  That copy grows lazily on first eager use and cannot grow while an epoch is recorded (DORY_ERR_ARG).
+ * Kernels: K1s and K1 have bf16 forms; K1b has none -- where the fp32 dispatch would take K1b, the bf16 path runs K1, and
+ * dory_aggregate fails with DORY_ERR_ARG for spmm_variant = 1 together with a nonzero value.  A GAT / multi-head GAT context
+ * rejects values other than 0, as do values outside {0, 1, 2}.  Read-only "gcn_bf16_gathers_k1s" / "gcn_bf16_gathers_k1"
+ * count the aggregations that ran on bf16 rows per kernel family (eager calls and recordings, not replays); timing family
+ * "bf16_convert" times the conversions. */
+
 /* Epoch graph (MI355X-side addition, no reference counterpart): record the calls of one
  * epoch -- dory_aggregate / dory_apply_vertex / dory_apply_edge / dory_predict_gat /
  * dory_weight_update, exactly as Engine::runEpoch issues them -- into a hipGraph and replay
