@@ -274,6 +274,7 @@ int dory_create(int device, dory_ctx **out) {
     c->opt["gatmh_fused_stats"] = 1;         // multi-head GAT, blocked forward: online softmax per source block + merge in the reduce (0: separate statistics pass first)
     c->opt["gcn_cache_ah0"] = 0;         // GCN: keep ah@0 = A_hat x across epochs while x, fg@0 and the adjacency are unchanged (opt-in; the reference recomputes it)
     c->opt["gcn_bf16_gather"] = 0;       // GCN: aggregations read their source rows rounded to bf16, fp32 sums: 1 = forward, 2 = forward and backward (opt-in; see dorylus_hip.h)
+    c->opt["gatmh_bf16_gather"] = 0;     // multi-head GAT: the sweep forms' edge passes gather their rows rounded to bf16, fp32 sums: 1 = forward (z), 2 = and the backward's source side (do) (opt-in; see dorylus_hip.h)
     c->opt["gcn_transform_first"] = 0;   // GCN layers as A(XW) instead of (AX)W where the input is wider than the output: 1 = layer 0, 2 = all (see tf_layer)
     c->opt["epoch_graph"] = 0;       // engine: replay a recorded epoch (hipGraph) when the partition is alone
     c->opt["spmm_blk_nb"] = 0;       // K1b: number of source blocks (0 = auto, ~3.75 MB windows)
@@ -398,6 +399,8 @@ int dory_configure(dory_ctx *c, int gnn_type, uint32_t num_layers, const uint32_
         if (dims[i] == 0) return fail(c, DORY_ERR_ARG, "dory_configure: zero layer width");
     if (gnn_type != DORY_GCN && c->opt["gcn_bf16_gather"])
         return fail(c, DORY_ERR_ARG, "dory_configure: gcn_bf16_gather is a GCN option (set it to 0 first)");
+    if (gnn_type != DORY_GATMH && c->opt["gatmh_bf16_gather"])
+        return fail(c, DORY_ERR_ARG, "dory_configure: gatmh_bf16_gather is an option of the multi-head GAT (set it to 0 first)");
     c->gnn = gnn_type;
     c->L = num_layers;
     c->dims.assign(dims, dims + num_layers + 1);
@@ -958,6 +961,8 @@ int dory_get_option(dory_ctx *c, const char *key, int64_t *value) {
     }
     if (key && value && !strcmp(key, "gcn_bf16_gathers_k1s")) { *value = (int64_t)c->bf16_gathers_k1s; return DORY_OK; }   // read-only: aggregations
     if (key && value && !strcmp(key, "gcn_bf16_gathers_k1")) { *value = (int64_t)c->bf16_gathers_k1; return DORY_OK; }     // on bf16 rows, per kernel family
+    if (key && value && !strcmp(key, "gatmh_bf16_gathers_fwd")) { *value = (int64_t)c->gatmh_bf16_gathers_fwd; return DORY_OK; }   // read-only: multi-head GAT
+    if (key && value && !strcmp(key, "gatmh_bf16_gathers_src")) { *value = (int64_t)c->gatmh_bf16_gathers_src; return DORY_OK; }   // edge passes on bf16 rows
     if (key && value && !strcmp(key, "epoch_graph_recorded")) {   // read-only: does the ctx still hold a recorded epoch?
         *value = c->epoch_exec ? 1 : 0;
         return DORY_OK;
@@ -1024,6 +1029,10 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     if (key && !strcmp(key, "gcn_bf16_gather")) {
         if (value < 0 || value > 2) return fail(c, DORY_ERR_ARG, "gcn_bf16_gather: 0 (off), 1 (forward) or 2 (forward and backward)");
         if (value && c->gnn != DORY_GCN) return fail(c, DORY_ERR_ARG, "gcn_bf16_gather: GCN contexts only");
+    }
+    if (key && !strcmp(key, "gatmh_bf16_gather")) {
+        if (value < 0 || value > 2) return fail(c, DORY_ERR_ARG, "gatmh_bf16_gather: 0 (off), 1 (forward) or 2 (forward and the backward's source side)");
+        if (value && c->configured && c->gnn != DORY_GATMH) return fail(c, DORY_ERR_ARG, "gatmh_bf16_gather: multi-head GAT contexts (DORY_GATMH) only");
     }
     if (!key || c->opt.find(key) == c->opt.end()) return fail(c, DORY_ERR_ARG, "unknown option '%s'", key ? key : "(null)");
     c->opt[key] = value;

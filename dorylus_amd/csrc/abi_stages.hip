@@ -109,13 +109,13 @@ int blk_group_for(dory_ctx *c, uint32_t ld) {
     return group;
 }
 
-// Option gcn_bf16_gather: the rows of one aggregation rounded to bf16 into the context's shadow buffer, [N local rows ;
-// ghost rows], every call (nothing is kept: a caller may write x / h / fg through a raw pointer between two calls).  The
-// buffer only grows, outside a recording.
-static int bf16_shadow(dory_ctx *c, uint64_t rows, uint32_t ld) {
+// Options gcn_bf16_gather / gatmh_bf16_gather: the rows of one aggregation rounded to bf16 into the context's shadow buffer,
+// [N local rows ; ghost rows], every call (nothing is kept: a caller may write x / h / fg through a raw pointer between two
+// calls).  The buffer only grows, outside a recording.
+static int bf16_shadow(dory_ctx *c, uint64_t rows, uint32_t ld, const char *option = "gcn_bf16_gather") {
     const size_t need = (size_t)rows * ld * sizeof(uint16_t);
     if (need <= c->bf16_rows_bytes) return DORY_OK;
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the bf16 rows of gcn_bf16_gather would have to grow while recording");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the bf16 rows of %s would have to grow while recording", option);
     if (c->bf16_rows) {
         HIPCK(c, hipStreamSynchronize(c->compute));
         (void)hipFree(c->bf16_rows);
@@ -448,6 +448,10 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
         const bool last = fl == c->L - 1;
         NEED(z, fl, "z"); NEED(el, fl, "el"); NEED(er, fl, "er"); NEED(m, fl, "m"); NEED(den, fl, "den"); NEED(o, fl, "o");
         const uint32_t D = z->cols / K;
+        // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
+        // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
+        // Only the sweep forms have bf16 kernels: where the dispatch below would leave them the call is refused, never run in fp32
+        const int64_t bfm = c->opt["gatmh_bf16_gather"];
         if (dir == DORY_FORWARD) {
             {
                 Timed t(c, "spmm", c->compute);
@@ -465,11 +469,20 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
                 sa.N = c->N; sa.ld = z->ld;
                 const bool sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && c->swpIn_built && !c->swpIn_na && Sf.nb > 0 &&
                                    shl != 0 && op && dpos && sweep_supported(sa, Sf, z->ld >= 128 ? 32 : 16);
+                const bool bf16 = bfm >= 1;
+                if (bf16 && !sweep)
+                    return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
+                                (long long)bfm,
+                                !c->opt["gatmh_sweep"] ? "gatmh_sweep = 0" :
+                                c->opt["spmm_variant"] != 2 ? "spmm_variant is not 2" :
+                                !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
+                                (!op || !dpos) ? "tensors op / dpos missing" : "the sweep layout of the in-edges does not apply to this graph");
                 if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 0;
                 if (sweep) {
                     // K1s's skeleton: sums in registers over all source blocks, single-pass softmax against the upper-bound shift
                     int src_ = ensure_scratch(c, gatmh_sweep_scratch_bytes(Sf, c->N, z->ld, el->ld));
                     if (src_) return src_;
+                    if (bf16 && (src_ = bf16_shadow(c, (uint64_t)c->N + c->Gsrc, z->ld, "gatmh_bf16_gather"))) return src_;
                     const uint32_t G = std::min<uint32_t>(32u, c->cus_per_xcd);
                     const bool two = c->Gsrc > 0 && Sf.nb_local > 0 && Sf.nb_local < Sf.nb;
                     const int sgroup = z->ld >= 128 ? 32 : 16;
@@ -481,20 +494,36 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
                     const uint32_t sflags = (uint32_t)c->opt["spmm_sweep_flags"] |
                                             (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
                     const float *a_l = c->weights[fl]["a_l"].d;
+                    // the rows the sweep gathers: z / fg_z, or (bf16) their rounded copies in the shadow buffer -- the local rows
+                    // converted now, the ghost rows once their exchange has landed (halo() below)
+                    const float *zs = z->d, *zgs = fgz->d;
+                    if (bf16) {
+                        Tensor local = *z;
+                        local.rows = c->N;
+                        if ((src_ = bf16_convert(c, local, 0))) return src_;
+                        zs = reinterpret_cast<const float *>(c->bf16_rows);
+                        zgs = reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * z->ld);
+                        c->gatmh_bf16_gathers_fwd++;
+                    }
+                    auto halo = [&]() -> int {
+                        int rc = wait_halo(c);
+                        if (!rc && bf16 && c->Gsrc) rc = bf16_convert(c, *fgz, c->N);
+                        return rc;
+                    };
                     HIPCK(c, launch_gatmh_sweep_begin(c->N, c->Gsrc, K, z->ld, el->ld, Sf, el->d, fgel->d, c->scratch, c->compute));
                     if (two) {
-                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, z->d, fgz->d, er->d, a_l, o->d, op->d, c->scratch, G, 0,
-                                                                 Sf.nb_local, false, done, ctl, sflags, c->compute, el->d, fgel->d));
-                        if ((src_ = wait_halo(c))) return src_;
-                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, z->d, fgz->d, er->d, a_l, o->d, op->d, c->scratch, G,
-                                                                 Sf.nb_local, Sf.nb, true, done, ctl, sflags, c->compute, el->d, fgel->d));
+                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, G, 0,
+                                                                 Sf.nb_local, false, done, ctl, sflags, c->compute, el->d, fgel->d, bf16));
+                        if ((src_ = halo())) return src_;
+                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, G,
+                                                                 Sf.nb_local, Sf.nb, true, done, ctl, sflags, c->compute, el->d, fgel->d, bf16));
                     } else {
-                        if ((src_ = wait_halo(c))) return src_;
-                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, z->d, c->Gsrc ? fgz->d : nullptr, er->d, a_l, o->d,
-                                                                 op->d, c->scratch, G, 0, Sf.nb, false, done, ctl, sflags, c->compute, el->d, fgel->d));
+                        if ((src_ = halo())) return src_;
+                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, c->Gsrc ? zgs : nullptr, er->d, a_l, o->d,
+                                                                 op->d, c->scratch, G, 0, Sf.nb, false, done, ctl, sflags, c->compute, el->d, fgel->d, bf16));
                     }
                     HIPCK(c, launch_gatmh_forward_sweep_finish(c->N, K, D, z->ld, el->ld, c->colPtr, c->rowIdx, Sf, z->d, fgz->d, el->d, fgel->d,
-                                                               er->d, o->d, op->d, m->d, den->d, dpos->d, c->scratch, c->compute));
+                                                               er->d, o->d, op->d, m->d, den->d, dpos->d, c->scratch, c->compute, bf16));
                     if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
                 }
                 else if (blocked) {
@@ -530,18 +559,6 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
         NEED(dO, fl, "do"); NEED(dz, fl, "dz"); NEED(tt, fl, "t"); NEED(del, fl, "del"); NEED(der, fl, "der");
         NEED(st, fl, "st"); NEED(fgz, fl, "fg_z"); NEED(fgel, fl, "fg_el"); NEED(bgdo, fl, "bg_do"); NEED(bgst, fl, "bg_st");
         const int64_t phase = c->opt["gatmh_bwd_phase"];   // 0: whole sweep; 1 / 2: one phase (caller moves the ghost rows)
-        if (phase != 2) {
-            Timed t(c, "loss", c->compute);
-            if (last) {
-                NEED(gr, fl, "grad");
-                HIPCK(c, launch_gatmh_head_expand(c->N, K, gr->cols, gr->d, gr->ld, dO->d, dO->ld, c->compute));
-            } else {
-                NEED(dh, fl + 1, "dh");
-                HIPCK(c, launch_gatmh_elu_bwd(c->N, o->cols, dh->d, dh->ld, o->d, o->ld, dO->d, dO->ld, c->compute));
-            }
-        }
-        int rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + (size_t)c->N * K * 16 + 256);
-        if (rc) return rc;
         // The sweep forms (gat_mh_sweep.hip).  Destination side: when this layer's forward ran on the skeleton it left the
         // positive-branch sums, and t / der / st come from a row-wise kernel -- no edge pass.  Source side: the sweep over the
         // out-edges' layout.  Either falls back to the blocked kernels on its own (same m / den / st semantics).
@@ -555,6 +572,31 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
         const bool src_sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && shl && c->swpOut_built && !c->swpOut_na && So.nb > 0 &&
                                ((z->ld >> 2) % (uint32_t)shl) == 0 && sweep_supported(sa, So, z->ld >= 128 ? 32 : 16) &&
                                (uint64_t)std::max(c->N, c->Gdst) * K * 16u < (1ull << 32) && K * 16u < (1u << 24);
+        // bf16 rows of do / bg_do for the source-side sweep (gatmh_bf16_gather = 2): refused, before anything is launched, where
+        // the call would not take that sweep; the shadow buffer is sized here too (it cannot grow inside a recording)
+        const bool bf16 = bfm >= 2;
+        if (bf16 && !(dst_rowwise && src_sweep))
+            return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = 2 needs the sweep forms of the backward pass, which this call would not take: %s",
+                        !c->opt["gatmh_sweep"] ? "gatmh_sweep = 0" :
+                        c->opt["spmm_variant"] != 2 ? "spmm_variant is not 2" :
+                        !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
+                        !dst_rowwise ? "this layer's forward pass did not run the sweep form" : "the sweep layout of the out-edges does not apply to this graph");
+        if (bf16 && phase != 1) {
+            int brc = bf16_shadow(c, (uint64_t)c->N + c->Gdst, z->ld, "gatmh_bf16_gather");
+            if (brc) return brc;
+        }
+        if (phase != 2) {
+            Timed t(c, "loss", c->compute);
+            if (last) {
+                NEED(gr, fl, "grad");
+                HIPCK(c, launch_gatmh_head_expand(c->N, K, gr->cols, gr->d, gr->ld, dO->d, dO->ld, c->compute));
+            } else {
+                NEED(dh, fl + 1, "dh");
+                HIPCK(c, launch_gatmh_elu_bwd(c->N, o->cols, dh->d, dh->ld, o->d, o->ld, dO->d, dO->ld, c->compute));
+            }
+        }
+        int rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + (size_t)c->N * K * 16 + 256);
+        if (rc) return rc;
         if (dst_rowwise && src_sweep) {
             float4 *st4 = reinterpret_cast<float4 *>(st->d);
             const uint32_t lds4 = st->ld / 4;
@@ -581,19 +623,31 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
                                     (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
             {
                 Timed t(c, "spmm", c->compute);
+                // the rows the sweep gathers: do / bg_do, or (bf16) their rounded copies -- the ghost rows have landed by now
+                // (phase 0: exchange_rows above made the compute stream wait; phase 2: the caller moved them before this call)
+                const float *dos = dO->d, *dogs = bgdo->d;
+                if (bf16) {
+                    Tensor local = *dO;
+                    local.rows = c->N;
+                    if ((rc = bf16_convert(c, local, 0))) return rc;
+                    if (c->Gdst && (rc = bf16_convert(c, *bgdo, c->N))) return rc;
+                    dos = reinterpret_cast<const float *>(c->bf16_rows);
+                    dogs = reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * z->ld);
+                    c->gatmh_bf16_gathers_src++;
+                }
                 HIPCK(c, launch_gatmh_src_sweep_begin(c->N, c->Gdst, K, z->ld, el->ld, So, st4, reinterpret_cast<const float4 *>(bgst->d), lds4,
                                                       c->scratch, c->compute));
                 if (two) {
-                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dO->d, bgdo->d, el->d, dz->d, c->scratch, G, 0,
-                                                         So.nb_local, false, done, ctl, sflags, c->compute));
-                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dO->d, bgdo->d, el->d, dz->d, c->scratch, G,
-                                                         So.nb_local, So.nb, true, done, ctl, sflags, c->compute));
+                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dos, dogs, el->d, dz->d, c->scratch, G, 0,
+                                                         So.nb_local, false, done, ctl, sflags, c->compute, bf16));
+                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dos, dogs, el->d, dz->d, c->scratch, G,
+                                                         So.nb_local, So.nb, true, done, ctl, sflags, c->compute, bf16));
                 } else {
-                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dO->d, c->Gdst ? bgdo->d : nullptr, el->d, dz->d,
-                                                         c->scratch, G, 0, So.nb, false, done, ctl, sflags, c->compute));
+                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dos, c->Gdst ? dogs : nullptr, el->d, dz->d,
+                                                         c->scratch, G, 0, So.nb, false, done, ctl, sflags, c->compute, bf16));
                 }
                 HIPCK(c, launch_gatmh_src_sweep_finish(c->N, K, D, z->ld, el->ld, So, z->d, el->d, dO->d, der->d, c->weights[fl]["a_l"].d,
-                                                       c->weights[fl]["a_r"].d, del->d, dz->d, c->scratch, c->compute));
+                                                       c->weights[fl]["a_r"].d, del->d, dz->d, c->scratch, c->compute, bf16));
             }
             // (the attention gradients' column sums take the scratch buffer next: the sweep's sums are consumed by then)
             if ((rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + 256))) return rc;

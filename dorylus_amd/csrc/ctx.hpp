@@ -183,11 +183,12 @@ struct dory_ctx {
     bool prealloc = false;
     bool ah0_valid = false;      // option gcn_cache_ah0: ah@0 holds the aggregate of the current x / fg@0 / adjacency
     uint64_t ah0_skips = 0;      // layer-0 aggregations answered from it
-    // option gcn_bf16_gather: the bf16 copy of the rows an aggregation reads ((N + ghosts) x ld, rewritten by every
-    // aggregation that uses it, never kept across calls), and the aggregations that ran on it per kernel family
+    // options gcn_bf16_gather / gatmh_bf16_gather: the bf16 copy of the rows an aggregation reads ((N + ghosts) x ld, rewritten
+    // by every pass that uses it, never kept across calls), and the passes that ran on it per kernel family
     uint16_t *bf16_rows = nullptr;
     size_t bf16_rows_bytes = 0;
     uint64_t bf16_gathers_k1s = 0, bf16_gathers_k1 = 0;
+    uint64_t gatmh_bf16_gathers_fwd = 0, gatmh_bf16_gathers_src = 0;   // multi-head GAT: forward edge passes, source-side passes
     std::vector<std::map<std::string, dory::Tensor>> tensors;   // [layer][name]
     std::vector<std::map<std::string, dory::Tensor>> weights;   // "w", "a_i"
     std::vector<std::map<std::string, dory::Tensor>> wgrads;    // same names
@@ -320,8 +321,8 @@ hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, 
                              bool bf16 = false /* bf16 source rows (launch_spmm), no row_scale */);
 hipError_t launch_spmm_sweep_combine(const SpmmArgs &a, const BlockedAdj &B, const float *row_scale, const float *split_partial,
                                      hipStream_t s, bool bf16 = false);
-// fp32 -> bf16 (round to nearest even) of n elements, n a multiple of 4: the rows an aggregation reads under option
-// gcn_bf16_gather (elementwise.hip)
+// fp32 -> bf16 (round to nearest even) of n elements, n a multiple of 4: the rows an aggregation reads under options
+// gcn_bf16_gather / gatmh_bf16_gather (elementwise.hip)
 hipError_t launch_bf16_rows(const float *x, uint16_t *y, uint64_t n, hipStream_t s);
 hipError_t launch_occupy_cus(uint32_t workgroups, uint64_t usec, hipStream_t s);   // diagnostic (dory_debug_occupy_cus)
 hipError_t launch_xcd_probe(uint32_t *xcc /*grid words*/, uint32_t grid, hipStream_t s);   // HW_REG_XCC_ID of every probe workgroup
@@ -445,11 +446,13 @@ hipError_t launch_gatmh_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t
 hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
                                            float *scratch, uint32_t cus, uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done,
-                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg /* the sources' scores (local, ghost rows) */);
+                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg /* the sources' scores (local, ghost rows) */,
+                                           bool bf16 = false /* z / zg point at bf16 rows of ld elements (launch_bf16_rows; option gatmh_bf16_gather) */);
 hipError_t launch_gatmh_forward_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                              const uint32_t *rowidx, const BlockedAdj &S, const float *z, const float *zg, const float *el,
                                              const float *elg, const float *er, float *o, float *op, float *m, float *den, float *dpos,
-                                             float *scratch, hipStream_t s);
+                                             float *scratch, hipStream_t s,
+                                             bool bf16 = false /* z / zg stay fp32: the self edge's and the recomputed rows' are rounded in registers */);
 hipError_t launch_gatmh_dst_rowwise(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const float *d_o, const float *o,
                                     const float *op, const float *dpos, const float *er, const float *m, const float *den, float *t,
                                     float *der, float4 *st4, uint32_t lds4, hipStream_t s);
@@ -459,10 +462,11 @@ hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                        const float *d_o, const float *dog, const float *el, float *dz, float *scratch, uint32_t cus,
                                        uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags,
-                                       hipStream_t s);
+                                       hipStream_t s, bool bf16 = false /* d_o / dog point at bf16 rows (option gatmh_bf16_gather = 2) */);
 hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *z,
                                          const float *el, const float *d_o, const float *der, const float *a_l, const float *a_r, float *del,
-                                         float *dz, float *scratch, hipStream_t s);
+                                         float *dz, float *scratch, hipStream_t s,
+                                         bool bf16 = false /* d_o stays fp32: the self edge's row is rounded in registers */);
 // row-wise backward (single partition; feature-per-lane or (edge, head, piece)-per-lane kernels by shape)
 hipError_t launch_gatmh_backward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const uint64_t *rowptr, const uint32_t *colidx,

@@ -123,9 +123,13 @@ __global__ __launch_bounds__(256) void gatmh_elmax_kernel(uint32_t N, uint32_t G
 
 // ---- forward: acc[v,:] = sum_e exp(s_e - m_v) z[src(e),:],  den[v,k] = sum_e exp(s_e - m_v), and the positive-branch parts
 // of both (self edge, normalisation: finish kernel) ----------------------------------------------------------------------
-template <int GROUP, int HL, int R>
+// BF16 (option gatmh_bf16_gather >= 1; gatmh_forward_sweep_bf16_kernel): a.xl / a.xg hold the rows of z / fg_z rounded to bf16
+// (launch_bf16_rows) -- the skeleton gathers 8 bytes per lane and hands entry() the expanded float4, so the score formed from
+// the row (<z_u, a_l>, the form without the el table) is the rounded row's; the el table, er, the shift and every sum stay fp32
+template <int GROUP, int HL, int R, bool BF16 = false>
 struct GatFwdSweepOp {
     static constexpr bool PLAIN = false, UNIT_W = true, PROLOGUE = true, AUX_BATCH = (GROUP <= GATMH_FWD_EL_TABLE);
+    static constexpr bool BF16_ROWS = BF16;
     static constexpr int EPL = HL >= 4 ? 4 : 2;
     static constexpr int BATCH = GROUP == 16 ? GATMH_FWD16_BATCH : GATMH_FWD_BATCH;
     static constexpr int SLACK = GATMH_SLACK;
@@ -257,6 +261,15 @@ __global__ __launch_bounds__(SWEEP_NT) void gatmh_forward_sweep_kernel(SpmmArgs 
     GatFwdSweepOp<GROUP, HL, R> op{er, a_l, elmax_key, accp, dacc, pos_slots, den_slots, K, D, ldk, el, elg};
     sweep_run<GROUP, R, false, LOADER>(a, B, w, op);
 }
+// the same sweep over bf16 rows of z (option gatmh_bf16_gather): 8-byte gathers, fp32 sums in the same order
+template <int GROUP, int HL, int R, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void gatmh_forward_sweep_bf16_kernel(SpmmArgs a, BlockedAdj B, SweepArgs w, const float *er,
+                                                                            const float *a_l, const int *elmax_key, float *accp, float *dacc,
+                                                                            float *pos_slots, float *den_slots, uint32_t K, uint32_t D,
+                                                                            uint32_t ldk, const float *el, const float *elg) {
+    GatFwdSweepOp<GROUP, HL, R, true> op{er, a_l, elmax_key, accp, dacc, pos_slots, den_slots, K, D, ldk, el, elg};
+    sweep_run<GROUP, R, false, LOADER>(a, B, w, op);
+}
 
 // pieces of split rows: dst[v,:] = sum of the pieces' slots (piece order), for a row tensor (width ld) and a per-head one
 __global__ __launch_bounds__(256) void gatmh_sweep_combine_kernel(BlockedAdj B, uint32_t ld, uint32_t ldh, const float *part,
@@ -277,11 +290,13 @@ __global__ __launch_bounds__(256) void gatmh_sweep_combine_kernel(BlockedAdj B, 
 }
 
 // o = (acc + e_self z_v) / (dacc + e_self), op / dpos likewise with the self edge on its branch; m, den for the backward
-// passes; rows whose denominator underflowed are listed
-__global__ __launch_bounds__(256) void gatmh_forward_finish_kernel(GatMhArgs a, const float *z, const float *el, const float *er,
-                                                                   const int *elmax_key, const float *dacc, float *o, float *op,
-                                                                   float *m_out, float *den_out, float *dpos_out, uint32_t *redo_flag,
-                                                                   uint32_t *redo_list /*[0] = count*/) {
+// passes; rows whose denominator underflowed are listed.  RND (option gatmh_bf16_gather): the self edge's row z_v is rounded
+// to bf16 in registers, as the sweep read its neighbours' rows
+template <bool RND>
+__device__ __forceinline__ void gatmh_forward_finish_body(GatMhArgs a, const float *z, const float *el, const float *er,
+                                                          const int *elmax_key, const float *dacc, float *o, float *op,
+                                                          float *m_out, float *den_out, float *dpos_out, uint32_t *redo_flag,
+                                                          uint32_t *redo_list /*[0] = count*/) {
     const uint32_t nchunk = a.ld >> 2;
     const size_t n = (size_t)a.N * nchunk;
     const float4 *z4 = reinterpret_cast<const float4 *>(z);
@@ -298,7 +313,7 @@ __global__ __launch_bounds__(256) void gatmh_forward_finish_kernel(GatMhArgs a, 
         const float2 d2 = reinterpret_cast<const float2 *>(dacc + (size_t)v * 2 * a.ldk)[k];
         const float dn = d2.x + es;
         const float idn = 1.f / dn;
-        const float4 acc = o4[i], accp = p4[i], x = z4[i];
+        const float4 acc = o4[i], accp = p4[i], x = RND ? bf16_round(z4[i]) : z4[i];
         o4[i] = make_float4(fmaf(es, x.x, acc.x) * idn, fmaf(es, x.y, acc.y) * idn, fmaf(es, x.z, acc.z) * idn, fmaf(es, x.w, acc.w) * idn);
         p4[i] = make_float4(fmaf(esp, x.x, accp.x) * idn, fmaf(esp, x.y, accp.y) * idn, fmaf(esp, x.z, accp.z) * idn, fmaf(esp, x.w, accp.w) * idn);
         if ((col * 4) % a.D < 4 || a.K == 1) {
@@ -307,13 +322,27 @@ __global__ __launch_bounds__(256) void gatmh_forward_finish_kernel(GatMhArgs a, 
         }
     }
 }
+__global__ __launch_bounds__(256) void gatmh_forward_finish_kernel(GatMhArgs a, const float *z, const float *el, const float *er,
+                                                                   const int *elmax_key, const float *dacc, float *o, float *op,
+                                                                   float *m_out, float *den_out, float *dpos_out, uint32_t *redo_flag,
+                                                                   uint32_t *redo_list) {
+    gatmh_forward_finish_body<false>(a, z, el, er, elmax_key, dacc, o, op, m_out, den_out, dpos_out, redo_flag, redo_list);
+}
+__global__ __launch_bounds__(256) void gatmh_forward_finish_bf16_kernel(GatMhArgs a, const float *z, const float *el, const float *er,
+                                                                        const int *elmax_key, const float *dacc, float *o, float *op,
+                                                                        float *m_out, float *den_out, float *dpos_out, uint32_t *redo_flag,
+                                                                        uint32_t *redo_list) {
+    gatmh_forward_finish_body<true>(a, z, el, er, elmax_key, dacc, o, op, m_out, den_out, dpos_out, redo_flag, redo_list);
+}
 
 // the rows the finish kernel listed, recomputed with their own maximum (online softmax over the row's in-edges and the
-// self edge, one wave per row, lanes over the features); rare by construction, so nothing here is tuned
-__global__ __launch_bounds__(256) void gatmh_forward_redo_kernel(GatMhArgs a, const float *z, const float *zg, const float *el,
-                                                                 const float *elg, const float *er, float *o, float *op, float *m_out,
-                                                                 float *den_out, float *dpos_out, uint32_t *redo_flag,
-                                                                 const uint32_t *redo_list) {
+// self edge, one wave per row, lanes over the features); rare by construction, so nothing here is tuned.  RND: every row of
+// z / fg_z it reads is rounded to bf16 in registers (option gatmh_bf16_gather)
+template <bool RND>
+__device__ __forceinline__ void gatmh_forward_redo_body(GatMhArgs a, const float *z, const float *zg, const float *el,
+                                                        const float *elg, const float *er, float *o, float *op, float *m_out,
+                                                        float *den_out, float *dpos_out, uint32_t *redo_flag,
+                                                        const uint32_t *redo_list) {
     const uint32_t cnt = redo_list[0];
     const int lane = threadIdx.x & 63;
     const uint32_t KD = a.K * a.D;
@@ -328,7 +357,8 @@ __global__ __launch_bounds__(256) void gatmh_forward_redo_kernel(GatMhArgs a, co
                 const uint32_t u = e < e1 ? a.idx[e] : v;
                 const bool loc = u < a.N;
                 const float el_u = loc ? el[(size_t)u * a.ldk + k] : elg[(size_t)(u - a.N) * a.ldk + k];
-                const float zu = loc ? z[(size_t)u * a.ld + f] : zg[(size_t)(u - a.N) * a.ld + f];
+                float zu = loc ? z[(size_t)u * a.ld + f] : zg[(size_t)(u - a.N) * a.ld + f];
+                if constexpr (RND) zu = bf16_round(zu);
                 const float pre = el_u + er_v, s = lrelu02(pre);
                 const float mn = fmaxf(mx, s);
                 const float sc = __expf(mx - mn), al = __expf(s - mn);   // (exp(-inf) = 0 on the first edge)
@@ -347,6 +377,18 @@ __global__ __launch_bounds__(256) void gatmh_forward_redo_kernel(GatMhArgs a, co
         }
         if (lane == 0) redo_flag[v] = 0u;
     }
+}
+__global__ __launch_bounds__(256) void gatmh_forward_redo_kernel(GatMhArgs a, const float *z, const float *zg, const float *el,
+                                                                 const float *elg, const float *er, float *o, float *op, float *m_out,
+                                                                 float *den_out, float *dpos_out, uint32_t *redo_flag,
+                                                                 const uint32_t *redo_list) {
+    gatmh_forward_redo_body<false>(a, z, zg, el, elg, er, o, op, m_out, den_out, dpos_out, redo_flag, redo_list);
+}
+__global__ __launch_bounds__(256) void gatmh_forward_redo_bf16_kernel(GatMhArgs a, const float *z, const float *zg, const float *el,
+                                                                      const float *elg, const float *er, float *o, float *op, float *m_out,
+                                                                      float *den_out, float *dpos_out, uint32_t *redo_flag,
+                                                                      const uint32_t *redo_list) {
+    gatmh_forward_redo_body<true>(a, z, zg, el, elg, er, o, op, m_out, den_out, dpos_out, redo_flag, redo_list);
 }
 
 // ---- backward, destination side: no edges (header).  t = <dO, O>, der = 0.8 (<dO, P> - t dpos), st4 = (er, m, 1/den, t):
@@ -386,8 +428,11 @@ __global__ void gatmh_stx_kernel(uint64_t n /*rows x K*/, uint32_t K, const floa
     stx[i] = make_float4(fmaf(s.x - s.y, GATMH_LOG2E, li), fmaf(GATMH_SLOPE * s.x - s.y, GATMH_LOG2E, li), s.w, 0.f);
 }
 
-template <int GROUP, int HL, int R>
+// BF16 (option gatmh_bf16_gather = 2; gatmh_src_sweep_bf16_kernel): a.xl / a.xg hold the rows of do / bg_do rounded to bf16; the
+// statistics records (second gather), el and every sum stay fp32
+template <int GROUP, int HL, int R, bool BF16 = false>
 struct GatSrcSweepOp {
+    static constexpr bool BF16_ROWS = BF16;
     // (the destinations' statistics fetched once per batch through the LDS crossbar instead of once per entry: measured, no gain --
     // profiles/r05_gatmh_src_aux_batch_experiment.patch)
     static constexpr bool PLAIN = false, UNIT_W = true, PROLOGUE = true, AUX_BATCH = GATMH_SRC_AUX_MODE == 3;
@@ -509,12 +554,23 @@ __global__ __launch_bounds__(SWEEP_NT) void gatmh_src_sweep_kernel(SpmmArgs a, B
     GatSrcSweepOp<GROUP, HL, R> op{el, stx, stxg, sp, tacc, pos_slots, t_slots, K, D, ldk, a.N, G};
     sweep_run<GROUP, R, false, LOADER>(a, B, w, op);
 }
+// the same sweep over bf16 rows of do (option gatmh_bf16_gather = 2)
+template <int GROUP, int HL, int R, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void gatmh_src_sweep_bf16_kernel(SpmmArgs a, BlockedAdj B, SweepArgs w, const float *el,
+                                                                        const float4 *stx, const float4 *stxg, float *sp, float *tacc,
+                                                                        float *pos_slots, float *t_slots, uint32_t K, uint32_t D, uint32_t ldk,
+                                                                        uint32_t G) {
+    GatSrcSweepOp<GROUP, HL, R, true> op{el, stx, stxg, sp, tacc, pos_slots, t_slots, K, D, ldk, a.N, G};
+    sweep_run<GROUP, R, false, LOADER>(a, B, w, op);
+}
 
 // dz[u,:] = S + alpha_self dO[u,:] + del[u,k] a_l + der[u,k] a_r,   del[u,k] = <Z[u,k,:], 0.2 S' + 0.8 S+'> - (0.2 T' + 0.8 T+')
-// (primes: with the self edge); one float4 of a row per thread, the head's HL threads reduced by shuffles
-__global__ __launch_bounds__(256) void gatmh_src_finish_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float4 *stx,
-                                                               const float *d_o, const float *sp, const float *tacc, const float *der,
-                                                               const float *a_l, const float *a_r, float *dz, float *del_out) {
+// (primes: with the self edge); one float4 of a row per thread, the head's HL threads reduced by shuffles.  RND (option
+// gatmh_bf16_gather = 2): the self edge's dO[u] is rounded to bf16 in registers, as the sweep read the out-edges' rows; z[u] stays fp32
+template <bool RND>
+__device__ __forceinline__ void gatmh_src_finish_body(GatMhArgs a, int HL, const float *z, const float *el, const float4 *stx,
+                                                      const float *d_o, const float *sp, const float *tacc, const float *der,
+                                                      const float *a_l, const float *a_r, float *dz, float *del_out) {
     const uint32_t nchunk = a.ld >> 2;
     const size_t n = (size_t)a.N * nchunk;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -528,7 +584,8 @@ __global__ __launch_bounds__(256) void gatmh_src_finish_kernel(GatMhArgs a, int 
     const float e = el[uk] * GATMH_LOG2E;
     const float t1 = e + sv.x, t2 = fmaf(e, GATMH_SLOPE, sv.y);
     const float as = __builtin_amdgcn_exp2f(fmaxf(t1, t2)), asp = t1 > t2 ? as : 0.f;       // the self edge
-    const float4 g = reinterpret_cast<const float4 *>(d_o)[ii], zz = reinterpret_cast<const float4 *>(z)[ii];
+    const float4 g = RND ? bf16_round(reinterpret_cast<const float4 *>(d_o)[ii]) : reinterpret_cast<const float4 *>(d_o)[ii];
+    const float4 zz = reinterpret_cast<const float4 *>(z)[ii];
     float4 s = reinterpret_cast<const float4 *>(dz)[ii], p = reinterpret_cast<const float4 *>(sp)[ii];
     s = make_float4(fmaf(as, g.x, s.x), fmaf(as, g.y, s.y), fmaf(as, g.z, s.z), fmaf(as, g.w, s.w));
     p = make_float4(fmaf(asp, g.x, p.x), fmaf(asp, g.y, p.y), fmaf(asp, g.z, p.z), fmaf(asp, g.w, p.w));
@@ -547,6 +604,16 @@ __global__ __launch_bounds__(256) void gatmh_src_finish_kernel(GatMhArgs a, int 
         out[c] = f < a.K * a.D ? r[c] + del * a_l[f] + dr * a_r[f] : 0.f;
     }
     if ((col % (uint32_t)HL) == 0) del_out[uk] = del;
+}
+__global__ __launch_bounds__(256) void gatmh_src_finish_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float4 *stx,
+                                                               const float *d_o, const float *sp, const float *tacc, const float *der,
+                                                               const float *a_l, const float *a_r, float *dz, float *del_out) {
+    gatmh_src_finish_body<false>(a, HL, z, el, stx, d_o, sp, tacc, der, a_l, a_r, dz, del_out);
+}
+__global__ __launch_bounds__(256) void gatmh_src_finish_bf16_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float4 *stx,
+                                                                    const float *d_o, const float *sp, const float *tacc, const float *der,
+                                                                    const float *a_l, const float *a_r, float *dz, float *del_out) {
+    gatmh_src_finish_body<true>(a, HL, z, el, stx, d_o, sp, tacc, der, a_l, a_r, dz, del_out);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
@@ -652,7 +719,7 @@ static bool gatmh_sweep_geom(const SpmmArgs &a, const BlockedAdj &S, int group, 
 hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
                                            float *scratch, uint32_t cus, uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done,
-                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg) {
+                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg, bool bf16) {
     if (N == 0 || b_lo >= b_hi) return hipSuccess;
     const int group = ld >= 128 ? 32 : 16;
     const int HL = gatmh_sweep_hl(K, D, ld);
@@ -666,7 +733,11 @@ hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, u
     hipError_t e = hipMemsetAsync(done, 0, ((size_t)8 * w.nsweeps * (b_hi - b_lo) * 32 + 1) * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
-#define GFS(GRP, HLV, RR, LD) hipLaunchKernelGGL((gatmh_forward_sweep_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk, el, elg)
+#define GFS(GRP, HLV, RR, LD)                                                                                                                    \
+    do {                                                                                                                                         \
+        if (bf16) hipLaunchKernelGGL((gatmh_forward_sweep_bf16_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk, el, elg); \
+        else hipLaunchKernelGGL((gatmh_forward_sweep_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk, el, elg);          \
+    } while (0)
 #define GFS_R(HLV) do { if (R == 4) GFS(32, HLV, 4, true); else GFS(32, HLV, 2, true); } while (0)
 #define GFS_R16(HLV) do { if (R == 4) GFS(16, HLV, 4, true); else GFS(16, HLV, 2, true); } while (0)
     if (group == 32) {
@@ -686,7 +757,7 @@ hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, u
 hipError_t launch_gatmh_forward_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                              const uint32_t *rowidx, const BlockedAdj &S, const float *z, const float *zg, const float *el,
                                              const float *elg, const float *er, float *o, float *op, float *m, float *den, float *dpos,
-                                             float *scratch, hipStream_t s) {
+                                             float *scratch, hipStream_t s, bool bf16) {
     if (N == 0) return hipSuccess;
     const GatSweepScratch c = gatmh_carve(scratch, S, N, ld, ldk);
     GatMhArgs a{N, K, D, ld, ldk, colptr, rowidx};
@@ -696,8 +767,10 @@ hipError_t launch_gatmh_forward_sweep_finish(uint32_t N, uint32_t K, uint32_t D,
     }
     const size_t n = (size_t)N * (ld >> 2);
     const int blocks = (int)std::min<size_t>((n + 255) / 256, 8192);
-    hipLaunchKernelGGL(gatmh_forward_finish_kernel, dim3(blocks), dim3(256), 0, s, a, z, el, er, c.keys, c.dacc, o, op, m, den, dpos, c.redo_flag, c.redo_list);
-    hipLaunchKernelGGL(gatmh_forward_redo_kernel, dim3(64), dim3(256), 0, s, a, z, zg, el, elg, er, o, op, m, den, dpos, c.redo_flag, c.redo_list);
+    hipLaunchKernelGGL(bf16 ? gatmh_forward_finish_bf16_kernel : gatmh_forward_finish_kernel, dim3(blocks), dim3(256), 0, s, a, z, el, er, c.keys,
+                       c.dacc, o, op, m, den, dpos, c.redo_flag, c.redo_list);
+    hipLaunchKernelGGL(bf16 ? gatmh_forward_redo_bf16_kernel : gatmh_forward_redo_kernel, dim3(64), dim3(256), 0, s, a, z, zg, el, elg, er, o, op, m,
+                       den, dpos, c.redo_flag, c.redo_list);
     return hipGetLastError();
 }
 
@@ -749,7 +822,7 @@ hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                        const float *d_o, const float *dog, const float *el, float *dz, float *scratch, uint32_t cus,
                                        uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags,
-                                       hipStream_t s) {
+                                       hipStream_t s, bool bf16) {
     if (N == 0 || b_lo >= b_hi) return hipSuccess;
     const int group = ld >= 128 ? 32 : 16;
     const int HL = gatmh_sweep_hl(K, D, ld);
@@ -765,7 +838,11 @@ hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint3
     hipError_t e = hipMemsetAsync(done, 0, ((size_t)8 * w.nsweeps * (b_hi - b_lo) * 32 + 1) * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
-#define GSS(GRP, HLV, RR, LD) hipLaunchKernelGGL((gatmh_src_sweep_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G)
+#define GSS(GRP, HLV, RR, LD)                                                                                                                    \
+    do {                                                                                                                                         \
+        if (bf16) hipLaunchKernelGGL((gatmh_src_sweep_bf16_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G); \
+        else hipLaunchKernelGGL((gatmh_src_sweep_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G);          \
+    } while (0)
     if (group == 32) {
         if (R != 2 && R != 4) return hipErrorInvalidValue;
 #define GSS_R(HLV) do { if (R == 4) GSS(32, HLV, 4, true); else GSS(32, HLV, 2, true); } while (0)
@@ -784,7 +861,7 @@ hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint3
 // pieces of split rows, the self edge, del, dz
 hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *z,
                                          const float *el, const float *d_o, const float *der, const float *a_l, const float *a_r, float *del,
-                                         float *dz, float *scratch, hipStream_t s) {
+                                         float *dz, float *scratch, hipStream_t s, bool bf16) {
     if (N == 0) return hipSuccess;
     const int HL = gatmh_sweep_hl(K, D, ld);
     if (!HL || ((ld >> 2) % (uint32_t)HL) != 0) return hipErrorInvalidValue;
@@ -795,8 +872,8 @@ hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uin
         hipLaunchKernelGGL(gatmh_sweep_combine_kernel, dim3(S.nsplit), dim3(256), 0, s, S, ld, 0u, c.pos_slots, c.t_slots, c.sp, c.tacc);
     }
     const size_t n = (size_t)N * (ld >> 2);
-    hipLaunchKernelGGL(gatmh_src_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, a, HL, z, el, c.stx, d_o, c.sp, c.tacc, der,
-                       a_l, a_r, dz, del);
+    hipLaunchKernelGGL(bf16 ? gatmh_src_finish_bf16_kernel : gatmh_src_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, a, HL, z, el,
+                       c.stx, d_o, c.sp, c.tacc, der, a_l, a_r, dz, del);
     return hipGetLastError();
 }
 

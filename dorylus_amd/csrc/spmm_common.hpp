@@ -42,6 +42,14 @@ __device__ __forceinline__ float4 bf16x4_to_float4(uint32_t lo, uint32_t hi) {
     return make_float4(__uint_as_float(lo << 16), __uint_as_float(lo & 0xFFFF0000u), __uint_as_float(hi << 16),
                        __uint_as_float(hi & 0xFFFF0000u));
 }
+// a value as a kernel that gathers bf16 rows sees it: rounded to bf16 (nearest even, the conversion of launch_bf16_rows) and
+// expanded again -- for the rows a kernel reads once per destination (self edge) and rounds in registers
+__device__ __forceinline__ float bf16_round(float x) {
+    return __uint_as_float((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)x) << 16);
+}
+__device__ __forceinline__ float4 bf16_round(const float4 &x) {
+    return make_float4(bf16_round(x.x), bf16_round(x.y), bf16_round(x.z), bf16_round(x.w));
+}
 __device__ __forceinline__ float4 row_chunk(const float4 &x) { return x; }
 __device__ __forceinline__ float4 row_chunk(const uint2 &x) { return bf16x4_to_float4(x.x, x.y); }
 // one row chunk of four features as the kernels load it: a float4, or four bf16 in a uint2

@@ -114,7 +114,7 @@ __device__ __forceinline__ void sweep_arrive(uint32_t sb, uint32_t t, uint32_t *
 // wave: taken by one wave (whose lane groups the layout deals fewer rows: option spmm_sweep_loader_relief,
 // host/sweep_deal.cpp) it is off the path of the other fifteen, which issue nothing but gathers.
 
-// OP trait BF16_ROWS (default false: the GAT OPs): the source rows are bf16 (option gcn_bf16_gather) -- the gathers read
+// OP trait BF16_ROWS (default false): the source rows are bf16 (options gcn_bf16_gather, gatmh_bf16_gather) -- the gathers read
 // 8 bytes per lane (four features) through the same buffer resource and expand them to a float4 by shifts and masks;
 // lane mapping, slabs, layout, gates and loader wave are those of the fp32 rows
 template <class OP, class = void> struct sweep_bf16_rows : std::false_type {};

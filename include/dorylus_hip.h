@@ -307,6 +307,33 @@ int dory_transform_first_layer(dory_ctx *ctx, uint32_t layer);
  * count the aggregations that ran on bf16 rows per kernel family (eager calls and recordings, not replays); timing family
  * "bf16_convert" times the conversions. */
 
+/* bf16 row gathers in the multi-head GAT sweeps (option "gatmh_bf16_gather", default 0; DORY_GATMH contexts only, no reference
+ * counterpart; "gcn_bf16_gather" keeps refusing these contexts).  1: the forward edge pass of every layer reads the rows of
+ * "z" / "fg_z" rounded to bf16.  2: as 1, and the backward's source-side pass reads the rows of "do" / "bg_do" rounded to bf16.
+ * Rounding is round to nearest even (fp32 subnormals stay bf16 subnormals), the conversion "gcn_bf16_gather" uses.  The
+ * stored tensors stay fp32; "el", "er", the shift "m", the statistics records "st", a_l, every sum, "den", "dpos" and all
+ * outputs stay fp32, and the sums run in the fp32 kernels' order:
+ *   forward   dory_aggregate(layer, DORY_FORWARD) produces bit for bit what the call with the option off produces after
+ *             "z" (and "fg_z") have been replaced by their rounded values between dory_apply_edge and dory_aggregate.  That
+ *             covers the gathered rows, the score a 128-float launch forms from the gathered row, the self edge's row and the
+ *             rows re-read for underflowed denominators.  Where the fp32 path takes el[u] from the table "el" / "fg_el", it
+ *             still does: dory_apply_edge wrote the table from the unrounded "z".
+ *   backward  with "gatmh_bwd_phase" = 2 the call produces bit for bit what the call with the option off produces after "do"
+ *             (and "bg_do") have been replaced by their rounded values between phase 1 and phase 2: the rows gathered over
+ *             the out-edges and the self edge's do[u].  The destination side (t, der, "st") keeps the fp32 "do", and z[u]
+ *             stays fp32.  "gatmh_bwd_phase" = 0 equals phases 1 and 2 in turn.
+ * The bf16 rows are the per-call copy "gcn_bf16_gather" uses ((N + ghosts) x ld, ghost rows converted only once their
+ * exchange has landed, never kept across calls); it grows lazily in eager calls and cannot grow while an epoch is recorded
+ * (DORY_ERR_ARG: run one eager epoch with the option first).
+ * Only the sweep forms (gat_mh_sweep.hip) have bf16 kernels.  Where the dispatch would leave them -- "gatmh_sweep" = 0,
+ * "spmm_variant" other than 2, heads x features outside the sweep's shapes, no sweep layout for the graph (a graph whose rows
+ * fit the L2, unless "spmm_blk_nb" asks for one), and for value 2 a layer whose backward takes the blocked kernels (its
+ * forward did not run the sweep form; a single head of at most 32 features) -- dory_aggregate fails with DORY_ERR_ARG and
+ * names the condition; it never runs fp32 in silence.  The option is read by every call: a caller may run such a layer's
+ * backward with value 1.  Values outside {0, 1, 2} and nonzero values on DORY_GCN / DORY_GAT contexts are rejected.
+ * Read-only "gatmh_bf16_gathers_fwd" / "gatmh_bf16_gathers_src" count the passes that ran on bf16 rows (eager calls and
+ * recordings, not replays); timing family "bf16_convert" times the conversions.  Measured: profiles/r08_gatmh_bf16_ab.txt. */
+
 /* Epoch graph (MI355X-side addition, no reference counterpart): record the calls of one
  * epoch -- dory_aggregate / dory_apply_vertex / dory_apply_edge / dory_predict_gat /
  * dory_weight_update, exactly as Engine::runEpoch issues them -- into a hipGraph and replay

@@ -26,12 +26,15 @@ def main():
     tag = sys.argv[1]
     f = os.path.join(ROOT, "profiles", f"{tag}_pmc_fetch_size.txt")
     w = os.path.join(ROOT, "profiles", f"{tag}_pmc_write_size.txt")
-    fetch, names = counter_sum(f, "FETCH_SIZE", r"spmm_sweep_kernel|spmm_sweep_combine")
-    write, _ = counter_sum(w, "WRITE_SIZE", r"spmm_sweep_kernel|spmm_sweep_combine")
+    # a collection of the multi-head GAT passes alone (gat_mh_sweep.hip changed, spmm.hip and sweep_core.hpp did not) leaves the
+    # K1s and Amazon entries as they are
+    have_k1s = os.path.exists(f) and os.path.exists(w)
+    fetch, names = counter_sum(f, "FETCH_SIZE", r"spmm_sweep_kernel|spmm_sweep_combine") if have_k1s else (0.0, [])
+    write, _ = counter_sum(w, "WRITE_SIZE", r"spmm_sweep_kernel|spmm_sweep_combine") if have_k1s else (0.0, [])
     launches = 3   # the epoch's aggregations: F=602 forward, F=128 forward, F=128 backward (bench.py --steps 1 --warmup 0)
     p = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     pm = json.load(open(p))
-    pm["spmm_variant_2"] = {
+    k1s_entry = {
         "kernels": "spmm_sweep_kernel<32,10,false,PAIR> (K1s; PAIR on for the five-slab F=602 launch, off for the single-slab F=128 launches)",
         "fetch_size_kb_avg": round(fetch / launches, 1), "write_size_kb_avg": round(write / launches, 1),
         "bytes_per_launch": int((2 * fetch + write) / launches * 1024),
@@ -41,9 +44,11 @@ def main():
                 "`bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-alt`, summed over the sweep kernels of the epoch / 3 launches; "
                 "FETCH_SIZE doubled (gfx950 tallies 128-B requests at 64 B), WRITE_SIZE as reported.  Round 2 (r02e): 10.445 GB",
     }
+    if have_k1s:
+        pm["spmm_variant_2"] = k1s_entry
     # config 4 as one rank of 8 holds it (bench.py key amazon_rank0of8, K1 row gather): FETCH_SIZE of the epoch's five launches
     amz = os.path.join(ROOT, "profiles", f"{tag}_k1_amazon_rank_pmc_fetch_size.txt")
-    if not os.path.exists(amz):
+    if not os.path.exists(amz) and have_k1s:
         amz = os.path.join(ROOT, "profiles", "r04_k1_amazon_rank_pmc_fetch_size.txt")
     if os.path.exists(amz):
         fetch_a, names_a = counter_sum(amz, "FETCH_SIZE", r"spmm_rows_kernel")
