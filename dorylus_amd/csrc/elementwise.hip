@@ -45,6 +45,7 @@ __global__ void tanh_backward_kernel(uint64_t rows, uint32_t cols, const float *
 hipError_t launch_tanh_backward(uint64_t rows, uint32_t cols, const float *aTg, uint32_t lda,
                                 const float *z, uint32_t ldz, float *g, uint32_t ldg, hipStream_t s) {
     if (rows == 0) return hipSuccess;
+    if ((lda | ldz | ldg) & 3u) return hipErrorInvalidValue;   // 16-byte lanes: a one-column tensor (ld = 1) would be read and written past its rows
     const uint64_t n = rows * ((cols + 3) / 4);
     int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL(tanh_backward_kernel, dim3(blocks), dim3(256), 0, s, rows, cols, aTg, lda, z, ldz, g, ldg);

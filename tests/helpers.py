@@ -162,6 +162,21 @@ def make_ctx(da, g, dims, globalV, gnn=0, node_id=0, num_nodes=1, device=0, opti
     return ctx
 
 
+def _poison_padding(ctx, layer, name):
+    """NaN into the padding columns [cols, ld) of a device tensor, through its dory_tensor_info pointer"""
+    import ctypes as C
+    rows, cols, ld, p = ctx.info(layer, name)
+    if ld == cols or rows == 0:
+        return 0
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy2D.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    pad = np.full((rows, ld - cols), np.nan, np.float32)
+    ctx.sync()
+    rc = hip.hipMemcpy2D(C.c_void_p(p + cols * 4), ld * 4, pad.ctypes.data_as(C.c_void_p), (ld - cols) * 4, (ld - cols) * 4, rows, 1)
+    assert rc == 0
+    return ld - cols
+
+
 def oracle_gat_epoch(g, H0, labels, Ws, As):
     """One synchronous epoch of the reference's GAT prototype on a single partition
     (no ghosts), stage order of SURVEY.md 3.3, with the C oracle.  Ws[l]: d_l x d_{l+1},

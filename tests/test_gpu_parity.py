@@ -1203,21 +1203,6 @@ def test_sweep_variant_random_shapes(da):
         c.close()
 
 
-def _poison_padding(ctx, layer, name):
-    """NaN into the padding columns [cols, ld) of a device tensor, through its dory_tensor_info pointer"""
-    import ctypes as C
-    rows, cols, ld, p = ctx.info(layer, name)
-    if ld == cols or rows == 0:
-        return 0
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMemcpy2D.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
-    pad = np.full((rows, ld - cols), np.nan, np.float32)
-    ctx.sync()
-    rc = hip.hipMemcpy2D(C.c_void_p(p + cols * 4), ld * 4, pad.ctypes.data_as(C.c_void_p), (ld - cols) * 4, (ld - cols) * 4, rows, 1)
-    assert rc == 0
-    return ld - cols
-
-
 def test_gemm_does_not_read_operand_padding(da):
     """K2's operand tiles come in 16-byte pieces of 16-deep k-tiles, so the last k-tile of a row-major operand covers columns
     past K (602 -> 608, 24 -> 32, 12 -> 16): whatever lies there must not reach the product.  The tensors' padding is poisoned
@@ -1225,7 +1210,7 @@ def test_gemm_does_not_read_operand_padding(da):
     oracle's -- a missing mask or a wrong out-of-range bound shows up as NaN, not as a 1e-7 difference."""
     import orc
     import partition_oracle as po
-    from helpers import assert_parity, make_ctx
+    from helpers import _poison_padding, assert_parity, make_ctx
     V, dims = 777, [50, 24, 12, 7]
     ids = np.arange(V)
     g = po.preprocess(ids, ids, np.zeros(V, np.int64), 0, 1)     # one self edge per vertex: the graph does not matter here
