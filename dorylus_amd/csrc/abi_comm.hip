@@ -251,7 +251,7 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
     }
     p.send_total = p.send_off[P];
     p.recv_total = p.recv_off[P];
-    const uint32_t G = dir == DORY_FORWARD ? c->Gsrc : c->Gdst;
+    const uint32_t G = c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts;
     if (p.send_counts[c->nodeId] || p.recv_counts[c->nodeId]) return fail(c, DORY_ERR_ARG, "halo_plan: self entry must be empty");
     if (p.recv_total != G) return fail(c, DORY_ERR_ARG, "halo_plan: recv rows %u != ghost count %u", p.recv_total, G);
     for (uint32_t i = 0; i < p.send_total; ++i)
@@ -494,7 +494,7 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
     Tensor *ghost = name ? find(c, layer, name) : nullptr;
     if (!ghost || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
     HaloPlan &p = c->plan[dir];
-    if (ghost->rows != (dir == DORY_FORWARD ? c->Gsrc : c->Gdst)) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: '%s' is not a ghost tensor of that direction", name);
+    if (ghost->rows != c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: '%s' is not a ghost tensor of that direction", name);
     Timed t(c, "halo", c->compute);
     HIPCK(c, launch_scatter_rows(ghost->d, recv_buf, ghost->ld, ghost->ld, p.d_recv_slots, p.recv_total, c->compute));
     return DORY_OK;

@@ -88,6 +88,18 @@ int ensure_scratch(dory_ctx *c, size_t bytes) {
     return DORY_OK;
 }
 
+int ensure_partial(dory_ctx *c, size_t bytes, const char *what) {
+    if (bytes <= c->partial_bytes) return DORY_OK;
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: %s would have to grow while recording", what);
+    HIPCK(c, hipStreamSynchronize(c->compute));
+    if (c->partial) (void)hipFree(c->partial);
+    c->partial = nullptr;
+    c->partial_bytes = 0;
+    HIPCK(c, hipMalloc((void **)&c->partial, bytes));
+    c->partial_bytes = bytes;
+    return DORY_OK;
+}
+
 // longest-row-first schedule for skewed degree distributions
 std::vector<uint32_t> degree_order(const uint64_t *ptr, uint32_t N) {
     std::vector<uint32_t> o(N);
@@ -148,17 +160,17 @@ int gat_materialize(dory_ctx *c, uint32_t layer, int which) {
     if (c->gnn != DORY_GAT || !c->prealloc) return DORY_OK;
     if ((which & 1) && layer < c->gat_az_stale.size() && c->gat_az_stale[layer]) {
         Tensor *az = find(c, layer, "az"), *azrow = find(c, layer, "azrow");
-        if (az && azrow) HIPCK(c, launch_expand_rows_to_edges(c->N, c->colPtr, azrow->d, az->d, c->compute));
+        if (az && azrow) HIPCK(c, launch_expand_rows_to_edges(c->N, c->adj[ADJ_IN].ptr, azrow->d, az->d, c->compute));
         c->gat_az_stale[layer] = 0;
     }
     if ((which & 2) && c->gat_A_stale_layer >= 0) {
         Tensor *arow = find(c, (uint32_t)c->gat_A_stale_layer, "arow");
-        if (arow) HIPCK(c, launch_expand_rows_to_edges(c->N, c->colPtr, arow->d, c->cscVal, c->compute));
+        if (arow) HIPCK(c, launch_expand_rows_to_edges(c->N, c->adj[ADJ_IN].ptr, arow->d, c->adj[ADJ_IN].val, c->compute));
         c->gat_A_stale_layer = -1;
     }
     if ((which & 4) && layer < c->gat_dA_stale.size() && c->gat_dA_stale[layer]) {
         Tensor *dA = find(c, layer, "dA"), *drow = find(c, layer, "drow");
-        if (dA && drow) HIPCK(c, launch_expand_rows_to_edges(c->N, c->colPtr, drow->d, dA->d, c->compute));
+        if (dA && drow) HIPCK(c, launch_expand_rows_to_edges(c->N, c->adj[ADJ_IN].ptr, drow->d, dA->d, c->compute));
         c->gat_dA_stale[layer] = 0;
     }
     return DORY_OK;
@@ -283,38 +295,16 @@ int dory_create(int device, dory_ctx **out) {
 }
 
 static void free_graph(dory_ctx *c) {
-    void *ps[] = {c->colPtr, c->rowPtr, c->rowIdx, c->colIdx, c->cscVal, c->csrVal, c->norm, c->orderIn, c->orderOut,
-                  c->splitIn, c->splitOut};
-    for (void *p : ps)
-        if (p) (void)hipFree(p);
-    c->colPtr = c->rowPtr = nullptr;
-    c->rowIdx = c->colIdx = nullptr;
-    c->cscVal = c->csrVal = c->norm = nullptr;
-    c->orderIn = c->orderOut = nullptr;
-    c->splitIn = c->splitOut = nullptr;
-    c->nIntIn = c->nIntOut = 0;
-    for (EdgeSplit *E : {&c->esIn, &c->esOut}) {
-        if (E->idx) (void)hipFree(E->idx);
-        if (E->val) (void)hipFree(E->val);
-        if (E->mid) (void)hipFree(E->mid);
-        *E = EdgeSplit{};
+    if (c->norm) (void)hipFree(c->norm);
+    c->norm = nullptr;
+    for (Adjacency &A : c->adj) {
+        for (void *p : {(void *)A.ptr, (void *)A.idx, (void *)A.val, (void *)A.order, (void *)A.split, (void *)A.edge_split.idx,
+                        (void *)A.edge_split.val, (void *)A.edge_split.mid, (void *)A.long_rows.rows, (void *)A.long_rows.row_chunk_ptr,
+                        (void *)A.long_rows.chunks})
+            if (p) (void)hipFree(p);
+        for (BlockedAdj *B : {(BlockedAdj *)&A.blk, (BlockedAdj *)&A.blk16, (BlockedAdj *)&A.swp}) free_blocked(B);
+        A = Adjacency{};   // every schedule, layout and flag of the direction at once
     }
-    for (LongRowsDev *L : {&c->longIn, &c->longOut}) {
-        if (L->rows) (void)hipFree(L->rows);
-        if (L->row_chunk_ptr) (void)hipFree(L->row_chunk_ptr);
-        if (L->chunks) (void)hipFree(L->chunks);
-        *L = LongRowsDev{};
-    }
-    free_blocked(&c->blkIn);
-    free_blocked(&c->blkOut);
-    free_blocked(&c->blkIn16);
-    free_blocked(&c->blkOut16);
-    c->blkIn16_built = c->blkOut16_built = false;
-    free_blocked(&c->swpIn);
-    free_blocked(&c->swpOut);
-    c->swpIn_built = c->swpOut_built = c->swpIn_na = c->swpOut_na = false;
-    c->blkIn_built = c->blkOut_built = false;
-    c->blkIn_na = c->blkOut_na = false;
     c->has_graph = false;
 }
 
@@ -443,79 +433,72 @@ int dory_graph_upload(dory_ctx *c, uint32_t N, uint32_t Gsrc, uint32_t Gdst, uin
         if (column_idxs[e] >= (uint64_t)N + Gdst) return fail(c, DORY_ERR_ARG, "column index %u out of range at %llu", column_idxs[e], (unsigned long long)e);
     HIPCK(c, hipDeviceSynchronize());
     free_graph(c);
-    c->N = N; c->Gsrc = Gsrc; c->Gdst = Gdst; c->nnz_in = nnz_in; c->nnz_out = nnz_out;
+    c->N = N;
     int rc;
-    if ((rc = upload_array(c, &c->colPtr, column_ptrs, (uint64_t)N + 1))) return rc;
-    if ((rc = upload_array(c, &c->rowIdx, row_idxs, nnz_in))) return rc;
-    if ((rc = upload_array(c, &c->cscVal, csc_values, nnz_in))) return rc;
-    if ((rc = upload_array(c, &c->rowPtr, row_ptrs, (uint64_t)N + 1))) return rc;
-    if ((rc = upload_array(c, &c->colIdx, column_idxs, nnz_out))) return rc;
-    if ((rc = upload_array(c, &c->csrVal, csr_values, nnz_out))) return rc;
     if ((rc = upload_array(c, &c->norm, vtx_norms, (uint64_t)N))) return rc;
     const bool by_median = c->opt["spmm_order"] == 3;    // (set before the upload: the schedule is built here)
-    auto oi = by_median ? median_source_order(column_ptrs, row_idxs, N) : degree_order(column_ptrs, N);
-    auto oo = by_median ? median_source_order(row_ptrs, column_idxs, N) : degree_order(row_ptrs, N);
-    {   // is the degree distribution skewed enough for the longest-first row schedule to pay?  (Amazon-size uniform graph:
-        // 129 ms per epoch in row order against 134 longest first; R-MAT of the same size: 118 against 104)
-        auto skew = [&](const uint64_t *ptr, uint64_t nnz) {
+    struct HostAdj { const uint64_t *ptr; const uint32_t *idx; const float *val; uint64_t nnz; uint32_t ghosts; };
+    const HostAdj host[2] = {{column_ptrs, row_idxs, csc_values, nnz_in, Gsrc}, {row_ptrs, column_idxs, csr_values, nnz_out, Gdst}};
+    for (int d = 0; d < 2; ++d) {   // ADJ_IN, ADJ_OUT: each direction on its own
+        Adjacency &A = c->adj[d];
+        const uint64_t *ptr = host[d].ptr;
+        const uint32_t *idx = host[d].idx;
+        const float *val = host[d].val;
+        const uint64_t nnz = A.nnz = host[d].nnz;
+        A.ghosts = host[d].ghosts;
+        if ((rc = upload_array(c, &A.ptr, ptr, (uint64_t)N + 1))) return rc;
+        if ((rc = upload_array(c, &A.idx, idx, nnz))) return rc;
+        if ((rc = upload_array(c, &A.val, val, nnz))) return rc;
+        const std::vector<uint32_t> ord = by_median ? median_source_order(ptr, idx, N) : degree_order(ptr, N);
+        if ((rc = upload_array(c, &A.order, ord.data(), (uint64_t)N))) return rc;
+        {   // is the degree distribution skewed enough for the longest-first row schedule to pay?  (Amazon-size uniform graph:
+            // 129 ms per epoch in row order against 134 longest first; R-MAT of the same size: 118 against 104)
             uint64_t mx = 0;
             for (uint32_t v = 0; v < N; ++v) mx = std::max<uint64_t>(mx, ptr[v + 1] - ptr[v]);
-            return N > 0 && mx * (uint64_t)N > 8ull * nnz + 8ull * N;
-        };
-        c->skewIn = skew(column_ptrs, nnz_in);
-        c->skewOut = skew(row_ptrs, nnz_out);
-    }
-    if ((rc = upload_array(c, &c->orderIn, oi.data(), (uint64_t)N))) return rc;
-    if ((rc = upload_array(c, &c->orderOut, oo.data(), (uint64_t)N))) return rc;
-    for (int d = 0; d < 2; ++d) {   // K1's interior / boundary row split (partitions with ghosts), each direction on its own
-        if ((d == 0 ? Gsrc : Gdst) == 0) continue;
-        const uint64_t *ptr = d == 0 ? column_ptrs : row_ptrs;
-        const uint32_t *idx = d == 0 ? row_idxs : column_idxs;
-        const std::vector<uint32_t> &ord = d == 0 ? oi : oo;
-        std::vector<uint32_t> interior, boundary;
-        for (uint32_t v : ord) {   // keeps the longest-row-first order inside both parts
-            bool local = true;
-            for (uint64_t e = ptr[v]; e < ptr[v + 1] && local; ++e) local = idx[e] < N;
-            (local ? interior : boundary).push_back(v);
+            A.skew = N > 0 && mx * (uint64_t)N > 8ull * nnz + 8ull * N;
         }
-        (d == 0 ? c->nIntIn : c->nIntOut) = (uint32_t)interior.size();
-        interior.insert(interior.end(), boundary.begin(), boundary.end());
-        if ((rc = upload_array(c, d == 0 ? &c->splitIn : &c->splitOut, interior.data(), (uint64_t)N))) return rc;
-    }
-    for (int d = 0; d < 2; ++d) {   // K1's hub rows (spmm.hip: long rows)
-        LongRowsHost h;
-        plan_long_rows(d == 0 ? column_ptrs : row_ptrs, N, &h);
-        LongRowsDev &L = d == 0 ? c->longIn : c->longOut;
-        L.nrows = (uint32_t)h.rows.size();
-        L.nchunks = (uint32_t)(h.chunks.size() / 6);
-        if (!L.nchunks) continue;
-        if ((rc = upload_array(c, &L.rows, h.rows.data(), h.rows.size()))) return rc;
-        if ((rc = upload_array(c, &L.row_chunk_ptr, h.row_chunk_ptr.data(), h.row_chunk_ptr.size()))) return rc;
-        if ((rc = upload_array(c, &L.chunks, h.chunks.data(), h.chunks.size()))) return rc;
-    }
-    // K1's local-first edge order (ctx.hpp: EdgeSplit) for GCN partitions with ghosts and without hub rows
-    for (int d = 0; d < 2 && c->gnn == DORY_GCN && c->opt["spmm_edge_split"]; ++d) {
-        if ((d == 0 ? Gsrc : Gdst) == 0 || (d == 0 ? c->longIn : c->longOut).nchunks) continue;
-        const uint64_t *ptr = d == 0 ? column_ptrs : row_ptrs;
-        const uint32_t *idx = d == 0 ? row_idxs : column_idxs;
-        const float *val = d == 0 ? csc_values : csr_values;
-        const uint64_t nnz = d == 0 ? nnz_in : nnz_out;
-        std::vector<uint32_t> i2(nnz);
-        std::vector<float> v2(nnz);
-        std::vector<uint64_t> mid(N);
+        if (A.ghosts) {   // K1's interior / boundary row split (partitions with ghosts)
+            std::vector<uint32_t> interior, boundary;
+            for (uint32_t v : ord) {   // keeps the longest-row-first order inside both parts
+                bool local = true;
+                for (uint64_t e = ptr[v]; e < ptr[v + 1] && local; ++e) local = idx[e] < N;
+                (local ? interior : boundary).push_back(v);
+            }
+            A.n_interior = (uint32_t)interior.size();
+            interior.insert(interior.end(), boundary.begin(), boundary.end());
+            if ((rc = upload_array(c, &A.split, interior.data(), (uint64_t)N))) return rc;
+        }
+        {   // K1's hub rows (spmm.hip: long rows)
+            LongRowsHost h;
+            plan_long_rows(ptr, N, &h);
+            LongRowsDev &L = A.long_rows;
+            L.nrows = (uint32_t)h.rows.size();
+            L.nchunks = (uint32_t)(h.chunks.size() / 6);
+            if (L.nchunks) {
+                if ((rc = upload_array(c, &L.rows, h.rows.data(), h.rows.size()))) return rc;
+                if ((rc = upload_array(c, &L.row_chunk_ptr, h.row_chunk_ptr.data(), h.row_chunk_ptr.size()))) return rc;
+                if ((rc = upload_array(c, &L.chunks, h.chunks.data(), h.chunks.size()))) return rc;
+            }
+        }
+        // K1's local-first edge order (ctx.hpp: EdgeSplit) for GCN partitions with ghosts and without hub rows
+        if (c->gnn == DORY_GCN && c->opt["spmm_edge_split"] && A.ghosts && !A.long_rows.nchunks) {
+            std::vector<uint32_t> i2(nnz);
+            std::vector<float> v2(nnz);
+            std::vector<uint64_t> mid(N);
 #pragma omp parallel for schedule(dynamic, 4096)
-        for (int64_t v = 0; v < (int64_t)N; ++v) {
-            uint64_t w = ptr[v];
-            for (uint64_t e = ptr[v]; e < ptr[v + 1]; ++e)
-                if (idx[e] < N) { i2[w] = idx[e]; v2[w] = val[e]; ++w; }
-            mid[v] = w;
-            for (uint64_t e = ptr[v]; e < ptr[v + 1]; ++e)
-                if (idx[e] >= N) { i2[w] = idx[e]; v2[w] = val[e]; ++w; }
+            for (int64_t v = 0; v < (int64_t)N; ++v) {
+                uint64_t w = ptr[v];
+                for (uint64_t e = ptr[v]; e < ptr[v + 1]; ++e)
+                    if (idx[e] < N) { i2[w] = idx[e]; v2[w] = val[e]; ++w; }
+                mid[v] = w;
+                for (uint64_t e = ptr[v]; e < ptr[v + 1]; ++e)
+                    if (idx[e] >= N) { i2[w] = idx[e]; v2[w] = val[e]; ++w; }
+            }
+            EdgeSplit &E = A.edge_split;
+            if ((rc = upload_array(c, &E.idx, i2.data(), nnz))) return rc;
+            if ((rc = upload_array(c, &E.val, v2.data(), nnz))) return rc;
+            if ((rc = upload_array(c, &E.mid, mid.data(), (uint64_t)N))) return rc;
         }
-        EdgeSplit &E = d == 0 ? c->esIn : c->esOut;
-        if ((rc = upload_array(c, &E.idx, i2.data(), nnz))) return rc;
-        if ((rc = upload_array(c, &E.val, v2.data(), nnz))) return rc;
-        if ((rc = upload_array(c, &E.mid, mid.data(), (uint64_t)N))) return rc;
     }
     c->has_graph = true;
     return DORY_OK;
@@ -529,6 +512,7 @@ int dory_preallocate(dory_ctx *c) {
     HIPCK(c, hipDeviceSynchronize());
     free_table(c->tensors); free_table(c->weights); free_table(c->wgrads); free_table(c->adam_m); free_table(c->adam_v);
     const uint32_t L = c->L, N = c->N;
+    Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
     auto &d = c->dims;
     c->tensors.assign(L + 1, {});
     c->weights.assign(L, {}); c->wgrads.assign(L, {}); c->adam_m.assign(L, {}); c->adam_v.assign(L, {});
@@ -539,28 +523,28 @@ int dory_preallocate(dory_ctx *c) {
     };
     if (c->gnn == DORY_GCN) {  // Engine::preallocateGCN (engine/ops/gcn_ops.cpp:27-93)
         mk(0, "x", N, d[0]);
-        mk(0, "fg", c->Gsrc, d[0]);
+        mk(0, "fg", In.ghosts, d[0]);
         mk(L - 1, "lab", N, d[L]);
         for (uint32_t l = 0; l < L; ++l) {
             mk(l, "ah", N, d[l]);
             mk(l, "z", N, d[l + 1]);            // reference keeps z only for l < L-1; last-layer logits are a temporary there
             if (l < L - 1) {
                 mk(l, "h", N, d[l + 1]);
-                mk(l + 1, "fg", c->Gsrc, d[l + 1]);
+                mk(l + 1, "fg", In.ghosts, d[l + 1]);
             }
             mk(l, "g", N, d[l + 1]);            // interGrad / d_output temporaries of CPU_comm.cpp:121,143
         }
         for (uint32_t l = L - 1; l > 0; --l) {
             mk(l, "grad", N, d[l]);
-            mk(l - 1, "bg", c->Gdst, d[l]);
+            mk(l - 1, "bg", Out.ghosts, d[l]);
             mk(l - 1, "aTg", N, d[l]);
         }
         for (uint32_t l = 0; l < L && L >= 2; ++l) {   // transform-first order (option gcn_transform_first)
             if (d[l] <= d[l + 1]) continue;
             mk(l, "xw", N, d[l + 1]);          // in_l W_l
-            mk(l, "fgxw", c->Gsrc, d[l + 1]);  // its ghost rows (layer 0: transformed locally from fg@0, else exchanged)
+            mk(l, "fgxw", In.ghosts, d[l + 1]);  // its ghost rows (layer 0: transformed locally from fg@0, else exchanged)
             mk(l, "u", N, d[l + 1]);           // A^T g_l
-            mk(l, "bgg", c->Gdst, d[l + 1]);   // ghost rows of g_l (backward exchange)
+            mk(l, "bgg", Out.ghosts, d[l + 1]);   // ghost rows of g_l (backward exchange)
         }
     } else if (c->gnn == DORY_GATMH) {  // extension (no reference counterpart): see dory_gatmh_heads
         mk(0, "h", N, d[0]);
@@ -584,11 +568,11 @@ int dory_preallocate(dory_ctx *c) {
             mk(l, "dpos", N, K);                 // and the attention mass of those edges
             // partitioned runs: ghost sources of the in-edges (z exchanged forward, el/er recomputed from it) and
             // ghost destinations of the out-edges (dO and st exchanged between the two phases of the backward sweep)
-            mk(l, "fg_z", c->Gsrc, zw);
-            mk(l, "fg_el", c->Gsrc, K);
-            mk(l, "fg_er", c->Gsrc, K);
-            mk(l, "bg_do", c->Gdst, zw);
-            mk(l, "bg_st", c->Gdst, 4 * K);
+            mk(l, "fg_z", In.ghosts, zw);
+            mk(l, "fg_el", In.ghosts, K);
+            mk(l, "fg_er", In.ghosts, K);
+            mk(l, "bg_do", Out.ghosts, zw);
+            mk(l, "bg_st", Out.ghosts, 4 * K);
             if (!last) mk(l + 1, "h", N, d[l + 1]);
             if (l > 0) mk(l, "dh", N, d[l]);
         }
@@ -597,17 +581,17 @@ int dory_preallocate(dory_ctx *c) {
         mk(L - 1, "lab", N, d[L]);
         for (uint32_t l = 0; l < L; ++l) {
             mk(l, "z", N, d[l + 1]);
-            mk(l, "az", c->nnz_in, 1);
-            mk(l, "fg_z", c->Gsrc, d[l + 1]);
+            mk(l, "az", In.nnz, 1);
+            mk(l, "fg_z", In.ghosts, d[l + 1]);
             Tensor A;  // "A" aliases forwardAdj.values (gat_ops.cpp:61-64)
-            A.rows = c->nnz_in; A.cols = 1; A.ld = 1; A.d = c->cscVal; A.owned = false;
+            A.rows = In.nnz; A.cols = 1; A.ld = 1; A.d = In.val; A.owned = false;
             c->tensors[l]["A"] = A;
             mk(l, "ah", N, d[l + 1]);
             if (l < L - 1) mk(l + 1, "h", N, d[l + 1]);
             mk(l, "grad", N, d[l + 1]);
-            mk(l, "dA", c->nnz_in, 1);
+            mk(l, "dA", In.nnz, 1);
             mk(l, "aTg", N, d[l + 1]);
-            mk(l, "bg_d", c->Gdst, d[l + 1]);
+            mk(l, "bg_d", Out.ghosts, d[l + 1]);
         }
         mk(0, "cw", N, 1);  // column weights for the a_i gradient (K5)
         for (uint32_t l = 0; l < L; ++l) {
@@ -649,53 +633,39 @@ int dory_preallocate(dory_ctx *c) {
     }
     c->adam.epochs = 1;
     HIPCK(c, hipStreamSynchronize(c->compute));
+    auto layer_ld = [&](uint32_t l) { return pad_ld(l == L - 1 ? d[l + 1] * c->heads[l] : d[l + 1]); };   // multi-head GAT: z / o of layer l
+    const uint32_t G = std::min<uint32_t>(32u, c->cus_per_xcd);
     if (c->opt["spmm_variant"] == 2 && N > 0 && c->gnn == DORY_GATMH && c->opt["gatmh_sweep"]) {
         // the sweep layouts (K1s's even layout; the deal is made for the 32-lane launches) and the gate counters now
         uint32_t maxld = 0;
-        for (uint32_t l = 0; l < L; ++l) maxld = std::max(maxld, pad_ld(l == L - 1 ? d[l + 1] * c->heads[l] : d[l + 1]));
+        for (uint32_t l = 0; l < L; ++l) maxld = std::max(maxld, layer_ld(l));
         const int group = blk_group_for(c, maxld);
-        if ((rc = ensure_sweep(c, true, group))) return rc;
-        if ((rc = ensure_sweep(c, false, group))) return rc;
         c->gatmh_fwd_swept.assign(L, 0);
         size_t need = 0;
-        for (const BlockedAdj *S : {&c->swpIn, &c->swpOut})
-            if (S->nb)
-                for (uint32_t l = 0; l < L; ++l) {   // every layer's own launch shape: its leading dimension (a 96-float layer runs 16-lane
-                    // groups on two slabs) and the group blk_group_for() gives it; launches walk fewer rows per group than the
-                    // layout deals (more sweeps, more counters): 2 is the least
-                    const uint32_t ld_l = pad_ld(l == L - 1 ? d[l + 1] * c->heads[l] : d[l + 1]);
-                    need = std::max(need, sweep_scratch_bytes(*S, ld_l, blk_group_for(c, ld_l), std::min<uint32_t>(32u, c->cus_per_xcd), S->nb, 2));
-                }
-        if (need > c->partial_bytes) {
-            if (c->partial) (void)hipFree(c->partial);
-            c->partial = nullptr;
-            c->partial_bytes = 0;
-            HIPCK(c, hipMalloc((void **)&c->partial, need));
-            c->partial_bytes = need;
+        for (Adjacency &A : c->adj) {
+            if ((rc = ensure_sweep(c, A, group))) return rc;
+            for (uint32_t l = 0; l < L && A.swp.nb; ++l)   // every layer's own launch shape: its leading dimension (a 96-float layer runs 16-lane
+                // groups on two slabs) and the group blk_group_for() gives it; launches walk fewer rows per group than the
+                // layout deals (more sweeps, more counters): 2 is the least
+                need = std::max(need, sweep_scratch_bytes(A.swp, layer_ld(l), blk_group_for(c, layer_ld(l)), G, A.swp.nb, 2));
         }
+        // (ensure_partial synchronises the compute stream before it frees; nothing in flight reads c->partial before `prealloc` is set)
+        if ((rc = ensure_partial(c, need, "sweep counters"))) return rc;
     }
     if (c->opt["spmm_variant"] >= 1 && N > 0 && c->gnn == DORY_GATMH && c->opt["gatmh_blocked"]) {
         // the extension's forward sum gathers through the same source-blocked copy of the in-edges
-        uint32_t maxld = 0;
-        for (uint32_t l = 0; l < L; ++l) maxld = std::max(maxld, pad_ld(l == L - 1 ? d[l + 1] * c->heads[l] : d[l + 1]));
-        if ((rc = ensure_blocked(c, true, blk_group_for(c, maxld)))) return rc;
-        if ((rc = ensure_blocked(c, false, blk_group_for(c, maxld)))) return rc;   // backward, source side
-        uint32_t minld = maxld;
-        for (uint32_t l = 0; l < L; ++l) minld = std::min(minld, pad_ld(l == L - 1 ? d[l + 1] * c->heads[l] : d[l + 1]));
-        if (maxld >= 128 && minld < 128 && !c->blkIn_na && !c->blkOut_na) {   // narrow layers beside wide ones: their own pair (256-B slabs)
-            if ((rc = ensure_blocked(c, true, 16, true))) return rc;
-            if ((rc = ensure_blocked(c, false, 16, true))) return rc;
+        uint32_t maxld = 0, minld = 0xFFFFFFFFu;
+        for (uint32_t l = 0; l < L; ++l) { maxld = std::max(maxld, layer_ld(l)); minld = std::min(minld, layer_ld(l)); }
+        if ((rc = ensure_blocked(c, In, blk_group_for(c, maxld)))) return rc;
+        if ((rc = ensure_blocked(c, Out, blk_group_for(c, maxld)))) return rc;   // backward, source side
+        if (maxld >= 128 && minld < 128 && !In.blk.na && !Out.blk.na) {   // narrow layers beside wide ones: their own copies (256-B slabs)
+            if ((rc = ensure_blocked(c, In, 16, true))) return rc;
+            if ((rc = ensure_blocked(c, Out, 16, true))) return rc;
         }
-        const uint32_t nbmax = std::max(c->blkIn.nb, c->blkOut.nb);
+        const uint32_t nbmax = std::max(In.blk.nb, Out.blk.nb);
         size_t need = (size_t)nbmax * N * (maxld + 64) * sizeof(float);            // + per-(block,row,head) partials
-        need = std::max(need, (size_t)std::max(c->blkIn16.nb, c->blkOut16.nb) * N * (std::min<uint32_t>(maxld, 96u) + 64) * sizeof(float));
-        if (nbmax && need <= ((size_t)48 << 30) && need > c->partial_bytes) {
-            if (c->partial) (void)hipFree(c->partial);
-            c->partial = nullptr;
-            c->partial_bytes = 0;
-            HIPCK(c, hipMalloc((void **)&c->partial, need));
-            c->partial_bytes = need;
-        }
+        need = std::max(need, (size_t)std::max(In.blk16.nb, Out.blk16.nb) * N * (std::min<uint32_t>(maxld, 96u) + 64) * sizeof(float));
+        if (nbmax && need <= ((size_t)48 << 30) && (rc = ensure_partial(c, need, "partial buffer"))) return rc;
     }
     if (c->opt["spmm_variant"] >= 1 && N > 0 && c->gnn != DORY_GATMH) {   // K1b: regroup the edges now, not inside the first epoch
         uint32_t minld = 0xFFFFFFFFu;
@@ -709,35 +679,23 @@ int dory_preallocate(dory_ctx *c) {
         if (minld >= 32 && c->opt["spmm_variant"] == 2) {
             // K1s: its layouts and the gate counters of the largest launch now, so that nothing is built or allocated
             // inside an epoch (a partition it does not take -- too small, too large -- keeps K1 / builds K1b on demand)
-            if ((rc = ensure_sweep(c, true, group))) return rc;
-            if ((rc = ensure_sweep(c, false, group))) return rc;
             size_t need = 0;
-            for (const BlockedAdj *S : {&c->swpIn, &c->swpOut})
-                if (S->nb) need = std::max(need, sweep_scratch_bytes(*S, maxld, group, std::min<uint32_t>(32u, c->cus_per_xcd), S->nb, (int)c->opt["spmm_sweep_rows"]));
-            if (need > c->partial_bytes) {
-                if (c->partial) (void)hipFree(c->partial);
-                c->partial = nullptr;
-                c->partial_bytes = 0;
-                HIPCK(c, hipMalloc((void **)&c->partial, need));
-                c->partial_bytes = need;
+            for (Adjacency &A : c->adj) {
+                if ((rc = ensure_sweep(c, A, group))) return rc;
+                if (A.swp.nb) need = std::max(need, sweep_scratch_bytes(A.swp, maxld, group, G, A.swp.nb, (int)c->opt["spmm_sweep_rows"]));
             }
+            if ((rc = ensure_partial(c, need, "sweep counters"))) return rc;
             // the slots of the split rows' pieces too (skewed graphs): an epoch recorded into a hipGraph right after a
             // re-upload must not find anything left to allocate
-            const uint32_t nslots = std::max(c->swpIn.nslots, c->swpOut.nslots);
+            const uint32_t nslots = std::max(In.swp.nslots, Out.swp.nslots);
             if (nslots && (rc = ensure_scratch(c, (size_t)nslots * maxld * sizeof(float)))) return rc;
         } else if (minld >= 32) {
-            if ((rc = ensure_blocked(c, true, group))) return rc;
-            if ((rc = ensure_blocked(c, false, group))) return rc;
+            if ((rc = ensure_blocked(c, In, group))) return rc;
+            if ((rc = ensure_blocked(c, Out, group))) return rc;
             // the partial-sum buffer too, so that no allocation happens inside an epoch
-            const uint32_t nbmax = std::max(c->blkIn.nb, c->blkOut.nb);
+            const uint32_t nbmax = std::max(In.blk.nb, Out.blk.nb);
             const size_t need = (size_t)nbmax * N * maxld * sizeof(float);
-            if (nbmax && need <= ((size_t)48 << 30) && need > c->partial_bytes) {
-                if (c->partial) (void)hipFree(c->partial);
-                c->partial = nullptr;
-                c->partial_bytes = 0;
-                HIPCK(c, hipMalloc((void **)&c->partial, need));
-                c->partial_bytes = need;
-            }
+            if (nbmax && need <= ((size_t)48 << 30) && (rc = ensure_partial(c, need, "partial buffer"))) return rc;
         }
     }
     c->gat_ones_set = false;

@@ -39,9 +39,10 @@ int fail(dory_ctx *c, int code, const char *fmt, ...);
     std::lock_guard<std::mutex> lock__((c)->mu);                                       \
     HIPCK((c), hipSetDevice((c)->device))
 
-#define NEED(ptr, l, nm)                                                                  \
+#define NEED_IN(fn, ptr, l, nm)                                                           \
     Tensor *ptr = find(c, (l), nm);                                                       \
-    if (!ptr) return fail(c, DORY_ERR_ARG, "%s: tensor '%s'@%u missing", __func__, nm, (unsigned)(l))
+    if (!ptr) return fail(c, DORY_ERR_ARG, "%s: tensor '%s'@%u missing", fn, nm, (unsigned)(l))
+#define NEED(ptr, l, nm) NEED_IN(__func__, ptr, l, nm)
 
 // ---- timing: HIP events on the stream the kernels run on --------------------------
 struct Timed {
@@ -78,7 +79,9 @@ Tensor *find(dory_ctx *c, uint32_t layer, const char *name);
 Tensor *findw(std::vector<std::map<std::string, Tensor>> &tab, uint32_t layer, const char *name);
 void free_table(std::vector<std::map<std::string, Tensor>> &tab);
 int ensure_scratch(dory_ctx *c, size_t bytes);
-int ensure_sweep(dory_ctx *c, bool csc, int group);
+// c->partial (K1b's partial rows, the sweeps' gate counters); `what` names it in the refusal inside a recording
+int ensure_partial(dory_ctx *c, size_t bytes, const char *what);
+int ensure_sweep(dory_ctx *c, Adjacency &A, int group);
 // drops a recorded epoch (hipGraph): anything that frees or moves what the recorded kernels point at calls this
 void epoch_graph_drop_locked(dory_ctx *c);
 std::vector<uint32_t> degree_order(const uint64_t *ptr, uint32_t N);
@@ -106,9 +109,7 @@ bool tf_active(dory_ctx *c);   // = tf_layer(c, 0)
 // one all-to-all-v of rows with the plan of `dir` (abi_comm.hip)
 int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer);
 // K1b bookkeeping (abi_stages.hip)
-int ensure_blocked(dory_ctx *c, bool csc, int group, bool narrow_set = false /* the multi-head GAT contexts' second pair (ctx.hpp) */);
-// the blocked copy a multi-head GAT layer of leading dimension ld gathers through
-BlockedAdj &gatmh_blocked_for(dory_ctx *c, bool csc, uint32_t ld);
+int ensure_blocked(dory_ctx *c, Adjacency &A, int group, bool narrow_set = false /* the multi-head GAT contexts' second copy (Adjacency::blk16) */);
 int blk_group_for(dory_ctx *c, uint32_t ld);
 
 }  // namespace dory

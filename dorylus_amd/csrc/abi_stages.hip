@@ -4,26 +4,24 @@
 
 namespace dory {
 // ---------------------------------------------------------------------------------------
-// K1b bookkeeping: (re)build the source-blocked copy of one adjacency for `group` lanes/row
-BlockedAdj &gatmh_blocked_for(dory_ctx *c, bool csc, uint32_t ld) {
-    if (ld < 128 && (csc ? c->blkIn16_built : c->blkOut16_built)) return csc ? c->blkIn16 : c->blkOut16;
-    return csc ? c->blkIn : c->blkOut;
-}
+// the blocked copy a multi-head GAT layer of leading dimension ld gathers through
+static BlockedAdj &gatmh_blocked_for(Adjacency &A, uint32_t ld) { return ld < 128 && A.blk16.built ? A.blk16 : A.blk; }
 
-int ensure_blocked(dory_ctx *c, bool csc, int group, bool narrow_set) {
-    BlockedAdj &B = narrow_set ? (csc ? c->blkIn16 : c->blkOut16) : (csc ? c->blkIn : c->blkOut);
-    bool &built = narrow_set ? (csc ? c->blkIn16_built : c->blkOut16_built) : (csc ? c->blkIn_built : c->blkOut_built);
+// K1b bookkeeping: (re)build the source-blocked copy of one adjacency for `group` lanes/row
+int ensure_blocked(dory_ctx *c, Adjacency &A, int group, bool narrow_set) {
+    DerivedAdj &B = narrow_set ? A.blk16 : A.blk;
     const uint32_t want_nb = (uint32_t)c->opt["spmm_blk_nb"];
     // the block structure serves every slab width; only an explicit block count forces a rebuild
-    if (c->capturing && (!built || (want_nb && B.nb != (want_nb + 7) / 8 * 8)) && !(csc ? c->blkIn_na : c->blkOut_na))
+    const bool rebuild = B.built && want_nb && B.nb != (want_nb + 7) / 8 * 8;
+    if (c->capturing && (!B.built || rebuild) && !A.blk.na)
         return fail(c, DORY_ERR_ARG, "epoch graph: blocked adjacency would have to be (re)built while recording");
-    if (built && want_nb && B.nb != (want_nb + 7) / 8 * 8) {
+    if (rebuild) {
         HIPCK(c, hipStreamSynchronize(c->compute));
         free_blocked(&B);
-        built = false;
+        B.built = false;
     }
-    if (!built) {
-        const uint32_t NG = c->N + (csc ? c->Gsrc : c->Gdst);
+    if (!B.built) {
+        const uint32_t NG = c->N + A.ghosts;
         // K1b pays nb partial rows per output row: only worth it (and only affordable: the
         // per-(block,row) offset table is nb*(N+1) words) while the source space is a few
         // hundred L2 windows at most.  Larger partitions keep K1.
@@ -35,31 +33,28 @@ int ensure_blocked(dory_ctx *c, bool csc, int group, bool narrow_set) {
         const bool tiny = !want_nb && (uint64_t)NG * group * 16u <= ((uint64_t)4 << 20) &&
                           !(c->gnn == DORY_GATMH && c->numNodes > 1);
         if (tiny || nb > 256 || (uint64_t)nb * (c->N + 1) * 8ull > ((uint64_t)8 << 30)) {
-            if (!narrow_set) (csc ? c->blkIn_na : c->blkOut_na) = true;   // (no second pair: the narrow layers share the first)
+            if (!narrow_set) A.blk.na = true;   // (no second copy: the narrow layers share the first)
             return DORY_OK;
         }
-        HIPCK(c, build_blocked(csc ? c->colPtr : c->rowPtr, csc ? c->rowIdx : c->colIdx, csc ? c->cscVal : c->csrVal,
-                               c->N, NG, csc ? c->nnz_in : c->nnz_out, want_nb, (uint32_t)group * 16u, &B, c->compute, window));
+        HIPCK(c, build_blocked(A.ptr, A.idx, A.val, c->N, NG, A.nnz, want_nb, (uint32_t)group * 16u, &B, c->compute, window));
         B.row_bytes = (uint32_t)group * 16u;
-        built = true;
+        B.built = true;
     }
     return DORY_OK;
 }
 
 // K1s bookkeeping: the even layout build_blocked_sweep makes of one adjacency (spmm.hip)
-int ensure_sweep(dory_ctx *c, bool csc, int group) {
-    BlockedAdj &S = csc ? c->swpIn : c->swpOut;
-    bool &built = csc ? c->swpIn_built : c->swpOut_built;
-    bool &na = csc ? c->swpIn_na : c->swpOut_na;
+int ensure_sweep(dory_ctx *c, Adjacency &A, int group) {
+    DerivedAdj &S = A.swp;
     const uint32_t want_nb = (uint32_t)c->opt["spmm_blk_nb"];
-    if (built && (csc ? c->swpIn_want_nb : c->swpOut_want_nb) != want_nb && !c->capturing) {   // another block count requested (tests): rebuild
+    if (S.built && S.want_nb != want_nb && !c->capturing) {   // another block count requested (tests): rebuild
         HIPCK(c, hipStreamSynchronize(c->compute));
         free_blocked(&S);
-        built = false;
+        S.built = false;
     }
-    if (built || na) return DORY_OK;
+    if (S.built || S.na) return DORY_OK;
     if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the sweep layout would have to be built while recording");
-    const uint32_t NG = c->N + (csc ? c->Gsrc : c->Gdst);
+    const uint32_t NG = c->N + A.ghosts;
     // the deal is made for the 32-lane launches; the multi-head GAT passes keep ten registers per row: 4 rows at most
     int R;
     if (c->gnn == DORY_GATMH) {
@@ -80,7 +75,8 @@ int ensure_sweep(dory_ctx *c, bool csc, int group) {
     // (round 6: the 8-head GAT's SOURCE side gathers a 128-byte statistics record beside every 512-byte row -- its window is a
     // quarter larger than the forward's for the same rows, and at 4.5 MB of rows it ran fabric-bound: 29.6 GB fetched in 5.1 ms
     // per 128-float launch; the out-edge layout therefore gets its own window, option gatmh_src_window_kb)
-    const uint64_t gat_kb = (c->gnn == DORY_GATMH && !csc && c->opt["gatmh_src_window_kb"]) ? (uint64_t)c->opt["gatmh_src_window_kb"] : 4608u;
+    const bool out_edges = &A == &c->adj[ADJ_OUT];   // (by identity: an Adjacency is only ever handed on by reference into c->adj)
+    const uint64_t gat_kb = (c->gnn == DORY_GATMH && out_edges && c->opt["gatmh_src_window_kb"]) ? (uint64_t)c->opt["gatmh_src_window_kb"] : 4608u;
     const uint64_t window_kb = c->opt["spmm_sweep_window_kb"] ? (uint64_t)c->opt["spmm_sweep_window_kb"]
                                                               : (c->gnn == DORY_GATMH && R >= 4 ? gat_kb : (R <= 4 ? 3584u : 2432u));
     const uint64_t window = window_kb << 10;
@@ -90,15 +86,14 @@ int ensure_sweep(dory_ctx *c, bool csc, int group) {
     // position) offset table alone would be nb*(N+1) words -- K1
     const bool tiny = !want_nb && (uint64_t)NG * group * 16u <= ((uint64_t)4 << 20);
     if (tiny || c->N < 8 || (want_nb ? want_nb : nb_est) > 512 || (want_nb ? want_nb : nb_est) * (uint64_t)(c->N + 1) * 8ull > ((uint64_t)8 << 30)) {
-        na = true;
+        S.na = true;
         return DORY_OK;
     }
-    HIPCK(c, build_blocked_sweep(csc ? c->colPtr : c->rowPtr, csc ? c->rowIdx : c->colIdx, csc ? c->cscVal : c->csrVal, c->N,
-                                 NG, csc ? c->nnz_in : c->nnz_out, want_nb, (uint32_t)group * 16u, window, R, &S, c->compute,
+    HIPCK(c, build_blocked_sweep(A.ptr, A.idx, A.val, c->N, NG, A.nnz, want_nb, (uint32_t)group * 16u, window, R, &S, c->compute,
                                  (uint32_t)c->opt["spmm_sweep_layout"], std::min<uint32_t>(32u, c->cus_per_xcd),
                                  group == 32 && c->opt["spmm_sweep_loader"] ? (uint32_t)c->opt["spmm_sweep_loader_relief"] : 0u));
-    (csc ? c->swpIn_want_nb : c->swpOut_want_nb) = want_nb;
-    built = true;
+    S.want_nb = want_nb;
+    S.built = true;
     return DORY_OK;
 }
 
@@ -112,7 +107,7 @@ int blk_group_for(dory_ctx *c, uint32_t ld) {
 // Options gcn_bf16_gather / gatmh_bf16_gather: the rows of one aggregation rounded to bf16 into the context's shadow buffer,
 // [N local rows ; ghost rows], every call (nothing is kept: a caller may write x / h / fg through a raw pointer between two
 // calls).  The buffer only grows, outside a recording.
-static int bf16_shadow(dory_ctx *c, uint64_t rows, uint32_t ld, const char *option = "gcn_bf16_gather") {
+static int bf16_reserve(dory_ctx *c, uint64_t rows, uint32_t ld, const char *option) {
     const size_t need = (size_t)rows * ld * sizeof(uint16_t);
     if (need <= c->bf16_rows_bytes) return DORY_OK;
     if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the bf16 rows of %s would have to grow while recording", option);
@@ -133,6 +128,220 @@ static int bf16_convert(dory_ctx *c, const Tensor &t, uint64_t first_row) {
     HIPCK(c, launch_bf16_rows(t.d, c->bf16_rows + first_row * t.ld, t.rows * t.ld, c->compute));
     return DORY_OK;
 }
+// One aggregation's use of the shadow buffer.  begin() sizes it and converts the N local rows at once: xl / xg are what the
+// kernels' row pointers become.  The ghost rows are converted by ghosts_landed(), to be called once the exchange that writes
+// them has landed (after wait_halo; at once where they have landed already).  Never begun = fp32 rows: nothing to convert.
+struct Bf16Rows {
+    dory_ctx *c = nullptr;
+    const Tensor *ghost = nullptr;
+    const float *xl = nullptr, *xg = nullptr;   // bf16 rows of ld elements; xg == nullptr: no ghost rows
+    int begin(dory_ctx *ctx, const Tensor &rows, const Tensor *ghost_rows, uint64_t nghost, const char *option) {
+        Tensor local = rows;
+        local.rows = ctx->N;
+        int rc = bf16_reserve(ctx, (uint64_t)ctx->N + nghost, rows.ld, option);
+        if (!rc) rc = bf16_convert(ctx, local, 0);
+        if (rc) return rc;
+        c = ctx;
+        ghost = nghost ? ghost_rows : nullptr;
+        xl = reinterpret_cast<const float *>(c->bf16_rows);
+        xg = nghost ? reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * rows.ld) : nullptr;
+        return DORY_OK;
+    }
+    bool on() const { return c != nullptr; }
+    int ghosts_landed() { return ghost ? bf16_convert(c, *ghost, c->N) : DORY_OK; }
+};
+
+// The schedule every kernel family of spmm() follows around a halo exchange: what does not read the ghost rows is launched
+// `first`, timed as "spmm_beside_halo" (under an exchange in flight; "spmm_local_first": the same split with nothing in
+// flight), then the compute stream waits for the ghosts (and rounds them, for an aggregation on bf16 rows), then `rest` runs.
+// Not split: the wait, then `rest` alone.  bf == nullptr: an aggregation on fp32 rows (K1b has no other).
+template <class First, class Rest>
+static int around_halo(dory_ctx *c, bool split, Bf16Rows *bf, First first, Rest rest) {
+    int rc;
+    if (split) {
+        Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
+        if ((rc = first())) return rc;
+    }
+    if ((rc = wait_halo(c)) || (bf && (rc = bf->ghosts_landed()))) return rc;
+    return rest();
+}
+
+// What a launch sequence on the sweep skeleton (K1s, the 8-head GAT's edge passes) needs beside its tensors.
+struct SweepLaunch {
+    int group = 32;             // lanes per row
+    uint32_t G = 32;            // workgroups per sweep and XCD
+    // With ghost rows the blocks that hold local rows only always run as a launch of their own (they do not
+    // depend on an exchange in flight), so the overlapped and the sequential schedule are the same arithmetic.
+    bool two = false;
+    SweepCtl ctl;
+    uint32_t sflags = 0;        // option spmm_sweep_flags, + 8 (ungated) where the XCD placement check failed and "gated" was not measured faster
+    size_t need = 0;            // bytes of gate counters the larger of its launches takes
+    uint32_t *done = nullptr;   // the counters (c->partial); nullptr: c->partial holds fewer than `need` bytes
+};
+static uint32_t sweep_flags(dory_ctx *c) {
+    return (uint32_t)c->opt["spmm_sweep_flags"] | (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
+}
+static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, int group, bool ghosts, int rows /* per lane group */) {
+    SweepLaunch sw;
+    sw.group = group;
+    sw.G = std::min<uint32_t>(32u, c->cus_per_xcd);
+    sw.two = ghosts && S.nb_local > 0 && S.nb_local < S.nb;
+    sw.ctl.stat = c->sweep_stat;
+    sw.sflags = sweep_flags(c);
+    sw.need = sweep_scratch_bytes(S, ld, group, sw.G, sw.two ? std::max(S.nb_local, S.nb - S.nb_local) : S.nb, rows);
+    sw.done = sw.need <= c->partial_bytes ? reinterpret_cast<uint32_t *>(c->partial) : nullptr;
+    return sw;
+}
+
+// K1s's placement check failed (ctx.hpp): gates would synchronise workgroups that do not share an L2.  Decide once per context,
+// by measurement, on a launch that may be repeated (it writes, does not accumulate): gated against ungated.  The three probe
+// launches are timed under their own key ("spmm_xcd_probe"), outside the caller's "spmm" region.
+static int xcd_probe(dory_ctx *c, const SpmmArgs &a, const BlockedAdj &S, const float *row_scale, const SweepLaunch &sw, bool bf16) {
+    struct Ev3 {   // destroyed on every way out (HIPCK returns)
+        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+        ~Ev3() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    Timed tp(c, "spmm_xcd_probe", c->compute);
+    for (auto &x : ev.e) HIPCK(c, hipEventCreate(&x));
+    const uint32_t hi = sw.two ? S.nb_local : S.nb, gated = sw.sflags & ~8u;
+    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16));   // (warm: layout, code)
+    HIPCK(c, hipEventRecord(ev.e[0], c->compute));
+    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated, c->scratch, 0, bf16));
+    HIPCK(c, hipEventRecord(ev.e[1], c->compute));
+    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16));
+    HIPCK(c, hipEventRecord(ev.e[2], c->compute));
+    HIPCK(c, hipEventSynchronize(ev.e[2]));
+    (void)hipEventElapsedTime(&c->xcd_gated_ms, ev.e[0], ev.e[1]);
+    (void)hipEventElapsedTime(&c->xcd_ungated_ms, ev.e[1], ev.e[2]);
+    c->xcd_policy = c->xcd_gated_ms <= c->xcd_ungated_ms ? 0 : 8;
+    return DORY_OK;
+}
+
+constexpr int SPMM_NOT_MINE = 1;   // spmm_k1s / spmm_k1b: this aggregation goes to the next kernel family
+
+// K1s: register accumulators, every workgroup sweeps all source blocks of its own even layout (spmm.hip).
+static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *row_scale, Bf16Rows &bf) {
+    const int group = blk_group_for(c, a.ld);
+    int rc = ensure_sweep(c, A, group);
+    if (rc) return rc;
+    const DerivedAdj &S = A.swp;
+    if (S.na || !sweep_supported(a, S, group)) return SPMM_NOT_MINE;
+    const bool bf16 = bf.on();
+    SweepLaunch sw = sweep_launch(c, S, a.ld, group, a.xg != nullptr, (int)c->opt["spmm_sweep_rows"]);
+    if ((rc = ensure_partial(c, sw.need, "sweep counters"))) return rc;   // (K1s may still size its counters here, outside a recording)
+    sw.done = reinterpret_cast<uint32_t *>(c->partial);
+    if (S.nslots && (rc = ensure_scratch(c, (size_t)S.nslots * a.ld * sizeof(float)))) return rc;   // pieces of split rows
+    c->last_spmm_unit = row_scale != nullptr;
+    sw.ctl.force_r = (int)c->opt["spmm_sweep_rows"];
+    sw.ctl.pair = (int)c->opt["spmm_sweep_pair"];
+    sw.ctl.loader = c->opt["spmm_sweep_loader"] != 0;
+    if ((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && !(c->opt["spmm_sweep_flags"] & 8) && c->xcd_policy < 0 &&
+        !c->capturing && !a.accumulate && !c->halo_pending) {
+        if ((rc = xcd_probe(c, a, S, row_scale, sw, bf16))) return rc;
+        sw.sflags = sweep_flags(c);   // (left undecided -- recording, accumulating caller: ungated, never a timeout)
+    }
+    Timed t(c, "spmm", c->compute);
+    if (bf16) c->bf16_gathers_k1s++;
+    auto sweep = [&](const SpmmArgs &x, uint32_t b_lo, uint32_t b_hi, uint32_t flags, uint32_t reserve) -> int {
+        HIPCK(c, launch_spmm_sweep(x, S, group, row_scale, sw.G, b_lo, b_hi, sw.done, c->compute, sw.ctl, flags, c->scratch, reserve, bf16));
+        return DORY_OK;
+    };
+    // under an exchange in flight the RCCL kernels need CUs of their own
+    const uint32_t reserve = c->halo_pending ? (uint32_t)c->opt["spmm_sweep_reserve_cus"] : 0u;
+    SpmmArgs a2 = a;   // the ghost-source blocks go on from the first launch's sums
+    a2.self_mode = 0;
+    a2.accumulate = 1;
+    rc = around_halo(c, sw.two, &bf, [&] { return sweep(a, 0, S.nb_local, sw.sflags, reserve); },
+                     [&] { return sw.two ? sweep(a2, S.nb_local, S.nb, sw.sflags | 2u, 0) : sweep(a, 0, S.nb, sw.sflags, 0); });
+    if (rc) return rc;
+    HIPCK(c, launch_spmm_sweep_combine(a, S, row_scale, c->scratch, c->compute, bf16));
+    return DORY_OK;
+}
+
+// K1b: partial rows per source block, then a reduce (spmm_blocked.hip).  No bf16 form.
+static int spmm_k1b(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *row_scale) {
+    const int group = blk_group_for(c, a.ld);
+    int rc = ensure_blocked(c, A, group);
+    if (rc) return rc;
+    const DerivedAdj &B = A.blk;
+    const size_t need = blocked_partial_bytes(a, B);
+    if (B.na || B.nb == 0 || need > ((size_t)48 << 30)) return SPMM_NOT_MINE;
+    c->last_spmm_unit = row_scale != nullptr;
+    if ((rc = ensure_partial(c, need, "partial buffer"))) return rc;
+    Timed t(c, "spmm", c->compute);
+    auto part = [&](uint32_t b_lo, uint32_t b_hi) -> int {
+        HIPCK(c, launch_spmm_blocked_part(a, B, c->partial, group, row_scale != nullptr, b_lo, b_hi, c->compute));
+        return DORY_OK;
+    };
+    // source blocks that contain local rows only do not depend on the exchange in
+    // flight: they run first, the ghost blocks after the comm stream's event
+    const uint32_t nb_local = std::min(B.nb, c->N / B.SB);
+    const bool split = (c->halo_pending || c->opt["spmm_blk_force_split"]) && nb_local > 0 && nb_local < B.nb;
+    if ((rc = around_halo(c, split, nullptr, [&] { return part(0, nb_local); }, [&] { return part(split ? nb_local : 0, B.nb); }))) return rc;
+    if (B.nchunks) {   // hubs: the remainder of the (block,row) segments K1b stopped in
+        if ((rc = ensure_scratch(c, (size_t)B.nchunks * a.ld * sizeof(float)))) return rc;
+        HIPCK(c, launch_spmm_blocked_long_segments(a, B, c->partial, row_scale != nullptr, c->scratch, c->compute));
+    }
+    HIPCK(c, launch_spmm_blocked_reduce(a, B, c->partial, row_scale, c->compute));
+    return DORY_OK;
+}
+
+// K1: the row gather with per-edge values (spmm.hip), whatever the graph.
+static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
+    if (!a.val) return fail(c, DORY_ERR_ARG, "spmm: no edge values");
+    const bool bf16 = bf.on();
+    if (bf16) c->bf16_gathers_k1++;
+    auto launch = [&](const SpmmArgs &x) -> int {
+        HIPCK(c, launch_spmm(x, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
+        return DORY_OK;
+    };
+    const LongRowsDev &longRows = A.long_rows;
+    if (longRows.nchunks) {   // hubs: K1 stops after LONG_ROW_CLAMP edges of a row, workgroup-per-chunk kernels do the rest
+        int rc = ensure_scratch(c, (size_t)longRows.nchunks * a.ld * sizeof(float));
+        if (rc) return rc;
+        a.row_clamp = LONG_ROW_CLAMP;
+    }
+    const bool in_flight = c->halo_pending || c->opt["spmm_blk_force_split"];
+    // K1 under an exchange in flight.  GCN partitions with ghosts hold a local-first copy of the edges (ctx.hpp: EdgeSplit): one
+    // launch sums every row's local-source edges beside the exchange, a second one goes on from those sums with the ghost-
+    // source edges (boundary rows only) -- the additions happen in the same order as in ONE launch over the copy, which is what
+    // runs when nothing is in flight: overlapped and sequential schedule give the same bits.
+    const EdgeSplit &es = A.edge_split;
+    // (layer 0's forward aggregation reads ghost rows that came from a file: no exchange ever precedes it, in either schedule,
+    // so it keeps the reference's edge order -- the local-first copy costs the 300-float Amazon launch a few per cent)
+    if (es.idx && a.xg && a.val == A.val && !longRows.nchunks && !a.accumulate && c->opt["spmm_edge_split"] && !c->agg_static_ghosts) {
+        a.idx = es.idx;
+        a.val = es.val;
+        Timed t(c, "spmm", c->compute);
+        SpmmArgs p1 = a, p2 = a;
+        p1.ptr_end = es.mid;
+        p2.ptr = es.mid;
+        p2.ptr_end = a.ptr + 1;
+        p2.self_mode = 0;
+        p2.accumulate = 2;
+        const bool boundary = !A.split || A.n_interior < c->N;   // rows without a ghost source are done
+        if (A.split && boundary) { p2.order = A.split + A.n_interior; p2.rows = c->N - A.n_interior; }
+        return around_halo(c, in_flight, &bf, [&] { return launch(p1); },
+                           [&] { return !in_flight ? launch(a) : boundary ? launch(p2) : (int)DORY_OK; });
+    }
+    // (other cases -- GAT's per-epoch edge values, hub rows: the rows whose sources are all local run first, the rows that read
+    // ghost rows after the comm stream's event)
+    const bool split_rows = in_flight && A.split && A.n_interior > 0 && A.n_interior < c->N && !longRows.nchunks;
+    Timed t(c, "spmm", c->compute);
+    SpmmArgs interior = a, boundary = a;
+    if (split_rows) {
+        interior.order = A.split;
+        interior.rows = A.n_interior;
+        boundary.order = A.split + A.n_interior;
+        boundary.rows = c->N - A.n_interior;
+    }
+    return around_halo(c, split_rows, &bf, [&] { return launch(interior); }, [&]() -> int {
+        if (split_rows) return launch(boundary);
+        int rc = launch(a);
+        if (!rc && longRows.nchunks) HIPCK(c, launch_spmm_long_rows(a, longRows, c->scratch, c->compute, bf16));
+        return rc;
+    });
+}
 
 // One aggregation.  Edge weights come from `val` (any per-edge array, K1), or -- when
 // `val` is the adjacency's own static array -- from the source-blocked copy (K1b), or are
@@ -141,7 +350,7 @@ static int bf16_convert(dory_ctx *c, const Tensor &t, uint64_t first_row) {
 // bf16 (option gcn_bf16_gather, GCN only): every row read -- self row, local and ghost rows -- is rounded to bf16 first;
 // edge values, norm, the sums and `out` stay fp32, the sums in the order of the fp32 path.  K1s and K1 have bf16 forms,
 // K1b has none: where fp32 would take K1b, bf16 takes K1.
-static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &xl, Tensor *xg, Tensor &out,
+static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tensor &xl, Tensor *xg, Tensor &out,
                 uint32_t F, int accumulate, const float *row_scale = nullptr, bool bf16 = false) {
     if (xl.ld != out.ld || (xg && xg->rows && xg->ld != xl.ld) || xl.cols != F)
         return fail(c, DORY_ERR_ARG, "spmm: tensor shapes disagree (F=%u ld %u/%u)", F, xl.ld, out.ld);
@@ -150,552 +359,340 @@ static int spmm(dory_ctx *c, bool csc, const float *val, int self_mode, Tensor &
     c->last_spmm_unit = false;
     SpmmArgs a{};
     a.N = c->N; a.F = F; a.ld = xl.ld;
-    a.ptr = csc ? c->colPtr : c->rowPtr;
-    a.idx = csc ? c->rowIdx : c->colIdx;
+    a.ptr = A.ptr;
+    a.idx = A.idx;
     a.val = val;
     a.self_scale = c->norm;
     a.self_mode = self_mode;
     a.xl = xl.d; a.xg = (xg && xg->rows) ? xg->d : nullptr; a.out = out.d;   // nullptr: no ghost rows (the blocked kernel then skips the select)
-    const uint64_t ghost_rows = a.xg ? xg->rows : 0;
-    if (bf16) {
-        // the kernels' xl / xg point at bf16 rows from here on; the local rows are converted now, the ghost rows only once
-        // the exchange that writes them has landed (halo() below, at every wait_halo of this function)
-        Tensor local = xl;
-        local.rows = c->N;
-        int rc = bf16_shadow(c, (uint64_t)c->N + ghost_rows, a.ld);
-        if (!rc) rc = bf16_convert(c, local, 0);
+    Bf16Rows bf;
+    if (bf16) {   // the kernels' xl / xg point at bf16 rows from here on
+        int rc = bf.begin(c, xl, xg, a.xg ? xg->rows : 0, "gcn_bf16_gather");
         if (rc) return rc;
-        a.xl = reinterpret_cast<const float *>(c->bf16_rows);
-        a.xg = ghost_rows ? reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * a.ld) : nullptr;
+        a.xl = bf.xl;
+        a.xg = bf.xg;
     }
-    auto halo = [&]() -> int {
-        int rc = wait_halo(c);
-        if (!rc && bf16 && ghost_rows) rc = bf16_convert(c, *xg, c->N);
-        return rc;
-    };
     a.accumulate = accumulate;
-    a.order = (c->opt["spmm_order"] >= 2 || (c->opt["spmm_order"] == 1 && (csc ? c->skewIn : c->skewOut))) ? (csc ? c->orderIn : c->orderOut) : nullptr;
-    const bool static_vals = val == (csc ? c->cscVal : c->csrVal) && !(c->gnn == DORY_GAT && csc);  // GAT rewrites cscVal
-    if (c->opt["spmm_variant"] == 2 && (static_vals || row_scale) && c->N > 0 && a.ld >= 32) {
-        // K1s: register accumulators, every workgroup sweeps all source blocks of its own even layout (spmm.hip).
-        const int group = blk_group_for(c, a.ld);
-        int rc = ensure_sweep(c, csc, group);
-        if (rc) return rc;
-        BlockedAdj &S = csc ? c->swpIn : c->swpOut;
-        if (!(csc ? c->swpIn_na : c->swpOut_na) && sweep_supported(a, S, group)) {
-            const uint32_t G = std::min<uint32_t>(32u, c->cus_per_xcd);
-            // With ghost rows the blocks that hold local rows only always run as a launch of their own (they do not
-            // depend on an exchange in flight), so the overlapped and the sequential schedule are the same arithmetic.
-            const bool two = a.xg != nullptr && S.nb_local > 0 && S.nb_local < S.nb;
-            const int force_r = (int)c->opt["spmm_sweep_rows"];
-            const size_t need = sweep_scratch_bytes(S, a.ld, group, G, two ? std::max(S.nb_local, S.nb - S.nb_local) : S.nb, force_r);
-            if (need > c->partial_bytes) {
-                if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: sweep counters would have to grow while recording");
-                HIPCK(c, hipStreamSynchronize(c->compute));
-                if (c->partial) (void)hipFree(c->partial);
-                c->partial = nullptr;
-                c->partial_bytes = 0;
-                HIPCK(c, hipMalloc((void **)&c->partial, need));
-                c->partial_bytes = need;
-            }
-            if (S.nslots && (rc = ensure_scratch(c, (size_t)S.nslots * a.ld * sizeof(float)))) return rc;   // pieces of split rows
-            c->last_spmm_unit = row_scale != nullptr;
-            uint32_t *done = reinterpret_cast<uint32_t *>(c->partial);
-            uint32_t sflags = (uint32_t)c->opt["spmm_sweep_flags"];
-            SweepCtl ctl;
-            ctl.force_r = force_r;
-            ctl.pair = (int)c->opt["spmm_sweep_pair"];
-            ctl.stat = c->sweep_stat;
-            ctl.loader = c->opt["spmm_sweep_loader"] != 0;
-            SpmmArgs a1 = a;          // the pieces' slots are written, not accumulated, by the first launch
-            // placement check failed (ctx.hpp): gates would synchronise workgroups that do not share an L2.  Decide once, by
-            // measurement, on a launch that may be repeated (it writes, does not accumulate): gated against ungated.  The
-            // three probe launches are timed under their own key ("spmm_xcd_probe"), outside the caller's "spmm" region.
-            if ((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && !(sflags & 8u)) {
-                if (c->xcd_policy < 0 && !c->capturing && !a.accumulate && !c->halo_pending) {
-                    struct Ev3 {   // destroyed on every way out (HIPCK returns)
-                        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-                        ~Ev3() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-                    } ev;
-                    Timed tp(c, "spmm_xcd_probe", c->compute);
-                    for (auto &x : ev.e) HIPCK(c, hipEventCreate(&x));
-                    const uint32_t hi = two ? S.nb_local : S.nb;
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags | 8u, c->scratch, 0, bf16));   // (warm: layout, code)
-                    HIPCK(c, hipEventRecord(ev.e[0], c->compute));
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags, c->scratch, 0, bf16));
-                    HIPCK(c, hipEventRecord(ev.e[1], c->compute));
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, hi, done, c->compute, ctl, sflags | 8u, c->scratch, 0, bf16));
-                    HIPCK(c, hipEventRecord(ev.e[2], c->compute));
-                    HIPCK(c, hipEventSynchronize(ev.e[2]));
-                    (void)hipEventElapsedTime(&c->xcd_gated_ms, ev.e[0], ev.e[1]);
-                    (void)hipEventElapsedTime(&c->xcd_ungated_ms, ev.e[1], ev.e[2]);
-                    c->xcd_policy = c->xcd_gated_ms <= c->xcd_ungated_ms ? 0 : 8;
-                }
-                sflags |= c->xcd_policy == 0 ? 0u : 8u;      // undecided (recording, accumulating caller): ungated, never a timeout
-            }
-            Timed t(c, "spmm", c->compute);
-            if (bf16) c->bf16_gathers_k1s++;
-            if (two) {
-                // under an exchange in flight the RCCL kernels need CUs of their own
-                const uint32_t reserve = c->halo_pending ? (uint32_t)c->opt["spmm_sweep_reserve_cus"] : 0u;
-                {
-                    Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
-                    HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, S.nb_local, done, c->compute, ctl, sflags, c->scratch, reserve, bf16));
-                }
-                if ((rc = halo())) return rc;
-                SpmmArgs a2 = a;
-                a2.self_mode = 0;
-                a2.accumulate = 1;
-                HIPCK(c, launch_spmm_sweep(a2, S, group, row_scale, G, S.nb_local, S.nb, done, c->compute, ctl, sflags | 2u, c->scratch, 0, bf16));
-            } else {
-                if ((rc = halo())) return rc;
-                HIPCK(c, launch_spmm_sweep(a1, S, group, row_scale, G, 0, S.nb, done, c->compute, ctl, sflags, c->scratch, 0, bf16));
-            }
-            HIPCK(c, launch_spmm_sweep_combine(a, S, row_scale, c->scratch, c->compute, bf16));
-            return DORY_OK;
-        }
-    }
-    if (c->opt["spmm_variant"] >= 1 && !bf16 && (static_vals || row_scale) && c->N > 0 && a.ld >= 32) {
-        const int group = blk_group_for(c, a.ld);
-        int rc = ensure_blocked(c, csc, group);
-        if (rc) return rc;
-        BlockedAdj &B = csc ? c->blkIn : c->blkOut;
-        const size_t need = blocked_partial_bytes(a, B);
-        if (!(csc ? c->blkIn_na : c->blkOut_na) && B.nb > 0 && need <= ((size_t)48 << 30)) {
-            c->last_spmm_unit = row_scale != nullptr;
-            if (need > c->partial_bytes) {
-                if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: partial buffer would have to grow while recording");
-                HIPCK(c, hipStreamSynchronize(c->compute));
-                if (c->partial) (void)hipFree(c->partial);
-                c->partial = nullptr;
-                c->partial_bytes = 0;
-                HIPCK(c, hipMalloc((void **)&c->partial, need));
-                c->partial_bytes = need;
-            }
-            Timed t(c, "spmm", c->compute);
-            // source blocks that contain local rows only do not depend on the exchange in
-            // flight: they run first, the ghost blocks after the comm stream's event
-            const uint32_t nb_local = std::min(B.nb, c->N / B.SB);
-            const bool split = (c->halo_pending || c->opt["spmm_blk_force_split"]) && nb_local > 0 && nb_local < B.nb;
-            if (split) {
-                {
-                    Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
-                    HIPCK(c, launch_spmm_blocked_part(a, B, c->partial, group, row_scale != nullptr, 0, nb_local, c->compute));
-                }
-                if ((rc = wait_halo(c))) return rc;
-                HIPCK(c, launch_spmm_blocked_part(a, B, c->partial, group, row_scale != nullptr, nb_local, B.nb, c->compute));
-            } else {
-                if ((rc = wait_halo(c))) return rc;
-                HIPCK(c, launch_spmm_blocked_part(a, B, c->partial, group, row_scale != nullptr, 0, B.nb, c->compute));
-            }
-            if (B.nchunks) {   // hubs: the remainder of the (block,row) segments K1b stopped in
-                if ((rc = ensure_scratch(c, (size_t)B.nchunks * a.ld * sizeof(float)))) return rc;
-                HIPCK(c, launch_spmm_blocked_long_segments(a, B, c->partial, row_scale != nullptr, c->scratch, c->compute));
-            }
-            HIPCK(c, launch_spmm_blocked_reduce(a, B, c->partial, row_scale, c->compute));
-            return DORY_OK;
-        }
-    }
-    if (!val) return fail(c, DORY_ERR_ARG, "spmm: no edge values");
-    if (bf16) c->bf16_gathers_k1++;
-    const LongRowsDev &longRows = csc ? c->longIn : c->longOut;
-    if (longRows.nchunks) {   // hubs: K1 stops after LONG_ROW_CLAMP edges of a row, workgroup-per-chunk kernels do the rest
-        int rc = ensure_scratch(c, (size_t)longRows.nchunks * a.ld * sizeof(float));
-        if (rc) return rc;
-        a.row_clamp = LONG_ROW_CLAMP;
-    }
-    // K1 under an exchange in flight.  GCN partitions with ghosts hold a local-first copy of the edges (ctx.hpp: EdgeSplit): one
-    // launch sums every row's local-source edges beside the exchange, a second one goes on from those sums with the ghost-
-    // source edges (boundary rows only) -- the additions happen in the same order as in ONE launch over the copy, which is what
-    // runs when nothing is in flight: overlapped and sequential schedule give the same bits.
-    uint32_t *split = csc ? c->splitIn : c->splitOut;
-    const uint32_t nInt = csc ? c->nIntIn : c->nIntOut;
-    const EdgeSplit &es = csc ? c->esIn : c->esOut;
-    // (layer 0's forward aggregation reads ghost rows that came from a file: no exchange ever precedes it, in either schedule,
-    // so it keeps the reference's edge order -- the local-first copy costs the 300-float Amazon launch a few per cent)
-    if (es.idx && a.xg && val == (csc ? c->cscVal : c->csrVal) && !longRows.nchunks && !a.accumulate && c->opt["spmm_edge_split"] &&
-        !c->agg_static_ghosts) {
-        a.idx = es.idx;
-        a.val = es.val;
-        Timed t(c, "spmm", c->compute);
-        if (c->halo_pending || c->opt["spmm_blk_force_split"]) {
-            SpmmArgs p1 = a;
-            p1.ptr_end = es.mid;
-            {
-                Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
-                HIPCK(c, launch_spmm(p1, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
-            }
-            int rc = halo();
-            if (rc) return rc;
-            SpmmArgs p2 = a;
-            p2.ptr = es.mid;
-            p2.ptr_end = a.ptr + 1;
-            p2.self_mode = 0;
-            p2.accumulate = 2;
-            if (split && nInt < c->N) { p2.order = split + nInt; p2.rows = c->N - nInt; }   // rows without a ghost source are done
-            if (!split || nInt < c->N) HIPCK(c, launch_spmm(p2, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
-            return DORY_OK;
-        }
-        int rc = halo();
-        if (rc) return rc;
-        HIPCK(c, launch_spmm(a, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
-        return DORY_OK;
-    }
-    // (other cases -- GAT's per-epoch edge values, hub rows: the rows whose sources are all local run first, the rows that read
-    // ghost rows after the comm stream's event)
-    const bool split_rows = (c->halo_pending || c->opt["spmm_blk_force_split"]) && split && nInt > 0 && nInt < c->N &&
-                            !longRows.nchunks;
-    Timed t(c, "spmm", c->compute);
-    if (split_rows) {
-        SpmmArgs part = a;
-        part.order = split;
-        part.rows = nInt;
-        {
-            Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
-            HIPCK(c, launch_spmm(part, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
-        }
-        int rc = halo();
-        if (rc) return rc;
-        part.order = split + nInt;
-        part.rows = c->N - nInt;
-        HIPCK(c, launch_spmm(part, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
-        return DORY_OK;
-    }
-    {
-        int rc = halo();
-        if (rc) return rc;
-    }
-    HIPCK(c, launch_spmm(a, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
-    if (longRows.nchunks) HIPCK(c, launch_spmm_long_rows(a, longRows, c->scratch, c->compute, bf16));
-    return DORY_OK;
+    a.order = (c->opt["spmm_order"] >= 2 || (c->opt["spmm_order"] == 1 && A.skew)) ? A.order : nullptr;
+    // GAT rewrites forwardAdj's values (the record is recognised by identity: A is a reference into c->adj, never a copy)
+    const bool static_vals = val == A.val && !(c->gnn == DORY_GAT && &A == &c->adj[ADJ_IN]);
+    const bool layouts = (static_vals || row_scale) && c->N > 0 && a.ld >= 32;   // K1s / K1b gather through copies of the static adjacency
+    int rc = SPMM_NOT_MINE;
+    if (layouts && c->opt["spmm_variant"] == 2) rc = spmm_k1s(c, A, a, row_scale, bf);
+    if (rc == SPMM_NOT_MINE && layouts && c->opt["spmm_variant"] >= 1 && !bf16) rc = spmm_k1b(c, A, a, row_scale);
+    if (rc == SPMM_NOT_MINE) rc = spmm_k1(c, A, a, bf);
+    return rc;
 }
 
+// ---------------------------------------------------------------------------------------
+// The bodies of dory_aggregate, one per model.  They run under its lock; a missing tensor is reported under its name.
+#define AGG_NEED(ptr, l, nm) NEED_IN("dory_aggregate", ptr, l, nm)
 
-}  // namespace dory
-
-using namespace dory;
-
-extern "C" {
-
-int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
-    CHECK_CTX(c);
-    if (!c->prealloc) return fail(c, DORY_ERR_ARG, "aggregate: preallocate first");
-    if (c->gnn == DORY_GCN) {  // Engine::aggregateGCN (gcn_ops.cpp:130-191)
-        // opt-in "gcn_bf16_gather" (no reference counterpart): 1 = the forward aggregations read bf16 rows, 2 = the backward
-        // ones too (spmm(): fp32 sums, same order).  K1b has no bf16 form: an explicit spmm_variant = 1 is refused
-        const int64_t bfm = c->opt["gcn_bf16_gather"];
-        if (bfm && c->opt["spmm_variant"] == 1)
-            return fail(c, DORY_ERR_ARG, "aggregate: gcn_bf16_gather = %lld with spmm_variant = 1 (K1b has no bf16 form: spmm_variant 0 or 2)",
-                        (long long)bfm);
-        const bool bf_fwd = bfm >= 1, bf_bwd = bfm >= 2;
-        if (dir == DORY_FORWARD) {
-            if (layer >= c->L) return fail(c, DORY_ERR_ARG, "aggregate: layer %u out of range", layer);
-            Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
-            NEED(fg, layer, "fg");
-            NEED(ah, layer, "ah");
-            if (!in) return fail(c, DORY_ERR_ARG, "aggregate: input tensor missing");
-            if (tf_layer(c, layer)) {   // z_l = A (in_l W_l): gather d[l+1]-wide
-                NEED(xw, layer, "xw"); NEED(fgxw, layer, "fgxw"); NEED(z, layer, "z");
-                if (layer == 0) {   // the input and its ghost rows are static: transform both here
-                    Tensor &W = c->weights[0]["w"];
-                    int rc = gemm(c, 0, 0, c->N, c->dims[1], c->dims[0], *in, W, *xw);
-                    if (!rc && c->Gsrc) rc = gemm(c, 0, 0, c->Gsrc, c->dims[1], c->dims[0], *fg, W, *fgxw);
-                    if (rc) return rc;
-                }   // deeper layers: apply_vertex(l-1) left xw@l, the forward exchange of layer l its ghost rows
-                return spmm(c, true, c->cscVal, 1, *xw, fgxw, *z, c->dims[layer + 1], 0, nullptr, bf_fwd);
-            }
-            // Opt-in "gcn_cache_ah0" (no reference counterpart; the reference recomputes it every epoch and so does the
-            // default here): in full-graph training ah@0 = A_hat [x ; fg@0] is a constant of the run -- x and fg@0 come
-            // from files, the adjacency never changes -- and with 288 GB of HBM it can simply stay.  The aggregation of
-            // layer 0 is skipped while nothing it reads has been written through this ABI since it was last computed.
-            if (layer == 0 && c->opt["gcn_cache_ah0"] && !c->capturing) {
-                if (c->ah0_valid) { c->ah0_skips++; return DORY_OK; }
-                c->agg_static_ghosts = true;
-                int rc = spmm(c, true, c->cscVal, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd);
-                c->agg_static_ghosts = false;
-                c->ah0_valid = rc == DORY_OK;
-                return rc;
-            }
-            if (layer == 0) c->ah0_valid = false;
-            c->agg_static_ghosts = layer == 0;
-            const int src_ = spmm(c, true, c->cscVal, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd);
-            c->agg_static_ghosts = false;
-            return src_;
+// Engine::aggregateGCN (gcn_ops.cpp:130-191)
+static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
+    Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
+    // opt-in "gcn_bf16_gather" (no reference counterpart): 1 = the forward aggregations read bf16 rows, 2 = the backward
+    // ones too (spmm(): fp32 sums, same order).  K1b has no bf16 form: an explicit spmm_variant = 1 is refused
+    const int64_t bfm = c->opt["gcn_bf16_gather"];
+    if (bfm && c->opt["spmm_variant"] == 1)
+        return fail(c, DORY_ERR_ARG, "aggregate: gcn_bf16_gather = %lld with spmm_variant = 1 (K1b has no bf16 form: spmm_variant 0 or 2)",
+                    (long long)bfm);
+    const bool bf_fwd = bfm >= 1, bf_bwd = bfm >= 2;
+    if (dir == DORY_FORWARD) {
+        if (layer >= c->L) return fail(c, DORY_ERR_ARG, "aggregate: layer %u out of range", layer);
+        Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
+        AGG_NEED(fg, layer, "fg");
+        AGG_NEED(ah, layer, "ah");
+        if (!in) return fail(c, DORY_ERR_ARG, "aggregate: input tensor missing");
+        if (tf_layer(c, layer)) {   // z_l = A (in_l W_l): gather d[l+1]-wide
+            AGG_NEED(xw, layer, "xw"); AGG_NEED(fgxw, layer, "fgxw"); AGG_NEED(z, layer, "z");
+            if (layer == 0) {   // the input and its ghost rows are static: transform both here
+                Tensor &W = c->weights[0]["w"];
+                int rc = gemm(c, 0, 0, c->N, c->dims[1], c->dims[0], *in, W, *xw);
+                if (!rc && In.ghosts) rc = gemm(c, 0, 0, In.ghosts, c->dims[1], c->dims[0], *fg, W, *fgxw);
+                if (rc) return rc;
+            }   // deeper layers: apply_vertex(l-1) left xw@l, the forward exchange of layer l its ghost rows
+            return spmm(c, In, In.val, 1, *xw, fgxw, *z, c->dims[layer + 1], 0, nullptr, bf_fwd);
         }
-        if (tf_layer(c, layer)) {   // u_l = A^T g_l (ghost rows of g_l: backward exchange of layer l); dW_l = in_l^T u_l
-            NEED(g, layer, "g"); NEED(bgg, layer, "bgg"); NEED(u, layer, "u");
-            Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
-            if (!in) return fail(c, DORY_ERR_ARG, "aggregate: input tensor missing");
-            const uint32_t Fin = c->dims[layer], Fout = c->dims[layer + 1];
-            int rc = spmm(c, false, c->csrVal, 1, *g, bgg, *u, Fout, 0, nullptr, bf_bwd);
-            if (rc) return rc;
-            if ((rc = gemm(c, 1, 0, Fin, Fout, c->N, *in, *u, c->wgrads[layer]["w"]))) return rc;
-            if (layer == 0) return DORY_OK;
-            NEED(aTg, layer - 1, "aTg");   // the gradient handed down: A^T (g_l W_l^T) = u_l W_l^T
-            return gemm(c, 0, 1, c->N, Fin, Fout, *u, c->weights[layer]["w"], *aTg);
-        }
-        if (layer == 0 || layer >= c->L) return fail(c, DORY_ERR_ARG, "aggregate backward: layer %u out of range", layer);
-        NEED(grad, layer, "grad");
-        NEED(bg, layer - 1, "bg");
-        NEED(aTg, layer - 1, "aTg");
-        return spmm(c, false, c->csrVal, 1, *grad, bg, *aTg, c->dims[layer], 0, nullptr, bf_bwd);
+        // Opt-in "gcn_cache_ah0" (no reference counterpart; the reference recomputes it every epoch and so does the
+        // default here): in full-graph training ah@0 = A_hat [x ; fg@0] is a constant of the run -- x and fg@0 come
+        // from files, the adjacency never changes -- and with 288 GB of HBM it can simply stay.  The aggregation of
+        // layer 0 is skipped while nothing it reads has been written through this ABI since it was last computed.
+        const bool cache = layer == 0 && c->opt["gcn_cache_ah0"] && !c->capturing;
+        if (cache && c->ah0_valid) { c->ah0_skips++; return DORY_OK; }
+        if (layer == 0) c->ah0_valid = false;
+        c->agg_static_ghosts = layer == 0;
+        const int rc = spmm(c, In, In.val, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd);
+        c->agg_static_ghosts = false;
+        if (cache) c->ah0_valid = rc == DORY_OK;
+        return rc;
     }
-    // Engine::aggregateGAT (gat_ops.cpp:173-243): tensors live at layer-1
-    if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "aggregate GAT: layer %u out of range", layer);
-    const uint32_t fl = layer - 1;
-    if (c->gnn == DORY_GATMH) {  // extension: edge softmax + weighted sum, and its backward
-        const uint32_t K = c->heads[fl];
-        const bool last = fl == c->L - 1;
-        NEED(z, fl, "z"); NEED(el, fl, "el"); NEED(er, fl, "er"); NEED(m, fl, "m"); NEED(den, fl, "den"); NEED(o, fl, "o");
-        const uint32_t D = z->cols / K;
-        // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
-        // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
-        // Only the sweep forms have bf16 kernels: where the dispatch below would leave them the call is refused, never run in fp32
-        const int64_t bfm = c->opt["gatmh_bf16_gather"];
-        if (dir == DORY_FORWARD) {
-            {
-                Timed t(c, "spmm", c->compute);
-                const BlockedAdj &Bf = gatmh_blocked_for(c, true, z->ld);
-                const bool blocked = c->opt["gatmh_blocked"] && c->blkIn_built && !c->blkIn_na && Bf.nb > 0 &&
-                                     (D % 4 == 0 || K == 1) &&
-                                     (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
-                NEED(fgz, fl, "fg_z"); NEED(fgel, fl, "fg_el");
-                const BlockedAdj &Sf = c->swpIn;
-                const int shl = gatmh_sweep_hl(K, D, z->ld);
-                Tensor *op = find(c, fl, "op"), *dpos = find(c, fl, "dpos");
-                // (the same addressing test the launchers make -- 32-bit byte offsets through the buffer resource -- so that a
-                // partition they would refuse takes the blocked kernels instead of failing, as spmm() does)
-                SpmmArgs sa{};
-                sa.N = c->N; sa.ld = z->ld;
-                const bool sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && c->swpIn_built && !c->swpIn_na && Sf.nb > 0 &&
-                                   shl != 0 && op && dpos && sweep_supported(sa, Sf, z->ld >= 128 ? 32 : 16);
-                const bool bf16 = bfm >= 1;
-                if (bf16 && !sweep)
-                    return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
-                                (long long)bfm,
-                                !c->opt["gatmh_sweep"] ? "gatmh_sweep = 0" :
-                                c->opt["spmm_variant"] != 2 ? "spmm_variant is not 2" :
-                                !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
-                                (!op || !dpos) ? "tensors op / dpos missing" : "the sweep layout of the in-edges does not apply to this graph");
-                if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 0;
-                if (sweep) {
-                    // K1s's skeleton: sums in registers over all source blocks, single-pass softmax against the upper-bound shift
-                    int src_ = ensure_scratch(c, gatmh_sweep_scratch_bytes(Sf, c->N, z->ld, el->ld));
-                    if (src_) return src_;
-                    if (bf16 && (src_ = bf16_shadow(c, (uint64_t)c->N + c->Gsrc, z->ld, "gatmh_bf16_gather"))) return src_;
-                    const uint32_t G = std::min<uint32_t>(32u, c->cus_per_xcd);
-                    const bool two = c->Gsrc > 0 && Sf.nb_local > 0 && Sf.nb_local < Sf.nb;
-                    const int sgroup = z->ld >= 128 ? 32 : 16;
-                    const size_t need = sweep_scratch_bytes(Sf, z->ld, sgroup, G, two ? std::max(Sf.nb_local, Sf.nb - Sf.nb_local) : Sf.nb, gatmh_sweep_rows(Sf, sgroup, shl, 0));
-                    if (need > c->partial_bytes) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
-                    SweepCtl ctl;
-                    ctl.stat = c->sweep_stat;
-                    uint32_t *done = reinterpret_cast<uint32_t *>(c->partial);
-                    const uint32_t sflags = (uint32_t)c->opt["spmm_sweep_flags"] |
-                                            (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
-                    const float *a_l = c->weights[fl]["a_l"].d;
-                    // the rows the sweep gathers: z / fg_z, or (bf16) their rounded copies in the shadow buffer -- the local rows
-                    // converted now, the ghost rows once their exchange has landed (halo() below)
-                    const float *zs = z->d, *zgs = fgz->d;
-                    if (bf16) {
-                        Tensor local = *z;
-                        local.rows = c->N;
-                        if ((src_ = bf16_convert(c, local, 0))) return src_;
-                        zs = reinterpret_cast<const float *>(c->bf16_rows);
-                        zgs = reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * z->ld);
-                        c->gatmh_bf16_gathers_fwd++;
-                    }
-                    auto halo = [&]() -> int {
-                        int rc = wait_halo(c);
-                        if (!rc && bf16 && c->Gsrc) rc = bf16_convert(c, *fgz, c->N);
-                        return rc;
-                    };
-                    HIPCK(c, launch_gatmh_sweep_begin(c->N, c->Gsrc, K, z->ld, el->ld, Sf, el->d, fgel->d, c->scratch, c->compute));
-                    if (two) {
-                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, G, 0,
-                                                                 Sf.nb_local, false, done, ctl, sflags, c->compute, el->d, fgel->d, bf16));
-                        if ((src_ = halo())) return src_;
-                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, G,
-                                                                 Sf.nb_local, Sf.nb, true, done, ctl, sflags, c->compute, el->d, fgel->d, bf16));
-                    } else {
-                        if ((src_ = halo())) return src_;
-                        HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, c->Gsrc ? zgs : nullptr, er->d, a_l, o->d,
-                                                                 op->d, c->scratch, G, 0, Sf.nb, false, done, ctl, sflags, c->compute, el->d, fgel->d, bf16));
-                    }
-                    HIPCK(c, launch_gatmh_forward_sweep_finish(c->N, K, D, z->ld, el->ld, c->colPtr, c->rowIdx, Sf, z->d, fgz->d, el->d, fgel->d,
-                                                               er->d, o->d, op->d, m->d, den->d, dpos->d, c->scratch, c->compute, bf16));
-                    if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
-                }
-                else if (blocked) {
-                    // "gatmh_fused_stats" (default 1): the blocks' own online softmax + a merge in the reduce kernel instead
-                    // of a statistics pass over all edges first; the blocks' (m_b, den_b) live in the scratch buffer
-                    float *stat_partial = nullptr;
-                    if (c->opt["gatmh_fused_stats"]) {
-                        int src_ = ensure_scratch(c, (size_t)2 * Bf.nb * c->N * el->ld * sizeof(float));
-                        if (src_) return src_;
-                        stat_partial = c->scratch;
-                    }
-                    HIPCK(c, launch_gatmh_forward_blocked(c->N, K, D, z->ld, el->ld, c->colPtr, c->rowIdx, Bf, z->d,
-                                                          fgz->d, el->d, fgel->d, er->d, o->d, m->d, den->d, c->partial,
-                                                          c->Gsrc > 0, c->compute, stat_partial,
-                                                          c->opt["gatmh_el_on_the_fly"] ? c->weights[fl]["a_l"].d : nullptr));
-                }
-                else if (c->numNodes > 1)
-                    return fail(c, DORY_ERR_ARG, "multi-head GAT: a partitioned run needs the source-blocked kernels (gatmh_blocked = 1, K*D a shape they cover)");
-                else
-                    HIPCK(c, launch_gatmh_forward(c->N, K, D, z->ld, el->ld, c->colPtr, c->rowIdx, z->d, el->d, er->d,
-                                                  o->d, m->d, den->d, c->compute));
-            }
-            Timed t(c, "loss", c->compute);
-            if (!last) {
-                NEED(hn, fl + 1, "h");
-                HIPCK(c, launch_gatmh_elu(c->N, o->cols, o->d, o->ld, hn->d, hn->ld, c->compute));
-            } else {
-                NEED(lg, fl, "logits");
-                HIPCK(c, launch_gatmh_head_mean(c->N, K, lg->cols, o->d, o->ld, lg->d, lg->ld, c->compute));
-            }
-            return DORY_OK;
-        }
-        NEED(dO, fl, "do"); NEED(dz, fl, "dz"); NEED(tt, fl, "t"); NEED(del, fl, "del"); NEED(der, fl, "der");
-        NEED(st, fl, "st"); NEED(fgz, fl, "fg_z"); NEED(fgel, fl, "fg_el"); NEED(bgdo, fl, "bg_do"); NEED(bgst, fl, "bg_st");
-        const int64_t phase = c->opt["gatmh_bwd_phase"];   // 0: whole sweep; 1 / 2: one phase (caller moves the ghost rows)
-        // The sweep forms (gat_mh_sweep.hip).  Destination side: when this layer's forward ran on the skeleton it left the
-        // positive-branch sums, and t / der / st come from a row-wise kernel -- no edge pass.  Source side: the sweep over the
-        // out-edges' layout.  Either falls back to the blocked kernels on its own (same m / den / st semantics).
-        const int shl = gatmh_sweep_hl(K, D, z->ld);
+    if (tf_layer(c, layer)) {   // u_l = A^T g_l (ghost rows of g_l: backward exchange of layer l); dW_l = in_l^T u_l
+        AGG_NEED(g, layer, "g"); AGG_NEED(bgg, layer, "bgg"); AGG_NEED(u, layer, "u");
+        Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
+        if (!in) return fail(c, DORY_ERR_ARG, "aggregate: input tensor missing");
+        const uint32_t Fin = c->dims[layer], Fout = c->dims[layer + 1];
+        int rc = spmm(c, Out, Out.val, 1, *g, bgg, *u, Fout, 0, nullptr, bf_bwd);
+        if (rc) return rc;
+        if ((rc = gemm(c, 1, 0, Fin, Fout, c->N, *in, *u, c->wgrads[layer]["w"]))) return rc;
+        if (layer == 0) return DORY_OK;
+        AGG_NEED(aTg, layer - 1, "aTg");   // the gradient handed down: A^T (g_l W_l^T) = u_l W_l^T
+        return gemm(c, 0, 1, c->N, Fin, Fout, *u, c->weights[layer]["w"], *aTg);
+    }
+    if (layer == 0 || layer >= c->L) return fail(c, DORY_ERR_ARG, "aggregate backward: layer %u out of range", layer);
+    AGG_NEED(grad, layer, "grad");
+    AGG_NEED(bg, layer - 1, "bg");
+    AGG_NEED(aTg, layer - 1, "aTg");
+    return spmm(c, Out, Out.val, 1, *grad, bg, *aTg, c->dims[layer], 0, nullptr, bf_bwd);
+}
+
+// The multi-head GAT extension: edge softmax + weighted sum.
+// opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
+// bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
+// Only the sweep forms have bf16 kernels: where the dispatch below would leave them the call is refused, never run in fp32
+static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
+    Adjacency &In = c->adj[ADJ_IN];
+    const uint32_t K = c->heads[fl];
+    AGG_NEED(z, fl, "z"); AGG_NEED(el, fl, "el"); AGG_NEED(er, fl, "er"); AGG_NEED(m, fl, "m"); AGG_NEED(den, fl, "den"); AGG_NEED(o, fl, "o");
+    const uint32_t D = z->cols / K;
+    const int64_t bfm = c->opt["gatmh_bf16_gather"];
+    {
+        Timed t(c, "spmm", c->compute);
+        const BlockedAdj &Bf = gatmh_blocked_for(In, z->ld);
+        const bool blocked = c->opt["gatmh_blocked"] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
+                             (D % 4 == 0 || K == 1) &&
+                             (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
+        AGG_NEED(fgz, fl, "fg_z"); AGG_NEED(fgel, fl, "fg_el");
+        const DerivedAdj &Sf = In.swp;
+        const int shl = gatmh_sweep_hl(K, D, z->ld), sgroup = z->ld >= 128 ? 32 : 16;
         Tensor *op = find(c, fl, "op"), *dpos = find(c, fl, "dpos");
-        const bool dst_rowwise = c->opt["gatmh_sweep"] && shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] &&
-                                 ((z->ld >> 2) % (uint32_t)shl) == 0;
-        const BlockedAdj &So = c->swpOut;
-        SpmmArgs sa{};     // the launchers' addressing tests (rows and the 16-byte statistics records through buffer resources): a
-        sa.N = c->N; sa.ld = z->ld;   // partition they would refuse takes the blocked kernels
-        const bool src_sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && shl && c->swpOut_built && !c->swpOut_na && So.nb > 0 &&
-                               ((z->ld >> 2) % (uint32_t)shl) == 0 && sweep_supported(sa, So, z->ld >= 128 ? 32 : 16) &&
-                               (uint64_t)std::max(c->N, c->Gdst) * K * 16u < (1ull << 32) && K * 16u < (1u << 24);
-        // bf16 rows of do / bg_do for the source-side sweep (gatmh_bf16_gather = 2): refused, before anything is launched, where
-        // the call would not take that sweep; the shadow buffer is sized here too (it cannot grow inside a recording)
-        const bool bf16 = bfm >= 2;
-        if (bf16 && !(dst_rowwise && src_sweep))
-            return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = 2 needs the sweep forms of the backward pass, which this call would not take: %s",
+        // (the same addressing test the launchers make -- 32-bit byte offsets through the buffer resource -- so that a
+        // partition they would refuse takes the blocked kernels instead of failing, as spmm() does)
+        SpmmArgs sa{};
+        sa.N = c->N; sa.ld = z->ld;
+        const bool sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
+                           shl != 0 && op && dpos && sweep_supported(sa, Sf, sgroup);
+        const bool bf16 = bfm >= 1;
+        if (bf16 && !sweep)
+            return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
+                        (long long)bfm,
                         !c->opt["gatmh_sweep"] ? "gatmh_sweep = 0" :
                         c->opt["spmm_variant"] != 2 ? "spmm_variant is not 2" :
                         !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
-                        !dst_rowwise ? "this layer's forward pass did not run the sweep form" : "the sweep layout of the out-edges does not apply to this graph");
-        if (bf16 && phase != 1) {
-            int brc = bf16_shadow(c, (uint64_t)c->N + c->Gdst, z->ld, "gatmh_bf16_gather");
-            if (brc) return brc;
+                        (!op || !dpos) ? "tensors op / dpos missing" : "the sweep layout of the in-edges does not apply to this graph");
+        if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 0;
+        if (sweep) {
+            // K1s's skeleton: sums in registers over all source blocks, single-pass softmax against the upper-bound shift
+            int rc = ensure_scratch(c, gatmh_sweep_scratch_bytes(Sf, c->N, z->ld, el->ld));
+            if (rc) return rc;
+            const SweepLaunch sw = sweep_launch(c, Sf, z->ld, sgroup, In.ghosts > 0, gatmh_sweep_rows(Sf, sgroup, shl, 0));
+            if (!sw.done) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
+            // the rows the sweep gathers: z / fg_z, or (bf16) their rounded copies in the shadow buffer -- the local rows
+            // converted now, the ghost rows once their exchange has landed
+            Bf16Rows bf;
+            if (bf16) {
+                if ((rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
+                c->gatmh_bf16_gathers_fwd++;
+            }
+            const float *zs = bf16 ? bf.xl : z->d, *zgs = bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), *a_l = c->weights[fl]["a_l"].d;
+            auto part = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
+                HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, sw.G, b_lo,
+                                                         b_hi, accumulate, sw.done, sw.ctl, sw.sflags, c->compute, el->d, fgel->d, bf16));
+                return DORY_OK;
+            };
+            HIPCK(c, launch_gatmh_sweep_begin(c->N, In.ghosts, K, z->ld, el->ld, Sf, el->d, fgel->d, c->scratch, c->compute));
+            if (sw.two && (rc = part(0, Sf.nb_local, false))) return rc;
+            if ((rc = wait_halo(c)) || (rc = bf.ghosts_landed())) return rc;
+            if ((rc = sw.two ? part(Sf.nb_local, Sf.nb, true) : part(0, Sf.nb, false))) return rc;
+            HIPCK(c, launch_gatmh_forward_sweep_finish(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Sf, z->d, fgz->d, el->d, fgel->d,
+                                                       er->d, o->d, op->d, m->d, den->d, dpos->d, c->scratch, c->compute, bf16));
+            if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
         }
-        if (phase != 2) {
-            Timed t(c, "loss", c->compute);
-            if (last) {
-                NEED(gr, fl, "grad");
-                HIPCK(c, launch_gatmh_head_expand(c->N, K, gr->cols, gr->d, gr->ld, dO->d, dO->ld, c->compute));
-            } else {
-                NEED(dh, fl + 1, "dh");
-                HIPCK(c, launch_gatmh_elu_bwd(c->N, o->cols, dh->d, dh->ld, o->d, o->ld, dO->d, dO->ld, c->compute));
+        else if (blocked) {
+            // "gatmh_fused_stats" (default 1): the blocks' own online softmax + a merge in the reduce kernel instead
+            // of a statistics pass over all edges first; the blocks' (m_b, den_b) live in the scratch buffer
+            float *stat_partial = nullptr;
+            if (c->opt["gatmh_fused_stats"]) {
+                int rc = ensure_scratch(c, (size_t)2 * Bf.nb * c->N * el->ld * sizeof(float));
+                if (rc) return rc;
+                stat_partial = c->scratch;
             }
+            HIPCK(c, launch_gatmh_forward_blocked(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Bf, z->d,
+                                                  fgz->d, el->d, fgel->d, er->d, o->d, m->d, den->d, c->partial,
+                                                  In.ghosts > 0, c->compute, stat_partial,
+                                                  c->opt["gatmh_el_on_the_fly"] ? c->weights[fl]["a_l"].d : nullptr));
         }
-        int rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + (size_t)c->N * K * 16 + 256);
-        if (rc) return rc;
-        if (dst_rowwise && src_sweep) {
-            float4 *st4 = reinterpret_cast<float4 *>(st->d);
-            const uint32_t lds4 = st->ld / 4;
-            if (phase != 2) {
-                Timed t(c, "loss", c->compute);
-                HIPCK(c, launch_gatmh_dst_rowwise(c->N, K, D, z->ld, el->ld, dO->d, o->d, op->d, dpos->d, er->d, m->d, den->d, tt->d, der->d,
-                                                  st4, lds4, c->compute));
-            }
-            if (phase == 1) return DORY_OK;
-            if (phase == 0 && c->numNodes > 1) {   // ghost destinations of the out-edges: their dO and st rows
-                if ((rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, false))) return rc;
-                if ((rc = exchange_rows(c, DORY_BACKWARD, st, bgst, false))) return rc;
-            }
-            if ((rc = ensure_scratch(c, gatmh_src_sweep_scratch_bytes(So, c->N, c->Gdst, K, z->ld, el->ld)))) return rc;
-            const uint32_t G = std::min<uint32_t>(32u, c->cus_per_xcd);
-            const bool two = c->Gdst > 0 && So.nb_local > 0 && So.nb_local < So.nb;
-            const int sgroup = z->ld >= 128 ? 32 : 16;
-            const size_t need = sweep_scratch_bytes(So, z->ld, sgroup, G, two ? std::max(So.nb_local, So.nb - So.nb_local) : So.nb, gatmh_sweep_rows(So, sgroup, shl, 1));
-            if (need > c->partial_bytes) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
-            SweepCtl ctl;
-            ctl.stat = c->sweep_stat;
-            uint32_t *done = reinterpret_cast<uint32_t *>(c->partial);
-            const uint32_t sflags = (uint32_t)c->opt["spmm_sweep_flags"] |
-                                    (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
-            {
-                Timed t(c, "spmm", c->compute);
-                // the rows the sweep gathers: do / bg_do, or (bf16) their rounded copies -- the ghost rows have landed by now
-                // (phase 0: exchange_rows above made the compute stream wait; phase 2: the caller moved them before this call)
-                const float *dos = dO->d, *dogs = bgdo->d;
-                if (bf16) {
-                    Tensor local = *dO;
-                    local.rows = c->N;
-                    if ((rc = bf16_convert(c, local, 0))) return rc;
-                    if (c->Gdst && (rc = bf16_convert(c, *bgdo, c->N))) return rc;
-                    dos = reinterpret_cast<const float *>(c->bf16_rows);
-                    dogs = reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * z->ld);
-                    c->gatmh_bf16_gathers_src++;
-                }
-                HIPCK(c, launch_gatmh_src_sweep_begin(c->N, c->Gdst, K, z->ld, el->ld, So, st4, reinterpret_cast<const float4 *>(bgst->d), lds4,
-                                                      c->scratch, c->compute));
-                if (two) {
-                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dos, dogs, el->d, dz->d, c->scratch, G, 0,
-                                                         So.nb_local, false, done, ctl, sflags, c->compute, bf16));
-                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dos, dogs, el->d, dz->d, c->scratch, G,
-                                                         So.nb_local, So.nb, true, done, ctl, sflags, c->compute, bf16));
-                } else {
-                    HIPCK(c, launch_gatmh_src_sweep_part(c->N, c->Gdst, K, D, z->ld, el->ld, So, dos, c->Gdst ? dogs : nullptr, el->d, dz->d,
-                                                         c->scratch, G, 0, So.nb, false, done, ctl, sflags, c->compute, bf16));
-                }
-                HIPCK(c, launch_gatmh_src_sweep_finish(c->N, K, D, z->ld, el->ld, So, z->d, el->d, dO->d, der->d, c->weights[fl]["a_l"].d,
-                                                       c->weights[fl]["a_r"].d, del->d, dz->d, c->scratch, c->compute, bf16));
-            }
-            // (the attention gradients' column sums take the scratch buffer next: the sweep's sums are consumed by then)
-            if ((rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + 256))) return rc;
-            HIPCK(c, launch_gatmh_dattn(c->N, K, D, z->ld, el->ld, z->d, del->d, der->d, c->wgrads[fl]["a_l"].d,
-                                        c->wgrads[fl]["a_r"].d, c->scratch, c->scratch_bytes, c->compute));
-            return DORY_OK;
-        }
-        const BlockedAdj &Bbi = gatmh_blocked_for(c, true, z->ld), &Bbo = gatmh_blocked_for(c, false, z->ld);
-        const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
-        if (c->opt["gatmh_blocked"] && c->blkIn_built && c->blkOut_built && !c->blkIn_na && !c->blkOut_na && nbmax > 0 &&
-            gatmh_backward_blocked_ok(K, D, z->ld) &&
-            (size_t)nbmax * c->N * (z->ld + K) * sizeof(float) <= c->partial_bytes) {
-            float4 *st4 = reinterpret_cast<float4 *>(st->d);
-            const uint32_t lds4 = st->ld / 4;
-            if (phase != 2) {   // destination side: t, der, st
-                Timed t(c, "spmm", c->compute);
-                HIPCK(c, launch_gatmh_backward_blocked_dst(c->N, K, D, z->ld, el->ld, Bbi, z->d, fgz->d, el->d, fgel->d,
-                                                           er->d, m->d, den->d, dO->d, tt->d, der->d, c->partial, st4, lds4,
-                                                           c->Gsrc > 0, c->compute,
-                                                           // (el from the gathered row only where the forward formed its statistics that
-                                                           //  way too: its ELFLY form needs the fused statistics -- same rounding of alpha)
-                                                           (c->opt["gatmh_el_on_the_fly"] && c->opt["gatmh_fused_stats"]) ? c->weights[fl]["a_l"].d : nullptr));
-            }
-            if (phase == 1) return DORY_OK;
-            if (phase == 0 && c->numNodes > 1) {   // ghost destinations of the out-edges: their dO and st rows
-                if ((rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, false))) return rc;
-                if ((rc = exchange_rows(c, DORY_BACKWARD, st, bgst, false))) return rc;
-            }
-            Timed t(c, "spmm", c->compute);
-            HIPCK(c, launch_gatmh_backward_blocked_src(c->N, K, D, z->ld, el->ld, Bbo, z->d, el->d, dO->d, bgdo->d, st4,
-                                                       reinterpret_cast<const float4 *>(bgst->d), lds4, der->d,
-                                                       c->weights[fl]["a_l"].d, c->weights[fl]["a_r"].d, del->d, dz->d,
-                                                       c->partial, c->Gdst > 0, c->compute));
-            HIPCK(c, launch_gatmh_dattn(c->N, K, D, z->ld, el->ld, z->d, del->d, der->d, c->wgrads[fl]["a_l"].d,
-                                        c->wgrads[fl]["a_r"].d, c->scratch, c->scratch_bytes, c->compute));
-            return DORY_OK;
-        }
-        if (c->numNodes > 1)
+        else if (c->numNodes > 1)
             return fail(c, DORY_ERR_ARG, "multi-head GAT: a partitioned run needs the source-blocked kernels (gatmh_blocked = 1, K*D a shape they cover)");
-        Timed t(c, "spmm", c->compute);
-        HIPCK(c, launch_gatmh_backward(c->N, K, D, z->ld, el->ld, c->colPtr, c->rowIdx, c->rowPtr, c->colIdx, z->d, el->d,
-                                       er->d, m->d, den->d, dO->d, c->weights[fl]["a_l"].d, c->weights[fl]["a_r"].d,
-                                       tt->d, del->d, der->d, dz->d, c->wgrads[fl]["a_l"].d, c->wgrads[fl]["a_r"].d,
-                                       c->scratch, c->scratch_bytes, c->compute));
-        return DORY_OK;
+        else
+            HIPCK(c, launch_gatmh_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, z->d, el->d, er->d,
+                                          o->d, m->d, den->d, c->compute));
     }
-    NEED(z, fl, "z");
-    NEED(fgz, fl, "fg_z");
+    Timed t(c, "loss", c->compute);
+    if (fl != c->L - 1) {
+        AGG_NEED(hn, fl + 1, "h");
+        HIPCK(c, launch_gatmh_elu(c->N, o->cols, o->d, o->ld, hn->d, hn->ld, c->compute));
+    } else {
+        AGG_NEED(lg, fl, "logits");
+        HIPCK(c, launch_gatmh_head_mean(c->N, K, lg->cols, o->d, o->ld, lg->d, lg->ld, c->compute));
+    }
+    return DORY_OK;
+}
+
+// what the forms of the 8-head backward share
+struct GatmhBwd {
+    uint32_t fl, K, D;
+    int64_t phase;   // option gatmh_bwd_phase: 0 = whole sweep; 1 / 2 = one phase (the caller moves the ghost rows)
+    Tensor *z, *el, *er, *m, *den, *o, *dO, *dz, *tt, *del, *der, *st, *fgz, *fgel, *bgdo, *bgst;
+};
+
+// ghost destinations of the out-edges: their dO and st rows, between the two phases of a whole backward pass
+static int gatmh_backward_exchange(dory_ctx *c, const GatmhBwd &T) {
+    if (T.phase != 0 || c->numNodes <= 1) return DORY_OK;
+    int rc = exchange_rows(c, DORY_BACKWARD, T.dO, T.bgdo, false);
+    return rc ? rc : exchange_rows(c, DORY_BACKWARD, T.st, T.bgst, false);
+}
+
+// The sweep forms (gat_mh_sweep.hip).  Destination side: this layer's forward ran on the skeleton and left the positive-branch
+// sums, so t / der / st come from a row-wise kernel -- no edge pass.  Source side: the sweep over the out-edges' layout.
+static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tensor *dpos, int shl, bool bf16) {
+    Adjacency &Out = c->adj[ADJ_OUT];
+    const DerivedAdj &So = Out.swp;
+    const uint32_t K = T.K, D = T.D, ld = T.z->ld, ldk = T.el->ld, lds4 = T.st->ld / 4;
+    float4 *st4 = reinterpret_cast<float4 *>(T.st->d);
+    int rc;
+    if (T.phase != 2) {
+        Timed t(c, "loss", c->compute);
+        HIPCK(c, launch_gatmh_dst_rowwise(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
+                                          st4, lds4, c->compute));
+    }
+    if (T.phase == 1) return DORY_OK;
+    if ((rc = gatmh_backward_exchange(c, T))) return rc;
+    if ((rc = ensure_scratch(c, gatmh_src_sweep_scratch_bytes(So, c->N, Out.ghosts, K, ld, ldk)))) return rc;
+    const int sgroup = ld >= 128 ? 32 : 16;
+    const SweepLaunch sw = sweep_launch(c, So, ld, sgroup, Out.ghosts > 0, gatmh_sweep_rows(So, sgroup, shl, 1));
+    if (!sw.done) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
+    {
+        Timed t(c, "spmm", c->compute);
+        // the rows the sweep gathers: do / bg_do, or (bf16) their rounded copies -- the ghost rows have landed by now
+        // (phase 0: exchange_rows above made the compute stream wait; phase 2: the caller moved them before this call)
+        Bf16Rows bf;
+        if (bf16) {
+            if ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed())) return rc;
+            c->gatmh_bf16_gathers_src++;
+        }
+        const float *dos = bf16 ? bf.xl : T.dO->d, *dogs = bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr);
+        auto part = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
+            HIPCK(c, launch_gatmh_src_sweep_part(c->N, Out.ghosts, K, D, ld, ldk, So, dos, dogs, T.el->d, T.dz->d, c->scratch, sw.G, b_lo, b_hi,
+                                                 accumulate, sw.done, sw.ctl, sw.sflags, c->compute, bf16));
+            return DORY_OK;
+        };
+        HIPCK(c, launch_gatmh_src_sweep_begin(c->N, Out.ghosts, K, ld, ldk, So, st4, reinterpret_cast<const float4 *>(T.bgst->d), lds4,
+                                              c->scratch, c->compute));
+        if (sw.two && (rc = part(0, So.nb_local, false))) return rc;
+        if ((rc = sw.two ? part(So.nb_local, So.nb, true) : part(0, So.nb, false))) return rc;
+        HIPCK(c, launch_gatmh_src_sweep_finish(c->N, K, D, ld, ldk, So, T.z->d, T.el->d, T.dO->d, T.der->d, c->weights[T.fl]["a_l"].d,
+                                               c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->scratch, c->compute, bf16));
+    }
+    // (the attention gradients' column sums take the scratch buffer next: the sweep's sums are consumed by then)
+    if ((rc = ensure_scratch(c, (size_t)2048 * T.z->cols * sizeof(float) + 256))) return rc;
+    HIPCK(c, launch_gatmh_dattn(c->N, K, D, ld, ldk, T.z->d, T.del->d, T.der->d, c->wgrads[T.fl]["a_l"].d,
+                                c->wgrads[T.fl]["a_r"].d, c->scratch, c->scratch_bytes, c->compute));
+    return DORY_OK;
+}
+
+// the source-blocked form (gat_mh_blocked.hip): destination side over the in-edges' blocks, source side over the out-edges'
+static int gatmh_backward_blocked(dory_ctx *c, const GatmhBwd &T, const BlockedAdj &Bbi, const BlockedAdj &Bbo) {
+    const uint32_t K = T.K, D = T.D, ld = T.z->ld, ldk = T.el->ld, lds4 = T.st->ld / 4;
+    float4 *st4 = reinterpret_cast<float4 *>(T.st->d);
+    if (T.phase != 2) {   // destination side: t, der, st
+        Timed t(c, "spmm", c->compute);
+        HIPCK(c, launch_gatmh_backward_blocked_dst(c->N, K, D, ld, ldk, Bbi, T.z->d, T.fgz->d, T.el->d, T.fgel->d,
+                                                   T.er->d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, c->partial, st4, lds4,
+                                                   c->adj[ADJ_IN].ghosts > 0, c->compute,
+                                                   // (el from the gathered row only where the forward formed its statistics that
+                                                   //  way too: its ELFLY form needs the fused statistics -- same rounding of alpha)
+                                                   (c->opt["gatmh_el_on_the_fly"] && c->opt["gatmh_fused_stats"]) ? c->weights[T.fl]["a_l"].d : nullptr));
+    }
+    if (T.phase == 1) return DORY_OK;
+    int rc = gatmh_backward_exchange(c, T);
+    if (rc) return rc;
+    Timed t(c, "spmm", c->compute);
+    HIPCK(c, launch_gatmh_backward_blocked_src(c->N, K, D, ld, ldk, Bbo, T.z->d, T.el->d, T.dO->d, T.bgdo->d, st4,
+                                               reinterpret_cast<const float4 *>(T.bgst->d), lds4, T.der->d,
+                                               c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d,
+                                               c->partial, c->adj[ADJ_OUT].ghosts > 0, c->compute));
+    HIPCK(c, launch_gatmh_dattn(c->N, K, D, ld, ldk, T.z->d, T.del->d, T.der->d, c->wgrads[T.fl]["a_l"].d,
+                                c->wgrads[T.fl]["a_r"].d, c->scratch, c->scratch_bytes, c->compute));
+    return DORY_OK;
+}
+
+// the backward of the edge softmax + weighted sum: the sweep forms, else the blocked kernels (same m / den / st semantics),
+// else (single partition) the row-wise kernels
+static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
+    Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
+    const uint32_t K = c->heads[fl];
+    AGG_NEED(z, fl, "z"); AGG_NEED(el, fl, "el"); AGG_NEED(er, fl, "er"); AGG_NEED(m, fl, "m"); AGG_NEED(den, fl, "den"); AGG_NEED(o, fl, "o");
+    AGG_NEED(dO, fl, "do"); AGG_NEED(dz, fl, "dz"); AGG_NEED(tt, fl, "t"); AGG_NEED(del, fl, "del"); AGG_NEED(der, fl, "der");
+    AGG_NEED(st, fl, "st"); AGG_NEED(fgz, fl, "fg_z"); AGG_NEED(fgel, fl, "fg_el"); AGG_NEED(bgdo, fl, "bg_do"); AGG_NEED(bgst, fl, "bg_st");
+    const uint32_t D = z->cols / K;
+    const GatmhBwd T{fl, K, D, c->opt["gatmh_bwd_phase"], z, el, er, m, den, o, dO, dz, tt, del, der, st, fgz, fgel, bgdo, bgst};
+    const int64_t bfm = c->opt["gatmh_bf16_gather"];
+    const int shl = gatmh_sweep_hl(K, D, z->ld);
+    Tensor *op = find(c, fl, "op"), *dpos = find(c, fl, "dpos");
+    const bool dst_rowwise = c->opt["gatmh_sweep"] && shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] &&
+                             ((z->ld >> 2) % (uint32_t)shl) == 0;
+    const DerivedAdj &So = Out.swp;
+    SpmmArgs sa{};     // the launchers' addressing tests (rows and the 16-byte statistics records through buffer resources): a
+    sa.N = c->N; sa.ld = z->ld;   // partition they would refuse takes the blocked kernels
+    const bool src_sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && shl && So.built && !So.na && So.nb > 0 &&
+                           ((z->ld >> 2) % (uint32_t)shl) == 0 && sweep_supported(sa, So, z->ld >= 128 ? 32 : 16) &&
+                           (uint64_t)std::max(c->N, Out.ghosts) * K * 16u < (1ull << 32) && K * 16u < (1u << 24);
+    // bf16 rows of do / bg_do for the source-side sweep (gatmh_bf16_gather = 2): refused, before anything is launched, where
+    // the call would not take that sweep; the shadow buffer is sized here too (it cannot grow inside a recording)
+    const bool bf16 = bfm >= 2;
+    if (bf16 && !(dst_rowwise && src_sweep))
+        return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = 2 needs the sweep forms of the backward pass, which this call would not take: %s",
+                    !c->opt["gatmh_sweep"] ? "gatmh_sweep = 0" :
+                    c->opt["spmm_variant"] != 2 ? "spmm_variant is not 2" :
+                    !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
+                    !dst_rowwise ? "this layer's forward pass did not run the sweep form" : "the sweep layout of the out-edges does not apply to this graph");
+    int rc;
+    if (bf16 && T.phase != 1 && (rc = bf16_reserve(c, (uint64_t)c->N + Out.ghosts, z->ld, "gatmh_bf16_gather"))) return rc;
+    if (T.phase != 2) {
+        Timed t(c, "loss", c->compute);
+        if (fl == c->L - 1) {
+            AGG_NEED(gr, fl, "grad");
+            HIPCK(c, launch_gatmh_head_expand(c->N, K, gr->cols, gr->d, gr->ld, dO->d, dO->ld, c->compute));
+        } else {
+            AGG_NEED(dh, fl + 1, "dh");
+            HIPCK(c, launch_gatmh_elu_bwd(c->N, o->cols, dh->d, dh->ld, o->d, o->ld, dO->d, dO->ld, c->compute));
+        }
+    }
+    if ((rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + (size_t)c->N * K * 16 + 256))) return rc;
+    if (dst_rowwise && src_sweep) return gatmh_backward_sweep(c, T, op, dpos, shl, bf16);
+    const BlockedAdj &Bbi = gatmh_blocked_for(In, z->ld), &Bbo = gatmh_blocked_for(Out, z->ld);
+    const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
+    if (c->opt["gatmh_blocked"] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na && nbmax > 0 &&
+        gatmh_backward_blocked_ok(K, D, z->ld) &&
+        (size_t)nbmax * c->N * (z->ld + K) * sizeof(float) <= c->partial_bytes)
+        return gatmh_backward_blocked(c, T, Bbi, Bbo);
+    if (c->numNodes > 1)
+        return fail(c, DORY_ERR_ARG, "multi-head GAT: a partitioned run needs the source-blocked kernels (gatmh_blocked = 1, K*D a shape they cover)");
+    Timed t(c, "spmm", c->compute);
+    HIPCK(c, launch_gatmh_backward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Out.ptr, Out.idx, z->d, el->d,
+                                   er->d, m->d, den->d, dO->d, c->weights[fl]["a_l"].d, c->weights[fl]["a_r"].d,
+                                   tt->d, del->d, der->d, dz->d, c->wgrads[fl]["a_l"].d, c->wgrads[fl]["a_r"].d,
+                                   c->scratch, c->scratch_bytes, c->compute));
+    return DORY_OK;
+}
+
+// Engine::aggregateGAT (gat_ops.cpp:173-243), the reference's prototype: edge scores that depend on the destination only
+static int aggregate_gat(dory_ctx *c, uint32_t fl, int dir) {
+    Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
+    const uint32_t F = c->dims[fl + 1];
+    AGG_NEED(z, fl, "z");
+    AGG_NEED(fgz, fl, "fg_z");
     // dory_apply_edge leaves, next to the per-edge tensors "A" / "dA", the one value all
     // edges of a destination share; while that is current the SpMM gathers unweighted
     // (K1b) and scales per row.  A caller that overwrote "A"/"dA" gets the general K1 path.
@@ -707,7 +704,7 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
     Tensor *nsum = find(c, fl, "nsum"), *ones = find(c, 0, "ones");
     const bool reuse = c->opt["gat_reuse_nsum"] && nsum && ones && fl < c->gat_nsum_valid.size() && z->ld == nsum->ld;
     if (dir == DORY_FORWARD) {
-        NEED(ah, fl, "ah");
+        AGG_NEED(ah, fl, "ah");
         Tensor *arow = find(c, fl, "arow");
         const bool fast = arow && fl < c->gat_arow_valid.size() && c->gat_arow_valid[fl];
         if (fl < c->gat_nsum_valid.size()) c->gat_nsum_valid[fl] = 0;
@@ -716,7 +713,7 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
                 HIPCK(c, hipMemsetD32Async((hipDeviceptr_t)ones->d, 0x3f800000, c->N, c->compute));
                 c->gat_ones_set = true;
             }
-            int rc = spmm(c, true, c->cscVal, 0, *z, fgz, *nsum, c->dims[layer], 0, ones->d);
+            int rc = spmm(c, In, In.val, 0, *z, fgz, *nsum, F, 0, ones->d);
             if (rc) return rc;
             if (c->last_spmm_unit) {      // (K1 -- graphs without a blocked layout -- gathers with the per-edge values: not a unit sum)
                 Timed t(c, "spmm", c->compute);
@@ -726,14 +723,14 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
             }
         }
         { int mrc = gat_materialize(c, fl, 2); if (mrc) return mrc; }   // (K1 reads the per-edge values)
-        return spmm(c, true, c->cscVal, 2, *z, fgz, *ah, c->dims[layer], 0, fast ? arow->d : nullptr);
+        return spmm(c, In, In.val, 2, *z, fgz, *ah, F, 0, fast ? arow->d : nullptr);
     }
-    NEED(grad, fl, "grad");
-    NEED(bgd, fl, "bg_d");
-    NEED(dA, fl, "dA");
-    NEED(aTg, fl, "aTg");
+    AGG_NEED(grad, fl, "grad");
+    AGG_NEED(bgd, fl, "bg_d");
+    AGG_NEED(dA, fl, "dA");
+    AGG_NEED(aTg, fl, "aTg");
     // fresh two-term sum (the CUDA path's semantics, gat_ops.cpp:155-163): A^T.dP then += dA.Z
-    int rc = spmm(c, false, c->csrVal, 0, *grad, bgd, *aTg, c->dims[layer], 0);
+    int rc = spmm(c, Out, Out.val, 0, *grad, bgd, *aTg, F, 0);
     if (rc) return rc;
     Tensor *drow = find(c, fl, "drow");
     const bool fast = drow && fl < c->gat_drow_valid.size() && c->gat_drow_valid[fl];
@@ -743,7 +740,25 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
         return DORY_OK;
     }
     { int mrc = gat_materialize(c, fl, 4); if (mrc) return mrc; }
-    return spmm(c, true, dA->d, 0, *z, fgz, *aTg, c->dims[layer], 1, fast ? drow->d : nullptr);
+    return spmm(c, In, dA->d, 0, *z, fgz, *aTg, F, 1, fast ? drow->d : nullptr);
+}
+
+#undef AGG_NEED
+
+}  // namespace dory
+
+using namespace dory;
+
+extern "C" {
+
+int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
+    CHECK_CTX(c);
+    if (!c->prealloc) return fail(c, DORY_ERR_ARG, "aggregate: preallocate first");
+    if (c->gnn == DORY_GCN) return aggregate_gcn(c, layer, dir);
+    // Engine::aggregateGAT (gat_ops.cpp:173-243): tensors live at layer-1
+    if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "aggregate GAT: layer %u out of range", layer);
+    if (c->gnn != DORY_GATMH) return aggregate_gat(c, layer - 1, dir);
+    return dir == DORY_FORWARD ? aggregate_gatmh_forward(c, layer - 1) : aggregate_gatmh_backward(c, layer - 1);
 }
 
 int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {
@@ -857,9 +872,9 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
         Timed t(c, "edge", c->compute);
         HIPCK(c, launch_gatmh_scores(c->N, K, z->cols / K, z->d, z->ld, c->weights[l0]["a_l"].d, c->weights[l0]["a_r"].d,
                                      el->d, er->d, el->ld, c->compute));
-        if (c->Gsrc) {   // scores of the ghost sources from their exchanged z rows (el is all the in-edge side needs)
+        if (c->adj[ADJ_IN].ghosts) {   // scores of the ghost sources from their exchanged z rows (el is all the in-edge side needs)
             NEED(fgz, l0, "fg_z"); NEED(fgel, l0, "fg_el"); NEED(fger, l0, "fg_er");
-            HIPCK(c, launch_gatmh_scores(c->Gsrc, K, z->cols / K, fgz->d, fgz->ld, c->weights[l0]["a_l"].d,
+            HIPCK(c, launch_gatmh_scores(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->d, fgz->ld, c->weights[l0]["a_l"].d,
                                          c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
         }
         return DORY_OK;
@@ -874,7 +889,7 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
         NEED(azrow, fl, "azrow");
         Timed t(c, "edge", c->compute);
         const bool lazy = c->opt["gat_lazy_edge_tensors"] != 0;
-        HIPCK(c, launch_edge_forward_gat(c->N, F, c->colPtr, z->d, z->ld, a.d, lazy ? nullptr : az->d, lazy ? nullptr : c->cscVal, arow->d,
+        HIPCK(c, launch_edge_forward_gat(c->N, F, c->adj[ADJ_IN].ptr, z->d, z->ld, a.d, lazy ? nullptr : az->d, lazy ? nullptr : c->adj[ADJ_IN].val, arow->d,
                                          c->compute, azrow->d));
         for (auto &f : c->gat_arow_valid) f = 0;   // "A" now holds this layer's scores only
         c->gat_arow_valid[fl] = 1;
@@ -901,7 +916,7 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
         const bool have_row = azrow && c->gat_azrow_valid[fl];
         const bool lazy = c->opt["gat_lazy_edge_tensors"] != 0 && have_row;
         if (!have_row) { int mrc = gat_materialize(c, fl, 1); if (mrc) return mrc; }   // (az comes from the caller, or is current already)
-        HIPCK(c, launch_edge_backward_gat(c->N, F, c->colPtr, grad->d, grad->ld, az->d, a.d, lazy ? nullptr : dA->d, cw->d, drow->d, c->compute,
+        HIPCK(c, launch_edge_backward_gat(c->N, F, c->adj[ADJ_IN].ptr, grad->d, grad->ld, az->d, a.d, lazy ? nullptr : dA->d, cw->d, drow->d, c->compute,
                                           have_row ? azrow->d : nullptr));
         c->gat_dA_stale[fl] = lazy ? 1 : 0;
     }

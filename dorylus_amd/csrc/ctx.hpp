@@ -93,6 +93,37 @@ struct LongRowsDev {
     uint32_t nrows = 0, nchunks = 0;
     uint32_t *rows = nullptr, *row_chunk_ptr = nullptr, *chunks = nullptr;
 };
+// a layout derived from one adjacency (built on first use) with its state
+struct DerivedAdj : BlockedAdj {
+    bool built = false;
+    bool na = false;        // not applicable to this graph: the next kernel family takes the aggregation
+    uint32_t want_nb = 0;   // the spmm_blk_nb it was built for
+};
+// One direction of the graph (Graph, graph/graph.hpp:60-99) and everything built from it.  dory_ctx::adj[ADJ_IN] is the CSC of
+// the in-edges = the reference's forwardAdj (ptr: column pointers, idx: source rows, ghosts: ghost sources); adj[ADJ_OUT] is the
+// CSR of the out-edges = backwardAdj (row pointers, destination columns, ghost destinations).
+struct Adjacency {
+    uint64_t *ptr = nullptr;   // N+1
+    uint32_t *idx = nullptr;   // nnz, local ids; >= N means ghost row idx-N
+    float *val = nullptr;      // nnz
+    uint64_t nnz = 0;
+    uint32_t ghosts = 0;
+    // longest-row-first schedule for the SpMM (built at upload)
+    uint32_t *order = nullptr;
+    bool skew = false;           // max degree > 8 x mean: K1 walks the rows longest first (option spmm_order = 1)
+    // K1 under a halo exchange in flight: rows whose sources are all local ("interior", first n_interior entries) run
+    // first, the rows that read ghost rows after the exchange; both parts longest row first
+    uint32_t *split = nullptr;   // N entries: interior rows, then boundary rows
+    uint32_t n_interior = 0;
+    LongRowsDev long_rows;       // K1: hub rows
+    EdgeSplit edge_split;        // K1: local-first copy (GCN partitions with ghosts)
+    DerivedAdj blk;              // K1b blocked copy; na: too many source blocks, use K1
+    // multi-head GAT contexts with layers on both sides of 128 floats: a second copy, blocked for the 256-B slabs of the narrow
+    // layers (K1b's windows hold a fixed number of BYTES: 24 blocks of 512-B rows, 16 of 256-B rows at Reddit size)
+    DerivedAdj blk16;
+    DerivedAdj swp;              // K1s layout (when spmm_variant == 2)
+};
+enum { ADJ_IN = 0, ADJ_OUT = 1 };
 // In-process device transport (dory_comm_init_local, abi_comm.hip): the contexts of one process that are each other's
 // peers.  Peers read each other's plans, buffers, events and progress counters; nothing else.
 struct LocalGroup {
@@ -126,32 +157,10 @@ struct dory_ctx {
 
     // graph (Graph, graph/graph.hpp:60-99)
     bool has_graph = false;
-    uint32_t N = 0, Gsrc = 0, Gdst = 0;
-    uint64_t nnz_in = 0, nnz_out = 0;
-    uint64_t *colPtr = nullptr, *rowPtr = nullptr;
-    uint32_t *rowIdx = nullptr, *colIdx = nullptr;
-    float *cscVal = nullptr, *csrVal = nullptr, *norm = nullptr;
-    // longest-row-first schedules for the SpMM (built at upload)
-    uint32_t *orderIn = nullptr, *orderOut = nullptr;
-    bool skewIn = false, skewOut = false;   // max degree > 8 x mean: K1 walks the rows longest first (option spmm_order = 1)
-    // K1 under a halo exchange in flight: rows whose sources are all local ("interior", first nInt entries) run
-    // first, the rows that read ghost rows after the exchange; both parts longest row first
-    uint32_t *splitIn = nullptr, *splitOut = nullptr;   // N entries: interior rows, then boundary rows
-    uint32_t nIntIn = 0, nIntOut = 0;
-    dory::LongRowsDev longIn, longOut;          // K1: hub rows of forwardAdj / backwardAdj
+    uint32_t N = 0;
+    float *norm = nullptr;
+    dory::Adjacency adj[2];                     // [ADJ_IN] forwardAdj, [ADJ_OUT] backwardAdj
     bool agg_static_ghosts = false;             // the aggregation being issued reads ghost rows no exchange writes (layer 0 forward)
-    dory::EdgeSplit esIn, esOut;                // K1: local-first copies of forwardAdj / backwardAdj (GCN partitions with ghosts)
-    // K1b blocked copies of forwardAdj / backwardAdj (built on first use) + partial buffer
-    dory::BlockedAdj blkIn, blkOut;
-    // multi-head GAT contexts with layers on both sides of 128 floats: a second pair, blocked for the 256-B slabs of the narrow
-    // layers (K1b's windows hold a fixed number of BYTES: 24 blocks of 512-B rows, 16 of 256-B rows at Reddit size)
-    dory::BlockedAdj blkIn16, blkOut16;
-    bool blkIn16_built = false, blkOut16_built = false;
-    dory::BlockedAdj swpIn, swpOut;             // K1s layouts (built on first use when spmm_variant == 2)
-    bool swpIn_built = false, swpOut_built = false, swpIn_na = false, swpOut_na = false;
-    uint32_t swpIn_want_nb = 0, swpOut_want_nb = 0;   // the spmm_blk_nb the layouts were built for
-    bool blkIn_built = false, blkOut_built = false;
-    bool blkIn_na = false, blkOut_na = false;   // K1b not applicable (too many source blocks): use K1
     uint32_t cus_per_xcd = 32;                  // K1s: workgroups per sweep
     // K1s's placement assumption, checked once per context (dory_create: HW_REG_XCC_ID of 2048 probe workgroups -- equal
     // id & 7 => same XCD, the eight residues on eight XCDs).  When it does not hold (a CPX / NPS-partitioned or CU-masked device) the gates
