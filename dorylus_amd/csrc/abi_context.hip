@@ -919,6 +919,10 @@ int dory_get_option(dory_ctx *c, const char *key, int64_t *value) {
     }
     if (key && value && !strcmp(key, "gcn_bf16_gathers_k1s")) { *value = (int64_t)c->bf16_gathers_k1s; return DORY_OK; }   // read-only: aggregations
     if (key && value && !strcmp(key, "gcn_bf16_gathers_k1")) { *value = (int64_t)c->bf16_gathers_k1; return DORY_OK; }     // on bf16 rows, per kernel family
+    // read-only: aggregations of spmm() per kernel family that committed to running them (eager calls and recordings, not replays)
+    if (key && value && !strcmp(key, "spmm_launches_k1s")) { *value = (int64_t)c->spmm_launches_k1s; return DORY_OK; }
+    if (key && value && !strcmp(key, "spmm_launches_k1b")) { *value = (int64_t)c->spmm_launches_k1b; return DORY_OK; }
+    if (key && value && !strcmp(key, "spmm_launches_k1")) { *value = (int64_t)c->spmm_launches_k1; return DORY_OK; }
     if (key && value && !strcmp(key, "gatmh_bf16_gathers_fwd")) { *value = (int64_t)c->gatmh_bf16_gathers_fwd; return DORY_OK; }   // read-only: multi-head GAT
     if (key && value && !strcmp(key, "gatmh_bf16_gathers_src")) { *value = (int64_t)c->gatmh_bf16_gathers_src; return DORY_OK; }   // edge passes on bf16 rows
     if (key && value && !strcmp(key, "epoch_graph_recorded")) {   // read-only: does the ctx still hold a recorded epoch?

@@ -241,6 +241,7 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
         sw.sflags = sweep_flags(c);   // (left undecided -- recording, accumulating caller: ungated, never a timeout)
     }
     Timed t(c, "spmm", c->compute);
+    c->spmm_launches_k1s++;
     if (bf16) c->bf16_gathers_k1s++;
     auto sweep = [&](const SpmmArgs &x, uint32_t b_lo, uint32_t b_hi, uint32_t flags, uint32_t reserve) -> int {
         HIPCK(c, launch_spmm_sweep(x, S, group, row_scale, sw.G, b_lo, b_hi, sw.done, c->compute, sw.ctl, flags, c->scratch, reserve, bf16));
@@ -269,6 +270,7 @@ static int spmm_k1b(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     c->last_spmm_unit = row_scale != nullptr;
     if ((rc = ensure_partial(c, need, "partial buffer"))) return rc;
     Timed t(c, "spmm", c->compute);
+    c->spmm_launches_k1b++;
     auto part = [&](uint32_t b_lo, uint32_t b_hi) -> int {
         HIPCK(c, launch_spmm_blocked_part(a, B, c->partial, group, row_scale != nullptr, b_lo, b_hi, c->compute));
         return DORY_OK;
@@ -290,6 +292,7 @@ static int spmm_k1b(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
 static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
     if (!a.val) return fail(c, DORY_ERR_ARG, "spmm: no edge values");
     const bool bf16 = bf.on();
+    c->spmm_launches_k1++;
     if (bf16) c->bf16_gathers_k1++;
     auto launch = [&](const SpmmArgs &x) -> int {
         HIPCK(c, launch_spmm(x, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));

@@ -197,6 +197,7 @@ struct dory_ctx {
     uint16_t *bf16_rows = nullptr;
     size_t bf16_rows_bytes = 0;
     uint64_t bf16_gathers_k1s = 0, bf16_gathers_k1 = 0;
+    uint64_t spmm_launches_k1s = 0, spmm_launches_k1b = 0, spmm_launches_k1 = 0;   // aggregations per kernel family (read-only options of the same names)
     uint64_t gatmh_bf16_gathers_fwd = 0, gatmh_bf16_gathers_src = 0;   // multi-head GAT: forward edge passes, source-side passes
     std::vector<std::map<std::string, dory::Tensor>> tensors;   // [layer][name]
     std::vector<std::map<std::string, dory::Tensor>> weights;   // "w", "a_i"

@@ -307,6 +307,11 @@ int dory_transform_first_layer(dory_ctx *ctx, uint32_t layer);
  * count the aggregations that ran on bf16 rows per kernel family (eager calls and recordings, not replays); timing family
  * "bf16_convert" times the conversions. */
 
+/* Which kernel family ran.  Read-only "spmm_launches_k1s" / "spmm_launches_k1b" / "spmm_launches_k1" count the aggregations
+ * (GCN's, and the GAT prototype's) per kernel family, at the point where the family commits to running one: K1s the gated
+ * sweep, K1b the partial rows per source block, K1 the row gather.  One aggregation moves exactly one of them by one, however
+ * many launches it is made of (eager calls and recordings, not replays).  The multi-head GAT's edge passes are not counted. */
+
 /* bf16 row gathers in the multi-head GAT sweeps (option "gatmh_bf16_gather", default 0; DORY_GATMH contexts only, no reference
  * counterpart; "gcn_bf16_gather" keeps refusing these contexts).  1: the forward edge pass of every layer reads the rows of
  * "z" / "fg_z" rounded to bf16.  2: as 1, and the backward's source-side pass reads the rows of "do" / "bg_do" rounded to bf16.
