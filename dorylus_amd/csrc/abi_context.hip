@@ -286,6 +286,7 @@ int dory_create(int device, dory_ctx **out) {
     c->opt["gatmh_fused_stats"] = 1;         // multi-head GAT, blocked forward: online softmax per source block + merge in the reduce (0: separate statistics pass first)
     c->opt["gcn_cache_ah0"] = 0;         // GCN: keep ah@0 = A_hat x across epochs while x, fg@0 and the adjacency are unchanged (opt-in; the reference recomputes it)
     c->opt["gcn_bf16_gather"] = 0;       // GCN: aggregations read their source rows rounded to bf16, fp32 sums: 1 = forward, 2 = forward and backward (opt-in; see dorylus_hip.h)
+    c->opt["gcn_bf16_wide"] = 0;         // GCN, with gcn_bf16_gather: K1s gathers bf16 rows of 128 floats or more eight features per lane (16-byte gathers); same bits (opt-in; see dorylus_hip.h)
     c->opt["gatmh_bf16_gather"] = 0;     // multi-head GAT: the sweep forms' edge passes gather their rows rounded to bf16, fp32 sums: 1 = forward (z), 2 = and the backward's source side (do) (opt-in; see dorylus_hip.h)
     c->opt["gcn_transform_first"] = 0;   // GCN layers as A(XW) instead of (AX)W where the input is wider than the output: 1 = layer 0, 2 = all (see tf_layer)
     c->opt["epoch_graph"] = 0;       // engine: replay a recorded epoch (hipGraph) when the partition is alone
@@ -389,6 +390,8 @@ int dory_configure(dory_ctx *c, int gnn_type, uint32_t num_layers, const uint32_
         if (dims[i] == 0) return fail(c, DORY_ERR_ARG, "dory_configure: zero layer width");
     if (gnn_type != DORY_GCN && c->opt["gcn_bf16_gather"])
         return fail(c, DORY_ERR_ARG, "dory_configure: gcn_bf16_gather is a GCN option (set it to 0 first)");
+    if (gnn_type != DORY_GCN && c->opt["gcn_bf16_wide"])
+        return fail(c, DORY_ERR_ARG, "dory_configure: gcn_bf16_wide is a GCN option (set it to 0 first)");
     if (gnn_type != DORY_GATMH && c->opt["gatmh_bf16_gather"])
         return fail(c, DORY_ERR_ARG, "dory_configure: gatmh_bf16_gather is an option of the multi-head GAT (set it to 0 first)");
     c->gnn = gnn_type;
@@ -683,6 +686,9 @@ int dory_preallocate(dory_ctx *c) {
             for (Adjacency &A : c->adj) {
                 if ((rc = ensure_sweep(c, A, group))) return rc;
                 if (A.swp.nb) need = std::max(need, sweep_scratch_bytes(A.swp, maxld, group, G, A.swp.nb, (int)c->opt["spmm_sweep_rows"]));
+                // (option gcn_bf16_wide's launches never need more, but for a forced row count that only 16-lane groups take)
+                if (A.swp.nb && c->gnn == DORY_GCN && sweep_wide_applies(A.swp, maxld, group, G, (int)c->opt["spmm_sweep_rows"]))
+                    need = std::max(need, sweep_scratch_bytes(A.swp, maxld, group, G, A.swp.nb, (int)c->opt["spmm_sweep_rows"], true));
             }
             if ((rc = ensure_partial(c, need, "sweep counters"))) return rc;
             // the slots of the split rows' pieces too (skewed graphs): an epoch recorded into a hipGraph right after a
@@ -918,6 +924,7 @@ int dory_get_option(dory_ctx *c, const char *key, int64_t *value) {
         return DORY_OK;
     }
     if (key && value && !strcmp(key, "gcn_bf16_gathers_k1s")) { *value = (int64_t)c->bf16_gathers_k1s; return DORY_OK; }   // read-only: aggregations
+    if (key && value && !strcmp(key, "gcn_bf16_gathers_k1s_wide")) { *value = (int64_t)c->bf16_gathers_k1s_wide; return DORY_OK; }   // (of _k1s: the wide form, option gcn_bf16_wide)
     if (key && value && !strcmp(key, "gcn_bf16_gathers_k1")) { *value = (int64_t)c->bf16_gathers_k1; return DORY_OK; }     // on bf16 rows, per kernel family
     // read-only: aggregations of spmm() per kernel family that committed to running them (eager calls and recordings, not replays)
     if (key && value && !strcmp(key, "spmm_launches_k1s")) { *value = (int64_t)c->spmm_launches_k1s; return DORY_OK; }
@@ -991,6 +998,10 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     if (key && !strcmp(key, "gcn_bf16_gather")) {
         if (value < 0 || value > 2) return fail(c, DORY_ERR_ARG, "gcn_bf16_gather: 0 (off), 1 (forward) or 2 (forward and backward)");
         if (value && c->gnn != DORY_GCN) return fail(c, DORY_ERR_ARG, "gcn_bf16_gather: GCN contexts only");
+    }
+    if (key && !strcmp(key, "gcn_bf16_wide")) {
+        if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "gcn_bf16_wide: 0 (off) or 1 (16-byte gathers of bf16 rows in K1s)");
+        if (value && c->gnn != DORY_GCN) return fail(c, DORY_ERR_ARG, "gcn_bf16_wide: GCN contexts only");
     }
     if (key && !strcmp(key, "gatmh_bf16_gather")) {
         if (value < 0 || value > 2) return fail(c, DORY_ERR_ARG, "gatmh_bf16_gather: 0 (off), 1 (forward) or 2 (forward and the backward's source side)");

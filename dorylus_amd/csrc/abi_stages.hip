@@ -181,14 +181,15 @@ struct SweepLaunch {
 static uint32_t sweep_flags(dory_ctx *c) {
     return (uint32_t)c->opt["spmm_sweep_flags"] | (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
 }
-static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, int group, bool ghosts, int rows /* per lane group */) {
+static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, int group, bool ghosts, int rows /* per lane group */,
+                                bool wide = false /* K1s on bf16 rows, eight features per lane: its own groups and slabs */) {
     SweepLaunch sw;
     sw.group = group;
     sw.G = std::min<uint32_t>(32u, c->cus_per_xcd);
     sw.two = ghosts && S.nb_local > 0 && S.nb_local < S.nb;
     sw.ctl.stat = c->sweep_stat;
     sw.sflags = sweep_flags(c);
-    sw.need = sweep_scratch_bytes(S, ld, group, sw.G, sw.two ? std::max(S.nb_local, S.nb - S.nb_local) : S.nb, rows);
+    sw.need = sweep_scratch_bytes(S, ld, group, sw.G, sw.two ? std::max(S.nb_local, S.nb - S.nb_local) : S.nb, rows, wide);
     sw.done = sw.need <= c->partial_bytes ? reinterpret_cast<uint32_t *>(c->partial) : nullptr;
     return sw;
 }
@@ -196,7 +197,7 @@ static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, i
 // K1s's placement check failed (ctx.hpp): gates would synchronise workgroups that do not share an L2.  Decide once per context,
 // by measurement, on a launch that may be repeated (it writes, does not accumulate): gated against ungated.  The three probe
 // launches are timed under their own key ("spmm_xcd_probe"), outside the caller's "spmm" region.
-static int xcd_probe(dory_ctx *c, const SpmmArgs &a, const BlockedAdj &S, const float *row_scale, const SweepLaunch &sw, bool bf16) {
+static int xcd_probe(dory_ctx *c, const SpmmArgs &a, const BlockedAdj &S, const float *row_scale, const SweepLaunch &sw, bool bf16, bool wide) {
     struct Ev3 {   // destroyed on every way out (HIPCK returns)
         hipEvent_t e[3] = {nullptr, nullptr, nullptr};
         ~Ev3() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
@@ -204,11 +205,11 @@ static int xcd_probe(dory_ctx *c, const SpmmArgs &a, const BlockedAdj &S, const 
     Timed tp(c, "spmm_xcd_probe", c->compute);
     for (auto &x : ev.e) HIPCK(c, hipEventCreate(&x));
     const uint32_t hi = sw.two ? S.nb_local : S.nb, gated = sw.sflags & ~8u;
-    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16));   // (warm: layout, code)
+    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16, wide));   // (warm: layout, code)
     HIPCK(c, hipEventRecord(ev.e[0], c->compute));
-    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated, c->scratch, 0, bf16));
+    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated, c->scratch, 0, bf16, wide));
     HIPCK(c, hipEventRecord(ev.e[1], c->compute));
-    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16));
+    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16, wide));
     HIPCK(c, hipEventRecord(ev.e[2], c->compute));
     HIPCK(c, hipEventSynchronize(ev.e[2]));
     (void)hipEventElapsedTime(&c->xcd_gated_ms, ev.e[0], ev.e[1]);
@@ -227,7 +228,10 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     const DerivedAdj &S = A.swp;
     if (S.na || !sweep_supported(a, S, group)) return SPMM_NOT_MINE;
     const bool bf16 = bf.on();
-    SweepLaunch sw = sweep_launch(c, S, a.ld, group, a.xg != nullptr, (int)c->opt["spmm_sweep_rows"]);
+    // option gcn_bf16_wide: bf16 rows of 128 floats or more are gathered eight features per lane (same bits; spmm.hip)
+    const bool wide = bf16 && c->opt["gcn_bf16_wide"] == 1 &&
+                      sweep_wide_applies(S, a.ld, group, std::min<uint32_t>(32u, c->cus_per_xcd), (int)c->opt["spmm_sweep_rows"]);
+    SweepLaunch sw = sweep_launch(c, S, a.ld, group, a.xg != nullptr, (int)c->opt["spmm_sweep_rows"], wide);
     if ((rc = ensure_partial(c, sw.need, "sweep counters"))) return rc;   // (K1s may still size its counters here, outside a recording)
     sw.done = reinterpret_cast<uint32_t *>(c->partial);
     if (S.nslots && (rc = ensure_scratch(c, (size_t)S.nslots * a.ld * sizeof(float)))) return rc;   // pieces of split rows
@@ -237,14 +241,15 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     sw.ctl.loader = c->opt["spmm_sweep_loader"] != 0;
     if ((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && !(c->opt["spmm_sweep_flags"] & 8) && c->xcd_policy < 0 &&
         !c->capturing && !a.accumulate && !c->halo_pending) {
-        if ((rc = xcd_probe(c, a, S, row_scale, sw, bf16))) return rc;
+        if ((rc = xcd_probe(c, a, S, row_scale, sw, bf16, wide))) return rc;
         sw.sflags = sweep_flags(c);   // (left undecided -- recording, accumulating caller: ungated, never a timeout)
     }
     Timed t(c, "spmm", c->compute);
     c->spmm_launches_k1s++;
     if (bf16) c->bf16_gathers_k1s++;
+    if (wide) c->bf16_gathers_k1s_wide++;
     auto sweep = [&](const SpmmArgs &x, uint32_t b_lo, uint32_t b_hi, uint32_t flags, uint32_t reserve) -> int {
-        HIPCK(c, launch_spmm_sweep(x, S, group, row_scale, sw.G, b_lo, b_hi, sw.done, c->compute, sw.ctl, flags, c->scratch, reserve, bf16));
+        HIPCK(c, launch_spmm_sweep(x, S, group, row_scale, sw.G, b_lo, b_hi, sw.done, c->compute, sw.ctl, flags, c->scratch, reserve, bf16, wide));
         return DORY_OK;
     };
     // under an exchange in flight the RCCL kernels need CUs of their own

@@ -196,7 +196,7 @@ struct dory_ctx {
     // by every pass that uses it, never kept across calls), and the passes that ran on it per kernel family
     uint16_t *bf16_rows = nullptr;
     size_t bf16_rows_bytes = 0;
-    uint64_t bf16_gathers_k1s = 0, bf16_gathers_k1 = 0;
+    uint64_t bf16_gathers_k1s = 0, bf16_gathers_k1 = 0, bf16_gathers_k1s_wide = 0;   // (_wide: those of _k1s that ran the wide form, option gcn_bf16_wide)
     uint64_t spmm_launches_k1s = 0, spmm_launches_k1b = 0, spmm_launches_k1 = 0;   // aggregations per kernel family (read-only options of the same names)
     uint64_t gatmh_bf16_gathers_fwd = 0, gatmh_bf16_gathers_src = 0;   // multi-head GAT: forward edge passes, source-side passes
     std::vector<std::map<std::string, dory::Tensor>> tensors;   // [layer][name]
@@ -323,12 +323,16 @@ struct SweepCtl {
     uint32_t *stat = nullptr;   // SWEEP_STAT_WORDS device words that outlive the launches (dory_ctx::sweep_stat)
 };
 constexpr int SWEEP_STAT_WORDS = 8;
-size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, uint32_t nblocks, int force_r = 0);
+// wide: the launch's form on bf16 rows with eight features per lane (option gcn_bf16_wide; spmm.hip: spmm_sweep_bf16x8_kernel) --
+// 16-lane groups on 128-feature slabs whatever `group`; sweep_wide_applies: rows of 128 floats or more and an instantiated row count
+bool sweep_wide_applies(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, int force_r);
+size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, uint32_t nblocks, int force_r = 0, bool wide = false);
 hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, const float *row_scale, uint32_t cus_per_xcd,
                              uint32_t b_lo, uint32_t b_hi, uint32_t *done /* sweep_scratch_bytes() */, hipStream_t s,
                              const SweepCtl &ctl, uint32_t flags = 0, float *split_partial = nullptr /* B.nslots x ld floats */,
                              uint32_t reserve_cus = 0 /* CUs per XCD left to concurrent kernels */,
-                             bool bf16 = false /* bf16 source rows (launch_spmm), no row_scale */);
+                             bool bf16 = false /* bf16 source rows (launch_spmm), no row_scale */,
+                             bool wide = false /* bf16 rows, eight features per lane: where sweep_wide_applies() */);
 hipError_t launch_spmm_sweep_combine(const SpmmArgs &a, const BlockedAdj &B, const float *row_scale, const float *split_partial,
                                      hipStream_t s, bool bf16 = false);
 // fp32 -> bf16 (round to nearest even) of n elements, n a multiple of 4: the rows an aggregation reads under options

@@ -320,22 +320,28 @@ void free_blocked(BlockedAdj *B) {
 // 2.9 ms (3.9).  Hub (block,row) segments (B.nchunks != 0) keep K1b.
 // =======================================================================================
 // The skeleton (gates, loader wave, staging, batches of gathers) is sweep_core.hpp; the plain SpMM is this OP on it.
-template <bool UNIT, bool BF16 = false>
-struct SweepPlainOp {
-    static constexpr bool PLAIN = true, UNIT_W = UNIT, PROLOGUE = false, AUX_BATCH = false;
-    static constexpr bool BF16_ROWS = BF16;     // source rows (and the self row) are bf16: spmm_sweep_bf16_kernel
 #ifndef K1S_BATCH
 #define K1S_BATCH SWEEP_U   // 3 / 4 / 5 / 6 gathers per batch = 18.60 / 18.10 / 18.64 / 19.58 ms per epoch (round 5, re-measured on the final kernel)
 #endif
-    static constexpr int BATCH = K1S_BATCH;     // gathers per batch
+template <bool UNIT, bool BF16 = false, bool WIDE = false, int U = K1S_BATCH>
+struct SweepPlainOp {
+    static constexpr bool PLAIN = true, UNIT_W = UNIT, PROLOGUE = false, AUX_BATCH = false;
+    static constexpr bool BF16_ROWS = BF16;     // source rows (and the self row) are bf16: spmm_sweep_bf16_kernel
+    static constexpr bool WIDE_ROWS = WIDE;     // eight features per lane, 16-byte gathers of bf16: spmm_sweep_bf16x8_kernel
+    static constexpr int BATCH = U;             // gathers per batch
     static constexpr int SLACK = SWEEP_SLACK; // windows a workgroup may run ahead of its sweep's slowest
     const float *row_scale;
-    struct Row { float4 acc; };
+    struct Row4 { float4 acc; };
+    struct Row8 { float4 acc, acc2; };            // WIDE: features 0-3 and 4-7 of the lane's chunk
+    typedef typename std::conditional<WIDE, Row8, Row4>::type Row;
     struct RowC {};
     typedef uint32_t Aux;                       // the entry's weight (bits)
     __device__ __forceinline__ Aux aux(uint32_t, uint32_t vbits, bool) const { return vbits; }
     template <int NB> __device__ __forceinline__ void aux_batch(const uint2 *, uint32_t, Aux (&)[NB]) const {}
-    __device__ __forceinline__ void init(Row &r) const { r.acc = make_float4(0.f, 0.f, 0.f, 0.f); }
+    __device__ __forceinline__ void init(Row &r) const {
+        r.acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (WIDE) r.acc2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     __device__ __forceinline__ RowC row_const(uint32_t) const { return RowC{}; }
     __device__ __forceinline__ void prologue(const SpmmArgs &, const BlockedAdj &, uint32_t, uint32_t, bool, uint32_t, int) {}
     template <bool FULL>
@@ -343,10 +349,39 @@ struct SweepPlainOp {
         const float wv = UNIT ? 1.f : __uint_as_float(vbits);
         r.acc = fma4(FULL ? wv : (on ? wv : 0.f), x, r.acc);
     }
+    template <bool FULL>
+    __device__ __forceinline__ void entry(Row &r, const RowC &, const Float4x2 &x, uint32_t vbits, bool on) const {
+        static_assert(WIDE && !UNIT, "eight features per entry: the wide form, edge weights");
+        const float wv = FULL ? __uint_as_float(vbits) : (on ? __uint_as_float(vbits) : 0.f);
+        r.acc = fma4(wv, x.lo, r.acc);
+        if constexpr (WIDE) r.acc2 = fma4(wv, x.hi, r.acc2);
+    }
     // one store path for rows and for pieces of split rows (a piece: the bare sum into its slot, no scale, no self
     // term; spmm_sweep_combine_kernel finishes those rows)
     __device__ __forceinline__ void store(const Row &r, const SpmmArgs &a, const SweepArgs &w, uint32_t v, bool piece, uint32_t slot,
                                           uint32_t col, uint32_t nchunk, const float4 *xl4 /* a.xl + this lane's column */) const {
+        if constexpr (WIDE) {   // col, nchunk count eight features: two float4 per row and lane, each finished as the narrow form's one
+            const size_t at = ((size_t)(piece ? slot : v) * nchunk + col) * 2;
+            float4 *q = (piece ? reinterpret_cast<float4 *>(w.split_partial) : reinterpret_cast<float4 *>(a.out)) + at;
+            float sc = 0.f;
+            float4 xs0 = make_float4(0.f, 0.f, 0.f, 0.f), xs1 = xs0;
+            if (a.self_mode != 0 && !piece) {
+                sc = a.self_mode == 1 ? a.self_scale[v] : 1.f;
+                const uint4 s8 = reinterpret_cast<const uint4 *>(a.xl)[(size_t)v * nchunk + col];
+                xs0 = bf16x4_to_float4(s8.x, s8.y);
+                xs1 = bf16x4_to_float4(s8.z, s8.w);
+            }
+            // (no row factor: bf16 rows have edge weights -- launch_spmm_sweep refuses row_scale)
+            float4 o0 = fma4(sc, xs0, r.acc), o1 = fma4(sc, xs1, r.acc2);
+            if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {
+                const float4 p0 = q[0], p1 = q[1];
+                o0.x += p0.x; o0.y += p0.y; o0.z += p0.z; o0.w += p0.w;
+                o1.x += p1.x; o1.y += p1.y; o1.z += p1.z; o1.w += p1.w;
+            }
+            q[0] = o0;
+            q[1] = o1;
+            return;
+        }
         float4 *out4 = reinterpret_cast<float4 *>(a.out);
         float4 *part4 = reinterpret_cast<float4 *>(w.split_partial);
         float4 *q = piece ? part4 + (size_t)slot * nchunk + col : out4 + (size_t)v * nchunk + col;
@@ -380,6 +415,20 @@ __global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16_kernel(SpmmArgs a, B
                                                                    SweepArgs w) {
     SweepPlainOp<UNIT, true> op{row_scale};
     sweep_run<GROUP, R, PAIR, LOADER>(a, B, w, op);
+}
+
+// the same sweep over bf16 rows with eight features per lane (option gcn_bf16_wide; rows of 128 floats or more): 16-lane
+// groups on the layout dealt for 32-lane groups, R = the 16-lane row count of that layout (2 .. 5; with 5 on the ten-row
+// layout a workgroup walks the same 320 rows per step), one 16-byte gather of eight bf16 per lane and entry, two float4
+// accumulators per row (40 registers at R = 5, as the ten-row fp32 form).  Rows are never taken in pairs (the rule of the
+// 16-lane launches with an odd R, kept for every R: one form per row count).  Gathers per batch: four (16 registers of raw
+// bf16 in flight, expanded as they are summed) -- but three for five rows without the loader wave, whose lanes also hold the
+// pre-loaded entries of the next step: four spill two registers there (120 with the loader, 128 + 2 without).  Every
+// instantiation then fits the 128 registers of a 1024-thread workgroup without scratch (tests/test_bf16_wide_resources.py).  Summation order per element: the narrow form's -- same bits on finite rows.
+template <int R, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16x8_kernel(SpmmArgs a, BlockedAdj B, SweepArgs w) {
+    SweepPlainOp<false, true, true, (R == 5 && !LOADER) ? 3 : K1S_BATCH> op{nullptr};
+    sweep_run<16, R, false, LOADER>(a, B, w, op);
 }
 
 // out[row] (+)= self + (row_scale *) sum of the row's pieces, in piece order.  TPR threads per split row (a float4
@@ -652,23 +701,34 @@ static int sweep_rows_for(const BlockedAdj &B, int group, uint32_t G, int force_
     return sweep_pick_r(B.npos, group, G, 0, 10);
 }
 
+// does a launch on bf16 rows take the wide form (eight features per lane on 16-lane groups: spmm_sweep_bf16x8_kernel)?  Rows of
+// 128 floats or more, a layout whose 16-lane row count is instantiated (2 .. 5: a forced 6 or 8 keeps the narrow form)
+bool sweep_wide_applies(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, int force_r) {
+    if (ld < 128 || (group != 16 && group != 32)) return false;
+    const int R = sweep_rows_for(B, 16, G, force_r);
+    return R >= 2 && R <= 5;
+}
+
 // counter words one launch over nblocks source blocks needs (callers size the scratch for the largest launch)
-size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, uint32_t nblocks, int force_r) {
+size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, uint32_t nblocks, int force_r, bool wide) {
+    if (wide) group = 16;                          // (the wide form: 16-lane groups, chunks of eight features)
     const int R = sweep_rows_for(B, group, G, force_r);
     const uint32_t RW = (uint32_t)(SWEEP_NT / group) * R;
     const uint32_t Gmin = G > 12 ? G - 8 : G;      // launches may leave up to 8 CUs per XCD to concurrent kernels
     const uint32_t rpx = (B.npos + 7) / 8 + 16, tiles = (rpx + RW - 1) / RW + 1, spp = (tiles + Gmin - 1) / Gmin;
-    const uint32_t slabs = ((ld >> 2) + group - 1) / group;
+    const uint32_t slabs = ((ld >> (wide ? 3 : 2)) + group - 1) / group;
     return ((size_t)8 * slabs * spp * nblocks * 32 + 1) * sizeof(uint32_t);
 }
 
 // out (+)= self + (row_scale *) sum over source blocks [b_lo, b_hi); `done` = sweep_scratch_bytes() of device memory
 hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, const float *row_scale, uint32_t cus,
                              uint32_t b_lo, uint32_t b_hi, uint32_t *done, hipStream_t s, const SweepCtl &ctl, uint32_t flags,
-                             float *split_partial, uint32_t reserve, bool bf16) {
+                             float *split_partial, uint32_t reserve, bool bf16, bool wide) {
     if (a.N == 0 || a.ld == 0 || b_lo >= b_hi) return hipSuccess;
     if (bf16 && row_scale) return hipErrorInvalidValue;   // bf16 rows: the GCN aggregations (edge weights) only
     if (!sweep_supported(a, B, group) || b_hi > B.nb || cus == 0 || cus > 32 || !ctl.stat) return hipErrorInvalidValue;
+    if (wide && (!bf16 || (a.ld & 7) || !sweep_wide_applies(B, a.ld, group, cus, ctl.force_r))) return hipErrorInvalidValue;
+    if (wide) group = 16;
     if (b_lo < B.nb_local && b_hi > B.nb_local) return hipErrorInvalidValue;   // one source array per launch
     if (b_lo >= B.nb_local && !a.xg) return hipErrorInvalidValue;
     const int R = sweep_rows_for(B, group, cus, ctl.force_r);
@@ -682,7 +742,7 @@ hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, 
     w.tiles_x = (w.rpx + RW - 1) / RW;
     w.G = G;
     const uint32_t spp = (w.tiles_x + G - 1) / G;
-    const uint32_t slabs = ((a.ld >> 2) + group - 1) / group;
+    const uint32_t slabs = ((a.ld >> (wide ? 3 : 2)) + group - 1) / group;
     w.nsweeps = slabs * spp;
     w.b_lo = b_lo; w.b_hi = b_hi;
     w.done = done;
@@ -697,6 +757,16 @@ hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, 
     // rows in pairs (one stream of entries per two rows) pay on launches of several slabs (five slabs, F=602: 13.8 ->
     // 13.3 ms; four: 11.0 -> 10.8; three: 8.16 -> 8.1), not on one or two (F=128: 2.70 -> 2.78; F=256: 5.43 -> 5.46);
     // ctl.pair (option spmm_sweep_pair): -1 = that rule, 0 / 1 = forced (experiments)
+    if (wide) {   // one form per row count and loader setting, weighted, rows never in pairs
+#define SWEEP_LAUNCH_W(RR)                                                                                             \
+    do {                                                                                                               \
+        if (ctl.loader) hipLaunchKernelGGL((spmm_sweep_bf16x8_kernel<RR, true>), gr, bl, 0, s, a, B, w);               \
+        else hipLaunchKernelGGL((spmm_sweep_bf16x8_kernel<RR, false>), gr, bl, 0, s, a, B, w);                         \
+    } while (0)
+        if (R == 5) SWEEP_LAUNCH_W(5); else if (R == 4) SWEEP_LAUNCH_W(4); else if (R == 3) SWEEP_LAUNCH_W(3); else SWEEP_LAUNCH_W(2);
+#undef SWEEP_LAUNCH_W
+        return hipGetLastError();
+    }
     const bool pair = (R & 1) ? false : (ctl.pair < 0 ? slabs >= 3 : ctl.pair != 0);   // (odd R: 16-lane launches on a 6- or 10-row layout)
 #define SWEEP_LAUNCH_L(GRP, RR, LD)                                                                                    \
     do {                                                                                                               \

@@ -119,6 +119,13 @@ __device__ __forceinline__ void sweep_arrive(uint32_t sb, uint32_t t, uint32_t *
 // lane mapping, slabs, layout, gates and loader wave are those of the fp32 rows
 template <class OP, class = void> struct sweep_bf16_rows : std::false_type {};
 template <class OP> struct sweep_bf16_rows<OP, std::void_t<decltype(OP::BF16_ROWS)>> : std::integral_constant<bool, OP::BF16_ROWS> {};
+// OP trait WIDE_ROWS (default false; bf16 rows on 16-lane groups only; option gcn_bf16_wide): a lane holds EIGHT consecutive
+// features of a 128-feature slab and fetches them with one 16-byte gather -- the bytes per instruction of the fp32 rows at
+// half the gather instructions per row.  What one gather returns, and what OP::entry takes, is then a pair of float4
+// (Float4x2); chunks and slabs count eight features.  Layout, gates, loader wave and staging are untouched.
+template <class OP, class = void> struct sweep_wide_rows : std::false_type {};
+template <class OP> struct sweep_wide_rows<OP, std::void_t<decltype(OP::WIDE_ROWS)>> : std::integral_constant<bool, OP::WIDE_ROWS> {};
+struct Float4x2 { float4 lo, hi; };
 
 #ifndef SWEEP_DMA_AUX
 #define SWEEP_DMA_AUX 2   // cache policy of the loader's copies: nt (the entry stream is read once: it must not push the window out of L2)
@@ -127,6 +134,9 @@ template <int GROUP, int R, bool PAIR, bool LOADER, class OP>
 __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B, const SweepArgs &w, OP &op) {
     constexpr bool UNIT = OP::UNIT_W;
     constexpr bool BF16 = sweep_bf16_rows<OP>::value;
+    constexpr bool WIDE = sweep_wide_rows<OP>::value;
+    static_assert(!WIDE || (BF16 && GROUP == 16 && !PAIR), "eight features per lane: bf16 rows, 16-lane groups, rows not in pairs");
+    typedef typename std::conditional<WIDE, Float4x2, float4>::type XT;   // what one gather of a lane returns
     static_assert(!PAIR || OP::PLAIN, "rows in pairs: the plain SpMM only");
     constexpr int GPW = 64 / GROUP;
     constexpr int NGRP = SWEEP_NT / GROUP;
@@ -134,7 +144,9 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
     constexpr int RW = NGRP * R;
     // staged (idx, val) pairs per lane group and pass.  With the loader wave a 16-lane launch (64 lane groups) gets 512-byte slots:
     // three buffers of 64 x 1 KB would not fit the LDS, and its groups hold at most a few rows (tens of entries per step)
-    constexpr int C = (LOADER && GROUP == 16) ? SWEEP_C / 2 : SWEEP_C;
+    // (WIDE without the loader: the same 512-byte slots -- the pre-loaded entries of 1 KB slots are eight registers more per lane than
+    // five rows of eight features leave)
+    constexpr int C = ((LOADER || WIDE) && GROUP == 16) ? SWEEP_C / 2 : SWEEP_C;
     constexpr int U = OP::BATCH, CQ = C / (2 * GROUP), CE = C - 1;   // CQ 16-byte loads of two entries per lane; a pass holds CE entries (its first may be the odd one of a pair)
     constexpr int NBUF = LOADER ? 3 : 1;
     constexpr int OFFB = (RW + 1 + 63) / 64 * 64;           // LOADER: the block's base (lo, hi) sits behind the copied offsets
@@ -180,7 +192,7 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
     const int g = wave * GPW + gi;
     const uint32_t xend = min((xcd + 1) * w.rpx, B.npos);   // positions (= rows without B.perm)
     const uint32_t v0 = min(xcd * w.rpx + t * RW + (uint32_t)g * R, xend);
-    const uint32_t nchunk = a.ld >> 2;
+    const uint32_t nchunk = a.ld >> (WIDE ? 3 : 2);
     const uint32_t col = slab * GROUP + li;
     const bool col_ok = col < nchunk;
     const uint32_t ccol = col_ok ? col : 0;
@@ -202,12 +214,15 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
         const_cast<float *>(ghost_launch ? a.xg : a.xl), 0, (ghost_launch ? B.nghost : a.N) * row_b, 0x00020000);
     // a lane without a column (the last slab of a row narrower than the slabs) multiplies by 0 and adds -1: always out of range,
     // at no instruction
-    const uint32_t lane_b = col_ok ? ccol * (BF16 ? 8u : 16u) - (ghost_launch ? a.N : 0u) * row_b : 0xFFFFFFFFu;   // (mod 2^32) + idx * row_b = byte offset
+    const uint32_t lane_b = col_ok ? ccol * (BF16 && !WIDE ? 8u : 16u) - (ghost_launch ? a.N : 0u) * row_b : 0xFFFFFFFFu;   // (mod 2^32) + idx * row_b = byte offset
     const uint32_t lane_m = col_ok ? row_b : 0u;
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-    auto gather = [&](uint32_t sidx, bool on) -> float4 {
-        if constexpr (BF16) {
+    auto gather = [&](uint32_t sidx, bool on) -> XT {
+        if constexpr (WIDE) {
+            const u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, on ? __umul24(sidx, lane_m) + lane_b : 0xFFFFFFFFu, 0, 0);
+            return Float4x2{bf16x4_to_float4(v.x, v.y), bf16x4_to_float4(v.z, v.w)};
+        } else if constexpr (BF16) {
             const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, on ? __umul24(sidx, lane_m) + lane_b : 0xFFFFFFFFu, 0, 0);
             return bf16x4_to_float4(v.x, v.y);
         } else {
@@ -360,7 +375,7 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
 #pragma unroll
                     for (int u = 0; u < U; ++u) en[u] = st[e + u - cs];
                     for (; e + U <= hi; e += U) {
-                        float4 x[U];
+                        XT x[U];
                         float wv[U];
 #pragma unroll
                         for (int u = 0; u < U; ++u) { x[u] = gather(en[u].x, true); wv[u] = UNIT ? 1.f : __uint_as_float(en[u].y); }
@@ -375,7 +390,7 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
                     }
                     if (e < hi) {
                         const uint32_t n = hi - e;
-                        float4 x[U - 1];
+                        XT x[U - 1];
 #pragma unroll
                         for (int u = 0; u < U - 1; ++u) x[u] = gather(en[u].x, (uint32_t)u < n);
 #pragma unroll
@@ -403,7 +418,7 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
 #pragma unroll
                     for (int u = 0; u < U; ++u) en[u] = st[e + u - cs];
                     for (; e + U <= hi; e += U) {               // full batches: nothing predicated
-                        float4 x[U];
+                        XT x[U];
                         typename OP::Aux ax[U];                  // the entry's weight bits, or the OP's second gather
 #pragma unroll
                         for (int u = 0; u < U; ++u) x[u] = gather(en[u].x, true);
@@ -420,7 +435,7 @@ __device__ __forceinline__ void sweep_run(const SpmmArgs &a, const BlockedAdj &B
                     }
                     if (e < hi) {                                // tail: 1 .. U-1 edges
                         const uint32_t n = hi - e;
-                        float4 x[U - 1];
+                        XT x[U - 1];
                         typename OP::Aux ax[U - 1];
 #pragma unroll
                         for (int u = 0; u < U - 1; ++u) x[u] = gather(en[u].x, (uint32_t)u < n);

@@ -307,6 +307,19 @@ int dory_transform_first_layer(dory_ctx *ctx, uint32_t layer);
  * count the aggregations that ran on bf16 rows per kernel family (eager calls and recordings, not replays); timing family
  * "bf16_convert" times the conversions. */
 
+/* 16-byte gathers of those bf16 rows (option "gcn_bf16_wide", default 0; GCN contexts only; read by every call).  1 changes
+ * the lane mapping of the K1s launches on bf16 rows of 128 floats or more: 16-lane groups on slabs of 128 features, a lane
+ * holding eight consecutive features and fetching them with one 16-byte load -- half the gather instructions per row of the
+ * 8-byte form.  It changes no bit of any result: the same rounded rows, the same fp32 sums in the same order (bit for bit the
+ * 8-byte form's on finite rows), the same layout, gates, schedule around a halo exchange and shadow copy; nothing new is
+ * allocated, so it may be switched inside and outside an epoch-graph recording.  It does not apply -- the aggregation runs
+ * as with 0 -- while "gcn_bf16_gather" is 0 (or 1, for the backward aggregations), to rows narrower than 128 floats, to K1
+ * (and where K1 runs in K1b's place), to lane groups of 8 ("spmm_blk_group"), and where "spmm_sweep_rows" forces 6 or 8 rows
+ * per lane group (the form is built for the 2 .. 5 rows a 16-lane launch takes of a layout).  Values outside {0, 1} are
+ * rejected, 1 also by GAT / multi-head GAT contexts and by dory_configure for them.  Read-only "gcn_bf16_gathers_k1s_wide"
+ * counts the aggregations that ran this form (eager calls and recordings, not replays); "gcn_bf16_gathers_k1s" and
+ * "spmm_launches_k1s" count them too.  Measured: DESIGN.md section 3, profiles/r09_bf16_wide_ab.txt. */
+
 /* Which kernel family ran.  Read-only "spmm_launches_k1s" / "spmm_launches_k1b" / "spmm_launches_k1" count the aggregations
  * (GCN's, and the GAT prototype's) per kernel family, at the point where the family commits to running one: K1s the gated
  * sweep, K1b the partial rows per source block, K1 the row gather.  One aggregation moves exactly one of them by one, however
