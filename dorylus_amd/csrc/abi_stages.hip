@@ -458,6 +458,8 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
 // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
 // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
 // Only the sweep forms have bf16 kernels: where the dispatch below would leave them the call is refused, never run in fp32
+// opt-in "gatmh_bf16_wide" on top of it: where a pass runs on bf16 rows of 128 floats or more with several heads of 16 / 32 / 64
+// features, its gathers fetch eight features per lane (16 bytes) on 16-lane groups -- the narrow bf16 form's bits
 static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
     Adjacency &In = c->adj[ADJ_IN];
     const uint32_t K = c->heads[fl];
@@ -493,7 +495,11 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             // K1s's skeleton: sums in registers over all source blocks, single-pass softmax against the upper-bound shift
             int rc = ensure_scratch(c, gatmh_sweep_scratch_bytes(Sf, c->N, z->ld, el->ld));
             if (rc) return rc;
-            const SweepLaunch sw = sweep_launch(c, Sf, z->ld, sgroup, In.ghosts > 0, gatmh_sweep_rows(Sf, sgroup, shl, 0));
+            // option gatmh_bf16_wide: bf16 rows of 128 floats or more, several heads of 16 / 32 / 64 features, are gathered eight
+            // features per lane on 16-lane groups (same bits; gat_mh_sweep.hip).  Everywhere else: as with 0
+            const bool wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, z->ld) && sweep_supported(sa, Sf, GATMH_WIDE_GROUP);
+            const SweepLaunch sw = wide ? sweep_launch(c, Sf, z->ld, GATMH_WIDE_GROUP, In.ghosts > 0, GATMH_WIDE_ROWS, true)
+                                        : sweep_launch(c, Sf, z->ld, sgroup, In.ghosts > 0, gatmh_sweep_rows(Sf, sgroup, shl, 0));
             if (!sw.done) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
             // the rows the sweep gathers: z / fg_z, or (bf16) their rounded copies in the shadow buffer -- the local rows
             // converted now, the ghost rows once their exchange has landed
@@ -501,11 +507,12 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             if (bf16) {
                 if ((rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
                 c->gatmh_bf16_gathers_fwd++;
+                if (wide) c->gatmh_bf16_gathers_fwd_wide++;
             }
             const float *zs = bf16 ? bf.xl : z->d, *zgs = bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), *a_l = c->weights[fl]["a_l"].d;
             auto part = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
                 HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, sw.G, b_lo,
-                                                         b_hi, accumulate, sw.done, sw.ctl, sw.sflags, c->compute, el->d, fgel->d, bf16));
+                                                         b_hi, accumulate, sw.done, sw.ctl, sw.sflags, c->compute, el->d, fgel->d, bf16, wide));
                 return DORY_OK;
             };
             HIPCK(c, launch_gatmh_sweep_begin(c->N, In.ghosts, K, z->ld, el->ld, Sf, el->d, fgel->d, c->scratch, c->compute));
@@ -578,7 +585,12 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
     if ((rc = gatmh_backward_exchange(c, T))) return rc;
     if ((rc = ensure_scratch(c, gatmh_src_sweep_scratch_bytes(So, c->N, Out.ghosts, K, ld, ldk)))) return rc;
     const int sgroup = ld >= 128 ? 32 : 16;
-    const SweepLaunch sw = sweep_launch(c, So, ld, sgroup, Out.ghosts > 0, gatmh_sweep_rows(So, sgroup, shl, 1));
+    SpmmArgs sa{};
+    sa.N = c->N; sa.ld = ld;
+    // option gatmh_bf16_wide, as in the forward pass: the source side's bf16 rows eight features per lane (same bits)
+    const bool wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, ld) && sweep_supported(sa, So, GATMH_WIDE_GROUP);
+    const SweepLaunch sw = wide ? sweep_launch(c, So, ld, GATMH_WIDE_GROUP, Out.ghosts > 0, GATMH_WIDE_ROWS, true)
+                                : sweep_launch(c, So, ld, sgroup, Out.ghosts > 0, gatmh_sweep_rows(So, sgroup, shl, 1));
     if (!sw.done) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
     {
         Timed t(c, "spmm", c->compute);
@@ -588,11 +600,12 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
         if (bf16) {
             if ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed())) return rc;
             c->gatmh_bf16_gathers_src++;
+            if (wide) c->gatmh_bf16_gathers_src_wide++;
         }
         const float *dos = bf16 ? bf.xl : T.dO->d, *dogs = bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr);
         auto part = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
             HIPCK(c, launch_gatmh_src_sweep_part(c->N, Out.ghosts, K, D, ld, ldk, So, dos, dogs, T.el->d, T.dz->d, c->scratch, sw.G, b_lo, b_hi,
-                                                 accumulate, sw.done, sw.ctl, sw.sflags, c->compute, bf16));
+                                                 accumulate, sw.done, sw.ctl, sw.sflags, c->compute, bf16, wide));
             return DORY_OK;
         };
         HIPCK(c, launch_gatmh_src_sweep_begin(c->N, Out.ghosts, K, ld, ldk, So, st4, reinterpret_cast<const float4 *>(T.bgst->d), lds4,

@@ -199,6 +199,7 @@ struct dory_ctx {
     uint64_t bf16_gathers_k1s = 0, bf16_gathers_k1 = 0, bf16_gathers_k1s_wide = 0;   // (_wide: those of _k1s that ran the wide form, option gcn_bf16_wide)
     uint64_t spmm_launches_k1s = 0, spmm_launches_k1b = 0, spmm_launches_k1 = 0;   // aggregations per kernel family (read-only options of the same names)
     uint64_t gatmh_bf16_gathers_fwd = 0, gatmh_bf16_gathers_src = 0;   // multi-head GAT: forward edge passes, source-side passes
+    uint64_t gatmh_bf16_gathers_fwd_wide = 0, gatmh_bf16_gathers_src_wide = 0;   // (those of them that ran the wide form, option gatmh_bf16_wide)
     std::vector<std::map<std::string, dory::Tensor>> tensors;   // [layer][name]
     std::vector<std::map<std::string, dory::Tensor>> weights;   // "w", "a_i"
     std::vector<std::map<std::string, dory::Tensor>> wgrads;    // same names
@@ -454,6 +455,10 @@ hipError_t launch_gatmh_backward_blocked_src(uint32_t N, uint32_t K, uint32_t D,
 // single-pass softmax against a per-(v,k) upper-bound shift; the destination side of the backward pass needs no edges
 int gatmh_sweep_hl(uint32_t K, uint32_t D, uint32_t ld);   // lanes per head; 0 = shape not covered (blocked kernels)
 int gatmh_sweep_rows(const BlockedAdj &S, int group, int HL, int pass /*0 forward, 1 source side*/);   // rows per lane group of a launch
+// the wide form of the passes on bf16 rows (option gatmh_bf16_wide; gatmh_*_sweep_bf16x8_kernel): 16-lane groups, two rows per group,
+// eight features per lane -- rows of 128 floats or more, several heads of 16 / 32 / 64 features
+bool gatmh_wide_applies(uint32_t K, uint32_t D, uint32_t ld);
+constexpr int GATMH_WIDE_GROUP = 16, GATMH_WIDE_ROWS = 2;
 size_t gatmh_sweep_scratch_bytes(const BlockedAdj &S, uint32_t N, uint32_t ld, uint32_t ldk);
 hipError_t launch_gatmh_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *el,
                                     const float *elg, float *scratch, hipStream_t s);
@@ -461,7 +466,8 @@ hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, u
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
                                            float *scratch, uint32_t cus, uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done,
                                            const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg /* the sources' scores (local, ghost rows) */,
-                                           bool bf16 = false /* z / zg point at bf16 rows of ld elements (launch_bf16_rows; option gatmh_bf16_gather) */);
+                                           bool bf16 = false /* z / zg point at bf16 rows of ld elements (launch_bf16_rows; option gatmh_bf16_gather) */,
+                                           bool wide = false /* bf16 rows, eight features per lane (option gatmh_bf16_wide): where gatmh_wide_applies() */);
 hipError_t launch_gatmh_forward_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                              const uint32_t *rowidx, const BlockedAdj &S, const float *z, const float *zg, const float *el,
                                              const float *elg, const float *er, float *o, float *op, float *m, float *den, float *dpos,
@@ -476,7 +482,8 @@ hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                        const float *d_o, const float *dog, const float *el, float *dz, float *scratch, uint32_t cus,
                                        uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags,
-                                       hipStream_t s, bool bf16 = false /* d_o / dog point at bf16 rows (option gatmh_bf16_gather = 2) */);
+                                       hipStream_t s, bool bf16 = false /* d_o / dog point at bf16 rows (option gatmh_bf16_gather = 2) */,
+                                       bool wide = false /* eight features per lane (option gatmh_bf16_wide): where gatmh_wide_applies() */);
 hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *z,
                                          const float *el, const float *d_o, const float *der, const float *a_l, const float *a_r, float *del,
                                          float *dz, float *scratch, hipStream_t s,

@@ -66,6 +66,15 @@ namespace dory {
 #ifndef GATMH_SRC16_ROWS
 #define GATMH_SRC16_ROWS 2
 #endif
+// the wide bf16 forms (option gatmh_bf16_wide: eight features per lane on 16-lane groups, two rows per group, loader wave):
+// gathers per batch.  Four spill in the forward (128 registers + 3-4 in scratch), three do not
+// (GATMH_WIDE_ROWS = 2, ctx.hpp: three or more rows per group do not fit 128 registers at any batch size)
+#ifndef GATMH_FWD_WIDE_BATCH
+#define GATMH_FWD_WIDE_BATCH 3
+#endif
+#ifndef GATMH_SRC_WIDE_BATCH
+#define GATMH_SRC_WIDE_BATCH 3
+#endif
 #ifndef GATMH_SRC_BATCH
 #define GATMH_SRC_BATCH 3
 #endif
@@ -126,12 +135,26 @@ __global__ __launch_bounds__(256) void gatmh_elmax_kernel(uint32_t N, uint32_t G
 // BF16 (option gatmh_bf16_gather >= 1; gatmh_forward_sweep_bf16_kernel): a.xl / a.xg hold the rows of z / fg_z rounded to bf16
 // (launch_bf16_rows) -- the skeleton gathers 8 bytes per lane and hands entry() the expanded float4, so the score formed from
 // the row (<z_u, a_l>, the form without the el table) is the rounded row's; the el table, er, the shift and every sum stay fp32
-template <int GROUP, int HL, int R, bool BF16 = false>
+// WIDE (option gatmh_bf16_wide on top of it; gatmh_forward_sweep_bf16x8_kernel; rows of 128 floats or more, heads of 16 / 32 / 64
+// features): the skeleton's WIDE_ROWS form -- 16-lane groups on the same 128-feature slabs, a lane holds EIGHT consecutive
+// features (one 16-byte gather of bf16, handed over as a Float4x2), a head spans HL = D / 8 lanes instead of D / 4: half the
+// gather instructions, half the lanes that repeat a head's exp, compare and (den, dpos) update, one DPP step fewer per score.
+// The outputs are the narrow bf16 form's BIT FOR BIT, because every sum keeps its order:
+//   * a wide lane holds the features of two neighbouring narrow lanes.  It forms each half's s = p.x + p.y exactly as its narrow
+//     lane does and adds the two -- the first step of the narrow lanes' pairwise tree (lanes 2j and 2j + 1: fp32 addition
+//     commutes, so both narrow lanes hold this very number) -- then runs the tree's remaining log2(D / 8) steps, each of which
+//     adds the sum of the OTHER half of the lanes gathered so far, as the narrow tree's step does;
+//   * the score is formed from the gathered row here as there (never from the el table: AUX_BATCH is false whatever GROUP is --
+//     the table holds scores of the unrounded z);
+//   * everything after the score is per lane and per feature in the same entry order: exp2, the branch test t1 > t2, the fma
+//     sums, (den, dpos), the pieces of split rows, the accumulating second launch.
+template <int GROUP, int HL, int R, bool BF16 = false, bool WIDE = false>
 struct GatFwdSweepOp {
-    static constexpr bool PLAIN = false, UNIT_W = true, PROLOGUE = true, AUX_BATCH = (GROUP <= GATMH_FWD_EL_TABLE);
-    static constexpr bool BF16_ROWS = BF16;
+    static_assert(!WIDE || (BF16 && GROUP == 16 && HL >= 2 && HL <= 8), "eight features per lane: bf16 rows, 16-lane groups, heads of 16 / 32 / 64 features");
+    static constexpr bool PLAIN = false, UNIT_W = true, PROLOGUE = true, AUX_BATCH = !WIDE && (GROUP <= GATMH_FWD_EL_TABLE);
+    static constexpr bool BF16_ROWS = BF16, WIDE_ROWS = WIDE;
     static constexpr int EPL = HL >= 4 ? 4 : 2;
-    static constexpr int BATCH = GROUP == 16 ? GATMH_FWD16_BATCH : GATMH_FWD_BATCH;
+    static constexpr int BATCH = WIDE ? GATMH_FWD_WIDE_BATCH : GROUP == 16 ? GATMH_FWD16_BATCH : GATMH_FWD_BATCH;
     static constexpr int SLACK = GATMH_SLACK;
     static constexpr int HPS = GROUP / HL;                     // heads per slab of GROUP lanes
     static constexpr int RW = (SWEEP_NT / GROUP) * R;
@@ -148,8 +171,11 @@ struct GatFwdSweepOp {
     uint32_t k, hl, aux_b, qpos;
     __amdgpu_buffer_rsrc_t rs2;
     const float2 *ctab;
+    float4 al4h;                                               // WIDE: a_l of the lane's features 4 .. 7
     typedef float f2 __attribute__((ext_vector_type(2)));
-    struct Row { float4 acc, accp; f2 den; };                  // den = (all edges, positive-branch edges)
+    struct Row4 { float4 acc, accp; f2 den; };                 // den = (all edges, positive-branch edges)
+    struct Row8 { float4 acc, accp, acc2, accp2; f2 den; };    // WIDE: features 0-3 and 4-7 of the lane's chunk
+    typedef typename std::conditional<WIDE, Row8, Row4>::type Row;
     struct RowC { float c1, c2; };
     typedef float Aux;                                          // AUX_BATCH: el[src, k]
     __device__ __forceinline__ Aux aux(uint32_t, uint32_t, bool) const { return 0.f; }
@@ -175,6 +201,7 @@ struct GatFwdSweepOp {
     }
     __device__ __forceinline__ void init(Row &r) const {
         r.acc = make_float4(0.f, 0.f, 0.f, 0.f); r.accp = r.acc; r.den = (f2){0.f, 0.f};
+        if constexpr (WIDE) { r.acc2 = r.acc; r.accp2 = r.acc; }
     }
     __device__ __forceinline__ void prologue(const SpmmArgs &a, const BlockedAdj &B, uint32_t pos0, uint32_t xend, bool ghost_launch, uint32_t col, int li) {
         __shared__ float2 tab[RW * HPS];
@@ -198,9 +225,12 @@ struct GatFwdSweepOp {
             aux_b = k * 4u - (ghost_launch ? a.N : 0u) * ldk * 4u;
             qpos = (uint32_t)li & (HL >= 4 ? 3u : 1u);
         }
-        const uint32_t f0 = col * 4, KD = K * D;               // a_l is a dense K x D vector (41-feature heads end mid-float4)
+        const uint32_t f0 = col * (WIDE ? 8 : 4), KD = K * D;  // a_l is a dense K x D vector (41-feature heads end mid-float4)
         al4 = make_float4(f0 < KD ? a_l[f0] * GATMH_LOG2E : 0.f, f0 + 1 < KD ? a_l[f0 + 1] * GATMH_LOG2E : 0.f,
                           f0 + 2 < KD ? a_l[f0 + 2] * GATMH_LOG2E : 0.f, f0 + 3 < KD ? a_l[f0 + 3] * GATMH_LOG2E : 0.f);
+        if constexpr (WIDE)
+            al4h = make_float4(f0 + 4 < KD ? a_l[f0 + 4] * GATMH_LOG2E : 0.f, f0 + 5 < KD ? a_l[f0 + 5] * GATMH_LOG2E : 0.f,
+                               f0 + 6 < KD ? a_l[f0 + 6] * GATMH_LOG2E : 0.f, f0 + 7 < KD ? a_l[f0 + 7] * GATMH_LOG2E : 0.f);
     }
     __device__ __forceinline__ RowC row_const(uint32_t lrow) const {
         const float2 c = ctab[lrow * HPS + hl];
@@ -231,8 +261,49 @@ struct GatFwdSweepOp {
         r.acc = fma4(al, x, r.acc);
         r.accp = fma4(alp, x, r.accp);
     }
+    // WIDE: the entry of eight features (the comment above the struct: why these are the narrow form's bits)
+    template <bool FULL>
+    __device__ __forceinline__ void entry(Row &r, const RowC &c, const Float4x2 &x, Aux, bool on) const {
+        static_assert(WIDE, "eight features per entry: the wide form");
+        const f2 xlo = {x.lo.x, x.lo.y}, xhi = {x.lo.z, x.lo.w}, alo = {al4.x, al4.y}, ahi = {al4.z, al4.w};
+        const f2 ylo = {x.hi.x, x.hi.y}, yhi = {x.hi.z, x.hi.w}, blo = {al4h.x, al4h.y}, bhi = {al4h.z, al4h.w};
+        const f2 p = __builtin_elementwise_fma(xhi, ahi, xlo * alo);                 // the narrow lane 2j's
+        const f2 q = __builtin_elementwise_fma(yhi, bhi, ylo * blo);                 // the narrow lane 2j + 1's
+        const float e = sw_head_sum<HL>((p.x + p.y) + (q.x + q.y));                   // (the tree's first step, then the rest)
+        const f2 ee = {e, e}, cc = {c.c1, c.c2}, kk = {1.f, GATMH_SLOPE};
+        const f2 t = __builtin_elementwise_fma(ee, kk, cc);
+        float al = __builtin_amdgcn_exp2f(fmaxf(t.x, t.y));
+        if constexpr (!FULL) al = on ? al : 0.f;
+        const float alp = t.x > t.y ? al : 0.f;
+        r.den += (f2){al, alp};
+        r.acc = fma4(al, x.lo, r.acc);
+        r.accp = fma4(alp, x.lo, r.accp);
+        r.acc2 = fma4(al, x.hi, r.acc2);
+        r.accp2 = fma4(alp, x.hi, r.accp2);
+    }
     __device__ __forceinline__ void store(const Row &r, const SpmmArgs &a, const SweepArgs &w, uint32_t v, bool piece, uint32_t slot,
                                           uint32_t col, uint32_t nchunk, const float4 *) const {
+        if constexpr (WIDE) {   // col, nchunk count eight features: two float4 per tensor, at the addresses the narrow form's two lanes write
+            const size_t at = ((size_t)(piece ? slot : v) * nchunk + col) * 2;
+            float4 *q = reinterpret_cast<float4 *>(piece ? w.split_partial : a.out) + at;
+            float4 *qp = reinterpret_cast<float4 *>(piece ? pos_slots : accp) + at;
+            float2 *dq = reinterpret_cast<float2 *>(piece ? den_slots + (size_t)slot * 2 * ldk : dacc + (size_t)v * 2 * ldk) + k;
+            float4 o0 = r.acc, o1 = r.acc2, p0 = r.accp, p1 = r.accp2;
+            float2 dn = make_float2(r.den.x, r.den.y);
+            const bool head_lane = (threadIdx.x % HL) == 0 && col * 8 < K * D;
+            if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {
+                const float4 a0 = q[0], a1 = q[1], b0 = qp[0], b1 = qp[1];
+                o0.x += a0.x; o0.y += a0.y; o0.z += a0.z; o0.w += a0.w;
+                o1.x += a1.x; o1.y += a1.y; o1.z += a1.z; o1.w += a1.w;
+                p0.x += b0.x; p0.y += b0.y; p0.z += b0.z; p0.w += b0.w;
+                p1.x += b1.x; p1.y += b1.y; p1.z += b1.z; p1.w += b1.w;
+                if (head_lane) { const float2 d0 = *dq; dn.x += d0.x; dn.y += d0.y; }
+            }
+            q[0] = o0; q[1] = o1;
+            qp[0] = p0; qp[1] = p1;
+            if (head_lane) *dq = dn;
+            return;
+        }
         float4 *q = piece ? reinterpret_cast<float4 *>(w.split_partial) + (size_t)slot * nchunk + col
                           : reinterpret_cast<float4 *>(a.out) + (size_t)v * nchunk + col;
         float4 *qp = piece ? reinterpret_cast<float4 *>(pos_slots) + (size_t)slot * nchunk + col
@@ -269,6 +340,19 @@ __global__ __launch_bounds__(SWEEP_NT) void gatmh_forward_sweep_bf16_kernel(Spmm
                                                                             uint32_t ldk, const float *el, const float *elg) {
     GatFwdSweepOp<GROUP, HL, R, true> op{er, a_l, elmax_key, accp, dacc, pos_slots, den_slots, K, D, ldk, el, elg};
     sweep_run<GROUP, R, false, LOADER>(a, B, w, op);
+}
+
+// the same over bf16 rows with eight features per lane (option gatmh_bf16_wide; GatFwdSweepOp<.., WIDE>): 16-lane groups, HL = D / 8
+// lanes per head.  Two rows per group with the loader wave and batches of three gathers is what fits 128 registers without
+// scratch (tests/test_gatmh_bf16_wide_resources.py): the only form instantiated, and the 128 rows per workgroup and step of
+// the narrow form's four rows on 32 lanes.
+template <int HL, int R, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void gatmh_forward_sweep_bf16x8_kernel(SpmmArgs a, BlockedAdj B, SweepArgs w, const float *er,
+                                                                              const float *a_l, const int *elmax_key, float *accp, float *dacc,
+                                                                              float *pos_slots, float *den_slots, uint32_t K, uint32_t D,
+                                                                              uint32_t ldk) {
+    GatFwdSweepOp<16, HL, R, true, true> op{er, a_l, elmax_key, accp, dacc, pos_slots, den_slots, K, D, ldk, nullptr, nullptr};
+    sweep_run<16, R, false, LOADER>(a, B, w, op);
 }
 
 // pieces of split rows: dst[v,:] = sum of the pieces' slots (piece order), for a row tensor (width ld) and a per-head one
@@ -430,13 +514,17 @@ __global__ void gatmh_stx_kernel(uint64_t n /*rows x K*/, uint32_t K, const floa
 
 // BF16 (option gatmh_bf16_gather = 2; gatmh_src_sweep_bf16_kernel): a.xl / a.xg hold the rows of do / bg_do rounded to bf16; the
 // statistics records (second gather), el and every sum stay fp32
-template <int GROUP, int HL, int R, bool BF16 = false>
+// WIDE (option gatmh_bf16_wide; gatmh_src_sweep_bf16x8_kernel): eight features per lane on 16-lane groups, HL = D / 8 lanes per
+// head, as GatFwdSweepOp's wide form.  Nothing here crosses lanes but the spread of the statistics records, which moves bits:
+// alpha, the branch test and every sum are per lane and per feature in the narrow form's entry order -- the same bits.
+template <int GROUP, int HL, int R, bool BF16 = false, bool WIDE = false>
 struct GatSrcSweepOp {
-    static constexpr bool BF16_ROWS = BF16;
+    static_assert(!WIDE || (BF16 && GROUP == 16 && HL >= 2 && HL <= 8), "eight features per lane: bf16 rows, 16-lane groups, heads of 16 / 32 / 64 features");
+    static constexpr bool BF16_ROWS = BF16, WIDE_ROWS = WIDE;
     // (the destinations' statistics fetched once per batch through the LDS crossbar instead of once per entry: measured, no gain --
     // profiles/r05_gatmh_src_aux_batch_experiment.patch)
     static constexpr bool PLAIN = false, UNIT_W = true, PROLOGUE = true, AUX_BATCH = GATMH_SRC_AUX_MODE == 3;
-    static constexpr int BATCH = GROUP == 16 ? GATMH_SRC16_BATCH : GATMH_SRC_BATCH;   // two gathers per entry (rows, statistics); 16-lane groups: four lane groups per gather instruction
+    static constexpr int BATCH = WIDE ? GATMH_SRC_WIDE_BATCH : GROUP == 16 ? GATMH_SRC16_BATCH : GATMH_SRC_BATCH;   // two gathers per entry (rows, statistics); 16-lane groups: four lane groups per gather instruction
     static constexpr int EPL = HL >= 4 ? 4 : 2;    // AUX_BATCH: entries one statistics gather serves (the lanes of a quad that share a head)
     static constexpr int SLACK = GATMH_SLACK;
     static constexpr int HPS = GROUP / HL;
@@ -453,11 +541,14 @@ struct GatSrcSweepOp {
     __amdgpu_buffer_rsrc_t rs2;
     const float2 *etab;
     typedef float f2 __attribute__((ext_vector_type(2)));
-    struct Row { float4 s, sp; f2 tt; };
+    struct Row4 { float4 s, sp; f2 tt; };
+    struct Row8 { float4 s, sp, s2, sp2; f2 tt; };   // WIDE: features 0-3 and 4-7 of the lane's chunk
+    typedef typename std::conditional<WIDE, Row8, Row4>::type Row;
     struct RowC { f2 e; };          // (el'_u, 0.2 el'_u)
     typedef float3 Aux;             // (c1', c2', t): a 12-byte load (a register less per gather in flight than the 16 bytes)
     __device__ __forceinline__ void init(Row &r) const {
         r.s = make_float4(0.f, 0.f, 0.f, 0.f); r.sp = r.s; r.tt = (f2){0.f, 0.f};
+        if constexpr (WIDE) { r.s2 = r.s; r.sp2 = r.s; }
     }
     __device__ __forceinline__ void prologue(const SpmmArgs &a, const BlockedAdj &B, uint32_t pos0, uint32_t xend, bool ghost_launch, uint32_t col, int li) {
         __shared__ float2 tab[RW * HPS];
@@ -524,8 +615,42 @@ struct GatSrcSweepOp {
         r.s = fma4(al, x, r.s);
         r.sp = fma4(alp, x, r.sp);
     }
+    template <bool FULL>
+    __device__ __forceinline__ void entry(Row &r, const RowC &c, const Float4x2 &x, const Aux &sv, bool on) const {
+        static_assert(WIDE, "eight features per entry: the wide form");
+        const f2 t = c.e + (f2){sv.x, sv.y};
+        float al = __builtin_amdgcn_exp2f(fmaxf(t.x, t.y));
+        if constexpr (!FULL) al = on ? al : 0.f;
+        const float alp = t.x > t.y ? al : 0.f;
+        r.tt = __builtin_elementwise_fma((f2){al, alp}, (f2){sv.z, sv.z}, r.tt);
+        r.s = fma4(al, x.lo, r.s);
+        r.sp = fma4(alp, x.lo, r.sp);
+        r.s2 = fma4(al, x.hi, r.s2);
+        r.sp2 = fma4(alp, x.hi, r.sp2);
+    }
     __device__ __forceinline__ void store(const Row &r, const SpmmArgs &a, const SweepArgs &w, uint32_t u, bool piece, uint32_t slot,
                                           uint32_t col, uint32_t nchunk, const float4 *) const {
+        if constexpr (WIDE) {   // col, nchunk count eight features: two float4 per tensor, at the addresses the narrow form's two lanes write
+            const size_t at = ((size_t)(piece ? slot : u) * nchunk + col) * 2;
+            float4 *q = reinterpret_cast<float4 *>(piece ? w.split_partial : a.out) + at;
+            float4 *qp = reinterpret_cast<float4 *>(piece ? pos_slots : sp) + at;
+            float2 *tq = reinterpret_cast<float2 *>(piece ? t_slots + (size_t)slot * 2 * ldk : tacc + (size_t)u * 2 * ldk) + k;
+            float4 s0 = r.s, s1 = r.s2, p0 = r.sp, p1 = r.sp2;
+            float2 t2 = make_float2(r.tt.x, r.tt.y);
+            const bool head_lane = (threadIdx.x % HL) == 0 && col * 8 < K * D;
+            if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {
+                const float4 a0 = q[0], a1 = q[1], b0 = qp[0], b1 = qp[1];
+                s0.x += a0.x; s0.y += a0.y; s0.z += a0.z; s0.w += a0.w;
+                s1.x += a1.x; s1.y += a1.y; s1.z += a1.z; s1.w += a1.w;
+                p0.x += b0.x; p0.y += b0.y; p0.z += b0.z; p0.w += b0.w;
+                p1.x += b1.x; p1.y += b1.y; p1.z += b1.z; p1.w += b1.w;
+                if (head_lane) { const float2 d0 = *tq; t2.x += d0.x; t2.y += d0.y; }
+            }
+            q[0] = s0; q[1] = s1;
+            qp[0] = p0; qp[1] = p1;
+            if (head_lane) *tq = t2;
+            return;
+        }
         float4 *q = piece ? reinterpret_cast<float4 *>(w.split_partial) + (size_t)slot * nchunk + col
                           : reinterpret_cast<float4 *>(a.out) + (size_t)u * nchunk + col;
         float4 *qp = piece ? reinterpret_cast<float4 *>(pos_slots) + (size_t)slot * nchunk + col
@@ -562,6 +687,17 @@ __global__ __launch_bounds__(SWEEP_NT) void gatmh_src_sweep_bf16_kernel(SpmmArgs
                                                                         uint32_t G) {
     GatSrcSweepOp<GROUP, HL, R, true> op{el, stx, stxg, sp, tacc, pos_slots, t_slots, K, D, ldk, a.N, G};
     sweep_run<GROUP, R, false, LOADER>(a, B, w, op);
+}
+
+// the same over bf16 rows with eight features per lane (option gatmh_bf16_wide; GatSrcSweepOp<.., WIDE>): two rows per 16-lane
+// group, loader wave, as gatmh_forward_sweep_bf16x8_kernel
+template <int HL, int R, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void gatmh_src_sweep_bf16x8_kernel(SpmmArgs a, BlockedAdj B, SweepArgs w, const float *el,
+                                                                          const float4 *stx, const float4 *stxg, float *sp, float *tacc,
+                                                                          float *pos_slots, float *t_slots, uint32_t K, uint32_t D, uint32_t ldk,
+                                                                          uint32_t G) {
+    GatSrcSweepOp<16, HL, R, true, true> op{el, stx, stxg, sp, tacc, pos_slots, t_slots, K, D, ldk, a.N, G};
+    sweep_run<16, R, false, LOADER>(a, B, w, op);
 }
 
 // dz[u,:] = S + alpha_self dO[u,:] + del[u,k] a_l + der[u,k] a_r,   del[u,k] = <Z[u,k,:], 0.2 S' + 0.8 S+'> - (0.2 T' + 0.8 T+')
@@ -625,6 +761,12 @@ int gatmh_sweep_hl(uint32_t K, uint32_t D, uint32_t ld) {
     if ((D & 3) || (D & (D - 1))) return 0;
     const int hl = (int)(D / 4);
     return (hl >= 2 && hl <= 16 && hl <= group) ? hl : 0;
+}
+
+// does a pass on bf16 rows take the wide form (option gatmh_bf16_wide: eight features per lane, D / 8 lanes per head, on 16-lane
+// groups)?  Rows of 128 floats or more, several heads of 16, 32 or 64 features (8: a head inside one lane, not built)
+bool gatmh_wide_applies(uint32_t K, uint32_t D, uint32_t ld) {
+    return ld >= 128 && !(ld & 7) && K > 1 && (D == 16 || D == 32 || D == 64) && gatmh_sweep_hl(K, D, ld) == (int)(D / 4);
 }
 
 // rows per lane group of a launch.  The layout is dealt for the 32-lane launches; a launch walks its positions with as many
@@ -692,7 +834,8 @@ hipError_t launch_gatmh_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t
 
 // geometry of one launch over the source blocks [b_lo, b_hi) of a sweep layout (as launch_spmm_sweep)
 static bool gatmh_sweep_geom(const SpmmArgs &a, const BlockedAdj &S, int group, int R, uint32_t cus, uint32_t b_lo, uint32_t b_hi,
-                             bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags, float *pieces, SweepArgs *w, dim3 *grid) {
+                             bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags, float *pieces, SweepArgs *w, dim3 *grid,
+                             bool wide = false /* chunks of eight features: the same 128-feature slabs on 16-lane groups */) {
     if (!sweep_supported(a, S, group) || b_hi > S.nb || cus == 0 || cus > 32 || !ctl.stat) return false;
     if (b_lo < S.nb_local && b_hi > S.nb_local) return false;
     if (b_lo >= S.nb_local && !a.xg) return false;
@@ -703,7 +846,7 @@ static bool gatmh_sweep_geom(const SpmmArgs &a, const BlockedAdj &S, int group, 
     w->tiles_x = (w->rpx + RW - 1) / RW;
     w->G = cus;
     const uint32_t spp = (w->tiles_x + cus - 1) / cus;
-    const uint32_t slabs = ((a.ld >> 2) + group - 1) / group;
+    const uint32_t slabs = ((a.ld >> (wide ? 3 : 2)) + group - 1) / group;
     w->nsweeps = slabs * spp;
     w->b_lo = b_lo; w->b_hi = b_hi;
     w->done = done;
@@ -719,20 +862,28 @@ static bool gatmh_sweep_geom(const SpmmArgs &a, const BlockedAdj &S, int group, 
 hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
                                            float *scratch, uint32_t cus, uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done,
-                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg, bool bf16) {
+                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg, bool bf16,
+                                           bool wide) {
     if (N == 0 || b_lo >= b_hi) return hipSuccess;
-    const int group = ld >= 128 ? 32 : 16;
-    const int HL = gatmh_sweep_hl(K, D, ld);
+    if (wide && !(bf16 && gatmh_wide_applies(K, D, ld))) return hipErrorInvalidValue;
+    const int group = wide ? GATMH_WIDE_GROUP : ld >= 128 ? 32 : 16;
+    const int HL = wide ? (int)(D / 8) : gatmh_sweep_hl(K, D, ld);
     SpmmArgs a{};
     a.N = N; a.F = K * D; a.ld = ld; a.xl = z; a.xg = zg; a.out = o; a.accumulate = accumulate ? 1 : 0; a.self_mode = 0;
-    const int R = gatmh_sweep_rows(S, group, HL, 0);
+    const int R = wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(S, group, HL, 0);
     const GatSweepScratch c = gatmh_carve(scratch, S, N, ld, ldk);
     SweepArgs w;
     dim3 gr;
-    if (!HL || !gatmh_sweep_geom(a, S, group, R, cus, b_lo, b_hi, accumulate, done, ctl, flags, c.pieces, &w, &gr)) return hipErrorInvalidValue;
+    if (!HL || !gatmh_sweep_geom(a, S, group, R, cus, b_lo, b_hi, accumulate, done, ctl, flags, c.pieces, &w, &gr, wide)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(done, 0, ((size_t)8 * w.nsweeps * (b_hi - b_lo) * 32 + 1) * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
+    if (wide) {   // one form: two rows per 16-lane group, loader wave
+#define GFW(HLV) hipLaunchKernelGGL((gatmh_forward_sweep_bf16x8_kernel<HLV, GATMH_WIDE_ROWS, true>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk)
+        if (HL == 2) GFW(2); else if (HL == 4) GFW(4); else GFW(8);
+#undef GFW
+        return hipGetLastError();
+    }
 #define GFS(GRP, HLV, RR, LD)                                                                                                                    \
     do {                                                                                                                                         \
         if (bf16) hipLaunchKernelGGL((gatmh_forward_sweep_bf16_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk, el, elg); \
@@ -822,22 +973,29 @@ hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                        const float *d_o, const float *dog, const float *el, float *dz, float *scratch, uint32_t cus,
                                        uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags,
-                                       hipStream_t s, bool bf16) {
+                                       hipStream_t s, bool bf16, bool wide) {
     if (N == 0 || b_lo >= b_hi) return hipSuccess;
-    const int group = ld >= 128 ? 32 : 16;
-    const int HL = gatmh_sweep_hl(K, D, ld);
+    if (wide && !(bf16 && gatmh_wide_applies(K, D, ld))) return hipErrorInvalidValue;
+    const int group = wide ? GATMH_WIDE_GROUP : ld >= 128 ? 32 : 16;
+    const int HL = wide ? (int)(D / 8) : gatmh_sweep_hl(K, D, ld);
     SpmmArgs a{};
     a.N = N; a.F = K * D; a.ld = ld; a.xl = d_o; a.xg = dog; a.out = dz; a.accumulate = accumulate ? 1 : 0; a.self_mode = 0;
-    const int R = gatmh_sweep_rows(S, group, HL, 1);
+    const int R = wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(S, group, HL, 1);
     const GatSrcScratch c = gatmh_src_carve(scratch, S, N, K, ld, ldk);
     SweepArgs w;
     dim3 gr;
     if (!HL || (uint64_t)(N > G ? N : G) * K * 16u >= (1ull << 32) || K * 16u >= (1u << 24) ||
-        !gatmh_sweep_geom(a, S, group, R, cus, b_lo, b_hi, accumulate, done, ctl, flags, c.pieces, &w, &gr))
+        !gatmh_sweep_geom(a, S, group, R, cus, b_lo, b_hi, accumulate, done, ctl, flags, c.pieces, &w, &gr, wide))
         return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(done, 0, ((size_t)8 * w.nsweeps * (b_hi - b_lo) * 32 + 1) * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
+    if (wide) {   // one form: two rows per 16-lane group, loader wave
+#define GSW(HLV) hipLaunchKernelGGL((gatmh_src_sweep_bf16x8_kernel<HLV, GATMH_WIDE_ROWS, true>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G)
+        if (HL == 2) GSW(2); else if (HL == 4) GSW(4); else GSW(8);
+#undef GSW
+        return hipGetLastError();
+    }
 #define GSS(GRP, HLV, RR, LD)                                                                                                                    \
     do {                                                                                                                                         \
         if (bf16) hipLaunchKernelGGL((gatmh_src_sweep_bf16_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G); \

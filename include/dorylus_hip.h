@@ -352,6 +352,22 @@ int dory_transform_first_layer(dory_ctx *ctx, uint32_t layer);
  * Read-only "gatmh_bf16_gathers_fwd" / "gatmh_bf16_gathers_src" count the passes that ran on bf16 rows (eager calls and
  * recordings, not replays); timing family "bf16_convert" times the conversions.  Measured: profiles/r08_gatmh_bf16_ab.txt. */
 
+/* 16-byte gathers of those bf16 rows (option "gatmh_bf16_wide", default 0; DORY_GATMH contexts only; read by every call).  1
+ * changes the lane mapping of the sweep launches that run on bf16 rows: 16-lane groups on the same slabs of 128 features, a
+ * lane holding eight consecutive features and fetching them with one 16-byte load, a head of D features spanning D / 8 lanes
+ * instead of D / 4 -- half the gather instructions per row and half the lanes that repeat a head's exponential, branch test
+ * and statistics update per edge.  It changes no bit of any result: the same rounded rows, the score formed from the gathered
+ * row with the sums in the 8-byte form's order, every later sum per feature in the same entry order, the same layout, gates,
+ * two launches around an exchange, pieces of split rows and shadow copy; nothing new is allocated, so it may be switched
+ * inside and outside an epoch-graph recording.  It takes effect on a pass that already runs on bf16 rows ("gatmh_bf16_gather"
+ * >= 1 for the forward edge pass, 2 for the backward's source-side pass) of a layer whose rows are 128 floats or wider with
+ * more than one head of 16, 32 or 64 features.  Everywhere else -- heads of 8 features, a single head, narrower rows,
+ * "gatmh_bf16_gather" too small for the pass -- the pass runs exactly as with 0, and no error is raised.  Values outside
+ * {0, 1} are rejected, 1 also by configured DORY_GCN / DORY_GAT contexts and by dory_configure for them.  Read-only
+ * "gatmh_bf16_gathers_fwd_wide" / "gatmh_bf16_gathers_src_wide" count the passes that ran this form (eager calls and
+ * recordings, not replays); "gatmh_bf16_gathers_fwd" / "_src" count them too.  Measured: DESIGN.md section 3,
+ * profiles/r10_gatmh_bf16_wide_ab.txt. */
+
 /* Epoch graph (MI355X-side addition, no reference counterpart): record the calls of one
  * epoch -- dory_aggregate / dory_apply_vertex / dory_apply_edge / dory_predict_gat /
  * dory_weight_update, exactly as Engine::runEpoch issues them -- into a hipGraph and replay
