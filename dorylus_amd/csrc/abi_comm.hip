@@ -58,6 +58,35 @@ void timed_open(dory_ctx *c, const char *fam, hipStream_t s, hipEvent_t *end_out
     *end_out = b;
 }
 
+// Option halo_exact_rows: a packed row holds exactly `cols` floats instead of the padded `ld` -- what the reference ships
+// (featDim floats per row, engine/utils.cpp:623-650).  Every pack and unpack of this file goes through these three.
+inline bool halo_exact(const dory_ctx *c) { return c->halo_exact.load(std::memory_order_acquire) == 1; }
+
+// the plan's send rows of `src`, dense at width w (src->ld, or with `exact` src->cols), into dst; counted (eager calls)
+int pack_rows(dory_ctx *c, float *dst, const Tensor *src, uint32_t w, bool exact, const HaloPlan &p, hipStream_t s) {
+    if (exact && (w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, w, p.d_send_lvids, p.send_total, s));
+    else HIPCK(c, launch_gather_rows(dst, src->d, src->ld, w, p.d_send_lvids, p.send_total, s));
+    if (!c->capturing) {
+        c->halo_rows_packed += p.send_total;
+        c->halo_floats_packed += (uint64_t)p.send_total * w;
+        if (exact && w < src->ld) c->halo_exact_packs++;
+    }
+    return DORY_OK;
+}
+// the received rows, dense at width w, into the plan's ghost slots; the exact form writes the whole row: [0, w) from the
+// buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever the padding held before
+int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, uint32_t w, bool exact, const float *buf, const HaloPlan &p, hipStream_t s) {
+    if (exact && (w & 3)) {
+        HIPCK(c, launch_scatter_rows_exact(ghost, buf, ld, w, p.d_recv_slots, p.recv_total, s));
+    } else {
+        HIPCK(c, launch_scatter_rows(ghost, buf, ld, w, p.d_recv_slots, p.recv_total, s));
+        if (exact && w < ld) HIPCK(c, launch_zero_rows_pad(ghost, ld, w, p.d_recv_slots, p.recv_total, s));
+    }
+    return DORY_OK;
+}
+// a caller's buffer of exact rows is addressed in 16-byte quads of the whole stream when the width is no multiple of 4
+bool exact_ptr_ok(bool exact, uint32_t w, const void *buf) { return !exact || !(w & 3) || !((uintptr_t)buf & 15); }
+
 struct PeerPtrs { const float *p[LOCAL_MAX_RANKS]; };
 __global__ __launch_bounds__(256) void local_sum_kernel(PeerPtrs pp, uint32_t P, uint64_t n, float *out) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -90,7 +119,7 @@ int local_exchange_finish(dory_ctx *c) {
         HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_sent[s & 1], 0));
     }
     lp.on = false;     // (a peer that has not arrived leaves the second half pending: the caller may try again)
-    HIPCK(c, launch_scatter_rows(lp.ghost, c->recv_buf, lp.ghost_ld, lp.w, p.d_recv_slots, p.recv_total, c->comm));
+    { int rc = unpack_rows(c, lp.ghost, lp.ghost_ld, lp.w, lp.exact, c->recv_buf, p, c->comm); if (rc) return rc; }
     HIPCK(c, hipEventRecord(c->ev_cons[s & 1], c->comm));
     c->posted_cons.store(s, std::memory_order_release);
     if (lp.t_kind_b) (void)hipEventRecord(lp.t_kind_b, c->comm);
@@ -101,7 +130,7 @@ int local_exchange_finish(dory_ctx *c) {
 }
 
 // first half: pack, push my rows into every peer's receive buffer, "sent"
-static int local_exchange_send(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, uint32_t w, bool deferred) {
+static int local_exchange_send(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, uint32_t w, bool exact, bool deferred) {
     HaloPlan &p = c->plan[dir];
     LocalGroup &grp = *c->local;
     if (c->local_pending.on) {   // (not reached: every consumer and every exchange calls wait_halo first)
@@ -112,7 +141,7 @@ static int local_exchange_send(dory_ctx *c, int dir, Tensor *src, Tensor *ghost,
     dory_ctx::LocalPending &lp = c->local_pending;
     timed_open(c, "halo", c->comm, &lp.t_halo_b);
     timed_open(c, deferred ? "halo_deferred" : "halo_waited", c->comm, &lp.t_kind_b);
-    HIPCK(c, launch_gather_rows(c->send_buf, src->d, src->ld, w, p.d_send_lvids, p.send_total, c->comm));
+    { int rc = pack_rows(c, c->send_buf, src, w, exact, p, c->comm); if (rc) return rc; }
     for (uint32_t q = 0; q < c->numNodes; ++q) {
         if (q == c->nodeId || !p.send_counts[q]) continue;
         dory_ctx *Q = grp.ctx[q];
@@ -138,6 +167,7 @@ static int local_exchange_send(dory_ctx *c, int dir, Tensor *src, Tensor *ghost,
     lp.ghost = ghost->d;
     lp.ghost_ld = ghost->ld;
     lp.w = w;
+    lp.exact = exact;
     if (deferred) {
         c->halo_pending = true;      // wait_halo(): local_exchange_finish, then the compute stream waits for ev_b
         return DORY_OK;
@@ -356,9 +386,12 @@ int dory_halo_pack(dory_ctx *c, uint32_t layer, int dir, float *send_buf) {
     if (rc) return rc;
     HaloPlan &p = c->plan[dir];
     if (!p.set) return fail(c, DORY_ERR_ARG, "halo_pack: no plan");
+    const bool exact = halo_exact(c);
+    if (exact && src->cols != ghost->cols) return fail(c, DORY_ERR_ARG, "halo_pack: widths of source (%u) and ghost tensor (%u) differ", src->cols, ghost->cols);
+    const uint32_t w = exact ? src->cols : src->ld;
+    if (!exact_ptr_ok(exact, w, send_buf)) return fail(c, DORY_ERR_ARG, "halo_pack: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
     Timed t(c, "halo", c->compute);
-    HIPCK(c, launch_gather_rows(send_buf, src->d, src->ld, src->ld, p.d_send_lvids, p.send_total, c->compute));
-    return DORY_OK;
+    return pack_rows(c, send_buf, src, w, exact, p, c->compute);
 }
 
 int dory_halo_unpack(dory_ctx *c, uint32_t layer, int dir, const float *recv_buf) {
@@ -370,9 +403,12 @@ int dory_halo_unpack(dory_ctx *c, uint32_t layer, int dir, const float *recv_buf
     if (rc) return rc;
     HaloPlan &p = c->plan[dir];
     if (!p.set) return fail(c, DORY_ERR_ARG, "halo_unpack: no plan");
+    const bool exact = halo_exact(c);
+    if (exact && src->cols != ghost->cols) return fail(c, DORY_ERR_ARG, "halo_unpack: widths of source (%u) and ghost tensor (%u) differ", src->cols, ghost->cols);
+    const uint32_t w = exact ? ghost->cols : ghost->ld;
+    if (!exact_ptr_ok(exact, w, recv_buf)) return fail(c, DORY_ERR_ARG, "halo_unpack: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
     Timed t(c, "halo", c->compute);
-    HIPCK(c, launch_scatter_rows(ghost->d, recv_buf, ghost->ld, ghost->ld, p.d_recv_slots, p.recv_total, c->compute));
-    return DORY_OK;
+    return unpack_rows(c, ghost->d, ghost->ld, w, exact, recv_buf, p, c->compute);
 }
 
 }  // extern "C"
@@ -390,7 +426,18 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
         if (c->nranks != (int)c->numNodes) return fail(c, DORY_ERR_COMM, "halo_exchange: communicator size != num_nodes");
     }
     if (src->ld != ghost->ld) return fail(c, DORY_ERR_ARG, "halo_exchange: row widths of source and ghost tensor differ");
-    const uint32_t w = src->ld;  // padded row width travels (keeps 16-B lanes)
+    // the padded row width travels (keeps 16-B lanes), or, with option halo_exact_rows, exactly the tensor's columns
+    const bool exact = halo_exact(c);
+    if (exact && src->cols != ghost->cols) return fail(c, DORY_ERR_ARG, "halo_exchange: widths of source (%u) and ghost tensor (%u) differ", src->cols, ghost->cols);
+    const uint32_t w = exact ? src->cols : src->ld;
+    if (local) {   // every rank packs and unpacks at one width: checked here, before anything of this exchange is enqueued or counted
+        for (uint32_t q = 0; q < c->numNodes; ++q) {
+            dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
+            if (Q && halo_exact(Q) != exact)
+                return fail(c, DORY_ERR_COMM, "local transport: option halo_exact_rows differs: rank %u has %d, rank %u has %d (all ranks must agree)",
+                            c->nodeId, (int)exact, q, (int)!exact);
+        }
+    }
     const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
     if (local && (sb > c->send_cap || rb > c->recv_cap))
         return fail(c, DORY_ERR_COMM, "local transport: exchange buffers too small for %u-float rows (peers hold their addresses: no regrowth)", w);
@@ -412,11 +459,11 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     // comm stream waits for the producer of `src` on the compute stream
     HIPCK(c, hipEventRecord(c->ev_a, c->compute));
     HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
-    if (local) return local_exchange_send(c, dir, src, ghost, w, defer && c->opt["halo_overlap"]);
+    if (local) return local_exchange_send(c, dir, src, ghost, w, exact, defer && c->opt["halo_overlap"]);
     {
         Timed t(c, "halo", c->comm);
         Timed td(c, (defer && c->opt["halo_overlap"]) ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
-        HIPCK(c, launch_gather_rows(c->send_buf, src->d, src->ld, w, p.d_send_lvids, p.send_total, c->comm));
+        { int prc = pack_rows(c, c->send_buf, src, w, exact, p, c->comm); if (prc) return prc; }
         if (c->tx_a2a) {   // host transport: same pack / unpack / events, the bytes travel through the caller
             c->tx_send.resize((size_t)p.send_total * w);
             c->tx_recv.resize((size_t)p.recv_total * w);
@@ -430,7 +477,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
             if (c->tx_a2a(c->tx_user, c->tx_send.data(), sc.data(), so.data(), c->tx_recv.data(), rc_.data(), ro.data(), c->numNodes))
                 return fail(c, DORY_ERR_COMM, "halo_exchange: host transport alltoallv failed");
             if (rb) HIPCK(c, hipMemcpyAsync(c->recv_buf, c->tx_recv.data(), rb, hipMemcpyHostToDevice, c->comm));
-            HIPCK(c, launch_scatter_rows(ghost->d, c->recv_buf, ghost->ld, w, p.d_recv_slots, p.recv_total, c->comm));
+            { int urc = unpack_rows(c, ghost->d, ghost->ld, w, exact, c->recv_buf, p, c->comm); if (urc) return urc; }
             HIPCK(c, hipStreamSynchronize(c->comm));   // tx_recv is reused by the next exchange
         } else {
         ncclComm_t comm = (ncclComm_t)c->nccl;
@@ -445,7 +492,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
                                    ncclFloat, (int)peer, comm, c->comm));
         }
         NCCLCK(c, ncclGroupEnd());
-        HIPCK(c, launch_scatter_rows(ghost->d, c->recv_buf, ghost->ld, w, p.d_recv_slots, p.recv_total, c->comm));
+        { int urc = unpack_rows(c, ghost->d, ghost->ld, w, exact, c->recv_buf, p, c->comm); if (urc) return urc; }
         }
     }
     HIPCK(c, hipEventRecord(c->ev_b, c->comm));
@@ -482,9 +529,11 @@ int dory_halo_pack_tensor(dory_ctx *c, uint32_t layer, const char *name, int dir
     if (!src || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
     HaloPlan &p = c->plan[dir];
     if (src->rows != c->N) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: '%s' is not a per-local-vertex tensor", name);
+    const bool exact = halo_exact(c);
+    const uint32_t w = exact ? src->cols : src->ld;
+    if (!exact_ptr_ok(exact, w, send_buf)) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
     Timed t(c, "halo", c->compute);
-    HIPCK(c, launch_gather_rows(send_buf, src->d, src->ld, src->ld, p.d_send_lvids, p.send_total, c->compute));
-    return DORY_OK;
+    return pack_rows(c, send_buf, src, w, exact, p, c->compute);
 }
 
 int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int dir, const float *recv_buf) {
@@ -495,9 +544,11 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
     if (!ghost || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
     HaloPlan &p = c->plan[dir];
     if (ghost->rows != c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: '%s' is not a ghost tensor of that direction", name);
+    const bool exact = halo_exact(c);
+    const uint32_t w = exact ? ghost->cols : ghost->ld;
+    if (!exact_ptr_ok(exact, w, recv_buf)) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
     Timed t(c, "halo", c->compute);
-    HIPCK(c, launch_scatter_rows(ghost->d, recv_buf, ghost->ld, ghost->ld, p.d_recv_slots, p.recv_total, c->compute));
-    return DORY_OK;
+    return unpack_rows(c, ghost->d, ghost->ld, w, exact, recv_buf, p, c->compute);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -289,6 +289,7 @@ int dory_create(int device, dory_ctx **out) {
     c->opt["gcn_bf16_wide"] = 0;         // GCN, with gcn_bf16_gather: K1s gathers bf16 rows of 128 floats or more eight features per lane (16-byte gathers); same bits (opt-in; see dorylus_hip.h)
     c->opt["gatmh_bf16_gather"] = 0;     // multi-head GAT: the sweep forms' edge passes gather their rows rounded to bf16, fp32 sums: 1 = forward (z), 2 = and the backward's source side (do) (opt-in; see dorylus_hip.h)
     c->opt["gatmh_bf16_wide"] = 0;       // multi-head GAT, with gatmh_bf16_gather: passes on bf16 rows of 128 floats or more (several heads of 16 / 32 / 64 features) gather eight features per lane (16-byte gathers); same bits (opt-in; see dorylus_hip.h)
+    c->opt["halo_exact_rows"] = 0;       // packed halo rows hold exactly `cols` floats instead of the padded `ld` (every transport and the split entry points; same ghost rows bit for bit; opt-in; see dorylus_hip.h)
     c->opt["gcn_transform_first"] = 0;   // GCN layers as A(XW) instead of (AX)W where the input is wider than the output: 1 = layer 0, 2 = all (see tf_layer)
     c->opt["epoch_graph"] = 0;       // engine: replay a recorded epoch (hipGraph) when the partition is alone
     c->opt["spmm_blk_nb"] = 0;       // K1b: number of source blocks (0 = auto, ~3.75 MB windows)
@@ -937,6 +938,11 @@ int dory_get_option(dory_ctx *c, const char *key, int64_t *value) {
     if (key && value && !strcmp(key, "gatmh_bf16_gathers_src")) { *value = (int64_t)c->gatmh_bf16_gathers_src; return DORY_OK; }   // edge passes on bf16 rows
     if (key && value && !strcmp(key, "gatmh_bf16_gathers_fwd_wide")) { *value = (int64_t)c->gatmh_bf16_gathers_fwd_wide; return DORY_OK; }   // (of those: the wide
     if (key && value && !strcmp(key, "gatmh_bf16_gathers_src_wide")) { *value = (int64_t)c->gatmh_bf16_gathers_src_wide; return DORY_OK; }   //  form, option gatmh_bf16_wide)
+    // read-only: what the eager packs (exchanges and dory_halo_pack*) wrote into send buffers since dory_create, and the packs
+    // that ran the exact form of option halo_exact_rows on rows narrower than their padding
+    if (key && value && !strcmp(key, "halo_rows_packed")) { *value = (int64_t)c->halo_rows_packed; return DORY_OK; }
+    if (key && value && !strcmp(key, "halo_floats_packed")) { *value = (int64_t)c->halo_floats_packed; return DORY_OK; }
+    if (key && value && !strcmp(key, "halo_exact_packs")) { *value = (int64_t)c->halo_exact_packs; return DORY_OK; }
     if (key && value && !strcmp(key, "epoch_graph_recorded")) {   // read-only: does the ctx still hold a recorded epoch?
         *value = c->epoch_exec ? 1 : 0;
         return DORY_OK;
@@ -1015,6 +1021,10 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     if (key && !strcmp(key, "gatmh_bf16_wide")) {
         if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "gatmh_bf16_wide: 0 (off) or 1 (16-byte gathers of bf16 rows in the multi-head GAT's sweeps)");
         if (value && c->configured && c->gnn != DORY_GATMH) return fail(c, DORY_ERR_ARG, "gatmh_bf16_wide: multi-head GAT contexts (DORY_GATMH) only");
+    }
+    if (key && !strcmp(key, "halo_exact_rows")) {
+        if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "halo_exact_rows: 0 (padded rows travel) or 1 (rows of exactly cols floats)");
+        c->halo_exact.store((int)value, std::memory_order_release);
     }
     if (!key || c->opt.find(key) == c->opt.end()) return fail(c, DORY_ERR_ARG, "unknown option '%s'", key ? key : "(null)");
     c->opt[key] = value;

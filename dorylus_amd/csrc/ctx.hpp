@@ -217,6 +217,10 @@ struct dory_ctx {
     dory::HaloPlan plan[2];
     float *send_buf = nullptr, *recv_buf = nullptr;
     size_t send_cap = 0, recv_cap = 0;
+    // option halo_exact_rows (a copy the peers of the local transport may read without this context's lock), and what the
+    // eager packs wrote into send buffers since dory_create: rows, floats, packs that ran the exact form with cols < ld
+    std::atomic<int> halo_exact{0};
+    uint64_t halo_rows_packed = 0, halo_floats_packed = 0, halo_exact_packs = 0;
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
     dory_alltoallv_fn tx_a2a = nullptr;
@@ -239,6 +243,7 @@ struct dory_ctx {
         int dir = 0;
         float *ghost = nullptr;
         uint32_t ghost_ld = 0, w = 0;
+        bool exact = false;                         // w is the exact width (option halo_exact_rows): the unpack zeroes [w, ghost_ld)
         hipEvent_t t_halo_b = nullptr, t_kind_b = nullptr;   // timing: end events of the "halo" / "halo_deferred|waited" intervals
     } local_pending;
     float *ar_tmp = nullptr;          // gradient sum before it replaces the local gradient
@@ -511,6 +516,14 @@ hipError_t launch_gather_rows(float *dst, const float *src, uint32_t ld, uint32_
                               const uint32_t *rows, uint32_t n, hipStream_t s);
 hipError_t launch_scatter_rows(float *dst, const float *src, uint32_t ld, uint32_t cols,
                                const uint32_t *rows, uint32_t n, hipStream_t s);
+// option halo_exact_rows, cols % 4 != 0: the dense side is one stream of n x cols floats (16-byte aligned), a thread per
+// 16-byte quad of it; the scatter also zeroes [cols, ld) of every row it writes.  cols % 4 == 0 < ld takes the kernels
+// above with the exact width, and launch_zero_rows_pad after the scatter.
+hipError_t launch_gather_rows_exact(float *dst, const float *src, uint32_t ld, uint32_t cols,
+                                    const uint32_t *rows, uint32_t n, hipStream_t s);
+hipError_t launch_scatter_rows_exact(float *dst, const float *src, uint32_t ld, uint32_t cols,
+                                     const uint32_t *rows, uint32_t n, hipStream_t s);
+hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const uint32_t *rows, uint32_t n, hipStream_t s);
 
 // K7 Adam
 hipError_t launch_adam(float *w, const float *g, float *m, float *v, uint64_t n, float lr_t,

@@ -593,6 +593,129 @@ hipError_t launch_scatter_rows(float *dst, const float *src, uint32_t ld, uint32
     return hipGetLastError();
 }
 
+// ---- K6, exact-width rows (option halo_exact_rows) ----------------------------------------
+// The dense side holds rows of exactly `cols` floats, cols % 4 != 0: a dense row starts on a 4-byte boundary only, so the dense
+// buffer is treated as ONE stream of n x cols floats and a thread owns one 16-byte-aligned quad of it.  A quad may straddle two
+// rows (three and more when cols < 4): the thread resolves (row, col) of its first float once and walks the four elements with
+// a carry.  A workgroup takes a run of `rpb` rows (a multiple of 4, so that the run starts on a 16-byte boundary of the
+// stream; rpb x cols < 2^32): every index inside the run is 32-bit, one 32-bit divide per quad, no 64-bit divide.  The dense
+// side moves as one 16-byte access per thread, the padded side as dwords (consecutive lanes, consecutive addresses within a
+// row).  Only the stream's last quad can be partial (n x cols % 4 != 0): it moves as dwords -- not one float beyond n x cols
+// is read or written on the dense side, the caller's buffer ends there.
+// pack: the row list may repeat a row (a vertex goes to several peers).
+__global__ __launch_bounds__(256) void gather_rows_exact_kernel(float *dst, const float *src, uint32_t ld, uint32_t cols,
+                                                                const uint32_t *rows, uint32_t n, uint32_t rpb) {
+    const uint32_t r0 = blockIdx.x * rpb;
+    const uint32_t nr = n - r0 < rpb ? n - r0 : rpb;
+    const uint32_t total = nr * cols;
+    float *d = dst + (size_t)r0 * cols;
+    const uint32_t *rw = rows + r0;
+    for (uint32_t f = threadIdx.x * 4u; f < total; f += 1024u) {
+        uint32_t r = f / cols, c = f - r * cols;
+        const float *p = src + (size_t)rw[r] * ld;
+        const uint32_t k_end = total - f < 4u ? total - f : 4u;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            if (k < k_end) {
+                v[k] = p[c];
+                if (++c == cols) {
+                    c = 0;
+                    if (++r < nr) p = src + (size_t)rw[r] * ld;
+                }
+            }
+        }
+        if (k_end == 4u) {
+            *reinterpret_cast<float4 *>(d + f) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 3; ++k)
+                if (k < k_end) d[f + k] = v[k];
+        }
+    }
+}
+// unpack: the row list is a permutation of the ghost slots.  Writes [0, cols) of every listed row from the stream and zeros
+// into [cols, ld): the raw ld-wide ghost rows are the bits the padded form leaves (the owner's zero padding travelled there).
+__global__ __launch_bounds__(256) void scatter_rows_exact_kernel(float *dst, const float *src, uint32_t ld, uint32_t cols,
+                                                                 const uint32_t *rows, uint32_t n, uint32_t rpb) {
+    const uint32_t r0 = blockIdx.x * rpb;
+    const uint32_t nr = n - r0 < rpb ? n - r0 : rpb;
+    const uint32_t total = nr * cols;
+    const float *s = src + (size_t)r0 * cols;
+    const uint32_t *rw = rows + r0;
+    for (uint32_t f = threadIdx.x * 4u; f < total; f += 1024u) {
+        uint32_t r = f / cols, c = f - r * cols;
+        float *p = dst + (size_t)rw[r] * ld;
+        const uint32_t k_end = total - f < 4u ? total - f : 4u;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (k_end == 4u) {
+            const float4 q = *reinterpret_cast<const float4 *>(s + f);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 3; ++k)
+                if (k < k_end) v[k] = s[f + k];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            if (k < k_end) {
+                p[c] = v[k];
+                if (++c == cols) {
+                    c = 0;
+                    if (++r < nr) p = dst + (size_t)rw[r] * ld;
+                }
+            }
+        }
+    }
+    const uint32_t pad = ld - cols, ptotal = nr * pad;   // (ld <= cols + 31: far below 2^32 for a run of rows)
+    for (uint32_t i = threadIdx.x; i < ptotal; i += 256u) {
+        const uint32_t r = i / pad, c = cols + (i - r * pad);
+        dst[(size_t)rw[r] * ld + c] = 0.f;
+    }
+}
+// the same zeros after scatter_rows_kernel has written an exact width that is a multiple of 4 (cols4 < ld4, float4 units)
+__global__ __launch_bounds__(256) void zero_rows_pad_kernel(float *dst, uint32_t ld, uint32_t cols4, uint32_t pad4,
+                                                            const uint32_t *rows, uint32_t n) {
+    const uint64_t total = (uint64_t)n * pad4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / pad4);
+        const uint32_t c = cols4 + (uint32_t)(i % pad4);
+        reinterpret_cast<float4 *>(dst + (size_t)rows[r] * ld)[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// rows per workgroup of the exact kernels: a multiple of 4 (see above) with about 4096 floats = four quads per thread
+static bool exact_rows_per_block(uint32_t cols, uint32_t ld, uint32_t *rpb) {
+    const uint32_t r = ((4096u + cols - 1) / cols + 3u) & ~3u;
+    if ((uint64_t)r * ld >= (1ull << 32)) return false;   // (ld >= cols: covers the stream's and the padding's indices)
+    *rpb = r;
+    return true;
+}
+hipError_t launch_gather_rows_exact(float *dst, const float *src, uint32_t ld, uint32_t cols,
+                                    const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || cols == 0) return hipSuccess;
+    uint32_t rpb;
+    if (cols > ld || ((uintptr_t)dst & 15) || !exact_rows_per_block(cols, ld, &rpb)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rows_exact_kernel, dim3((n - 1) / rpb + 1), dim3(256), 0, s, dst, src, ld, cols, rows, n, rpb);
+    return hipGetLastError();
+}
+hipError_t launch_scatter_rows_exact(float *dst, const float *src, uint32_t ld, uint32_t cols,
+                                     const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || cols == 0) return hipSuccess;
+    uint32_t rpb;
+    if (cols > ld || ((uintptr_t)src & 15) || !exact_rows_per_block(cols, ld, &rpb)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scatter_rows_exact_kernel, dim3((n - 1) / rpb + 1), dim3(256), 0, s, dst, src, ld, cols, rows, n, rpb);
+    return hipGetLastError();
+}
+hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || cols >= ld) return hipSuccess;
+    if ((cols & 3) || (ld & 3)) return hipErrorInvalidValue;
+    const uint64_t total = (uint64_t)n * ((ld - cols) / 4);
+    int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(zero_rows_pad_kernel, dim3(blocks), dim3(256), 0, s, dst, ld, cols / 4, (ld - cols) / 4, rows, n);
+    return hipGetLastError();
+}
+
 // ---- K7: Adam -----------------------------------------------------------------------------
 // AdamOptimizer::update (reference src/weight-server/AdamOptimizer.cpp:36-51), the
 // mixed float/double expressions kept as written there ("(1. - BETA1) * gt" is double).

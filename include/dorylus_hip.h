@@ -368,6 +368,37 @@ int dory_transform_first_layer(dory_ctx *ctx, uint32_t layer);
  * recordings, not replays); "gatmh_bf16_gathers_fwd" / "_src" count them too.  Measured: DESIGN.md section 3,
  * profiles/r10_gatmh_bf16_wide_ab.txt. */
 
+/* Exact-width halo rows (option "halo_exact_rows", default 0; every gnn_type; read by every call).  0: every packed halo row
+ * holds the padded `ld` floats of its tensor (41 -> 64, 48 -> 64, 25 -> 32), the owner's zero padding included.  1: it holds
+ * exactly `cols` floats, the logical width of the tensor that travels -- what the reference ships (featDim floats per row,
+ * engine/utils.cpp:623-650, verticesPushOut).  Layout: rows are dense, row i at float offset i * cols, peer q's segment at
+ * send_off[q] * cols / recv_off[q] * cols (row offsets of the plan, in peer order).  This holds for the library's own send /
+ * receive buffers in all three arms of an exchange (dory_halo_exchange and the multi-head GAT backward's "do" / "st"
+ * exchanges) and for the caller's buffers of dory_halo_pack / dory_halo_unpack / dory_halo_pack_tensor /
+ * dory_halo_unpack_tensor (total_send_rows x cols / total_recv_rows x cols floats, not one more).
+ *   host transport  the counts and offsets handed to dory_alltoallv_fn are rows x cols and row offset x cols floats: the
+ *                   reference's own wire format, no re-packing on the host.
+ *   unpack          writes the whole ghost row: [0, cols) from the buffer, zeros into [cols, ld).  The raw ld-wide ghost rows
+ *                   are the bits the padded form leaves; no result of any later call changes by a bit.
+ *   widths          source and ghost tensor must agree in cols as well as ld (DORY_ERR_ARG).
+ *   alignment       with 1 and cols % 4 != 0 the caller's pointer of the four split entry points must be 16-byte aligned
+ *                   (DORY_ERR_ARG otherwise): the buffer is addressed in 16-byte quads of the whole stream of rows x cols
+ *                   floats.  (The padded form has always assumed that alignment without checking; 0 stays as it is.)
+ *   agreement       all ranks must use the same value.  The in-process device transport checks it against every peer before
+ *                   anything of the exchange is enqueued or counted and fails at once with DORY_ERR_COMM, naming both ranks;
+ *                   the call may be repeated after the option is fixed.  Over RCCL and over a host transport agreement is
+ *                   the caller's contract: a rank with another value sends and expects other counts.
+ *   buffers         nothing new is allocated: what dory_halo_plan sized for the widest padded row is large enough, and the
+ *                   option may be switched between calls.  num_nodes == 1 keeps exchanging nothing.
+ * Values outside {0, 1} are rejected.  Read-only "halo_rows_packed" / "halo_floats_packed": rows and floats the eager packs
+ * (exchanges and dory_halo_pack*) wrote into send buffers since dory_create, one step per pack; "halo_exact_packs": the packs
+ * that ran the exact form on rows narrower than their padding (cols < ld).  Kernels: widths that are multiples of 4 keep
+ * gather_rows_kernel / scatter_rows_kernel at the exact width (plus a kernel that zeroes the padding); other widths take
+ * gather_rows_exact_kernel / scatter_rows_exact_kernel (csrc/elementwise.hip).  The RCCL arm takes its counts and offsets from
+ * the same width variable as the other two, but no run with more than one RCCL rank has ever executed it (two ranks cannot
+ * share one GPU under RCCL): the link bytes saved -- 41/64, 48/64, 25/32 of the padded form's -- are arithmetic, not a
+ * measurement.  Pack / unpack cost measured on one GPU: DESIGN.md section 5, profiles/r11_halo_exact_rows.txt. */
+
 /* Epoch graph (MI355X-side addition, no reference counterpart): record the calls of one
  * epoch -- dory_aggregate / dory_apply_vertex / dory_apply_edge / dory_predict_gat /
  * dory_weight_update, exactly as Engine::runEpoch issues them -- into a hipGraph and replay
