@@ -1,11 +1,132 @@
-// abi_comm.hip -- C-ABI, part 3: ghost-vertex halo exchange (plan, RCCL all-to-all-v, pack / unpack for foreign
-// transports), weight-gradient all-reduce + Adam, and the epoch graph (hipGraph record / replay).
+// abi_comm.hip -- C-ABI, part 3: ghost-vertex halo exchange (plan, one wire-format record for a packed row, one arm per
+// transport: caller's host callbacks / in-process device transport / RCCL all-to-all-v, pack / unpack for foreign
+// transports), all-reduce over the same transports for the weight gradients + Adam and for the validation statistics, and
+// the epoch graph (hipGraph record / replay).  Layout: helpers in dependency order (file-local ones, then the four that
+// abi_internal.hpp declares), then the extern "C" entry points.
+#include <chrono>
+#include <thread>
+
 #include "abi_internal.hpp"
 
 using namespace dory;
 
-#include <chrono>
-#include <thread>
+namespace {
+
+// ---- which transport carries the bytes: the caller's host callbacks, else the in-process group, else RCCL ----------------
+enum class Transport { Host, Local, Rccl, None };
+Transport transport_of(const dory_ctx *c) {
+    if (c->tx_a2a && c->tx_ar) return Transport::Host;   // (dory_comm_set_host_transport sets both or none)
+    if (c->local) return Transport::Local;
+    return c->nccl ? Transport::Rccl : Transport::None;
+}
+
+// ---- timing ---------------------------------------------------------------------------------------------------------------
+// an interval for dory_timing_get whose end is recorded by a later call: entry pushed now (order of `pending` = order of
+// the first events), end event handed back
+void timed_open(dory_ctx *c, const char *fam, hipStream_t s, hipEvent_t *end_out) {
+    *end_out = nullptr;
+    if (!c->timing || c->capturing) return;
+    const auto ev = take_event_pair(c);
+    (void)hipEventRecord(ev.first, s);
+    c->pending.push_back({fam, ev.first, ev.second});
+    *end_out = ev.second;
+}
+
+// ---- the wire format of a packed row --------------------------------------------------------------------------------------
+// Option halo_exact_rows: a packed row holds exactly `cols` floats instead of the padded `ld` -- what the reference ships
+// (featDim floats per row, engine/utils.cpp:623-650).  Every pack and unpack of this file goes through row_wire, pack_rows
+// and unpack_rows.
+inline bool halo_exact(const dory_ctx *c) { return c->halo_exact.load(std::memory_order_acquire) == 1; }
+
+// The record for the rows `who` packs from `src` (pack == true: its width travels) or unpacks into `ghost` (pack == false);
+// the tensor of the other end may be null (the *_tensor entry points know one only), `buf` is a caller's buffer or null.
+// The padded row width travels (keeps 16-B lanes), or, with option halo_exact_rows, exactly the tensor's columns -- then
+// both ends must have the same, and a caller's buffer of rows whose width is no multiple of 4 is addressed in 16-byte quads
+// of the whole stream.
+int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghost, bool pack, const void *buf, RowWire *out) {
+    const Tensor *rows = pack ? src : ghost;
+    out->exact = halo_exact(c);
+    if (out->exact && src && ghost && src->cols != ghost->cols)
+        return fail(c, DORY_ERR_ARG, "%s: widths of source (%u) and ghost tensor (%u) differ", who, src->cols, ghost->cols);
+    out->w = out->exact ? rows->cols : rows->ld;
+    if (out->exact && (out->w & 3) && ((uintptr_t)buf & 15))
+        return fail(c, DORY_ERR_ARG, "%s: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", who, out->w);
+    return DORY_OK;
+}
+
+// the plan's send rows of `src`, dense at the wire's width, into dst; counted (eager calls)
+int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const HaloPlan &p, hipStream_t s) {
+    if (wire.exact && (wire.w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
+    else HIPCK(c, launch_gather_rows(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
+    if (!c->capturing) {
+        c->halo_rows_packed += p.send_total;
+        c->halo_floats_packed += (uint64_t)p.send_total * wire.w;
+        if (wire.exact && wire.w < src->ld) c->halo_exact_packs++;
+    }
+    return DORY_OK;
+}
+// the received rows, dense at the wire's width w, into the plan's ghost slots; the exact form writes the whole row: [0, w)
+// from the buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever the padding held before
+int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s) {
+    if (wire.exact && (wire.w & 3)) {
+        HIPCK(c, launch_scatter_rows_exact(ghost, buf, ld, wire.w, p.d_recv_slots, p.recv_total, s));
+    } else {
+        HIPCK(c, launch_scatter_rows(ghost, buf, ld, wire.w, p.d_recv_slots, p.recv_total, s));
+        if (wire.exact && wire.w < ld) HIPCK(c, launch_zero_rows_pad(ghost, ld, wire.w, p.d_recv_slots, p.recv_total, s));
+    }
+    return DORY_OK;
+}
+
+// the four split entry points (foreign transports, multi-context tests) after their own checks: pack the plan's send rows of
+// `src` into the caller's buffer, or unpack it into `ghost`; the other tensor is the one halo_tensors resolved, or null
+int split_rows(dory_ctx *c, const char *who, bool pack, int dir, const Tensor *src, Tensor *ghost, float *buf) {
+    RowWire wire;
+    int rc = row_wire(c, who, src, ghost, pack, buf, &wire);
+    if (rc) return rc;
+    Timed t(c, "halo", c->compute);
+    return pack ? pack_rows(c, buf, src, wire, c->plan[dir], c->compute)
+                : unpack_rows(c, ghost->d, ghost->ld, wire, buf, c->plan[dir], c->compute);
+}
+
+// resolve (layer, dir) -> source tensor, ghost tensor, as Engine::scatterGCN/GAT do
+int halo_tensors(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **ghost) {
+    if (c->gnn == DORY_GCN && dir == DORY_BACKWARD && tf_layer(c, layer)) {
+        *src = find(c, layer, "g");      // transform-first: A^T g_l needs the ghost rows of g_l
+        *ghost = find(c, layer, "bgg");
+    } else if (c->gnn == DORY_GCN && dir == DORY_FORWARD && layer > 0 && tf_layer(c, layer)) {
+        *src = find(c, layer, "xw");     // transform-first: the already transformed (narrower) rows travel
+        *ghost = find(c, layer, "fgxw");
+    } else if (c->gnn == DORY_GCN) {
+        if (layer == 0 || layer >= c->L) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
+        if (dir == DORY_FORWARD) { *src = find(c, layer - 1, "h"); *ghost = find(c, layer, "fg"); }   // gcn_ops.cpp:205-214
+        else { *src = find(c, layer, "grad"); *ghost = find(c, layer - 1, "bg"); }
+    } else {
+        if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
+        if (dir == DORY_FORWARD) {   // gat_ops.cpp:277-287
+            *src = find(c, layer - 1, "z"); *ghost = find(c, layer - 1, "fg_z");
+            if (layer - 1 < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer - 1] = 0;   // fg_z is about to change: the kept neighbour sum no longer holds
+        }
+        else { *src = find(c, layer - 1, "grad"); *ghost = find(c, layer - 1, "bg_d"); }
+    }
+    if (!*src || !*ghost) return fail(c, DORY_ERR_ARG, "halo: tensors missing");
+    return DORY_OK;
+}
+
+// ---- the pack / receive buffers -------------------------------------------------------------------------------------------
+int grow_buffer(dory_ctx *c, float **buf, size_t *cap, size_t bytes) {
+    if (bytes <= *cap) return DORY_OK;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+    HIPCK(c, hipMalloc((void **)buf, bytes));
+    *cap = bytes;
+    return DORY_OK;
+}
+// c->send_buf / c->recv_buf hold at least that much: one device-wide synchronisation if either grows, then free, then malloc
+int ensure_exchange_buffers(dory_ctx *c, size_t send_bytes, size_t recv_bytes) {
+    if (send_bytes > c->send_cap || recv_bytes > c->recv_cap) HIPCK(c, hipDeviceSynchronize());
+    int rc = grow_buffer(c, &c->send_buf, &c->send_cap, send_bytes);
+    return rc ? rc : grow_buffer(c, &c->recv_buf, &c->recv_cap, recv_bytes);
+}
 
 // ---------------------------------------------------------------------------------------
 // In-process device transport (dory_comm_init_local): P contexts of one process on one device are each other's peers.
@@ -20,8 +141,6 @@ using namespace dory;
 // the peer's counter BEFORE it makes its stream wait.  That read may block the calling host thread until the peer's host
 // thread has got there (bounded: option local_timeout_ms) -- so the ranks must be driven by one host thread each, or stage
 // by stage (all ranks' scatter before any rank's next gather), exactly as real ranks are.
-namespace {
-
 constexpr uint32_t LOCAL_MAX_RANKS = 16;
 
 int local_wait_posted(dory_ctx *c, const std::atomic<uint64_t> &ctr, uint64_t want, uint32_t peer, const char *what) {
@@ -39,54 +158,92 @@ int local_wait_posted(dory_ctx *c, const std::atomic<uint64_t> &ctr, uint64_t wa
     return DORY_OK;
 }
 
-// an interval for dory_timing_get whose end is recorded by a later call: entry pushed now (order of `pending` = order of
-// the first events), end event handed back
-void timed_open(dory_ctx *c, const char *fam, hipStream_t s, hipEvent_t *end_out) {
-    *end_out = nullptr;
-    if (!c->timing || c->capturing) return;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (c->ev_pool.empty()) {
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
-    } else {
-        a = c->ev_pool.back().first;
-        b = c->ev_pool.back().second;
-        c->ev_pool.pop_back();
+// first half of an exchange: pack, push my rows into every peer's receive buffer, "sent"; the second half
+// (local_exchange_finish, below) at once, or with `deferred` when wait_halo() is next called
+int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wire, bool deferred) {
+    HaloPlan &p = c->plan[dir];
+    LocalGroup &grp = *c->local;
+    const uint32_t w = wire.w;
+    if (c->local_pending.on) {   // (not reached: every consumer and every exchange calls wait_halo first)
+        int rc = local_exchange_finish(c);
+        if (rc) return rc;
     }
-    (void)hipEventRecord(a, s);
-    c->pending.push_back({fam, a, b});
-    *end_out = b;
-}
-
-// Option halo_exact_rows: a packed row holds exactly `cols` floats instead of the padded `ld` -- what the reference ships
-// (featDim floats per row, engine/utils.cpp:623-650).  Every pack and unpack of this file goes through these three.
-inline bool halo_exact(const dory_ctx *c) { return c->halo_exact.load(std::memory_order_acquire) == 1; }
-
-// the plan's send rows of `src`, dense at width w (src->ld, or with `exact` src->cols), into dst; counted (eager calls)
-int pack_rows(dory_ctx *c, float *dst, const Tensor *src, uint32_t w, bool exact, const HaloPlan &p, hipStream_t s) {
-    if (exact && (w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, w, p.d_send_lvids, p.send_total, s));
-    else HIPCK(c, launch_gather_rows(dst, src->d, src->ld, w, p.d_send_lvids, p.send_total, s));
-    if (!c->capturing) {
-        c->halo_rows_packed += p.send_total;
-        c->halo_floats_packed += (uint64_t)p.send_total * w;
-        if (exact && w < src->ld) c->halo_exact_packs++;
+    const uint64_t s = ++c->local_seq;
+    dory_ctx::LocalPending &lp = c->local_pending;
+    timed_open(c, "halo", c->comm, &lp.t_halo_b);
+    timed_open(c, deferred ? "halo_deferred" : "halo_waited", c->comm, &lp.t_kind_b);
+    { int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm); if (rc) return rc; }
+    for (uint32_t q = 0; q < c->numNodes; ++q) {
+        if (q == c->nodeId || !p.send_counts[q]) continue;
+        dory_ctx *Q = grp.ctx[q];
+        if (!Q) return fail(c, DORY_ERR_COMM, "local transport: rank %u has been destroyed", q);
+        const HaloPlan &pq = Q->plan[dir];
+        if (!pq.set || pq.recv_counts.size() != c->numNodes || pq.recv_counts[c->nodeId] != p.send_counts[q])
+            return fail(c, DORY_ERR_COMM, "local transport: rank %u expects %u rows from rank %u, which sends %u", q,
+                        pq.set && pq.recv_counts.size() == c->numNodes ? pq.recv_counts[c->nodeId] : 0u, c->nodeId, p.send_counts[q]);
+        if ((size_t)pq.recv_total * w * sizeof(float) > Q->recv_cap)
+            return fail(c, DORY_ERR_COMM, "local transport: receive buffer of rank %u too small for %u-float rows", q, w);
+        if (s > 1) {   // its receive buffer must have been unpacked (exchange s - 1)
+            int rc = local_wait_posted(c, Q->posted_cons, s - 1, q, "the unpack of exchange");
+            if (rc) return rc;
+            HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_cons[(s - 1) & 1], 0));
+        }
+        HIPCK(c, hipMemcpyAsync(Q->recv_buf + (size_t)pq.recv_off[c->nodeId] * w, c->send_buf + (size_t)p.send_off[q] * w,
+                                (size_t)p.send_counts[q] * w * sizeof(float), hipMemcpyDeviceToDevice, c->comm));
     }
+    HIPCK(c, hipEventRecord(c->ev_sent[s & 1], c->comm));
+    c->posted_sent.store(s, std::memory_order_release);
+    lp.on = true;
+    lp.dir = dir;
+    lp.ghost = ghost->d;
+    lp.ghost_ld = ghost->ld;
+    lp.wire = wire;
+    if (deferred) {
+        c->halo_pending = true;      // wait_halo(): local_exchange_finish, then the compute stream waits for ev_b
+        return DORY_OK;
+    }
+    int rc = local_exchange_finish(c);
+    if (rc) return rc;
+    HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
     return DORY_OK;
 }
-// the received rows, dense at width w, into the plan's ghost slots; the exact form writes the whole row: [0, w) from the
-// buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever the padding held before
-int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, uint32_t w, bool exact, const float *buf, const HaloPlan &p, hipStream_t s) {
-    if (exact && (w & 3)) {
-        HIPCK(c, launch_scatter_rows_exact(ghost, buf, ld, w, p.d_recv_slots, p.recv_total, s));
-    } else {
-        HIPCK(c, launch_scatter_rows(ghost, buf, ld, w, p.d_recv_slots, p.recv_total, s));
-        if (exact && w < ld) HIPCK(c, launch_zero_rows_pad(ghost, ld, w, p.d_recv_slots, p.recv_total, s));
+
+// ---- the other two arms: the packed rows in c->send_buf travel, the peers' rows arrive in c->recv_buf (comm stream) -----
+// host transport: the bytes travel through the caller (c->tx_recv is still being read when this returns)
+int exchange_host(dory_ctx *c, const HaloPlan &p, uint32_t w) {
+    const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
+    c->tx_send.resize((size_t)p.send_total * w);
+    c->tx_recv.resize((size_t)p.recv_total * w);
+    if (sb) HIPCK(c, hipMemcpyAsync(c->tx_send.data(), c->send_buf, sb, hipMemcpyDeviceToHost, c->comm));
+    HIPCK(c, hipStreamSynchronize(c->comm));
+    std::vector<uint64_t> sc(c->numNodes), so(c->numNodes), rc_(c->numNodes), ro(c->numNodes);
+    for (uint32_t peer = 0; peer < c->numNodes; ++peer) {
+        sc[peer] = (uint64_t)p.send_counts[peer] * w; so[peer] = (uint64_t)p.send_off[peer] * w;
+        rc_[peer] = (uint64_t)p.recv_counts[peer] * w; ro[peer] = (uint64_t)p.recv_off[peer] * w;
     }
+    if (c->tx_a2a(c->tx_user, c->tx_send.data(), sc.data(), so.data(), c->tx_recv.data(), rc_.data(), ro.data(), c->numNodes))
+        return fail(c, DORY_ERR_COMM, "halo_exchange: host transport alltoallv failed");
+    if (rb) HIPCK(c, hipMemcpyAsync(c->recv_buf, c->tx_recv.data(), rb, hipMemcpyHostToDevice, c->comm));
     return DORY_OK;
 }
-// a caller's buffer of exact rows is addressed in 16-byte quads of the whole stream when the width is no multiple of 4
-bool exact_ptr_ok(bool exact, uint32_t w, const void *buf) { return !exact || !(w & 3) || !((uintptr_t)buf & 15); }
+// RCCL: grouped ncclSend / ncclRecv
+int exchange_rccl(dory_ctx *c, const HaloPlan &p, uint32_t w) {
+    ncclComm_t comm = (ncclComm_t)c->nccl;
+    NCCLCK(c, ncclGroupStart());
+    for (uint32_t peer = 0; peer < c->numNodes; ++peer) {
+        if (peer == c->nodeId) continue;
+        if (p.send_counts[peer])
+            NCCLCK(c, ncclSend(c->send_buf + (size_t)p.send_off[peer] * w, (size_t)p.send_counts[peer] * w,
+                               ncclFloat, (int)peer, comm, c->comm));
+        if (p.recv_counts[peer])
+            NCCLCK(c, ncclRecv(c->recv_buf + (size_t)p.recv_off[peer] * w, (size_t)p.recv_counts[peer] * w,
+                               ncclFloat, (int)peer, comm, c->comm));
+    }
+    NCCLCK(c, ncclGroupEnd());
+    return DORY_OK;
+}
 
+// ---- all-reduce -----------------------------------------------------------------------------------------------------------
 struct PeerPtrs { const float *p[LOCAL_MAX_RANKS]; };
 __global__ __launch_bounds__(256) void local_sum_kernel(PeerPtrs pp, uint32_t P, uint64_t n, float *out) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -94,6 +251,75 @@ __global__ __launch_bounds__(256) void local_sum_kernel(PeerPtrs pp, uint32_t P,
         for (uint32_t q = 0; q < P; ++q) sum += pp.p[q][i];      // rank order on every rank: identical bits everywhere
         out[i] = sum;
     }
+}
+
+// sum of n floats over the group into gd: every rank adds the P buffers in rank order (identical bits on every rank).
+// peer_buf(Q) = that buffer of rank Q (mine included), or null after recording why rank Q has none of this shape
+template <typename PeerBuf>
+int local_allreduce(dory_ctx *c, float *gd, uint64_t n, PeerBuf peer_buf) {
+    LocalGroup &grp = *c->local;
+    const uint32_t P = c->numNodes;
+    if (n * sizeof(float) > c->ar_tmp_cap) return fail(c, DORY_ERR_COMM, "local transport: gradient staging buffer too small (preallocate before dory_comm_init_local)");
+    const uint64_t t = ++c->local_ar_seq;
+    HIPCK(c, hipEventRecord(c->ev_gready[t & 1], c->compute));
+    c->posted_g.store(t, std::memory_order_release);
+    PeerPtrs pp{};
+    for (uint32_t q = 0; q < P; ++q) {
+        dory_ctx *Q = q == c->nodeId ? c : grp.ctx[q];
+        if (!Q) return fail(c, DORY_ERR_COMM, "local transport: rank %u has been destroyed", q);
+        if (q != c->nodeId) {
+            int rc = local_wait_posted(c, Q->posted_g, t, q, "gradient sum");
+            if (rc) return rc;
+            HIPCK(c, hipStreamWaitEvent(c->compute, Q->ev_gready[t & 1], 0));
+        }
+        if (!(pp.p[q] = peer_buf(Q))) return DORY_ERR_COMM;
+    }
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
+    hipLaunchKernelGGL(local_sum_kernel, dim3(blocks), dim3(256), 0, c->compute, pp, P, n, c->ar_tmp);
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipEventRecord(c->ev_gdone[t & 1], c->compute));
+    c->posted_gdone.store(t, std::memory_order_release);
+    for (uint32_t q = 0; q < P; ++q) {     // nobody reads my gradient any more: the sum may replace it
+        if (q == c->nodeId) continue;
+        dory_ctx *Q = grp.ctx[q];
+        int rc = local_wait_posted(c, Q->posted_gdone, t, q, "the end of gradient sum");
+        if (rc) return rc;
+        HIPCK(c, hipStreamWaitEvent(c->compute, Q->ev_gdone[t & 1], 0));
+    }
+    HIPCK(c, hipMemcpyAsync(gd, c->ar_tmp, n * sizeof(float), hipMemcpyDeviceToDevice, c->compute));
+    return DORY_OK;
+}
+
+// Sum of n floats at device pointer `buf` over all ranks, in place, on the compute stream: the sum of per-partition updates
+// (WeightTensor::localUpdate/ghostUpdate, src/weight-server/weighttensor.cpp:131-166) as one collective.  peer_buf: see
+// local_allreduce (the in-process transport reads the peers' buffers itself).
+template <typename PeerBuf>
+int allreduce_sum(dory_ctx *c, const char *who, float *buf, uint64_t n, PeerBuf peer_buf) {
+    switch (transport_of(c)) {
+    case Transport::Host:
+        c->tx_send.resize(n);
+        HIPCK(c, hipMemcpyAsync(c->tx_send.data(), buf, n * sizeof(float), hipMemcpyDeviceToHost, c->compute));
+        HIPCK(c, hipStreamSynchronize(c->compute));
+        if (c->tx_ar(c->tx_user, c->tx_send.data(), n)) return fail(c, DORY_ERR_COMM, "%s: host transport allreduce failed", who);
+        HIPCK(c, hipMemcpyAsync(buf, c->tx_send.data(), n * sizeof(float), hipMemcpyHostToDevice, c->compute));
+        HIPCK(c, hipStreamSynchronize(c->compute));
+        return DORY_OK;
+    case Transport::Local:
+        return local_allreduce(c, buf, n, peer_buf);
+    case Transport::Rccl:
+        NCCLCK(c, ncclAllReduce(buf, buf, n, ncclFloat, ncclSum, (ncclComm_t)c->nccl, c->compute));
+        return DORY_OK;
+    case Transport::None:   // (reached from dory_train_stat_global only: dory_weight_update refuses before its "allreduce" interval opens)
+        break;
+    }
+    return fail(c, DORY_ERR_COMM, "%s: dory_comm_init not called", who);
+}
+
+// AdamOptimizer::nextIteration (src/weight-server/AdamOptimizer.cpp:29-34): the step size of iteration `epochs`
+float adam_lr_t(const dory_ctx *c, unsigned epochs) {
+    const float b1p = (float)std::pow((double)0.9f, (double)epochs);
+    const float b2p = (float)std::pow((double)0.999f, (double)epochs);
+    return (float)(c->adam.lr * (std::sqrt((double)(1 - b2p))) / (1 - b1p));
 }
 
 }  // namespace
@@ -119,7 +345,7 @@ int local_exchange_finish(dory_ctx *c) {
         HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_sent[s & 1], 0));
     }
     lp.on = false;     // (a peer that has not arrived leaves the second half pending: the caller may try again)
-    { int rc = unpack_rows(c, lp.ghost, lp.ghost_ld, lp.w, lp.exact, c->recv_buf, p, c->comm); if (rc) return rc; }
+    { int rc = unpack_rows(c, lp.ghost, lp.ghost_ld, lp.wire, c->recv_buf, p, c->comm); if (rc) return rc; }
     HIPCK(c, hipEventRecord(c->ev_cons[s & 1], c->comm));
     c->posted_cons.store(s, std::memory_order_release);
     if (lp.t_kind_b) (void)hipEventRecord(lp.t_kind_b, c->comm);
@@ -129,94 +355,81 @@ int local_exchange_finish(dory_ctx *c) {
     return DORY_OK;
 }
 
-// first half: pack, push my rows into every peer's receive buffer, "sent"
-static int local_exchange_send(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, uint32_t w, bool exact, bool deferred) {
-    HaloPlan &p = c->plan[dir];
-    LocalGroup &grp = *c->local;
-    if (c->local_pending.on) {   // (not reached: every consumer and every exchange calls wait_halo first)
-        int rc = local_exchange_finish(c);
-        if (rc) return rc;
-    }
-    const uint64_t s = ++c->local_seq;
-    dory_ctx::LocalPending &lp = c->local_pending;
-    timed_open(c, "halo", c->comm, &lp.t_halo_b);
-    timed_open(c, deferred ? "halo_deferred" : "halo_waited", c->comm, &lp.t_kind_b);
-    { int rc = pack_rows(c, c->send_buf, src, w, exact, p, c->comm); if (rc) return rc; }
-    for (uint32_t q = 0; q < c->numNodes; ++q) {
-        if (q == c->nodeId || !p.send_counts[q]) continue;
-        dory_ctx *Q = grp.ctx[q];
-        if (!Q) return fail(c, DORY_ERR_COMM, "local transport: rank %u has been destroyed", q);
-        const HaloPlan &pq = Q->plan[dir];
-        if (!pq.set || pq.recv_counts.size() != c->numNodes || pq.recv_counts[c->nodeId] != p.send_counts[q])
-            return fail(c, DORY_ERR_COMM, "local transport: rank %u expects %u rows from rank %u, which sends %u", q,
-                        pq.set && pq.recv_counts.size() == c->numNodes ? pq.recv_counts[c->nodeId] : 0u, c->nodeId, p.send_counts[q]);
-        if ((size_t)pq.recv_total * w * sizeof(float) > Q->recv_cap)
-            return fail(c, DORY_ERR_COMM, "local transport: receive buffer of rank %u too small for %u-float rows", q, w);
-        if (s > 1) {   // its receive buffer must have been unpacked (exchange s - 1)
-            int rc = local_wait_posted(c, Q->posted_cons, s - 1, q, "the unpack of exchange");
+// Ghost rows of the last halo exchange land on the comm stream; with "halo_overlap" the
+// compute stream is only made to wait for them (event ev_b) by the first consumer.
+int wait_halo(dory_ctx *c) {
+    if (c->halo_pending) {
+        if (c->local_pending.on) {   // in-process device transport: the peers' rows, unpack, ev_b
+            int rc = local_exchange_finish(c);
             if (rc) return rc;
-            HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_cons[(s - 1) & 1], 0));
         }
-        HIPCK(c, hipMemcpyAsync(Q->recv_buf + (size_t)pq.recv_off[c->nodeId] * w, c->send_buf + (size_t)p.send_off[q] * w,
-                                (size_t)p.send_counts[q] * w * sizeof(float), hipMemcpyDeviceToDevice, c->comm));
+        HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
+        c->halo_pending = false;
     }
-    HIPCK(c, hipEventRecord(c->ev_sent[s & 1], c->comm));
-    c->posted_sent.store(s, std::memory_order_release);
-    lp.on = true;
-    lp.dir = dir;
-    lp.ghost = ghost->d;
-    lp.ghost_ld = ghost->ld;
-    lp.w = w;
-    lp.exact = exact;
-    if (deferred) {
-        c->halo_pending = true;      // wait_halo(): local_exchange_finish, then the compute stream waits for ev_b
-        return DORY_OK;
-    }
-    int rc = local_exchange_finish(c);
-    if (rc) return rc;
-    HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
     return DORY_OK;
 }
 
-// weight-gradient sum over the group: every rank adds the P gradients in rank order (identical bits on every rank)
-// (`stat` = true: the three validation scalars in every context's d_stat3 instead of a weight gradient)
-static int local_allreduce(dory_ctx *c, uint32_t layer, const std::string &name, float *gd, uint64_t n, bool stat = false) {
-    LocalGroup &grp = *c->local;
-    const uint32_t P = c->numNodes;
-    if (n * sizeof(float) > c->ar_tmp_cap) return fail(c, DORY_ERR_COMM, "local transport: gradient staging buffer too small (preallocate before dory_comm_init_local)");
-    const uint64_t t = ++c->local_ar_seq;
-    HIPCK(c, hipEventRecord(c->ev_gready[t & 1], c->compute));
-    c->posted_g.store(t, std::memory_order_release);
-    PeerPtrs pp{};
-    for (uint32_t q = 0; q < P; ++q) {
-        dory_ctx *Q = q == c->nodeId ? c : grp.ctx[q];
-        if (!Q) return fail(c, DORY_ERR_COMM, "local transport: rank %u has been destroyed", q);
-        if (q != c->nodeId) {
-            int rc = local_wait_posted(c, Q->posted_g, t, q, "gradient sum");
-            if (rc) return rc;
-            HIPCK(c, hipStreamWaitEvent(c->compute, Q->ev_gready[t & 1], 0));
+// One all-to-all-v of rows: src rows listed in plan[dir] -> the peers' ghost tensors.  pack -> the transport's arm ->
+// unpack on the comm stream, ordered after the compute stream's work so far; the compute stream waits for the ghosts
+// at once (defer == false) or when wait_halo() is next called (halo_overlap).
+int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) {
+    HaloPlan &p = c->plan[dir];
+    if (!p.set) return fail(c, DORY_ERR_ARG, "halo_exchange: no plan");
+    const Transport tr = transport_of(c);
+    if (tr == Transport::None) return fail(c, DORY_ERR_COMM, "halo_exchange: dory_comm_init not called");
+    if (tr == Transport::Rccl && c->nranks != (int)c->numNodes) return fail(c, DORY_ERR_COMM, "halo_exchange: communicator size != num_nodes");
+    if (src->ld != ghost->ld) return fail(c, DORY_ERR_ARG, "halo_exchange: row widths of source and ghost tensor differ");
+    RowWire wire;
+    { int rc = row_wire(c, "halo_exchange", src, ghost, true, nullptr, &wire); if (rc) return rc; }
+    const uint32_t w = wire.w;
+    if (tr == Transport::Local) {   // every rank packs and unpacks at one width: checked here, before anything of this exchange is enqueued or counted
+        for (uint32_t q = 0; q < c->numNodes; ++q) {
+            dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
+            if (Q && halo_exact(Q) != wire.exact)
+                return fail(c, DORY_ERR_COMM, "local transport: option halo_exact_rows differs: rank %u has %d, rank %u has %d (all ranks must agree)",
+                            c->nodeId, (int)wire.exact, q, (int)!wire.exact);
         }
-        if (stat) { pp.p[q] = Q->d_stat3; continue; }
-        if (layer >= Q->wgrads.size()) return fail(c, DORY_ERR_COMM, "local transport: rank %u has no layer %u", q, layer);
-        auto it = Q->wgrads[layer].find(name);
-        if (it == Q->wgrads[layer].end() || (uint64_t)it->second.rows * it->second.ld != n)
-            return fail(c, DORY_ERR_COMM, "local transport: rank %u's gradient '%s'@%u has another shape", q, name.c_str(), layer);
-        pp.p[q] = it->second.d;
     }
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
-    hipLaunchKernelGGL(local_sum_kernel, dim3(blocks), dim3(256), 0, c->compute, pp, P, n, c->ar_tmp);
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(c->ev_gdone[t & 1], c->compute));
-    c->posted_gdone.store(t, std::memory_order_release);
-    for (uint32_t q = 0; q < P; ++q) {     // nobody reads my gradient any more: the sum may replace it
-        if (q == c->nodeId) continue;
-        dory_ctx *Q = grp.ctx[q];
-        int rc = local_wait_posted(c, Q->posted_gdone, t, q, "the end of gradient sum");
+    const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
+    if (tr == Transport::Local && (sb > c->send_cap || rb > c->recv_cap))
+        return fail(c, DORY_ERR_COMM, "local transport: exchange buffers too small for %u-float rows (peers hold their addresses: no regrowth)", w);
+    // (no growth after dory_halo_plan sized them for the widest layer: only for a tensor uploaded with other dimensions than
+    // dory_configure's)
+    { int rc = ensure_exchange_buffers(c, sb, rb); if (rc) return rc; }
+    // comm stream waits for the producer of `src` on the compute stream
+    HIPCK(c, hipEventRecord(c->ev_a, c->compute));
+    HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
+    const bool deferred = defer && c->opt["halo_overlap"];
+    if (tr == Transport::Local) return exchange_local(c, dir, src, ghost, wire, deferred);
+    {   // host transport and RCCL: same pack / unpack / events, only the way from send_buf to recv_buf differs
+        Timed t(c, "halo", c->comm);
+        Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
+        int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm);
+        if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, w) : exchange_rccl(c, p, w);
+        if (!rc) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm);
         if (rc) return rc;
-        HIPCK(c, hipStreamWaitEvent(c->compute, Q->ev_gdone[t & 1], 0));
+        // the one step of an arm left in the shared body: the host arm's, but it stays behind the unpack, so that the unpack
+        // is enqueued before the host blocks for the copy out of tx_recv (which the next exchange reuses)
+        if (tr == Transport::Host) HIPCK(c, hipStreamSynchronize(c->comm));
     }
-    HIPCK(c, hipMemcpyAsync(gd, c->ar_tmp, n * sizeof(float), hipMemcpyDeviceToDevice, c->compute));
+    HIPCK(c, hipEventRecord(c->ev_b, c->comm));
+    if (deferred) c->halo_pending = true;
+    else HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
     return DORY_OK;
+}
+
+void epoch_graph_drop_locked(dory_ctx *c) {
+    if (c->capturing) {   // abandon a recording in progress
+        hipGraph_t g = nullptr;
+        (void)hipStreamEndCapture(c->compute, &g);
+        if (g) (void)hipGraphDestroy(g);
+        c->capturing = false;
+    }
+    if (c->epoch_exec) (void)hipGraphExecDestroy(c->epoch_exec);
+    if (c->epoch_graph) (void)hipGraphDestroy(c->epoch_graph);
+    c->epoch_exec = nullptr;
+    c->epoch_graph = nullptr;
+    c->lr_table_left = 0;
 }
 
 }  // namespace dory
@@ -305,21 +518,7 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
         w = std::max(w, pad_ld(c->dims[l]));
         if (c->gnn == DORY_GATMH && l < c->L && l < c->heads.size()) w = std::max(w, pad_ld(c->dims[l + 1] * c->heads[l]));
     }
-    const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
-    if (sb > c->send_cap || rb > c->recv_cap) HIPCK(c, hipDeviceSynchronize());
-    if (sb > c->send_cap) {
-        if (c->send_buf) (void)hipFree(c->send_buf);
-        c->send_buf = nullptr; c->send_cap = 0;
-        HIPCK(c, hipMalloc((void **)&c->send_buf, sb));
-        c->send_cap = sb;
-    }
-    if (rb > c->recv_cap) {
-        if (c->recv_buf) (void)hipFree(c->recv_buf);
-        c->recv_buf = nullptr; c->recv_cap = 0;
-        HIPCK(c, hipMalloc((void **)&c->recv_buf, rb));
-        c->recv_cap = rb;
-    }
-    return DORY_OK;
+    return ensure_exchange_buffers(c, (size_t)p.send_total * w * sizeof(float), (size_t)p.recv_total * w * sizeof(float));
 }
 
 int dory_comm_set_host_transport(dory_ctx *c, dory_alltoallv_fn alltoallv, dory_allreduce_fn allreduce_sum, void *user) {
@@ -354,156 +553,6 @@ int dory_comm_init(dory_ctx *c, const void *id128, int rank, int nranks) {
     return DORY_OK;
 }
 
-// resolve (layer, dir) -> source tensor, ghost tensor, width, as Engine::scatterGCN/GAT do
-static int halo_tensors(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **ghost) {
-    if (c->gnn == DORY_GCN && dir == DORY_BACKWARD && tf_layer(c, layer)) {
-        *src = find(c, layer, "g");      // transform-first: A^T g_l needs the ghost rows of g_l
-        *ghost = find(c, layer, "bgg");
-    } else if (c->gnn == DORY_GCN && dir == DORY_FORWARD && layer > 0 && tf_layer(c, layer)) {
-        *src = find(c, layer, "xw");     // transform-first: the already transformed (narrower) rows travel
-        *ghost = find(c, layer, "fgxw");
-    } else if (c->gnn == DORY_GCN) {
-        if (layer == 0 || layer >= c->L) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
-        if (dir == DORY_FORWARD) { *src = find(c, layer - 1, "h"); *ghost = find(c, layer, "fg"); }   // gcn_ops.cpp:205-214
-        else { *src = find(c, layer, "grad"); *ghost = find(c, layer - 1, "bg"); }
-    } else {
-        if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
-        if (dir == DORY_FORWARD) {   // gat_ops.cpp:277-287
-            *src = find(c, layer - 1, "z"); *ghost = find(c, layer - 1, "fg_z");
-            if (layer - 1 < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer - 1] = 0;   // fg_z is about to change: the kept neighbour sum no longer holds
-        }
-        else { *src = find(c, layer - 1, "grad"); *ghost = find(c, layer - 1, "bg_d"); }
-    }
-    if (!*src || !*ghost) return fail(c, DORY_ERR_ARG, "halo: tensors missing");
-    return DORY_OK;
-}
-
-int dory_halo_pack(dory_ctx *c, uint32_t layer, int dir, float *send_buf) {
-    CHECK_CTX(c);
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    Tensor *src, *ghost;
-    int rc = halo_tensors(c, layer, dir, &src, &ghost);
-    if (rc) return rc;
-    HaloPlan &p = c->plan[dir];
-    if (!p.set) return fail(c, DORY_ERR_ARG, "halo_pack: no plan");
-    const bool exact = halo_exact(c);
-    if (exact && src->cols != ghost->cols) return fail(c, DORY_ERR_ARG, "halo_pack: widths of source (%u) and ghost tensor (%u) differ", src->cols, ghost->cols);
-    const uint32_t w = exact ? src->cols : src->ld;
-    if (!exact_ptr_ok(exact, w, send_buf)) return fail(c, DORY_ERR_ARG, "halo_pack: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
-    Timed t(c, "halo", c->compute);
-    return pack_rows(c, send_buf, src, w, exact, p, c->compute);
-}
-
-int dory_halo_unpack(dory_ctx *c, uint32_t layer, int dir, const float *recv_buf) {
-    CHECK_CTX(c);
-    if (layer == 0) c->ah0_valid = false;   // (a caller's transport writing fg@0)
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    Tensor *src, *ghost;
-    int rc = halo_tensors(c, layer, dir, &src, &ghost);
-    if (rc) return rc;
-    HaloPlan &p = c->plan[dir];
-    if (!p.set) return fail(c, DORY_ERR_ARG, "halo_unpack: no plan");
-    const bool exact = halo_exact(c);
-    if (exact && src->cols != ghost->cols) return fail(c, DORY_ERR_ARG, "halo_unpack: widths of source (%u) and ghost tensor (%u) differ", src->cols, ghost->cols);
-    const uint32_t w = exact ? ghost->cols : ghost->ld;
-    if (!exact_ptr_ok(exact, w, recv_buf)) return fail(c, DORY_ERR_ARG, "halo_unpack: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
-    Timed t(c, "halo", c->compute);
-    return unpack_rows(c, ghost->d, ghost->ld, w, exact, recv_buf, p, c->compute);
-}
-
-}  // extern "C"
-
-namespace dory {
-// One all-to-all-v of rows: src rows listed in plan[dir] -> the peers' ghost tensors.  pack -> grouped
-// ncclSend/ncclRecv -> unpack on the comm stream, ordered after the compute stream's work so far; the compute
-// stream waits for the ghosts at once (defer == false) or when wait_halo() is next called (halo_overlap).
-int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) {
-    HaloPlan &p = c->plan[dir];
-    if (!p.set) return fail(c, DORY_ERR_ARG, "halo_exchange: no plan");
-    const bool local = !c->tx_a2a && c->local;
-    if (!c->tx_a2a && !local) {
-        if (!c->nccl) return fail(c, DORY_ERR_COMM, "halo_exchange: dory_comm_init not called");
-        if (c->nranks != (int)c->numNodes) return fail(c, DORY_ERR_COMM, "halo_exchange: communicator size != num_nodes");
-    }
-    if (src->ld != ghost->ld) return fail(c, DORY_ERR_ARG, "halo_exchange: row widths of source and ghost tensor differ");
-    // the padded row width travels (keeps 16-B lanes), or, with option halo_exact_rows, exactly the tensor's columns
-    const bool exact = halo_exact(c);
-    if (exact && src->cols != ghost->cols) return fail(c, DORY_ERR_ARG, "halo_exchange: widths of source (%u) and ghost tensor (%u) differ", src->cols, ghost->cols);
-    const uint32_t w = exact ? src->cols : src->ld;
-    if (local) {   // every rank packs and unpacks at one width: checked here, before anything of this exchange is enqueued or counted
-        for (uint32_t q = 0; q < c->numNodes; ++q) {
-            dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
-            if (Q && halo_exact(Q) != exact)
-                return fail(c, DORY_ERR_COMM, "local transport: option halo_exact_rows differs: rank %u has %d, rank %u has %d (all ranks must agree)",
-                            c->nodeId, (int)exact, q, (int)!exact);
-        }
-    }
-    const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
-    if (local && (sb > c->send_cap || rb > c->recv_cap))
-        return fail(c, DORY_ERR_COMM, "local transport: exchange buffers too small for %u-float rows (peers hold their addresses: no regrowth)", w);
-    if (sb > c->send_cap || rb > c->recv_cap) {   // not reached after dory_halo_plan sized them for the widest layer (a
-        HIPCK(c, hipDeviceSynchronize());          // tensor uploaded with other dimensions than dory_configure's)
-        if (sb > c->send_cap) {
-            if (c->send_buf) (void)hipFree(c->send_buf);
-            c->send_buf = nullptr; c->send_cap = 0;
-            HIPCK(c, hipMalloc((void **)&c->send_buf, sb));
-            c->send_cap = sb;
-        }
-        if (rb > c->recv_cap) {
-            if (c->recv_buf) (void)hipFree(c->recv_buf);
-            c->recv_buf = nullptr; c->recv_cap = 0;
-            HIPCK(c, hipMalloc((void **)&c->recv_buf, rb));
-            c->recv_cap = rb;
-        }
-    }
-    // comm stream waits for the producer of `src` on the compute stream
-    HIPCK(c, hipEventRecord(c->ev_a, c->compute));
-    HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
-    if (local) return local_exchange_send(c, dir, src, ghost, w, exact, defer && c->opt["halo_overlap"]);
-    {
-        Timed t(c, "halo", c->comm);
-        Timed td(c, (defer && c->opt["halo_overlap"]) ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
-        { int prc = pack_rows(c, c->send_buf, src, w, exact, p, c->comm); if (prc) return prc; }
-        if (c->tx_a2a) {   // host transport: same pack / unpack / events, the bytes travel through the caller
-            c->tx_send.resize((size_t)p.send_total * w);
-            c->tx_recv.resize((size_t)p.recv_total * w);
-            if (sb) HIPCK(c, hipMemcpyAsync(c->tx_send.data(), c->send_buf, sb, hipMemcpyDeviceToHost, c->comm));
-            HIPCK(c, hipStreamSynchronize(c->comm));
-            std::vector<uint64_t> sc(c->numNodes), so(c->numNodes), rc_(c->numNodes), ro(c->numNodes);
-            for (uint32_t peer = 0; peer < c->numNodes; ++peer) {
-                sc[peer] = (uint64_t)p.send_counts[peer] * w; so[peer] = (uint64_t)p.send_off[peer] * w;
-                rc_[peer] = (uint64_t)p.recv_counts[peer] * w; ro[peer] = (uint64_t)p.recv_off[peer] * w;
-            }
-            if (c->tx_a2a(c->tx_user, c->tx_send.data(), sc.data(), so.data(), c->tx_recv.data(), rc_.data(), ro.data(), c->numNodes))
-                return fail(c, DORY_ERR_COMM, "halo_exchange: host transport alltoallv failed");
-            if (rb) HIPCK(c, hipMemcpyAsync(c->recv_buf, c->tx_recv.data(), rb, hipMemcpyHostToDevice, c->comm));
-            { int urc = unpack_rows(c, ghost->d, ghost->ld, w, exact, c->recv_buf, p, c->comm); if (urc) return urc; }
-            HIPCK(c, hipStreamSynchronize(c->comm));   // tx_recv is reused by the next exchange
-        } else {
-        ncclComm_t comm = (ncclComm_t)c->nccl;
-        NCCLCK(c, ncclGroupStart());
-        for (uint32_t peer = 0; peer < c->numNodes; ++peer) {
-            if (peer == c->nodeId) continue;
-            if (p.send_counts[peer])
-                NCCLCK(c, ncclSend(c->send_buf + (size_t)p.send_off[peer] * w, (size_t)p.send_counts[peer] * w,
-                                   ncclFloat, (int)peer, comm, c->comm));
-            if (p.recv_counts[peer])
-                NCCLCK(c, ncclRecv(c->recv_buf + (size_t)p.recv_off[peer] * w, (size_t)p.recv_counts[peer] * w,
-                                   ncclFloat, (int)peer, comm, c->comm));
-        }
-        NCCLCK(c, ncclGroupEnd());
-        { int urc = unpack_rows(c, ghost->d, ghost->ld, w, exact, c->recv_buf, p, c->comm); if (urc) return urc; }
-        }
-    }
-    HIPCK(c, hipEventRecord(c->ev_b, c->comm));
-    if (defer && c->opt["halo_overlap"]) c->halo_pending = true;
-    else HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
-    return DORY_OK;
-}
-}  // namespace dory
-
-extern "C" {
-
 int dory_halo_exchange(dory_ctx *c, uint32_t layer, int dir) {
     CHECK_CTX(c);
     { int wrc = wait_halo(c); if (wrc) return wrc; }
@@ -521,19 +570,36 @@ int dory_halo_exchange(dory_ctx *c, uint32_t layer, int dir) {
     return exchange_rows(c, dir, src, ghost, true);
 }
 
-// pack / unpack of any named tensor with the plan of `dir` (foreign transports, multi-context tests)
+// The split entry points: each does its own checks, then split_rows (the wire record, the "halo" interval, the kernels).
+int dory_halo_pack(dory_ctx *c, uint32_t layer, int dir, float *send_buf) {
+    CHECK_CTX(c);
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    Tensor *src, *ghost;
+    int rc = halo_tensors(c, layer, dir, &src, &ghost);
+    if (rc) return rc;
+    if (!c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_pack: no plan");
+    return split_rows(c, "halo_pack", true, dir, src, ghost, send_buf);
+}
+
+int dory_halo_unpack(dory_ctx *c, uint32_t layer, int dir, const float *recv_buf) {
+    CHECK_CTX(c);
+    if (layer == 0) c->ah0_valid = false;   // (a caller's transport writing fg@0)
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    Tensor *src, *ghost;
+    int rc = halo_tensors(c, layer, dir, &src, &ghost);
+    if (rc) return rc;
+    if (!c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack: no plan");
+    return split_rows(c, "halo_unpack", false, dir, src, ghost, const_cast<float *>(recv_buf));
+}
+
+// pack / unpack of any named tensor with the plan of `dir`
 int dory_halo_pack_tensor(dory_ctx *c, uint32_t layer, const char *name, int dir, float *send_buf) {
     CHECK_CTX(c);
     { int wrc = wait_halo(c); if (wrc) return wrc; }
     Tensor *src = name ? find(c, layer, name) : nullptr;
     if (!src || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
-    HaloPlan &p = c->plan[dir];
     if (src->rows != c->N) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: '%s' is not a per-local-vertex tensor", name);
-    const bool exact = halo_exact(c);
-    const uint32_t w = exact ? src->cols : src->ld;
-    if (!exact_ptr_ok(exact, w, send_buf)) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
-    Timed t(c, "halo", c->compute);
-    return pack_rows(c, send_buf, src, w, exact, p, c->compute);
+    return split_rows(c, "halo_pack_tensor", true, dir, src, nullptr, send_buf);
 }
 
 int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int dir, const float *recv_buf) {
@@ -542,13 +608,8 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
     { int wrc = wait_halo(c); if (wrc) return wrc; }
     Tensor *ghost = name ? find(c, layer, name) : nullptr;
     if (!ghost || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
-    HaloPlan &p = c->plan[dir];
     if (ghost->rows != c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: '%s' is not a ghost tensor of that direction", name);
-    const bool exact = halo_exact(c);
-    const uint32_t w = exact ? ghost->cols : ghost->ld;
-    if (!exact_ptr_ok(exact, w, recv_buf)) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", w);
-    Timed t(c, "halo", c->compute);
-    return unpack_rows(c, ghost->d, ghost->ld, w, exact, recv_buf, p, c->compute);
+    return split_rows(c, "halo_unpack_tensor", false, dir, nullptr, ghost, const_cast<float *>(recv_buf));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -564,17 +625,15 @@ int dory_train_stat_global(dory_ctx *c, float *acc_sum, float *loss_sum, uint32_
     HIPCK(c, hipMemcpyAsync(h, c->d_stat, 2 * sizeof(float), hipMemcpyDeviceToHost, c->compute));
     HIPCK(c, hipStreamSynchronize(c->compute));
     h[2] = (float)c->val_rows;      // (exact below 2^24 rows per sum: Friendster's 6.6 M validation rows fit)
-    if (c->numNodes > 1 && c->tx_ar) {
+    if (c->numNodes > 1 && transport_of(c) == Transport::Host) {   // the three floats are on the host already
         if (c->tx_ar(c->tx_user, h, 3)) return fail(c, DORY_ERR_COMM, "train_stat_global: host transport allreduce failed");
     } else if (c->numNodes > 1) {
         HIPCK(c, hipMemcpyAsync(c->d_stat3, h, sizeof(h), hipMemcpyHostToDevice, c->compute));
-        if (c->local) {
-            int rc = local_allreduce(c, 0, "", c->d_stat3, 3, true);
-            if (rc) return rc;
-        } else {
-            if (!c->nccl) return fail(c, DORY_ERR_COMM, "train_stat_global: dory_comm_init not called");
-            NCCLCK(c, ncclAllReduce(c->d_stat3, c->d_stat3, 3, ncclFloat, ncclSum, (ncclComm_t)c->nccl, c->compute));
-        }
+        int rc = allreduce_sum(c, "train_stat_global", c->d_stat3, 3, [&](dory_ctx *Q) -> const float * {
+            if (!Q->d_stat3) fail(c, DORY_ERR_COMM, "local transport: rank %u has no statistics buffer", Q->nodeId);
+            return Q->d_stat3;
+        });
+        if (rc) return rc;
         HIPCK(c, hipMemcpyAsync(h, c->d_stat3, sizeof(h), hipMemcpyDeviceToHost, c->compute));
         HIPCK(c, hipStreamSynchronize(c->compute));
     }
@@ -597,10 +656,7 @@ int dory_weight_update(dory_ctx *c, uint32_t layer) {
     CHECK_CTX(c);
     { int wrc = wait_halo(c); if (wrc) return wrc; }
     if (!c->prealloc || layer >= c->L) return fail(c, DORY_ERR_ARG, "weight_update: bad state or layer");
-    // AdamOptimizer::nextIteration (src/weight-server/AdamOptimizer.cpp:29-34)
-    const float b1p = (float)std::pow((double)0.9f, (double)c->adam.epochs);
-    const float b2p = (float)std::pow((double)0.999f, (double)c->adam.epochs);
-    const float lr_t = (float)(c->adam.lr * (std::sqrt((double)(1 - b2p))) / (1 - b1p));
+    const float lr_t = adam_lr_t(c, c->adam.epochs);
     for (auto &kv : c->weights[layer]) {
         const std::string &name = kv.first;
         // the reference only updates "w"; a_i updates are faked on the weight server
@@ -609,24 +665,22 @@ int dory_weight_update(dory_ctx *c, uint32_t layer) {
         Tensor &w = kv.second;
         Tensor &g = c->wgrads[layer][name];
         const uint64_t n = (uint64_t)w.rows * w.ld;
-        if (c->numNodes > 1 && c->tx_ar) {   // host transport
+        if (c->numNodes > 1) {
+            auto peer_grad = [&](dory_ctx *Q) -> const float * {   // rank Q's gradient of this weight
+                if (layer >= Q->wgrads.size()) {
+                    fail(c, DORY_ERR_COMM, "local transport: rank %u has no layer %u", Q->nodeId, layer);
+                    return nullptr;
+                }
+                auto it = Q->wgrads[layer].find(name);
+                if (it != Q->wgrads[layer].end() && (uint64_t)it->second.rows * it->second.ld == n) return it->second.d;
+                fail(c, DORY_ERR_COMM, "local transport: rank %u's gradient '%s'@%u has another shape", Q->nodeId, name.c_str(), layer);
+                return nullptr;
+            };
+            // (refused before the interval opens: no communicator leaves no "allreduce" timing entry)
+            if (transport_of(c) == Transport::None) return fail(c, DORY_ERR_COMM, "weight_update: dory_comm_init not called");
             Timed t(c, "allreduce", c->compute);
-            c->tx_send.resize(n);
-            HIPCK(c, hipMemcpyAsync(c->tx_send.data(), g.d, n * sizeof(float), hipMemcpyDeviceToHost, c->compute));
-            HIPCK(c, hipStreamSynchronize(c->compute));
-            if (c->tx_ar(c->tx_user, c->tx_send.data(), n)) return fail(c, DORY_ERR_COMM, "weight_update: host transport allreduce failed");
-            HIPCK(c, hipMemcpyAsync(g.d, c->tx_send.data(), n * sizeof(float), hipMemcpyHostToDevice, c->compute));
-            HIPCK(c, hipStreamSynchronize(c->compute));
-        } else if (c->numNodes > 1 && c->local) {
-            Timed t(c, "allreduce", c->compute);
-            int rc = local_allreduce(c, layer, name, g.d, n);
+            int rc = allreduce_sum(c, "weight_update", g.d, n, peer_grad);
             if (rc) return rc;
-        } else if (c->numNodes > 1) {
-            if (!c->nccl) return fail(c, DORY_ERR_COMM, "weight_update: dory_comm_init not called");
-            // sum of per-partition updates (WeightTensor::localUpdate/ghostUpdate,
-            // src/weight-server/weighttensor.cpp:131-166) as one RCCL all-reduce
-            Timed t(c, "allreduce", c->compute);
-            NCCLCK(c, ncclAllReduce(g.d, g.d, n, ncclFloat, ncclSum, (ncclComm_t)c->nccl, c->compute));
         }
         Timed t(c, "adam", c->compute);
         if (c->capturing)   // replayed epochs: step size from the table dory_epoch_graph_launch fills
@@ -649,31 +703,6 @@ int dory_weight_update(dory_ctx *c, uint32_t layer) {
 // recorded).  Everything an epoch allocates lazily must exist already: run one eager epoch
 // first.  Per-epoch host scalars do not survive recording, so Adam's step size comes from a
 // device table indexed by a replay counter that the graph's last node bumps.
-static float adam_lr_t(const dory_ctx *c, unsigned epochs) {   // AdamOptimizer::nextIteration, as dory_weight_update
-    const float b1p = (float)std::pow((double)0.9f, (double)epochs);
-    const float b2p = (float)std::pow((double)0.999f, (double)epochs);
-    return (float)(c->adam.lr * (std::sqrt((double)(1 - b2p))) / (1 - b1p));
-}
-
-}  // extern "C"
-namespace dory {
-void epoch_graph_drop_locked(dory_ctx *c) {
-    if (c->capturing) {   // abandon a recording in progress
-        hipGraph_t g = nullptr;
-        (void)hipStreamEndCapture(c->compute, &g);
-        if (g) (void)hipGraphDestroy(g);
-        c->capturing = false;
-    }
-    if (c->epoch_exec) (void)hipGraphExecDestroy(c->epoch_exec);
-    if (c->epoch_graph) (void)hipGraphDestroy(c->epoch_graph);
-    c->epoch_exec = nullptr;
-    c->epoch_graph = nullptr;
-    c->lr_table_left = 0;
-}
-
-}  // namespace dory
-extern "C" {
-
 int dory_epoch_graph_drop(dory_ctx *c) {
     CHECK_CTX(c);
     epoch_graph_drop_locked(c);

@@ -142,19 +142,6 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
     HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
     return DORY_OK;
 }
-// Ghost rows of the last halo exchange land on the comm stream; with "halo_overlap" the
-// compute stream is only made to wait for them (event ev_b) by the first consumer.
-int wait_halo(dory_ctx *c) {
-    if (c->halo_pending) {
-        if (c->local_pending.on) {   // in-process device transport: the peers' rows, unpack, ev_b
-            int rc = local_exchange_finish(c);
-            if (rc) return rc;
-        }
-        HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
-        c->halo_pending = false;
-    }
-    return DORY_OK;
-}
 
 int gat_materialize(dory_ctx *c, uint32_t layer, int which) {
     if (c->gnn != DORY_GAT || !c->prealloc) return DORY_OK;

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <numeric>
 #include <random>
+#include <tuple>
 
 #include "ctx.hpp"
 
@@ -45,6 +46,18 @@ int fail(dory_ctx *c, int code, const char *fmt, ...);
 #define NEED(ptr, l, nm) NEED_IN(__func__, ptr, l, nm)
 
 // ---- timing: HIP events on the stream the kernels run on --------------------------
+// the two events of one timed interval: from c->ev_pool (drain_timing hands them back), or new ones
+inline std::pair<hipEvent_t, hipEvent_t> take_event_pair(dory_ctx *c) {
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    if (c->ev_pool.empty()) {
+        (void)hipEventCreate(&ev.first);
+        (void)hipEventCreate(&ev.second);
+    } else {
+        ev = c->ev_pool.back();
+        c->ev_pool.pop_back();
+    }
+    return ev;
+}
 struct Timed {
     dory_ctx *c;
     hipStream_t s;
@@ -52,14 +65,7 @@ struct Timed {
     hipEvent_t a = nullptr, b = nullptr;
     Timed(dory_ctx *ctx, const char *family, hipStream_t st) : c(ctx), s(st), fam(family) {
         if (!c->timing || c->capturing) return;
-        if (c->ev_pool.empty()) {
-            (void)hipEventCreate(&a);
-            (void)hipEventCreate(&b);
-        } else {
-            a = c->ev_pool.back().first;
-            b = c->ev_pool.back().second;
-            c->ev_pool.pop_back();
-        }
+        std::tie(a, b) = take_event_pair(c);
         (void)hipEventRecord(a, s);
     }
     ~Timed() {
@@ -97,7 +103,7 @@ int upload_array(dory_ctx *c, T **dst, const T *src, uint64_t n) {
 }
 
 // Ghost rows of the last halo exchange land on the comm stream; with "halo_overlap" the compute stream is only
-// made to wait for them (event ev_b) by the first consumer.
+// made to wait for them (event ev_b) by the first consumer (abi_comm.hip).
 int wait_halo(dory_ctx *c);
 // in-process device transport: second half of a deferred exchange (abi_comm.hip); wait_halo and dory_sync run it
 int local_exchange_finish(dory_ctx *c);

@@ -43,6 +43,13 @@ struct HaloPlan {
     uint32_t *d_recv_slots = nullptr;  // concat over peers
 };
 
+// The wire format of a packed halo row: w floats per row -- the tensor's padded ld, or with `exact` (option halo_exact_rows)
+// its cols.  Made by row_wire() (abi_comm.hip) alone; which pack / unpack kernels run and the zeroing of [w, ld) follow from it.
+struct RowWire {
+    uint32_t w = 0;
+    bool exact = false;
+};
+
 // K1b: source-blocked adjacency (per-block CSR over the virtual source space [local;ghost])
 struct BlockedAdj {
     uint32_t nb = 0;        // number of source blocks (multiple of 8: one per XCD per round)
@@ -242,8 +249,8 @@ struct dory_ctx {
         bool on = false;
         int dir = 0;
         float *ghost = nullptr;
-        uint32_t ghost_ld = 0, w = 0;
-        bool exact = false;                         // w is the exact width (option halo_exact_rows): the unpack zeroes [w, ghost_ld)
+        uint32_t ghost_ld = 0;
+        dory::RowWire wire;                         // what the rows in recv_buf look like (exact: the unpack zeroes [w, ghost_ld))
         hipEvent_t t_halo_b = nullptr, t_kind_b = nullptr;   // timing: end events of the "halo" / "halo_deferred|waited" intervals
     } local_pending;
     float *ar_tmp = nullptr;          // gradient sum before it replaces the local gradient
