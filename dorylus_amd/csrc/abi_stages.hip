@@ -454,6 +454,37 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
     return spmm(c, Out, Out.val, 1, *grad, bg, *aTg, c->dims[layer], 0, nullptr, bf_bwd);
 }
 
+// What the two edge passes of the multi-head GAT on the sweep skeleton do alike (forward: the layout of the in-edges; source side of
+// the backward: of the out-edges).  plan() decides the wide form -- option gatmh_bf16_wide: bf16 rows of 128 floats or more, several
+// heads of 16 / 32 / 64 features, are gathered eight features per lane on 16-lane groups (same bits; gat_mh_sweep.hip); everywhere else:
+// as with 0 -- and sizes the launches.  run() makes them: the blocks of local rows, `between` (what has to land before a ghost row
+// is read), then the ghost blocks on top of the first launch's sums; without ghost rows `between`, then all blocks at once.
+struct GatmhSweep {
+    const DerivedAdj *S = nullptr;
+    bool bf16 = false, wide = false;
+    SweepLaunch sw;
+    int plan(dory_ctx *c, const DerivedAdj &layout, const SpmmArgs &sa /* N, ld: as in the caller's own sweep_supported test */, uint32_t K,
+             uint32_t D, bool ghosts, int shl, int pass, bool bf16_rows) {
+        S = &layout;
+        bf16 = bf16_rows;
+        wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, sa.ld) && sweep_supported(sa, layout, GATMH_WIDE_GROUP);
+        const int group = gatmh_sweep_group(sa.ld);
+        sw = wide ? sweep_launch(c, layout, sa.ld, GATMH_WIDE_GROUP, ghosts, GATMH_WIDE_ROWS, true)
+                  : sweep_launch(c, layout, sa.ld, group, ghosts, gatmh_sweep_rows(layout, group, shl, pass));
+        return sw.done ? (int)DORY_OK : fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
+    }
+    template <class Between, class Part>
+    int run(dory_ctx *c, Between between, Part part) const {
+        auto blocks = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
+            return part(GatSweepPart{sw.G, b_lo, b_hi, accumulate, sw.done, sw.ctl, sw.sflags, c->compute, bf16, wide});
+        };
+        int rc;
+        if (sw.two && (rc = blocks(0, S->nb_local, false))) return rc;
+        if ((rc = between())) return rc;
+        return sw.two ? blocks(S->nb_local, S->nb, true) : blocks(0, S->nb, false);
+    }
+};
+
 // The multi-head GAT extension: edge softmax + weighted sum.
 // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
 // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
@@ -474,14 +505,14 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                              (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
         AGG_NEED(fgz, fl, "fg_z"); AGG_NEED(fgel, fl, "fg_el");
         const DerivedAdj &Sf = In.swp;
-        const int shl = gatmh_sweep_hl(K, D, z->ld), sgroup = z->ld >= 128 ? 32 : 16;
+        const int shl = gatmh_sweep_hl(K, D, z->ld);
         Tensor *op = find(c, fl, "op"), *dpos = find(c, fl, "dpos");
         // (the same addressing test the launchers make -- 32-bit byte offsets through the buffer resource -- so that a
         // partition they would refuse takes the blocked kernels instead of failing, as spmm() does)
         SpmmArgs sa{};
         sa.N = c->N; sa.ld = z->ld;
         const bool sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
-                           shl != 0 && op && dpos && sweep_supported(sa, Sf, sgroup);
+                           shl != 0 && op && dpos && sweep_supported(sa, Sf, gatmh_sweep_group(z->ld));
         const bool bf16 = bfm >= 1;
         if (bf16 && !sweep)
             return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
@@ -495,30 +526,23 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             // K1s's skeleton: sums in registers over all source blocks, single-pass softmax against the upper-bound shift
             int rc = ensure_scratch(c, gatmh_sweep_scratch_bytes(Sf, c->N, z->ld, el->ld));
             if (rc) return rc;
-            // option gatmh_bf16_wide: bf16 rows of 128 floats or more, several heads of 16 / 32 / 64 features, are gathered eight
-            // features per lane on 16-lane groups (same bits; gat_mh_sweep.hip).  Everywhere else: as with 0
-            const bool wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, z->ld) && sweep_supported(sa, Sf, GATMH_WIDE_GROUP);
-            const SweepLaunch sw = wide ? sweep_launch(c, Sf, z->ld, GATMH_WIDE_GROUP, In.ghosts > 0, GATMH_WIDE_ROWS, true)
-                                        : sweep_launch(c, Sf, z->ld, sgroup, In.ghosts > 0, gatmh_sweep_rows(Sf, sgroup, shl, 0));
-            if (!sw.done) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
+            GatmhSweep gs;
+            if ((rc = gs.plan(c, Sf, sa, K, D, In.ghosts > 0, shl, 0, bf16))) return rc;
             // the rows the sweep gathers: z / fg_z, or (bf16) their rounded copies in the shadow buffer -- the local rows
             // converted now, the ghost rows once their exchange has landed
             Bf16Rows bf;
             if (bf16) {
                 if ((rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
                 c->gatmh_bf16_gathers_fwd++;
-                if (wide) c->gatmh_bf16_gathers_fwd_wide++;
+                if (gs.wide) c->gatmh_bf16_gathers_fwd_wide++;
             }
             const float *zs = bf16 ? bf.xl : z->d, *zgs = bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), *a_l = c->weights[fl]["a_l"].d;
-            auto part = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
-                HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, sw.G, b_lo,
-                                                         b_hi, accumulate, sw.done, sw.ctl, sw.sflags, c->compute, el->d, fgel->d, bf16, wide));
-                return DORY_OK;
-            };
             HIPCK(c, launch_gatmh_sweep_begin(c->N, In.ghosts, K, z->ld, el->ld, Sf, el->d, fgel->d, c->scratch, c->compute));
-            if (sw.two && (rc = part(0, Sf.nb_local, false))) return rc;
-            if ((rc = wait_halo(c)) || (rc = bf.ghosts_landed())) return rc;
-            if ((rc = sw.two ? part(Sf.nb_local, Sf.nb, true) : part(0, Sf.nb, false))) return rc;
+            rc = gs.run(c, [&]() -> int { const int r = wait_halo(c); return r ? r : bf.ghosts_landed(); }, [&](const GatSweepPart &p) -> int {
+                HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, p, el->d, fgel->d));
+                return DORY_OK;
+            });
+            if (rc) return rc;
             HIPCK(c, launch_gatmh_forward_sweep_finish(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Sf, z->d, fgz->d, el->d, fgel->d,
                                                        er->d, o->d, op->d, m->d, den->d, dpos->d, c->scratch, c->compute, bf16));
             if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
@@ -570,7 +594,7 @@ static int gatmh_backward_exchange(dory_ctx *c, const GatmhBwd &T) {
 
 // The sweep forms (gat_mh_sweep.hip).  Destination side: this layer's forward ran on the skeleton and left the positive-branch
 // sums, so t / der / st come from a row-wise kernel -- no edge pass.  Source side: the sweep over the out-edges' layout.
-static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tensor *dpos, int shl, bool bf16) {
+static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tensor *dpos, int shl, const SpmmArgs &sa, bool bf16) {
     Adjacency &Out = c->adj[ADJ_OUT];
     const DerivedAdj &So = Out.swp;
     const uint32_t K = T.K, D = T.D, ld = T.z->ld, ldk = T.el->ld, lds4 = T.st->ld / 4;
@@ -584,14 +608,8 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
     if (T.phase == 1) return DORY_OK;
     if ((rc = gatmh_backward_exchange(c, T))) return rc;
     if ((rc = ensure_scratch(c, gatmh_src_sweep_scratch_bytes(So, c->N, Out.ghosts, K, ld, ldk)))) return rc;
-    const int sgroup = ld >= 128 ? 32 : 16;
-    SpmmArgs sa{};
-    sa.N = c->N; sa.ld = ld;
-    // option gatmh_bf16_wide, as in the forward pass: the source side's bf16 rows eight features per lane (same bits)
-    const bool wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, ld) && sweep_supported(sa, So, GATMH_WIDE_GROUP);
-    const SweepLaunch sw = wide ? sweep_launch(c, So, ld, GATMH_WIDE_GROUP, Out.ghosts > 0, GATMH_WIDE_ROWS, true)
-                                : sweep_launch(c, So, ld, sgroup, Out.ghosts > 0, gatmh_sweep_rows(So, sgroup, shl, 1));
-    if (!sw.done) return fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
+    GatmhSweep gs;
+    if ((rc = gs.plan(c, So, sa, K, D, Out.ghosts > 0, shl, 1, bf16))) return rc;
     {
         Timed t(c, "spmm", c->compute);
         // the rows the sweep gathers: do / bg_do, or (bf16) their rounded copies -- the ghost rows have landed by now
@@ -600,18 +618,16 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
         if (bf16) {
             if ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed())) return rc;
             c->gatmh_bf16_gathers_src++;
-            if (wide) c->gatmh_bf16_gathers_src_wide++;
+            if (gs.wide) c->gatmh_bf16_gathers_src_wide++;
         }
         const float *dos = bf16 ? bf.xl : T.dO->d, *dogs = bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr);
-        auto part = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
-            HIPCK(c, launch_gatmh_src_sweep_part(c->N, Out.ghosts, K, D, ld, ldk, So, dos, dogs, T.el->d, T.dz->d, c->scratch, sw.G, b_lo, b_hi,
-                                                 accumulate, sw.done, sw.ctl, sw.sflags, c->compute, bf16, wide));
-            return DORY_OK;
-        };
         HIPCK(c, launch_gatmh_src_sweep_begin(c->N, Out.ghosts, K, ld, ldk, So, st4, reinterpret_cast<const float4 *>(T.bgst->d), lds4,
                                               c->scratch, c->compute));
-        if (sw.two && (rc = part(0, So.nb_local, false))) return rc;
-        if ((rc = sw.two ? part(So.nb_local, So.nb, true) : part(0, So.nb, false))) return rc;
+        rc = gs.run(c, [] { return (int)DORY_OK; }, [&](const GatSweepPart &p) -> int {
+            HIPCK(c, launch_gatmh_src_sweep_part(c->N, Out.ghosts, K, D, ld, ldk, So, dos, dogs, T.el->d, T.dz->d, c->scratch, p));
+            return DORY_OK;
+        });
+        if (rc) return rc;
         HIPCK(c, launch_gatmh_src_sweep_finish(c->N, K, D, ld, ldk, So, T.z->d, T.el->d, T.dO->d, T.der->d, c->weights[T.fl]["a_l"].d,
                                                c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->scratch, c->compute, bf16));
     }
@@ -667,7 +683,7 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     SpmmArgs sa{};     // the launchers' addressing tests (rows and the 16-byte statistics records through buffer resources): a
     sa.N = c->N; sa.ld = z->ld;   // partition they would refuse takes the blocked kernels
     const bool src_sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && shl && So.built && !So.na && So.nb > 0 &&
-                           ((z->ld >> 2) % (uint32_t)shl) == 0 && sweep_supported(sa, So, z->ld >= 128 ? 32 : 16) &&
+                           ((z->ld >> 2) % (uint32_t)shl) == 0 && sweep_supported(sa, So, gatmh_sweep_group(z->ld)) &&
                            (uint64_t)std::max(c->N, Out.ghosts) * K * 16u < (1ull << 32) && K * 16u < (1u << 24);
     // bf16 rows of do / bg_do for the source-side sweep (gatmh_bf16_gather = 2): refused, before anything is launched, where
     // the call would not take that sweep; the shadow buffer is sized here too (it cannot grow inside a recording)
@@ -691,7 +707,7 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
         }
     }
     if ((rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + (size_t)c->N * K * 16 + 256))) return rc;
-    if (dst_rowwise && src_sweep) return gatmh_backward_sweep(c, T, op, dpos, shl, bf16);
+    if (dst_rowwise && src_sweep) return gatmh_backward_sweep(c, T, op, dpos, shl, sa, bf16);
     const BlockedAdj &Bbi = gatmh_blocked_for(In, z->ld), &Bbo = gatmh_blocked_for(Out, z->ld);
     const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
     if (c->opt["gatmh_blocked"] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na && nbmax > 0 &&

@@ -465,6 +465,7 @@ hipError_t launch_gatmh_backward_blocked_src(uint32_t N, uint32_t K, uint32_t D,
                                              float *partial /*nb x N x (ld + K) floats*/, bool ghosts, hipStream_t s);
 // the edge passes on K1s's skeleton (csrc/gat_mh_sweep.hip): register-resident sums over all source blocks of the sweep layout,
 // single-pass softmax against a per-(v,k) upper-bound shift; the destination side of the backward pass needs no edges
+inline int gatmh_sweep_group(uint32_t ld) { return ld >= 128 ? 32 : 16; }   // lanes per slab of a row: 128 floats, or one slab of 64
 int gatmh_sweep_hl(uint32_t K, uint32_t D, uint32_t ld);   // lanes per head; 0 = shape not covered (blocked kernels)
 int gatmh_sweep_rows(const BlockedAdj &S, int group, int HL, int pass /*0 forward, 1 source side*/);   // rows per lane group of a launch
 // the wide form of the passes on bf16 rows (option gatmh_bf16_wide; gatmh_*_sweep_bf16x8_kernel): 16-lane groups, two rows per group,
@@ -474,12 +475,21 @@ constexpr int GATMH_WIDE_GROUP = 16, GATMH_WIDE_ROWS = 2;
 size_t gatmh_sweep_scratch_bytes(const BlockedAdj &S, uint32_t N, uint32_t ld, uint32_t ldk);
 hipError_t launch_gatmh_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *el,
                                     const float *elg, float *scratch, hipStream_t s);
+// what the launches of the forward and of the source-side pass take alike
+struct GatSweepPart {
+    uint32_t cus;            // workgroups per sweep and XCD
+    uint32_t b_lo, b_hi;     // the blocks of the sweep layout this launch walks
+    bool accumulate;         // go on from the sums an earlier launch left (the ghost blocks of a partitioned run)
+    uint32_t *done;          // gate counters
+    SweepCtl ctl;
+    uint32_t flags;
+    hipStream_t s;
+    bool bf16;               // the rows gathered are bf16 rows of ld elements (launch_bf16_rows; option gatmh_bf16_gather)
+    bool wide;               // bf16 rows, eight features per lane (option gatmh_bf16_wide): where gatmh_wide_applies()
+};
 hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
-                                           float *scratch, uint32_t cus, uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done,
-                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg /* the sources' scores (local, ghost rows) */,
-                                           bool bf16 = false /* z / zg point at bf16 rows of ld elements (launch_bf16_rows; option gatmh_bf16_gather) */,
-                                           bool wide = false /* bf16 rows, eight features per lane (option gatmh_bf16_wide): where gatmh_wide_applies() */);
+                                           float *scratch, const GatSweepPart &p, const float *el, const float *elg /* the sources' scores (local, ghost rows) */);
 hipError_t launch_gatmh_forward_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                              const uint32_t *rowidx, const BlockedAdj &S, const float *z, const float *zg, const float *el,
                                              const float *elg, const float *er, float *o, float *op, float *m, float *den, float *dpos,
@@ -492,10 +502,7 @@ size_t gatmh_src_sweep_scratch_bytes(const BlockedAdj &S, uint32_t N, uint32_t G
 hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                         const float4 *st4, const float4 *stg, uint32_t lds4, float *scratch, hipStream_t s);
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
-                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, uint32_t cus,
-                                       uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags,
-                                       hipStream_t s, bool bf16 = false /* d_o / dog point at bf16 rows (option gatmh_bf16_gather = 2) */,
-                                       bool wide = false /* eight features per lane (option gatmh_bf16_wide): where gatmh_wide_applies() */);
+                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, const GatSweepPart &p);
 hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *z,
                                          const float *el, const float *d_o, const float *der, const float *a_l, const float *a_r, float *del,
                                          float *dz, float *scratch, hipStream_t s,

@@ -71,10 +71,6 @@ constexpr int GATMH_BLK_ROWS = GATMH_BLK_ROWS_DEF;   // destination rows per wor
 // as well as an xor would.  Only a head wider than 16 lanes (a single head on a 32-lane slab) still needs ds_bpermute.
 // Lane groups of 16 are DPP rows (lane / 16), so this covers the single-head 64-float layer entirely (round 4; it used two
 // ds_bpermute round trips through the LDS crossbar per entry before).
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
 __device__ __forceinline__ float head_lanes_sum(float v, int HL) {
     if (HL >= 2) v += dpp_mov<0xB1>(v);
     if (HL >= 4) v += dpp_mov<0x4E>(v);

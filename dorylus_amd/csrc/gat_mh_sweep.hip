@@ -39,9 +39,6 @@ namespace dory {
 #ifndef GATMH_SLACK
 #define GATMH_SLACK SWEEP_SLACK   // windows a workgroup may run ahead of its sweep's slowest: 0 / 1 / 2 = 20.5 / 18.0 / 18.4 ms per 8-head epoch (round 5)
 #endif
-#ifndef GATMH_SRC16_LOADER
-#define GATMH_SRC16_LOADER true
-#endif
 #ifndef GATMH_SRC16_BATCH
 #define GATMH_SRC16_BATCH 4   // (round 6, with one statistics gather per batch: 2 -> 4 = 2.91 -> 2.77 ms; 2 was best while every entry had its own)
 #endif
@@ -93,18 +90,135 @@ namespace dory {
 constexpr float GATMH_LOG2E = 1.4426950408889634f;
 constexpr float GATMH_DEN_TINY = 1e-30f;
 
-template <int CTRL>
-__device__ __forceinline__ float sw_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
 // sum over the HL neighbouring lanes of a head, all inside the VALU (gat_mh_blocked.hip: head_lanes_sum); HL <= 16
 template <int HL>
 __device__ __forceinline__ float sw_head_sum(float v) {
-    if constexpr (HL >= 2) v += sw_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-    if constexpr (HL >= 4) v += sw_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-    if constexpr (HL >= 8) v += sw_dpp<0x141>(v);   // row_half_mirror
-    if constexpr (HL >= 16) v += sw_dpp<0x140>(v);  // row_mirror
+    if constexpr (HL >= 2) v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+    if constexpr (HL >= 4) v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+    if constexpr (HL >= 8) v += dpp_mov<0x141>(v);   // row_half_mirror
+    if constexpr (HL >= 16) v += dpp_mov<0x140>(v);  // row_mirror
     return v;
+}
+
+// ---- what the forward and the source-side sweep share: GatFwdSweepOp and GatSrcSweepOp differ in their tensors and in how a score is formed
+typedef float gm_f2 __attribute__((ext_vector_type(2)));
+// the sums of one row in a lane: NC float4 of the main sums (the forward's acc, the source side's S), the same of their positive-branch
+// parts, and the head's pair ((den, dpos) / (T, T+)).  NC = 1: four features per lane; 2 (the wide forms): features 0-3 and 4-7 of the lane's chunk
+template <int NC> struct GatRow { float4 m[NC], p[NC]; gm_f2 pair; };
+__device__ __forceinline__ void gatmh_row_fma(GatRow<1> &r, gm_f2 al, const float4 &x) {
+    r.m[0] = fma4(al.x, x, r.m[0]);
+    r.p[0] = fma4(al.y, x, r.p[0]);
+}
+__device__ __forceinline__ void gatmh_row_fma(GatRow<2> &r, gm_f2 al, const Float4x2 &x) {
+    r.m[0] = fma4(al.x, x.lo, r.m[0]);
+    r.p[0] = fma4(al.y, x.lo, r.p[0]);
+    r.m[1] = fma4(al.x, x.hi, r.m[1]);
+    r.p[1] = fma4(al.y, x.hi, r.p[1]);
+}
+// an entry's weight from its shifted scores t = (t1, t2), in log2 units: (alpha, alpha on LeakyReLU's positive branch)
+template <bool FULL>
+__device__ __forceinline__ gm_f2 gatmh_entry_alpha(gm_f2 t, bool on) {
+    float al = __builtin_amdgcn_exp2f(fmaxf(t.x, t.y));
+    if constexpr (!FULL) al = on ? al : 0.f;               // (an absent slot gathered zeros: its score is not zero)
+    return (gm_f2){al, t.x > t.y ? al : 0.f};              // positive branch: el + er > 0  <=>  t1 > t2
+}
+
+// The per-(row, head) constants of a workgroup's rows in an LDS table, value(row, head) each (zeros past the rows and the heads);
+// sets the lane's head inside its slab (hl) and in the row (k)
+template <int GROUP, int HL, int R, class F>
+__device__ __forceinline__ const float2 *gatmh_row_head_table(const BlockedAdj &B, uint32_t pos0, uint32_t xend, uint32_t col, int li, uint32_t K,
+                                                              uint32_t &hl, uint32_t &k, F value) {
+    constexpr int HPS = GROUP / HL, RW = (SWEEP_NT / GROUP) * R;   // heads per slab of GROUP lanes, rows per workgroup
+    __shared__ float2 tab[RW * HPS];
+    const uint32_t head0 = (col / GROUP) * HPS;            // first head of this slab
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(RW * HPS); i += SWEEP_NT) {
+        const uint32_t lrow = i / HPS, kk = head0 + i % HPS, pos = pos0 + lrow;
+        const uint32_t v = pos < xend ? (B.perm ? B.perm[pos] : pos) : 0xFFFFFFFFu;
+        float2 c = make_float2(0.f, 0.f);
+        if (v != 0xFFFFFFFFu && kk < K) c = value(v, kk);
+        tab[i] = c;
+    }
+    hl = (uint32_t)li / HL;
+    k = min(head0 + hl, K - 1);
+    return tab;
+}
+
+// AUX_BATCH: the second table's records of a batch's entries [0, n), ONE gather instruction for EPL entries -- lane (quad position
+// qpos) fetches entry i * EPL + qpos with load i, and the lanes of a quad that share a head get entry u's record by a DPP quad
+// broadcast (heads of two lanes: two entries per instruction).  The record is a float (4-byte load, one DPP move) or a float3 (12, three)
+__device__ __forceinline__ void gatmh_rec_load(float &r, __amdgpu_buffer_rsrc_t rs, uint32_t off) {
+    r = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
+}
+__device__ __forceinline__ void gatmh_rec_load(float3 &r, __amdgpu_buffer_rsrc_t rs, uint32_t off) {
+    typedef uint32_t u3 __attribute__((ext_vector_type(3)));
+    const u3 v = __builtin_amdgcn_raw_buffer_load_b96(rs, off, 0, 0);
+    r = make_float3(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z));
+}
+template <int QP> __device__ __forceinline__ float gatmh_rec_bcast(float v) { return dpp_mov<QP>(v); }
+template <int QP> __device__ __forceinline__ float3 gatmh_rec_bcast(const float3 &v) { return make_float3(dpp_mov<QP>(v.x), dpp_mov<QP>(v.y), dpp_mov<QP>(v.z)); }
+template <int HL> struct GatRecBatch {
+    static constexpr int EPL = HL >= 4 ? 4 : 2;            // entries one gather serves (the lanes of a quad that share a head)
+    static __device__ __forceinline__ uint32_t qpos(int li) { return (uint32_t)li & (uint32_t)(EPL - 1); }
+    template <int U0, int NB, int NL, class Rec>
+    static __device__ __forceinline__ void spread(const Rec (&rec)[NL], Rec (&ax)[NB]) {
+        if constexpr (U0 < NB) {
+            constexpr int pp = U0 % EPL;
+            constexpr int QP = HL >= 4 ? pp * 0x55 : (pp | (pp << 2) | ((2 + pp) << 4) | ((2 + pp) << 6));
+            ax[U0] = gatmh_rec_bcast<QP>(rec[U0 / EPL]);
+            spread<U0 + 1, NB, NL>(rec, ax);
+        }
+    }
+    // rs, rowb, base: the table's buffer resource, the bytes of a row of it and the lane's offset inside a row
+    template <int NB, class Rec>
+    static __device__ __forceinline__ void fetch(__amdgpu_buffer_rsrc_t rs, uint32_t rowb, uint32_t base, uint32_t qp, const uint2 *stp, uint32_t n,
+                                                 Rec (&ax)[NB]) {
+        constexpr int NL = (NB + EPL - 1) / EPL;
+        Rec rec[NL];
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const uint32_t j = (uint32_t)i * EPL + qp;
+            const uint32_t sidx = stp[j < (uint32_t)NB ? j : (uint32_t)NB - 1].x;       // (one LDS read per lane: four addresses per head)
+            gatmh_rec_load(rec[i], rs, j < n ? __umul24(sidx, rowb) + base : 0xFFFFFFFFu);
+        }
+        spread<0, NB, NL>(rec, ax);
+    }
+};
+
+// One row's sums to their tensors: the NC main chunks to a.out (a piece of a split row: its slot of w.split_partial), the positive-
+// branch chunks to pos_rows / pos_slots, the head's pair to pair_rows / pair_slots ([.][2 ldk]) by the head's first lane; the second
+// launch of a partitioned run (ghost blocks) adds what the first left there.  WIDE (NC = 2): col, nchunk count eight features -- two
+// float4 per tensor, at the addresses the narrow form's two lanes write
+template <int HL, int NC>
+__device__ __forceinline__ void gatmh_store_row(const GatRow<NC> &r, const SpmmArgs &a, const SweepArgs &w, uint32_t v, bool piece, uint32_t slot,
+                                                uint32_t col, uint32_t nchunk, float *pos_rows, float *pos_slots, float *pair_rows,
+                                                float *pair_slots, uint32_t k, uint32_t ldk, uint32_t KD) {
+    float4 *q = piece ? reinterpret_cast<float4 *>(w.split_partial) + ((size_t)slot * nchunk + col) * NC
+                      : reinterpret_cast<float4 *>(a.out) + ((size_t)v * nchunk + col) * NC;
+    float4 *qp = piece ? reinterpret_cast<float4 *>(pos_slots) + ((size_t)slot * nchunk + col) * NC
+                       : reinterpret_cast<float4 *>(pos_rows) + ((size_t)v * nchunk + col) * NC;
+    float2 *dq = reinterpret_cast<float2 *>(piece ? pair_slots + (size_t)slot * 2 * ldk : pair_rows + (size_t)v * 2 * ldk) + k;
+    float4 o[NC], p[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { o[c] = r.m[c]; p[c] = r.p[c]; }
+    float2 dn = make_float2(r.pair.x, r.pair.y);
+    const bool head_lane = (threadIdx.x % HL) == 0 && col * 4 * NC < KD;
+    if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {   // second launch of a partitioned run (ghost blocks)
+        float4 o0[NC], p0[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) o0[c] = q[c];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) p0[c] = qp[c];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { o[c].x += o0[c].x; o[c].y += o0[c].y; o[c].z += o0[c].z; o[c].w += o0[c].w; }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { p[c].x += p0[c].x; p[c].y += p0[c].y; p[c].z += p0[c].z; p[c].w += p0[c].w; }
+        if (head_lane) { const float2 d0 = *dq; dn.x += d0.x; dn.y += d0.y; }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) q[c] = o[c];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) qp[c] = p[c];
+    if (head_lane) *dq = dn;
 }
 
 // ---- max_u el[u,k]: ordered-int keys so that an integer atomic max orders floats -----------------------------------
@@ -153,11 +267,9 @@ struct GatFwdSweepOp {
     static_assert(!WIDE || (BF16 && GROUP == 16 && HL >= 2 && HL <= 8), "eight features per lane: bf16 rows, 16-lane groups, heads of 16 / 32 / 64 features");
     static constexpr bool PLAIN = false, UNIT_W = true, PROLOGUE = true, AUX_BATCH = !WIDE && (GROUP <= GATMH_FWD_EL_TABLE);
     static constexpr bool BF16_ROWS = BF16, WIDE_ROWS = WIDE;
-    static constexpr int EPL = HL >= 4 ? 4 : 2;
     static constexpr int BATCH = WIDE ? GATMH_FWD_WIDE_BATCH : GROUP == 16 ? GATMH_FWD16_BATCH : GATMH_FWD_BATCH;
     static constexpr int SLACK = GATMH_SLACK;
     static constexpr int HPS = GROUP / HL;                     // heads per slab of GROUP lanes
-    static constexpr int RW = (SWEEP_NT / GROUP) * R;
     // arguments
     const float *er, *a_l;
     const int *elmax_key;
@@ -172,58 +284,25 @@ struct GatFwdSweepOp {
     __amdgpu_buffer_rsrc_t rs2;
     const float2 *ctab;
     float4 al4h;                                               // WIDE: a_l of the lane's features 4 .. 7
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    struct Row4 { float4 acc, accp; f2 den; };                 // den = (all edges, positive-branch edges)
-    struct Row8 { float4 acc, accp, acc2, accp2; f2 den; };    // WIDE: features 0-3 and 4-7 of the lane's chunk
-    typedef typename std::conditional<WIDE, Row8, Row4>::type Row;
+    typedef gm_f2 f2;
+    typedef GatRow<WIDE ? 2 : 1> Row;                          // pair = den = (all edges, positive-branch edges)
     struct RowC { float c1, c2; };
     typedef float Aux;                                          // AUX_BATCH: el[src, k]
     __device__ __forceinline__ Aux aux(uint32_t, uint32_t, bool) const { return 0.f; }
-    template <int U0, int NB, int NL>
-    __device__ __forceinline__ void aux_spread(const float (&rec)[NL], Aux (&ax)[NB]) const {
-        if constexpr (U0 < NB) {
-            constexpr int pp = U0 % EPL;
-            constexpr int QP = HL >= 4 ? pp * 0x55 : (pp | (pp << 2) | ((2 + pp) << 4) | ((2 + pp) << 6));
-            ax[U0] = sw_dpp<QP>(rec[U0 / EPL]);
-            aux_spread<U0 + 1, NB, NL>(rec, ax);
-        }
-    }
     template <int NB> __device__ __forceinline__ void aux_batch(const uint2 *stp, uint32_t n, Aux (&ax)[NB]) const {
-        constexpr int NL = (NB + EPL - 1) / EPL;
-        float rec[NL];
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const uint32_t j = (uint32_t)i * EPL + qpos;
-            const uint32_t sidx = stp[j < (uint32_t)NB ? j : (uint32_t)NB - 1].x;
-            rec[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs2, j < n ? __umul24(sidx, ldk * 4u) + aux_b : 0xFFFFFFFFu, 0, 0));
-        }
-        aux_spread<0, NB, NL>(rec, ax);
+        GatRecBatch<HL>::template fetch<NB>(rs2, ldk * 4u, aux_b, qpos, stp, n, ax);
     }
-    __device__ __forceinline__ void init(Row &r) const {
-        r.acc = make_float4(0.f, 0.f, 0.f, 0.f); r.accp = r.acc; r.den = (f2){0.f, 0.f};
-        if constexpr (WIDE) { r.acc2 = r.acc; r.accp2 = r.acc; }
-    }
+    __device__ __forceinline__ void init(Row &r) const { r = Row{}; }
     __device__ __forceinline__ void prologue(const SpmmArgs &a, const BlockedAdj &B, uint32_t pos0, uint32_t xend, bool ghost_launch, uint32_t col, int li) {
-        __shared__ float2 tab[RW * HPS];
-        const uint32_t head0 = (col / GROUP) * HPS;            // first head of this slab
-        for (uint32_t i = threadIdx.x; i < (uint32_t)(RW * HPS); i += SWEEP_NT) {
-            const uint32_t lrow = i / HPS, kk = head0 + i % HPS, pos = pos0 + lrow;
-            const uint32_t v = pos < xend ? (B.perm ? B.perm[pos] : pos) : 0xFFFFFFFFu;
-            float2 c = make_float2(0.f, 0.f);
-            if (v != 0xFFFFFFFFu && kk < K) {
-                const float e = er[(size_t)v * ldk + kk];
-                const float mm = lrelu02(gm_fkey_inv(elmax_key[kk]) + e);
-                c = make_float2((e - mm) * GATMH_LOG2E, (GATMH_SLOPE * e - mm) * GATMH_LOG2E);
-            }
-            tab[i] = c;
-        }
-        ctab = tab;
-        hl = (uint32_t)li / HL;
-        k = min(head0 + hl, K - 1);
+        ctab = gatmh_row_head_table<GROUP, HL, R>(B, pos0, xend, col, li, K, hl, k, [&](uint32_t v, uint32_t kk) {
+            const float e = er[(size_t)v * ldk + kk];
+            const float mm = lrelu02(gm_fkey_inv(elmax_key[kk]) + e);
+            return make_float2((e - mm) * GATMH_LOG2E, (GATMH_SLOPE * e - mm) * GATMH_LOG2E);
+        });
         if constexpr (AUX_BATCH) {
             rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ghost_launch ? elg : el), 0, (ghost_launch ? B.nghost : a.N) * ldk * 4u, 0x00020000);
             aux_b = k * 4u - (ghost_launch ? a.N : 0u) * ldk * 4u;
-            qpos = (uint32_t)li & (HL >= 4 ? 3u : 1u);
+            qpos = GatRecBatch<HL>::qpos(li);
         }
         const uint32_t f0 = col * (WIDE ? 8 : 4), KD = K * D;  // a_l is a dense K x D vector (41-feature heads end mid-float4)
         al4 = make_float4(f0 < KD ? a_l[f0] * GATMH_LOG2E : 0.f, f0 + 1 < KD ? a_l[f0 + 1] * GATMH_LOG2E : 0.f,
@@ -239,88 +318,40 @@ struct GatFwdSweepOp {
     // The sweep is bound by the vector ALU as much as by the addresser (16 vector instructions per gather instruction in the
     // first cut: 3.78 ms per 128-float launch whatever the rows per group or the gates; 13 with the packed forms: 3.39 ms):
     // everything here is written for the packed fp32 instructions (v_pk_mul / v_pk_fma: two lanes' worth per issue slot).
-    template <bool FULL>
-    __device__ __forceinline__ void entry(Row &r, const RowC &c, const float4 &x, Aux ax, bool on) const {
+    // el'[src] of this lane's head, formed from the gathered row
+    __device__ __forceinline__ float score(const float4 &x) const {
+        const f2 xlo = {x.x, x.y}, xhi = {x.z, x.w}, alo = {al4.x, al4.y}, ahi = {al4.z, al4.w};
+        const f2 p = __builtin_elementwise_fma(xhi, ahi, xlo * alo);             // v_pk_mul + v_pk_fma
+        return sw_head_sum<HL>(p.x + p.y);
+    }
+    // WIDE: the same of eight features (the comment above the struct: why these are the narrow form's bits)
+    __device__ __forceinline__ float score(const Float4x2 &x) const {
+        static_assert(WIDE, "eight features per entry: the wide form");
+        const f2 xlo = {x.lo.x, x.lo.y}, xhi = {x.lo.z, x.lo.w}, alo = {al4.x, al4.y}, ahi = {al4.z, al4.w};
+        const f2 ylo = {x.hi.x, x.hi.y}, yhi = {x.hi.z, x.hi.w}, blo = {al4h.x, al4h.y}, bhi = {al4h.z, al4h.w};
+        const f2 p = __builtin_elementwise_fma(xhi, ahi, xlo * alo);                 // the narrow lane 2j's
+        const f2 q = __builtin_elementwise_fma(yhi, bhi, ylo * blo);                 // the narrow lane 2j + 1's
+        return sw_head_sum<HL>((p.x + p.y) + (q.x + q.y));                            // (the tree's first step, then the rest)
+    }
+    template <bool FULL, class X>
+    __device__ __forceinline__ void entry(Row &r, const RowC &c, const X &x, Aux ax, bool on) const {
         float e;
         f2 kk;
         if constexpr (AUX_BATCH) {
             e = ax;                                                                   // el[src] as the scores kernel wrote it
             kk = (f2){GATMH_LOG2E, GATMH_SLOPE * GATMH_LOG2E};
         } else {
-            const f2 xlo = {x.x, x.y}, xhi = {x.z, x.w}, alo = {al4.x, al4.y}, ahi = {al4.z, al4.w};
-            const f2 p = __builtin_elementwise_fma(xhi, ahi, xlo * alo);             // v_pk_mul + v_pk_fma
-            e = sw_head_sum<HL>(p.x + p.y);                                           // el'[src] of this lane's head
+            e = score(x);
             kk = (f2){1.f, GATMH_SLOPE};
         }
         const f2 ee = {e, e}, cc = {c.c1, c.c2};
-        const f2 t = __builtin_elementwise_fma(ee, kk, cc);                            // (e + c1, 0.2 e + c2): one v_pk_fma
-        float al = __builtin_amdgcn_exp2f(fmaxf(t.x, t.y));
-        if constexpr (!FULL) al = on ? al : 0.f;               // (an absent slot gathered zeros: its score is not zero)
-        const float alp = t.x > t.y ? al : 0.f;                // positive branch: el + er > 0  <=>  t1 > t2
-        r.den += (f2){al, alp};
-        r.acc = fma4(al, x, r.acc);
-        r.accp = fma4(alp, x, r.accp);
-    }
-    // WIDE: the entry of eight features (the comment above the struct: why these are the narrow form's bits)
-    template <bool FULL>
-    __device__ __forceinline__ void entry(Row &r, const RowC &c, const Float4x2 &x, Aux, bool on) const {
-        static_assert(WIDE, "eight features per entry: the wide form");
-        const f2 xlo = {x.lo.x, x.lo.y}, xhi = {x.lo.z, x.lo.w}, alo = {al4.x, al4.y}, ahi = {al4.z, al4.w};
-        const f2 ylo = {x.hi.x, x.hi.y}, yhi = {x.hi.z, x.hi.w}, blo = {al4h.x, al4h.y}, bhi = {al4h.z, al4h.w};
-        const f2 p = __builtin_elementwise_fma(xhi, ahi, xlo * alo);                 // the narrow lane 2j's
-        const f2 q = __builtin_elementwise_fma(yhi, bhi, ylo * blo);                 // the narrow lane 2j + 1's
-        const float e = sw_head_sum<HL>((p.x + p.y) + (q.x + q.y));                   // (the tree's first step, then the rest)
-        const f2 ee = {e, e}, cc = {c.c1, c.c2}, kk = {1.f, GATMH_SLOPE};
-        const f2 t = __builtin_elementwise_fma(ee, kk, cc);
-        float al = __builtin_amdgcn_exp2f(fmaxf(t.x, t.y));
-        if constexpr (!FULL) al = on ? al : 0.f;
-        const float alp = t.x > t.y ? al : 0.f;
-        r.den += (f2){al, alp};
-        r.acc = fma4(al, x.lo, r.acc);
-        r.accp = fma4(alp, x.lo, r.accp);
-        r.acc2 = fma4(al, x.hi, r.acc2);
-        r.accp2 = fma4(alp, x.hi, r.accp2);
+        const f2 al = gatmh_entry_alpha<FULL>(__builtin_elementwise_fma(ee, kk, cc), on);   // (e + c1, 0.2 e + c2): one v_pk_fma
+        r.pair += al;
+        gatmh_row_fma(r, al, x);
     }
     __device__ __forceinline__ void store(const Row &r, const SpmmArgs &a, const SweepArgs &w, uint32_t v, bool piece, uint32_t slot,
                                           uint32_t col, uint32_t nchunk, const float4 *) const {
-        if constexpr (WIDE) {   // col, nchunk count eight features: two float4 per tensor, at the addresses the narrow form's two lanes write
-            const size_t at = ((size_t)(piece ? slot : v) * nchunk + col) * 2;
-            float4 *q = reinterpret_cast<float4 *>(piece ? w.split_partial : a.out) + at;
-            float4 *qp = reinterpret_cast<float4 *>(piece ? pos_slots : accp) + at;
-            float2 *dq = reinterpret_cast<float2 *>(piece ? den_slots + (size_t)slot * 2 * ldk : dacc + (size_t)v * 2 * ldk) + k;
-            float4 o0 = r.acc, o1 = r.acc2, p0 = r.accp, p1 = r.accp2;
-            float2 dn = make_float2(r.den.x, r.den.y);
-            const bool head_lane = (threadIdx.x % HL) == 0 && col * 8 < K * D;
-            if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {
-                const float4 a0 = q[0], a1 = q[1], b0 = qp[0], b1 = qp[1];
-                o0.x += a0.x; o0.y += a0.y; o0.z += a0.z; o0.w += a0.w;
-                o1.x += a1.x; o1.y += a1.y; o1.z += a1.z; o1.w += a1.w;
-                p0.x += b0.x; p0.y += b0.y; p0.z += b0.z; p0.w += b0.w;
-                p1.x += b1.x; p1.y += b1.y; p1.z += b1.z; p1.w += b1.w;
-                if (head_lane) { const float2 d0 = *dq; dn.x += d0.x; dn.y += d0.y; }
-            }
-            q[0] = o0; q[1] = o1;
-            qp[0] = p0; qp[1] = p1;
-            if (head_lane) *dq = dn;
-            return;
-        }
-        float4 *q = piece ? reinterpret_cast<float4 *>(w.split_partial) + (size_t)slot * nchunk + col
-                          : reinterpret_cast<float4 *>(a.out) + (size_t)v * nchunk + col;
-        float4 *qp = piece ? reinterpret_cast<float4 *>(pos_slots) + (size_t)slot * nchunk + col
-                           : reinterpret_cast<float4 *>(accp) + (size_t)v * nchunk + col;
-        float2 *dq = reinterpret_cast<float2 *>(piece ? den_slots + (size_t)slot * 2 * ldk : dacc + (size_t)v * 2 * ldk) + k;
-        float4 o4 = r.acc, p4 = r.accp;
-        float2 dn = make_float2(r.den.x, r.den.y);
-        const bool head_lane = (threadIdx.x % HL) == 0 && col * 4 < K * D;
-        if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {   // second launch of a partitioned run (ghost blocks)
-            const float4 p = *q, pp = *qp;
-            o4.x += p.x; o4.y += p.y; o4.z += p.z; o4.w += p.w;
-            p4.x += pp.x; p4.y += pp.y; p4.z += pp.z; p4.w += pp.w;
-            if (head_lane) { const float2 d0 = *dq; dn.x += d0.x; dn.y += d0.y; }
-        }
-        *q = o4;
-        *qp = p4;
-        if (head_lane) *dq = dn;
+        gatmh_store_row<HL>(r, a, w, v, piece, slot, col, nchunk, accp, pos_slots, dacc, den_slots, k, ldk, K * D);
     }
 };
 
@@ -525,10 +556,8 @@ struct GatSrcSweepOp {
     // profiles/r05_gatmh_src_aux_batch_experiment.patch)
     static constexpr bool PLAIN = false, UNIT_W = true, PROLOGUE = true, AUX_BATCH = GATMH_SRC_AUX_MODE == 3;
     static constexpr int BATCH = WIDE ? GATMH_SRC_WIDE_BATCH : GROUP == 16 ? GATMH_SRC16_BATCH : GATMH_SRC_BATCH;   // two gathers per entry (rows, statistics); 16-lane groups: four lane groups per gather instruction
-    static constexpr int EPL = HL >= 4 ? 4 : 2;    // AUX_BATCH: entries one statistics gather serves (the lanes of a quad that share a head)
     static constexpr int SLACK = GATMH_SLACK;
     static constexpr int HPS = GROUP / HL;
-    static constexpr int RW = (SWEEP_NT / GROUP) * R;
     // arguments
     const float *el;                // [N][ldk] of the sources (= the rows)
     const float4 *stx, *stxg;       // [N][K], [Gdst][K]
@@ -540,134 +569,43 @@ struct GatSrcSweepOp {
     uint32_t k, hl, aux_b, qpos;
     __amdgpu_buffer_rsrc_t rs2;
     const float2 *etab;
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    struct Row4 { float4 s, sp; f2 tt; };
-    struct Row8 { float4 s, sp, s2, sp2; f2 tt; };   // WIDE: features 0-3 and 4-7 of the lane's chunk
-    typedef typename std::conditional<WIDE, Row8, Row4>::type Row;
+    typedef gm_f2 f2;
+    typedef GatRow<WIDE ? 2 : 1> Row;   // m = S, p = S+, pair = (T, T+)
     struct RowC { f2 e; };          // (el'_u, 0.2 el'_u)
     typedef float3 Aux;             // (c1', c2', t): a 12-byte load (a register less per gather in flight than the 16 bytes)
-    __device__ __forceinline__ void init(Row &r) const {
-        r.s = make_float4(0.f, 0.f, 0.f, 0.f); r.sp = r.s; r.tt = (f2){0.f, 0.f};
-        if constexpr (WIDE) { r.s2 = r.s; r.sp2 = r.s; }
-    }
+    __device__ __forceinline__ void init(Row &r) const { r = Row{}; }
     __device__ __forceinline__ void prologue(const SpmmArgs &a, const BlockedAdj &B, uint32_t pos0, uint32_t xend, bool ghost_launch, uint32_t col, int li) {
-        __shared__ float2 tab[RW * HPS];
-        const uint32_t head0 = (col / GROUP) * HPS;
-        for (uint32_t i = threadIdx.x; i < (uint32_t)(RW * HPS); i += SWEEP_NT) {
-            const uint32_t lrow = i / HPS, kk = head0 + i % HPS, pos = pos0 + lrow;
-            const uint32_t u = pos < xend ? (B.perm ? B.perm[pos] : pos) : 0xFFFFFFFFu;
-            float2 c = make_float2(0.f, 0.f);
-            if (u != 0xFFFFFFFFu && kk < K) {
-                const float e = el[(size_t)u * ldk + kk] * GATMH_LOG2E;
-                c = make_float2(e, GATMH_SLOPE * e);
-            }
-            tab[i] = c;
-        }
-        etab = tab;
-        hl = (uint32_t)li / HL;
-        k = min(head0 + hl, K - 1);
+        etab = gatmh_row_head_table<GROUP, HL, R>(B, pos0, xend, col, li, K, hl, k, [&](uint32_t u, uint32_t kk) {
+            const float e = el[(size_t)u * ldk + kk] * GATMH_LOG2E;
+            return make_float2(e, GATMH_SLOPE * e);
+        });
         // the destinations' packed statistics through a buffer resource of their own: 16 bytes per (v, k)
         const uint32_t rowb = K * 16u;
         rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(ghost_launch ? stxg : stx), 0, (ghost_launch ? G : N) * rowb, 0x00020000);
         aux_b = k * 16u - (ghost_launch ? N : 0u) * rowb;
-        qpos = (uint32_t)li & (HL >= 4 ? 3u : 1u);
+        qpos = GatRecBatch<HL>::qpos(li);
     }
     __device__ __forceinline__ RowC row_const(uint32_t lrow) const {
         const float2 c = etab[lrow * HPS + hl];
         return RowC{(f2){c.x, c.y}};
     }
     __device__ __forceinline__ Aux aux(uint32_t sidx, uint32_t, bool on) const {
-        typedef uint32_t u3 __attribute__((ext_vector_type(3)));
-        const u3 v = __builtin_amdgcn_raw_buffer_load_b96(rs2, on ? __umul24(sidx, K * 16u) + aux_b : 0xFFFFFFFFu, 0, 0);
-        return make_float3(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z));
-    }
-    // AUX_BATCH: the records of the batch's entries [0, n) -- lane (quad position j) fetches entry i * EPL + j with load i
-    template <int U0, int NB, int NL>
-    __device__ __forceinline__ void aux_spread(const float3 (&rec)[NL], Aux (&ax)[NB]) const {
-        if constexpr (U0 < NB) {
-            constexpr int pp = U0 % EPL;
-            constexpr int QP = HL >= 4 ? pp * 0x55 : (pp | (pp << 2) | ((2 + pp) << 4) | ((2 + pp) << 6));
-            const float3 &v = rec[U0 / EPL];
-            ax[U0] = make_float3(sw_dpp<QP>(v.x), sw_dpp<QP>(v.y), sw_dpp<QP>(v.z));
-            aux_spread<U0 + 1, NB, NL>(rec, ax);
-        }
+        Aux sv;
+        gatmh_rec_load(sv, rs2, on ? __umul24(sidx, K * 16u) + aux_b : 0xFFFFFFFFu);
+        return sv;
     }
     template <int NB> __device__ __forceinline__ void aux_batch(const uint2 *stp, uint32_t n, Aux (&ax)[NB]) const {
-        typedef uint32_t u3 __attribute__((ext_vector_type(3)));
-        constexpr int NL = (NB + EPL - 1) / EPL;
-        float3 rec[NL];
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const uint32_t j = (uint32_t)i * EPL + qpos;
-            const uint32_t sidx = stp[j < (uint32_t)NB ? j : (uint32_t)NB - 1].x;       // (one LDS read per lane: four addresses per head)
-            const u3 v = __builtin_amdgcn_raw_buffer_load_b96(rs2, j < n ? __umul24(sidx, K * 16u) + aux_b : 0xFFFFFFFFu, 0, 0);
-            rec[i] = make_float3(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z));
-        }
-        aux_spread<0, NB, NL>(rec, ax);
+        GatRecBatch<HL>::template fetch<NB>(rs2, K * 16u, aux_b, qpos, stp, n, ax);
     }
-    template <bool FULL>
-    __device__ __forceinline__ void entry(Row &r, const RowC &c, const float4 &x, const Aux &sv, bool on) const {
-        const f2 t = c.e + (f2){sv.x, sv.y};                     // (el' + c1', 0.2 el' + c2')
-        float al = __builtin_amdgcn_exp2f(fmaxf(t.x, t.y));
-        if constexpr (!FULL) al = on ? al : 0.f;                 // (an absent slot read zeros: exp2(el') is not zero)
-        const float alp = t.x > t.y ? al : 0.f;
-        r.tt = __builtin_elementwise_fma((f2){al, alp}, (f2){sv.z, sv.z}, r.tt);
-        r.s = fma4(al, x, r.s);
-        r.sp = fma4(alp, x, r.sp);
-    }
-    template <bool FULL>
-    __device__ __forceinline__ void entry(Row &r, const RowC &c, const Float4x2 &x, const Aux &sv, bool on) const {
-        static_assert(WIDE, "eight features per entry: the wide form");
-        const f2 t = c.e + (f2){sv.x, sv.y};
-        float al = __builtin_amdgcn_exp2f(fmaxf(t.x, t.y));
-        if constexpr (!FULL) al = on ? al : 0.f;
-        const float alp = t.x > t.y ? al : 0.f;
-        r.tt = __builtin_elementwise_fma((f2){al, alp}, (f2){sv.z, sv.z}, r.tt);
-        r.s = fma4(al, x.lo, r.s);
-        r.sp = fma4(alp, x.lo, r.sp);
-        r.s2 = fma4(al, x.hi, r.s2);
-        r.sp2 = fma4(alp, x.hi, r.sp2);
+    template <bool FULL, class X>   // X: float4, or (WIDE) the Float4x2 of eight features
+    __device__ __forceinline__ void entry(Row &r, const RowC &c, const X &x, const Aux &sv, bool on) const {
+        const f2 al = gatmh_entry_alpha<FULL>(c.e + (f2){sv.x, sv.y}, on);   // (el' + c1', 0.2 el' + c2'); an absent slot read zeros: exp2(el') is not zero
+        r.pair = __builtin_elementwise_fma(al, (f2){sv.z, sv.z}, r.pair);
+        gatmh_row_fma(r, al, x);
     }
     __device__ __forceinline__ void store(const Row &r, const SpmmArgs &a, const SweepArgs &w, uint32_t u, bool piece, uint32_t slot,
                                           uint32_t col, uint32_t nchunk, const float4 *) const {
-        if constexpr (WIDE) {   // col, nchunk count eight features: two float4 per tensor, at the addresses the narrow form's two lanes write
-            const size_t at = ((size_t)(piece ? slot : u) * nchunk + col) * 2;
-            float4 *q = reinterpret_cast<float4 *>(piece ? w.split_partial : a.out) + at;
-            float4 *qp = reinterpret_cast<float4 *>(piece ? pos_slots : sp) + at;
-            float2 *tq = reinterpret_cast<float2 *>(piece ? t_slots + (size_t)slot * 2 * ldk : tacc + (size_t)u * 2 * ldk) + k;
-            float4 s0 = r.s, s1 = r.s2, p0 = r.sp, p1 = r.sp2;
-            float2 t2 = make_float2(r.tt.x, r.tt.y);
-            const bool head_lane = (threadIdx.x % HL) == 0 && col * 8 < K * D;
-            if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {
-                const float4 a0 = q[0], a1 = q[1], b0 = qp[0], b1 = qp[1];
-                s0.x += a0.x; s0.y += a0.y; s0.z += a0.z; s0.w += a0.w;
-                s1.x += a1.x; s1.y += a1.y; s1.z += a1.z; s1.w += a1.w;
-                p0.x += b0.x; p0.y += b0.y; p0.z += b0.z; p0.w += b0.w;
-                p1.x += b1.x; p1.y += b1.y; p1.z += b1.z; p1.w += b1.w;
-                if (head_lane) { const float2 d0 = *tq; t2.x += d0.x; t2.y += d0.y; }
-            }
-            q[0] = s0; q[1] = s1;
-            qp[0] = p0; qp[1] = p1;
-            if (head_lane) *tq = t2;
-            return;
-        }
-        float4 *q = piece ? reinterpret_cast<float4 *>(w.split_partial) + (size_t)slot * nchunk + col
-                          : reinterpret_cast<float4 *>(a.out) + (size_t)u * nchunk + col;
-        float4 *qp = piece ? reinterpret_cast<float4 *>(pos_slots) + (size_t)slot * nchunk + col
-                           : reinterpret_cast<float4 *>(sp) + (size_t)u * nchunk + col;
-        float2 *tq = reinterpret_cast<float2 *>(piece ? t_slots + (size_t)slot * 2 * ldk : tacc + (size_t)u * 2 * ldk) + k;
-        float4 s4 = r.s, p4 = r.sp;
-        float2 t2 = make_float2(r.tt.x, r.tt.y);
-        const bool head_lane = (threadIdx.x % HL) == 0 && col * 4 < K * D;
-        if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {
-            const float4 p = *q, pp = *qp;
-            s4.x += p.x; s4.y += p.y; s4.z += p.z; s4.w += p.w;
-            p4.x += pp.x; p4.y += pp.y; p4.z += pp.z; p4.w += pp.w;
-            if (head_lane) { const float2 d0 = *tq; t2.x += d0.x; t2.y += d0.y; }
-        }
-        *q = s4;
-        *qp = p4;
-        if (head_lane) *tq = t2;
+        gatmh_store_row<HL>(r, a, w, u, piece, slot, col, nchunk, sp, pos_slots, tacc, t_slots, k, ldk, K * D);
     }
 };
 
@@ -755,7 +693,7 @@ __global__ __launch_bounds__(256) void gatmh_src_finish_bf16_kernel(GatMhArgs a,
 // ---- launchers ------------------------------------------------------------------------------------------------------
 // lanes per head on a slab of `group` lanes; 0 = a shape the sweep kernels do not cover (the blocked kernels take it)
 int gatmh_sweep_hl(uint32_t K, uint32_t D, uint32_t ld) {
-    const int group = ld >= 128 ? 32 : 16;
+    const int group = gatmh_sweep_group(ld);
     if (!gatmh_shape_ok(K, D) || (ld & 3)) return 0;
     if (K == 1) return (ld <= 64 && group == 16) ? 16 : 0;        // a single head: the whole (one-slab, 16-lane) row
     if ((D & 3) || (D & (D - 1))) return 0;
@@ -832,76 +770,79 @@ hipError_t launch_gatmh_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t
     return hipGetLastError();
 }
 
-// geometry of one launch over the source blocks [b_lo, b_hi) of a sweep layout (as launch_spmm_sweep)
-static bool gatmh_sweep_geom(const SpmmArgs &a, const BlockedAdj &S, int group, int R, uint32_t cus, uint32_t b_lo, uint32_t b_hi,
-                             bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags, float *pieces, SweepArgs *w, dim3 *grid,
-                             bool wide = false /* chunks of eight features: the same 128-feature slabs on 16-lane groups */) {
-    if (!sweep_supported(a, S, group) || b_hi > S.nb || cus == 0 || cus > 32 || !ctl.stat) return false;
-    if (b_lo < S.nb_local && b_hi > S.nb_local) return false;
-    if (b_lo >= S.nb_local && !a.xg) return false;
-    if (R != 8 && R != 6 && R != 4 && R != 2) return false;
+// What a launch of either edge pass is made of, decided once: the lane group, the lanes per head and the rows per group of its kernel,
+// the skeleton's arguments and geometry over the source blocks [p.b_lo, p.b_hi) of the sweep layout S (as launch_spmm_sweep), the
+// gate counters cleared.  pass: 0 forward, 1 source side; xl / xg / out: the rows gathered (local, ghost) and the main sums
+struct GatSweepPlan {
+    int group, HL, R;
+    SpmmArgs a;
+    SweepArgs w;
+    dim3 grid;
+};
+static hipError_t gatmh_sweep_plan(const GatSweepPart &p, int pass, uint32_t N, uint32_t K, uint32_t D, uint32_t ld, const BlockedAdj &S,
+                                   const float *xl, const float *xg, float *out, float *pieces, GatSweepPlan *pl) {
+    if (p.wide && !(p.bf16 && gatmh_wide_applies(K, D, ld))) return hipErrorInvalidValue;
+    const int group = pl->group = p.wide ? GATMH_WIDE_GROUP : gatmh_sweep_group(ld);
+    pl->HL = p.wide ? (int)(D / 8) : gatmh_sweep_hl(K, D, ld);
+    const int R = pl->R = p.wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(S, group, pl->HL, pass);
+    SpmmArgs &a = pl->a = SpmmArgs{};
+    a.N = N; a.F = K * D; a.ld = ld; a.xl = xl; a.xg = xg; a.out = out; a.accumulate = p.accumulate ? 1 : 0; a.self_mode = 0;
+    if (!pl->HL || (R != 2 && R != 4)) return hipErrorInvalidValue;   // (the rows per group that have kernels)
+    if (!sweep_supported(a, S, group) || p.b_hi > S.nb || p.cus == 0 || p.cus > 32 || !p.ctl.stat) return hipErrorInvalidValue;
+    if (p.b_lo < S.nb_local && p.b_hi > S.nb_local) return hipErrorInvalidValue;
+    if (p.b_lo >= S.nb_local && !a.xg) return hipErrorInvalidValue;
     const uint32_t RW = (uint32_t)(SWEEP_NT / group) * R;
-    *w = SweepArgs{};
-    w->rpx = ((S.npos + 7) / 8 + R - 1) / R * R;
-    w->tiles_x = (w->rpx + RW - 1) / RW;
-    w->G = cus;
-    const uint32_t spp = (w->tiles_x + cus - 1) / cus;
-    const uint32_t slabs = ((a.ld >> (wide ? 3 : 2)) + group - 1) / group;
-    w->nsweeps = slabs * spp;
-    w->b_lo = b_lo; w->b_hi = b_hi;
-    w->done = done;
-    w->flags = flags | (accumulate ? 2u : 0u);
-    w->split_partial = pieces;
-    w->stat = ctl.stat;
-    *grid = dim3(8u * slabs * spp * cus);
-    return true;
+    SweepArgs &w = pl->w = SweepArgs{};
+    w.rpx = ((S.npos + 7) / 8 + R - 1) / R * R;
+    w.tiles_x = (w.rpx + RW - 1) / RW;
+    w.G = p.cus;
+    const uint32_t spp = (w.tiles_x + p.cus - 1) / p.cus;
+    const uint32_t slabs = ((ld >> (p.wide ? 3 : 2)) + group - 1) / group;   // wide: chunks of eight features -- the same 128-feature slabs on 16-lane groups
+    w.nsweeps = slabs * spp;
+    w.b_lo = p.b_lo; w.b_hi = p.b_hi;
+    w.done = p.done;
+    w.flags = p.flags | (p.accumulate ? 2u : 0u);
+    w.split_partial = pieces;
+    w.stat = p.ctl.stat;
+    pl->grid = dim3(8u * slabs * spp * p.cus);
+    return hipMemsetAsync(p.done, 0, ((size_t)8 * w.nsweeps * (p.b_hi - p.b_lo) * 32 + 1) * sizeof(uint32_t), p.s);
 }
 
-// one launch over the source blocks [b_lo, b_hi) of the sweep layout S (a partition with ghost rows: local-source blocks
+// The kernels that are instantiated, all with the loader wave.  gatmh_pick: f(V as a compile-time constant) for the one of V... that v
+// equals; false: none does.  Narrow forms: GROUP 16 / 32 x HL 2 / 4 / 8 / 16 x R 2 / 4, f(G, H, R).  Wide forms: HL 2 / 4 / 8 (two rows per
+// 16-lane group: gatmh_sweep_plan gives a wide launch no other)
+template <int... V, class F>
+static bool gatmh_pick(int v, F f) {
+    return ((v == V && f(std::integral_constant<int, V>{})) || ...);
+}
+template <class F>
+static bool gatmh_narrow_form(const GatSweepPlan &pl, F f) {
+    return gatmh_pick<16, 32>(pl.group, [&](auto G) {
+        return gatmh_pick<2, 4, 8, 16>(pl.HL, [&](auto H) { return gatmh_pick<2, 4>(pl.R, [&](auto R) { return f(G, H, R); }); });
+    });
+}
+
+// one launch over the source blocks [p.b_lo, p.b_hi) of the sweep layout S (a partition with ghost rows: local-source blocks
 // first, then the ghost blocks with accumulate = true)
 hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
-                                           float *scratch, uint32_t cus, uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done,
-                                           const SweepCtl &ctl, uint32_t flags, hipStream_t s, const float *el, const float *elg, bool bf16,
-                                           bool wide) {
-    if (N == 0 || b_lo >= b_hi) return hipSuccess;
-    if (wide && !(bf16 && gatmh_wide_applies(K, D, ld))) return hipErrorInvalidValue;
-    const int group = wide ? GATMH_WIDE_GROUP : ld >= 128 ? 32 : 16;
-    const int HL = wide ? (int)(D / 8) : gatmh_sweep_hl(K, D, ld);
-    SpmmArgs a{};
-    a.N = N; a.F = K * D; a.ld = ld; a.xl = z; a.xg = zg; a.out = o; a.accumulate = accumulate ? 1 : 0; a.self_mode = 0;
-    const int R = wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(S, group, HL, 0);
+                                           float *scratch, const GatSweepPart &p, const float *el, const float *elg) {
+    if (N == 0 || p.b_lo >= p.b_hi) return hipSuccess;
     const GatSweepScratch c = gatmh_carve(scratch, S, N, ld, ldk);
-    SweepArgs w;
-    dim3 gr;
-    if (!HL || !gatmh_sweep_geom(a, S, group, R, cus, b_lo, b_hi, accumulate, done, ctl, flags, c.pieces, &w, &gr, wide)) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(done, 0, ((size_t)8 * w.nsweeps * (b_hi - b_lo) * 32 + 1) * sizeof(uint32_t), s);
+    GatSweepPlan pl;
+    const hipError_t e = gatmh_sweep_plan(p, 0, N, K, D, ld, S, z, zg, o, c.pieces, &pl);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
-    if (wide) {   // one form: two rows per 16-lane group, loader wave
-#define GFW(HLV) hipLaunchKernelGGL((gatmh_forward_sweep_bf16x8_kernel<HLV, GATMH_WIDE_ROWS, true>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk)
-        if (HL == 2) GFW(2); else if (HL == 4) GFW(4); else GFW(8);
-#undef GFW
-        return hipGetLastError();
-    }
-#define GFS(GRP, HLV, RR, LD)                                                                                                                    \
-    do {                                                                                                                                         \
-        if (bf16) hipLaunchKernelGGL((gatmh_forward_sweep_bf16_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk, el, elg); \
-        else hipLaunchKernelGGL((gatmh_forward_sweep_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk, el, elg);          \
-    } while (0)
-#define GFS_R(HLV) do { if (R == 4) GFS(32, HLV, 4, true); else GFS(32, HLV, 2, true); } while (0)
-#define GFS_R16(HLV) do { if (R == 4) GFS(16, HLV, 4, true); else GFS(16, HLV, 2, true); } while (0)
-    if (group == 32) {
-        if (R > 4) return hipErrorInvalidValue;
-        if (HL == 2) GFS_R(2); else if (HL == 4) GFS_R(4); else if (HL == 8) GFS_R(8); else GFS_R(16);
-    } else {
-        if (R > 4) return hipErrorInvalidValue;
-        if (HL == 2) GFS_R16(2); else if (HL == 4) GFS_R16(4); else if (HL == 8) GFS_R16(8); else GFS_R16(16);
-    }
-#undef GFS_R16
-#undef GFS_R
-#undef GFS
-    return hipGetLastError();
+    const bool found = p.wide ? gatmh_pick<2, 4, 8>(pl.HL, [&](auto H) {
+        hipLaunchKernelGGL((gatmh_forward_sweep_bf16x8_kernel<H(), GATMH_WIDE_ROWS, true>), pl.grid, bl, 0, p.s, pl.a, S, pl.w, er, a_l, c.keys, op, c.dacc,
+                           c.pos_slots, c.den_slots, K, D, ldk);
+        return true;
+    }) : gatmh_narrow_form(pl, [&](auto G, auto H, auto R) {
+        hipLaunchKernelGGL((p.bf16 ? gatmh_forward_sweep_bf16_kernel<G(), H(), R(), true> : gatmh_forward_sweep_kernel<G(), H(), R(), true>), pl.grid, bl, 0,
+                           p.s, pl.a, S, pl.w, er, a_l, c.keys, op, c.dacc, c.pos_slots, c.den_slots, K, D, ldk, el, elg);
+        return true;
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // pieces of split rows, the self edge, the normalisation, m / den / dpos; then the rows whose denominator underflowed
@@ -969,51 +910,27 @@ hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint
     return hipGetLastError();
 }
 
-// one launch over the destination blocks [b_lo, b_hi) of the sweep layout of the OUT-edges
+// one launch over the destination blocks [p.b_lo, p.b_hi) of the sweep layout of the OUT-edges
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
-                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, uint32_t cus,
-                                       uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t *done, const SweepCtl &ctl, uint32_t flags,
-                                       hipStream_t s, bool bf16, bool wide) {
-    if (N == 0 || b_lo >= b_hi) return hipSuccess;
-    if (wide && !(bf16 && gatmh_wide_applies(K, D, ld))) return hipErrorInvalidValue;
-    const int group = wide ? GATMH_WIDE_GROUP : ld >= 128 ? 32 : 16;
-    const int HL = wide ? (int)(D / 8) : gatmh_sweep_hl(K, D, ld);
-    SpmmArgs a{};
-    a.N = N; a.F = K * D; a.ld = ld; a.xl = d_o; a.xg = dog; a.out = dz; a.accumulate = accumulate ? 1 : 0; a.self_mode = 0;
-    const int R = wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(S, group, HL, 1);
+                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, const GatSweepPart &p) {
+    if (N == 0 || p.b_lo >= p.b_hi) return hipSuccess;
+    // the statistics records through their buffer resource: 32-bit byte offsets, record id x row bytes in 24 x 24 bits
+    if ((uint64_t)(N > G ? N : G) * K * 16u >= (1ull << 32) || K * 16u >= (1u << 24)) return hipErrorInvalidValue;
     const GatSrcScratch c = gatmh_src_carve(scratch, S, N, K, ld, ldk);
-    SweepArgs w;
-    dim3 gr;
-    if (!HL || (uint64_t)(N > G ? N : G) * K * 16u >= (1ull << 32) || K * 16u >= (1u << 24) ||
-        !gatmh_sweep_geom(a, S, group, R, cus, b_lo, b_hi, accumulate, done, ctl, flags, c.pieces, &w, &gr, wide))
-        return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(done, 0, ((size_t)8 * w.nsweeps * (b_hi - b_lo) * 32 + 1) * sizeof(uint32_t), s);
+    GatSweepPlan pl;
+    const hipError_t e = gatmh_sweep_plan(p, 1, N, K, D, ld, S, d_o, dog, dz, c.pieces, &pl);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
-    if (wide) {   // one form: two rows per 16-lane group, loader wave
-#define GSW(HLV) hipLaunchKernelGGL((gatmh_src_sweep_bf16x8_kernel<HLV, GATMH_WIDE_ROWS, true>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G)
-        if (HL == 2) GSW(2); else if (HL == 4) GSW(4); else GSW(8);
-#undef GSW
-        return hipGetLastError();
-    }
-#define GSS(GRP, HLV, RR, LD)                                                                                                                    \
-    do {                                                                                                                                         \
-        if (bf16) hipLaunchKernelGGL((gatmh_src_sweep_bf16_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G); \
-        else hipLaunchKernelGGL((gatmh_src_sweep_kernel<GRP, HLV, RR, LD>), gr, bl, 0, s, a, S, w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G);          \
-    } while (0)
-    if (group == 32) {
-        if (R != 2 && R != 4) return hipErrorInvalidValue;
-#define GSS_R(HLV) do { if (R == 4) GSS(32, HLV, 4, true); else GSS(32, HLV, 2, true); } while (0)
-        if (HL == 2) GSS_R(2); else if (HL == 4) GSS_R(4); else if (HL == 8) GSS_R(8); else GSS_R(16);
-#undef GSS_R
-    } else {
-        if (R != 2 && R != 4 && R != 6) return hipErrorInvalidValue;
-#define GSS_R16(HLV) do { if (R == 4) GSS(16, HLV, 4, GATMH_SRC16_LOADER); else GSS(16, HLV, 2, GATMH_SRC16_LOADER); } while (0)
-        if (HL == 2) GSS_R16(2); else if (HL == 4) GSS_R16(4); else if (HL == 8) GSS_R16(8); else GSS_R16(16);
-#undef GSS_R16
-    }
-#undef GSS
-    return hipGetLastError();
+    const bool found = p.wide ? gatmh_pick<2, 4, 8>(pl.HL, [&](auto H) {
+        hipLaunchKernelGGL((gatmh_src_sweep_bf16x8_kernel<H(), GATMH_WIDE_ROWS, true>), pl.grid, bl, 0, p.s, pl.a, S, pl.w, el, c.stx, c.stxg, c.sp, c.tacc,
+                           c.pos_slots, c.t_slots, K, D, ldk, G);
+        return true;
+    }) : gatmh_narrow_form(pl, [&](auto GR, auto H, auto R) {
+        hipLaunchKernelGGL((p.bf16 ? gatmh_src_sweep_bf16_kernel<GR(), H(), R(), true> : gatmh_src_sweep_kernel<GR(), H(), R(), true>), pl.grid, bl, 0,
+                           p.s, pl.a, S, pl.w, el, c.stx, c.stxg, c.sp, c.tacc, c.pos_slots, c.t_slots, K, D, ldk, G);
+        return true;
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // pieces of split rows, the self edge, del, dz

@@ -8,17 +8,8 @@ pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 
 
-@pytest.mark.parametrize("dims,heads,V,E", [
-    ([24, 32, 8], [4, 2], 200, 1500),        # 4 heads x 8, two output heads (of 8 classes) averaged
-    ([40, 128, 41], [8, 1], 300, 4000),      # the Reddit layer shape: 8 heads x 16 -> 41 classes
-    ([16, 64, 7], [1, 1], 150, 900),         # single head: reductions span the whole row
-    ([20, 128, 5], [4, 1], 180, 1300),       # 4 heads x 32
-    ([12, 100, 6], [1, 1], 160, 1100),       # one head of 100 features: split over 4 lanes, last piece ragged
-    ([24, 256, 6], [4, 1], 170, 1200),       # 4 heads x 64: two 128-float slabs per row
-    ([24, 256, 9], [32, 1], 140, 1000),      # 32 heads x 8
-])
-@pytest.mark.parametrize("nb,sweep", [(0, 1), (8, 1), (8, 0)])    # 8: force the L2-window kernels on these L2-sized graphs: the
-def test_gat_mh_epoch_vs_oracle(dims, heads, V, E, nb, sweep):       # sweep forms where the shape allows, or (sweep = 0) the blocked ones
+def _epoch_vs_oracle(dims, heads, V, E, options):
+    """one epoch of a two-layer model on a random graph with a hub source, every tensor against the oracle"""
     import dorylus_amd as da
     import gat_mh_oracle as go
     import partition_oracle as po
@@ -38,8 +29,8 @@ def test_gat_mh_epoch_vs_oracle(dims, heads, V, E, nb, sweep):       # sweep for
     ctx = da.Context(0)
     ctx.configure(da.GATMH, dims, V)
     ctx.gatmh_heads(heads)
-    ctx.set_option("spmm_blk_nb", nb)
-    ctx.set_option("gatmh_sweep", sweep)
+    for name, value in options.items():
+        ctx.set_option(name, value)
     ctx.graph_upload(g)
     ctx.preallocate()
     ctx.upload(0, "h", X)
@@ -78,6 +69,32 @@ def test_gat_mh_epoch_vs_oracle(dims, heads, V, E, nb, sweep):       # sweep for
             assert not np.array_equal(ctx.weight_get(l, nm).reshape(p.shape), p)
     eng.close()
     ctx.close()
+
+
+@pytest.mark.parametrize("dims,heads,V,E", [
+    ([24, 32, 8], [4, 2], 200, 1500),        # 4 heads x 8, two output heads (of 8 classes) averaged
+    ([40, 128, 41], [8, 1], 300, 4000),      # the Reddit layer shape: 8 heads x 16 -> 41 classes
+    ([16, 64, 7], [1, 1], 150, 900),         # single head: reductions span the whole row
+    ([20, 128, 5], [4, 1], 180, 1300),       # 4 heads x 32
+    ([12, 100, 6], [1, 1], 160, 1100),       # one head of 100 features: split over 4 lanes, last piece ragged
+    ([24, 256, 6], [4, 1], 170, 1200),       # 4 heads x 64: two 128-float slabs per row
+    ([24, 256, 9], [32, 1], 140, 1000),      # 32 heads x 8
+])
+@pytest.mark.parametrize("nb,sweep", [(0, 1), (8, 1), (8, 0)])    # 8: force the L2-window kernels on these L2-sized graphs: the
+def test_gat_mh_epoch_vs_oracle(dims, heads, V, E, nb, sweep):       # sweep forms where the shape allows, or (sweep = 0) the blocked ones
+    _epoch_vs_oracle(dims, heads, V, E, {"spmm_blk_nb": nb, "gatmh_sweep": sweep})
+
+
+@pytest.mark.parametrize("dims,heads", [([24, 64, 6], [4, 1]),        # 16-lane groups, 4 lanes per head
+                                        ([40, 128, 41], [8, 1])])     # 32-lane groups, 4 lanes per head
+@pytest.mark.parametrize("rows", [2, 4])
+def test_gat_mh_sweep_epoch_vs_oracle_with_forced_rows_per_group(dims, heads, rows):
+    """option gatmh_sweep_rows: the sweep layouts dealt for two and for four rows per lane group.  On the 128-float layer (32-lane
+    groups) the launchers then pick the two-row kernels <32, 4, 2> and the four-row kernels <32, 4, 4> of both passes, whatever the fill
+    of a graph this small would choose.  The 64-float layers (16-lane groups) launch two-row kernels with either value: gatmh_sweep_rows()
+    gives a 16-lane launch half the layout's rows, at most two, so the four-row kernels <16, HL, 4> are not reached by this test (no
+    option selects them)"""
+    _epoch_vs_oracle(dims, heads, 300, 4000, {"spmm_blk_nb": 8, "gatmh_sweep_rows": rows})
 
 
 def test_gat_mh_rejects_bad_shapes():

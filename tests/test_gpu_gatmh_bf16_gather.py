@@ -246,7 +246,7 @@ SHAPES = [([40, 128, 41], [8, 1], 300, 4000),      # 8 heads x 16 on a 32-lane s
 EL_TABLE_LAYERS = {128: (1,), 32: (0, 1), 256: (1,)}
 
 
-def _pair(da, dims, heads, V, E, nb, mode, **kw):
+def _pair(da, dims, heads, V, E, nb, mode, options=None, **kw):
     if nb == 0:      # the automatic layout: graphs of a few hundred vertices get no sweep layout at all (their rows fit the L2: the
         V = 20000    # fp32 path gathers row-wise there, and the option refuses -- test_refusals); one that does get it
         E = 13 * V
@@ -255,8 +255,9 @@ def _pair(da, dims, heads, V, E, nb, mode, **kw):
     X = rng.uniform(-1, 1, (V, dims[0])).astype(np.float32)
     labels = rng.integers(0, dims[-1], V).astype(np.uint32)
     params = make_params(rng, dims, heads)
-    A = make_gatmh(da, g, dims, heads, V, X, labels, params, {"spmm_blk_nb": nb})
-    B = make_gatmh(da, g, dims, heads, V, X, labels, params, {"spmm_blk_nb": nb})
+    options = dict(options or {}, spmm_blk_nb=nb)
+    A = make_gatmh(da, g, dims, heads, V, X, labels, params, options)
+    B = make_gatmh(da, g, dims, heads, V, X, labels, params, options)
     return Pair(da, A, B, mode, **kw), rng
 
 
@@ -310,6 +311,19 @@ def test_identity_on_bf16_representable_rows(da, dims, heads, V, E, nb):
     """z and do hold bf16-representable values in both contexts: option 2 and option 0 give identical bits -- nothing but the
     rounding differs between the kernels"""
     p, _ = _pair(da, dims, heads, V, E, nb, 2, representable=True)
+    p.forward()
+    p.backward()
+    assert counters(p.A) == (2, p.src_passes) and p.src_passes >= 1 and counters(p.B) == (0, 0)
+    p.close()
+
+
+@pytest.mark.parametrize("dims,heads", [([24, 64, 6], [4, 1]),        # 16-lane groups, 4 lanes per head
+                                        ([40, 128, 41], [8, 1])])     # 32-lane groups, 4 lanes per head
+@pytest.mark.parametrize("rows", [2, 4])
+def test_forced_rows_per_group_equal_fp32_on_rounded_rows(da, dims, heads, rows):
+    """option gatmh_sweep_rows 2 and 4 (tests/test_gpu_gat_mh.py: the two-row and the four-row kernels): both passes on bf16 rows
+    equal the fp32 passes on host-rounded rows bit for bit"""
+    p, _ = _pair(da, dims, heads, 300, 4000, 8, 2, options={"gatmh_sweep_rows": rows})
     p.forward()
     p.backward()
     assert counters(p.A) == (2, p.src_passes) and p.src_passes >= 1 and counters(p.B) == (0, 0)
