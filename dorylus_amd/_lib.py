@@ -105,6 +105,7 @@ def load():
         "dory_partition_get": [vp, vp],
         "dory_partition_upload": [vp, vp, vp],
         "dory_partition_recv_plan": [vp, vp, i32, vp, vp],
+        "dory_partition_wire_order": [vp, vp, i32, vp, vp],
         "dory_read_layer_config": [cp, vp, u32, C.POINTER(u32)],
         "dory_read_features": [cp, vp, u32, u32, cp, vp, vp],
         "dory_read_labels": [cp, vp, u32, vp],
@@ -121,6 +122,8 @@ def load():
         "dory_sweep_deal_weighted": [u32, vp, u32, u32, u32, vp, vp, vp],
     }
     for name, args in sig.items():
+        if name == "dory_partition_wire_order" and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32

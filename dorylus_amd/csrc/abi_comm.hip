@@ -37,6 +37,14 @@ void timed_open(dory_ctx *c, const char *fam, hipStream_t s, hipEvent_t *end_out
 // (featDim floats per row, engine/utils.cpp:623-650).  Every pack and unpack of this file goes through row_wire, pack_rows
 // and unpack_rows.
 inline bool halo_exact(const dory_ctx *c) { return c->halo_exact.load(std::memory_order_acquire) == 1; }
+// Option halo_direct_recv: ghost rows are stored in wire order (received row r at ghost row r), so an exchange whose wire
+// width is the ghost tensor's ld lands in the tensor itself -- no receive buffer, no unpack.  Rows narrower than ld
+// (halo_exact_rows with cols < ld) are strided in the tensor: they keep the receive buffer and the unpack kernels, which then
+// scatter by an identity list (HaloPlan::d_unpack_slots).
+inline bool halo_direct(const dory_ctx *c) { return c->halo_direct.load(std::memory_order_acquire) == 1; }
+inline bool lands_directly(const HaloPlan &p, RowWire wire, uint32_t ghost_ld) { return p.direct && wire.w == ghost_ld; }
+const char *const NO_RECV_BUF = "halo_direct_recv: this exchange needs the receive buffer (rows of %u floats in a tensor of ld %u) and "
+                                "dory_halo_plan allocated none: set halo_exact_rows = 1 before dory_halo_plan";
 
 // The record for the rows `who` packs from `src` (pack == true: its width travels) or unpacks into `ghost` (pack == false);
 // the tensor of the other end may be null (the *_tensor entry points know one only), `buf` is a caller's buffer or null.
@@ -65,14 +73,15 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
     }
     return DORY_OK;
 }
-// the received rows, dense at the wire's width w, into the plan's ghost slots; the exact form writes the whole row: [0, w)
-// from the buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever the padding held before
+// the received rows, dense at the wire's width w, into the plan's ghost slots (option halo_direct_recv: row r into ghost row r);
+// the exact form writes the whole row: [0, w) from the buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever
+// the padding held before
 int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s) {
     if (wire.exact && (wire.w & 3)) {
-        HIPCK(c, launch_scatter_rows_exact(ghost, buf, ld, wire.w, p.d_recv_slots, p.recv_total, s));
+        HIPCK(c, launch_scatter_rows_exact(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
     } else {
-        HIPCK(c, launch_scatter_rows(ghost, buf, ld, wire.w, p.d_recv_slots, p.recv_total, s));
-        if (wire.exact && wire.w < ld) HIPCK(c, launch_zero_rows_pad(ghost, ld, wire.w, p.d_recv_slots, p.recv_total, s));
+        HIPCK(c, launch_scatter_rows(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
+        if (wire.exact && wire.w < ld) HIPCK(c, launch_zero_rows_pad(ghost, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
     }
     return DORY_OK;
 }
@@ -158,6 +167,27 @@ int local_wait_posted(dory_ctx *c, const std::atomic<uint64_t> &ctr, uint64_t wa
     return DORY_OK;
 }
 
+// Option halo_direct_recv, first half: the RECEIVER pulls, so a sender's part is pack and "sent".  What a peer's "consumed" of
+// exchange s - 1 now frees is MY send buffer (it has copied its rows out of it): the same counter and event, waited for in
+// the same place as the push form waits for them -- the first half of exchange s, before anything is enqueued -- by the
+// ranks that sent to that peer in exchange s - 1 (the push form: that send to it in exchange s; the same ranks wherever both
+// directions' plans name the same peers).  No host-side wait is added.
+int local_pull_send(dory_ctx *c, const HaloPlan &p, Tensor *src, RowWire wire, uint64_t s) {
+    LocalGroup &grp = *c->local;
+    for (uint32_t q = 0; q < c->numNodes && s > 1; ++q) {
+        if (q == c->nodeId || q >= c->local_sent_to.size() || !c->local_sent_to[q]) continue;
+        dory_ctx *Q = grp.ctx[q];
+        if (!Q) return fail(c, DORY_ERR_COMM, "local transport: rank %u has been destroyed", q);
+        int rc = local_wait_posted(c, Q->posted_cons, s - 1, q, "the receive of exchange");
+        if (rc) return rc;
+        HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_cons[(s - 1) & 1], 0));
+    }
+    { int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm); if (rc) return rc; }
+    c->local_sent_to.assign(c->numNodes, 0);
+    for (uint32_t q = 0; q < c->numNodes; ++q) c->local_sent_to[q] = q != c->nodeId && p.send_counts[q] != 0;
+    return DORY_OK;
+}
+
 // first half of an exchange: pack, push my rows into every peer's receive buffer, "sent"; the second half
 // (local_exchange_finish, below) at once, or with `deferred` when wait_halo() is next called
 int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wire, bool deferred) {
@@ -172,8 +202,9 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     dory_ctx::LocalPending &lp = c->local_pending;
     timed_open(c, "halo", c->comm, &lp.t_halo_b);
     timed_open(c, deferred ? "halo_deferred" : "halo_waited", c->comm, &lp.t_kind_b);
-    { int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm); if (rc) return rc; }
-    for (uint32_t q = 0; q < c->numNodes; ++q) {
+    if (p.direct) { int rc = local_pull_send(c, p, src, wire, s); if (rc) return rc; }
+    else { int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm); if (rc) return rc; }
+    for (uint32_t q = 0; q < c->numNodes && !p.direct; ++q) {
         if (q == c->nodeId || !p.send_counts[q]) continue;
         dory_ctx *Q = grp.ctx[q];
         if (!Q) return fail(c, DORY_ERR_COMM, "local transport: rank %u has been destroyed", q);
@@ -198,6 +229,7 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     lp.ghost = ghost->d;
     lp.ghost_ld = ghost->ld;
     lp.wire = wire;
+    lp.direct = lands_directly(p, wire, ghost->ld);
     if (deferred) {
         c->halo_pending = true;      // wait_halo(): local_exchange_finish, then the compute stream waits for ev_b
         return DORY_OK;
@@ -208,9 +240,9 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     return DORY_OK;
 }
 
-// ---- the other two arms: the packed rows in c->send_buf travel, the peers' rows arrive in c->recv_buf (comm stream) -----
+// ---- the other two arms: the packed rows in c->send_buf travel, the peers' rows arrive in `recv` (comm stream) ----------
 // host transport: the bytes travel through the caller (c->tx_recv is still being read when this returns)
-int exchange_host(dory_ctx *c, const HaloPlan &p, uint32_t w) {
+int exchange_host(dory_ctx *c, const HaloPlan &p, uint32_t w, float *recv /* c->recv_buf, or the ghost tensor (halo_direct_recv) */) {
     const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
     c->tx_send.resize((size_t)p.send_total * w);
     c->tx_recv.resize((size_t)p.recv_total * w);
@@ -223,11 +255,11 @@ int exchange_host(dory_ctx *c, const HaloPlan &p, uint32_t w) {
     }
     if (c->tx_a2a(c->tx_user, c->tx_send.data(), sc.data(), so.data(), c->tx_recv.data(), rc_.data(), ro.data(), c->numNodes))
         return fail(c, DORY_ERR_COMM, "halo_exchange: host transport alltoallv failed");
-    if (rb) HIPCK(c, hipMemcpyAsync(c->recv_buf, c->tx_recv.data(), rb, hipMemcpyHostToDevice, c->comm));
+    if (rb) HIPCK(c, hipMemcpyAsync(recv, c->tx_recv.data(), rb, hipMemcpyHostToDevice, c->comm));
     return DORY_OK;
 }
 // RCCL: grouped ncclSend / ncclRecv
-int exchange_rccl(dory_ctx *c, const HaloPlan &p, uint32_t w) {
+int exchange_rccl(dory_ctx *c, const HaloPlan &p, uint32_t w, float *recv /* as exchange_host's */) {
     ncclComm_t comm = (ncclComm_t)c->nccl;
     NCCLCK(c, ncclGroupStart());
     for (uint32_t peer = 0; peer < c->numNodes; ++peer) {
@@ -236,7 +268,7 @@ int exchange_rccl(dory_ctx *c, const HaloPlan &p, uint32_t w) {
             NCCLCK(c, ncclSend(c->send_buf + (size_t)p.send_off[peer] * w, (size_t)p.send_counts[peer] * w,
                                ncclFloat, (int)peer, comm, c->comm));
         if (p.recv_counts[peer])
-            NCCLCK(c, ncclRecv(c->recv_buf + (size_t)p.recv_off[peer] * w, (size_t)p.recv_counts[peer] * w,
+            NCCLCK(c, ncclRecv(recv + (size_t)p.recv_off[peer] * w, (size_t)p.recv_counts[peer] * w,
                                ncclFloat, (int)peer, comm, c->comm));
     }
     NCCLCK(c, ncclGroupEnd());
@@ -345,7 +377,24 @@ int local_exchange_finish(dory_ctx *c) {
         HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_sent[s & 1], 0));
     }
     lp.on = false;     // (a peer that has not arrived leaves the second half pending: the caller may try again)
-    { int rc = unpack_rows(c, lp.ghost, lp.ghost_ld, lp.wire, c->recv_buf, p, c->comm); if (rc) return rc; }
+    if (p.direct) {   // option halo_direct_recv: I pull every peer's segment out of its send buffer -- into the ghost tensor (the
+        // wire's width is its ld), or into my receive buffer for the unpack (exact rows narrower than ld)
+        const uint32_t w = lp.wire.w;
+        float *dst = lp.direct ? lp.ghost : c->recv_buf;
+        for (uint32_t q = 0; q < c->numNodes; ++q) {
+            if (q == c->nodeId || !p.recv_counts[q]) continue;
+            const dory_ctx *Q = grp.ctx[q];
+            const HaloPlan &pq = Q->plan[lp.dir];
+            if (!pq.set || pq.send_counts.size() != c->numNodes || pq.send_counts[c->nodeId] != p.recv_counts[q])
+                return fail(c, DORY_ERR_COMM, "local transport: rank %u expects %u rows from rank %u, which sends %u", c->nodeId, p.recv_counts[q], q,
+                            pq.set && pq.send_counts.size() == c->numNodes ? pq.send_counts[c->nodeId] : 0u);
+            if ((size_t)pq.send_total * w * sizeof(float) > Q->send_cap)
+                return fail(c, DORY_ERR_COMM, "local transport: send buffer of rank %u too small for %u-float rows", q, w);
+            HIPCK(c, hipMemcpyAsync(dst + (size_t)p.recv_off[q] * w, Q->send_buf + (size_t)pq.send_off[c->nodeId] * w,
+                                    (size_t)p.recv_counts[q] * w * sizeof(float), hipMemcpyDeviceToDevice, c->comm));
+        }
+    }
+    if (!lp.direct) { int rc = unpack_rows(c, lp.ghost, lp.ghost_ld, lp.wire, c->recv_buf, p, c->comm); if (rc) return rc; }
     HIPCK(c, hipEventRecord(c->ev_cons[s & 1], c->comm));
     c->posted_cons.store(s, std::memory_order_release);
     if (lp.t_kind_b) (void)hipEventRecord(lp.t_kind_b, c->comm);
@@ -388,9 +437,17 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
             if (Q && halo_exact(Q) != wire.exact)
                 return fail(c, DORY_ERR_COMM, "local transport: option halo_exact_rows differs: rank %u has %d, rank %u has %d (all ranks must agree)",
                             c->nodeId, (int)wire.exact, q, (int)!wire.exact);
+            if (Q && halo_direct(Q) != p.direct)   // (who pushes and who pulls)
+                return fail(c, DORY_ERR_COMM, "local transport: option halo_direct_recv differs: rank %u has %d, rank %u has %d (all ranks must agree)",
+                            c->nodeId, (int)p.direct, q, (int)!p.direct);
         }
     }
-    const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
+    const bool direct = lands_directly(p, wire, ghost->ld);
+    if (direct && ghost->rows != p.recv_total)   // (the received rows are written at the tensor's own stride: it must hold exactly them)
+        return fail(c, DORY_ERR_ARG, "halo_exchange: ghost tensor of %llu rows for a plan that receives %u", (unsigned long long)ghost->rows, p.recv_total);
+    // (option halo_direct_recv: a receive buffer only where dory_halo_plan allocated one -- never inside an epoch)
+    const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = direct ? 0 : (size_t)p.recv_total * w * sizeof(float);
+    if (p.direct && rb > c->recv_cap) return fail(c, DORY_ERR_ARG, NO_RECV_BUF, w, ghost->ld);
     if (tr == Transport::Local && (sb > c->send_cap || rb > c->recv_cap))
         return fail(c, DORY_ERR_COMM, "local transport: exchange buffers too small for %u-float rows (peers hold their addresses: no regrowth)", w);
     // (no growth after dory_halo_plan sized them for the widest layer: only for a tensor uploaded with other dimensions than
@@ -400,13 +457,15 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     HIPCK(c, hipEventRecord(c->ev_a, c->compute));
     HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
     const bool deferred = defer && c->opt["halo_overlap"];
+    (direct ? c->halo_direct_recvs : c->halo_staged_recvs) += 1;
     if (tr == Transport::Local) return exchange_local(c, dir, src, ghost, wire, deferred);
     {   // host transport and RCCL: same pack / unpack / events, only the way from send_buf to recv_buf differs
         Timed t(c, "halo", c->comm);
         Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
         int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm);
-        if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, w) : exchange_rccl(c, p, w);
-        if (!rc) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm);
+        float *recv = direct ? ghost->d : c->recv_buf;
+        if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, w, recv) : exchange_rccl(c, p, w, recv);
+        if (!rc && !direct) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm);
         if (rc) return rc;
         // the one step of an arm left in the shared body: the host arm's, but it stays behind the unpack, so that the unpack
         // is enqueued before the host blocks for the copy out of tx_recv (which the next exchange reuses)
@@ -471,6 +530,7 @@ int dory_comm_init_local(dory_ctx *const *ctxs, uint32_t n) {
         c->posted_sent = 0; c->posted_cons = 0; c->posted_g = 0; c->posted_gdone = 0;
         c->local_seq = c->local_ar_seq = 0;
         c->local_pending = dory_ctx::LocalPending();
+        c->local_sent_to.clear();
         c->local = grp;
     }
     return DORY_OK;
@@ -505,11 +565,24 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
         seen[recv_slots[i]] = 1;
     }
     if (p.d_send_lvids) (void)hipFree(p.d_send_lvids);
+    if (p.d_unpack_slots && p.d_unpack_slots != p.d_recv_slots) (void)hipFree(p.d_unpack_slots);
     if (p.d_recv_slots) (void)hipFree(p.d_recv_slots);
-    p.d_send_lvids = p.d_recv_slots = nullptr;
+    p.d_send_lvids = p.d_recv_slots = p.d_unpack_slots = nullptr;
     int rc;
     if ((rc = upload_array(c, &p.d_send_lvids, send_lvids, p.send_total))) return rc;
     if ((rc = upload_array(c, &p.d_recv_slots, recv_slots, p.recv_total))) return rc;
+    // option halo_direct_recv: received row r is ghost row r; recv_slots names the caller-visible index of that row (kept for
+    // the uploads and downloads of ghost tensors), the unpack kernels get the identity
+    p.direct = halo_direct(c);
+    p.order.clear();
+    p.d_unpack_slots = p.d_recv_slots;
+    if (p.direct) {
+        p.order.assign(recv_slots, recv_slots + p.recv_total);
+        std::vector<uint32_t> ident(p.recv_total);
+        std::iota(ident.begin(), ident.end(), 0u);
+        p.d_unpack_slots = nullptr;
+        if ((rc = upload_array(c, &p.d_unpack_slots, ident.data(), p.recv_total))) return rc;
+    }
     p.set = true;
     // pack / receive buffers for the widest row any layer exchanges, now, so that no allocation (and no device-wide
     // synchronisation) happens inside an epoch
@@ -518,7 +591,10 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
         w = std::max(w, pad_ld(c->dims[l]));
         if (c->gnn == DORY_GATMH && l < c->L && l < c->heads.size()) w = std::max(w, pad_ld(c->dims[l + 1] * c->heads[l]));
     }
-    return ensure_exchange_buffers(c, (size_t)p.send_total * w * sizeof(float), (size_t)p.recv_total * w * sizeof(float));
+    // (option halo_direct_recv: padded rows land in the ghost tensors; only exact rows narrower than their padding -- option
+    // halo_exact_rows, as it stands now -- are staged)
+    const bool staged = !p.direct || halo_exact(c);
+    return ensure_exchange_buffers(c, (size_t)p.send_total * w * sizeof(float), staged ? (size_t)p.recv_total * w * sizeof(float) : 0);
 }
 
 int dory_comm_set_host_transport(dory_ctx *c, dory_alltoallv_fn alltoallv, dory_allreduce_fn allreduce_sum, void *user) {

@@ -277,6 +277,7 @@ int dory_create(int device, dory_ctx **out) {
     c->opt["gatmh_bf16_gather"] = 0;     // multi-head GAT: the sweep forms' edge passes gather their rows rounded to bf16, fp32 sums: 1 = forward (z), 2 = and the backward's source side (do) (opt-in; see dorylus_hip.h)
     c->opt["gatmh_bf16_wide"] = 0;       // multi-head GAT, with gatmh_bf16_gather: passes on bf16 rows of 128 floats or more (several heads of 16 / 32 / 64 features) gather eight features per lane (16-byte gathers); same bits (opt-in; see dorylus_hip.h)
     c->opt["halo_exact_rows"] = 0;       // packed halo rows hold exactly `cols` floats instead of the padded `ld` (every transport and the split entry points; same ghost rows bit for bit; opt-in; see dorylus_hip.h)
+    c->opt["halo_direct_recv"] = 0;      // halo rows land in the ghost tensors themselves, ghost rows stored in wire order: no receive buffer, no unpack (before dory_graph_upload; opt-in; see dorylus_hip.h)
     c->opt["gcn_transform_first"] = 0;   // GCN layers as A(XW) instead of (AX)W where the input is wider than the output: 1 = layer 0, 2 = all (see tf_layer)
     c->opt["epoch_graph"] = 0;       // engine: replay a recorded epoch (hipGraph) when the partition is alone
     c->opt["spmm_blk_nb"] = 0;       // K1b: number of source blocks (0 = auto, ~3.75 MB windows)
@@ -320,6 +321,7 @@ int dory_destroy(dory_ctx *c) {
     free_graph(c);
     for (int d = 0; d < 2; ++d) {
         if (c->plan[d].d_send_lvids) (void)hipFree(c->plan[d].d_send_lvids);
+        if (c->plan[d].d_unpack_slots && c->plan[d].d_unpack_slots != c->plan[d].d_recv_slots) (void)hipFree(c->plan[d].d_unpack_slots);
         if (c->plan[d].d_recv_slots) (void)hipFree(c->plan[d].d_recv_slots);
     }
     if (c->scratch) (void)hipFree(c->scratch);
@@ -744,6 +746,49 @@ static int download_dense(dory_ctx *c, const Tensor &t, float *host) {
     return DORY_OK;
 }
 
+// Option halo_direct_recv: the plan whose wire order the rows of tensor `name` are stored in -- a ghost tensor of that direction
+// with rows -- or null: row r of the tensor is the received row r, the caller's row order[r] (HaloPlan, ctx.hpp).
+static int ghost_wire_plan(dory_ctx *c, const char *who, const char *name, const Tensor &t, const HaloPlan **out) {
+    *out = nullptr;
+    if (!c->halo_direct.load(std::memory_order_acquire) || t.rows == 0) return DORY_OK;
+    int dir = -1;
+    for (const char *nm : {"fg", "fgxw", "fg_z", "fg_el", "fg_er"}) if (!strcmp(name, nm)) dir = DORY_FORWARD;
+    for (const char *nm : {"bg", "bgg", "bg_d", "bg_do", "bg_st"}) if (!strcmp(name, nm)) dir = DORY_BACKWARD;
+    if (dir < 0) return DORY_OK;
+    const HaloPlan &p = c->plan[dir];
+    if (!p.set || !p.direct || p.recv_total != t.rows)
+        return fail(c, DORY_ERR_ARG, "%s: halo_direct_recv keeps '%s' in wire order: dory_halo_plan of direction %d first", who, name, dir);
+    *out = &p;
+    return DORY_OK;
+}
+// host rows in the caller's order -> the tensor's rows in wire order: the dense rows are permuted, then padded as upload_dense pads
+static int upload_ghost_wire(dory_ctx *c, Tensor &t, const float *host, const HaloPlan &p) {
+    if (t.cols == 0) return DORY_OK;
+    const size_t n = (size_t)t.rows * t.cols;
+    float *stage = nullptr;
+    HIPCK(c, hipMalloc((void **)&stage, 2 * n * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(stage, host, n * sizeof(float), hipMemcpyHostToDevice, c->compute);
+    if (e == hipSuccess) e = launch_permute_rows(t.ld == t.cols ? t.d : stage + n, stage, t.cols, p.d_recv_slots, (uint32_t)t.rows, true, c->compute);
+    if (e == hipSuccess && t.ld != t.cols) e = launch_pad_copy(t.d, t.ld, stage + n, t.cols, t.rows, t.cols, c->compute);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->compute);
+    (void)hipFree(stage);
+    HIPCK(c, e);
+    return DORY_OK;
+}
+// and back: the rows return to the caller's order in a staging copy, which travels as download_dense moves a tensor
+static int download_ghost_wire(dory_ctx *c, const Tensor &t, float *host, const HaloPlan &p) {
+    if (t.cols == 0) return DORY_OK;
+    Tensor st = t;
+    st.d = nullptr;
+    HIPCK(c, hipStreamSynchronize(c->comm));
+    HIPCK(c, hipMalloc((void **)&st.d, t.bytes()));
+    hipError_t e = launch_permute_rows(st.d, t.d, t.ld, p.d_recv_slots, (uint32_t)t.rows, false, c->compute);
+    int rc = e == hipSuccess ? download_dense(c, st, host) : fail(c, DORY_ERR_HIP, "tensor_download: row permutation failed: %s", hipGetErrorString(e));
+    (void)hipStreamSynchronize(c->compute);
+    (void)hipFree(st.d);
+    return rc;
+}
+
 int dory_tensor_upload(dory_ctx *c, uint32_t layer, const char *name, const float *host) {
     CHECK_CTX(c);
     { int wrc = wait_halo(c); if (wrc) return wrc; }
@@ -754,7 +799,9 @@ int dory_tensor_upload(dory_ctx *c, uint32_t layer, const char *name, const floa
     if (!strcmp(name, "dA") && layer < c->gat_drow_valid.size()) c->gat_drow_valid[layer] = 0;
     if ((!strcmp(name, "z") || !strcmp(name, "fg_z")) && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;
     { int hrc = gat_edge_tensor_hook(c, layer, name, true); if (hrc) return hrc; }
-    return upload_dense(c, *t, host);
+    const HaloPlan *wire = nullptr;
+    { int prc = ghost_wire_plan(c, "tensor_upload", name, *t, &wire); if (prc) return prc; }
+    return wire ? upload_ghost_wire(c, *t, host, *wire) : upload_dense(c, *t, host);
 }
 
 int dory_tensor_download(dory_ctx *c, uint32_t layer, const char *name, float *host) {
@@ -763,7 +810,9 @@ int dory_tensor_download(dory_ctx *c, uint32_t layer, const char *name, float *h
     Tensor *t = name ? find(c, layer, name) : nullptr;
     if (!t || !host) return fail(c, DORY_ERR_ARG, "tensor_download: no tensor '%s' at layer %u", name ? name : "(null)", layer);
     { int hrc = gat_edge_tensor_hook(c, layer, name, false); if (hrc) return hrc; }
-    return download_dense(c, *t, host);
+    const HaloPlan *wire = nullptr;
+    { int prc = ghost_wire_plan(c, "tensor_download", name, *t, &wire); if (prc) return prc; }
+    return wire ? download_ghost_wire(c, *t, host, *wire) : download_dense(c, *t, host);
 }
 
 int dory_tensor_fill_uniform(dory_ctx *c, uint32_t layer, const char *name, uint64_t seed, float lo,
@@ -775,7 +824,14 @@ int dory_tensor_fill_uniform(dory_ctx *c, uint32_t layer, const char *name, uint
     if (layer == 0) c->ah0_valid = false;
     if ((!strcmp(name, "z") || !strcmp(name, "fg_z")) && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;
     uint32_t *ids = nullptr;
-    if (global_row_ids && t->rows) {
+    const HaloPlan *wire = nullptr;
+    { int prc = ghost_wire_plan(c, "tensor_fill", name, *t, &wire); if (prc) return prc; }
+    if (wire) {   // option halo_direct_recv: stored row r is the caller's row order[r] -- it gets that row's values
+        std::vector<uint32_t> wids(t->rows);
+        for (uint64_t r = 0; r < t->rows; ++r) wids[r] = global_row_ids ? global_row_ids[wire->order[r]] : wire->order[r];
+        int rc = upload_array(c, &ids, wids.data(), t->rows);
+        if (rc) return rc;
+    } else if (global_row_ids && t->rows) {
         int rc = upload_array(c, &ids, global_row_ids, t->rows);
         if (rc) return rc;
     }
@@ -930,6 +986,11 @@ int dory_get_option(dory_ctx *c, const char *key, int64_t *value) {
     if (key && value && !strcmp(key, "halo_rows_packed")) { *value = (int64_t)c->halo_rows_packed; return DORY_OK; }
     if (key && value && !strcmp(key, "halo_floats_packed")) { *value = (int64_t)c->halo_floats_packed; return DORY_OK; }
     if (key && value && !strcmp(key, "halo_exact_packs")) { *value = (int64_t)c->halo_exact_packs; return DORY_OK; }
+    // read-only: the exchanges (eager calls and recordings, one step each) whose rows landed in the ghost tensor itself (option
+    // halo_direct_recv) / went through the receive buffer and an unpack, and the bytes of that buffer
+    if (key && value && !strcmp(key, "halo_direct_recvs")) { *value = (int64_t)c->halo_direct_recvs; return DORY_OK; }
+    if (key && value && !strcmp(key, "halo_staged_recvs")) { *value = (int64_t)c->halo_staged_recvs; return DORY_OK; }
+    if (key && value && !strcmp(key, "halo_recv_buf_bytes")) { *value = (int64_t)c->recv_cap; return DORY_OK; }
     if (key && value && !strcmp(key, "epoch_graph_recorded")) {   // read-only: does the ctx still hold a recorded epoch?
         *value = c->epoch_exec ? 1 : 0;
         return DORY_OK;
@@ -1012,6 +1073,11 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     if (key && !strcmp(key, "halo_exact_rows")) {
         if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "halo_exact_rows: 0 (padded rows travel) or 1 (rows of exactly cols floats)");
         c->halo_exact.store((int)value, std::memory_order_release);
+    }
+    if (key && !strcmp(key, "halo_direct_recv")) {
+        if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "halo_direct_recv: 0 (receive buffer and unpack) or 1 (halo rows land in the ghost tensors, stored in wire order)");
+        if (c->has_graph) return fail(c, DORY_ERR_ARG, "halo_direct_recv: set it before the graph is uploaded (the adjacency's ghost numbering depends on it)");
+        c->halo_direct.store((int)value, std::memory_order_release);
     }
     if (!key || c->opt.find(key) == c->opt.end()) return fail(c, DORY_ERR_ARG, "unknown option '%s'", key ? key : "(null)");
     c->opt[key] = value;

@@ -41,6 +41,13 @@ struct HaloPlan {
     uint32_t send_total = 0, recv_total = 0;
     uint32_t *d_send_lvids = nullptr;  // concat over peers
     uint32_t *d_recv_slots = nullptr;  // concat over peers
+    // option halo_direct_recv (the value when the plan was made): received row r is stored at ghost row r, and recv_slots[r]
+    // (`order`, on the device d_recv_slots) is the caller-visible ghost index of that row -- what dory_tensor_upload / download /
+    // fill_uniform of a ghost tensor permute by.  d_unpack_slots is what the unpack kernels scatter by: d_recv_slots, or under
+    // the option an identity list of its own (a staged exchange and dory_halo_unpack* copy row r to ghost row r).
+    bool direct = false;
+    std::vector<uint32_t> order;
+    uint32_t *d_unpack_slots = nullptr;
 };
 
 // The wire format of a packed halo row: w floats per row -- the tensor's padded ld, or with `exact` (option halo_exact_rows)
@@ -228,6 +235,11 @@ struct dory_ctx {
     // eager packs wrote into send buffers since dory_create: rows, floats, packs that ran the exact form with cols < ld
     std::atomic<int> halo_exact{0};
     uint64_t halo_rows_packed = 0, halo_floats_packed = 0, halo_exact_packs = 0;
+    // option halo_direct_recv (a copy the peers of the local transport may read without this context's lock; fixed once a graph
+    // is uploaded: the adjacency's ghost numbering depends on it), and the exchanges (eager calls and recordings) whose rows
+    // landed in the ghost tensor itself / went through a receive buffer and an unpack
+    std::atomic<int> halo_direct{0};
+    uint64_t halo_direct_recvs = 0, halo_staged_recvs = 0;
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
     dory_alltoallv_fn tx_a2a = nullptr;
@@ -240,7 +252,7 @@ struct dory_ctx {
     // host side checks the peer's progress counter first -- so no stream depends on a host call still to come
     std::shared_ptr<dory::LocalGroup> local;
     hipEvent_t ev_sent[2] = {nullptr, nullptr};    // [seq & 1]: my rows of exchange seq have landed in the peers' receive buffers
-    hipEvent_t ev_cons[2] = {nullptr, nullptr};    // [seq & 1]: my receive buffer of exchange seq has been unpacked
+    hipEvent_t ev_cons[2] = {nullptr, nullptr};    // [seq & 1]: my receive buffer of exchange seq has been unpacked (halo_direct_recv: I have copied my rows of exchange seq out of the peers' send buffers)
     hipEvent_t ev_gready[2] = {nullptr, nullptr};  // [seq & 1]: my weight gradient of sum seq is final
     hipEvent_t ev_gdone[2] = {nullptr, nullptr};   // [seq & 1]: I have read every peer's gradient of sum seq
     std::atomic<uint64_t> posted_sent{0}, posted_cons{0}, posted_g{0}, posted_gdone{0};   // last seq whose event is recorded
@@ -251,8 +263,10 @@ struct dory_ctx {
         float *ghost = nullptr;
         uint32_t ghost_ld = 0;
         dory::RowWire wire;                         // what the rows in recv_buf look like (exact: the unpack zeroes [w, ghost_ld))
+        bool direct = false;                        // halo_direct_recv and w == ghost_ld: the peers' segments are copied into the ghost tensor itself
         hipEvent_t t_halo_b = nullptr, t_kind_b = nullptr;   // timing: end events of the "halo" / "halo_deferred|waited" intervals
     } local_pending;
+    std::vector<char> local_sent_to;  // halo_direct_recv: the peers that read my send buffer in the last exchange (they pull; I pack again after their "consumed")
     float *ar_tmp = nullptr;          // gradient sum before it replaces the local gradient
     size_t ar_tmp_cap = 0;
 
@@ -538,6 +552,9 @@ hipError_t launch_gather_rows_exact(float *dst, const float *src, uint32_t ld, u
 hipError_t launch_scatter_rows_exact(float *dst, const float *src, uint32_t ld, uint32_t cols,
                                      const uint32_t *rows, uint32_t n, hipStream_t s);
 hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const uint32_t *rows, uint32_t n, hipStream_t s);
+// option halo_direct_recv: whole ld-wide rows (any ld) between the caller-visible order of a ghost tensor and its stored (wire)
+// order, off the epoch's path -- to_wire: dst[i] = src[order[i]] (upload), else dst[order[i]] = src[i] (download)
+hipError_t launch_permute_rows(float *dst, const float *src, uint32_t ld, const uint32_t *order, uint32_t n, bool to_wire, hipStream_t s);
 
 // K7 Adam
 hipError_t launch_adam(float *w, const float *g, float *m, float *v, uint64_t n, float lr_t,

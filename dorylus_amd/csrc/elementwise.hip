@@ -716,6 +716,28 @@ hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const ui
     return hipGetLastError();
 }
 
+// ---- option halo_direct_recv: a ghost tensor between its caller-visible and its stored (wire) order ------------------------
+// Whole ld-wide rows, a dword per thread (ld may be 1: the per-head tensors of a single head), `order` a permutation of
+// [0, n).  Off the epoch's path: dory_tensor_upload / dory_tensor_download of a ghost tensor only.
+__global__ __launch_bounds__(256) void permute_rows_kernel(float *dst, const float *src, uint32_t ld, const uint32_t *order,
+                                                           uint32_t n, int to_wire) {
+    const uint64_t total = (uint64_t)n * ld;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / ld);
+        const uint32_t c = (uint32_t)(i - (uint64_t)r * ld);
+        const size_t other = (size_t)order[r] * ld + c;
+        if (to_wire) dst[i] = src[other];
+        else dst[other] = src[i];
+    }
+}
+hipError_t launch_permute_rows(float *dst, const float *src, uint32_t ld, const uint32_t *order, uint32_t n, bool to_wire, hipStream_t s) {
+    if (n == 0 || ld == 0) return hipSuccess;
+    const uint64_t total = (uint64_t)n * ld;
+    int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(permute_rows_kernel, dim3(blocks), dim3(256), 0, s, dst, src, ld, order, n, to_wire ? 1 : 0);
+    return hipGetLastError();
+}
+
 // ---- K7: Adam -----------------------------------------------------------------------------
 // AdamOptimizer::update (reference src/weight-server/AdamOptimizer.cpp:36-51), the
 // mixed float/double expressions kept as written there ("(1. - BETA1) * gt" is double).

@@ -21,6 +21,10 @@
 
 #include "../../include/dorylus_host.h"
 
+// dory_partition_upload asks the context for option halo_direct_recv.  Weak: a host-only build of this file (the sanitizer
+// driver links it without the device library) has no contexts that carry options; the upload then takes the plain arrays.
+extern "C" int dory_get_option(dory_ctx *ctx, const char *key, int64_t *value) __attribute__((weak));
+
 struct dory_partition {
     uint32_t N = 0, V = 0, Gsrc = 0, Gdst = 0, P = 0;
     uint64_t nin = 0, nout = 0, nglobal = 0;
@@ -420,16 +424,54 @@ int dory_partition_recv_plan(const dory_partition *p, const int32_t *parts, int 
     return DORY_OK;
 }
 
+int dory_partition_wire_order(const dory_partition *p, const int32_t *parts, int dir, uint32_t *order, uint32_t *idxs) {
+    if (!p || !parts || (dir != 0 && dir != 1)) return herr(DORY_ERR_ARG, "wire_order: bad arguments");
+    const uint32_t G = dir == 0 ? p->Gsrc : p->Gdst;
+    const std::vector<uint32_t> &idx = dir == 0 ? p->rowIdx : p->colIdx;
+    if ((G && !order) || (!idx.empty() && !idxs)) return herr(DORY_ERR_ARG, "wire_order: bad arguments");
+    // the r-th received row: peers in rank order, a peer's rows in the order of its send list = the ghost slots it owns in
+    // ascending global id -- what dory_partition_recv_plan emits
+    std::vector<uint32_t> cnt(p->P, 0), ord((size_t)G + 1, 0);
+    int rc = dory_partition_recv_plan(p, parts, dir, cnt.data(), ord.data());
+    if (rc) return rc;
+    std::vector<uint32_t> inv(G);
+    for (uint32_t r = 0; r < G; ++r) {
+        order[r] = ord[r];
+        inv[ord[r]] = r;
+    }
+    for (size_t e = 0; e < idx.size(); ++e) {
+        const uint32_t id = idx[e];
+        if (id >= p->N && id - p->N >= G) return herr(DORY_ERR_ARG, "wire_order: ghost id out of range");
+        idxs[e] = id < p->N ? id : p->N + inv[id - p->N];
+    }
+    return DORY_OK;
+}
+
 int dory_partition_upload(dory_ctx *ctx, const dory_partition *p, const int32_t *parts) {
     if (!ctx || !p) return herr(DORY_ERR_ARG, "partition_upload: bad arguments");
-    int rc = dory_graph_upload(ctx, p->N, p->Gsrc, p->Gdst, p->nin, p->colPtr.data(), p->rowIdx.data(),
-                               p->cscVal.data(), p->nout, p->rowPtr.data(), p->colIdx.data(),
-                               p->csrVal.data(), p->norm.data());
+    // option halo_direct_recv: the adjacency goes up with its ghost ids in wire order (copies: the partition stays as it is)
+    int64_t direct = 0;
+    int rc = dory_get_option ? dory_get_option(ctx, "halo_direct_recv", &direct) : (int)DORY_OK;
+    if (rc) return rc;
+    std::vector<uint32_t> order[2], wired[2];
+    if (direct && p->Gsrc + p->Gdst > 0) {
+        if (!parts) return herr(DORY_ERR_ARG, "partition_upload: halo_direct_recv needs the parts vector (the wire order follows the ghosts' owners)");
+        for (int dir = 0; dir < 2; ++dir) {
+            order[dir].resize((size_t)(dir == 0 ? p->Gsrc : p->Gdst) + 1);
+            wired[dir].resize((dir == 0 ? p->rowIdx : p->colIdx).size() + 1);
+            if ((rc = dory_partition_wire_order(p, parts, dir, order[dir].data(), wired[dir].data()))) return rc;
+        }
+    }
+    const bool renum = !wired[0].empty();
+    rc = dory_graph_upload(ctx, p->N, p->Gsrc, p->Gdst, p->nin, p->colPtr.data(), renum ? wired[0].data() : p->rowIdx.data(),
+                           p->cscVal.data(), p->nout, p->rowPtr.data(), renum ? wired[1].data() : p->colIdx.data(),
+                           p->csrVal.data(), p->norm.data());
     if (rc) return rc;
     // the transform-first GCN order needs csrVal == cscVal transposed: only known for directed builds
     if ((rc = dory_set_option(ctx, "adjacency_values_asymmetric", p->undirected == 0 ? 0 : 1))) return rc;
     if (!parts || p->P <= 1) return rc;
-    // receive side of the plan: peer q's k-th row lands in the k-th ghost slot owned by q
+    // receive side of the plan: peer q's k-th row lands in the k-th ghost slot owned by q (halo_direct_recv: the same list
+    // -- it is the wire order -- now names the caller-visible ghost index of every received row)
     for (int dir = 0; dir < 2; ++dir) {
         const std::vector<uint32_t> &ghost = dir == 0 ? p->srcGhost : p->dstGhost;
         std::vector<uint32_t> rcnt(p->P, 0), rslots(ghost.size() + 1, 0);

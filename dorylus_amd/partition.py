@@ -114,6 +114,20 @@ class Partition:
         off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
         return [slots[off[i]:off[i + 1]].copy() for i in range(P)]
 
+    def wire_order(self, parts, direction):
+        """(order, idxs) of dory_partition_wire_order: order[r] = the ghost slot of the r-th received row (= the concatenated
+        recv_plan lists), idxs = that direction's index array (rowIdx / colIdx) with every ghost id N + order[r] replaced by
+        N + r -- the adjacency a context with option halo_direct_recv takes.  The partition itself is not modified."""
+        v = self.view()
+        G = int(v["srcGhostCnt"] if direction == 0 else v["dstGhostCnt"])
+        nnz = int(v["localInEdgeCnt"] if direction == 0 else v["localOutEdgeCnt"])
+        p = np.ascontiguousarray(parts, np.int32)
+        order = np.zeros(G + 1, np.uint32)
+        idxs = np.zeros(nnz + 1, np.uint32)
+        self._ck(self.lib, self.lib.dory_partition_wire_order(self.h, p.ctypes.data, direction, order.ctypes.data,
+                                                               idxs.ctypes.data))
+        return order[:G].copy(), idxs[:nnz].copy()
+
     def upload(self, ctx, parts=None):
         """dory_graph_upload + both halo plans (when the .parts vector is given)."""
         p = None if parts is None else np.ascontiguousarray(parts, np.int32)

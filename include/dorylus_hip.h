@@ -169,7 +169,9 @@ int dory_train_stat_global(dory_ctx *ctx, float *acc_sum, float *loss_sum, uint3
  * The plan is the per-peer send lists of graph.<id>.bin (forwardGhostsList /
  * backwardGhostsList, graph/dataloader.cpp:277-297) plus, per peer, the ghost
  * slots its rows land in (srcGhostVtcs / dstGhostVtcs order, dataloader.cpp:311-322).
- * counts arrays have num_nodes entries; lists are concatenated in peer order. */
+ * counts arrays have num_nodes entries; lists are concatenated in peer order.
+ * (With option "halo_direct_recv" = 1 received row r is stored at ghost row r and recv_slots names its caller-visible index:
+ * see the option's comment below.) */
 int dory_halo_plan(dory_ctx *ctx, int dir, const uint32_t *send_counts,
                    const uint32_t *send_lvids, const uint32_t *recv_counts,
                    const uint32_t *recv_slots);
@@ -398,6 +400,52 @@ int dory_transform_first_layer(dory_ctx *ctx, uint32_t layer);
  * the same width variable as the other two, but no run with more than one RCCL rank has ever executed it (two ranks cannot
  * share one GPU under RCCL): the link bytes saved -- 41/64, 48/64, 25/32 of the padded form's -- are arithmetic, not a
  * measurement.  Pack / unpack cost measured on one GPU: DESIGN.md section 5, profiles/r11_halo_exact_rows.txt. */
+
+/* Wire-ordered ghosts (option "halo_direct_recv", default 0; every gnn_type; set before dory_graph_upload and refused with
+ * DORY_ERR_ARG once a graph is uploaded: the adjacency's ghost numbering depends on it; read by dory_graph_upload's callers and
+ * by dory_halo_plan).  0: a halo exchange packs, transports into a receive buffer, and unpacks that buffer into the ghost tensor
+ * by recv_slots.  1: ghost rows are stored in the order they arrive on the wire -- peer by peer, each peer's rows in the order
+ * of its send list -- so the received row r IS ghost row r, the receive targets the ghost tensor itself, and the unpack kernel
+ * and the receive buffer disappear.  Every gather already reads ghost rows through an index (a source id >= N is row id - N of
+ * the ghost tensor), so nothing changes on the epoch's path but the ids.
+ *   adjacency       the caller of dory_graph_upload promises index arrays whose ghost ids are already in wire order: id N + r
+ *                   names the r-th received row.  dory_partition_upload does this itself (dory_partition_wire_order,
+ *                   dorylus_host.h: renumbered copies, the partition object is not modified) and needs the parts vector.
+ *   recv_slots      dory_halo_plan's recv_slots no longer says where a received row is stored -- row r is stored at ghost row r
+ *                   -- but names the caller-visible ghost index of that row: the reference's slot k of local id N + k
+ *                   (srcGhostVtcs / dstGhostVtcs order).  It must still be a permutation of the ghost slots.
+ *   ghost tensors   dory_tensor_upload, dory_tensor_download and dory_tensor_fill_uniform of fg, fgxw, fg_z, fg_el, fg_er (plan
+ *                   of DORY_FORWARD) and bg, bgg, bg_d, bg_do, bg_st (DORY_BACKWARD) keep the caller-visible order: host row k
+ *                   is the reference's ghost k, global_row_ids[k] its id.  The rows are permuted on the device on the way in
+ *                   and out (a row kernel on the compute stream, not on the epoch's path), so they need that direction's plan
+ *                   (DORY_ERR_ARG before it).  The raw device_ptr of dory_tensor_info points at WIRE-ordered rows.
+ *   exchange        where the wire's width is the tensor's ld (always with halo_exact_rows = 0; with 1 for tensors whose cols
+ *                   equal ld): RCCL -- ncclRecv targets the ghost tensor at recv_off[peer] * ld; host transport -- the
+ *                   host-to-device copy of the received floats targets the ghost tensor; in-process transport -- the RECEIVER
+ *                   pulls: once its peers' "sent" events are recorded it copies each peer's segment out of that peer's send
+ *                   buffer into its own ghost tensor on its own comm stream and records "consumed", and a sender waits for the
+ *                   "consumed" of the ranks that read its send buffer in the previous exchange before it packs the next one (the
+ *                   same counters and events, waited for in the same place as the push form's; no host-side wait is added).
+ *                   The multi-head GAT backward's "do" / "st" exchanges land the same way.
+ *   exact rows      with halo_exact_rows = 1 a tensor with cols < ld cannot land (its rows are strided): such an exchange keeps
+ *                   the receive buffer and the unpack kernels, which scatter by an identity list; results are unchanged.
+ *   receive buffer  dory_halo_plan allocates none unless halo_exact_rows is 1 at that moment.  A later exchange that needs it
+ *                   fails with DORY_ERR_ARG and says so (set halo_exact_rows = 1 before dory_halo_plan); nothing is allocated
+ *                   and no device-wide synchronisation happens inside an epoch.
+ *   split calls     dory_halo_unpack / dory_halo_unpack_tensor (the caller's buffer in plan order) copy row r to ghost row r at
+ *                   the wire's width; dory_halo_pack* are unchanged.
+ *   agreement       all ranks must use the same value.  The in-process transport checks it against every peer before anything
+ *                   of the exchange is enqueued or counted (DORY_ERR_COMM, naming both ranks); over RCCL and over a host
+ *                   transport it is the caller's contract, as for halo_exact_rows.
+ *   numbers         K1 walks a row's edges in edge order: its sums are bit-identical with 0 and 1.  K1s and K1b spread source
+ *                   rows over blocks by id; renumbered ghosts fall into other blocks, the order of additions inside a row
+ *                   changes, and results hold to the parity criteria, not to the bits of option 0.
+ * Values outside {0, 1} are rejected.  Read-only "halo_direct_recvs" / "halo_staged_recvs": the exchanges (eager calls and
+ * recordings, one step per exchange) whose rows landed in the ghost tensor / went through the receive buffer and an unpack;
+ * "halo_recv_buf_bytes": the bytes of that buffer.  The bf16 shadow rows, the kept neighbour sum of the GAT prototype, the
+ * invalidation of a cached ah@0 and the timing families "halo", "halo_deferred", "halo_waited" behave as with 0.  Not executed:
+ * the RCCL arm with more than one rank (two ranks cannot share one GPU under RCCL).  Measured on one GPU: DESIGN.md section 5,
+ * profiles/r12_halo_direct_recv.txt. */
 
 /* Epoch graph (MI355X-side addition, no reference counterpart): record the calls of one
  * epoch -- dory_aggregate / dory_apply_vertex / dory_apply_edge / dory_predict_gat /

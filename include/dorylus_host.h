@@ -66,8 +66,18 @@ int dory_partition_get(const dory_partition *p, struct dory_partition_view *view
 int dory_partition_recv_plan(const dory_partition *p, const int32_t *parts, int dir,
                              uint32_t *recv_counts, uint32_t *recv_slots);
 
+/* Wire order of a partition's ghosts for direction dir (no GPU needed; option "halo_direct_recv" of dorylus_hip.h):
+ * order[r] = the ghost slot k (local id N + k in the partition) of the r-th row that arrives -- peers in rank order, a peer's
+ * rows in the order of its send list -- which is the list dory_partition_recv_plan emits; idxs = a copy of that direction's index
+ * array (row_idxs for dir 0, column_idxs for dir 1) in which every ghost id N + k is replaced by N + r with order[r] == k, local
+ * ids, edge order, values and pointers untouched.  order has src/dst_ghost_cnt entries, idxs local_in/out_edge_cnt.  The
+ * partition itself is not modified (dory_partition_get and dory_partition_save keep giving the reference's numbering). */
+int dory_partition_wire_order(const dory_partition *p, const int32_t *parts, int dir, uint32_t *order, uint32_t *idxs);
+
 /* upload adjacency (dory_graph_upload) and, when parts is given, both halo plans
- * (dory_halo_plan): recv slots of peer q = ghost slots whose owner is q, ascending. */
+ * (dory_halo_plan): recv slots of peer q = ghost slots whose owner is q, ascending.  On a context with option
+ * "halo_direct_recv" = 1 the index arrays uploaded are the renumbered copies of dory_partition_wire_order (parts is then
+ * required for a partition with ghosts); the plans are the same lists. */
 int dory_partition_upload(dory_ctx *ctx, const dory_partition *p, const int32_t *parts);
 
 /* ---- input files of the reference graph server (engine/utils.cpp:460-596) ------------- */

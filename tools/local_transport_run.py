@@ -11,7 +11,10 @@ to run beside), the local-source launch that runs beside them (spmm_beside_halo)
 ranks SHARE the device: each rank's sweeps take spmm_sweep_cus = 32 / P - 2 CUs of every XCD.  A second configuration gives
 rank 0 98 % of the vertices: rank 0's K1s beside its own comm stream
 with next to nothing else on the device -- the closest one GPU gets to one rank of a real run (24 CUs of every XCD to rank 0's
-sweeps, 4 to rank 1's, 4 left to the copies)."""
+sweeps, 4 to rank 1's, 4 left to the copies).
+A/B runs: --opt KEY=VALUE (repeatable) sets a context option on every rank before the upload (e.g. halo_direct_recv=1),
+--configs NAME... keeps only those configurations, --skip-oracle leaves the CPU oracle's epoch out; DORY_LIB_PATH picks the
+library.  Each run then also records every rank's receive-buffer bytes where the library reports them."""
 import argparse
 import json
 import os
@@ -31,6 +34,9 @@ def main():
     ap.add_argument("--E", type=int, default=4000000)
     ap.add_argument("--dims", type=int, nargs="*", default=[128, 128, 16])
     ap.add_argument("--epochs", type=int, default=50)
+    ap.add_argument("--opt", action="append", default=[], help="KEY=VALUE, a context option of every rank")
+    ap.add_argument("--configs", nargs="*", default=None)
+    ap.add_argument("--skip-oracle", action="store_true")
     a = ap.parse_args()
     import torch  # noqa: F401
     import dorylus_amd as da
@@ -43,7 +49,20 @@ def main():
     labels = rng.integers(0, dims[-1], a.V).astype(np.uint32)
     Ws = [(rng.standard_normal((dims[i], dims[i + 1])) / np.sqrt(dims[i])).astype(np.float32) for i in range(L)]
 
+    extra = {k: int(v) for k, v in (kv.split("=", 1) for kv in a.opt)}
+    recv_bytes = {}
+
     def setup(ctx, r, g):
+        close = ctx.close
+
+        def closing():      # run_local closes its contexts: the receive buffer's size is read just before
+            if ctx.h:
+                try:
+                    recv_bytes[r] = ctx.get_option("halo_recv_buf_bytes")
+                except da.DoryError:
+                    recv_bytes[r] = None      # (a library from before the counter)
+            close()
+        ctx.close = closing
         if g["localVtxCnt"]:
             ctx.upload(0, "x", X[g["localToGlobal"]])
         if g["srcGhostCnt"]:
@@ -70,7 +89,12 @@ def main():
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     from helpers import oracle_gcn_epoch, rel_err
     out["oracle_check"] = []
-    for name, P, parts, share in configs[:2]:
+    if a.configs is not None:
+        configs = [c for c in configs if c[0] in a.configs]
+    with_extra = lambda sh: [dict(x, **extra) for x in sh] if isinstance(sh, list) else dict(sh, **extra)
+    configs = [(name, P, parts, with_extra(share)) for name, P, parts, share in configs]
+    out["options"] = extra
+    for name, P, parts, share in ([] if a.skip_oracle else [c for c in configs if c[0] == "balanced"]):
         pobjs = [da.Partition.build(src, dst, parts, r, P) for r in range(P)]
         dl = [(l, nm) for l in range(L) for nm in ("ah",)] + [(l, nm) for l in range(L - 1) for nm in ("h", "aTg")] + [(l, "grad") for l in range(1, L)]
         res = run_local(da, pobjs, parts, dims, da.GCN, 1, setup, dict(share, halo_overlap=1), downloads=dl)
@@ -102,7 +126,7 @@ def main():
                    "epoch_ms_first_last": [round(float(ms.max(axis=0)[0]), 4), round(float(ms.max(axis=0)[-1]), 4)],
                    "timing_sum_over_ranks_ms": {k: v for k, v in tm.items()},
                    "halo_overlap_fraction": round(tm["halo_hidden"]["ms"] / tm["halo_deferred"]["ms"], 4) if tm["halo_deferred"]["ms"] else None,
-                   "spmm_gates": res["gates"], "wall_s": round(wall, 2)}
+                   "spmm_gates": res["gates"], "recv_buf_bytes_per_rank": [recv_bytes.get(r) for r in range(P)], "wall_s": round(wall, 2)}
             out["runs"].append(rec)
             bits[overlap] = res
             sys.stderr.write(json.dumps({k: rec[k] for k in ("config", "P", "halo_overlap", "epoch_ms_median_max_rank", "halo_overlap_fraction", "spmm_gates")}) + "\n")
