@@ -120,10 +120,11 @@ def load():
         "dory_engine_report": [vp, cp, C.c_size_t],
         "dory_sweep_deal": [u32, u32, u32, vp, vp, vp],
         "dory_sweep_deal_weighted": [u32, vp, u32, u32, u32, vp, vp, vp],
+        "dory_sweep_geometry": [u32, u32, i32, i32, i32, u32, u32, u32, i32, vp],
     }
     for name, args in sig.items():
-        if name == "dory_partition_wire_order" and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv)
+        if name in ("dory_partition_wire_order", "dory_sweep_geometry") and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32

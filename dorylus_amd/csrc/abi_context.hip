@@ -643,7 +643,7 @@ int dory_preallocate(dory_ctx *c) {
             for (uint32_t l = 0; l < L && A.swp.nb; ++l)   // every layer's own launch shape: its leading dimension (a 96-float layer runs 16-lane
                 // groups on two slabs) and the group blk_group_for() gives it; launches walk fewer rows per group than the
                 // layout deals (more sweeps, more counters): 2 is the least
-                need = std::max(need, sweep_scratch_bytes(A.swp, layer_ld(l), blk_group_for(c, layer_ld(l)), G, A.swp.nb, 2));
+                need = std::max(need, sweep_counter_bound(A.swp.npos, layer_ld(l), blk_group_for(c, layer_ld(l)), 2, false, G, A.swp.nb));
         }
         // (ensure_partial synchronises the compute stream before it frees; nothing in flight reads c->partial before `prealloc` is set)
         if ((rc = ensure_partial(c, need, "sweep counters"))) return rc;
@@ -678,10 +678,10 @@ int dory_preallocate(dory_ctx *c) {
             size_t need = 0;
             for (Adjacency &A : c->adj) {
                 if ((rc = ensure_sweep(c, A, group))) return rc;
-                if (A.swp.nb) need = std::max(need, sweep_scratch_bytes(A.swp, maxld, group, G, A.swp.nb, (int)c->opt["spmm_sweep_rows"]));
+                if (A.swp.nb) need = std::max(need, sweep_counter_bound(A.swp.npos, maxld, group, k1s_rows(c, A.swp, group), false, G, A.swp.nb));
                 // (option gcn_bf16_wide's launches never need more, but for a forced row count that only 16-lane groups take)
-                if (A.swp.nb && c->gnn == DORY_GCN && sweep_wide_applies(A.swp, maxld, group, G, (int)c->opt["spmm_sweep_rows"]))
-                    need = std::max(need, sweep_scratch_bytes(A.swp, maxld, group, G, A.swp.nb, (int)c->opt["spmm_sweep_rows"], true));
+                if (A.swp.nb && c->gnn == DORY_GCN && sweep_wide_applies(maxld, group, k1s_rows(c, A.swp, 16)))
+                    need = std::max(need, sweep_counter_bound(A.swp.npos, maxld, group, k1s_rows(c, A.swp, 16), true, G, A.swp.nb));
             }
             if ((rc = ensure_partial(c, need, "sweep counters"))) return rc;
             // the slots of the split rows' pieces too (skewed graphs): an epoch recorded into a hipGraph right after a

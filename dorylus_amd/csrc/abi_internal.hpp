@@ -88,6 +88,7 @@ int ensure_scratch(dory_ctx *c, size_t bytes);
 // c->partial (K1b's partial rows, the sweeps' gate counters); `what` names it in the refusal inside a recording
 int ensure_partial(dory_ctx *c, size_t bytes, const char *what);
 int ensure_sweep(dory_ctx *c, Adjacency &A, int group);
+int k1s_rows(dory_ctx *c, const BlockedAdj &S, int group /* the wide form: 16 */);   // K1s's rows per lane group on the layout S (abi_stages.hip)
 // drops a recorded epoch (hipGraph): anything that frees or moves what the recorded kernels point at calls this
 void epoch_graph_drop_locked(dory_ctx *c);
 std::vector<uint32_t> degree_order(const uint64_t *ptr, uint32_t N);

@@ -166,51 +166,66 @@ static int around_halo(dory_ctx *c, bool split, Bf16Rows *bf, First first, Rest 
     return rest();
 }
 
-// What a launch sequence on the sweep skeleton (K1s, the 8-head GAT's edge passes) needs beside its tensors.
+// What a launch sequence on the sweep skeleton (K1s, the 8-head GAT's edge passes) needs beside its tensors, decided once per
+// aggregation; part() is one launch of it.
 struct SweepLaunch {
     int group = 32;             // lanes per row
+    int R = 0;                  // rows per lane group: the actual count, whichever family
     uint32_t G = 32;            // workgroups per sweep and XCD
     // With ghost rows the blocks that hold local rows only always run as a launch of their own (they do not
     // depend on an exchange in flight), so the overlapped and the sequential schedule are the same arithmetic.
     bool two = false;
+    bool bf16 = false, wide = false;   // the rows gathered: bf16 rows; eight features per lane (its own groups and slabs)
     SweepCtl ctl;
     uint32_t sflags = 0;        // option spmm_sweep_flags, + 8 (ungated) where the XCD placement check failed and "gated" was not measured faster
     size_t need = 0;            // bytes of gate counters the larger of its launches takes
     uint32_t *done = nullptr;   // the counters (c->partial); nullptr: c->partial holds fewer than `need` bytes
+    hipStream_t s = nullptr;
+    SweepPart part(uint32_t b_lo, uint32_t b_hi, bool accumulate, uint32_t reserve = 0) const {
+        return SweepPart{G, b_lo, b_hi, accumulate, reserve, R, done, ctl, sflags, s, bf16, wide};
+    }
 };
 static uint32_t sweep_flags(dory_ctx *c) {
     return (uint32_t)c->opt["spmm_sweep_flags"] | (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
 }
-static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, int group, bool ghosts, int rows /* per lane group */,
-                                bool wide = false /* K1s on bf16 rows, eight features per lane: its own groups and slabs */) {
+static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, int group, bool ghosts, int R, bool bf16, bool wide) {
     SweepLaunch sw;
     sw.group = group;
+    sw.R = R;
     sw.G = std::min<uint32_t>(32u, c->cus_per_xcd);
     sw.two = ghosts && S.nb_local > 0 && S.nb_local < S.nb;
-    sw.ctl.stat = c->sweep_stat;
+    sw.bf16 = bf16;
+    sw.wide = wide;
+    sw.ctl = SweepCtl{(int)c->opt["spmm_sweep_pair"], c->opt["spmm_sweep_loader"] != 0, c->sweep_stat};   // (pair, loader: K1s's forms)
     sw.sflags = sweep_flags(c);
-    sw.need = sweep_scratch_bytes(S, ld, group, sw.G, sw.two ? std::max(S.nb_local, S.nb - S.nb_local) : S.nb, rows, wide);
+    sw.need = sweep_counter_bound(S.npos, ld, group, R, wide, sw.G, sw.two ? std::max(S.nb_local, S.nb - S.nb_local) : S.nb);
     sw.done = sw.need <= c->partial_bytes ? reinterpret_cast<uint32_t *>(c->partial) : nullptr;
+    sw.s = c->compute;
     return sw;
+}
+
+// K1s's rows per lane group on `group` lanes (the wide form: 16) of the layout S: option spmm_sweep_rows, else what S was dealt for
+int k1s_rows(dory_ctx *c, const BlockedAdj &S, int group) {
+    return sweep_rows(S.rows_per_group, S.npos, group, std::min<uint32_t>(32u, c->cus_per_xcd), (int)c->opt["spmm_sweep_rows"]);
 }
 
 // K1s's placement check failed (ctx.hpp): gates would synchronise workgroups that do not share an L2.  Decide once per context,
 // by measurement, on a launch that may be repeated (it writes, does not accumulate): gated against ungated.  The three probe
 // launches are timed under their own key ("spmm_xcd_probe"), outside the caller's "spmm" region.
-static int xcd_probe(dory_ctx *c, const SpmmArgs &a, const BlockedAdj &S, const float *row_scale, const SweepLaunch &sw, bool bf16, bool wide) {
+static int xcd_probe(dory_ctx *c, const SpmmArgs &a, const BlockedAdj &S, const float *row_scale, const SweepLaunch &sw) {
     struct Ev3 {   // destroyed on every way out (HIPCK returns)
         hipEvent_t e[3] = {nullptr, nullptr, nullptr};
         ~Ev3() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
     } ev;
     Timed tp(c, "spmm_xcd_probe", c->compute);
     for (auto &x : ev.e) HIPCK(c, hipEventCreate(&x));
-    const uint32_t hi = sw.two ? S.nb_local : S.nb, gated = sw.sflags & ~8u;
-    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16, wide));   // (warm: layout, code)
-    HIPCK(c, hipEventRecord(ev.e[0], c->compute));
-    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated, c->scratch, 0, bf16, wide));
-    HIPCK(c, hipEventRecord(ev.e[1], c->compute));
-    HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, sw.G, 0, hi, sw.done, c->compute, sw.ctl, gated | 8u, c->scratch, 0, bf16, wide));
-    HIPCK(c, hipEventRecord(ev.e[2], c->compute));
+    SweepPart p = sw.part(0, sw.two ? S.nb_local : S.nb, false);
+    const uint32_t gated = sw.sflags & ~8u;
+    for (int i = 0; i < 3; ++i) {   // ungated (warm: layout, code), gated, ungated
+        p.flags = i == 1 ? gated : gated | 8u;
+        HIPCK(c, launch_spmm_sweep(a, S, sw.group, row_scale, c->scratch, p));
+        HIPCK(c, hipEventRecord(ev.e[i], c->compute));
+    }
     HIPCK(c, hipEventSynchronize(ev.e[2]));
     (void)hipEventElapsedTime(&c->xcd_gated_ms, ev.e[0], ev.e[1]);
     (void)hipEventElapsedTime(&c->xcd_ungated_ms, ev.e[1], ev.e[2]);
@@ -229,36 +244,29 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     if (S.na || !sweep_supported(a, S, group)) return SPMM_NOT_MINE;
     const bool bf16 = bf.on();
     // option gcn_bf16_wide: bf16 rows of 128 floats or more are gathered eight features per lane (same bits; spmm.hip)
-    const bool wide = bf16 && c->opt["gcn_bf16_wide"] == 1 &&
-                      sweep_wide_applies(S, a.ld, group, std::min<uint32_t>(32u, c->cus_per_xcd), (int)c->opt["spmm_sweep_rows"]);
-    SweepLaunch sw = sweep_launch(c, S, a.ld, group, a.xg != nullptr, (int)c->opt["spmm_sweep_rows"], wide);
+    const bool wide = bf16 && c->opt["gcn_bf16_wide"] == 1 && sweep_wide_applies(a.ld, group, k1s_rows(c, S, 16));
+    SweepLaunch sw = sweep_launch(c, S, a.ld, group, a.xg != nullptr, k1s_rows(c, S, wide ? 16 : group), bf16, wide);
     if ((rc = ensure_partial(c, sw.need, "sweep counters"))) return rc;   // (K1s may still size its counters here, outside a recording)
     sw.done = reinterpret_cast<uint32_t *>(c->partial);
     if (S.nslots && (rc = ensure_scratch(c, (size_t)S.nslots * a.ld * sizeof(float)))) return rc;   // pieces of split rows
     c->last_spmm_unit = row_scale != nullptr;
-    sw.ctl.force_r = (int)c->opt["spmm_sweep_rows"];
-    sw.ctl.pair = (int)c->opt["spmm_sweep_pair"];
-    sw.ctl.loader = c->opt["spmm_sweep_loader"] != 0;
     if ((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && !(c->opt["spmm_sweep_flags"] & 8) && c->xcd_policy < 0 &&
         !c->capturing && !a.accumulate && !c->halo_pending) {
-        if ((rc = xcd_probe(c, a, S, row_scale, sw, bf16, wide))) return rc;
+        if ((rc = xcd_probe(c, a, S, row_scale, sw))) return rc;
         sw.sflags = sweep_flags(c);   // (left undecided -- recording, accumulating caller: ungated, never a timeout)
     }
     Timed t(c, "spmm", c->compute);
     c->spmm_launches_k1s++;
     if (bf16) c->bf16_gathers_k1s++;
     if (wide) c->bf16_gathers_k1s_wide++;
-    auto sweep = [&](const SpmmArgs &x, uint32_t b_lo, uint32_t b_hi, uint32_t flags, uint32_t reserve) -> int {
-        HIPCK(c, launch_spmm_sweep(x, S, group, row_scale, sw.G, b_lo, b_hi, sw.done, c->compute, sw.ctl, flags, c->scratch, reserve, bf16, wide));
+    auto sweep = [&](const SweepPart &p) -> int {
+        HIPCK(c, launch_spmm_sweep(a, S, group, row_scale, c->scratch, p));
         return DORY_OK;
     };
-    // under an exchange in flight the RCCL kernels need CUs of their own
+    // under an exchange in flight the RCCL kernels need CUs of their own; the ghost-source blocks go on from the first launch's sums
     const uint32_t reserve = c->halo_pending ? (uint32_t)c->opt["spmm_sweep_reserve_cus"] : 0u;
-    SpmmArgs a2 = a;   // the ghost-source blocks go on from the first launch's sums
-    a2.self_mode = 0;
-    a2.accumulate = 1;
-    rc = around_halo(c, sw.two, &bf, [&] { return sweep(a, 0, S.nb_local, sw.sflags, reserve); },
-                     [&] { return sw.two ? sweep(a2, S.nb_local, S.nb, sw.sflags | 2u, 0) : sweep(a, 0, S.nb, sw.sflags, 0); });
+    rc = around_halo(c, sw.two, &bf, [&] { return sweep(sw.part(0, S.nb_local, false, reserve)); },
+                     [&] { return sweep(sw.two ? sw.part(S.nb_local, S.nb, true) : sw.part(0, S.nb, false)); });
     if (rc) return rc;
     HIPCK(c, launch_spmm_sweep_combine(a, S, row_scale, c->scratch, c->compute, bf16));
     return DORY_OK;
@@ -300,7 +308,7 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
     c->spmm_launches_k1++;
     if (bf16) c->bf16_gathers_k1++;
     auto launch = [&](const SpmmArgs &x) -> int {
-        HIPCK(c, launch_spmm(x, (int)c->opt["spmm_variant"], (int)c->opt["spmm_slab"], c->compute, bf16));
+        HIPCK(c, launch_spmm(x, (int)c->opt["spmm_slab"], c->compute, bf16));
         return DORY_OK;
     };
     const LongRowsDev &longRows = A.long_rows;
@@ -461,27 +469,21 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
 // is read), then the ghost blocks on top of the first launch's sums; without ghost rows `between`, then all blocks at once.
 struct GatmhSweep {
     const DerivedAdj *S = nullptr;
-    bool bf16 = false, wide = false;
     SweepLaunch sw;
     int plan(dory_ctx *c, const DerivedAdj &layout, const SpmmArgs &sa /* N, ld: as in the caller's own sweep_supported test */, uint32_t K,
-             uint32_t D, bool ghosts, int shl, int pass, bool bf16_rows) {
+             uint32_t D, bool ghosts, int shl, int pass, bool bf16) {
         S = &layout;
-        bf16 = bf16_rows;
-        wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, sa.ld) && sweep_supported(sa, layout, GATMH_WIDE_GROUP);
-        const int group = gatmh_sweep_group(sa.ld);
-        sw = wide ? sweep_launch(c, layout, sa.ld, GATMH_WIDE_GROUP, ghosts, GATMH_WIDE_ROWS, true)
-                  : sweep_launch(c, layout, sa.ld, group, ghosts, gatmh_sweep_rows(layout, group, shl, pass));
+        const bool wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, sa.ld) && sweep_supported(sa, layout, GATMH_WIDE_GROUP);
+        const int group = wide ? GATMH_WIDE_GROUP : gatmh_sweep_group(sa.ld);
+        sw = sweep_launch(c, layout, sa.ld, group, ghosts, wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(layout, group, shl, pass), bf16, wide);
         return sw.done ? (int)DORY_OK : fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
     }
     template <class Between, class Part>
-    int run(dory_ctx *c, Between between, Part part) const {
-        auto blocks = [&](uint32_t b_lo, uint32_t b_hi, bool accumulate) -> int {
-            return part(GatSweepPart{sw.G, b_lo, b_hi, accumulate, sw.done, sw.ctl, sw.sflags, c->compute, bf16, wide});
-        };
+    int run(Between between, Part part) const {
         int rc;
-        if (sw.two && (rc = blocks(0, S->nb_local, false))) return rc;
+        if (sw.two && (rc = part(sw.part(0, S->nb_local, false)))) return rc;
         if ((rc = between())) return rc;
-        return sw.two ? blocks(S->nb_local, S->nb, true) : blocks(0, S->nb, false);
+        return part(sw.two ? sw.part(S->nb_local, S->nb, true) : sw.part(0, S->nb, false));
     }
 };
 
@@ -534,11 +536,11 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             if (bf16) {
                 if ((rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
                 c->gatmh_bf16_gathers_fwd++;
-                if (gs.wide) c->gatmh_bf16_gathers_fwd_wide++;
+                if (gs.sw.wide) c->gatmh_bf16_gathers_fwd_wide++;
             }
             const float *zs = bf16 ? bf.xl : z->d, *zgs = bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), *a_l = c->weights[fl]["a_l"].d;
             HIPCK(c, launch_gatmh_sweep_begin(c->N, In.ghosts, K, z->ld, el->ld, Sf, el->d, fgel->d, c->scratch, c->compute));
-            rc = gs.run(c, [&]() -> int { const int r = wait_halo(c); return r ? r : bf.ghosts_landed(); }, [&](const GatSweepPart &p) -> int {
+            rc = gs.run([&]() -> int { const int r = wait_halo(c); return r ? r : bf.ghosts_landed(); }, [&](const SweepPart &p) -> int {
                 HIPCK(c, launch_gatmh_forward_sweep_part(c->N, K, D, z->ld, el->ld, Sf, zs, zgs, er->d, a_l, o->d, op->d, c->scratch, p, el->d, fgel->d));
                 return DORY_OK;
             });
@@ -618,12 +620,12 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
         if (bf16) {
             if ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed())) return rc;
             c->gatmh_bf16_gathers_src++;
-            if (gs.wide) c->gatmh_bf16_gathers_src_wide++;
+            if (gs.sw.wide) c->gatmh_bf16_gathers_src_wide++;
         }
         const float *dos = bf16 ? bf.xl : T.dO->d, *dogs = bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr);
         HIPCK(c, launch_gatmh_src_sweep_begin(c->N, Out.ghosts, K, ld, ldk, So, st4, reinterpret_cast<const float4 *>(T.bgst->d), lds4,
                                               c->scratch, c->compute));
-        rc = gs.run(c, [] { return (int)DORY_OK; }, [&](const GatSweepPart &p) -> int {
+        rc = gs.run([] { return (int)DORY_OK; }, [&](const SweepPart &p) -> int {
             HIPCK(c, launch_gatmh_src_sweep_part(c->N, Out.ghosts, K, D, ld, ldk, So, dos, dogs, T.el->d, T.dz->d, c->scratch, p));
             return DORY_OK;
         });

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/dorylus_hip.h"
+#include "sweep_geometry.hpp"
 
 namespace dory {
 
@@ -313,7 +314,7 @@ struct SpmmArgs {
     const uint64_t *ptr_end;// K1: end of every row's edge range (nullptr: ptr[v + 1]); with accumulate == 2 the sum STARTS from out[v]
 };
 // bf16: xl / xg point at bf16 rows of ld elements (launch_bf16_rows; option gcn_bf16_gather), the sums stay fp32
-hipError_t launch_spmm(const SpmmArgs &a, int variant, int slab, hipStream_t s, bool bf16 = false);
+hipError_t launch_spmm(const SpmmArgs &a, int slab, hipStream_t s, bool bf16 = false);
 
 void plan_long_rows(const uint64_t *ptr, uint32_t N, LongRowsHost *out);
 hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float *partial /*nchunks x ld*/, hipStream_t s, bool bf16 = false);
@@ -336,30 +337,47 @@ hipError_t build_blocked_sweep(const uint64_t *ptr, const uint32_t *idx, const f
                                BlockedAdj *out, hipStream_t s, uint32_t layout = 3 /* 1: spread sources, 2: deal rows by degree */,
                                uint32_t sweep_tiles = 32 /* workgroups per sweep and XCD the deal is made for */,
                                uint32_t loader_relief = 0 /* rows per sweep kept off the two lane groups of every workgroup's wave 0 */);
-int sweep_pick_r(uint32_t N, int group, uint32_t G, int force_r = 0 /* option spmm_sweep_rows: 0 = by fill */, int max_r = 10);
 // host/sweep_deal.cpp: rows per lane group of the K1s layout and the position of every (sorted) item
 bool sweep_deal_plan(uint32_t nl, uint32_t R, uint32_t sweep_tiles, std::vector<uint32_t> *cap, uint32_t *npos, uint32_t loader_relief = 0);
 bool sweep_deal_positions(uint32_t nl, uint32_t R, const std::vector<uint32_t> &cap, uint32_t *pos, uint32_t loader_lo = 0);
 bool sweep_deal_balanced(uint32_t nl, uint32_t R, const std::vector<uint32_t> &cap, const uint64_t *w, uint32_t *pos);
+// host/sweep_geometry.cpp: the rows per lane group of a launch on the sweep skeleton, and the geometry that follows from them
+int sweep_pick_r(uint32_t N, int group, uint32_t G, int force_r = 0 /* option spmm_sweep_rows: 0 = by fill */, int max_r = 10);
+// K1s's row rule: the rows a launch on `group` lanes walks on a layout dealt for rows_per_group (the wide form: ask for 16 lanes)
+int sweep_rows(uint32_t rows_per_group, uint32_t npos, int group, uint32_t G, int force_r /* option spmm_sweep_rows */);
+bool sweep_wide_rows_ok(int R);   // K1s's wide form has kernels for R rows per 16-lane group
+SweepGeometry sweep_geometry(uint32_t npos, uint32_t ld, int group, int R, bool wide, uint32_t G);
+size_t sweep_counter_bytes(const SweepGeometry &g, uint32_t nblocks);   // what a launch over nblocks source blocks clears
+// ... and the bound callers size the counters by: any launch of that shape, whatever it leaves to concurrent kernels
+size_t sweep_counter_bound(uint32_t npos, uint32_t ld, int group, int R, bool wide, uint32_t G, uint32_t nblocks);
 bool sweep_supported(const SpmmArgs &a, const BlockedAdj &B, int group);
 // per-context knobs and state of the K1s launches (nothing process-wide)
 struct SweepCtl {
-    int force_r = 0;            // option spmm_sweep_rows
     int pair = -1;              // option spmm_sweep_pair
     bool loader = true;         // option spmm_sweep_loader: wave 0 of a workgroup copies the next step's entries for all (32-lane launches)
     uint32_t *stat = nullptr;   // SWEEP_STAT_WORDS device words that outlive the launches (dory_ctx::sweep_stat)
 };
 constexpr int SWEEP_STAT_WORDS = 8;
-// wide: the launch's form on bf16 rows with eight features per lane (option gcn_bf16_wide; spmm.hip: spmm_sweep_bf16x8_kernel) --
-// 16-lane groups on 128-feature slabs whatever `group`; sweep_wide_applies: rows of 128 floats or more and an instantiated row count
-bool sweep_wide_applies(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, int force_r);
-size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, uint32_t nblocks, int force_r = 0, bool wide = false);
-hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, const float *row_scale, uint32_t cus_per_xcd,
-                             uint32_t b_lo, uint32_t b_hi, uint32_t *done /* sweep_scratch_bytes() */, hipStream_t s,
-                             const SweepCtl &ctl, uint32_t flags = 0, float *split_partial = nullptr /* B.nslots x ld floats */,
-                             uint32_t reserve_cus = 0 /* CUs per XCD left to concurrent kernels */,
-                             bool bf16 = false /* bf16 source rows (launch_spmm), no row_scale */,
-                             bool wide = false /* bf16 rows, eight features per lane: where sweep_wide_applies() */);
+// One launch on the sweep skeleton over the blocks [b_lo, b_hi) of a sweep layout: what K1s's launcher and those of the multi-head
+// GAT's edge passes take alike (abi_stages.hip: SweepLaunch hands them out; sweep_core.hpp: sweep_plan turns one into a launch)
+struct SweepPart {
+    uint32_t cus;            // workgroups per sweep and XCD
+    uint32_t b_lo, b_hi;     // the blocks of the sweep layout this launch walks
+    bool accumulate;         // the second launch of an aggregation: go on from the sums the first left (the ghost blocks of a partitioned run)
+    uint32_t reserve;        // CUs per XCD left to concurrent kernels (an exchange in flight)
+    int R;                   // rows per lane group: the actual count (sweep_rows, gatmh_sweep_rows), one that has a kernel
+    uint32_t *done;          // gate counters: sweep_counter_bytes() of device memory
+    SweepCtl ctl;
+    uint32_t flags;          // SweepArgs::flags but 2 and 32, which follow from accumulate and reserve
+    hipStream_t s;
+    bool bf16;               // the rows gathered are bf16 rows of ld elements (launch_bf16_rows; options gcn_bf16_gather, gatmh_bf16_gather)
+    bool wide;               // bf16 rows, eight features per lane on 16-lane groups (options gcn_bf16_wide, gatmh_bf16_wide)
+};
+// K1s's wide form (spmm_sweep_bf16x8_kernel): rows of 128 floats or more, 16-lane groups on 128-feature slabs whatever `group`,
+// R16 = sweep_rows(.., 16, ..) rows
+inline bool sweep_wide_applies(uint32_t ld, int group, int R16) { return ld >= 128 && (group == 16 || group == 32) && sweep_wide_rows_ok(R16); }
+// out (+)= self + (row_scale *) sum over the source blocks of p; bf16 rows take no row_scale; split_partial: B.nslots x ld floats
+hipError_t launch_spmm_sweep(SpmmArgs a, const BlockedAdj &B, int group, const float *row_scale, float *split_partial, const SweepPart &p);
 hipError_t launch_spmm_sweep_combine(const SpmmArgs &a, const BlockedAdj &B, const float *row_scale, const float *split_partial,
                                      hipStream_t s, bool bf16 = false);
 // fp32 -> bf16 (round to nearest even) of n elements, n a multiple of 4: the rows an aggregation reads under options
@@ -489,21 +507,9 @@ constexpr int GATMH_WIDE_GROUP = 16, GATMH_WIDE_ROWS = 2;
 size_t gatmh_sweep_scratch_bytes(const BlockedAdj &S, uint32_t N, uint32_t ld, uint32_t ldk);
 hipError_t launch_gatmh_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *el,
                                     const float *elg, float *scratch, hipStream_t s);
-// what the launches of the forward and of the source-side pass take alike
-struct GatSweepPart {
-    uint32_t cus;            // workgroups per sweep and XCD
-    uint32_t b_lo, b_hi;     // the blocks of the sweep layout this launch walks
-    bool accumulate;         // go on from the sums an earlier launch left (the ghost blocks of a partitioned run)
-    uint32_t *done;          // gate counters
-    SweepCtl ctl;
-    uint32_t flags;
-    hipStream_t s;
-    bool bf16;               // the rows gathered are bf16 rows of ld elements (launch_bf16_rows; option gatmh_bf16_gather)
-    bool wide;               // bf16 rows, eight features per lane (option gatmh_bf16_wide): where gatmh_wide_applies()
-};
 hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
-                                           float *scratch, const GatSweepPart &p, const float *el, const float *elg /* the sources' scores (local, ghost rows) */);
+                                           float *scratch, const SweepPart &p, const float *el, const float *elg /* the sources' scores (local, ghost rows) */);
 hipError_t launch_gatmh_forward_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                              const uint32_t *rowidx, const BlockedAdj &S, const float *z, const float *zg, const float *el,
                                              const float *elg, const float *er, float *o, float *op, float *m, float *den, float *dpos,
@@ -516,7 +522,7 @@ size_t gatmh_src_sweep_scratch_bytes(const BlockedAdj &S, uint32_t N, uint32_t G
 hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                         const float4 *st4, const float4 *stg, uint32_t lds4, float *scratch, hipStream_t s);
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
-                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, const GatSweepPart &p);
+                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, const SweepPart &p);
 hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S, const float *z,
                                          const float *el, const float *d_o, const float *der, const float *a_l, const float *a_r, float *del,
                                          float *dz, float *scratch, hipStream_t s,

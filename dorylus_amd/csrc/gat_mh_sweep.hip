@@ -770,55 +770,29 @@ hipError_t launch_gatmh_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t
     return hipGetLastError();
 }
 
-// What a launch of either edge pass is made of, decided once: the lane group, the lanes per head and the rows per group of its kernel,
-// the skeleton's arguments and geometry over the source blocks [p.b_lo, p.b_hi) of the sweep layout S (as launch_spmm_sweep), the
-// gate counters cleared.  pass: 0 forward, 1 source side; xl / xg / out: the rows gathered (local, ghost) and the main sums
-struct GatSweepPlan {
-    int group, HL, R;
-    SpmmArgs a;
-    SweepArgs w;
-    dim3 grid;
-};
-static hipError_t gatmh_sweep_plan(const GatSweepPart &p, int pass, uint32_t N, uint32_t K, uint32_t D, uint32_t ld, const BlockedAdj &S,
+// What a launch of either edge pass is made of, decided once: the lane group and the lanes per head of its kernel, and the skeleton's
+// plan (sweep_plan) over the source blocks [p.b_lo, p.b_hi) of the sweep layout S for the p.R rows per group the kernel holds.
+// xl / xg / out: the rows gathered (local, ghost) and the main sums
+struct GatSweepPlan : SweepPlan { int group, HL, R; SpmmArgs a; };
+static hipError_t gatmh_sweep_plan(const SweepPart &p, uint32_t N, uint32_t K, uint32_t D, uint32_t ld, const BlockedAdj &S,
                                    const float *xl, const float *xg, float *out, float *pieces, GatSweepPlan *pl) {
     if (p.wide && !(p.bf16 && gatmh_wide_applies(K, D, ld))) return hipErrorInvalidValue;
-    const int group = pl->group = p.wide ? GATMH_WIDE_GROUP : gatmh_sweep_group(ld);
+    pl->group = p.wide ? GATMH_WIDE_GROUP : gatmh_sweep_group(ld);
     pl->HL = p.wide ? (int)(D / 8) : gatmh_sweep_hl(K, D, ld);
-    const int R = pl->R = p.wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(S, group, pl->HL, pass);
+    pl->R = p.R;
     SpmmArgs &a = pl->a = SpmmArgs{};
     a.N = N; a.F = K * D; a.ld = ld; a.xl = xl; a.xg = xg; a.out = out; a.accumulate = p.accumulate ? 1 : 0; a.self_mode = 0;
-    if (!pl->HL || (R != 2 && R != 4)) return hipErrorInvalidValue;   // (the rows per group that have kernels)
-    if (!sweep_supported(a, S, group) || p.b_hi > S.nb || p.cus == 0 || p.cus > 32 || !p.ctl.stat) return hipErrorInvalidValue;
-    if (p.b_lo < S.nb_local && p.b_hi > S.nb_local) return hipErrorInvalidValue;
-    if (p.b_lo >= S.nb_local && !a.xg) return hipErrorInvalidValue;
-    const uint32_t RW = (uint32_t)(SWEEP_NT / group) * R;
-    SweepArgs &w = pl->w = SweepArgs{};
-    w.rpx = ((S.npos + 7) / 8 + R - 1) / R * R;
-    w.tiles_x = (w.rpx + RW - 1) / RW;
-    w.G = p.cus;
-    const uint32_t spp = (w.tiles_x + p.cus - 1) / p.cus;
-    const uint32_t slabs = ((ld >> (p.wide ? 3 : 2)) + group - 1) / group;   // wide: chunks of eight features -- the same 128-feature slabs on 16-lane groups
-    w.nsweeps = slabs * spp;
-    w.b_lo = p.b_lo; w.b_hi = p.b_hi;
-    w.done = p.done;
-    w.flags = p.flags | (p.accumulate ? 2u : 0u);
-    w.split_partial = pieces;
-    w.stat = p.ctl.stat;
-    pl->grid = dim3(8u * slabs * spp * p.cus);
-    return hipMemsetAsync(p.done, 0, ((size_t)8 * w.nsweeps * (p.b_hi - p.b_lo) * 32 + 1) * sizeof(uint32_t), p.s);
+    // (the rows per group that have kernels: 2 and 4, the wide forms GATMH_WIDE_ROWS)
+    if (!pl->HL || (p.wide ? p.R != GATMH_WIDE_ROWS : (p.R != 2 && p.R != 4))) return hipErrorInvalidValue;
+    return sweep_plan(a, S, pl->group, p, pieces, pl);
 }
 
-// The kernels that are instantiated, all with the loader wave.  gatmh_pick: f(V as a compile-time constant) for the one of V... that v
-// equals; false: none does.  Narrow forms: GROUP 16 / 32 x HL 2 / 4 / 8 / 16 x R 2 / 4, f(G, H, R).  Wide forms: HL 2 / 4 / 8 (two rows per
-// 16-lane group: gatmh_sweep_plan gives a wide launch no other)
-template <int... V, class F>
-static bool gatmh_pick(int v, F f) {
-    return ((v == V && f(std::integral_constant<int, V>{})) || ...);
-}
+// The kernels that are instantiated, all with the loader wave (sweep_pick: sweep_core.hpp).  Narrow forms: GROUP 16 / 32 x HL 2 / 4 / 8 /
+// 16 x R 2 / 4, f(G, H, R).  Wide forms: HL 2 / 4 / 8 (two rows per 16-lane group: gatmh_sweep_plan admits no other)
 template <class F>
 static bool gatmh_narrow_form(const GatSweepPlan &pl, F f) {
-    return gatmh_pick<16, 32>(pl.group, [&](auto G) {
-        return gatmh_pick<2, 4, 8, 16>(pl.HL, [&](auto H) { return gatmh_pick<2, 4>(pl.R, [&](auto R) { return f(G, H, R); }); });
+    return sweep_pick<16, 32>(pl.group, [&](auto G) {
+        return sweep_pick<2, 4, 8, 16>(pl.HL, [&](auto H) { return sweep_pick<2, 4>(pl.R, [&](auto R) { return f(G, H, R); }); });
     });
 }
 
@@ -826,14 +800,14 @@ static bool gatmh_narrow_form(const GatSweepPlan &pl, F f) {
 // first, then the ghost blocks with accumulate = true)
 hipError_t launch_gatmh_forward_sweep_part(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                            const float *z, const float *zg, const float *er, const float *a_l, float *o, float *op,
-                                           float *scratch, const GatSweepPart &p, const float *el, const float *elg) {
+                                           float *scratch, const SweepPart &p, const float *el, const float *elg) {
     if (N == 0 || p.b_lo >= p.b_hi) return hipSuccess;
     const GatSweepScratch c = gatmh_carve(scratch, S, N, ld, ldk);
     GatSweepPlan pl;
-    const hipError_t e = gatmh_sweep_plan(p, 0, N, K, D, ld, S, z, zg, o, c.pieces, &pl);
+    const hipError_t e = gatmh_sweep_plan(p, N, K, D, ld, S, z, zg, o, c.pieces, &pl);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
-    const bool found = p.wide ? gatmh_pick<2, 4, 8>(pl.HL, [&](auto H) {
+    const bool found = p.wide ? sweep_pick<2, 4, 8>(pl.HL, [&](auto H) {
         hipLaunchKernelGGL((gatmh_forward_sweep_bf16x8_kernel<H(), GATMH_WIDE_ROWS, true>), pl.grid, bl, 0, p.s, pl.a, S, pl.w, er, a_l, c.keys, op, c.dacc,
                            c.pos_slots, c.den_slots, K, D, ldk);
         return true;
@@ -912,16 +886,16 @@ hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint
 
 // one launch over the destination blocks [p.b_lo, p.b_hi) of the sweep layout of the OUT-edges
 hipError_t launch_gatmh_src_sweep_part(uint32_t N, uint32_t G, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
-                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, const GatSweepPart &p) {
+                                       const float *d_o, const float *dog, const float *el, float *dz, float *scratch, const SweepPart &p) {
     if (N == 0 || p.b_lo >= p.b_hi) return hipSuccess;
     // the statistics records through their buffer resource: 32-bit byte offsets, record id x row bytes in 24 x 24 bits
     if ((uint64_t)(N > G ? N : G) * K * 16u >= (1ull << 32) || K * 16u >= (1u << 24)) return hipErrorInvalidValue;
     const GatSrcScratch c = gatmh_src_carve(scratch, S, N, K, ld, ldk);
     GatSweepPlan pl;
-    const hipError_t e = gatmh_sweep_plan(p, 1, N, K, D, ld, S, d_o, dog, dz, c.pieces, &pl);
+    const hipError_t e = gatmh_sweep_plan(p, N, K, D, ld, S, d_o, dog, dz, c.pieces, &pl);
     if (e != hipSuccess) return e;
     const dim3 bl(SWEEP_NT);
-    const bool found = p.wide ? gatmh_pick<2, 4, 8>(pl.HL, [&](auto H) {
+    const bool found = p.wide ? sweep_pick<2, 4, 8>(pl.HL, [&](auto H) {
         hipLaunchKernelGGL((gatmh_src_sweep_bf16x8_kernel<H(), GATMH_WIDE_ROWS, true>), pl.grid, bl, 0, p.s, pl.a, S, pl.w, el, c.stx, c.stxg, c.sp, c.tacc,
                            c.pos_slots, c.t_slots, K, D, ldk, G);
         return true;

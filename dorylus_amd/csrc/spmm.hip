@@ -256,10 +256,8 @@ hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float 
     return hipGetLastError();
 }
 
-// variant 0 = auto.  slab = floats per feature slab (0 = whole row in one pass
-// where it fits 4 chunks per lane).
-hipError_t launch_spmm(const SpmmArgs &a, int variant, int slab, hipStream_t s, bool bf16) {
-    (void)variant;
+// slab = floats per feature slab (0 = whole row in one pass where it fits 4 chunks per lane).
+hipError_t launch_spmm(const SpmmArgs &a, int slab, hipStream_t s, bool bf16) {
     if (a.ld & 3) return hipErrorInvalidValue;
     uint32_t width = a.ld;                  // floats handled by one block pass
     if (slab > 0 && (uint32_t)slab < width) width = (uint32_t)slab;
@@ -658,26 +656,6 @@ hipError_t build_blocked_sweep(const uint64_t *ptr, const uint32_t *idx, const f
     return hipSuccess;
 }
 
-// rows per lane group: the choice that leaves the fewest idle workgroup slots in the last sweep of a slab;
-// force_r (option spmm_sweep_rows of the context; tests, experiments): 0 = pick by fill
-int sweep_pick_r(uint32_t N, int group, uint32_t G, int force_r, int max_r) {
-    if (force_r == 2 || force_r == 4 || force_r == 6 || force_r == 8 || (force_r == 10 && group == 32 && max_r >= 10) ||
-        ((force_r == 3 || force_r == 5) && group == 16))
-        return force_r;
-    const uint32_t rpx = (N + 7) / 8;
-    int best = 8;
-    double best_fill = 0;
-    for (int R : {10, 8, 6, 4, 2}) {            // few rows per group: small partitions (one of 8 ranks) still fill every CU
-        if ((group == 16 && R == 10) || R > max_r) continue;   // 16-lane groups stage twice the entries per lane: 10 rows would spill
-        const uint32_t RW = (uint32_t)(SWEEP_NT / group) * R;
-        const uint32_t tiles = (rpx + RW - 1) / RW;
-        const uint32_t spp = (tiles + G - 1) / G;
-        const double fill = (double)rpx / ((double)spp * G * RW);
-        if (fill > best_fill + 0.02) { best_fill = fill; best = R; }
-    }
-    return best;
-}
-
 bool sweep_supported(const SpmmArgs &a, const BlockedAdj &B, int group) {
     // source rows are addressed through a buffer resource: 32-bit byte offsets, row id x row bytes in 24 x 24 bits
     const uint64_t row_b = (uint64_t)a.ld * 4u;
@@ -686,112 +664,62 @@ bool sweep_supported(const SpmmArgs &a, const BlockedAdj &B, int group) {
     return (group == 16 || group == 32) && !(a.ld & 3) && B.nb > 0 && B.nchunks == 0 && a.N >= 8 && B.npos >= 8 && addr_ok;
 }
 
-// rows per lane group of a launch: what the layout was dealt for, unless forced (option) or not instantiated for the
-// lane-group width
-static int sweep_rows_for(const BlockedAdj &B, int group, uint32_t G, int force_r) {
-    const int forced = sweep_pick_r(0, group, G, force_r, 10);      // (returns the forced value whatever N when one is valid)
-    if (force_r && forced == force_r) return forced;
-    // (16-lane groups stage twice the entries per lane: eight rows spill two registers into the chain LDS -> gathers -> sums;
-    // a spilling variant is not launched unless an option forces it -- tests/test_kernel_resources.py)
-    // 16-lane launches (64-float rows) have twice the lane groups per workgroup: half the layout's rows per group walks the
-    // rows per workgroup and step the layout was dealt for, and leaves registers for the loader wave (round 5: the 64-float
-    // aggregations of the GAT prototype 2.00 -> see DESIGN; 6 rows without the loader was the round-4 form)
-    if (B.rows_per_group && group == 16) return std::max<int>(2, (int)B.rows_per_group / 2);
-    if (B.rows_per_group && group == 32) return (int)B.rows_per_group;
-    return sweep_pick_r(B.npos, group, G, 0, 10);
-}
-
-// does a launch on bf16 rows take the wide form (eight features per lane on 16-lane groups: spmm_sweep_bf16x8_kernel)?  Rows of
-// 128 floats or more, a layout whose 16-lane row count is instantiated (2 .. 5: a forced 6 or 8 keeps the narrow form)
-bool sweep_wide_applies(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, int force_r) {
-    if (ld < 128 || (group != 16 && group != 32)) return false;
-    const int R = sweep_rows_for(B, 16, G, force_r);
-    return R >= 2 && R <= 5;
-}
-
-// counter words one launch over nblocks source blocks needs (callers size the scratch for the largest launch)
-size_t sweep_scratch_bytes(const BlockedAdj &B, uint32_t ld, int group, uint32_t G, uint32_t nblocks, int force_r, bool wide) {
-    if (wide) group = 16;                          // (the wide form: 16-lane groups, chunks of eight features)
-    const int R = sweep_rows_for(B, group, G, force_r);
-    const uint32_t RW = (uint32_t)(SWEEP_NT / group) * R;
-    const uint32_t Gmin = G > 12 ? G - 8 : G;      // launches may leave up to 8 CUs per XCD to concurrent kernels
-    const uint32_t rpx = (B.npos + 7) / 8 + 16, tiles = (rpx + RW - 1) / RW + 1, spp = (tiles + Gmin - 1) / Gmin;
-    const uint32_t slabs = ((ld >> (wide ? 3 : 2)) + group - 1) / group;
-    return ((size_t)8 * slabs * spp * nblocks * 32 + 1) * sizeof(uint32_t);
-}
-
-// out (+)= self + (row_scale *) sum over source blocks [b_lo, b_hi); `done` = sweep_scratch_bytes() of device memory
-hipError_t launch_spmm_sweep(const SpmmArgs &a, const BlockedAdj &B, int group, const float *row_scale, uint32_t cus,
-                             uint32_t b_lo, uint32_t b_hi, uint32_t *done, hipStream_t s, const SweepCtl &ctl, uint32_t flags,
-                             float *split_partial, uint32_t reserve, bool bf16, bool wide) {
-    if (a.N == 0 || a.ld == 0 || b_lo >= b_hi) return hipSuccess;
-    if (bf16 && row_scale) return hipErrorInvalidValue;   // bf16 rows: the GCN aggregations (edge weights) only
-    if (!sweep_supported(a, B, group) || b_hi > B.nb || cus == 0 || cus > 32 || !ctl.stat) return hipErrorInvalidValue;
-    if (wide && (!bf16 || (a.ld & 7) || !sweep_wide_applies(B, a.ld, group, cus, ctl.force_r))) return hipErrorInvalidValue;
-    if (wide) group = 16;
-    if (b_lo < B.nb_local && b_hi > B.nb_local) return hipErrorInvalidValue;   // one source array per launch
-    if (b_lo >= B.nb_local && !a.xg) return hipErrorInvalidValue;
-    const int R = sweep_rows_for(B, group, cus, ctl.force_r);
+hipError_t sweep_plan(const SpmmArgs &a, const BlockedAdj &B, int group, const SweepPart &p, float *split_partial, SweepPlan *pl) {
+    if (!sweep_supported(a, B, group) || p.b_hi > B.nb || p.cus == 0 || p.cus > 32 || !p.ctl.stat) return hipErrorInvalidValue;
+    if (p.b_lo < B.nb_local && p.b_hi > B.nb_local) return hipErrorInvalidValue;   // one source array per launch
+    if (p.b_lo >= B.nb_local && !a.xg) return hipErrorInvalidValue;
     // A sweep is the workgroups that must be resident on an XCD together; each takes a whole CU (all its registers).
     // While other kernels hold CUs (the exchange's RCCL kernels under the local-source launch) fewer fit: a smaller
     // sweep leaves them room -- the surplus workgroups of the next sweep simply wait at their first gates.
-    const uint32_t G = cus > 12 ? cus - std::min<uint32_t>(reserve, 8u) : cus;
-    SweepArgs w{};
-    const uint32_t RW = (uint32_t)(SWEEP_NT / group) * R;
-    w.rpx = ((B.npos + 7) / 8 + R - 1) / R * R;   // whole lane groups per XCD
-    w.tiles_x = (w.rpx + RW - 1) / RW;
-    w.G = G;
-    const uint32_t spp = (w.tiles_x + G - 1) / G;
-    const uint32_t slabs = ((a.ld >> (wide ? 3 : 2)) + group - 1) / group;
-    w.nsweeps = slabs * spp;
-    w.b_lo = b_lo; w.b_hi = b_hi;
-    w.done = done;
-    w.flags = flags | (reserve ? 32u : 0u);
-    w.split_partial = split_partial;
-    w.stat = ctl.stat;
+    const uint32_t G = p.cus > 12 ? p.cus - std::min<uint32_t>(p.reserve, 8u) : p.cus;
+    const SweepGeometry g = sweep_geometry(B.npos, a.ld, group, p.R, p.wide, G);
+    const uint32_t flags = p.flags | (p.accumulate ? 2u : 0u) | (p.reserve ? 32u : 0u);
+    *pl = SweepPlan{SweepArgs{g.rpx, g.tiles_x, G, g.nsweeps, p.b_lo, p.b_hi, p.done, flags, split_partial, p.ctl.stat}, dim3(g.grid_x), g.slabs};
+    return hipMemsetAsync(p.done, 0, sweep_counter_bytes(g, p.b_hi - p.b_lo), p.s);
+}
+
+// The narrow forms that are instantiated: GROUP 32 x R 2 / 4 / 6 / 8 / 10, GROUP 16 x R 2 / 3 / 4 / 5 / 6 / 8 (16-lane groups stage
+// twice the entries per lane: ten rows would spill; 3 and 5: a 6- or 10-row layout on 64-float rows), f(GROUP, R)
+template <class F>
+static bool k1s_narrow_form(int group, int R, F f) {
+    if (group == 32) return sweep_pick<2, 4, 6, 8, 10>(R, [&](auto RR) { return f(std::integral_constant<int, 32>{}, RR); });
+    return group == 16 && sweep_pick<2, 3, 4, 5, 6, 8>(R, [&](auto RR) { return f(std::integral_constant<int, 16>{}, RR); });
+}
+
+// one launch over the source blocks of p; a second launch (p.accumulate) adds to the first one's sums: no self term again
+hipError_t launch_spmm_sweep(SpmmArgs a, const BlockedAdj &B, int group, const float *row_scale, float *split_partial, const SweepPart &p) {
+    if (a.N == 0 || a.ld == 0 || p.b_lo >= p.b_hi) return hipSuccess;
+    if (p.bf16 && row_scale) return hipErrorInvalidValue;   // bf16 rows: the GCN aggregations (edge weights) only
+    if (p.wide && (!p.bf16 || (a.ld & 7) || !sweep_wide_applies(a.ld, group, p.R))) return hipErrorInvalidValue;
     if (B.nslots && !split_partial) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(done, 0, ((size_t)8 * w.nsweeps * (b_hi - b_lo) * 32 + 1) * sizeof(uint32_t), s);
+    if (p.accumulate) { a.self_mode = 0; a.accumulate = 1; }
+    SweepPlan pl;
+    const hipError_t e = sweep_plan(a, B, group, p, split_partial, &pl);
     if (e != hipSuccess) return e;
-    const dim3 gr(8u * slabs * spp * G), bl(SWEEP_NT);
+    const dim3 bl(SWEEP_NT);
     const bool unit = row_scale != nullptr;
     // rows in pairs (one stream of entries per two rows) pay on launches of several slabs (five slabs, F=602: 13.8 ->
     // 13.3 ms; four: 11.0 -> 10.8; three: 8.16 -> 8.1), not on one or two (F=128: 2.70 -> 2.78; F=256: 5.43 -> 5.46);
     // ctl.pair (option spmm_sweep_pair): -1 = that rule, 0 / 1 = forced (experiments)
-    if (wide) {   // one form per row count and loader setting, weighted, rows never in pairs
-#define SWEEP_LAUNCH_W(RR)                                                                                             \
-    do {                                                                                                               \
-        if (ctl.loader) hipLaunchKernelGGL((spmm_sweep_bf16x8_kernel<RR, true>), gr, bl, 0, s, a, B, w);               \
-        else hipLaunchKernelGGL((spmm_sweep_bf16x8_kernel<RR, false>), gr, bl, 0, s, a, B, w);                         \
-    } while (0)
-        if (R == 5) SWEEP_LAUNCH_W(5); else if (R == 4) SWEEP_LAUNCH_W(4); else if (R == 3) SWEEP_LAUNCH_W(3); else SWEEP_LAUNCH_W(2);
-#undef SWEEP_LAUNCH_W
-        return hipGetLastError();
-    }
-    const bool pair = (R & 1) ? false : (ctl.pair < 0 ? slabs >= 3 : ctl.pair != 0);   // (odd R: 16-lane launches on a 6- or 10-row layout)
-#define SWEEP_LAUNCH_L(GRP, RR, LD)                                                                                    \
-    do {                                                                                                               \
-        if (bf16) { if (pair) hipLaunchKernelGGL((spmm_sweep_bf16_kernel<GRP, RR, false, true, LD>), gr, bl, 0, s, a, B, row_scale, w); \
-                    else hipLaunchKernelGGL((spmm_sweep_bf16_kernel<GRP, RR, false, false, LD>), gr, bl, 0, s, a, B, row_scale, w); } \
-        else if (unit) { if (pair) hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, true, true, LD>), gr, bl, 0, s, a, B, row_scale, w);   \
-                    else hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, true, false, LD>), gr, bl, 0, s, a, B, row_scale, w); }   \
-        else { if (pair) hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, false, true, LD>), gr, bl, 0, s, a, B, row_scale, w);       \
-               else hipLaunchKernelGGL((spmm_sweep_kernel<GRP, RR, false, false, LD>), gr, bl, 0, s, a, B, row_scale, w); }       \
-    } while (0)
-#define SWEEP_LAUNCH(GRP, RR)                                                                                          \
-    do {                                                                                                               \
-        if (ctl.loader) SWEEP_LAUNCH_L(GRP, RR, true); else SWEEP_LAUNCH_L(GRP, RR, false);                            \
-    } while (0)
-#define SWEEP_LAUNCH_R(GRP)                                                                                            \
-    do {                                                                                                               \
-        if (R == 8) SWEEP_LAUNCH(GRP, 8); else if (R == 6) SWEEP_LAUNCH(GRP, 6); else if (R == 4) SWEEP_LAUNCH(GRP, 4);  \
-        else SWEEP_LAUNCH(GRP, 2);                                                                                     \
-    } while (0)
-    if (group == 32) { if (R == 10) SWEEP_LAUNCH(32, 10); else SWEEP_LAUNCH_R(32); }
-    else { if (R == 5) SWEEP_LAUNCH(16, 5); else if (R == 3) SWEEP_LAUNCH(16, 3); else SWEEP_LAUNCH_R(16); }
-#undef SWEEP_LAUNCH_R
-#undef SWEEP_LAUNCH
-#undef SWEEP_LAUNCH_L
-    return hipGetLastError();
+    const bool pair = (p.R & 1) ? false : (p.ctl.pair < 0 ? pl.slabs >= 3 : p.ctl.pair != 0);   // (odd R: 16-lane launches on a 6- or 10-row layout)
+    // wide: one form per row count (2 .. 5) and loader setting, weighted, rows never in pairs.  Narrow: each (GROUP, R) with and
+    // without the loader wave and rows in pairs, on fp32 rows with and without the row factor
+    const bool found = p.wide ? sweep_pick<2, 3, 4, 5>(p.R, [&](auto R) {
+        return sweep_pick<0, 1>(p.ctl.loader, [&](auto L) {
+            hipLaunchKernelGGL((spmm_sweep_bf16x8_kernel<R(), L() != 0>), pl.grid, bl, 0, p.s, a, B, pl.w);
+            return true;
+        });
+    }) : k1s_narrow_form(group, p.R, [&](auto G, auto R) {
+        return sweep_pick<0, 1>(p.ctl.loader, [&](auto L) {
+            return sweep_pick<0, 1>(pair, [&](auto P) {
+                hipLaunchKernelGGL((p.bf16 ? spmm_sweep_bf16_kernel<G(), R(), false, P() != 0, L() != 0>
+                                    : unit ? spmm_sweep_kernel<G(), R(), true, P() != 0, L() != 0>
+                                           : spmm_sweep_kernel<G(), R(), false, P() != 0, L() != 0>), pl.grid, bl, 0, p.s, a, B, row_scale, pl.w);
+                return true;
+            });
+        });
+    });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ---- diagnostic: hold CUs the way a concurrent kernel (an exchange's RCCL kernels, a co-tenant) would -----------------

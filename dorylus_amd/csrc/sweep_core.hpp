@@ -11,7 +11,6 @@
 
 namespace dory {
 
-constexpr int SWEEP_NT = 1024;
 constexpr int SWEEP_C = 128;             // staged (idx,val) pairs per lane group and pass
 constexpr int SWEEP_U = 4;               // gathers per batch
 constexpr int SWEEP_SLACK = 1;           // start step b when all finished b - SWEEP_SLACK - 1
@@ -44,6 +43,20 @@ struct SweepArgs {
                          // on every replay: a kernel argument would be frozen at recording time and a back-off could
                          // never end.
 };
+
+// What a launch is made of, decided once for K1s and the multi-head GAT's edge passes alike (spmm.hip): refuses a part the skeleton
+// cannot run (sweep_supported; blocks past the layout's or on both sides of nb_local -- one source array per launch; ghost blocks
+// without a.xg; no CUs, more than 32; no statistics words), fills the skeleton's arguments and the grid from sweep_geometry() for the
+// p.R rows per lane group the caller's kernel holds, and clears the gate counters.
+struct SweepPlan { SweepArgs w; dim3 grid; uint32_t slabs; };
+hipError_t sweep_plan(const SpmmArgs &a, const BlockedAdj &B, int group, const SweepPart &p, float *split_partial, SweepPlan *pl);
+
+// The dispatch over the instantiated forms: f(V as a compile-time constant) for the one of V... that v equals; false: none does --
+// a form without a kernel is the launcher's hipErrorInvalidValue, never another form's kernel.
+template <int... V, class F>
+static bool sweep_pick(int v, F f) {
+    return ((v == V && f(std::integral_constant<int, V>{})) || ...);
+}
 
 // ---- the gate and the arrival, shared by the sweep kernels ------------------------------------------------------------
 // gate: step sb may start once every workgroup of the sweep has finished step sb - SWEEP_SLACK - 1 (for the first steps:

@@ -138,6 +138,16 @@ int dory_sweep_deal(uint32_t items, uint32_t rows_per_group, uint32_t sweep_tile
 int dory_sweep_deal_weighted(uint32_t items, const uint64_t *weights, uint32_t rows_per_group, uint32_t sweep_tiles,
                              uint32_t loader_relief, uint32_t *positions_out, uint32_t *group_rows_out,
                              uint32_t *item_position);
+/* Launch introspection (tests): the geometry of one launch on the sweep skeleton -- dorylus_amd/host/sweep_geometry.cpp.  The
+ * launch walks `rows` rows per lane group (the actual count, never an option value: < 1 is refused) over `positions` positions
+ * of a layout, on rows of ld floats with `group` (16 | 32) lanes per row (wide: 16 lanes of eight features, whatever group) and
+ * `cus` workgroups per sweep and XCD.  out, 11 words: slabs, rows per XCD, workgroups per XCD and slab, sweeps per slab,
+ * sweeps, workgroups, gate counter words per source block; [7] the counter words a launch over nblocks blocks clears, [8] the
+ * bound callers size the counters by (any launch of this shape over nblocks blocks, whatever it leaves to concurrent kernels).
+ * Separately, K1s's row rule: [9] the rows a launch of this lane-group width walks on a layout dealt for layout_rows rows per
+ * group under option spmm_sweep_rows = rows_option, [10] whether its 16-lane row count has a wide form.  0 = ok. */
+int dory_sweep_geometry(uint32_t positions, uint32_t ld, int group, int rows, int wide, uint32_t cus, uint32_t nblocks,
+                        uint32_t layout_rows, int rows_option, uint64_t *out);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,7 @@ def test_mirror_constants_match_the_sources():
     """if this fails a kernel was retuned: update the mirror, then look at what the case list still reaches
     (test_case_list_reaches_every_form)"""
     ctx, spmm, blk, core, stages = _src("ctx.hpp"), _src("spmm.hip"), _src("spmm_blocked.hip"), _src("sweep_core.hpp"), _src("abi_stages.hip")
+    geo, rows = _src("sweep_geometry.hpp"), _src("../host/sweep_geometry.cpp")
     m = re.search(r"constexpr uint32_t LONG_ROW_CLAMP = (\d+), LONG_ROW_CHUNK = (\d+);", ctx)
     assert (int(m[1]), int(m[2])) == (ar.LONG_ROW_CLAMP, ar.LONG_ROW_CHUNK)
     m = re.search(r"constexpr uint32_t BLK_SEG_CLAMP = (\d+), BLK_SEG_CHUNK = (\d+);", ctx)
@@ -104,7 +105,7 @@ def test_mirror_constants_match_the_sources():
     assert int(_one(spmm, r"constexpr uint32_t SWEEP_SPLIT = (\d+);")) == ar.SWEEP_SPLIT
     assert int(_one(spmm, r"split_deg = std::max<uint64_t>\((\d+), \(uint64_t\)SWEEP_SPLIT \* \(nnz / N \+ 1\)\);")) == ar.SWEEP_SPLIT_MIN
     assert int(_one(core, r"constexpr int SWEEP_C = (\d+);")) == ar.SWEEP_C
-    assert int(_one(core, r"constexpr int SWEEP_NT = (\d+);")) == ar.SWEEP_NT
+    assert int(_one(geo, r"constexpr int SWEEP_NT = (\d+);")) == ar.SWEEP_NT
     assert "CE = C - 1" in core                      # a pass holds SWEEP_C - 1 entries
     assert int(_one(blk, r"constexpr int BLK_ROWS = (\d+);")) == ar.BLK_ROWS
     # the "tiny" rule of both layouts, the block-count and offset-table limits
@@ -125,13 +126,14 @@ def test_mirror_constants_match_the_sources():
     last = re.search(r"\n    return launch_t<(\d+), (\d+)>\(a, s, bf16\);", spmm)
     assert table + [(None, int(last[1]), int(last[2]))] == ar.K1_TABLE
     # sweep_pick_r's candidates and rules; the instantiated (GROUP, R)
-    assert [int(x) for x in _one(spmm, r"for \(int R : \{([\d, ]+)\}\)").split(",")] == ar.PICK_R
-    assert "if (fill > best_fill + 0.02) { best_fill = fill; best = R; }" in spmm
-    assert "if (B.rows_per_group && group == 16) return std::max<int>(2, (int)B.rows_per_group / 2);" in spmm
-    inst = {(32, 10)} | {(16, 5), (16, 3)} | {(g, r) for g in (16, 32) for r in (8, 6, 4, 2)}
-    assert "if (R == 10) SWEEP_LAUNCH(32, 10); else SWEEP_LAUNCH_R(32);" in spmm
-    assert "if (R == 5) SWEEP_LAUNCH(16, 5); else if (R == 3) SWEEP_LAUNCH(16, 3); else SWEEP_LAUNCH_R(16);" in spmm
-    assert "if (R == 8) SWEEP_LAUNCH(GRP, 8); else if (R == 6) SWEEP_LAUNCH(GRP, 6); else if (R == 4) SWEEP_LAUNCH(GRP, 4);" in spmm
+    assert [int(x) for x in _one(rows, r"for \(int R : \{([\d, ]+)\}\)").split(",")] == ar.PICK_R
+    assert "if (fill > best_fill + 0.02) { best_fill = fill; best = R; }" in rows
+    assert "if (rows_per_group && group == 16) return std::max<int>(2, (int)rows_per_group / 2);" in rows
+    inst = set()
+    for g in (32, 16):   # k1s_narrow_form: the row counts each lane-group width is instantiated for
+        picked = _one(spmm, r"group == %d\)? (?:return|&&) sweep_pick<([\d, ]+)>\(R, \[&\]\(auto RR\) \{ return f\(std::integral_constant<int, %d>" % (g, g))
+        inst |= {(g, int(r)) for r in picked.split(",")}
+    assert inst == {(32, 10)} | {(16, 5), (16, 3)} | {(g, r) for g in (16, 32) for r in (8, 6, 4, 2)}
     assert inst == set(ar.K1S_FORMS)
     assert int(_one(_src("abi_context.hip"), r'c->opt\["spmm_sweep_loader_relief"\] = (\d+);')) == ar.LOADER_RELIEF
     # the defaults of the options the mirror reads

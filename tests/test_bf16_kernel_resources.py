@@ -1,7 +1,7 @@
 """Register budget of the bf16-row aggregation kernels (option gcn_bf16_gather), read from the code objects inside the built
 library as tests/test_kernel_resources.py reads the fp32 ones (no GPU needed).  The bf16 sweeps run on the same one
 1024-thread workgroup per CU: every variant stays at 128 registers or fewer, and the variants the launcher selects by
-default (sweep_rows_for, the loader wave on 32-lane launches) do not spill."""
+default (sweep_rows, the loader wave on 32-lane launches) do not spill."""
 from test_kernel_resources import _kernels, _tparams
 
 

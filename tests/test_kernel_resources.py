@@ -2,7 +2,7 @@
 
 Why this is a test: the gated sweeps run one 1024-thread workgroup per CU (128 registers per lane) and their inner chain is
 LDS -> gathers -> sums; a spilled register there is a dependent scratch access per step.  The launchers therefore only
-select variants that hipcc allocates without spills (gatmh_sweep_rows, sweep_rows_for) -- a toolchain or code change that
+select variants that hipcc allocates without spills (gatmh_sweep_rows, sweep_rows) -- a toolchain or code change that
 makes one of them spill, or pushes one past 128 registers, must fail here and not show up as a slower epoch."""
 import os
 import re
@@ -67,7 +67,7 @@ def test_selectable_sweep_variants_do_not_spill():
         p = _tparams(name, "spmm_sweep_kernel")
         if p:   # GROUP, R, UNIT, PAIR, LOADER: the default launches = loader wave on 32 lanes, rows in pairs only with it,
             group, r, unit, pair, loader = p   # no pairs on 16 lanes (they need three slabs: 32-lane tensors)
-            default = (group == 32 and loader == 1) or (group == 16 and pair == 0 and r <= 6)   # (sweep_rows_for: six rows at most on 16 lanes)
+            default = (group == 32 and loader == 1) or (group == 16 and pair == 0 and r <= 6)   # (sweep_rows: six rows at most on 16 lanes)
             if default:
                 seen["k1s"] += 1
                 if spill:

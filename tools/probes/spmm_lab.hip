@@ -3,7 +3,7 @@
 // of -- or a -D switch for -- the one kernel source; there is no second copy to drift.  (Rounds 2-3 kept five generations
 // of K1s in this file; they are in the history: git log -- tools/probes/spmm_lab.hip.)  GPU box only.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude [-DSWEEP_DMA_AUX=0 ...] -c tools/probes/spmm_lab.hip -o /tmp/spmm_lab.o && \
-//   hipcc --offload-arch=gfx950 /tmp/spmm_lab.o dorylus_amd/host/sweep_deal.o -o tools/probes/spmm_lab
+//   hipcc --offload-arch=gfx950 /tmp/spmm_lab.o dorylus_amd/host/sweep_deal.o dorylus_amd/host/sweep_geometry.o -o tools/probes/spmm_lab
 //   tools/probes/spmm_lab [F=602] [deg=492] [window_rows=N] [rows_per_group=10] [window_kb=2432] [flags=0] [loader=1]
 //     window_rows < N draws every source from [0, window_rows): the L2-resident ceiling of the same kernel
 //     flags: 8 = no gates (SweepArgs::flags)
@@ -99,7 +99,7 @@ int main(int argc, char **argv) {
     a.N = N; a.F = F; a.ld = ld; a.ptr = d_ptr; a.idx = d_idx; a.val = d_val; a.self_scale = d_self; a.self_mode = 1;
     a.xl = d_x; a.xg = nullptr; a.out = d_ref;
     const double gather = (double)E * ld * 4;
-    const float t_ref = time_ms([&] { CK(launch_spmm(a, 0, 64, 0)); }, 1);     // reference: K1 row kernel
+    const float t_ref = time_ms([&] { CK(launch_spmm(a, 64, 0)); }, 1);     // reference: K1 row kernel
     printf("K1 (slab 64): %.3f ms  gather %.2f TB/s\n", t_ref, gather / t_ref / 1e9);
     std::vector<float> href((size_t)N * ld), hout((size_t)N * ld);
     CK(hipMemcpy(href.data(), d_ref, href.size() * 4, hipMemcpyDeviceToHost));
@@ -109,19 +109,19 @@ int main(int argc, char **argv) {
     BlockedAdj S{};
     CK(build_blocked_sweep(d_ptr, d_idx, d_val, N, N, E, 0, 512, window_kb << 10, R, &S, 0, 3, 32, loader ? 3u : 0u));
     uint32_t *d_done, *d_stat;
-    const size_t scratch = sweep_scratch_bytes(S, ld, 32, 32, S.nb, R);
+    const int rows = sweep_rows(S.rows_per_group, S.npos, 32, 32, R);   // (a count 32-lane groups have no kernel for: the layout's)
+    const size_t scratch = sweep_counter_bound(S.npos, ld, 32, rows, false, 32, S.nb);
     CK(hipMalloc(&d_done, scratch));
     CK(hipMalloc(&d_stat, SWEEP_STAT_WORDS * sizeof(uint32_t)));
     CK(hipMemset(d_stat, 0, SWEEP_STAT_WORDS * sizeof(uint32_t)));
     float *d_split = nullptr;
     if (S.nslots) CK(hipMalloc(&d_split, (size_t)S.nslots * ld * 4));
     SweepCtl ctl;
-    ctl.force_r = R;
     ctl.stat = d_stat;
     ctl.loader = loader;
     CK(hipMemset(d_out, 0, (size_t)N * ld * 4));
     const float t = time_ms([&] {
-        CK(launch_spmm_sweep(a, S, 32, nullptr, 32, 0, S.nb, d_done, 0, ctl, flags, d_split));
+        CK(launch_spmm_sweep(a, S, 32, nullptr, d_split, SweepPart{32, 0, S.nb, false, 0, rows, d_done, ctl, flags, 0, false, false}));
         CK(launch_spmm_sweep_combine(a, S, nullptr, d_split, 0));
     });
     CK(hipMemcpy(hout.data(), d_out, hout.size() * 4, hipMemcpyDeviceToHost));
