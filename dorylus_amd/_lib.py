@@ -121,10 +121,12 @@ def load():
         "dory_sweep_deal": [u32, u32, u32, vp, vp, vp],
         "dory_sweep_deal_weighted": [u32, vp, u32, u32, u32, vp, vp, vp],
         "dory_sweep_geometry": [u32, u32, i32, i32, i32, u32, u32, u32, i32, vp],
+        "dory_option_spec": [u32, C.POINTER(cp)] + [C.POINTER(t) for t in (i32, C.c_int64, C.c_int64, C.c_int64, i32, i32, i32)],
+        "dory_option_check": [cp, C.c_int64, i32, i32, i32, cp, C.c_size_t],
     }
     for name, args in sig.items():
-        if name in ("dory_partition_wire_order", "dory_sweep_geometry") and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook)
+        if name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check") and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -135,6 +137,33 @@ def load():
     lib.dory_formats_last_error.argtypes = []
     lib.dory_formats_last_error.restype = cp
     return lib
+
+
+OPTION, READ_ONLY, ACTION = 0, 1, 2     # option_specs()[i]["kind"]
+
+
+def option_specs(lib=None):
+    """The table of the keys of set_option / get_option (dory_option_spec; no context, no GPU): one dict per key with name, kind,
+    default, lo, hi (lo > hi: any value), gnn (-1: any model), fixed_by_graph and read (when the library reads it)."""
+    lib = lib or load()
+    specs = []
+    while True:
+        name = C.c_char_p()
+        kind, gnn, fixed, read = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        default, lo, hi = C.c_int64(), C.c_int64(), C.c_int64()
+        if lib.dory_option_spec(len(specs), C.byref(name), C.byref(kind), C.byref(default), C.byref(lo), C.byref(hi), C.byref(gnn),
+                                C.byref(fixed), C.byref(read)) != 0:
+            return specs
+        specs.append({"name": name.value.decode(), "kind": kind.value, "default": default.value, "lo": lo.value, "hi": hi.value,
+                      "gnn": gnn.value, "fixed_by_graph": bool(fixed.value), "read": read.value})
+
+
+def option_check(name, value, gnn=GCN, configured=False, has_graph=False, lib=None):
+    """What set_option(name, value) answers on a context of that state (dory_option_check): (return code, refusal text)."""
+    lib = lib or load()
+    msg = C.create_string_buffer(512)
+    rc = lib.dory_option_check(name.encode(), int(value), int(gnn), int(configured), int(has_graph), msg, len(msg))
+    return rc, msg.value.decode()
 
 
 def _ptr(a):

@@ -154,7 +154,7 @@ constexpr uint32_t LOCAL_MAX_RANKS = 16;
 
 int local_wait_posted(dory_ctx *c, const std::atomic<uint64_t> &ctr, uint64_t want, uint32_t peer, const char *what) {
     if (ctr.load(std::memory_order_acquire) >= want) return DORY_OK;
-    const int64_t lim = c->opt["local_timeout_ms"] > 0 ? c->opt["local_timeout_ms"] : 30000;
+    const int64_t lim = c->opt[OPT_LOCAL_TIMEOUT_MS] > 0 ? c->opt[OPT_LOCAL_TIMEOUT_MS] : 30000;
     const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(lim);
     uint32_t spins = 0;
     while (ctr.load(std::memory_order_acquire) < want) {
@@ -456,7 +456,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     // comm stream waits for the producer of `src` on the compute stream
     HIPCK(c, hipEventRecord(c->ev_a, c->compute));
     HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
-    const bool deferred = defer && c->opt["halo_overlap"];
+    const bool deferred = defer && c->opt[OPT_HALO_OVERLAP];
     (direct ? c->halo_direct_recvs : c->halo_staged_recvs) += 1;
     if (tr == Transport::Local) return exchange_local(c, dir, src, ghost, wire, deferred);
     {   // host transport and RCCL: same pack / unpack / events, only the way from send_buf to recv_buf differs

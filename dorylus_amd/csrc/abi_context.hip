@@ -180,8 +180,8 @@ static int gat_edge_tensor_hook(dory_ctx *c, uint32_t layer, const char *name, b
 // dW_l = in_l^T u_l, and the gradient handed down is u_l W_l^T (= A^T (g_l W_l^T), the reference's aTg).  "ah"@l is
 // not produced for such a layer.  Option gcn_transform_first: 1 = layer 0 only, 2 = every layer that narrows.
 bool tf_layer(dory_ctx *c, uint32_t layer) {
-    const int64_t mode = c->opt["gcn_transform_first"];
-    if (c->gnn != DORY_GCN || c->L < 2 || layer >= c->L || mode == 0 || c->opt["adjacency_values_asymmetric"] != 0) return false;
+    const int64_t mode = c->opt[OPT_GCN_TRANSFORM_FIRST];
+    if (c->gnn != DORY_GCN || c->L < 2 || layer >= c->L || mode == 0 || c->opt[OPT_ADJACENCY_VALUES_ASYMMETRIC] != 0) return false;
     if (mode == 1 && layer != 0) return false;
     return c->dims[layer] > c->dims[layer + 1];
 }
@@ -221,15 +221,7 @@ int dory_create(int device, dory_ctx **out) {
     (void)hipMemset(c->d_stat, 0, 2 * sizeof(float));
     (void)hipMemset(c->sweep_stat, 0, SWEEP_STAT_WORDS * sizeof(uint32_t));
     c->own_compute = c->own_comm = true;
-    c->opt["spmm_variant"] = 2;      // 2: K1s register-accumulating sweep over the blocked adjacency, 1: K1b (partial rows), 0: K1 only
-    c->opt["spmm_sweep_flags"] = 0;          // K1s: reserved for experiments (bit 1 is the library's own "second launch" mark)
-    c->opt["spmm_sweep_rows"] = 0;           // K1s: rows per lane group, 0 = by fill (2/4/6/8/10; tests and experiments)
-    c->opt["spmm_sweep_pair"] = -1;          // K1s: two rows of a lane group as one stream of entries: -1 = launches of >= 3 slabs, 0 = never, 1 = always
-    c->opt["spmm_sweep_loader"] = 1;         // K1s, 32-lane launches: wave 0 of a workgroup copies the next step's entries and offsets into LDS for all sixteen
-    c->opt["spmm_sweep_loader_relief"] = 3;  // ... and the layout gives each of its two lane groups this many rows fewer per sweep (set before the layout is built)
-    c->opt["spmm_sweep_reserve_cus"] = 4;    // K1s under an exchange in flight: CUs per XCD its sweeps leave to the RCCL kernels
-    c->opt["spmm_sweep_layout"] = 3;         // K1s layout: 1 = spread the source rows over the blocks at random, 2 = deal the rows by degree (0: K1b's order -- graphs without structure only)
-    c->opt["spmm_sweep_window_kb"] = 0;      // K1s: source window per block; 0 = 2432 KB (two live windows in one XCD's 4 MB L2), 3584 KB for partitions of <= 4 rows per lane group
+    for (int i = 0; i < OPT_COUNT; ++i) c->opt[i] = option_spec(i)->def;   // every option at the table's default (host/options.cpp)
     c->cus_per_xcd = (uint32_t)std::max(1, prop.multiProcessorCount / 8);
     {   // K1s's placement assumption (ctx.hpp): workgroup id & 7 = XCD, eight XCDs
         const uint32_t PG = 2048;
@@ -251,36 +243,6 @@ int dory_create(int device, dory_ctx **out) {
             c->xcd_mapping_ok = false;
         }
     }
-    c->opt["spmm_xcd_assume_mismatch"] = 0;  // testing: treat the placement check as failed (the gated / ungated choice is then made by measurement)
-    c->opt["spmm_slab"] = 0;
-    c->opt["spmm_order"] = 1;    // K1: rows longest first -- 1 = when the degrees are skewed (max > 8 x mean), 2 = always, 0 = never;
-                                 // 3 (before dory_graph_upload) = rows by their median source id instead (experiment, profiles/HISTORY.md)
-    c->opt["spmm_blk_group"] = 32;   // K1b: lanes per row (slab = 4*group floats = 512 B)
-    c->opt["spmm_blk_force_split"] = 0;   // testing: always launch local / ghost source blocks separately
-    c->opt["halo_overlap"] = 1;      // let local-source blocks of the next SpMM run under the exchange
-    c->opt["gat_lazy_edge_tensors"] = 1;  // GAT prototype: az / A / dA (one value per destination) are written per edge only when read (download, raw pointer, K1's per-edge path)
-    c->opt["gat_reuse_nsum"] = 1;         // GAT prototype: the backward's dA-weighted aggregation from the forward's neighbour sum (abi_stages.hip)
-    c->opt["spmm_edge_split"] = 1;        // K1 on GCN partitions with ghosts: every row's local-source edges first (set before dory_graph_upload)
-    c->opt["spmm_sweep_cus"] = 0;         // K1s / GAT sweeps: workgroups per sweep and XCD (0 = all CUs of an XCD); see dory_set_option
-    c->opt["local_timeout_ms"] = 30000;   // in-process device transport: how long a rank's host thread waits for a peer's host thread
-    c->opt["adjacency_values_asymmetric"] = 0;   // set by dory_partition_upload for undirected / unknown builds: csrVal != cscVal^T
-    c->opt["gatmh_bwd_phase"] = 0;       // multi-head GAT backward: 0 = whole sweep (exchanging the ghost rows itself), 1 / 2 = first / second phase only (callers with their own transport)
-    c->opt["gatmh_blocked"] = 1;         // multi-head GAT: source-blocked (L2-resident) gathers where the blocked adjacency applies
-    c->opt["gatmh_el_on_the_fly"] = 1;       // multi-head GAT, blocked forward with fused statistics, heads of <= 16 features: el[src] from the gathered row instead of a second gather
-    c->opt["gatmh_sweep"] = 1;               // multi-head GAT: the edge passes on K1s's skeleton (gat_mh_sweep.hip) where the sweep layout and the shape apply (1: forward)
-    c->opt["gatmh_src_window_kb"] = 0;       // multi-head GAT: source window of the OUT-edge sweep layout in KB of 512-byte rows (0 = as the forward's, 4608)
-    c->opt["gatmh_sweep_rows"] = 0;          // rows per lane group of the multi-head GAT contexts' sweep layouts (0 = by fill, at most 8)
-    c->opt["gatmh_fused_stats"] = 1;         // multi-head GAT, blocked forward: online softmax per source block + merge in the reduce (0: separate statistics pass first)
-    c->opt["gcn_cache_ah0"] = 0;         // GCN: keep ah@0 = A_hat x across epochs while x, fg@0 and the adjacency are unchanged (opt-in; the reference recomputes it)
-    c->opt["gcn_bf16_gather"] = 0;       // GCN: aggregations read their source rows rounded to bf16, fp32 sums: 1 = forward, 2 = forward and backward (opt-in; see dorylus_hip.h)
-    c->opt["gcn_bf16_wide"] = 0;         // GCN, with gcn_bf16_gather: K1s gathers bf16 rows of 128 floats or more eight features per lane (16-byte gathers); same bits (opt-in; see dorylus_hip.h)
-    c->opt["gatmh_bf16_gather"] = 0;     // multi-head GAT: the sweep forms' edge passes gather their rows rounded to bf16, fp32 sums: 1 = forward (z), 2 = and the backward's source side (do) (opt-in; see dorylus_hip.h)
-    c->opt["gatmh_bf16_wide"] = 0;       // multi-head GAT, with gatmh_bf16_gather: passes on bf16 rows of 128 floats or more (several heads of 16 / 32 / 64 features) gather eight features per lane (16-byte gathers); same bits (opt-in; see dorylus_hip.h)
-    c->opt["halo_exact_rows"] = 0;       // packed halo rows hold exactly `cols` floats instead of the padded `ld` (every transport and the split entry points; same ghost rows bit for bit; opt-in; see dorylus_hip.h)
-    c->opt["halo_direct_recv"] = 0;      // halo rows land in the ghost tensors themselves, ghost rows stored in wire order: no receive buffer, no unpack (before dory_graph_upload; opt-in; see dorylus_hip.h)
-    c->opt["gcn_transform_first"] = 0;   // GCN layers as A(XW) instead of (AX)W where the input is wider than the output: 1 = layer 0, 2 = all (see tf_layer)
-    c->opt["epoch_graph"] = 0;       // engine: replay a recorded epoch (hipGraph) when the partition is alone
-    c->opt["spmm_blk_nb"] = 0;       // K1b: number of source blocks (0 = auto, ~3.75 MB windows)
     *out = c;
     return DORY_OK;
 }
@@ -379,14 +341,8 @@ int dory_configure(dory_ctx *c, int gnn_type, uint32_t num_layers, const uint32_
         return fail(c, DORY_ERR_ARG, "dory_configure: bad arguments");
     for (uint32_t i = 0; i <= num_layers; ++i)
         if (dims[i] == 0) return fail(c, DORY_ERR_ARG, "dory_configure: zero layer width");
-    if (gnn_type != DORY_GCN && c->opt["gcn_bf16_gather"])
-        return fail(c, DORY_ERR_ARG, "dory_configure: gcn_bf16_gather is a GCN option (set it to 0 first)");
-    if (gnn_type != DORY_GCN && c->opt["gcn_bf16_wide"])
-        return fail(c, DORY_ERR_ARG, "dory_configure: gcn_bf16_wide is a GCN option (set it to 0 first)");
-    if (gnn_type != DORY_GATMH && c->opt["gatmh_bf16_gather"])
-        return fail(c, DORY_ERR_ARG, "dory_configure: gatmh_bf16_gather is an option of the multi-head GAT (set it to 0 first)");
-    if (gnn_type != DORY_GATMH && c->opt["gatmh_bf16_wide"])
-        return fail(c, DORY_ERR_ARG, "dory_configure: gatmh_bf16_wide is an option of the multi-head GAT (set it to 0 first)");
+    char msg[256];
+    if (option_model_conflict(c->opt, gnn_type, msg, sizeof(msg))) return fail(c, DORY_ERR_ARG, "%s", msg);
     c->gnn = gnn_type;
     c->L = num_layers;
     c->dims.assign(dims, dims + num_layers + 1);
@@ -432,7 +388,7 @@ int dory_graph_upload(dory_ctx *c, uint32_t N, uint32_t Gsrc, uint32_t Gdst, uin
     c->N = N;
     int rc;
     if ((rc = upload_array(c, &c->norm, vtx_norms, (uint64_t)N))) return rc;
-    const bool by_median = c->opt["spmm_order"] == 3;    // (set before the upload: the schedule is built here)
+    const bool by_median = c->opt[OPT_SPMM_ORDER] == 3;    // (set before the upload: the schedule is built here)
     struct HostAdj { const uint64_t *ptr; const uint32_t *idx; const float *val; uint64_t nnz; uint32_t ghosts; };
     const HostAdj host[2] = {{column_ptrs, row_idxs, csc_values, nnz_in, Gsrc}, {row_ptrs, column_idxs, csr_values, nnz_out, Gdst}};
     for (int d = 0; d < 2; ++d) {   // ADJ_IN, ADJ_OUT: each direction on its own
@@ -477,7 +433,7 @@ int dory_graph_upload(dory_ctx *c, uint32_t N, uint32_t Gsrc, uint32_t Gdst, uin
             }
         }
         // K1's local-first edge order (ctx.hpp: EdgeSplit) for GCN partitions with ghosts and without hub rows
-        if (c->gnn == DORY_GCN && c->opt["spmm_edge_split"] && A.ghosts && !A.long_rows.nchunks) {
+        if (c->gnn == DORY_GCN && c->opt[OPT_SPMM_EDGE_SPLIT] && A.ghosts && !A.long_rows.nchunks) {
             std::vector<uint32_t> i2(nnz);
             std::vector<float> v2(nnz);
             std::vector<uint64_t> mid(N);
@@ -631,7 +587,7 @@ int dory_preallocate(dory_ctx *c) {
     HIPCK(c, hipStreamSynchronize(c->compute));
     auto layer_ld = [&](uint32_t l) { return pad_ld(l == L - 1 ? d[l + 1] * c->heads[l] : d[l + 1]); };   // multi-head GAT: z / o of layer l
     const uint32_t G = std::min<uint32_t>(32u, c->cus_per_xcd);
-    if (c->opt["spmm_variant"] == 2 && N > 0 && c->gnn == DORY_GATMH && c->opt["gatmh_sweep"]) {
+    if (c->opt[OPT_SPMM_VARIANT] == 2 && N > 0 && c->gnn == DORY_GATMH && c->opt[OPT_GATMH_SWEEP]) {
         // the sweep layouts (K1s's even layout; the deal is made for the 32-lane launches) and the gate counters now
         uint32_t maxld = 0;
         for (uint32_t l = 0; l < L; ++l) maxld = std::max(maxld, layer_ld(l));
@@ -648,7 +604,7 @@ int dory_preallocate(dory_ctx *c) {
         // (ensure_partial synchronises the compute stream before it frees; nothing in flight reads c->partial before `prealloc` is set)
         if ((rc = ensure_partial(c, need, "sweep counters"))) return rc;
     }
-    if (c->opt["spmm_variant"] >= 1 && N > 0 && c->gnn == DORY_GATMH && c->opt["gatmh_blocked"]) {
+    if (c->opt[OPT_SPMM_VARIANT] >= 1 && N > 0 && c->gnn == DORY_GATMH && c->opt[OPT_GATMH_BLOCKED]) {
         // the extension's forward sum gathers through the same source-blocked copy of the in-edges
         uint32_t maxld = 0, minld = 0xFFFFFFFFu;
         for (uint32_t l = 0; l < L; ++l) { maxld = std::max(maxld, layer_ld(l)); minld = std::min(minld, layer_ld(l)); }
@@ -663,7 +619,7 @@ int dory_preallocate(dory_ctx *c) {
         need = std::max(need, (size_t)std::max(In.blk16.nb, Out.blk16.nb) * N * (std::min<uint32_t>(maxld, 96u) + 64) * sizeof(float));
         if (nbmax && need <= ((size_t)48 << 30) && (rc = ensure_partial(c, need, "partial buffer"))) return rc;
     }
-    if (c->opt["spmm_variant"] >= 1 && N > 0 && c->gnn != DORY_GATMH) {   // K1b: regroup the edges now, not inside the first epoch
+    if (c->opt[OPT_SPMM_VARIANT] >= 1 && N > 0 && c->gnn != DORY_GATMH) {   // K1b: regroup the edges now, not inside the first epoch
         uint32_t minld = 0xFFFFFFFFu;
         for (uint32_t l = 0; l < L; ++l) {
             const uint32_t w = c->gnn == DORY_GCN ? (l == 0 ? d[0] : d[l]) : d[l + 1];
@@ -672,7 +628,7 @@ int dory_preallocate(dory_ctx *c) {
         uint32_t maxld = 0;
         for (uint32_t l = 0; l <= L; ++l) maxld = std::max(maxld, pad_ld(d[l]));
         const int group = blk_group_for(c, maxld);   // block size for the widest rows (most of the traffic)
-        if (minld >= 32 && c->opt["spmm_variant"] == 2) {
+        if (minld >= 32 && c->opt[OPT_SPMM_VARIANT] == 2) {
             // K1s: its layouts and the gate counters of the largest launch now, so that nothing is built or allocated
             // inside an epoch (a partition it does not take -- too small, too large -- keeps K1 / builds K1b on demand)
             size_t need = 0;
@@ -925,14 +881,19 @@ int dory_timing_enable(dory_ctx *c, int on) {
     c->timing = on != 0;
     return DORY_OK;
 }
+// the K1s gate words (dory_ctx::sweep_stat) on the host, for the keys that report them: reading synchronises the stream
+static int read_sweep_stat(dory_ctx *c, const char *key, uint32_t (&st)[SWEEP_STAT_WORDS]) {
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "%s: not while an epoch graph is being recorded (reading synchronises the stream)", key);
+    HIPCK(c, hipStreamSynchronize(c->compute));
+    HIPCK(c, hipMemcpy(st, c->sweep_stat, sizeof(st), hipMemcpyDeviceToHost));
+    return DORY_OK;
+}
 int dory_timing_get(dory_ctx *c, const char *family, double *total_ms, uint64_t *launches) {
     CHECK_CTX(c);
     if (!family) return DORY_ERR_ARG;
     if (!strcmp(family, "spmm_gate_timeouts")) {   // not a kernel family: launches = gate timeouts, total_ms = ungated launches
-        uint32_t st[4] = {0, 0, 0, 0};
-        if (c->capturing) return fail(c, DORY_ERR_ARG, "spmm_gate_timeouts: not while an epoch graph is being recorded (reading synchronises the stream)");
-        HIPCK(c, hipStreamSynchronize(c->compute));
-        HIPCK(c, hipMemcpy(st, c->sweep_stat, sizeof(st), hipMemcpyDeviceToHost));
+        uint32_t st[SWEEP_STAT_WORDS];
+        if (int rc = read_sweep_stat(c, family, st)) return rc;
         if (total_ms) *total_ms = (double)st[2];
         if (launches) *launches = st[0];
         return DORY_OK;
@@ -966,61 +927,46 @@ int dory_transform_first_layer(dory_ctx *c, uint32_t layer) {
 
 int dory_get_option(dory_ctx *c, const char *key, int64_t *value) {
     CHECK_CTX(c);
-    if (key && value && !strcmp(key, "gcn_cache_ah0_skips")) {   // read-only: layer-0 aggregations answered from the cached ah@0
-        *value = (int64_t)c->ah0_skips;
-        return DORY_OK;
-    }
-    if (key && value && !strcmp(key, "gcn_bf16_gathers_k1s")) { *value = (int64_t)c->bf16_gathers_k1s; return DORY_OK; }   // read-only: aggregations
-    if (key && value && !strcmp(key, "gcn_bf16_gathers_k1s_wide")) { *value = (int64_t)c->bf16_gathers_k1s_wide; return DORY_OK; }   // (of _k1s: the wide form, option gcn_bf16_wide)
-    if (key && value && !strcmp(key, "gcn_bf16_gathers_k1")) { *value = (int64_t)c->bf16_gathers_k1; return DORY_OK; }     // on bf16 rows, per kernel family
-    // read-only: aggregations of spmm() per kernel family that committed to running them (eager calls and recordings, not replays)
-    if (key && value && !strcmp(key, "spmm_launches_k1s")) { *value = (int64_t)c->spmm_launches_k1s; return DORY_OK; }
-    if (key && value && !strcmp(key, "spmm_launches_k1b")) { *value = (int64_t)c->spmm_launches_k1b; return DORY_OK; }
-    if (key && value && !strcmp(key, "spmm_launches_k1")) { *value = (int64_t)c->spmm_launches_k1; return DORY_OK; }
-    if (key && value && !strcmp(key, "gatmh_bf16_gathers_fwd")) { *value = (int64_t)c->gatmh_bf16_gathers_fwd; return DORY_OK; }   // read-only: multi-head GAT
-    if (key && value && !strcmp(key, "gatmh_bf16_gathers_src")) { *value = (int64_t)c->gatmh_bf16_gathers_src; return DORY_OK; }   // edge passes on bf16 rows
-    if (key && value && !strcmp(key, "gatmh_bf16_gathers_fwd_wide")) { *value = (int64_t)c->gatmh_bf16_gathers_fwd_wide; return DORY_OK; }   // (of those: the wide
-    if (key && value && !strcmp(key, "gatmh_bf16_gathers_src_wide")) { *value = (int64_t)c->gatmh_bf16_gathers_src_wide; return DORY_OK; }   //  form, option gatmh_bf16_wide)
-    // read-only: what the eager packs (exchanges and dory_halo_pack*) wrote into send buffers since dory_create, and the packs
-    // that ran the exact form of option halo_exact_rows on rows narrower than their padding
-    if (key && value && !strcmp(key, "halo_rows_packed")) { *value = (int64_t)c->halo_rows_packed; return DORY_OK; }
-    if (key && value && !strcmp(key, "halo_floats_packed")) { *value = (int64_t)c->halo_floats_packed; return DORY_OK; }
-    if (key && value && !strcmp(key, "halo_exact_packs")) { *value = (int64_t)c->halo_exact_packs; return DORY_OK; }
-    // read-only: the exchanges (eager calls and recordings, one step each) whose rows landed in the ghost tensor itself (option
-    // halo_direct_recv) / went through the receive buffer and an unpack, and the bytes of that buffer
-    if (key && value && !strcmp(key, "halo_direct_recvs")) { *value = (int64_t)c->halo_direct_recvs; return DORY_OK; }
-    if (key && value && !strcmp(key, "halo_staged_recvs")) { *value = (int64_t)c->halo_staged_recvs; return DORY_OK; }
-    if (key && value && !strcmp(key, "halo_recv_buf_bytes")) { *value = (int64_t)c->recv_cap; return DORY_OK; }
-    if (key && value && !strcmp(key, "epoch_graph_recorded")) {   // read-only: does the ctx still hold a recorded epoch?
-        *value = c->epoch_exec ? 1 : 0;
-        return DORY_OK;
-    }
-    // read-only counters of the K1s gates (device words that outlive the launches): timeouts = a sweep's workgroups were
-    // not co-resident within the polling bound; ungated launches = launches that ran without gates while the context
-    // backed off after a timeout (same results, unsynchronised rate)
-    if (key && value && !strcmp(key, "spmm_gates_rearm")) {   // (write-only action; reads as "is a back-off pending": launch number below a horizon)
-        uint32_t st[SWEEP_STAT_WORDS] = {0};
-        if (c->capturing) return fail(c, DORY_ERR_ARG, "spmm_gates_rearm: not while an epoch graph is being recorded (reading synchronises the stream)");
-        HIPCK(c, hipStreamSynchronize(c->compute));
-        HIPCK(c, hipMemcpy(st, c->sweep_stat, sizeof(st), hipMemcpyDeviceToHost));
+    const int id = value ? option_find(key) : -1;
+    if (id < 0) return fail(c, DORY_ERR_ARG, "unknown option '%s'", key ? key : "(null)");
+    if (id < OPT_COUNT) { *value = c->opt[id]; return DORY_OK; }
+    uint32_t st[SWEEP_STAT_WORDS];
+    if (id == KEY_SPMM_GATES_REARM) {   // "is a back-off pending": the launch number is below a horizon
+        if (int rc = read_sweep_stat(c, key, st)) return rc;
         *value = (st[4] < st[1] || st[4] < st[3]) ? 1 : 0;
         return DORY_OK;
     }
-    if (key && value && !strcmp(key, "spmm_xcd_mapping_ok")) { *value = c->xcd_mapping_ok ? 1 : 0; return DORY_OK; }   // read-only: dory_create's check
-    if (key && value && !strcmp(key, "spmm_xcd_count")) { *value = c->xcd_count; return DORY_OK; }
-    if (key && value && !strcmp(key, "spmm_xcd_policy")) { *value = c->xcd_policy; return DORY_OK; }                  // -1 undecided / not needed, 0 gated, 8 ungated
-    if (key && value && !strcmp(key, "spmm_xcd_gated_us")) { *value = (int64_t)(c->xcd_gated_ms * 1e3f); return DORY_OK; }
-    if (key && value && !strcmp(key, "spmm_xcd_ungated_us")) { *value = (int64_t)(c->xcd_ungated_ms * 1e3f); return DORY_OK; }
-    if (key && value && (!strcmp(key, "spmm_gate_timeouts") || !strcmp(key, "spmm_ungated_launches"))) {
-        uint32_t st[4] = {0, 0, 0, 0};
-        if (c->capturing) return fail(c, DORY_ERR_ARG, "%s: not while an epoch graph is being recorded (reading synchronises the stream)", key);
-        HIPCK(c, hipStreamSynchronize(c->compute));
-        HIPCK(c, hipMemcpy(st, c->sweep_stat, sizeof(st), hipMemcpyDeviceToHost));
-        *value = !strcmp(key, "spmm_gate_timeouts") ? st[0] : st[2];
-        return DORY_OK;
+    switch ((ReadOnlyId)(id - OPT_COUNT)) {   // (no default: the compiler names a read-only key without a case)
+    case RO_GCN_CACHE_AH0_SKIPS: *value = (int64_t)c->ah0_skips; break;
+    case RO_GCN_BF16_GATHERS_K1S: *value = (int64_t)c->bf16_gathers_k1s; break;
+    case RO_GCN_BF16_GATHERS_K1S_WIDE: *value = (int64_t)c->bf16_gathers_k1s_wide; break;
+    case RO_GCN_BF16_GATHERS_K1: *value = (int64_t)c->bf16_gathers_k1; break;
+    case RO_SPMM_LAUNCHES_K1S: *value = (int64_t)c->spmm_launches_k1s; break;
+    case RO_SPMM_LAUNCHES_K1B: *value = (int64_t)c->spmm_launches_k1b; break;
+    case RO_SPMM_LAUNCHES_K1: *value = (int64_t)c->spmm_launches_k1; break;
+    case RO_GATMH_BF16_GATHERS_FWD: *value = (int64_t)c->gatmh_bf16_gathers_fwd; break;
+    case RO_GATMH_BF16_GATHERS_SRC: *value = (int64_t)c->gatmh_bf16_gathers_src; break;
+    case RO_GATMH_BF16_GATHERS_FWD_WIDE: *value = (int64_t)c->gatmh_bf16_gathers_fwd_wide; break;
+    case RO_GATMH_BF16_GATHERS_SRC_WIDE: *value = (int64_t)c->gatmh_bf16_gathers_src_wide; break;
+    case RO_HALO_ROWS_PACKED: *value = (int64_t)c->halo_rows_packed; break;
+    case RO_HALO_FLOATS_PACKED: *value = (int64_t)c->halo_floats_packed; break;
+    case RO_HALO_EXACT_PACKS: *value = (int64_t)c->halo_exact_packs; break;
+    case RO_HALO_DIRECT_RECVS: *value = (int64_t)c->halo_direct_recvs; break;
+    case RO_HALO_STAGED_RECVS: *value = (int64_t)c->halo_staged_recvs; break;
+    case RO_HALO_RECV_BUF_BYTES: *value = (int64_t)c->recv_cap; break;
+    case RO_EPOCH_GRAPH_RECORDED: *value = c->epoch_exec ? 1 : 0; break;
+    case RO_SPMM_XCD_MAPPING_OK: *value = c->xcd_mapping_ok ? 1 : 0; break;
+    case RO_SPMM_XCD_COUNT: *value = c->xcd_count; break;
+    case RO_SPMM_XCD_POLICY: *value = c->xcd_policy; break;
+    case RO_SPMM_XCD_GATED_US: *value = (int64_t)(c->xcd_gated_ms * 1e3f); break;
+    case RO_SPMM_XCD_UNGATED_US: *value = (int64_t)(c->xcd_ungated_ms * 1e3f); break;
+    case RO_SPMM_GATE_TIMEOUTS:
+    case RO_SPMM_UNGATED_LAUNCHES:
+        if (int rc = read_sweep_stat(c, key, st)) return rc;
+        *value = id - OPT_COUNT == RO_SPMM_GATE_TIMEOUTS ? st[0] : st[2];
+        break;
+    case RO_COUNT: break;
     }
-    if (!key || !value || c->opt.find(key) == c->opt.end()) return fail(c, DORY_ERR_ARG, "unknown option '%s'", key ? key : "(null)");
-    *value = c->opt[key];
     return DORY_OK;
 }
 
@@ -1033,7 +979,8 @@ int dory_debug_occupy_cus(dory_ctx *c, uint32_t workgroups, uint64_t usec) {
 
 int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     CHECK_CTX(c);
-    if (key && !strcmp(key, "spmm_gates_rearm")) {   // write-only: end a K1s gate back-off now (both launch classes); the counters stay.
+    const int id = option_find(key);
+    if (id == KEY_SPMM_GATES_REARM) {   // write-only: end a K1s gate back-off now (both launch classes); the counters stay.
         // For a caller that has just changed what caused the timeouts (bench.py trying another spmm_sweep_reserve_cus).
         if (c->capturing) return fail(c, DORY_ERR_ARG, "spmm_gates_rearm: not while an epoch graph is being recorded (it synchronises the stream)");
         HIPCK(c, hipStreamSynchronize(c->compute));
@@ -1042,45 +989,22 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
         HIPCK(c, hipMemcpy(c->sweep_stat + 3, &zero, sizeof(zero), hipMemcpyHostToDevice));
         return DORY_OK;
     }
-    if (key && !strcmp(key, "spmm_sweep_cus")) {   // workgroups per sweep and XCD of K1s and the GAT sweeps (0: every CU of an XCD).  For several
+    if (id < 0 || id >= OPT_COUNT) return fail(c, DORY_ERR_ARG, "unknown option '%s'", key ? key : "(null)");
+    char msg[256];
+    if (option_check(id, value, c->gnn, c->configured, c->has_graph, msg, sizeof(msg))) return fail(c, DORY_ERR_ARG, "%s", msg);
+    if (id == OPT_SPMM_SWEEP_CUS) {   // workgroups per sweep and XCD of K1s and the GAT sweeps (0: every CU of an XCD).  For several
         // contexts that SHARE a device (dory_comm_init_local: P ranks on one GPU): each takes its share of the CUs, so that
         // the ranks' gated sweeps are co-resident beside each other.  Before dory_graph_upload (the layouts are dealt for it).
-        if (c->has_graph) return fail(c, DORY_ERR_ARG, "spmm_sweep_cus: set it before the graph is uploaded");
         hipDeviceProp_t prop;
         HIPCK(c, hipGetDeviceProperties(&prop, c->device));
         const uint32_t all = (uint32_t)std::max(1, prop.multiProcessorCount / 8);
         if (value < 0 || value > (int64_t)all) return fail(c, DORY_ERR_ARG, "spmm_sweep_cus: 0..%u", all);
         c->cus_per_xcd = value == 0 ? all : (uint32_t)value;
-        c->opt[key] = value;
-        return DORY_OK;
     }
-    if (key && !strcmp(key, "gcn_bf16_gather")) {
-        if (value < 0 || value > 2) return fail(c, DORY_ERR_ARG, "gcn_bf16_gather: 0 (off), 1 (forward) or 2 (forward and backward)");
-        if (value && c->gnn != DORY_GCN) return fail(c, DORY_ERR_ARG, "gcn_bf16_gather: GCN contexts only");
-    }
-    if (key && !strcmp(key, "gcn_bf16_wide")) {
-        if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "gcn_bf16_wide: 0 (off) or 1 (16-byte gathers of bf16 rows in K1s)");
-        if (value && c->gnn != DORY_GCN) return fail(c, DORY_ERR_ARG, "gcn_bf16_wide: GCN contexts only");
-    }
-    if (key && !strcmp(key, "gatmh_bf16_gather")) {
-        if (value < 0 || value > 2) return fail(c, DORY_ERR_ARG, "gatmh_bf16_gather: 0 (off), 1 (forward) or 2 (forward and the backward's source side)");
-        if (value && c->configured && c->gnn != DORY_GATMH) return fail(c, DORY_ERR_ARG, "gatmh_bf16_gather: multi-head GAT contexts (DORY_GATMH) only");
-    }
-    if (key && !strcmp(key, "gatmh_bf16_wide")) {
-        if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "gatmh_bf16_wide: 0 (off) or 1 (16-byte gathers of bf16 rows in the multi-head GAT's sweeps)");
-        if (value && c->configured && c->gnn != DORY_GATMH) return fail(c, DORY_ERR_ARG, "gatmh_bf16_wide: multi-head GAT contexts (DORY_GATMH) only");
-    }
-    if (key && !strcmp(key, "halo_exact_rows")) {
-        if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "halo_exact_rows: 0 (padded rows travel) or 1 (rows of exactly cols floats)");
-        c->halo_exact.store((int)value, std::memory_order_release);
-    }
-    if (key && !strcmp(key, "halo_direct_recv")) {
-        if (value < 0 || value > 1) return fail(c, DORY_ERR_ARG, "halo_direct_recv: 0 (receive buffer and unpack) or 1 (halo rows land in the ghost tensors, stored in wire order)");
-        if (c->has_graph) return fail(c, DORY_ERR_ARG, "halo_direct_recv: set it before the graph is uploaded (the adjacency's ghost numbering depends on it)");
-        c->halo_direct.store((int)value, std::memory_order_release);
-    }
-    if (!key || c->opt.find(key) == c->opt.end()) return fail(c, DORY_ERR_ARG, "unknown option '%s'", key ? key : "(null)");
-    c->opt[key] = value;
+    c->opt[id] = value;
+    // the copies the peers of the in-process transport read without this context's lock
+    if (id == OPT_HALO_EXACT_ROWS) c->halo_exact.store((int)value, std::memory_order_release);
+    if (id == OPT_HALO_DIRECT_RECV) c->halo_direct.store((int)value, std::memory_order_release);
     c->ah0_valid = false;   // (another kernel variant sums in another order: a cached ah@0 is only kept across identical settings)
     return DORY_OK;
 }

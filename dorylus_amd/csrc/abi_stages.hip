@@ -10,7 +10,7 @@ static BlockedAdj &gatmh_blocked_for(Adjacency &A, uint32_t ld) { return ld < 12
 // K1b bookkeeping: (re)build the source-blocked copy of one adjacency for `group` lanes/row
 int ensure_blocked(dory_ctx *c, Adjacency &A, int group, bool narrow_set) {
     DerivedAdj &B = narrow_set ? A.blk16 : A.blk;
-    const uint32_t want_nb = (uint32_t)c->opt["spmm_blk_nb"];
+    const uint32_t want_nb = (uint32_t)c->opt[OPT_SPMM_BLK_NB];
     // the block structure serves every slab width; only an explicit block count forces a rebuild
     const bool rebuild = B.built && want_nb && B.nb != (want_nb + 7) / 8 * 8;
     if (c->capturing && (!B.built || rebuild) && !A.blk.na)
@@ -46,7 +46,7 @@ int ensure_blocked(dory_ctx *c, Adjacency &A, int group, bool narrow_set) {
 // K1s bookkeeping: the even layout build_blocked_sweep makes of one adjacency (spmm.hip)
 int ensure_sweep(dory_ctx *c, Adjacency &A, int group) {
     DerivedAdj &S = A.swp;
-    const uint32_t want_nb = (uint32_t)c->opt["spmm_blk_nb"];
+    const uint32_t want_nb = (uint32_t)c->opt[OPT_SPMM_BLK_NB];
     if (S.built && S.want_nb != want_nb && !c->capturing) {   // another block count requested (tests): rebuild
         HIPCK(c, hipStreamSynchronize(c->compute));
         free_blocked(&S);
@@ -61,10 +61,10 @@ int ensure_sweep(dory_ctx *c, Adjacency &A, int group) {
         // four rows while that fills every CU at least once (fewer sweeps = fewer refills of every window: 4.47 -> 4.17 ms per
         // 128-float forward launch from two rows to four); small partitions pick by fill
         const uint32_t G_ = std::min<uint32_t>(32u, c->cus_per_xcd);
-        const int forced = (int)c->opt["gatmh_sweep_rows"];
+        const int forced = (int)c->opt[OPT_GATMH_SWEEP_ROWS];
         R = (!forced && c->N >= 8u * G_ * 32u * 4u) ? 4 : sweep_pick_r(c->N, 32, G_, forced, 4);
     } else {
-        R = sweep_pick_r(c->N, 32, std::min<uint32_t>(32u, c->cus_per_xcd), (int)c->opt["spmm_sweep_rows"]);
+        R = sweep_pick_r(c->N, 32, std::min<uint32_t>(32u, c->cus_per_xcd), (int)c->opt[OPT_SPMM_SWEEP_ROWS]);
     }
     // source window per block.  0 = by the rows a lane group holds: a step costs ~3 us whatever it gathers, and a small
     // partition (one rank of 8: four rows per group) gathers little per step -- fewer, larger windows win there although
@@ -76,8 +76,8 @@ int ensure_sweep(dory_ctx *c, Adjacency &A, int group) {
     // quarter larger than the forward's for the same rows, and at 4.5 MB of rows it ran fabric-bound: 29.6 GB fetched in 5.1 ms
     // per 128-float launch; the out-edge layout therefore gets its own window, option gatmh_src_window_kb)
     const bool out_edges = &A == &c->adj[ADJ_OUT];   // (by identity: an Adjacency is only ever handed on by reference into c->adj)
-    const uint64_t gat_kb = (c->gnn == DORY_GATMH && out_edges && c->opt["gatmh_src_window_kb"]) ? (uint64_t)c->opt["gatmh_src_window_kb"] : 4608u;
-    const uint64_t window_kb = c->opt["spmm_sweep_window_kb"] ? (uint64_t)c->opt["spmm_sweep_window_kb"]
+    const uint64_t gat_kb = (c->gnn == DORY_GATMH && out_edges && c->opt[OPT_GATMH_SRC_WINDOW_KB]) ? (uint64_t)c->opt[OPT_GATMH_SRC_WINDOW_KB] : 4608u;
+    const uint64_t window_kb = c->opt[OPT_SPMM_SWEEP_WINDOW_KB] ? (uint64_t)c->opt[OPT_SPMM_SWEEP_WINDOW_KB]
                                                               : (c->gnn == DORY_GATMH && R >= 4 ? gat_kb : (R <= 4 ? 3584u : 2432u));
     const uint64_t window = window_kb << 10;
     const uint64_t nb_est = ((uint64_t)NG * group * 16u + window - 1) / window + 1;
@@ -90,15 +90,15 @@ int ensure_sweep(dory_ctx *c, Adjacency &A, int group) {
         return DORY_OK;
     }
     HIPCK(c, build_blocked_sweep(A.ptr, A.idx, A.val, c->N, NG, A.nnz, want_nb, (uint32_t)group * 16u, window, R, &S, c->compute,
-                                 (uint32_t)c->opt["spmm_sweep_layout"], std::min<uint32_t>(32u, c->cus_per_xcd),
-                                 group == 32 && c->opt["spmm_sweep_loader"] ? (uint32_t)c->opt["spmm_sweep_loader_relief"] : 0u));
+                                 (uint32_t)c->opt[OPT_SPMM_SWEEP_LAYOUT], std::min<uint32_t>(32u, c->cus_per_xcd),
+                                 group == 32 && c->opt[OPT_SPMM_SWEEP_LOADER] ? (uint32_t)c->opt[OPT_SPMM_SWEEP_LOADER_RELIEF] : 0u));
     S.want_nb = want_nb;
     S.built = true;
     return DORY_OK;
 }
 
 int blk_group_for(dory_ctx *c, uint32_t ld) {
-    int group = (int)c->opt["spmm_blk_group"];
+    int group = (int)c->opt[OPT_SPMM_BLK_GROUP];
     if (group != 8 && group != 16 && group != 32) group = 32;
     if (ld < 128 && group == 32) group = 16;   // narrow tensors: one 256-B slab
     return group;
@@ -186,7 +186,7 @@ struct SweepLaunch {
     }
 };
 static uint32_t sweep_flags(dory_ctx *c) {
-    return (uint32_t)c->opt["spmm_sweep_flags"] | (((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && c->xcd_policy != 0) ? 8u : 0u);
+    return (uint32_t)c->opt[OPT_SPMM_SWEEP_FLAGS] | (((!c->xcd_mapping_ok || c->opt[OPT_SPMM_XCD_ASSUME_MISMATCH]) && c->xcd_policy != 0) ? 8u : 0u);
 }
 static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, int group, bool ghosts, int R, bool bf16, bool wide) {
     SweepLaunch sw;
@@ -196,7 +196,7 @@ static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, i
     sw.two = ghosts && S.nb_local > 0 && S.nb_local < S.nb;
     sw.bf16 = bf16;
     sw.wide = wide;
-    sw.ctl = SweepCtl{(int)c->opt["spmm_sweep_pair"], c->opt["spmm_sweep_loader"] != 0, c->sweep_stat};   // (pair, loader: K1s's forms)
+    sw.ctl = SweepCtl{(int)c->opt[OPT_SPMM_SWEEP_PAIR], c->opt[OPT_SPMM_SWEEP_LOADER] != 0, c->sweep_stat};   // (pair, loader: K1s's forms)
     sw.sflags = sweep_flags(c);
     sw.need = sweep_counter_bound(S.npos, ld, group, R, wide, sw.G, sw.two ? std::max(S.nb_local, S.nb - S.nb_local) : S.nb);
     sw.done = sw.need <= c->partial_bytes ? reinterpret_cast<uint32_t *>(c->partial) : nullptr;
@@ -206,7 +206,7 @@ static SweepLaunch sweep_launch(dory_ctx *c, const BlockedAdj &S, uint32_t ld, i
 
 // K1s's rows per lane group on `group` lanes (the wide form: 16) of the layout S: option spmm_sweep_rows, else what S was dealt for
 int k1s_rows(dory_ctx *c, const BlockedAdj &S, int group) {
-    return sweep_rows(S.rows_per_group, S.npos, group, std::min<uint32_t>(32u, c->cus_per_xcd), (int)c->opt["spmm_sweep_rows"]);
+    return sweep_rows(S.rows_per_group, S.npos, group, std::min<uint32_t>(32u, c->cus_per_xcd), (int)c->opt[OPT_SPMM_SWEEP_ROWS]);
 }
 
 // K1s's placement check failed (ctx.hpp): gates would synchronise workgroups that do not share an L2.  Decide once per context,
@@ -244,13 +244,13 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     if (S.na || !sweep_supported(a, S, group)) return SPMM_NOT_MINE;
     const bool bf16 = bf.on();
     // option gcn_bf16_wide: bf16 rows of 128 floats or more are gathered eight features per lane (same bits; spmm.hip)
-    const bool wide = bf16 && c->opt["gcn_bf16_wide"] == 1 && sweep_wide_applies(a.ld, group, k1s_rows(c, S, 16));
+    const bool wide = bf16 && c->opt[OPT_GCN_BF16_WIDE] == 1 && sweep_wide_applies(a.ld, group, k1s_rows(c, S, 16));
     SweepLaunch sw = sweep_launch(c, S, a.ld, group, a.xg != nullptr, k1s_rows(c, S, wide ? 16 : group), bf16, wide);
     if ((rc = ensure_partial(c, sw.need, "sweep counters"))) return rc;   // (K1s may still size its counters here, outside a recording)
     sw.done = reinterpret_cast<uint32_t *>(c->partial);
     if (S.nslots && (rc = ensure_scratch(c, (size_t)S.nslots * a.ld * sizeof(float)))) return rc;   // pieces of split rows
     c->last_spmm_unit = row_scale != nullptr;
-    if ((!c->xcd_mapping_ok || c->opt["spmm_xcd_assume_mismatch"]) && !(c->opt["spmm_sweep_flags"] & 8) && c->xcd_policy < 0 &&
+    if ((!c->xcd_mapping_ok || c->opt[OPT_SPMM_XCD_ASSUME_MISMATCH]) && !(c->opt[OPT_SPMM_SWEEP_FLAGS] & 8) && c->xcd_policy < 0 &&
         !c->capturing && !a.accumulate && !c->halo_pending) {
         if ((rc = xcd_probe(c, a, S, row_scale, sw))) return rc;
         sw.sflags = sweep_flags(c);   // (left undecided -- recording, accumulating caller: ungated, never a timeout)
@@ -264,7 +264,7 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
         return DORY_OK;
     };
     // under an exchange in flight the RCCL kernels need CUs of their own; the ghost-source blocks go on from the first launch's sums
-    const uint32_t reserve = c->halo_pending ? (uint32_t)c->opt["spmm_sweep_reserve_cus"] : 0u;
+    const uint32_t reserve = c->halo_pending ? (uint32_t)c->opt[OPT_SPMM_SWEEP_RESERVE_CUS] : 0u;
     rc = around_halo(c, sw.two, &bf, [&] { return sweep(sw.part(0, S.nb_local, false, reserve)); },
                      [&] { return sweep(sw.two ? sw.part(S.nb_local, S.nb, true) : sw.part(0, S.nb, false)); });
     if (rc) return rc;
@@ -291,7 +291,7 @@ static int spmm_k1b(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     // source blocks that contain local rows only do not depend on the exchange in
     // flight: they run first, the ghost blocks after the comm stream's event
     const uint32_t nb_local = std::min(B.nb, c->N / B.SB);
-    const bool split = (c->halo_pending || c->opt["spmm_blk_force_split"]) && nb_local > 0 && nb_local < B.nb;
+    const bool split = (c->halo_pending || c->opt[OPT_SPMM_BLK_FORCE_SPLIT]) && nb_local > 0 && nb_local < B.nb;
     if ((rc = around_halo(c, split, nullptr, [&] { return part(0, nb_local); }, [&] { return part(split ? nb_local : 0, B.nb); }))) return rc;
     if (B.nchunks) {   // hubs: the remainder of the (block,row) segments K1b stopped in
         if ((rc = ensure_scratch(c, (size_t)B.nchunks * a.ld * sizeof(float)))) return rc;
@@ -308,7 +308,7 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
     c->spmm_launches_k1++;
     if (bf16) c->bf16_gathers_k1++;
     auto launch = [&](const SpmmArgs &x) -> int {
-        HIPCK(c, launch_spmm(x, (int)c->opt["spmm_slab"], c->compute, bf16));
+        HIPCK(c, launch_spmm(x, (int)c->opt[OPT_SPMM_SLAB], c->compute, bf16));
         return DORY_OK;
     };
     const LongRowsDev &longRows = A.long_rows;
@@ -317,7 +317,7 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
         if (rc) return rc;
         a.row_clamp = LONG_ROW_CLAMP;
     }
-    const bool in_flight = c->halo_pending || c->opt["spmm_blk_force_split"];
+    const bool in_flight = c->halo_pending || c->opt[OPT_SPMM_BLK_FORCE_SPLIT];
     // K1 under an exchange in flight.  GCN partitions with ghosts hold a local-first copy of the edges (ctx.hpp: EdgeSplit): one
     // launch sums every row's local-source edges beside the exchange, a second one goes on from those sums with the ghost-
     // source edges (boundary rows only) -- the additions happen in the same order as in ONE launch over the copy, which is what
@@ -325,7 +325,7 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
     const EdgeSplit &es = A.edge_split;
     // (layer 0's forward aggregation reads ghost rows that came from a file: no exchange ever precedes it, in either schedule,
     // so it keeps the reference's edge order -- the local-first copy costs the 300-float Amazon launch a few per cent)
-    if (es.idx && a.xg && a.val == A.val && !longRows.nchunks && !a.accumulate && c->opt["spmm_edge_split"] && !c->agg_static_ghosts) {
+    if (es.idx && a.xg && a.val == A.val && !longRows.nchunks && !a.accumulate && c->opt[OPT_SPMM_EDGE_SPLIT] && !c->agg_static_ghosts) {
         a.idx = es.idx;
         a.val = es.val;
         Timed t(c, "spmm", c->compute);
@@ -389,13 +389,13 @@ static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tens
         a.xg = bf.xg;
     }
     a.accumulate = accumulate;
-    a.order = (c->opt["spmm_order"] >= 2 || (c->opt["spmm_order"] == 1 && A.skew)) ? A.order : nullptr;
+    a.order = (c->opt[OPT_SPMM_ORDER] >= 2 || (c->opt[OPT_SPMM_ORDER] == 1 && A.skew)) ? A.order : nullptr;
     // GAT rewrites forwardAdj's values (the record is recognised by identity: A is a reference into c->adj, never a copy)
     const bool static_vals = val == A.val && !(c->gnn == DORY_GAT && &A == &c->adj[ADJ_IN]);
     const bool layouts = (static_vals || row_scale) && c->N > 0 && a.ld >= 32;   // K1s / K1b gather through copies of the static adjacency
     int rc = SPMM_NOT_MINE;
-    if (layouts && c->opt["spmm_variant"] == 2) rc = spmm_k1s(c, A, a, row_scale, bf);
-    if (rc == SPMM_NOT_MINE && layouts && c->opt["spmm_variant"] >= 1 && !bf16) rc = spmm_k1b(c, A, a, row_scale);
+    if (layouts && c->opt[OPT_SPMM_VARIANT] == 2) rc = spmm_k1s(c, A, a, row_scale, bf);
+    if (rc == SPMM_NOT_MINE && layouts && c->opt[OPT_SPMM_VARIANT] >= 1 && !bf16) rc = spmm_k1b(c, A, a, row_scale);
     if (rc == SPMM_NOT_MINE) rc = spmm_k1(c, A, a, bf);
     return rc;
 }
@@ -409,8 +409,8 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
     Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
     // opt-in "gcn_bf16_gather" (no reference counterpart): 1 = the forward aggregations read bf16 rows, 2 = the backward
     // ones too (spmm(): fp32 sums, same order).  K1b has no bf16 form: an explicit spmm_variant = 1 is refused
-    const int64_t bfm = c->opt["gcn_bf16_gather"];
-    if (bfm && c->opt["spmm_variant"] == 1)
+    const int64_t bfm = c->opt[OPT_GCN_BF16_GATHER];
+    if (bfm && c->opt[OPT_SPMM_VARIANT] == 1)
         return fail(c, DORY_ERR_ARG, "aggregate: gcn_bf16_gather = %lld with spmm_variant = 1 (K1b has no bf16 form: spmm_variant 0 or 2)",
                     (long long)bfm);
     const bool bf_fwd = bfm >= 1, bf_bwd = bfm >= 2;
@@ -434,7 +434,7 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
         // default here): in full-graph training ah@0 = A_hat [x ; fg@0] is a constant of the run -- x and fg@0 come
         // from files, the adjacency never changes -- and with 288 GB of HBM it can simply stay.  The aggregation of
         // layer 0 is skipped while nothing it reads has been written through this ABI since it was last computed.
-        const bool cache = layer == 0 && c->opt["gcn_cache_ah0"] && !c->capturing;
+        const bool cache = layer == 0 && c->opt[OPT_GCN_CACHE_AH0] && !c->capturing;
         if (cache && c->ah0_valid) { c->ah0_skips++; return DORY_OK; }
         if (layer == 0) c->ah0_valid = false;
         c->agg_static_ghosts = layer == 0;
@@ -473,7 +473,7 @@ struct GatmhSweep {
     int plan(dory_ctx *c, const DerivedAdj &layout, const SpmmArgs &sa /* N, ld: as in the caller's own sweep_supported test */, uint32_t K,
              uint32_t D, bool ghosts, int shl, int pass, bool bf16) {
         S = &layout;
-        const bool wide = bf16 && c->opt["gatmh_bf16_wide"] == 1 && gatmh_wide_applies(K, D, sa.ld) && sweep_supported(sa, layout, GATMH_WIDE_GROUP);
+        const bool wide = bf16 && c->opt[OPT_GATMH_BF16_WIDE] == 1 && gatmh_wide_applies(K, D, sa.ld) && sweep_supported(sa, layout, GATMH_WIDE_GROUP);
         const int group = wide ? GATMH_WIDE_GROUP : gatmh_sweep_group(sa.ld);
         sw = sweep_launch(c, layout, sa.ld, group, ghosts, wide ? GATMH_WIDE_ROWS : gatmh_sweep_rows(layout, group, shl, pass), bf16, wide);
         return sw.done ? (int)DORY_OK : fail(c, DORY_ERR_ARG, "multi-head GAT sweep: gate counters not allocated (preallocate)");
@@ -498,11 +498,11 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
     const uint32_t K = c->heads[fl];
     AGG_NEED(z, fl, "z"); AGG_NEED(el, fl, "el"); AGG_NEED(er, fl, "er"); AGG_NEED(m, fl, "m"); AGG_NEED(den, fl, "den"); AGG_NEED(o, fl, "o");
     const uint32_t D = z->cols / K;
-    const int64_t bfm = c->opt["gatmh_bf16_gather"];
+    const int64_t bfm = c->opt[OPT_GATMH_BF16_GATHER];
     {
         Timed t(c, "spmm", c->compute);
         const BlockedAdj &Bf = gatmh_blocked_for(In, z->ld);
-        const bool blocked = c->opt["gatmh_blocked"] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
+        const bool blocked = c->opt[OPT_GATMH_BLOCKED] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
                              (D % 4 == 0 || K == 1) &&
                              (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
         AGG_NEED(fgz, fl, "fg_z"); AGG_NEED(fgel, fl, "fg_el");
@@ -513,14 +513,14 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
         // partition they would refuse takes the blocked kernels instead of failing, as spmm() does)
         SpmmArgs sa{};
         sa.N = c->N; sa.ld = z->ld;
-        const bool sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
+        const bool sweep = c->opt[OPT_GATMH_SWEEP] && c->opt[OPT_SPMM_VARIANT] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
                            shl != 0 && op && dpos && sweep_supported(sa, Sf, gatmh_sweep_group(z->ld));
         const bool bf16 = bfm >= 1;
         if (bf16 && !sweep)
             return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
                         (long long)bfm,
-                        !c->opt["gatmh_sweep"] ? "gatmh_sweep = 0" :
-                        c->opt["spmm_variant"] != 2 ? "spmm_variant is not 2" :
+                        !c->opt[OPT_GATMH_SWEEP] ? "gatmh_sweep = 0" :
+                        c->opt[OPT_SPMM_VARIANT] != 2 ? "spmm_variant is not 2" :
                         !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
                         (!op || !dpos) ? "tensors op / dpos missing" : "the sweep layout of the in-edges does not apply to this graph");
         if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 0;
@@ -553,7 +553,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             // "gatmh_fused_stats" (default 1): the blocks' own online softmax + a merge in the reduce kernel instead
             // of a statistics pass over all edges first; the blocks' (m_b, den_b) live in the scratch buffer
             float *stat_partial = nullptr;
-            if (c->opt["gatmh_fused_stats"]) {
+            if (c->opt[OPT_GATMH_FUSED_STATS]) {
                 int rc = ensure_scratch(c, (size_t)2 * Bf.nb * c->N * el->ld * sizeof(float));
                 if (rc) return rc;
                 stat_partial = c->scratch;
@@ -561,7 +561,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             HIPCK(c, launch_gatmh_forward_blocked(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Bf, z->d,
                                                   fgz->d, el->d, fgel->d, er->d, o->d, m->d, den->d, c->partial,
                                                   In.ghosts > 0, c->compute, stat_partial,
-                                                  c->opt["gatmh_el_on_the_fly"] ? c->weights[fl]["a_l"].d : nullptr));
+                                                  c->opt[OPT_GATMH_EL_ON_THE_FLY] ? c->weights[fl]["a_l"].d : nullptr));
         }
         else if (c->numNodes > 1)
             return fail(c, DORY_ERR_ARG, "multi-head GAT: a partitioned run needs the source-blocked kernels (gatmh_blocked = 1, K*D a shape they cover)");
@@ -651,7 +651,7 @@ static int gatmh_backward_blocked(dory_ctx *c, const GatmhBwd &T, const BlockedA
                                                    c->adj[ADJ_IN].ghosts > 0, c->compute,
                                                    // (el from the gathered row only where the forward formed its statistics that
                                                    //  way too: its ELFLY form needs the fused statistics -- same rounding of alpha)
-                                                   (c->opt["gatmh_el_on_the_fly"] && c->opt["gatmh_fused_stats"]) ? c->weights[T.fl]["a_l"].d : nullptr));
+                                                   (c->opt[OPT_GATMH_EL_ON_THE_FLY] && c->opt[OPT_GATMH_FUSED_STATS]) ? c->weights[T.fl]["a_l"].d : nullptr));
     }
     if (T.phase == 1) return DORY_OK;
     int rc = gatmh_backward_exchange(c, T);
@@ -675,16 +675,16 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     AGG_NEED(dO, fl, "do"); AGG_NEED(dz, fl, "dz"); AGG_NEED(tt, fl, "t"); AGG_NEED(del, fl, "del"); AGG_NEED(der, fl, "der");
     AGG_NEED(st, fl, "st"); AGG_NEED(fgz, fl, "fg_z"); AGG_NEED(fgel, fl, "fg_el"); AGG_NEED(bgdo, fl, "bg_do"); AGG_NEED(bgst, fl, "bg_st");
     const uint32_t D = z->cols / K;
-    const GatmhBwd T{fl, K, D, c->opt["gatmh_bwd_phase"], z, el, er, m, den, o, dO, dz, tt, del, der, st, fgz, fgel, bgdo, bgst};
-    const int64_t bfm = c->opt["gatmh_bf16_gather"];
+    const GatmhBwd T{fl, K, D, c->opt[OPT_GATMH_BWD_PHASE], z, el, er, m, den, o, dO, dz, tt, del, der, st, fgz, fgel, bgdo, bgst};
+    const int64_t bfm = c->opt[OPT_GATMH_BF16_GATHER];
     const int shl = gatmh_sweep_hl(K, D, z->ld);
     Tensor *op = find(c, fl, "op"), *dpos = find(c, fl, "dpos");
-    const bool dst_rowwise = c->opt["gatmh_sweep"] && shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] &&
+    const bool dst_rowwise = c->opt[OPT_GATMH_SWEEP] && shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] &&
                              ((z->ld >> 2) % (uint32_t)shl) == 0;
     const DerivedAdj &So = Out.swp;
     SpmmArgs sa{};     // the launchers' addressing tests (rows and the 16-byte statistics records through buffer resources): a
     sa.N = c->N; sa.ld = z->ld;   // partition they would refuse takes the blocked kernels
-    const bool src_sweep = c->opt["gatmh_sweep"] && c->opt["spmm_variant"] == 2 && shl && So.built && !So.na && So.nb > 0 &&
+    const bool src_sweep = c->opt[OPT_GATMH_SWEEP] && c->opt[OPT_SPMM_VARIANT] == 2 && shl && So.built && !So.na && So.nb > 0 &&
                            ((z->ld >> 2) % (uint32_t)shl) == 0 && sweep_supported(sa, So, gatmh_sweep_group(z->ld)) &&
                            (uint64_t)std::max(c->N, Out.ghosts) * K * 16u < (1ull << 32) && K * 16u < (1u << 24);
     // bf16 rows of do / bg_do for the source-side sweep (gatmh_bf16_gather = 2): refused, before anything is launched, where
@@ -692,8 +692,8 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     const bool bf16 = bfm >= 2;
     if (bf16 && !(dst_rowwise && src_sweep))
         return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = 2 needs the sweep forms of the backward pass, which this call would not take: %s",
-                    !c->opt["gatmh_sweep"] ? "gatmh_sweep = 0" :
-                    c->opt["spmm_variant"] != 2 ? "spmm_variant is not 2" :
+                    !c->opt[OPT_GATMH_SWEEP] ? "gatmh_sweep = 0" :
+                    c->opt[OPT_SPMM_VARIANT] != 2 ? "spmm_variant is not 2" :
                     !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
                     !dst_rowwise ? "this layer's forward pass did not run the sweep form" : "the sweep layout of the out-edges does not apply to this graph");
     int rc;
@@ -712,7 +712,7 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     if (dst_rowwise && src_sweep) return gatmh_backward_sweep(c, T, op, dpos, shl, sa, bf16);
     const BlockedAdj &Bbi = gatmh_blocked_for(In, z->ld), &Bbo = gatmh_blocked_for(Out, z->ld);
     const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
-    if (c->opt["gatmh_blocked"] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na && nbmax > 0 &&
+    if (c->opt[OPT_GATMH_BLOCKED] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na && nbmax > 0 &&
         gatmh_backward_blocked_ok(K, D, z->ld) &&
         (size_t)nbmax * c->N * (z->ld + K) * sizeof(float) <= c->partial_bytes)
         return gatmh_backward_blocked(c, T, Bbi, Bbo);
@@ -741,7 +741,7 @@ static int aggregate_gat(dory_ctx *c, uint32_t fl, int dir) {
     // weights), the backward reuses it: two aggregations per layer and epoch instead of three ("gat_reuse_nsum"; a caller who
     // replaced z / fg_z / "A" / "dA" in between gets the general path).
     Tensor *nsum = find(c, fl, "nsum"), *ones = find(c, 0, "ones");
-    const bool reuse = c->opt["gat_reuse_nsum"] && nsum && ones && fl < c->gat_nsum_valid.size() && z->ld == nsum->ld;
+    const bool reuse = c->opt[OPT_GAT_REUSE_NSUM] && nsum && ones && fl < c->gat_nsum_valid.size() && z->ld == nsum->ld;
     if (dir == DORY_FORWARD) {
         AGG_NEED(ah, fl, "ah");
         Tensor *arow = find(c, fl, "arow");
@@ -927,7 +927,7 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
         NEED(arow, fl, "arow");
         NEED(azrow, fl, "azrow");
         Timed t(c, "edge", c->compute);
-        const bool lazy = c->opt["gat_lazy_edge_tensors"] != 0;
+        const bool lazy = c->opt[OPT_GAT_LAZY_EDGE_TENSORS] != 0;
         HIPCK(c, launch_edge_forward_gat(c->N, F, c->adj[ADJ_IN].ptr, z->d, z->ld, a.d, lazy ? nullptr : az->d, lazy ? nullptr : c->adj[ADJ_IN].val, arow->d,
                                          c->compute, azrow->d));
         for (auto &f : c->gat_arow_valid) f = 0;   // "A" now holds this layer's scores only
@@ -953,7 +953,7 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
     {
         Tensor *azrow = find(c, fl, "azrow");
         const bool have_row = azrow && c->gat_azrow_valid[fl];
-        const bool lazy = c->opt["gat_lazy_edge_tensors"] != 0 && have_row;
+        const bool lazy = c->opt[OPT_GAT_LAZY_EDGE_TENSORS] != 0 && have_row;
         if (!have_row) { int mrc = gat_materialize(c, fl, 1); if (mrc) return mrc; }   // (az comes from the caller, or is current already)
         HIPCK(c, launch_edge_backward_gat(c->N, F, c->adj[ADJ_IN].ptr, grad->d, grad->ld, az->d, a.d, lazy ? nullptr : dA->d, cw->d, drow->d, c->compute,
                                           have_row ? azrow->d : nullptr));

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/dorylus_hip.h"
+#include "options.hpp"
 #include "sweep_geometry.hpp"
 
 namespace dory {
@@ -282,7 +283,7 @@ struct dory_ctx {
     std::vector<float> lr_table_host;
 
     // options / timing
-    std::map<std::string, int64_t> opt;
+    int64_t opt[dory::OPT_COUNT] = {};   // by dory::OptionId; dory_create fills it from the table (host/options.cpp)
     bool timing = false;
     std::map<std::string, dory::Timing> times;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

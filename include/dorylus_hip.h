@@ -237,7 +237,7 @@ int dory_ctx_describe(dory_ctx *ctx, int *gnn_type, uint32_t *num_layers, uint32
 int dory_timing_enable(dory_ctx *ctx, int on);
 int dory_timing_get(dory_ctx *ctx, const char *family, double *total_ms, uint64_t *launches);
 int dory_timing_reset(dory_ctx *ctx);
-/* tuning knobs (e.g. "spmm_variant", "spmm_slab"); unknown keys are an error.  Read-only keys of dory_get_option:
+/* tuning knobs (e.g. "spmm_variant", "spmm_slab"); unknown keys are an error (DORY_ERR_ARG).  Read-only keys of dory_get_option:
  * "spmm_gate_timeouts" (K1s sweeps whose workgroups were not co-resident within the polling bound: the launch and the
  * context's next 16 K1s launches ran without gates -- same results, unsynchronised gather rate) and
  * "spmm_ungated_launches"; "epoch_graph_recorded".  dory_timing_get("spmm_gate_timeouts") returns the same pair
@@ -248,13 +248,13 @@ int dory_timing_reset(dory_ctx *ctx);
  * read-only "spmm_xcd_mapping_ok", "spmm_xcd_count"; when it does not hold, the first repeatable K1s launch is timed with
  * and without gates and the faster form kept ("spmm_xcd_policy": -1 nothing to decide, 0 gated, 8 ungated;
  * "spmm_xcd_gated_us" / "spmm_xcd_ungated_us"); "spmm_xcd_assume_mismatch" = 1 forces that path (tests).
- * Round 6: "spmm_edge_split" (default 1; before dory_graph_upload): K1 on GCN partitions with ghosts walks a local-first copy
- * of every row's edges, so that an exchange in flight hides under the local-source part of EVERY row; "spmm_sweep_cus"
- * (before dory_graph_upload): workgroups per sweep and XCD of the gated sweeps, for contexts that share a device
- * (dory_comm_init_local); "local_timeout_ms"; "spmm_order" = 3 (before the upload): rows by median source id (experiment);
- * "gatmh_src_window_kb": the 8-head GAT's out-edge sweep layout on its own source window; "gat_reuse_nsum" (default 1): the GAT
- * prototype's backward dA-weighted aggregation from the forward's unweighted neighbour sum (tensor "nsum") instead of a third sweep.  The timing family
- * "spmm_local_first" is the first launch of a two-launch aggregation when no exchange is in flight ("spmm_blk_force_split"). */
+ * Every key -- the options with their defaults, accepted values, model and when the library reads them (every call, at
+ * dory_graph_upload, at dory_preallocate, when a layout is built, by the engine), the read-only keys and the action -- is a
+ * record of one table: dorylus_amd/host/options.cpp, ids in dorylus_amd/csrc/options.hpp; dory_option_spec and
+ * dory_option_check (dorylus_host.h) enumerate and ask it without a context.  Two options are refused once a graph is uploaded
+ * ("spmm_sweep_cus", "halo_direct_recv"); the others that the table marks as read at the upload or at a layout's build are
+ * accepted later and reach what is built from then on.  The timing family "spmm_local_first" is the first launch of a
+ * two-launch aggregation when no exchange is in flight ("spmm_blk_force_split"). */
 int dory_set_option(dory_ctx *ctx, const char *key, int64_t value);
 int dory_get_option(dory_ctx *ctx, const char *key, int64_t *value);
 /* Diagnostic (no reference counterpart): hold `workgroups` whole CUs for `usec` microseconds with a sleeping kernel on

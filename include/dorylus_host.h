@@ -148,6 +148,19 @@ int dory_sweep_deal_weighted(uint32_t items, const uint64_t *weights, uint32_t r
  * group under option spmm_sweep_rows = rows_option, [10] whether its 16-lane row count has a wide form.  0 = ok. */
 int dory_sweep_geometry(uint32_t positions, uint32_t ld, int group, int rows, int wide, uint32_t cus, uint32_t nblocks,
                         uint32_t layout_rows, int rows_option, uint64_t *out);
+/* Option introspection (tests, tools; no context needed): the table of the keys of dory_set_option / dory_get_option --
+ * dorylus_amd/host/options.cpp, dorylus_amd/csrc/options.hpp.  dory_option_spec: record `index` (0, 1, ... until DORY_ERR_ARG;
+ * options first, then the read-only keys, then the action "spmm_gates_rearm"); any pointer may be NULL.  kind: 0 option, 1
+ * read-only, 2 action.  def: the value dory_create gives an option.  lo..hi: the accepted values (lo > hi: any int64_t).
+ * gnn: -1, or the dory_gnn a nonzero value needs.  fixed_by_graph: refused once a graph is uploaded.  read: when the library
+ * reads it -- 0 every call, 1 dory_graph_upload, 2 dory_preallocate (and the calls after it), 3 when a blocked / sweep layout
+ * is built (dory_preallocate or the first aggregation that needs one), 4 dory_engine_run. */
+int dory_option_spec(uint32_t index, const char **name, int *kind, int64_t *def, int64_t *lo, int64_t *hi, int *gnn,
+                     int *fixed_by_graph, int *read);
+/* What dory_set_option(name, value) answers on a context of model gnn that is / is not configured and has / has no graph:
+ * DORY_OK, or DORY_ERR_ARG and the refusal in msg (n bytes).  "spmm_sweep_cus" is the exception: its range, 0..CUs per XCD, is
+ * the device's and only the context checks it. */
+int dory_option_check(const char *name, int64_t value, int gnn, int configured, int has_graph, char *msg, size_t n);
 
 #ifdef __cplusplus
 }
