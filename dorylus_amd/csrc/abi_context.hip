@@ -778,7 +778,11 @@ int dory_tensor_fill_uniform(dory_ctx *c, uint32_t layer, const char *name, uint
     Tensor *t = name ? find(c, layer, name) : nullptr;
     if (!t) return fail(c, DORY_ERR_ARG, "tensor_fill: no tensor '%s' at layer %u", name ? name : "(null)", layer);
     if (layer == 0) c->ah0_valid = false;
+    // (as in dory_tensor_upload: the caller's values replace what the stages kept of the tensor)
+    if (!strcmp(name, "A")) for (auto &f : c->gat_arow_valid) f = 0;
+    if (!strcmp(name, "dA") && layer < c->gat_drow_valid.size()) c->gat_drow_valid[layer] = 0;
     if ((!strcmp(name, "z") || !strcmp(name, "fg_z")) && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;
+    { int hrc = gat_edge_tensor_hook(c, layer, name, true); if (hrc) return hrc; }
     uint32_t *ids = nullptr;
     const HaloPlan *wire = nullptr;
     { int prc = ghost_wire_plan(c, "tensor_fill", name, *t, &wire); if (prc) return prc; }

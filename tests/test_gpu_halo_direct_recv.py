@@ -284,7 +284,11 @@ def test_local_transport_gat_prototype_direct_recv(da):
     real permutation (a rank of parts_toy60_p2 has a single peer: its rows arrive in slot order).  parts_toy60_p4_hash is not
     a case here: the prototype's aTg@0 misses the element-wise criterion on it with the option OFF already (measured: 2.57
     times the bound with option 0, 1.84 with option 1, 2.58 under K1 either way; max-norm 1.7e-6) -- a property of that graph
-    and the prototype's fp32 sums that this option neither causes nor cures"""
+    and the prototype's fp32 sums that this option neither causes nor cures.  Since established as rounding on a cancelling
+    sum, not a kernel error: the fp32 C oracle's own epoch misses the same criterion there against a float64 epoch (1.2 times,
+    tests/test_gat_stage_reference.py), and stage by stage on the oracle epoch's inputs the GPU's aTg@0 sits at 0.27 of the
+    bound derived from the magnitudes summed (0.009 of this criterion; the oracle: 0.29 and 0.018) --
+    tests/test_gpu_gat_stage.py::test_open_case_p4_hash_per_stage is that graph's GAT-prototype coverage"""
     from helpers import assert_parity, oracle_gat_epoch_parts
     from local_ranks import run_local
     from test_gpu_local_transport import _same_bits

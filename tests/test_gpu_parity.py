@@ -1249,7 +1249,8 @@ def test_gat_lazy_edge_tensors_are_the_eager_ones(da):
     """GAT prototype, gat_lazy_edge_tensors (round 6): az / A / dA hold one value per DESTINATION, so the stages keep the
     per-vertex values and write the per-edge tensors only when somebody reads them (download, raw pointer, K1's per-edge
     path).  After the same epoch the tensors a caller can see are the eager run's, bit for bit -- through
-    dory_tensor_download and through the dory_tensor_info pointer -- and a caller's own "az" still drives the backward."""
+    dory_tensor_download and through the dory_tensor_info pointer.  (That a caller's own "az" still drives the backward is
+    checked where one is uploaded: tests/test_gpu_gat_stage.py, test_edge_stage and test_cached_state_follows_the_caller.)"""
     import ctypes as C
     import partition_oracle as po
     from helpers import make_ctx, random_graph
