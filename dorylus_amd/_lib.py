@@ -25,12 +25,25 @@ SYMBOLS = [
     "dory_epoch_graph_begin", "dory_epoch_graph_end", "dory_epoch_graph_launch", "dory_epoch_graph_drop",
     "dory_gatmh_heads", "dory_transform_first_active", "dory_transform_first_layer",
     "dory_comm_set_host_transport", "dory_comm_init_local", "dory_debug_occupy_cus",
+    "dory_halo_wire_ids", "dory_scatter_msgs_layout", "dory_scatter_msgs_pack", "dory_scatter_msgs_deliver", "dory_scatter_msgs_unpack",
+    "dory_scatter_msgs_finish",
+    "dory_comm_set_scatter_transport",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
 ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                            C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_uint64)
+
+
+
+class ScatterMsg(C.Structure):
+    """struct dory_scatter_msg: one message of an exchange inside one buffer"""
+    _fields_ = [("peer", C.c_uint32), ("first_row", C.c_uint32), ("rows", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+# scatter transport callback (include/dorylus_hip.h)
+SCATTER_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ScatterMsg), C.c_uint32)
 
 FORWARD, BACKWARD = 0, 1
 GCN, GAT, GATMH = 0, 1, 2
@@ -96,6 +109,13 @@ def load():
         "dory_gatmh_heads": [vp, vp],
         "dory_comm_set_host_transport": [vp, ALLTOALLV_FN, ALLREDUCE_FN, vp],
         "dory_comm_init_local": [vp, C.c_uint32],
+        "dory_halo_wire_ids": [vp, vp, vp, vp],
+        "dory_scatter_msgs_layout": [vp, u32, i32, cp, u64, C.POINTER(ScatterMsg), u32, C.POINTER(u32), C.POINTER(u64)],
+        "dory_scatter_msgs_pack": [vp, u32, i32, cp, u64, vp],
+        "dory_scatter_msgs_deliver": [vp, cp, C.POINTER(vp), C.POINTER(u64), u32],
+        "dory_scatter_msgs_unpack": [vp, u32, i32, cp, vp, u32],
+        "dory_scatter_msgs_finish": [vp, u32, i32, cp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
+        "dory_comm_set_scatter_transport": [vp, SCATTER_EXCHANGE_FN, ALLREDUCE_FN, vp, u64],
         # include/dorylus_host.h
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
         "dory_partition_build_from_files": [cp, u32, u32, i32, C.POINTER(vp)],
@@ -125,8 +145,9 @@ def load():
         "dory_option_check": [cp, C.c_int64, i32, i32, i32, cp, C.c_size_t],
     }
     for name, args in sig.items():
-        if name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check") and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table)
+        if (name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check", "dory_halo_wire_ids",
+                     "dory_comm_set_scatter_transport") or name.startswith("dory_scatter_msgs_")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -379,6 +400,76 @@ class Context:
                 return 1
         self._tx = (ALLTOALLV_FN(a2a), ALLREDUCE_FN(ar))      # keep the thunks alive
         self._ck(self.lib.dory_comm_set_host_transport(self.h, self._tx[0], self._tx[1], None))
+
+    # -- scatter messages: the reference's own graph-server <-> graph-server wire (include/dorylus_wire.h) -------------------
+    def halo_wire_ids(self, local_to_global, src_ghost_gvids, dst_ghost_gvids):
+        a = [np.ascontiguousarray(x, np.uint32) for x in (local_to_global, src_ghost_gvids, dst_ghost_gvids)]
+        self._ck(self.lib.dory_halo_wire_ids(self.h, *[_ptr(x) for x in a]))
+
+    def scatter_msgs_layout(self, layer, direction, name=None, max_msg_bytes=0):
+        """([(peer, first_row, rows, offset, bytes), ...], total_bytes): the messages of that exchange inside one buffer"""
+        n, total = C.c_uint32(), C.c_uint64()
+        nm = name.encode() if name else None
+        self._ck(self.lib.dory_scatter_msgs_layout(self.h, layer, direction, nm, int(max_msg_bytes), None, 0, C.byref(n), C.byref(total)))
+        arr = (ScatterMsg * max(n.value, 1))()
+        self._ck(self.lib.dory_scatter_msgs_layout(self.h, layer, direction, nm, int(max_msg_bytes), arr, n.value, C.byref(n), C.byref(total)))
+        return [(m.peer, m.first_row, m.rows, m.offset, m.bytes) for m in arr[:n.value]], total.value
+
+    def scatter_msgs_pack(self, layer, direction, dev_ptr, name=None, max_msg_bytes=0):
+        self._ck(self.lib.dory_scatter_msgs_pack(self.h, layer, direction, name.encode() if name else None, int(max_msg_bytes), C.c_void_p(dev_ptr)))
+
+    def scatter_msgs_deliver(self, msgs, name=None):
+        """msgs: whole messages (bytes, or contiguous uint8 arrays), from any senders in any order"""
+        keep = [np.frombuffer(m, np.uint8) if isinstance(m, (bytes, bytearray, memoryview)) else np.ascontiguousarray(m, np.uint8) for m in msgs]
+        ptrs = (C.c_void_p * max(len(keep), 1))(*[k.ctypes.data for k in keep])
+        sizes = (C.c_uint64 * max(len(keep), 1))(*[k.size for k in keep])
+        self._ck(self.lib.dory_scatter_msgs_deliver(self.h, name.encode() if name else None, ptrs, sizes, len(keep)))
+
+    def scatter_msgs_unpack(self, layer, direction, dev_ptr, count, name=None):
+        """`count` records (id, cols floats) that are in device memory already"""
+        self._ck(self.lib.dory_scatter_msgs_unpack(self.h, layer, direction, name.encode() if name else None, C.c_void_p(dev_ptr), int(count)))
+
+    def scatter_msgs_finish(self, layer, direction, name=None, check=True):
+        """(rows written, unknown ids, duplicates) of the round that ends; check=False: (return code, rows, unknown, duplicates)"""
+        r, u, d = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        rc = self.lib.dory_scatter_msgs_finish(self.h, layer, direction, name.encode() if name else None, C.byref(r), C.byref(u), C.byref(d))
+        if not check:
+            return rc, r.value, u.value, d.value
+        self._ck(rc)
+        return r.value, u.value, d.value
+
+    def set_scatter_transport(self, exchange, allreduce, max_msg_bytes=0):
+        """exchange(msgs: [(peer, uint8 array), ...]) sends this rank's messages and, before it returns, hands every message that
+        arrived for this rank to scatter_msgs_deliver (e.g. over gloo, as bytes); allreduce(buf) as set_host_transport's.
+        (None, None) returns to RCCL."""
+        if exchange is None:
+            self._tx = None
+            self._ck(self.lib.dory_comm_set_scatter_transport(self.h, SCATTER_EXCHANGE_FN(0), ALLREDUCE_FN(0), None, 0))
+            return
+
+        def ex(user, ctx, host_buf, msgs, n):
+            try:
+                out = []
+                for i in range(n):
+                    m = msgs[i]
+                    out.append((int(m.peer), np.ctypeslib.as_array(C.cast(host_buf + m.offset, C.POINTER(C.c_uint8)), (int(m.bytes),))))
+                exchange(out)
+                return 0
+            except Exception:       # never let an exception cross the C boundary
+                import traceback
+                traceback.print_exc()
+                return 1
+
+        def ar(user, buf, n):
+            try:
+                allreduce(np.ctypeslib.as_array(buf, (int(n),)))
+                return 0
+            except Exception:
+                import traceback
+                traceback.print_exc()
+                return 1
+        self._tx = (SCATTER_EXCHANGE_FN(ex), ALLREDUCE_FN(ar))      # keep the thunks alive
+        self._ck(self.lib.dory_comm_set_scatter_transport(self.h, self._tx[0], self._tx[1], None, int(max_msg_bytes)))
 
     def halo_exchange(self, layer, direction):
         self._ck(self.lib.dory_halo_exchange(self.h, layer, direction))

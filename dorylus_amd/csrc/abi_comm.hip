@@ -6,15 +6,18 @@
 #include <chrono>
 #include <thread>
 
+#include "../../include/dorylus_wire.h"
 #include "abi_internal.hpp"
 
 using namespace dory;
 
 namespace {
 
-// ---- which transport carries the bytes: the caller's host callbacks, else the in-process group, else RCCL ----------------
-enum class Transport { Host, Local, Rccl, None };
+// ---- which transport carries the bytes: the caller's host callbacks (dense rows, or the reference's scatter messages), else the
+// in-process group, else RCCL ----------------
+enum class Transport { Host, Scatter, Local, Rccl, None };
 Transport transport_of(const dory_ctx *c) {
+    if (c->scatter.fn && c->tx_ar) return Transport::Scatter;   // (dory_comm_set_scatter_transport: it clears tx_a2a)
     if (c->tx_a2a && c->tx_ar) return Transport::Host;   // (dory_comm_set_host_transport sets both or none)
     if (c->local) return Transport::Local;
     return c->nccl ? Transport::Rccl : Transport::None;
@@ -135,6 +138,258 @@ int ensure_exchange_buffers(dory_ctx *c, size_t send_bytes, size_t recv_bytes) {
     if (send_bytes > c->send_cap || recv_bytes > c->recv_cap) HIPCK(c, hipDeviceSynchronize());
     int rc = grow_buffer(c, &c->send_buf, &c->send_cap, send_bytes);
     return rc ? rc : grow_buffer(c, &c->recv_buf, &c->recv_cap, recv_bytes);
+}
+
+// ---- scatter messages (include/dorylus_wire.h: the reference's own graph-server <-> graph-server wire) -------------------
+// Layout: the reference's sender loop (scatterGCN, gcn_ops.cpp:237-257) over the plan's send lists.  Pack: one kernel over the
+// layout's message table.  Deliver: headers parsed and checked on the host, the records through the fixed staging area, one
+// unpack kernel per staging slot on the comm stream.  Finish: the round's counters against the ghost count, next round.
+uint32_t tensor_layer(dory_ctx *c, const Tensor *t) {
+    for (uint32_t l = 0; l < c->tensors.size(); ++l)
+        for (auto &kv : c->tensors[l])
+            if (&kv.second == t) return l;
+    return 0xFFFFFFFFu;
+}
+inline uint32_t ghost_count(const dory_ctx *c, int dir) { return c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts; }
+
+void scatter_drop_layouts(dory_ctx *c, int dir /* -1: all */) {
+    auto &L = c->scatter.layouts;
+    for (size_t i = L.size(); i-- > 0;)
+        if (dir < 0 || L[i].dir == dir) {
+            if (L[i].d_msgs) (void)hipFree(L[i].d_msgs);
+            L.erase(L.begin() + (long)i);
+        }
+}
+
+// the messages of the exchange of `cols`-wide rows with the plan of `dir` (kept: the same exchange asks again every epoch);
+// on_device: with its table uploaded for the pack kernel
+int scatter_layout(dory_ctx *c, const char *who, int dir, uint32_t cols, uint64_t max_msg, bool on_device, ScatterLayout **out) {
+    const HaloPlan &p = c->plan[dir];
+    if (!p.set) return fail(c, DORY_ERR_ARG, "%s: no plan", who);
+    if (max_msg > 0xFFFFFFFFull) return fail(c, DORY_ERR_ARG, "%s: max_msg_bytes %llu is not below 2^32", who, (unsigned long long)max_msg);
+    if (cols == 0 || cols > scatter_msgs_max_cols())
+        return fail(c, DORY_ERR_ARG, "%s: rows of %u floats (scatter messages carry 1 .. %u)", who, cols, scatter_msgs_max_cols());
+    if (max_msg == 0) max_msg = DORY_WIRE_MAX_MSG_SIZE;
+    ScatterLayout *L = nullptr;
+    for (auto &l : c->scatter.layouts)
+        if (l.dir == dir && l.cols == cols && l.max_msg == max_msg) L = &l;
+    if (!L) {
+        if (c->scatter.layouts.size() >= 32) scatter_drop_layouts(c, -1);   // (a caller sweeping message sizes: start over)
+        ScatterLayout n;
+        n.dir = dir; n.cols = cols; n.max_msg = max_msg;
+        const uint32_t batch = dory_wire_scatter_batch(cols, max_msg);
+        uint64_t end = 0;
+        for (uint32_t q = 0; q < c->numNodes; ++q) {
+            if (q == c->nodeId) continue;
+            for (uint32_t ib = 0; ib < p.send_counts[q]; ib += batch) {
+                dory_scatter_msg m;
+                m.peer = q;
+                m.first_row = p.send_off[q] + ib;
+                m.rows = std::min(batch, p.send_counts[q] - ib);
+                m.offset = (end + 15ull) & ~15ull;
+                m.bytes = dory_wire_scatter_msg_bytes(m.rows, cols);
+                if (m.bytes > 0xFFFFFFFFull) return fail(c, DORY_ERR_ARG, "%s: a message of %llu bytes (below 2^32 only)", who, (unsigned long long)m.bytes);
+                end = m.offset + m.bytes;
+                n.max_rows = std::max(n.max_rows, m.rows);
+                n.msgs.push_back(m);
+            }
+        }
+        n.total_bytes = end;
+        c->scatter.layouts.push_back(std::move(n));
+        L = &c->scatter.layouts.back();
+    }
+    if (on_device && !L->d_msgs && !L->msgs.empty()) {
+        int rc = upload_array(c, &L->d_msgs, L->msgs.data(), L->msgs.size());
+        if (rc) return rc;
+    }
+    *out = L;
+    return DORY_OK;
+}
+
+// option halo_direct_recv: ghost slot k is stored at the row the plan's wire order gives it
+int scatter_slot_rows(dory_ctx *c, int dir) {
+    ScatterState &S = c->scatter;
+    const HaloPlan &p = c->plan[dir];
+    if (S.d_slot_row[dir]) (void)hipFree(S.d_slot_row[dir]);
+    S.d_slot_row[dir] = nullptr;
+    if (!S.ids || !p.set || !p.direct) return DORY_OK;
+    std::vector<uint32_t> inv(p.recv_total);
+    for (uint32_t r = 0; r < p.recv_total; ++r) inv[p.order[r]] = r;
+    return upload_array(c, &S.d_slot_row[dir], inv.data(), inv.size());
+}
+
+int scatter_pack(dory_ctx *c, const char *who, int dir, const Tensor *src, uint32_t hdr_layer, uint64_t max_msg, void *dev_buf,
+                 hipStream_t s, ScatterLayout **layout) {
+    if (!c->scatter.ids) return fail(c, DORY_ERR_ARG, "%s: dory_halo_wire_ids first (the records carry global vertex ids)", who);
+    if ((uintptr_t)dev_buf & 15) return fail(c, DORY_ERR_ARG, "%s: the message buffer must be 16-byte aligned", who);
+    ScatterLayout *L;
+    int rc = scatter_layout(c, who, dir, src->cols, max_msg, true, &L);
+    if (rc) return rc;
+    if (layout) *layout = L;
+    if (L->msgs.empty()) return DORY_OK;
+    if (!dev_buf) return fail(c, DORY_ERR_ARG, "%s: no buffer", who);
+    const HaloPlan &p = c->plan[dir];
+    HIPCK(c, launch_scatter_msgs_pack(dev_buf, src->d, src->ld, src->cols, p.d_send_lvids, c->scatter.d_l2g, L->d_msgs, (uint32_t)L->msgs.size(),
+                                      L->max_rows, c->nodeId, hdr_layer, (uint32_t)dir, s));
+    if (!c->capturing) {
+        c->halo_rows_packed += p.send_total;
+        c->halo_floats_packed += (uint64_t)p.send_total * src->cols;
+    }
+    return DORY_OK;
+}
+
+// the ghost tensor a message names by (layer, dir), as ghostReceiverGCN / ghostReceiverGAT pick it (gcn_ops.cpp:293-302,
+// gat_ops.cpp:366-375), or `name` at the header's layer
+Tensor *scatter_ghost_of(dory_ctx *c, const char *name, uint32_t layer, uint32_t dir) {
+    if (layer >= c->tensors.size()) return nullptr;
+    if (name) return find(c, layer, name);
+    if (c->gnn == DORY_GCN) return find(c, layer, dir == DORY_FORWARD ? "fg" : "bg");
+    return find(c, layer, dir == DORY_FORWARD ? "fg_z" : "bg_d");
+}
+
+int scatter_deliver(dory_ctx *c, const char *name, const void *const *msgs, const uint64_t *bytes, uint32_t n, bool in_cb) {
+    const char *who = "scatter_msgs_deliver";
+    ScatterState &S = c->scatter;
+    if (!msgs || !bytes || n == 0) return fail(c, DORY_ERR_ARG, "%s: at least one message", who);
+    if (!S.ids) return fail(c, DORY_ERR_ARG, "%s: dory_halo_wire_ids first", who);
+    struct Parsed { Tensor *ghost; uint32_t dir, count, layer; const uint8_t *rec; };
+    std::vector<Parsed> P(n);
+    // everything is checked before anything is enqueued
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!msgs[i]) return fail(c, DORY_ERR_ARG, "%s: message %u is null", who, i);
+        if (bytes[i] < DORY_WIRE_SCATTER_HDR_SIZE)
+            return fail(c, DORY_ERR_ARG, "%s: message %u is truncated: %llu bytes, the header alone has %u", who, i, (unsigned long long)bytes[i], DORY_WIRE_SCATTER_HDR_SIZE);
+        const uint8_t *m = static_cast<const uint8_t *>(msgs[i]);
+        uint32_t recv = 0, snd = 0, cnt = 0, fd = 0, lay = 0, dr = 0;
+        if (dory_wire_parse_scatter_header(m, bytes[i], &recv, &snd, &cnt, &fd, &lay, &dr)) {
+            dory_wire_parse_fields_header(m + DORY_WIRE_NODE_ID_DIGITS, &snd, &cnt, &fd, &lay, &dr);
+            const uint64_t want = dory_wire_scatter_msg_bytes(cnt, fd);
+            if (want != bytes[i])
+                return fail(c, DORY_ERR_ARG, "%s: message %u is truncated or malformed: %llu bytes, count %u x featDim %u make %llu", who, i,
+                            (unsigned long long)bytes[i], cnt, fd, (unsigned long long)want);
+            return fail(c, DORY_ERR_ARG, "%s: message %u: the receiver field is not eight characters of %%8X", who, i);
+        }
+        if (recv != c->nodeId) return fail(c, DORY_ERR_ARG, "%s: message %u: receiver %u is not this rank (%u)", who, i, recv, c->nodeId);
+        if (dr > 1u) return fail(c, DORY_ERR_ARG, "%s: message %u: dir %u is neither forward (0) nor backward (1)", who, i, dr);
+        Tensor *ghost;
+        if (in_cb && !name) {
+            if (lay != S.cb_layer || (int)dr != S.cb_dir)
+                return fail(c, DORY_ERR_ARG, "%s: message %u: layer %u dir %u is not the exchange in progress (layer %u dir %d)", who, i, lay, dr, S.cb_layer, S.cb_dir);
+            ghost = S.cb_ghost;
+        } else {
+            if (lay >= c->tensors.size()) return fail(c, DORY_ERR_ARG, "%s: message %u: layer %u out of range", who, i, lay);
+            ghost = scatter_ghost_of(c, name, lay, dr);
+            if (!ghost) return fail(c, DORY_ERR_ARG, "%s: message %u: layer %u out of range (no ghost tensor '%s' of dir %u there)", who, i, lay,
+                                    name ? name : (c->gnn == DORY_GCN ? (dr ? "bg" : "fg") : (dr ? "bg_d" : "fg_z")), dr);
+        }
+        if (ghost->rows != ghost_count(c, (int)dr) || ghost->rows != S.gvids[dr].size())
+            return fail(c, DORY_ERR_ARG, "%s: message %u: the tensor is not a ghost tensor of dir %u", who, i, dr);
+        if (fd != ghost->cols) return fail(c, DORY_ERR_ARG, "%s: message %u: featDim %u is not the tensor's cols %u", who, i, fd, ghost->cols);
+        if (!c->plan[dr].set) return fail(c, DORY_ERR_ARG, "%s: no plan", who);
+        if (fd > scatter_msgs_max_cols() || 4ull * (1ull + fd) > S.stage_bytes)
+            return fail(c, DORY_ERR_ARG, "%s: message %u: a record of %u floats does not fit the staging area", who, i, fd);
+        P[i] = {ghost, dr, cnt, lay, m + DORY_WIRE_SCATTER_HDR_SIZE};
+    }
+    for (const Parsed &q : P) {   // what halo_tensors and dory_halo_exchange drop when these ghost rows change
+        if (q.ghost == find(c, 0, "fg")) c->ah0_valid = false;
+        if (q.ghost == find(c, q.layer, "fg_z") && q.layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[q.layer] = 0;
+    }
+    std::unique_ptr<Timed> t;
+    if (!in_cb) {   // (inside an exchange the comm stream waits already, and the exchange times itself)
+        HIPCK(c, hipEventRecord(c->ev_a, c->compute));
+        HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
+        t.reset(new Timed(c, "halo", c->comm));
+    }
+    int slot = 0;
+    size_t fill = 0;
+    const Parsed *cur = nullptr;
+    auto flush = [&]() -> int {
+        if (!fill) return DORY_OK;
+        const uint32_t d = cur->dir, recb = 4u * (1u + cur->ghost->cols);
+        HIPCK(c, hipMemcpyAsync(S.d_stage[slot], S.h_stage[slot], fill, hipMemcpyHostToDevice, c->comm));
+        HIPCK(c, launch_scatter_msgs_unpack(cur->ghost->d, cur->ghost->ld, cur->ghost->cols, S.d_stage[slot], (uint32_t)(fill / recb), S.d_gvids[d],
+                                            (uint32_t)S.gvids[d].size(), S.d_slot_row[d], S.d_stamp[d], S.round[d], S.d_counts[d], c->comm));
+        HIPCK(c, hipEventRecord(S.ev_stage[slot], c->comm));
+        S.stage_used[slot] = true;
+        S.next_slot = slot ^ 1;
+        fill = 0;
+        return DORY_OK;
+    };
+    for (const Parsed &q : P) {
+        if (cur && (cur->ghost != q.ghost || cur->dir != q.dir)) { int rc = flush(); if (rc) return rc; }
+        cur = &q;
+        const size_t recb = 4u * (size_t)(1u + q.ghost->cols);
+        uint32_t left = q.count;
+        const uint8_t *rec = q.rec;
+        while (left) {
+            if (!fill) {   // a fresh slot: free once the unpack that read it last has run
+                slot = S.next_slot;
+                if (S.stage_used[slot]) HIPCK(c, hipEventSynchronize(S.ev_stage[slot]));
+            }
+            const uint32_t take = (uint32_t)std::min<size_t>(left, (S.stage_bytes - fill) / recb);
+            std::memcpy(S.h_stage[slot] + fill, rec, take * recb);
+            fill += take * recb;
+            rec += take * recb;
+            left -= take;
+            if (S.stage_bytes - fill < recb) { int rc = flush(); if (rc) return rc; }
+        }
+    }
+    return flush();
+}
+
+int scatter_finish(dory_ctx *c, int dir, uint32_t *rows, uint32_t *unknown, uint32_t *duplicate) {
+    ScatterState &S = c->scatter;
+    uint32_t h[3] = {0, 0, 0};
+    HIPCK(c, hipMemcpyAsync(h, S.d_counts[dir], sizeof(h), hipMemcpyDeviceToHost, c->comm));
+    HIPCK(c, hipMemsetAsync(S.d_counts[dir], 0, sizeof(h), c->comm));
+    HIPCK(c, hipStreamSynchronize(c->comm));
+    if (++S.round[dir] == 0) S.round[dir] = 1;   // (the stamps start at 0: never a round's number)
+    if (rows) *rows = h[0];
+    if (unknown) *unknown = h[1];
+    if (duplicate) *duplicate = h[2];
+    const uint32_t G = (uint32_t)S.gvids[dir].size();
+    if (h[0] != G || h[1] || h[2])
+        return fail(c, DORY_ERR_COMM, "scatter_msgs_finish: %u of %u ghost rows of dir %d written, %u records with unknown ids, %u duplicates", h[0], G, dir, h[1], h[2]);
+    return DORY_OK;
+}
+
+int scatter_send_buffers(dory_ctx *c, size_t bytes) {
+    ScatterState &S = c->scatter;
+    if (bytes <= S.send_cap) return DORY_OK;
+    HIPCK(c, hipDeviceSynchronize());
+    if (S.d_send) (void)hipFree(S.d_send);
+    if (S.h_send) (void)hipHostFree(S.h_send);
+    S.d_send = S.h_send = nullptr; S.send_cap = 0;
+    HIPCK(c, hipMalloc((void **)&S.d_send, bytes));
+    HIPCK(c, hipHostMalloc((void **)&S.h_send, bytes, hipHostMallocDefault));
+    S.send_cap = bytes;
+    return DORY_OK;
+}
+
+// the scatter transport's arm of an exchange (the comm stream waits for the producer of `src` already): pack the messages, copy
+// them to pinned host memory, let the caller's function send them and deliver what arrived, finish the round
+int exchange_scatter(dory_ctx *c, int dir, Tensor *src, Tensor *ghost) {
+    ScatterState &S = c->scatter;
+    if (src->cols != ghost->cols) return fail(c, DORY_ERR_ARG, "halo_exchange: widths of source (%u) and ghost tensor (%u) differ", src->cols, ghost->cols);
+    if (!S.ids) return fail(c, DORY_ERR_ARG, "halo_exchange: the scatter transport needs dory_halo_wire_ids");
+    const uint32_t hdr_layer = tensor_layer(c, ghost);
+    ScatterLayout *L;
+    int rc = scatter_layout(c, "halo_exchange", dir, src->cols, S.max_msg, true, &L);
+    if (rc) return rc;
+    if ((rc = scatter_send_buffers(c, (size_t)L->total_bytes))) return rc;
+    if ((rc = scatter_pack(c, "halo_exchange", dir, src, hdr_layer, S.max_msg, S.d_send, c->comm, nullptr))) return rc;
+    if (L->total_bytes) HIPCK(c, hipMemcpyAsync(S.h_send, S.d_send, (size_t)L->total_bytes, hipMemcpyDeviceToHost, c->comm));
+    HIPCK(c, hipStreamSynchronize(c->comm));
+    S.cb_thread = std::this_thread::get_id();
+    S.cb_ghost = ghost; S.cb_layer = hdr_layer; S.cb_dir = dir;
+    S.in_cb.store(true, std::memory_order_release);
+    const int cb = S.fn(c->tx_user, c, S.h_send, L->msgs.data(), (uint32_t)L->msgs.size());
+    S.in_cb.store(false, std::memory_order_release);
+    S.cb_ghost = nullptr;
+    const std::string cb_err = c->err;   // (a refusal of dory_scatter_msgs_deliver inside the callback: keep its text)
+    rc = scatter_finish(c, dir, nullptr, nullptr, nullptr);
+    if (cb) return fail(c, DORY_ERR_COMM, "halo_exchange: scatter transport exchange failed (%d)%s%s", cb, cb_err.empty() ? "" : ": ", cb_err.c_str());
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -329,6 +584,7 @@ template <typename PeerBuf>
 int allreduce_sum(dory_ctx *c, const char *who, float *buf, uint64_t n, PeerBuf peer_buf) {
     switch (transport_of(c)) {
     case Transport::Host:
+    case Transport::Scatter:   // (the gradient sum is the host transport arm's)
         c->tx_send.resize(n);
         HIPCK(c, hipMemcpyAsync(c->tx_send.data(), buf, n * sizeof(float), hipMemcpyDeviceToHost, c->compute));
         HIPCK(c, hipStreamSynchronize(c->compute));
@@ -428,6 +684,21 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     if (tr == Transport::None) return fail(c, DORY_ERR_COMM, "halo_exchange: dory_comm_init not called");
     if (tr == Transport::Rccl && c->nranks != (int)c->numNodes) return fail(c, DORY_ERR_COMM, "halo_exchange: communicator size != num_nodes");
     if (src->ld != ghost->ld) return fail(c, DORY_ERR_ARG, "halo_exchange: row widths of source and ghost tensor differ");
+    if (tr == Transport::Scatter) {   // messages of (id, cols floats) records: no row wire, no receive buffer; scheduled as the host arm is
+        HIPCK(c, hipEventRecord(c->ev_a, c->compute));
+        HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
+        const bool deferred = defer && c->opt[OPT_HALO_OVERLAP];
+        {
+            Timed t(c, "halo", c->comm);
+            Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);
+            int rc = exchange_scatter(c, dir, src, ghost);
+            if (rc) return rc;
+        }
+        HIPCK(c, hipEventRecord(c->ev_b, c->comm));
+        if (deferred) c->halo_pending = true;
+        else HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
+        return DORY_OK;
+    }
     RowWire wire;
     { int rc = row_wire(c, "halo_exchange", src, ghost, true, nullptr, &wire); if (rc) return rc; }
     const uint32_t w = wire.w;
@@ -475,6 +746,18 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     if (deferred) c->halo_pending = true;
     else HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
     return DORY_OK;
+}
+
+void scatter_free(dory_ctx *c) {
+    ScatterState &S = c->scatter;
+    scatter_drop_layouts(c, -1);
+    for (void *p : {(void *)S.d_l2g, (void *)S.d_gvids[0], (void *)S.d_gvids[1], (void *)S.d_slot_row[0], (void *)S.d_slot_row[1], (void *)S.d_stamp[0],
+                    (void *)S.d_stamp[1], (void *)S.d_counts[0], (void *)S.d_counts[1], (void *)S.d_stage[0], (void *)S.d_stage[1], (void *)S.d_send})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)S.h_stage[0], (void *)S.h_stage[1], (void *)S.h_send})
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : {S.ev_stage[0], S.ev_stage[1]})
+        if (e) (void)hipEventDestroy(e);
 }
 
 void epoch_graph_drop_locked(dory_ctx *c) {
@@ -584,6 +867,8 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
         if ((rc = upload_array(c, &p.d_unpack_slots, ident.data(), p.recv_total))) return rc;
     }
     p.set = true;
+    scatter_drop_layouts(c, dir);   // (scatter messages: the message tables follow the send lists, the slot -> row map the wire order)
+    if ((rc = scatter_slot_rows(c, dir))) return rc;
     // pack / receive buffers for the widest row any layer exchanges, now, so that no allocation (and no device-wide
     // synchronisation) happens inside an epoch
     uint32_t w = 0;
@@ -603,7 +888,37 @@ int dory_comm_set_host_transport(dory_ctx *c, dory_alltoallv_fn alltoallv, dory_
     c->tx_a2a = alltoallv;
     c->tx_ar = allreduce_sum;
     c->tx_user = user;
+    c->scatter.fn = nullptr;   // (setting one transport clears the other)
     return DORY_OK;
+}
+
+int dory_comm_set_scatter_transport(dory_ctx *c, dory_scatter_exchange_fn exchange, dory_allreduce_fn allreduce_sum, void *user, uint64_t max_msg_bytes) {
+    CHECK_CTX(c);
+    if ((exchange == nullptr) != (allreduce_sum == nullptr)) return fail(c, DORY_ERR_ARG, "set_scatter_transport: both callbacks or none");
+    if (max_msg_bytes > 0xFFFFFFFFull) return fail(c, DORY_ERR_ARG, "set_scatter_transport: max_msg_bytes %llu is not below 2^32", (unsigned long long)max_msg_bytes);
+    c->scatter.fn = exchange;
+    c->scatter.max_msg = max_msg_bytes;
+    c->tx_a2a = nullptr;
+    c->tx_ar = allreduce_sum;
+    c->tx_user = user;
+    if (!exchange) return DORY_OK;
+    // the send buffers for the widest row any layer exchanges, now (as dory_halo_plan sizes the dense ones), where the plans exist
+    uint32_t w = 1;
+    for (uint32_t l = 0; l <= c->L && l < c->dims.size(); ++l) {
+        w = std::max(w, c->dims[l]);
+        if (c->gnn == DORY_GATMH && l < c->L && l < c->heads.size()) w = std::max(w, std::max(c->dims[l + 1], 4u) * c->heads[l]);
+    }
+    size_t need = 0;
+    for (int dir = 0; dir < 2 && w <= scatter_msgs_max_cols(); ++dir) {
+        if (!c->plan[dir].set) continue;
+        const uint32_t batch = dory_wire_scatter_batch(w, max_msg_bytes);
+        uint64_t end = 0;
+        for (uint32_t q = 0; q < c->numNodes; ++q)
+            for (uint32_t ib = 0; ib < c->plan[dir].send_counts[q]; ib += batch)
+                end = ((end + 15ull) & ~15ull) + dory_wire_scatter_msg_bytes(std::min(batch, c->plan[dir].send_counts[q] - ib), w);
+        need = std::max(need, (size_t)end);
+    }
+    return scatter_send_buffers(c, need);
 }
 
 int dory_comm_unique_id(void *id128) {
@@ -689,6 +1004,161 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
     return split_rows(c, "halo_unpack_tensor", false, dir, nullptr, ghost, const_cast<float *>(recv_buf));
 }
 
+// ---- scatter messages: the entry points (helpers above) ------------------------------------------------------------------
+int dory_halo_wire_ids(dory_ctx *c, const uint32_t *local_to_global, const uint32_t *src_ghost_gvids, const uint32_t *dst_ghost_gvids) {
+    CHECK_CTX(c);
+    if (!c->configured || !c->has_graph) return fail(c, DORY_ERR_ARG, "halo_wire_ids: configure + graph_upload first");
+    if (c->N && !local_to_global) return fail(c, DORY_ERR_ARG, "halo_wire_ids: no local_to_global");
+    const uint32_t *gv[2] = {src_ghost_gvids, dst_ghost_gvids};
+    for (int dir = 0; dir < 2; ++dir) {
+        const uint32_t G = ghost_count(c, dir);
+        if (G && !gv[dir]) return fail(c, DORY_ERR_ARG, "halo_wire_ids: no ghost ids of dir %d (%u ghosts)", dir, G);
+        for (uint32_t k = 1; k < G; ++k)
+            if (gv[dir][k - 1] >= gv[dir][k])
+                return fail(c, DORY_ERR_ARG, "halo_wire_ids: the ghost ids of dir %d are not ascending (slot %u: %u, then %u)", dir, k - 1, gv[dir][k - 1], gv[dir][k]);
+    }
+    ScatterState &S = c->scatter;
+    HIPCK(c, hipDeviceSynchronize());
+    for (uint32_t **p : {&S.d_l2g, &S.d_gvids[0], &S.d_gvids[1], &S.d_stamp[0], &S.d_stamp[1], &S.d_counts[0], &S.d_counts[1]}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    S.ids = false;
+    int rc;
+    if ((rc = upload_array(c, &S.d_l2g, local_to_global, c->N))) return rc;
+    for (int dir = 0; dir < 2; ++dir) {
+        const uint32_t G = ghost_count(c, dir);
+        S.gvids[dir].assign(gv[dir], gv[dir] + G);
+        if ((rc = upload_array(c, &S.d_gvids[dir], gv[dir], G))) return rc;
+        HIPCK(c, hipMalloc((void **)&S.d_stamp[dir], G ? (size_t)G * sizeof(uint32_t) : 256));
+        HIPCK(c, hipMemset(S.d_stamp[dir], 0, G ? (size_t)G * sizeof(uint32_t) : 256));
+        HIPCK(c, hipMalloc((void **)&S.d_counts[dir], 256));
+        HIPCK(c, hipMemset(S.d_counts[dir], 0, 256));
+        S.round[dir] = 1;
+    }
+    // the staging area of dory_scatter_msgs_deliver, once: a reference message (1 MiB) or the widest record any layer exchanges
+    uint32_t w = 1;
+    for (uint32_t l = 0; l <= c->L && l < c->dims.size(); ++l) {
+        w = std::max(w, c->dims[l]);
+        if (c->gnn == DORY_GATMH && l < c->L && l < c->heads.size()) w = std::max(w, std::max(c->dims[l + 1], 4u) * c->heads[l]);
+    }
+    const size_t stage = std::max<size_t>(DORY_WIRE_MAX_MSG_SIZE, ((size_t)4 * (1 + w) + 4095) & ~(size_t)4095);
+    if (stage > S.stage_bytes) {
+        for (int i = 0; i < 2; ++i) {
+            if (S.h_stage[i]) (void)hipHostFree(S.h_stage[i]);
+            if (S.d_stage[i]) (void)hipFree(S.d_stage[i]);
+            S.h_stage[i] = S.d_stage[i] = nullptr;
+        }
+        S.stage_bytes = 0;
+        for (int i = 0; i < 2; ++i) {
+            HIPCK(c, hipHostMalloc((void **)&S.h_stage[i], stage, hipHostMallocDefault));
+            HIPCK(c, hipMalloc((void **)&S.d_stage[i], stage));
+            if (!S.ev_stage[i]) HIPCK(c, hipEventCreateWithFlags(&S.ev_stage[i], hipEventDisableTiming));
+            S.stage_used[i] = false;
+        }
+        S.stage_bytes = stage;
+    }
+    S.ids = true;
+    for (int dir = 0; dir < 2; ++dir)
+        if ((rc = scatter_slot_rows(c, dir))) return rc;
+    return DORY_OK;
+}
+
+// (layer, dir, name) -> the source tensor of a pack and the layer its messages name
+static int scatter_source(dory_ctx *c, const char *who, uint32_t layer, int dir, const char *name, Tensor **src, uint32_t *hdr_layer) {
+    if (dir != 0 && dir != 1) return fail(c, DORY_ERR_ARG, "%s: dir %d", who, dir);
+    if (name) {
+        *src = find(c, layer, name);
+        if (!*src) return fail(c, DORY_ERR_ARG, "%s: no tensor '%s'@%u", who, name, layer);
+        if ((*src)->rows != c->N) return fail(c, DORY_ERR_ARG, "%s: '%s' is not a per-local-vertex tensor", who, name);
+        *hdr_layer = layer;
+        return DORY_OK;
+    }
+    Tensor *ghost;
+    int rc = halo_tensors(c, layer, dir, src, &ghost);
+    if (rc) return rc;
+    *hdr_layer = tensor_layer(c, ghost);
+    return DORY_OK;
+}
+
+int dory_scatter_msgs_layout(dory_ctx *c, uint32_t layer, int dir, const char *name, uint64_t max_msg_bytes, struct dory_scatter_msg *msgs,
+                             uint32_t max_msgs, uint32_t *n_msgs, uint64_t *total_bytes) {
+    CHECK_CTX(c);
+    Tensor *src;
+    uint32_t hdr_layer;
+    int rc = scatter_source(c, "scatter_msgs_layout", layer, dir, name, &src, &hdr_layer);
+    if (rc) return rc;
+    ScatterLayout *L;
+    if ((rc = scatter_layout(c, "scatter_msgs_layout", dir, src->cols, max_msg_bytes, false, &L))) return rc;
+    if (n_msgs) *n_msgs = (uint32_t)L->msgs.size();
+    if (total_bytes) *total_bytes = L->total_bytes;
+    if (msgs) {
+        if (max_msgs < L->msgs.size()) return fail(c, DORY_ERR_ARG, "scatter_msgs_layout: %zu messages, room for %u", L->msgs.size(), max_msgs);
+        std::copy(L->msgs.begin(), L->msgs.end(), msgs);
+    }
+    return DORY_OK;
+}
+
+int dory_scatter_msgs_pack(dory_ctx *c, uint32_t layer, int dir, const char *name, uint64_t max_msg_bytes, void *dev_buf) {
+    CHECK_CTX(c);
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    Tensor *src;
+    uint32_t hdr_layer;
+    int rc = scatter_source(c, "scatter_msgs_pack", layer, dir, name, &src, &hdr_layer);
+    if (rc) return rc;
+    Timed t(c, "halo", c->compute);
+    return scatter_pack(c, "scatter_msgs_pack", dir, src, hdr_layer, max_msg_bytes, dev_buf, c->compute, nullptr);
+}
+
+int dory_scatter_msgs_deliver(dory_ctx *c, const char *name, const void *const *msgs, const uint64_t *bytes, uint32_t n) {
+    if (!c) return DORY_ERR_ARG;
+    // from the scatter transport's callback (the thread that runs the exchange holds the lock) or from anywhere else
+    const bool in_cb = c->scatter.in_cb.load(std::memory_order_acquire) && c->scatter.cb_thread == std::this_thread::get_id();
+    std::unique_lock<std::mutex> lock(c->mu, std::defer_lock);
+    if (!in_cb) {
+        lock.lock();
+        HIPCK(c, hipSetDevice(c->device));
+        int wrc = wait_halo(c);
+        if (wrc) return wrc;
+    }
+    return scatter_deliver(c, name, msgs, bytes, n, in_cb);
+}
+
+int dory_scatter_msgs_unpack(dory_ctx *c, uint32_t layer, int dir, const char *name, const void *dev_records, uint32_t count) {
+    CHECK_CTX(c);
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    const char *who = "scatter_msgs_unpack";
+    ScatterState &S = c->scatter;
+    if (dir != 0 && dir != 1) return fail(c, DORY_ERR_ARG, "%s: dir %d", who, dir);
+    if (!S.ids || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "%s: dory_halo_wire_ids and a plan first", who);
+    Tensor *src = nullptr, *ghost = nullptr;
+    if (name) ghost = find(c, layer, name);
+    else { int rc = halo_tensors(c, layer, dir, &src, &ghost); if (rc) return rc; }
+    if (!ghost) return fail(c, DORY_ERR_ARG, "%s: no tensor '%s'@%u", who, name, layer);
+    if (ghost->rows != ghost_count(c, dir) || ghost->rows != S.gvids[dir].size())
+        return fail(c, DORY_ERR_ARG, "%s: the tensor is not a ghost tensor of dir %d", who, dir);
+    if (ghost->cols > scatter_msgs_max_cols()) return fail(c, DORY_ERR_ARG, "%s: rows of %u floats (scatter messages carry 1 .. %u)", who, ghost->cols, scatter_msgs_max_cols());
+    if (count && (!dev_records || ((uintptr_t)dev_records & 15))) return fail(c, DORY_ERR_ARG, "%s: the records must be 16-byte aligned", who);
+    const uint32_t tl = tensor_layer(c, ghost);
+    if (ghost == find(c, 0, "fg")) c->ah0_valid = false;
+    if (ghost == find(c, tl, "fg_z") && tl < c->gat_nsum_valid.size()) c->gat_nsum_valid[tl] = 0;
+    HIPCK(c, hipEventRecord(c->ev_a, c->compute));
+    HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
+    Timed t(c, "halo", c->comm);
+    HIPCK(c, launch_scatter_msgs_unpack(ghost->d, ghost->ld, ghost->cols, dev_records, count, S.d_gvids[dir], (uint32_t)S.gvids[dir].size(), S.d_slot_row[dir],
+                                        S.d_stamp[dir], S.round[dir], S.d_counts[dir], c->comm));
+    return DORY_OK;
+}
+
+int dory_scatter_msgs_finish(dory_ctx *c, uint32_t layer, int dir, const char *name, uint32_t *rows, uint32_t *unknown, uint32_t *duplicate) {
+    CHECK_CTX(c);
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    if (dir != 0 && dir != 1) return fail(c, DORY_ERR_ARG, "scatter_msgs_finish: dir %d", dir);
+    if (!c->scatter.ids) return fail(c, DORY_ERR_ARG, "scatter_msgs_finish: dory_halo_wire_ids first");
+    if (name && !find(c, layer, name)) return fail(c, DORY_ERR_ARG, "scatter_msgs_finish: no tensor '%s'@%u", name, layer);
+    return scatter_finish(c, dir, rows, unknown, duplicate);
+}
+
 // ---------------------------------------------------------------------------------------
 // The validation statistics of the last forward pass summed over all partitions: what WeightServer::updateLocalAccLoss /
 // updateGlobalAccLoss do with the AccLoss records the graph servers send (src/weight-server/weightserver.cpp:190-262:
@@ -702,7 +1172,7 @@ int dory_train_stat_global(dory_ctx *c, float *acc_sum, float *loss_sum, uint32_
     HIPCK(c, hipMemcpyAsync(h, c->d_stat, 2 * sizeof(float), hipMemcpyDeviceToHost, c->compute));
     HIPCK(c, hipStreamSynchronize(c->compute));
     h[2] = (float)c->val_rows;      // (exact below 2^24 rows per sum: Friendster's 6.6 M validation rows fit)
-    if (c->numNodes > 1 && transport_of(c) == Transport::Host) {   // the three floats are on the host already
+    if (c->numNodes > 1 && (transport_of(c) == Transport::Host || transport_of(c) == Transport::Scatter)) {   // the three floats are on the host already
         if (c->tx_ar(c->tx_user, h, 3)) return fail(c, DORY_ERR_COMM, "train_stat_global: host transport allreduce failed");
     } else if (c->numNodes > 1) {
         HIPCK(c, hipMemcpyAsync(c->d_stat3, h, sizeof(h), hipMemcpyHostToDevice, c->compute));

@@ -295,6 +295,7 @@ int dory_destroy(dory_ctx *c) {
     if (c->d_replay_idx) (void)hipFree(c->d_replay_idx);
     if (c->send_buf) (void)hipFree(c->send_buf);
     if (c->recv_buf) (void)hipFree(c->recv_buf);
+    scatter_free(c);
     if (c->d_stat) (void)hipFree(c->d_stat);
     if (c->sweep_stat) (void)hipFree(c->sweep_stat);
     if (c->d_stat3) (void)hipFree(c->d_stat3);

@@ -115,6 +115,8 @@ bool tf_layer(dory_ctx *c, uint32_t layer);
 bool tf_active(dory_ctx *c);   // = tf_layer(c, 0)
 // one all-to-all-v of rows with the plan of `dir` (abi_comm.hip)
 int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer);
+// scatter messages (abi_comm.hip): everything dory_ctx::scatter owns, at dory_destroy
+void scatter_free(dory_ctx *c);
 // K1b bookkeeping (abi_stages.hip)
 int ensure_blocked(dory_ctx *c, Adjacency &A, int group, bool narrow_set = false /* the multi-head GAT contexts' second copy (Adjacency::blk16) */);
 int blk_group_for(dory_ctx *c, uint32_t ld);

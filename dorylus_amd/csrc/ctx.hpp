@@ -9,6 +9,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/dorylus_hip.h"
@@ -57,6 +58,46 @@ struct HaloPlan {
 struct RowWire {
     uint32_t w = 0;
     bool exact = false;
+};
+
+// Scatter messages (dory_scatter_msgs_*, abi_comm.hip): the id tables of dory_halo_wire_ids, the round stamps and counters of
+// the unpack, the fixed staging area of dory_scatter_msgs_deliver, the message tables of the layouts asked for so far, and the
+// scatter transport's callback with its send buffers.
+struct ScatterLayout {
+    int dir = 0;
+    uint32_t cols = 0, max_rows = 0;
+    uint64_t max_msg = 0, total_bytes = 0;
+    std::vector<dory_scatter_msg> msgs;
+    dory_scatter_msg *d_msgs = nullptr;
+};
+struct ScatterState {
+    bool ids = false;
+    uint32_t *d_l2g = nullptr;                      // N
+    std::vector<uint32_t> gvids[2];                 // per direction: the ghosts' global ids, ascending (slot order)
+    uint32_t *d_gvids[2] = {nullptr, nullptr};
+    uint32_t *d_slot_row[2] = {nullptr, nullptr};   // option halo_direct_recv: ghost slot -> stored (wire-order) row; null: identity
+    uint32_t *d_stamp[2] = {nullptr, nullptr};      // per ghost slot: the round that wrote it last
+    uint32_t *d_counts[2] = {nullptr, nullptr};     // rows written, unknown ids, duplicates of the round in progress
+    uint32_t round[2] = {1, 1};
+    std::vector<ScatterLayout> layouts;
+    // staging: slot i is free again when ev_stage[i] has happened (the unpack that read it)
+    uint8_t *h_stage[2] = {nullptr, nullptr};
+    uint8_t *d_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    bool stage_used[2] = {false, false};
+    size_t stage_bytes = 0;
+    int next_slot = 0;
+    // transport
+    dory_scatter_exchange_fn fn = nullptr;
+    uint64_t max_msg = 0;
+    uint8_t *d_send = nullptr, *h_send = nullptr;
+    size_t send_cap = 0;
+    // the exchange whose callback is running (on cb_thread): its ghost tensor, and what the headers must say
+    std::atomic<bool> in_cb{false};
+    std::thread::id cb_thread;
+    Tensor *cb_ghost = nullptr;
+    uint32_t cb_layer = 0;
+    int cb_dir = 0;
 };
 
 // K1b: source-blocked adjacency (per-block CSR over the virtual source space [local;ghost])
@@ -242,6 +283,7 @@ struct dory_ctx {
     // landed in the ghost tensor itself / went through a receive buffer and an unpack
     std::atomic<int> halo_direct{0};
     uint64_t halo_direct_recvs = 0, halo_staged_recvs = 0;
+    dory::ScatterState scatter;   // scatter messages (dory_scatter_msgs_*) and the scatter transport
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
     dory_alltoallv_fn tx_a2a = nullptr;
@@ -562,6 +604,15 @@ hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const ui
 // option halo_direct_recv: whole ld-wide rows (any ld) between the caller-visible order of a ghost tensor and its stored (wire)
 // order, off the epoch's path -- to_wire: dst[i] = src[order[i]] (upload), else dst[order[i]] = src[i] (download)
 hipError_t launch_permute_rows(float *dst, const float *src, uint32_t ld, const uint32_t *order, uint32_t n, bool to_wire, hipStream_t s);
+
+// scatter messages (include/dorylus_wire.h): every message of a layout into `buf` (16-byte aligned; d_msgs: the layout's table on
+// the device, max_rows: its longest message), and a stream of `nrec` records (16-byte aligned, no header) into the ghost rows
+uint32_t scatter_msgs_max_cols();
+hipError_t launch_scatter_msgs_pack(void *buf, const float *src, uint32_t ld, uint32_t cols, const uint32_t *lvids, const uint32_t *l2g,
+                                    const dory_scatter_msg *d_msgs, uint32_t n_msgs, uint32_t max_rows, uint32_t sender, uint32_t layer,
+                                    uint32_t dir, hipStream_t s);
+hipError_t launch_scatter_msgs_unpack(float *ghost, uint32_t ld, uint32_t cols, const void *records, uint32_t nrec, const uint32_t *gvids,
+                                      uint32_t G, const uint32_t *slot_row, uint32_t *stamp, uint32_t round, uint32_t *counts, hipStream_t s);
 
 // K7 Adam
 hipError_t launch_adam(float *w, const float *g, float *m, float *v, uint64_t n, float lr_t,

@@ -738,6 +738,171 @@ hipError_t launch_permute_rows(float *dst, const float *src, uint32_t ld, const 
     return hipGetLastError();
 }
 
+// ---- K6, scatter messages (dory_scatter_msgs_*: the reference's own wire, include/dorylus_wire.h) ---------------------------
+// A message is 7 header dwords and then records of 1 + F dwords (global vertex id, F floats): every row sits at a one-dword
+// skew against the last one, whatever F is.  Both kernels stage through LDS, which absorbs that skew: the tensor side moves as
+// 16-byte accesses of whole rows (rows start on 128-byte lines; tensors with ld % 4 != 0 -- ld == 1 -- move as dwords), the
+// message side as 16-byte accesses of the message's own quads (messages start 16-byte aligned), and only LDS is addressed dword
+// by dword.  Indices inside a workgroup's piece are 32-bit; the piece's base is the only 64-bit value.
+__device__ __forceinline__ uint32_t scatter_hex8_word(uint32_t receiver, uint32_t w) {   // characters 4w .. 4w + 3 of sprintf("%8X")
+    uint32_t out = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t j = 4 * w + k, rest = receiver >> (4 * (7 - j)), d = rest & 15u;
+        const uint32_t ch = (rest == 0 && j != 7) ? 0x20u : (d < 10 ? 0x30u + d : 0x41u + d - 10u);
+        out |= ch << (8 * k);
+    }
+    return out;
+}
+// pack: a workgroup writes SCATTER_PACK_DW consecutive dwords [lo, hi) of one message -- whole quads, but for the message's last
+// dwords -- after gathering what falls into them: header words, ids (l2g[lvid]) and the columns [0, F) of the listed rows (a
+// record cut by lo or hi is loaded by both neighbours, each keeping its own part; a float4 wholly outside is not loaded).  The
+// padding columns of a source row may be read into registers and are never stored.  The send list may repeat a row.  Behind a
+// message that is not the last one, the dwords up to the next 16-byte boundary are written as zeros.
+constexpr uint32_t SCATTER_PACK_DW = 4096;
+template <bool VEC>
+__global__ __launch_bounds__(256) void scatter_msgs_pack_kernel(uint32_t *buf, const float *src, uint32_t ld, uint32_t F, const uint32_t *lvids,
+                                                                const uint32_t *l2g, const dory_scatter_msg *msgs, uint32_t n_msgs,
+                                                                uint32_t chunks_per_msg, uint32_t sender, uint32_t layer, uint32_t dir) {
+    __shared__ __attribute__((aligned(16))) uint32_t stage[SCATTER_PACK_DW];
+    const uint32_t m = blockIdx.x / chunks_per_msg, k = blockIdx.x - m * chunks_per_msg;
+    const dory_scatter_msg M = msgs[m];
+    const uint32_t rec = 1u + F, msg_dw = 7u + M.rows * rec, lo = k * SCATTER_PACK_DW;
+    if (lo >= msg_dw) return;
+    const uint32_t hi = msg_dw - lo < SCATTER_PACK_DW ? msg_dw : lo + SCATTER_PACK_DW, n = hi - lo;
+    if (lo == 0 && threadIdx.x < 7) {
+        const uint32_t t = threadIdx.x;
+        stage[t] = t < 2 ? scatter_hex8_word(M.peer, t) : t == 2 ? sender : t == 3 ? M.rows : t == 4 ? F : t == 5 ? layer : dir;
+    }
+    const uint32_t r_lo = lo > 7u ? (lo - 7u) / rec : 0u, r_hi = (hi - 7u + rec - 1u) / rec, nr = r_hi - r_lo;   // (hi > 7: a message has a record)
+    const uint32_t *lv = lvids + M.first_row + r_lo;
+    const int32_t b0 = (int32_t)(7u + r_lo * rec) - (int32_t)lo;   // where record r_lo starts in `stage` (may lie in front of it)
+    for (uint32_t r = threadIdx.x; r < nr; r += 256u) {
+        const uint32_t p = (uint32_t)(b0 + (int32_t)(r * rec));
+        if (p < n) stage[p] = l2g[lv[r]];
+    }
+    if (VEC) {
+        const uint32_t F4 = (F + 3u) >> 2;
+        for (uint32_t i = threadIdx.x; i < nr * F4; i += 256u) {
+            const uint32_t r = i / F4, c = (i - r * F4) * 4u;
+            const int32_t p0 = b0 + (int32_t)(r * rec + 1u + c);
+            if (p0 + 4 <= 0 || p0 >= (int32_t)n) continue;
+            const uint4 v = *reinterpret_cast<const uint4 *>(src + (size_t)lv[r] * ld + c);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t e = 0; e < 4; ++e)
+                if (c + e < F && (uint32_t)(p0 + (int32_t)e) < n) stage[p0 + (int32_t)e] = w[e];
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < nr * F; i += 256u) {
+            const uint32_t r = i / F, c = i - r * F, p = (uint32_t)(b0 + (int32_t)(r * rec + 1u + c));
+            if (p < n) stage[p] = __float_as_uint(src[(size_t)lv[r] * ld + c]);
+        }
+    }
+    __syncthreads();
+    uint32_t *out = buf + (M.offset >> 2) + lo;
+    const uint32_t nq = n >> 2, tail = n & 3u;
+    for (uint32_t q = threadIdx.x; q < nq; q += 256u)
+        *reinterpret_cast<uint4 *>(out + 4u * q) = *reinterpret_cast<const uint4 *>(stage + 4u * q);
+    if (tail && threadIdx.x < 4u) {   // the message's last dwords, and the zeros between it and the next message
+        if (threadIdx.x < tail) out[4u * nq + threadIdx.x] = stage[4u * nq + threadIdx.x];
+        else if (m + 1u < n_msgs) out[4u * nq + threadIdx.x] = 0u;
+    }
+}
+// unpack: a workgroup takes a run of `rpb` WHOLE records of a stream of records (a message's payload: no header), loads the quads
+// that cover them into LDS (a quad shared with the neighbour run is read by both; the stream's last dwords move as dwords), finds
+// every record's ghost slot by binary search of the ascending id table, claims the slot for this round (atomic exchange of its
+// stamp: an id that is not in the table, or whose slot carries this round's stamp already, is counted and never written), maps
+// the slot to its stored row (option halo_direct_recv: slot_row) and writes the whole ld-wide row: [0, F) from the record, zeros
+// into [F, ld).  rpb x (1 + F) + 6 <= SCATTER_UNPACK_DW.
+constexpr uint32_t SCATTER_UNPACK_DW = 8192;
+template <bool VEC>
+__global__ __launch_bounds__(256) void scatter_msgs_unpack_kernel(float *ghost, uint32_t ld, uint32_t F, const uint32_t *stream, uint32_t nrec,
+                                                                  uint32_t rpb, const uint32_t *gvids, uint32_t G, const uint32_t *slot_row,
+                                                                  uint32_t *stamp, uint32_t round, uint32_t *counts) {
+    __shared__ __attribute__((aligned(16))) uint32_t stage[SCATTER_UNPACK_DW];
+    __shared__ uint32_t cnt[3];
+    const uint32_t rec = 1u + F, r0 = blockIdx.x * rpb, nr = nrec - r0 < rpb ? nrec - r0 : rpb;
+    const uint64_t total = (uint64_t)nrec * rec, d_lo = (uint64_t)r0 * rec, a_lo = d_lo & ~3ull;
+    const uint64_t d_hi = d_lo + (uint64_t)nr * rec, a_hi = ((d_hi + 3ull) & ~3ull) < total ? ((d_hi + 3ull) & ~3ull) : total;
+    const uint32_t off = (uint32_t)(d_lo - a_lo), n = (uint32_t)(a_hi - a_lo), nq = n >> 2, tail = n & 3u;
+    const uint32_t *in = stream + a_lo;
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+    for (uint32_t q = threadIdx.x; q < nq; q += 256u)
+        *reinterpret_cast<uint4 *>(stage + 4u * q) = *reinterpret_cast<const uint4 *>(in + 4u * q);
+    if (threadIdx.x < tail) stage[4u * nq + threadIdx.x] = in[4u * nq + threadIdx.x];
+    __syncthreads();
+    for (uint32_t r = threadIdx.x; r < nr; r += 256u) {
+        const uint32_t p = off + r * rec, gv = stage[p];
+        uint32_t a = 0, b = G;
+        while (a < b) {
+            const uint32_t mid = (a + b) >> 1;
+            if (gvids[mid] < gv) a = mid + 1u;
+            else b = mid;
+        }
+        uint32_t row = 0xFFFFFFFFu;
+        if (a >= G || gvids[a] != gv) {
+            atomicAdd(&cnt[1], 1u);
+        } else if (atomicExch(&stamp[a], round) == round) {
+            atomicAdd(&cnt[2], 1u);
+        } else {
+            atomicAdd(&cnt[0], 1u);
+            row = slot_row ? slot_row[a] : a;
+        }
+        stage[p] = row;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], cnt[threadIdx.x]);
+    if (VEC) {
+        const uint32_t ld4 = ld >> 2;
+        for (uint32_t i = threadIdx.x; i < nr * ld4; i += 256u) {
+            const uint32_t r = i / ld4, c = (i - r * ld4) * 4u, p = off + r * rec, row = stage[p];
+            if (row == 0xFFFFFFFFu) continue;
+            uint4 v;
+            v.x = c < F ? stage[p + 1u + c] : 0u;
+            v.y = c + 1u < F ? stage[p + 2u + c] : 0u;
+            v.z = c + 2u < F ? stage[p + 3u + c] : 0u;
+            v.w = c + 3u < F ? stage[p + 4u + c] : 0u;
+            *reinterpret_cast<uint4 *>(ghost + (size_t)row * ld + c) = v;
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < nr * ld; i += 256u) {
+            const uint32_t r = i / ld, c = i - r * ld, p = off + r * rec, row = stage[p];
+            if (row != 0xFFFFFFFFu) ghost[(size_t)row * ld + c] = c < F ? __uint_as_float(stage[p + 1u + c]) : 0.f;
+        }
+    }
+}
+
+uint32_t scatter_msgs_max_cols() { return SCATTER_UNPACK_DW - 7u; }
+hipError_t launch_scatter_msgs_pack(void *buf, const float *src, uint32_t ld, uint32_t cols, const uint32_t *lvids, const uint32_t *l2g,
+                                    const dory_scatter_msg *d_msgs, uint32_t n_msgs, uint32_t max_rows, uint32_t sender, uint32_t layer,
+                                    uint32_t dir, hipStream_t s) {
+    if (n_msgs == 0) return hipSuccess;
+    const uint64_t msg_dw = 7ull + (uint64_t)max_rows * (1ull + cols);
+    if (cols == 0 || cols > ld || max_rows == 0 || msg_dw >= (1ull << 30) || ((uintptr_t)buf & 15)) return hipErrorInvalidValue;
+    const uint64_t cpm = (msg_dw + SCATTER_PACK_DW - 1) / SCATTER_PACK_DW, grid = cpm * n_msgs;
+    if (grid >= (1ull << 31)) return hipErrorInvalidValue;
+    const bool vec = (ld & 3u) == 0 && ((cols + 3u) & ~3u) <= ld && ((uintptr_t)src & 15) == 0;
+    if (vec) hipLaunchKernelGGL(scatter_msgs_pack_kernel<true>, dim3((uint32_t)grid), dim3(256), 0, s, (uint32_t *)buf, src, ld, cols, lvids, l2g,
+                                d_msgs, n_msgs, (uint32_t)cpm, sender, layer, dir);
+    else hipLaunchKernelGGL(scatter_msgs_pack_kernel<false>, dim3((uint32_t)grid), dim3(256), 0, s, (uint32_t *)buf, src, ld, cols, lvids, l2g,
+                            d_msgs, n_msgs, (uint32_t)cpm, sender, layer, dir);
+    return hipGetLastError();
+}
+hipError_t launch_scatter_msgs_unpack(float *ghost, uint32_t ld, uint32_t cols, const void *records, uint32_t nrec, const uint32_t *gvids,
+                                      uint32_t G, const uint32_t *slot_row, uint32_t *stamp, uint32_t round, uint32_t *counts, hipStream_t s) {
+    if (nrec == 0) return hipSuccess;
+    if (cols == 0 || cols > ld || cols > scatter_msgs_max_cols() || ((uintptr_t)records & 15)) return hipErrorInvalidValue;
+    const uint32_t rpb = (SCATTER_UNPACK_DW - 6u) / (1u + cols);
+    const uint32_t grid = (nrec - 1u) / rpb + 1u;
+    const bool vec = (ld & 3u) == 0 && ((uintptr_t)ghost & 15) == 0;
+    if (vec) hipLaunchKernelGGL(scatter_msgs_unpack_kernel<true>, dim3(grid), dim3(256), 0, s, ghost, ld, cols, (const uint32_t *)records, nrec, rpb,
+                                gvids, G, slot_row, stamp, round, counts);
+    else hipLaunchKernelGGL(scatter_msgs_unpack_kernel<false>, dim3(grid), dim3(256), 0, s, ghost, ld, cols, (const uint32_t *)records, nrec, rpb,
+                            gvids, G, slot_row, stamp, round, counts);
+    return hipGetLastError();
+}
+
 // ---- K7: Adam -----------------------------------------------------------------------------
 // AdamOptimizer::update (reference src/weight-server/AdamOptimizer.cpp:36-51), the
 // mixed float/double expressions kept as written there ("(1. - BETA1) * gt" is double).

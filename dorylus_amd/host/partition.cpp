@@ -24,6 +24,9 @@
 // dory_partition_upload asks the context for option halo_direct_recv.  Weak: a host-only build of this file (the sanitizer
 // driver links it without the device library) has no contexts that carry options; the upload then takes the plain arrays.
 extern "C" int dory_get_option(dory_ctx *ctx, const char *key, int64_t *value) __attribute__((weak));
+// ... and hands it the ids of the scatter messages: weak for the same reason
+extern "C" int dory_halo_wire_ids(dory_ctx *ctx, const uint32_t *local_to_global, const uint32_t *src_ghost_gvids,
+                                  const uint32_t *dst_ghost_gvids) __attribute__((weak));
 
 struct dory_partition {
     uint32_t N = 0, V = 0, Gsrc = 0, Gdst = 0, P = 0;
@@ -482,6 +485,8 @@ int dory_partition_upload(dory_ctx *ctx, const dory_partition *p, const int32_t 
         rc = dory_halo_plan(ctx, dir, scnt.data(), slist.empty() ? &dummy : slist.data(), rcnt.data(), rslots.data());
         if (rc) return rc;
     }
+    // the global ids scatter messages carry (dory_scatter_msgs_*): ghost slots are in ascending global id already
+    if (dory_halo_wire_ids) return dory_halo_wire_ids(ctx, p->l2g.data(), p->srcGhost.data(), p->dstGhost.data());
     return DORY_OK;
 }
 

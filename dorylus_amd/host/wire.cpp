@@ -131,4 +131,59 @@ int dory_wire_parse_pull_reply(const void *hdr, size_t payload_bytes, char name9
     return 0;
 }
 
+// ---- scatter messages: the graph-server <-> graph-server data path (Engine::verticesPushOut, engine/utils.cpp:623-650) ----
+// BATCH_SIZE of scatterGCN / scatterGAT (gcn_ops.cpp:225-228, gat_ops.cpp:298-301): at least one vertex per message
+uint32_t dory_wire_scatter_batch(uint32_t feat_dim, uint64_t max_msg_bytes) {
+    const uint64_t max_msg = max_msg_bytes ? max_msg_bytes : DORY_WIRE_MAX_MSG_SIZE;
+    const uint64_t rec = 4ull + 4ull * feat_dim;
+    const uint64_t n = max_msg > DORY_WIRE_SCATTER_HDR_SIZE ? (max_msg - DORY_WIRE_SCATTER_HDR_SIZE) / rec : 0;
+    return (uint32_t)(n < 1 ? 1 : n > 0xFFFFFFFFull ? 0xFFFFFFFFull : n);
+}
+
+uint64_t dory_wire_scatter_msg_bytes(uint32_t rows, uint32_t feat_dim) {
+    return DORY_WIRE_SCATTER_HDR_SIZE + (uint64_t)rows * (4ull + 4ull * feat_dim);
+}
+
+// sprintf(msgPtr, NODE_ID_HEADER, receiver) -- "%8X" -- then populateHeader(msgPtr + 8, nodeId, totCnt, featDim, featLayer,
+// c.dir) (utils.cpp:630-640); the NUL sprintf leaves at offset 8 is overwritten by the sender field
+void dory_wire_pack_scatter_header(void *buf, uint32_t receiver, uint32_t sender, uint32_t count, uint32_t feat_dim,
+                                   uint32_t layer, uint32_t dir) {
+    uint8_t *p = static_cast<uint8_t *>(buf);
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t rest = receiver >> (4 * (7 - j));
+        p[j] = (rest == 0 && j != 7) ? ' ' : (uint8_t)"0123456789ABCDEF"[rest & 15u];
+    }
+    dory_wire_pack_fields_header(p + DORY_WIRE_NODE_ID_DIGITS, sender, count, feat_dim, layer, dir);
+}
+
+int dory_wire_parse_scatter_header(const void *buf, uint64_t bytes, uint32_t *receiver, uint32_t *sender, uint32_t *count,
+                                   uint32_t *feat_dim, uint32_t *layer, uint32_t *dir) {
+    if (!buf || bytes < DORY_WIRE_SCATTER_HDR_SIZE) return -1;
+    const uint8_t *p = static_cast<const uint8_t *>(buf);
+    uint32_t recv = 0;
+    bool digits = false;
+    for (int j = 0; j < 8; ++j) {   // spaces, then upper-case hex digits without a leading zero (a lone "0" for receiver 0)
+        const uint8_t ch = p[j];
+        if (ch == ' ' && !digits) continue;
+        uint32_t d;
+        if (ch >= '0' && ch <= '9') d = ch - '0';
+        else if (ch >= 'A' && ch <= 'F') d = 10u + (ch - 'A');
+        else return -1;
+        if (!digits && d == 0 && j != 7) return -1;
+        digits = true;
+        recv = (recv << 4) | d;
+    }
+    if (!digits) return -1;
+    uint32_t snd, cnt, fd, lay, dr;
+    dory_wire_parse_fields_header(p + DORY_WIRE_NODE_ID_DIGITS, &snd, &cnt, &fd, &lay, &dr);
+    if (dory_wire_scatter_msg_bytes(cnt, fd) != bytes) return -1;
+    if (receiver) *receiver = recv;
+    if (sender) *sender = snd;
+    if (count) *count = cnt;
+    if (feat_dim) *feat_dim = fd;
+    if (layer) *layer = lay;
+    if (dir) *dir = dr;
+    return 0;
+}
+
 }  // extern "C"

@@ -215,6 +215,72 @@ int dory_halo_unpack(dory_ctx *ctx, uint32_t layer, int dir, const float *recv_b
 int dory_halo_pack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int dir, float *send_buf);
 int dory_halo_unpack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int dir, const float *recv_buf);
 
+/* ---- scatter messages: the reference's own graph-server <-> graph-server wire, packed and unpacked on the device ----------
+ * What Engine::verticesPushOut puts on a socket and ghostReceiver* takes apart (include/dorylus_wire.h: the format table with
+ * its citations): messages of an 8-character receiver topic, five unsigned header fields and (global vertex id, featDim floats)
+ * records, at most max_msg_bytes each.  With these entry points a HIP graph server hands an unmodified reference graph server
+ * the very bytes it expects, and takes its messages as a socket leaves them, with no work on the rows by the host.  The sockets,
+ * the per-message ACK, the barrier and async mode stay the caller's.  max_msg_bytes: 0 = the reference's
+ * 1 MiB; below 2^32.  name == NULL: the tensors dory_halo_exchange(layer, dir) would move; otherwise any per-vertex tensor
+ * (pack) / ghost tensor of that direction (deliver) at `layer`, as in dory_halo_pack_tensor.  Rows of at most 8185 floats.
+ * Not executed against a reference binary and not measured over any link: DESIGN.md sections 4 and 5. */
+
+/* The global ids the records carry: local_to_global[N] (localToGlobalId), and the ghosts' global ids of both directions in slot
+ * order (srcGhostVtcs / dstGhostVtcs; what dory_partition_view holds) -- ascending, anything else is refused.  After
+ * dory_graph_upload; dory_partition_upload calls it itself when `parts` is given.  Off the epoch's path: it uploads the tables,
+ * clears the round stamps and allocates the fixed staging area of dory_scatter_msgs_deliver (two pinned host slots and two
+ * device slots of max(1 MiB, the widest record) bytes). */
+int dory_halo_wire_ids(dory_ctx *ctx, const uint32_t *local_to_global, const uint32_t *src_ghost_gvids, const uint32_t *dst_ghost_gvids);
+
+/* one message of an exchange inside one buffer: `rows` records for `peer`, the entries first_row .. first_row + rows - 1 of the
+ * plan's send list (dory_halo_plan's send_lvids, all peers concatenated), at byte `offset` (a multiple of 16), `bytes` =
+ * 28 + rows x (4 + 4 cols) long */
+struct dory_scatter_msg {
+    uint32_t peer, first_row, rows;
+    uint64_t offset, bytes;
+};
+/* The messages of one exchange, as the reference's sender loop cuts them (per peer in rank order the send list in consecutive
+ * batches of dory_wire_scatter_batch(cols, max_msg_bytes) rows, the last one short, none for a peer without rows), laid out in
+ * ONE buffer of *total_bytes bytes, every message 16-byte aligned.  msgs may be NULL (sizes only); otherwise max_msgs entries
+ * are available, and fewer than *n_msgs is DORY_ERR_ARG.  Host only. */
+int dory_scatter_msgs_layout(dory_ctx *ctx, uint32_t layer, int dir, const char *name, uint64_t max_msg_bytes,
+                             struct dory_scatter_msg *msgs, uint32_t max_msgs, uint32_t *n_msgs, uint64_t *total_bytes);
+/* Writes every message of that layout, headers included, into the device buffer dev_buf (16-byte aligned, total_bytes bytes; not
+ * one byte beyond is touched) on the compute stream: each message is byte for byte what the reference sends for the same
+ * tensor, the bytes between messages are zero.  The header's layer is the ghost tensor's (name: `layer` itself). */
+int dory_scatter_msgs_pack(dory_ctx *ctx, uint32_t layer, int dir, const char *name, uint64_t max_msg_bytes, void *dev_buf);
+/* n >= 1 whole messages in host memory (msgs[i] of bytes[i] bytes), from any senders, in any order and batching.  The headers
+ * are parsed on the host; every message names its ghost tensor by (layer, dir) -- GCN "fg"@layer / "bg"@layer, GAT and GATMH
+ * "fg_z"@layer / "bg_d"@layer -- or `name` names it at the header's layer.  Before anything is enqueued the call refuses
+ * (DORY_ERR_ARG, the text names the field) a malformed or truncated message, a featDim other than the tensor's cols, a receiver
+ * other than this rank, a dir other than 0 / 1 and a layer out of range.  The records then go through the staging area to the
+ * device and an unpack kernel on the comm stream finds each record's ghost slot by binary search of the ids, and writes the
+ * whole stored row ([0, cols) from the record, zeros into [cols, ld); under halo_direct_recv at the slot's wire-order row):
+ * the raw rows are the bits dory_halo_exchange leaves.  Every ghost slot carries a round stamp: an unknown id and an id that
+ * arrives twice in a round are counted on the device and never written.  Writing "fg"@0 / "fg_z" drops the cached ah@0 / the
+ * kept neighbour sum, as dory_halo_exchange does.  Allocates nothing. */
+int dory_scatter_msgs_deliver(dory_ctx *ctx, const char *name, const void *const *msgs, const uint64_t *bytes, uint32_t n);
+/* The unpack alone, for records that are in device memory already (a transport that lands payloads there; what
+ * tools/scatter_msgs_rate.py times): `count` records of (id, cols floats), no header, at the 16-byte aligned dev_records, into
+ * the ghost tensor of the exchange (layer, dir) or the named one -- the same kernel, stamps and counters as the deliver's, on
+ * the comm stream; dory_scatter_msgs_finish ends the round. */
+int dory_scatter_msgs_unpack(dory_ctx *ctx, uint32_t layer, int dir, const char *name, const void *dev_records, uint32_t count);
+/* Ends a round of direction `dir`: waits for the unpacks, reports the ghost rows written and the records refused, opens the next
+ * round.  DORY_ERR_COMM unless every ghost slot of the direction was written exactly once (rows == ghost count, unknown ==
+ * duplicate == 0): the reference's ghostVtcsRecvd == totalGhostCnt (gcn_ops.cpp:339-347).  Outputs may be NULL. */
+int dory_scatter_msgs_finish(dory_ctx *ctx, uint32_t layer, int dir, const char *name, uint32_t *rows, uint32_t *unknown,
+                             uint32_t *duplicate);
+/* The same as a transport, next to dory_comm_set_host_transport (setting one clears the other; NULLs return to RCCL):
+ * dory_halo_exchange and the multi-head GAT backward's "do" / "st" exchanges pack the messages on the device, copy the buffer
+ * to pinned host memory and call exchange(user, ctx, host_buf, msgs, n_msgs) on the calling thread: message i is host_buf +
+ * msgs[i].offset.  The callee sends them and, before it returns, hands every message that arrived for this rank to
+ * dory_scatter_msgs_deliver(ctx, NULL, ...) (from this thread; NULL = the exchange's own ghost tensor); the library then runs
+ * dory_scatter_msgs_finish.  Scheduling around the aggregation (halo_overlap, the timing families) is the host transport's, and
+ * dory_weight_update / dory_train_stat_global use allreduce_sum as that arm does. */
+typedef int (*dory_scatter_exchange_fn)(void *user, dory_ctx *ctx, const void *host_buf, const struct dory_scatter_msg *msgs, uint32_t n_msgs);
+int dory_comm_set_scatter_transport(dory_ctx *ctx, dory_scatter_exchange_fn exchange, dory_allreduce_fn allreduce_sum, void *user,
+                                    uint64_t max_msg_bytes);
+
 /* ---- weight-gradient reduction + optimiser (replaces the weight server's
  * PUB/SUB all-gather-and-sum + Adam, src/weight-server/weightserver.cpp:89-187,
  * weighttensor.cpp:131-166,246-328, AdamOptimizer.cpp:29-51) ---------------------
