@@ -28,6 +28,7 @@ SYMBOLS = [
     "dory_halo_wire_ids", "dory_scatter_msgs_layout", "dory_scatter_msgs_pack", "dory_scatter_msgs_deliver", "dory_scatter_msgs_unpack",
     "dory_scatter_msgs_finish",
     "dory_comm_set_scatter_transport",
+    "dory_halo_fused_pack", "dory_halo_fused_pack_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -116,7 +117,10 @@ def load():
         "dory_scatter_msgs_unpack": [vp, u32, i32, cp, vp, u32],
         "dory_scatter_msgs_finish": [vp, u32, i32, cp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
         "dory_comm_set_scatter_transport": [vp, SCATTER_EXCHANGE_FN, ALLREDUCE_FN, vp, u64],
+        "dory_halo_fused_pack": [vp, i32],
+        "dory_halo_fused_pack_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
         # include/dorylus_host.h
+        "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
         "dory_partition_build_from_files": [cp, u32, u32, i32, C.POINTER(vp)],
         "dory_partition_load": [cp, C.POINTER(vp)],
@@ -146,8 +150,9 @@ def load():
     }
     for name, args in sig.items():
         if (name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check", "dory_halo_wire_ids",
-                     "dory_comm_set_scatter_transport") or name.startswith("dory_scatter_msgs_")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages)
+                     "dory_comm_set_scatter_transport", "dory_halo_send_map") or name.startswith("dory_scatter_msgs_")
+                or name.startswith("dory_halo_fused_pack")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -189,6 +194,20 @@ def option_check(name, value, gnn=GCN, configured=False, has_graph=False, lib=No
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def halo_send_map(local_vtx_cnt, send_lists, lib=None):
+    """(row_ptr[N + 1], row_slots[sum of the list lengths]): the send lists of a halo plan (one list of local row ids per peer, as
+    Context.halo_plan takes them) turned round -- the slots row r has in the packed send buffer are
+    row_slots[row_ptr[r]:row_ptr[r + 1]], ascending (dory_halo_send_map; no context, no GPU)."""
+    lib = lib or load()
+    sc = np.array([len(x) for x in send_lists], np.uint32)
+    sl = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint32) for x in send_lists] + [np.zeros(0, np.uint32)]), np.uint32)
+    row_ptr, row_slots = np.zeros(int(local_vtx_cnt) + 1, np.uint32), np.zeros(max(sl.size, 1), np.uint32)
+    rc = lib.dory_halo_send_map(int(local_vtx_cnt), len(send_lists), _ptr(sc), _ptr(sl), _ptr(row_ptr), _ptr(row_slots))
+    if rc != 0:
+        raise DoryError(f"dory_halo_send_map failed ({rc}): {lib.dory_host_last_error().decode()}")
+    return row_ptr, row_slots[:sl.size]
 
 
 class Context:
@@ -255,21 +274,23 @@ class Context:
         self._ck(self.lib.dory_preallocate(self.h))
 
     # -- tensors ------------------------------------------------------------------
-    def info(self, layer, name):
+    def info(self, layer, name, ptr=True):
+        """(rows, cols, ld, device pointer).  ptr=False asks for the shape alone (pointer None): a tensor whose raw pointer has
+        been handed out is never again the target of a fused halo pack (halo_fused_pack)."""
         rows, cols, ld, p = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_void_p()
         self._ck(self.lib.dory_tensor_info(self.h, layer, name.encode(), C.byref(rows), C.byref(cols),
-                                           C.byref(ld), C.byref(p)))
+                                           C.byref(ld), C.byref(p) if ptr else None))
         return rows.value, cols.value, ld.value, p.value
 
     def upload(self, layer, name, a):
-        rows, cols, _, _ = self.info(layer, name)
+        rows, cols, _, _ = self.info(layer, name, ptr=False)
         a = np.ascontiguousarray(a, dtype=np.float32)
         if a.size != rows * cols:
             raise DoryError(f"upload {name}@{layer}: got {a.shape}, tensor is {rows}x{cols}")
         self._ck(self.lib.dory_tensor_upload(self.h, layer, name.encode(), _ptr(a)))
 
     def download(self, layer, name):
-        rows, cols, _, _ = self.info(layer, name)
+        rows, cols, _, _ = self.info(layer, name, ptr=False)
         a = np.empty((rows, cols), np.float32)
         self._ck(self.lib.dory_tensor_download(self.h, layer, name.encode(), _ptr(a)))
         return a
@@ -485,6 +506,16 @@ class Context:
 
     def halo_unpack_tensor(self, layer, name, direction, dev_ptr):
         self._ck(self.lib.dory_halo_unpack_tensor(self.h, layer, name.encode(), direction, C.c_void_p(dev_ptr)))
+
+    def halo_fused_pack(self, on=True):
+        """the GEMM epilogues write the send rows of the exchange that follows (opt-in; dory_halo_fused_pack)"""
+        self._ck(self.lib.dory_halo_fused_pack(self.h, int(on)))
+
+    def halo_fused_pack_stats(self):
+        """(exchanges that skipped their pack kernel, the send rows of those, exchanges that packed although the feature was on)"""
+        a, b, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.dory_halo_fused_pack_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
+        return a.value, b.value, f.value
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

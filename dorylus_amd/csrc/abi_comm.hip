@@ -6,6 +6,7 @@
 #include <chrono>
 #include <thread>
 
+#include "../../include/dorylus_host.h"
 #include "../../include/dorylus_wire.h"
 #include "abi_internal.hpp"
 
@@ -54,12 +55,13 @@ const char *const NO_RECV_BUF = "halo_direct_recv: this exchange needs the recei
 // The padded row width travels (keeps 16-B lanes), or, with option halo_exact_rows, exactly the tensor's columns -- then
 // both ends must have the same, and a caller's buffer of rows whose width is no multiple of 4 is addressed in 16-byte quads
 // of the whole stream.
+inline uint32_t wire_width(const dory_ctx *c, const Tensor *rows) { return halo_exact(c) ? rows->cols : rows->ld; }
 int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghost, bool pack, const void *buf, RowWire *out) {
     const Tensor *rows = pack ? src : ghost;
     out->exact = halo_exact(c);
     if (out->exact && src && ghost && src->cols != ghost->cols)
         return fail(c, DORY_ERR_ARG, "%s: widths of source (%u) and ghost tensor (%u) differ", who, src->cols, ghost->cols);
-    out->w = out->exact ? rows->cols : rows->ld;
+    out->w = wire_width(c, rows);
     if (out->exact && (out->w & 3) && ((uintptr_t)buf & 15))
         return fail(c, DORY_ERR_ARG, "%s: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", who, out->w);
     return DORY_OK;
@@ -67,6 +69,7 @@ int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghos
 
 // the plan's send rows of `src`, dense at the wire's width, into dst; counted (eager calls)
 int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const HaloPlan &p, hipStream_t s) {
+    if (dst == c->send_buf) fused_stamp_drop(c);   // (the fused halo pack: whatever a GEMM left in the internal buffer is overwritten)
     if (wire.exact && (wire.w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
     else HIPCK(c, launch_gather_rows(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
     if (!c->capturing) {
@@ -75,6 +78,22 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
         if (wire.exact && wire.w < src->ld) c->halo_exact_packs++;
     }
     return DORY_OK;
+}
+// The send rows of an exchange into c->send_buf.  The fused halo pack: they are there already when the stamp names this source,
+// direction, width and buffer -- the producer's epilogue wrote them -- and then no kernel runs and the stamp is consumed; with the
+// feature on every other exchange is a counted fallback (`may_fuse` false: an arm that never takes them, section "not taken" of
+// dorylus_hip.h).
+int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloPlan &p, hipStream_t s, bool may_fuse) {
+    if (c->fused_pack) {
+        const FusedStamp &st = c->fused_stamp;
+        if (may_fuse && st.src == src && st.dir == dir && st.w == wire.w && st.buf == c->send_buf) {
+            fused_stamp_drop(c);
+            if (!c->capturing) { c->fused_exchanges++; c->fused_rows += p.send_total; }
+            return DORY_OK;
+        }
+        if (!c->capturing) c->fallback_exchanges++;
+    }
+    return pack_rows(c, c->send_buf, src, wire, p, s);
 }
 // the received rows, dense at the wire's width w, into the plan's ghost slots (option halo_direct_recv: row r into ghost row r);
 // the exact form writes the whole row: [0, w) from the buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever
@@ -100,8 +119,10 @@ int split_rows(dory_ctx *c, const char *who, bool pack, int dir, const Tensor *s
                 : unpack_rows(c, ghost->d, ghost->ld, wire, buf, c->plan[dir], c->compute);
 }
 
-// resolve (layer, dir) -> source tensor, ghost tensor, as Engine::scatterGCN/GAT do
-int halo_tensors(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **ghost) {
+// resolve (layer, dir) -> source tensor, ghost tensor, as Engine::scatterGCN/GAT do; false: layer out of range.  No side effects:
+// halo_tensors (every exchange and split entry point) and fused_pack_target (which GEMM outputs travel) both read this one table.
+bool halo_route(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **ghost) {
+    *src = *ghost = nullptr;
     if (c->gnn == DORY_GCN && dir == DORY_BACKWARD && tf_layer(c, layer)) {
         *src = find(c, layer, "g");      // transform-first: A^T g_l needs the ghost rows of g_l
         *ghost = find(c, layer, "bgg");
@@ -109,19 +130,36 @@ int halo_tensors(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **gh
         *src = find(c, layer, "xw");     // transform-first: the already transformed (narrower) rows travel
         *ghost = find(c, layer, "fgxw");
     } else if (c->gnn == DORY_GCN) {
-        if (layer == 0 || layer >= c->L) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
+        if (layer == 0 || layer >= c->L) return false;
         if (dir == DORY_FORWARD) { *src = find(c, layer - 1, "h"); *ghost = find(c, layer, "fg"); }   // gcn_ops.cpp:205-214
         else { *src = find(c, layer, "grad"); *ghost = find(c, layer - 1, "bg"); }
     } else {
-        if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
-        if (dir == DORY_FORWARD) {   // gat_ops.cpp:277-287
-            *src = find(c, layer - 1, "z"); *ghost = find(c, layer - 1, "fg_z");
-            if (layer - 1 < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer - 1] = 0;   // fg_z is about to change: the kept neighbour sum no longer holds
-        }
+        if (layer == 0 || layer > c->L) return false;
+        if (dir == DORY_FORWARD) { *src = find(c, layer - 1, "z"); *ghost = find(c, layer - 1, "fg_z"); }   // gat_ops.cpp:277-287
         else { *src = find(c, layer - 1, "grad"); *ghost = find(c, layer - 1, "bg_d"); }
     }
+    return true;
+}
+int halo_tensors(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **ghost) {
+    if (!halo_route(c, layer, dir, src, ghost)) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
+    // fg_z is about to change: the kept neighbour sum no longer holds
+    if (c->gnn != DORY_GCN && dir == DORY_FORWARD && layer - 1 < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer - 1] = 0;
     if (!*src || !*ghost) return fail(c, DORY_ERR_ARG, "halo: tensors missing");
     return DORY_OK;
+}
+// multi-head extension: the backward sweep exchanges dO and its per-vertex statistics itself, between its two phases
+// (dory_aggregate); the scatter stage of the reference's GAT order has nothing to ship before it
+inline bool exchange_skipped(const dory_ctx *c, int dir) { return c->gnn == DORY_GATMH && dir == DORY_BACKWARD; }
+
+// ---- the fused halo pack: the plan's send list turned round, on the device (HaloPlan::d_send_map) -------------------------------
+int build_send_map(dory_ctx *c, HaloPlan &p, const uint32_t *send_lvids) {
+    std::vector<uint32_t> map((size_t)c->N + 1 + p.send_total);
+    if (dory_halo_send_map(c->N, c->numNodes, p.send_counts.data(), send_lvids, map.data(), map.data() + c->N + 1))
+        return fail(c, DORY_ERR_ARG, "halo_fused_pack: %s", dory_host_last_error());
+    if (p.d_send_map) (void)hipFree(p.d_send_map);
+    p.d_send_map = nullptr;
+    p.send_map_rows = c->N;
+    return upload_array(c, &p.d_send_map, map.data(), map.size());
 }
 
 // ---- the pack / receive buffers -------------------------------------------------------------------------------------------
@@ -136,6 +174,7 @@ int grow_buffer(dory_ctx *c, float **buf, size_t *cap, size_t bytes) {
 // c->send_buf / c->recv_buf hold at least that much: one device-wide synchronisation if either grows, then free, then malloc
 int ensure_exchange_buffers(dory_ctx *c, size_t send_bytes, size_t recv_bytes) {
     if (send_bytes > c->send_cap || recv_bytes > c->recv_cap) HIPCK(c, hipDeviceSynchronize());
+    if (send_bytes > c->send_cap) fused_stamp_drop(c);   // (the fused halo pack: the rows a GEMM left go with the old buffer)
     int rc = grow_buffer(c, &c->send_buf, &c->send_cap, send_bytes);
     return rc ? rc : grow_buffer(c, &c->recv_buf, &c->recv_cap, recv_bytes);
 }
@@ -427,7 +466,7 @@ int local_wait_posted(dory_ctx *c, const std::atomic<uint64_t> &ctr, uint64_t wa
 // the same place as the push form waits for them -- the first half of exchange s, before anything is enqueued -- by the
 // ranks that sent to that peer in exchange s - 1 (the push form: that send to it in exchange s; the same ranks wherever both
 // directions' plans name the same peers).  No host-side wait is added.
-int local_pull_send(dory_ctx *c, const HaloPlan &p, Tensor *src, RowWire wire, uint64_t s) {
+int local_pull_send(dory_ctx *c, int dir, const HaloPlan &p, Tensor *src, RowWire wire, uint64_t s) {
     LocalGroup &grp = *c->local;
     for (uint32_t q = 0; q < c->numNodes && s > 1; ++q) {
         if (q == c->nodeId || q >= c->local_sent_to.size() || !c->local_sent_to[q]) continue;
@@ -437,7 +476,7 @@ int local_pull_send(dory_ctx *c, const HaloPlan &p, Tensor *src, RowWire wire, u
         if (rc) return rc;
         HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_cons[(s - 1) & 1], 0));
     }
-    { int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm); if (rc) return rc; }
+    { int rc = send_rows(c, src, dir, wire, p, c->comm, false); if (rc) return rc; }   // (the peers read my send buffer on their own streams: never fused)
     c->local_sent_to.assign(c->numNodes, 0);
     for (uint32_t q = 0; q < c->numNodes; ++q) c->local_sent_to[q] = q != c->nodeId && p.send_counts[q] != 0;
     return DORY_OK;
@@ -457,8 +496,8 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     dory_ctx::LocalPending &lp = c->local_pending;
     timed_open(c, "halo", c->comm, &lp.t_halo_b);
     timed_open(c, deferred ? "halo_deferred" : "halo_waited", c->comm, &lp.t_kind_b);
-    if (p.direct) { int rc = local_pull_send(c, p, src, wire, s); if (rc) return rc; }
-    else { int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm); if (rc) return rc; }
+    if (p.direct) { int rc = local_pull_send(c, dir, p, src, wire, s); if (rc) return rc; }
+    else { int rc = send_rows(c, src, dir, wire, p, c->comm, true); if (rc) return rc; }
     for (uint32_t q = 0; q < c->numNodes && !p.direct; ++q) {
         if (q == c->nodeId || !p.send_counts[q]) continue;
         dory_ctx *Q = grp.ctx[q];
@@ -688,6 +727,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
         HIPCK(c, hipEventRecord(c->ev_a, c->compute));
         HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
         const bool deferred = defer && c->opt[OPT_HALO_OVERLAP];
+        if (c->fused_pack && !c->capturing) c->fallback_exchanges++;   // (messages have another layout: never fused)
         {
             Timed t(c, "halo", c->comm);
             Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);
@@ -733,7 +773,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     {   // host transport and RCCL: same pack / unpack / events, only the way from send_buf to recv_buf differs
         Timed t(c, "halo", c->comm);
         Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
-        int rc = pack_rows(c, c->send_buf, src, wire, p, c->comm);
+        int rc = send_rows(c, src, dir, wire, p, c->comm, true);
         float *recv = direct ? ghost->d : c->recv_buf;
         if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, w, recv) : exchange_rccl(c, p, w, recv);
         if (!rc && !direct) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm);
@@ -746,6 +786,35 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     if (deferred) c->halo_pending = true;
     else HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
     return DORY_OK;
+}
+
+bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd, int *dir) {
+    if (!c->fused_pack || c->numNodes <= 1 || c->capturing || out->raw_handed || M != c->N || out->rows != c->N) return false;
+    const Transport tr = transport_of(c);
+    if (tr == Transport::Scatter || tr == Transport::None) return false;
+    for (int d = 0; d < 2; ++d) {
+        const HaloPlan &p = c->plan[d];
+        if (!p.set || !p.d_send_map || p.send_map_rows != c->N || exchange_skipped(c, d) || (tr == Transport::Local && p.direct)) continue;
+        for (uint32_t layer = 0; layer <= c->L; ++layer) {
+            Tensor *src, *ghost;
+            if (!halo_route(c, layer, d, &src, &ghost) || src != out || !ghost) continue;
+            const uint32_t w = wire_width(c, out);
+            if ((size_t)p.send_total * w * sizeof(float) > c->send_cap) return false;   // (the exchange would regrow the buffer)
+            sd->buf = c->send_buf;
+            sd->row_ptr = p.d_send_map;
+            sd->row_slots = p.d_send_map + c->N + 1;
+            sd->w = w;
+            *dir = d;
+            return true;
+        }
+    }
+    return false;
+}
+void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &sd) {
+    c->fused_stamp.src = out;
+    c->fused_stamp.dir = dir;
+    c->fused_stamp.w = sd.w;
+    c->fused_stamp.buf = sd.buf;
 }
 
 void scatter_free(dory_ctx *c) {
@@ -814,6 +883,7 @@ int dory_comm_init_local(dory_ctx *const *ctxs, uint32_t n) {
         c->local_seq = c->local_ar_seq = 0;
         c->local_pending = dory_ctx::LocalPending();
         c->local_sent_to.clear();
+        fused_stamp_drop(c);
         c->local = grp;
     }
     return DORY_OK;
@@ -847,12 +917,15 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
         if (recv_slots[i] >= G || seen[recv_slots[i]]) return fail(c, DORY_ERR_ARG, "halo_plan: recv slots must be a permutation of the ghost slots");
         seen[recv_slots[i]] = 1;
     }
+    fused_stamp_drop(c);   // (the fused halo pack: slots of the old plan)
     if (p.d_send_lvids) (void)hipFree(p.d_send_lvids);
     if (p.d_unpack_slots && p.d_unpack_slots != p.d_recv_slots) (void)hipFree(p.d_unpack_slots);
     if (p.d_recv_slots) (void)hipFree(p.d_recv_slots);
-    p.d_send_lvids = p.d_recv_slots = p.d_unpack_slots = nullptr;
+    if (p.d_send_map) (void)hipFree(p.d_send_map);
+    p.d_send_lvids = p.d_recv_slots = p.d_unpack_slots = p.d_send_map = nullptr;
     int rc;
     if ((rc = upload_array(c, &p.d_send_lvids, send_lvids, p.send_total))) return rc;
+    if (c->fused_pack && (rc = build_send_map(c, p, send_lvids))) return rc;
     if ((rc = upload_array(c, &p.d_recv_slots, recv_slots, p.recv_total))) return rc;
     // option halo_direct_recv: received row r is ghost row r; recv_slots names the caller-visible index of that row (kept for
     // the uploads and downloads of ghost tensors), the unpack kernels get the identity
@@ -885,6 +958,7 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
 int dory_comm_set_host_transport(dory_ctx *c, dory_alltoallv_fn alltoallv, dory_allreduce_fn allreduce_sum, void *user) {
     CHECK_CTX(c);
     if ((alltoallv == nullptr) != (allreduce_sum == nullptr)) return fail(c, DORY_ERR_ARG, "set_host_transport: both callbacks or none");
+    fused_stamp_drop(c);
     c->tx_a2a = alltoallv;
     c->tx_ar = allreduce_sum;
     c->tx_user = user;
@@ -896,6 +970,7 @@ int dory_comm_set_scatter_transport(dory_ctx *c, dory_scatter_exchange_fn exchan
     CHECK_CTX(c);
     if ((exchange == nullptr) != (allreduce_sum == nullptr)) return fail(c, DORY_ERR_ARG, "set_scatter_transport: both callbacks or none");
     if (max_msg_bytes > 0xFFFFFFFFull) return fail(c, DORY_ERR_ARG, "set_scatter_transport: max_msg_bytes %llu is not below 2^32", (unsigned long long)max_msg_bytes);
+    fused_stamp_drop(c);
     c->scatter.fn = exchange;
     c->scatter.max_msg = max_msg_bytes;
     c->tx_a2a = nullptr;
@@ -933,6 +1008,7 @@ int dory_comm_unique_id(void *id128) {
 int dory_comm_init(dory_ctx *c, const void *id128, int rank, int nranks) {
     CHECK_CTX(c);
     if (!id128 || rank < 0 || rank >= nranks) return fail(c, DORY_ERR_ARG, "comm_init: bad arguments");
+    fused_stamp_drop(c);
     if (c->nccl) { ncclCommDestroy((ncclComm_t)c->nccl); c->nccl = nullptr; }
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
@@ -948,9 +1024,7 @@ int dory_halo_exchange(dory_ctx *c, uint32_t layer, int dir) {
     CHECK_CTX(c);
     { int wrc = wait_halo(c); if (wrc) return wrc; }
     if (c->numNodes == 1) return DORY_OK;  // no ghosts
-    // multi-head extension: the backward sweep exchanges dO and its per-vertex statistics itself, between its two
-    // phases (dory_aggregate); the scatter stage of the reference's GAT order has nothing to ship before it
-    if (c->gnn == DORY_GATMH && dir == DORY_BACKWARD) return DORY_OK;
+    if (exchange_skipped(c, dir)) return DORY_OK;
     Tensor *src, *ghost;
     int rc = halo_tensors(c, layer, dir, &src, &ghost);
     if (rc) return rc;
@@ -1002,6 +1076,32 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
     if (ghost->rows != c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: '%s' is not a ghost tensor of that direction", name);
     if (!strcmp(name, "fg_z") && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;   // (as halo_tensors: the kept neighbour sum of the old ghost rows no longer holds)
     return split_rows(c, "halo_unpack_tensor", false, dir, nullptr, ghost, const_cast<float *>(recv_buf));
+}
+
+// ---- the fused halo pack: switch and counters (include/dorylus_hip.h) ----------------------------------------------------------
+int dory_halo_fused_pack(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_fused_pack: dory_configure first; on is 0 or 1");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    fused_stamp_drop(c);
+    c->fused_pack = on == 1;
+    for (int dir = 0; dir < 2 && on; ++dir) {   // the plans that exist already: their lists come back from the device
+        HaloPlan &p = c->plan[dir];
+        if (!p.set || p.d_send_map) continue;
+        std::vector<uint32_t> lv(p.send_total);
+        if (p.send_total) HIPCK(c, hipMemcpy(lv.data(), p.d_send_lvids, (size_t)p.send_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        int rc = build_send_map(c, p, lv.data());
+        if (rc) return rc;
+    }
+    return DORY_OK;
+}
+
+int dory_halo_fused_pack_stats(dory_ctx *c, uint64_t *fused_exchanges, uint64_t *fused_rows, uint64_t *fallback_exchanges) {
+    CHECK_CTX(c);
+    if (fused_exchanges) *fused_exchanges = c->fused_exchanges;
+    if (fused_rows) *fused_rows = c->fused_rows;
+    if (fallback_exchanges) *fallback_exchanges = c->fallback_exchanges;
+    return DORY_OK;
 }
 
 // ---- scatter messages: the entry points (helpers above) ------------------------------------------------------------------

@@ -138,8 +138,28 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
     if (need > ((size_t)256 << 20)) need = (size_t)256 << 20;
     int rc = ensure_scratch(c, need);
     if (rc) return rc;
+    // the fused halo pack: a product that is the source of an exchange also goes into the send buffer -- once the previous
+    // exchange has finished reading it (dory_apply_vertex has waited already; a producer reached by another route waits here)
+    GemmSend sd{};
+    int send_dir = 0;
+    const Tensor *sent = nullptr;
+    if (c->fused_pack && ta == 0) {
+        if (C2 && fused_pack_target(c, C2, M, &sd, &send_dir)) { sent = C2; sd.which = 1; }
+        else if (fused_pack_target(c, &C, M, &sd, &send_dir)) { sent = &C; sd.which = 0; }
+    }
+    if (sent && (rc = wait_halo(c))) return rc;
     Timed t(c, "gemm", c->compute);
-    HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
+    if (!sent) {
+        fused_note_write(c, &C);
+        fused_note_write(c, C2);
+        HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
+        return DORY_OK;
+    }
+    sd.cols = N;
+    bool fused = false;
+    HIPCK(c, launch_gemm_send(g, sd, c->scratch, c->scratch_bytes, c->compute, &fused));
+    if (fused) fused_pack_stamp(c, sent, send_dir, sd);
+    else if (c->fused_stamp.src == sent) fused_stamp_drop(c);   // (rewritten without its rows in the buffer: K == 0)
     return DORY_OK;
 }
 
@@ -285,6 +305,7 @@ int dory_destroy(dory_ctx *c) {
         if (c->plan[d].d_send_lvids) (void)hipFree(c->plan[d].d_send_lvids);
         if (c->plan[d].d_unpack_slots && c->plan[d].d_unpack_slots != c->plan[d].d_recv_slots) (void)hipFree(c->plan[d].d_unpack_slots);
         if (c->plan[d].d_recv_slots) (void)hipFree(c->plan[d].d_recv_slots);
+        if (c->plan[d].d_send_map) (void)hipFree(c->plan[d].d_send_map);
     }
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->bf16_rows) (void)hipFree(c->bf16_rows);
@@ -669,7 +690,11 @@ int dory_tensor_info(dory_ctx *c, uint32_t layer, const char *name, uint64_t *ro
     if (rows) *rows = t->rows;
     if (cols) *cols = t->cols;
     if (ld) *ld = t->ld;
-    if (device_ptr) *device_ptr = t->d;
+    if (device_ptr) {   // (the fused halo pack: the caller may now write the rows itself -- this tensor's exchanges pack from here on)
+        *device_ptr = t->d;
+        t->raw_handed = true;
+        fused_note_write(c, t);
+    }
     return DORY_OK;
 }
 
@@ -756,6 +781,7 @@ int dory_tensor_upload(dory_ctx *c, uint32_t layer, const char *name, const floa
     if (!strcmp(name, "dA") && layer < c->gat_drow_valid.size()) c->gat_drow_valid[layer] = 0;
     if ((!strcmp(name, "z") || !strcmp(name, "fg_z")) && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;
     { int hrc = gat_edge_tensor_hook(c, layer, name, true); if (hrc) return hrc; }
+    fused_note_write(c, t);
     const HaloPlan *wire = nullptr;
     { int prc = ghost_wire_plan(c, "tensor_upload", name, *t, &wire); if (prc) return prc; }
     return wire ? upload_ghost_wire(c, *t, host, *wire) : upload_dense(c, *t, host);
@@ -784,6 +810,7 @@ int dory_tensor_fill_uniform(dory_ctx *c, uint32_t layer, const char *name, uint
     if (!strcmp(name, "dA") && layer < c->gat_drow_valid.size()) c->gat_drow_valid[layer] = 0;
     if ((!strcmp(name, "z") || !strcmp(name, "fg_z")) && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;
     { int hrc = gat_edge_tensor_hook(c, layer, name, true); if (hrc) return hrc; }
+    fused_note_write(c, t);
     uint32_t *ids = nullptr;
     const HaloPlan *wire = nullptr;
     { int prc = ghost_wire_plan(c, "tensor_fill", name, *t, &wire); if (prc) return prc; }

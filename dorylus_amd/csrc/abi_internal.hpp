@@ -115,6 +115,15 @@ bool tf_layer(dory_ctx *c, uint32_t layer);
 bool tf_active(dory_ctx *c);   // = tf_layer(c, 0)
 // one all-to-all-v of rows with the plan of `dir` (abi_comm.hip)
 int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer);
+// The fused halo pack (abi_comm.hip).  fused_pack_target: the GEMM about to write `out` (M rows, the product's C or its tanh output)
+// may store its rows into the send buffer too -- the feature is on, a plan and its map exist, `out` is the source of an exchange
+// of this model (the resolver halo_tensors uses), nothing of section "not taken" of dorylus_hip.h applies -- then *sd (but `which`)
+// and *dir are filled in.  fused_pack_stamp: that GEMM has been enqueued.  fused_stamp_drop: whatever the stamp named may be stale.
+bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd, int *dir);
+void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &sd);
+inline void fused_stamp_drop(dory_ctx *c) { c->fused_stamp = FusedStamp(); }
+// something other than a fusing GEMM writes `t` (may be null): a stamp that names it no longer describes its rows
+inline void fused_note_write(dory_ctx *c, const Tensor *t) { if (t && c->fused_stamp.src == t) fused_stamp_drop(c); }
 // scatter messages (abi_comm.hip): everything dory_ctx::scatter owns, at dory_destroy
 void scatter_free(dory_ctx *c);
 // K1b bookkeeping (abi_stages.hip)

@@ -818,6 +818,7 @@ int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {
                 NEED(h, layer, "h");
                 if (tf_layer(c, layer)) {   // z_l came out of dory_aggregate already
                     Timed t(c, "loss", c->compute);
+                    fused_note_write(c, h);
                     HIPCK(c, launch_tanh_forward(N, Fout, z->d, z->ld, h->d, h->ld, c->compute));
                 } else if ((rc = gemm(c, 0, 0, N, Fout, Fin, *ah, W, *z, h))) {
                     return rc;
@@ -984,6 +985,7 @@ int dory_predict_gat(dory_ctx *c, uint32_t layer) {
     NEED(ah, fl, "ah");
     NEED(lab, fl, "lab");
     NEED(grad, fl, "grad");
+    fused_note_write(c, grad);
     Timed t(c, "loss", c->compute);
     HIPCK(c, launch_softmax_sub(c->N, c->dims[layer], ah->d, ah->ld, lab->d, lab->ld, grad->d, grad->ld, c->compute));
     return DORY_OK;

@@ -27,6 +27,7 @@ struct Tensor {
     uint32_t ld = 0;
     float *d = nullptr;
     bool owned = true;  // false: alias of another allocation (GAT "A" = csc values)
+    bool raw_handed = false;   // dory_tensor_info has handed out its device pointer: never the target of a fused halo pack again
     size_t bytes() const { return (size_t)rows * ld * sizeof(float); }
 };
 
@@ -51,6 +52,18 @@ struct HaloPlan {
     bool direct = false;
     std::vector<uint32_t> order;
     uint32_t *d_unpack_slots = nullptr;
+    // the fused halo pack (dory_halo_fused_pack): the send list turned round, row -> slots of the packed send buffer, as
+    // dory_halo_send_map makes it -- one allocation of row_ptr[N + 1] followed by row_slots[send_total]; null: not built
+    uint32_t *d_send_map = nullptr;
+    uint32_t send_map_rows = 0;   // the N it was built for (a graph uploaded again with another N: no fusing until the next plan)
+};
+// The fused halo pack's stamp: the rows of `src` lie in `buf` (the context's send buffer as it was then) packed for the exchange
+// of direction `dir` at w floats per row, written by a GEMM epilogue.  abi_comm.hip makes, matches and drops it.
+struct FusedStamp {
+    const Tensor *src = nullptr;   // null: no stamp
+    int dir = 0;
+    uint32_t w = 0;
+    const float *buf = nullptr;
 };
 
 // The wire format of a packed halo row: w floats per row -- the tensor's padded ld, or with `exact` (option halo_exact_rows)
@@ -283,6 +296,10 @@ struct dory_ctx {
     // landed in the ghost tensor itself / went through a receive buffer and an unpack
     std::atomic<int> halo_direct{0};
     uint64_t halo_direct_recvs = 0, halo_staged_recvs = 0;
+    // the fused halo pack (dory_halo_fused_pack; default off), its one stamp, and the eager exchanges counted while it is on
+    bool fused_pack = false;
+    dory::FusedStamp fused_stamp;
+    uint64_t fused_exchanges = 0, fused_rows = 0, fallback_exchanges = 0;
     dory::ScatterState scatter;   // scatter messages (dory_scatter_msgs_*) and the scatter transport
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
@@ -446,6 +463,17 @@ struct GemmArgs {
     const float *Zp; uint32_t ldz;
 };
 hipError_t launch_gemm(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s);
+// The fused halo pack (dory_halo_fused_pack): the extra argument of K2's send kernels.  Row r of the product is also stored at the
+// rows row_slots[row_ptr[r] .. row_ptr[r + 1]) of buf, w floats each -- w == the tensor's ld (a padded wire row: [cols, w) gets
+// zeros) or == cols (halo_exact_rows: dense rows); `which`: 0 the rows of C, 1 those of the tanh output C2.
+struct GemmSend {
+    float *buf;
+    const uint32_t *row_ptr;     // M + 1 (dory_halo_send_map)
+    const uint32_t *row_slots;   // row_ptr[M]
+    uint32_t w, which, cols;
+};
+// NN and NT with M, K > 0: *fused = true and the rows are in buf; anything else runs as launch_gemm and leaves *fused false
+hipError_t launch_gemm_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *fused);
 size_t gemm_scratch_bytes(uint32_t M, uint32_t N, uint32_t K);
 
 // tanh of the transform's epilogue (K2), of the stand-alone activation and of K3's backward -- one function for all three, so

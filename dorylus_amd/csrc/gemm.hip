@@ -94,8 +94,22 @@ __device__ __forceinline__ void dma_frag(float (&f)[8], const float *img, int bl
     }
 }
 
-template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
-__device__ __forceinline__ void gemm_dma_body(const GemmArgs &g, uint32_t klen, float *partial, float *smem) {
+// one element of row `row` into every slot the row has in the send buffer (64-bit offsets: a send buffer may exceed 4 GB): the
+// split-K reduce's form, whose consecutive threads walk one row
+__device__ __forceinline__ void send_store(const GemmSend &sd, uint32_t row, uint32_t col, float v) {
+    const uint32_t s1 = sd.row_ptr[row + 1];
+    for (uint32_t s = sd.row_ptr[row]; s < s1; ++s) sd.buf[(size_t)sd.row_slots[s] * sd.w + col] = v;
+}
+
+// SEND (the fused halo pack, dory_halo_fused_pack): the epilogue stores every element of a row once more into each of the row's
+// slots of the packed send buffer -- what gather_rows_kernel would copy out of C (or of the tanh output C2) afterwards.  Columns
+// [cols, w) of a padded wire row get the zeros of the tensor's padding; a split launch leaves all of it to the reduce kernel.
+// The store loop leaves the value that travels in the accumulator, and a second pass walks the rows: the 32 lanes that hold a row
+// load its slot range and each slot once for both column tiles and write 128 contiguous bytes of the slot's row per tile (the
+// slot loop inside the store loop, indices reloaded per element, cost more than the pack kernel at two shapes:
+// profiles/r17_halo_fused_pack.txt).
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK, bool SEND = false>
+__device__ __forceinline__ void gemm_dma_body(const GemmArgs &g, uint32_t klen, float *partial, float *smem, const GemmSend &sd = GemmSend{}) {
     static_assert(WM * WN == 4 && WN * TN * 32 == BN, "tile shape");
     constexpr int BM = WM * TM * 32;
     constexpr int A_SZ = BM * BK, B_SZ = BN * BK, STAGE = A_SZ + B_SZ;
@@ -174,14 +188,40 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs &g, uint32_t klen, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const uint32_t row = i0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+                float sv = 0.f;   // SEND: what travels of this element (zero: the padding of a padded wire row)
                 if (row < g.M && col < g.N) {
                     const float v = acc[a][b][r];
                     C[(size_t)row * g.ldc + col] = v;
-                    if (!split && g.epilogue == EPI_TANH)
-                        g.C2[(size_t)row * g.ldc2 + col] = dory_tanh(v);
+                    sv = v;
+                    if (!split && g.epilogue == EPI_TANH) {
+                        const float t = dory_tanh(v);
+                        g.C2[(size_t)row * g.ldc2 + col] = t;
+                        if (SEND && sd.which) sv = t;
+                    }
                 }
+                if constexpr (SEND) acc[a][b][r] = sv;   // (the accumulator is spent: it carries the value to the pass below)
             }
         }
+    if constexpr (SEND) {
+        // a pass of its own, row by row: the row's slot range and every slot are loaded once for all its column tiles
+        if (split) return;
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t row = i0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+                if (row >= g.M) continue;
+                const uint32_t s1 = sd.row_ptr[row + 1];
+                for (uint32_t s = sd.row_ptr[row]; s < s1; ++s) {
+                    float *dst = sd.buf + (size_t)sd.row_slots[s] * sd.w;   // (64-bit: a send buffer may exceed 4 GB)
+#pragma unroll
+                    for (int b = 0; b < TN; ++b) {
+                        const uint32_t col = j0 + (wn * TN + b) * 32 + fr;
+                        if (col < sd.w) dst[col] = acc[a][b][r];
+                    }
+                }
+            }
+    }
 }
 
 template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
@@ -194,6 +234,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                                                                      float *partial) {
     __shared__ __attribute__((aligned(1024))) float smem[2 * (WM * TM * 32 + BN) * BK];
     gemm_dma_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK>(g, klen, partial, smem);
+}
+
+// the same two with SEND: kernels of their own (the send descriptor is their extra argument), so that the ones above keep their
+// names and code objects
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) void gemm_dma_send_kernel(GemmArgs g, uint32_t klen, float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) float smem[2 * (WM * TM * 32 + BN) * BK];
+    gemm_dma_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true>(g, klen, partial, smem, sd);
+}
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_dma_send_kernel_occ4(GemmArgs g, uint32_t klen,
+                                                                                                          float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) float smem[2 * (WM * TM * 32 + BN) * BK];
+    gemm_dma_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true>(g, klen, partial, smem, sd);
 }
 
 // second stage of split-K: C = sum_z partial[z] in z order (deterministic); eight
@@ -217,6 +271,41 @@ __global__ void splitk_reduce_kernel(float *C, const float *partial, uint32_t M,
         for (; z < S; ++z) s += partial[(size_t)z * n + i];
         C[i] = s;
         if (C2) C2[(i / ldc) * ldc2 + (i % ldc)] = dory_tanh(s);
+    }
+}
+
+// ... and its SEND form, a kernel of its own (sharing one body with the kernel above changed that kernel's code object): the sums in
+// the same order -- RU partials requested at a time, RU = the unroll above -- and every element, with the zero padding of a padded
+// wire row, also into the row's slots of the send buffer
+__global__ void splitk_reduce_send_kernel(float *C, const float *partial, uint32_t M, uint32_t N, uint32_t ldc, uint32_t S,
+                                          float *C2 /*EPI_TANH: tanh(C), or nullptr*/, uint32_t ldc2, GemmSend sd) {
+    constexpr uint32_t RU = 8;
+    const size_t n = (size_t)M * ldc;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t row = (uint32_t)(i / ldc), col = (uint32_t)(i % ldc);
+        if (col >= N) {
+            if (col < sd.w) send_store(sd, row, col, 0.f);
+            continue;
+        }
+        float s = 0.f;
+        uint32_t z = 0;
+        for (; z + RU <= S; z += RU) {
+            float v[RU];
+#pragma unroll
+            for (uint32_t u = 0; u < RU; ++u) v[u] = partial[(size_t)(z + u) * n + i];
+#pragma unroll
+            for (uint32_t u = 0; u < RU; ++u) s += v[u];
+        }
+        for (; z < S; ++z) s += partial[(size_t)z * n + i];
+        C[i] = s;
+        float sv = s;
+        if (C2) {
+            const float t = dory_tanh(s);
+            C2[(size_t)row * ldc2 + col] = t;
+            if (sd.which) sv = t;
+        }
+        if (col < sd.w) send_store(sd, row, col, sv);
     }
 }
 
@@ -247,7 +336,7 @@ size_t gemm_scratch_bytes(uint32_t M, uint32_t N, uint32_t K) {
 }
 
 template <int BN, int WM, int WN, int TM, int TN, int BK>
-static hipError_t launch_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s) {
+static hipError_t launch_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd = nullptr) {
     if (g.K == 0) {   // empty partition: the product of an M x 0 and a 0 x N matrix is all zeros (tanh(0) = 0 too)
         hipError_t e = hipMemsetAsync(g.C, 0, (size_t)g.M * g.ldc * sizeof(float), s);
         if (e == hipSuccess && g.epilogue == EPI_TANH && g.C2)
@@ -272,31 +361,57 @@ static hipError_t launch_bn(const GemmArgs &g, float *scratch, size_t scratch_by
         else                                                                                                                  \
             hipLaunchKernelGGL((gemm_dma_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch);      \
     } while (0)
-    if (!g.ta && !g.tb) GEMM_LAUNCH(false, true);
+#define GEMM_LAUNCH_SEND(AK, BKM)                                                                                                        \
+    do {                                                                                                                                 \
+        if constexpr (BN == 128 && WM * TM * 32 == 128)                                                                                  \
+            hipLaunchKernelGGL((gemm_dma_send_kernel_occ4<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd); \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((gemm_dma_send_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd);      \
+    } while (0)
+    if (sd && !g.ta && !g.tb) GEMM_LAUNCH_SEND(false, true);          // (launch_gemm_send: NN and NT only)
+    else if (sd && !g.ta && g.tb) GEMM_LAUNCH_SEND(false, false);
+    else if (sd) return hipErrorInvalidValue;
+    else if (!g.ta && !g.tb) GEMM_LAUNCH(false, true);
     else if (!g.ta && g.tb) GEMM_LAUNCH(false, false);
     else if (g.ta && !g.tb) GEMM_LAUNCH(true, true);
     else return hipErrorInvalidValue;
 #undef GEMM_LAUNCH
+#undef GEMM_LAUNCH_SEND
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (S > 1) {
         const size_t n = (size_t)g.M * g.ldc;
         int blocks = (int)((n + 255) / 256);
         if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, g.C, scratch, g.M, g.N, g.ldc, S,
-                           g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2);
+        if (sd)
+            hipLaunchKernelGGL(splitk_reduce_send_kernel, dim3(blocks), dim3(256), 0, s, g.C, scratch, g.M, g.N, g.ldc, S,
+                               g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2, *sd);
+        else
+            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, g.C, scratch, g.M, g.N, g.ldc, S,
+                               g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2);
         e = hipGetLastError();
     }
     return e;
 }
 
-hipError_t launch_gemm(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s) {
+// with sd: the product's rows also go into the send buffer (*fused = true), where a send form exists -- NN and NT with rows and a
+// K to sum over; everything else (TN, the memset of K == 0, M == 0) runs as without and leaves *fused false
+static hipError_t launch_gemm_any(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd, bool *fused) {
+    if (fused) *fused = false;
     if (g.M == 0 || g.N == 0) return hipSuccess;
+    if (sd && (g.ta || g.K == 0 || sd->cols != g.N || sd->w > g.ldc || sd->w > pad_ld(g.N) || (sd->which && g.epilogue != EPI_TANH))) sd = nullptr;
     // the DMA moves 16-byte pieces: rows must start on 16-byte boundaries (every tensor of the table does: ld is padded to 32 floats)
     if ((g.lda & 3u) || (g.ldb & 3u) || (reinterpret_cast<uintptr_t>(g.A) & 15u) || (reinterpret_cast<uintptr_t>(g.B) & 15u))
         return hipErrorInvalidValue;
-    if (g.N > 64) return launch_bn<128, 2, 2, GEMM_BM_WIDE / 64, 2, 16>(g, scratch, scratch_bytes, s);
-    return launch_bn<64, 4, 1, GEMM_BM_NARROW / 128, 2, 16>(g, scratch, scratch_bytes, s);
+    if (fused) *fused = sd != nullptr;
+    if (g.N > 64) return launch_bn<128, 2, 2, GEMM_BM_WIDE / 64, 2, 16>(g, scratch, scratch_bytes, s, sd);
+    return launch_bn<64, 4, 1, GEMM_BM_NARROW / 128, 2, 16>(g, scratch, scratch_bytes, s, sd);
+}
+hipError_t launch_gemm(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s) {
+    return launch_gemm_any(g, scratch, scratch_bytes, s, nullptr, nullptr);
+}
+hipError_t launch_gemm_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *fused) {
+    return launch_gemm_any(g, scratch, scratch_bytes, s, &sd, fused);
 }
 
 }  // namespace dory

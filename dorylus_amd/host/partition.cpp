@@ -427,6 +427,26 @@ int dory_partition_recv_plan(const dory_partition *p, const int32_t *parts, int 
     return DORY_OK;
 }
 
+// the send lists turned round (the fused halo pack): a counting pass over the concatenated lists, slot by slot, so that the slots of
+// a row come out ascending
+int dory_halo_send_map(uint32_t local_vtx_cnt, uint32_t num_nodes, const uint32_t *send_counts, const uint32_t *send_lvids,
+                       uint32_t *row_ptr, uint32_t *row_slots) {
+    if (!send_counts || !row_ptr || num_nodes == 0) return herr(DORY_ERR_ARG, "halo_send_map: bad arguments");
+    const uint32_t N = local_vtx_cnt;
+    uint64_t total = 0;
+    for (uint32_t q = 0; q < num_nodes; ++q) total += send_counts[q];
+    if (total > 0xFFFFFFFFull) return herr(DORY_ERR_ARG, "halo_send_map: more than 2^32 - 1 send rows");
+    if (total && (!send_lvids || !row_slots)) return herr(DORY_ERR_ARG, "halo_send_map: bad arguments");
+    for (uint64_t s = 0; s < total; ++s)
+        if (send_lvids[s] >= N) return herr(DORY_ERR_ARG, "halo_send_map: send lvid out of range");
+    std::fill(row_ptr, row_ptr + (size_t)N + 1, 0u);
+    for (uint64_t s = 0; s < total; ++s) row_ptr[send_lvids[s] + 1]++;
+    for (uint32_t r = 0; r < N; ++r) row_ptr[r + 1] += row_ptr[r];
+    std::vector<uint32_t> next(row_ptr, row_ptr + N);
+    for (uint64_t s = 0; s < total; ++s) row_slots[next[send_lvids[s]]++] = (uint32_t)s;
+    return DORY_OK;
+}
+
 int dory_partition_wire_order(const dory_partition *p, const int32_t *parts, int dir, uint32_t *order, uint32_t *idxs) {
     if (!p || !parts || (dir != 0 && dir != 1)) return herr(DORY_ERR_ARG, "wire_order: bad arguments");
     const uint32_t G = dir == 0 ? p->Gsrc : p->Gdst;

@@ -215,6 +215,34 @@ int dory_halo_unpack(dory_ctx *ctx, uint32_t layer, int dir, const float *recv_b
 int dory_halo_pack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int dir, float *send_buf);
 int dory_halo_unpack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int dir, const float *recv_buf);
 
+/* ---- fused halo pack: the GEMM epilogues write the send rows (opt-in, default off; nothing in the reference: an MI355X-side
+ * addition) ----
+ * An exchange's pack kernel re-reads rows a GEMM wrote just before and sits in front of the link.  With the feature on, a K2 GEMM
+ * whose output (C, or the tanh output C2) is the tensor dory_halo_exchange would pack next -- GCN h@l (l < L-1, forward), grad@l
+ * (l >= 1, backward), xw@l (l > 0 of a transform-first layer, forward); GAT z@l (forward), grad@(l-1) of dory_apply_vertex
+ * backward (backward); multi-head GAT z@l (forward) -- stores every row once more from its epilogue into the row's slots of the
+ * internal send buffer (the plan's send lists turned round: dory_halo_send_map of dorylus_host.h, kept on the device per direction,
+ * 4 (N + 1) + 4 send_total bytes, built by dory_halo_plan while on or by this call for the plans that exist, freed with the plan;
+ * nothing is allocated inside an epoch).  The row width is the exchange's own (halo_exact_rows: cols floats, else ld with the
+ * padding zeroed): the buffer is byte for byte what the pack kernel leaves, every tensor keeps its bits.  The context then holds
+ * ONE stamp {source tensor, direction, width, send buffer}; the exchange whose source, direction, width and buffer match it skips
+ * its pack kernel and consumes the stamp (fused_exchanges += 1, fused_rows += send rows); with the feature on any other exchange
+ * packs as ever and counts as a fallback.  The stamp is dropped by dory_tensor_upload / dory_tensor_fill_uniform of that tensor,
+ * by any pack into the internal send buffer (another exchange; the multi-head GAT's "do" / "st"), by the buffer growing, by a new
+ * plan, by dory_halo_fused_pack(ctx, 0), by any dory_comm_* call; a second producer of the same tensor replaces it.  Once
+ * dory_tensor_info has handed out a source tensor's device pointer that tensor never fuses again on this context (its rows may
+ * change behind the library's back).  Not taken, i.e. a counted fallback with the same results: sources no GEMM writes (h of a
+ * transform-first layer, g, the GAT models' last-layer grad, do / st), a product with K == 0 or no local rows, the scatter
+ * transport (another buffer layout), the in-process transport with halo_direct_recv = 1 (the peers read the send buffer on their
+ * own streams), epoch-graph recording.  dory_halo_pack* always run the kernel into the caller's buffer and leave the stamp
+ * alone.  The producer waits for the previous exchange (as dory_apply_vertex does anyway) before its epilogue writes the
+ * buffer.  num_nodes == 1: accepted, nothing changes.
+ * dory_halo_fused_pack: on = 0 / 1, any time after dory_configure, outside an exchange.
+ * dory_halo_fused_pack_stats: exchanges that skipped the pack, their send rows, exchanges that packed although the feature was
+ * on -- eager calls only, counted since dory_create; any pointer may be NULL. */
+int dory_halo_fused_pack(dory_ctx *ctx, int on);
+int dory_halo_fused_pack_stats(dory_ctx *ctx, uint64_t *fused_exchanges, uint64_t *fused_rows, uint64_t *fallback_exchanges);
+
 /* ---- scatter messages: the reference's own graph-server <-> graph-server wire, packed and unpacked on the device ----------
  * What Engine::verticesPushOut puts on a socket and ghostReceiver* takes apart (include/dorylus_wire.h: the format table with
  * its citations): messages of an 8-character receiver topic, five unsigned header fields and (global vertex id, featDim floats)

@@ -74,6 +74,16 @@ int dory_partition_recv_plan(const dory_partition *p, const int32_t *parts, int 
  * partition itself is not modified (dory_partition_get and dory_partition_save keep giving the reference's numbering). */
 int dory_partition_wire_order(const dory_partition *p, const int32_t *parts, int dir, uint32_t *order, uint32_t *idxs);
 
+/* The inverse of a halo plan's send side (pure host code, no context, no device; nothing in the reference: an MI355X-side
+ * addition for dory_halo_fused_pack of dorylus_hip.h).  send_counts (num_nodes entries) and send_lvids (all peers' lists
+ * concatenated) are dory_halo_plan's: entry s of send_lvids is the local row that travels as row s -- "slot" s -- of the packed send
+ * buffer.  Out: row_ptr (local_vtx_cnt + 1 entries) and row_slots (sum of the counts), a CSR of row -> slots: the slots of row r are
+ * row_slots[row_ptr[r] .. row_ptr[r + 1]), ascending.  A row has one slot per peer that needs it (at most num_nodes - 1, maybe
+ * none); a list that names a row twice gives it two.  Every slot appears exactly once.  DORY_ERR_ARG for an id >=
+ * local_vtx_cnt. */
+int dory_halo_send_map(uint32_t local_vtx_cnt, uint32_t num_nodes, const uint32_t *send_counts, const uint32_t *send_lvids,
+                       uint32_t *row_ptr, uint32_t *row_slots);
+
 /* upload adjacency (dory_graph_upload) and, when parts is given, both halo plans
  * (dory_halo_plan): recv slots of peer q = ghost slots whose owner is q, ascending.  On a context with option
  * "halo_direct_recv" = 1 the index arrays uploaded are the renumbered copies of dory_partition_wire_order (parts is then

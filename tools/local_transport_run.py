@@ -14,7 +14,8 @@ with next to nothing else on the device -- the closest one GPU gets to one rank 
 sweeps, 4 to rank 1's, 4 left to the copies).
 A/B runs: --opt KEY=VALUE (repeatable) sets a context option on every rank before the upload (e.g. halo_direct_recv=1),
 --configs NAME... keeps only those configurations, --skip-oracle leaves the CPU oracle's epoch out; DORY_LIB_PATH picks the
-library.  Each run then also records every rank's receive-buffer bytes where the library reports them."""
+library.  Each run then also records every rank's receive-buffer bytes where the library reports them.  --fused-pack switches
+dory_halo_fused_pack on on every rank and records its counters (exchanges fused, their rows, fallbacks) per rank."""
 import argparse
 import json
 import os
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--opt", action="append", default=[], help="KEY=VALUE, a context option of every rank")
     ap.add_argument("--configs", nargs="*", default=None)
     ap.add_argument("--skip-oracle", action="store_true")
+    ap.add_argument("--fused-pack", action="store_true", help="dory_halo_fused_pack(1) on every rank")
     a = ap.parse_args()
     import torch  # noqa: F401
     import dorylus_amd as da
@@ -50,7 +52,7 @@ def main():
     Ws = [(rng.standard_normal((dims[i], dims[i + 1])) / np.sqrt(dims[i])).astype(np.float32) for i in range(L)]
 
     extra = {k: int(v) for k, v in (kv.split("=", 1) for kv in a.opt)}
-    recv_bytes = {}
+    recv_bytes, fused_stats = {}, {}
 
     def setup(ctx, r, g):
         close = ctx.close
@@ -61,8 +63,12 @@ def main():
                     recv_bytes[r] = ctx.get_option("halo_recv_buf_bytes")
                 except da.DoryError:
                     recv_bytes[r] = None      # (a library from before the counter)
+                if a.fused_pack:
+                    fused_stats[r] = list(ctx.halo_fused_pack_stats())
             close()
         ctx.close = closing
+        if a.fused_pack:
+            ctx.halo_fused_pack(1)
         if g["localVtxCnt"]:
             ctx.upload(0, "x", X[g["localToGlobal"]])
         if g["srcGhostCnt"]:
@@ -93,7 +99,7 @@ def main():
         configs = [c for c in configs if c[0] in a.configs]
     with_extra = lambda sh: [dict(x, **extra) for x in sh] if isinstance(sh, list) else dict(sh, **extra)
     configs = [(name, P, parts, with_extra(share)) for name, P, parts, share in configs]
-    out["options"] = extra
+    out["options"] = dict(extra, fused_pack=int(a.fused_pack))
     for name, P, parts, share in ([] if a.skip_oracle else [c for c in configs if c[0] == "balanced"]):
         pobjs = [da.Partition.build(src, dst, parts, r, P) for r in range(P)]
         dl = [(l, nm) for l in range(L) for nm in ("ah",)] + [(l, nm) for l in range(L - 1) for nm in ("h", "aTg")] + [(l, "grad") for l in range(1, L)]
@@ -126,7 +132,8 @@ def main():
                    "epoch_ms_first_last": [round(float(ms.max(axis=0)[0]), 4), round(float(ms.max(axis=0)[-1]), 4)],
                    "timing_sum_over_ranks_ms": {k: v for k, v in tm.items()},
                    "halo_overlap_fraction": round(tm["halo_hidden"]["ms"] / tm["halo_deferred"]["ms"], 4) if tm["halo_deferred"]["ms"] else None,
-                   "spmm_gates": res["gates"], "recv_buf_bytes_per_rank": [recv_bytes.get(r) for r in range(P)], "wall_s": round(wall, 2)}
+                   "spmm_gates": res["gates"], "recv_buf_bytes_per_rank": [recv_bytes.get(r) for r in range(P)],
+                   "fused_pack_stats_per_rank": [fused_stats.get(r) for r in range(P)] if a.fused_pack else None, "wall_s": round(wall, 2)}
             out["runs"].append(rec)
             bits[overlap] = res
             sys.stderr.write(json.dumps({k: rec[k] for k in ("config", "P", "halo_overlap", "epoch_ms_median_max_rank", "halo_overlap_fraction", "spmm_gates")}) + "\n")
