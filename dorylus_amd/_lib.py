@@ -29,6 +29,7 @@ SYMBOLS = [
     "dory_scatter_msgs_finish",
     "dory_comm_set_scatter_transport",
     "dory_halo_fused_pack", "dory_halo_fused_pack_stats",
+    "dory_gat_bf16_gather", "dory_gat_bf16_gather_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -119,6 +120,8 @@ def load():
         "dory_comm_set_scatter_transport": [vp, SCATTER_EXCHANGE_FN, ALLREDUCE_FN, vp, u64],
         "dory_halo_fused_pack": [vp, i32],
         "dory_halo_fused_pack_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
+        "dory_gat_bf16_gather": [vp, i32, i32],
+        "dory_gat_bf16_gather_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -151,8 +154,8 @@ def load():
     for name, args in sig.items():
         if (name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check", "dory_halo_wire_ids",
                      "dory_comm_set_scatter_transport", "dory_halo_send_map") or name.startswith("dory_scatter_msgs_")
-                or name.startswith("dory_halo_fused_pack")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack)
+                or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -510,6 +513,17 @@ class Context:
     def halo_fused_pack(self, on=True):
         """the GEMM epilogues write the send rows of the exchange that follows (opt-in; dory_halo_fused_pack)"""
         self._ck(self.lib.dory_halo_fused_pack(self.h, int(on)))
+
+    def gat_bf16_gather(self, mode, wide=False):
+        """GAT prototype: the aggregations gather their rows rounded to bf16 (opt-in; dory_gat_bf16_gather) -- mode 1: those that
+        read z / fg_z, 2: the backward's A^T grad too; wide: 16-byte gathers on K1s for rows of 128 floats or more, same bits"""
+        self._ck(self.lib.dory_gat_bf16_gather(self.h, int(mode), int(wide)))
+
+    def gat_bf16_gather_stats(self):
+        """aggregations that ran on bf16 rows per kernel family: dict(k1s, k1s_wide, k1, fp32_fallbacks)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._ck(self.lib.dory_gat_bf16_gather_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("k1s", "k1s_wide", "k1", "fp32_fallbacks"), (int(x.value) for x in v)))
 
     def halo_fused_pack_stats(self):
         """(exchanges that skipped their pack kernel, the send rows of those, exchanges that packed although the feature was on)"""

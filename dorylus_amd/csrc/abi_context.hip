@@ -365,6 +365,8 @@ int dory_configure(dory_ctx *c, int gnn_type, uint32_t num_layers, const uint32_
         if (dims[i] == 0) return fail(c, DORY_ERR_ARG, "dory_configure: zero layer width");
     char msg[256];
     if (option_model_conflict(c->opt, gnn_type, msg, sizeof(msg))) return fail(c, DORY_ERR_ARG, "%s", msg);
+    if (c->gat_bf16_mode && gnn_type != DORY_GAT)
+        return fail(c, DORY_ERR_ARG, "dory_configure: dory_gat_bf16_gather mode %d is set, which serves the GAT prototype (DORY_GAT) only", c->gat_bf16_mode);
     c->gnn = gnn_type;
     c->L = num_layers;
     c->dims.assign(dims, dims + num_layers + 1);
@@ -374,6 +376,31 @@ int dory_configure(dory_ctx *c, int gnn_type, uint32_t num_layers, const uint32_
     c->heads.assign(num_layers, 8);   // multi-head GAT extension defaults: 8 hidden heads, 1 output head
     c->heads[num_layers - 1] = 1;
     c->configured = true;
+    return DORY_OK;
+}
+
+// ---- the GAT prototype's bf16 row gathers: switch and counters (include/dorylus_hip.h; the dispatch: abi_stages.hip) ----
+int dory_gat_bf16_gather(dory_ctx *c, int mode, int wide) {
+    CHECK_CTX(c);
+    if (c->configured && c->gnn != DORY_GAT)
+        return fail(c, DORY_ERR_ARG, "gat_bf16_gather: this context is configured as %s; the feature serves the GAT prototype (DORY_GAT) only",
+                    c->gnn == DORY_GCN ? "DORY_GCN (its option: gcn_bf16_gather)" : "DORY_GATMH (its option: gatmh_bf16_gather)");
+    if (mode < 0 || mode > 2) return fail(c, DORY_ERR_ARG, "gat_bf16_gather: mode %d outside 0..2", mode);
+    if (wide < 0 || wide > 1) return fail(c, DORY_ERR_ARG, "gat_bf16_gather: wide %d outside 0..1", wide);
+    if (wide && !mode) return fail(c, DORY_ERR_ARG, "gat_bf16_gather: wide = 1 needs mode 1 or 2 (nothing gathers bf16 rows with mode 0)");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gat_bf16_gather: not while an epoch graph is being recorded");
+    if (mode != c->gat_bf16_mode || (wide == 1) != c->gat_bf16_wide) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other mode's kernels)
+    c->gat_bf16_mode = mode;
+    c->gat_bf16_wide = wide == 1;
+    return gat_bf16_reserve_all(c);   // (before dory_preallocate: nothing yet -- the first eager aggregation reserves)
+}
+
+int dory_gat_bf16_gather_stats(dory_ctx *c, uint64_t *k1s, uint64_t *k1s_wide, uint64_t *k1, uint64_t *fp32_fallbacks) {
+    CHECK_CTX(c);
+    if (k1s) *k1s = c->gat_bf16_gathers_k1s;
+    if (k1s_wide) *k1s_wide = c->gat_bf16_gathers_k1s_wide;
+    if (k1) *k1 = c->gat_bf16_gathers_k1;
+    if (fp32_fallbacks) *fp32_fallbacks = c->gat_bf16_fp32_fallbacks;
     return DORY_OK;
 }
 
@@ -582,6 +609,7 @@ int dory_preallocate(dory_ctx *c) {
         c->gat_arow_valid.assign(L, 0);
         c->gat_drow_valid.assign(L, 0);
         c->gat_nsum_valid.assign(L, 0);
+        c->gat_nsum_bf16.assign(L, 0);
     }
     if (rc) return rc;
     for (uint32_t l = 0; l < L; ++l) {
@@ -657,8 +685,9 @@ int dory_preallocate(dory_ctx *c) {
             for (Adjacency &A : c->adj) {
                 if ((rc = ensure_sweep(c, A, group))) return rc;
                 if (A.swp.nb) need = std::max(need, sweep_counter_bound(A.swp.npos, maxld, group, k1s_rows(c, A.swp, group), false, G, A.swp.nb));
-                // (option gcn_bf16_wide's launches never need more, but for a forced row count that only 16-lane groups take)
-                if (A.swp.nb && c->gnn == DORY_GCN && sweep_wide_applies(maxld, group, k1s_rows(c, A.swp, 16)))
+                // (the wide launches of option gcn_bf16_wide / dory_gat_bf16_gather never need more, but for a forced row count that only
+                //  16-lane groups take)
+                if (A.swp.nb && sweep_wide_applies(maxld, group, k1s_rows(c, A.swp, 16)))
                     need = std::max(need, sweep_counter_bound(A.swp.npos, maxld, group, k1s_rows(c, A.swp, 16), true, G, A.swp.nb));
             }
             if ((rc = ensure_partial(c, need, "sweep counters"))) return rc;

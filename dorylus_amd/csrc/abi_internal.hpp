@@ -129,6 +129,8 @@ void scatter_free(dory_ctx *c);
 // K1b bookkeeping (abi_stages.hip)
 int ensure_blocked(dory_ctx *c, Adjacency &A, int group, bool narrow_set = false /* the multi-head GAT contexts' second copy (Adjacency::blk16) */);
 int blk_group_for(dory_ctx *c, uint32_t ld);
+// dory_gat_bf16_gather: the bf16 shadow rows of the model's largest aggregation, reserved outside a recording (abi_stages.hip)
+int gat_bf16_reserve_all(dory_ctx *c);
 
 }  // namespace dory
 #endif

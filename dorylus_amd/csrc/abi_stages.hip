@@ -104,7 +104,7 @@ int blk_group_for(dory_ctx *c, uint32_t ld) {
     return group;
 }
 
-// Options gcn_bf16_gather / gatmh_bf16_gather: the rows of one aggregation rounded to bf16 into the context's shadow buffer,
+// Options gcn_bf16_gather / gatmh_bf16_gather, dory_gat_bf16_gather: the rows of one aggregation rounded to bf16 into the context's shadow buffer,
 // [N local rows ; ghost rows], every call (nothing is kept: a caller may write x / h / fg through a raw pointer between two
 // calls).  The buffer only grows, outside a recording.
 static int bf16_reserve(dory_ctx *c, uint64_t rows, uint32_t ld, const char *option) {
@@ -243,8 +243,10 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     const DerivedAdj &S = A.swp;
     if (S.na || !sweep_supported(a, S, group)) return SPMM_NOT_MINE;
     const bool bf16 = bf.on();
-    // option gcn_bf16_wide: bf16 rows of 128 floats or more are gathered eight features per lane (same bits; spmm.hip)
-    const bool wide = bf16 && c->opt[OPT_GCN_BF16_WIDE] == 1 && sweep_wide_applies(a.ld, group, k1s_rows(c, S, 16));
+    // option gcn_bf16_wide (GAT prototype: dory_gat_bf16_gather's `wide`): bf16 rows of 128 floats or more are gathered eight
+    // features per lane (same bits; spmm.hip)
+    const bool gat = c->gnn == DORY_GAT;
+    const bool wide = bf16 && (gat ? c->gat_bf16_wide : c->opt[OPT_GCN_BF16_WIDE] == 1) && sweep_wide_applies(a.ld, group, k1s_rows(c, S, 16));
     SweepLaunch sw = sweep_launch(c, S, a.ld, group, a.xg != nullptr, k1s_rows(c, S, wide ? 16 : group), bf16, wide);
     if ((rc = ensure_partial(c, sw.need, "sweep counters"))) return rc;   // (K1s may still size its counters here, outside a recording)
     sw.done = reinterpret_cast<uint32_t *>(c->partial);
@@ -257,8 +259,8 @@ static int spmm_k1s(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
     }
     Timed t(c, "spmm", c->compute);
     c->spmm_launches_k1s++;
-    if (bf16) c->bf16_gathers_k1s++;
-    if (wide) c->bf16_gathers_k1s_wide++;
+    if (bf16) (gat ? c->gat_bf16_gathers_k1s : c->bf16_gathers_k1s)++;
+    if (wide) (gat ? c->gat_bf16_gathers_k1s_wide : c->bf16_gathers_k1s_wide)++;
     auto sweep = [&](const SweepPart &p) -> int {
         HIPCK(c, launch_spmm_sweep(a, S, group, row_scale, c->scratch, p));
         return DORY_OK;
@@ -306,7 +308,7 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
     if (!a.val) return fail(c, DORY_ERR_ARG, "spmm: no edge values");
     const bool bf16 = bf.on();
     c->spmm_launches_k1++;
-    if (bf16) c->bf16_gathers_k1++;
+    if (bf16) (c->gnn == DORY_GAT ? c->gat_bf16_gathers_k1 : c->bf16_gathers_k1)++;
     auto launch = [&](const SpmmArgs &x) -> int {
         HIPCK(c, launch_spmm(x, (int)c->opt[OPT_SPMM_SLAB], c->compute, bf16));
         return DORY_OK;
@@ -363,15 +365,17 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
 // `val` is the adjacency's own static array -- from the source-blocked copy (K1b), or are
 // 1 with a per-destination factor `row_scale` (K1b, unit mode; the reference GAT's edge
 // scores depend on the destination only, CPU_comm.cpp:299-319).
-// bf16 (option gcn_bf16_gather, GCN only): every row read -- self row, local and ghost rows -- is rounded to bf16 first;
-// edge values, norm, the sums and `out` stay fp32, the sums in the order of the fp32 path.  K1s and K1 have bf16 forms,
-// K1b has none: where fp32 would take K1b, bf16 takes K1.
+// bf16 (option gcn_bf16_gather; GAT prototype: dory_gat_bf16_gather): every row read -- self row, local and ghost rows -- is
+// rounded to bf16 first; edge values, norm, row_scale, the sums and `out` stay fp32, the sums in the order of the fp32 path.
+// K1s and K1 have bf16 forms, K1b has none: where fp32 would take K1b, bf16 takes K1.  row_scale on bf16 rows: the GAT
+// prototype's unit-weight forms of K1s only.  bf_out (optional): the aggregation's shadow rows, for a caller that reads the
+// rounded self rows once more (they stay until the next aggregation on bf16 rows).
 static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tensor &xl, Tensor *xg, Tensor &out,
-                uint32_t F, int accumulate, const float *row_scale = nullptr, bool bf16 = false) {
+                uint32_t F, int accumulate, const float *row_scale = nullptr, bool bf16 = false, Bf16Rows *bf_out = nullptr) {
     if (xl.ld != out.ld || (xg && xg->rows && xg->ld != xl.ld) || xl.cols != F)
         return fail(c, DORY_ERR_ARG, "spmm: tensor shapes disagree (F=%u ld %u/%u)", F, xl.ld, out.ld);
-    if (bf16 && (row_scale || xl.rows < c->N))
-        return fail(c, DORY_ERR_ARG, "spmm: bf16 rows need edge weights and N rows");
+    if (bf16 && ((row_scale && c->gnn != DORY_GAT) || xl.rows < c->N))
+        return fail(c, DORY_ERR_ARG, "spmm: bf16 rows need edge weights (but on a GAT context) and N rows");
     c->last_spmm_unit = false;
     SpmmArgs a{};
     a.N = c->N; a.F = F; a.ld = xl.ld;
@@ -383,7 +387,7 @@ static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tens
     a.xl = xl.d; a.xg = (xg && xg->rows) ? xg->d : nullptr; a.out = out.d;   // nullptr: no ghost rows (the blocked kernel then skips the select)
     Bf16Rows bf;
     if (bf16) {   // the kernels' xl / xg point at bf16 rows from here on
-        int rc = bf.begin(c, xl, xg, a.xg ? xg->rows : 0, "gcn_bf16_gather");
+        int rc = bf.begin(c, xl, xg, a.xg ? xg->rows : 0, c->gnn == DORY_GAT ? "dory_gat_bf16_gather" : "gcn_bf16_gather");
         if (rc) return rc;
         a.xl = bf.xl;
         a.xg = bf.xg;
@@ -397,6 +401,7 @@ static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tens
     if (layouts && c->opt[OPT_SPMM_VARIANT] == 2) rc = spmm_k1s(c, A, a, row_scale, bf);
     if (rc == SPMM_NOT_MINE && layouts && c->opt[OPT_SPMM_VARIANT] >= 1 && !bf16) rc = spmm_k1b(c, A, a, row_scale);
     if (rc == SPMM_NOT_MINE) rc = spmm_k1(c, A, a, bf);
+    if (bf_out) *bf_out = bf;
     return rc;
 }
 
@@ -726,6 +731,15 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     return DORY_OK;
 }
 
+// dory_gat_bf16_gather: the shadow rows of the largest aggregation of the model -- (N + ghosts) rows of the widest z / grad --
+// reserved at once (the setter, the first eager aggregation), so that an epoch recorded after one eager epoch finds nothing to grow
+int gat_bf16_reserve_all(dory_ctx *c) {
+    if (!c->prealloc || c->gnn != DORY_GAT || !c->gat_bf16_mode) return DORY_OK;
+    uint32_t maxld = 0;
+    for (uint32_t l = 0; l < c->L; ++l) maxld = std::max(maxld, pad_ld(c->dims[l + 1]));
+    return bf16_reserve(c, (uint64_t)c->N + std::max(c->adj[ADJ_IN].ghosts, c->adj[ADJ_OUT].ghosts), maxld, "dory_gat_bf16_gather");
+}
+
 // Engine::aggregateGAT (gat_ops.cpp:173-243), the reference's prototype: edge scores that depend on the destination only
 static int aggregate_gat(dory_ctx *c, uint32_t fl, int dir) {
     Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
@@ -742,6 +756,15 @@ static int aggregate_gat(dory_ctx *c, uint32_t fl, int dir) {
     // replaced z / fg_z / "A" / "dA" in between gets the general path).
     Tensor *nsum = find(c, fl, "nsum"), *ones = find(c, 0, "ones");
     const bool reuse = c->opt[OPT_GAT_REUSE_NSUM] && nsum && ones && fl < c->gat_nsum_valid.size() && z->ld == nsum->ld;
+    // opt-in dory_gat_bf16_gather (no reference counterpart): 1 = the aggregations that gather z / fg_z read them rounded to bf16
+    // (the forward's, and the backward's dA-weighted term, reused or recomputed), 2 = the backward's A^T grad gather of grad / bg_d
+    // too (spmm(): fp32 sums, same order).  K1b has no bf16 form: an explicit spmm_variant = 1 is refused
+    const int bfm = c->gat_bf16_mode;
+    if (bfm && c->opt[OPT_SPMM_VARIANT] == 1)
+        return fail(c, DORY_ERR_ARG, "aggregate: dory_gat_bf16_gather mode %d with spmm_variant = 1 (K1b has no bf16 form: spmm_variant 0 or 2)", bfm);
+    const bool bf_z = bfm >= 1, bf_grad = bfm >= 2;
+    // the shadow buffer cannot grow inside a recording: all of it at the first eager aggregation, for the widest layer
+    if (bfm && !c->capturing) { int rrc = gat_bf16_reserve_all(c); if (rrc) return rrc; }
     if (dir == DORY_FORWARD) {
         AGG_NEED(ah, fl, "ah");
         Tensor *arow = find(c, fl, "arow");
@@ -752,34 +775,41 @@ static int aggregate_gat(dory_ctx *c, uint32_t fl, int dir) {
                 HIPCK(c, hipMemsetD32Async((hipDeviceptr_t)ones->d, 0x3f800000, c->N, c->compute));
                 c->gat_ones_set = true;
             }
-            int rc = spmm(c, In, In.val, 0, *z, fgz, *nsum, F, 0, ones->d);
+            Bf16Rows bf;
+            int rc = spmm(c, In, In.val, 0, *z, fgz, *nsum, F, 0, ones->d, bf_z, &bf);
             if (rc) return rc;
             if (c->last_spmm_unit) {      // (K1 -- graphs without a blocked layout -- gathers with the per-edge values: not a unit sum)
                 Timed t(c, "spmm", c->compute);
-                HIPCK(c, launch_row_axpy(ah->d, nsum->d, arow->d, z->d, c->N, z->ld, c->compute));
+                // on bf16 rows the self row is the rounded one: the shadow buffer still holds z's rows, [0, N) x ld, as the launch(es)
+                // above gathered them (nothing between here and there writes it: the combine kernel only reads it)
+                if (bf.on()) HIPCK(c, launch_row_axpy_bf16(ah->d, nsum->d, arow->d, c->bf16_rows, c->N, z->ld, c->compute));
+                else HIPCK(c, launch_row_axpy(ah->d, nsum->d, arow->d, z->d, c->N, z->ld, c->compute));
                 c->gat_nsum_valid[fl] = 1;
+                c->gat_nsum_bf16[fl] = bf.on() ? 1 : 0;
                 return DORY_OK;
             }
+            // (the K1 launch above counted as an aggregation on bf16 rows already; the general path below is a second one)
         }
         { int mrc = gat_materialize(c, fl, 2); if (mrc) return mrc; }   // (K1 reads the per-edge values)
-        return spmm(c, In, In.val, 2, *z, fgz, *ah, F, 0, fast ? arow->d : nullptr);
+        return spmm(c, In, In.val, 2, *z, fgz, *ah, F, 0, fast ? arow->d : nullptr, bf_z);
     }
     AGG_NEED(grad, fl, "grad");
     AGG_NEED(bgd, fl, "bg_d");
     AGG_NEED(dA, fl, "dA");
     AGG_NEED(aTg, fl, "aTg");
     // fresh two-term sum (the CUDA path's semantics, gat_ops.cpp:155-163): A^T.dP then += dA.Z
-    int rc = spmm(c, Out, Out.val, 0, *grad, bgd, *aTg, F, 0);
+    int rc = spmm(c, Out, Out.val, 0, *grad, bgd, *aTg, F, 0, nullptr, bf_grad);
     if (rc) return rc;
     Tensor *drow = find(c, fl, "drow");
     const bool fast = drow && fl < c->gat_drow_valid.size() && c->gat_drow_valid[fl];
-    if (fast && reuse && c->gat_nsum_valid[fl]) {
+    // the kept neighbour sum serves only the rounding the mode asks for now (a mode switched between forward and backward: recompute)
+    if (fast && reuse && c->gat_nsum_valid[fl] && (c->gat_nsum_bf16[fl] != 0) == bf_z) {
         Timed t(c, "spmm", c->compute);
         HIPCK(c, launch_row_axpy(aTg->d, nsum->d, drow->d, nullptr, c->N, aTg->ld, c->compute));
         return DORY_OK;
     }
     { int mrc = gat_materialize(c, fl, 4); if (mrc) return mrc; }
-    return spmm(c, In, dA->d, 0, *z, fgz, *aTg, F, 1, fast ? drow->d : nullptr);
+    return spmm(c, In, dA->d, 0, *z, fgz, *aTg, F, 1, fast ? drow->d : nullptr, bf_z);
 }
 
 #undef AGG_NEED

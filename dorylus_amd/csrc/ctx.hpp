@@ -252,6 +252,7 @@ struct dory_ctx {
     std::vector<char> gat_az_stale, gat_dA_stale;   // per layer: az@l / dA@l are behind azrow@l / drow@l
     int gat_A_stale_layer = -1;                     // "A" (= forwardAdj.values) is behind arow@this layer
     std::vector<char> gat_nsum_valid;    // GAT prototype: "nsum"@l holds the unweighted neighbour sum of the current z / fg_z (forward -> backward)
+    std::vector<char> gat_nsum_bf16;     // ... summed over rows rounded to bf16 (dory_gat_bf16_gather was on when the forward made it)
     bool gat_ones_set = false;           // "ones"@0 filled
     bool last_spmm_unit = false;         // the last spmm() gathered with unit weights and a per-row factor (K1s / K1b), not with per-edge values (K1)
     std::vector<char> gatmh_fwd_swept;   // multi-head GAT: the forward of this layer ran on the sweep skeleton ("op", "dpos" are current)
@@ -267,6 +268,11 @@ struct dory_ctx {
     uint16_t *bf16_rows = nullptr;
     size_t bf16_rows_bytes = 0;
     uint64_t bf16_gathers_k1s = 0, bf16_gathers_k1 = 0, bf16_gathers_k1s_wide = 0;   // (_wide: those of _k1s that ran the wide form, option gcn_bf16_wide)
+    // dory_gat_bf16_gather (GAT prototype): mode 0 / 1 / 2, the wide form of K1s, and the aggregations that ran on bf16 rows per
+    // kernel family (_wide: those of _k1s that ran the wide form; fallbacks: requested on bf16 rows, run on fp32 rows)
+    int gat_bf16_mode = 0;
+    bool gat_bf16_wide = false;
+    uint64_t gat_bf16_gathers_k1s = 0, gat_bf16_gathers_k1s_wide = 0, gat_bf16_gathers_k1 = 0, gat_bf16_fp32_fallbacks = 0;
     uint64_t spmm_launches_k1s = 0, spmm_launches_k1b = 0, spmm_launches_k1 = 0;   // aggregations per kernel family (read-only options of the same names)
     uint64_t gatmh_bf16_gathers_fwd = 0, gatmh_bf16_gathers_src = 0;   // multi-head GAT: forward edge passes, source-side passes
     uint64_t gatmh_bf16_gathers_fwd_wide = 0, gatmh_bf16_gathers_src_wide = 0;   // (those of them that ran the wide form, option gatmh_bf16_wide)
@@ -436,7 +442,8 @@ struct SweepPart {
 // K1s's wide form (spmm_sweep_bf16x8_kernel): rows of 128 floats or more, 16-lane groups on 128-feature slabs whatever `group`,
 // R16 = sweep_rows(.., 16, ..) rows
 inline bool sweep_wide_applies(uint32_t ld, int group, int R16) { return ld >= 128 && (group == 16 || group == 32) && sweep_wide_rows_ok(R16); }
-// out (+)= self + (row_scale *) sum over the source blocks of p; bf16 rows take no row_scale; split_partial: B.nslots x ld floats
+// out (+)= self + (row_scale *) sum over the source blocks of p (row_scale: unit edge weights; on bf16 rows the GAT prototype's
+// forms, dory_gat_bf16_gather); split_partial: B.nslots x ld floats
 hipError_t launch_spmm_sweep(SpmmArgs a, const BlockedAdj &B, int group, const float *row_scale, float *split_partial, const SweepPart &p);
 hipError_t launch_spmm_sweep_combine(const SpmmArgs &a, const BlockedAdj &B, const float *row_scale, const float *split_partial,
                                      hipStream_t s, bool bf16 = false);
@@ -522,6 +529,8 @@ hipError_t launch_pad_copy(float *dst, uint32_t ldd, const float *src, uint32_t 
                            uint32_t cols, hipStream_t s);
 hipError_t launch_row_axpy(float *out, const float *S, const float *rs, const float *x /* nullptr: out += rs * S */, uint64_t rows, uint32_t ld,
                            hipStream_t s);
+// out = xb + rs * S with xb read from bf16 rows of ld elements (launch_bf16_rows; dory_gat_bf16_gather)
+hipError_t launch_row_axpy_bf16(float *out, const float *S, const float *rs, const uint16_t *xb, uint64_t rows, uint32_t ld, hipStream_t s);
 
 // K5 GAT edge kernels
 hipError_t launch_edge_forward_gat(uint32_t N, uint32_t F, const uint64_t *colptr, const float *z,

@@ -336,6 +336,29 @@ hipError_t launch_row_axpy(float *out, const float *S, const float *rs, const fl
     return hipGetLastError();
 }
 
+// out[v,:] = xb[v,:] + rs[v] * S[v,:] with the self row xb read from bf16 rows (dory_gat_bf16_gather: the shadow rows the
+// neighbour sum S was gathered from, 8 bytes per four features): row_axpy_kernel's fmaf per element on the expanded values
+__global__ __launch_bounds__(256) void row_axpy_bf16_kernel(float *out, const float *S, const float *rs, const uint2 *xb, uint32_t ld4, uint64_t n4) {
+    float4 *o4 = reinterpret_cast<float4 *>(out);
+    const float4 *s4 = reinterpret_cast<const float4 *>(S);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * blockDim.x) {
+        const float r = rs[i / ld4];
+        const uint2 xr = xb[i];
+        const float4 sv = s4[i];
+        const float4 b = make_float4(__uint_as_float(xr.x << 16), __uint_as_float(xr.x & 0xFFFF0000u), __uint_as_float(xr.y << 16),
+                                     __uint_as_float(xr.y & 0xFFFF0000u));
+        o4[i] = make_float4(fmaf(r, sv.x, b.x), fmaf(r, sv.y, b.y), fmaf(r, sv.z, b.z), fmaf(r, sv.w, b.w));
+    }
+}
+hipError_t launch_row_axpy_bf16(float *out, const float *S, const float *rs, const uint16_t *xb, uint64_t rows, uint32_t ld, hipStream_t s) {
+    if (rows == 0 || ld == 0) return hipSuccess;
+    if ((ld & 3) || !xb) return hipErrorInvalidValue;
+    const uint64_t n4 = rows * (ld >> 2);
+    hipLaunchKernelGGL(row_axpy_bf16_kernel, dim3((uint32_t)std::min<uint64_t>(8192, (n4 + 255) / 256)), dim3(256), 0, s, out, S, rs,
+                       reinterpret_cast<const uint2 *>(xb), ld >> 2, n4);
+    return hipGetLastError();
+}
+
 // option gcn_bf16_gather: the rows an aggregation reads, rounded to bf16 (nearest even; v_cvt_pk_bf16_f32), into the
 // context's shadow buffer -- every element of an ld-wide row, so that padding columns stay 0
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {

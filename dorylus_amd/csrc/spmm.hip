@@ -349,7 +349,13 @@ struct SweepPlainOp {
     }
     template <bool FULL>
     __device__ __forceinline__ void entry(Row &r, const RowC &, const Float4x2 &x, uint32_t vbits, bool on) const {
-        static_assert(WIDE && !UNIT, "eight features per entry: the wide form, edge weights");
+        static_assert(WIDE, "eight features per entry: the wide form");
+        if constexpr (UNIT) {   // spmm_sweep_bf16x8_unit_kernel: weight 1, the narrow unit form's products
+            const float wv = FULL ? 1.f : (on ? 1.f : 0.f);
+            r.acc = fma4(wv, x.lo, r.acc);
+            r.acc2 = fma4(wv, x.hi, r.acc2);
+            return;
+        }
         const float wv = FULL ? __uint_as_float(vbits) : (on ? __uint_as_float(vbits) : 0.f);
         r.acc = fma4(wv, x.lo, r.acc);
         if constexpr (WIDE) r.acc2 = fma4(wv, x.hi, r.acc2);
@@ -369,8 +375,15 @@ struct SweepPlainOp {
                 xs0 = bf16x4_to_float4(s8.x, s8.y);
                 xs1 = bf16x4_to_float4(s8.z, s8.w);
             }
-            // (no row factor: bf16 rows have edge weights -- launch_spmm_sweep refuses row_scale)
-            float4 o0 = fma4(sc, xs0, r.acc), o1 = fma4(sc, xs1, r.acc2);
+            float4 o0, o1;
+            if constexpr (UNIT) {   // the row factor first, as the narrow store: r.acc * rs, then the self term -- same bits
+                const float rs = (row_scale && !piece) ? row_scale[v] : 1.f;
+                o0 = fma4(sc, xs0, make_float4(r.acc.x * rs, r.acc.y * rs, r.acc.z * rs, r.acc.w * rs));
+                o1 = fma4(sc, xs1, make_float4(r.acc2.x * rs, r.acc2.y * rs, r.acc2.z * rs, r.acc2.w * rs));
+            } else {   // (no row factor: the weighted wide form is launched without one)
+                o0 = fma4(sc, xs0, r.acc);
+                o1 = fma4(sc, xs1, r.acc2);
+            }
             if (piece ? (w.flags & 2u) != 0 : a.accumulate != 0) {
                 const float4 p0 = q[0], p1 = q[1];
                 o0.x += p0.x; o0.y += p0.y; o0.z += p0.z; o0.w += p0.w;
@@ -414,6 +427,17 @@ __global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16_kernel(SpmmArgs a, B
     SweepPlainOp<UNIT, true> op{row_scale};
     sweep_run<GROUP, R, PAIR, LOADER>(a, B, w, op);
 }
+// ... with unit weights and a per-row factor (dory_gat_bf16_gather, GAT prototype: the neighbour sum of z, ah = z + arow (.) sum):
+// a kernel name of its own beside the weighted form's, every (GROUP, R) of k1s_narrow_form.  Rows in pairs without the loader
+// wave at the largest row count of either group: four gathers per batch spill 8 / 4 registers, three fit (the entries are summed
+// in the same order whatever the batch; tests/test_gat_bf16_resources.py)
+template <int GROUP, int R, bool PAIR, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16_unit_kernel(SpmmArgs a, BlockedAdj B, const float *row_scale,
+                                                                        SweepArgs w) {
+    constexpr bool TIGHT = PAIR && !LOADER && ((GROUP == 16 && R == 8) || (GROUP == 32 && R == 10));
+    SweepPlainOp<true, true, false, TIGHT ? 3 : K1S_BATCH> op{row_scale};
+    sweep_run<GROUP, R, PAIR, LOADER>(a, B, w, op);
+}
 
 // the same sweep over bf16 rows with eight features per lane (option gcn_bf16_wide; rows of 128 floats or more): 16-lane
 // groups on the layout dealt for 32-lane groups, R = the 16-lane row count of that layout (2 .. 5; with 5 on the ten-row
@@ -426,6 +450,18 @@ __global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16_kernel(SpmmArgs a, B
 template <int R, bool LOADER>
 __global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16x8_kernel(SpmmArgs a, BlockedAdj B, SweepArgs w) {
     SweepPlainOp<false, true, true, (R == 5 && !LOADER) ? 3 : K1S_BATCH> op{nullptr};
+    sweep_run<16, R, false, LOADER>(a, B, w, op);
+}
+
+// ... and with unit weights and a per-row factor (dory_gat_bf16_gather, GAT prototype: the neighbour sum of z): the weighted form's
+// rows, loader settings and slots; no weight bits travel from the entries to the sums, so four gathers per batch fit every row count
+// (tests/test_gat_bf16_resources.py).  The store scales both accumulators by row_scale[v] before the self term, as the narrow store.
+#ifndef K1S_WIDE_UNIT_BATCH5
+#define K1S_WIDE_UNIT_BATCH5 K1S_BATCH   // gathers per batch of the five-row form without the loader wave
+#endif
+template <int R, bool LOADER>
+__global__ __launch_bounds__(SWEEP_NT) void spmm_sweep_bf16x8_unit_kernel(SpmmArgs a, BlockedAdj B, const float *row_scale, SweepArgs w) {
+    SweepPlainOp<true, true, true, (R == 5 && !LOADER) ? K1S_WIDE_UNIT_BATCH5 : K1S_BATCH> op{row_scale};
     sweep_run<16, R, false, LOADER>(a, B, w, op);
 }
 
@@ -689,7 +725,6 @@ static bool k1s_narrow_form(int group, int R, F f) {
 // one launch over the source blocks of p; a second launch (p.accumulate) adds to the first one's sums: no self term again
 hipError_t launch_spmm_sweep(SpmmArgs a, const BlockedAdj &B, int group, const float *row_scale, float *split_partial, const SweepPart &p) {
     if (a.N == 0 || a.ld == 0 || p.b_lo >= p.b_hi) return hipSuccess;
-    if (p.bf16 && row_scale) return hipErrorInvalidValue;   // bf16 rows: the GCN aggregations (edge weights) only
     if (p.wide && (!p.bf16 || (a.ld & 7) || !sweep_wide_applies(a.ld, group, p.R))) return hipErrorInvalidValue;
     if (B.nslots && !split_partial) return hipErrorInvalidValue;
     if (p.accumulate) { a.self_mode = 0; a.accumulate = 1; }
@@ -702,17 +737,19 @@ hipError_t launch_spmm_sweep(SpmmArgs a, const BlockedAdj &B, int group, const f
     // 13.3 ms; four: 11.0 -> 10.8; three: 8.16 -> 8.1), not on one or two (F=128: 2.70 -> 2.78; F=256: 5.43 -> 5.46);
     // ctl.pair (option spmm_sweep_pair): -1 = that rule, 0 / 1 = forced (experiments)
     const bool pair = (p.R & 1) ? false : (p.ctl.pair < 0 ? pl.slabs >= 3 : p.ctl.pair != 0);   // (odd R: 16-lane launches on a 6- or 10-row layout)
-    // wide: one form per row count (2 .. 5) and loader setting, weighted, rows never in pairs.  Narrow: each (GROUP, R) with and
-    // without the loader wave and rows in pairs, on fp32 rows with and without the row factor
+    // wide: one form per row count (2 .. 5) and loader setting, weighted or unit with the row factor, rows never in pairs.  Narrow:
+    // each (GROUP, R) with and without the loader wave and rows in pairs, on fp32 and on bf16 rows with and without the row factor
     const bool found = p.wide ? sweep_pick<2, 3, 4, 5>(p.R, [&](auto R) {
         return sweep_pick<0, 1>(p.ctl.loader, [&](auto L) {
-            hipLaunchKernelGGL((spmm_sweep_bf16x8_kernel<R(), L() != 0>), pl.grid, bl, 0, p.s, a, B, pl.w);
+            if (unit) hipLaunchKernelGGL((spmm_sweep_bf16x8_unit_kernel<R(), L() != 0>), pl.grid, bl, 0, p.s, a, B, row_scale, pl.w);
+            else hipLaunchKernelGGL((spmm_sweep_bf16x8_kernel<R(), L() != 0>), pl.grid, bl, 0, p.s, a, B, pl.w);
             return true;
         });
     }) : k1s_narrow_form(group, p.R, [&](auto G, auto R) {
         return sweep_pick<0, 1>(p.ctl.loader, [&](auto L) {
             return sweep_pick<0, 1>(pair, [&](auto P) {
-                hipLaunchKernelGGL((p.bf16 ? spmm_sweep_bf16_kernel<G(), R(), false, P() != 0, L() != 0>
+                hipLaunchKernelGGL((p.bf16 ? (unit ? spmm_sweep_bf16_unit_kernel<G(), R(), P() != 0, L() != 0>
+                                                   : spmm_sweep_bf16_kernel<G(), R(), false, P() != 0, L() != 0>)
                                     : unit ? spmm_sweep_kernel<G(), R(), true, P() != 0, L() != 0>
                                            : spmm_sweep_kernel<G(), R(), false, P() != 0, L() != 0>), pl.grid, bl, 0, p.s, a, B, row_scale, pl.w);
                 return true;

@@ -243,6 +243,31 @@ int dory_halo_unpack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int
 int dory_halo_fused_pack(dory_ctx *ctx, int on);
 int dory_halo_fused_pack_stats(dory_ctx *ctx, uint64_t *fused_exchanges, uint64_t *fused_rows, uint64_t *fallback_exchanges);
 
+/* ---- bf16 row gathers of the GAT prototype's aggregations (opt-in, default off; nothing in the reference) ----
+ * GAT prototype (DORY_GAT) only.  mode 0 = off (default), 1 = the aggregations that gather z / fg_z read them rounded to bf16
+ * (the forward's, and the backward's dA-weighted term, reused or recomputed), 2 = also the backward's A^T grad gather of
+ * grad / bg_d.  wide = 1: K1s gathers bf16 rows of 128 floats or more eight features per lane (16-byte gathers), same bits.
+ * One rule, that of gcn_bf16_gather: with the mode on every row such an aggregation reads -- local rows, ghost rows (rounded
+ * after their exchange has landed) and the self row -- is rounded to bf16, round to nearest even, into a shadow buffer of
+ * (N + ghosts) x the widest layer's ld x 2 bytes (reserved by this call after dory_preallocate, else by the first eager
+ * aggregation; it cannot grow while an epoch graph is recorded).  Edge values, arow / drow, the sums and the outputs stay fp32 and
+ * the sums are added in the fp32 path's order: ah and aTg are, bit for bit, what the same context gives with mode 0 on z / fg_z
+ * (mode 2: and grad / bg_d) already rounded to bf16 -- for either setting of gat_reuse_nsum, each against its own fp32
+ * counterpart.  The neighbour sum kept from the forward ("nsum") is reused by the backward only if it was summed under the
+ * rounding the mode asks for then; otherwise the dA term is gathered again.  K1s and K1 have the bf16 forms, K1b has none: where
+ * fp32 would take K1b the aggregation takes K1, and spmm_variant = 1 with mode != 0 is refused by dory_aggregate.  No requested
+ * aggregation runs on fp32 rows unannounced (fp32_fallbacks counts any that would; there is no such path today).
+ * Refused with DORY_ERR_ARG: a context configured as another model (here, and by dory_configure when the mode was set first),
+ * mode outside 0..2, wide outside 0..1, wide without mode, a call while an epoch graph is being recorded.  Changing mode or wide
+ * drops a recorded epoch.
+ * dory_gat_bf16_gather_stats: aggregations that ran on bf16 rows since dory_create, per kernel family (k1s_wide: those of k1s
+ * that took the wide form); any pointer may be NULL.
+ * Measured on one MI355X (profiles/r18_gat_bf16_gather.txt, profiles/HISTORY.md section 19), Reddit-size uniform graph, dims
+ * 602-128-41: epoch 9.78 ms off, 9.57 ms mode 2, 8.68 ms mode 2 with wide; the four conversions cost 0.09 ms of it.  The
+ * per-aggregation table there says which launch gains what; a form that is not faster at a shape is named there. */
+int dory_gat_bf16_gather(dory_ctx *ctx, int mode, int wide);
+int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide, uint64_t *k1, uint64_t *fp32_fallbacks);
+
 /* ---- scatter messages: the reference's own graph-server <-> graph-server wire, packed and unpacked on the device ----------
  * What Engine::verticesPushOut puts on a socket and ghostReceiver* takes apart (include/dorylus_wire.h: the format table with
  * its citations): messages of an 8-character receiver topic, five unsigned header fields and (global vertex id, featDim floats)
