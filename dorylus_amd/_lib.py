@@ -30,6 +30,7 @@ SYMBOLS = [
     "dory_comm_set_scatter_transport",
     "dory_halo_fused_pack", "dory_halo_fused_pack_stats",
     "dory_gat_bf16_gather", "dory_gat_bf16_gather_stats",
+    "dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -122,6 +123,9 @@ def load():
         "dory_halo_fused_pack_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
         "dory_gat_bf16_gather": [vp, i32, i32],
         "dory_gat_bf16_gather_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
+        "dory_halo_bf16_rows": [vp, i32],
+        "dory_halo_bf16_rows_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
+        "dory_halo_wire_row": [vp, u32, i32, C.POINTER(u32), C.POINTER(u32)],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -154,8 +158,9 @@ def load():
     for name, args in sig.items():
         if (name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check", "dory_halo_wire_ids",
                      "dory_comm_set_scatter_transport", "dory_halo_send_map") or name.startswith("dory_scatter_msgs_")
-                or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers)
+                or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
+                or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -524,6 +529,22 @@ class Context:
         v = [C.c_uint64(0) for _ in range(4)]
         self._ck(self.lib.dory_gat_bf16_gather_stats(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("k1s", "k1s_wide", "k1", "fp32_fallbacks"), (int(x.value) for x in v)))
+
+    def halo_bf16_rows(self, on=True):
+        """exchanges whose consumer gathers bf16 rows ship bf16 rows (opt-in; dory_halo_bf16_rows): half the bytes, the same bits"""
+        self._ck(self.lib.dory_halo_bf16_rows(self.h, int(on)))
+
+    def halo_bf16_rows_stats(self):
+        """(packs that wrote bf16 rows, their bytes, packs that wrote fp32 rows while the switch was on)"""
+        a, b, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.dory_halo_bf16_rows_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
+        return a.value, b.value, f.value
+
+    def halo_wire_row(self, layer, direction):
+        """(bytes per element, elements per row) of what halo_exchange / halo_pack of (layer, direction) put on the wire now"""
+        e, n = C.c_uint32(), C.c_uint32()
+        self._ck(self.lib.dory_halo_wire_row(self.h, layer, direction, C.byref(e), C.byref(n)))
+        return e.value, n.value
 
     def halo_fused_pack_stats(self):
         """(exchanges that skipped their pack kernel, the send rows of those, exchanges that packed although the feature was on)"""

@@ -55,27 +55,45 @@ const char *const NO_RECV_BUF = "halo_direct_recv: this exchange needs the recei
 // The padded row width travels (keeps 16-B lanes), or, with option halo_exact_rows, exactly the tensor's columns -- then
 // both ends must have the same, and a caller's buffer of rows whose width is no multiple of 4 is addressed in 16-byte quads
 // of the whole stream.
+// dory_halo_bf16_rows: `rule_dir` is the direction of the exchange whose rule decides the element (wire_bf16, below), or -1 for rows
+// whose consumer is unknown (the *_tensor entry points: fp32).  bf16 rows hold the width rounded up to a multiple of 4 elements
+// (zeros behind the tensor's cols): multiples of 8 bytes, in a buffer aligned to 8.
 inline uint32_t wire_width(const dory_ctx *c, const Tensor *rows) { return halo_exact(c) ? rows->cols : rows->ld; }
-int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghost, bool pack, const void *buf, RowWire *out) {
+bool wire_bf16(const dory_ctx *c, int dir);
+int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghost, bool pack, const void *buf, int rule_dir, RowWire *out) {
     const Tensor *rows = pack ? src : ghost;
     out->exact = halo_exact(c);
     if (out->exact && src && ghost && src->cols != ghost->cols)
         return fail(c, DORY_ERR_ARG, "%s: widths of source (%u) and ghost tensor (%u) differ", who, src->cols, ghost->cols);
     out->w = wire_width(c, rows);
+    out->bf16 = rule_dir >= 0 && wire_bf16(c, rule_dir);
+    if (out->bf16) {
+        out->cols = rows->cols;
+        out->w = (out->w + 3u) & ~3u;
+        if ((uintptr_t)buf & 7) return fail(c, DORY_ERR_ARG, "%s: dory_halo_bf16_rows needs an 8-byte aligned buffer", who);
+        return DORY_OK;
+    }
     if (out->exact && (out->w & 3) && ((uintptr_t)buf & 15))
         return fail(c, DORY_ERR_ARG, "%s: halo_exact_rows with rows of %u floats needs a 16-byte aligned buffer", who, out->w);
     return DORY_OK;
 }
 
+// dory_halo_bf16_rows: an eager exchange or pack that ships fp32 rows while the switch is on (section "not taken" of dorylus_hip.h)
+inline void fp32_while_on(dory_ctx *c) {
+    if (!c->capturing && c->halo_bf16.load(std::memory_order_acquire) == 1) c->halo_fp32_packs_while_on++;
+}
 // the plan's send rows of `src`, dense at the wire's width, into dst; counted (eager calls)
 int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const HaloPlan &p, hipStream_t s) {
     if (dst == c->send_buf) fused_stamp_drop(c);   // (the fused halo pack: whatever a GEMM left in the internal buffer is overwritten)
-    if (wire.exact && (wire.w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
+    if (wire.bf16) HIPCK(c, launch_gather_rows_bf16(dst, src->d, src->ld, wire.cols, wire.w, p.d_send_lvids, p.send_total, s));
+    else if (wire.exact && (wire.w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
     else HIPCK(c, launch_gather_rows(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
     if (!c->capturing) {
         c->halo_rows_packed += p.send_total;
-        c->halo_floats_packed += (uint64_t)p.send_total * wire.w;
-        if (wire.exact && wire.w < src->ld) c->halo_exact_packs++;
+        c->halo_floats_packed += (uint64_t)p.send_total * (wire.row_bytes() / sizeof(float));   // (bf16 rows: 4-byte units, w / 2 a row)
+        if (wire.exact && (wire.bf16 ? wire.cols : wire.w) < src->ld) c->halo_exact_packs++;
+        if (wire.bf16) { c->halo_bf16_packs++; c->halo_bf16_bytes += (uint64_t)p.send_total * wire.row_bytes(); }
+        else fp32_while_on(c);
     }
     return DORY_OK;
 }
@@ -86,9 +104,10 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
 int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloPlan &p, hipStream_t s, bool may_fuse) {
     if (c->fused_pack) {
         const FusedStamp &st = c->fused_stamp;
-        if (may_fuse && st.src == src && st.dir == dir && st.w == wire.w && st.buf == c->send_buf) {
+        if (may_fuse && !wire.bf16 && st.src == src && st.dir == dir && st.w == wire.w && st.buf == c->send_buf) {   // (a stamp holds fp32 rows)
             fused_stamp_drop(c);
             if (!c->capturing) { c->fused_exchanges++; c->fused_rows += p.send_total; }
+            fp32_while_on(c);
             return DORY_OK;
         }
         if (!c->capturing) c->fallback_exchanges++;
@@ -99,7 +118,9 @@ int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloP
 // the exact form writes the whole row: [0, w) from the buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever
 // the padding held before
 int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s) {
-    if (wire.exact && (wire.w & 3)) {
+    if (wire.bf16) {   // (the whole ld-wide row: widened values, zeros behind them)
+        HIPCK(c, launch_scatter_rows_bf16(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
+    } else if (wire.exact && (wire.w & 3)) {
         HIPCK(c, launch_scatter_rows_exact(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
     } else {
         HIPCK(c, launch_scatter_rows(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
@@ -110,9 +131,9 @@ int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const floa
 
 // the four split entry points (foreign transports, multi-context tests) after their own checks: pack the plan's send rows of
 // `src` into the caller's buffer, or unpack it into `ghost`; the other tensor is the one halo_tensors resolved, or null
-int split_rows(dory_ctx *c, const char *who, bool pack, int dir, const Tensor *src, Tensor *ghost, float *buf) {
+int split_rows(dory_ctx *c, const char *who, bool pack, int dir, const Tensor *src, Tensor *ghost, float *buf, bool follows_rule) {
     RowWire wire;
-    int rc = row_wire(c, who, src, ghost, pack, buf, &wire);
+    int rc = row_wire(c, who, src, ghost, pack, buf, follows_rule ? dir : -1, &wire);
     if (rc) return rc;
     Timed t(c, "halo", c->compute);
     return pack ? pack_rows(c, buf, src, wire, c->plan[dir], c->compute)
@@ -139,6 +160,21 @@ bool halo_route(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **gho
         else { *src = find(c, layer - 1, "grad"); *ghost = find(c, layer - 1, "bg_d"); }
     }
     return true;
+}
+// dory_halo_bf16_rows, the rule: with the switch on, an exchange ships bf16 rows iff the aggregation that reads its ghost tensor gathers
+// bf16 rows under the settings of this moment -- GCN (fg / fgxw forward, bg / bgg backward): option gcn_bf16_gather >= 1 forward, == 2
+// backward; GAT prototype (fg_z, bg_d): dory_gat_bf16_gather's mode likewise; the multi-head GAT never (its finishing kernels and
+// blocked forms read fg_z in fp32, and it exchanges do / st itself).  The same for every layer of a model.  Reads atomics only: the peers
+// of the local transport ask it of each other.
+bool halo_ships_bf16(const dory_ctx *c, int dir) {
+    if (c->halo_bf16.load(std::memory_order_acquire) != 1 || c->gnn == DORY_GATMH) return false;
+    const int mode = (c->gnn == DORY_GCN ? c->gcn_bf16_mode : c->gat_bf16_mode_pub).load(std::memory_order_acquire);
+    return mode >= (dir == DORY_FORWARD ? 1 : 2);
+}
+// ... and what keeps fp32 although the rule says yes: the scatter-message transport (the reference's format), and a plan made with
+// halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer)
+bool wire_bf16(const dory_ctx *c, int dir) {
+    return halo_ships_bf16(c, dir) && !c->plan[dir].direct && transport_of(c) != Transport::Scatter;
 }
 int halo_tensors(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **ghost) {
     if (!halo_route(c, layer, dir, src, ghost)) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
@@ -487,7 +523,7 @@ int local_pull_send(dory_ctx *c, int dir, const HaloPlan &p, Tensor *src, RowWir
 int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wire, bool deferred) {
     HaloPlan &p = c->plan[dir];
     LocalGroup &grp = *c->local;
-    const uint32_t w = wire.w;
+    const size_t rb = wire.row_bytes();
     if (c->local_pending.on) {   // (not reached: every consumer and every exchange calls wait_halo first)
         int rc = local_exchange_finish(c);
         if (rc) return rc;
@@ -506,15 +542,15 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
         if (!pq.set || pq.recv_counts.size() != c->numNodes || pq.recv_counts[c->nodeId] != p.send_counts[q])
             return fail(c, DORY_ERR_COMM, "local transport: rank %u expects %u rows from rank %u, which sends %u", q,
                         pq.set && pq.recv_counts.size() == c->numNodes ? pq.recv_counts[c->nodeId] : 0u, c->nodeId, p.send_counts[q]);
-        if ((size_t)pq.recv_total * w * sizeof(float) > Q->recv_cap)
-            return fail(c, DORY_ERR_COMM, "local transport: receive buffer of rank %u too small for %u-float rows", q, w);
+        if ((size_t)pq.recv_total * rb > Q->recv_cap)
+            return fail(c, DORY_ERR_COMM, "local transport: receive buffer of rank %u too small for rows of %zu bytes", q, rb);
         if (s > 1) {   // its receive buffer must have been unpacked (exchange s - 1)
             int rc = local_wait_posted(c, Q->posted_cons, s - 1, q, "the unpack of exchange");
             if (rc) return rc;
             HIPCK(c, hipStreamWaitEvent(c->comm, Q->ev_cons[(s - 1) & 1], 0));
         }
-        HIPCK(c, hipMemcpyAsync(Q->recv_buf + (size_t)pq.recv_off[c->nodeId] * w, c->send_buf + (size_t)p.send_off[q] * w,
-                                (size_t)p.send_counts[q] * w * sizeof(float), hipMemcpyDeviceToDevice, c->comm));
+        HIPCK(c, hipMemcpyAsync((char *)Q->recv_buf + (size_t)pq.recv_off[c->nodeId] * rb, (const char *)c->send_buf + (size_t)p.send_off[q] * rb,
+                                (size_t)p.send_counts[q] * rb, hipMemcpyDeviceToDevice, c->comm));
     }
     HIPCK(c, hipEventRecord(c->ev_sent[s & 1], c->comm));
     c->posted_sent.store(s, std::memory_order_release);
@@ -536,6 +572,7 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
 
 // ---- the other two arms: the packed rows in c->send_buf travel, the peers' rows arrive in `recv` (comm stream) ----------
 // host transport: the bytes travel through the caller (c->tx_recv is still being read when this returns)
+// (w: the floats of a row on the wire, RowWire::row_bytes() / 4 -- bf16 rows travel as w / 2 floats' worth of bytes)
 int exchange_host(dory_ctx *c, const HaloPlan &p, uint32_t w, float *recv /* c->recv_buf, or the ghost tensor (halo_direct_recv) */) {
     const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = (size_t)p.recv_total * w * sizeof(float);
     c->tx_send.resize((size_t)p.send_total * w);
@@ -674,8 +711,8 @@ int local_exchange_finish(dory_ctx *c) {
     lp.on = false;     // (a peer that has not arrived leaves the second half pending: the caller may try again)
     if (p.direct) {   // option halo_direct_recv: I pull every peer's segment out of its send buffer -- into the ghost tensor (the
         // wire's width is its ld), or into my receive buffer for the unpack (exact rows narrower than ld)
-        const uint32_t w = lp.wire.w;
-        float *dst = lp.direct ? lp.ghost : c->recv_buf;
+        const size_t rb = lp.wire.row_bytes();
+        char *dst = reinterpret_cast<char *>(lp.direct ? lp.ghost : c->recv_buf);
         for (uint32_t q = 0; q < c->numNodes; ++q) {
             if (q == c->nodeId || !p.recv_counts[q]) continue;
             const dory_ctx *Q = grp.ctx[q];
@@ -683,10 +720,10 @@ int local_exchange_finish(dory_ctx *c) {
             if (!pq.set || pq.send_counts.size() != c->numNodes || pq.send_counts[c->nodeId] != p.recv_counts[q])
                 return fail(c, DORY_ERR_COMM, "local transport: rank %u expects %u rows from rank %u, which sends %u", c->nodeId, p.recv_counts[q], q,
                             pq.set && pq.send_counts.size() == c->numNodes ? pq.send_counts[c->nodeId] : 0u);
-            if ((size_t)pq.send_total * w * sizeof(float) > Q->send_cap)
-                return fail(c, DORY_ERR_COMM, "local transport: send buffer of rank %u too small for %u-float rows", q, w);
-            HIPCK(c, hipMemcpyAsync(dst + (size_t)p.recv_off[q] * w, Q->send_buf + (size_t)pq.send_off[c->nodeId] * w,
-                                    (size_t)p.recv_counts[q] * w * sizeof(float), hipMemcpyDeviceToDevice, c->comm));
+            if ((size_t)pq.send_total * rb > Q->send_cap)
+                return fail(c, DORY_ERR_COMM, "local transport: send buffer of rank %u too small for rows of %zu bytes", q, rb);
+            HIPCK(c, hipMemcpyAsync(dst + (size_t)p.recv_off[q] * rb, (const char *)Q->send_buf + (size_t)pq.send_off[c->nodeId] * rb,
+                                    (size_t)p.recv_counts[q] * rb, hipMemcpyDeviceToDevice, c->comm));
         }
     }
     if (!lp.direct) { int rc = unpack_rows(c, lp.ghost, lp.ghost_ld, lp.wire, c->recv_buf, p, c->comm); if (rc) return rc; }
@@ -728,6 +765,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
         HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
         const bool deferred = defer && c->opt[OPT_HALO_OVERLAP];
         if (c->fused_pack && !c->capturing) c->fallback_exchanges++;   // (messages have another layout: never fused)
+        fp32_while_on(c);   // (... and carry fp32)
         {
             Timed t(c, "halo", c->comm);
             Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);
@@ -740,8 +778,9 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
         return DORY_OK;
     }
     RowWire wire;
-    { int rc = row_wire(c, "halo_exchange", src, ghost, true, nullptr, &wire); if (rc) return rc; }
+    { int rc = row_wire(c, "halo_exchange", src, ghost, true, nullptr, dir, &wire); if (rc) return rc; }
     const uint32_t w = wire.w;
+    const size_t row_b = wire.row_bytes();
     if (tr == Transport::Local) {   // every rank packs and unpacks at one width: checked here, before anything of this exchange is enqueued or counted
         for (uint32_t q = 0; q < c->numNodes; ++q) {
             dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
@@ -751,13 +790,16 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
             if (Q && halo_direct(Q) != p.direct)   // (who pushes and who pulls)
                 return fail(c, DORY_ERR_COMM, "local transport: option halo_direct_recv differs: rank %u has %d, rank %u has %d (all ranks must agree)",
                             c->nodeId, (int)p.direct, q, (int)!p.direct);
+            if (Q && halo_ships_bf16(Q, dir) != halo_ships_bf16(c, dir))   // (the switch, or the gather mode that drives the rule)
+                return fail(c, DORY_ERR_COMM, "local transport: dory_halo_bf16_rows differs: rank %u ships %s rows, rank %u %s rows (the switch and the "
+                            "gather mode must be the same on all ranks)", c->nodeId, halo_ships_bf16(c, dir) ? "bf16" : "fp32", q, halo_ships_bf16(c, dir) ? "fp32" : "bf16");
         }
     }
     const bool direct = lands_directly(p, wire, ghost->ld);
     if (direct && ghost->rows != p.recv_total)   // (the received rows are written at the tensor's own stride: it must hold exactly them)
         return fail(c, DORY_ERR_ARG, "halo_exchange: ghost tensor of %llu rows for a plan that receives %u", (unsigned long long)ghost->rows, p.recv_total);
     // (option halo_direct_recv: a receive buffer only where dory_halo_plan allocated one -- never inside an epoch)
-    const size_t sb = (size_t)p.send_total * w * sizeof(float), rb = direct ? 0 : (size_t)p.recv_total * w * sizeof(float);
+    const size_t sb = (size_t)p.send_total * row_b, rb = direct ? 0 : (size_t)p.recv_total * row_b;
     if (p.direct && rb > c->recv_cap) return fail(c, DORY_ERR_ARG, NO_RECV_BUF, w, ghost->ld);
     if (tr == Transport::Local && (sb > c->send_cap || rb > c->recv_cap))
         return fail(c, DORY_ERR_COMM, "local transport: exchange buffers too small for %u-float rows (peers hold their addresses: no regrowth)", w);
@@ -775,7 +817,8 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
         Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
         int rc = send_rows(c, src, dir, wire, p, c->comm, true);
         float *recv = direct ? ghost->d : c->recv_buf;
-        if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, w, recv) : exchange_rccl(c, p, w, recv);
+        const uint32_t wf = (uint32_t)(row_b / sizeof(float));
+        if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, wf, recv) : exchange_rccl(c, p, wf, recv);
         if (!rc && !direct) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm);
         if (rc) return rc;
         // the one step of an arm left in the shared body: the host arm's, but it stays behind the unpack, so that the unpack
@@ -798,6 +841,7 @@ bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd,
         for (uint32_t layer = 0; layer <= c->L; ++layer) {
             Tensor *src, *ghost;
             if (!halo_route(c, layer, d, &src, &ghost) || src != out || !ghost) continue;
+            if (wire_bf16(c, d)) return false;   // (dory_halo_bf16_rows: the pack kernel rounds the rows; no GEMM stores fp32 rows nobody sends)
             const uint32_t w = wire_width(c, out);
             if ((size_t)p.send_total * w * sizeof(float) > c->send_cap) return false;   // (the exchange would regrow the buffer)
             sd->buf = c->send_buf;
@@ -951,6 +995,7 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
     }
     // (option halo_direct_recv: padded rows land in the ghost tensors; only exact rows narrower than their padding -- option
     // halo_exact_rows, as it stands now -- are staged)
+    w = std::max(w, 2u);   // (dory_halo_bf16_rows: a one-column row travels as 4 bf16)
     const bool staged = !p.direct || halo_exact(c);
     return ensure_exchange_buffers(c, (size_t)p.send_total * w * sizeof(float), staged ? (size_t)p.recv_total * w * sizeof(float) : 0);
 }
@@ -1043,7 +1088,7 @@ int dory_halo_pack(dory_ctx *c, uint32_t layer, int dir, float *send_buf) {
     int rc = halo_tensors(c, layer, dir, &src, &ghost);
     if (rc) return rc;
     if (!c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_pack: no plan");
-    return split_rows(c, "halo_pack", true, dir, src, ghost, send_buf);
+    return split_rows(c, "halo_pack", true, dir, src, ghost, send_buf, true);
 }
 
 int dory_halo_unpack(dory_ctx *c, uint32_t layer, int dir, const float *recv_buf) {
@@ -1054,7 +1099,7 @@ int dory_halo_unpack(dory_ctx *c, uint32_t layer, int dir, const float *recv_buf
     int rc = halo_tensors(c, layer, dir, &src, &ghost);
     if (rc) return rc;
     if (!c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack: no plan");
-    return split_rows(c, "halo_unpack", false, dir, src, ghost, const_cast<float *>(recv_buf));
+    return split_rows(c, "halo_unpack", false, dir, src, ghost, const_cast<float *>(recv_buf), true);
 }
 
 // pack / unpack of any named tensor with the plan of `dir`
@@ -1064,7 +1109,7 @@ int dory_halo_pack_tensor(dory_ctx *c, uint32_t layer, const char *name, int dir
     Tensor *src = name ? find(c, layer, name) : nullptr;
     if (!src || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
     if (src->rows != c->N) return fail(c, DORY_ERR_ARG, "halo_pack_tensor: '%s' is not a per-local-vertex tensor", name);
-    return split_rows(c, "halo_pack_tensor", true, dir, src, nullptr, send_buf);
+    return split_rows(c, "halo_pack_tensor", true, dir, src, nullptr, send_buf, false);
 }
 
 int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int dir, const float *recv_buf) {
@@ -1075,7 +1120,7 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
     if (!ghost || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
     if (ghost->rows != c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: '%s' is not a ghost tensor of that direction", name);
     if (!strcmp(name, "fg_z") && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;   // (as halo_tensors: the kept neighbour sum of the old ghost rows no longer holds)
-    return split_rows(c, "halo_unpack_tensor", false, dir, nullptr, ghost, const_cast<float *>(recv_buf));
+    return split_rows(c, "halo_unpack_tensor", false, dir, nullptr, ghost, const_cast<float *>(recv_buf), false);
 }
 
 // ---- the fused halo pack: switch and counters (include/dorylus_hip.h) ----------------------------------------------------------
@@ -1101,6 +1146,39 @@ int dory_halo_fused_pack_stats(dory_ctx *c, uint64_t *fused_exchanges, uint64_t 
     if (fused_exchanges) *fused_exchanges = c->fused_exchanges;
     if (fused_rows) *fused_rows = c->fused_rows;
     if (fallback_exchanges) *fallback_exchanges = c->fallback_exchanges;
+    return DORY_OK;
+}
+
+// ---- bf16 halo rows: switch, counters, and the row an exchange puts on the wire (include/dorylus_hip.h) ------------------------
+int dory_halo_bf16_rows(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_bf16_rows: dory_configure first; on is 0 or 1");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_bf16_rows: not while an epoch graph is being recorded");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange that may now ship bf16)
+    c->halo_bf16.store(on, std::memory_order_release);
+    return DORY_OK;
+}
+
+int dory_halo_bf16_rows_stats(dory_ctx *c, uint64_t *bf16_packs, uint64_t *bf16_bytes, uint64_t *fp32_packs_while_on) {
+    CHECK_CTX(c);
+    if (bf16_packs) *bf16_packs = c->halo_bf16_packs;
+    if (bf16_bytes) *bf16_bytes = c->halo_bf16_bytes;
+    if (fp32_packs_while_on) *fp32_packs_while_on = c->halo_fp32_packs_while_on;
+    return DORY_OK;
+}
+
+int dory_halo_wire_row(dory_ctx *c, uint32_t layer, int dir, uint32_t *elem_bytes, uint32_t *row_elems) {
+    CHECK_CTX(c);
+    if (!c->configured || !c->prealloc || (dir != 0 && dir != 1)) return fail(c, DORY_ERR_ARG, "halo_wire_row: configure + preallocate first; dir is 0 or 1");
+    Tensor *src, *ghost;
+    if (!halo_route(c, layer, dir, &src, &ghost)) return fail(c, DORY_ERR_ARG, "halo_wire_row: layer %u out of range", layer);
+    if (!src || !ghost) return fail(c, DORY_ERR_ARG, "halo_wire_row: tensors missing");
+    RowWire wire;
+    int rc = row_wire(c, "halo_wire_row", src, ghost, true, nullptr, dir, &wire);
+    if (rc) return rc;
+    if (elem_bytes) *elem_bytes = wire.elem_bytes();
+    if (row_elems) *row_elems = wire.w;
     return DORY_OK;
 }
 

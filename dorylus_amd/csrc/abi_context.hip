@@ -242,6 +242,7 @@ int dory_create(int device, dory_ctx **out) {
     (void)hipMemset(c->sweep_stat, 0, SWEEP_STAT_WORDS * sizeof(uint32_t));
     c->own_compute = c->own_comm = true;
     for (int i = 0; i < OPT_COUNT; ++i) c->opt[i] = option_spec(i)->def;   // every option at the table's default (host/options.cpp)
+    c->gcn_bf16_mode.store((int)c->opt[OPT_GCN_BF16_GATHER], std::memory_order_release);
     c->cus_per_xcd = (uint32_t)std::max(1, prop.multiProcessorCount / 8);
     {   // K1s's placement assumption (ctx.hpp): workgroup id & 7 = XCD, eight XCDs
         const uint32_t PG = 2048;
@@ -391,6 +392,7 @@ int dory_gat_bf16_gather(dory_ctx *c, int mode, int wide) {
     if (c->capturing) return fail(c, DORY_ERR_ARG, "gat_bf16_gather: not while an epoch graph is being recorded");
     if (mode != c->gat_bf16_mode || (wide == 1) != c->gat_bf16_wide) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other mode's kernels)
     c->gat_bf16_mode = mode;
+    c->gat_bf16_mode_pub.store(mode, std::memory_order_release);   // (dory_halo_bf16_rows: the peers of the local transport read the rule's inputs)
     c->gat_bf16_wide = wide == 1;
     return gat_bf16_reserve_all(c);   // (before dory_preallocate: nothing yet -- the first eager aggregation reserves)
 }
@@ -1066,6 +1068,7 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     // the copies the peers of the in-process transport read without this context's lock
     if (id == OPT_HALO_EXACT_ROWS) c->halo_exact.store((int)value, std::memory_order_release);
     if (id == OPT_HALO_DIRECT_RECV) c->halo_direct.store((int)value, std::memory_order_release);
+    if (id == OPT_GCN_BF16_GATHER) c->gcn_bf16_mode.store((int)value, std::memory_order_release);   // (dory_halo_bf16_rows' rule)
     c->ah0_valid = false;   // (another kernel variant sums in another order: a cached ah@0 is only kept across identical settings)
     return DORY_OK;
 }

@@ -66,11 +66,17 @@ struct FusedStamp {
     const float *buf = nullptr;
 };
 
-// The wire format of a packed halo row: w floats per row -- the tensor's padded ld, or with `exact` (option halo_exact_rows)
-// its cols.  Made by row_wire() (abi_comm.hip) alone; which pack / unpack kernels run and the zeroing of [w, ld) follow from it.
+// The wire format of a packed halo row: w elements per row -- the tensor's padded ld, or with `exact` (option halo_exact_rows)
+// its cols -- of 4 bytes (fp32), or with `bf16` (dory_halo_bf16_rows) of 2: then w is rounded up to a multiple of 4 elements and
+// `cols` of them hold values, the rest zeros.  Made by row_wire() (abi_comm.hip) alone; which pack / unpack kernels run and the
+// zeroing of [w, ld) follow from it, and every byte count of an exchange from row_bytes().
 struct RowWire {
     uint32_t w = 0;
     bool exact = false;
+    bool bf16 = false;
+    uint32_t cols = 0;   // (bf16 only: the columns of the tensor below w that the pack reads)
+    uint32_t elem_bytes() const { return bf16 ? 2u : 4u; }
+    size_t row_bytes() const { return (size_t)w * elem_bytes(); }
 };
 
 // Scatter messages (dory_scatter_msgs_*, abi_comm.hip): the id tables of dory_halo_wire_ids, the round stamps and counters of
@@ -306,7 +312,12 @@ struct dory_ctx {
     bool fused_pack = false;
     dory::FusedStamp fused_stamp;
     uint64_t fused_exchanges = 0, fused_rows = 0, fallback_exchanges = 0;
-    dory::ScatterState scatter;   // scatter messages (dory_scatter_msgs_*) and the scatter transport
+    // bf16 halo rows (dory_halo_bf16_rows; default off) and the two gather modes its rule reads (option gcn_bf16_gather,
+    // dory_gat_bf16_gather's mode) -- copies the peers of the local transport may read without this context's lock -- and the
+    // eager packs counted: those that wrote bf16 rows, their bytes, those that wrote fp32 rows while the switch was on
+    std::atomic<int> halo_bf16{0}, gcn_bf16_mode{0}, gat_bf16_mode_pub{0};
+    uint64_t halo_bf16_packs = 0, halo_bf16_bytes = 0, halo_fp32_packs_while_on = 0;
+    dory::ScatterState scatter;  // scatter messages (dory_scatter_msgs_*) and the scatter transport
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
     dory_alltoallv_fn tx_a2a = nullptr;
@@ -638,6 +649,13 @@ hipError_t launch_gather_rows_exact(float *dst, const float *src, uint32_t ld, u
 hipError_t launch_scatter_rows_exact(float *dst, const float *src, uint32_t ld, uint32_t cols,
                                      const uint32_t *rows, uint32_t n, hipStream_t s);
 hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const uint32_t *rows, uint32_t n, hipStream_t s);
+// dory_halo_bf16_rows: the dense side holds rows of row_elems bf16 (a multiple of 4, 8-byte aligned).  The gather rounds
+// [0, cols) of every listed row (nearest even, the conversion of launch_bf16_rows) and writes zeros into [cols, row_elems); the
+// scatter writes the whole ld-wide row: [0, row_elems) widened from the stream, zeros behind.
+hipError_t launch_gather_rows_bf16(void *dst, const float *src, uint32_t ld, uint32_t cols, uint32_t row_elems,
+                                   const uint32_t *rows, uint32_t n, hipStream_t s);
+hipError_t launch_scatter_rows_bf16(float *dst, const void *src, uint32_t ld, uint32_t row_elems,
+                                    const uint32_t *rows, uint32_t n, hipStream_t s);
 // option halo_direct_recv: whole ld-wide rows (any ld) between the caller-visible order of a ghost tensor and its stored (wire)
 // order, off the epoch's path -- to_wire: dst[i] = src[order[i]] (upload), else dst[order[i]] = src[i] (download)
 hipError_t launch_permute_rows(float *dst, const float *src, uint32_t ld, const uint32_t *order, uint32_t n, bool to_wire, hipStream_t s);

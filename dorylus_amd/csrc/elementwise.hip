@@ -739,6 +739,88 @@ hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const ui
     return hipGetLastError();
 }
 
+// ---- K6, bf16 rows (dory_halo_bf16_rows) ----------------------------------------------------------------------------------------
+// The dense side holds rows of `re4` quads of bf16 (row_elems = 4 x re4 elements, 8 bytes a quad): a row is a multiple of 8
+// bytes, so no quad straddles two rows and a lane owns one quad of one row -- four elements per lane: one 16-byte load (or
+// store) on the fp32 side, one 8-byte store (or load) on the dense side.  VEC: the tensor's ld is a multiple of 4 (every
+// exchanged tensor but the one-column ones, ld == 1: those move as dwords on the fp32 side).
+// pack: rounds with pack_bf16x2, the conversion of bf16_rows_kernel -- the bits the consumer's own rounding would give.
+// Columns >= cols are never read: they are zeros on the dense side (padded form: cols == ld, the owner's padding travels as in
+// the fp32 form).  The row list may repeat a row.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gather_rows_bf16_kernel(uint2 *dst, const float *src, uint32_t ld, uint32_t cols, uint32_t re4,
+                                                               const uint32_t *rows, uint32_t n) {
+    const uint64_t total = (uint64_t)n * re4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / re4);
+        const uint32_t c0 = (uint32_t)(i % re4) * 4u;
+        const float *p = src + (size_t)rows[r] * ld;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (c0 < cols) {
+            if (VEC) {   // (c0 < cols <= ld, both multiples of 4 apart from cols: the quad lies inside the row)
+                const float4 q = *reinterpret_cast<const float4 *>(p + c0);
+                v[0] = q.x;
+                v[1] = c0 + 1 < cols ? q.y : 0.f;
+                v[2] = c0 + 2 < cols ? q.z : 0.f;
+                v[3] = c0 + 3 < cols ? q.w : 0.f;
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    if (c0 + k < cols) v[k] = p[c0 + k];
+            }
+        }
+        dst[i] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+    }
+}
+// unpack: writes the whole ld-wide row of every listed ghost slot -- quads below re4 widened from the stream (a bf16 is the
+// high half of the fp32 with the same value), zeros behind them: the bits the fp32 forms leave, whatever the padding held.
+template <bool VEC>
+__global__ __launch_bounds__(256) void scatter_rows_bf16_kernel(float *dst, const uint2 *src, uint32_t ld, uint32_t re4,
+                                                                const uint32_t *rows, uint32_t n) {
+    const uint32_t ld4 = (ld + 3u) >> 2;
+    const uint64_t total = (uint64_t)n * ld4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / ld4);
+        const uint32_t q = (uint32_t)(i % ld4);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < re4) {
+            const uint2 u = src[(uint64_t)r * re4 + q];
+            v = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
+                            __uint_as_float(u.y & 0xFFFF0000u));
+        }
+        float *p = dst + (size_t)rows[r] * ld;
+        if (VEC) {
+            reinterpret_cast<float4 *>(p)[q] = v;
+        } else {
+            const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k)
+                if (q * 4u + k < ld) p[q * 4u + k] = e[k];
+        }
+    }
+}
+
+hipError_t launch_gather_rows_bf16(void *dst, const float *src, uint32_t ld, uint32_t cols, uint32_t row_elems,
+                                   const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || row_elems == 0) return hipSuccess;
+    if ((row_elems & 3) || cols > ld || cols > row_elems || ((uintptr_t)dst & 7)) return hipErrorInvalidValue;
+    const uint64_t total = (uint64_t)n * (row_elems / 4);
+    int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    if (ld & 3) hipLaunchKernelGGL(gather_rows_bf16_kernel<false>, dim3(blocks), dim3(256), 0, s, static_cast<uint2 *>(dst), src, ld, cols, row_elems / 4, rows, n);
+    else hipLaunchKernelGGL(gather_rows_bf16_kernel<true>, dim3(blocks), dim3(256), 0, s, static_cast<uint2 *>(dst), src, ld, cols, row_elems / 4, rows, n);
+    return hipGetLastError();
+}
+hipError_t launch_scatter_rows_bf16(float *dst, const void *src, uint32_t ld, uint32_t row_elems,
+                                    const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || ld == 0) return hipSuccess;
+    if ((row_elems & 3) || row_elems > ((ld + 3u) & ~3u) || ((uintptr_t)src & 7)) return hipErrorInvalidValue;
+    const uint64_t total = (uint64_t)n * ((ld + 3u) / 4);
+    int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    if (ld & 3) hipLaunchKernelGGL(scatter_rows_bf16_kernel<false>, dim3(blocks), dim3(256), 0, s, dst, static_cast<const uint2 *>(src), ld, row_elems / 4, rows, n);
+    else hipLaunchKernelGGL(scatter_rows_bf16_kernel<true>, dim3(blocks), dim3(256), 0, s, dst, static_cast<const uint2 *>(src), ld, row_elems / 4, rows, n);
+    return hipGetLastError();
+}
+
 // ---- option halo_direct_recv: a ghost tensor between its caller-visible and its stored (wire) order ------------------------
 // Whole ld-wide rows, a dword per thread (ld may be 1: the per-head tensors of a single head), `order` a permutation of
 // [0, n).  Off the epoch's path: dory_tensor_upload / dory_tensor_download of a ghost tensor only.

@@ -268,6 +268,59 @@ int dory_halo_fused_pack_stats(dory_ctx *ctx, uint64_t *fused_exchanges, uint64_
 int dory_gat_bf16_gather(dory_ctx *ctx, int mode, int wide);
 int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide, uint64_t *k1, uint64_t *fp32_fallbacks);
 
+/* ---- bf16 halo rows: exchanges whose consumer gathers bf16 ship bf16 (opt-in, default off; nothing in the reference) ----
+ * With the bf16 gathers on (option gcn_bf16_gather, dory_gat_bf16_gather) the aggregation that reads a ghost tensor rounds every
+ * ghost row to bf16 (nearest even) before it reads it: the lower 16 bits of every fp32 the exchange ships are dropped unseen.
+ * Rounding is idempotent, so with this switch on the pack rounds (the same conversion, v_cvt_pk_bf16_f32), 16 bits per element
+ * travel, and the unpack widens them (bits << 16) into the fp32 ghost tensor: the aggregation's own conversion reproduces the
+ * same bf16 row, and every result keeps its bits relative to the fp32 payload under the same gather mode.
+ * The rule -- decided per exchange from the settings at that moment (the switch, the gather mode), the same for every layer:
+ *     model           forward exchange                        backward exchange
+ *     GCN             h -> fg, xw -> fgxw: gcn_bf16_gather >= 1    grad -> bg, g -> bgg: gcn_bf16_gather == 2
+ *     GAT prototype   z -> fg_z: dory_gat_bf16_gather mode >= 1    grad -> bg_d: mode == 2
+ *     multi-head GAT  never                                    never
+ * (the multi-head GAT's finishing kernels and blocked forms read fg_z in fp32, and it exchanges do / st itself).
+ * Not taken, i.e. fp32 rows travel as without the switch, the results are the same and the pack is counted in
+ * fp32_packs_while_on: the rule says no; the scatter-message transport (the reference's format); a plan made with
+ * halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer);
+ * dory_halo_pack_tensor / dory_halo_unpack_tensor (the consumer is unknown).  dory_halo_pack / dory_halo_unpack follow the rule
+ * as they follow halo_exact_rows: the caller's buffer (8-byte aligned) then holds rows x row_elems x 2 bytes.  The fused halo
+ * pack never serves an exchange that ships bf16 (no GEMM stores fp32 rows nobody sends; its statistics count a fallback).
+ * Wire format: a packed row holds row_elems bf16 values -- the tensor's ld, or with halo_exact_rows = 1 its cols rounded up to a
+ * multiple of 4 with zeros in the trailing elements, which the pack writes itself (a one-column tensor, ld == 1: 4 elements).
+ * Rows are multiples of 8 bytes.  The host transport's counts and offsets stay in floats: rows x row_elems / 2.  RCCL and the
+ * in-process copies move the same bytes; no buffer is re-sized.  In the in-process transport ranks that disagree -- on the switch
+ * or on the gather mode that drives the rule -- fail at once with DORY_ERR_COMM; for RCCL and host transports EVERY RANK MUST SET
+ * THE SAME.  The read-only key halo_floats_packed counts a bf16 row as row_elems / 2.
+ * Visible consequence: after a bf16 exchange the fp32 ghost tensor holds the owner's rows rounded to bf16 (and zeros in
+ * [cols, ld)): dory_tensor_download of fg / fgxw / bg / bgg / fg_z / bg_d shows rounded rows.
+ * Bytes per row on the link -- ARITHMETIC, nothing here has run on more than one GPU:
+ *     row                                          fp32 padded  fp32 exact  bf16 padded  bf16 exact
+ *     Reddit h / grad, 128 floats                     512 B       512 B       256 B       256 B
+ *     Amazon, 64 floats                               256 B       256 B       128 B       128 B
+ *     Friendster, 48 floats                           256 B       192 B       128 B        96 B
+ *     41-float rows (GAT z, transform-first xw)       256 B       164 B       128 B        88 B
+ * dory_halo_bf16_rows: on = 0 (default) / 1, any time after dory_configure, outside an exchange; accepted and inert with
+ * num_nodes == 1; DORY_ERR_ARG for other values or while an epoch graph is being recorded.
+ * dory_halo_bf16_rows_stats: packs that wrote bf16 rows, their bytes, packs (and fused or scatter-message exchanges) that shipped
+ * fp32 while the switch was on -- eager calls only, since dory_create; any pointer may be NULL.
+ * dory_halo_wire_row: what dory_halo_exchange(layer, dir) and dory_halo_pack(layer, dir, ...) would put on the wire with the
+ * settings of this moment: bytes per element (4 or 2) and elements per row -- what a foreign transport sizes its buffers by.
+ * Kernels (csrc/elementwise.hip): four elements per lane, one 16-byte access on the fp32 side and one 8-byte access on the
+ * packed side.  Chosen by measurement against an 8-element form (two 16-byte accesses, one 16-byte access; stand-alone copies of
+ * both, 3.15 M rows): the 8-element unpack is 15-18 % SLOWER at every width, the 8-element pack 2-7 % faster on padded rows and even
+ * on exact ones, and rows of row_elems % 8 == 4 (41 exact: 44) have no 16-byte grid at all -- one form of four serves every row.
+ * Measured on one MI355X (profiles/r19_halo_bf16_rows.txt, profiles/HISTORY.md section 20; NOTHING HERE CROSSED A LINK), 3.15 M
+ * send rows and as many ghost rows, switch off / on alternated: pack 0.293 -> 0.210 ms (64 floats), 1.477 -> 1.105 (300), 0.599 ->
+ * 0.437 (128), 0.284 -> 0.212 (48 padded), 0.246 -> 0.195 (48 exact), 0.285 -> 0.205 (41 padded), 0.322 -> 0.188 (41 exact); unpack
+ * 0.315 -> 0.218, 1.610 -> 1.092, 0.668 -> 0.461, 0.330 -> 0.211, 0.393 -> 0.203, 0.304 -> 0.210, 0.433 -> 0.202.  No bf16 kernel is
+ * slower than its fp32 counterpart at a measured shape.  The in-process-transport epoch (200 000 vertices, 4 M edges, 128-128-16,
+ * gather mode 2) does not move beyond its run-to-run spread at P = 2 or 4; with the switch off the headline and 8-head GAT epochs
+ * are inside the parent's ranges. */
+int dory_halo_bf16_rows(dory_ctx *ctx, int on);
+int dory_halo_bf16_rows_stats(dory_ctx *ctx, uint64_t *bf16_packs, uint64_t *bf16_bytes, uint64_t *fp32_packs_while_on);
+int dory_halo_wire_row(dory_ctx *ctx, uint32_t layer, int dir, uint32_t *elem_bytes, uint32_t *row_elems);
+
 /* ---- scatter messages: the reference's own graph-server <-> graph-server wire, packed and unpacked on the device ----------
  * What Engine::verticesPushOut puts on a socket and ghostReceiver* takes apart (include/dorylus_wire.h: the format table with
  * its citations): messages of an 8-character receiver topic, five unsigned header fields and (global vertex id, featDim floats)
