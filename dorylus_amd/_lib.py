@@ -31,6 +31,7 @@ SYMBOLS = [
     "dory_halo_fused_pack", "dory_halo_fused_pack_stats",
     "dory_gat_bf16_gather", "dory_gat_bf16_gather_stats",
     "dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row",
+    "dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -126,6 +127,9 @@ def load():
         "dory_halo_bf16_rows": [vp, i32],
         "dory_halo_bf16_rows_stats": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
         "dory_halo_wire_row": [vp, u32, i32, C.POINTER(u32), C.POINTER(u32)],
+        "dory_halo_bf16_ghosts": [vp, i32],
+        "dory_halo_bf16_ghosts_stats": [vp] + [C.POINTER(u64)] * 5,
+        "dory_halo_bf16_ghost_peek": [vp, u32, cp, C.POINTER(vp), C.POINTER(i32)],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -159,8 +163,9 @@ def load():
         if (name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check", "dory_halo_wire_ids",
                      "dory_comm_set_scatter_transport", "dory_halo_send_map") or name.startswith("dory_scatter_msgs_")
                 or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
-                or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows)
+                or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")
+                or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -539,6 +544,25 @@ class Context:
         a, b, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._ck(self.lib.dory_halo_bf16_rows_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
         return a.value, b.value, f.value
+
+    GHOST_STATES = ("FP32", "TWIN", "BOTH")     # DORY_GHOST_FP32 / _TWIN / _BOTH
+
+    def halo_bf16_ghosts(self, on=True):
+        """bf16 halo rows stay bf16 on arrival, in a bf16 twin of the ghost tensor that the aggregation on bf16 rows gathers from
+        (opt-in on top of halo_bf16_rows; dory_halo_bf16_ghosts; after preallocate)"""
+        self._ck(self.lib.dory_halo_bf16_ghosts(self.h, int(on)))
+
+    def halo_bf16_ghosts_stats(self):
+        """dict(landed_direct, landed_by_kernel, conversions_skipped, widened, twin_bytes)"""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._ck(self.lib.dory_halo_bf16_ghosts_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("landed_direct", "landed_by_kernel", "conversions_skipped", "widened", "twin_bytes"), (int(x.value) for x in v)))
+
+    def halo_bf16_ghost_peek(self, layer, name):
+        """(device pointer of the tensor's bf16 twin or None, state "FP32" / "TWIN" / "BOTH"): which copy holds the current rows"""
+        p, st = C.c_void_p(), C.c_int(0)
+        self._ck(self.lib.dory_halo_bf16_ghost_peek(self.h, layer, name.encode(), C.byref(p), C.byref(st)))
+        return p.value, self.GHOST_STATES[st.value]
 
     def halo_wire_row(self, layer, direction):
         """(bytes per element, elements per row) of what halo_exchange / halo_pack of (layer, direction) put on the wire now"""

@@ -46,7 +46,12 @@ inline bool halo_exact(const dory_ctx *c) { return c->halo_exact.load(std::memor
 // (halo_exact_rows with cols < ld) are strided in the tensor: they keep the receive buffer and the unpack kernels, which then
 // scatter by an identity list (HaloPlan::d_unpack_slots).
 inline bool halo_direct(const dory_ctx *c) { return c->halo_direct.load(std::memory_order_acquire) == 1; }
-inline bool lands_directly(const HaloPlan &p, RowWire wire, uint32_t ghost_ld) { return p.direct && wire.w == ghost_ld; }
+// dory_halo_bf16_ghosts: received bf16 rows stay bf16 in the ghost tensor's twin (`keeps`); then an exchange lands directly where
+// the wire's row is the twin's -- compared in elements (fp32 rows in an fp32 tensor, bf16 rows in a bf16 twin).  bf16 rows never
+// land in fp32 rows.
+inline bool ghosts_on(const dory_ctx *c) { return c->halo_bf16_ghosts.load(std::memory_order_acquire) == 1; }
+inline bool keeps_bf16(const dory_ctx *c, RowWire wire, const Tensor *ghost) { return wire.bf16 && ghosts_on(c) && ghost && ghost->twin; }
+inline bool lands_directly(const HaloPlan &p, RowWire wire, uint32_t ghost_ld, bool keep) { return p.direct && wire.w == ghost_ld && wire.bf16 == keep; }
 const char *const NO_RECV_BUF = "halo_direct_recv: this exchange needs the receive buffer (rows of %u floats in a tensor of ld %u) and "
                                 "dory_halo_plan allocated none: set halo_exact_rows = 1 before dory_halo_plan";
 
@@ -59,14 +64,14 @@ const char *const NO_RECV_BUF = "halo_direct_recv: this exchange needs the recei
 // whose consumer is unknown (the *_tensor entry points: fp32).  bf16 rows hold the width rounded up to a multiple of 4 elements
 // (zeros behind the tensor's cols): multiples of 8 bytes, in a buffer aligned to 8.
 inline uint32_t wire_width(const dory_ctx *c, const Tensor *rows) { return halo_exact(c) ? rows->cols : rows->ld; }
-bool wire_bf16(const dory_ctx *c, int dir);
+bool wire_bf16(const dory_ctx *c, int dir, uint32_t ld);
 int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghost, bool pack, const void *buf, int rule_dir, RowWire *out) {
     const Tensor *rows = pack ? src : ghost;
     out->exact = halo_exact(c);
     if (out->exact && src && ghost && src->cols != ghost->cols)
         return fail(c, DORY_ERR_ARG, "%s: widths of source (%u) and ghost tensor (%u) differ", who, src->cols, ghost->cols);
     out->w = wire_width(c, rows);
-    out->bf16 = rule_dir >= 0 && wire_bf16(c, rule_dir);
+    out->bf16 = rule_dir >= 0 && wire_bf16(c, rule_dir, rows->ld);
     if (out->bf16) {
         out->cols = rows->cols;
         out->w = (out->w + 3u) & ~3u;
@@ -117,8 +122,12 @@ int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloP
 // the received rows, dense at the wire's width w, into the plan's ghost slots (option halo_direct_recv: row r into ghost row r);
 // the exact form writes the whole row: [0, w) from the buffer, zeros into [w, ld) -- the bits the padded form leaves, whatever
 // the padding held before
-int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s) {
-    if (wire.bf16) {   // (the whole ld-wide row: widened values, zeros behind them)
+// dory_halo_bf16_ghosts (`twin` not null: the rows are bf16 and stay bf16): the keep form copies them into the twin's rows instead,
+// zeros in [w, ld); `ghost` is not touched
+int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s, uint16_t *twin = nullptr) {
+    if (twin) {
+        HIPCK(c, launch_scatter_rows_bf16_keep(twin, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
+    } else if (wire.bf16) {   // (the whole ld-wide row: widened values, zeros behind them)
         HIPCK(c, launch_scatter_rows_bf16(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
     } else if (wire.exact && (wire.w & 3)) {
         HIPCK(c, launch_scatter_rows_exact(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
@@ -129,15 +138,32 @@ int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const floa
     return DORY_OK;
 }
 
+// dory_halo_bf16_ghosts: all rows of `ghost` have been enqueued on stream s -- fp32 rows (state FP32), or (keep) bf16 rows in its twin:
+// counted (eager calls) as landed in the twin itself or copied there by the keep kernel; state TWIN, or, where the tensor's raw
+// pointer is out (the caller reads fp32 rows behind the library's back), widened at once behind them on s (widen_now; the deferred
+// half of the local transport does it itself, LocalPending::widen_to) and BOTH
+int ghost_rows_landed(dory_ctx *c, Tensor *ghost, bool keep, bool direct, hipStream_t s, bool widen_now) {
+    if (!keep) { ghost_wrote_fp32(ghost); return DORY_OK; }
+    if (!c->capturing) (direct ? c->ghost_landed_direct : c->ghost_landed_by_kernel) += 1;
+    ghost->twin_state = ghost->raw_handed ? DORY_GHOST_BOTH : DORY_GHOST_TWIN;
+    if (ghost->raw_handed && widen_now) HIPCK(c, launch_widen_rows_bf16(ghost->d, ghost->twin, ghost->rows * ghost->ld, s));
+    return DORY_OK;
+}
+
 // the four split entry points (foreign transports, multi-context tests) after their own checks: pack the plan's send rows of
-// `src` into the caller's buffer, or unpack it into `ghost`; the other tensor is the one halo_tensors resolved, or null
+// `src` into the caller's buffer, or unpack it into `ghost` (dory_halo_bf16_ghosts: into its twin, by the exchange's rule); the
+// other tensor is the one halo_tensors resolved, or null
 int split_rows(dory_ctx *c, const char *who, bool pack, int dir, const Tensor *src, Tensor *ghost, float *buf, bool follows_rule) {
     RowWire wire;
     int rc = row_wire(c, who, src, ghost, pack, buf, follows_rule ? dir : -1, &wire);
     if (rc) return rc;
     Timed t(c, "halo", c->compute);
-    return pack ? pack_rows(c, buf, src, wire, c->plan[dir], c->compute)
-                : unpack_rows(c, ghost->d, ghost->ld, wire, buf, c->plan[dir], c->compute);
+    if (pack) return pack_rows(c, buf, src, wire, c->plan[dir], c->compute);
+    const bool keep = keeps_bf16(c, wire, ghost);
+    if (ghost->rows != c->plan[dir].recv_total && keep)   // (the twin holds exactly the plan's rows)
+        return fail(c, DORY_ERR_ARG, "%s: ghost tensor of %llu rows for a plan that receives %u", who, (unsigned long long)ghost->rows, c->plan[dir].recv_total);
+    rc = unpack_rows(c, ghost->d, ghost->ld, wire, buf, c->plan[dir], c->compute, keep ? ghost->twin : nullptr);
+    return rc ? rc : ghost_rows_landed(c, ghost, keep, false, c->compute, true);
 }
 
 // resolve (layer, dir) -> source tensor, ghost tensor, as Engine::scatterGCN/GAT do; false: layer out of range.  No side effects:
@@ -172,9 +198,12 @@ bool halo_ships_bf16(const dory_ctx *c, int dir) {
     return mode >= (dir == DORY_FORWARD ? 1 : 2);
 }
 // ... and what keeps fp32 although the rule says yes: the scatter-message transport (the reference's format), and a plan made with
-// halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer)
-bool wire_bf16(const dory_ctx *c, int dir) {
-    return halo_ships_bf16(c, dir) && !c->plan[dir].direct && transport_of(c) != Transport::Scatter;
+// halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer) -- unless
+// dory_halo_bf16_ghosts is on and the tensor (ld: the same number on every rank) has a twin for them to land in.  direct_keeps: that
+// exception, from settings every rank can read of every other.
+inline bool direct_keeps(const dory_ctx *c, uint32_t ld) { return ghosts_on(c) && ld >= 4; }
+bool wire_bf16(const dory_ctx *c, int dir, uint32_t ld) {
+    return halo_ships_bf16(c, dir) && (!c->plan[dir].direct || direct_keeps(c, ld)) && transport_of(c) != Transport::Scatter;
 }
 int halo_tensors(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **ghost) {
     if (!halo_route(c, layer, dir, src, ghost)) return fail(c, DORY_ERR_ARG, "halo: layer %u out of range", layer);
@@ -368,6 +397,7 @@ int scatter_deliver(dory_ctx *c, const char *name, const void *const *msgs, cons
     for (const Parsed &q : P) {   // what halo_tensors and dory_halo_exchange drop when these ghost rows change
         if (q.ghost == find(c, 0, "fg")) c->ah0_valid = false;
         if (q.ghost == find(c, q.layer, "fg_z") && q.layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[q.layer] = 0;
+        ghost_wrote_fp32(q.ghost);   // (dory_halo_bf16_ghosts: records are fp32; a round writes every ghost row)
     }
     std::unique_ptr<Timed> t;
     if (!in_cb) {   // (inside an exchange the comm stream waits already, and the exchange times itself)
@@ -556,10 +586,14 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     c->posted_sent.store(s, std::memory_order_release);
     lp.on = true;
     lp.dir = dir;
-    lp.ghost = ghost->d;
+    lp.keep = keeps_bf16(c, wire, ghost);
+    lp.ghost = lp.keep ? reinterpret_cast<char *>(ghost->twin) : reinterpret_cast<char *>(ghost->d);
     lp.ghost_ld = ghost->ld;
     lp.wire = wire;
-    lp.direct = lands_directly(p, wire, ghost->ld);
+    lp.direct = lands_directly(p, wire, ghost->ld, lp.keep);
+    lp.widen_to = lp.keep && ghost->raw_handed ? ghost->d : nullptr;
+    lp.ghost_rows = ghost->rows;
+    { int rc = ghost_rows_landed(c, ghost, lp.keep, lp.direct, c->comm, false); if (rc) return rc; }   // (every reader calls wait_halo first: the second half)
     if (deferred) {
         c->halo_pending = true;      // wait_halo(): local_exchange_finish, then the compute stream waits for ev_b
         return DORY_OK;
@@ -712,7 +746,7 @@ int local_exchange_finish(dory_ctx *c) {
     if (p.direct) {   // option halo_direct_recv: I pull every peer's segment out of its send buffer -- into the ghost tensor (the
         // wire's width is its ld), or into my receive buffer for the unpack (exact rows narrower than ld)
         const size_t rb = lp.wire.row_bytes();
-        char *dst = reinterpret_cast<char *>(lp.direct ? lp.ghost : c->recv_buf);
+        char *dst = lp.direct ? lp.ghost : reinterpret_cast<char *>(c->recv_buf);
         for (uint32_t q = 0; q < c->numNodes; ++q) {
             if (q == c->nodeId || !p.recv_counts[q]) continue;
             const dory_ctx *Q = grp.ctx[q];
@@ -726,7 +760,13 @@ int local_exchange_finish(dory_ctx *c) {
                                     (size_t)p.recv_counts[q] * rb, hipMemcpyDeviceToDevice, c->comm));
         }
     }
-    if (!lp.direct) { int rc = unpack_rows(c, lp.ghost, lp.ghost_ld, lp.wire, c->recv_buf, p, c->comm); if (rc) return rc; }
+    if (!lp.direct) {
+        int rc = unpack_rows(c, lp.keep ? nullptr : reinterpret_cast<float *>(lp.ghost), lp.ghost_ld, lp.wire, c->recv_buf, p, c->comm,
+                             lp.keep ? reinterpret_cast<uint16_t *>(lp.ghost) : nullptr);
+        if (rc) return rc;
+    }
+    // (dory_halo_bf16_ghosts, the tensor's raw pointer is out: its fp32 rows follow the twin at once)
+    if (lp.widen_to) HIPCK(c, launch_widen_rows_bf16(lp.widen_to, reinterpret_cast<const uint16_t *>(lp.ghost), lp.ghost_rows * lp.ghost_ld, c->comm));
     HIPCK(c, hipEventRecord(c->ev_cons[s & 1], c->comm));
     c->posted_cons.store(s, std::memory_order_release);
     if (lp.t_kind_b) (void)hipEventRecord(lp.t_kind_b, c->comm);
@@ -790,13 +830,20 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
             if (Q && halo_direct(Q) != p.direct)   // (who pushes and who pulls)
                 return fail(c, DORY_ERR_COMM, "local transport: option halo_direct_recv differs: rank %u has %d, rank %u has %d (all ranks must agree)",
                             c->nodeId, (int)p.direct, q, (int)!p.direct);
-            if (Q && halo_ships_bf16(Q, dir) != halo_ships_bf16(c, dir))   // (the switch, or the gather mode that drives the rule)
+            // what each rank would ship: the switch, the gather mode that drives the rule, and -- under a direct plan (the same on both by
+            // now) -- dory_halo_bf16_ghosts, without which such a plan keeps fp32
+            const bool q_ships = Q && halo_ships_bf16(Q, dir) && (!p.direct || direct_keeps(Q, ghost->ld));
+            if (Q && q_ships != wire.bf16)
                 return fail(c, DORY_ERR_COMM, "local transport: dory_halo_bf16_rows differs: rank %u ships %s rows, rank %u %s rows (the switch and the "
-                            "gather mode must be the same on all ranks)", c->nodeId, halo_ships_bf16(c, dir) ? "bf16" : "fp32", q, halo_ships_bf16(c, dir) ? "fp32" : "bf16");
+                            "gather mode must be the same on all ranks%s)", c->nodeId, wire.bf16 ? "bf16" : "fp32", q, wire.bf16 ? "fp32" : "bf16",
+                            p.direct ? ", and dory_halo_bf16_ghosts under halo_direct_recv" : "");
         }
     }
-    const bool direct = lands_directly(p, wire, ghost->ld);
-    if (direct && ghost->rows != p.recv_total)   // (the received rows are written at the tensor's own stride: it must hold exactly them)
+    const bool keep = keeps_bf16(c, wire, ghost);
+    const bool direct = lands_directly(p, wire, ghost->ld, keep);
+    if (wire.bf16 && p.direct && !keep)   // (not reached: every tensor halo_route names for a model that ships bf16 has a twin while the switch is on)
+        return fail(c, DORY_ERR_ARG, "halo_exchange: dory_halo_bf16_ghosts: the ghost tensor has no bf16 twin for a plan made with halo_direct_recv = 1");
+    if ((direct || keep) && ghost->rows != p.recv_total)   // (the received rows are written at the tensor's own stride: it must hold exactly them)
         return fail(c, DORY_ERR_ARG, "halo_exchange: ghost tensor of %llu rows for a plan that receives %u", (unsigned long long)ghost->rows, p.recv_total);
     // (option halo_direct_recv: a receive buffer only where dory_halo_plan allocated one -- never inside an epoch)
     const size_t sb = (size_t)p.send_total * row_b, rb = direct ? 0 : (size_t)p.recv_total * row_b;
@@ -816,10 +863,12 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
         Timed t(c, "halo", c->comm);
         Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
         int rc = send_rows(c, src, dir, wire, p, c->comm, true);
-        float *recv = direct ? ghost->d : c->recv_buf;
+        // (dory_halo_bf16_ghosts: bf16 rows that land directly land in the twin -- ld / 2 floats' worth of bytes a row)
+        float *recv = !direct ? c->recv_buf : keep ? reinterpret_cast<float *>(ghost->twin) : ghost->d;
         const uint32_t wf = (uint32_t)(row_b / sizeof(float));
         if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, wf, recv) : exchange_rccl(c, p, wf, recv);
-        if (!rc && !direct) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm);
+        if (!rc && !direct) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm, keep ? ghost->twin : nullptr);
+        if (!rc) rc = ghost_rows_landed(c, ghost, keep, direct, c->comm, true);
         if (rc) return rc;
         // the one step of an arm left in the shared body: the host arm's, but it stays behind the unpack, so that the unpack
         // is enqueued before the host blocks for the copy out of tx_recv (which the next exchange reuses)
@@ -841,7 +890,7 @@ bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd,
         for (uint32_t layer = 0; layer <= c->L; ++layer) {
             Tensor *src, *ghost;
             if (!halo_route(c, layer, d, &src, &ghost) || src != out || !ghost) continue;
-            if (wire_bf16(c, d)) return false;   // (dory_halo_bf16_rows: the pack kernel rounds the rows; no GEMM stores fp32 rows nobody sends)
+            if (wire_bf16(c, d, out->ld)) return false;   // (dory_halo_bf16_rows: the pack kernel rounds the rows; no GEMM stores fp32 rows nobody sends)
             const uint32_t w = wire_width(c, out);
             if ((size_t)p.send_total * w * sizeof(float) > c->send_cap) return false;   // (the exchange would regrow the buffer)
             sd->buf = c->send_buf;
@@ -859,6 +908,38 @@ void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &s
     c->fused_stamp.dir = dir;
     c->fused_stamp.w = sd.w;
     c->fused_stamp.buf = sd.buf;
+}
+
+// ---- bf16 ghost twins (dory_halo_bf16_ghosts) -----------------------------------------------------------------------------------
+int ghost_fp32_current(dory_ctx *c, Tensor *t) {
+    if (!t || !t->twin || t->twin_state != DORY_GHOST_TWIN) return DORY_OK;
+    { int wrc = wait_halo(c); if (wrc) return wrc; }   // (the exchange that fills the twin may still be in flight)
+    Timed tw(c, "bf16_widen", c->compute);
+    HIPCK(c, launch_widen_rows_bf16(t->d, t->twin, t->rows * t->ld, c->compute));
+    t->twin_state = DORY_GHOST_BOTH;
+    if (!c->capturing) c->ghost_widened++;
+    return DORY_OK;
+}
+
+// every ghost tensor halo_route can ever name for a model whose exchanges may ship bf16 (halo_ships_bf16: never the multi-head GAT;
+// fg@0 comes from a file), where a row has at least one 8-byte quad
+static bool ghost_gets_twin(const dory_ctx *c, uint32_t layer, const std::string &name, const Tensor &t) {
+    if (!t.owned || t.ld < 4) return false;
+    if (c->gnn == DORY_GCN) return (name == "fg" && layer >= 1) || name == "fgxw" || name == "bg" || name == "bgg";
+    return c->gnn == DORY_GAT && (name == "fg_z" || name == "bg_d");
+}
+int ghost_twins_alloc(dory_ctx *c) {
+    if (!ghosts_on(c)) return DORY_OK;
+    for (uint32_t l = 0; l < c->tensors.size(); ++l)
+        for (auto &kv : c->tensors[l]) {
+            Tensor &t = kv.second;
+            if (t.twin || !ghost_gets_twin(c, l, kv.first, t)) continue;
+            const size_t b = t.twin_bytes() ? t.twin_bytes() : 256;   // (as alloc_tensor: a valid pointer for empty ghosts)
+            HIPCK(c, hipMalloc((void **)&t.twin, b));
+            HIPCK(c, hipMemsetAsync(t.twin, 0, b, c->compute));
+            t.twin_state = DORY_GHOST_FP32;
+        }
+    return DORY_OK;
 }
 
 void scatter_free(dory_ctx *c) {
@@ -1182,6 +1263,61 @@ int dory_halo_wire_row(dory_ctx *c, uint32_t layer, int dir, uint32_t *elem_byte
     return DORY_OK;
 }
 
+// ---- bf16 ghost twins: switch, counters, and a look at one tensor's twin (include/dorylus_hip.h) ---------------------------------
+int dory_halo_bf16_ghosts(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || !c->prealloc || (on != 0 && on != 1))
+        return fail(c, DORY_ERR_ARG, "halo_bf16_ghosts: dory_configure and dory_preallocate first (the twins of the tensors are allocated here); on is 0 or 1");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_bf16_ghosts: not while an epoch graph is being recorded");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange of a direct plan that may now ship bf16)
+    if (on) {
+        c->halo_bf16_ghosts.store(1, std::memory_order_release);
+        return ghost_twins_alloc(c);
+    }
+    // off: a twin that holds the only current copy is widened first; nothing in flight reads a twin once both streams are idle
+    for (auto &m : c->tensors)
+        for (auto &kv : m) { int rc = ghost_fp32_current(c, &kv.second); if (rc) return rc; }
+    c->halo_bf16_ghosts.store(0, std::memory_order_release);
+    HIPCK(c, hipStreamSynchronize(c->comm));
+    HIPCK(c, hipStreamSynchronize(c->compute));
+    epoch_graph_drop_locked(c);   // (a recorded epoch may point at a twin)
+    for (auto &m : c->tensors)
+        for (auto &kv : m) {
+            Tensor &t = kv.second;
+            if (t.twin) (void)hipFree(t.twin);
+            t.twin = nullptr;
+            t.twin_state = DORY_GHOST_FP32;
+        }
+    return DORY_OK;
+}
+
+int dory_halo_bf16_ghosts_stats(dory_ctx *c, uint64_t *landed_direct, uint64_t *landed_by_kernel, uint64_t *conversions_skipped, uint64_t *widened,
+                                uint64_t *twin_bytes) {
+    CHECK_CTX(c);
+    if (landed_direct) *landed_direct = c->ghost_landed_direct;
+    if (landed_by_kernel) *landed_by_kernel = c->ghost_landed_by_kernel;
+    if (conversions_skipped) *conversions_skipped = c->ghost_conversions_skipped;
+    if (widened) *widened = c->ghost_widened;
+    if (twin_bytes) {
+        *twin_bytes = 0;
+        for (auto &m : c->tensors)
+            for (auto &kv : m)
+                if (kv.second.twin) *twin_bytes += kv.second.twin_bytes();
+    }
+    return DORY_OK;
+}
+
+int dory_halo_bf16_ghost_peek(dory_ctx *c, uint32_t layer, const char *name, const void **twin, int *state) {
+    CHECK_CTX(c);
+    Tensor *t = name ? find(c, layer, name) : nullptr;
+    if (!t) return fail(c, DORY_ERR_ARG, "halo_bf16_ghost_peek: no tensor '%s' at layer %u", name ? name : "(null)", layer);
+    { int wrc = wait_halo(c); if (wrc) return wrc; }   // (a deferred exchange: its rows are enqueued before the caller looks; dory_sync waits for them)
+    if (twin) *twin = t->twin;
+    if (state) *state = t->twin_state;
+    return DORY_OK;
+}
+
 // ---- scatter messages: the entry points (helpers above) ------------------------------------------------------------------
 int dory_halo_wire_ids(dory_ctx *c, const uint32_t *local_to_global, const uint32_t *src_ghost_gvids, const uint32_t *dst_ghost_gvids) {
     CHECK_CTX(c);
@@ -1320,6 +1456,7 @@ int dory_scatter_msgs_unpack(dory_ctx *c, uint32_t layer, int dir, const char *n
     const uint32_t tl = tensor_layer(c, ghost);
     if (ghost == find(c, 0, "fg")) c->ah0_valid = false;
     if (ghost == find(c, tl, "fg_z") && tl < c->gat_nsum_valid.size()) c->gat_nsum_valid[tl] = 0;
+    ghost_wrote_fp32(ghost);   // (dory_halo_bf16_ghosts: records are fp32; a round writes every ghost row)
     HIPCK(c, hipEventRecord(c->ev_a, c->compute));
     HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
     Timed t(c, "halo", c->comm);

@@ -69,8 +69,10 @@ Tensor *findw(std::vector<std::map<std::string, Tensor>> &tab, uint32_t layer, c
 
 void free_table(std::vector<std::map<std::string, Tensor>> &tab) {
     for (auto &m : tab)
-        for (auto &kv : m)
+        for (auto &kv : m) {
             if (kv.second.owned && kv.second.d) (void)hipFree(kv.second.d);
+            if (kv.second.twin) (void)hipFree(kv.second.twin);   // (dory_halo_bf16_ghosts: the bf16 twin of a ghost tensor)
+        }
     tab.clear();
 }
 
@@ -148,6 +150,8 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
         else if (fused_pack_target(c, &C, M, &sd, &send_dir)) { sent = &C; sd.which = 0; }
     }
     if (sent && (rc = wait_halo(c))) return rc;
+    ghost_wrote_fp32(&C);   // (dory_halo_bf16_ghosts: a product written into a ghost tensor -- fgxw@0 -- is fp32 rows)
+    ghost_wrote_fp32(C2);
     Timed t(c, "gemm", c->compute);
     if (!sent) {
         fused_note_write(c, &C);
@@ -636,6 +640,7 @@ int dory_preallocate(dory_ctx *c) {
         }
     }
     c->adam.epochs = 1;
+    if ((rc = ghost_twins_alloc(c))) return rc;   // (dory_halo_bf16_ghosts is on: the new ghost tensors' twins, now)
     HIPCK(c, hipStreamSynchronize(c->compute));
     auto layer_ld = [&](uint32_t l) { return pad_ld(l == L - 1 ? d[l + 1] * c->heads[l] : d[l + 1]); };   // multi-head GAT: z / o of layer l
     const uint32_t G = std::min<uint32_t>(32u, c->cus_per_xcd);
@@ -718,6 +723,8 @@ int dory_tensor_info(dory_ctx *c, uint32_t layer, const char *name, uint64_t *ro
     Tensor *t = name ? find(c, layer, name) : nullptr;
     if (!t) return fail(c, DORY_ERR_ARG, "no tensor '%s' at layer %u", name ? name : "(null)", layer);
     if (device_ptr) { int hrc = gat_edge_tensor_hook(c, layer, name, false); if (hrc) return hrc; }   // a raw pointer: the data behind it must be current
+    // (dory_halo_bf16_ghosts: ... the fp32 rows too, now and -- raw_handed -- after every later exchange)
+    if (device_ptr) { int grc = ghost_fp32_current(c, t); if (grc) return grc; }
     if (rows) *rows = t->rows;
     if (cols) *cols = t->cols;
     if (ld) *ld = t->ld;
@@ -815,6 +822,7 @@ int dory_tensor_upload(dory_ctx *c, uint32_t layer, const char *name, const floa
     fused_note_write(c, t);
     const HaloPlan *wire = nullptr;
     { int prc = ghost_wire_plan(c, "tensor_upload", name, *t, &wire); if (prc) return prc; }
+    ghost_wrote_fp32(t);   // (dory_halo_bf16_ghosts: the caller's fp32 rows are the current ones)
     return wire ? upload_ghost_wire(c, *t, host, *wire) : upload_dense(c, *t, host);
 }
 
@@ -824,6 +832,7 @@ int dory_tensor_download(dory_ctx *c, uint32_t layer, const char *name, float *h
     Tensor *t = name ? find(c, layer, name) : nullptr;
     if (!t || !host) return fail(c, DORY_ERR_ARG, "tensor_download: no tensor '%s' at layer %u", name ? name : "(null)", layer);
     { int hrc = gat_edge_tensor_hook(c, layer, name, false); if (hrc) return hrc; }
+    { int grc = ghost_fp32_current(c, t); if (grc) return grc; }   // (dory_halo_bf16_ghosts: a twin that alone is current is widened first)
     const HaloPlan *wire = nullptr;
     { int prc = ghost_wire_plan(c, "tensor_download", name, *t, &wire); if (prc) return prc; }
     return wire ? download_ghost_wire(c, *t, host, *wire) : download_dense(c, *t, host);
@@ -845,6 +854,7 @@ int dory_tensor_fill_uniform(dory_ctx *c, uint32_t layer, const char *name, uint
     uint32_t *ids = nullptr;
     const HaloPlan *wire = nullptr;
     { int prc = ghost_wire_plan(c, "tensor_fill", name, *t, &wire); if (prc) return prc; }
+    ghost_wrote_fp32(t);   // (dory_halo_bf16_ghosts: as dory_tensor_upload)
     if (wire) {   // option halo_direct_recv: stored row r is the caller's row order[r] -- it gets that row's values
         std::vector<uint32_t> wids(t->rows);
         for (uint64_t r = 0; r < t->rows; ++r) wids[r] = global_row_ids ? global_row_ids[wire->order[r]] : wire->order[r];

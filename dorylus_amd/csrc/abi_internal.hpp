@@ -124,6 +124,14 @@ void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &s
 inline void fused_stamp_drop(dory_ctx *c) { c->fused_stamp = FusedStamp(); }
 // something other than a fusing GEMM writes `t` (may be null): a stamp that names it no longer describes its rows
 inline void fused_note_write(dory_ctx *c, const Tensor *t) { if (t && c->fused_stamp.src == t) fused_stamp_drop(c); }
+// bf16 ghost twins (dory_halo_bf16_ghosts; abi_comm.hip).  ghost_fp32_current: somebody is about to read the fp32 rows of `t` (may be
+// null) -- where only its twin is current (DORY_GHOST_TWIN) the exchange in flight is waited for and the twin widened into the fp32
+// rows on the compute stream (then DORY_GHOST_BOTH, counted); anything else: nothing.  ghost_wrote_fp32: fp32 rows have been written
+// into `t`, all of them.  ghost_twins_alloc: with the switch on, a twin for every tensor the rule of dory_halo_bf16_rows can cover
+// that has none yet (GCN: fg of layers >= 1, fgxw, bg, bgg; GAT prototype: fg_z, bg_d; ld >= 4) -- never inside an epoch.
+int ghost_fp32_current(dory_ctx *c, Tensor *t);
+inline void ghost_wrote_fp32(Tensor *t) { if (t) t->twin_state = DORY_GHOST_FP32; }
+int ghost_twins_alloc(dory_ctx *c);
 // scatter messages (abi_comm.hip): everything dory_ctx::scatter owns, at dory_destroy
 void scatter_free(dory_ctx *c);
 // K1b bookkeeping (abi_stages.hip)

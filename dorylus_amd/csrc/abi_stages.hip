@@ -135,16 +135,23 @@ struct Bf16Rows {
     dory_ctx *c = nullptr;
     const Tensor *ghost = nullptr;
     const float *xl = nullptr, *xg = nullptr;   // bf16 rows of ld elements; xg == nullptr: no ghost rows
+    // dory_halo_bf16_ghosts: where the ghost tensor's bf16 twin is current (the exchange landed its rows there) the ghost rows are
+    // the twin itself -- only the N local rows are reserved and converted, ghosts_landed() has nothing to do (counted).  Not for a
+    // tensor whose raw pointer is out: the caller may have written its fp32 rows since (they are kept current: state BOTH), so those
+    // are converted as ever
     int begin(dory_ctx *ctx, const Tensor &rows, const Tensor *ghost_rows, uint64_t nghost, const char *option) {
         Tensor local = rows;
         local.rows = ctx->N;
-        int rc = bf16_reserve(ctx, (uint64_t)ctx->N + nghost, rows.ld, option);
+        const bool twin = nghost && ghost_rows->twin_current() && !ghost_rows->raw_handed;
+        int rc = bf16_reserve(ctx, (uint64_t)ctx->N + (twin ? 0 : nghost), rows.ld, option);
         if (!rc) rc = bf16_convert(ctx, local, 0);
         if (rc) return rc;
         c = ctx;
-        ghost = nghost ? ghost_rows : nullptr;
+        ghost = nghost && !twin ? ghost_rows : nullptr;
         xl = reinterpret_cast<const float *>(c->bf16_rows);
-        xg = nghost ? reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * rows.ld) : nullptr;
+        xg = !nghost ? nullptr : twin ? reinterpret_cast<const float *>(ghost_rows->twin)
+                                      : reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * rows.ld);
+        if (twin && !c->capturing) c->ghost_conversions_skipped++;
         return DORY_OK;
     }
     bool on() const { return c != nullptr; }
@@ -377,6 +384,9 @@ static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tens
     if (bf16 && ((row_scale && c->gnn != DORY_GAT) || xl.rows < c->N))
         return fail(c, DORY_ERR_ARG, "spmm: bf16 rows need edge weights (but on a GAT context) and N rows");
     c->last_spmm_unit = false;
+    // dory_halo_bf16_ghosts: an aggregation on fp32 rows of a ghost tensor whose twin alone is current (the gather mode changed after
+    // the exchange) gets the twin widened first; one on bf16 rows reads the twin itself (Bf16Rows::begin)
+    if (!bf16 && xg && xg->rows) { int grc = ghost_fp32_current(c, xg); if (grc) return grc; }
     SpmmArgs a{};
     a.N = c->N; a.F = F; a.ld = xl.ld;
     a.ptr = A.ptr;
@@ -430,6 +440,7 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
             if (layer == 0) {   // the input and its ghost rows are static: transform both here
                 Tensor &W = c->weights[0]["w"];
                 int rc = gemm(c, 0, 0, c->N, c->dims[1], c->dims[0], *in, W, *xw);
+                if (!rc && In.ghosts) rc = ghost_fp32_current(c, fg);   // (dory_halo_bf16_ghosts: the GEMM reads fp32 rows; fg@0 has no twin today)
                 if (!rc && In.ghosts) rc = gemm(c, 0, 0, In.ghosts, c->dims[1], c->dims[0], *fg, W, *fgxw);
                 if (rc) return rc;
             }   // deeper layers: apply_vertex(l-1) left xw@l, the forward exchange of layer l its ghost rows

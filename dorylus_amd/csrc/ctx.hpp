@@ -28,7 +28,14 @@ struct Tensor {
     float *d = nullptr;
     bool owned = true;  // false: alias of another allocation (GAT "A" = csc values)
     bool raw_handed = false;   // dory_tensor_info has handed out its device pointer: never the target of a fused halo pack again
+    // dory_halo_bf16_ghosts: the bf16 twin of a ghost tensor -- rows x ld bf16 in the tensor's own row order, allocated by the
+    // setter / dory_preallocate, freed with the tensor (free_table) -- and which of the two copies holds the current rows
+    // (DORY_GHOST_FP32 / _TWIN / _BOTH).  null: no twin (every other tensor; one-column ghost tensors): always DORY_GHOST_FP32.
+    uint16_t *twin = nullptr;
+    int twin_state = DORY_GHOST_FP32;
     size_t bytes() const { return (size_t)rows * ld * sizeof(float); }
+    size_t twin_bytes() const { return (size_t)rows * ld * sizeof(uint16_t); }
+    bool twin_current() const { return twin && twin_state != DORY_GHOST_FP32; }
 };
 
 inline uint32_t pad_ld(uint32_t cols) { return cols <= 1 ? cols : (cols + 31u) & ~31u; }
@@ -317,6 +324,12 @@ struct dory_ctx {
     // eager packs counted: those that wrote bf16 rows, their bytes, those that wrote fp32 rows while the switch was on
     std::atomic<int> halo_bf16{0}, gcn_bf16_mode{0}, gat_bf16_mode_pub{0};
     uint64_t halo_bf16_packs = 0, halo_bf16_bytes = 0, halo_fp32_packs_while_on = 0;
+    // bf16 ghost twins (dory_halo_bf16_ghosts; default off: a copy the peers of the local transport may read without this context's
+    // lock) and the eager calls counted: exchanges / unpacks whose bf16 rows landed in a twin itself, those a kernel copied into one,
+    // aggregations on bf16 rows that read a twin instead of converting the ghost rows, twins widened into their fp32 tensor for a reader
+    // of fp32 rows
+    std::atomic<int> halo_bf16_ghosts{0};
+    uint64_t ghost_landed_direct = 0, ghost_landed_by_kernel = 0, ghost_conversions_skipped = 0, ghost_widened = 0;
     dory::ScatterState scatter;  // scatter messages (dory_scatter_msgs_*) and the scatter transport
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
@@ -338,10 +351,13 @@ struct dory_ctx {
     struct LocalPending {                           // second half of a deferred exchange (wait for the peers' rows, unpack)
         bool on = false;
         int dir = 0;
-        float *ghost = nullptr;
+        char *ghost = nullptr;                      // where the rows land: the ghost tensor's fp32 rows, or (keep) its bf16 twin
         uint32_t ghost_ld = 0;
         dory::RowWire wire;                         // what the rows in recv_buf look like (exact: the unpack zeroes [w, ghost_ld))
-        bool direct = false;                        // halo_direct_recv and w == ghost_ld: the peers' segments are copied into the ghost tensor itself
+        bool direct = false;                        // halo_direct_recv and w == ghost_ld: the peers' segments are copied into the ghost tensor (or twin) itself
+        bool keep = false;                          // dory_halo_bf16_ghosts: bf16 rows stay bf16, in the twin
+        float *widen_to = nullptr;                  // ... and are widened into these fp32 rows at once (the tensor's raw pointer is out)
+        uint64_t ghost_rows = 0;
         hipEvent_t t_halo_b = nullptr, t_kind_b = nullptr;   // timing: end events of the "halo" / "halo_deferred|waited" intervals
     } local_pending;
     std::vector<char> local_sent_to;  // halo_direct_recv: the peers that read my send buffer in the last exchange (they pull; I pack again after their "consumed")
@@ -656,6 +672,13 @@ hipError_t launch_gather_rows_bf16(void *dst, const float *src, uint32_t ld, uin
                                    const uint32_t *rows, uint32_t n, hipStream_t s);
 hipError_t launch_scatter_rows_bf16(float *dst, const void *src, uint32_t ld, uint32_t row_elems,
                                     const uint32_t *rows, uint32_t n, hipStream_t s);
+// dory_halo_bf16_ghosts: the received bf16 rows stay bf16.  The keep form of the scatter copies row i of the stream (row_elems bf16, a
+// multiple of 4, 8-byte aligned) into row rows[i] of a bf16 twin at stride ld (a multiple of 32: rows of whole 64 bytes), zeros in
+// [row_elems, ld) -- the bits rounding the fp32 row launch_scatter_rows_bf16 leaves would give.  The widening is dense: all rows x ld
+// elements of a twin into the fp32 tensor of the same shape (n: elements, a multiple of 8; both 16-byte aligned).
+hipError_t launch_scatter_rows_bf16_keep(uint16_t *dst, const void *src, uint32_t ld, uint32_t row_elems,
+                                         const uint32_t *rows, uint32_t n, hipStream_t s);
+hipError_t launch_widen_rows_bf16(float *dst, const uint16_t *src, uint64_t n, hipStream_t s);
 // option halo_direct_recv: whole ld-wide rows (any ld) between the caller-visible order of a ghost tensor and its stored (wire)
 // order, off the epoch's path -- to_wire: dst[i] = src[order[i]] (upload), else dst[order[i]] = src[i] (download)
 hipError_t launch_permute_rows(float *dst, const float *src, uint32_t ld, const uint32_t *order, uint32_t n, bool to_wire, hipStream_t s);

@@ -821,6 +821,66 @@ hipError_t launch_scatter_rows_bf16(float *dst, const void *src, uint32_t ld, ui
     return hipGetLastError();
 }
 
+// ---- K6, bf16 ghost twins (dory_halo_bf16_ghosts) --------------------------------------------------------------------------------
+// keep: the received bf16 rows stay bf16 -- row r of the stream (re4 quads of 8 bytes) goes to row rows[r] of the twin (stride ld, a
+// multiple of 32 elements: rows of whole 64 bytes, 16-byte aligned), zeros in [4 x re4, ld): the bits rounding the fp32 row that
+// scatter_rows_bf16_kernel leaves would give (widening and rounding a bf16 cancel), whatever the twin held before.  A lane owns LE
+// elements of a twin row.  LE == 8: one 16-byte chunk, filled from two 8-byte quads of the stream (rows of the stream are 8-byte
+// aligned only), either of which may lie behind the stream's row; one 16-byte store.  LE == 4: one quad, one 8-byte load (or zeros),
+// one 8-byte store.  The launcher instantiates LE == 4: measured 4-10 % faster than LE == 8 at every shape (3.15 M rows; stand-alone
+// copies of both in tools/probes/halo_bf16_keep_forms.hip, numbers in profiles/HISTORY.md section 21) -- as with the widening unpack.
+template <int LE>
+__global__ __launch_bounds__(256) void scatter_rows_bf16_keep_kernel(uint16_t *dst, const uint2 *src, uint32_t ld, uint32_t re4,
+                                                                     const uint32_t *rows, uint32_t n) {
+    static_assert(LE == 4 || LE == 8, "a lane owns one 8-byte quad or one 16-byte chunk");
+    const uint32_t per_row = ld / LE;
+    const uint64_t total = (uint64_t)n * per_row;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / per_row);
+        const uint32_t k = (uint32_t)(i % per_row);
+        const uint2 *in = src + (uint64_t)r * re4;
+        uint16_t *out = dst + (size_t)rows[r] * ld;
+        if (LE == 8) {
+            const uint32_t q = 2u * k;
+            const uint2 a = q < re4 ? in[q] : make_uint2(0u, 0u);
+            const uint2 b = q + 1u < re4 ? in[q + 1u] : make_uint2(0u, 0u);
+            reinterpret_cast<uint4 *>(out)[k] = make_uint4(a.x, a.y, b.x, b.y);
+        } else {
+            reinterpret_cast<uint2 *>(out)[k] = k < re4 ? in[k] : make_uint2(0u, 0u);
+        }
+    }
+}
+// widen: a whole twin into its fp32 tensor, dense (row r to row r, every one of the ld elements): a lane reads 8 bf16 (16 bytes) and
+// stores two float4 -- a bf16 is the high half of the fp32 with the same value
+__global__ __launch_bounds__(256) void widen_rows_bf16_kernel(float4 *dst, const uint4 *src, uint64_t n8) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint4 u = src[i];
+        dst[2 * i] = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
+                                 __uint_as_float(u.y & 0xFFFF0000u));
+        dst[2 * i + 1] = make_float4(__uint_as_float(u.z << 16), __uint_as_float(u.z & 0xFFFF0000u), __uint_as_float(u.w << 16),
+                                     __uint_as_float(u.w & 0xFFFF0000u));
+    }
+}
+
+hipError_t launch_scatter_rows_bf16_keep(uint16_t *dst, const void *src, uint32_t ld, uint32_t row_elems,
+                                         const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || ld == 0) return hipSuccess;
+    if ((ld & 31) || (row_elems & 3) || row_elems > ld || ((uintptr_t)src & 7) || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+    constexpr int LE = 4;   // (the lane form in use: the faster of the two)
+    const uint64_t total = (uint64_t)n * (ld / LE);
+    int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(scatter_rows_bf16_keep_kernel<LE>, dim3(blocks), dim3(256), 0, s, dst, static_cast<const uint2 *>(src), ld, row_elems / 4, rows, n);
+    return hipGetLastError();
+}
+hipError_t launch_widen_rows_bf16(float *dst, const uint16_t *src, uint64_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((n & 7) || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+    const uint64_t n8 = n / 8;
+    hipLaunchKernelGGL(widen_rows_bf16_kernel, dim3((uint32_t)std::min<uint64_t>(8192, (n8 + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<float4 *>(dst), reinterpret_cast<const uint4 *>(src), n8);
+    return hipGetLastError();
+}
+
 // ---- option halo_direct_recv: a ghost tensor between its caller-visible and its stored (wire) order ------------------------
 // Whole ld-wide rows, a dword per thread (ld may be 1: the per-head tensors of a single head), `order` a permutation of
 // [0, n).  Off the epoch's path: dory_tensor_upload / dory_tensor_download of a ghost tensor only.

@@ -282,7 +282,8 @@ int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide,
  * (the multi-head GAT's finishing kernels and blocked forms read fg_z in fp32, and it exchanges do / st itself).
  * Not taken, i.e. fp32 rows travel as without the switch, the results are the same and the pack is counted in
  * fp32_packs_while_on: the rule says no; the scatter-message transport (the reference's format); a plan made with
- * halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer);
+ * halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer) -- unless
+ * dory_halo_bf16_ghosts (below) gives the rows a bf16 tensor to land in;
  * dory_halo_pack_tensor / dory_halo_unpack_tensor (the consumer is unknown).  dory_halo_pack / dory_halo_unpack follow the rule
  * as they follow halo_exact_rows: the caller's buffer (8-byte aligned) then holds rows x row_elems x 2 bytes.  The fused halo
  * pack never serves an exchange that ships bf16 (no GEMM stores fp32 rows nobody sends; its statistics count a fallback).
@@ -320,6 +321,62 @@ int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide,
 int dory_halo_bf16_rows(dory_ctx *ctx, int on);
 int dory_halo_bf16_rows_stats(dory_ctx *ctx, uint64_t *bf16_packs, uint64_t *bf16_bytes, uint64_t *fp32_packs_while_on);
 int dory_halo_wire_row(dory_ctx *ctx, uint32_t layer, int dir, uint32_t *elem_bytes, uint32_t *row_elems);
+
+/* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
+ * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
+ * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels
+ * for a 128-float row, the second one on the compute stream between the wait for the exchange and the ghost-block launch.  With
+ * this second switch on too, every ghost tensor the rule above can ever cover has a bf16 TWIN -- rows x ld bf16 in the tensor's own
+ * row order (wire order under halo_direct_recv), owned by the tensor -- the received rows stay bf16 in it, and the aggregation on
+ * bf16 rows gathers its ghost rows from it: no widening, no conversion of ghost rows (the N local rows are converted as ever).
+ * Twins: GCN fg of layers >= 1, fgxw, bg, bgg; GAT prototype fg_z, bg_d; never the multi-head GAT; never a tensor of ld < 4 (one
+ * column: as without the switch).  Allocated by the setter for the tensors that exist (it needs dory_preallocate: DORY_ERR_ARG
+ * before it) and by dory_preallocate while the switch is on; never inside an exchange or an aggregation; freed with the tensor, or
+ * by on = 0 after any twin that holds the only current copy has been widened.
+ * Every such tensor has a state, which dory_halo_bf16_ghost_peek reports next to the twin's device pointer (NULL: no twin):
+ * DORY_GHOST_FP32 only the fp32 rows are current, DORY_GHOST_TWIN only the twin is, DORY_GHOST_BOTH both are.
+ * The exchange.  The wire is what dory_halo_bf16_rows makes it (same rule, same row_elems), with one addition: a plan made with
+ * halo_direct_recv = 1 now ships bf16 too where the tensor has ld >= 4 -- dory_halo_wire_row says so; in-process ranks that
+ * disagree on what they would ship fail at once with DORY_ERR_COMM as above; over RCCL and host transports EVERY RANK MUST SET THE
+ * SAME.  On arrival, where the wire is bf16 and the tensor has a twin:
+ *   - a direct plan and row_elems == ld: the rows land in the twin itself (ncclRecv target, the host transport's H2D copy, the
+ *     in-process pull); no kernel, no receive buffer; counted in landed_direct and in the read-only key halo_direct_recvs;
+ *   - anything else (a plan that is not direct; exact rows narrower than ld, e.g. 41 -> 44 elements in an ld of 64): receive
+ *     buffer, then one kernel copies the bf16 rows into the twin rows the plan names, zeros in [row_elems, ld) whatever the twin
+ *     held -- the bits rounding today's fp32 ghost row would give; counted in landed_by_kernel.  Under a direct plan that buffer
+ *     exists only if halo_exact_rows was 1 before dory_halo_plan (the refusal of halo_direct_recv, unchanged).
+ * State afterwards: TWIN; or, for a tensor whose raw pointer dory_tensor_info has handed out, the fp32 rows are widened behind the
+ * twin at once on the comm stream and the state is BOTH (the caller reads fp32 rows behind the library's back and keeps seeing
+ * them; an aggregation on bf16 rows of such a tensor converts its fp32 rows as ever -- the caller may have written them).
+ * dory_halo_unpack follows the same rule (its kernel always copies: landed_by_kernel).  Everything else that writes a ghost tensor
+ * writes fp32 rows and sets FP32: an exchange that ships fp32, dory_halo_unpack_tensor, the scatter messages,
+ * dory_tensor_upload, dory_tensor_fill_uniform.
+ * The readers.  An aggregation on bf16 rows whose ghost tensor is TWIN or BOTH reads the twin (conversions_skipped); in state FP32
+ * everything is as without the switch (layer 0's file-loaded fg always).  Whoever reads fp32 rows -- an aggregation on fp32 rows
+ * (the gather mode changed after the exchange), dory_tensor_download, dory_tensor_info handing out the device pointer -- finds a
+ * TWIN tensor widened first: the exchange is waited for, one dense kernel on the compute stream writes all rows x ld floats
+ * (bits << 16), the state becomes BOTH, `widened` counts it.  Visible contract: that of dory_halo_bf16_rows -- a download of fg /
+ * fgxw / bg / bgg / fg_z / bg_d shows the owner's rows rounded to bf16, zeros in [cols, ld); every local tensor, weight and gradient
+ * keeps its bits.  With dory_halo_bf16_rows off, or where its rule says fp32, this switch changes nothing and no twin is written.
+ * dory_halo_bf16_ghosts: on = 0 (default) / 1, after dory_preallocate, outside an exchange; DORY_ERR_ARG for other values, before
+ * dory_preallocate, or while an epoch graph is being recorded (which more than one partition never is).
+ * dory_halo_bf16_ghosts_stats: eager calls since dory_create -- exchanges / unpacks that landed in a twin itself, that a kernel
+ * copied into one, aggregations that read a twin, widenings -- and the bytes of all twins now; any pointer may be NULL.
+ * Kernels (csrc/elementwise.hip): scatter_rows_bf16_keep_kernel, a lane per 8-byte quad of a twin row (one 8-byte load or zeros,
+ * one 8-byte store) -- chosen by measurement over a lane per 16-byte chunk (two 8-byte loads, one 16-byte store), which is 4-10 %
+ * SLOWER at every measured shape -- and widen_rows_bf16_kernel (one 16-byte load, two 16-byte stores); no LDS, no scratch.
+ * Measured on one MI355X (profiles/r20_halo_bf16_ghosts.txt, profiles/HISTORY.md section 21), 3.15 M ghost rows, switch off / on
+ * alternated: unpack, widening -> keep, 0.221 -> 0.150 ms (64 floats), 1.153 -> 0.803 (300), 1.131 -> 0.745 (300 exact), 0.455 -> 0.308
+ * (128), 0.216 -> 0.148 / 0.207 -> 0.129 (48 padded / exact), 0.214 -> 0.147 / 0.207 -> 0.127 (41): faster at every measured shape.  In the
+ * in-process-transport epoch (200 000 vertices, 4 M edges, 128-128-16, gather mode 2) the ghost half of the timing key bf16_convert is
+ * gone (launches 600 -> 400 per 50 epochs at P = 2, 1200 -> 800 at P = 4) and the epoch stays inside its run-to-run spread, direct 0
+ * and 1; with both switches off the headline and the GAT prototype epoch are at the parent's level (one headline reading of seven
+ * 0.5 % above the parent's highest of its session).  NO RCCL CALL WITH MORE THAN ONE RANK HAS RUN AND NO LINK IS MEASURED. */
+enum { DORY_GHOST_FP32 = 0, DORY_GHOST_TWIN = 1, DORY_GHOST_BOTH = 2 };
+int dory_halo_bf16_ghosts(dory_ctx *ctx, int on);
+int dory_halo_bf16_ghosts_stats(dory_ctx *ctx, uint64_t *landed_direct, uint64_t *landed_by_kernel, uint64_t *conversions_skipped,
+                                uint64_t *widened, uint64_t *twin_bytes);
+int dory_halo_bf16_ghost_peek(dory_ctx *ctx, uint32_t layer, const char *name, const void **twin, int *state);
 
 /* ---- scatter messages: the reference's own graph-server <-> graph-server wire, packed and unpacked on the device ----------
  * What Engine::verticesPushOut puts on a socket and ghostReceiver* takes apart (include/dorylus_wire.h: the format table with

@@ -16,7 +16,9 @@ A/B runs: --opt KEY=VALUE (repeatable) sets a context option on every rank befor
 --configs NAME... keeps only those configurations, --skip-oracle leaves the CPU oracle's epoch out; DORY_LIB_PATH picks the
 library.  Each run then also records every rank's receive-buffer bytes where the library reports them.  --fused-pack switches
 dory_halo_fused_pack on on every rank and records its counters (exchanges fused, their rows, fallbacks) per rank; --bf16-rows switches
-dory_halo_bf16_rows on on every rank (with --opt gcn_bf16_gather=1 or 2) and records its counters (bf16 packs, their bytes, fp32 packs)."""
+dory_halo_bf16_rows on on every rank (with --opt gcn_bf16_gather=1 or 2) and records its counters (bf16 packs, their bytes, fp32 packs);
+--bf16-ghosts switches dory_halo_bf16_ghosts on on top of it and records its counters per rank; with either, the timing key
+"bf16_convert" (the conversions of the aggregations on bf16 rows: ms and launches, summed over the ranks) is recorded too."""
 import argparse
 import json
 import os
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--skip-oracle", action="store_true")
     ap.add_argument("--fused-pack", action="store_true", help="dory_halo_fused_pack(1) on every rank")
     ap.add_argument("--bf16-rows", action="store_true", help="dory_halo_bf16_rows(1) on every rank")
+    ap.add_argument("--bf16-ghosts", action="store_true", help="dory_halo_bf16_ghosts(1) on every rank (with --bf16-rows)")
     a = ap.parse_args()
     import torch  # noqa: F401
     import dorylus_amd as da
@@ -54,7 +57,7 @@ def main():
     Ws = [(rng.standard_normal((dims[i], dims[i + 1])) / np.sqrt(dims[i])).astype(np.float32) for i in range(L)]
 
     extra = {k: int(v) for k, v in (kv.split("=", 1) for kv in a.opt)}
-    recv_bytes, fused_stats, bf16_stats = {}, {}, {}
+    recv_bytes, fused_stats, bf16_stats, ghost_stats, convert = {}, {}, {}, {}, {}
 
     def setup(ctx, r, g):
         close = ctx.close
@@ -69,12 +72,17 @@ def main():
                     fused_stats[r] = list(ctx.halo_fused_pack_stats())
                 if a.bf16_rows:
                     bf16_stats[r] = list(ctx.halo_bf16_rows_stats())
+                    convert[r] = ctx.timing_get("bf16_convert")
+                if a.bf16_ghosts:
+                    ghost_stats[r] = ctx.halo_bf16_ghosts_stats()
             close()
         ctx.close = closing
         if a.fused_pack:
             ctx.halo_fused_pack(1)
         if a.bf16_rows:
             ctx.halo_bf16_rows(1)
+        if a.bf16_ghosts:
+            ctx.halo_bf16_ghosts(1)
         if g["localVtxCnt"]:
             ctx.upload(0, "x", X[g["localToGlobal"]])
         if g["srcGhostCnt"]:
@@ -105,7 +113,7 @@ def main():
         configs = [c for c in configs if c[0] in a.configs]
     with_extra = lambda sh: [dict(x, **extra) for x in sh] if isinstance(sh, list) else dict(sh, **extra)
     configs = [(name, P, parts, with_extra(share)) for name, P, parts, share in configs]
-    out["options"] = dict(extra, fused_pack=int(a.fused_pack), bf16_rows=int(a.bf16_rows))
+    out["options"] = dict(extra, fused_pack=int(a.fused_pack), bf16_rows=int(a.bf16_rows), bf16_ghosts=int(a.bf16_ghosts))
     for name, P, parts, share in ([] if a.skip_oracle else [c for c in configs if c[0] == "balanced"]):
         pobjs = [da.Partition.build(src, dst, parts, r, P) for r in range(P)]
         dl = [(l, nm) for l in range(L) for nm in ("ah",)] + [(l, nm) for l in range(L - 1) for nm in ("h", "aTg")] + [(l, "grad") for l in range(1, L)]
@@ -140,7 +148,10 @@ def main():
                    "halo_overlap_fraction": round(tm["halo_hidden"]["ms"] / tm["halo_deferred"]["ms"], 4) if tm["halo_deferred"]["ms"] else None,
                    "spmm_gates": res["gates"], "recv_buf_bytes_per_rank": [recv_bytes.get(r) for r in range(P)],
                    "fused_pack_stats_per_rank": [fused_stats.get(r) for r in range(P)] if a.fused_pack else None,
-                   "bf16_rows_stats_per_rank": [bf16_stats.get(r) for r in range(P)] if a.bf16_rows else None, "wall_s": round(wall, 2)}
+                   "bf16_rows_stats_per_rank": [bf16_stats.get(r) for r in range(P)] if a.bf16_rows else None,
+                   "bf16_ghosts_stats_per_rank": [ghost_stats.get(r) for r in range(P)] if a.bf16_ghosts else None,
+                   "bf16_convert_sum_over_ranks": {"ms": round(sum(convert[r][0] for r in range(P)), 4), "launches": sum(convert[r][1] for r in range(P))} if a.bf16_rows else None,
+                   "wall_s": round(wall, 2)}
             out["runs"].append(rec)
             bits[overlap] = res
             sys.stderr.write(json.dumps({k: rec[k] for k in ("config", "P", "halo_overlap", "epoch_ms_median_max_rank", "halo_overlap_fraction", "spmm_gates")}) + "\n")
