@@ -32,6 +32,7 @@ SYMBOLS = [
     "dory_gat_bf16_gather", "dory_gat_bf16_gather_stats",
     "dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row",
     "dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek",
+    "dory_halo_fused_pack_bf16", "dory_halo_fused_pack_bf16_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -130,6 +131,8 @@ def load():
         "dory_halo_bf16_ghosts": [vp, i32],
         "dory_halo_bf16_ghosts_stats": [vp] + [C.POINTER(u64)] * 5,
         "dory_halo_bf16_ghost_peek": [vp, u32, cp, C.POINTER(vp), C.POINTER(i32)],
+        "dory_halo_fused_pack_bf16": [vp, i32],
+        "dory_halo_fused_pack_bf16_stats": [vp, C.POINTER(u64), C.POINTER(u64)],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -165,7 +168,7 @@ def load():
                 or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
                 or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")
                 or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins)
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -575,6 +578,17 @@ class Context:
         a, b, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._ck(self.lib.dory_halo_fused_pack_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
         return a.value, b.value, f.value
+
+    def halo_fused_pack_bf16(self, on=True):
+        """the fused halo pack also serves exchanges that ship bf16 rows: the GEMM epilogues round and write them (opt-in on top of
+        halo_fused_pack and halo_bf16_rows; dory_halo_fused_pack_bf16)"""
+        self._ck(self.lib.dory_halo_fused_pack_bf16(self.h, int(on)))
+
+    def halo_fused_pack_bf16_stats(self):
+        """(exchanges whose bf16 send rows a GEMM epilogue wrote, the send rows of those)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.dory_halo_fused_pack_bf16_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

@@ -65,16 +65,24 @@ const char *const NO_RECV_BUF = "halo_direct_recv: this exchange needs the recei
 // (zeros behind the tensor's cols): multiples of 8 bytes, in a buffer aligned to 8.
 inline uint32_t wire_width(const dory_ctx *c, const Tensor *rows) { return halo_exact(c) ? rows->cols : rows->ld; }
 bool wire_bf16(const dory_ctx *c, int dir, uint32_t ld);
+// the shape alone, without the checks of a buffer: what row_wire fills in and what fused_pack_target sizes the send rows by
+inline RowWire wire_shape(const dory_ctx *c, const Tensor *rows, int rule_dir) {
+    RowWire out;
+    out.exact = halo_exact(c);
+    out.w = wire_width(c, rows);
+    out.bf16 = rule_dir >= 0 && wire_bf16(c, rule_dir, rows->ld);
+    if (out.bf16) {
+        out.cols = rows->cols;
+        out.w = (out.w + 3u) & ~3u;
+    }
+    return out;
+}
 int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghost, bool pack, const void *buf, int rule_dir, RowWire *out) {
     const Tensor *rows = pack ? src : ghost;
-    out->exact = halo_exact(c);
-    if (out->exact && src && ghost && src->cols != ghost->cols)
+    if (halo_exact(c) && src && ghost && src->cols != ghost->cols)
         return fail(c, DORY_ERR_ARG, "%s: widths of source (%u) and ghost tensor (%u) differ", who, src->cols, ghost->cols);
-    out->w = wire_width(c, rows);
-    out->bf16 = rule_dir >= 0 && wire_bf16(c, rule_dir, rows->ld);
+    *out = wire_shape(c, rows, rule_dir);
     if (out->bf16) {
-        out->cols = rows->cols;
-        out->w = (out->w + 3u) & ~3u;
         if ((uintptr_t)buf & 7) return fail(c, DORY_ERR_ARG, "%s: dory_halo_bf16_rows needs an 8-byte aligned buffer", who);
         return DORY_OK;
     }
@@ -103,16 +111,27 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
     return DORY_OK;
 }
 // The send rows of an exchange into c->send_buf.  The fused halo pack: they are there already when the stamp names this source,
-// direction, width and buffer -- the producer's epilogue wrote them -- and then no kernel runs and the stamp is consumed; with the
+// direction, element kind (dory_halo_fused_pack_bf16: and the columns that hold values), width and buffer as the wire of this moment
+// has them -- the producer's epilogue wrote them -- and then no kernel runs and the stamp is consumed; with the
 // feature on every other exchange is a counted fallback (`may_fuse` false: an arm that never takes them, section "not taken" of
 // dorylus_hip.h).
 int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloPlan &p, hipStream_t s, bool may_fuse) {
     if (c->fused_pack) {
         const FusedStamp &st = c->fused_stamp;
-        if (may_fuse && !wire.bf16 && st.src == src && st.dir == dir && st.w == wire.w && st.buf == c->send_buf) {   // (a stamp holds fp32 rows)
+        if (may_fuse && st.src == src && st.dir == dir && st.bf16 == wire.bf16 && (!wire.bf16 || st.cols == wire.cols) && st.w == wire.w &&
+            st.buf == c->send_buf) {
             fused_stamp_drop(c);
-            if (!c->capturing) { c->fused_exchanges++; c->fused_rows += p.send_total; }
-            fp32_while_on(c);
+            if (!c->capturing) {
+                c->fused_exchanges++;
+                c->fused_rows += p.send_total;
+                if (wire.bf16) {   // (what travelled as bf16 is counted as for a pack: a foreign transport sizes by it)
+                    c->fused_bf16_exchanges++;
+                    c->fused_bf16_rows += p.send_total;
+                    c->halo_bf16_packs++;
+                    c->halo_bf16_bytes += (uint64_t)p.send_total * wire.row_bytes();
+                }
+            }
+            if (!wire.bf16) fp32_while_on(c);
             return DORY_OK;
         }
         if (!c->capturing) c->fallback_exchanges++;
@@ -890,13 +909,16 @@ bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd,
         for (uint32_t layer = 0; layer <= c->L; ++layer) {
             Tensor *src, *ghost;
             if (!halo_route(c, layer, d, &src, &ghost) || src != out || !ghost) continue;
-            if (wire_bf16(c, d, out->ld)) return false;   // (dory_halo_bf16_rows: the pack kernel rounds the rows; no GEMM stores fp32 rows nobody sends)
-            const uint32_t w = wire_width(c, out);
-            if ((size_t)p.send_total * w * sizeof(float) > c->send_cap) return false;   // (the exchange would regrow the buffer)
+            const RowWire wire = wire_shape(c, out, d);
+            // dory_halo_bf16_rows: the pack kernel rounds the rows (no GEMM stores fp32 rows nobody sends) -- unless
+            // dory_halo_fused_pack_bf16 has the epilogue round them; a wire row wider than the tensor's (one column, ld == 1) packs
+            if (wire.bf16 && (!c->fused_pack_bf16 || wire.w > out->ld)) return false;
+            if ((size_t)p.send_total * wire.row_bytes() > c->send_cap) return false;   // (the exchange would regrow the buffer)
             sd->buf = c->send_buf;
             sd->row_ptr = p.d_send_map;
             sd->row_slots = p.d_send_map + c->N + 1;
-            sd->w = w;
+            sd->w = wire.w;
+            sd->bf16 = wire.bf16 ? 1u : 0u;
             *dir = d;
             return true;
         }
@@ -908,6 +930,8 @@ void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &s
     c->fused_stamp.dir = dir;
     c->fused_stamp.w = sd.w;
     c->fused_stamp.buf = sd.buf;
+    c->fused_stamp.bf16 = sd.bf16 != 0;
+    c->fused_stamp.cols = sd.bf16 ? sd.cols : 0;
 }
 
 // ---- bf16 ghost twins (dory_halo_bf16_ghosts) -----------------------------------------------------------------------------------
@@ -1227,6 +1251,24 @@ int dory_halo_fused_pack_stats(dory_ctx *c, uint64_t *fused_exchanges, uint64_t 
     if (fused_exchanges) *fused_exchanges = c->fused_exchanges;
     if (fused_rows) *fused_rows = c->fused_rows;
     if (fallback_exchanges) *fallback_exchanges = c->fallback_exchanges;
+    return DORY_OK;
+}
+
+// dory_halo_fused_pack_bf16: the fused pack also serves the exchanges that ship bf16 rows (K2's send16 kernels)
+int dory_halo_fused_pack_bf16(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_fused_pack_bf16: dory_configure first; on is 0 or 1");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_fused_pack_bf16: not while an epoch graph is being recorded");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    fused_stamp_drop(c);
+    c->fused_pack_bf16 = on == 1;
+    return DORY_OK;
+}
+
+int dory_halo_fused_pack_bf16_stats(dory_ctx *c, uint64_t *fused_bf16_exchanges, uint64_t *fused_bf16_rows) {
+    CHECK_CTX(c);
+    if (fused_bf16_exchanges) *fused_bf16_exchanges = c->fused_bf16_exchanges;
+    if (fused_bf16_rows) *fused_bf16_rows = c->fused_bf16_rows;
     return DORY_OK;
 }
 

@@ -71,6 +71,8 @@ struct FusedStamp {
     int dir = 0;
     uint32_t w = 0;
     const float *buf = nullptr;
+    bool bf16 = false;   // dory_halo_fused_pack_bf16: the rows are bf16 (w elements of 2 bytes, the first `cols` hold values)
+    uint32_t cols = 0;
 };
 
 // The wire format of a packed halo row: w elements per row -- the tensor's padded ld, or with `exact` (option halo_exact_rows)
@@ -319,6 +321,9 @@ struct dory_ctx {
     bool fused_pack = false;
     dory::FusedStamp fused_stamp;
     uint64_t fused_exchanges = 0, fused_rows = 0, fallback_exchanges = 0;
+    // ... and its bf16 form (dory_halo_fused_pack_bf16; default off): the epilogues round the rows of an exchange that ships bf16
+    bool fused_pack_bf16 = false;
+    uint64_t fused_bf16_exchanges = 0, fused_bf16_rows = 0;
     // bf16 halo rows (dory_halo_bf16_rows; default off) and the two gather modes its rule reads (option gcn_bf16_gather,
     // dory_gat_bf16_gather's mode) -- copies the peers of the local transport may read without this context's lock -- and the
     // eager packs counted: those that wrote bf16 rows, their bytes, those that wrote fp32 rows while the switch was on
@@ -500,11 +505,14 @@ hipError_t launch_gemm(const GemmArgs &g, float *scratch, size_t scratch_bytes, 
 // The fused halo pack (dory_halo_fused_pack): the extra argument of K2's send kernels.  Row r of the product is also stored at the
 // rows row_slots[row_ptr[r] .. row_ptr[r + 1]) of buf, w floats each -- w == the tensor's ld (a padded wire row: [cols, w) gets
 // zeros) or == cols (halo_exact_rows: dense rows); `which`: 0 the rows of C, 1 those of the tanh output C2.
+// bf16 (dory_halo_fused_pack_bf16; the send16 kernels): buf is addressed in 2-byte elements, a row is w of them (a multiple of 4; w <=
+// ld), rounded with pack_bf16x2, zeros in [cols, w) -- what gather_rows_bf16_kernel leaves.
 struct GemmSend {
     float *buf;
     const uint32_t *row_ptr;     // M + 1 (dory_halo_send_map)
     const uint32_t *row_slots;   // row_ptr[M]
     uint32_t w, which, cols;
+    uint32_t bf16;               // the element kind: 0 fp32, 1 bf16
 };
 // NN and NT with M, K > 0: *fused = true and the rows are in buf; anything else runs as launch_gemm and leaves *fused false
 hipError_t launch_gemm_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *fused);
@@ -528,6 +536,14 @@ __device__ __forceinline__ float dory_tanh(float x) {
     const float t = __builtin_amdgcn_exp2f(ax * 2.885390081777927f);   // exp(2|x|); inf for |x| > 44: 2/(1+inf) = 0
     const float big = copysignf(1.f - 2.f * __builtin_amdgcn_rcpf(1.f + t), x);
     return ax < 0.35f ? small : big;
+}
+
+// fp32 -> bf16, round to nearest even, two at a time (the compiler's cast: v_cvt_pk_bf16_f32) -- the one conversion of the bf16 row
+// gathers' shadow rows, of the bf16 halo pack (csrc/elementwise.hip) and of K2's bf16 send epilogues (csrc/gemm.hip)
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 p = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(uint32_t, p);
 }
 
 // K3/K4 elementwise + loss

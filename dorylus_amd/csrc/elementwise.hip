@@ -360,12 +360,7 @@ hipError_t launch_row_axpy_bf16(float *out, const float *S, const float *rs, con
 }
 
 // option gcn_bf16_gather: the rows an aggregation reads, rounded to bf16 (nearest even; v_cvt_pk_bf16_f32), into the
-// context's shadow buffer -- every element of an ld-wide row, so that padding columns stay 0
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 p = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, p);
-}
+// context's shadow buffer -- every element of an ld-wide row, so that padding columns stay 0 (pack_bf16x2: ctx.hpp)
 __global__ __launch_bounds__(256) void bf16_rows_kernel(const float4 *x, uint2 *y, uint64_t n4) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * blockDim.x) {
         const float4 v = x[i];

@@ -101,6 +101,18 @@ __device__ __forceinline__ void send_store(const GemmSend &sd, uint32_t row, uin
     for (uint32_t s = sd.row_ptr[row]; s < s1; ++s) sd.buf[(size_t)sd.row_slots[s] * sd.w + col] = v;
 }
 
+// ... and its bf16 form (dory_halo_fused_pack_bf16): buf in 2-byte elements, `bits` the cvt_pk dword of columns col (even) and col + 1
+__device__ __forceinline__ void send_store16(const GemmSend &sd, uint32_t row, uint32_t col, uint32_t bits) {
+    uint16_t *buf = reinterpret_cast<uint16_t *>(sd.buf);
+    const uint32_t s1 = sd.row_ptr[row + 1];
+    for (uint32_t s = sd.row_ptr[row]; s < s1; ++s) *reinterpret_cast<uint32_t *>(buf + (size_t)sd.row_slots[s] * sd.w + col) = bits;
+}
+// the value of the lane to the right within a pair of lanes (DPP quad_perm [1, 1, 3, 3]; lanes 1 and 3 of a quad read themselves):
+// to be called where both lanes of every pair are active
+__device__ __forceinline__ float lane_right(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xF5, 0xF, 0xF, true));
+}
+
 // SEND (the fused halo pack, dory_halo_fused_pack): the epilogue stores every element of a row once more into each of the row's
 // slots of the packed send buffer -- what gather_rows_kernel would copy out of C (or of the tanh output C2) afterwards.  Columns
 // [cols, w) of a padded wire row get the zeros of the tensor's padding; a split launch leaves all of it to the reduce kernel.
@@ -108,7 +120,13 @@ __device__ __forceinline__ void send_store(const GemmSend &sd, uint32_t row, uin
 // load its slot range and each slot once for both column tiles and write 128 contiguous bytes of the slot's row per tile (the
 // slot loop inside the store loop, indices reloaded per element, cost more than the pack kernel at two shapes:
 // profiles/r17_halo_fused_pack.txt).
-template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK, bool SEND = false>
+// S16 != 0 (dory_halo_fused_pack_bf16): the rows go out as bf16, byte for byte what gather_rows_bf16_kernel leaves -- sd.w 2-byte
+// elements a row (a multiple of 4), rounded with pack_bf16x2, zeros in [cols, w).  A lane holds one column and its neighbour the next
+// one, so S16 == 1, the form the library runs, takes the neighbour's value by DPP at the head of a row's turn, where the whole wave walks together, leaves
+// the cvt_pk dword of the pair in the accumulator, and the even lanes store it: 16 lanes x 4 bytes = the 64 contiguous bytes of a
+// row and tile.  S16 == 2 is the plain form, every lane a 2-byte store; tools/probes/gemm_send16_forms.hip times both
+// (profiles/r21_halo_fused_pack_bf16.txt).
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK, bool SEND = false, int S16 = 0>
 __device__ __forceinline__ void gemm_dma_body(const GemmArgs &g, uint32_t klen, float *partial, float *smem, const GemmSend &sd = GemmSend{}) {
     static_assert(WM * WN == 4 && WN * TN * 32 == BN, "tile shape");
     constexpr int BM = WM * TM * 32;
@@ -210,14 +228,28 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs &g, uint32_t klen, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const uint32_t row = i0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+                if constexpr (S16 == 1) {   // (here the whole wave still walks together; in the store loop above it cost the 128-wide form spills)
+#pragma unroll
+                    for (int b = 0; b < TN; ++b) acc[a][b][r] = __uint_as_float(pack_bf16x2(acc[a][b][r], lane_right(acc[a][b][r])));
+                }
                 if (row >= g.M) continue;
                 const uint32_t s1 = sd.row_ptr[row + 1];
                 for (uint32_t s = sd.row_ptr[row]; s < s1; ++s) {
-                    float *dst = sd.buf + (size_t)sd.row_slots[s] * sd.w;   // (64-bit: a send buffer may exceed 4 GB)
+                    if constexpr (S16 != 0) {
+                        uint16_t *dst = reinterpret_cast<uint16_t *>(sd.buf) + (size_t)sd.row_slots[s] * sd.w;
 #pragma unroll
-                    for (int b = 0; b < TN; ++b) {
-                        const uint32_t col = j0 + (wn * TN + b) * 32 + fr;
-                        if (col < sd.w) dst[col] = acc[a][b][r];
+                        for (int b = 0; b < TN; ++b) {
+                            const uint32_t col = j0 + (wn * TN + b) * 32 + fr;   // (w is even: col + 1 < w for an even col < w)
+                            if (S16 == 1 && !(fr & 1) && col < sd.w) *reinterpret_cast<uint32_t *>(dst + col) = __float_as_uint(acc[a][b][r]);
+                            if (S16 == 2 && col < sd.w) dst[col] = (uint16_t)pack_bf16x2(acc[a][b][r], 0.f);
+                        }
+                    } else {
+                        float *dst = sd.buf + (size_t)sd.row_slots[s] * sd.w;   // (64-bit: a send buffer may exceed 4 GB)
+#pragma unroll
+                        for (int b = 0; b < TN; ++b) {
+                            const uint32_t col = j0 + (wn * TN + b) * 32 + fr;
+                            if (col < sd.w) dst[col] = acc[a][b][r];
+                        }
                     }
                 }
             }
@@ -248,6 +280,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                                                                           float *partial, GemmSend sd) {
     __shared__ __attribute__((aligned(1024))) float smem[2 * (WM * TM * 32 + BN) * BK];
     gemm_dma_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true>(g, klen, partial, smem, sd);
+}
+
+// ... and with the rows as bf16 (dory_halo_fused_pack_bf16): kernels of their own again.  FORM: S16 of the body (the library
+// instantiates 1 only)
+#ifndef GEMM_SEND16_FORM
+#define GEMM_SEND16_FORM 1
+#endif
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK, int FORM>
+__global__ __launch_bounds__(256) void gemm_dma_send16_kernel(GemmArgs g, uint32_t klen, float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) float smem[2 * (WM * TM * 32 + BN) * BK];
+    gemm_dma_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, FORM>(g, klen, partial, smem, sd);
+}
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK, int FORM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_dma_send16_kernel_occ4(GemmArgs g, uint32_t klen,
+                                                                                                            float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) float smem[2 * (WM * TM * 32 + BN) * BK];
+    gemm_dma_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, FORM>(g, klen, partial, smem, sd);
 }
 
 // second stage of split-K: C = sum_z partial[z] in z order (deterministic); eight
@@ -306,6 +355,40 @@ __global__ void splitk_reduce_send_kernel(float *C, const float *partial, uint32
             if (sd.which) sv = t;
         }
         if (col < sd.w) send_store(sd, row, col, sv);
+    }
+}
+
+// ... and the reduce with the rows as bf16: the same sums in the same order; ldc is even (launch_gemm_any), so the two threads of a
+// pair of lanes hold columns col (even) and col + 1 of one row and leave the loop together: the even one stores the pair's dword
+__global__ void splitk_reduce_send16_kernel(float *C, const float *partial, uint32_t M, uint32_t N, uint32_t ldc, uint32_t S,
+                                            float *C2 /*EPI_TANH: tanh(C), or nullptr*/, uint32_t ldc2, GemmSend sd) {
+    constexpr uint32_t RU = 8;
+    const size_t n = (size_t)M * ldc;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t row = (uint32_t)(i / ldc), col = (uint32_t)(i % ldc);
+        float sv = 0.f;   // (columns [N, w): the zeros of the wire row's padding)
+        if (col < N) {
+            float s = 0.f;
+            uint32_t z = 0;
+            for (; z + RU <= S; z += RU) {
+                float v[RU];
+#pragma unroll
+                for (uint32_t u = 0; u < RU; ++u) v[u] = partial[(size_t)(z + u) * n + i];
+#pragma unroll
+                for (uint32_t u = 0; u < RU; ++u) s += v[u];
+            }
+            for (; z < S; ++z) s += partial[(size_t)z * n + i];
+            C[i] = s;
+            sv = s;
+            if (C2) {
+                const float t = dory_tanh(s);
+                C2[(size_t)row * ldc2 + col] = t;
+                if (sd.which) sv = t;
+            }
+        }
+        const uint32_t bits = pack_bf16x2(sv, lane_right(sv));
+        if (!(col & 1) && col < sd.w) send_store16(sd, row, col, bits);
     }
 }
 
@@ -368,7 +451,18 @@ static hipError_t launch_bn(const GemmArgs &g, float *scratch, size_t scratch_by
         else                                                                                                                             \
             hipLaunchKernelGGL((gemm_dma_send_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd);      \
     } while (0)
-    if (sd && !g.ta && !g.tb) GEMM_LAUNCH_SEND(false, true);          // (launch_gemm_send: NN and NT only)
+#define GEMM_LAUNCH_SEND16(AK, BKM)                                                                                                      \
+    do {                                                                                                                                 \
+        if constexpr (BN == 128 && WM * TM * 32 == 128)                                                                                  \
+            hipLaunchKernelGGL((gemm_dma_send16_kernel_occ4<BN, WM, WN, TM, TN, AK, BKM, BK, GEMM_SEND16_FORM>), grid, block, 0, s, g,   \
+                               klen, scratch, *sd);                                                                                      \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((gemm_dma_send16_kernel<BN, WM, WN, TM, TN, AK, BKM, BK, GEMM_SEND16_FORM>), grid, block, 0, s, g, klen,  \
+                               scratch, *sd);                                                                                            \
+    } while (0)
+    if (sd && sd->bf16 && !g.ta && !g.tb) GEMM_LAUNCH_SEND16(false, true);
+    else if (sd && sd->bf16 && !g.ta && g.tb) GEMM_LAUNCH_SEND16(false, false);
+    else if (sd && !g.ta && !g.tb) GEMM_LAUNCH_SEND(false, true);          // (launch_gemm_send: NN and NT only)
     else if (sd && !g.ta && g.tb) GEMM_LAUNCH_SEND(false, false);
     else if (sd) return hipErrorInvalidValue;
     else if (!g.ta && !g.tb) GEMM_LAUNCH(false, true);
@@ -377,13 +471,17 @@ static hipError_t launch_bn(const GemmArgs &g, float *scratch, size_t scratch_by
     else return hipErrorInvalidValue;
 #undef GEMM_LAUNCH
 #undef GEMM_LAUNCH_SEND
+#undef GEMM_LAUNCH_SEND16
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (S > 1) {
         const size_t n = (size_t)g.M * g.ldc;
         int blocks = (int)((n + 255) / 256);
         if (blocks > 2048) blocks = 2048;
-        if (sd)
+        if (sd && sd->bf16)
+            hipLaunchKernelGGL(splitk_reduce_send16_kernel, dim3(blocks), dim3(256), 0, s, g.C, scratch, g.M, g.N, g.ldc, S,
+                               g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2, *sd);
+        else if (sd)
             hipLaunchKernelGGL(splitk_reduce_send_kernel, dim3(blocks), dim3(256), 0, s, g.C, scratch, g.M, g.N, g.ldc, S,
                                g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2, *sd);
         else
@@ -400,6 +498,8 @@ static hipError_t launch_gemm_any(const GemmArgs &g, float *scratch, size_t scra
     if (fused) *fused = false;
     if (g.M == 0 || g.N == 0) return hipSuccess;
     if (sd && (g.ta || g.K == 0 || sd->cols != g.N || sd->w > g.ldc || sd->w > pad_ld(g.N) || (sd->which && g.epilogue != EPI_TANH))) sd = nullptr;
+    // bf16 rows: whole quads of elements inside the tensor's row (a one-column tensor, ld == 1, has none), columns paired across lanes
+    if (sd && sd->bf16 && ((sd->w & 3u) || (g.ldc & 1u) || (reinterpret_cast<uintptr_t>(sd->buf) & 7u))) sd = nullptr;
     // the DMA moves 16-byte pieces: rows must start on 16-byte boundaries (every tensor of the table does: ld is padded to 32 floats)
     if ((g.lda & 3u) || (g.ldb & 3u) || (reinterpret_cast<uintptr_t>(g.A) & 15u) || (reinterpret_cast<uintptr_t>(g.B) & 15u))
         return hipErrorInvalidValue;

@@ -286,7 +286,8 @@ int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide,
  * dory_halo_bf16_ghosts (below) gives the rows a bf16 tensor to land in;
  * dory_halo_pack_tensor / dory_halo_unpack_tensor (the consumer is unknown).  dory_halo_pack / dory_halo_unpack follow the rule
  * as they follow halo_exact_rows: the caller's buffer (8-byte aligned) then holds rows x row_elems x 2 bytes.  The fused halo
- * pack never serves an exchange that ships bf16 (no GEMM stores fp32 rows nobody sends; its statistics count a fallback).
+ * pack never serves an exchange that ships bf16 (no GEMM stores fp32 rows nobody sends; its statistics count a fallback) -- unless
+ * dory_halo_fused_pack_bf16 (below) has the GEMM epilogue round the rows itself.
  * Wire format: a packed row holds row_elems bf16 values -- the tensor's ld, or with halo_exact_rows = 1 its cols rounded up to a
  * multiple of 4 with zeros in the trailing elements, which the pack writes itself (a one-column tensor, ld == 1: 4 elements).
  * Rows are multiples of 8 bytes.  The host transport's counts and offsets stay in floats: rows x row_elems / 2.  RCCL and the
@@ -304,7 +305,8 @@ int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide,
  * dory_halo_bf16_rows: on = 0 (default) / 1, any time after dory_configure, outside an exchange; accepted and inert with
  * num_nodes == 1; DORY_ERR_ARG for other values or while an epoch graph is being recorded.
  * dory_halo_bf16_rows_stats: packs that wrote bf16 rows, their bytes, packs (and fused or scatter-message exchanges) that shipped
- * fp32 while the switch was on -- eager calls only, since dory_create; any pointer may be NULL.
+ * fp32 while the switch was on -- eager calls only, since dory_create; any pointer may be NULL.  An exchange whose bf16 rows a GEMM
+ * epilogue wrote (dory_halo_fused_pack_bf16) counts in bf16_packs and bf16_bytes like a pack: they say what travelled as bf16.
  * dory_halo_wire_row: what dory_halo_exchange(layer, dir) and dory_halo_pack(layer, dir, ...) would put on the wire with the
  * settings of this moment: bytes per element (4 or 2) and elements per row -- what a foreign transport sizes its buffers by.
  * Kernels (csrc/elementwise.hip): four elements per lane, one 16-byte access on the fp32 side and one 8-byte access on the
@@ -321,6 +323,53 @@ int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide,
 int dory_halo_bf16_rows(dory_ctx *ctx, int on);
 int dory_halo_bf16_rows_stats(dory_ctx *ctx, uint64_t *bf16_packs, uint64_t *bf16_bytes, uint64_t *fp32_packs_while_on);
 int dory_halo_wire_row(dory_ctx *ctx, uint32_t layer, int dir, uint32_t *elem_bytes, uint32_t *row_elems);
+
+/* ---- fused halo pack for bf16 rows: the GEMM epilogues write the bf16 send rows (opt-in, default off; nothing in the reference) ----
+ * dory_halo_fused_pack and dory_halo_bf16_rows cancel each other where both apply: the GEMM writes fp32, and the bf16 pack kernel
+ * reads it back to round it.  With this third switch on, the fused pack also serves the exchanges that ship bf16: the producing K2
+ * GEMM (NN / NT of both tile shapes, or the split-K reduce; kernels of their own, gemm_dma_send16_kernel[_occ4] and
+ * splitk_reduce_send16_kernel in csrc/gemm.hip -- every other kernel keeps its code object) rounds each element with the pack's own
+ * conversion (v_cvt_pk_bf16_f32) and stores it into the row's slots of the send buffer: row_elems bf16 a row, zeros in
+ * [cols, row_elems) -- byte for byte what gather_rows_bf16_kernel would leave; C and C2 keep their bits.  The exchange then runs no
+ * pack kernel.  It has an effect only while dory_halo_fused_pack is 1, dory_halo_bf16_rows is 1 and the rule above says the
+ * exchange ships bf16; off (default): everything as before, bf16 exchanges pack and count as fallbacks of the fused pack.
+ * The stamp carries the element kind and, for bf16, the columns that hold values; the exchange takes it only if source,
+ * direction, kind, columns, width and buffer are what its own wire -- computed at the exchange -- has: a gather mode, any of the three
+ * halo switches or halo_exact_rows changed between producer and exchange is a counted fallback with the bytes of the moment.
+ * Not taken (counted fallbacks, same bytes): everything the fused pack does not take (above); a one-column tensor (ld == 1: a wire
+ * row of 4 elements is wider than the tensor's row); TN products, K == 0, no local rows.  The multi-head GAT never ships bf16.
+ * Direct plans over RCCL or the host transport whose rows land in twins fuse like any other: only the send side changes.
+ * Counters of a fused bf16 exchange: fused_exchanges / fused_rows of dory_halo_fused_pack_stats move as for an fp32 one, and the
+ * two of this section; bf16_packs / bf16_bytes of dory_halo_bf16_rows_stats move too (what travelled as bf16: a foreign
+ * transport sizes by them); halo_rows_packed / halo_floats_packed do not (no pack kernel ran).  Eager calls only, since dory_create.
+ * dory_halo_fused_pack_bf16: on = 0 (default) / 1, any time after dory_configure, outside an exchange; drops the stamp; accepted
+ * and inert with num_nodes == 1; DORY_ERR_ARG for other values, before dory_configure, or while an epoch graph is being recorded.
+ * Epilogue form (tools/probes/gemm_send16_forms.hip; profiles/r21_halo_fused_pack_bf16.txt, profiles/HISTORY.md section 22): a lane
+ * holds one column and its neighbour the next, so the value of the lane to the right comes by DPP (quad_perm) and the even lanes
+ * store one cvt_pk dword -- 16 lanes x 4 bytes per row and tile -- against the plain form of one 2-byte store per lane:
+ *     N (w)          128     64      48 (64)  48 (48)  41 (64)  41 (44)  300 (320)  300 (300)     [1.05 M rows, K = 128, ms, medians of 3]
+ *     GEMM + pack    0.493   0.259   0.255    0.265    0.266    0.257    1.362      1.394
+ *     DPP pair       0.474   0.253   0.255    0.260    0.249    0.243    1.345      1.375
+ *     2-byte stores  0.468   0.251   0.255    0.255    0.251    0.242    1.341      1.374
+ * NO FORM WON: they lie within 2 % of each other at every shape (the 2-byte form ahead by 0-1.8 % at seven, behind by 0.8 % at one),
+ * inside the 2-6 % between rounds (a second session: the same, the pair form at 64 floats 1.3 % above GEMM + pack, inside its rounds'
+ * spread).  The pair form is the one instantiated: half the store instructions for the same bytes.  Both spend
+ * most of what the pack kernel took: the row's slot range and slots are loaded in the epilogue with nothing to hide them behind.
+ * Measured on one MI355X (same files; NO LINK AND NO MULTI-RANK RCCL RUN IS BEHIND ANY NUMBER), baseline = the parent's pair, the
+ * GEMM plus gather_rows_bf16_kernel, against the bf16 send GEMM alone:
+ *     1.05 M local rows, every row to 1 peer / to 3 peers (3.15 M send rows); ms per call, medians of 3 alternating rounds
+ *     NN+tanh 602->128        1.602 -> 1.571 / 1.854 -> 1.698        NN 128->41 padded   0.282 -> 0.263 / 0.403 -> 0.372
+ *     NT 41->128              0.726 -> 0.732 / 0.988 -> 0.945        NN 128->41 exact    0.280 -> 0.264 / 0.376 -> 0.352
+ *     NN 300->64              0.523 -> 0.476 / 0.626 -> 0.560        NN 128->300 padded  1.378 -> 1.357 / 2.121 -> 1.794
+ *     NN 128->48 padded       0.287 -> 0.274 / 0.402 -> 0.374        NN 128->300 exact   1.383 -> 1.363 / 2.096 -> 1.851
+ *     NN 128->48 exact        0.285 -> 0.266 / 0.381 -> 0.359
+ * x0.85-0.99 of the pair; the first round of every series is its slowest (0.01-0.25 ms between rounds), so only six of the eighteen
+ * differences exceed the spread of their own series.  ONE SHAPE IS A TIE ON THE WRONG SIDE: NT 41->128 with one peer per row, +0.006 ms
+ * (+0.8 %), far inside its spread of 0.095 ms; it is taken like the others.  With every switch off the headline epoch of bench.py is
+ * inside the parent's range (18.057-18.064 ms against 18.037-18.092); the GAT epochs read 0.1-0.3 % above it when the parent's
+ * process ran first of each pair and inside or below it when it ran second (same file, section 3: the position, not the library). */
+int dory_halo_fused_pack_bf16(dory_ctx *ctx, int on);   /* 0 (default) / 1 */
+int dory_halo_fused_pack_bf16_stats(dory_ctx *ctx, uint64_t *fused_bf16_exchanges, uint64_t *fused_bf16_rows);
 
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
