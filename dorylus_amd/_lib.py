@@ -33,6 +33,7 @@ SYMBOLS = [
     "dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row",
     "dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek",
     "dory_halo_fused_pack_bf16", "dory_halo_fused_pack_bf16_stats",
+    "dory_halo_fused_pack_rowwise", "dory_halo_fused_pack_rowwise_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -133,6 +134,8 @@ def load():
         "dory_halo_bf16_ghost_peek": [vp, u32, cp, C.POINTER(vp), C.POINTER(i32)],
         "dory_halo_fused_pack_bf16": [vp, i32],
         "dory_halo_fused_pack_bf16_stats": [vp, C.POINTER(u64), C.POINTER(u64)],
+        "dory_halo_fused_pack_rowwise": [vp, i32],
+        "dory_halo_fused_pack_rowwise_stats": [vp, C.POINTER(u64), C.POINTER(u64)],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -588,6 +591,18 @@ class Context:
         """(exchanges whose bf16 send rows a GEMM epilogue wrote, the send rows of those)"""
         a, b = C.c_uint64(), C.c_uint64()
         self._ck(self.lib.dory_halo_fused_pack_bf16_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def halo_fused_pack_rowwise(self, on=True):
+        """the fused halo pack also serves exchanges whose source a row-wise kernel writes (g, h of a transform-first layer, the GAT
+        prototype's last-layer grad): the send forms of those kernels write the rows (opt-in on top of halo_fused_pack, and of
+        halo_fused_pack_bf16 for bf16 rows; dory_halo_fused_pack_rowwise)"""
+        self._ck(self.lib.dory_halo_fused_pack_rowwise(self.h, int(on)))
+
+    def halo_fused_pack_rowwise_stats(self):
+        """(exchanges whose send rows a row-wise producer wrote, the send rows of those)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.dory_halo_fused_pack_rowwise_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     # -- optimiser ---------------------------------------------------------------------------

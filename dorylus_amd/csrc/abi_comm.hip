@@ -120,10 +120,15 @@ int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloP
         const FusedStamp &st = c->fused_stamp;
         if (may_fuse && st.src == src && st.dir == dir && st.bf16 == wire.bf16 && (!wire.bf16 || st.cols == wire.cols) && st.w == wire.w &&
             st.buf == c->send_buf) {
+            const bool rowwise = st.rowwise;
             fused_stamp_drop(c);
             if (!c->capturing) {
                 c->fused_exchanges++;
                 c->fused_rows += p.send_total;
+                if (rowwise) {   // (dory_halo_fused_pack_rowwise: a row-wise producer wrote them -- counted besides)
+                    c->rowwise_exchanges++;
+                    c->rowwise_rows += p.send_total;
+                }
                 if (wire.bf16) {   // (what travelled as bf16 is counted as for a pack: a foreign transport sizes by it)
                     c->fused_bf16_exchanges++;
                     c->fused_bf16_rows += p.send_total;
@@ -925,13 +930,14 @@ bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd,
     }
     return false;
 }
-void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &sd) {
+void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &sd, bool rowwise) {
     c->fused_stamp.src = out;
     c->fused_stamp.dir = dir;
     c->fused_stamp.w = sd.w;
     c->fused_stamp.buf = sd.buf;
     c->fused_stamp.bf16 = sd.bf16 != 0;
     c->fused_stamp.cols = sd.bf16 ? sd.cols : 0;
+    c->fused_stamp.rowwise = rowwise;
 }
 
 // ---- bf16 ghost twins (dory_halo_bf16_ghosts) -----------------------------------------------------------------------------------
@@ -1269,6 +1275,25 @@ int dory_halo_fused_pack_bf16_stats(dory_ctx *c, uint64_t *fused_bf16_exchanges,
     CHECK_CTX(c);
     if (fused_bf16_exchanges) *fused_bf16_exchanges = c->fused_bf16_exchanges;
     if (fused_bf16_rows) *fused_bf16_rows = c->fused_bf16_rows;
+    return DORY_OK;
+}
+
+// dory_halo_fused_pack_rowwise: the fused pack also serves the exchanges whose source a row-wise kernel writes (the send forms of
+// csrc/elementwise.hip; dory_apply_vertex and dory_predict_gat launch them)
+int dory_halo_fused_pack_rowwise(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_fused_pack_rowwise: dory_configure first; on is 0 or 1");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_fused_pack_rowwise: not while an epoch graph is being recorded");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    fused_stamp_drop(c);
+    c->fused_pack_rowwise = on == 1;
+    return DORY_OK;
+}
+
+int dory_halo_fused_pack_rowwise_stats(dory_ctx *c, uint64_t *rowwise_exchanges, uint64_t *rowwise_rows) {
+    CHECK_CTX(c);
+    if (rowwise_exchanges) *rowwise_exchanges = c->rowwise_exchanges;
+    if (rowwise_rows) *rowwise_rows = c->rowwise_rows;
     return DORY_OK;
 }
 

@@ -118,9 +118,10 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer);
 // The fused halo pack (abi_comm.hip).  fused_pack_target: the GEMM about to write `out` (M rows, the product's C or its tanh output)
 // may store its rows into the send buffer too -- the feature is on, a plan and its map exist, `out` is the source of an exchange
 // of this model (the resolver halo_tensors uses), nothing of section "not taken" of dorylus_hip.h applies -- then *sd (but `which`)
-// and *dir are filled in.  fused_pack_stamp: that GEMM has been enqueued.  fused_stamp_drop: whatever the stamp named may be stale.
+// and *dir are filled in.  fused_pack_stamp: that GEMM has been enqueued (`rowwise`: a row-wise producer's send form instead,
+// dory_halo_fused_pack_rowwise, which asks fused_pack_target the same question about the tensor it writes).  fused_stamp_drop: whatever the stamp named may be stale.
 bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd, int *dir);
-void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &sd);
+void fused_pack_stamp(dory_ctx *c, const Tensor *out, int dir, const GemmSend &sd, bool rowwise = false);
 inline void fused_stamp_drop(dory_ctx *c) { c->fused_stamp = FusedStamp(); }
 // something other than a fusing GEMM writes `t` (may be null): a stamp that names it no longer describes its rows
 inline void fused_note_write(dory_ctx *c, const Tensor *t) { if (t && c->fused_stamp.src == t) fused_stamp_drop(c); }

@@ -825,6 +825,22 @@ static int aggregate_gat(dory_ctx *c, uint32_t fl, int dir) {
 
 #undef AGG_NEED
 
+// dory_halo_fused_pack_rowwise: the row-wise kernel about to write `out` (N rows of `cols` columns) may store its rows into the send
+// buffer too -- what gemm() (abi_context.hip) asks for a product, with the switch in front; the previous exchange has finished
+// reading the buffer before true comes back.  A one-column tensor (ld == 1) is left to the pack kernels, whatever the wire.
+static int rowwise_send_target(dory_ctx *c, const Tensor *out, uint32_t cols, GemmSend *sd, int *dir, bool *send) {
+    *send = c->fused_pack_rowwise && out->cols == cols && (out->ld & 3u) == 0 && fused_pack_target(c, out, c->N, sd, dir);
+    if (!*send) return DORY_OK;
+    sd->which = 0;
+    sd->cols = cols;
+    return wait_halo(c);
+}
+// ... and after its launch: the rows are in the buffer (stamped), or the plain kernel ran after all
+static void rowwise_sent(dory_ctx *c, const Tensor *out, int dir, const GemmSend &sd, bool fused) {
+    if (fused) fused_pack_stamp(c, out, dir, sd, true);
+    else fused_note_write(c, out);
+}
+
 }  // namespace dory
 
 using namespace dory;
@@ -858,9 +874,14 @@ int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {
             if (layer != c->L - 1) {  // vtxNNForwardGCN hidden (CPU_comm.cpp:98-107)
                 NEED(h, layer, "h");
                 if (tf_layer(c, layer)) {   // z_l came out of dory_aggregate already
+                    GemmSend sd{};
+                    int send_dir = 0;
+                    bool send = false, fused = false;
+                    if ((rc = rowwise_send_target(c, h, Fout, &sd, &send_dir, &send))) return rc;
                     Timed t(c, "loss", c->compute);
-                    fused_note_write(c, h);
-                    HIPCK(c, launch_tanh_forward(N, Fout, z->d, z->ld, h->d, h->ld, c->compute));
+                    if (send) HIPCK(c, launch_tanh_forward_send(N, Fout, z->d, z->ld, h->d, h->ld, sd, c->compute, &fused));
+                    else HIPCK(c, launch_tanh_forward(N, Fout, z->d, z->ld, h->d, h->ld, c->compute));
+                    rowwise_sent(c, h, send_dir, sd, fused);
                 } else if ((rc = gemm(c, 0, 0, N, Fout, Fin, *ah, W, *z, h))) {
                     return rc;
                 }
@@ -880,11 +901,20 @@ int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {
             const float denom = (float)(c->globalV * 0.66);
             if ((rc = ensure_scratch(c, softmax_xent_scratch_bytes(Fout, vend - stt)))) return rc;
             {
+                GemmSend sd{};
+                int send_dir = 0;
+                bool send = false, fused = false;
+                if ((rc = rowwise_send_target(c, g, Fout, &sd, &send_dir, &send))) return rc;
                 Timed t(c, "loss", c->compute);
                 // maskout copies (N - stt) floats starting at dense offset stt*cols (CPU_comm.cpp:464-471)
-                HIPCK(c, launch_softmax_xent(N, Fout, z->d, z->ld, lab->d, lab->ld, g->d, g->ld, denom, stt,
-                                             vend, (uint64_t)stt * Fout, (uint64_t)(N - stt), c->d_stat,
-                                             c->scratch, c->compute));
+                if (send)
+                    HIPCK(c, launch_softmax_xent_send(N, Fout, z->d, z->ld, lab->d, lab->ld, g->d, g->ld, denom, stt, vend, (uint64_t)stt * Fout,
+                                                      (uint64_t)(N - stt), c->d_stat, c->scratch, sd, c->compute, &fused));
+                else
+                    HIPCK(c, launch_softmax_xent(N, Fout, z->d, z->ld, lab->d, lab->ld, g->d, g->ld, denom, stt,
+                                                 vend, (uint64_t)stt * Fout, (uint64_t)(N - stt), c->d_stat,
+                                                 c->scratch, c->compute));
+                rowwise_sent(c, g, send_dir, sd, fused);
             }
             if (tfl) return DORY_OK;
             if (layer > 0) {  // interGrad = d_output * W^T -> "grad"
@@ -896,8 +926,14 @@ int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {
         // vtxNNBackwardGCN (CPU_comm.cpp:137-159)
         NEED(aTg, layer, "aTg");
         {
+            GemmSend sd{};
+            int send_dir = 0;
+            bool send = false, fused = false;
+            if ((rc = rowwise_send_target(c, g, Fout, &sd, &send_dir, &send))) return rc;
             Timed t(c, "loss", c->compute);
-            HIPCK(c, launch_tanh_backward(N, Fout, aTg->d, aTg->ld, z->d, z->ld, g->d, g->ld, c->compute));
+            if (send) HIPCK(c, launch_tanh_backward_send(N, Fout, aTg->d, aTg->ld, z->d, z->ld, g->d, g->ld, sd, c->compute, &fused));
+            else HIPCK(c, launch_tanh_backward(N, Fout, aTg->d, aTg->ld, z->d, z->ld, g->d, g->ld, c->compute));
+            rowwise_sent(c, g, send_dir, sd, fused);
         }
         if (tf_layer(c, layer)) return DORY_OK;   // dW_l (and the gradient for layer l-1) follow in dory_aggregate(l, backward)
         if ((rc = gemm(c, 1, 0, Fin, Fout, N, *ah, *g, dW))) return rc;
@@ -1026,9 +1062,14 @@ int dory_predict_gat(dory_ctx *c, uint32_t layer) {
     NEED(ah, fl, "ah");
     NEED(lab, fl, "lab");
     NEED(grad, fl, "grad");
-    fused_note_write(c, grad);
+    GemmSend sd{};
+    int send_dir = 0;
+    bool send = false, fused = false;
+    { int rc = rowwise_send_target(c, grad, c->dims[layer], &sd, &send_dir, &send); if (rc) return rc; }
     Timed t(c, "loss", c->compute);
-    HIPCK(c, launch_softmax_sub(c->N, c->dims[layer], ah->d, ah->ld, lab->d, lab->ld, grad->d, grad->ld, c->compute));
+    if (send) HIPCK(c, launch_softmax_sub_send(c->N, c->dims[layer], ah->d, ah->ld, lab->d, lab->ld, grad->d, grad->ld, sd, c->compute, &fused));
+    else HIPCK(c, launch_softmax_sub(c->N, c->dims[layer], ah->d, ah->ld, lab->d, lab->ld, grad->d, grad->ld, c->compute));
+    rowwise_sent(c, grad, send_dir, sd, fused);
     return DORY_OK;
 }
 

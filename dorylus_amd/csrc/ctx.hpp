@@ -73,6 +73,7 @@ struct FusedStamp {
     const float *buf = nullptr;
     bool bf16 = false;   // dory_halo_fused_pack_bf16: the rows are bf16 (w elements of 2 bytes, the first `cols` hold values)
     uint32_t cols = 0;
+    bool rowwise = false;   // dory_halo_fused_pack_rowwise: who wrote them -- a row-wise producer's send form, not a GEMM epilogue
 };
 
 // The wire format of a packed halo row: w elements per row -- the tensor's padded ld, or with `exact` (option halo_exact_rows)
@@ -324,6 +325,10 @@ struct dory_ctx {
     // ... and its bf16 form (dory_halo_fused_pack_bf16; default off): the epilogues round the rows of an exchange that ships bf16
     bool fused_pack_bf16 = false;
     uint64_t fused_bf16_exchanges = 0, fused_bf16_rows = 0;
+    // ... and its row-wise form (dory_halo_fused_pack_rowwise; default off): the send forms of tanh_backward, tanh_forward and the
+    // two softmax producers write the rows of g / h / grad that travel; the consumed stamps they made, counted
+    bool fused_pack_rowwise = false;
+    uint64_t rowwise_exchanges = 0, rowwise_rows = 0;
     // bf16 halo rows (dory_halo_bf16_rows; default off) and the two gather modes its rule reads (option gcn_bf16_gather,
     // dory_gat_bf16_gather's mode) -- copies the peers of the local transport may read without this context's lock -- and the
     // eager packs counted: those that wrote bf16 rows, their bytes, those that wrote fp32 rows while the switch was on
@@ -545,6 +550,11 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     const bf16x2 p = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(uint32_t, p);
 }
+// the value of the lane to the right within a pair of lanes (DPP quad_perm [1, 1, 3, 3]; lanes 1 and 3 of a quad read themselves):
+// to be called where both lanes of every pair are active
+__device__ __forceinline__ float lane_right(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xF5, 0xF, 0xF, true));
+}
 
 // K3/K4 elementwise + loss
 hipError_t launch_tanh_backward(uint64_t rows, uint32_t cols, const float *aTg, uint32_t lda,
@@ -561,6 +571,19 @@ hipError_t launch_softmax_xent(uint32_t rows, uint32_t cols, const float *z, uin
 // predictGAT: grad = softmax(z) - lab
 hipError_t launch_softmax_sub(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz,
                               const float *lab, uint32_t ldl, float *out, uint32_t ldo, hipStream_t s);
+// The send forms of the four producers above (dory_halo_fused_pack_rowwise; elementwise.hip): the tensor as the plain launch leaves
+// it, and its rows once more in sd.buf at the slots of sd's map, in sd's wire format (w, bf16, cols; `which` is not read).  *fused =
+// true: the rows are in the buffer; false: the plain launch ran instead (no rows, a tensor whose ld is no multiple of 4 in the tanh
+// forms).
+hipError_t launch_tanh_backward_send(uint64_t rows, uint32_t cols, const float *aTg, uint32_t lda, const float *z, uint32_t ldz, float *g,
+                                     uint32_t ldg, const GemmSend &sd, hipStream_t s, bool *fused);
+hipError_t launch_tanh_forward_send(uint64_t rows, uint32_t cols, const float *z, uint32_t ldz, float *h, uint32_t ldh, const GemmSend &sd,
+                                    hipStream_t s, bool *fused);
+hipError_t launch_softmax_xent_send(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz, const float *lab, uint32_t ldl, float *d,
+                                    uint32_t ldd, float denom, uint32_t val_stt, uint32_t val_end, uint64_t mask_first, uint64_t mask_count,
+                                    float *stat, float *stat_partial, const GemmSend &sd, hipStream_t s, bool *fused);
+hipError_t launch_softmax_sub_send(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz, const float *lab, uint32_t ldl, float *out,
+                                   uint32_t ldo, const GemmSend &sd, hipStream_t s, bool *fused);
 hipError_t launch_fill_uniform(float *d, uint64_t rows, uint32_t cols, uint32_t ld, uint64_t seed,
                                float lo, float hi, hipStream_t s);
 hipError_t launch_fill_uniform_ids(float *d, uint64_t rows, uint32_t cols, uint32_t ld,

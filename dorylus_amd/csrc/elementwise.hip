@@ -114,9 +114,30 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(
     }
 }
 
+template <int LPR, bool BF16>
+__global__ __launch_bounds__(256) void softmax_rows_send_kernel(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz, const float *lab,
+                                                                uint32_t ldl, float *d, uint32_t ldd, float inv_mode_denom, uint64_t mask_first,
+                                                                uint64_t mask_count, int sub_only, GemmSend sd);
+
 static void launch_softmax_rows(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz, const float *lab,
                                 uint32_t ldl, float *d, uint32_t ldd, float denom, uint64_t mask_first,
-                                uint64_t mask_count, int sub_only, hipStream_t s) {
+                                uint64_t mask_count, int sub_only, hipStream_t s, const GemmSend *sd = nullptr) {
+    if (sd) {   // dory_halo_fused_pack_rowwise: the send forms, at the lanes per row of the plain ones
+#define SOFTMAX_SEND(L)                                                                                                                  \
+    do {                                                                                                                                 \
+        if (sd->bf16) hipLaunchKernelGGL((softmax_rows_send_kernel<L, true>), dim3((rows + 256 / L - 1) / (256 / L)), dim3(256), 0, s, rows, cols, \
+                                         z, ldz, lab, ldl, d, ldd, denom, mask_first, mask_count, sub_only, *sd);                        \
+        else hipLaunchKernelGGL((softmax_rows_send_kernel<L, false>), dim3((rows + 256 / L - 1) / (256 / L)), dim3(256), 0, s, rows, cols, z,     \
+                                ldz, lab, ldl, d, ldd, denom, mask_first, mask_count, sub_only, *sd);                                    \
+    } while (0)
+        if (cols <= 8) SOFTMAX_SEND(8);
+        else if (cols <= 16) SOFTMAX_SEND(16);
+        else if (cols <= 32) SOFTMAX_SEND(32);
+        else if (cols <= 48) SOFTMAX_SEND(16);
+        else SOFTMAX_SEND(64);
+#undef SOFTMAX_SEND
+        return;
+    }
 #define SOFTMAX_LPR(L)                                                                                              \
     hipLaunchKernelGGL(softmax_xent_kernel<L>, dim3((rows + 256 / L - 1) / (256 / L)), dim3(256), 0, s, rows, cols, z, \
                        ldz, lab, ldl, d, ldd, denom, mask_first, mask_count, sub_only)
@@ -219,17 +240,23 @@ size_t softmax_xent_scratch_bytes(uint32_t cols, uint32_t val_rows) {   // per-b
     return (size_t)(2 * ((val_rows + rb - 1) / rb) + 64) * sizeof(float);
 }
 
-hipError_t launch_softmax_xent(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz,
-                               const float *lab, uint32_t ldl, float *d, uint32_t ldd, float denom,
-                               uint32_t val_stt, uint32_t val_end, uint64_t mask_first,
-                               uint64_t mask_count, float *stat, float *stat_partial, hipStream_t s) {
-    if (rows == 0) return hipSuccess;
+// the validation statistics of launch_softmax_xent and of its send form
+static void launch_train_stat(uint32_t cols, const float *z, uint32_t ldz, const float *lab, uint32_t ldl, uint32_t val_stt, uint32_t val_end,
+                              float *stat, float *stat_partial, hipStream_t s) {
     const uint32_t rb = stat_rows_per_block(cols);
     const uint32_t nb = (val_end - val_stt + rb - 1) / rb;
     if (nb)
         hipLaunchKernelGGL(train_stat_kernel, dim3(nb), dim3(256), (size_t)2 * rb * (cols + 1) * sizeof(float), s, cols, z,
                            ldz, lab, ldl, val_stt, val_end, stat_partial, rb);
     hipLaunchKernelGGL(train_stat_final_kernel, dim3(1), dim3(256), 0, s, stat_partial, nb, stat);
+}
+
+hipError_t launch_softmax_xent(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz,
+                               const float *lab, uint32_t ldl, float *d, uint32_t ldd, float denom,
+                               uint32_t val_stt, uint32_t val_end, uint64_t mask_first,
+                               uint64_t mask_count, float *stat, float *stat_partial, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    launch_train_stat(cols, z, ldz, lab, ldl, val_stt, val_end, stat, stat_partial, s);
     launch_softmax_rows(rows, cols, z, ldz, lab, ldl, d, ldd, denom, mask_first, mask_count, 0, s);
     return hipGetLastError();
 }
@@ -238,6 +265,209 @@ hipError_t launch_softmax_sub(uint32_t rows, uint32_t cols, const float *z, uint
                               const float *lab, uint32_t ldl, float *out, uint32_t ldo, hipStream_t s) {
     if (rows == 0) return hipSuccess;
     launch_softmax_rows(rows, cols, z, ldz, lab, ldl, out, ldo, 1.f, 0, 0, 1, s);
+    return hipGetLastError();
+}
+
+// ---- K3 / K4, send forms (dory_halo_fused_pack_rowwise) --------------------------------------------------------------------------
+// The row-wise producers of a tensor that is the source of the next exchange: each computes and stores its tensor exactly as its
+// parent above does (the same expressions on the same operands), and stores row r once more into every slot
+// row_slots[row_ptr[r] .. row_ptr[r + 1]) of the packed send buffer, in the wire format of the moment (GemmSend, ctx.hpp) -- what
+// the pack kernel would copy out of the tensor afterwards:
+//   SEND_F4   fp32, w a multiple of 4 (the padded row, w == ld, or an exact row whose cols is one): 16-byte stores
+//   SEND_F1   fp32 exact rows with cols % 4 != 0 (w == cols): a slot's row starts on a 4-byte boundary only -- dword stores
+//   SEND_BF16 w 2-byte elements (a multiple of 4): pack_bf16x2 of the values, zeros in [cols, w) -- 8-byte stores (tanh forms),
+//             4-byte stores of a lane pair's dword (softmax forms)
+// Columns [cols, w) of a padded fp32 row get what the tensor holds there: the zeros of its padding (tanh_backward: what it has just
+// stored into the last quad).  Most rows go to no peer: the slot range is loaded once per lane and quad (softmax: per lane and
+// row), outside every loop over elements, and an empty one skips the rest.  Offsets into the send buffer are 64-bit.
+enum { SEND_F4 = 0, SEND_F1 = 1, SEND_BF16 = 2 };
+// the quad of columns c .. c + 3 (c a multiple of 4, c < w) of a row into the slots [s0, s1); v: the wire's values (zeros where it has them)
+template <int FORM>
+__device__ __forceinline__ void send_quad(const GemmSend &sd, uint32_t s0, uint32_t s1, uint32_t c, float4 v) {
+    if (FORM == SEND_BF16) {
+        const uint2 bits = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+        uint16_t *buf = reinterpret_cast<uint16_t *>(sd.buf);
+        for (uint32_t s = s0; s < s1; ++s) *reinterpret_cast<uint2 *>(buf + (size_t)sd.row_slots[s] * sd.w + c) = bits;
+    } else if (FORM == SEND_F4) {
+        for (uint32_t s = s0; s < s1; ++s) *reinterpret_cast<float4 *>(sd.buf + (size_t)sd.row_slots[s] * sd.w + c) = v;
+    } else {
+        const float e[4] = {v.x, v.y, v.z, v.w};
+        for (uint32_t s = s0; s < s1; ++s) {
+            float *p = sd.buf + (size_t)sd.row_slots[s] * sd.w + c;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k)
+                if (c + k < sd.w) p[k] = e[k];
+        }
+    }
+}
+// quads per row of a send form: those of the tensor (the parent's) or of the wire's row, whichever are more (a padded row: ld / 4)
+__host__ __device__ __forceinline__ uint32_t send_quads(uint32_t cols, uint32_t w) { return ((cols > w ? cols : w) + 3u) / 4u; }
+
+// g = aTg * (1 - tanh(z)^2) as tanh_backward_kernel, a float4 per lane
+template <int FORM>
+__global__ __launch_bounds__(256) void tanh_backward_send_kernel(uint64_t rows, uint32_t cols, const float *aTg, uint32_t lda, const float *z,
+                                                                 uint32_t ldz, float *g, uint32_t ldg, GemmSend sd) {
+    const uint32_t c4 = (cols + 3) / 4, q4 = send_quads(cols, sd.w);
+    const uint64_t n = rows * q4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = i / q4;
+        const uint32_t c = (uint32_t)(i % q4) * 4;
+        const uint32_t s0 = sd.row_ptr[r], s1 = sd.row_ptr[r + 1];
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < c4 * 4) {
+            const float4 a = *reinterpret_cast<const float4 *>(aTg + r * lda + c);
+            const float4 zz = *reinterpret_cast<const float4 *>(z + r * ldz + c);
+            float t;
+            t = dory_tanh(zz.x); o.x = a.x * (1.f - t * t);
+            t = dory_tanh(zz.y); o.y = a.y * (1.f - t * t);
+            t = dory_tanh(zz.z); o.z = a.z * (1.f - t * t);
+            t = dory_tanh(zz.w); o.w = a.w * (1.f - t * t);
+            *reinterpret_cast<float4 *>(g + r * ldg + c) = o;
+        }
+        if (s0 == s1 || c >= sd.w) continue;
+        if (FORM == SEND_BF16) {   // (the pack reads `cols` columns: zeros behind them)
+            if (c + 1 >= cols) o.y = 0.f;
+            if (c + 2 >= cols) o.z = 0.f;
+            if (c + 3 >= cols) o.w = 0.f;
+            if (c >= cols) o.x = 0.f;
+        }
+        send_quad<FORM>(sd, s0, s1, c, o);
+    }
+}
+
+// h = tanh(z) as tanh_forward_kernel, but a float4 per lane (ldz, ldh multiples of 4): columns >= cols of h are not written
+template <int FORM>
+__global__ __launch_bounds__(256) void tanh_forward_send_kernel(uint64_t rows, uint32_t cols, const float *z, uint32_t ldz, float *h, uint32_t ldh,
+                                                                GemmSend sd) {
+    const uint32_t q4 = send_quads(cols, sd.w);
+    const uint64_t n = rows * q4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = i / q4;
+        const uint32_t c = (uint32_t)(i % q4) * 4;
+        const uint32_t s0 = sd.row_ptr[r], s1 = sd.row_ptr[r + 1];
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < cols) {
+            const float4 zz = *reinterpret_cast<const float4 *>(z + r * ldz + c);   // (c + 3 < ldz: ldz >= cols, a multiple of 4)
+            float *hr = h + r * ldh + c;
+            o.x = dory_tanh(zz.x);
+            if (c + 3 < cols) {
+                o.y = dory_tanh(zz.y); o.z = dory_tanh(zz.z); o.w = dory_tanh(zz.w);
+                *reinterpret_cast<float4 *>(hr) = o;
+            } else {
+                hr[0] = o.x;
+                if (c + 1 < cols) hr[1] = o.y = dory_tanh(zz.y);
+                if (c + 2 < cols) hr[2] = o.z = dory_tanh(zz.z);
+            }
+        }
+        if (s0 == s1 || c >= sd.w) continue;
+        send_quad<FORM>(sd, s0, s1, c, o);
+    }
+}
+
+// softmax_xent_kernel<LPR> with the row's slots: lane c owns columns c, c + LPR, ... as there; the loop that stores the row runs to
+// the wire's width on every lane of the row's group, so that in the bf16 form an even lane can take its right neighbour's value by
+// DPP (lane_right: LPR is even, so column parity is lane parity and both lanes of a pair take every turn together) and store the
+// pair's dword
+template <int LPR, bool BF16>
+__global__ __launch_bounds__(256) void softmax_rows_send_kernel(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz, const float *lab,
+                                                                uint32_t ldl, float *d, uint32_t ldd, float inv_mode_denom, uint64_t mask_first,
+                                                                uint64_t mask_count, int sub_only, GemmSend sd) {
+    const int lane = threadIdx.x % LPR;
+    const uint32_t row = blockIdx.x * (256 / LPR) + threadIdx.x / LPR;
+    if (row >= rows) return;
+    const uint32_t s0 = sd.row_ptr[row], s1 = sd.row_ptr[row + 1];
+    const uint32_t slot0 = s0 != s1 ? sd.row_slots[s0] : 0u;   // (the first slot -- for most rows that travel the only one -- ahead of the arithmetic)
+    const float *zr = z + (size_t)row * ldz;
+    float mx = -INFINITY;
+    for (uint32_t c = lane; c < cols; c += LPR) mx = fmaxf(mx, zr[c]);
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float sum = 0.f;
+    for (uint32_t c = lane; c < cols; c += LPR) sum += expf(zr[c] - mx);
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum += 1e-20f;
+    const float *lr = lab + (size_t)row * ldl;
+    float *dr = d + (size_t)row * ldd;
+    const uint32_t cend = s0 != s1 && sd.w > cols ? sd.w : cols;   // (the same on every lane of the row)
+    for (uint32_t c0 = 0; c0 < cend; c0 += LPR) {
+        const uint32_t c = c0 + lane;
+        float v = 0.f;
+        if (c < cols) {
+            float p = expf(zr[c] - mx) / sum;
+            const float l = lr[c];
+            if (sub_only) {
+                v = p - l;
+            } else {
+                const uint64_t flat = (uint64_t)row * cols + c;
+                if (flat >= mask_first && flat - mask_first < mask_count) p = l;
+                v = (p - l) / inv_mode_denom;
+            }
+            dr[c] = v;
+        }
+        if (BF16) {
+            const uint32_t bits = pack_bf16x2(v, lane_right(v));
+            if (!(lane & 1) && c < sd.w) {
+                uint16_t *buf = reinterpret_cast<uint16_t *>(sd.buf);
+                if (s0 != s1) *reinterpret_cast<uint32_t *>(buf + (size_t)slot0 * sd.w + c) = bits;
+                for (uint32_t s = s0 + 1; s < s1; ++s) *reinterpret_cast<uint32_t *>(buf + (size_t)sd.row_slots[s] * sd.w + c) = bits;
+            }
+        } else if (c < sd.w) {
+            if (s0 != s1) sd.buf[(size_t)slot0 * sd.w + c] = v;
+            for (uint32_t s = s0 + 1; s < s1; ++s) sd.buf[(size_t)sd.row_slots[s] * sd.w + c] = v;
+        }
+    }
+}
+
+// the wire format a GemmSend asks of the tanh forms
+static int send_form(const GemmSend &sd) { return sd.bf16 ? SEND_BF16 : (sd.w & 3u) ? SEND_F1 : SEND_F4; }
+
+hipError_t launch_tanh_backward_send(uint64_t rows, uint32_t cols, const float *aTg, uint32_t lda, const float *z, uint32_t ldz, float *g,
+                                     uint32_t ldg, const GemmSend &sd, hipStream_t s, bool *fused) {
+    *fused = false;
+    if (rows == 0 || cols == 0 || ((lda | ldz | ldg) & 3u) || (sd.bf16 && (sd.w & 3u)))
+        return launch_tanh_backward(rows, cols, aTg, lda, z, ldz, g, ldg, s);
+    const uint64_t n = rows * send_quads(cols, sd.w);
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    switch (send_form(sd)) {
+    case SEND_F4: hipLaunchKernelGGL(tanh_backward_send_kernel<SEND_F4>, dim3(blocks), dim3(256), 0, s, rows, cols, aTg, lda, z, ldz, g, ldg, sd); break;
+    case SEND_F1: hipLaunchKernelGGL(tanh_backward_send_kernel<SEND_F1>, dim3(blocks), dim3(256), 0, s, rows, cols, aTg, lda, z, ldz, g, ldg, sd); break;
+    default: hipLaunchKernelGGL(tanh_backward_send_kernel<SEND_BF16>, dim3(blocks), dim3(256), 0, s, rows, cols, aTg, lda, z, ldz, g, ldg, sd); break;
+    }
+    *fused = true;
+    return hipGetLastError();
+}
+hipError_t launch_tanh_forward_send(uint64_t rows, uint32_t cols, const float *z, uint32_t ldz, float *h, uint32_t ldh, const GemmSend &sd,
+                                    hipStream_t s, bool *fused) {
+    *fused = false;
+    if (rows == 0 || cols == 0 || ((ldz | ldh) & 3u) || (sd.bf16 && (sd.w & 3u))) return launch_tanh_forward(rows, cols, z, ldz, h, ldh, s);
+    const uint64_t n = rows * send_quads(cols, sd.w);
+    const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    switch (send_form(sd)) {
+    case SEND_F4: hipLaunchKernelGGL(tanh_forward_send_kernel<SEND_F4>, dim3(blocks), dim3(256), 0, s, rows, cols, z, ldz, h, ldh, sd); break;
+    case SEND_F1: hipLaunchKernelGGL(tanh_forward_send_kernel<SEND_F1>, dim3(blocks), dim3(256), 0, s, rows, cols, z, ldz, h, ldh, sd); break;
+    default: hipLaunchKernelGGL(tanh_forward_send_kernel<SEND_BF16>, dim3(blocks), dim3(256), 0, s, rows, cols, z, ldz, h, ldh, sd); break;
+    }
+    *fused = true;
+    return hipGetLastError();
+}
+hipError_t launch_softmax_xent_send(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz, const float *lab, uint32_t ldl, float *d,
+                                    uint32_t ldd, float denom, uint32_t val_stt, uint32_t val_end, uint64_t mask_first, uint64_t mask_count,
+                                    float *stat, float *stat_partial, const GemmSend &sd, hipStream_t s, bool *fused) {
+    *fused = false;
+    if (rows == 0 || cols == 0 || (sd.bf16 && (sd.w & 3u)))
+        return launch_softmax_xent(rows, cols, z, ldz, lab, ldl, d, ldd, denom, val_stt, val_end, mask_first, mask_count, stat, stat_partial, s);
+    launch_train_stat(cols, z, ldz, lab, ldl, val_stt, val_end, stat, stat_partial, s);
+    launch_softmax_rows(rows, cols, z, ldz, lab, ldl, d, ldd, denom, mask_first, mask_count, 0, s, &sd);
+    *fused = true;
+    return hipGetLastError();
+}
+hipError_t launch_softmax_sub_send(uint32_t rows, uint32_t cols, const float *z, uint32_t ldz, const float *lab, uint32_t ldl, float *out,
+                                   uint32_t ldo, const GemmSend &sd, hipStream_t s, bool *fused) {
+    *fused = false;
+    if (rows == 0 || cols == 0 || (sd.bf16 && (sd.w & 3u))) return launch_softmax_sub(rows, cols, z, ldz, lab, ldl, out, ldo, s);
+    launch_softmax_rows(rows, cols, z, ldz, lab, ldl, out, ldo, 1.f, 0, 0, 1, s, &sd);
+    *fused = true;
     return hipGetLastError();
 }
 

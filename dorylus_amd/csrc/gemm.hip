@@ -107,11 +107,6 @@ __device__ __forceinline__ void send_store16(const GemmSend &sd, uint32_t row, u
     const uint32_t s1 = sd.row_ptr[row + 1];
     for (uint32_t s = sd.row_ptr[row]; s < s1; ++s) *reinterpret_cast<uint32_t *>(buf + (size_t)sd.row_slots[s] * sd.w + col) = bits;
 }
-// the value of the lane to the right within a pair of lanes (DPP quad_perm [1, 1, 3, 3]; lanes 1 and 3 of a quad read themselves):
-// to be called where both lanes of every pair are active
-__device__ __forceinline__ float lane_right(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xF5, 0xF, 0xF, true));
-}
 
 // SEND (the fused halo pack, dory_halo_fused_pack): the epilogue stores every element of a row once more into each of the row's
 // slots of the packed send buffer -- what gather_rows_kernel would copy out of C (or of the tanh output C2) afterwards.  Columns

@@ -232,7 +232,8 @@ int dory_halo_unpack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int
  * plan, by dory_halo_fused_pack(ctx, 0), by any dory_comm_* call; a second producer of the same tensor replaces it.  Once
  * dory_tensor_info has handed out a source tensor's device pointer that tensor never fuses again on this context (its rows may
  * change behind the library's back).  Not taken, i.e. a counted fallback with the same results: sources no GEMM writes (h of a
- * transform-first layer, g, the GAT models' last-layer grad, do / st), a product with K == 0 or no local rows, the scatter
+ * transform-first layer, g, the GAT prototype's last-layer grad -- unless dory_halo_fused_pack_rowwise, below -- and the multi-head
+ * GAT's do / st, always), a product with K == 0 or no local rows, the scatter
  * transport (another buffer layout), the in-process transport with halo_direct_recv = 1 (the peers read the send buffer on their
  * own streams), epoch-graph recording.  dory_halo_pack* always run the kernel into the caller's buffer and leave the stamp
  * alone.  The producer waits for the previous exchange (as dory_apply_vertex does anyway) before its epilogue writes the
@@ -370,6 +371,64 @@ int dory_halo_wire_row(dory_ctx *ctx, uint32_t layer, int dir, uint32_t *elem_by
  * process ran first of each pair and inside or below it when it ran second (same file, section 3: the position, not the library). */
 int dory_halo_fused_pack_bf16(dory_ctx *ctx, int on);   /* 0 (default) / 1 */
 int dory_halo_fused_pack_bf16_stats(dory_ctx *ctx, uint64_t *fused_bf16_exchanges, uint64_t *fused_bf16_rows);
+
+/* ---- fused halo pack for rows the row-wise kernels produce (opt-in, default off; nothing in the reference) ----
+ * The fused pack removes the pack kernel only where a K2 GEMM wrote the rows that travel.  With gcn_transform_first = 2, the
+ * fastest configuration, a 2-layer GCN makes three exchanges an epoch and two of them ship g, which no GEMM writes.  With this
+ * switch on, the row-wise kernels that produce the source of an exchange run SEND FORMS (kernels of their own in
+ * csrc/elementwise.hip -- tanh_backward_send_kernel, tanh_forward_send_kernel, softmax_rows_send_kernel; every other kernel keeps
+ * its code object) that compute and store the tensor exactly as the plain kernel does and store every row once more into the row's
+ * slots of the send buffer, in the wire format of the moment: fp32 padded (ld floats, the zeros of the padding behind cols), fp32
+ * exact (cols floats, dense), or bf16 (row_elems elements rounded with the pack's conversion, zeros in [cols, row_elems)) -- byte
+ * for byte what the pack kernel would leave; every tensor keeps its bits.  Fused:
+ *     dory_apply_vertex, GCN backward            g@l         travels backward when layer l is transform-first   (tanh backward)
+ *     dory_apply_vertex, GCN last layer forward  g@(L-1)     travels backward when the last layer is            (softmax + loss)
+ *     dory_apply_vertex, GCN hidden transform-first layer    h@l travels forward when layer l + 1 is not        (tanh forward)
+ *     dory_predict_gat, GAT prototype            grad@(L-1)  travels backward                                   (softmax - label)
+ * Each asks the question the GEMMs ask (same target, width, element kind and capacity rule), waits for the previous exchange
+ * before the buffer is written, and leaves the one stamp -- which now also records who made it.  The switch has an effect only
+ * while dory_halo_fused_pack is 1; an exchange that ships bf16 rows is fused by a row-wise producer only if
+ * dory_halo_fused_pack_bf16 is 1 too.  Everything that drops or mismatches a GEMM's stamp does so with these (upload, fill, another
+ * exchange, a new plan, halo_exact_rows or a wire switch changed, the raw pointer handed out: counted fallbacks with the rows of the
+ * moment); a producer that runs its plain kernel drops a stamp that names its tensor.
+ * Not taken: the multi-head GAT's do / st (two exchanges in a row through one send buffer with one stamp, and no (layer, direction)
+ * of dory_halo_exchange names them): they keep packing.  A one-column tensor (ld == 1).  Everything the fused pack does not take.
+ * Counters: a consumed stamp of a row-wise producer moves rowwise_exchanges / rowwise_rows IN ADDITION to fused_exchanges /
+ * fused_rows, and for a bf16 wire to fused_bf16_* and bf16_packs / bf16_bytes, exactly as a GEMM-made one.  Eager calls only, since
+ * dory_create; any pointer may be NULL.
+ * dory_halo_fused_pack_rowwise: on = 0 (default) / 1, any time after dory_configure, outside an exchange; drops the stamp; accepted
+ * and inert with num_nodes == 1; DORY_ERR_ARG for other values, before dory_configure, or while an epoch graph is being recorded.
+ * Forms: tanh_backward keeps its parent's float4 per lane (bf16: one 8-byte store per slot); tanh_forward takes a float4 per lane
+ * where its parent takes one element (the DPP pair form was not built: no probe compares the two); the softmax forms keep lane c on
+ * columns c, c + LPR, ... and form bf16 pairs by DPP.  A row's slot range is loaded once per lane and quad (softmax: per lane and
+ * row), outside every element loop, and the softmax forms fetch the first slot ahead of the arithmetic (before that they were
+ * x1.01-1.09 on every bf16 line below).
+ * Measured on one MI355X (profiles/r22_halo_fused_pack_rowwise.txt, profiles/HISTORY.md section 23; tools/halo_fused_rowwise_rate.py;
+ * NO LINK AND NO MULTI-RANK RCCL RUN IS BEHIND ANY NUMBER), 1.05 M local rows, every row to 1 peer / to 3 peers, each step a child
+ * process, the parent commit's library (plain producer + pack kernel) and this one (send producer alone) alternated over three
+ * rounds; send / pair, medians:
+ *                        padded 1 / 3     exact 1 / 3      bf16 1 / 3
+ *     tanh_backward 128  x0.71 / x0.68    x0.71 / x0.68    x0.70 / x0.63         (0.537 -> 0.380 ms ... 0.743 -> 0.467)
+ *     tanh_backward 64   x0.73 / x0.69    x0.72 / x0.71    x0.72 / x0.65
+ *     tanh_backward 48   x0.69 / x0.68    x0.71 / x0.77    x0.68 / x0.68
+ *     tanh_backward 41   x0.71 / x0.67    x0.66 / x0.74    x0.71 / x0.71
+ *     tanh_forward 128   x0.66 / x0.67    x0.66 / x0.69    x0.60 / x0.56
+ *     tanh_forward 64    x0.68 / x0.73    x0.66 / x0.74    x0.59 / x0.58
+ *     tanh_forward 48    x0.75 / x0.78    x0.72 / x0.82    x0.64 / x0.67
+ *     tanh_forward 41    x0.71 / x0.74    x0.75 / x0.89    x0.64 / x0.64
+ *     softmax_xent 41    x0.92 / x0.88    x0.80 / x0.72    x0.95 / x0.97
+ *     softmax_xent 16    x1.03 / x0.97    x0.99 / x0.90    x1.04 / x1.05
+ *     softmax_xent 64    x1.03 / x0.98    x1.05 / x1.01    x1.09 / x1.08
+ *     softmax_sub 41     x0.88 / x0.92    x0.75 / x0.82    x0.91 / x1.03
+ *     softmax_sub 16     x1.00 / x0.94    x0.98 / x0.86    x1.03 / x1.03
+ *     softmax_sub 64     x1.02 / x0.98    x1.04 / x1.01    x1.08 / x1.08
+ * The tanh forms gain at every shape.  NOT FASTER, NAMED: the softmax forms at 64 classes (every line but the padded one with three
+ * peers: +1-9 %), at 16 classes under a bf16 wire (+3-5 %) and padded with one peer (+0-3 %), and softmax_sub 41 bf16 with three
+ * peers (+3 %): a softmax row is held by 8-64 lanes that store dwords, and the slot loads sit at the end of a latency-bound kernel.
+ * They are TAKEN all the same -- one rule per switch, and these lines have every row travelling, where a partition sends a
+ * fraction of its rows -- so a caller whose last layer is that wide and whose rows mostly travel should leave the switch off. */
+int dory_halo_fused_pack_rowwise(dory_ctx *ctx, int on);   /* 0 (default) / 1 */
+int dory_halo_fused_pack_rowwise_stats(dory_ctx *ctx, uint64_t *rowwise_exchanges, uint64_t *rowwise_rows);
 
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows

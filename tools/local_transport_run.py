@@ -18,7 +18,9 @@ library.  Each run then also records every rank's receive-buffer bytes where the
 dory_halo_fused_pack on on every rank and records its counters (exchanges fused, their rows, fallbacks) per rank; --bf16-rows switches
 dory_halo_bf16_rows on on every rank (with --opt gcn_bf16_gather=1 or 2) and records its counters (bf16 packs, their bytes, fp32 packs);
 --bf16-ghosts switches dory_halo_bf16_ghosts on on top of it and records its counters per rank; with either, the timing key
-"bf16_convert" (the conversions of the aggregations on bf16 rows: ms and launches, summed over the ranks) is recorded too."""
+"bf16_convert" (the conversions of the aggregations on bf16 rows: ms and launches, summed over the ranks) is recorded too.
+--fused-rowwise switches dory_halo_fused_pack_rowwise on on top of --fused-pack and records its counters per rank and the timing key
+"loss" (the row-wise producers: tanh, softmax + loss), summed over the ranks."""
 import argparse
 import json
 import os
@@ -44,6 +46,7 @@ def main():
     ap.add_argument("--fused-pack", action="store_true", help="dory_halo_fused_pack(1) on every rank")
     ap.add_argument("--bf16-rows", action="store_true", help="dory_halo_bf16_rows(1) on every rank")
     ap.add_argument("--bf16-ghosts", action="store_true", help="dory_halo_bf16_ghosts(1) on every rank (with --bf16-rows)")
+    ap.add_argument("--fused-rowwise", action="store_true", help="dory_halo_fused_pack_rowwise(1) on every rank (with --fused-pack)")
     a = ap.parse_args()
     import torch  # noqa: F401
     import dorylus_amd as da
@@ -58,6 +61,7 @@ def main():
 
     extra = {k: int(v) for k, v in (kv.split("=", 1) for kv in a.opt)}
     recv_bytes, fused_stats, bf16_stats, ghost_stats, convert = {}, {}, {}, {}, {}
+    rowwise_stats, loss = {}, {}
 
     def setup(ctx, r, g):
         close = ctx.close
@@ -70,6 +74,9 @@ def main():
                     recv_bytes[r] = None      # (a library from before the counter)
                 if a.fused_pack:
                     fused_stats[r] = list(ctx.halo_fused_pack_stats())
+                    loss[r] = ctx.timing_get("loss")
+                if a.fused_rowwise:
+                    rowwise_stats[r] = list(ctx.halo_fused_pack_rowwise_stats())
                 if a.bf16_rows:
                     bf16_stats[r] = list(ctx.halo_bf16_rows_stats())
                     convert[r] = ctx.timing_get("bf16_convert")
@@ -79,6 +86,8 @@ def main():
         ctx.close = closing
         if a.fused_pack:
             ctx.halo_fused_pack(1)
+        if a.fused_rowwise:
+            ctx.halo_fused_pack_rowwise(1)
         if a.bf16_rows:
             ctx.halo_bf16_rows(1)
         if a.bf16_ghosts:
@@ -113,7 +122,7 @@ def main():
         configs = [c for c in configs if c[0] in a.configs]
     with_extra = lambda sh: [dict(x, **extra) for x in sh] if isinstance(sh, list) else dict(sh, **extra)
     configs = [(name, P, parts, with_extra(share)) for name, P, parts, share in configs]
-    out["options"] = dict(extra, fused_pack=int(a.fused_pack), bf16_rows=int(a.bf16_rows), bf16_ghosts=int(a.bf16_ghosts))
+    out["options"] = dict(extra, fused_pack=int(a.fused_pack), fused_rowwise=int(a.fused_rowwise), bf16_rows=int(a.bf16_rows), bf16_ghosts=int(a.bf16_ghosts))
     for name, P, parts, share in ([] if a.skip_oracle else [c for c in configs if c[0] == "balanced"]):
         pobjs = [da.Partition.build(src, dst, parts, r, P) for r in range(P)]
         dl = [(l, nm) for l in range(L) for nm in ("ah",)] + [(l, nm) for l in range(L - 1) for nm in ("h", "aTg")] + [(l, "grad") for l in range(1, L)]
@@ -148,6 +157,8 @@ def main():
                    "halo_overlap_fraction": round(tm["halo_hidden"]["ms"] / tm["halo_deferred"]["ms"], 4) if tm["halo_deferred"]["ms"] else None,
                    "spmm_gates": res["gates"], "recv_buf_bytes_per_rank": [recv_bytes.get(r) for r in range(P)],
                    "fused_pack_stats_per_rank": [fused_stats.get(r) for r in range(P)] if a.fused_pack else None,
+                   "fused_rowwise_stats_per_rank": [rowwise_stats.get(r) for r in range(P)] if a.fused_rowwise else None,
+                   "loss_sum_over_ranks": {"ms": round(sum(loss[r][0] for r in range(P)), 4), "launches": sum(loss[r][1] for r in range(P))} if a.fused_pack else None,
                    "bf16_rows_stats_per_rank": [bf16_stats.get(r) for r in range(P)] if a.bf16_rows else None,
                    "bf16_ghosts_stats_per_rank": [ghost_stats.get(r) for r in range(P)] if a.bf16_ghosts else None,
                    "bf16_convert_sum_over_ranks": {"ms": round(sum(convert[r][0] for r in range(P)), 4), "launches": sum(convert[r][1] for r in range(P))} if a.bf16_rows else None,
