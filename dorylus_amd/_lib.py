@@ -34,6 +34,8 @@ SYMBOLS = [
     "dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek",
     "dory_halo_fused_pack_bf16", "dory_halo_fused_pack_bf16_stats",
     "dory_halo_fused_pack_rowwise", "dory_halo_fused_pack_rowwise_stats",
+    "dory_gatmh_bwd_merged_exchange", "dory_gatmh_bwd_merged_exchange_stats", "dory_gatmh_bwd_wire_row", "dory_gatmh_bwd_pack",
+    "dory_gatmh_bwd_unpack",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -136,6 +138,11 @@ def load():
         "dory_halo_fused_pack_bf16_stats": [vp, C.POINTER(u64), C.POINTER(u64)],
         "dory_halo_fused_pack_rowwise": [vp, i32],
         "dory_halo_fused_pack_rowwise_stats": [vp, C.POINTER(u64), C.POINTER(u64)],
+        "dory_gatmh_bwd_merged_exchange": [vp, i32],
+        "dory_gatmh_bwd_merged_exchange_stats": [vp] + [C.POINTER(u64)] * 4,
+        "dory_gatmh_bwd_wire_row": [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
+        "dory_gatmh_bwd_pack": [vp, u32, vp],
+        "dory_gatmh_bwd_unpack": [vp, u32, vp],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -170,8 +177,9 @@ def load():
                      "dory_comm_set_scatter_transport", "dory_halo_send_map") or name.startswith("dory_scatter_msgs_")
                 or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
                 or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")
-                or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form)
+                or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")
+                or name.startswith("dory_gatmh_bwd_")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -604,6 +612,34 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         self._ck(self.lib.dory_halo_fused_pack_rowwise_stats(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def gatmh_bwd_merged_exchange(self, on=True):
+        """the multi-head GAT's backward sweep ships do and st of a sent vertex as ONE merged row [do | st] in one exchange instead of
+        two (opt-in; dory_gatmh_bwd_merged_exchange); with halo_fused_pack on and the sweep forms running, the row-wise kernel that
+        produces st writes the send rows itself and no pack kernel runs.  All ranks must set the same value"""
+        self._ck(self.lib.dory_gatmh_bwd_merged_exchange(self.h, int(on)))
+
+    def gatmh_bwd_merged_exchange_stats(self):
+        """(merged exchanges made, their send rows, those of them whose rows the producer wrote, backward passes that kept the two
+        exchanges although the switch was on)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._ck(self.lib.dory_gatmh_bwd_merged_exchange_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def gatmh_bwd_wire_row(self, layer):
+        """(floats per merged row, of which do, of which st) of the tensors' layer `layer`, as the wire stands now"""
+        r, d, s = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._ck(self.lib.dory_gatmh_bwd_wire_row(self.h, layer, C.byref(r), C.byref(d), C.byref(s)))
+        return r.value, d.value, s.value
+
+    def gatmh_bwd_pack(self, layer, dev_ptr):
+        """the backward plan's send rows of do / st of `layer` as merged rows into a device buffer (option gatmh_bwd_phase = 1 / 2:
+        the caller moves them)"""
+        self._ck(self.lib.dory_gatmh_bwd_pack(self.h, layer, C.c_void_p(dev_ptr)))
+
+    def gatmh_bwd_unpack(self, layer, dev_ptr):
+        """received merged rows out of a device buffer into bg_do / bg_st of `layer`, whole ghost rows (padding zeroed)"""
+        self._ck(self.lib.dory_gatmh_bwd_unpack(self.h, layer, C.c_void_p(dev_ptr)))
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

@@ -91,14 +91,26 @@ int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghos
     return DORY_OK;
 }
 
+// dory_gatmh_bwd_merged_exchange: the merged row [do[v, 0:w) | st[v, 0:4K)] -- w = ld floats of do, or with halo_exact_rows its cols
+// rounded up to a multiple of 4 (the columns past cols are the tensor's zero padding, as in the bf16 rows' rule); always fp32
+// (halo_ships_bf16: never the multi-head GAT); R = w + 4K is a multiple of 4, so every row starts on a 16-byte boundary
+inline RowWire pair_wire(const dory_ctx *c, const Tensor *rows, const Tensor *rows2) {
+    RowWire out;
+    out.exact = halo_exact(c);
+    out.w = out.exact ? std::min((rows->cols + 3u) & ~3u, rows->ld) : rows->ld;
+    out.w2 = rows2->cols;
+    return out;
+}
+
 // dory_halo_bf16_rows: an eager exchange or pack that ships fp32 rows while the switch is on (section "not taken" of dorylus_hip.h)
 inline void fp32_while_on(dory_ctx *c) {
     if (!c->capturing && c->halo_bf16.load(std::memory_order_acquire) == 1) c->halo_fp32_packs_while_on++;
 }
-// the plan's send rows of `src`, dense at the wire's width, into dst; counted (eager calls)
-int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const HaloPlan &p, hipStream_t s) {
+// the plan's send rows of `src`, dense at the wire's width, into dst; counted (eager calls); merged rows (wire.w2): those of src2 behind them
+int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const HaloPlan &p, hipStream_t s, const Tensor *src2 = nullptr) {
     if (dst == c->send_buf) fused_stamp_drop(c);   // (the fused halo pack: whatever a GEMM left in the internal buffer is overwritten)
-    if (wire.bf16) HIPCK(c, launch_gather_rows_bf16(dst, src->d, src->ld, wire.cols, wire.w, p.d_send_lvids, p.send_total, s));
+    if (wire.w2) HIPCK(c, launch_gather_rows_pair(dst, src->d, src->ld, wire.w, src2->d, src2->ld, wire.w2, p.d_send_lvids, p.send_total, s));
+    else if (wire.bf16) HIPCK(c, launch_gather_rows_bf16(dst, src->d, src->ld, wire.cols, wire.w, p.d_send_lvids, p.send_total, s));
     else if (wire.exact && (wire.w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
     else HIPCK(c, launch_gather_rows(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
     if (!c->capturing) {
@@ -115,7 +127,23 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
 // has them -- the producer's epilogue wrote them -- and then no kernel runs and the stamp is consumed; with the
 // feature on every other exchange is a counted fallback (`may_fuse` false: an arm that never takes them, section "not taken" of
 // dorylus_hip.h).
-int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloPlan &p, hipStream_t s, bool may_fuse) {
+// dory_gatmh_bwd_merged_exchange (`pair`): the producer wrote the merged rows inside this very call of dory_aggregate -- no stamp --
+// or the pair kernel packs them; the fused pack counts the one as a fused exchange, the other as a fallback.
+int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloPlan &p, hipStream_t s, bool may_fuse, const RowPair *pair = nullptr) {
+    if (pair) {
+        if (!c->capturing) {
+            c->merged_exchanges++;
+            c->merged_rows += p.send_total;
+            if (pair->producer_packed) c->merged_producer_packed++;
+            if (c->fused_pack) {
+                if (pair->producer_packed) { c->fused_exchanges++; c->fused_rows += p.send_total; }
+                else c->fallback_exchanges++;
+            }
+        }
+        if (!pair->producer_packed) return pack_rows(c, c->send_buf, src, wire, p, s, pair->src2);
+        fp32_while_on(c);
+        return DORY_OK;
+    }
     if (c->fused_pack) {
         const FusedStamp &st = c->fused_stamp;
         if (may_fuse && st.src == src && st.dir == dir && st.bf16 == wire.bf16 && (!wire.bf16 || st.cols == wire.cols) && st.w == wire.w &&
@@ -148,8 +176,12 @@ int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloP
 // the padding held before
 // dory_halo_bf16_ghosts (`twin` not null: the rows are bf16 and stay bf16): the keep form copies them into the twin's rows instead,
 // zeros in [w, ld); `ghost` is not touched
-int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s, uint16_t *twin = nullptr) {
-    if (twin) {
+// merged rows (wire.w2): whole rows of both ghost tensors, ghost2 at stride ld2 behind the first
+int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s, uint16_t *twin = nullptr,
+                float *ghost2 = nullptr, uint32_t ld2 = 0) {
+    if (wire.w2) {
+        HIPCK(c, launch_scatter_rows_pair(ghost, ld, wire.w, ghost2, ld2, wire.w2, buf, p.d_unpack_slots, p.recv_total, s));
+    } else if (twin) {
         HIPCK(c, launch_scatter_rows_bf16_keep(twin, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
     } else if (wire.bf16) {   // (the whole ld-wide row: widened values, zeros behind them)
         HIPCK(c, launch_scatter_rows_bf16(ghost, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
@@ -574,7 +606,7 @@ int local_pull_send(dory_ctx *c, int dir, const HaloPlan &p, Tensor *src, RowWir
 
 // first half of an exchange: pack, push my rows into every peer's receive buffer, "sent"; the second half
 // (local_exchange_finish, below) at once, or with `deferred` when wait_halo() is next called
-int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wire, bool deferred) {
+int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wire, bool deferred, const RowPair *pair) {
     HaloPlan &p = c->plan[dir];
     LocalGroup &grp = *c->local;
     const size_t rb = wire.row_bytes();
@@ -587,7 +619,7 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     timed_open(c, "halo", c->comm, &lp.t_halo_b);
     timed_open(c, deferred ? "halo_deferred" : "halo_waited", c->comm, &lp.t_kind_b);
     if (p.direct) { int rc = local_pull_send(c, dir, p, src, wire, s); if (rc) return rc; }
-    else { int rc = send_rows(c, src, dir, wire, p, c->comm, true); if (rc) return rc; }
+    else { int rc = send_rows(c, src, dir, wire, p, c->comm, true, pair); if (rc) return rc; }
     for (uint32_t q = 0; q < c->numNodes && !p.direct; ++q) {
         if (q == c->nodeId || !p.send_counts[q]) continue;
         dory_ctx *Q = grp.ctx[q];
@@ -613,6 +645,8 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     lp.keep = keeps_bf16(c, wire, ghost);
     lp.ghost = lp.keep ? reinterpret_cast<char *>(ghost->twin) : reinterpret_cast<char *>(ghost->d);
     lp.ghost_ld = ghost->ld;
+    lp.ghost2 = pair ? pair->ghost2->d : nullptr;
+    lp.ghost2_ld = pair ? pair->ghost2->ld : 0;
     lp.wire = wire;
     lp.direct = lands_directly(p, wire, ghost->ld, lp.keep);
     lp.widen_to = lp.keep && ghost->raw_handed ? ghost->d : nullptr;
@@ -786,7 +820,7 @@ int local_exchange_finish(dory_ctx *c) {
     }
     if (!lp.direct) {
         int rc = unpack_rows(c, lp.keep ? nullptr : reinterpret_cast<float *>(lp.ghost), lp.ghost_ld, lp.wire, c->recv_buf, p, c->comm,
-                             lp.keep ? reinterpret_cast<uint16_t *>(lp.ghost) : nullptr);
+                             lp.keep ? reinterpret_cast<uint16_t *>(lp.ghost) : nullptr, lp.ghost2, lp.ghost2_ld);
         if (rc) return rc;
     }
     // (dory_halo_bf16_ghosts, the tensor's raw pointer is out: its fp32 rows follow the twin at once)
@@ -817,7 +851,9 @@ int wait_halo(dory_ctx *c) {
 // One all-to-all-v of rows: src rows listed in plan[dir] -> the peers' ghost tensors.  pack -> the transport's arm ->
 // unpack on the comm stream, ordered after the compute stream's work so far; the compute stream waits for the ghosts
 // at once (defer == false) or when wait_halo() is next called (halo_overlap).
-int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) {
+// `pair` (dory_gatmh_bwd_merged_exchange; gatmh_bwd_exchange has checked transport and plan): merged rows [src | pair->src2] into
+// ghost and pair->ghost2 -- the same arms, a row of w + w2 floats.
+int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, const RowPair *pair) {
     HaloPlan &p = c->plan[dir];
     if (!p.set) return fail(c, DORY_ERR_ARG, "halo_exchange: no plan");
     const Transport tr = transport_of(c);
@@ -843,6 +879,11 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     }
     RowWire wire;
     { int rc = row_wire(c, "halo_exchange", src, ghost, true, nullptr, dir, &wire); if (rc) return rc; }
+    if (pair) {
+        if (p.direct || wire.bf16 || pair->src2->ld != pair->ghost2->ld || pair->src2->cols != pair->ghost2->cols)
+            return fail(c, DORY_ERR_ARG, "halo_exchange: merged rows need a plan without halo_direct_recv and two tensors of one shape at either end");
+        wire = pair_wire(c, src, pair->src2);
+    }
     const uint32_t w = wire.w;
     const size_t row_b = wire.row_bytes();
     if (tr == Transport::Local) {   // every rank packs and unpacks at one width: checked here, before anything of this exchange is enqueued or counted
@@ -882,17 +923,20 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
     const bool deferred = defer && c->opt[OPT_HALO_OVERLAP];
     (direct ? c->halo_direct_recvs : c->halo_staged_recvs) += 1;
-    if (tr == Transport::Local) return exchange_local(c, dir, src, ghost, wire, deferred);
+    if (tr == Transport::Local) return exchange_local(c, dir, src, ghost, wire, deferred, pair);
     {   // host transport and RCCL: same pack / unpack / events, only the way from send_buf to recv_buf differs
         Timed t(c, "halo", c->comm);
         Timed td(c, deferred ? "halo_deferred" : "halo_waited", c->comm);   // (overlap bookkeeping: abi_internal.hpp)
-        int rc = send_rows(c, src, dir, wire, p, c->comm, true);
+        int rc = send_rows(c, src, dir, wire, p, c->comm, true, pair);
         // (dory_halo_bf16_ghosts: bf16 rows that land directly land in the twin -- ld / 2 floats' worth of bytes a row)
         float *recv = !direct ? c->recv_buf : keep ? reinterpret_cast<float *>(ghost->twin) : ghost->d;
         const uint32_t wf = (uint32_t)(row_b / sizeof(float));
         if (!rc) rc = tr == Transport::Host ? exchange_host(c, p, wf, recv) : exchange_rccl(c, p, wf, recv);
-        if (!rc && !direct) rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm, keep ? ghost->twin : nullptr);
+        if (!rc && !direct)
+            rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm, keep ? ghost->twin : nullptr, pair ? pair->ghost2->d : nullptr,
+                             pair ? pair->ghost2->ld : 0);
         if (!rc) rc = ghost_rows_landed(c, ghost, keep, direct, c->comm, true);
+        if (!rc && pair) ghost_wrote_fp32(pair->ghost2);
         if (rc) return rc;
         // the one step of an arm left in the shared body: the host arm's, but it stays behind the unpack, so that the unpack
         // is enqueued before the host blocks for the copy out of tx_recv (which the next exchange reuses)
@@ -902,6 +946,62 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer) 
     if (deferred) c->halo_pending = true;
     else HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
     return DORY_OK;
+}
+
+// ---- dory_gatmh_bwd_merged_exchange: do -> bg_do and st -> bg_st between the two phases of a whole backward sweep --------------
+// the widest merged row any layer of the model ships, padded wire (what dory_halo_plan and the setter size the buffers by)
+uint32_t gatmh_merged_row_max(const dory_ctx *c) {
+    uint32_t r = 0;
+    for (uint32_t l = 0; l < c->L && l < c->heads.size() && l + 1 < c->dims.size(); ++l) {
+        const uint32_t K = c->heads[l], zw = l == c->L - 1 ? c->dims[l + 1] * K : c->dims[l + 1];
+        r = std::max(r, pad_ld(zw) + 4 * K);
+    }
+    return r;
+}
+// the merged exchange is taken: the switch, a whole sweep, a transport that moves dense rows, a plan whose received rows go through
+// the receive buffer (halo_direct_recv lands rows in ONE tensor)
+static bool gatmh_merged_taken(const dory_ctx *c) {
+    if (c->gatmh_merged.load(std::memory_order_acquire) != 1 || c->opt[OPT_GATMH_BWD_PHASE] != 0 || c->numNodes <= 1) return false;
+    const Transport tr = transport_of(c);
+    return (tr == Transport::Rccl || tr == Transport::Host || tr == Transport::Local) && c->plan[DORY_BACKWARD].set && !c->plan[DORY_BACKWARD].direct;
+}
+int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, GatmhSend *sd, bool *send) {
+    const HaloPlan &p = c->plan[DORY_BACKWARD];
+    *send = false;
+    if (!gatmh_merged_taken(c) || !c->fused_pack || c->capturing || !p.d_send_map || p.send_map_rows != c->N || dO->rows != c->N) return DORY_OK;
+    const RowWire wire = pair_wire(c, dO, st);
+    if ((size_t)p.send_total * wire.row_bytes() > c->send_cap) return DORY_OK;   // (the exchange would regrow the buffer)
+    if (transport_of(c) == Transport::Local)   // (its refusal comes from gatmh_bwd_exchange, before anything is written)
+        for (uint32_t q = 0; q < c->numNodes; ++q) {
+            const dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
+            if (Q && Q->gatmh_merged.load(std::memory_order_acquire) != 1) return DORY_OK;
+        }
+    sd->buf = c->send_buf;
+    sd->row_ptr = p.d_send_map;
+    sd->row_slots = p.d_send_map + c->N + 1;
+    sd->w = wire.w;
+    sd->R = wire.w + wire.w2;
+    fused_stamp_drop(c);   // (whatever a GEMM left in the send buffer is about to be overwritten)
+    *send = true;
+    return wait_halo(c);   // the previous exchange has finished reading the buffer
+}
+int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor *bgst, bool producer_packed) {
+    const int on = c->gatmh_merged.load(std::memory_order_acquire);
+    if (transport_of(c) == Transport::Local)   // every rank ships one row format: checked before anything of this pass is enqueued or counted
+        for (uint32_t q = 0; q < c->numNodes; ++q) {
+            const dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
+            if (Q && Q->gatmh_merged.load(std::memory_order_acquire) != on)
+                return fail(c, DORY_ERR_COMM, "local transport: dory_gatmh_bwd_merged_exchange differs: rank %u has %d, rank %u has %d (all ranks must agree)",
+                            c->nodeId, on, q, 1 - on);
+        }
+    if (gatmh_merged_taken(c)) {
+        RowPair pair;
+        pair.src2 = st; pair.ghost2 = bgst; pair.producer_packed = producer_packed;
+        return exchange_rows(c, DORY_BACKWARD, dO, bgdo, false, &pair);
+    }
+    if (on == 1 && !c->capturing) c->merged_split_fallbacks++;   // (the scatter transport: its own layout; halo_direct_recv: two tensors)
+    int rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, false);
+    return rc ? rc : exchange_rows(c, DORY_BACKWARD, st, bgst, false);
 }
 
 bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd, int *dir) {
@@ -1107,6 +1207,8 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
     // (option halo_direct_recv: padded rows land in the ghost tensors; only exact rows narrower than their padding -- option
     // halo_exact_rows, as it stands now -- are staged)
     w = std::max(w, 2u);   // (dory_halo_bf16_rows: a one-column row travels as 4 bf16)
+    if (c->gnn == DORY_GATMH && dir == DORY_BACKWARD && !p.direct && c->gatmh_merged.load(std::memory_order_acquire) == 1)
+        w = std::max(w, gatmh_merged_row_max(c));   // (dory_gatmh_bwd_merged_exchange: [do | st] rows)
     const bool staged = !p.direct || halo_exact(c);
     return ensure_exchange_buffers(c, (size_t)p.send_total * w * sizeof(float), staged ? (size_t)p.recv_total * w * sizeof(float) : 0);
 }
@@ -1295,6 +1397,91 @@ int dory_halo_fused_pack_rowwise_stats(dory_ctx *c, uint64_t *rowwise_exchanges,
     if (rowwise_exchanges) *rowwise_exchanges = c->rowwise_exchanges;
     if (rowwise_rows) *rowwise_rows = c->rowwise_rows;
     return DORY_OK;
+}
+
+// ---- the multi-head GAT's merged backward exchange: switch, counters, and the split entry points (include/dorylus_hip.h) ----------
+int dory_gatmh_bwd_merged_exchange(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || c->gnn != DORY_GATMH || (on != 0 && on != 1))
+        return fail(c, DORY_ERR_ARG, "gatmh_bwd_merged_exchange: a context configured as DORY_GATMH; on is 0 or 1");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_bwd_merged_exchange: not while an epoch graph is being recorded");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    const HaloPlan &p = c->plan[DORY_BACKWARD];
+    if (on && c->numNodes > 1 && p.set && !p.direct) {   // a backward plan that exists already: the buffers hold its widest merged rows from now on -- never a regrowth inside an epoch
+        const size_t rb = (size_t)gatmh_merged_row_max(c) * sizeof(float);
+        const size_t sb = (size_t)p.send_total * rb, rcb = (size_t)p.recv_total * rb;
+        if (c->local && (sb > c->send_cap || rcb > c->recv_cap))
+            return fail(c, DORY_ERR_ARG, "gatmh_bwd_merged_exchange: the exchange buffers are too small for merged rows and the in-process peers hold "
+                        "their addresses: call it before dory_comm_init_local");
+        int rc = ensure_exchange_buffers(c, sb, rcb);
+        if (rc) return rc;
+    }
+    c->gatmh_merged.store(on, std::memory_order_release);
+    return DORY_OK;
+}
+
+int dory_gatmh_bwd_merged_exchange_stats(dory_ctx *c, uint64_t *merged_exchanges, uint64_t *merged_rows, uint64_t *producer_packed,
+                                         uint64_t *split_fallbacks) {
+    CHECK_CTX(c);
+    if (merged_exchanges) *merged_exchanges = c->merged_exchanges;
+    if (merged_rows) *merged_rows = c->merged_rows;
+    if (producer_packed) *producer_packed = c->merged_producer_packed;
+    if (split_fallbacks) *split_fallbacks = c->merged_split_fallbacks;
+    return DORY_OK;
+}
+
+// the tensors of the three split entry points after their checks: DORY_GATMH, preallocated, a backward plan, `layer` the tensors' layer
+static int gatmh_bwd_split(dory_ctx *c, const char *who, uint32_t layer, Tensor **dO, Tensor **st, Tensor **bgdo, Tensor **bgst, RowWire *wire) {
+    if (!c->configured || c->gnn != DORY_GATMH || !c->prealloc || !c->plan[DORY_BACKWARD].set)
+        return fail(c, DORY_ERR_ARG, "%s: a DORY_GATMH context after dory_preallocate with a backward plan", who);
+    if (layer >= c->L) return fail(c, DORY_ERR_ARG, "%s: layer %u out of range", who, layer);
+    *dO = find(c, layer, "do"); *st = find(c, layer, "st"); *bgdo = find(c, layer, "bg_do"); *bgst = find(c, layer, "bg_st");
+    if (!*dO || !*st || !*bgdo || !*bgst) return fail(c, DORY_ERR_ARG, "%s: tensors missing", who);
+    *wire = pair_wire(c, *dO, *st);
+    return DORY_OK;
+}
+
+int dory_gatmh_bwd_wire_row(dory_ctx *c, uint32_t layer, uint32_t *row_floats, uint32_t *do_floats, uint32_t *st_floats) {
+    CHECK_CTX(c);
+    Tensor *dO, *st, *bgdo, *bgst;
+    RowWire wire;
+    int rc = gatmh_bwd_split(c, "gatmh_bwd_wire_row", layer, &dO, &st, &bgdo, &bgst, &wire);
+    if (rc) return rc;
+    if (row_floats) *row_floats = wire.w + wire.w2;
+    if (do_floats) *do_floats = wire.w;
+    if (st_floats) *st_floats = wire.w2;
+    return DORY_OK;
+}
+
+int dory_gatmh_bwd_pack(dory_ctx *c, uint32_t layer, float *send_buf) {
+    CHECK_CTX(c);
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    Tensor *dO, *st, *bgdo, *bgst;
+    RowWire wire;
+    int rc = gatmh_bwd_split(c, "gatmh_bwd_pack", layer, &dO, &st, &bgdo, &bgst, &wire);
+    if (rc) return rc;
+    const HaloPlan &p = c->plan[DORY_BACKWARD];
+    if (p.send_total && (!send_buf || ((uintptr_t)send_buf & 15))) return fail(c, DORY_ERR_ARG, "gatmh_bwd_pack: a 16-byte aligned device buffer");
+    Timed t(c, "halo", c->compute);
+    return pack_rows(c, send_buf, dO, wire, p, c->compute, st);
+}
+
+int dory_gatmh_bwd_unpack(dory_ctx *c, uint32_t layer, const float *recv_buf) {
+    CHECK_CTX(c);
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    Tensor *dO, *st, *bgdo, *bgst;
+    RowWire wire;
+    int rc = gatmh_bwd_split(c, "gatmh_bwd_unpack", layer, &dO, &st, &bgdo, &bgst, &wire);
+    if (rc) return rc;
+    const HaloPlan &p = c->plan[DORY_BACKWARD];
+    if (bgdo->rows != p.recv_total || bgst->rows != p.recv_total)
+        return fail(c, DORY_ERR_ARG, "gatmh_bwd_unpack: ghost tensors of %llu rows for a plan that receives %u", (unsigned long long)bgdo->rows, p.recv_total);
+    if (p.recv_total && (!recv_buf || ((uintptr_t)recv_buf & 15))) return fail(c, DORY_ERR_ARG, "gatmh_bwd_unpack: a 16-byte aligned device buffer");
+    Timed t(c, "halo", c->compute);
+    rc = unpack_rows(c, bgdo->d, bgdo->ld, wire, recv_buf, p, c->compute, nullptr, bgst->d, bgst->ld);
+    ghost_wrote_fp32(bgdo);
+    ghost_wrote_fp32(bgst);
+    return rc;
 }
 
 // ---- bf16 halo rows: switch, counters, and the row an exchange puts on the wire (include/dorylus_hip.h) ------------------------

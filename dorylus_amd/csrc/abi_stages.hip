@@ -603,11 +603,11 @@ struct GatmhBwd {
     Tensor *z, *el, *er, *m, *den, *o, *dO, *dz, *tt, *del, *der, *st, *fgz, *fgel, *bgdo, *bgst;
 };
 
-// ghost destinations of the out-edges: their dO and st rows, between the two phases of a whole backward pass
-static int gatmh_backward_exchange(dory_ctx *c, const GatmhBwd &T) {
+// ghost destinations of the out-edges: their dO and st rows, between the two phases of a whole backward pass -- two exchanges, or
+// (dory_gatmh_bwd_merged_exchange) one of merged rows, which `producer_packed` says the destination side has written already
+static int gatmh_backward_exchange(dory_ctx *c, const GatmhBwd &T, bool producer_packed = false) {
     if (T.phase != 0 || c->numNodes <= 1) return DORY_OK;
-    int rc = exchange_rows(c, DORY_BACKWARD, T.dO, T.bgdo, false);
-    return rc ? rc : exchange_rows(c, DORY_BACKWARD, T.st, T.bgst, false);
+    return gatmh_bwd_exchange(c, T.dO, T.bgdo, T.st, T.bgst, producer_packed);
 }
 
 // The sweep forms (gat_mh_sweep.hip).  Destination side: this layer's forward ran on the skeleton and left the positive-branch
@@ -618,13 +618,21 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
     const uint32_t K = T.K, D = T.D, ld = T.z->ld, ldk = T.el->ld, lds4 = T.st->ld / 4;
     float4 *st4 = reinterpret_cast<float4 *>(T.st->d);
     int rc;
+    // dory_gatmh_bwd_merged_exchange: the send form writes the merged rows the exchange below ships (phase 0 only: asked in front of the launch)
+    GatmhSend sd{};
+    bool send = false;
+    if (T.phase == 0 && c->numNodes > 1 && (rc = gatmh_bwd_send_target(c, T.dO, T.st, &sd, &send))) return rc;
     if (T.phase != 2) {
         Timed t(c, "loss", c->compute);
-        HIPCK(c, launch_gatmh_dst_rowwise(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
-                                          st4, lds4, c->compute));
+        if (send)
+            HIPCK(c, launch_gatmh_dst_rowwise_send(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
+                                                   st4, lds4, sd, c->compute));
+        else
+            HIPCK(c, launch_gatmh_dst_rowwise(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
+                                              st4, lds4, c->compute));
     }
     if (T.phase == 1) return DORY_OK;
-    if ((rc = gatmh_backward_exchange(c, T))) return rc;
+    if ((rc = gatmh_backward_exchange(c, T, send))) return rc;
     if ((rc = ensure_scratch(c, gatmh_src_sweep_scratch_bytes(So, c->N, Out.ghosts, K, ld, ldk)))) return rc;
     GatmhSweep gs;
     if ((rc = gs.plan(c, So, sa, K, D, Out.ghosts > 0, shl, 1, bf16))) return rc;

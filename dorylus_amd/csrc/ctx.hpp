@@ -80,13 +80,23 @@ struct FusedStamp {
 // its cols -- of 4 bytes (fp32), or with `bf16` (dory_halo_bf16_rows) of 2: then w is rounded up to a multiple of 4 elements and
 // `cols` of them hold values, the rest zeros.  Made by row_wire() (abi_comm.hip) alone; which pack / unpack kernels run and the
 // zeroing of [w, ld) follow from it, and every byte count of an exchange from row_bytes().
+// dory_gatmh_bwd_merged_exchange: w2 != 0 makes it a merged row [w floats of the first tensor | w2 floats of a second] (fp32, both
+// multiples of 4: a row starts on a 16-byte boundary) -- the pair kernels pack and unpack it.
 struct RowWire {
     uint32_t w = 0;
     bool exact = false;
     bool bf16 = false;
     uint32_t cols = 0;   // (bf16 only: the columns of the tensor below w that the pack reads)
+    uint32_t w2 = 0;     // (merged rows only: the floats of the second tensor behind the first's w)
     uint32_t elem_bytes() const { return bf16 ? 2u : 4u; }
-    size_t row_bytes() const { return (size_t)w * elem_bytes(); }
+    size_t row_bytes() const { return (size_t)(w + w2) * elem_bytes(); }
+};
+// The second tensor of an exchange of merged rows (the multi-head GAT's st -> bg_st behind do -> bg_do), and whether the producer has
+// written the send rows into the context's send buffer already (gatmh_dst_rowwise_send_kernel): then the exchange runs no pack.
+struct RowPair {
+    const Tensor *src2 = nullptr;
+    Tensor *ghost2 = nullptr;
+    bool producer_packed = false;
 };
 
 // Scatter messages (dory_scatter_msgs_*, abi_comm.hip): the id tables of dory_halo_wire_ids, the round stamps and counters of
@@ -329,6 +339,11 @@ struct dory_ctx {
     // two softmax producers write the rows of g / h / grad that travel; the consumed stamps they made, counted
     bool fused_pack_rowwise = false;
     uint64_t rowwise_exchanges = 0, rowwise_rows = 0;
+    // dory_gatmh_bwd_merged_exchange (default off; a copy the peers of the local transport may read without this context's lock): the
+    // multi-head GAT's backward sweep ships [do | st] rows in one exchange; eager exchanges counted: merged ones, their send rows,
+    // those whose rows the producer wrote, backward passes that kept the two exchanges although the switch was on
+    std::atomic<int> gatmh_merged{0};
+    uint64_t merged_exchanges = 0, merged_rows = 0, merged_producer_packed = 0, merged_split_fallbacks = 0;
     // bf16 halo rows (dory_halo_bf16_rows; default off) and the two gather modes its rule reads (option gcn_bf16_gather,
     // dory_gat_bf16_gather's mode) -- copies the peers of the local transport may read without this context's lock -- and the
     // eager packs counted: those that wrote bf16 rows, their bytes, those that wrote fp32 rows while the switch was on
@@ -363,6 +378,8 @@ struct dory_ctx {
         int dir = 0;
         char *ghost = nullptr;                      // where the rows land: the ghost tensor's fp32 rows, or (keep) its bf16 twin
         uint32_t ghost_ld = 0;
+        float *ghost2 = nullptr;                    // merged rows (RowWire::w2): the second ghost tensor and its ld
+        uint32_t ghost2_ld = 0;
         dory::RowWire wire;                         // what the rows in recv_buf look like (exact: the unpack zeroes [w, ghost_ld))
         bool direct = false;                        // halo_direct_recv and w == ghost_ld: the peers' segments are copied into the ghost tensor (or twin) itself
         bool keep = false;                          // dory_halo_bf16_ghosts: bf16 rows stay bf16, in the twin
@@ -664,6 +681,17 @@ hipError_t launch_gatmh_forward_sweep_finish(uint32_t N, uint32_t K, uint32_t D,
 hipError_t launch_gatmh_dst_rowwise(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const float *d_o, const float *o,
                                     const float *op, const float *dpos, const float *er, const float *m, const float *den, float *t,
                                     float *der, float4 *st4, uint32_t lds4, hipStream_t s);
+// dory_gatmh_bwd_merged_exchange, producer-packed: the send form also stores row v's quads of dO below column w and its st records
+// (at float offset w + 4k) into the rows row_slots[row_ptr[v] .. row_ptr[v + 1]) of buf, R = w + 4K floats each
+struct GatmhSend {
+    float *buf;
+    const uint32_t *row_ptr;     // N + 1 (dory_halo_send_map)
+    const uint32_t *row_slots;   // row_ptr[N]
+    uint32_t w, R;
+};
+hipError_t launch_gatmh_dst_rowwise_send(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const float *d_o, const float *o,
+                                         const float *op, const float *dpos, const float *er, const float *m, const float *den, float *t,
+                                         float *der, float4 *st4, uint32_t lds4, const GatmhSend &sd, hipStream_t s);
 size_t gatmh_src_sweep_scratch_bytes(const BlockedAdj &S, uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk);
 hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                         const float4 *st4, const float4 *stg, uint32_t lds4, float *scratch, hipStream_t s);
@@ -704,6 +732,13 @@ hipError_t launch_gather_rows_exact(float *dst, const float *src, uint32_t ld, u
 hipError_t launch_scatter_rows_exact(float *dst, const float *src, uint32_t ld, uint32_t cols,
                                      const uint32_t *rows, uint32_t n, hipStream_t s);
 hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const uint32_t *rows, uint32_t n, hipStream_t s);
+// dory_gatmh_bwd_merged_exchange: merged rows [a[v, 0:wa) | b[v, 0:wb)] of wa + wb floats (all widths and lds multiples of 4, the
+// dense side 16-byte aligned).  The gather packs the listed rows; the scatter writes whole rows of both tensors: [0, wa) and [0, wb)
+// from the stream, zeros into [wa, lda) and [wb, ldb).
+hipError_t launch_gather_rows_pair(float *dst, const float *a, uint32_t lda, uint32_t wa, const float *b, uint32_t ldb, uint32_t wb,
+                                   const uint32_t *rows, uint32_t n, hipStream_t s);
+hipError_t launch_scatter_rows_pair(float *a, uint32_t lda, uint32_t wa, float *b, uint32_t ldb, uint32_t wb, const float *src,
+                                    const uint32_t *rows, uint32_t n, hipStream_t s);
 // dory_halo_bf16_rows: the dense side holds rows of row_elems bf16 (a multiple of 4, 8-byte aligned).  The gather rounds
 // [0, cols) of every listed row (nearest even, the conversion of launch_bf16_rows) and writes zeros into [cols, row_elems); the
 // scatter writes the whole ld-wide row: [0, row_elems) widened from the stream, zeros behind.

@@ -964,6 +964,60 @@ hipError_t launch_zero_rows_pad(float *dst, uint32_t ld, uint32_t cols, const ui
     return hipGetLastError();
 }
 
+// ---- K6, merged rows (dory_gatmh_bwd_merged_exchange) ----------------------------------------------------------------------------
+// The dense side holds rows of wa4 + wb4 quads: [a[v, 0:wa) | b[v, 0:wb)], the multi-head GAT's [do | st].  Every width and ld is a
+// multiple of 4 floats, so no quad straddles the two parts or two rows: a thread owns one 16-byte quad -- one 16-byte load, one
+// 16-byte store, 32-bit divides only (a run of rows per workgroup would save nothing here: the row width is not a compile-time
+// constant either way).  pack: the row list may repeat a row (a vertex goes to several peers).
+__global__ __launch_bounds__(256) void gather_rows_pair_kernel(float4 *dst, const float *a, uint32_t lda, uint32_t wa4, const float *b,
+                                                               uint32_t ldb, uint32_t wb4, const uint32_t *rows, uint32_t n) {
+    const uint32_t r4 = wa4 + wb4;
+    const uint64_t total = (uint64_t)n * r4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / r4), c = (uint32_t)(i - (uint64_t)r * r4);
+        const size_t v = rows[r];
+        dst[i] = c < wa4 ? reinterpret_cast<const float4 *>(a + v * lda)[c] : reinterpret_cast<const float4 *>(b + v * ldb)[c - wa4];
+    }
+}
+// unpack: the row list is a permutation of the ghost slots.  A thread owns one quad of a WHOLE row of a or of b (lda4 + ldb4 quads
+// per listed row): the stream's value below the wire's width, zeros behind it -- the raw ghost rows are the bits the two separate
+// exchanges leave (the owner's zero padding travelled there, or the exact form's zeroing wrote it).
+__global__ __launch_bounds__(256) void scatter_rows_pair_kernel(float *a, uint32_t lda4, uint32_t wa4, float *b, uint32_t ldb4, uint32_t wb4,
+                                                                const float4 *src, const uint32_t *rows, uint32_t n) {
+    const uint32_t t4 = lda4 + ldb4, r4 = wa4 + wb4;
+    const uint64_t total = (uint64_t)n * t4;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / t4), c = (uint32_t)(i - (uint64_t)r * t4);
+        const size_t v = rows[r];
+        const bool first = c < lda4;
+        const uint32_t cc = first ? c : c - lda4;                  // the quad inside its tensor's row
+        const bool on_wire = cc < (first ? wa4 : wb4);
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (on_wire) q = src[(uint64_t)r * r4 + (first ? cc : wa4 + cc)];
+        float4 *row = first ? reinterpret_cast<float4 *>(a + v * lda4 * 4) : reinterpret_cast<float4 *>(b + v * ldb4 * 4);
+        row[cc] = q;
+    }
+}
+hipError_t launch_gather_rows_pair(float *dst, const float *a, uint32_t lda, uint32_t wa, const float *b, uint32_t ldb, uint32_t wb,
+                                   const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || wa + wb == 0) return hipSuccess;
+    if (((wa | wb | lda | ldb) & 3) || wa > lda || wb > ldb || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+    const uint64_t total = (uint64_t)n * ((wa + wb) / 4);
+    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(gather_rows_pair_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<float4 *>(dst), a, lda, wa / 4, b, ldb, wb / 4, rows, n);
+    return hipGetLastError();
+}
+hipError_t launch_scatter_rows_pair(float *a, uint32_t lda, uint32_t wa, float *b, uint32_t ldb, uint32_t wb, const float *src,
+                                    const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || lda + ldb == 0) return hipSuccess;
+    if (((wa | wb | lda | ldb) & 3) || wa > lda || wb > ldb || ((uintptr_t)src & 15)) return hipErrorInvalidValue;
+    const uint64_t total = (uint64_t)n * ((lda + ldb) / 4);
+    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(scatter_rows_pair_kernel, dim3(blocks), dim3(256), 0, s, a, lda / 4, wa / 4, b, ldb / 4, wb / 4,
+                       reinterpret_cast<const float4 *>(src), rows, n);
+    return hipGetLastError();
+}
+
 // ---- K6, bf16 rows (dory_halo_bf16_rows) ----------------------------------------------------------------------------------------
 // The dense side holds rows of `re4` quads of bf16 (row_elems = 4 x re4 elements, 8 bytes a quad): a row is a multiple of 8
 // bytes, so no quad straddles two rows and a lane owns one quad of one row -- four elements per lane: one 16-byte load (or

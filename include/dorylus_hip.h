@@ -78,8 +78,13 @@ int dory_configure(dory_ctx *ctx, int gnn_type, uint32_t num_layers,
  * "z" -> "fg_z" (the ghost sources' scores are recomputed from it); the backward sweep of dory_aggregate runs in two
  * phases and ships "do" -> "bg_do" and "st" -> "bg_st" (the packed (er, m, 1/den, t) rows) of the out-edges' ghost
  * destinations in between -- itself over RCCL, or, with option "gatmh_bwd_phase" = 1 / 2, one phase per call so that
- * the caller can move those rows (dory_halo_pack_tensor / dory_halo_unpack_tensor); dory_halo_exchange(layer,
- * BACKWARD) is a no-op for this model.  Partitioned runs need the source-blocked kernels ("gatmh_blocked" = 1).
+ * the caller can move those rows (dory_halo_pack_tensor / dory_halo_unpack_tensor, or as one merged row
+ * dory_gatmh_bwd_pack / dory_gatmh_bwd_unpack); dory_halo_exchange(layer, BACKWARD) is a no-op for this model.
+ * dory_gatmh_bwd_merged_exchange (below; opt-in): a whole sweep ships ONE row [do[v, 0:w) | st[v, 0:4K)] per sent vertex in
+ * one exchange (w = ld of do, or cols rounded up to 4 with halo_exact_rows) and, with dory_halo_fused_pack on and the sweep
+ * forms running, the row-wise kernel that produces st writes the send rows itself.  Not taken (two exchanges as ever): the
+ * scatter transport, a plan made with halo_direct_recv = 1, gatmh_bwd_phase = 1 / 2 (the caller's own transport).
+ * Partitioned runs need the source-blocked kernels ("gatmh_blocked" = 1).
  * Sweep forms (option "gatmh_sweep" = 1, default; round 5): where the K1s layouts apply and a head spans 2..16 lanes of a
  * 16-byte-per-lane row slab, the forward runs on K1s's skeleton with a single-pass softmax against an upper-bound shift
  * ("m" then holds that shift, "den" the matching denominator: alpha = exp(s - m) / den as before) and leaves two more
@@ -392,7 +397,8 @@ int dory_halo_fused_pack_bf16_stats(dory_ctx *ctx, uint64_t *fused_bf16_exchange
  * exchange, a new plan, halo_exact_rows or a wire switch changed, the raw pointer handed out: counted fallbacks with the rows of the
  * moment); a producer that runs its plain kernel drops a stamp that names its tensor.
  * Not taken: the multi-head GAT's do / st (two exchanges in a row through one send buffer with one stamp, and no (layer, direction)
- * of dory_halo_exchange names them): they keep packing.  A one-column tensor (ld == 1).  Everything the fused pack does not take.
+ * of dory_halo_exchange names them): they keep packing under this switch -- dory_gatmh_bwd_merged_exchange, below, is the switch
+ * that has their producer write them.  A one-column tensor (ld == 1).  Everything the fused pack does not take.
  * Counters: a consumed stamp of a row-wise producer moves rowwise_exchanges / rowwise_rows IN ADDITION to fused_exchanges /
  * fused_rows, and for a bf16 wire to fused_bf16_* and bf16_packs / bf16_bytes, exactly as a GEMM-made one.  Eager calls only, since
  * dory_create; any pointer may be NULL.
@@ -429,6 +435,55 @@ int dory_halo_fused_pack_bf16_stats(dory_ctx *ctx, uint64_t *fused_bf16_exchange
  * fraction of its rows -- so a caller whose last layer is that wide and whose rows mostly travel should leave the switch off. */
 int dory_halo_fused_pack_rowwise(dory_ctx *ctx, int on);   /* 0 (default) / 1 */
 int dory_halo_fused_pack_rowwise_stats(dory_ctx *ctx, uint64_t *rowwise_exchanges, uint64_t *rowwise_rows);
+
+/* ---- the multi-head GAT's backward exchange, merged (opt-in, default off; nothing in the reference) ---------------------------
+ * A whole backward sweep of the 8-head GAT (dory_gatmh_heads, option gatmh_bwd_phase = 0) ships do -> bg_do and st -> bg_st between
+ * its two phases: two exchanges back to back -- two packs, two unpacks, two all-to-all-v rounds (each a stream synchronisation under
+ * the host transport), two event hand-overs -- and st travels at its padded width (32 floats for 4 K of data).  With this switch on
+ * a sent vertex v of layer l travels as ONE merged row
+ *     [ do[v, 0:w) | st[v, 0:4K) ]      R = w + 4K floats, fp32, rows in the order of the backward plan's send lists
+ * with w = ld of do, or, with option halo_exact_rows = 1, its cols rounded up to a multiple of 4 (the columns past cols are the
+ * tensor's zero padding, as in the bf16 rows' rule).  R is a multiple of 4: every row starts on a 16-byte boundary.  One pack (or
+ * none), one all-to-all-v, one unpack, one hand-over; the host transport's callback sees counts and offsets in floats of R per row.
+ * The unpack (scatter_rows_pair_kernel) writes whole ghost rows -- bg_do[slot, 0:w) and bg_st[slot, 0:4K) from the buffer, zeros
+ * into [w, ld) and [4K, ld of st) -- so every float of both ghost tensors is what the two exchanges leave; every tensor, weight and
+ * gradient keeps its bits.  Bytes per sent row for 602-128-41 with heads 8 / 1, as arithmetic: hidden layer 512 + 128 B -> 640 B
+ * (the same bytes in one message), last layer 256 + 128 = 384 B -> 272 B, 192 B with halo_exact_rows.
+ * Taken when the switch is on, gatmh_bwd_phase == 0, the transport is RCCL, the host callbacks or the in-process one, and the plan
+ * was not made with halo_direct_recv = 1.  NOT TAKEN -- the two exchanges as ever, the same bits, one split_fallbacks per backward
+ * pass: the scatter transport (its messages have their own layout); a plan made with halo_direct_recv = 1 (received rows land in
+ * one tensor and there are two).
+ * Producer-packed: where the merged exchange is taken, dory_halo_fused_pack is 1, the backward runs the sweep forms, the backward
+ * plan has its send map, no epoch graph is being recorded and the send buffer holds send_total x R floats, the row-wise kernel that
+ * produces st runs its send form (csrc/gat_mh_sweep.hip: gatmh_dst_rowwise_send_kernel -- the same arithmetic in the same order, and
+ * each thread stores the do quad it has loaded, the head's leader lane its st record, into the row's slots of the send buffer) and
+ * the exchange runs no pack kernel.  Producer and exchange sit inside one dory_aggregate call under the context's lock: no stamp
+ * is involved and no caller can get between them.  It counts in dory_halo_fused_pack_stats as one fused exchange of send_total
+ * rows; a merged exchange that packs by kernel (gather_rows_pair_kernel: the blocked forms, whose st comes out of an edge pass)
+ * while dory_halo_fused_pack is on counts there as one fallback -- fused + fallback == exchanges made still holds.
+ * Buffers: dory_halo_plan sizes them for the widest merged row while the switch is on; the setter grows those of plans that exist;
+ * after dory_comm_init_local the peers hold the buffers' addresses, so a setter that would have to grow them fails with
+ * DORY_ERR_ARG and leaves the switch off: call it before dory_comm_init_local.
+ * ALL RANKS MUST SET THE SAME VALUE.  In-process ranks that disagree fail with DORY_ERR_COMM (both ranks named) before anything of
+ * the backward pass's exchange is enqueued; under RCCL and the host transport a mismatch cannot be seen.
+ * dory_gatmh_bwd_merged_exchange: on = 0 (default) / 1; DORY_ERR_ARG for a context that is not DORY_GATMH or not configured, other
+ * values, or while an epoch graph is being recorded; accepted and inert with num_nodes == 1 (all counters stay 0).
+ * dory_gatmh_bwd_merged_exchange_stats: eager calls since dory_create -- merged exchanges, their send rows, those of them whose rows
+ * the producer wrote, backward passes that kept the two exchanges while the switch was on; any pointer may be NULL.
+ * For callers that move the rows themselves (gatmh_bwd_phase = 1 / 2: the library exchanges nothing), whatever the switch says:
+ * dory_gatmh_bwd_wire_row tells the row (R, w, 4K floats) of the tensors' layer `layer` (dory_halo_pack_tensor's layer) as the wire
+ * stands now; dory_gatmh_bwd_pack writes the plan's send_total merged rows into a device buffer, dory_gatmh_bwd_unpack takes
+ * recv_total of them out of one (16-byte aligned; on the compute stream).  DORY_ERR_ARG before dory_preallocate or without a
+ * backward plan.  dory_halo_pack_tensor / dory_halo_unpack_tensor on do / st keep working.
+ * Measured on one MI355X -- NO LINK AND NO SECOND GPU ARE BEHIND ANY NUMBER; the halved message count and the last layer's narrower
+ * row are arithmetic until an RCCL run with more than one rank exists: profiles/r23_gatmh_bwd_merged_exchange.txt
+ * (tools/gatmh_bwd_exchange_rate.py), which also names the shapes that are not faster. */
+int dory_gatmh_bwd_merged_exchange(dory_ctx *ctx, int on);          /* 0 (default) / 1 */
+int dory_gatmh_bwd_merged_exchange_stats(dory_ctx *ctx, uint64_t *merged_exchanges, uint64_t *merged_rows, uint64_t *producer_packed,
+                                         uint64_t *split_fallbacks);
+int dory_gatmh_bwd_wire_row(dory_ctx *ctx, uint32_t layer, uint32_t *row_floats, uint32_t *do_floats, uint32_t *st_floats);
+int dory_gatmh_bwd_pack(dory_ctx *ctx, uint32_t layer, float *send_buf);
+int dory_gatmh_bwd_unpack(dory_ctx *ctx, uint32_t layer, const float *recv_buf);
 
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows

@@ -20,7 +20,11 @@ dory_halo_bf16_rows on on every rank (with --opt gcn_bf16_gather=1 or 2) and rec
 --bf16-ghosts switches dory_halo_bf16_ghosts on on top of it and records its counters per rank; with either, the timing key
 "bf16_convert" (the conversions of the aggregations on bf16 rows: ms and launches, summed over the ranks) is recorded too.
 --fused-rowwise switches dory_halo_fused_pack_rowwise on on top of --fused-pack and records its counters per rank and the timing key
-"loss" (the row-wise producers: tanh, softmax + loss), summed over the ranks."""
+"loss" (the row-wise producers: tanh, softmax + loss), summed over the ranks.
+--gatmh-heads K... runs the multi-head GAT (dory_gatmh_heads; the oracle's epoch is left out) instead of the GCN, and
+--gatmh-merged switches dory_gatmh_bwd_merged_exchange on on every rank and records its counters per rank (merged exchanges, their
+rows, producer-packed ones, split fallbacks); with --gatmh-heads the timing key "loss" (the backward's row-wise destination side among
+it) is recorded too."""
 import argparse
 import json
 import os
@@ -47,7 +51,12 @@ def main():
     ap.add_argument("--bf16-rows", action="store_true", help="dory_halo_bf16_rows(1) on every rank")
     ap.add_argument("--bf16-ghosts", action="store_true", help="dory_halo_bf16_ghosts(1) on every rank (with --bf16-rows)")
     ap.add_argument("--fused-rowwise", action="store_true", help="dory_halo_fused_pack_rowwise(1) on every rank (with --fused-pack)")
+    ap.add_argument("--ranks", type=int, nargs="*", default=None, help="keep only the configurations of these rank counts")
+    ap.add_argument("--gatmh-heads", type=int, nargs="*", default=None, help="heads per layer: the multi-head GAT instead of the GCN")
+    ap.add_argument("--gatmh-merged", action="store_true", help="dory_gatmh_bwd_merged_exchange(1) on every rank (with --gatmh-heads)")
     a = ap.parse_args()
+    if a.gatmh_heads:
+        a.skip_oracle = True
     import torch  # noqa: F401
     import dorylus_amd as da
     from local_ranks import run_local
@@ -58,6 +67,16 @@ def main():
     X = rng.uniform(-1, 1, (a.V, dims[0])).astype(np.float32)
     labels = rng.integers(0, dims[-1], a.V).astype(np.uint32)
     Ws = [(rng.standard_normal((dims[i], dims[i + 1])) / np.sqrt(dims[i])).astype(np.float32) for i in range(L)]
+    if a.gatmh_heads:      # (the last layer's z holds all its heads)
+        zw = [dims[l + 1] * (a.gatmh_heads[l] if l == L - 1 else 1) for l in range(L)]
+        inw = [dims[0]] + zw[:-1]
+        Ws = [(rng.standard_normal((inw[l], zw[l])) / np.sqrt(inw[l])).astype(np.float32) for l in range(L)]
+        Al = [(rng.standard_normal(zw[l]) * 0.3).astype(np.float32) for l in range(L)]
+        Ar = [(rng.standard_normal(zw[l]) * 0.3).astype(np.float32) for l in range(L)]
+    gnn = da.GATMH if a.gatmh_heads else da.GCN
+    pre = (lambda c: c.gatmh_heads(a.gatmh_heads)) if a.gatmh_heads else None
+    wnames = ("w", "a_l", "a_r") if a.gatmh_heads else None
+    merged_stats = {}
 
     extra = {k: int(v) for k, v in (kv.split("=", 1) for kv in a.opt)}
     recv_bytes, fused_stats, bf16_stats, ghost_stats, convert = {}, {}, {}, {}, {}
@@ -72,9 +91,11 @@ def main():
                     recv_bytes[r] = ctx.get_option("halo_recv_buf_bytes")
                 except da.DoryError:
                     recv_bytes[r] = None      # (a library from before the counter)
-                if a.fused_pack:
+                if a.fused_pack or a.gatmh_heads:
                     fused_stats[r] = list(ctx.halo_fused_pack_stats())
                     loss[r] = ctx.timing_get("loss")
+                if a.gatmh_merged:
+                    merged_stats[r] = list(ctx.gatmh_bwd_merged_exchange_stats())
                 if a.fused_rowwise:
                     rowwise_stats[r] = list(ctx.halo_fused_pack_rowwise_stats())
                 if a.bf16_rows:
@@ -92,6 +113,16 @@ def main():
             ctx.halo_bf16_rows(1)
         if a.bf16_ghosts:
             ctx.halo_bf16_ghosts(1)
+        if a.gatmh_merged:
+            ctx.gatmh_bwd_merged_exchange(1)
+        if a.gatmh_heads:
+            ctx.upload(0, "h", X[g["localToGlobal"]])
+            ctx.labels_upload(labels[g["localToGlobal"]])
+            for l in range(L):
+                ctx.weight_set(l, "w", Ws[l])
+                ctx.weight_set(l, "a_l", Al[l])
+                ctx.weight_set(l, "a_r", Ar[l])
+            return
         if g["localVtxCnt"]:
             ctx.upload(0, "x", X[g["localToGlobal"]])
         if g["srcGhostCnt"]:
@@ -120,9 +151,12 @@ def main():
     out["oracle_check"] = []
     if a.configs is not None:
         configs = [c for c in configs if c[0] in a.configs]
+    if a.ranks:
+        configs = [c for c in configs if c[1] in a.ranks]
     with_extra = lambda sh: [dict(x, **extra) for x in sh] if isinstance(sh, list) else dict(sh, **extra)
     configs = [(name, P, parts, with_extra(share)) for name, P, parts, share in configs]
-    out["options"] = dict(extra, fused_pack=int(a.fused_pack), fused_rowwise=int(a.fused_rowwise), bf16_rows=int(a.bf16_rows), bf16_ghosts=int(a.bf16_ghosts))
+    out["options"] = dict(extra, fused_pack=int(a.fused_pack), fused_rowwise=int(a.fused_rowwise), bf16_rows=int(a.bf16_rows), bf16_ghosts=int(a.bf16_ghosts),
+                          gatmh_heads=a.gatmh_heads, gatmh_merged=int(a.gatmh_merged))
     for name, P, parts, share in ([] if a.skip_oracle else [c for c in configs if c[0] == "balanced"]):
         pobjs = [da.Partition.build(src, dst, parts, r, P) for r in range(P)]
         dl = [(l, nm) for l in range(L) for nm in ("ah",)] + [(l, nm) for l in range(L - 1) for nm in ("h", "aTg")] + [(l, "grad") for l in range(1, L)]
@@ -143,8 +177,8 @@ def main():
             pobjs = [da.Partition.build(src, dst, parts, r, P) for r in range(P)]
             opts = [dict(sh, halo_overlap=overlap) for sh in share] if isinstance(share, list) else dict(share, halo_overlap=overlap)
             t0 = time.time()
-            res = run_local(da, pobjs, parts, dims, da.GCN, a.epochs, setup, opts, timing=True, warm_epochs=2,
-                            downloads=[(0, "ah"), (1, "ah"), (0, "aTg")])
+            res = run_local(da, pobjs, parts, dims, gnn, a.epochs, setup, opts, timing=True, warm_epochs=2,
+                            downloads=[(0, "o"), (1, "o"), (0, "dz")] if a.gatmh_heads else [(0, "ah"), (1, "ah"), (0, "aTg")], pre=pre, wnames=wnames)
             wall = time.time() - t0
             ms = np.stack(res["epoch_ms"])          # [rank][epoch]
             tm = res["timing"]
@@ -157,8 +191,9 @@ def main():
                    "halo_overlap_fraction": round(tm["halo_hidden"]["ms"] / tm["halo_deferred"]["ms"], 4) if tm["halo_deferred"]["ms"] else None,
                    "spmm_gates": res["gates"], "recv_buf_bytes_per_rank": [recv_bytes.get(r) for r in range(P)],
                    "fused_pack_stats_per_rank": [fused_stats.get(r) for r in range(P)] if a.fused_pack else None,
+                   "gatmh_merged_stats_per_rank": [merged_stats.get(r) for r in range(P)] if a.gatmh_merged else None,
                    "fused_rowwise_stats_per_rank": [rowwise_stats.get(r) for r in range(P)] if a.fused_rowwise else None,
-                   "loss_sum_over_ranks": {"ms": round(sum(loss[r][0] for r in range(P)), 4), "launches": sum(loss[r][1] for r in range(P))} if a.fused_pack else None,
+                   "loss_sum_over_ranks": {"ms": round(sum(loss[r][0] for r in range(P)), 4), "launches": sum(loss[r][1] for r in range(P))} if (a.fused_pack or a.gatmh_heads) else None,
                    "bf16_rows_stats_per_rank": [bf16_stats.get(r) for r in range(P)] if a.bf16_rows else None,
                    "bf16_ghosts_stats_per_rank": [ghost_stats.get(r) for r in range(P)] if a.bf16_ghosts else None,
                    "bf16_convert_sum_over_ranks": {"ms": round(sum(convert[r][0] for r in range(P)), 4), "launches": sum(convert[r][1] for r in range(P))} if a.bf16_rows else None,
