@@ -35,7 +35,7 @@ SYMBOLS = [
     "dory_halo_fused_pack_bf16", "dory_halo_fused_pack_bf16_stats",
     "dory_halo_fused_pack_rowwise", "dory_halo_fused_pack_rowwise_stats",
     "dory_gatmh_bwd_merged_exchange", "dory_gatmh_bwd_merged_exchange_stats", "dory_gatmh_bwd_wire_row", "dory_gatmh_bwd_pack",
-    "dory_gatmh_bwd_unpack",
+    "dory_gatmh_bwd_unpack", "dory_gatmh_halo_bf16", "dory_gatmh_halo_bf16_stats", "dory_gatmh_bwd_wire_do",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -143,6 +143,9 @@ def load():
         "dory_gatmh_bwd_wire_row": [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
         "dory_gatmh_bwd_pack": [vp, u32, vp],
         "dory_gatmh_bwd_unpack": [vp, u32, vp],
+        "dory_gatmh_halo_bf16": [vp, i32],
+        "dory_gatmh_halo_bf16_stats": [vp] + [C.POINTER(u64)] * 4,
+        "dory_gatmh_bwd_wire_do": [vp, u32, C.POINTER(u32), C.POINTER(u32)],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -178,8 +181,8 @@ def load():
                 or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
                 or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")
                 or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")
-                or name.startswith("dory_gatmh_bwd_")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange)
+                or name.startswith("dory_gatmh_bwd_") or name.startswith("dory_gatmh_halo_bf16")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange / its bf16 halo rows)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -631,6 +634,23 @@ class Context:
         r, d, s = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._ck(self.lib.dory_gatmh_bwd_wire_row(self.h, layer, C.byref(r), C.byref(d), C.byref(s)))
         return r.value, d.value, s.value
+
+    def gatmh_halo_bf16(self, on=True):
+        """the 8-head GAT under the rule of halo_bf16_rows (opt-in, on top of it; dory_gatmh_halo_bf16): z ships bf16 while
+        gatmh_bf16_gather >= 1, the backward sweep's do while it is 2; st stays fp32"""
+        self._ck(self.lib.dory_gatmh_halo_bf16(self.h, int(on)))
+
+    def gatmh_halo_bf16_stats(self):
+        """(fwd_bf16_exchanges, bwd_bf16_exchanges, bwd_bf16_rows, producer_packed_bf16) of the eager exchanges since dory_create"""
+        v = [C.c_uint64() for _ in range(4)]
+        self._ck(self.lib.dory_gatmh_halo_bf16_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def gatmh_bwd_wire_do(self, layer):
+        """(elem_bytes, elems) of the do part of the backward rows of `layer` as the wire stands now"""
+        e, n = C.c_uint32(), C.c_uint32()
+        self._ck(self.lib.dory_gatmh_bwd_wire_do(self.h, layer, C.byref(e), C.byref(n)))
+        return int(e.value), int(n.value)
 
     def gatmh_bwd_pack(self, layer, dev_ptr):
         """the backward plan's send rows of do / st of `layer` as merged rows into a device buffer (option gatmh_bwd_phase = 1 / 2:

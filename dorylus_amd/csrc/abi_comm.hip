@@ -92,15 +92,22 @@ int row_wire(dory_ctx *c, const char *who, const Tensor *src, const Tensor *ghos
 }
 
 // dory_gatmh_bwd_merged_exchange: the merged row [do[v, 0:w) | st[v, 0:4K)] -- w = ld floats of do, or with halo_exact_rows its cols
-// rounded up to a multiple of 4 (the columns past cols are the tensor's zero padding, as in the bf16 rows' rule); always fp32
-// (halo_ships_bf16: never the multi-head GAT); R = w + 4K is a multiple of 4, so every row starts on a 16-byte boundary
-inline RowWire pair_wire(const dory_ctx *c, const Tensor *rows, const Tensor *rows2) {
+// rounded up to a multiple of 4 (the columns past cols are the tensor's zero padding, as in the bf16 rows' rule); R = w + 4K is a
+// multiple of 4, so every row starts on a 16-byte boundary.
+// dory_gatmh_halo_bf16 (`do16`: the rule says bf16 for do at this moment, gatmh_do_bf16 below): the do part as bf16, the exact width
+// rounded up to a multiple of 8 -- st starts on a 16-byte boundary, the row is w / 2 + 4K floats, a multiple of 4; st stays fp32
+inline RowWire pair_wire(const dory_ctx *c, const Tensor *rows, const Tensor *rows2, bool do16) {
     RowWire out;
     out.exact = halo_exact(c);
-    out.w = out.exact ? std::min((rows->cols + 3u) & ~3u, rows->ld) : rows->ld;
+    out.bf16 = do16 && !(rows->ld & 7);
+    const uint32_t up = out.bf16 ? 7u : 3u;
+    out.w = out.exact ? std::min((rows->cols + up) & ~up, rows->ld) : rows->ld;
+    out.cols = out.bf16 ? rows->cols : 0;
     out.w2 = rows2->cols;
     return out;
 }
+// the element kind of the do part of the multi-head GAT's backward rows at this moment: the rule and the arms that keep fp32
+inline bool gatmh_do_bf16(const dory_ctx *c, const Tensor *dO) { return c->gnn == DORY_GATMH && wire_bf16(c, DORY_BACKWARD, dO->ld); }
 
 // dory_halo_bf16_rows: an eager exchange or pack that ships fp32 rows while the switch is on (section "not taken" of dorylus_hip.h)
 inline void fp32_while_on(dory_ctx *c) {
@@ -109,7 +116,8 @@ inline void fp32_while_on(dory_ctx *c) {
 // the plan's send rows of `src`, dense at the wire's width, into dst; counted (eager calls); merged rows (wire.w2): those of src2 behind them
 int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const HaloPlan &p, hipStream_t s, const Tensor *src2 = nullptr) {
     if (dst == c->send_buf) fused_stamp_drop(c);   // (the fused halo pack: whatever a GEMM left in the internal buffer is overwritten)
-    if (wire.w2) HIPCK(c, launch_gather_rows_pair(dst, src->d, src->ld, wire.w, src2->d, src2->ld, wire.w2, p.d_send_lvids, p.send_total, s));
+    if (wire.w2 && wire.bf16) HIPCK(c, launch_gather_rows_pair_bf16(dst, src->d, src->ld, wire.w, src2->d, src2->ld, wire.w2, p.d_send_lvids, p.send_total, s));
+    else if (wire.w2) HIPCK(c, launch_gather_rows_pair(dst, src->d, src->ld, wire.w, src2->d, src2->ld, wire.w2, p.d_send_lvids, p.send_total, s));
     else if (wire.bf16) HIPCK(c, launch_gather_rows_bf16(dst, src->d, src->ld, wire.cols, wire.w, p.d_send_lvids, p.send_total, s));
     else if (wire.exact && (wire.w & 3)) HIPCK(c, launch_gather_rows_exact(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
     else HIPCK(c, launch_gather_rows(dst, src->d, src->ld, wire.w, p.d_send_lvids, p.send_total, s));
@@ -130,6 +138,14 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
 // dory_gatmh_bwd_merged_exchange (`pair`): the producer wrote the merged rows inside this very call of dory_aggregate -- no stamp --
 // or the pair kernel packs them; the fused pack counts the one as a fused exchange, the other as a fallback.
 int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloPlan &p, hipStream_t s, bool may_fuse, const RowPair *pair = nullptr) {
+    if (wire.bf16 && c->gnn == DORY_GATMH && !c->capturing) {   // (dory_gatmh_halo_bf16_stats: z forward; do backward, alone or in a merged row)
+        if (dir == DORY_FORWARD) c->gatmh_fwd_bf16_exchanges++;
+        else {
+            c->gatmh_bwd_bf16_exchanges++;
+            c->gatmh_bwd_bf16_rows += p.send_total;
+            if (pair && pair->producer_packed) c->gatmh_producer_packed_bf16++;
+        }
+    }
     if (pair) {
         if (!c->capturing) {
             c->merged_exchanges++;
@@ -141,7 +157,11 @@ int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloP
             }
         }
         if (!pair->producer_packed) return pack_rows(c, c->send_buf, src, wire, p, s, pair->src2);
-        fp32_while_on(c);
+        if (wire.bf16 && !c->capturing) {   // (what travelled as bf16 is counted as for a pack: the merged row with all its bytes)
+            c->halo_bf16_packs++;
+            c->halo_bf16_bytes += (uint64_t)p.send_total * wire.row_bytes();
+        }
+        if (!wire.bf16) fp32_while_on(c);
         return DORY_OK;
     }
     if (c->fused_pack) {
@@ -179,7 +199,9 @@ int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloP
 // merged rows (wire.w2): whole rows of both ghost tensors, ghost2 at stride ld2 behind the first
 int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s, uint16_t *twin = nullptr,
                 float *ghost2 = nullptr, uint32_t ld2 = 0) {
-    if (wire.w2) {
+    if (wire.w2 && wire.bf16) {
+        HIPCK(c, launch_scatter_rows_pair_bf16(ghost, ld, wire.w, ghost2, ld2, wire.w2, buf, p.d_unpack_slots, p.recv_total, s));
+    } else if (wire.w2) {
         HIPCK(c, launch_scatter_rows_pair(ghost, ld, wire.w, ghost2, ld2, wire.w2, buf, p.d_unpack_slots, p.recv_total, s));
     } else if (twin) {
         HIPCK(c, launch_scatter_rows_bf16_keep(twin, buf, ld, wire.w, p.d_unpack_slots, p.recv_total, s));
@@ -245,19 +267,22 @@ bool halo_route(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **gho
 }
 // dory_halo_bf16_rows, the rule: with the switch on, an exchange ships bf16 rows iff the aggregation that reads its ghost tensor gathers
 // bf16 rows under the settings of this moment -- GCN (fg / fgxw forward, bg / bgg backward): option gcn_bf16_gather >= 1 forward, == 2
-// backward; GAT prototype (fg_z, bg_d): dory_gat_bf16_gather's mode likewise; the multi-head GAT never (its finishing kernels and
-// blocked forms read fg_z in fp32, and it exchanges do / st itself).  The same for every layer of a model.  Reads atomics only: the peers
-// of the local transport ask it of each other.
+// backward; GAT prototype (fg_z, bg_d): dory_gat_bf16_gather's mode likewise; the multi-head GAT only with dory_gatmh_halo_bf16 on top:
+// then option gatmh_bf16_gather likewise (z -> fg_z forward; backward: the do of the sweep's own exchange -- with the option set its
+// sweeps gather fg_z / bg_do from rounded copies only, and the blocked forms that read them in fp32 are refused).  The same for every
+// layer of a model.  Reads atomics only: the peers of the local transport ask it of each other.
 bool halo_ships_bf16(const dory_ctx *c, int dir) {
-    if (c->halo_bf16.load(std::memory_order_acquire) != 1 || c->gnn == DORY_GATMH) return false;
-    const int mode = (c->gnn == DORY_GCN ? c->gcn_bf16_mode : c->gat_bf16_mode_pub).load(std::memory_order_acquire);
+    if (c->halo_bf16.load(std::memory_order_acquire) != 1) return false;
+    if (c->gnn == DORY_GATMH && c->gatmh_halo_bf16.load(std::memory_order_acquire) != 1) return false;
+    const int mode = (c->gnn == DORY_GCN ? c->gcn_bf16_mode : c->gnn == DORY_GATMH ? c->gatmh_bf16_mode_pub : c->gat_bf16_mode_pub).load(std::memory_order_acquire);
     return mode >= (dir == DORY_FORWARD ? 1 : 2);
 }
 // ... and what keeps fp32 although the rule says yes: the scatter-message transport (the reference's format), and a plan made with
 // halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer) -- unless
 // dory_halo_bf16_ghosts is on and the tensor (ld: the same number on every rank) has a twin for them to land in.  direct_keeps: that
 // exception, from settings every rank can read of every other.
-inline bool direct_keeps(const dory_ctx *c, uint32_t ld) { return ghosts_on(c) && ld >= 4; }
+// (the multi-head GAT has no twins: its direct plans keep fp32)
+inline bool direct_keeps(const dory_ctx *c, uint32_t ld) { return ghosts_on(c) && ld >= 4 && c->gnn != DORY_GATMH; }
 bool wire_bf16(const dory_ctx *c, int dir, uint32_t ld) {
     return halo_ships_bf16(c, dir) && (!c->plan[dir].direct || direct_keeps(c, ld)) && transport_of(c) != Transport::Scatter;
 }
@@ -853,7 +878,7 @@ int wait_halo(dory_ctx *c) {
 // at once (defer == false) or when wait_halo() is next called (halo_overlap).
 // `pair` (dory_gatmh_bwd_merged_exchange; gatmh_bwd_exchange has checked transport and plan): merged rows [src | pair->src2] into
 // ghost and pair->ghost2 -- the same arms, a row of w + w2 floats.
-int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, const RowPair *pair) {
+int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, const RowPair *pair, bool follows_rule) {
     HaloPlan &p = c->plan[dir];
     if (!p.set) return fail(c, DORY_ERR_ARG, "halo_exchange: no plan");
     const Transport tr = transport_of(c);
@@ -878,11 +903,12 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
         return DORY_OK;
     }
     RowWire wire;
-    { int rc = row_wire(c, "halo_exchange", src, ghost, true, nullptr, dir, &wire); if (rc) return rc; }
+    { int rc = row_wire(c, "halo_exchange", src, ghost, true, nullptr, follows_rule ? dir : -1, &wire); if (rc) return rc; }
+    const bool ships16 = wire.bf16;   // (what the rule says of this exchange: the peers of the local transport must say the same)
     if (pair) {
-        if (p.direct || wire.bf16 || pair->src2->ld != pair->ghost2->ld || pair->src2->cols != pair->ghost2->cols)
+        if (p.direct || (wire.bf16 && c->gnn != DORY_GATMH) || pair->src2->ld != pair->ghost2->ld || pair->src2->cols != pair->ghost2->cols)
             return fail(c, DORY_ERR_ARG, "halo_exchange: merged rows need a plan without halo_direct_recv and two tensors of one shape at either end");
-        wire = pair_wire(c, src, pair->src2);
+        wire = pair_wire(c, src, pair->src2, ships16);
     }
     const uint32_t w = wire.w;
     const size_t row_b = wire.row_bytes();
@@ -897,11 +923,11 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
                             c->nodeId, (int)p.direct, q, (int)!p.direct);
             // what each rank would ship: the switch, the gather mode that drives the rule, and -- under a direct plan (the same on both by
             // now) -- dory_halo_bf16_ghosts, without which such a plan keeps fp32
-            const bool q_ships = Q && halo_ships_bf16(Q, dir) && (!p.direct || direct_keeps(Q, ghost->ld));
-            if (Q && q_ships != wire.bf16)
+            const bool q_ships = Q && follows_rule && halo_ships_bf16(Q, dir) && (!p.direct || direct_keeps(Q, ghost->ld));
+            if (Q && q_ships != ships16)
                 return fail(c, DORY_ERR_COMM, "local transport: dory_halo_bf16_rows differs: rank %u ships %s rows, rank %u %s rows (the switch and the "
-                            "gather mode must be the same on all ranks%s)", c->nodeId, wire.bf16 ? "bf16" : "fp32", q, wire.bf16 ? "fp32" : "bf16",
-                            p.direct ? ", and dory_halo_bf16_ghosts under halo_direct_recv" : "");
+                            "gather mode must be the same on all ranks%s%s)", c->nodeId, ships16 ? "bf16" : "fp32", q, ships16 ? "fp32" : "bf16",
+                            p.direct ? ", and dory_halo_bf16_ghosts under halo_direct_recv" : "", c->gnn == DORY_GATMH ? ", and dory_gatmh_halo_bf16" : "");
         }
     }
     const bool keep = keeps_bf16(c, wire, ghost);
@@ -965,22 +991,24 @@ static bool gatmh_merged_taken(const dory_ctx *c) {
     const Transport tr = transport_of(c);
     return (tr == Transport::Rccl || tr == Transport::Host || tr == Transport::Local) && c->plan[DORY_BACKWARD].set && !c->plan[DORY_BACKWARD].direct;
 }
-int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, GatmhSend *sd, bool *send) {
+int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, GatmhSend *sd, bool *send, bool *bf16) {
     const HaloPlan &p = c->plan[DORY_BACKWARD];
-    *send = false;
+    *send = *bf16 = false;
     if (!gatmh_merged_taken(c) || !c->fused_pack || c->capturing || !p.d_send_map || p.send_map_rows != c->N || dO->rows != c->N) return DORY_OK;
-    const RowWire wire = pair_wire(c, dO, st);
+    const bool do16 = gatmh_do_bf16(c, dO);
+    const RowWire wire = pair_wire(c, dO, st, do16);
     if ((size_t)p.send_total * wire.row_bytes() > c->send_cap) return DORY_OK;   // (the exchange would regrow the buffer)
-    if (transport_of(c) == Transport::Local)   // (its refusal comes from gatmh_bwd_exchange, before anything is written)
+    if (transport_of(c) == Transport::Local)   // (its refusal comes from gatmh_bwd_exchange / exchange_rows, before anything is written)
         for (uint32_t q = 0; q < c->numNodes; ++q) {
             const dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
-            if (Q && Q->gatmh_merged.load(std::memory_order_acquire) != 1) return DORY_OK;
+            if (Q && (Q->gatmh_merged.load(std::memory_order_acquire) != 1 || halo_ships_bf16(Q, DORY_BACKWARD) != do16)) return DORY_OK;
         }
     sd->buf = c->send_buf;
     sd->row_ptr = p.d_send_map;
     sd->row_slots = p.d_send_map + c->N + 1;
     sd->w = wire.w;
-    sd->R = wire.w + wire.w2;
+    sd->R = (uint32_t)(wire.row_bytes() / sizeof(float));
+    *bf16 = wire.bf16;
     fused_stamp_drop(c);   // (whatever a GEMM left in the send buffer is about to be overwritten)
     *send = true;
     return wait_halo(c);   // the previous exchange has finished reading the buffer
@@ -1000,8 +1028,8 @@ int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor
         return exchange_rows(c, DORY_BACKWARD, dO, bgdo, false, &pair);
     }
     if (on == 1 && !c->capturing) c->merged_split_fallbacks++;   // (the scatter transport: its own layout; halo_direct_recv: two tensors)
-    int rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, false);
-    return rc ? rc : exchange_rows(c, DORY_BACKWARD, st, bgst, false);
+    int rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, false);   // (dory_gatmh_halo_bf16: do by the rule, st always fp32)
+    return rc ? rc : exchange_rows(c, DORY_BACKWARD, st, bgst, false, nullptr, false);
 }
 
 bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd, int *dir) {
@@ -1051,8 +1079,8 @@ int ghost_fp32_current(dory_ctx *c, Tensor *t) {
     return DORY_OK;
 }
 
-// every ghost tensor halo_route can ever name for a model whose exchanges may ship bf16 (halo_ships_bf16: never the multi-head GAT;
-// fg@0 comes from a file), where a row has at least one 8-byte quad
+// every ghost tensor halo_route can ever name for a model whose exchanges may land bf16 (never the multi-head GAT: it has no twins,
+// direct_keeps; fg@0 comes from a file), where a row has at least one 8-byte quad
 static bool ghost_gets_twin(const dory_ctx *c, uint32_t layer, const std::string &name, const Tensor &t) {
     if (!t.owned || t.ld < 4) return false;
     if (c->gnn == DORY_GCN) return (name == "fg" && layer >= 1) || name == "fgxw" || name == "bg" || name == "bgg";
@@ -1437,7 +1465,7 @@ static int gatmh_bwd_split(dory_ctx *c, const char *who, uint32_t layer, Tensor 
     if (layer >= c->L) return fail(c, DORY_ERR_ARG, "%s: layer %u out of range", who, layer);
     *dO = find(c, layer, "do"); *st = find(c, layer, "st"); *bgdo = find(c, layer, "bg_do"); *bgst = find(c, layer, "bg_st");
     if (!*dO || !*st || !*bgdo || !*bgst) return fail(c, DORY_ERR_ARG, "%s: tensors missing", who);
-    *wire = pair_wire(c, *dO, *st);
+    *wire = pair_wire(c, *dO, *st, gatmh_do_bf16(c, *dO));
     return DORY_OK;
 }
 
@@ -1447,9 +1475,42 @@ int dory_gatmh_bwd_wire_row(dory_ctx *c, uint32_t layer, uint32_t *row_floats, u
     RowWire wire;
     int rc = gatmh_bwd_split(c, "gatmh_bwd_wire_row", layer, &dO, &st, &bgdo, &bgst, &wire);
     if (rc) return rc;
-    if (row_floats) *row_floats = wire.w + wire.w2;
-    if (do_floats) *do_floats = wire.w;
+    if (row_floats) *row_floats = (uint32_t)(wire.row_bytes() / sizeof(float));
+    if (do_floats) *do_floats = wire.bf16 ? wire.w / 2 : wire.w;   // (4-byte units: w bf16 are w / 2 of them)
     if (st_floats) *st_floats = wire.w2;
+    return DORY_OK;
+}
+
+int dory_gatmh_bwd_wire_do(dory_ctx *c, uint32_t layer, uint32_t *elem_bytes, uint32_t *elems) {
+    CHECK_CTX(c);
+    Tensor *dO, *st, *bgdo, *bgst;
+    RowWire wire;
+    int rc = gatmh_bwd_split(c, "gatmh_bwd_wire_do", layer, &dO, &st, &bgdo, &bgst, &wire);
+    if (rc) return rc;
+    if (elem_bytes) *elem_bytes = wire.elem_bytes();
+    if (elems) *elems = wire.w;
+    return DORY_OK;
+}
+
+// ---- dory_gatmh_halo_bf16: the multi-head GAT under the rule of dory_halo_bf16_rows (halo_ships_bf16) -------------------------------
+int dory_gatmh_halo_bf16(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || c->gnn != DORY_GATMH || (on != 0 && on != 1))
+        return fail(c, DORY_ERR_ARG, "gatmh_halo_bf16: a context configured as DORY_GATMH; on is 0 or 1");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_halo_bf16: not while an epoch graph is being recorded");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange that may now ship the other element)
+    c->gatmh_halo_bf16.store(on, std::memory_order_release);
+    return DORY_OK;
+}
+
+int dory_gatmh_halo_bf16_stats(dory_ctx *c, uint64_t *fwd_bf16_exchanges, uint64_t *bwd_bf16_exchanges, uint64_t *bwd_bf16_rows,
+                               uint64_t *producer_packed_bf16) {
+    CHECK_CTX(c);
+    if (fwd_bf16_exchanges) *fwd_bf16_exchanges = c->gatmh_fwd_bf16_exchanges;
+    if (bwd_bf16_exchanges) *bwd_bf16_exchanges = c->gatmh_bwd_bf16_exchanges;
+    if (bwd_bf16_rows) *bwd_bf16_rows = c->gatmh_bwd_bf16_rows;
+    if (producer_packed_bf16) *producer_packed_bf16 = c->gatmh_producer_packed_bf16;
     return DORY_OK;
 }
 
@@ -1463,7 +1524,7 @@ int dory_gatmh_bwd_pack(dory_ctx *c, uint32_t layer, float *send_buf) {
     const HaloPlan &p = c->plan[DORY_BACKWARD];
     if (p.send_total && (!send_buf || ((uintptr_t)send_buf & 15))) return fail(c, DORY_ERR_ARG, "gatmh_bwd_pack: a 16-byte aligned device buffer");
     Timed t(c, "halo", c->compute);
-    return pack_rows(c, send_buf, dO, wire, p, c->compute, st);
+    return pack_rows(c, send_buf, dO, wire, p, c->compute, st);   // (dory_gatmh_halo_bf16: the do part by the rule of this moment)
 }
 
 int dory_gatmh_bwd_unpack(dory_ctx *c, uint32_t layer, const float *recv_buf) {

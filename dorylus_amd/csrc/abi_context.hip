@@ -1079,6 +1079,7 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     if (id == OPT_HALO_EXACT_ROWS) c->halo_exact.store((int)value, std::memory_order_release);
     if (id == OPT_HALO_DIRECT_RECV) c->halo_direct.store((int)value, std::memory_order_release);
     if (id == OPT_GCN_BF16_GATHER) c->gcn_bf16_mode.store((int)value, std::memory_order_release);   // (dory_halo_bf16_rows' rule)
+    if (id == OPT_GATMH_BF16_GATHER) c->gatmh_bf16_mode_pub.store((int)value, std::memory_order_release);   // (dory_gatmh_halo_bf16's rule)
     c->ah0_valid = false;   // (another kernel variant sums in another order: a cached ah@0 is only kept across identical settings)
     return DORY_OK;
 }

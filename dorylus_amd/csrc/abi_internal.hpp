@@ -114,7 +114,9 @@ int gat_materialize(dory_ctx *c, uint32_t layer, int which);
 bool tf_layer(dory_ctx *c, uint32_t layer);
 bool tf_active(dory_ctx *c);   // = tf_layer(c, 0)
 // one all-to-all-v of rows with the plan of `dir` (abi_comm.hip)
-int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, const RowPair *pair = nullptr /* merged rows: ctx.hpp */);
+// follows_rule == false: rows whose element the rule of dory_halo_bf16_rows does not decide (the multi-head GAT's st: always fp32)
+int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, const RowPair *pair = nullptr /* merged rows: ctx.hpp */,
+                  bool follows_rule = true);
 // dory_gatmh_bwd_merged_exchange (abi_comm.hip).  gatmh_bwd_exchange: the ghost destinations' do and st rows between the two phases of
 // a whole backward sweep -- one exchange of merged rows where the switch, the transport and the plan allow it, else the two exchanges
 // (a counted split fallback while the switch is on).  gatmh_bwd_send_target: asked before the destination side's row-wise kernel is
@@ -122,7 +124,8 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
 // the backward plan has its send map, no recording, the send buffer holds them); then *sd is filled in and the previous exchange has
 // finished reading the buffer.  Producer and exchange sit inside one dory_aggregate call: no stamp.
 int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor *bgst, bool producer_packed);
-int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, GatmhSend *sd, bool *send);
+// *bf16 (dory_gatmh_halo_bf16): the do part of those rows is bf16 by the rule of this moment -- the launcher's bf16 send form.
+int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, GatmhSend *sd, bool *send, bool *bf16);
 uint32_t gatmh_merged_row_max(const dory_ctx *c);
 // The fused halo pack (abi_comm.hip).  fused_pack_target: the GEMM about to write `out` (M rows, the product's C or its tanh output)
 // may store its rows into the send buffer too -- the feature is on, a plan and its map exist, `out` is the source of an exchange

@@ -515,6 +515,10 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
     AGG_NEED(z, fl, "z"); AGG_NEED(el, fl, "el"); AGG_NEED(er, fl, "er"); AGG_NEED(m, fl, "m"); AGG_NEED(den, fl, "den"); AGG_NEED(o, fl, "o");
     const uint32_t D = z->cols / K;
     const int64_t bfm = c->opt[OPT_GATMH_BF16_GATHER];
+    if (c->N == 0) {   // a rank without vertices: no row to aggregate, whatever the forms and options -- its (empty) exchange is finished as by any consumer
+        if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 0;
+        return wait_halo(c);
+    }
     {
         Timed t(c, "spmm", c->compute);
         const BlockedAdj &Bf = gatmh_blocked_for(In, z->ld);
@@ -620,13 +624,13 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
     int rc;
     // dory_gatmh_bwd_merged_exchange: the send form writes the merged rows the exchange below ships (phase 0 only: asked in front of the launch)
     GatmhSend sd{};
-    bool send = false;
-    if (T.phase == 0 && c->numNodes > 1 && (rc = gatmh_bwd_send_target(c, T.dO, T.st, &sd, &send))) return rc;
+    bool send = false, send16 = false;   // (send16, dory_gatmh_halo_bf16: the wire of this call ships do as bf16)
+    if (T.phase == 0 && c->numNodes > 1 && (rc = gatmh_bwd_send_target(c, T.dO, T.st, &sd, &send, &send16))) return rc;
     if (T.phase != 2) {
         Timed t(c, "loss", c->compute);
         if (send)
             HIPCK(c, launch_gatmh_dst_rowwise_send(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
-                                                   st4, lds4, sd, c->compute));
+                                                   st4, lds4, sd, c->compute, send16));
         else
             HIPCK(c, launch_gatmh_dst_rowwise(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
                                               st4, lds4, c->compute));
@@ -701,6 +705,13 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     const uint32_t D = z->cols / K;
     const GatmhBwd T{fl, K, D, c->opt[OPT_GATMH_BWD_PHASE], z, el, er, m, den, o, dO, dz, tt, del, der, st, fgz, fgel, bgdo, bgst};
     const int64_t bfm = c->opt[OPT_GATMH_BF16_GATHER];
+    if (c->N == 0) {   // a rank without vertices: its share of the attention gradients is zero, and it takes part in the sweep's exchange(s) of no rows
+        for (const char *nm : {"a_l", "a_r"}) {
+            Tensor &g = c->wgrads[fl][nm];
+            HIPCK(c, hipMemsetAsync(g.d, 0, (size_t)g.rows * g.ld * sizeof(float), c->compute));
+        }
+        return gatmh_backward_exchange(c, T);
+    }
     const int shl = gatmh_sweep_hl(K, D, z->ld);
     Tensor *op = find(c, fl, "op"), *dpos = find(c, fl, "dpos");
     const bool dst_rowwise = c->opt[OPT_GATMH_SWEEP] && shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] &&

@@ -88,8 +88,10 @@ struct RowWire {
     bool bf16 = false;
     uint32_t cols = 0;   // (bf16 only: the columns of the tensor below w that the pack reads)
     uint32_t w2 = 0;     // (merged rows only: the floats of the second tensor behind the first's w)
+    // dory_gatmh_halo_bf16: a merged row whose first part is bf16 -- [w bf16 of the first tensor | w2 fp32 of the second], w a multiple of
+    // 8 (the second part starts on a 16-byte boundary, the row is w / 2 + w2 floats, a multiple of 4); `bf16` with w2 != 0 means that
     uint32_t elem_bytes() const { return bf16 ? 2u : 4u; }
-    size_t row_bytes() const { return (size_t)(w + w2) * elem_bytes(); }
+    size_t row_bytes() const { return w2 ? ((size_t)(bf16 ? w / 2 : w) + w2) * 4u : (size_t)w * elem_bytes(); }
 };
 // The second tensor of an exchange of merged rows (the multi-head GAT's st -> bg_st behind do -> bg_do), and whether the producer has
 // written the send rows into the context's send buffer already (gatmh_dst_rowwise_send_kernel): then the exchange runs no pack.
@@ -348,6 +350,11 @@ struct dory_ctx {
     // dory_gat_bf16_gather's mode) -- copies the peers of the local transport may read without this context's lock -- and the
     // eager packs counted: those that wrote bf16 rows, their bytes, those that wrote fp32 rows while the switch was on
     std::atomic<int> halo_bf16{0}, gcn_bf16_mode{0}, gat_bf16_mode_pub{0};
+    // dory_gatmh_halo_bf16 (default off; on top of dory_halo_bf16_rows): the multi-head GAT ships z (gatmh_bf16_gather >= 1) and the
+    // backward sweep's do (== 2) as bf16; the option's mirror for the peers; eager exchanges counted: forward ones that shipped bf16,
+    // backward ones whose do shipped bf16, their send rows, those of them whose merged rows the producer wrote
+    std::atomic<int> gatmh_halo_bf16{0}, gatmh_bf16_mode_pub{0};
+    uint64_t gatmh_fwd_bf16_exchanges = 0, gatmh_bwd_bf16_exchanges = 0, gatmh_bwd_bf16_rows = 0, gatmh_producer_packed_bf16 = 0;
     uint64_t halo_bf16_packs = 0, halo_bf16_bytes = 0, halo_fp32_packs_while_on = 0;
     // bf16 ghost twins (dory_halo_bf16_ghosts; default off: a copy the peers of the local transport may read without this context's
     // lock) and the eager calls counted: exchanges / unpacks whose bf16 rows landed in a twin itself, those a kernel copied into one,
@@ -683,6 +690,8 @@ hipError_t launch_gatmh_dst_rowwise(uint32_t N, uint32_t K, uint32_t D, uint32_t
                                     float *der, float4 *st4, uint32_t lds4, hipStream_t s);
 // dory_gatmh_bwd_merged_exchange, producer-packed: the send form also stores row v's quads of dO below column w and its st records
 // (at float offset w + 4k) into the rows row_slots[row_ptr[v] .. row_ptr[v + 1]) of buf, R = w + 4K floats each
+// dory_gatmh_halo_bf16 (the launcher's `bf16`; gatmh_dst_rowwise_send_bf16_kernel): the do part is w bf16 (a multiple of 8), the st
+// records follow at byte 2 w, R = w / 2 + 4K floats a slot
 struct GatmhSend {
     float *buf;
     const uint32_t *row_ptr;     // N + 1 (dory_halo_send_map)
@@ -691,7 +700,7 @@ struct GatmhSend {
 };
 hipError_t launch_gatmh_dst_rowwise_send(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const float *d_o, const float *o,
                                          const float *op, const float *dpos, const float *er, const float *m, const float *den, float *t,
-                                         float *der, float4 *st4, uint32_t lds4, const GatmhSend &sd, hipStream_t s);
+                                         float *der, float4 *st4, uint32_t lds4, const GatmhSend &sd, hipStream_t s, bool bf16 = false);
 size_t gatmh_src_sweep_scratch_bytes(const BlockedAdj &S, uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk);
 hipError_t launch_gatmh_src_sweep_begin(uint32_t N, uint32_t G, uint32_t K, uint32_t ld, uint32_t ldk, const BlockedAdj &S,
                                         const float4 *st4, const float4 *stg, uint32_t lds4, float *scratch, hipStream_t s);
@@ -739,6 +748,13 @@ hipError_t launch_gather_rows_pair(float *dst, const float *a, uint32_t lda, uin
                                    const uint32_t *rows, uint32_t n, hipStream_t s);
 hipError_t launch_scatter_rows_pair(float *a, uint32_t lda, uint32_t wa, float *b, uint32_t ldb, uint32_t wb, const float *src,
                                     const uint32_t *rows, uint32_t n, hipStream_t s);
+// dory_gatmh_halo_bf16: the same with the first part as bf16 -- rows of [wa bf16 | wb fp32], wa a multiple of 8 (wa / 2 + wb floats a
+// row), lda and ldb multiples of 4.  The gather rounds a[v, 0:wa) to nearest even (pack_bf16x2; the columns behind the tensor's cols
+// are its zero padding); the scatter widens them into [0, wa) of a's whole row, zeros into [wa, lda) and [wb, ldb).
+hipError_t launch_gather_rows_pair_bf16(float *dst, const float *a, uint32_t lda, uint32_t wa, const float *b, uint32_t ldb, uint32_t wb,
+                                        const uint32_t *rows, uint32_t n, hipStream_t s);
+hipError_t launch_scatter_rows_pair_bf16(float *a, uint32_t lda, uint32_t wa, float *b, uint32_t ldb, uint32_t wb, const float *src,
+                                         const uint32_t *rows, uint32_t n, hipStream_t s);
 // dory_halo_bf16_rows: the dense side holds rows of row_elems bf16 (a multiple of 4, 8-byte aligned).  The gather rounds
 // [0, cols) of every listed row (nearest even, the conversion of launch_bf16_rows) and writes zeros into [cols, row_elems); the
 // scatter writes the whole ld-wide row: [0, row_elems) widened from the stream, zeros behind.

@@ -1018,6 +1018,83 @@ hipError_t launch_scatter_rows_pair(float *a, uint32_t lda, uint32_t wa, float *
     return hipGetLastError();
 }
 
+// ---- K6, merged rows with a bf16 first part (dory_gatmh_halo_bf16) ------------------------------------------------------------------
+// The dense side holds rows of wa8 + wb4 chunks of 16 bytes: [a[v, 0:wa) as bf16 | b[v, 0:wb) as fp32], wa = 8 x wa8 -- the multiple
+// of 8 puts the second part on a 16-byte boundary, so no chunk straddles the two parts or two rows and a thread owns one chunk.  pack:
+// in the first part two 16-byte loads, four pack_bf16x2 (round to nearest even, the conversion of every bf16 path) and one 16-byte
+// store; in the second one 16-byte load and one store.  The columns of a behind its cols are the tensor's zero padding, as in the fp32
+// form.  The row list may repeat a row.  `total` = rows x chunks of this launch is at most 2^31 (the launcher slices the rows), so the
+// index and its one divide are 32-bit.
+__global__ __launch_bounds__(256) void gather_rows_pair_bf16_kernel(uint4 *dst, const float *a, uint32_t lda, uint32_t wa8, const float *b,
+                                                                    uint32_t ldb, uint32_t wb4, const uint32_t *rows, uint32_t total) {
+    const uint32_t r16 = wa8 + wb4, stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const uint32_t r = i / r16, c = i - r * r16;
+        const size_t v = rows[r];
+        uint4 q;
+        if (c < wa8) {
+            const float4 *p = reinterpret_cast<const float4 *>(a + v * lda) + 2u * c;
+            const float4 lo = p[0], hi = p[1];
+            q = make_uint4(pack_bf16x2(lo.x, lo.y), pack_bf16x2(lo.z, lo.w), pack_bf16x2(hi.x, hi.y), pack_bf16x2(hi.z, hi.w));
+        } else {
+            q = reinterpret_cast<const uint4 *>(b + v * ldb)[c - wa8];
+        }
+        dst[i] = q;
+    }
+}
+// unpack: a thread owns one quad of a WHOLE row of a or of b (lda4 + ldb4 quads per listed row), as the fp32 form's: below the wire's
+// width four bf16 of the stream widened (a bf16 is the high half of the fp32 with the same value; 8-byte load) or one fp32 quad
+// (16-byte load), zeros behind it.  `total` = rows x (lda4 + ldb4) of this launch is at most 2^31.
+__global__ __launch_bounds__(256) void scatter_rows_pair_bf16_kernel(float *a, uint32_t lda4, uint32_t wa4, float *b, uint32_t ldb4, uint32_t wb4,
+                                                                     const uint4 *src, const uint32_t *rows, uint32_t total) {
+    const uint32_t t4 = lda4 + ldb4, wa8 = wa4 >> 1, r16 = wa8 + wb4, stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const uint32_t r = i / t4, c = i - r * t4;
+        const size_t v = rows[r];
+        const bool first = c < lda4;
+        const uint32_t cc = first ? c : c - lda4;                  // the quad inside its tensor's row
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (first && cc < wa4) {
+            const uint2 u = reinterpret_cast<const uint2 *>(src + (size_t)r * r16)[cc];
+            q = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
+                            __uint_as_float(u.y & 0xFFFF0000u));
+        } else if (!first && cc < wb4) {
+            const uint4 u = src[(size_t)r * r16 + wa8 + cc];
+            q = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
+        }
+        float4 *row = first ? reinterpret_cast<float4 *>(a + v * lda4 * 4) : reinterpret_cast<float4 *>(b + v * ldb4 * 4);
+        row[cc] = q;
+    }
+}
+// (rows per launch: rows x per_row <= 2^31, so that the kernels' indices stay 32-bit)
+static uint32_t pair_bf16_rows_per_launch(uint32_t per_row) { return (1u << 31) / per_row; }
+hipError_t launch_gather_rows_pair_bf16(float *dst, const float *a, uint32_t lda, uint32_t wa, const float *b, uint32_t ldb, uint32_t wb,
+                                        const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || wa + wb == 0) return hipSuccess;
+    if ((wa & 7) || ((wb | lda | ldb) & 3) || wa > lda || wb > ldb || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+    const uint32_t r16 = wa / 8 + wb / 4, step = pair_bf16_rows_per_launch(r16);
+    for (uint32_t r0 = 0; r0 < n; r0 += std::min(step, n - r0)) {
+        const uint32_t total = std::min(step, n - r0) * r16;
+        const uint32_t blocks = std::min<uint32_t>(2048u, (total + 255u) / 256u);
+        hipLaunchKernelGGL(gather_rows_pair_bf16_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(dst) + (size_t)r0 * r16, a, lda, wa / 8,
+                           b, ldb, wb / 4, rows + r0, total);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_scatter_rows_pair_bf16(float *a, uint32_t lda, uint32_t wa, float *b, uint32_t ldb, uint32_t wb, const float *src,
+                                         const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || lda + ldb == 0) return hipSuccess;
+    if ((wa & 7) || ((wb | lda | ldb) & 3) || wa > lda || wb > ldb || ((uintptr_t)src & 15)) return hipErrorInvalidValue;
+    const uint32_t t4 = (lda + ldb) / 4, r16 = wa / 8 + wb / 4, step = pair_bf16_rows_per_launch(t4);
+    for (uint32_t r0 = 0; r0 < n; r0 += std::min(step, n - r0)) {
+        const uint32_t total = std::min(step, n - r0) * t4;
+        const uint32_t blocks = std::min<uint32_t>(2048u, (total + 255u) / 256u);
+        hipLaunchKernelGGL(scatter_rows_pair_bf16_kernel, dim3(blocks), dim3(256), 0, s, a, lda / 4, wa / 4, b, ldb / 4, wb / 4,
+                           reinterpret_cast<const uint4 *>(src) + (size_t)r0 * r16, rows + r0, total);
+    }
+    return hipGetLastError();
+}
+
 // ---- K6, bf16 rows (dory_halo_bf16_rows) ----------------------------------------------------------------------------------------
 // The dense side holds rows of `re4` quads of bf16 (row_elems = 4 x re4 elements, 8 bytes a quad): a row is a multiple of 8
 // bytes, so no quad straddles two rows and a lane owns one quad of one row -- four elements per lane: one 16-byte load (or

@@ -566,6 +566,41 @@ __global__ __launch_bounds__(256) void gatmh_dst_rowwise_send_kernel(GatMhArgs a
     }
 }
 
+// The send form for a bf16 wire (dory_gatmh_halo_bf16): the loads, arithmetic, order and stores of the send form above -- t, der and st
+// come from the fp32 dO and keep their bits -- with the merged row as [dO[v, 0:w) as bf16 | st[v, 0:4K) as fp32] (w a multiple of 8,
+// R = w / 2 + 4K floats a slot): the quad of dO a thread holds goes out as one 8-byte store of four bf16 (pack_bf16x2) at byte 8 col of
+// every slot, the head leader's st record as a 16-byte store at byte 2 w + 16 k.
+__global__ __launch_bounds__(256) void gatmh_dst_rowwise_send_bf16_kernel(GatMhArgs a, int HL, const float *d_o, const float *o, const float *op,
+                                                                          const float *dpos, const float *er, const float *m, const float *den,
+                                                                          float *t_out, float *der_out, float4 *st4, uint32_t lds4, GatmhSend sd) {
+    const uint32_t nchunk = a.ld >> 2;
+    const size_t n = (size_t)a.N * nchunk;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = i < n;
+    const size_t ii = ok ? i : 0;
+    const uint32_t v = (uint32_t)(ii / nchunk), col = (uint32_t)(ii % nchunk);
+    const bool live = ok && col * 4 < a.K * a.D;
+    const uint32_t s0 = sd.row_ptr[v], s1 = ok ? sd.row_ptr[v + 1] : s0;
+    const float4 g = reinterpret_cast<const float4 *>(d_o)[ii], x = reinterpret_cast<const float4 *>(o)[ii],
+                 p = reinterpret_cast<const float4 *>(op)[ii];
+    float tt = live ? fmaf(g.x, x.x, fmaf(g.y, x.y, fmaf(g.z, x.z, g.w * x.w))) : 0.f;     // (columns past K*D are zero in all three)
+    float tp = live ? fmaf(g.x, p.x, fmaf(g.y, p.y, fmaf(g.z, p.z, g.w * p.w))) : 0.f;
+    for (int off = 1; off < HL; off <<= 1) { tt += __shfl_xor(tt, off, 64); tp += __shfl_xor(tp, off, 64); }
+    if (s0 != s1 && col * 4 < sd.w) {
+        const uint2 g16 = make_uint2(pack_bf16x2(g.x, g.y), pack_bf16x2(g.z, g.w));
+        for (uint32_t s = s0; s < s1; ++s) reinterpret_cast<uint2 *>(sd.buf + (size_t)sd.row_slots[s] * sd.R)[col] = g16;
+    }
+    if (live && (col % (uint32_t)HL) == 0) {
+        const uint32_t k = min((col * 4) / a.D, a.K - 1);
+        const size_t vk = (size_t)v * a.ldk + k;
+        t_out[vk] = tt;
+        der_out[vk] = (1.f - GATMH_SLOPE) * (tp - tt * dpos[vk]);
+        const float4 rec = make_float4(er[vk], m[vk], 1.f / den[vk], tt);
+        st4[(size_t)v * lds4 + k] = rec;
+        for (uint32_t s = s0; s < s1; ++s) *reinterpret_cast<float4 *>(sd.buf + (size_t)sd.row_slots[s] * sd.R + (sd.w >> 1) + 4 * k) = rec;
+    }
+}
+
 // ---- backward, source side, on the skeleton: rows = sources u (out-edges), entries = destinations v ---------------------------
 // stx[v,k] = (c1', c2', t): the destination's side of the score in log2 units with 1/den folded in,
 //     alpha_uv = exp2(max(el'_u + c1'_v, 0.2 el'_u + c2'_v)),   c1' = (er - m) log2e + log2(1/den),  c2' = (0.2 er - m) log2e + log2(1/den)
@@ -887,16 +922,22 @@ hipError_t launch_gatmh_dst_rowwise(uint32_t N, uint32_t K, uint32_t D, uint32_t
     return hipGetLastError();
 }
 
-// ... and its send form: the merged rows of the vertices the backward plan sends, written by the producer (sd.w <= ld, sd.R = sd.w + 4 K)
+// ... and its send form: the merged rows of the vertices the backward plan sends, written by the producer (sd.w <= ld, sd.R = sd.w + 4 K; bf16: sd.R = sd.w / 2 + 4 K)
 hipError_t launch_gatmh_dst_rowwise_send(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const float *d_o, const float *o,
                                          const float *op, const float *dpos, const float *er, const float *m, const float *den, float *t,
-                                         float *der, float4 *st4, uint32_t lds4, const GatmhSend &sd, hipStream_t s) {
+                                         float *der, float4 *st4, uint32_t lds4, const GatmhSend &sd, hipStream_t s, bool bf16) {
     if (N == 0) return hipSuccess;
     const int HL = gatmh_sweep_hl(K, D, ld);
     if (!HL || ((ld >> 2) % (uint32_t)HL) != 0) return hipErrorInvalidValue;
-    if (!sd.buf || !sd.row_ptr || !sd.row_slots || (sd.w & 3) || sd.w > ld || sd.R != sd.w + 4 * K || ((uintptr_t)sd.buf & 15)) return hipErrorInvalidValue;
+    if (!sd.buf || !sd.row_ptr || !sd.row_slots || sd.w > ld || ((uintptr_t)sd.buf & 15)) return hipErrorInvalidValue;
+    if (bf16 ? ((sd.w & 7) || sd.R != sd.w / 2 + 4 * K) : ((sd.w & 3) || sd.R != sd.w + 4 * K)) return hipErrorInvalidValue;
     GatMhArgs a{N, K, D, ld, ldk, nullptr, nullptr};
     const size_t n = (size_t)N * (ld >> 2);
+    if (bf16) {   // (dory_gatmh_halo_bf16: the do part of the merged rows as bf16)
+        hipLaunchKernelGGL(gatmh_dst_rowwise_send_bf16_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, a, HL, d_o, o, op, dpos, er, m, den, t,
+                           der, st4, lds4, sd);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(gatmh_dst_rowwise_send_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, a, HL, d_o, o, op, dpos, er, m, den, t, der, st4,
                        lds4, sd);
     return hipGetLastError();

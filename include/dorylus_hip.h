@@ -284,8 +284,9 @@ int dory_gat_bf16_gather_stats(dory_ctx *ctx, uint64_t *k1s, uint64_t *k1s_wide,
  *     model           forward exchange                        backward exchange
  *     GCN             h -> fg, xw -> fgxw: gcn_bf16_gather >= 1    grad -> bg, g -> bgg: gcn_bf16_gather == 2
  *     GAT prototype   z -> fg_z: dory_gat_bf16_gather mode >= 1    grad -> bg_d: mode == 2
- *     multi-head GAT  never                                    never
- * (the multi-head GAT's finishing kernels and blocked forms read fg_z in fp32, and it exchanges do / st itself).
+ *     multi-head GAT  never, unless dory_gatmh_halo_bf16 (below) is on too: then option gatmh_bf16_gather >= 1 / == 2 (its own do)
+ * (without that switch the multi-head GAT keeps fp32 rows: a caller who had gatmh_bf16_gather and this switch on before it existed
+ * keeps the bytes they had).
  * Not taken, i.e. fp32 rows travel as without the switch, the results are the same and the pack is counted in
  * fp32_packs_while_on: the rule says no; the scatter-message transport (the reference's format); a plan made with
  * halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer) -- unless
@@ -343,7 +344,8 @@ int dory_halo_wire_row(dory_ctx *ctx, uint32_t layer, int dir, uint32_t *elem_by
  * direction, kind, columns, width and buffer are what its own wire -- computed at the exchange -- has: a gather mode, any of the three
  * halo switches or halo_exact_rows changed between producer and exchange is a counted fallback with the bytes of the moment.
  * Not taken (counted fallbacks, same bytes): everything the fused pack does not take (above); a one-column tensor (ld == 1: a wire
- * row of 4 elements is wider than the tensor's row); TN products, K == 0, no local rows.  The multi-head GAT never ships bf16.
+ * row of 4 elements is wider than the tensor's row); TN products, K == 0, no local rows.  The multi-head GAT's z ships bf16, and is fused here, only under
+ * dory_gatmh_halo_bf16 (below).
  * Direct plans over RCCL or the host transport whose rows land in twins fuse like any other: only the send side changes.
  * Counters of a fused bf16 exchange: fused_exchanges / fused_rows of dory_halo_fused_pack_stats move as for an fp32 one, and the
  * two of this section; bf16_packs / bf16_bytes of dory_halo_bf16_rows_stats move too (what travelled as bf16: a foreign
@@ -485,6 +487,60 @@ int dory_gatmh_bwd_wire_row(dory_ctx *ctx, uint32_t layer, uint32_t *row_floats,
 int dory_gatmh_bwd_pack(dory_ctx *ctx, uint32_t layer, float *send_buf);
 int dory_gatmh_bwd_unpack(dory_ctx *ctx, uint32_t layer, const float *recv_buf);
 
+/* ---- bf16 halo rows for the 8-head GAT (opt-in, default off, on top of dory_halo_bf16_rows; nothing in the reference) -------------
+ * With option gatmh_bf16_gather >= 1 the forward sweep gathers z / fg_z only from their rounded shadow copy (and the redo kernel rounds
+ * what it re-reads: rounding a rounded row is the identity); with == 2 the source-side sweep gathers do / bg_do only from rounded copies
+ * and nothing else reads bg_do; where the dispatch would take a blocked form, which reads fp32, the option already fails with
+ * DORY_ERR_ARG.  So half of every fp32 ghost row shipped is thrown away on arrival.  With this switch AND dory_halo_bf16_rows on, the
+ * rule of that section covers this model:
+ *     dory_halo_exchange(layer, FORWARD)   z -> fg_z ships bf16 iff gatmh_bf16_gather >= 1 at that moment: the existing bf16 row (row_elems
+ *                                          bf16 = ld, or with halo_exact_rows cols rounded up to 4, zeros behind cols; dory_halo_wire_row
+ *                                          reports it; dory_halo_pack / _unpack follow)
+ *     the backward sweep's do -> bg_do     ships bf16 iff gatmh_bf16_gather == 2 at the moment of that dory_aggregate call (read per call:
+ *                                          a layer run with 1 ships fp32)
+ *     st -> bg_st                          always fp32
+ * Two exchanges (dory_gatmh_bwd_merged_exchange off): do through the bf16 pack / unpack, st through the fp32 ones.  Merged: one row
+ *     [ do[v, 0:w) as bf16 | st[v, 0:4K) as fp32 ]      w = ld, or with halo_exact_rows cols rounded up to a multiple of 8
+ * -- the multiple of 8 puts the st records on a 16-byte boundary and makes the row w / 2 + 4K floats, a multiple of 4; the elements
+ * behind cols are zeros (the tensor's padding).  dory_gatmh_bwd_wire_row keeps answering in 4-byte units (do_floats = w / 2),
+ * dory_gatmh_bwd_wire_do reports the element size and the count w; dory_gatmh_bwd_pack / _unpack follow the rule, so that a caller's own
+ * transport (gatmh_bwd_phase 1 / 2) gets the same rows.  Rounding is round to nearest even (v_cvt_pk_bf16_f32), the conversion of every
+ * bf16 path.  do, st, t, der and every local tensor keep their bits; raw bg_do rows hold the widened rounded values and zeros in
+ * [w, ld), whatever they held before.  Kernels of their own beside the fp32 ones, whose code objects do not change:
+ * gather_rows_pair_bf16_kernel / scatter_rows_pair_bf16_kernel (csrc/elementwise.hip) and gatmh_dst_rowwise_send_bf16_kernel
+ * (csrc/gat_mh_sweep.hip: taken where the fp32 send form is taken, when the wire of that call is bf16 -- no stamp, no further switch).
+ * Forward z: the K2 GEMM's send16 epilogue (dory_halo_fused_pack_bf16) writes exactly this row; without that switch the bf16 pack
+ * kernel runs, a counted fallback of the fused pack as elsewhere.
+ * KEEP FP32 (eager calls counted in fp32_packs_while_on): the scatter transport; plans made with halo_direct_recv = 1 (no twins for
+ * this model: dory_halo_bf16_ghosts stays inert for it); dory_halo_pack_tensor / dory_halo_unpack_tensor (the consumer is unknown); st.
+ * VISIBLE CONSEQUENCE: dory_apply_edge computes fg_el from fg_z after the exchange, so with a bf16 forward wire fg_el comes from rounded
+ * rows.  The contract: every tensor, weight and gradient is bit for bit what a run with the switch off and the same options produces
+ * in which every ghost row of fg_z is replaced by its rounded value between dory_halo_exchange and dory_apply_edge.  The backward under
+ * value 2 changes no bit of any local result; only the raw bg_do shows rounded rows.  After a bf16 exchange the shadow-copy conversion
+ * of the ghost rows still runs (it re-rounds rounded rows: correct, and wasted work; removing it needs twins for this model).
+ * Counters: halo_floats_packed counts 4-byte units; bf16_packs / bf16_bytes of dory_halo_bf16_rows_stats count what travelled as bf16,
+ * a merged row with all its bytes; the merged and fused counters move as for an fp32 exchange.  No buffer is re-sized: rows only get
+ * narrower.  Bytes per sent vertex for 602-128-41, heads 8 / 1, AS ARITHMETIC (no RCCL run with more than one rank is behind them):
+ * forward z 512 -> 256 B (hidden), 256 -> 128 B (last; 88 B exact); merged [do | st] 640 -> 384 B (hidden), 272 -> 144 B (last; 112 B exact).
+ * ALL RANKS MUST SET THE SAME VALUES: in-process ranks that disagree on the switch or the gather value fail with DORY_ERR_COMM before
+ * anything of the exchange is enqueued (the option is published in an atomic mirror when dory_set_option writes it).
+ * dory_gatmh_halo_bf16: on = 0 (default) / 1, any time after dory_configure, outside an exchange; it has an effect only while
+ * dory_halo_bf16_rows is 1; drops the fused pack's stamp; accepted and inert with num_nodes == 1; DORY_ERR_ARG for a context that is
+ * not DORY_GATMH or not configured, other values, or while an epoch graph is being recorded.  With it off every byte and counter is as
+ * before.  dory_gatmh_halo_bf16_stats: eager exchanges since dory_create -- forward ones that shipped bf16, backward ones whose do shipped
+ * bf16 (merged or alone), their send rows, the merged ones of them whose rows the producer wrote; any pointer may be NULL.
+ * Measured on one MI355X -- NO LINK AND NO SECOND GPU ARE BEHIND ANY NUMBER -- profiles/r24_gatmh_halo_bf16.txt
+ * (tools/gatmh_halo_bf16_rate.py: 1.05 M local rows, every row to 1 / 3 peers, 8 x 16, 4 x 16, 4 x 64 and 1 x 41, padded and exact, the
+ * parent's library and this one alternated over three rounds): pair pack -> bf16 pair pack x0.72-0.86 at all sixteen lines, pair unpack
+ * -> bf16 pair unpack x0.75-0.86 at fourteen, row-wise send -> bf16 send x0.82-0.94 at fourteen.  NOT FASTER, NAMED: the bf16 pair
+ * unpack at 1 x 41 with exact rows (x1.010 / x1.008).  A TIE: the bf16 send form at 4 x 64 with one peer per row (x0.977 / x0.978).
+ * With the switch off the headline epoch reads 18.160 / 18.185 ms against the parent's 18.157-18.160 (the second 0.14 % above, as
+ * the last process of the series) and the 8-head GAT epoch 16.055 against 16.051. */
+int dory_gatmh_halo_bf16(dory_ctx *ctx, int on);     /* 0 (default) / 1 */
+int dory_gatmh_halo_bf16_stats(dory_ctx *ctx, uint64_t *fwd_bf16_exchanges, uint64_t *bwd_bf16_exchanges, uint64_t *bwd_bf16_rows,
+                               uint64_t *producer_packed_bf16);
+int dory_gatmh_bwd_wire_do(dory_ctx *ctx, uint32_t layer, uint32_t *elem_bytes, uint32_t *elems);
+
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
  * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels
@@ -492,7 +548,8 @@ int dory_gatmh_bwd_unpack(dory_ctx *ctx, uint32_t layer, const float *recv_buf);
  * this second switch on too, every ghost tensor the rule above can ever cover has a bf16 TWIN -- rows x ld bf16 in the tensor's own
  * row order (wire order under halo_direct_recv), owned by the tensor -- the received rows stay bf16 in it, and the aggregation on
  * bf16 rows gathers its ghost rows from it: no widening, no conversion of ghost rows (the N local rows are converted as ever).
- * Twins: GCN fg of layers >= 1, fgxw, bg, bgg; GAT prototype fg_z, bg_d; never the multi-head GAT; never a tensor of ld < 4 (one
+ * Twins: GCN fg of layers >= 1, fgxw, bg, bgg; GAT prototype fg_z, bg_d; never the multi-head GAT (with dory_gatmh_halo_bf16 its bf16 rows are
+ * widened on arrival and its plans made with halo_direct_recv = 1 keep fp32); never a tensor of ld < 4 (one
  * column: as without the switch).  Allocated by the setter for the tensors that exist (it needs dory_preallocate: DORY_ERR_ARG
  * before it) and by dory_preallocate while the switch is on; never inside an exchange or an aggregation; freed with the tensor, or
  * by on = 0 after any twin that holds the only current copy has been widened.

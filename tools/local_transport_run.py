@@ -54,6 +54,7 @@ def main():
     ap.add_argument("--ranks", type=int, nargs="*", default=None, help="keep only the configurations of these rank counts")
     ap.add_argument("--gatmh-heads", type=int, nargs="*", default=None, help="heads per layer: the multi-head GAT instead of the GCN")
     ap.add_argument("--gatmh-merged", action="store_true", help="dory_gatmh_bwd_merged_exchange(1) on every rank (with --gatmh-heads)")
+    ap.add_argument("--gatmh-halo-bf16", action="store_true", help="dory_gatmh_halo_bf16(1) on every rank (with --gatmh-heads, --bf16-rows and --opt gatmh_bf16_gather=1|2)")
     a = ap.parse_args()
     if a.gatmh_heads:
         a.skip_oracle = True
@@ -80,6 +81,7 @@ def main():
 
     extra = {k: int(v) for k, v in (kv.split("=", 1) for kv in a.opt)}
     recv_bytes, fused_stats, bf16_stats, ghost_stats, convert = {}, {}, {}, {}, {}
+    gat16_stats = {}
     rowwise_stats, loss = {}, {}
 
     def setup(ctx, r, g):
@@ -103,6 +105,8 @@ def main():
                     convert[r] = ctx.timing_get("bf16_convert")
                 if a.bf16_ghosts:
                     ghost_stats[r] = ctx.halo_bf16_ghosts_stats()
+                if a.gatmh_halo_bf16:
+                    gat16_stats[r] = list(ctx.gatmh_halo_bf16_stats())
             close()
         ctx.close = closing
         if a.fused_pack:
@@ -115,6 +119,10 @@ def main():
             ctx.halo_bf16_ghosts(1)
         if a.gatmh_merged:
             ctx.gatmh_bwd_merged_exchange(1)
+        if a.gatmh_halo_bf16:
+            ctx.gatmh_halo_bf16(1)
+            if a.fused_pack:
+                ctx.halo_fused_pack_bf16(1)
         if a.gatmh_heads:
             ctx.upload(0, "h", X[g["localToGlobal"]])
             ctx.labels_upload(labels[g["localToGlobal"]])
@@ -196,6 +204,7 @@ def main():
                    "loss_sum_over_ranks": {"ms": round(sum(loss[r][0] for r in range(P)), 4), "launches": sum(loss[r][1] for r in range(P))} if (a.fused_pack or a.gatmh_heads) else None,
                    "bf16_rows_stats_per_rank": [bf16_stats.get(r) for r in range(P)] if a.bf16_rows else None,
                    "bf16_ghosts_stats_per_rank": [ghost_stats.get(r) for r in range(P)] if a.bf16_ghosts else None,
+                   "gatmh_halo_bf16_stats_per_rank": [gat16_stats.get(r) for r in range(P)] if a.gatmh_halo_bf16 else None,
                    "bf16_convert_sum_over_ranks": {"ms": round(sum(convert[r][0] for r in range(P)), 4), "launches": sum(convert[r][1] for r in range(P))} if a.bf16_rows else None,
                    "wall_s": round(wall, 2)}
             out["runs"].append(rec)
