@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value $(EXTRA)
 CSRC = dorylus_amd/csrc
-OBJS = $(CSRC)/abi_context.o $(CSRC)/abi_stages.o $(CSRC)/abi_comm.o $(CSRC)/spmm.o $(CSRC)/spmm_blocked.o $(CSRC)/gemm.o $(CSRC)/elementwise.o $(CSRC)/gat_mh.o $(CSRC)/gat_mh_blocked.o $(CSRC)/gat_mh_sweep.o
+OBJS = $(CSRC)/abi_context.o $(CSRC)/abi_stages.o $(CSRC)/abi_comm.o $(CSRC)/spmm.o $(CSRC)/spmm_blocked.o $(CSRC)/gemm.o $(CSRC)/elementwise.o $(CSRC)/gat_mh.o $(CSRC)/gat_mh_blocked.o $(CSRC)/gat_mh_sweep.o $(CSRC)/gat_mh_rows.o
 HOSTOBJS = $(patsubst %.cpp,%.o,$(filter-out %_main.cpp,$(wildcard dorylus_amd/host/*.cpp)))
 GRAPHSERVER = dorylus_amd/graphserver
 INPUTS = dorylus_amd/dory-inputs

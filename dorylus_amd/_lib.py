@@ -36,6 +36,7 @@ SYMBOLS = [
     "dory_halo_fused_pack_rowwise", "dory_halo_fused_pack_rowwise_stats",
     "dory_gatmh_bwd_merged_exchange", "dory_gatmh_bwd_merged_exchange_stats", "dory_gatmh_bwd_wire_row", "dory_gatmh_bwd_pack",
     "dory_gatmh_bwd_unpack", "dory_gatmh_halo_bf16", "dory_gatmh_halo_bf16_stats", "dory_gatmh_bwd_wire_do",
+    "dory_gatmh_row_gather", "dory_gatmh_row_gather_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -146,6 +147,8 @@ def load():
         "dory_gatmh_halo_bf16": [vp, i32],
         "dory_gatmh_halo_bf16_stats": [vp] + [C.POINTER(u64)] * 4,
         "dory_gatmh_bwd_wire_do": [vp, u32, C.POINTER(u32), C.POINTER(u32)],
+        "dory_gatmh_row_gather": [vp, i32],
+        "dory_gatmh_row_gather_stats": [vp] + [C.POINTER(u64)] * 4,
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -181,8 +184,8 @@ def load():
                 or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
                 or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")
                 or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")
-                or name.startswith("dory_gatmh_bwd_") or name.startswith("dory_gatmh_halo_bf16")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange / its bf16 halo rows)
+                or name.startswith("dory_gatmh_bwd_") or name.startswith("dory_gatmh_halo_bf16") or name.startswith("dory_gatmh_row_gather")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange / its bf16 halo rows / its row-gather kernels)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -660,6 +663,18 @@ class Context:
     def gatmh_bwd_unpack(self, layer, dev_ptr):
         """received merged rows out of a device buffer into bg_do / bg_st of `layer`, whole ghost rows (padding zeroed)"""
         self._ck(self.lib.dory_gatmh_bwd_unpack(self.h, layer, C.c_void_p(dev_ptr)))
+
+    def gatmh_row_gather(self, mode=1):
+        """the multi-head GAT's row-gather kernels with ghost rows (dory_gatmh_row_gather): 0 (default) = where a partitioned
+        aggregate would otherwise be refused (no sweep layout, no blocked layout, a head shape neither covers), 1 = in place of
+        every other family, single partitions included (tests, measurement)"""
+        self._ck(self.lib.dory_gatmh_row_gather(self.h, int(mode)))
+
+    def gatmh_row_gather_stats(self):
+        """(fwd, dst_edge_pass, dst_rowwise, src): the passes the row-gather family ran since dory_create, eager calls and recordings"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._ck(self.lib.dory_gatmh_row_gather_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

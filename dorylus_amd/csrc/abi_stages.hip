@@ -522,7 +522,10 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
     {
         Timed t(c, "spmm", c->compute);
         const BlockedAdj &Bf = gatmh_blocked_for(In, z->ld);
-        const bool blocked = c->opt[OPT_GATMH_BLOCKED] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
+        // dory_gatmh_row_gather = 1: the row-gather family (gat_mh_rows.hip) in place of every other; 0: where a partitioned call
+        // finds neither layout below
+        const bool rows_forced = c->gatmh_row_gather == 1;
+        const bool blocked = !rows_forced && c->opt[OPT_GATMH_BLOCKED] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
                              (D % 4 == 0 || K == 1) &&
                              (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
         AGG_NEED(fgz, fl, "fg_z"); AGG_NEED(fgel, fl, "fg_el");
@@ -533,12 +536,13 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
         // partition they would refuse takes the blocked kernels instead of failing, as spmm() does)
         SpmmArgs sa{};
         sa.N = c->N; sa.ld = z->ld;
-        const bool sweep = c->opt[OPT_GATMH_SWEEP] && c->opt[OPT_SPMM_VARIANT] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
+        const bool sweep = !rows_forced && c->opt[OPT_GATMH_SWEEP] && c->opt[OPT_SPMM_VARIANT] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
                            shl != 0 && op && dpos && sweep_supported(sa, Sf, gatmh_sweep_group(z->ld));
         const bool bf16 = bfm >= 1;
         if (bf16 && !sweep)
             return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
                         (long long)bfm,
+                        rows_forced ? "dory_gatmh_row_gather = 1 (the row-gather kernels have no bf16 form)" :
                         !c->opt[OPT_GATMH_SWEEP] ? "gatmh_sweep = 0" :
                         c->opt[OPT_SPMM_VARIANT] != 2 ? "spmm_variant is not 2" :
                         !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
@@ -583,8 +587,18 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                                                   In.ghosts > 0, c->compute, stat_partial,
                                                   c->opt[OPT_GATMH_EL_ON_THE_FLY] ? c->weights[fl]["a_l"].d : nullptr));
         }
-        else if (c->numNodes > 1)
-            return fail(c, DORY_ERR_ARG, "multi-head GAT: a partitioned run needs the source-blocked kernels (gatmh_blocked = 1, K*D a shape they cover)");
+        else if (rows_forced || c->numNodes > 1) {
+            // the row-gather family: the ghost rows have to have landed (overlapping the interior rows with the exchange: DESIGN.md 7)
+            if (!op || !dpos || !gatmh_rows_ok(K, D, z->ld))
+                return fail(c, DORY_ERR_ARG, "multi-head GAT: the row-gather kernels need op / dpos and K*D <= ld <= 256 (K = %u, D = %u, ld = %u)", K, D, z->ld);
+            int rc = wait_halo(c);
+            if (rc) return rc;
+            HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, z->d, In.ghosts ? fgz->d : nullptr, el->d,
+                                               In.ghosts ? fgel->d : nullptr, er->d, c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d,
+                                               c->compute));
+            if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
+            c->gatmh_rows_fwd++;
+        }
         else
             HIPCK(c, launch_gatmh_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, z->d, el->d, er->d,
                                           o->d, m->d, den->d, c->compute));
@@ -694,8 +708,46 @@ static int gatmh_backward_blocked(dory_ctx *c, const GatmhBwd &T, const BlockedA
     return DORY_OK;
 }
 
+// the row-gather family (gat_mh_rows.hip), in the two phases of the blocked form: the destination side over the in-edges (ghost
+// sources) -- the row-wise kernel on op / dpos where this layer's forward left them and it covers the shape (`rowwise`), else an edge
+// pass --, the exchange of do / st (pack kernels: nothing here writes send rows), the source side over the out-edges (ghost destinations)
+static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tensor *dpos, bool rowwise) {
+    Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
+    const uint32_t K = T.K, D = T.D, ld = T.z->ld, ldk = T.el->ld, lds4 = T.st->ld / 4;
+    float4 *st4 = reinterpret_cast<float4 *>(T.st->d);
+    if (!gatmh_rows_ok(K, D, ld))
+        return fail(c, DORY_ERR_ARG, "multi-head GAT: the row-gather kernels need K*D <= ld <= 256 (K = %u, D = %u, ld = %u)", K, D, ld);
+    if (T.phase != 2) {   // destination side: t, der, st
+        if (rowwise) {
+            Timed t(c, "loss", c->compute);
+            HIPCK(c, launch_gatmh_dst_rowwise(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
+                                              st4, lds4, c->compute));
+            c->gatmh_rows_dst_rowwise++;
+        } else {
+            Timed t(c, "spmm", c->compute);
+            HIPCK(c, launch_gatmh_rows_dst(c->N, K, D, ld, ldk, In.ptr, In.idx, T.z->d, In.ghosts ? T.fgz->d : nullptr, T.el->d,
+                                           In.ghosts ? T.fgel->d : nullptr, T.er->d, c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d,
+                                           T.der->d, st4, lds4, c->compute));
+            c->gatmh_rows_dst_edge++;
+        }
+    }
+    if (T.phase == 1) return DORY_OK;
+    int rc = gatmh_backward_exchange(c, T);
+    if (rc) return rc;
+    {
+        Timed t(c, "spmm", c->compute);
+        HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, T.dO->d, Out.ghosts ? T.bgdo->d : nullptr, st4,
+                                       Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
+                                       c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute));
+        c->gatmh_rows_src++;
+    }
+    HIPCK(c, launch_gatmh_dattn(c->N, K, D, ld, ldk, T.z->d, T.del->d, T.der->d, c->wgrads[T.fl]["a_l"].d,
+                                c->wgrads[T.fl]["a_r"].d, c->scratch, c->scratch_bytes, c->compute));
+    return DORY_OK;
+}
+
 // the backward of the edge softmax + weighted sum: the sweep forms, else the blocked kernels (same m / den / st semantics),
-// else (single partition) the row-wise kernels
+// else (partitioned runs; dory_gatmh_row_gather = 1: first) the row-gather family, else (single partition) the row-wise kernels
 static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
     const uint32_t K = c->heads[fl];
@@ -725,8 +777,10 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     // bf16 rows of do / bg_do for the source-side sweep (gatmh_bf16_gather = 2): refused, before anything is launched, where
     // the call would not take that sweep; the shadow buffer is sized here too (it cannot grow inside a recording)
     const bool bf16 = bfm >= 2;
-    if (bf16 && !(dst_rowwise && src_sweep))
+    const bool rows_forced = c->gatmh_row_gather == 1;
+    if (bf16 && (rows_forced || !(dst_rowwise && src_sweep)))
         return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = 2 needs the sweep forms of the backward pass, which this call would not take: %s",
+                    rows_forced ? "dory_gatmh_row_gather = 1 (the row-gather kernels have no bf16 form)" :
                     !c->opt[OPT_GATMH_SWEEP] ? "gatmh_sweep = 0" :
                     c->opt[OPT_SPMM_VARIANT] != 2 ? "spmm_variant is not 2" :
                     !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
@@ -744,15 +798,16 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
         }
     }
     if ((rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + (size_t)c->N * K * 16 + 256))) return rc;
-    if (dst_rowwise && src_sweep) return gatmh_backward_sweep(c, T, op, dpos, shl, sa, bf16);
+    if (!rows_forced && dst_rowwise && src_sweep) return gatmh_backward_sweep(c, T, op, dpos, shl, sa, bf16);
     const BlockedAdj &Bbi = gatmh_blocked_for(In, z->ld), &Bbo = gatmh_blocked_for(Out, z->ld);
     const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
-    if (c->opt[OPT_GATMH_BLOCKED] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na && nbmax > 0 &&
+    if (!rows_forced && c->opt[OPT_GATMH_BLOCKED] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na && nbmax > 0 &&
         gatmh_backward_blocked_ok(K, D, z->ld) &&
         (size_t)nbmax * c->N * (z->ld + K) * sizeof(float) <= c->partial_bytes)
         return gatmh_backward_blocked(c, T, Bbi, Bbo);
-    if (c->numNodes > 1)
-        return fail(c, DORY_ERR_ARG, "multi-head GAT: a partitioned run needs the source-blocked kernels (gatmh_blocked = 1, K*D a shape they cover)");
+    if (rows_forced || c->numNodes > 1)   // (op / dpos are current whichever family's forward left them; gatmh_sweep is not asked)
+        return gatmh_backward_rows(c, T, op, dpos, shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] &&
+                                                   ((z->ld >> 2) % (uint32_t)shl) == 0);
     Timed t(c, "spmm", c->compute);
     HIPCK(c, launch_gatmh_backward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Out.ptr, Out.idx, z->d, el->d,
                                    er->d, m->d, den->d, dO->d, c->weights[fl]["a_l"].d, c->weights[fl]["a_r"].d,
@@ -874,6 +929,26 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
     if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "aggregate GAT: layer %u out of range", layer);
     if (c->gnn != DORY_GATMH) return aggregate_gat(c, layer - 1, dir);
     return dir == DORY_FORWARD ? aggregate_gatmh_forward(c, layer - 1) : aggregate_gatmh_backward(c, layer - 1);
+}
+
+// ---- dory_gatmh_row_gather: the switch of the row-gather family (gat_mh_rows.hip) and its pass counters (include/dorylus_hip.h) ----
+int dory_gatmh_row_gather(dory_ctx *c, int mode) {
+    CHECK_CTX(c);
+    if (mode != 0 && mode != 1) return fail(c, DORY_ERR_ARG, "gatmh_row_gather: mode is 0 or 1");
+    if (mode == 1 && (!c->configured || c->gnn != DORY_GATMH))
+        return fail(c, DORY_ERR_ARG, "gatmh_row_gather: mode 1 needs a context configured as DORY_GATMH");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather: not while an epoch graph is being recorded");
+    c->gatmh_row_gather = mode;
+    return DORY_OK;
+}
+
+int dory_gatmh_row_gather_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *dst_rowwise, uint64_t *src) {
+    CHECK_CTX(c);
+    if (fwd) *fwd = c->gatmh_rows_fwd;
+    if (dst_edge_pass) *dst_edge_pass = c->gatmh_rows_dst_edge;
+    if (dst_rowwise) *dst_rowwise = c->gatmh_rows_dst_rowwise;
+    if (src) *src = c->gatmh_rows_src;
+    return DORY_OK;
 }
 
 int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {

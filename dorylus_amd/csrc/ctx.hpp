@@ -283,7 +283,12 @@ struct dory_ctx {
     std::vector<char> gat_nsum_bf16;     // ... summed over rows rounded to bf16 (dory_gat_bf16_gather was on when the forward made it)
     bool gat_ones_set = false;           // "ones"@0 filled
     bool last_spmm_unit = false;         // the last spmm() gathered with unit weights and a per-row factor (K1s / K1b), not with per-edge values (K1)
-    std::vector<char> gatmh_fwd_swept;   // multi-head GAT: the forward of this layer ran on the sweep skeleton ("op", "dpos" are current)
+    std::vector<char> gatmh_fwd_swept;   // multi-head GAT: the forward of this layer left "op" / "dpos" (the sweep skeleton, or the row-gather family)
+    // dory_gatmh_row_gather: 0 = the row-gather family (gat_mh_rows.hip) where a partitioned aggregation would otherwise be refused,
+    // 1 = in place of every other family; the passes it ran (eager calls and recordings): forward, destination side as an edge pass /
+    // as the row-wise kernel on op and dpos, source side
+    int gatmh_row_gather = 0;
+    uint64_t gatmh_rows_fwd = 0, gatmh_rows_dst_edge = 0, gatmh_rows_dst_rowwise = 0, gatmh_rows_src = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -710,6 +715,23 @@ hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uin
                                          const float *el, const float *d_o, const float *der, const float *a_l, const float *a_r, float *del,
                                          float *dz, float *scratch, hipStream_t s,
                                          bool bf16 = false /* d_o stays fp32: the self edge's row is rounded in registers */);
+// the row-gather family with ghost rows (csrc/gat_mh_rows.hip): one lane group per row, one float4 per lane, ids >= N select row
+// id - N of the ghost array (zg / elg / dog / stg: null on a rank without ghosts); any shape of gatmh_shape_ok with K*D <= ld <= 256.
+// forward: o, m (the row's true maximum), den, op, dpos; dst: t, der, st4 (an edge pass; where op / dpos are current and
+// launch_gatmh_dst_rowwise covers the shape the caller runs that instead); src: del, dz with the finishing terms
+bool gatmh_rows_ok(uint32_t K, uint32_t D, uint32_t ld);
+hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
+                                     const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
+                                     const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
+                                     hipStream_t s);
+hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
+                                 const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
+                                 const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
+                                 float4 *st4, uint32_t lds4, hipStream_t s);
+hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
+                                 const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
+                                 const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
+                                 float *del, float *dz, hipStream_t s);
 // row-wise backward (single partition; feature-per-lane or (edge, head, piece)-per-lane kernels by shape)
 hipError_t launch_gatmh_backward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const uint64_t *rowptr, const uint32_t *colidx,

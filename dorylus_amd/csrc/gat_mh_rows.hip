@@ -1,0 +1,514 @@
+// gat_mh_rows.hip -- the multi-head GAT's row-gather kernels WITH ghost rows: the family a partitioned dory_aggregate runs where
+// neither the sweep layout (gat_mh_sweep.hip) nor the source-blocked layout (gat_mh_blocked.hip) applies -- more source windows or
+// blocks than the layouts hold, ghost tensors past the 32-bit byte offsets of the sweep's buffer resources, a head shape neither
+// family covers (D = 1, 2) -- and, with dory_gatmh_row_gather(ctx, 1), everywhere.  Written the way K1 (spmm_rows_body, spmm.hip) is
+// written for GCN:
+//
+//   * one lane GROUP (8 / 16 / 32 / 64 lanes, by ld / 4) owns one row; every lane keeps ONE float4 of it (K*D <= 256: a wave always
+//     covers a row), 256-thread workgroups, 16-byte loads;
+//   * the group loads GROUP edge ids with one coalesced load and broadcasts them (bcast_u32<GROUP>); four gathered rows are in
+//     flight per group (the source side with four heads per lane: two -- see gatmh_rows_src_kernel); the self edge is the last
+//     entry of the id stream, and a row's tail is one masked batch, not single steps;
+//   * an id s >= N selects row s - N of the ghost array (which may be null on a rank without ghosts); plain 64-bit addressing
+//     throughout -- a ghost tensor of 14.7 GB is exactly what sends a partition here;
+//   * nothing of size E x K is stored, no atomics (same input, same bits), no LDS, no gate, poll or inter-workgroup wait.
+//
+// Heads and lanes.  HPQ = heads per float4: 1 where D % 4 == 0 (the head's D / 4 lanes are reduced by DPP moves where a kernel
+// needs a dot product: rows_allreduce) and for a single head of any width (K == 1: the whole group is the head); 2 for D == 2; 4 for D == 1 (heads
+// inside a lane: no cross-lane step at all).  Columns past K*D are zero padding: they are masked out of every dot product and
+// stored as zeros.
+//
+// Forward (in-edges, self edge last): ONE pass with online rescaling -- the running maximum moves once per batch of four edges, so
+// a batch costs five exponentials per head, not eight; the two-pass form (scores first, as gatmh_forward_kernel) would gather every
+// el row twice and was not built.  The sources' scores are formed from the gathered rows (rows_el: the el tensor's bits, without
+// a second 128-byte line per edge); every lane of a head carries the head's (m, den, den+) itself.  It writes o, m, den and op,
+// dpos (the positive-branch part of o and of the attention mass, self edge on its branch: gatmh_forward_redo_body's definition).
+// m is the row's TRUE maximum per head, as in the blocked forms.
+// Backward, destination side (in-edges): where the forward left op / dpos and launch_gatmh_dst_rowwise covers the shape that
+// kernel runs (abi_stages.hip) -- no edges; otherwise gatmh_rows_dst_kernel: gatmh_backward_dst_kernel's arithmetic per edge.
+// Backward, source side (out-edges; destinations local or ghost: do / bg_do, st / bg_st): the form without dot products,
+//     del = <Z_u, 0.2 S + 0.8 S+> - (0.2 T + 0.8 T+),   dz = S + del a_l + der a_r      (sums of gatmh_src_finish_body)
+// one reduction per row instead of one per edge.
+//
+// Not taken here: bf16 rows (gatmh_bf16_gather stays with the sweep forms), overlap of the interior rows with the exchange, and
+// HUB SPLITTING -- a row's edges are walked by its one lane group; cutting hub rows into chunks with merged (m, den, acc) states
+// matters for power-law partitions too large for the layouts and is left out.
+#include "gat_mh.hpp"
+#include "spmm_common.hpp"
+
+namespace dory {
+
+// what a lane knows of its place: row, float4 column, the heads of its float4 (clamped: loads stay in bounds), which of its four
+// columns hold features
+template <int GROUP, int HPQ>
+struct RowsLane {
+    uint32_t v, nchunk, col, li;
+    bool row_ok, lane_ok;
+    uint32_t hk[HPQ];
+    bool cm[4];
+    __device__ __forceinline__ RowsLane(const GatMhArgs &a) {
+        constexpr int RPW = 64 / GROUP, RPB = 4 * RPW;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        li = (uint32_t)(lane % GROUP);
+        const uint32_t rid = blockIdx.x * RPB + wave * RPW + lane / GROUP;
+        row_ok = rid < a.N;
+        v = row_ok ? rid : 0;
+        if constexpr (GROUP == 64) v = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);   // one row per wave: scalar row base
+        nchunk = a.ld >> 2;
+        const uint32_t KD = a.K * a.D;
+        lane_ok = row_ok && li < nchunk && 4 * li < KD;
+        col = li < nchunk ? li : 0;           // lanes past the row gather column 0 (valid memory) and never store
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) hk[s] = min((4 * col) / a.D + (uint32_t)s, a.K - 1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) cm[c] = lane_ok && 4 * col + c < KD;
+    }
+    // the lane that stores a head's per-(v,k) values (HPQ == 1); with HPQ > 1 every lane stores its own heads (head_live)
+    __device__ __forceinline__ bool leader(const GatMhArgs &a) const {
+        return lane_ok && (a.K == 1 ? li == 0 : (col % (a.D >> 2)) == 0);
+    }
+    __device__ __forceinline__ bool head_live(const GatMhArgs &a, int s) const { return lane_ok && (4 * col) / a.D + (uint32_t)s < a.K; }
+};
+template <int HPQ> __device__ __forceinline__ constexpr int rows_slot(int c) { return c * HPQ / 4; }   // the head slot of column c
+
+__device__ __forceinline__ float4 rows_mask(const float4 &x, const bool (&cm)[4]) {
+    return make_float4(cm[0] ? x.x : 0.f, cm[1] ? x.y : 0.f, cm[2] ? x.z : 0.f, cm[3] ? x.w : 0.f);
+}
+// per-slot dot product of two float4 (the caller has masked one of them)
+template <int HPQ>
+__device__ __forceinline__ void rows_dot(const float4 &g, const float4 &x, float (&p)[HPQ]) {
+    if constexpr (HPQ == 1) p[0] = fmaf(g.x, x.x, fmaf(g.y, x.y, fmaf(g.z, x.z, g.w * x.w)));
+    else if constexpr (HPQ == 2) { p[0] = fmaf(g.x, x.x, g.y * x.y); p[1] = fmaf(g.z, x.z, g.w * x.w); }
+    else { p[0] = g.x * x.x; p[1] = g.y * x.y; p[2] = g.z * x.z; p[3] = g.w * x.w; }
+}
+// acc += w[slot(c)] * x[c]
+template <int HPQ>
+__device__ __forceinline__ float4 rows_axpy(const float (&w)[HPQ], const float4 &x, float4 acc) {
+    acc.x = fmaf(w[rows_slot<HPQ>(0)], x.x, acc.x);
+    acc.y = fmaf(w[rows_slot<HPQ>(1)], x.y, acc.y);
+    acc.z = fmaf(w[rows_slot<HPQ>(2)], x.z, acc.z);
+    acc.w = fmaf(w[rows_slot<HPQ>(3)], x.w, acc.w);
+    return acc;
+}
+template <int HPQ>
+__device__ __forceinline__ float4 rows_scale(const float (&w)[HPQ], const float4 &x) {
+    return make_float4(w[rows_slot<HPQ>(0)] * x.x, w[rows_slot<HPQ>(1)] * x.y, w[rows_slot<HPQ>(2)] * x.z, w[rows_slot<HPQ>(3)] * x.w);
+}
+
+// sum over the HL lanes of a head (a power of two, aligned), result in every lane: DPP inside the VALU up to a row of 16 lanes
+// (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror: after the quad steps all lanes of a quad agree, so a mirror hands
+// over the other half's sum), xor shuffles beyond -- the additions of a butterfly over offsets 1, 2, 4, ... in that order
+__device__ __forceinline__ float rows_allreduce(float v, int HL) {
+    if (HL > 1) v += dpp_mov<0xB1>(v);
+    if (HL > 2) v += dpp_mov<0x4E>(v);
+    if (HL > 4) v += dpp_mov<0x141>(v);
+    if (HL > 8) v += dpp_mov<0x140>(v);
+    if (HL > 16) v += __shfl_xor(v, 16, 64);
+    if (HL > 32) v += __shfl_xor(v, 32, 64);
+    return v;
+}
+// ELFLY: the source's scores el[u,k] = <Z[u,k,:], a_l[k,:]> formed from the gathered row instead of gathered from el / fg_el -- an
+// el row is a 128-byte line of its own per edge, half as much again as a 64-float row.  The arithmetic is launch_gatmh_scores's,
+// operation for operation (a float4's four fmaf in column order from zero, then the butterfly over the head's lanes; heads inside
+// a lane: the scalar kernel's chain), so the value is the el tensor's to the bit and the backward passes, which read the tensor,
+// see the same alpha.  Rows whose float4 count is no power of two (ld = 96, 160, 192, 224) get their scores from the scalar
+// kernel's chain over D columns: those shapes (one head per float4 only) gather el as before.  al: a_l's four columns, padding zeroed.
+template <int HPQ>
+__device__ __forceinline__ void rows_el(const float4 &x, const float4 &al, int HL, float (&sc)[HPQ]) {
+    if constexpr (HPQ == 1) sc[0] = rows_allreduce(fmaf(x.w, al.w, fmaf(x.z, al.z, fmaf(x.y, al.y, fmaf(x.x, al.x, 0.f)))), HL);
+    else if constexpr (HPQ == 2) { sc[0] = fmaf(x.y, al.y, fmaf(x.x, al.x, 0.f)); sc[1] = fmaf(x.w, al.w, fmaf(x.z, al.z, 0.f)); }
+    else { sc[0] = fmaf(x.x, al.x, 0.f); sc[1] = fmaf(x.y, al.y, 0.f); sc[2] = fmaf(x.z, al.z, 0.f); sc[3] = fmaf(x.w, al.w, 0.f); }
+}
+template <int GROUP, int HPQ>
+__device__ __forceinline__ float4 rows_attn4(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, const float *a_l) {
+    const uint32_t KD = a.K * a.D;
+    float v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] = L.cm[c] ? a_l[min(4 * L.col + c, KD - 1)] : 0.f;
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------------
+template <int HPQ>
+struct RowsFwdState {
+    float erv[HPQ], mx[HPQ], den[HPQ], denp[HPQ];
+    float4 acc, accp;
+    // NB edges at once: the maximum moves once, the sums are rescaled once
+    template <int NB>
+    __device__ __forceinline__ void step(const float4 (&x)[NB], const float (&sc)[NB][HPQ]) {
+        float al[NB][HPQ], alp[NB][HPQ], f[HPQ];
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) {
+            float pre[NB], sv[NB], mn = mx[s];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                pre[u] = sc[u][s] + erv[s];
+                sv[u] = lrelu02(pre[u]);
+                mn = fmaxf(mn, sv[u]);
+            }
+            f[s] = __expf(mx[s] - mn);            // (exp(-inf) = 0 on the first batch)
+            float d = den[s] * f[s], dp = denp[s] * f[s];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                al[u][s] = __expf(sv[u] - mn);
+                alp[u][s] = pre[u] > 0.f ? al[u][s] : 0.f;
+                d += al[u][s];
+                dp += alp[u][s];
+            }
+            den[s] = d; denp[s] = dp; mx[s] = mn;
+        }
+        acc = rows_scale<HPQ>(f, acc);
+        accp = rows_scale<HPQ>(f, accp);
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            acc = rows_axpy<HPQ>(al[u], x[u], acc);
+            accp = rows_axpy<HPQ>(alp[u], x[u], accp);
+        }
+    }
+};
+
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                                 const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                                 float *m_out, float *den_out, float *dpos_out) {
+    const RowsLane<GROUP, HPQ> L(a);
+    const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 *z4 = reinterpret_cast<const float4 *>(z), *zg4 = reinterpret_cast<const float4 *>(zg);
+    RowsFwdState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        S.erv[s] = er[(size_t)L.v * a.ldk + L.hk[s]];
+        S.mx[s] = -INFINITY;
+        S.den[s] = S.denp[s] = 0.f;
+    }
+    S.acc = S.accp = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the row's entries: its in-edges, then the self edge (id v, a local row like any other); batches of four, the dead slots of the
+    // last batch gather the last entry's row again and are masked by a score of -inf (alpha = exp(-inf) = 0)
+    const uint64_t e0 = L.row_ok ? a.ptr[L.v] : 0, end = L.row_ok ? a.ptr[L.v + 1] : 0;
+    const uint64_t total = L.row_ok ? end - e0 + 1 : 0;
+    for (uint64_t done = 0; done < total; done += GROUP) {                     // GROUP == 64: wave-uniform
+        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+        const uint64_t ee = e0 + done + L.li;
+        const uint32_t my_idx = ee < end ? a.idx[ee] : L.v;
+        for (int j = 0; j < n; j += 4) {
+            float4 x[4];
+            float sc[4][HPQ];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                const bool loc = s < a.N;
+                const size_t r = loc ? s : s - a.N;
+                x[u] = (loc ? z4 : zg4)[r * L.nchunk + L.col];
+                if constexpr (!ELFLY) {
+                    const float *ep = (loc ? el : elg) + r * a.ldk;
+#pragma unroll
+                    for (int h = 0; h < HPQ; ++h) sc[u][h] = ep[L.hk[h]];
+                }
+            }
+            if constexpr (ELFLY)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) rows_el<HPQ>(x[u], al4, HL, sc[u]);
+#pragma unroll
+            for (int u = 1; u < 4; ++u)
+#pragma unroll
+                for (int h = 0; h < HPQ; ++h) sc[u][h] = j + u < n ? sc[u][h] : -INFINITY;
+            S.template step<4>(x, sc);
+        }
+    }
+    if (!L.row_ok) return;
+    if (!L.lane_ok) return;
+    float idn[HPQ];
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) idn[s] = 1.f / S.den[s];
+    const size_t oi = (size_t)L.v * L.nchunk + L.col;
+    reinterpret_cast<float4 *>(o)[oi] = rows_mask(rows_scale<HPQ>(idn, S.acc), L.cm);
+    reinterpret_cast<float4 *>(op)[oi] = rows_mask(rows_scale<HPQ>(idn, S.accp), L.cm);
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s)
+        if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+            const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
+            m_out[vk] = S.mx[s];
+            den_out[vk] = S.den[s];
+            dpos_out[vk] = S.denp[s] * idn[s];
+        }
+}
+
+// ---- backward, destination side: t[v,k] = sum a*da, der[v,k] = sum a*da*l' - t * sum a*l', st = (er, m, 1/den, t) -------------------
+template <int HPQ>
+struct RowsDstState {
+    float erv[HPQ], mv[HPQ], idn[HPQ], t[HPQ], a1[HPQ], a2[HPQ];
+    float4 g;   // dO[v], padding columns zeroed
+    template <int NB>
+    __device__ __forceinline__ void step(const float4 (&x)[NB], const float (&sc)[NB][HPQ], int HL) {
+        float prod[NB][HPQ];
+#pragma unroll
+        for (int u = 0; u < NB; ++u) rows_dot<HPQ>(g, x[u], prod[u]);
+        if constexpr (HPQ == 1)
+#pragma unroll
+            for (int u = 0; u < NB; ++u) prod[u][0] = rows_allreduce(prod[u][0], HL);
+#pragma unroll
+        for (int u = 0; u < NB; ++u)
+#pragma unroll
+            for (int s = 0; s < HPQ; ++s) {
+                const float pre = sc[u][s] + erv[s];
+                const float al = __expf(lrelu02(pre) - mv[s]) * idn[s];
+                const float lp = pre > 0.f ? 1.f : GATMH_SLOPE;
+                t[s] = fmaf(al, prod[u][s], t[s]);
+                a1[s] = fmaf(al * prod[u][s], lp, a1[s]);
+                a2[s] = fmaf(al, lp, a2[s]);
+            }
+    }
+};
+
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_dst_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                             const float *elg, const float *er, const float *a_l, const float *m_in,
+                                                             const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
+                                                             uint32_t lds4) {
+    const RowsLane<GROUP, HPQ> L(a);
+    const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 *z4 = reinterpret_cast<const float4 *>(z), *zg4 = reinterpret_cast<const float4 *>(zg);
+    RowsDstState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
+        S.erv[s] = er[vk];
+        S.mv[s] = m_in[vk];
+        S.idn[s] = 1.f / den_in[vk];
+        S.t[s] = S.a1[s] = S.a2[s] = 0.f;
+    }
+    S.g = rows_mask(reinterpret_cast<const float4 *>(d_o)[(size_t)L.v * L.nchunk + L.col], L.cm);
+    // the row's entries: its in-edges, then the self edge (id v, a local row like any other); batches of four, the dead slots of the
+    // last batch gather the last entry's row again and are masked by a score of -inf (alpha = exp(-inf) = 0)
+    const uint64_t e0 = L.row_ok ? a.ptr[L.v] : 0, end = L.row_ok ? a.ptr[L.v + 1] : 0;
+    const uint64_t total = L.row_ok ? end - e0 + 1 : 0;
+    for (uint64_t done = 0; done < total; done += GROUP) {                     // GROUP == 64: wave-uniform
+        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+        const uint64_t ee = e0 + done + L.li;
+        const uint32_t my_idx = ee < end ? a.idx[ee] : L.v;
+        for (int j = 0; j < n; j += 4) {
+            float4 x[4];
+            float sc[4][HPQ];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                const bool loc = s < a.N;
+                const size_t r = loc ? s : s - a.N;
+                x[u] = (loc ? z4 : zg4)[r * L.nchunk + L.col];
+                if constexpr (!ELFLY) {
+                    const float *ep = (loc ? el : elg) + r * a.ldk;
+#pragma unroll
+                    for (int h = 0; h < HPQ; ++h) sc[u][h] = ep[L.hk[h]];
+                }
+            }
+            if constexpr (ELFLY)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) rows_el<HPQ>(x[u], al4, HL, sc[u]);
+#pragma unroll
+            for (int u = 1; u < 4; ++u)
+#pragma unroll
+                for (int h = 0; h < HPQ; ++h) sc[u][h] = j + u < n ? sc[u][h] : -INFINITY;
+            S.template step<4>(x, sc, HL);
+        }
+    }
+    if (!L.row_ok) return;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s)
+        if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+            const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
+            t_out[vk] = S.t[s];
+            der_out[vk] = S.a1[s] - S.t[s] * S.a2[s];
+            st4[(size_t)L.v * lds4 + L.hk[s]] = make_float4(S.erv[s], S.mv[s], S.idn[s], S.t[s]);
+        }
+}
+
+// ---- backward, source side: rows = sources u (out-edges), entries = destinations v (local: do / st, ghost: bg_do / bg_st) ---------
+template <int HPQ>
+struct RowsSrcState {
+    float elu[HPQ], T[HPQ], Tp[HPQ];
+    float4 S, Sp;
+    template <int NB>
+    __device__ __forceinline__ void step(const float4 (&x)[NB], const float4 (&rec)[NB][HPQ]) {
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            float al[HPQ], alp[HPQ];
+#pragma unroll
+            for (int s = 0; s < HPQ; ++s) {
+                const float4 r = rec[u][s];                       // (er, m, 1/den, t) of (v, k)
+                const float pre = elu[s] + r.x;
+                al[s] = __expf(lrelu02(pre) - r.y) * r.z;
+                alp[s] = pre > 0.f ? al[s] : 0.f;
+                T[s] = fmaf(al[s], r.w, T[s]);
+                Tp[s] = fmaf(alp[s], r.w, Tp[s]);
+            }
+            S = rows_axpy<HPQ>(al, x[u], S);
+            Sp = rows_axpy<HPQ>(alp, x[u], Sp);
+        }
+    }
+};
+
+// NB: destination rows in flight per group.  Four; the instantiations with four heads per lane (D == 1) keep two -- a batch holds
+// NB x HPQ statistics records of four registers each: 64 registers at NB = 4, 32 more than in the two-row form, which takes 111
+// in all -- past the 128 that leave four waves per SIMD (what a latency-bound gather lives on; tests/test_gatmh_row_gather_resources.py)
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
+                                                             const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                             const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                             float *dz) {
+    const RowsLane<GROUP, HPQ> L(a);
+    const float4 *d4 = reinterpret_cast<const float4 *>(d_o), *dg4 = reinterpret_cast<const float4 *>(dog);
+    RowsSrcState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        S.elu[s] = el[(size_t)L.v * a.ldk + L.hk[s]];
+        S.T[s] = S.Tp[s] = 0.f;
+    }
+    S.S = S.Sp = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the row's entries: its out-edges, then the self edge (id u); batches of NB, the dead slots of the last batch masked by a
+    // destination score of -inf (alpha = exp(-inf) = 0)
+    const uint64_t e0 = L.row_ok ? a.ptr[L.v] : 0, end = L.row_ok ? a.ptr[L.v + 1] : 0;
+    const uint64_t total = L.row_ok ? end - e0 + 1 : 0;
+    for (uint64_t done = 0; done < total; done += GROUP) {
+        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+        const uint64_t ee = e0 + done + L.li;
+        const uint32_t my_idx = ee < end ? a.idx[ee] : L.v;
+        for (int j = 0; j < n; j += NB) {
+            float4 x[NB], rec[NB][HPQ];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                const bool loc = s < a.N;
+                const size_t r = loc ? s : s - a.N;
+                x[u] = (loc ? d4 : dg4)[r * L.nchunk + L.col];
+                const float4 *sp = (loc ? st4 : stg) + r * lds4;
+#pragma unroll
+                for (int h = 0; h < HPQ; ++h) rec[u][h] = sp[L.hk[h]];
+            }
+#pragma unroll
+            for (int u = 1; u < NB; ++u)
+#pragma unroll
+                for (int h = 0; h < HPQ; ++h) rec[u][h].x = j + u < n ? rec[u][h].x : -INFINITY;
+            S.template step<NB>(x, rec);
+        }
+    }
+    if (!L.row_ok) return;
+    // del[u,k] = <Z[u,k,:], 0.2 S + 0.8 S+> - (0.2 T + 0.8 T+)
+    const float lo = GATMH_SLOPE, hi = 1.f - GATMH_SLOPE;
+    const float4 zz = rows_mask(reinterpret_cast<const float4 *>(z)[(size_t)L.v * L.nchunk + L.col], L.cm);
+    const float4 mix = make_float4(fmaf(hi, S.Sp.x, lo * S.S.x), fmaf(hi, S.Sp.y, lo * S.S.y), fmaf(hi, S.Sp.z, lo * S.S.z),
+                                   fmaf(hi, S.Sp.w, lo * S.S.w));
+    float dd[HPQ];
+    rows_dot<HPQ>(zz, mix, dd);
+    if constexpr (HPQ == 1) dd[0] = rows_allreduce(dd[0], HL);
+    if (!L.lane_ok) return;
+    const uint32_t KD = a.K * a.D;
+    float del[HPQ], dr[HPQ];
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        del[s] = dd[s] - (lo * S.T[s] + hi * S.Tp[s]);
+        dr[s] = der[(size_t)L.v * a.ldk + L.hk[s]];
+    }
+    float al4[4], ar4[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t f = min(4 * L.col + c, KD - 1);
+        al4[c] = a_l[f];
+        ar4[c] = a_r[f];
+    }
+    float4 out = S.S;
+    out = rows_axpy<HPQ>(del, make_float4(al4[0], al4[1], al4[2], al4[3]), out);
+    out = rows_axpy<HPQ>(dr, make_float4(ar4[0], ar4[1], ar4[2], ar4[3]), out);
+    reinterpret_cast<float4 *>(dz)[(size_t)L.v * L.nchunk + L.col] = rows_mask(out, L.cm);
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s)
+        if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) del_out[(size_t)L.v * a.ldk + L.hk[s]] = del[s];
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------------------------
+// lanes per row and heads per float4 of a shape; false: a shape the model does not allow (gatmh_shape_ok) or rows no float4 tiles
+static bool gatmh_rows_form(uint32_t K, uint32_t D, uint32_t ld, int *group, int *hpq, int *HL) {
+    if (!gatmh_shape_ok(K, D) || (ld & 3) || ld == 0 || ld > 256 || K * D > ld) return false;
+    const uint32_t nchunk = ld >> 2;
+    *group = nchunk <= 8 ? 8 : nchunk <= 16 ? 16 : nchunk <= 32 ? 32 : 64;
+    *hpq = (K == 1 || (D & 3) == 0) ? 1 : D == 2 ? 2 : 4;     // (K > 1: D is a power of two)
+    *HL = K == 1 ? *group : (D & 3) == 0 ? (int)(D >> 2) : 1;
+    return true;
+}
+bool gatmh_rows_ok(uint32_t K, uint32_t D, uint32_t ld) {
+    int g, h, hl;
+    return gatmh_rows_form(K, D, ld, &g, &h, &hl);
+}
+
+// F(group, hpq): the instantiations the launchers can select -- D == 2 means K*D <= 128 (K <= 64), D == 1 means K*D <= 64.
+// The forward and the destination side: F(group, hpq, elfly) -- scores from the gathered row wherever that gives the el tensor's
+// bits (rows_el): heads inside a lane, or a power-of-two float4 count
+static bool gatmh_rows_elfly(int hpq, uint32_t ld) { return hpq > 1 || ((ld >> 2) & ((ld >> 2) - 1)) == 0; }
+#define GATMH_ROWS_FORMS_EL(F)                                                                                                      \
+    do {                                                                                                                            \
+        if (hpq == 1 && elfly) { if (group == 8) F(8, 1, true); else if (group == 16) F(16, 1, true); else if (group == 32) F(32, 1, true); else F(64, 1, true); } \
+        else if (hpq == 1) { if (group == 32) F(32, 1, false); else F(64, 1, false); }                                               \
+        else if (hpq == 2) { if (group == 8) F(8, 2, true); else if (group == 16) F(16, 2, true); else F(32, 2, true); }             \
+        else { if (group == 8) F(8, 4, true); else F(16, 4, true); }                                                                \
+    } while (0)
+#define GATMH_ROWS_FORMS(F)                                                                                                         \
+    do {                                                                                                                            \
+        if (hpq == 1) { if (group == 8) F(8, 1); else if (group == 16) F(16, 1); else if (group == 32) F(32, 1); else F(64, 1); }   \
+        else if (hpq == 2) { if (group == 8) F(8, 2); else if (group == 16) F(16, 2); else F(32, 2); }                              \
+        else { if (group == 8) F(8, 4); else F(16, 4); }                                                                            \
+    } while (0)
+
+hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
+                                     const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
+                                     const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
+                                     hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    int group, hpq, HL;
+    if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    GatMhArgs a{N, K, D, ld, ldk, colptr, rowidx};
+    const uint32_t rpb = 4 * (64 / (uint32_t)group);
+    const dim3 gr((N + rpb - 1) / rpb), bl(256);
+    const bool elfly = gatmh_rows_elfly(hpq, ld);
+#define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_forward_kernel<G, H, E>), gr, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, o, op, m, den, dpos)
+    GATMH_ROWS_FORMS_EL(F);
+#undef F
+    return hipGetLastError();
+}
+
+hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
+                                 const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
+                                 const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
+                                 float4 *st4, uint32_t lds4, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    int group, hpq, HL;
+    if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    GatMhArgs a{N, K, D, ld, ldk, colptr, rowidx};
+    const uint32_t rpb = 4 * (64 / (uint32_t)group);
+    const dim3 gr((N + rpb - 1) / rpb), bl(256);
+    const bool elfly = gatmh_rows_elfly(hpq, ld);
+#define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_dst_kernel<G, H, E>), gr, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4)
+    GATMH_ROWS_FORMS_EL(F);
+#undef F
+    return hipGetLastError();
+}
+
+hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
+                                 const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
+                                 const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
+                                 float *del, float *dz, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    int group, hpq, HL;
+    if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    GatMhArgs a{N, K, D, ld, ldk, rowptr, colidx};
+    const uint32_t rpb = 4 * (64 / (uint32_t)group);
+    const dim3 gr((N + rpb - 1) / rpb), bl(256);
+#define F(G, H)                                                                                                                     \
+    hipLaunchKernelGGL((gatmh_rows_src_kernel<G, H, (H == 4 ? 2 : 4)>), gr, bl, 0, s, a, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, \
+                       a_r, del, dz)
+    GATMH_ROWS_FORMS(F);
+#undef F
+    return hipGetLastError();
+}
+#undef GATMH_ROWS_FORMS
+#undef GATMH_ROWS_FORMS_EL
+
+}  // namespace dory

@@ -84,7 +84,8 @@ int dory_configure(dory_ctx *ctx, int gnn_type, uint32_t num_layers,
  * one exchange (w = ld of do, or cols rounded up to 4 with halo_exact_rows) and, with dory_halo_fused_pack on and the sweep
  * forms running, the row-wise kernel that produces st writes the send rows itself.  Not taken (two exchanges as ever): the
  * scatter transport, a plan made with halo_direct_recv = 1, gatmh_bwd_phase = 1 / 2 (the caller's own transport).
- * Partitioned runs need the source-blocked kernels ("gatmh_blocked" = 1).
+ * Partitioned runs take the sweep forms, else the source-blocked kernels ("gatmh_blocked" = 1), else -- no layout, no partial
+ * buffer, a head shape neither covers -- the row-gather kernels with ghost rows (dory_gatmh_row_gather, below).
  * Sweep forms (option "gatmh_sweep" = 1, default; round 5): where the K1s layouts apply and a head spans 2..16 lanes of a
  * 16-byte-per-lane row slab, the forward runs on K1s's skeleton with a single-pass softmax against an upper-bound shift
  * ("m" then holds that shift, "den" the matching denominator: alpha = exp(s - m) / den as before) and leaves two more
@@ -540,6 +541,37 @@ int dory_gatmh_halo_bf16(dory_ctx *ctx, int on);     /* 0 (default) / 1 */
 int dory_gatmh_halo_bf16_stats(dory_ctx *ctx, uint64_t *fwd_bf16_exchanges, uint64_t *bwd_bf16_exchanges, uint64_t *bwd_bf16_rows,
                                uint64_t *producer_packed_bf16);
 int dory_gatmh_bwd_wire_do(dory_ctx *ctx, uint32_t layer, uint32_t *elem_bytes, uint32_t *elems);
+
+/* ---- the multi-head GAT's row-gather kernels with ghost rows (csrc/gat_mh_rows.hip; nothing in the reference) ----------------
+ * The sweep forms need a K1s layout (at most 512 source windows, N + ghosts < 2^24, 32-bit byte offsets into the gathered rows),
+ * the source-blocked forms a K1b layout (at most 256 blocks, D % 4 == 0 or one head) and a partial buffer of nb x N x (ld + 64)
+ * floats; the row-wise forms of round 1 read no ghost rows.  A partitioned dory_aggregate of a DORY_GATMH context that found none of
+ * them used to fail.  It now runs a fourth family, written as K1 is for GCN: one lane group of 8 / 16 / 32 / 64 lanes per row, one
+ * float4 per lane, a group's edge ids fetched with one coalesced load and broadcast, four gathered rows in flight, an id >= N
+ * selecting row id - N of the ghost tensor, 64-bit addressing, nothing of size E x K stored, no atomics (same input, same bits), no
+ * LDS and no wait between workgroups.  Any shape dory_preallocate accepts runs (32 heads x 2 and x 1 included).
+ *   forward            waits for the exchange in flight, then one pass over the in-edges with online rescaling (self edge last);
+ *                      writes "o", "m", "den" and "op" / "dpos" as the sweep forward does.  "m" holds the row's TRUE maximum per
+ *                      head, as with the blocked forms.
+ *   backward, phase 1  destination side: where this layer's forward left op / dpos and a head spans 2..16 lanes of a row slab (the
+ *                      shapes of the sweep forms) the row-wise kernel t = <do, o>, der = 0.8 (<do, op> - t dpos) -- no edges;
+ *                      every other shape an edge pass over the in-edges with ghost sources.  Both write "t", "der", "st".
+ *   exchange           do / st as ever (two exchanges, or one merged with dory_gatmh_bwd_merged_exchange: pack kernels, the
+ *                      producer-packed form does not apply); gatmh_bwd_phase 0 / 1 / 2 mean what they mean for the other forms.
+ *   backward, phase 2  source side over the out-edges, destinations local or ghost: del = <z, 0.2 S + 0.8 S+> - (0.2 T + 0.8 T+),
+ *                      dz with the finishing terms; the attention gradients' column sums follow unchanged.
+ * mode 0 (default): the family runs where a partitioned dory_aggregate of a DORY_GATMH context would otherwise be refused (no sweep
+ * layout, no blocked layout or partial buffer, a head shape neither covers); single partitions keep the row-wise forms.  mode 1: it
+ * runs in place of every other family, single partitions included (tests, measurement).  DORY_GCN / DORY_GAT contexts reject 1;
+ * other values and a call while an epoch graph is being recorded are DORY_ERR_ARG.  The family allocates nothing and waits for
+ * nothing on the host: a single-partition epoch in mode 1 can be recorded as an epoch graph like any other.
+ * NOT TAKEN: bf16 rows -- "gatmh_bf16_gather" >= 1 is still refused where the sweep forms do not run, mode 1 included, and the
+ * message says so; overlap of the interior rows with the forward exchange; hub splitting -- a row's edges are walked by its one lane
+ * group, however long the row.
+ * Counters: passes since dory_create, eager calls and recordings (not replays): forward, destination side as an edge pass,
+ * destination side as the row-wise kernel, source side; any pointer may be NULL. */
+int dory_gatmh_row_gather(dory_ctx *ctx, int mode);   /* 0 (default) / 1 */
+int dory_gatmh_row_gather_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *dst_rowwise, uint64_t *src);
 
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
