@@ -37,6 +37,7 @@ SYMBOLS = [
     "dory_gatmh_bwd_merged_exchange", "dory_gatmh_bwd_merged_exchange_stats", "dory_gatmh_bwd_wire_row", "dory_gatmh_bwd_pack",
     "dory_gatmh_bwd_unpack", "dory_gatmh_halo_bf16", "dory_gatmh_halo_bf16_stats", "dory_gatmh_bwd_wire_do",
     "dory_gatmh_row_gather", "dory_gatmh_row_gather_stats",
+    "dory_gatmh_row_gather_bf16", "dory_gatmh_row_gather_bf16_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -149,6 +150,8 @@ def load():
         "dory_gatmh_bwd_wire_do": [vp, u32, C.POINTER(u32), C.POINTER(u32)],
         "dory_gatmh_row_gather": [vp, i32],
         "dory_gatmh_row_gather_stats": [vp] + [C.POINTER(u64)] * 4,
+        "dory_gatmh_row_gather_bf16": [vp, i32],
+        "dory_gatmh_row_gather_bf16_stats": [vp] + [C.POINTER(u64)] * 3,
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -674,6 +677,17 @@ class Context:
         """(fwd, dst_edge_pass, dst_rowwise, src): the passes the row-gather family ran since dory_create, eager calls and recordings"""
         v = [C.c_uint64(0) for _ in range(4)]
         self._ck(self.lib.dory_gatmh_row_gather_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def gatmh_row_gather_bf16(self, on=1):
+        """option gatmh_bf16_gather reaches the row-gather family (dory_gatmh_row_gather_bf16): 0 (default) = refused there as ever,
+        1 = where the dispatch selects the family its bf16 forms run (8-byte gathers from the shadow rows, fp32 arithmetic)"""
+        self._ck(self.lib.dory_gatmh_row_gather_bf16(self.h, int(on)))
+
+    def gatmh_row_gather_bf16_stats(self):
+        """(fwd, dst_edge_pass, src): the passes of the row-gather family that ran a bf16 form since dory_create"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        self._ck(self.lib.dory_gatmh_row_gather_bf16_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
     # -- optimiser ---------------------------------------------------------------------------

@@ -269,7 +269,8 @@ bool halo_route(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **gho
 // bf16 rows under the settings of this moment -- GCN (fg / fgxw forward, bg / bgg backward): option gcn_bf16_gather >= 1 forward, == 2
 // backward; GAT prototype (fg_z, bg_d): dory_gat_bf16_gather's mode likewise; the multi-head GAT only with dory_gatmh_halo_bf16 on top:
 // then option gatmh_bf16_gather likewise (z -> fg_z forward; backward: the do of the sweep's own exchange -- with the option set its
-// sweeps gather fg_z / bg_do from rounded copies only, and the blocked forms that read them in fp32 are refused).  The same for every
+// sweeps, and with dory_gatmh_row_gather_bf16 the row-gather family, gather fg_z / bg_do from rounded copies only, and the blocked forms
+// that read them in fp32 are refused; the family's destination-side edge pass of a layer whose forward swept reads fg_z in fp32).  The same for every
 // layer of a model.  Reads atomics only: the peers of the local transport ask it of each other.
 bool halo_ships_bf16(const dory_ctx *c, int dir) {
     if (c->halo_bf16.load(std::memory_order_acquire) != 1) return false;

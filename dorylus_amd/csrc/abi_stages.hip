@@ -506,7 +506,8 @@ struct GatmhSweep {
 // The multi-head GAT extension: edge softmax + weighted sum.
 // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
 // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
-// Only the sweep forms have bf16 kernels: where the dispatch below would leave them the call is refused, never run in fp32
+// The sweep forms have bf16 kernels, and -- with dory_gatmh_row_gather_bf16 -- the row-gather family: where the dispatch below would
+// take any other form the call is refused, never run in fp32
 // opt-in "gatmh_bf16_wide" on top of it: where a pass runs on bf16 rows of 128 floats or more with several heads of 16 / 32 / 64
 // features, its gathers fetch eight features per lane (16 bytes) on 16-lane groups -- the narrow bf16 form's bits
 static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
@@ -517,6 +518,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
     const int64_t bfm = c->opt[OPT_GATMH_BF16_GATHER];
     if (c->N == 0) {   // a rank without vertices: no row to aggregate, whatever the forms and options -- its (empty) exchange is finished as by any consumer
         if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 0;
+        if (fl < c->gatmh_fwd_rows_bf16.size()) c->gatmh_fwd_rows_bf16[fl] = 0;
         return wait_halo(c);
     }
     {
@@ -539,7 +541,10 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
         const bool sweep = !rows_forced && c->opt[OPT_GATMH_SWEEP] && c->opt[OPT_SPMM_VARIANT] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
                            shl != 0 && op && dpos && sweep_supported(sa, Sf, gatmh_sweep_group(z->ld));
         const bool bf16 = bfm >= 1;
-        if (bf16 && !sweep)
+        // dory_gatmh_row_gather_bf16: where this call takes the row-gather family below, its bf16 form runs instead of the refusal
+        const bool rows_bf16 = bf16 && c->gatmh_row_gather_bf16 == 1 && !sweep && !blocked && (rows_forced || c->numNodes > 1);
+        if (c->gatmh_fwd_rows_bf16.size() < c->L) c->gatmh_fwd_rows_bf16.resize(c->L, 0);
+        if (bf16 && !sweep && !rows_bf16)
             return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
                         (long long)bfm,
                         rows_forced ? "dory_gatmh_row_gather = 1 (the row-gather kernels have no bf16 form)" :
@@ -548,6 +553,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                         !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
                         (!op || !dpos) ? "tensors op / dpos missing" : "the sweep layout of the in-edges does not apply to this graph");
         if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 0;
+        c->gatmh_fwd_rows_bf16[fl] = 0;   // (set by the row-gather family's bf16 form alone)
         if (sweep) {
             // K1s's skeleton: sums in registers over all source blocks, single-pass softmax against the upper-bound shift
             int rc = ensure_scratch(c, gatmh_sweep_scratch_bytes(Sf, c->N, z->ld, el->ld));
@@ -591,13 +597,20 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             // the row-gather family: the ghost rows have to have landed (overlapping the interior rows with the exchange: DESIGN.md 7)
             if (!op || !dpos || !gatmh_rows_ok(K, D, z->ld))
                 return fail(c, DORY_ERR_ARG, "multi-head GAT: the row-gather kernels need op / dpos and K*D <= ld <= 256 (K = %u, D = %u, ld = %u)", K, D, z->ld);
-            int rc = wait_halo(c);
-            if (rc) return rc;
-            HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, z->d, In.ghosts ? fgz->d : nullptr, el->d,
-                                               In.ghosts ? fgel->d : nullptr, er->d, c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d,
-                                               c->compute));
+            // bf16 form: z / fg_z from the shadow rows -- the local rows converted now, the ghost rows once their exchange has landed
+            Bf16Rows bf;
+            int rc = rows_bf16 ? bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather") : (int)DORY_OK;
+            if (rc || (rc = wait_halo(c)) || (rc = bf.ghosts_landed())) return rc;
+            HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
+                                               rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
+                                               c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16));
             if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
             c->gatmh_rows_fwd++;
+            if (rows_bf16) {
+                c->gatmh_fwd_rows_bf16[fl] = 1;
+                c->gatmh_bf16_gathers_fwd++;
+                c->gatmh_rows_bf16_fwd++;
+            }
         }
         else
             HIPCK(c, launch_gatmh_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, z->d, el->d, er->d,
@@ -711,10 +724,13 @@ static int gatmh_backward_blocked(dory_ctx *c, const GatmhBwd &T, const BlockedA
 // the row-gather family (gat_mh_rows.hip), in the two phases of the blocked form: the destination side over the in-edges (ghost
 // sources) -- the row-wise kernel on op / dpos where this layer's forward left them and it covers the shape (`rowwise`), else an edge
 // pass --, the exchange of do / st (pack kernels: nothing here writes send rows), the source side over the out-edges (ghost destinations)
-static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tensor *dpos, bool rowwise) {
+// dst_bf16 / src_bf16 (dory_gatmh_row_gather_bf16): the edge pass gathers z / fg_z, the source side do / bg_do, from the shadow rows
+// (the caller has reserved them); the ghost rows have landed where either is converted -- fg_z since the forward, bg_do after the exchange
+static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tensor *dpos, bool rowwise, bool dst_bf16, bool src_bf16) {
     Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
     const uint32_t K = T.K, D = T.D, ld = T.z->ld, ldk = T.el->ld, lds4 = T.st->ld / 4;
     float4 *st4 = reinterpret_cast<float4 *>(T.st->d);
+    int rc;
     if (!gatmh_rows_ok(K, D, ld))
         return fail(c, DORY_ERR_ARG, "multi-head GAT: the row-gather kernels need K*D <= ld <= 256 (K = %u, D = %u, ld = %u)", K, D, ld);
     if (T.phase != 2) {   // destination side: t, der, st
@@ -725,21 +741,31 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
             c->gatmh_rows_dst_rowwise++;
         } else {
             Timed t(c, "spmm", c->compute);
-            HIPCK(c, launch_gatmh_rows_dst(c->N, K, D, ld, ldk, In.ptr, In.idx, T.z->d, In.ghosts ? T.fgz->d : nullptr, T.el->d,
-                                           In.ghosts ? T.fgel->d : nullptr, T.er->d, c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d,
-                                           T.der->d, st4, lds4, c->compute));
+            Bf16Rows bf;
+            if (dst_bf16 && ((rc = bf.begin(c, *T.z, T.fgz, In.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
+            HIPCK(c, launch_gatmh_rows_dst(c->N, K, D, ld, ldk, In.ptr, In.idx, dst_bf16 ? bf.xl : T.z->d,
+                                           dst_bf16 ? bf.xg : (In.ghosts ? T.fgz->d : nullptr), T.el->d, In.ghosts ? T.fgel->d : nullptr, T.er->d,
+                                           c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, st4, lds4, c->compute, dst_bf16));
             c->gatmh_rows_dst_edge++;
+            if (dst_bf16) c->gatmh_rows_bf16_dst_edge++;
         }
     }
     if (T.phase == 1) return DORY_OK;
-    int rc = gatmh_backward_exchange(c, T);
-    if (rc) return rc;
+    if ((rc = gatmh_backward_exchange(c, T))) return rc;
     {
         Timed t(c, "spmm", c->compute);
-        HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, T.dO->d, Out.ghosts ? T.bgdo->d : nullptr, st4,
+        // (phase 0: the exchange above made the compute stream wait for bg_do; phase 2: the caller moved it before this call)
+        Bf16Rows bf;
+        if (src_bf16 && ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
+        HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
+                                       src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
                                        Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
-                                       c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute));
+                                       c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, src_bf16));
         c->gatmh_rows_src++;
+        if (src_bf16) {
+            c->gatmh_bf16_gathers_src++;
+            c->gatmh_rows_bf16_src++;
+        }
     }
     HIPCK(c, launch_gatmh_dattn(c->N, K, D, ld, ldk, T.z->d, T.del->d, T.der->d, c->wgrads[T.fl]["a_l"].d,
                                 c->wgrads[T.fl]["a_r"].d, c->scratch, c->scratch_bytes, c->compute));
@@ -778,7 +804,21 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     // the call would not take that sweep; the shadow buffer is sized here too (it cannot grow inside a recording)
     const bool bf16 = bfm >= 2;
     const bool rows_forced = c->gatmh_row_gather == 1;
-    if (bf16 && (rows_forced || !(dst_rowwise && src_sweep)))
+    const bool sweeps = !rows_forced && dst_rowwise && src_sweep;
+    const BlockedAdj &Bbi = gatmh_blocked_for(In, z->ld), &Bbo = gatmh_blocked_for(Out, z->ld);
+    const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
+    const bool blocked = !rows_forced && !sweeps && c->opt[OPT_GATMH_BLOCKED] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na &&
+                         nbmax > 0 && gatmh_backward_blocked_ok(K, D, z->ld) &&
+                         (size_t)nbmax * c->N * (z->ld + K) * sizeof(float) <= c->partial_bytes;
+    // the row-gather family (op / dpos are current whichever family's forward left them; gatmh_sweep is not asked), and what of it
+    // runs on bf16 rows with dory_gatmh_row_gather_bf16: the source side by the option; the destination side's edge pass where this
+    // layer's forward ran the family's bf16 form -- its scores have to be the forward's scores
+    const bool rows = !sweeps && !blocked && (rows_forced || c->numNodes > 1);
+    const bool rows_dst_rowwise = shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] && ((z->ld >> 2) % (uint32_t)shl) == 0;
+    const bool rows_bf16 = rows && c->gatmh_row_gather_bf16 == 1;
+    const bool rows_src_bf16 = rows_bf16 && bf16;
+    const bool rows_dst_bf16 = rows_bf16 && !rows_dst_rowwise && fl < c->gatmh_fwd_rows_bf16.size() && c->gatmh_fwd_rows_bf16[fl];
+    if (bf16 && !sweeps && !rows_src_bf16)
         return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = 2 needs the sweep forms of the backward pass, which this call would not take: %s",
                     rows_forced ? "dory_gatmh_row_gather = 1 (the row-gather kernels have no bf16 form)" :
                     !c->opt[OPT_GATMH_SWEEP] ? "gatmh_sweep = 0" :
@@ -787,6 +827,7 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
                     !dst_rowwise ? "this layer's forward pass did not run the sweep form" : "the sweep layout of the out-edges does not apply to this graph");
     int rc;
     if (bf16 && T.phase != 1 && (rc = bf16_reserve(c, (uint64_t)c->N + Out.ghosts, z->ld, "gatmh_bf16_gather"))) return rc;
+    if (rows_dst_bf16 && T.phase != 2 && (rc = bf16_reserve(c, (uint64_t)c->N + In.ghosts, z->ld, "gatmh_bf16_gather"))) return rc;
     if (T.phase != 2) {
         Timed t(c, "loss", c->compute);
         if (fl == c->L - 1) {
@@ -798,16 +839,9 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
         }
     }
     if ((rc = ensure_scratch(c, (size_t)2048 * z->cols * sizeof(float) + (size_t)c->N * K * 16 + 256))) return rc;
-    if (!rows_forced && dst_rowwise && src_sweep) return gatmh_backward_sweep(c, T, op, dpos, shl, sa, bf16);
-    const BlockedAdj &Bbi = gatmh_blocked_for(In, z->ld), &Bbo = gatmh_blocked_for(Out, z->ld);
-    const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
-    if (!rows_forced && c->opt[OPT_GATMH_BLOCKED] && In.blk.built && Out.blk.built && !In.blk.na && !Out.blk.na && nbmax > 0 &&
-        gatmh_backward_blocked_ok(K, D, z->ld) &&
-        (size_t)nbmax * c->N * (z->ld + K) * sizeof(float) <= c->partial_bytes)
-        return gatmh_backward_blocked(c, T, Bbi, Bbo);
-    if (rows_forced || c->numNodes > 1)   // (op / dpos are current whichever family's forward left them; gatmh_sweep is not asked)
-        return gatmh_backward_rows(c, T, op, dpos, shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] &&
-                                                   ((z->ld >> 2) % (uint32_t)shl) == 0);
+    if (sweeps) return gatmh_backward_sweep(c, T, op, dpos, shl, sa, bf16);
+    if (blocked) return gatmh_backward_blocked(c, T, Bbi, Bbo);
+    if (rows) return gatmh_backward_rows(c, T, op, dpos, rows_dst_rowwise, rows_dst_bf16, rows_src_bf16);
     Timed t(c, "spmm", c->compute);
     HIPCK(c, launch_gatmh_backward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Out.ptr, Out.idx, z->d, el->d,
                                    er->d, m->d, den->d, dO->d, c->weights[fl]["a_l"].d, c->weights[fl]["a_r"].d,
@@ -948,6 +982,25 @@ int dory_gatmh_row_gather_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_p
     if (dst_edge_pass) *dst_edge_pass = c->gatmh_rows_dst_edge;
     if (dst_rowwise) *dst_rowwise = c->gatmh_rows_dst_rowwise;
     if (src) *src = c->gatmh_rows_src;
+    return DORY_OK;
+}
+
+// ---- dory_gatmh_row_gather_bf16: option gatmh_bf16_gather reaches the row-gather family (its bf16 forms), and the passes that ran one ----
+int dory_gatmh_row_gather_bf16(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16: on is 0 or 1");
+    if (on == 1 && (!c->configured || c->gnn != DORY_GATMH))
+        return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16: on = 1 needs a context configured as DORY_GATMH");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16: not while an epoch graph is being recorded");
+    c->gatmh_row_gather_bf16 = on;
+    return DORY_OK;
+}
+
+int dory_gatmh_row_gather_bf16_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src) {
+    CHECK_CTX(c);
+    if (fwd) *fwd = c->gatmh_rows_bf16_fwd;
+    if (dst_edge_pass) *dst_edge_pass = c->gatmh_rows_bf16_dst_edge;
+    if (src) *src = c->gatmh_rows_bf16_src;
     return DORY_OK;
 }
 

@@ -289,6 +289,12 @@ struct dory_ctx {
     // as the row-wise kernel on op and dpos, source side
     int gatmh_row_gather = 0;
     uint64_t gatmh_rows_fwd = 0, gatmh_rows_dst_edge = 0, gatmh_rows_dst_rowwise = 0, gatmh_rows_src = 0;
+    // dory_gatmh_row_gather_bf16: 1 = where the dispatch selects the row-gather family, option gatmh_bf16_gather runs its bf16 forms
+    // (8-byte gathers from the shadow rows) instead of being refused; per layer: this layer's forward ran the family's bf16 form (its
+    // m / den are statistics of rounded rows: the destination-side edge pass has to gather the same); the passes that ran a bf16 form
+    int gatmh_row_gather_bf16 = 0;
+    std::vector<char> gatmh_fwd_rows_bf16;
+    uint64_t gatmh_rows_bf16_fwd = 0, gatmh_rows_bf16_dst_edge = 0, gatmh_rows_bf16_src = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -723,15 +729,15 @@ bool gatmh_rows_ok(uint32_t K, uint32_t D, uint32_t ld);
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
-                                     hipStream_t s);
+                                     hipStream_t s, bool bf16 = false /* z / zg: their shadow rows (launch_bf16_rows) */);
 hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                  const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
-                                 float4 *st4, uint32_t lds4, hipStream_t s);
+                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16 = false /* z / zg: their shadow rows */);
 hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
-                                 float *del, float *dz, hipStream_t s);
+                                 float *del, float *dz, hipStream_t s, bool bf16 = false /* d_o / dog: their shadow rows */);
 // row-wise backward (single partition; feature-per-lane or (edge, head, piece)-per-lane kernels by shape)
 hipError_t launch_gatmh_backward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const uint64_t *rowptr, const uint32_t *colidx,

@@ -30,7 +30,16 @@
 //     del = <Z_u, 0.2 S + 0.8 S+> - (0.2 T + 0.8 T+),   dz = S + del a_l + der a_r      (sums of gatmh_src_finish_body)
 // one reduction per row instead of one per edge.
 //
-// Not taken here: bf16 rows (gatmh_bf16_gather stays with the sweep forms), overlap of the interior rows with the exchange, and
+// bf16 rows (dory_gatmh_row_gather_bf16 + option gatmh_bf16_gather; gatmh_rows_{forward,dst,src}_bf16_kernel): the family is bound by
+// HBM bytes, and a gathered row chunk becomes ONE 8-byte load of four bf16 from the context's shadow rows, widened exactly
+// (row_chunk) -- a 64-float row is one 128-byte line read by 16 lanes.  Geometry, rows in flight, ghost addressing and every fp32
+// operation after the load are the fp32 kernels': each pass is one __device__ body over the chunk type, so a bf16 kernel gives its
+// sibling's bits on rows rounded beforehand.  The forward and the edge pass gather z / fg_z (scores from the ROUNDED row where ELFLY
+// holds; el / fg_el from the tensors elsewhere), the source side do / bg_do; records, el[u], the closing z[u], der, a_l, a_r stay
+// fp32.  Known consequence: with ELFLY the forward's m / den come from scores of rounded rows while the source side takes el[u]
+// from the fp32 tensor -- its alpha differs from the forward's by the rounding of a score (include/dorylus_hip.h).
+//
+// Not taken here: a wide (16-byte) bf16 form, overlap of the interior rows with the exchange, and
 // HUB SPLITTING -- a row's edges are walked by its one lane group; cutting hub rows into chunks with merged (m, den, acc) states
 // matters for power-law partitions too large for the layouts and is left out.
 #include "gat_mh.hpp"
@@ -167,13 +176,15 @@ struct RowsFwdState {
     }
 };
 
-template <int GROUP, int HPQ, bool ELFLY>
-__global__ __launch_bounds__(256) void gatmh_rows_forward_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
-                                                                 const float *elg, const float *er, const float *a_l, float *o, float *op,
-                                                                 float *m_out, float *den_out, float *dpos_out) {
+// CHUNK: what a lane gathers of a row -- float4 (fp32 rows), or uint2 (four bf16 of the shadow rows, launch_bf16_rows, widened
+// exactly by row_chunk).  Everything after the load is the same arithmetic in the same order, so a bf16 kernel gives its fp32
+// sibling's bits on rows that were rounded beforehand; the bodies below are shared by both, the __global__ kernels only name them.
+template <int GROUP, int HPQ, bool ELFLY, class CHUNK>
+__device__ __forceinline__ void gatmh_rows_forward_body(const GatMhArgs &a, int HL, const CHUNK *z4, const CHUNK *zg4, const float *el,
+                                                        const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                        float *m_out, float *den_out, float *dpos_out) {
     const RowsLane<GROUP, HPQ> L(a);
     const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 *z4 = reinterpret_cast<const float4 *>(z), *zg4 = reinterpret_cast<const float4 *>(zg);
     RowsFwdState<HPQ> S;
 #pragma unroll
     for (int s = 0; s < HPQ; ++s) {
@@ -198,7 +209,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_forward_kernel(GatMhArgs a, in
                 const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
                 const bool loc = s < a.N;
                 const size_t r = loc ? s : s - a.N;
-                x[u] = (loc ? z4 : zg4)[r * L.nchunk + L.col];
+                x[u] = row_chunk((loc ? z4 : zg4)[r * L.nchunk + L.col]);
                 if constexpr (!ELFLY) {
                     const float *ep = (loc ? el : elg) + r * a.ldk;
 #pragma unroll
@@ -232,6 +243,22 @@ __global__ __launch_bounds__(256) void gatmh_rows_forward_kernel(GatMhArgs a, in
             dpos_out[vk] = S.denp[s] * idn[s];
         }
 }
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                                 const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                                 float *m_out, float *den_out, float *dpos_out) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
+                                               a_l, o, op, m_out, den_out, dpos_out);
+}
+// zb / zgb: the shadow rows of z / fg_z (ld bf16 per row, one 8-byte load per lane and edge: a 64-float row is one 128-byte line).
+// Where ELFLY holds the sources' scores come from the gathered, rounded row -- what the sibling does when handed rounded rows;
+// elsewhere el / elg are gathered from the fp32 tensors as before
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
+                                                                      const float *elg, const float *er, const float *a_l, float *o,
+                                                                      float *op, float *m_out, float *den_out, float *dpos_out) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out);
+}
 
 // ---- backward, destination side: t[v,k] = sum a*da, der[v,k] = sum a*da*l' - t * sum a*l', st = (er, m, 1/den, t) -------------------
 template <int HPQ>
@@ -260,14 +287,13 @@ struct RowsDstState {
     }
 };
 
-template <int GROUP, int HPQ, bool ELFLY>
-__global__ __launch_bounds__(256) void gatmh_rows_dst_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
-                                                             const float *elg, const float *er, const float *a_l, const float *m_in,
-                                                             const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
-                                                             uint32_t lds4) {
+template <int GROUP, int HPQ, bool ELFLY, class CHUNK>
+__device__ __forceinline__ void gatmh_rows_dst_body(const GatMhArgs &a, int HL, const CHUNK *z4, const CHUNK *zg4, const float *el,
+                                                    const float *elg, const float *er, const float *a_l, const float *m_in,
+                                                    const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
+                                                    uint32_t lds4) {
     const RowsLane<GROUP, HPQ> L(a);
     const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 *z4 = reinterpret_cast<const float4 *>(z), *zg4 = reinterpret_cast<const float4 *>(zg);
     RowsDstState<HPQ> S;
 #pragma unroll
     for (int s = 0; s < HPQ; ++s) {
@@ -294,7 +320,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_kernel(GatMhArgs a, int HL
                 const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
                 const bool loc = s < a.N;
                 const size_t r = loc ? s : s - a.N;
-                x[u] = (loc ? z4 : zg4)[r * L.nchunk + L.col];
+                x[u] = row_chunk((loc ? z4 : zg4)[r * L.nchunk + L.col]);
                 if constexpr (!ELFLY) {
                     const float *ep = (loc ? el : elg) + r * a.ldk;
 #pragma unroll
@@ -320,6 +346,23 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_kernel(GatMhArgs a, int HL
             der_out[vk] = S.a1[s] - S.t[s] * S.a2[s];
             st4[(size_t)L.v * lds4 + L.hk[s]] = make_float4(S.erv[s], S.mv[s], S.idn[s], S.t[s]);
         }
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_dst_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                             const float *elg, const float *er, const float *a_l, const float *m_in,
+                                                             const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
+                                                             uint32_t lds4) {
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
+                                           m_in, den_in, d_o, t_out, der_out, st4, lds4);
+}
+// the edge pass of a layer whose forward ran gatmh_rows_forward_bf16_kernel: the same rounded rows, hence the forward's scores
+// (m / den are statistics of those); d_o, m, den and er stay fp32
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_dst_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
+                                                                  const float *elg, const float *er, const float *a_l, const float *m_in,
+                                                                  const float *den_in, const float *d_o, float *t_out, float *der_out,
+                                                                  float4 *st4, uint32_t lds4) {
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4);
 }
 
 // ---- backward, source side: rows = sources u (out-edges), entries = destinations v (local: do / st, ghost: bg_do / bg_st) ---------
@@ -350,13 +393,11 @@ struct RowsSrcState {
 // NB: destination rows in flight per group.  Four; the instantiations with four heads per lane (D == 1) keep two -- a batch holds
 // NB x HPQ statistics records of four registers each: 64 registers at NB = 4, 32 more than in the two-row form, which takes 111
 // in all -- past the 128 that leave four waves per SIMD (what a latency-bound gather lives on; tests/test_gatmh_row_gather_resources.py)
-template <int GROUP, int HPQ, int NB>
-__global__ __launch_bounds__(256) void gatmh_rows_src_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
-                                                             const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
-                                                             const float *der, const float *a_l, const float *a_r, float *del_out,
-                                                             float *dz) {
+template <int GROUP, int HPQ, int NB, class CHUNK>
+__device__ __forceinline__ void gatmh_rows_src_body(const GatMhArgs &a, int HL, const float *z, const float *el, const CHUNK *d4,
+                                                    const CHUNK *dg4, const float4 *st4, const float4 *stg, uint32_t lds4, const float *der,
+                                                    const float *a_l, const float *a_r, float *del_out, float *dz) {
     const RowsLane<GROUP, HPQ> L(a);
-    const float4 *d4 = reinterpret_cast<const float4 *>(d_o), *dg4 = reinterpret_cast<const float4 *>(dog);
     RowsSrcState<HPQ> S;
 #pragma unroll
     for (int s = 0; s < HPQ; ++s) {
@@ -379,7 +420,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_kernel(GatMhArgs a, int HL
                 const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
                 const bool loc = s < a.N;
                 const size_t r = loc ? s : s - a.N;
-                x[u] = (loc ? d4 : dg4)[r * L.nchunk + L.col];
+                x[u] = row_chunk((loc ? d4 : dg4)[r * L.nchunk + L.col]);
                 const float4 *sp = (loc ? st4 : stg) + r * lds4;
 #pragma unroll
                 for (int h = 0; h < HPQ; ++h) rec[u][h] = sp[L.hk[h]];
@@ -423,6 +464,23 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_kernel(GatMhArgs a, int HL
     for (int s = 0; s < HPQ; ++s)
         if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) del_out[(size_t)L.v * a.ldk + L.hk[s]] = del[s];
 }
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
+                                                             const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                             const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                             float *dz) {
+    gatmh_rows_src_body<GROUP, HPQ, NB>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
+                                        lds4, der, a_l, a_r, del_out, dz);
+}
+// dob / dogb: the shadow rows of do / bg_do (gatmh_bf16_gather = 2).  The 16-byte records, the row's own el[u], the closing z[u]
+// row, der, a_l and a_r stay fp32
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_bf16_kernel(GatMhArgs a, int HL, const float *z, const float *el, const uint2 *dob,
+                                                                  const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                  const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                  float *dz) {
+    gatmh_rows_src_body<GROUP, HPQ, NB>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz);
+}
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
 // lanes per row and heads per float4 of a shape; false: a shape the model does not allow (gatmh_shape_ok) or rows no float4 tiles
@@ -460,7 +518,7 @@ static bool gatmh_rows_elfly(int hpq, uint32_t ld) { return hpq > 1 || ((ld >> 2
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
-                                     hipStream_t s) {
+                                     hipStream_t s, bool bf16) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
@@ -468,6 +526,13 @@ hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     const bool elfly = gatmh_rows_elfly(hpq, ld);
+    if (bf16) {   // z / zg: the shadow rows
+        const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
+#define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_forward_bf16_kernel<G, H, E>), gr, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos)
+        GATMH_ROWS_FORMS_EL(F);
+#undef F
+        return hipGetLastError();
+    }
 #define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_forward_kernel<G, H, E>), gr, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, o, op, m, den, dpos)
     GATMH_ROWS_FORMS_EL(F);
 #undef F
@@ -477,7 +542,7 @@ hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_
 hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                  const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
-                                 float4 *st4, uint32_t lds4, hipStream_t s) {
+                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
@@ -485,6 +550,13 @@ hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     const bool elfly = gatmh_rows_elfly(hpq, ld);
+    if (bf16) {   // z / zg: the shadow rows
+        const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
+#define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_dst_bf16_kernel<G, H, E>), gr, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4)
+        GATMH_ROWS_FORMS_EL(F);
+#undef F
+        return hipGetLastError();
+    }
 #define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_dst_kernel<G, H, E>), gr, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4)
     GATMH_ROWS_FORMS_EL(F);
 #undef F
@@ -494,13 +566,22 @@ hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
 hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
-                                 float *del, float *dz, hipStream_t s) {
+                                 float *del, float *dz, hipStream_t s, bool bf16) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
     GatMhArgs a{N, K, D, ld, ldk, rowptr, colidx};
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
+    if (bf16) {   // d_o / dog: the shadow rows
+        const uint2 *dob = reinterpret_cast<const uint2 *>(d_o), *dogb = reinterpret_cast<const uint2 *>(dog);
+#define F(G, H)                                                                                                                     \
+    hipLaunchKernelGGL((gatmh_rows_src_bf16_kernel<G, H, (H == 4 ? 2 : 4)>), gr, bl, 0, s, a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, \
+                       a_r, del, dz)
+        GATMH_ROWS_FORMS(F);
+#undef F
+        return hipGetLastError();
+    }
 #define F(G, H)                                                                                                                     \
     hipLaunchKernelGGL((gatmh_rows_src_kernel<G, H, (H == 4 ? 2 : 4)>), gr, bl, 0, s, a, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, \
                        a_r, del, dz)

@@ -565,13 +565,52 @@ int dory_gatmh_bwd_wire_do(dory_ctx *ctx, uint32_t layer, uint32_t *elem_bytes, 
  * runs in place of every other family, single partitions included (tests, measurement).  DORY_GCN / DORY_GAT contexts reject 1;
  * other values and a call while an epoch graph is being recorded are DORY_ERR_ARG.  The family allocates nothing and waits for
  * nothing on the host: a single-partition epoch in mode 1 can be recorded as an epoch graph like any other.
- * NOT TAKEN: bf16 rows -- "gatmh_bf16_gather" >= 1 is still refused where the sweep forms do not run, mode 1 included, and the
- * message says so; overlap of the interior rows with the forward exchange; hub splitting -- a row's edges are walked by its one lane
+ * bf16 rows: "gatmh_bf16_gather" >= 1 is refused where the sweep forms do not run, mode 1 included, and the message says so --
+ * unless dory_gatmh_row_gather_bf16 (below) is on, which gives this family bf16 forms of its three edge passes.
+ * NOT TAKEN: overlap of the interior rows with the forward exchange; hub splitting -- a row's edges are walked by its one lane
  * group, however long the row.
  * Counters: passes since dory_create, eager calls and recordings (not replays): forward, destination side as an edge pass,
  * destination side as the row-wise kernel, source side; any pointer may be NULL. */
 int dory_gatmh_row_gather(dory_ctx *ctx, int mode);   /* 0 (default) / 1 */
 int dory_gatmh_row_gather_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *dst_rowwise, uint64_t *src);
+
+/* ---- bf16 row gathers for the row-gather kernels (opt-in, default off; nothing in the reference) --------------------------------
+ * The family above is the one form of the model that waits on HBM bytes: a 64-float row is 256 bytes gathered once per edge.  With
+ * on = 1, wherever dory_aggregate selects that family (mode 1, or mode 0's fall-back on a partitioned call) option
+ * "gatmh_bf16_gather" runs its bf16 forms instead of being refused: the gathered row chunk is ONE 8-byte load of four bf16 from the
+ * context's shadow rows (rounded to nearest even by a conversion kernel, as for the sweep forms; a 64-float row is then one 128-byte
+ * line), widened exactly; lane geometry, rows in flight, ghost addressing and every fp32 operation after the load are the fp32
+ * kernels', in their order (one shared body per pass).  CONTRACT: a bf16 pass equals, bit for bit, the fp32 pass run on rows that
+ * were rounded to bf16 beforehand.
+ *   forward ("gatmh_bf16_gather" >= 1)   gathers z / fg_z from the shadow rows (local rows converted at once, ghost rows after the
+ *                      exchange has landed).  Where the scores come from the gathered row (every shape but rows of 96, 160, 192, 224
+ *                      floats, which gather "el" / "fg_el" as before) they are scores of the ROUNDED row.
+ *   backward, phase 1  the row-wise kernel runs where it ran (it reads no rows).  The edge pass gathers bf16 rows iff this layer's
+ *                      forward ran the family's bf16 form (a per-layer flag, cleared by every other forward form): its scores must be
+ *                      the forward's.  Otherwise -- a forward that swept, the switch turned off since -- it runs in fp32.
+ *   backward, phase 2 ("gatmh_bf16_gather" = 2)   gathers do / bg_do from the shadow rows, converted after the do / st exchange has
+ *                      landed (at once under gatmh_bwd_phase = 2); the 16-byte records, el[u], z[u], der, a_l, a_r stay fp32.
+ * The shadow rows are reserved before anything is launched and never grow inside a recording (DORY_ERR_ARG there: run one eager epoch
+ * first).  Calls that would take the blocked family or the single-partition row-wise kernels are refused with the option set as
+ * before, with the messages as before; with on = 0 nothing changes anywhere.  DORY_GCN / DORY_GAT contexts reject 1; other values
+ * and a call while an epoch graph is being recorded are DORY_ERR_ARG.
+ * The bf16 wire: halo_ships_bf16 reads switches and the option only, so dory_halo_bf16_rows + dory_gatmh_halo_bf16 now reach these
+ * ranks (z forward, do backward); rounding is idempotent, so a rank's tensors are the same bits with the wire on and off wherever
+ * no kernel of the family reads fg_el (dory_apply_edge's fg_el is formed from the rounded fg_z: documented above).
+ * KNOWN CONSEQUENCE: where the forward's scores come from the gathered row, "m" / "den" are statistics of scores of ROUNDED rows,
+ * while the source side forms its alpha from the fp32 "el" tensor: the backward's alpha differs from the forward's by the rounding
+ * of a score, relative 2^-9 of a dot product's terms.  The sweep forms do not have this difference (they take scores from the
+ * table).  Forming el[u] from the rounded z[u] in the source kernel would remove it; not done here.  Measured on one epoch it
+ * does not show above the rounding of the rows: the family deviates from its fp32 run as the sweep forms do from theirs.
+ * MEASURED (one MI355X, rank 0 of 8 of the Amazon-size graph, 3.2 edges per converted row, against the parent's library;
+ * profiles/r26_gatmh_row_gather_bf16.txt): the kernels alone take x0.57-0.63 of their fp32 siblings' time on the forward and the edge
+ * pass at 64 / 128 floats, x0.73-0.87 on the source side, x0.90 at 32 floats; WITH the conversion into the shadow rows NO pass is
+ * faster (x1.00-1.13 at 64 / 128 floats, x1.15-1.44 at 32; epochs 18.6-18.9 -> 19.7-19.9 ms).  This switch is not a speed-up
+ * until the rows arrive as bf16 and stay (ghost twins for this model) or a partition has clearly more than 3 edges per row.
+ * Counters: passes that ran a bf16 form (forward, destination-side edge pass, source side); the read-only options
+ * "gatmh_bf16_gathers_fwd" / "_src" and dory_gatmh_row_gather_stats count those passes too.  Any pointer may be NULL. */
+int dory_gatmh_row_gather_bf16(dory_ctx *ctx, int on);   /* 0 (default) / 1 */
+int dory_gatmh_row_gather_bf16_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src);
 
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
