@@ -38,6 +38,7 @@ SYMBOLS = [
     "dory_gatmh_bwd_unpack", "dory_gatmh_halo_bf16", "dory_gatmh_halo_bf16_stats", "dory_gatmh_bwd_wire_do",
     "dory_gatmh_row_gather", "dory_gatmh_row_gather_stats",
     "dory_gatmh_row_gather_bf16", "dory_gatmh_row_gather_bf16_stats",
+    "dory_gatmh_bf16_ghosts", "dory_gatmh_bf16_ghosts_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -152,6 +153,8 @@ def load():
         "dory_gatmh_row_gather_stats": [vp] + [C.POINTER(u64)] * 4,
         "dory_gatmh_row_gather_bf16": [vp, i32],
         "dory_gatmh_row_gather_bf16_stats": [vp] + [C.POINTER(u64)] * 3,
+        "dory_gatmh_bf16_ghosts": [vp, i32],
+        "dory_gatmh_bf16_ghosts_stats": [vp] + [C.POINTER(u64)] * 7,
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
@@ -187,8 +190,9 @@ def load():
                 or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
                 or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")
                 or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")
-                or name.startswith("dory_gatmh_bwd_") or name.startswith("dory_gatmh_halo_bf16") or name.startswith("dory_gatmh_row_gather")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange / its bf16 halo rows / its row-gather kernels)
+                or name.startswith("dory_gatmh_bwd_") or name.startswith("dory_gatmh_halo_bf16") or name.startswith("dory_gatmh_row_gather")
+                or name.startswith("dory_gatmh_bf16_ghosts")) and not hasattr(lib, name):
+            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange / its bf16 halo rows / its row-gather kernels / its bf16 ghost twins)
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -689,6 +693,23 @@ class Context:
         v = [C.c_uint64(0) for _ in range(3)]
         self._ck(self.lib.dory_gatmh_row_gather_bf16_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    GATMH_BF16_GHOSTS_STATS = ("fwd_kept", "bwd_kept", "bwd_kept_merged", "twin_reads_rows", "twin_reads_sweep", "scores_from_twin", "widened")
+
+    def gatmh_bf16_ghosts(self, on=True):
+        """fg_z and bg_do of the multi-head GAT get bf16 twins too (dory_gatmh_bf16_ghosts; opt-in on top of halo_bf16_ghosts, after
+        preallocate): rows that travel as bf16 (halo_bf16_rows + gatmh_halo_bf16 + option gatmh_bf16_gather) stay bf16 where the bf16
+        edge passes gather them; dory_apply_edge forms fg_el / fg_er from the twin"""
+        self._ck(self.lib.dory_gatmh_bf16_ghosts(self.h, int(on)))
+
+    def gatmh_bf16_ghosts_stats(self):
+        """dict of the eager calls since dory_create: fwd_kept / bwd_kept / bwd_kept_merged (exchanges and unpacks whose rows stayed in
+        fg_z's / bg_do's twin, bg_do's through a merged row), twin_reads_rows / twin_reads_sweep (bf16 passes of the row-gather family /
+        the sweep forms that read a twin instead of converting ghost rows), scores_from_twin (dory_apply_edge), widened (for a reader
+        of fp32 rows)"""
+        v = [C.c_uint64(0) for _ in range(7)]
+        self._ck(self.lib.dory_gatmh_bf16_ghosts_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(self.GATMH_BF16_GHOSTS_STATS, (int(x.value) for x in v)))
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

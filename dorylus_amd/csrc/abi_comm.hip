@@ -196,10 +196,12 @@ int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloP
 // the padding held before
 // dory_halo_bf16_ghosts (`twin` not null: the rows are bf16 and stay bf16): the keep form copies them into the twin's rows instead,
 // zeros in [w, ld); `ghost` is not touched
-// merged rows (wire.w2): whole rows of both ghost tensors, ghost2 at stride ld2 behind the first
+// merged rows (wire.w2): whole rows of both ghost tensors, ghost2 at stride ld2 behind the first (`twin`: the first part into the twin's rows)
 int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const float *buf, const HaloPlan &p, hipStream_t s, uint16_t *twin = nullptr,
                 float *ghost2 = nullptr, uint32_t ld2 = 0) {
-    if (wire.w2 && wire.bf16) {
+    if (wire.w2 && wire.bf16 && twin) {   // (dory_gatmh_bf16_ghosts: the do part stays bf16 in bg_do's twin, st as below)
+        HIPCK(c, launch_scatter_rows_pair_bf16_keep(twin, ld, wire.w, ghost2, ld2, wire.w2, buf, p.d_unpack_slots, p.recv_total, s));
+    } else if (wire.w2 && wire.bf16) {
         HIPCK(c, launch_scatter_rows_pair_bf16(ghost, ld, wire.w, ghost2, ld2, wire.w2, buf, p.d_unpack_slots, p.recv_total, s));
     } else if (wire.w2) {
         HIPCK(c, launch_scatter_rows_pair(ghost, ld, wire.w, ghost2, ld2, wire.w2, buf, p.d_unpack_slots, p.recv_total, s));
@@ -220,9 +222,11 @@ int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const floa
 // counted (eager calls) as landed in the twin itself or copied there by the keep kernel; state TWIN, or, where the tensor's raw
 // pointer is out (the caller reads fp32 rows behind the library's back), widened at once behind them on s (widen_now; the deferred
 // half of the local transport does it itself, LocalPending::widen_to) and BOTH
-int ghost_rows_landed(dory_ctx *c, Tensor *ghost, bool keep, bool direct, hipStream_t s, bool widen_now) {
+// (dory_gatmh_bf16_ghosts_stats: `dir` and `merged` say which of the multi-head GAT's tensors it is -- fg_z, bg_do alone, bg_do of a merged row)
+int ghost_rows_landed(dory_ctx *c, Tensor *ghost, bool keep, bool direct, hipStream_t s, bool widen_now, int dir, bool merged = false) {
     if (!keep) { ghost_wrote_fp32(ghost); return DORY_OK; }
     if (!c->capturing) (direct ? c->ghost_landed_direct : c->ghost_landed_by_kernel) += 1;
+    if (!c->capturing && c->gnn == DORY_GATMH) (dir == DORY_FORWARD ? c->gatmh_twin_fwd : merged ? c->gatmh_twin_bwd_merged : c->gatmh_twin_bwd) += 1;
     ghost->twin_state = ghost->raw_handed ? DORY_GHOST_BOTH : DORY_GHOST_TWIN;
     if (ghost->raw_handed && widen_now) HIPCK(c, launch_widen_rows_bf16(ghost->d, ghost->twin, ghost->rows * ghost->ld, s));
     return DORY_OK;
@@ -241,7 +245,7 @@ int split_rows(dory_ctx *c, const char *who, bool pack, int dir, const Tensor *s
     if (ghost->rows != c->plan[dir].recv_total && keep)   // (the twin holds exactly the plan's rows)
         return fail(c, DORY_ERR_ARG, "%s: ghost tensor of %llu rows for a plan that receives %u", who, (unsigned long long)ghost->rows, c->plan[dir].recv_total);
     rc = unpack_rows(c, ghost->d, ghost->ld, wire, buf, c->plan[dir], c->compute, keep ? ghost->twin : nullptr);
-    return rc ? rc : ghost_rows_landed(c, ghost, keep, false, c->compute, true);
+    return rc ? rc : ghost_rows_landed(c, ghost, keep, false, c->compute, true, dir);
 }
 
 // resolve (layer, dir) -> source tensor, ghost tensor, as Engine::scatterGCN/GAT do; false: layer out of range.  No side effects:
@@ -282,8 +286,9 @@ bool halo_ships_bf16(const dory_ctx *c, int dir) {
 // halo_direct_recv = 1 (a 16-bit row cannot land in an fp32 ghost tensor, and such a plan may have no receive buffer) -- unless
 // dory_halo_bf16_ghosts is on and the tensor (ld: the same number on every rank) has a twin for them to land in.  direct_keeps: that
 // exception, from settings every rank can read of every other.
-// (the multi-head GAT has no twins: its direct plans keep fp32)
-inline bool direct_keeps(const dory_ctx *c, uint32_t ld) { return ghosts_on(c) && ld >= 4 && c->gnn != DORY_GATMH; }
+// (the multi-head GAT has twins only with dory_gatmh_bf16_ghosts on top: without it its direct plans keep fp32)
+inline bool gatmh_ghosts_on(const dory_ctx *c) { return c->gatmh_bf16_ghosts.load(std::memory_order_acquire) == 1; }
+inline bool direct_keeps(const dory_ctx *c, uint32_t ld) { return ghosts_on(c) && ld >= 4 && (c->gnn != DORY_GATMH || gatmh_ghosts_on(c)); }
 bool wire_bf16(const dory_ctx *c, int dir, uint32_t ld) {
     return halo_ships_bf16(c, dir) && (!c->plan[dir].direct || direct_keeps(c, ld)) && transport_of(c) != Transport::Scatter;
 }
@@ -677,7 +682,7 @@ int exchange_local(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, RowWire wir
     lp.direct = lands_directly(p, wire, ghost->ld, lp.keep);
     lp.widen_to = lp.keep && ghost->raw_handed ? ghost->d : nullptr;
     lp.ghost_rows = ghost->rows;
-    { int rc = ghost_rows_landed(c, ghost, lp.keep, lp.direct, c->comm, false); if (rc) return rc; }   // (every reader calls wait_halo first: the second half)
+    { int rc = ghost_rows_landed(c, ghost, lp.keep, lp.direct, c->comm, false, dir, pair != nullptr); if (rc) return rc; }   // (every reader calls wait_halo first: the second half)
     if (deferred) {
         c->halo_pending = true;      // wait_halo(): local_exchange_finish, then the compute stream waits for ev_b
         return DORY_OK;
@@ -922,6 +927,9 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
             if (Q && halo_direct(Q) != p.direct)   // (who pushes and who pulls)
                 return fail(c, DORY_ERR_COMM, "local transport: option halo_direct_recv differs: rank %u has %d, rank %u has %d (all ranks must agree)",
                             c->nodeId, (int)p.direct, q, (int)!p.direct);
+            if (Q && c->gnn == DORY_GATMH && gatmh_ghosts_on(Q) != gatmh_ghosts_on(c))
+                return fail(c, DORY_ERR_COMM, "local transport: dory_gatmh_bf16_ghosts differs: rank %u has %d, rank %u has %d (all ranks must agree)",
+                            c->nodeId, (int)gatmh_ghosts_on(c), q, (int)gatmh_ghosts_on(Q));
             // what each rank would ship: the switch, the gather mode that drives the rule, and -- under a direct plan (the same on both by
             // now) -- dory_halo_bf16_ghosts, without which such a plan keeps fp32
             const bool q_ships = Q && follows_rule && halo_ships_bf16(Q, dir) && (!p.direct || direct_keeps(Q, ghost->ld));
@@ -962,7 +970,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
         if (!rc && !direct)
             rc = unpack_rows(c, ghost->d, ghost->ld, wire, c->recv_buf, p, c->comm, keep ? ghost->twin : nullptr, pair ? pair->ghost2->d : nullptr,
                              pair ? pair->ghost2->ld : 0);
-        if (!rc) rc = ghost_rows_landed(c, ghost, keep, direct, c->comm, true);
+        if (!rc) rc = ghost_rows_landed(c, ghost, keep, direct, c->comm, true, dir, pair != nullptr);
         if (!rc && pair) ghost_wrote_fp32(pair->ghost2);
         if (rc) return rc;
         // the one step of an arm left in the shared body: the host arm's, but it stays behind the unpack, so that the unpack
@@ -1077,13 +1085,16 @@ int ghost_fp32_current(dory_ctx *c, Tensor *t) {
     HIPCK(c, launch_widen_rows_bf16(t->d, t->twin, t->rows * t->ld, c->compute));
     t->twin_state = DORY_GHOST_BOTH;
     if (!c->capturing) c->ghost_widened++;
+    if (!c->capturing && c->gnn == DORY_GATMH) c->gatmh_twin_widened++;
     return DORY_OK;
 }
 
-// every ghost tensor halo_route can ever name for a model whose exchanges may land bf16 (never the multi-head GAT: it has no twins,
-// direct_keeps; fg@0 comes from a file), where a row has at least one 8-byte quad
+// every ghost tensor halo_route can ever name for a model whose exchanges may land bf16 (fg@0 comes from a file), where a row has at
+// least one 8-byte quad; the multi-head GAT only with dory_gatmh_bf16_ghosts: fg_z and the bg_do of its own backward exchange (bg_st,
+// fg_el, fg_er never: they travel and are read as fp32)
 static bool ghost_gets_twin(const dory_ctx *c, uint32_t layer, const std::string &name, const Tensor &t) {
     if (!t.owned || t.ld < 4) return false;
+    if (c->gnn == DORY_GATMH) return gatmh_ghosts_on(c) && !(t.ld & 7) && (name == "fg_z" || name == "bg_do");
     if (c->gnn == DORY_GCN) return (name == "fg" && layer >= 1) || name == "fgxw" || name == "bg" || name == "bgg";
     return c->gnn == DORY_GAT && (name == "fg_z" || name == "bg_d");
 }
@@ -1099,6 +1110,10 @@ int ghost_twins_alloc(dory_ctx *c) {
             t.twin_state = DORY_GHOST_FP32;
         }
     return DORY_OK;
+}
+// (the merged row and the exchange of do alone ship bf16 by the same rule, gatmh_do_bf16; rows land in a twin as keeps_bf16 says)
+bool gatmh_do_lands_in_twin(const dory_ctx *c, const Tensor *dO, const Tensor *bgdo) {
+    return c->numNodes > 1 && ghosts_on(c) && bgdo->twin && !bgdo->raw_handed && gatmh_do_bf16(c, dO);
 }
 
 void scatter_free(dory_ctx *c) {
@@ -1540,10 +1555,10 @@ int dory_gatmh_bwd_unpack(dory_ctx *c, uint32_t layer, const float *recv_buf) {
         return fail(c, DORY_ERR_ARG, "gatmh_bwd_unpack: ghost tensors of %llu rows for a plan that receives %u", (unsigned long long)bgdo->rows, p.recv_total);
     if (p.recv_total && (!recv_buf || ((uintptr_t)recv_buf & 15))) return fail(c, DORY_ERR_ARG, "gatmh_bwd_unpack: a 16-byte aligned device buffer");
     Timed t(c, "halo", c->compute);
-    rc = unpack_rows(c, bgdo->d, bgdo->ld, wire, recv_buf, p, c->compute, nullptr, bgst->d, bgst->ld);
-    ghost_wrote_fp32(bgdo);
+    const bool keep = keeps_bf16(c, wire, bgdo);   // (dory_gatmh_bf16_ghosts: the do part stays bf16 in bg_do's twin)
+    rc = unpack_rows(c, bgdo->d, bgdo->ld, wire, recv_buf, p, c->compute, keep ? bgdo->twin : nullptr, bgst->d, bgst->ld);
     ghost_wrote_fp32(bgst);
-    return rc;
+    return rc ? rc : ghost_rows_landed(c, bgdo, keep, false, c->compute, true, DORY_BACKWARD, true);
 }
 
 // ---- bf16 halo rows: switch, counters, and the row an exchange puts on the wire (include/dorylus_hip.h) ------------------------
@@ -1595,6 +1610,7 @@ int dory_halo_bf16_ghosts(dory_ctx *c, int on) {
     for (auto &m : c->tensors)
         for (auto &kv : m) { int rc = ghost_fp32_current(c, &kv.second); if (rc) return rc; }
     c->halo_bf16_ghosts.store(0, std::memory_order_release);
+    c->gatmh_bf16_ghosts.store(0, std::memory_order_release);   // (dory_gatmh_bf16_ghosts lives on top of this switch: its twins go with the others)
     HIPCK(c, hipStreamSynchronize(c->comm));
     HIPCK(c, hipStreamSynchronize(c->compute));
     epoch_graph_drop_locked(c);   // (a recorded epoch may point at a twin)
@@ -1631,6 +1647,50 @@ int dory_halo_bf16_ghost_peek(dory_ctx *c, uint32_t layer, const char *name, con
     { int wrc = wait_halo(c); if (wrc) return wrc; }   // (a deferred exchange: its rows are enqueued before the caller looks; dory_sync waits for them)
     if (twin) *twin = t->twin;
     if (state) *state = t->twin_state;
+    return DORY_OK;
+}
+
+// ---- dory_gatmh_bf16_ghosts: twins for the multi-head GAT's fg_z and bg_do, on top of dory_halo_bf16_ghosts ------------------------
+int dory_gatmh_bf16_ghosts(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (!c->configured || c->gnn != DORY_GATMH) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: a context configured as DORY_GATMH");
+    if (!c->prealloc) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: dory_preallocate first (the twins of fg_z and bg_do are allocated here)");
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: on is 0 or 1");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: not while an epoch graph is being recorded");
+    if (!ghosts_on(c)) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: dory_halo_bf16_ghosts is off (turn it on first: this switch lives on top of it)");
+    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange of a direct plan that may now ship the other element)
+    if (on) {
+        c->gatmh_bf16_ghosts.store(1, std::memory_order_release);
+        return ghost_twins_alloc(c);
+    }
+    // off: as dory_halo_bf16_ghosts(0) -- the only current copies widened first, nothing in flight, no recording that points at a twin
+    for (auto &m : c->tensors)
+        for (auto &kv : m) { int rc = ghost_fp32_current(c, &kv.second); if (rc) return rc; }
+    c->gatmh_bf16_ghosts.store(0, std::memory_order_release);
+    HIPCK(c, hipStreamSynchronize(c->comm));
+    HIPCK(c, hipStreamSynchronize(c->compute));
+    epoch_graph_drop_locked(c);
+    for (auto &m : c->tensors)
+        for (auto &kv : m) {
+            Tensor &t = kv.second;
+            if (t.twin) (void)hipFree(t.twin);
+            t.twin = nullptr;
+            t.twin_state = DORY_GHOST_FP32;
+        }
+    return DORY_OK;
+}
+
+int dory_gatmh_bf16_ghosts_stats(dory_ctx *c, uint64_t *fwd_kept, uint64_t *bwd_kept, uint64_t *bwd_kept_merged, uint64_t *twin_reads_rows,
+                                 uint64_t *twin_reads_sweep, uint64_t *scores_from_twin, uint64_t *widened) {
+    CHECK_CTX(c);
+    if (fwd_kept) *fwd_kept = c->gatmh_twin_fwd;
+    if (bwd_kept) *bwd_kept = c->gatmh_twin_bwd;
+    if (bwd_kept_merged) *bwd_kept_merged = c->gatmh_twin_bwd_merged;
+    if (twin_reads_rows) *twin_reads_rows = c->gatmh_twin_reads_rows;
+    if (twin_reads_sweep) *twin_reads_sweep = c->gatmh_twin_reads_sweep;
+    if (scores_from_twin) *scores_from_twin = c->gatmh_twin_scores;
+    if (widened) *widened = c->gatmh_twin_widened;
     return DORY_OK;
 }
 

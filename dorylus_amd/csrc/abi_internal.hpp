@@ -141,10 +141,14 @@ inline void fused_note_write(dory_ctx *c, const Tensor *t) { if (t && c->fused_s
 // null) -- where only its twin is current (DORY_GHOST_TWIN) the exchange in flight is waited for and the twin widened into the fp32
 // rows on the compute stream (then DORY_GHOST_BOTH, counted); anything else: nothing.  ghost_wrote_fp32: fp32 rows have been written
 // into `t`, all of them.  ghost_twins_alloc: with the switch on, a twin for every tensor the rule of dory_halo_bf16_rows can cover
-// that has none yet (GCN: fg of layers >= 1, fgxw, bg, bgg; GAT prototype: fg_z, bg_d; ld >= 4) -- never inside an epoch.
+// that has none yet (GCN: fg of layers >= 1, fgxw, bg, bgg; GAT prototype: fg_z, bg_d; the multi-head GAT with dory_gatmh_bf16_ghosts:
+// fg_z, bg_do; ld >= 4) -- never inside an epoch.
 int ghost_fp32_current(dory_ctx *c, Tensor *t);
 inline void ghost_wrote_fp32(Tensor *t) { if (t) t->twin_state = DORY_GHOST_FP32; }
 int ghost_twins_alloc(dory_ctx *c);
+// dory_gatmh_bf16_ghosts: the exchange of do -> bg_do that a whole backward pass is about to make (gatmh_bwd_exchange, merged or not)
+// will leave its rows in bg_do's twin, by the settings of this moment -- what the reservation of the shadow rows asks before that exchange
+bool gatmh_do_lands_in_twin(const dory_ctx *c, const Tensor *dO, const Tensor *bgdo);
 // scatter messages (abi_comm.hip): everything dory_ctx::scatter owns, at dory_destroy
 void scatter_free(dory_ctx *c);
 // K1b bookkeeping (abi_stages.hip)

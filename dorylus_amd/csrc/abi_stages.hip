@@ -135,6 +135,7 @@ struct Bf16Rows {
     dory_ctx *c = nullptr;
     const Tensor *ghost = nullptr;
     const float *xl = nullptr, *xg = nullptr;   // bf16 rows of ld elements; xg == nullptr: no ghost rows
+    bool from_twin = false;                     // xg is the ghost tensor's twin (dory_gatmh_bf16_ghosts_stats counts by it)
     // dory_halo_bf16_ghosts: where the ghost tensor's bf16 twin is current (the exchange landed its rows there) the ghost rows are
     // the twin itself -- only the N local rows are reserved and converted, ghosts_landed() has nothing to do (counted).  Not for a
     // tensor whose raw pointer is out: the caller may have written its fp32 rows since (they are kept current: state BOTH), so those
@@ -151,6 +152,7 @@ struct Bf16Rows {
         xl = reinterpret_cast<const float *>(c->bf16_rows);
         xg = !nghost ? nullptr : twin ? reinterpret_cast<const float *>(ghost_rows->twin)
                                       : reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * rows.ld);
+        from_twin = twin;
         if (twin && !c->capturing) c->ghost_conversions_skipped++;
         return DORY_OK;
     }
@@ -567,7 +569,10 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                 if ((rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
                 c->gatmh_bf16_gathers_fwd++;
                 if (gs.sw.wide) c->gatmh_bf16_gathers_fwd_wide++;
+                if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_sweep++;
             }
+            // dory_gatmh_bf16_ghosts: the fp32 form gathers fg_z's fp32 rows (the option was lowered after the exchange): widened first
+            else if (In.ghosts && (rc = ghost_fp32_current(c, fgz))) return rc;
             const float *zs = bf16 ? bf.xl : z->d, *zgs = bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), *a_l = c->weights[fl]["a_l"].d;
             HIPCK(c, launch_gatmh_sweep_begin(c->N, In.ghosts, K, z->ld, el->ld, Sf, el->d, fgel->d, c->scratch, c->compute));
             rc = gs.run([&]() -> int { const int r = wait_halo(c); return r ? r : bf.ghosts_landed(); }, [&](const SweepPart &p) -> int {
@@ -575,6 +580,9 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                 return DORY_OK;
             });
             if (rc) return rc;
+            // (dory_gatmh_bf16_ghosts: the finish / redo kernels read fg_z's fp32 rows -- a twin that alone is current is widened for them:
+            //  correct, not a gain; twin-reading forms of these kernels are not built)
+            if (In.ghosts && (rc = ghost_fp32_current(c, fgz))) return rc;
             HIPCK(c, launch_gatmh_forward_sweep_finish(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Sf, z->d, fgz->d, el->d, fgel->d,
                                                        er->d, o->d, op->d, m->d, den->d, dpos->d, c->scratch, c->compute, bf16));
             if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
@@ -588,6 +596,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                 if (rc) return rc;
                 stat_partial = c->scratch;
             }
+            if (In.ghosts) { int grc = ghost_fp32_current(c, fgz); if (grc) return grc; }   // (dory_gatmh_bf16_ghosts: a reader of fp32 rows)
             HIPCK(c, launch_gatmh_forward_blocked(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, Bf, z->d,
                                                   fgz->d, el->d, fgel->d, er->d, o->d, m->d, den->d, c->partial,
                                                   In.ghosts > 0, c->compute, stat_partial,
@@ -599,8 +608,9 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                 return fail(c, DORY_ERR_ARG, "multi-head GAT: the row-gather kernels need op / dpos and K*D <= ld <= 256 (K = %u, D = %u, ld = %u)", K, D, z->ld);
             // bf16 form: z / fg_z from the shadow rows -- the local rows converted now, the ghost rows once their exchange has landed
             Bf16Rows bf;
-            int rc = rows_bf16 ? bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather") : (int)DORY_OK;
+            int rc = rows_bf16 ? bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather") : In.ghosts ? ghost_fp32_current(c, fgz) : (int)DORY_OK;
             if (rc || (rc = wait_halo(c)) || (rc = bf.ghosts_landed())) return rc;
+            if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_rows++;
             HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
                                                rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
                                                c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16));
@@ -676,7 +686,10 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
             if ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed())) return rc;
             c->gatmh_bf16_gathers_src++;
             if (gs.sw.wide) c->gatmh_bf16_gathers_src_wide++;
+            if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_sweep++;
         }
+        // dory_gatmh_bf16_ghosts: the fp32 form gathers bg_do's fp32 rows (gatmh_bwd_phase = 2 with the option lowered since the rows landed)
+        else if (Out.ghosts && (rc = ghost_fp32_current(c, T.bgdo))) return rc;
         const float *dos = bf16 ? bf.xl : T.dO->d, *dogs = bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr);
         HIPCK(c, launch_gatmh_src_sweep_begin(c->N, Out.ghosts, K, ld, ldk, So, st4, reinterpret_cast<const float4 *>(T.bgst->d), lds4,
                                               c->scratch, c->compute));
@@ -699,6 +712,8 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
 static int gatmh_backward_blocked(dory_ctx *c, const GatmhBwd &T, const BlockedAdj &Bbi, const BlockedAdj &Bbo) {
     const uint32_t K = T.K, D = T.D, ld = T.z->ld, ldk = T.el->ld, lds4 = T.st->ld / 4;
     float4 *st4 = reinterpret_cast<float4 *>(T.st->d);
+    // (dory_gatmh_bf16_ghosts: both sides read fp32 rows -- fg_z here, bg_do after the exchange)
+    if (T.phase != 2 && c->adj[ADJ_IN].ghosts) { int grc = ghost_fp32_current(c, T.fgz); if (grc) return grc; }
     if (T.phase != 2) {   // destination side: t, der, st
         Timed t(c, "spmm", c->compute);
         HIPCK(c, launch_gatmh_backward_blocked_dst(c->N, K, D, ld, ldk, Bbi, T.z->d, T.fgz->d, T.el->d, T.fgel->d,
@@ -710,7 +725,7 @@ static int gatmh_backward_blocked(dory_ctx *c, const GatmhBwd &T, const BlockedA
     }
     if (T.phase == 1) return DORY_OK;
     int rc = gatmh_backward_exchange(c, T);
-    if (rc) return rc;
+    if (rc || (c->adj[ADJ_OUT].ghosts && (rc = ghost_fp32_current(c, T.bgdo)))) return rc;
     Timed t(c, "spmm", c->compute);
     HIPCK(c, launch_gatmh_backward_blocked_src(c->N, K, D, ld, ldk, Bbo, T.z->d, T.el->d, T.dO->d, T.bgdo->d, st4,
                                                reinterpret_cast<const float4 *>(T.bgst->d), lds4, T.der->d,
@@ -743,6 +758,9 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
             Timed t(c, "spmm", c->compute);
             Bf16Rows bf;
             if (dst_bf16 && ((rc = bf.begin(c, *T.z, T.fgz, In.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
+            // (dory_gatmh_bf16_ghosts: the fp32 edge pass -- a layer whose forward swept, the option lowered since -- reads fg_z's fp32 rows)
+            if (!dst_bf16 && In.ghosts && (rc = ghost_fp32_current(c, T.fgz))) return rc;
+            if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_rows++;
             HIPCK(c, launch_gatmh_rows_dst(c->N, K, D, ld, ldk, In.ptr, In.idx, dst_bf16 ? bf.xl : T.z->d,
                                            dst_bf16 ? bf.xg : (In.ghosts ? T.fgz->d : nullptr), T.el->d, In.ghosts ? T.fgel->d : nullptr, T.er->d,
                                            c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, st4, lds4, c->compute, dst_bf16));
@@ -757,6 +775,8 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         // (phase 0: the exchange above made the compute stream wait for bg_do; phase 2: the caller moved it before this call)
         Bf16Rows bf;
         if (src_bf16 && ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
+        if (!src_bf16 && Out.ghosts && (rc = ghost_fp32_current(c, T.bgdo))) return rc;
+        if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_rows++;
         HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
                                        src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
                                        Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
@@ -826,8 +846,12 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
                     !shl ? "heads x features outside the shapes of gatmh_sweep_hl" :
                     !dst_rowwise ? "this layer's forward pass did not run the sweep form" : "the sweep layout of the out-edges does not apply to this graph");
     int rc;
-    if (bf16 && T.phase != 1 && (rc = bf16_reserve(c, (uint64_t)c->N + Out.ghosts, z->ld, "gatmh_bf16_gather"))) return rc;
-    if (rows_dst_bf16 && T.phase != 2 && (rc = bf16_reserve(c, (uint64_t)c->N + In.ghosts, z->ld, "gatmh_bf16_gather"))) return rc;
+    // dory_gatmh_bf16_ghosts: N rows only where the ghost rows will be read from a twin -- bg_do's once the exchange of this call has landed
+    // them there (a whole pass), or as it stands now (phase 2: the caller has moved the rows); fg_z's as it stands since the forward
+    const bool do_twin = T.phase == 0 ? gatmh_do_lands_in_twin(c, dO, bgdo) : bgdo->twin_current() && !bgdo->raw_handed;
+    const bool z_twin = fgz->twin_current() && !fgz->raw_handed;
+    if (bf16 && T.phase != 1 && (rc = bf16_reserve(c, (uint64_t)c->N + (do_twin ? 0 : Out.ghosts), z->ld, "gatmh_bf16_gather"))) return rc;
+    if (rows_dst_bf16 && T.phase != 2 && (rc = bf16_reserve(c, (uint64_t)c->N + (z_twin ? 0 : In.ghosts), z->ld, "gatmh_bf16_gather"))) return rc;
     if (T.phase != 2) {
         Timed t(c, "loss", c->compute);
         if (fl == c->L - 1) {
@@ -1138,6 +1162,14 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
                                      el->d, er->d, el->ld, c->compute));
         if (c->adj[ADJ_IN].ghosts) {   // scores of the ghost sources from their exchanged z rows (el is all the in-edge side needs)
             NEED(fgz, l0, "fg_z"); NEED(fgel, l0, "fg_el"); NEED(fger, l0, "fg_er");
+            // dory_gatmh_bf16_ghosts: the exchange left the rows in fg_z's twin alone -- the scores come from the twin, the bits the fp32
+            // kernel gives on the widened rows (the contract of dory_gatmh_halo_bf16: fg_el from rounded rows); nothing is widened
+            if (fgz->twin && fgz->twin_state == DORY_GHOST_TWIN) {
+                HIPCK(c, launch_gatmh_scores_bf16(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->twin, fgz->ld, c->weights[l0]["a_l"].d,
+                                                  c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
+                if (!c->capturing) c->gatmh_twin_scores++;
+                return DORY_OK;
+            }
             HIPCK(c, launch_gatmh_scores(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->d, fgz->ld, c->weights[l0]["a_l"].d,
                                          c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
         }

@@ -373,6 +373,13 @@ struct dory_ctx {
     // of fp32 rows
     std::atomic<int> halo_bf16_ghosts{0};
     uint64_t ghost_landed_direct = 0, ghost_landed_by_kernel = 0, ghost_conversions_skipped = 0, ghost_widened = 0;
+    // dory_gatmh_bf16_ghosts (default off; on top of dory_halo_bf16_ghosts; a copy the peers of the local transport may read without this
+    // context's lock): fg_z and bg_do of the multi-head GAT have twins too; eager calls counted: forward exchanges / unpacks whose rows stayed
+    // in fg_z's twin, backward ones for bg_do (unmerged, merged), aggregations that read a twin instead of converting ghost rows (the
+    // row-gather family, the sweep forms), dory_apply_edge calls that formed fg_el / fg_er from a twin, widenings for a reader of fp32 rows
+    std::atomic<int> gatmh_bf16_ghosts{0};
+    uint64_t gatmh_twin_fwd = 0, gatmh_twin_bwd = 0, gatmh_twin_bwd_merged = 0, gatmh_twin_reads_rows = 0, gatmh_twin_reads_sweep = 0,
+             gatmh_twin_scores = 0, gatmh_twin_widened = 0;
     dory::ScatterState scatter;  // scatter messages (dory_scatter_msgs_*) and the scatter transport
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
@@ -651,6 +658,10 @@ hipError_t launch_colsum_w(uint32_t N, uint32_t F, const float *X, uint32_t ld, 
 // multi-head GAT extension (csrc/gat_mh.hip)
 hipError_t launch_gatmh_scores(uint32_t N, uint32_t K, uint32_t D, const float *z, uint32_t ldz, const float *a_l,
                                const float *a_r, float *el, float *er, uint32_t ldk, hipStream_t s);
+// dory_gatmh_bf16_ghosts: the same scores from bf16 rows (a ghost tensor's twin, ldz elements a row) -- the bits launch_gatmh_scores gives
+// on the widened rows; the same selection between the two kernels
+hipError_t launch_gatmh_scores_bf16(uint32_t N, uint32_t K, uint32_t D, const uint16_t *z, uint32_t ldz, const float *a_l,
+                                    const float *a_r, float *el, float *er, uint32_t ldk, hipStream_t s);
 hipError_t launch_gatmh_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                 const uint32_t *rowidx, const float *z, const float *el, const float *er, float *o,
                                 float *m, float *den, hipStream_t s);
@@ -797,6 +808,10 @@ hipError_t launch_scatter_rows_bf16(float *dst, const void *src, uint32_t ld, ui
 hipError_t launch_scatter_rows_bf16_keep(uint16_t *dst, const void *src, uint32_t ld, uint32_t row_elems,
                                          const uint32_t *rows, uint32_t n, hipStream_t s);
 hipError_t launch_widen_rows_bf16(float *dst, const uint16_t *src, uint64_t n, hipStream_t s);
+// dory_gatmh_bf16_ghosts: the keep form of launch_scatter_rows_pair_bf16 -- the first part of a row [wa bf16 | wb fp32] stays bf16 in row
+// rows[i] of a's twin (stride lda elements, a multiple of 8; 16-byte chunks, zeros in [wa, lda)); the second part as the sibling leaves it
+hipError_t launch_scatter_rows_pair_bf16_keep(uint16_t *a16, uint32_t lda, uint32_t wa, float *b, uint32_t ldb, uint32_t wb, const float *src,
+                                              const uint32_t *rows, uint32_t n, hipStream_t s);
 // option halo_direct_recv: whole ld-wide rows (any ld) between the caller-visible order of a ghost tensor and its stored (wire)
 // order, off the epoch's path -- to_wire: dst[i] = src[order[i]] (upload), else dst[order[i]] = src[i] (download)
 hipError_t launch_permute_rows(float *dst, const float *src, uint32_t ld, const uint32_t *order, uint32_t n, bool to_wire, hipStream_t s);

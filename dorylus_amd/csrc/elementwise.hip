@@ -1066,6 +1066,24 @@ __global__ __launch_bounds__(256) void scatter_rows_pair_bf16_kernel(float *a, u
         row[cc] = q;
     }
 }
+// keep (dory_gatmh_bf16_ghosts): the first part stays bf16, in the row of a's bf16 twin (a16: lda8 chunks of 16 bytes a row) -- a thread owns
+// one 16-byte chunk of a twin row (below the wire's width the stream's chunk as it is, zeros behind it: the bits rounding the fp32 row
+// the kernel above leaves would give, whatever the twin held) or one quad of a whole row of b, as above.  `total` = rows x (lda8 + ldb4)
+// of this launch is at most 2^31.
+__global__ __launch_bounds__(256) void scatter_rows_pair_bf16_keep_kernel(uint16_t *a16, uint32_t lda8, uint32_t wa8, float *b, uint32_t ldb4,
+                                                                          uint32_t wb4, const uint4 *src, const uint32_t *rows, uint32_t total) {
+    const uint32_t t16 = lda8 + ldb4, r16 = wa8 + wb4, stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const uint32_t r = i / t16, c = i - r * t16;
+        const size_t v = rows[r];
+        const bool first = c < lda8;
+        const uint32_t cc = first ? c : c - lda8;                  // the chunk inside its tensor's row
+        uint4 q = make_uint4(0u, 0u, 0u, 0u);
+        if (cc < (first ? wa8 : wb4)) q = src[(size_t)r * r16 + (first ? cc : wa8 + cc)];
+        uint4 *row = first ? reinterpret_cast<uint4 *>(a16 + v * lda8 * 8) : reinterpret_cast<uint4 *>(b + v * ldb4 * 4);
+        row[cc] = q;
+    }
+}
 // (rows per launch: rows x per_row <= 2^31, so that the kernels' indices stay 32-bit)
 static uint32_t pair_bf16_rows_per_launch(uint32_t per_row) { return (1u << 31) / per_row; }
 hipError_t launch_gather_rows_pair_bf16(float *dst, const float *a, uint32_t lda, uint32_t wa, const float *b, uint32_t ldb, uint32_t wb,
@@ -1090,6 +1108,19 @@ hipError_t launch_scatter_rows_pair_bf16(float *a, uint32_t lda, uint32_t wa, fl
         const uint32_t total = std::min(step, n - r0) * t4;
         const uint32_t blocks = std::min<uint32_t>(2048u, (total + 255u) / 256u);
         hipLaunchKernelGGL(scatter_rows_pair_bf16_kernel, dim3(blocks), dim3(256), 0, s, a, lda / 4, wa / 4, b, ldb / 4, wb / 4,
+                           reinterpret_cast<const uint4 *>(src) + (size_t)r0 * r16, rows + r0, total);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_scatter_rows_pair_bf16_keep(uint16_t *a16, uint32_t lda, uint32_t wa, float *b, uint32_t ldb, uint32_t wb, const float *src,
+                                              const uint32_t *rows, uint32_t n, hipStream_t s) {
+    if (n == 0 || lda + ldb == 0) return hipSuccess;
+    if (((wa | lda) & 7) || ((wb | ldb) & 3) || wa > lda || wb > ldb || (((uintptr_t)src | (uintptr_t)a16 | (uintptr_t)b) & 15)) return hipErrorInvalidValue;
+    const uint32_t t16 = lda / 8 + ldb / 4, r16 = wa / 8 + wb / 4, step = pair_bf16_rows_per_launch(t16);
+    for (uint32_t r0 = 0; r0 < n; r0 += std::min(step, n - r0)) {
+        const uint32_t total = std::min(step, n - r0) * t16;
+        const uint32_t blocks = std::min<uint32_t>(2048u, (total + 255u) / 256u);
+        hipLaunchKernelGGL(scatter_rows_pair_bf16_keep_kernel, dim3(blocks), dim3(256), 0, s, a16, lda / 8, wa / 8, b, ldb / 4, wb / 4,
                            reinterpret_cast<const uint4 *>(src) + (size_t)r0 * r16, rows + r0, total);
     }
     return hipGetLastError();

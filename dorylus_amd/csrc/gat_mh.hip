@@ -73,6 +73,54 @@ __global__ __launch_bounds__(256) void gatmh_scores4_kernel(uint32_t N, uint32_t
     }
 }
 
+// dory_gatmh_bf16_ghosts: the two kernels above on bf16 rows (a ghost tensor's twin: ldz elements a row) -- an element widened exactly
+// (a bf16 is the high half of the fp32 with the same value), then the sibling's lane mapping, fmaf chain and shuffle butterfly: its
+// bits on the widened rows.  The float4 form's 16-byte load becomes one 8-byte load of four bf16.
+__global__ void gatmh_scores_bf16_kernel(uint32_t N, uint32_t K, uint32_t D, const uint16_t *z, uint32_t ldz,
+                                         const float *a_l, const float *a_r, float *el, float *er, uint32_t ldk) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint64_t)N * K) return;
+    const uint32_t v = (uint32_t)(i / K), k = (uint32_t)(i % K);
+    const uint16_t *zr = z + (size_t)v * ldz + (size_t)k * D;
+    float sl = 0.f, sr = 0.f;
+    for (uint32_t d = 0; d < D; ++d) {
+        const float x = __uint_as_float((uint32_t)zr[d] << 16);
+        sl = fmaf(x, a_l[k * D + d], sl);
+        sr = fmaf(x, a_r[k * D + d], sr);
+    }
+    el[(size_t)v * ldk + k] = sl;
+    er[(size_t)v * ldk + k] = sr;
+}
+__global__ __launch_bounds__(256) void gatmh_scores4_bf16_kernel(uint32_t N, uint32_t K, uint32_t D, uint32_t G, const uint16_t *z, uint32_t ldz,
+                                                                 const float *a_l, const float *a_r, float *el, float *er, uint32_t ldk) {
+    const uint32_t nchunk = ldz >> 2, KD = K * D;
+    const uint64_t n = (uint64_t)N * nchunk;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = i < n;
+    const uint64_t ii = ok ? i : 0;
+    const uint32_t v = (uint32_t)(ii / nchunk), col = (uint32_t)(ii % nchunk);
+    const uint2 u = ok ? reinterpret_cast<const uint2 *>(z)[ii] : make_uint2(0u, 0u);
+    const uint32_t f0 = col * 4;
+    float sl = 0.f, sr = 0.f;
+    const float xs[4] = {__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
+                         __uint_as_float(u.y & 0xFFFF0000u)};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (f0 + q < KD) {
+            sl = fmaf(xs[q], a_l[f0 + q], sl);
+            sr = fmaf(xs[q], a_r[f0 + q], sr);
+        }
+    for (uint32_t off = 1; off < G; off <<= 1) {
+        sl += __shfl_xor(sl, (int)off, 64);
+        sr += __shfl_xor(sr, (int)off, 64);
+    }
+    if (ok && (col % G) == 0 && f0 < KD) {
+        const uint32_t k = K == 1 ? 0u : col / G;
+        el[(size_t)v * ldk + k] = sl;
+        er[(size_t)v * ldk + k] = sr;
+    }
+}
+
 // Forward: online softmax statistics, then alpha-weighted aggregation (self edge last).
 template <int NC>
 __global__ __launch_bounds__(256) void gatmh_forward_kernel(GatMhArgs a, const float *z, const float *el,
@@ -540,6 +588,26 @@ hipError_t launch_gatmh_scores(uint32_t N, uint32_t K, uint32_t D, const float *
     }
     const uint64_t n = (uint64_t)N * K;
     hipLaunchKernelGGL(gatmh_scores_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, N, K, D, z, ldz, a_l, a_r, el, er, ldk);
+    return hipGetLastError();
+}
+// (the same selection: the four-element form where launch_gatmh_scores takes its float4 form -- its rows are then 8-byte aligned)
+hipError_t launch_gatmh_scores_bf16(uint32_t N, uint32_t K, uint32_t D, const uint16_t *z, uint32_t ldz, const float *a_l,
+                                    const float *a_r, float *el, float *er, uint32_t ldk, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    const uint32_t nchunk = ldz >> 2;
+    uint32_t G = 0;
+    if (!(ldz & 3) && nchunk && !(nchunk & (nchunk - 1)) && nchunk <= 64) {
+        if (K == 1) G = nchunk;
+        else if (!(D & 3) && !((D >> 2) & ((D >> 2) - 1)) && (D >> 2) <= 64 && nchunk % (D >> 2) == 0) G = D >> 2;
+    }
+    if (G) {
+        if ((uintptr_t)z & 7) return hipErrorInvalidValue;
+        const uint64_t n4 = (uint64_t)N * nchunk;
+        hipLaunchKernelGGL(gatmh_scores4_bf16_kernel, dim3((uint32_t)((n4 + 255) / 256)), dim3(256), 0, s, N, K, D, G, z, ldz, a_l, a_r, el, er, ldk);
+        return hipGetLastError();
+    }
+    const uint64_t n = (uint64_t)N * K;
+    hipLaunchKernelGGL(gatmh_scores_bf16_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, N, K, D, z, ldz, a_l, a_r, el, er, ldk);
     return hipGetLastError();
 }
 

@@ -513,12 +513,12 @@ int dory_gatmh_bwd_unpack(dory_ctx *ctx, uint32_t layer, const float *recv_buf);
  * Forward z: the K2 GEMM's send16 epilogue (dory_halo_fused_pack_bf16) writes exactly this row; without that switch the bf16 pack
  * kernel runs, a counted fallback of the fused pack as elsewhere.
  * KEEP FP32 (eager calls counted in fp32_packs_while_on): the scatter transport; plans made with halo_direct_recv = 1 (no twins for
- * this model: dory_halo_bf16_ghosts stays inert for it); dory_halo_pack_tensor / dory_halo_unpack_tensor (the consumer is unknown); st.
+ * this model: dory_halo_bf16_ghosts stays inert for it unless dory_gatmh_bf16_ghosts is on, below); dory_halo_pack_tensor / dory_halo_unpack_tensor (the consumer is unknown); st.
  * VISIBLE CONSEQUENCE: dory_apply_edge computes fg_el from fg_z after the exchange, so with a bf16 forward wire fg_el comes from rounded
  * rows.  The contract: every tensor, weight and gradient is bit for bit what a run with the switch off and the same options produces
  * in which every ghost row of fg_z is replaced by its rounded value between dory_halo_exchange and dory_apply_edge.  The backward under
  * value 2 changes no bit of any local result; only the raw bg_do shows rounded rows.  After a bf16 exchange the shadow-copy conversion
- * of the ghost rows still runs (it re-rounds rounded rows: correct, and wasted work; removing it needs twins for this model).
+ * of the ghost rows still runs (it re-rounds rounded rows: correct, and wasted work; dory_gatmh_bf16_ghosts, below, removes it).
  * Counters: halo_floats_packed counts 4-byte units; bf16_packs / bf16_bytes of dory_halo_bf16_rows_stats count what travelled as bf16,
  * a merged row with all its bytes; the merged and fused counters move as for an fp32 exchange.  No buffer is re-sized: rows only get
  * narrower.  Bytes per sent vertex for 602-128-41, heads 8 / 1, AS ARITHMETIC (no RCCL run with more than one rank is behind them):
@@ -619,8 +619,9 @@ int dory_gatmh_row_gather_bf16_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst
  * this second switch on too, every ghost tensor the rule above can ever cover has a bf16 TWIN -- rows x ld bf16 in the tensor's own
  * row order (wire order under halo_direct_recv), owned by the tensor -- the received rows stay bf16 in it, and the aggregation on
  * bf16 rows gathers its ghost rows from it: no widening, no conversion of ghost rows (the N local rows are converted as ever).
- * Twins: GCN fg of layers >= 1, fgxw, bg, bgg; GAT prototype fg_z, bg_d; never the multi-head GAT (with dory_gatmh_halo_bf16 its bf16 rows are
- * widened on arrival and its plans made with halo_direct_recv = 1 keep fp32); never a tensor of ld < 4 (one
+ * Twins: GCN fg of layers >= 1, fgxw, bg, bgg; GAT prototype fg_z, bg_d; the multi-head GAT only with dory_gatmh_bf16_ghosts (below) on
+ * top -- without it this switch is inert for that model: with dory_gatmh_halo_bf16 its bf16 rows are widened on arrival and its plans
+ * made with halo_direct_recv = 1 keep fp32; never a tensor of ld < 4 (one
  * column: as without the switch).  Allocated by the setter for the tensors that exist (it needs dory_preallocate: DORY_ERR_ARG
  * before it) and by dory_preallocate while the switch is on; never inside an exchange or an aggregation; freed with the tensor, or
  * by on = 0 after any twin that holds the only current copy has been widened.
@@ -668,6 +669,58 @@ int dory_halo_bf16_ghosts(dory_ctx *ctx, int on);
 int dory_halo_bf16_ghosts_stats(dory_ctx *ctx, uint64_t *landed_direct, uint64_t *landed_by_kernel, uint64_t *conversions_skipped,
                                 uint64_t *widened, uint64_t *twin_bytes);
 int dory_halo_bf16_ghost_peek(dory_ctx *ctx, uint32_t layer, const char *name, const void **twin, int *state);
+
+/* ---- bf16 ghost twins for the multi-head GAT (opt-in, default off; on top of dory_halo_bf16_ghosts; nothing in the reference) -----
+ * dory_halo_bf16_ghosts leaves the multi-head GAT out: the model has readers of fg_z's fp32 rows the other models do not have
+ * (dory_apply_edge forms fg_el / fg_er from them; the sweep forward's finish and redo kernels; the fp32 and the blocked forms) and it
+ * exchanges do / st itself.  With this switch on, "fg_z" and "bg_do" of every layer get a twin as well (allocated by the setter and by
+ * a later dory_preallocate; dory_halo_bf16_ghost_peek and twin_bytes report them); "bg_st", "fg_el" and "fg_er" never do.
+ * LANDING.  Wherever the wire of an exchange is bf16 by the rule of dory_gatmh_halo_bf16 (dory_halo_bf16_rows + dory_gatmh_halo_bf16 +
+ * option "gatmh_bf16_gather" at that call) the rows stay bf16 in the twin, states DORY_GHOST_TWIN / _BOTH exactly as for the other
+ * models: in the RCCL, host and in-process transports and in the split entry points -- dory_halo_unpack, and dory_gatmh_bwd_unpack for
+ * the merged row, whose do part goes into bg_do's twin while st goes into bg_st as fp32.  A plan made with halo_direct_recv = 1 now
+ * ships bf16 for this model too and lands in the twin itself (forward z -> fg_z, and the do -> bg_do exchange of an unmerged
+ * backward; the merged exchange is not taken under direct plans, as before).  There the switch changes what travels, fp32 -> bf16, so
+ * the visible consequence of dory_gatmh_halo_bf16 (fg_el from rounded rows) now holds under direct plans too.
+ * GATHERS.  The bf16 edge passes -- the row-gather family's three and the sweep forms' two -- gather their ghost rows from the twin
+ * and convert only the N local rows into the shadow rows; those are reserved for N rows where a twin serves.
+ * SCORES.  Where fg_z's twin alone is current, dory_apply_edge forms fg_el / fg_er from the twin (launch_gatmh_scores_bf16: one
+ * 8-byte load of four bf16 per lane where the fp32 kernel loads a float4, the same lane mapping, fmaf chain and shuffle butterfly):
+ * the fp32 kernel's result on the widened rows, bit for bit -- the contract of dory_gatmh_halo_bf16 (fg_el from rounded rows).
+ * READERS OF FP32 ROWS find a twin that alone is current widened first (ghost_fp32_current: one dense kernel, state BOTH, counted
+ * here and in dory_halo_bf16_ghosts_stats' `widened`).  CORRECT, AND NOT A GAIN: the sweep forward's finish and redo kernels, which
+ * read fg_z's fp32 rows after every forward of a layer that sweeps (twin-reading forms of them are not built: with the sweep forms
+ * this switch trades the conversion of the ghost rows for a widening of the same rows); the family's fp32 forms when
+ * "gatmh_bf16_gather" was lowered between exchange and aggregation; the fp32 destination-side edge pass of a layer whose forward
+ * swept; the blocked forms; dory_tensor_download; dory_tensor_info handing out a raw pointer (then BOTH after every later exchange).
+ * CONTRACT: with dory_halo_bf16_rows, dory_gatmh_halo_bf16 and dory_halo_bf16_ghosts on, every local tensor, weight and gradient
+ * has the same bits with this switch on and off, and a download of fg_z / bg_do shows the same (rounded) rows.
+ * Kernels beside their siblings, whose code objects do not change: gatmh_scores4_bf16_kernel / gatmh_scores_bf16_kernel
+ * (csrc/gat_mh.hip) and scatter_rows_pair_bf16_keep_kernel (csrc/elementwise.hip: the keep form of the merged unpack -- 16-byte
+ * chunks, zeros in [w, ld) of the twin row, 32-bit indices, the launcher slices at 2^31 chunks; no LDS, no scratch).
+ * dory_gatmh_bf16_ghosts: on = 0 (default) / 1; a DORY_GATMH context after dory_preallocate, outside an exchange, with
+ * dory_halo_bf16_ghosts already on -- anything else, other values and a call while an epoch graph is being recorded are DORY_ERR_ARG
+ * with a message naming what is missing.  dory_halo_bf16_ghosts(ctx, 0) turns this switch off too and frees these twins with the
+ * others (the only current copies widened first).  ALL RANKS MUST SET THE SAME VALUE: in-process ranks that disagree fail with
+ * DORY_ERR_COMM before anything of an exchange is enqueued.  With it off every byte and counter is as before.
+ * dory_gatmh_bf16_ghosts_stats: eager calls since dory_create (not recordings) -- forward exchanges / unpacks whose rows stayed in
+ * fg_z's twin; backward ones for bg_do, alone and through a merged row; bf16 passes that read a twin instead of converting ghost
+ * rows, of the row-gather family and of the sweep forms; dory_apply_edge calls that formed fg_el from a twin; widenings for a reader
+ * of fp32 rows.  dory_halo_bf16_ghosts_stats keeps moving as for the other models.  Any pointer may be NULL.
+ * MEASURED on one MI355X -- NO LINK, NO SECOND GPU AND NO RCCL RUN WITH MORE THAN ONE RANK ARE BEHIND ANY NUMBER --
+ * profiles/r27_gatmh_bf16_ghosts.txt (tools/gatmh_bf16_ghosts_rate.py: rank 0 of 8 of the Amazon-size graph, 3.2 edges per row, 87 % of
+ * the rows ghosts, delivered as bf16 through dory_halo_unpack / dory_gatmh_bwd_unpack; rows of 32 / 64 / 128 floats, heads 8 x 16, 8 x 8,
+ * 32 x 2; the parent's library and this one alternated over three rounds, each pass with the conversion that belongs to it).  The
+ * row-gather family: against the parent (N + ghosts rows converted) forward and edge pass x0.63-0.69, source side x0.71-0.81, a compute
+ * epoch x0.80-0.81 (19.5 -> 15.7, 12.3 -> 10.0, 15.7 -> 12.6 ms); against the fp32 pass, which r26 lost at every line, forward
+ * x0.61-0.71 at 64 / 128 floats and x0.89-0.90 at 32, edge pass x0.64 / x0.88-0.90, source side x0.75-0.83 / x0.91-0.95, the compute
+ * epoch x0.84-0.86.  The keep unpacks x0.66-0.75 (fg_z) and x0.75-0.90 (merged); dory_apply_edge x0.92-0.97 where the four-element
+ * kernel runs.  NOT FASTER, NAMED: dory_apply_edge at 32 x 2 (the scalar kernel; x1.012 against the parent, a tie).  NOT FASTER, NAMED:
+ * the SWEEP forms' Reddit-size epoch over the in-process transport at P = 2 (off 26.9-27.5 ms, on 27.4-28.4): bf16_convert falls
+ * 6.3-6.6 -> 2.0 ms per 10 epochs, and the widening for the finish kernel takes it back. */
+int dory_gatmh_bf16_ghosts(dory_ctx *ctx, int on);   /* 0 (default) / 1 */
+int dory_gatmh_bf16_ghosts_stats(dory_ctx *ctx, uint64_t *fwd_kept, uint64_t *bwd_kept, uint64_t *bwd_kept_merged, uint64_t *twin_reads_rows,
+                                 uint64_t *twin_reads_sweep, uint64_t *scores_from_twin, uint64_t *widened);
 
 /* ---- scatter messages: the reference's own graph-server <-> graph-server wire, packed and unpacked on the device ----------
  * What Engine::verticesPushOut puts on a socket and ghostReceiver* takes apart (include/dorylus_wire.h: the format table with

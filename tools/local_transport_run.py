@@ -24,7 +24,8 @@ dory_halo_bf16_rows on on every rank (with --opt gcn_bf16_gather=1 or 2) and rec
 --gatmh-heads K... runs the multi-head GAT (dory_gatmh_heads; the oracle's epoch is left out) instead of the GCN, and
 --gatmh-merged switches dory_gatmh_bwd_merged_exchange on on every rank and records its counters per rank (merged exchanges, their
 rows, producer-packed ones, split fallbacks); with --gatmh-heads the timing key "loss" (the backward's row-wise destination side among
-it) is recorded too."""
+it) is recorded too.  --gatmh-bf16-ghosts switches dory_gatmh_bf16_ghosts on on top of --bf16-ghosts and --gatmh-halo-bf16 and records
+its counters per rank."""
 import argparse
 import json
 import os
@@ -55,6 +56,7 @@ def main():
     ap.add_argument("--gatmh-heads", type=int, nargs="*", default=None, help="heads per layer: the multi-head GAT instead of the GCN")
     ap.add_argument("--gatmh-merged", action="store_true", help="dory_gatmh_bwd_merged_exchange(1) on every rank (with --gatmh-heads)")
     ap.add_argument("--gatmh-halo-bf16", action="store_true", help="dory_gatmh_halo_bf16(1) on every rank (with --gatmh-heads, --bf16-rows and --opt gatmh_bf16_gather=1|2)")
+    ap.add_argument("--gatmh-bf16-ghosts", action="store_true", help="dory_gatmh_bf16_ghosts(1) on every rank (with --gatmh-heads, --bf16-rows, --bf16-ghosts and --gatmh-halo-bf16)")
     a = ap.parse_args()
     if a.gatmh_heads:
         a.skip_oracle = True
@@ -82,6 +84,7 @@ def main():
     extra = {k: int(v) for k, v in (kv.split("=", 1) for kv in a.opt)}
     recv_bytes, fused_stats, bf16_stats, ghost_stats, convert = {}, {}, {}, {}, {}
     gat16_stats = {}
+    gat_ghost_stats = {}
     rowwise_stats, loss = {}, {}
 
     def setup(ctx, r, g):
@@ -107,6 +110,8 @@ def main():
                     ghost_stats[r] = ctx.halo_bf16_ghosts_stats()
                 if a.gatmh_halo_bf16:
                     gat16_stats[r] = list(ctx.gatmh_halo_bf16_stats())
+                if a.gatmh_bf16_ghosts:
+                    gat_ghost_stats[r] = ctx.gatmh_bf16_ghosts_stats()
             close()
         ctx.close = closing
         if a.fused_pack:
@@ -123,6 +128,8 @@ def main():
             ctx.gatmh_halo_bf16(1)
             if a.fused_pack:
                 ctx.halo_fused_pack_bf16(1)
+        if a.gatmh_bf16_ghosts:
+            ctx.gatmh_bf16_ghosts(1)
         if a.gatmh_heads:
             ctx.upload(0, "h", X[g["localToGlobal"]])
             ctx.labels_upload(labels[g["localToGlobal"]])
@@ -205,6 +212,7 @@ def main():
                    "bf16_rows_stats_per_rank": [bf16_stats.get(r) for r in range(P)] if a.bf16_rows else None,
                    "bf16_ghosts_stats_per_rank": [ghost_stats.get(r) for r in range(P)] if a.bf16_ghosts else None,
                    "gatmh_halo_bf16_stats_per_rank": [gat16_stats.get(r) for r in range(P)] if a.gatmh_halo_bf16 else None,
+                   "gatmh_bf16_ghosts_stats_per_rank": [gat_ghost_stats.get(r) for r in range(P)] if a.gatmh_bf16_ghosts else None,
                    "bf16_convert_sum_over_ranks": {"ms": round(sum(convert[r][0] for r in range(P)), 4), "launches": sum(convert[r][1] for r in range(P))} if a.bf16_rows else None,
                    "wall_s": round(wall, 2)}
             out["runs"].append(rec)
