@@ -120,6 +120,32 @@ def load():
         "dory_gatmh_heads": [vp, vp],
         "dory_comm_set_host_transport": [vp, ALLTOALLV_FN, ALLREDUCE_FN, vp],
         "dory_comm_init_local": [vp, C.c_uint32],
+        # include/dorylus_host.h
+        "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
+        "dory_partition_build_from_files": [cp, u32, u32, i32, C.POINTER(vp)],
+        "dory_partition_load": [cp, C.POINTER(vp)],
+        "dory_partition_save": [vp, cp],
+        "dory_partition_free": [vp],
+        "dory_partition_get": [vp, vp],
+        "dory_partition_upload": [vp, vp, vp],
+        "dory_partition_recv_plan": [vp, vp, i32, vp, vp],
+        "dory_read_layer_config": [cp, vp, u32, C.POINTER(u32)],
+        "dory_read_features": [cp, vp, u32, u32, cp, vp, vp],
+        "dory_read_labels": [cp, vp, u32, vp],
+        "dory_engine_create": [vp, C.POINTER(vp)],
+        "dory_engine_destroy": [vp],
+        "dory_engine_run": [vp, u32, vp],
+        "dory_engine_nn_compute": [vp, vp],
+        "dory_engine_inc_layer": [vp, vp, vp],
+        "dory_chunk_inc_layer": [i32, u32, vp, vp],
+        "dory_engine_trace_epoch": [i32, u32, C.c_char_p, C.c_size_t],
+        "dory_engine_is_last_layer": [vp, vp],
+        "dory_engine_report": [vp, cp, C.c_size_t],
+        "dory_sweep_deal": [u32, u32, u32, vp, vp, vp],
+        "dory_sweep_deal_weighted": [u32, vp, u32, u32, u32, vp, vp, vp],
+    }
+    # bound only if present: DORY_LIB_PATH may name an older build (an A/B run) from before these entry points
+    optional = {
         "dory_halo_wire_ids": [vp, vp, vp, vp],
         "dory_scatter_msgs_layout": [vp, u32, i32, cp, u64, C.POINTER(ScatterMsg), u32, C.POINTER(u32), C.POINTER(u64)],
         "dory_scatter_msgs_pack": [vp, u32, i32, cp, u64, vp],
@@ -157,42 +183,14 @@ def load():
         "dory_gatmh_bf16_ghosts_stats": [vp] + [C.POINTER(u64)] * 7,
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
-        "dory_partition_build": [vp, vp, u64, vp, u32, u32, u32, i32, C.POINTER(vp)],
-        "dory_partition_build_from_files": [cp, u32, u32, i32, C.POINTER(vp)],
-        "dory_partition_load": [cp, C.POINTER(vp)],
-        "dory_partition_save": [vp, cp],
-        "dory_partition_free": [vp],
-        "dory_partition_get": [vp, vp],
-        "dory_partition_upload": [vp, vp, vp],
-        "dory_partition_recv_plan": [vp, vp, i32, vp, vp],
         "dory_partition_wire_order": [vp, vp, i32, vp, vp],
-        "dory_read_layer_config": [cp, vp, u32, C.POINTER(u32)],
-        "dory_read_features": [cp, vp, u32, u32, cp, vp, vp],
-        "dory_read_labels": [cp, vp, u32, vp],
-        "dory_engine_create": [vp, C.POINTER(vp)],
-        "dory_engine_destroy": [vp],
-        "dory_engine_run": [vp, u32, vp],
-        "dory_engine_nn_compute": [vp, vp],
-        "dory_engine_inc_layer": [vp, vp, vp],
-        "dory_chunk_inc_layer": [i32, u32, vp, vp],
-        "dory_engine_trace_epoch": [i32, u32, C.c_char_p, C.c_size_t],
-        "dory_engine_is_last_layer": [vp, vp],
-        "dory_engine_report": [vp, cp, C.c_size_t],
-        "dory_sweep_deal": [u32, u32, u32, vp, vp, vp],
-        "dory_sweep_deal_weighted": [u32, vp, u32, u32, u32, vp, vp, vp],
         "dory_sweep_geometry": [u32, u32, i32, i32, i32, u32, u32, u32, i32, vp],
         "dory_option_spec": [u32, C.POINTER(cp)] + [C.POINTER(t) for t in (i32, C.c_int64, C.c_int64, C.c_int64, i32, i32, i32)],
         "dory_option_check": [cp, C.c_int64, i32, i32, i32, cp, C.c_size_t],
+        "dory_switch_spec": [u32, C.POINTER(cp)] + [C.POINTER(i32)] * 6,
+        "dory_switch_check": [cp, i32, i32, i32, i32, i32, i32, cp, C.c_size_t],
     }
-    for name, args in sig.items():
-        if (name in ("dory_partition_wire_order", "dory_sweep_geometry", "dory_option_spec", "dory_option_check", "dory_halo_wire_ids",
-                     "dory_comm_set_scatter_transport", "dory_halo_send_map") or name.startswith("dory_scatter_msgs_")
-                or name.startswith("dory_halo_fused_pack") or name.startswith("dory_gat_bf16_gather")
-                or name in ("dory_halo_bf16_rows", "dory_halo_bf16_rows_stats", "dory_halo_wire_row")
-                or name in ("dory_halo_bf16_ghosts", "dory_halo_bf16_ghosts_stats", "dory_halo_bf16_ghost_peek")
-                or name.startswith("dory_gatmh_bwd_") or name.startswith("dory_gatmh_halo_bf16") or name.startswith("dory_gatmh_row_gather")
-                or name.startswith("dory_gatmh_bf16_ghosts")) and not hasattr(lib, name):
-            continue      # (DORY_LIB_PATH: an A/B run against a build from before option halo_direct_recv / the geometry hook / the option table / the scatter messages / the fused halo pack / the GAT prototype's bf16 gathers / the bf16 halo rows / the bf16 ghost twins / the fused pack's bf16 form / the multi-head GAT's merged backward exchange / its bf16 halo rows / its row-gather kernels / its bf16 ghost twins)
+    for name, args in list(sig.items()) + [(n, a) for n, a in optional.items() if hasattr(lib, n)]:
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i32
@@ -229,6 +227,23 @@ def option_check(name, value, gnn=GCN, configured=False, has_graph=False, lib=No
     lib = lib or load()
     msg = C.create_string_buffer(512)
     rc = lib.dory_option_check(name.encode(), int(value), int(gnn), int(configured), int(has_graph), msg, len(msg))
+    return rc, msg.value.decode()
+
+
+def switch_specs(lib=None):
+    """The table of the feature switches Context.<name>(value) (dory_switch_spec; no context, no GPU): one dict per switch with name,
+    hi (values 0..hi), refusals (how many its setter has), waits_halo, drops_stamp, parent (index or -1) and counters (of <name>_stats)."""
+    lib, specs, name, v = lib or load(), [], C.c_char_p(), [C.c_int() for _ in range(6)]
+    while lib.dory_switch_spec(len(specs), C.byref(name), *[C.byref(x) for x in v]) == 0:
+        specs.append(dict(zip(("hi", "refusals", "waits_halo", "drops_stamp", "parent", "counters"), (x.value for x in v)), name=name.value.decode()))
+    return specs
+
+
+def switch_check(name, value, gnn=GCN, configured=False, prealloc=False, recording=False, parent_on=False, lib=None):
+    """What Context.<name>(value) answers on a context of that state (dory_switch_check): (return code, refusal text)."""
+    lib = lib or load()
+    msg = C.create_string_buffer(512)
+    rc = lib.dory_switch_check(name.encode(), int(value), int(gnn), int(configured), int(prealloc), int(recording), int(parent_on), msg, len(msg))
     return rc, msg.value.decode()
 
 
@@ -547,9 +562,18 @@ class Context:
     def halo_unpack_tensor(self, layer, name, direction, dev_ptr):
         self._ck(self.lib.dory_halo_unpack_tensor(self.h, layer, name.encode(), direction, C.c_void_p(dev_ptr)))
 
+    def _switch(self, fn, value):       # a feature switch's setter dory_<name>(ctx, int) (the table: switch_specs())
+        self._ck(fn(self.h, int(value)))
+
+    def _stats(self, fn, n, names=None):        # the n values of a dory_<name>_stats entry point: a tuple, or with names a dict
+        v = [C.c_uint64(0) for _ in range(n)]
+        self._ck(fn(self.h, *[C.byref(x) for x in v]))
+        v = tuple(int(x.value) for x in v)
+        return dict(zip(names, v)) if names else v
+
     def halo_fused_pack(self, on=True):
         """the GEMM epilogues write the send rows of the exchange that follows (opt-in; dory_halo_fused_pack)"""
-        self._ck(self.lib.dory_halo_fused_pack(self.h, int(on)))
+        self._switch(self.lib.dory_halo_fused_pack, on)
 
     def gat_bf16_gather(self, mode, wide=False):
         """GAT prototype: the aggregations gather their rows rounded to bf16 (opt-in; dory_gat_bf16_gather) -- mode 1: those that
@@ -564,26 +588,22 @@ class Context:
 
     def halo_bf16_rows(self, on=True):
         """exchanges whose consumer gathers bf16 rows ship bf16 rows (opt-in; dory_halo_bf16_rows): half the bytes, the same bits"""
-        self._ck(self.lib.dory_halo_bf16_rows(self.h, int(on)))
+        self._switch(self.lib.dory_halo_bf16_rows, on)
 
     def halo_bf16_rows_stats(self):
         """(packs that wrote bf16 rows, their bytes, packs that wrote fp32 rows while the switch was on)"""
-        a, b, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._ck(self.lib.dory_halo_bf16_rows_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
-        return a.value, b.value, f.value
+        return self._stats(self.lib.dory_halo_bf16_rows_stats, 3)
 
     GHOST_STATES = ("FP32", "TWIN", "BOTH")     # DORY_GHOST_FP32 / _TWIN / _BOTH
 
     def halo_bf16_ghosts(self, on=True):
         """bf16 halo rows stay bf16 on arrival, in a bf16 twin of the ghost tensor that the aggregation on bf16 rows gathers from
         (opt-in on top of halo_bf16_rows; dory_halo_bf16_ghosts; after preallocate)"""
-        self._ck(self.lib.dory_halo_bf16_ghosts(self.h, int(on)))
+        self._switch(self.lib.dory_halo_bf16_ghosts, on)
 
     def halo_bf16_ghosts_stats(self):
         """dict(landed_direct, landed_by_kernel, conversions_skipped, widened, twin_bytes)"""
-        v = [C.c_uint64(0) for _ in range(5)]
-        self._ck(self.lib.dory_halo_bf16_ghosts_stats(self.h, *[C.byref(x) for x in v]))
-        return dict(zip(("landed_direct", "landed_by_kernel", "conversions_skipped", "widened", "twin_bytes"), (int(x.value) for x in v)))
+        return self._stats(self.lib.dory_halo_bf16_ghosts_stats, 5, ("landed_direct", "landed_by_kernel", "conversions_skipped", "widened", "twin_bytes"))
 
     def halo_bf16_ghost_peek(self, layer, name):
         """(device pointer of the tensor's bf16 twin or None, state "FP32" / "TWIN" / "BOTH"): which copy holds the current rows"""
@@ -599,45 +619,37 @@ class Context:
 
     def halo_fused_pack_stats(self):
         """(exchanges that skipped their pack kernel, the send rows of those, exchanges that packed although the feature was on)"""
-        a, b, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._ck(self.lib.dory_halo_fused_pack_stats(self.h, C.byref(a), C.byref(b), C.byref(f)))
-        return a.value, b.value, f.value
+        return self._stats(self.lib.dory_halo_fused_pack_stats, 3)
 
     def halo_fused_pack_bf16(self, on=True):
         """the fused halo pack also serves exchanges that ship bf16 rows: the GEMM epilogues round and write them (opt-in on top of
         halo_fused_pack and halo_bf16_rows; dory_halo_fused_pack_bf16)"""
-        self._ck(self.lib.dory_halo_fused_pack_bf16(self.h, int(on)))
+        self._switch(self.lib.dory_halo_fused_pack_bf16, on)
 
     def halo_fused_pack_bf16_stats(self):
         """(exchanges whose bf16 send rows a GEMM epilogue wrote, the send rows of those)"""
-        a, b = C.c_uint64(), C.c_uint64()
-        self._ck(self.lib.dory_halo_fused_pack_bf16_stats(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._stats(self.lib.dory_halo_fused_pack_bf16_stats, 2)
 
     def halo_fused_pack_rowwise(self, on=True):
         """the fused halo pack also serves exchanges whose source a row-wise kernel writes (g, h of a transform-first layer, the GAT
         prototype's last-layer grad): the send forms of those kernels write the rows (opt-in on top of halo_fused_pack, and of
         halo_fused_pack_bf16 for bf16 rows; dory_halo_fused_pack_rowwise)"""
-        self._ck(self.lib.dory_halo_fused_pack_rowwise(self.h, int(on)))
+        self._switch(self.lib.dory_halo_fused_pack_rowwise, on)
 
     def halo_fused_pack_rowwise_stats(self):
         """(exchanges whose send rows a row-wise producer wrote, the send rows of those)"""
-        a, b = C.c_uint64(), C.c_uint64()
-        self._ck(self.lib.dory_halo_fused_pack_rowwise_stats(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._stats(self.lib.dory_halo_fused_pack_rowwise_stats, 2)
 
     def gatmh_bwd_merged_exchange(self, on=True):
         """the multi-head GAT's backward sweep ships do and st of a sent vertex as ONE merged row [do | st] in one exchange instead of
         two (opt-in; dory_gatmh_bwd_merged_exchange); with halo_fused_pack on and the sweep forms running, the row-wise kernel that
         produces st writes the send rows itself and no pack kernel runs.  All ranks must set the same value"""
-        self._ck(self.lib.dory_gatmh_bwd_merged_exchange(self.h, int(on)))
+        self._switch(self.lib.dory_gatmh_bwd_merged_exchange, on)
 
     def gatmh_bwd_merged_exchange_stats(self):
         """(merged exchanges made, their send rows, those of them whose rows the producer wrote, backward passes that kept the two
         exchanges although the switch was on)"""
-        v = [C.c_uint64(0) for _ in range(4)]
-        self._ck(self.lib.dory_gatmh_bwd_merged_exchange_stats(self.h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return self._stats(self.lib.dory_gatmh_bwd_merged_exchange_stats, 4)
 
     def gatmh_bwd_wire_row(self, layer):
         """(floats per merged row, of which do, of which st) of the tensors' layer `layer`, as the wire stands now"""
@@ -648,13 +660,11 @@ class Context:
     def gatmh_halo_bf16(self, on=True):
         """the 8-head GAT under the rule of halo_bf16_rows (opt-in, on top of it; dory_gatmh_halo_bf16): z ships bf16 while
         gatmh_bf16_gather >= 1, the backward sweep's do while it is 2; st stays fp32"""
-        self._ck(self.lib.dory_gatmh_halo_bf16(self.h, int(on)))
+        self._switch(self.lib.dory_gatmh_halo_bf16, on)
 
     def gatmh_halo_bf16_stats(self):
         """(fwd_bf16_exchanges, bwd_bf16_exchanges, bwd_bf16_rows, producer_packed_bf16) of the eager exchanges since dory_create"""
-        v = [C.c_uint64() for _ in range(4)]
-        self._ck(self.lib.dory_gatmh_halo_bf16_stats(self.h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return self._stats(self.lib.dory_gatmh_halo_bf16_stats, 4)
 
     def gatmh_bwd_wire_do(self, layer):
         """(elem_bytes, elems) of the do part of the backward rows of `layer` as the wire stands now"""
@@ -675,24 +685,20 @@ class Context:
         """the multi-head GAT's row-gather kernels with ghost rows (dory_gatmh_row_gather): 0 (default) = where a partitioned
         aggregate would otherwise be refused (no sweep layout, no blocked layout, a head shape neither covers), 1 = in place of
         every other family, single partitions included (tests, measurement)"""
-        self._ck(self.lib.dory_gatmh_row_gather(self.h, int(mode)))
+        self._switch(self.lib.dory_gatmh_row_gather, mode)
 
     def gatmh_row_gather_stats(self):
         """(fwd, dst_edge_pass, dst_rowwise, src): the passes the row-gather family ran since dory_create, eager calls and recordings"""
-        v = [C.c_uint64(0) for _ in range(4)]
-        self._ck(self.lib.dory_gatmh_row_gather_stats(self.h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return self._stats(self.lib.dory_gatmh_row_gather_stats, 4)
 
     def gatmh_row_gather_bf16(self, on=1):
         """option gatmh_bf16_gather reaches the row-gather family (dory_gatmh_row_gather_bf16): 0 (default) = refused there as ever,
         1 = where the dispatch selects the family its bf16 forms run (8-byte gathers from the shadow rows, fp32 arithmetic)"""
-        self._ck(self.lib.dory_gatmh_row_gather_bf16(self.h, int(on)))
+        self._switch(self.lib.dory_gatmh_row_gather_bf16, on)
 
     def gatmh_row_gather_bf16_stats(self):
         """(fwd, dst_edge_pass, src): the passes of the row-gather family that ran a bf16 form since dory_create"""
-        v = [C.c_uint64(0) for _ in range(3)]
-        self._ck(self.lib.dory_gatmh_row_gather_bf16_stats(self.h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return self._stats(self.lib.dory_gatmh_row_gather_bf16_stats, 3)
 
     GATMH_BF16_GHOSTS_STATS = ("fwd_kept", "bwd_kept", "bwd_kept_merged", "twin_reads_rows", "twin_reads_sweep", "scores_from_twin", "widened")
 
@@ -700,16 +706,14 @@ class Context:
         """fg_z and bg_do of the multi-head GAT get bf16 twins too (dory_gatmh_bf16_ghosts; opt-in on top of halo_bf16_ghosts, after
         preallocate): rows that travel as bf16 (halo_bf16_rows + gatmh_halo_bf16 + option gatmh_bf16_gather) stay bf16 where the bf16
         edge passes gather them; dory_apply_edge forms fg_el / fg_er from the twin"""
-        self._ck(self.lib.dory_gatmh_bf16_ghosts(self.h, int(on)))
+        self._switch(self.lib.dory_gatmh_bf16_ghosts, on)
 
     def gatmh_bf16_ghosts_stats(self):
         """dict of the eager calls since dory_create: fwd_kept / bwd_kept / bwd_kept_merged (exchanges and unpacks whose rows stayed in
         fg_z's / bg_do's twin, bg_do's through a merged row), twin_reads_rows / twin_reads_sweep (bf16 passes of the row-gather family /
         the sweep forms that read a twin instead of converting ghost rows), scores_from_twin (dory_apply_edge), widened (for a reader
         of fp32 rows)"""
-        v = [C.c_uint64(0) for _ in range(7)]
-        self._ck(self.lib.dory_gatmh_bf16_ghosts_stats(self.h, *[C.byref(x) for x in v]))
-        return dict(zip(self.GATMH_BF16_GHOSTS_STATS, (int(x.value) for x in v)))
+        return self._stats(self.lib.dory_gatmh_bf16_ghosts_stats, 7, self.GATMH_BF16_GHOSTS_STATS)
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

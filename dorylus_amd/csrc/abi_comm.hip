@@ -1,8 +1,9 @@
 // abi_comm.hip -- C-ABI, part 3: ghost-vertex halo exchange (plan, one wire-format record for a packed row, one arm per
 // transport: caller's host callbacks / in-process device transport / RCCL all-to-all-v, pack / unpack for foreign
 // transports), all-reduce over the same transports for the weight gradients + Adam and for the validation statistics, and
-// the epoch graph (hipGraph record / replay).  Layout: helpers in dependency order (file-local ones, then the four that
-// abi_internal.hpp declares), then the extern "C" entry points.
+// the epoch graph (hipGraph record / replay); and the one setter path of the feature switches (switches.hpp: switch_set, their
+// hooks, switch_stats).  Layout: helpers in dependency order (file-local ones, then the four that abi_internal.hpp declares),
+// then the extern "C" entry points.
 #include <chrono>
 #include <thread>
 
@@ -49,8 +50,7 @@ inline bool halo_direct(const dory_ctx *c) { return c->halo_direct.load(std::mem
 // dory_halo_bf16_ghosts: received bf16 rows stay bf16 in the ghost tensor's twin (`keeps`); then an exchange lands directly where
 // the wire's row is the twin's -- compared in elements (fp32 rows in an fp32 tensor, bf16 rows in a bf16 twin).  bf16 rows never
 // land in fp32 rows.
-inline bool ghosts_on(const dory_ctx *c) { return c->halo_bf16_ghosts.load(std::memory_order_acquire) == 1; }
-inline bool keeps_bf16(const dory_ctx *c, RowWire wire, const Tensor *ghost) { return wire.bf16 && ghosts_on(c) && ghost && ghost->twin; }
+inline bool keeps_bf16(const dory_ctx *c, RowWire wire, const Tensor *ghost) { return wire.bf16 && sw_on(c, SW_HALO_BF16_GHOSTS) && ghost && ghost->twin; }
 inline bool lands_directly(const HaloPlan &p, RowWire wire, uint32_t ghost_ld, bool keep) { return p.direct && wire.w == ghost_ld && wire.bf16 == keep; }
 const char *const NO_RECV_BUF = "halo_direct_recv: this exchange needs the receive buffer (rows of %u floats in a tensor of ld %u) and "
                                 "dory_halo_plan allocated none: set halo_exact_rows = 1 before dory_halo_plan";
@@ -111,7 +111,7 @@ inline bool gatmh_do_bf16(const dory_ctx *c, const Tensor *dO) { return c->gnn =
 
 // dory_halo_bf16_rows: an eager exchange or pack that ships fp32 rows while the switch is on (section "not taken" of dorylus_hip.h)
 inline void fp32_while_on(dory_ctx *c) {
-    if (!c->capturing && c->halo_bf16.load(std::memory_order_acquire) == 1) c->halo_fp32_packs_while_on++;
+    if (!c->capturing && sw_on(c, SW_HALO_BF16_ROWS)) c->count[CNT_HALO_FP32_PACKS_WHILE_ON]++;
 }
 // the plan's send rows of `src`, dense at the wire's width, into dst; counted (eager calls); merged rows (wire.w2): those of src2 behind them
 int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const HaloPlan &p, hipStream_t s, const Tensor *src2 = nullptr) {
@@ -125,7 +125,7 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
         c->halo_rows_packed += p.send_total;
         c->halo_floats_packed += (uint64_t)p.send_total * (wire.row_bytes() / sizeof(float));   // (bf16 rows: 4-byte units, w / 2 a row)
         if (wire.exact && (wire.bf16 ? wire.cols : wire.w) < src->ld) c->halo_exact_packs++;
-        if (wire.bf16) { c->halo_bf16_packs++; c->halo_bf16_bytes += (uint64_t)p.send_total * wire.row_bytes(); }
+        if (wire.bf16) { c->count[CNT_HALO_BF16_PACKS]++; c->count[CNT_HALO_BF16_BYTES] += (uint64_t)p.send_total * wire.row_bytes(); }
         else fp32_while_on(c);
     }
     return DORY_OK;
@@ -139,55 +139,55 @@ int pack_rows(dory_ctx *c, float *dst, const Tensor *src, RowWire wire, const Ha
 // or the pair kernel packs them; the fused pack counts the one as a fused exchange, the other as a fallback.
 int send_rows(dory_ctx *c, const Tensor *src, int dir, RowWire wire, const HaloPlan &p, hipStream_t s, bool may_fuse, const RowPair *pair = nullptr) {
     if (wire.bf16 && c->gnn == DORY_GATMH && !c->capturing) {   // (dory_gatmh_halo_bf16_stats: z forward; do backward, alone or in a merged row)
-        if (dir == DORY_FORWARD) c->gatmh_fwd_bf16_exchanges++;
+        if (dir == DORY_FORWARD) c->count[CNT_GATMH_FWD_BF16_EXCHANGES]++;
         else {
-            c->gatmh_bwd_bf16_exchanges++;
-            c->gatmh_bwd_bf16_rows += p.send_total;
-            if (pair && pair->producer_packed) c->gatmh_producer_packed_bf16++;
+            c->count[CNT_GATMH_BWD_BF16_EXCHANGES]++;
+            c->count[CNT_GATMH_BWD_BF16_ROWS] += p.send_total;
+            if (pair && pair->producer_packed) c->count[CNT_GATMH_PRODUCER_PACKED_BF16]++;
         }
     }
     if (pair) {
         if (!c->capturing) {
-            c->merged_exchanges++;
-            c->merged_rows += p.send_total;
-            if (pair->producer_packed) c->merged_producer_packed++;
-            if (c->fused_pack) {
-                if (pair->producer_packed) { c->fused_exchanges++; c->fused_rows += p.send_total; }
-                else c->fallback_exchanges++;
+            c->count[CNT_MERGED_EXCHANGES]++;
+            c->count[CNT_MERGED_ROWS] += p.send_total;
+            if (pair->producer_packed) c->count[CNT_MERGED_PRODUCER_PACKED]++;
+            if (sw_on(c, SW_HALO_FUSED_PACK)) {
+                if (pair->producer_packed) { c->count[CNT_FUSED_EXCHANGES]++; c->count[CNT_FUSED_ROWS] += p.send_total; }
+                else c->count[CNT_FALLBACK_EXCHANGES]++;
             }
         }
         if (!pair->producer_packed) return pack_rows(c, c->send_buf, src, wire, p, s, pair->src2);
         if (wire.bf16 && !c->capturing) {   // (what travelled as bf16 is counted as for a pack: the merged row with all its bytes)
-            c->halo_bf16_packs++;
-            c->halo_bf16_bytes += (uint64_t)p.send_total * wire.row_bytes();
+            c->count[CNT_HALO_BF16_PACKS]++;
+            c->count[CNT_HALO_BF16_BYTES] += (uint64_t)p.send_total * wire.row_bytes();
         }
         if (!wire.bf16) fp32_while_on(c);
         return DORY_OK;
     }
-    if (c->fused_pack) {
+    if (sw_on(c, SW_HALO_FUSED_PACK)) {
         const FusedStamp &st = c->fused_stamp;
         if (may_fuse && st.src == src && st.dir == dir && st.bf16 == wire.bf16 && (!wire.bf16 || st.cols == wire.cols) && st.w == wire.w &&
             st.buf == c->send_buf) {
             const bool rowwise = st.rowwise;
             fused_stamp_drop(c);
             if (!c->capturing) {
-                c->fused_exchanges++;
-                c->fused_rows += p.send_total;
+                c->count[CNT_FUSED_EXCHANGES]++;
+                c->count[CNT_FUSED_ROWS] += p.send_total;
                 if (rowwise) {   // (dory_halo_fused_pack_rowwise: a row-wise producer wrote them -- counted besides)
-                    c->rowwise_exchanges++;
-                    c->rowwise_rows += p.send_total;
+                    c->count[CNT_ROWWISE_EXCHANGES]++;
+                    c->count[CNT_ROWWISE_ROWS] += p.send_total;
                 }
                 if (wire.bf16) {   // (what travelled as bf16 is counted as for a pack: a foreign transport sizes by it)
-                    c->fused_bf16_exchanges++;
-                    c->fused_bf16_rows += p.send_total;
-                    c->halo_bf16_packs++;
-                    c->halo_bf16_bytes += (uint64_t)p.send_total * wire.row_bytes();
+                    c->count[CNT_FUSED_BF16_EXCHANGES]++;
+                    c->count[CNT_FUSED_BF16_ROWS] += p.send_total;
+                    c->count[CNT_HALO_BF16_PACKS]++;
+                    c->count[CNT_HALO_BF16_BYTES] += (uint64_t)p.send_total * wire.row_bytes();
                 }
             }
             if (!wire.bf16) fp32_while_on(c);
             return DORY_OK;
         }
-        if (!c->capturing) c->fallback_exchanges++;
+        if (!c->capturing) c->count[CNT_FALLBACK_EXCHANGES]++;
     }
     return pack_rows(c, c->send_buf, src, wire, p, s);
 }
@@ -225,8 +225,8 @@ int unpack_rows(dory_ctx *c, float *ghost, uint32_t ld, RowWire wire, const floa
 // (dory_gatmh_bf16_ghosts_stats: `dir` and `merged` say which of the multi-head GAT's tensors it is -- fg_z, bg_do alone, bg_do of a merged row)
 int ghost_rows_landed(dory_ctx *c, Tensor *ghost, bool keep, bool direct, hipStream_t s, bool widen_now, int dir, bool merged = false) {
     if (!keep) { ghost_wrote_fp32(ghost); return DORY_OK; }
-    if (!c->capturing) (direct ? c->ghost_landed_direct : c->ghost_landed_by_kernel) += 1;
-    if (!c->capturing && c->gnn == DORY_GATMH) (dir == DORY_FORWARD ? c->gatmh_twin_fwd : merged ? c->gatmh_twin_bwd_merged : c->gatmh_twin_bwd) += 1;
+    if (!c->capturing) (direct ? c->count[CNT_GHOST_LANDED_DIRECT] : c->count[CNT_GHOST_LANDED_BY_KERNEL]) += 1;
+    if (!c->capturing && c->gnn == DORY_GATMH) (dir == DORY_FORWARD ? c->count[CNT_GATMH_TWIN_FWD] : merged ? c->count[CNT_GATMH_TWIN_BWD_MERGED] : c->count[CNT_GATMH_TWIN_BWD]) += 1;
     ghost->twin_state = ghost->raw_handed ? DORY_GHOST_BOTH : DORY_GHOST_TWIN;
     if (ghost->raw_handed && widen_now) HIPCK(c, launch_widen_rows_bf16(ghost->d, ghost->twin, ghost->rows * ghost->ld, s));
     return DORY_OK;
@@ -277,8 +277,8 @@ bool halo_route(dory_ctx *c, uint32_t layer, int dir, Tensor **src, Tensor **gho
 // that read them in fp32 are refused; the family's destination-side edge pass of a layer whose forward swept reads fg_z in fp32).  The same for every
 // layer of a model.  Reads atomics only: the peers of the local transport ask it of each other.
 bool halo_ships_bf16(const dory_ctx *c, int dir) {
-    if (c->halo_bf16.load(std::memory_order_acquire) != 1) return false;
-    if (c->gnn == DORY_GATMH && c->gatmh_halo_bf16.load(std::memory_order_acquire) != 1) return false;
+    if (!sw_on(c, SW_HALO_BF16_ROWS)) return false;
+    if (c->gnn == DORY_GATMH && !sw_on(c, SW_GATMH_HALO_BF16)) return false;
     const int mode = (c->gnn == DORY_GCN ? c->gcn_bf16_mode : c->gnn == DORY_GATMH ? c->gatmh_bf16_mode_pub : c->gat_bf16_mode_pub).load(std::memory_order_acquire);
     return mode >= (dir == DORY_FORWARD ? 1 : 2);
 }
@@ -287,8 +287,7 @@ bool halo_ships_bf16(const dory_ctx *c, int dir) {
 // dory_halo_bf16_ghosts is on and the tensor (ld: the same number on every rank) has a twin for them to land in.  direct_keeps: that
 // exception, from settings every rank can read of every other.
 // (the multi-head GAT has twins only with dory_gatmh_bf16_ghosts on top: without it its direct plans keep fp32)
-inline bool gatmh_ghosts_on(const dory_ctx *c) { return c->gatmh_bf16_ghosts.load(std::memory_order_acquire) == 1; }
-inline bool direct_keeps(const dory_ctx *c, uint32_t ld) { return ghosts_on(c) && ld >= 4 && (c->gnn != DORY_GATMH || gatmh_ghosts_on(c)); }
+inline bool direct_keeps(const dory_ctx *c, uint32_t ld) { return sw_on(c, SW_HALO_BF16_GHOSTS) && ld >= 4 && (c->gnn != DORY_GATMH || sw_on(c, SW_GATMH_BF16_GHOSTS)); }
 bool wire_bf16(const dory_ctx *c, int dir, uint32_t ld) {
     return halo_ships_bf16(c, dir) && (!c->plan[dir].direct || direct_keeps(c, ld)) && transport_of(c) != Transport::Scatter;
 }
@@ -895,7 +894,7 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
         HIPCK(c, hipEventRecord(c->ev_a, c->compute));
         HIPCK(c, hipStreamWaitEvent(c->comm, c->ev_a, 0));
         const bool deferred = defer && c->opt[OPT_HALO_OVERLAP];
-        if (c->fused_pack && !c->capturing) c->fallback_exchanges++;   // (messages have another layout: never fused)
+        if (sw_on(c, SW_HALO_FUSED_PACK) && !c->capturing) c->count[CNT_FALLBACK_EXCHANGES]++;   // (messages have another layout: never fused)
         fp32_while_on(c);   // (... and carry fp32)
         {
             Timed t(c, "halo", c->comm);
@@ -927,9 +926,9 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
             if (Q && halo_direct(Q) != p.direct)   // (who pushes and who pulls)
                 return fail(c, DORY_ERR_COMM, "local transport: option halo_direct_recv differs: rank %u has %d, rank %u has %d (all ranks must agree)",
                             c->nodeId, (int)p.direct, q, (int)!p.direct);
-            if (Q && c->gnn == DORY_GATMH && gatmh_ghosts_on(Q) != gatmh_ghosts_on(c))
+            if (Q && c->gnn == DORY_GATMH && sw_on(Q, SW_GATMH_BF16_GHOSTS) != sw_on(c, SW_GATMH_BF16_GHOSTS))
                 return fail(c, DORY_ERR_COMM, "local transport: dory_gatmh_bf16_ghosts differs: rank %u has %d, rank %u has %d (all ranks must agree)",
-                            c->nodeId, (int)gatmh_ghosts_on(c), q, (int)gatmh_ghosts_on(Q));
+                            c->nodeId, (int)sw_on(c, SW_GATMH_BF16_GHOSTS), q, (int)sw_on(Q, SW_GATMH_BF16_GHOSTS));
             // what each rank would ship: the switch, the gather mode that drives the rule, and -- under a direct plan (the same on both by
             // now) -- dory_halo_bf16_ghosts, without which such a plan keeps fp32
             const bool q_ships = Q && follows_rule && halo_ships_bf16(Q, dir) && (!p.direct || direct_keeps(Q, ghost->ld));
@@ -996,21 +995,21 @@ uint32_t gatmh_merged_row_max(const dory_ctx *c) {
 // the merged exchange is taken: the switch, a whole sweep, a transport that moves dense rows, a plan whose received rows go through
 // the receive buffer (halo_direct_recv lands rows in ONE tensor)
 static bool gatmh_merged_taken(const dory_ctx *c) {
-    if (c->gatmh_merged.load(std::memory_order_acquire) != 1 || c->opt[OPT_GATMH_BWD_PHASE] != 0 || c->numNodes <= 1) return false;
+    if (!sw_on(c, SW_GATMH_BWD_MERGED_EXCHANGE) || c->opt[OPT_GATMH_BWD_PHASE] != 0 || c->numNodes <= 1) return false;
     const Transport tr = transport_of(c);
     return (tr == Transport::Rccl || tr == Transport::Host || tr == Transport::Local) && c->plan[DORY_BACKWARD].set && !c->plan[DORY_BACKWARD].direct;
 }
 int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, GatmhSend *sd, bool *send, bool *bf16) {
     const HaloPlan &p = c->plan[DORY_BACKWARD];
     *send = *bf16 = false;
-    if (!gatmh_merged_taken(c) || !c->fused_pack || c->capturing || !p.d_send_map || p.send_map_rows != c->N || dO->rows != c->N) return DORY_OK;
+    if (!gatmh_merged_taken(c) || !sw_on(c, SW_HALO_FUSED_PACK) || c->capturing || !p.d_send_map || p.send_map_rows != c->N || dO->rows != c->N) return DORY_OK;
     const bool do16 = gatmh_do_bf16(c, dO);
     const RowWire wire = pair_wire(c, dO, st, do16);
     if ((size_t)p.send_total * wire.row_bytes() > c->send_cap) return DORY_OK;   // (the exchange would regrow the buffer)
     if (transport_of(c) == Transport::Local)   // (its refusal comes from gatmh_bwd_exchange / exchange_rows, before anything is written)
         for (uint32_t q = 0; q < c->numNodes; ++q) {
             const dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
-            if (Q && (Q->gatmh_merged.load(std::memory_order_acquire) != 1 || halo_ships_bf16(Q, DORY_BACKWARD) != do16)) return DORY_OK;
+            if (Q && (!sw_on(Q, SW_GATMH_BWD_MERGED_EXCHANGE) || halo_ships_bf16(Q, DORY_BACKWARD) != do16)) return DORY_OK;
         }
     sd->buf = c->send_buf;
     sd->row_ptr = p.d_send_map;
@@ -1023,11 +1022,11 @@ int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, Gatmh
     return wait_halo(c);   // the previous exchange has finished reading the buffer
 }
 int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor *bgst, bool producer_packed) {
-    const int on = c->gatmh_merged.load(std::memory_order_acquire);
+    const int on = sw_value(c, SW_GATMH_BWD_MERGED_EXCHANGE);
     if (transport_of(c) == Transport::Local)   // every rank ships one row format: checked before anything of this pass is enqueued or counted
         for (uint32_t q = 0; q < c->numNodes; ++q) {
             const dory_ctx *Q = q == c->nodeId ? nullptr : c->local->ctx[q];
-            if (Q && Q->gatmh_merged.load(std::memory_order_acquire) != on)
+            if (Q && sw_value(Q, SW_GATMH_BWD_MERGED_EXCHANGE) != on)
                 return fail(c, DORY_ERR_COMM, "local transport: dory_gatmh_bwd_merged_exchange differs: rank %u has %d, rank %u has %d (all ranks must agree)",
                             c->nodeId, on, q, 1 - on);
         }
@@ -1036,13 +1035,13 @@ int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor
         pair.src2 = st; pair.ghost2 = bgst; pair.producer_packed = producer_packed;
         return exchange_rows(c, DORY_BACKWARD, dO, bgdo, false, &pair);
     }
-    if (on == 1 && !c->capturing) c->merged_split_fallbacks++;   // (the scatter transport: its own layout; halo_direct_recv: two tensors)
+    if (on == 1 && !c->capturing) c->count[CNT_MERGED_SPLIT_FALLBACKS]++;   // (the scatter transport: its own layout; halo_direct_recv: two tensors)
     int rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, false);   // (dory_gatmh_halo_bf16: do by the rule, st always fp32)
     return rc ? rc : exchange_rows(c, DORY_BACKWARD, st, bgst, false, nullptr, false);
 }
 
 bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd, int *dir) {
-    if (!c->fused_pack || c->numNodes <= 1 || c->capturing || out->raw_handed || M != c->N || out->rows != c->N) return false;
+    if (!sw_on(c, SW_HALO_FUSED_PACK) || c->numNodes <= 1 || c->capturing || out->raw_handed || M != c->N || out->rows != c->N) return false;
     const Transport tr = transport_of(c);
     if (tr == Transport::Scatter || tr == Transport::None) return false;
     for (int d = 0; d < 2; ++d) {
@@ -1054,7 +1053,7 @@ bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd,
             const RowWire wire = wire_shape(c, out, d);
             // dory_halo_bf16_rows: the pack kernel rounds the rows (no GEMM stores fp32 rows nobody sends) -- unless
             // dory_halo_fused_pack_bf16 has the epilogue round them; a wire row wider than the tensor's (one column, ld == 1) packs
-            if (wire.bf16 && (!c->fused_pack_bf16 || wire.w > out->ld)) return false;
+            if (wire.bf16 && (!sw_on(c, SW_HALO_FUSED_PACK_BF16) || wire.w > out->ld)) return false;
             if ((size_t)p.send_total * wire.row_bytes() > c->send_cap) return false;   // (the exchange would regrow the buffer)
             sd->buf = c->send_buf;
             sd->row_ptr = p.d_send_map;
@@ -1084,8 +1083,8 @@ int ghost_fp32_current(dory_ctx *c, Tensor *t) {
     Timed tw(c, "bf16_widen", c->compute);
     HIPCK(c, launch_widen_rows_bf16(t->d, t->twin, t->rows * t->ld, c->compute));
     t->twin_state = DORY_GHOST_BOTH;
-    if (!c->capturing) c->ghost_widened++;
-    if (!c->capturing && c->gnn == DORY_GATMH) c->gatmh_twin_widened++;
+    if (!c->capturing) c->count[CNT_GHOST_WIDENED]++;
+    if (!c->capturing && c->gnn == DORY_GATMH) c->count[CNT_GATMH_TWIN_WIDENED]++;
     return DORY_OK;
 }
 
@@ -1094,12 +1093,12 @@ int ghost_fp32_current(dory_ctx *c, Tensor *t) {
 // fg_el, fg_er never: they travel and are read as fp32)
 static bool ghost_gets_twin(const dory_ctx *c, uint32_t layer, const std::string &name, const Tensor &t) {
     if (!t.owned || t.ld < 4) return false;
-    if (c->gnn == DORY_GATMH) return gatmh_ghosts_on(c) && !(t.ld & 7) && (name == "fg_z" || name == "bg_do");
+    if (c->gnn == DORY_GATMH) return sw_on(c, SW_GATMH_BF16_GHOSTS) && !(t.ld & 7) && (name == "fg_z" || name == "bg_do");
     if (c->gnn == DORY_GCN) return (name == "fg" && layer >= 1) || name == "fgxw" || name == "bg" || name == "bgg";
     return c->gnn == DORY_GAT && (name == "fg_z" || name == "bg_d");
 }
 int ghost_twins_alloc(dory_ctx *c) {
-    if (!ghosts_on(c)) return DORY_OK;
+    if (!sw_on(c, SW_HALO_BF16_GHOSTS)) return DORY_OK;
     for (uint32_t l = 0; l < c->tensors.size(); ++l)
         for (auto &kv : c->tensors[l]) {
             Tensor &t = kv.second;
@@ -1113,7 +1112,7 @@ int ghost_twins_alloc(dory_ctx *c) {
 }
 // (the merged row and the exchange of do alone ship bf16 by the same rule, gatmh_do_bf16; rows land in a twin as keeps_bf16 says)
 bool gatmh_do_lands_in_twin(const dory_ctx *c, const Tensor *dO, const Tensor *bgdo) {
-    return c->numNodes > 1 && ghosts_on(c) && bgdo->twin && !bgdo->raw_handed && gatmh_do_bf16(c, dO);
+    return c->numNodes > 1 && sw_on(c, SW_HALO_BF16_GHOSTS) && bgdo->twin && !bgdo->raw_handed && gatmh_do_bf16(c, dO);
 }
 
 void scatter_free(dory_ctx *c) {
@@ -1140,6 +1139,89 @@ void epoch_graph_drop_locked(dory_ctx *c) {
     c->epoch_exec = nullptr;
     c->epoch_graph = nullptr;
     c->lr_table_left = 0;
+}
+
+// ---- the feature switches: one setter path and one reader of the counters (switches.hpp; the table: host/switches.cpp) ---------
+// The hooks: what a switch does beyond its record, between the checks and the store.  A hook that fails leaves the switch as it was -- but the
+// ghost twins' on path, which stores first (ghost_twins_alloc reads the switch): a failed allocation leaves it on, as it always did.
+// dory_halo_fused_pack on: the send maps of the plans that exist already -- their lists come back from the device
+static int fused_pack_hook(dory_ctx *c, SwitchId, int on) {
+    for (int dir = 0; dir < 2 && on; ++dir) {
+        HaloPlan &p = c->plan[dir];
+        if (!p.set || p.d_send_map) continue;
+        std::vector<uint32_t> lv(p.send_total);
+        if (p.send_total) HIPCK(c, hipMemcpy(lv.data(), p.d_send_lvids, (size_t)p.send_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        int rc = build_send_map(c, p, lv.data());
+        if (rc) return rc;
+    }
+    return DORY_OK;
+}
+// dory_gatmh_bwd_merged_exchange on, a backward plan that exists already: the buffers hold its widest merged rows from now on (no regrowth in an epoch)
+static int merged_exchange_hook(dory_ctx *c, SwitchId, int on) {
+    const HaloPlan &p = c->plan[DORY_BACKWARD];
+    if (!on || c->numNodes <= 1 || !p.set || p.direct) return DORY_OK;
+    const size_t rb = (size_t)gatmh_merged_row_max(c) * sizeof(float);
+    const size_t sb = (size_t)p.send_total * rb, rcb = (size_t)p.recv_total * rb;
+    if (c->local && (sb > c->send_cap || rcb > c->recv_cap))
+        return fail(c, DORY_ERR_ARG, "gatmh_bwd_merged_exchange: the exchange buffers are too small for merged rows and the in-process peers hold "
+                    "their addresses: call it before dory_comm_init_local");
+    return ensure_exchange_buffers(c, sb, rcb);
+}
+// dory_halo_bf16_ghosts / dory_gatmh_bf16_ghosts.  On: the twins are allocated here (ghost_twins_alloc reads the switch: stored first).  Off: a twin that holds
+// the only current copy is widened first; both streams idle, nothing in flight reads a twin; a recorded epoch may point at one; then every twin goes -- and the
+// switch on top of the other goes off with either.
+static int ghost_twins_hook(dory_ctx *c, SwitchId id, int on) {
+    if (on) { c->sw[id].store(1, std::memory_order_release); return ghost_twins_alloc(c); }
+    for (auto &m : c->tensors)
+        for (auto &kv : m) { int rc = ghost_fp32_current(c, &kv.second); if (rc) return rc; }
+    c->sw[id].store(0, std::memory_order_release);
+    c->sw[SW_GATMH_BF16_GHOSTS].store(0, std::memory_order_release);
+    HIPCK(c, hipStreamSynchronize(c->comm));
+    HIPCK(c, hipStreamSynchronize(c->compute));
+    epoch_graph_drop_locked(c);
+    for (auto &m : c->tensors)
+        for (auto &kv : m) {
+            Tensor &t = kv.second;
+            if (t.twin) (void)hipFree(t.twin);
+            t.twin = nullptr;
+            t.twin_state = DORY_GHOST_FP32;
+        }
+    return DORY_OK;
+}
+// the hook of every switch, by SwitchId (null: the record says it all): a new switch that owns memory adds its hook here
+static int (*const SWITCH_HOOKS[])(dory_ctx *, SwitchId, int) = {
+    fused_pack_hook, nullptr, nullptr, merged_exchange_hook, nullptr,   // halo_fused_pack, _bf16, _rowwise, gatmh_bwd_merged_exchange, gatmh_halo_bf16
+    nullptr, ghost_twins_hook, ghost_twins_hook, nullptr, nullptr,      // halo_bf16_rows, halo_bf16_ghosts, gatmh_bf16_ghosts, gatmh_row_gather, _bf16
+};
+static_assert(sizeof(SWITCH_HOOKS) / sizeof(SWITCH_HOOKS[0]) == SW_COUNT && SW_HALO_FUSED_PACK == 0 && SW_GATMH_BWD_MERGED_EXCHANGE == 3 &&
+              SW_HALO_BF16_GHOSTS == 6 && SW_GATMH_BF16_GHOSTS == 7, "switches: one hook slot per SwitchId, each hook at its switch's id");
+
+// every dory_<switch>(ctx, value): the record's refusals in their order, what the record says a set does first, the hook, the store
+static int switch_set(dory_ctx *c, SwitchId id, int value) {
+    CHECK_CTX(c);
+    const SwitchSpec &s = *switch_spec(id);
+    char msg[320];
+    if (switch_check(id, value, c->gnn, c->configured, c->prealloc, c->capturing, s.parent != SW_NONE && sw_on(c, (SwitchId)s.parent), msg, sizeof(msg)))
+        return fail(c, DORY_ERR_ARG, "%s", msg);
+    if (s.waits_halo) { int wrc = wait_halo(c); if (wrc) return wrc; }
+    if (s.drops_stamp) fused_stamp_drop(c);   // (rows a producer left for an exchange that may now ship another element, or not fuse)
+    if (SWITCH_HOOKS[id]) { int rc = SWITCH_HOOKS[id](c, id, value); if (rc) return rc; }
+    c->sw[id].store(value, std::memory_order_release);   // (the ghost twins' hook has stored it already: the same value again)
+    return DORY_OK;
+}
+// every dory_<switch>_stats: the record's counters into the non-null pointers, in the order of the signature (n of them)
+static int switch_stats(dory_ctx *c, SwitchId id, uint64_t *const out[], int n) {
+    CHECK_CTX(c);
+    const SwitchSpec &s = *switch_spec(id);
+    for (int i = 0; i < n && i < s.ncounters; ++i)
+        if (out[i]) *out[i] = c->count[s.counters[i]];
+    if (s.twin_bytes && n > s.ncounters && out[s.ncounters]) {   // computed, not counted: the bytes of all bf16 twins
+        *out[s.ncounters] = 0;
+        for (auto &m : c->tensors)
+            for (auto &kv : m)
+                if (kv.second.twin) *out[s.ncounters] += kv.second.twin_bytes();
+    }
+    return DORY_OK;
 }
 
 }  // namespace dory
@@ -1224,7 +1306,7 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
     p.d_send_lvids = p.d_recv_slots = p.d_unpack_slots = p.d_send_map = nullptr;
     int rc;
     if ((rc = upload_array(c, &p.d_send_lvids, send_lvids, p.send_total))) return rc;
-    if (c->fused_pack && (rc = build_send_map(c, p, send_lvids))) return rc;
+    if (sw_on(c, SW_HALO_FUSED_PACK) && (rc = build_send_map(c, p, send_lvids))) return rc;
     if ((rc = upload_array(c, &p.d_recv_slots, recv_slots, p.recv_total))) return rc;
     // option halo_direct_recv: received row r is ghost row r; recv_slots names the caller-visible index of that row (kept for
     // the uploads and downloads of ghost tensors), the unpack kernels get the identity
@@ -1251,7 +1333,7 @@ int dory_halo_plan(dory_ctx *c, int dir, const uint32_t *send_counts, const uint
     // (option halo_direct_recv: padded rows land in the ghost tensors; only exact rows narrower than their padding -- option
     // halo_exact_rows, as it stands now -- are staged)
     w = std::max(w, 2u);   // (dory_halo_bf16_rows: a one-column row travels as 4 bf16)
-    if (c->gnn == DORY_GATMH && dir == DORY_BACKWARD && !p.direct && c->gatmh_merged.load(std::memory_order_acquire) == 1)
+    if (c->gnn == DORY_GATMH && dir == DORY_BACKWARD && !p.direct && sw_on(c, SW_GATMH_BWD_MERGED_EXCHANGE))
         w = std::max(w, gatmh_merged_row_max(c));   // (dory_gatmh_bwd_merged_exchange: [do | st] rows)
     const bool staged = !p.direct || halo_exact(c);
     return ensure_exchange_buffers(c, (size_t)p.send_total * w * sizeof(float), staged ? (size_t)p.recv_total * w * sizeof(float) : 0);
@@ -1381,97 +1463,32 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
 }
 
 // ---- the fused halo pack: switch and counters (include/dorylus_hip.h) ----------------------------------------------------------
-int dory_halo_fused_pack(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_fused_pack: dory_configure first; on is 0 or 1");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    fused_stamp_drop(c);
-    c->fused_pack = on == 1;
-    for (int dir = 0; dir < 2 && on; ++dir) {   // the plans that exist already: their lists come back from the device
-        HaloPlan &p = c->plan[dir];
-        if (!p.set || p.d_send_map) continue;
-        std::vector<uint32_t> lv(p.send_total);
-        if (p.send_total) HIPCK(c, hipMemcpy(lv.data(), p.d_send_lvids, (size_t)p.send_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        int rc = build_send_map(c, p, lv.data());
-        if (rc) return rc;
-    }
-    return DORY_OK;
-}
-
+int dory_halo_fused_pack(dory_ctx *c, int on) { return switch_set(c, SW_HALO_FUSED_PACK, on); }
 int dory_halo_fused_pack_stats(dory_ctx *c, uint64_t *fused_exchanges, uint64_t *fused_rows, uint64_t *fallback_exchanges) {
-    CHECK_CTX(c);
-    if (fused_exchanges) *fused_exchanges = c->fused_exchanges;
-    if (fused_rows) *fused_rows = c->fused_rows;
-    if (fallback_exchanges) *fallback_exchanges = c->fallback_exchanges;
-    return DORY_OK;
+    uint64_t *const out[] = {fused_exchanges, fused_rows, fallback_exchanges};
+    return switch_stats(c, SW_HALO_FUSED_PACK, out, 3);
 }
 
 // dory_halo_fused_pack_bf16: the fused pack also serves the exchanges that ship bf16 rows (K2's send16 kernels)
-int dory_halo_fused_pack_bf16(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_fused_pack_bf16: dory_configure first; on is 0 or 1");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_fused_pack_bf16: not while an epoch graph is being recorded");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    fused_stamp_drop(c);
-    c->fused_pack_bf16 = on == 1;
-    return DORY_OK;
-}
-
+int dory_halo_fused_pack_bf16(dory_ctx *c, int on) { return switch_set(c, SW_HALO_FUSED_PACK_BF16, on); }
 int dory_halo_fused_pack_bf16_stats(dory_ctx *c, uint64_t *fused_bf16_exchanges, uint64_t *fused_bf16_rows) {
-    CHECK_CTX(c);
-    if (fused_bf16_exchanges) *fused_bf16_exchanges = c->fused_bf16_exchanges;
-    if (fused_bf16_rows) *fused_bf16_rows = c->fused_bf16_rows;
-    return DORY_OK;
+    uint64_t *const out[] = {fused_bf16_exchanges, fused_bf16_rows};
+    return switch_stats(c, SW_HALO_FUSED_PACK_BF16, out, 2);
 }
 
 // dory_halo_fused_pack_rowwise: the fused pack also serves the exchanges whose source a row-wise kernel writes (the send forms of
 // csrc/elementwise.hip; dory_apply_vertex and dory_predict_gat launch them)
-int dory_halo_fused_pack_rowwise(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_fused_pack_rowwise: dory_configure first; on is 0 or 1");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_fused_pack_rowwise: not while an epoch graph is being recorded");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    fused_stamp_drop(c);
-    c->fused_pack_rowwise = on == 1;
-    return DORY_OK;
-}
-
+int dory_halo_fused_pack_rowwise(dory_ctx *c, int on) { return switch_set(c, SW_HALO_FUSED_PACK_ROWWISE, on); }
 int dory_halo_fused_pack_rowwise_stats(dory_ctx *c, uint64_t *rowwise_exchanges, uint64_t *rowwise_rows) {
-    CHECK_CTX(c);
-    if (rowwise_exchanges) *rowwise_exchanges = c->rowwise_exchanges;
-    if (rowwise_rows) *rowwise_rows = c->rowwise_rows;
-    return DORY_OK;
+    uint64_t *const out[] = {rowwise_exchanges, rowwise_rows};
+    return switch_stats(c, SW_HALO_FUSED_PACK_ROWWISE, out, 2);
 }
 
 // ---- the multi-head GAT's merged backward exchange: switch, counters, and the split entry points (include/dorylus_hip.h) ----------
-int dory_gatmh_bwd_merged_exchange(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || c->gnn != DORY_GATMH || (on != 0 && on != 1))
-        return fail(c, DORY_ERR_ARG, "gatmh_bwd_merged_exchange: a context configured as DORY_GATMH; on is 0 or 1");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_bwd_merged_exchange: not while an epoch graph is being recorded");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    const HaloPlan &p = c->plan[DORY_BACKWARD];
-    if (on && c->numNodes > 1 && p.set && !p.direct) {   // a backward plan that exists already: the buffers hold its widest merged rows from now on -- never a regrowth inside an epoch
-        const size_t rb = (size_t)gatmh_merged_row_max(c) * sizeof(float);
-        const size_t sb = (size_t)p.send_total * rb, rcb = (size_t)p.recv_total * rb;
-        if (c->local && (sb > c->send_cap || rcb > c->recv_cap))
-            return fail(c, DORY_ERR_ARG, "gatmh_bwd_merged_exchange: the exchange buffers are too small for merged rows and the in-process peers hold "
-                        "their addresses: call it before dory_comm_init_local");
-        int rc = ensure_exchange_buffers(c, sb, rcb);
-        if (rc) return rc;
-    }
-    c->gatmh_merged.store(on, std::memory_order_release);
-    return DORY_OK;
-}
-
-int dory_gatmh_bwd_merged_exchange_stats(dory_ctx *c, uint64_t *merged_exchanges, uint64_t *merged_rows, uint64_t *producer_packed,
-                                         uint64_t *split_fallbacks) {
-    CHECK_CTX(c);
-    if (merged_exchanges) *merged_exchanges = c->merged_exchanges;
-    if (merged_rows) *merged_rows = c->merged_rows;
-    if (producer_packed) *producer_packed = c->merged_producer_packed;
-    if (split_fallbacks) *split_fallbacks = c->merged_split_fallbacks;
-    return DORY_OK;
+int dory_gatmh_bwd_merged_exchange(dory_ctx *c, int on) { return switch_set(c, SW_GATMH_BWD_MERGED_EXCHANGE, on); }
+int dory_gatmh_bwd_merged_exchange_stats(dory_ctx *c, uint64_t *merged_exchanges, uint64_t *merged_rows, uint64_t *producer_packed, uint64_t *split_fallbacks) {
+    uint64_t *const out[] = {merged_exchanges, merged_rows, producer_packed, split_fallbacks};
+    return switch_stats(c, SW_GATMH_BWD_MERGED_EXCHANGE, out, 4);
 }
 
 // the tensors of the three split entry points after their checks: DORY_GATMH, preallocated, a backward plan, `layer` the tensors' layer
@@ -1509,25 +1526,10 @@ int dory_gatmh_bwd_wire_do(dory_ctx *c, uint32_t layer, uint32_t *elem_bytes, ui
 }
 
 // ---- dory_gatmh_halo_bf16: the multi-head GAT under the rule of dory_halo_bf16_rows (halo_ships_bf16) -------------------------------
-int dory_gatmh_halo_bf16(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || c->gnn != DORY_GATMH || (on != 0 && on != 1))
-        return fail(c, DORY_ERR_ARG, "gatmh_halo_bf16: a context configured as DORY_GATMH; on is 0 or 1");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_halo_bf16: not while an epoch graph is being recorded");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange that may now ship the other element)
-    c->gatmh_halo_bf16.store(on, std::memory_order_release);
-    return DORY_OK;
-}
-
-int dory_gatmh_halo_bf16_stats(dory_ctx *c, uint64_t *fwd_bf16_exchanges, uint64_t *bwd_bf16_exchanges, uint64_t *bwd_bf16_rows,
-                               uint64_t *producer_packed_bf16) {
-    CHECK_CTX(c);
-    if (fwd_bf16_exchanges) *fwd_bf16_exchanges = c->gatmh_fwd_bf16_exchanges;
-    if (bwd_bf16_exchanges) *bwd_bf16_exchanges = c->gatmh_bwd_bf16_exchanges;
-    if (bwd_bf16_rows) *bwd_bf16_rows = c->gatmh_bwd_bf16_rows;
-    if (producer_packed_bf16) *producer_packed_bf16 = c->gatmh_producer_packed_bf16;
-    return DORY_OK;
+int dory_gatmh_halo_bf16(dory_ctx *c, int on) { return switch_set(c, SW_GATMH_HALO_BF16, on); }
+int dory_gatmh_halo_bf16_stats(dory_ctx *c, uint64_t *fwd_bf16_exchanges, uint64_t *bwd_bf16_exchanges, uint64_t *bwd_bf16_rows, uint64_t *producer_packed_bf16) {
+    uint64_t *const out[] = {fwd_bf16_exchanges, bwd_bf16_exchanges, bwd_bf16_rows, producer_packed_bf16};
+    return switch_stats(c, SW_GATMH_HALO_BF16, out, 4);
 }
 
 int dory_gatmh_bwd_pack(dory_ctx *c, uint32_t layer, float *send_buf) {
@@ -1562,22 +1564,10 @@ int dory_gatmh_bwd_unpack(dory_ctx *c, uint32_t layer, const float *recv_buf) {
 }
 
 // ---- bf16 halo rows: switch, counters, and the row an exchange puts on the wire (include/dorylus_hip.h) ------------------------
-int dory_halo_bf16_rows(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || (on != 0 && on != 1)) return fail(c, DORY_ERR_ARG, "halo_bf16_rows: dory_configure first; on is 0 or 1");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_bf16_rows: not while an epoch graph is being recorded");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange that may now ship bf16)
-    c->halo_bf16.store(on, std::memory_order_release);
-    return DORY_OK;
-}
-
+int dory_halo_bf16_rows(dory_ctx *c, int on) { return switch_set(c, SW_HALO_BF16_ROWS, on); }
 int dory_halo_bf16_rows_stats(dory_ctx *c, uint64_t *bf16_packs, uint64_t *bf16_bytes, uint64_t *fp32_packs_while_on) {
-    CHECK_CTX(c);
-    if (bf16_packs) *bf16_packs = c->halo_bf16_packs;
-    if (bf16_bytes) *bf16_bytes = c->halo_bf16_bytes;
-    if (fp32_packs_while_on) *fp32_packs_while_on = c->halo_fp32_packs_while_on;
-    return DORY_OK;
+    uint64_t *const out[] = {bf16_packs, bf16_bytes, fp32_packs_while_on};
+    return switch_stats(c, SW_HALO_BF16_ROWS, out, 3);
 }
 
 int dory_halo_wire_row(dory_ctx *c, uint32_t layer, int dir, uint32_t *elem_bytes, uint32_t *row_elems) {
@@ -1595,49 +1585,10 @@ int dory_halo_wire_row(dory_ctx *c, uint32_t layer, int dir, uint32_t *elem_byte
 }
 
 // ---- bf16 ghost twins: switch, counters, and a look at one tensor's twin (include/dorylus_hip.h) ---------------------------------
-int dory_halo_bf16_ghosts(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || !c->prealloc || (on != 0 && on != 1))
-        return fail(c, DORY_ERR_ARG, "halo_bf16_ghosts: dory_configure and dory_preallocate first (the twins of the tensors are allocated here); on is 0 or 1");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "halo_bf16_ghosts: not while an epoch graph is being recorded");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange of a direct plan that may now ship bf16)
-    if (on) {
-        c->halo_bf16_ghosts.store(1, std::memory_order_release);
-        return ghost_twins_alloc(c);
-    }
-    // off: a twin that holds the only current copy is widened first; nothing in flight reads a twin once both streams are idle
-    for (auto &m : c->tensors)
-        for (auto &kv : m) { int rc = ghost_fp32_current(c, &kv.second); if (rc) return rc; }
-    c->halo_bf16_ghosts.store(0, std::memory_order_release);
-    c->gatmh_bf16_ghosts.store(0, std::memory_order_release);   // (dory_gatmh_bf16_ghosts lives on top of this switch: its twins go with the others)
-    HIPCK(c, hipStreamSynchronize(c->comm));
-    HIPCK(c, hipStreamSynchronize(c->compute));
-    epoch_graph_drop_locked(c);   // (a recorded epoch may point at a twin)
-    for (auto &m : c->tensors)
-        for (auto &kv : m) {
-            Tensor &t = kv.second;
-            if (t.twin) (void)hipFree(t.twin);
-            t.twin = nullptr;
-            t.twin_state = DORY_GHOST_FP32;
-        }
-    return DORY_OK;
-}
-
-int dory_halo_bf16_ghosts_stats(dory_ctx *c, uint64_t *landed_direct, uint64_t *landed_by_kernel, uint64_t *conversions_skipped, uint64_t *widened,
-                                uint64_t *twin_bytes) {
-    CHECK_CTX(c);
-    if (landed_direct) *landed_direct = c->ghost_landed_direct;
-    if (landed_by_kernel) *landed_by_kernel = c->ghost_landed_by_kernel;
-    if (conversions_skipped) *conversions_skipped = c->ghost_conversions_skipped;
-    if (widened) *widened = c->ghost_widened;
-    if (twin_bytes) {
-        *twin_bytes = 0;
-        for (auto &m : c->tensors)
-            for (auto &kv : m)
-                if (kv.second.twin) *twin_bytes += kv.second.twin_bytes();
-    }
-    return DORY_OK;
+int dory_halo_bf16_ghosts(dory_ctx *c, int on) { return switch_set(c, SW_HALO_BF16_GHOSTS, on); }
+int dory_halo_bf16_ghosts_stats(dory_ctx *c, uint64_t *landed_direct, uint64_t *landed_by_kernel, uint64_t *conversions_skipped, uint64_t *widened, uint64_t *twin_bytes) {
+    uint64_t *const out[] = {landed_direct, landed_by_kernel, conversions_skipped, widened, twin_bytes};
+    return switch_stats(c, SW_HALO_BF16_GHOSTS, out, 5);
 }
 
 int dory_halo_bf16_ghost_peek(dory_ctx *c, uint32_t layer, const char *name, const void **twin, int *state) {
@@ -1651,47 +1602,25 @@ int dory_halo_bf16_ghost_peek(dory_ctx *c, uint32_t layer, const char *name, con
 }
 
 // ---- dory_gatmh_bf16_ghosts: twins for the multi-head GAT's fg_z and bg_do, on top of dory_halo_bf16_ghosts ------------------------
-int dory_gatmh_bf16_ghosts(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (!c->configured || c->gnn != DORY_GATMH) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: a context configured as DORY_GATMH");
-    if (!c->prealloc) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: dory_preallocate first (the twins of fg_z and bg_do are allocated here)");
-    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: on is 0 or 1");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: not while an epoch graph is being recorded");
-    if (!ghosts_on(c)) return fail(c, DORY_ERR_ARG, "gatmh_bf16_ghosts: dory_halo_bf16_ghosts is off (turn it on first: this switch lives on top of it)");
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
-    fused_stamp_drop(c);   // (the fused halo pack: rows a GEMM left for an exchange of a direct plan that may now ship the other element)
-    if (on) {
-        c->gatmh_bf16_ghosts.store(1, std::memory_order_release);
-        return ghost_twins_alloc(c);
-    }
-    // off: as dory_halo_bf16_ghosts(0) -- the only current copies widened first, nothing in flight, no recording that points at a twin
-    for (auto &m : c->tensors)
-        for (auto &kv : m) { int rc = ghost_fp32_current(c, &kv.second); if (rc) return rc; }
-    c->gatmh_bf16_ghosts.store(0, std::memory_order_release);
-    HIPCK(c, hipStreamSynchronize(c->comm));
-    HIPCK(c, hipStreamSynchronize(c->compute));
-    epoch_graph_drop_locked(c);
-    for (auto &m : c->tensors)
-        for (auto &kv : m) {
-            Tensor &t = kv.second;
-            if (t.twin) (void)hipFree(t.twin);
-            t.twin = nullptr;
-            t.twin_state = DORY_GHOST_FP32;
-        }
-    return DORY_OK;
-}
-
+int dory_gatmh_bf16_ghosts(dory_ctx *c, int on) { return switch_set(c, SW_GATMH_BF16_GHOSTS, on); }
 int dory_gatmh_bf16_ghosts_stats(dory_ctx *c, uint64_t *fwd_kept, uint64_t *bwd_kept, uint64_t *bwd_kept_merged, uint64_t *twin_reads_rows,
                                  uint64_t *twin_reads_sweep, uint64_t *scores_from_twin, uint64_t *widened) {
-    CHECK_CTX(c);
-    if (fwd_kept) *fwd_kept = c->gatmh_twin_fwd;
-    if (bwd_kept) *bwd_kept = c->gatmh_twin_bwd;
-    if (bwd_kept_merged) *bwd_kept_merged = c->gatmh_twin_bwd_merged;
-    if (twin_reads_rows) *twin_reads_rows = c->gatmh_twin_reads_rows;
-    if (twin_reads_sweep) *twin_reads_sweep = c->gatmh_twin_reads_sweep;
-    if (scores_from_twin) *scores_from_twin = c->gatmh_twin_scores;
-    if (widened) *widened = c->gatmh_twin_widened;
-    return DORY_OK;
+    uint64_t *const out[] = {fwd_kept, bwd_kept, bwd_kept_merged, twin_reads_rows, twin_reads_sweep, scores_from_twin, widened};
+    return switch_stats(c, SW_GATMH_BF16_GHOSTS, out, 7);
+}
+
+// ---- dory_gatmh_row_gather: the switch of the row-gather family (gat_mh_rows.hip) and its pass counters (include/dorylus_hip.h) ----
+int dory_gatmh_row_gather(dory_ctx *c, int mode) { return switch_set(c, SW_GATMH_ROW_GATHER, mode); }
+int dory_gatmh_row_gather_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *dst_rowwise, uint64_t *src) {
+    uint64_t *const out[] = {fwd, dst_edge_pass, dst_rowwise, src};
+    return switch_stats(c, SW_GATMH_ROW_GATHER, out, 4);
+}
+
+// ---- dory_gatmh_row_gather_bf16: option gatmh_bf16_gather reaches the row-gather family (its bf16 forms), and the passes that ran one ----
+int dory_gatmh_row_gather_bf16(dory_ctx *c, int on) { return switch_set(c, SW_GATMH_ROW_GATHER_BF16, on); }
+int dory_gatmh_row_gather_bf16_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src) {
+    uint64_t *const out[] = {fwd, dst_edge_pass, src};
+    return switch_stats(c, SW_GATMH_ROW_GATHER_BF16, out, 3);
 }
 
 // ---- scatter messages: the entry points (helpers above) ------------------------------------------------------------------

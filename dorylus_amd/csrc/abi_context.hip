@@ -145,7 +145,7 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
     GemmSend sd{};
     int send_dir = 0;
     const Tensor *sent = nullptr;
-    if (c->fused_pack && ta == 0) {
+    if (sw_on(c, SW_HALO_FUSED_PACK) && ta == 0) {
         if (C2 && fused_pack_target(c, C2, M, &sd, &send_dir)) { sent = C2; sd.which = 1; }
         else if (fused_pack_target(c, &C, M, &sd, &send_dir)) { sent = &C; sd.which = 0; }
     }

@@ -153,7 +153,7 @@ struct Bf16Rows {
         xg = !nghost ? nullptr : twin ? reinterpret_cast<const float *>(ghost_rows->twin)
                                       : reinterpret_cast<const float *>(c->bf16_rows + (size_t)c->N * rows.ld);
         from_twin = twin;
-        if (twin && !c->capturing) c->ghost_conversions_skipped++;
+        if (twin && !c->capturing) c->count[CNT_GHOST_CONVERSIONS_SKIPPED]++;
         return DORY_OK;
     }
     bool on() const { return c != nullptr; }
@@ -528,7 +528,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
         const BlockedAdj &Bf = gatmh_blocked_for(In, z->ld);
         // dory_gatmh_row_gather = 1: the row-gather family (gat_mh_rows.hip) in place of every other; 0: where a partitioned call
         // finds neither layout below
-        const bool rows_forced = c->gatmh_row_gather == 1;
+        const bool rows_forced = sw_value(c, SW_GATMH_ROW_GATHER) == 1;
         const bool blocked = !rows_forced && c->opt[OPT_GATMH_BLOCKED] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
                              (D % 4 == 0 || K == 1) &&
                              (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
@@ -544,7 +544,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                            shl != 0 && op && dpos && sweep_supported(sa, Sf, gatmh_sweep_group(z->ld));
         const bool bf16 = bfm >= 1;
         // dory_gatmh_row_gather_bf16: where this call takes the row-gather family below, its bf16 form runs instead of the refusal
-        const bool rows_bf16 = bf16 && c->gatmh_row_gather_bf16 == 1 && !sweep && !blocked && (rows_forced || c->numNodes > 1);
+        const bool rows_bf16 = bf16 && sw_on(c, SW_GATMH_ROW_GATHER_BF16) && !sweep && !blocked && (rows_forced || c->numNodes > 1);
         if (c->gatmh_fwd_rows_bf16.size() < c->L) c->gatmh_fwd_rows_bf16.resize(c->L, 0);
         if (bf16 && !sweep && !rows_bf16)
             return fail(c, DORY_ERR_ARG, "aggregate: gatmh_bf16_gather = %lld needs the sweep form of the forward pass, which this call would not take: %s",
@@ -569,7 +569,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                 if ((rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
                 c->gatmh_bf16_gathers_fwd++;
                 if (gs.sw.wide) c->gatmh_bf16_gathers_fwd_wide++;
-                if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_sweep++;
+                if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_SWEEP]++;
             }
             // dory_gatmh_bf16_ghosts: the fp32 form gathers fg_z's fp32 rows (the option was lowered after the exchange): widened first
             else if (In.ghosts && (rc = ghost_fp32_current(c, fgz))) return rc;
@@ -610,16 +610,16 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             Bf16Rows bf;
             int rc = rows_bf16 ? bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather") : In.ghosts ? ghost_fp32_current(c, fgz) : (int)DORY_OK;
             if (rc || (rc = wait_halo(c)) || (rc = bf.ghosts_landed())) return rc;
-            if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_rows++;
+            if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
             HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
                                                rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
                                                c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16));
             if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
-            c->gatmh_rows_fwd++;
+            c->count[CNT_GATMH_ROWS_FWD]++;
             if (rows_bf16) {
                 c->gatmh_fwd_rows_bf16[fl] = 1;
                 c->gatmh_bf16_gathers_fwd++;
-                c->gatmh_rows_bf16_fwd++;
+                c->count[CNT_GATMH_ROWS_BF16_FWD]++;
             }
         }
         else
@@ -686,7 +686,7 @@ static int gatmh_backward_sweep(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tens
             if ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed())) return rc;
             c->gatmh_bf16_gathers_src++;
             if (gs.sw.wide) c->gatmh_bf16_gathers_src_wide++;
-            if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_sweep++;
+            if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_SWEEP]++;
         }
         // dory_gatmh_bf16_ghosts: the fp32 form gathers bg_do's fp32 rows (gatmh_bwd_phase = 2 with the option lowered since the rows landed)
         else if (Out.ghosts && (rc = ghost_fp32_current(c, T.bgdo))) return rc;
@@ -753,19 +753,19 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
             Timed t(c, "loss", c->compute);
             HIPCK(c, launch_gatmh_dst_rowwise(c->N, K, D, ld, ldk, T.dO->d, T.o->d, op->d, dpos->d, T.er->d, T.m->d, T.den->d, T.tt->d, T.der->d,
                                               st4, lds4, c->compute));
-            c->gatmh_rows_dst_rowwise++;
+            c->count[CNT_GATMH_ROWS_DST_ROWWISE]++;
         } else {
             Timed t(c, "spmm", c->compute);
             Bf16Rows bf;
             if (dst_bf16 && ((rc = bf.begin(c, *T.z, T.fgz, In.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
             // (dory_gatmh_bf16_ghosts: the fp32 edge pass -- a layer whose forward swept, the option lowered since -- reads fg_z's fp32 rows)
             if (!dst_bf16 && In.ghosts && (rc = ghost_fp32_current(c, T.fgz))) return rc;
-            if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_rows++;
+            if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
             HIPCK(c, launch_gatmh_rows_dst(c->N, K, D, ld, ldk, In.ptr, In.idx, dst_bf16 ? bf.xl : T.z->d,
                                            dst_bf16 ? bf.xg : (In.ghosts ? T.fgz->d : nullptr), T.el->d, In.ghosts ? T.fgel->d : nullptr, T.er->d,
                                            c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, st4, lds4, c->compute, dst_bf16));
-            c->gatmh_rows_dst_edge++;
-            if (dst_bf16) c->gatmh_rows_bf16_dst_edge++;
+            c->count[CNT_GATMH_ROWS_DST_EDGE]++;
+            if (dst_bf16) c->count[CNT_GATMH_ROWS_BF16_DST_EDGE]++;
         }
     }
     if (T.phase == 1) return DORY_OK;
@@ -776,15 +776,15 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         Bf16Rows bf;
         if (src_bf16 && ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
         if (!src_bf16 && Out.ghosts && (rc = ghost_fp32_current(c, T.bgdo))) return rc;
-        if (bf.from_twin && !c->capturing) c->gatmh_twin_reads_rows++;
+        if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
         HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
                                        src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
                                        Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
                                        c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, src_bf16));
-        c->gatmh_rows_src++;
+        c->count[CNT_GATMH_ROWS_SRC]++;
         if (src_bf16) {
             c->gatmh_bf16_gathers_src++;
-            c->gatmh_rows_bf16_src++;
+            c->count[CNT_GATMH_ROWS_BF16_SRC]++;
         }
     }
     HIPCK(c, launch_gatmh_dattn(c->N, K, D, ld, ldk, T.z->d, T.del->d, T.der->d, c->wgrads[T.fl]["a_l"].d,
@@ -823,7 +823,7 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     // bf16 rows of do / bg_do for the source-side sweep (gatmh_bf16_gather = 2): refused, before anything is launched, where
     // the call would not take that sweep; the shadow buffer is sized here too (it cannot grow inside a recording)
     const bool bf16 = bfm >= 2;
-    const bool rows_forced = c->gatmh_row_gather == 1;
+    const bool rows_forced = sw_value(c, SW_GATMH_ROW_GATHER) == 1;
     const bool sweeps = !rows_forced && dst_rowwise && src_sweep;
     const BlockedAdj &Bbi = gatmh_blocked_for(In, z->ld), &Bbo = gatmh_blocked_for(Out, z->ld);
     const uint32_t nbmax = std::max(Bbi.nb, Bbo.nb);
@@ -835,7 +835,7 @@ static int aggregate_gatmh_backward(dory_ctx *c, uint32_t fl) {
     // layer's forward ran the family's bf16 form -- its scores have to be the forward's scores
     const bool rows = !sweeps && !blocked && (rows_forced || c->numNodes > 1);
     const bool rows_dst_rowwise = shl && op && dpos && fl < c->gatmh_fwd_swept.size() && c->gatmh_fwd_swept[fl] && ((z->ld >> 2) % (uint32_t)shl) == 0;
-    const bool rows_bf16 = rows && c->gatmh_row_gather_bf16 == 1;
+    const bool rows_bf16 = rows && sw_on(c, SW_GATMH_ROW_GATHER_BF16);
     const bool rows_src_bf16 = rows_bf16 && bf16;
     const bool rows_dst_bf16 = rows_bf16 && !rows_dst_rowwise && fl < c->gatmh_fwd_rows_bf16.size() && c->gatmh_fwd_rows_bf16[fl];
     if (bf16 && !sweeps && !rows_src_bf16)
@@ -961,7 +961,7 @@ static int aggregate_gat(dory_ctx *c, uint32_t fl, int dir) {
 // buffer too -- what gemm() (abi_context.hip) asks for a product, with the switch in front; the previous exchange has finished
 // reading the buffer before true comes back.  A one-column tensor (ld == 1) is left to the pack kernels, whatever the wire.
 static int rowwise_send_target(dory_ctx *c, const Tensor *out, uint32_t cols, GemmSend *sd, int *dir, bool *send) {
-    *send = c->fused_pack_rowwise && out->cols == cols && (out->ld & 3u) == 0 && fused_pack_target(c, out, c->N, sd, dir);
+    *send = sw_on(c, SW_HALO_FUSED_PACK_ROWWISE) && out->cols == cols && (out->ld & 3u) == 0 && fused_pack_target(c, out, c->N, sd, dir);
     if (!*send) return DORY_OK;
     sd->which = 0;
     sd->cols = cols;
@@ -987,45 +987,6 @@ int dory_aggregate(dory_ctx *c, uint32_t layer, int dir) {
     if (layer == 0 || layer > c->L) return fail(c, DORY_ERR_ARG, "aggregate GAT: layer %u out of range", layer);
     if (c->gnn != DORY_GATMH) return aggregate_gat(c, layer - 1, dir);
     return dir == DORY_FORWARD ? aggregate_gatmh_forward(c, layer - 1) : aggregate_gatmh_backward(c, layer - 1);
-}
-
-// ---- dory_gatmh_row_gather: the switch of the row-gather family (gat_mh_rows.hip) and its pass counters (include/dorylus_hip.h) ----
-int dory_gatmh_row_gather(dory_ctx *c, int mode) {
-    CHECK_CTX(c);
-    if (mode != 0 && mode != 1) return fail(c, DORY_ERR_ARG, "gatmh_row_gather: mode is 0 or 1");
-    if (mode == 1 && (!c->configured || c->gnn != DORY_GATMH))
-        return fail(c, DORY_ERR_ARG, "gatmh_row_gather: mode 1 needs a context configured as DORY_GATMH");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather: not while an epoch graph is being recorded");
-    c->gatmh_row_gather = mode;
-    return DORY_OK;
-}
-
-int dory_gatmh_row_gather_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *dst_rowwise, uint64_t *src) {
-    CHECK_CTX(c);
-    if (fwd) *fwd = c->gatmh_rows_fwd;
-    if (dst_edge_pass) *dst_edge_pass = c->gatmh_rows_dst_edge;
-    if (dst_rowwise) *dst_rowwise = c->gatmh_rows_dst_rowwise;
-    if (src) *src = c->gatmh_rows_src;
-    return DORY_OK;
-}
-
-// ---- dory_gatmh_row_gather_bf16: option gatmh_bf16_gather reaches the row-gather family (its bf16 forms), and the passes that ran one ----
-int dory_gatmh_row_gather_bf16(dory_ctx *c, int on) {
-    CHECK_CTX(c);
-    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16: on is 0 or 1");
-    if (on == 1 && (!c->configured || c->gnn != DORY_GATMH))
-        return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16: on = 1 needs a context configured as DORY_GATMH");
-    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16: not while an epoch graph is being recorded");
-    c->gatmh_row_gather_bf16 = on;
-    return DORY_OK;
-}
-
-int dory_gatmh_row_gather_bf16_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src) {
-    CHECK_CTX(c);
-    if (fwd) *fwd = c->gatmh_rows_bf16_fwd;
-    if (dst_edge_pass) *dst_edge_pass = c->gatmh_rows_bf16_dst_edge;
-    if (src) *src = c->gatmh_rows_bf16_src;
-    return DORY_OK;
 }
 
 int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {
@@ -1167,7 +1128,7 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
             if (fgz->twin && fgz->twin_state == DORY_GHOST_TWIN) {
                 HIPCK(c, launch_gatmh_scores_bf16(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->twin, fgz->ld, c->weights[l0]["a_l"].d,
                                                   c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
-                if (!c->capturing) c->gatmh_twin_scores++;
+                if (!c->capturing) c->count[CNT_GATMH_TWIN_SCORES]++;
                 return DORY_OK;
             }
             HIPCK(c, launch_gatmh_scores(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->d, fgz->ld, c->weights[l0]["a_l"].d,

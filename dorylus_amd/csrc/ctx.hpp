@@ -14,6 +14,7 @@
 
 #include "../../include/dorylus_hip.h"
 #include "options.hpp"
+#include "switches.hpp"
 #include "sweep_geometry.hpp"
 
 namespace dory {
@@ -284,17 +285,9 @@ struct dory_ctx {
     bool gat_ones_set = false;           // "ones"@0 filled
     bool last_spmm_unit = false;         // the last spmm() gathered with unit weights and a per-row factor (K1s / K1b), not with per-edge values (K1)
     std::vector<char> gatmh_fwd_swept;   // multi-head GAT: the forward of this layer left "op" / "dpos" (the sweep skeleton, or the row-gather family)
-    // dory_gatmh_row_gather: 0 = the row-gather family (gat_mh_rows.hip) where a partitioned aggregation would otherwise be refused,
-    // 1 = in place of every other family; the passes it ran (eager calls and recordings): forward, destination side as an edge pass /
-    // as the row-wise kernel on op and dpos, source side
-    int gatmh_row_gather = 0;
-    uint64_t gatmh_rows_fwd = 0, gatmh_rows_dst_edge = 0, gatmh_rows_dst_rowwise = 0, gatmh_rows_src = 0;
-    // dory_gatmh_row_gather_bf16: 1 = where the dispatch selects the row-gather family, option gatmh_bf16_gather runs its bf16 forms
-    // (8-byte gathers from the shadow rows) instead of being refused; per layer: this layer's forward ran the family's bf16 form (its
-    // m / den are statistics of rounded rows: the destination-side edge pass has to gather the same); the passes that ran a bf16 form
-    int gatmh_row_gather_bf16 = 0;
+    // dory_gatmh_row_gather_bf16, per layer: this layer's forward ran the row-gather family's bf16 form (its m / den are statistics
+    // of rounded rows: the destination-side edge pass has to gather the same)
     std::vector<char> gatmh_fwd_rows_bf16;
-    uint64_t gatmh_rows_bf16_fwd = 0, gatmh_rows_bf16_dst_edge = 0, gatmh_rows_bf16_src = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -341,45 +334,13 @@ struct dory_ctx {
     // landed in the ghost tensor itself / went through a receive buffer and an unpack
     std::atomic<int> halo_direct{0};
     uint64_t halo_direct_recvs = 0, halo_staged_recvs = 0;
-    // the fused halo pack (dory_halo_fused_pack; default off), its one stamp, and the eager exchanges counted while it is on
-    bool fused_pack = false;
+    // The feature switches (switches.hpp; all default 0) by SwitchId, read through sw_on / sw_value below -- atomics: the peers of the local
+    // transport read each other's without this context's lock -- the counters of their _stats entry points by CounterId, the fused pack's one stamp
+    std::atomic<int> sw[dory::SW_COUNT] = {};
+    uint64_t count[dory::CNT_COUNT] = {};
     dory::FusedStamp fused_stamp;
-    uint64_t fused_exchanges = 0, fused_rows = 0, fallback_exchanges = 0;
-    // ... and its bf16 form (dory_halo_fused_pack_bf16; default off): the epilogues round the rows of an exchange that ships bf16
-    bool fused_pack_bf16 = false;
-    uint64_t fused_bf16_exchanges = 0, fused_bf16_rows = 0;
-    // ... and its row-wise form (dory_halo_fused_pack_rowwise; default off): the send forms of tanh_backward, tanh_forward and the
-    // two softmax producers write the rows of g / h / grad that travel; the consumed stamps they made, counted
-    bool fused_pack_rowwise = false;
-    uint64_t rowwise_exchanges = 0, rowwise_rows = 0;
-    // dory_gatmh_bwd_merged_exchange (default off; a copy the peers of the local transport may read without this context's lock): the
-    // multi-head GAT's backward sweep ships [do | st] rows in one exchange; eager exchanges counted: merged ones, their send rows,
-    // those whose rows the producer wrote, backward passes that kept the two exchanges although the switch was on
-    std::atomic<int> gatmh_merged{0};
-    uint64_t merged_exchanges = 0, merged_rows = 0, merged_producer_packed = 0, merged_split_fallbacks = 0;
-    // bf16 halo rows (dory_halo_bf16_rows; default off) and the two gather modes its rule reads (option gcn_bf16_gather,
-    // dory_gat_bf16_gather's mode) -- copies the peers of the local transport may read without this context's lock -- and the
-    // eager packs counted: those that wrote bf16 rows, their bytes, those that wrote fp32 rows while the switch was on
-    std::atomic<int> halo_bf16{0}, gcn_bf16_mode{0}, gat_bf16_mode_pub{0};
-    // dory_gatmh_halo_bf16 (default off; on top of dory_halo_bf16_rows): the multi-head GAT ships z (gatmh_bf16_gather >= 1) and the
-    // backward sweep's do (== 2) as bf16; the option's mirror for the peers; eager exchanges counted: forward ones that shipped bf16,
-    // backward ones whose do shipped bf16, their send rows, those of them whose merged rows the producer wrote
-    std::atomic<int> gatmh_halo_bf16{0}, gatmh_bf16_mode_pub{0};
-    uint64_t gatmh_fwd_bf16_exchanges = 0, gatmh_bwd_bf16_exchanges = 0, gatmh_bwd_bf16_rows = 0, gatmh_producer_packed_bf16 = 0;
-    uint64_t halo_bf16_packs = 0, halo_bf16_bytes = 0, halo_fp32_packs_while_on = 0;
-    // bf16 ghost twins (dory_halo_bf16_ghosts; default off: a copy the peers of the local transport may read without this context's
-    // lock) and the eager calls counted: exchanges / unpacks whose bf16 rows landed in a twin itself, those a kernel copied into one,
-    // aggregations on bf16 rows that read a twin instead of converting the ghost rows, twins widened into their fp32 tensor for a reader
-    // of fp32 rows
-    std::atomic<int> halo_bf16_ghosts{0};
-    uint64_t ghost_landed_direct = 0, ghost_landed_by_kernel = 0, ghost_conversions_skipped = 0, ghost_widened = 0;
-    // dory_gatmh_bf16_ghosts (default off; on top of dory_halo_bf16_ghosts; a copy the peers of the local transport may read without this
-    // context's lock): fg_z and bg_do of the multi-head GAT have twins too; eager calls counted: forward exchanges / unpacks whose rows stayed
-    // in fg_z's twin, backward ones for bg_do (unmerged, merged), aggregations that read a twin instead of converting ghost rows (the
-    // row-gather family, the sweep forms), dory_apply_edge calls that formed fg_el / fg_er from a twin, widenings for a reader of fp32 rows
-    std::atomic<int> gatmh_bf16_ghosts{0};
-    uint64_t gatmh_twin_fwd = 0, gatmh_twin_bwd = 0, gatmh_twin_bwd_merged = 0, gatmh_twin_reads_rows = 0, gatmh_twin_reads_sweep = 0,
-             gatmh_twin_scores = 0, gatmh_twin_widened = 0;
+    // the gather modes the rule of dory_halo_bf16_rows reads (options gcn_bf16_gather / gatmh_bf16_gather, dory_gat_bf16_gather's mode); peers read them likewise
+    std::atomic<int> gcn_bf16_mode{0}, gat_bf16_mode_pub{0}, gatmh_bf16_mode_pub{0};
     dory::ScatterState scatter;  // scatter messages (dory_scatter_msgs_*) and the scatter transport
     void *nccl = nullptr;  // ncclComm_t
     // host transport (dory_comm_set_host_transport): callbacks + host staging
@@ -436,6 +397,10 @@ struct dory_ctx {
 };
 
 namespace dory {
+
+// the one way to read a feature switch: its value (dory_gatmh_row_gather's mode), or "is it on"
+inline int sw_value(const dory_ctx *c, SwitchId id) { return c->sw[id].load(std::memory_order_acquire); }
+inline bool sw_on(const dory_ctx *c, SwitchId id) { return sw_value(c, id) == 1; }
 
 // ---- kernel launchers (one translation unit per family) ---------------------
 // K1  CSR/CSC SpMM with fused self term:

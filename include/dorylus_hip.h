@@ -221,6 +221,14 @@ int dory_halo_unpack(dory_ctx *ctx, uint32_t layer, int dir, const float *recv_b
 int dory_halo_pack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int dir, float *send_buf);
 int dory_halo_unpack_tensor(dory_ctx *ctx, uint32_t layer, const char *name, int dir, const float *recv_buf);
 
+/* The feature switches of this header -- the ten entry points dory_<name>(ctx, int), each with a dory_<name>_stats beside it: the
+ * halo and ghost-twin switches of the sections below, from dory_halo_fused_pack to dory_gatmh_bf16_ghosts, and among them the
+ * row-gather pair dory_gatmh_row_gather / dory_gatmh_row_gather_bf16 -- are records of one table: dorylus_amd/host/switches.cpp, ids
+ * in dorylus_amd/csrc/switches.hpp.  A record holds the switch's values, its refusals in the order they are checked, whether a set
+ * waits for the halo in flight and drops the fused pack's stamp, and its counters; dory_switch_spec and dory_switch_check
+ * (dorylus_host.h) enumerate and ask it without a context.  All are off after dory_create.  (dory_gat_bf16_gather takes two values
+ * and dory_timing_enable is no feature: neither is in the table.) */
+
 /* ---- fused halo pack: the GEMM epilogues write the send rows (opt-in, default off; nothing in the reference: an MI355X-side
  * addition) ----
  * An exchange's pack kernel re-reads rows a GEMM wrote just before and sits in front of the link.  With the feature on, a K2 GEMM

@@ -171,6 +171,13 @@ int dory_option_spec(uint32_t index, const char **name, int *kind, int64_t *def,
  * DORY_OK, or DORY_ERR_ARG and the refusal in msg (n bytes).  "spmm_sweep_cus" is the exception: its range, 0..CUs per XCD, is
  * the device's and only the context checks it. */
 int dory_option_check(const char *name, int64_t value, int gnn, int configured, int has_graph, char *msg, size_t n);
+/* Switch introspection (tests, tools; no context needed): the table of the feature switches dory_<name>(ctx, int) of dorylus_hip.h --
+ * dorylus_amd/host/switches.cpp, dorylus_amd/csrc/switches.hpp.  dory_switch_spec: record `index` (0, 1, ... until DORY_ERR_ARG); any pointer
+ * may be NULL.  hi: the values are 0..hi.  refusals: how many its setter has.  waits_halo / drops_stamp: what a set does first.  parent: -1, or the
+ * index of the switch it lives on top of.  counters: the values dory_<name>_stats reports.  dory_switch_check: what dory_<name>(ctx, value) answers on a
+ * context of model gnn in that state -- DORY_OK, or DORY_ERR_ARG and in msg (n bytes) its setter's first refusal (a hook's refusal only a context knows). */
+int dory_switch_spec(uint32_t index, const char **name, int *hi, int *refusals, int *waits_halo, int *drops_stamp, int *parent, int *counters);
+int dory_switch_check(const char *name, int value, int gnn, int configured, int prealloc, int recording, int parent_on, char *msg, size_t n);
 
 #ifdef __cplusplus
 }
