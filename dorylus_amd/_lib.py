@@ -39,6 +39,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather", "dory_gatmh_row_gather_stats",
     "dory_gatmh_row_gather_bf16", "dory_gatmh_row_gather_bf16_stats",
     "dory_gatmh_bf16_ghosts", "dory_gatmh_bf16_ghosts_stats",
+    "dory_gatmh_row_gather_hub_split", "dory_gatmh_row_gather_hub_split_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -181,8 +182,11 @@ def load():
         "dory_gatmh_row_gather_bf16_stats": [vp] + [C.POINTER(u64)] * 3,
         "dory_gatmh_bf16_ghosts": [vp, i32],
         "dory_gatmh_bf16_ghosts_stats": [vp] + [C.POINTER(u64)] * 7,
+        "dory_gatmh_row_gather_hub_split": [vp, u32],
+        "dory_gatmh_row_gather_hub_split_stats": [vp] + [C.POINTER(u64)] * 7,
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
+        "dory_row_chunk_plan": [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), vp, vp, vp, vp, vp],
         "dory_partition_wire_order": [vp, vp, i32, vp, vp],
         "dory_sweep_geometry": [u32, u32, i32, i32, i32, u32, u32, u32, i32, vp],
         "dory_option_spec": [u32, C.POINTER(cp)] + [C.POINTER(t) for t in (i32, C.c_int64, C.c_int64, C.c_int64, i32, i32, i32)],
@@ -263,6 +267,24 @@ def halo_send_map(local_vtx_cnt, send_lists, lib=None):
     if rc != 0:
         raise DoryError(f"dory_halo_send_map failed ({rc}): {lib.dory_host_last_error().decode()}")
     return row_ptr, row_slots[:sl.size]
+
+
+def row_chunk_plan(ptr, chunk_entries, lib=None):
+    """The chunk plan of an adjacency's hub rows (dory_row_chunk_plan; no context, no GPU): ptr = the rows + 1 offsets of a CSR / CSC;
+    rows with more than chunk_entries entries are cut into consecutive chunks of chunk_entries entries, the last one shorter.
+    Returns (hub_rows, row_first_chunk[len(hub_rows) + 1], chunk_row, chunk_e0, chunk_e1)."""
+    lib = lib or load()
+    ptr = np.ascontiguousarray(ptr, np.uint64)
+    nr, nc = C.c_uint32(), C.c_uint32()
+    rc = lib.dory_row_chunk_plan(_ptr(ptr), ptr.size - 1, int(chunk_entries), C.byref(nr), C.byref(nc), None, None, None, None, None)
+    if rc != 0:
+        raise DoryError(f"dory_row_chunk_plan failed ({rc})")
+    rows, first = np.zeros(nr.value, np.uint32), np.zeros(nr.value + 1, np.uint32)
+    crow, e0, e1 = np.zeros(nc.value, np.uint32), np.zeros(nc.value, np.uint64), np.zeros(nc.value, np.uint64)
+    rc = lib.dory_row_chunk_plan(_ptr(ptr), ptr.size - 1, int(chunk_entries), None, None, _ptr(rows), _ptr(first), _ptr(crow), _ptr(e0), _ptr(e1))
+    if rc != 0:
+        raise DoryError(f"dory_row_chunk_plan failed ({rc})")
+    return rows, first, crow, e0, e1
 
 
 class Context:
@@ -714,6 +736,19 @@ class Context:
         the sweep forms that read a twin instead of converting ghost rows), scores_from_twin (dory_apply_edge), widened (for a reader
         of fp32 rows)"""
         return self._stats(self.lib.dory_gatmh_bf16_ghosts_stats, 7, self.GATMH_BF16_GHOSTS_STATS)
+
+    GATMH_HUB_SPLIT_STATS = ("fwd", "dst_edge_pass", "src", "in_hub_rows", "in_chunks", "out_hub_rows", "out_chunks")
+
+    def gatmh_row_gather_hub_split(self, chunk_entries):
+        """hub rows of the row-gather family run as chunks (dory_gatmh_row_gather_hub_split): 0 (default) = off; else a multiple of 64
+        in 64..2^20 -- a row with more adjacency entries than that is cut into consecutive chunks of that many, each on a lane group
+        of its own, and merged in chunk order (no atomics: same input, same bits); rows that are not cut keep their bits"""
+        self._ck(self.lib.dory_gatmh_row_gather_hub_split(self.h, int(chunk_entries)))
+
+    def gatmh_row_gather_hub_split_stats(self):
+        """dict: fwd / dst_edge_pass / src (passes that ran split since dory_create), in_hub_rows / in_chunks / out_hub_rows /
+        out_chunks (the current chunk plans of the in-edges and the out-edges)"""
+        return self._stats(self.lib.dory_gatmh_row_gather_hub_split_stats, 7, self.GATMH_HUB_SPLIT_STATS)
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

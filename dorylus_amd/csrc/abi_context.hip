@@ -211,6 +211,34 @@ bool tf_layer(dory_ctx *c, uint32_t layer) {
 }
 bool tf_active(dory_ctx *c) { return tf_layer(c, 0); }
 
+// dory_gatmh_row_gather_hub_split: the plan of one adjacency for the context's chunk size: built from the pointer array (read back from the device: the host copy is
+// the caller's), cached in the adjacency, dropped with it (free_graph) or when the chunk size changes
+int hub_plan_ensure(dory_ctx *c, Adjacency &A) {
+    if (A.hub_chunk == c->gatmh_hub_chunk) return DORY_OK;
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the hub rows' chunk plan would have to be built while recording (run one eager epoch first)");
+    LongRowsDev &L = A.hub_rows;
+    if (L.rows || L.row_chunk_ptr || L.chunks) HIPCK(c, hipDeviceSynchronize());   // (a launch in flight may still read the old plan)
+    for (void *p : {(void *)L.rows, (void *)L.row_chunk_ptr, (void *)L.chunks})
+        if (p) (void)hipFree(p);
+    L = LongRowsDev{};
+    A.hub_chunk = 0;
+    if (!c->gatmh_hub_chunk || !c->has_graph) return DORY_OK;
+    std::vector<uint64_t> ptr((size_t)c->N + 1);
+    HIPCK(c, hipMemcpy(ptr.data(), A.ptr, ptr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    LongRowsHost h;
+    plan_row_chunks(ptr.data(), c->N, c->gatmh_hub_chunk, 0, c->gatmh_hub_chunk, &h);
+    int rc;
+    if (!h.rows.empty()) {
+        if ((rc = upload_array(c, &L.rows, h.rows.data(), h.rows.size()))) return rc;
+        if ((rc = upload_array(c, &L.row_chunk_ptr, h.row_chunk_ptr.data(), h.row_chunk_ptr.size()))) return rc;
+        if ((rc = upload_array(c, &L.chunks, h.chunks.data(), h.chunks.size()))) return rc;
+    }
+    L.nrows = (uint32_t)h.rows.size();
+    L.nchunks = (uint32_t)(h.chunks.size() / 6);
+    A.hub_chunk = c->gatmh_hub_chunk;
+    return DORY_OK;
+}
+
 }  // namespace dory
 
 using namespace dory;
@@ -278,7 +306,7 @@ static void free_graph(dory_ctx *c) {
     for (Adjacency &A : c->adj) {
         for (void *p : {(void *)A.ptr, (void *)A.idx, (void *)A.val, (void *)A.order, (void *)A.split, (void *)A.edge_split.idx,
                         (void *)A.edge_split.val, (void *)A.edge_split.mid, (void *)A.long_rows.rows, (void *)A.long_rows.row_chunk_ptr,
-                        (void *)A.long_rows.chunks})
+                        (void *)A.long_rows.chunks, (void *)A.hub_rows.rows, (void *)A.hub_rows.row_chunk_ptr, (void *)A.hub_rows.chunks})
             if (p) (void)hipFree(p);
         for (BlockedAdj *B : {(BlockedAdj *)&A.blk, (BlockedAdj *)&A.blk16, (BlockedAdj *)&A.swp}) free_blocked(B);
         A = Adjacency{};   // every schedule, layout and flag of the direction at once
@@ -407,6 +435,40 @@ int dory_gat_bf16_gather_stats(dory_ctx *c, uint64_t *k1s, uint64_t *k1s_wide, u
     if (k1s_wide) *k1s_wide = c->gat_bf16_gathers_k1s_wide;
     if (k1) *k1 = c->gat_bf16_gathers_k1;
     if (fp32_fallbacks) *fp32_fallbacks = c->gat_bf16_fp32_fallbacks;
+    return DORY_OK;
+}
+
+// ---- dory_gatmh_row_gather_hub_split: hub rows of the row-gather family cut into chunks (gat_mh_rows.hip; include/dorylus_hip.h) ----
+int dory_gatmh_row_gather_hub_split(dory_ctx *c, uint32_t chunk_entries) {
+    CHECK_CTX(c);
+    if (chunk_entries && c->configured && c->gnn != DORY_GATMH)
+        return fail(c, DORY_ERR_ARG, "gatmh_row_gather_hub_split: this context is configured as %s; the feature serves the multi-head GAT (DORY_GATMH) only",
+                    c->gnn == DORY_GCN ? "DORY_GCN (K1 cuts its long rows itself)" : "DORY_GAT");
+    if (chunk_entries && ((chunk_entries & 63u) || chunk_entries > (1u << 20)))
+        return fail(c, DORY_ERR_ARG, "gatmh_row_gather_hub_split: chunk_entries %u is neither 0 nor a multiple of 64 in 64..1048576", chunk_entries);
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_hub_split: not while an epoch graph is being recorded");
+    if (chunk_entries != c->gatmh_hub_chunk) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->gatmh_hub_chunk = chunk_entries;
+    if (!c->has_graph) return DORY_OK;   // (before dory_graph_upload: the first aggregation plans)
+    for (Adjacency &A : c->adj) {
+        const int rc = hub_plan_ensure(c, A);
+        if (rc) return rc;
+    }
+    return DORY_OK;
+}
+
+int dory_gatmh_row_gather_hub_split_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src, uint64_t *in_hub_rows,
+                                          uint64_t *in_chunks, uint64_t *out_hub_rows, uint64_t *out_chunks) {
+    CHECK_CTX(c);
+    if (fwd) *fwd = c->gatmh_hub_fwd;
+    if (dst_edge_pass) *dst_edge_pass = c->gatmh_hub_dst;
+    if (src) *src = c->gatmh_hub_src;
+    const bool in = c->adj[ADJ_IN].hub_chunk && c->adj[ADJ_IN].hub_chunk == c->gatmh_hub_chunk;
+    const bool out = c->adj[ADJ_OUT].hub_chunk && c->adj[ADJ_OUT].hub_chunk == c->gatmh_hub_chunk;
+    if (in_hub_rows) *in_hub_rows = in ? c->adj[ADJ_IN].hub_rows.nrows : 0;
+    if (in_chunks) *in_chunks = in ? c->adj[ADJ_IN].hub_rows.nchunks : 0;
+    if (out_hub_rows) *out_hub_rows = out ? c->adj[ADJ_OUT].hub_rows.nrows : 0;
+    if (out_chunks) *out_chunks = out ? c->adj[ADJ_OUT].hub_rows.nchunks : 0;
     return DORY_OK;
 }
 

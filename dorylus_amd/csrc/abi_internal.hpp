@@ -85,6 +85,8 @@ Tensor *find(dory_ctx *c, uint32_t layer, const char *name);
 Tensor *findw(std::vector<std::map<std::string, Tensor>> &tab, uint32_t layer, const char *name);
 void free_table(std::vector<std::map<std::string, Tensor>> &tab);
 int ensure_scratch(dory_ctx *c, size_t bytes);
+// dory_gatmh_row_gather_hub_split: the adjacency's chunk plan for the context's chunk size, built if it is not the cached one (abi_context.hip)
+int hub_plan_ensure(dory_ctx *c, dory::Adjacency &A);
 // c->partial (K1b's partial rows, the sweeps' gate counters); `what` names it in the refusal inside a recording
 int ensure_partial(dory_ctx *c, size_t bytes, const char *what);
 int ensure_sweep(dory_ctx *c, Adjacency &A, int group);

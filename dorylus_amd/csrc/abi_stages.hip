@@ -505,6 +505,23 @@ struct GatmhSweep {
     }
 };
 
+// dory_gatmh_row_gather_hub_split: what a pass (0 forward, 1 destination-side edge pass, 2 source side) of the row-gather family over
+// adjacency A hands its launcher -- the adjacency's chunk plan (built here at first use) and scratch for the chunk states (the buffer only
+// ever grows: what a later kernel of the call was promised stays).  hubs->plan.nchunks == 0 -- the switch off, or no row over the
+// chunk size -- launches what it always launched.
+static int gatmh_hubs_for(dory_ctx *c, Adjacency &A, int pass, uint32_t ld, uint32_t ldk, GatmhHubs *hubs) {
+    *hubs = GatmhHubs{};
+    if (!c->gatmh_hub_chunk) return DORY_OK;
+    int rc = hub_plan_ensure(c, A);
+    if (rc || !A.hub_rows.nchunks) return rc;
+    const size_t need = (size_t)A.hub_rows.nchunks * gatmh_rows_hub_state_floats(pass, ld, ldk) * sizeof(float);
+    if ((rc = ensure_scratch(c, need))) return rc;
+    hubs->plan = A.hub_rows;
+    hubs->chunk = A.hub_chunk;
+    hubs->state = c->scratch;
+    return DORY_OK;
+}
+
 // The multi-head GAT extension: edge softmax + weighted sum.
 // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
 // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
@@ -611,9 +628,12 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             int rc = rows_bf16 ? bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather") : In.ghosts ? ghost_fp32_current(c, fgz) : (int)DORY_OK;
             if (rc || (rc = wait_halo(c)) || (rc = bf.ghosts_landed())) return rc;
             if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
+            GatmhHubs hubs;   // dory_gatmh_row_gather_hub_split: the hub rows of the in-edges, if any
+            if ((rc = gatmh_hubs_for(c, In, 0, z->ld, el->ld, &hubs))) return rc;
             HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
                                                rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
-                                               c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16));
+                                               c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16, &hubs));
+            if (hubs.plan.nchunks) c->gatmh_hub_fwd++;
             if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
             c->count[CNT_GATMH_ROWS_FWD]++;
             if (rows_bf16) {
@@ -761,9 +781,13 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
             // (dory_gatmh_bf16_ghosts: the fp32 edge pass -- a layer whose forward swept, the option lowered since -- reads fg_z's fp32 rows)
             if (!dst_bf16 && In.ghosts && (rc = ghost_fp32_current(c, T.fgz))) return rc;
             if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
+            GatmhHubs hubs;   // dory_gatmh_row_gather_hub_split: the hub rows of the in-edges, if any
+            if ((rc = gatmh_hubs_for(c, In, 1, ld, ldk, &hubs))) return rc;
             HIPCK(c, launch_gatmh_rows_dst(c->N, K, D, ld, ldk, In.ptr, In.idx, dst_bf16 ? bf.xl : T.z->d,
                                            dst_bf16 ? bf.xg : (In.ghosts ? T.fgz->d : nullptr), T.el->d, In.ghosts ? T.fgel->d : nullptr, T.er->d,
-                                           c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, st4, lds4, c->compute, dst_bf16));
+                                           c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, st4, lds4, c->compute, dst_bf16,
+                                           &hubs));
+            if (hubs.plan.nchunks) c->gatmh_hub_dst++;
             c->count[CNT_GATMH_ROWS_DST_EDGE]++;
             if (dst_bf16) c->count[CNT_GATMH_ROWS_BF16_DST_EDGE]++;
         }
@@ -777,10 +801,13 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         if (src_bf16 && ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
         if (!src_bf16 && Out.ghosts && (rc = ghost_fp32_current(c, T.bgdo))) return rc;
         if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
+        GatmhHubs hubs;   // dory_gatmh_row_gather_hub_split: the hub rows of the out-edges, if any (the merge has read the states before
+        if ((rc = gatmh_hubs_for(c, Out, 2, ld, ldk, &hubs))) return rc;   //  launch_gatmh_dattn below takes the scratch: one stream)
         HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
                                        src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
                                        Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
-                                       c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, src_bf16));
+                                       c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, src_bf16, &hubs));
+        if (hubs.plan.nchunks) c->gatmh_hub_src++;
         c->count[CNT_GATMH_ROWS_SRC]++;
         if (src_bf16) {
             c->gatmh_bf16_gathers_src++;

@@ -16,6 +16,7 @@
 #include "options.hpp"
 #include "switches.hpp"
 #include "sweep_geometry.hpp"
+#include "row_chunks.hpp"
 
 namespace dory {
 
@@ -174,11 +175,7 @@ struct BlockedAdj {
 constexpr uint32_t BLK_SEG_CLAMP = 2048, BLK_SEG_CHUNK = 4096;
 // K1's long rows (hubs): the part of a row beyond LONG_ROW_CLAMP edges, in chunks of LONG_ROW_CHUNK edges
 constexpr uint32_t LONG_ROW_CLAMP = 8192, LONG_ROW_CHUNK = 4096;
-struct LongRowsHost {                    // plan_long_rows output
-    std::vector<uint32_t> rows;          // long rows
-    std::vector<uint32_t> row_chunk_ptr; // rows+1: first chunk of each
-    std::vector<uint32_t> chunks;        // 6 words per chunk: row, 0, e0 (lo, hi), e1 (lo, hi)  (= struct LongChunk)
-};
+// (LongRowsHost, the output of plan_long_rows: row_chunks.hpp -- 6 words per chunk = struct LongChunk)
 // K1 beside an exchange in flight (round 6): every row's edges regrouped local sources first, ghost sources after (stable), so
 // that ONE pass over all rows sums the local part while the ghost rows are still travelling and a second pass adds the rest --
 // the row gather's counterpart of K1s's local-source blocks.  The interior / boundary ROW split it replaces hides nothing on
@@ -215,6 +212,10 @@ struct Adjacency {
     uint32_t *split = nullptr;   // N entries: interior rows, then boundary rows
     uint32_t n_interior = 0;
     LongRowsDev long_rows;       // K1: hub rows
+    // dory_gatmh_row_gather_hub_split: the rows with more than hub_chunk entries, whole, in chunks of hub_chunk entries (the row-gather
+    // family of the multi-head GAT; built by hub_plan_ensure when the value is set or at first use, dropped with the adjacency)
+    LongRowsDev hub_rows;
+    uint32_t hub_chunk = 0;      // the chunk size hub_rows was planned for (0: no plan)
     EdgeSplit edge_split;        // K1: local-first copy (GCN partitions with ghosts)
     DerivedAdj blk;              // K1b blocked copy; na: too many source blocks, use K1
     // multi-head GAT contexts with layers on both sides of 128 floats: a second copy, blocked for the 256-B slabs of the narrow
@@ -288,6 +289,9 @@ struct dory_ctx {
     // dory_gatmh_row_gather_bf16, per layer: this layer's forward ran the row-gather family's bf16 form (its m / den are statistics
     // of rounded rows: the destination-side edge pass has to gather the same)
     std::vector<char> gatmh_fwd_rows_bf16;
+    // dory_gatmh_row_gather_hub_split: entries per chunk (0 = off), and the forward / destination-side edge / source-side passes that ran split
+    uint32_t gatmh_hub_chunk = 0;
+    uint64_t gatmh_hub_fwd = 0, gatmh_hub_dst = 0, gatmh_hub_src = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -702,18 +706,30 @@ hipError_t launch_gatmh_src_sweep_finish(uint32_t N, uint32_t K, uint32_t D, uin
 // forward: o, m (the row's true maximum), den, op, dpos; dst: t, der, st4 (an edge pass; where op / dpos are current and
 // launch_gatmh_dst_rowwise covers the shape the caller runs that instead); src: del, dz with the finishing terms
 bool gatmh_rows_ok(uint32_t K, uint32_t D, uint32_t ld);
+// dory_gatmh_row_gather_hub_split: the hub rows of a launch -- the adjacency's chunk plan (Adjacency::hub_rows) and the scratch their
+// chunks leave their states in, nchunks x gatmh_rows_hub_state_floats(pass, ld, ldk) floats (pass 0 forward, 1 dst, 2 src).  With
+// hubs == nullptr or no chunk in the plan a launcher launches exactly what it launched before the feature.
+struct GatmhHubs {
+    LongRowsDev plan;
+    uint32_t chunk = 0;      // rows with more entries than this are the plan's rows
+    float *state = nullptr;
+};
+size_t gatmh_rows_hub_state_floats(int pass, uint32_t ld, uint32_t ldk);
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
-                                     hipStream_t s, bool bf16 = false /* z / zg: their shadow rows (launch_bf16_rows) */);
+                                     hipStream_t s, bool bf16 = false /* z / zg: their shadow rows (launch_bf16_rows) */,
+                                     const GatmhHubs *hubs = nullptr);
 hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                  const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
-                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16 = false /* z / zg: their shadow rows */);
+                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16 = false /* z / zg: their shadow rows */,
+                                 const GatmhHubs *hubs = nullptr);
 hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
-                                 float *del, float *dz, hipStream_t s, bool bf16 = false /* d_o / dog: their shadow rows */);
+                                 float *del, float *dz, hipStream_t s, bool bf16 = false /* d_o / dog: their shadow rows */,
+                                 const GatmhHubs *hubs = nullptr);
 // row-wise backward (single partition; feature-per-lane or (edge, head, piece)-per-lane kernels by shape)
 hipError_t launch_gatmh_backward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const uint64_t *rowptr, const uint32_t *colidx,

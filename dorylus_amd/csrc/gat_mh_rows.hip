@@ -39,9 +39,25 @@
 // fp32.  Known consequence: with ELFLY the forward's m / den come from scores of rounded rows while the source side takes el[u]
 // from the fp32 tensor -- its alpha differs from the forward's by the rounding of a score (include/dorylus_hip.h).
 //
-// Not taken here: a wide (16-byte) bf16 form, overlap of the interior rows with the exchange, and
-// HUB SPLITTING -- a row's edges are walked by its one lane group; cutting hub rows into chunks with merged (m, den, acc) states
-// matters for power-law partitions too large for the layouts and is left out.
+// Hub splitting (dory_gatmh_row_gather_hub_split(ctx, chunk); the *_hub_kernel / *_merge_kernel below).  A row's entries are walked by
+// its one lane group, four rows at a time: a destination with tens of thousands of in-edges is one serial chain.  With a chunk size
+// set, a row with MORE than `chunk` adjacency entries (edges; the self edge is not counted) is a hub row: the adjacency's plan
+// (row_chunks.hpp) cuts its entries into consecutive chunks of `chunk`, the last one shorter, and the self edge -- the last entry of
+// the id stream -- goes with the last chunk.  A split pass is two launches.  The first covers nchunks + N units: the chunk units
+// come first (the long work starts first), one lane group each, running the UNCHANGED per-entry arithmetic over their range and
+// leaving their state in a scratch slot; the row units follow and skip the hub rows -- every other row is computed by the
+// same body as without the feature, so it keeps its bits.  The second runs one lane group per hub row and folds the row's chunk states
+// in chunk order, then closes with the one-pass epilogue:
+//   forward   state (m_c, den_c, den+_c, acc_c, acc+_c), unnormalised;  M = max_c m_c;  f_c = exp(m_c - M);  den = sum_c f_c den_c
+//             (likewise den+, acc, acc+), then o = acc / den, op = acc+ / den, m = M (the row's TRUE maximum, exact), den, dpos = den+ / den
+//   dst       state (t_c, a1_c, a2_c) against the row's m / den: plain sums;  t, der = a1 - t a2, st = (er, m, 1 / den, t)
+//   src       state (S_c, S+_c, T_c, T+_c): plain sums, then del and dz as in the one-pass form
+// No atomics (chunk order is fixed: same input, same bits), no LDS, no gate or wait; 64-bit addressing; ghost ids as everywhere here.
+// A row that is split does NOT keep its one-pass bits (other association of the sums) except m.  With no hub row in the plan the
+// launchers launch exactly the kernels they launched before.  Measured (profiles/r28_gatmh_row_gather_hubs.txt): rank 0 of 8 of an
+// Amazon-size R-MAT graph, largest degree 101 152 -- 24-35 ms a pass one-pass, x0.05-0.15 of that at chunk 1 024; a uniform rank unchanged.
+//
+// Not taken here: a wide (16-byte) bf16 form and overlap of the interior rows with the exchange.
 #include "gat_mh.hpp"
 #include "spmm_common.hpp"
 
@@ -55,12 +71,10 @@ struct RowsLane {
     bool row_ok, lane_ok;
     uint32_t hk[HPQ];
     bool cm[4];
-    __device__ __forceinline__ RowsLane(const GatMhArgs &a) {
-        constexpr int RPW = 64 / GROUP, RPB = 4 * RPW;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        li = (uint32_t)(lane % GROUP);
-        const uint32_t rid = blockIdx.x * RPB + wave * RPW + lane / GROUP;
-        row_ok = rid < a.N;
+    // rid: the group's row where ok holds (a launch's units: rows_unit; a hub launch names rows through its plan)
+    __device__ __forceinline__ RowsLane(const GatMhArgs &a, uint32_t rid, bool ok) {
+        li = (uint32_t)((threadIdx.x & 63) % GROUP);
+        row_ok = ok;
         v = row_ok ? rid : 0;
         if constexpr (GROUP == 64) v = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);   // one row per wave: scalar row base
         nchunk = a.ld >> 2;
@@ -77,6 +91,58 @@ struct RowsLane {
         return lane_ok && (a.K == 1 ? li == 0 : (col % (a.D >> 2)) == 0);
     }
     __device__ __forceinline__ bool head_live(const GatMhArgs &a, int s) const { return lane_ok && (4 * col) / a.D + (uint32_t)s < a.K; }
+};
+// the unit of a launch a lane group works on: 4 waves of 64 / GROUP groups per workgroup
+template <int GROUP>
+__device__ __forceinline__ uint32_t rows_unit() {
+    constexpr int RPW = 64 / GROUP, RPB = 4 * RPW;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    return blockIdx.x * RPB + wave * RPW + lane / GROUP;
+}
+// the hub rows of a launch (GatmhHubs, ctx.hpp): nchunks chunk records of 6 words (row, 1 on the row's last chunk, e0, e1 as lo / hi),
+// nrows rows with their first chunks, and the chunk states -- one slot of rows_hub_stride floats per chunk
+struct RowsHubArgs {
+    uint32_t nchunks, nrows, chunk;
+    const uint32_t *chunks, *rows, *row_chunk_ptr;
+    float *state;
+};
+// floats of a chunk's slot: two rows of ld (16-byte aligned) and the per-head values in runs of ldk
+__host__ __device__ __forceinline__ size_t rows_hub_stride(int pass, uint32_t ld, uint32_t ldk) {
+    return ((size_t)(pass == 1 ? 0 : 2) * ld + (size_t)(pass == 0 ? 3 : pass == 1 ? 3 : 2) * ldk + 3) & ~(size_t)3;
+}
+// What a lane group of a launch does.  HUBS false: row = unit, all of it.  HUBS true: the first H.nchunks units are the chunks of the
+// hub rows (part: a range of the row's entries, the self edge with the last), the rest the rows, of which the hub rows are skipped.
+template <int GROUP, bool HUBS>
+struct RowsWork {
+    uint32_t row, slot;
+    bool ok, part, self;
+    uint64_t ce0, cend;
+    __device__ __forceinline__ RowsWork(const GatMhArgs &a, const RowsHubArgs &H) {
+        uint32_t unit = rows_unit<GROUP>();
+        part = false; self = true; slot = 0; ce0 = cend = 0;
+        if constexpr (HUBS) {
+            part = unit < H.nchunks;
+            if (part) {
+                const uint32_t *w = H.chunks + (size_t)6 * unit;
+                slot = unit; row = w[0]; ok = true; self = w[1] != 0;
+                ce0 = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+                cend = (uint64_t)w[4] | ((uint64_t)w[5] << 32);
+            } else unit -= H.nchunks;
+        }
+        if (!part) { ok = unit < a.N; row = ok ? unit : 0; }
+    }
+    // the group's entries: [e0, end) of idx, then -- total counts it -- the self edge; false: nothing to walk and nothing to store
+    template <class LANE>
+    __device__ __forceinline__ bool entries(const GatMhArgs &a, const LANE &L, const RowsHubArgs &H, uint64_t &e0, uint64_t &end,
+                                            uint64_t &total) const {
+        if constexpr (HUBS)
+            if (part) { e0 = ce0; end = cend; total = cend - ce0 + (self ? 1 : 0); return true; }
+        e0 = L.row_ok ? a.ptr[L.v] : 0; end = L.row_ok ? a.ptr[L.v + 1] : 0;
+        bool live = L.row_ok;
+        if constexpr (HUBS) live = live && end - e0 <= (uint64_t)H.chunk;     // (a hub row: its chunks and the merge kernel do it)
+        total = live ? end - e0 + 1 : 0;
+        return live;
+    }
 };
 template <int HPQ> __device__ __forceinline__ constexpr int rows_slot(int c) { return c * HPQ / 4; }   // the head slot of column c
 
@@ -176,14 +242,36 @@ struct RowsFwdState {
     }
 };
 
+// the one-pass epilogue: normalise and store o, op, m, den, dpos of row L.v (also the hub rows' merge kernel's)
+template <int GROUP, int HPQ>
+__device__ __forceinline__ void rows_fwd_store(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, const RowsFwdState<HPQ> &S, float *o, float *op,
+                                               float *m_out, float *den_out, float *dpos_out) {
+    if (!L.lane_ok) return;
+    float idn[HPQ];
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) idn[s] = 1.f / S.den[s];
+    const size_t oi = (size_t)L.v * L.nchunk + L.col;
+    reinterpret_cast<float4 *>(o)[oi] = rows_mask(rows_scale<HPQ>(idn, S.acc), L.cm);
+    reinterpret_cast<float4 *>(op)[oi] = rows_mask(rows_scale<HPQ>(idn, S.accp), L.cm);
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s)
+        if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+            const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
+            m_out[vk] = S.mx[s];
+            den_out[vk] = S.den[s];
+            dpos_out[vk] = S.denp[s] * idn[s];
+        }
+}
+
 // CHUNK: what a lane gathers of a row -- float4 (fp32 rows), or uint2 (four bf16 of the shadow rows, launch_bf16_rows, widened
 // exactly by row_chunk).  Everything after the load is the same arithmetic in the same order, so a bf16 kernel gives its fp32
 // sibling's bits on rows that were rounded beforehand; the bodies below are shared by both, the __global__ kernels only name them.
-template <int GROUP, int HPQ, bool ELFLY, class CHUNK>
+template <int GROUP, int HPQ, bool ELFLY, bool HUBS, class CHUNK>
 __device__ __forceinline__ void gatmh_rows_forward_body(const GatMhArgs &a, int HL, const CHUNK *z4, const CHUNK *zg4, const float *el,
                                                         const float *elg, const float *er, const float *a_l, float *o, float *op,
-                                                        float *m_out, float *den_out, float *dpos_out) {
-    const RowsLane<GROUP, HPQ> L(a);
+                                                        float *m_out, float *den_out, float *dpos_out, const RowsHubArgs &H) {
+    const RowsWork<GROUP, HUBS> W(a, H);
+    const RowsLane<GROUP, HPQ> L(a, W.row, W.ok);
     const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
     RowsFwdState<HPQ> S;
 #pragma unroll
@@ -195,8 +283,8 @@ __device__ __forceinline__ void gatmh_rows_forward_body(const GatMhArgs &a, int 
     S.acc = S.accp = make_float4(0.f, 0.f, 0.f, 0.f);
     // the row's entries: its in-edges, then the self edge (id v, a local row like any other); batches of four, the dead slots of the
     // last batch gather the last entry's row again and are masked by a score of -inf (alpha = exp(-inf) = 0)
-    const uint64_t e0 = L.row_ok ? a.ptr[L.v] : 0, end = L.row_ok ? a.ptr[L.v + 1] : 0;
-    const uint64_t total = L.row_ok ? end - e0 + 1 : 0;
+    uint64_t e0, end, total;
+    const bool live = W.entries(a, L, H, e0, end, total);
     for (uint64_t done = 0; done < total; done += GROUP) {                     // GROUP == 64: wave-uniform
         const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
         const uint64_t ee = e0 + done + L.li;
@@ -226,29 +314,80 @@ __device__ __forceinline__ void gatmh_rows_forward_body(const GatMhArgs &a, int 
             S.template step<4>(x, sc);
         }
     }
-    if (!L.row_ok) return;
-    if (!L.lane_ok) return;
-    float idn[HPQ];
+    if (!live) return;
+    if constexpr (HUBS)
+        if (W.part) {   // a chunk of a hub row: its unnormalised state, for gatmh_rows_forward_merge_kernel
+            if (L.li >= L.nchunk) return;
+            float *sp = H.state + (size_t)W.slot * rows_hub_stride(0, a.ld, a.ldk), *hp = sp + 2 * (size_t)a.ld;
+            reinterpret_cast<float4 *>(sp)[L.col] = S.acc;
+            reinterpret_cast<float4 *>(sp + a.ld)[L.col] = S.accp;
 #pragma unroll
-    for (int s = 0; s < HPQ; ++s) idn[s] = 1.f / S.den[s];
-    const size_t oi = (size_t)L.v * L.nchunk + L.col;
-    reinterpret_cast<float4 *>(o)[oi] = rows_mask(rows_scale<HPQ>(idn, S.acc), L.cm);
-    reinterpret_cast<float4 *>(op)[oi] = rows_mask(rows_scale<HPQ>(idn, S.accp), L.cm);
-#pragma unroll
-    for (int s = 0; s < HPQ; ++s)
-        if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
-            const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
-            m_out[vk] = S.mx[s];
-            den_out[vk] = S.den[s];
-            dpos_out[vk] = S.denp[s] * idn[s];
+            for (int s = 0; s < HPQ; ++s)
+                if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+                    hp[L.hk[s]] = S.mx[s];
+                    hp[a.ldk + L.hk[s]] = S.den[s];
+                    hp[2 * a.ldk + L.hk[s]] = S.denp[s];
+                }
+            return;
         }
+    rows_fwd_store(L, a, S, o, op, m_out, den_out, dpos_out);
 }
 template <int GROUP, int HPQ, bool ELFLY>
 __global__ __launch_bounds__(256) void gatmh_rows_forward_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
                                                                  const float *elg, const float *er, const float *a_l, float *o, float *op,
                                                                  float *m_out, float *den_out, float *dpos_out) {
-    gatmh_rows_forward_body<GROUP, HPQ, ELFLY>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
-                                               a_l, o, op, m_out, den_out, dpos_out);
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
+                                                      a_l, o, op, m_out, den_out, dpos_out, RowsHubArgs{});
+}
+// the launch of a split pass: the hub rows' chunks, then the rows that are no hub rows (RowsWork)
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_hub_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                                     const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                                     float *m_out, float *den_out, float *dpos_out, RowsHubArgs H) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
+                                                     a_l, o, op, m_out, den_out, dpos_out, H);
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_hub_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
+                                                                          const float *elg, const float *er, const float *a_l, float *o,
+                                                                          float *op, float *m_out, float *den_out, float *dpos_out,
+                                                                          RowsHubArgs H) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, H);
+}
+// one lane group per hub row: the chunk states folded in chunk order against the maximum of the chunk maxima (exp(m_c - M) <= 1: chunks
+// whose maxima lie far apart merge to a factor of zero, never to Inf or NaN -- every chunk has an entry, so every m_c is finite)
+template <int GROUP, int HPQ>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_merge_kernel(GatMhArgs a, float *o, float *op, float *m_out, float *den_out,
+                                                                       float *dpos_out, RowsHubArgs H) {
+    const uint32_t h = rows_unit<GROUP>();
+    const bool ok = h < H.nrows;
+    const RowsLane<GROUP, HPQ> L(a, ok ? H.rows[h] : 0, ok);
+    if (!L.row_ok) return;
+    const uint32_t c0 = H.row_chunk_ptr[h], c1 = H.row_chunk_ptr[h + 1];
+    const size_t stride = rows_hub_stride(0, a.ld, a.ldk);
+    RowsFwdState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        S.mx[s] = -INFINITY;
+        S.den[s] = S.denp[s] = 0.f;
+    }
+    S.acc = S.accp = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (uint32_t c = c0; c < c1; ++c)
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) S.mx[s] = fmaxf(S.mx[s], H.state[c * stride + 2 * (size_t)a.ld + L.hk[s]]);
+    for (uint32_t c = c0; c < c1; ++c) {
+        const float *sp = H.state + c * stride, *hp = sp + 2 * (size_t)a.ld;
+        float f[HPQ];
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) {
+            f[s] = __expf(hp[L.hk[s]] - S.mx[s]);
+            S.den[s] = fmaf(f[s], hp[a.ldk + L.hk[s]], S.den[s]);
+            S.denp[s] = fmaf(f[s], hp[2 * a.ldk + L.hk[s]], S.denp[s]);
+        }
+        S.acc = rows_axpy<HPQ>(f, reinterpret_cast<const float4 *>(sp)[L.col], S.acc);
+        S.accp = rows_axpy<HPQ>(f, reinterpret_cast<const float4 *>(sp + a.ld)[L.col], S.accp);
+    }
+    rows_fwd_store(L, a, S, o, op, m_out, den_out, dpos_out);
 }
 // zb / zgb: the shadow rows of z / fg_z (ld bf16 per row, one 8-byte load per lane and edge: a 64-float row is one 128-byte line).
 // Where ELFLY holds the sources' scores come from the gathered, rounded row -- what the sibling does when handed rounded rows;
@@ -257,7 +396,7 @@ template <int GROUP, int HPQ, bool ELFLY>
 __global__ __launch_bounds__(256) void gatmh_rows_forward_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
                                                                       const float *elg, const float *er, const float *a_l, float *o,
                                                                       float *op, float *m_out, float *den_out, float *dpos_out) {
-    gatmh_rows_forward_body<GROUP, HPQ, ELFLY>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out);
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, RowsHubArgs{});
 }
 
 // ---- backward, destination side: t[v,k] = sum a*da, der[v,k] = sum a*da*l' - t * sum a*l', st = (er, m, 1/den, t) -------------------
@@ -287,12 +426,27 @@ struct RowsDstState {
     }
 };
 
-template <int GROUP, int HPQ, bool ELFLY, class CHUNK>
+// the one-pass epilogue of the destination side: t, der, st of row L.v (also the hub rows' merge kernel's)
+template <int GROUP, int HPQ>
+__device__ __forceinline__ void rows_dst_store(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, const RowsDstState<HPQ> &S, float *t_out,
+                                               float *der_out, float4 *st4, uint32_t lds4) {
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s)
+        if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+            const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
+            t_out[vk] = S.t[s];
+            der_out[vk] = S.a1[s] - S.t[s] * S.a2[s];
+            st4[(size_t)L.v * lds4 + L.hk[s]] = make_float4(S.erv[s], S.mv[s], S.idn[s], S.t[s]);
+        }
+}
+
+template <int GROUP, int HPQ, bool ELFLY, bool HUBS, class CHUNK>
 __device__ __forceinline__ void gatmh_rows_dst_body(const GatMhArgs &a, int HL, const CHUNK *z4, const CHUNK *zg4, const float *el,
                                                     const float *elg, const float *er, const float *a_l, const float *m_in,
                                                     const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
-                                                    uint32_t lds4) {
-    const RowsLane<GROUP, HPQ> L(a);
+                                                    uint32_t lds4, const RowsHubArgs &H) {
+    const RowsWork<GROUP, HUBS> W(a, H);
+    const RowsLane<GROUP, HPQ> L(a, W.row, W.ok);
     const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
     RowsDstState<HPQ> S;
 #pragma unroll
@@ -306,8 +460,8 @@ __device__ __forceinline__ void gatmh_rows_dst_body(const GatMhArgs &a, int HL, 
     S.g = rows_mask(reinterpret_cast<const float4 *>(d_o)[(size_t)L.v * L.nchunk + L.col], L.cm);
     // the row's entries: its in-edges, then the self edge (id v, a local row like any other); batches of four, the dead slots of the
     // last batch gather the last entry's row again and are masked by a score of -inf (alpha = exp(-inf) = 0)
-    const uint64_t e0 = L.row_ok ? a.ptr[L.v] : 0, end = L.row_ok ? a.ptr[L.v + 1] : 0;
-    const uint64_t total = L.row_ok ? end - e0 + 1 : 0;
+    uint64_t e0, end, total;
+    const bool live = W.entries(a, L, H, e0, end, total);
     for (uint64_t done = 0; done < total; done += GROUP) {                     // GROUP == 64: wave-uniform
         const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
         const uint64_t ee = e0 + done + L.li;
@@ -337,23 +491,73 @@ __device__ __forceinline__ void gatmh_rows_dst_body(const GatMhArgs &a, int HL, 
             S.template step<4>(x, sc, HL);
         }
     }
-    if (!L.row_ok) return;
+    if (!live) return;
+    if constexpr (HUBS)
+        if (W.part) {   // a chunk of a hub row: its partial (t, a1, a2) against the row's m / den, for gatmh_rows_dst_merge_kernel
+            float *hp = H.state + (size_t)W.slot * rows_hub_stride(1, a.ld, a.ldk);
 #pragma unroll
-    for (int s = 0; s < HPQ; ++s)
-        if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
-            const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
-            t_out[vk] = S.t[s];
-            der_out[vk] = S.a1[s] - S.t[s] * S.a2[s];
-            st4[(size_t)L.v * lds4 + L.hk[s]] = make_float4(S.erv[s], S.mv[s], S.idn[s], S.t[s]);
+            for (int s = 0; s < HPQ; ++s)
+                if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+                    hp[L.hk[s]] = S.t[s];
+                    hp[a.ldk + L.hk[s]] = S.a1[s];
+                    hp[2 * a.ldk + L.hk[s]] = S.a2[s];
+                }
+            return;
         }
+    rows_dst_store(L, a, S, t_out, der_out, st4, lds4);
 }
 template <int GROUP, int HPQ, bool ELFLY>
 __global__ __launch_bounds__(256) void gatmh_rows_dst_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
                                                              const float *elg, const float *er, const float *a_l, const float *m_in,
                                                              const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
                                                              uint32_t lds4) {
-    gatmh_rows_dst_body<GROUP, HPQ, ELFLY>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
-                                           m_in, den_in, d_o, t_out, der_out, st4, lds4);
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
+                                                  m_in, den_in, d_o, t_out, der_out, st4, lds4, RowsHubArgs{});
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_dst_hub_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                                 const float *elg, const float *er, const float *a_l, const float *m_in,
+                                                                 const float *den_in, const float *d_o, float *t_out, float *der_out,
+                                                                 float4 *st4, uint32_t lds4, RowsHubArgs H) {
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, true>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
+                                                 m_in, den_in, d_o, t_out, der_out, st4, lds4, H);
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_dst_hub_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
+                                                                      const float *elg, const float *er, const float *a_l, const float *m_in,
+                                                                      const float *den_in, const float *d_o, float *t_out, float *der_out,
+                                                                      float4 *st4, uint32_t lds4, RowsHubArgs H) {
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, true>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4, H);
+}
+// one lane group per hub row: the chunks' (t, a1, a2) added in chunk order, then the one-pass epilogue
+template <int GROUP, int HPQ>
+__global__ __launch_bounds__(256) void gatmh_rows_dst_merge_kernel(GatMhArgs a, const float *er, const float *m_in, const float *den_in,
+                                                                   float *t_out, float *der_out, float4 *st4, uint32_t lds4, RowsHubArgs H) {
+    const uint32_t h = rows_unit<GROUP>();
+    const bool ok = h < H.nrows;
+    const RowsLane<GROUP, HPQ> L(a, ok ? H.rows[h] : 0, ok);
+    if (!L.row_ok) return;
+    const uint32_t c0 = H.row_chunk_ptr[h], c1 = H.row_chunk_ptr[h + 1];
+    const size_t stride = rows_hub_stride(1, a.ld, a.ldk);
+    RowsDstState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        const size_t vk = (size_t)L.v * a.ldk + L.hk[s];
+        S.erv[s] = er[vk];
+        S.mv[s] = m_in[vk];
+        S.idn[s] = 1.f / den_in[vk];
+        S.t[s] = S.a1[s] = S.a2[s] = 0.f;
+    }
+    for (uint32_t c = c0; c < c1; ++c) {
+        const float *hp = H.state + c * stride;
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) {
+            S.t[s] += hp[L.hk[s]];
+            S.a1[s] += hp[a.ldk + L.hk[s]];
+            S.a2[s] += hp[2 * a.ldk + L.hk[s]];
+        }
+    }
+    rows_dst_store(L, a, S, t_out, der_out, st4, lds4);
 }
 // the edge pass of a layer whose forward ran gatmh_rows_forward_bf16_kernel: the same rounded rows, hence the forward's scores
 // (m / den are statistics of those); d_o, m, den and er stay fp32
@@ -362,7 +566,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_bf16_kernel(GatMhArgs a, i
                                                                   const float *elg, const float *er, const float *a_l, const float *m_in,
                                                                   const float *den_in, const float *d_o, float *t_out, float *der_out,
                                                                   float4 *st4, uint32_t lds4) {
-    gatmh_rows_dst_body<GROUP, HPQ, ELFLY>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4);
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, false>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4, RowsHubArgs{});
 }
 
 // ---- backward, source side: rows = sources u (out-edges), entries = destinations v (local: do / st, ghost: bg_do / bg_st) ---------
@@ -393,46 +597,11 @@ struct RowsSrcState {
 // NB: destination rows in flight per group.  Four; the instantiations with four heads per lane (D == 1) keep two -- a batch holds
 // NB x HPQ statistics records of four registers each: 64 registers at NB = 4, 32 more than in the two-row form, which takes 111
 // in all -- past the 128 that leave four waves per SIMD (what a latency-bound gather lives on; tests/test_gatmh_row_gather_resources.py)
-template <int GROUP, int HPQ, int NB, class CHUNK>
-__device__ __forceinline__ void gatmh_rows_src_body(const GatMhArgs &a, int HL, const float *z, const float *el, const CHUNK *d4,
-                                                    const CHUNK *dg4, const float4 *st4, const float4 *stg, uint32_t lds4, const float *der,
-                                                    const float *a_l, const float *a_r, float *del_out, float *dz) {
-    const RowsLane<GROUP, HPQ> L(a);
-    RowsSrcState<HPQ> S;
-#pragma unroll
-    for (int s = 0; s < HPQ; ++s) {
-        S.elu[s] = el[(size_t)L.v * a.ldk + L.hk[s]];
-        S.T[s] = S.Tp[s] = 0.f;
-    }
-    S.S = S.Sp = make_float4(0.f, 0.f, 0.f, 0.f);
-    // the row's entries: its out-edges, then the self edge (id u); batches of NB, the dead slots of the last batch masked by a
-    // destination score of -inf (alpha = exp(-inf) = 0)
-    const uint64_t e0 = L.row_ok ? a.ptr[L.v] : 0, end = L.row_ok ? a.ptr[L.v + 1] : 0;
-    const uint64_t total = L.row_ok ? end - e0 + 1 : 0;
-    for (uint64_t done = 0; done < total; done += GROUP) {
-        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
-        const uint64_t ee = e0 + done + L.li;
-        const uint32_t my_idx = ee < end ? a.idx[ee] : L.v;
-        for (int j = 0; j < n; j += NB) {
-            float4 x[NB], rec[NB][HPQ];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
-                const bool loc = s < a.N;
-                const size_t r = loc ? s : s - a.N;
-                x[u] = row_chunk((loc ? d4 : dg4)[r * L.nchunk + L.col]);
-                const float4 *sp = (loc ? st4 : stg) + r * lds4;
-#pragma unroll
-                for (int h = 0; h < HPQ; ++h) rec[u][h] = sp[L.hk[h]];
-            }
-#pragma unroll
-            for (int u = 1; u < NB; ++u)
-#pragma unroll
-                for (int h = 0; h < HPQ; ++h) rec[u][h].x = j + u < n ? rec[u][h].x : -INFINITY;
-            S.template step<NB>(x, rec);
-        }
-    }
-    if (!L.row_ok) return;
+// the one-pass closing arithmetic of the source side: del and dz of row L.v from its sums (also the hub rows' merge kernel's; every
+// lane of a live group arrives: the head's lanes reduce the dot product)
+template <int GROUP, int HPQ>
+__device__ __forceinline__ void rows_src_close(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, int HL, const RowsSrcState<HPQ> &S, const float *z,
+                                               const float *der, const float *a_l, const float *a_r, float *del_out, float *dz) {
     // del[u,k] = <Z[u,k,:], 0.2 S + 0.8 S+> - (0.2 T + 0.8 T+)
     const float lo = GATMH_SLOPE, hi = 1.f - GATMH_SLOPE;
     const float4 zz = rows_mask(reinterpret_cast<const float4 *>(z)[(size_t)L.v * L.nchunk + L.col], L.cm);
@@ -464,13 +633,113 @@ __device__ __forceinline__ void gatmh_rows_src_body(const GatMhArgs &a, int HL, 
     for (int s = 0; s < HPQ; ++s)
         if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) del_out[(size_t)L.v * a.ldk + L.hk[s]] = del[s];
 }
+
+template <int GROUP, int HPQ, int NB, bool HUBS, class CHUNK>
+__device__ __forceinline__ void gatmh_rows_src_body(const GatMhArgs &a, int HL, const float *z, const float *el, const CHUNK *d4,
+                                                    const CHUNK *dg4, const float4 *st4, const float4 *stg, uint32_t lds4, const float *der,
+                                                    const float *a_l, const float *a_r, float *del_out, float *dz, const RowsHubArgs &H) {
+    const RowsWork<GROUP, HUBS> W(a, H);
+    const RowsLane<GROUP, HPQ> L(a, W.row, W.ok);
+    RowsSrcState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        S.elu[s] = el[(size_t)L.v * a.ldk + L.hk[s]];
+        S.T[s] = S.Tp[s] = 0.f;
+    }
+    S.S = S.Sp = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the row's entries: its out-edges, then the self edge (id u); batches of NB, the dead slots of the last batch masked by a
+    // destination score of -inf (alpha = exp(-inf) = 0)
+    uint64_t e0, end, total;
+    const bool live = W.entries(a, L, H, e0, end, total);
+    for (uint64_t done = 0; done < total; done += GROUP) {
+        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+        const uint64_t ee = e0 + done + L.li;
+        const uint32_t my_idx = ee < end ? a.idx[ee] : L.v;
+        for (int j = 0; j < n; j += NB) {
+            float4 x[NB], rec[NB][HPQ];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                const bool loc = s < a.N;
+                const size_t r = loc ? s : s - a.N;
+                x[u] = row_chunk((loc ? d4 : dg4)[r * L.nchunk + L.col]);
+                const float4 *sp = (loc ? st4 : stg) + r * lds4;
+#pragma unroll
+                for (int h = 0; h < HPQ; ++h) rec[u][h] = sp[L.hk[h]];
+            }
+#pragma unroll
+            for (int u = 1; u < NB; ++u)
+#pragma unroll
+                for (int h = 0; h < HPQ; ++h) rec[u][h].x = j + u < n ? rec[u][h].x : -INFINITY;
+            S.template step<NB>(x, rec);
+        }
+    }
+    if (!live) return;
+    if constexpr (HUBS)
+        if (W.part) {   // a chunk of a hub row: its partial sums, for gatmh_rows_src_merge_kernel
+            if (L.li >= L.nchunk) return;
+            float *sp = H.state + (size_t)W.slot * rows_hub_stride(2, a.ld, a.ldk), *hp = sp + 2 * (size_t)a.ld;
+            reinterpret_cast<float4 *>(sp)[L.col] = S.S;
+            reinterpret_cast<float4 *>(sp + a.ld)[L.col] = S.Sp;
+#pragma unroll
+            for (int s = 0; s < HPQ; ++s)
+                if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+                    hp[L.hk[s]] = S.T[s];
+                    hp[a.ldk + L.hk[s]] = S.Tp[s];
+                }
+            return;
+        }
+    rows_src_close(L, a, HL, S, z, der, a_l, a_r, del_out, dz);
+}
 template <int GROUP, int HPQ, int NB>
 __global__ __launch_bounds__(256) void gatmh_rows_src_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
                                                              const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
                                                              const float *der, const float *a_l, const float *a_r, float *del_out,
                                                              float *dz) {
-    gatmh_rows_src_body<GROUP, HPQ, NB>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
-                                        lds4, der, a_l, a_r, del_out, dz);
+    gatmh_rows_src_body<GROUP, HPQ, NB, false>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
+                                               lds4, der, a_l, a_r, del_out, dz, RowsHubArgs{});
+}
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_hub_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
+                                                                 const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                 const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                 float *dz, RowsHubArgs H) {
+    gatmh_rows_src_body<GROUP, HPQ, NB, true>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
+                                              lds4, der, a_l, a_r, del_out, dz, H);
+}
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_hub_bf16_kernel(GatMhArgs a, int HL, const float *z, const float *el, const uint2 *dob,
+                                                                      const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                      const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                      float *dz, RowsHubArgs H) {
+    gatmh_rows_src_body<GROUP, HPQ, NB, true>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, H);
+}
+// one lane group per hub row: the chunks' sums added in chunk order, then the one-pass closing arithmetic
+template <int GROUP, int HPQ>
+__global__ __launch_bounds__(256) void gatmh_rows_src_merge_kernel(GatMhArgs a, int HL, const float *z, const float *der, const float *a_l,
+                                                                   const float *a_r, float *del_out, float *dz, RowsHubArgs H) {
+    const uint32_t h = rows_unit<GROUP>();
+    const bool ok = h < H.nrows;
+    const RowsLane<GROUP, HPQ> L(a, ok ? H.rows[h] : 0, ok);
+    if (!L.row_ok) return;
+    const uint32_t c0 = H.row_chunk_ptr[h], c1 = H.row_chunk_ptr[h + 1];
+    const size_t stride = rows_hub_stride(2, a.ld, a.ldk);
+    RowsSrcState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) S.elu[s] = S.T[s] = S.Tp[s] = 0.f;
+    S.S = S.Sp = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (uint32_t c = c0; c < c1; ++c) {
+        const float *sp = H.state + c * stride, *hp = sp + 2 * (size_t)a.ld;
+        const float4 p = reinterpret_cast<const float4 *>(sp)[L.col], q = reinterpret_cast<const float4 *>(sp + a.ld)[L.col];
+        S.S = make_float4(S.S.x + p.x, S.S.y + p.y, S.S.z + p.z, S.S.w + p.w);
+        S.Sp = make_float4(S.Sp.x + q.x, S.Sp.y + q.y, S.Sp.z + q.z, S.Sp.w + q.w);
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) {
+            S.T[s] += hp[L.hk[s]];
+            S.Tp[s] += hp[a.ldk + L.hk[s]];
+        }
+    }
+    rows_src_close(L, a, HL, S, z, der, a_l, a_r, del_out, dz);
 }
 // dob / dogb: the shadow rows of do / bg_do (gatmh_bf16_gather = 2).  The 16-byte records, the row's own el[u], the closing z[u]
 // row, der, a_l and a_r stay fp32
@@ -479,7 +748,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_bf16_kernel(GatMhArgs a, i
                                                                   const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
                                                                   const float *der, const float *a_l, const float *a_r, float *del_out,
                                                                   float *dz) {
-    gatmh_rows_src_body<GROUP, HPQ, NB>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz);
+    gatmh_rows_src_body<GROUP, HPQ, NB, false>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, RowsHubArgs{});
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
@@ -515,10 +784,21 @@ static bool gatmh_rows_elfly(int hpq, uint32_t ld) { return hpq > 1 || ((ld >> 2
         else { if (group == 8) F(8, 4); else F(16, 4); }                                                                            \
     } while (0)
 
+size_t gatmh_rows_hub_state_floats(int pass, uint32_t ld, uint32_t ldk) { return rows_hub_stride(pass, ld, ldk); }
+// a split pass (hubs with chunks in the plan): the grid of the first launch -- chunk units, then row units -- and of the merge launch
+static bool gatmh_rows_split(const GatmhHubs *hubs, uint32_t N, uint32_t rpb, RowsHubArgs *H, dim3 *gr, dim3 *gm) {
+    if (!hubs || !hubs->plan.nchunks || !hubs->state) return false;
+    const LongRowsDev &P = hubs->plan;
+    *H = RowsHubArgs{P.nchunks, P.nrows, hubs->chunk, P.chunks, P.rows, P.row_chunk_ptr, hubs->state};
+    *gr = dim3((uint32_t)(((uint64_t)N + P.nchunks + rpb - 1) / rpb));
+    *gm = dim3((P.nrows + rpb - 1) / rpb);
+    return true;
+}
+
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
-                                     hipStream_t s, bool bf16) {
+                                     hipStream_t s, bool bf16, const GatmhHubs *hubs) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
@@ -526,6 +806,22 @@ hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     const bool elfly = gatmh_rows_elfly(hpq, ld);
+    RowsHubArgs HA;
+    dim3 gh, gm;
+    if (gatmh_rows_split(hubs, N, rpb, &HA, &gh, &gm)) {   // hub rows: their chunks and the other rows, then the merge
+        const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
+#define F(G, H, E)                                                                                                                  \
+    do {                                                                                                                            \
+        if (bf16) hipLaunchKernelGGL((gatmh_rows_forward_hub_bf16_kernel<G, H, E>), gh, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos, HA); \
+        else hipLaunchKernelGGL((gatmh_rows_forward_hub_kernel<G, H, E>), gh, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, o, op, m, den, dpos, HA); \
+    } while (0)
+        GATMH_ROWS_FORMS_EL(F);
+#undef F
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_forward_merge_kernel<G, H>), gm, bl, 0, s, a, o, op, m, den, dpos, HA)
+        GATMH_ROWS_FORMS(F);
+#undef F
+        return hipGetLastError();
+    }
     if (bf16) {   // z / zg: the shadow rows
         const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
 #define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_forward_bf16_kernel<G, H, E>), gr, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos)
@@ -542,7 +838,7 @@ hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_
 hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                  const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
-                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16) {
+                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16, const GatmhHubs *hubs) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
@@ -550,6 +846,22 @@ hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     const bool elfly = gatmh_rows_elfly(hpq, ld);
+    RowsHubArgs HA;
+    dim3 gh, gm;
+    if (gatmh_rows_split(hubs, N, rpb, &HA, &gh, &gm)) {
+        const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
+#define F(G, H, E)                                                                                                                  \
+    do {                                                                                                                            \
+        if (bf16) hipLaunchKernelGGL((gatmh_rows_dst_hub_bf16_kernel<G, H, E>), gh, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4, HA); \
+        else hipLaunchKernelGGL((gatmh_rows_dst_hub_kernel<G, H, E>), gh, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4, HA); \
+    } while (0)
+        GATMH_ROWS_FORMS_EL(F);
+#undef F
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_dst_merge_kernel<G, H>), gm, bl, 0, s, a, er, m, den, t, der, st4, lds4, HA)
+        GATMH_ROWS_FORMS(F);
+#undef F
+        return hipGetLastError();
+    }
     if (bf16) {   // z / zg: the shadow rows
         const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
 #define F(G, H, E) hipLaunchKernelGGL((gatmh_rows_dst_bf16_kernel<G, H, E>), gr, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4)
@@ -566,13 +878,29 @@ hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
 hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
-                                 float *del, float *dz, hipStream_t s, bool bf16) {
+                                 float *del, float *dz, hipStream_t s, bool bf16, const GatmhHubs *hubs) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
     GatMhArgs a{N, K, D, ld, ldk, rowptr, colidx};
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
+    RowsHubArgs HA;
+    dim3 gh, gm;
+    if (gatmh_rows_split(hubs, N, rpb, &HA, &gh, &gm)) {
+        const uint2 *dob = reinterpret_cast<const uint2 *>(d_o), *dogb = reinterpret_cast<const uint2 *>(dog);
+#define F(G, H)                                                                                                                     \
+    do {                                                                                                                            \
+        if (bf16) hipLaunchKernelGGL((gatmh_rows_src_hub_bf16_kernel<G, H, (H == 4 ? 2 : 4)>), gh, bl, 0, s, a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz, HA); \
+        else hipLaunchKernelGGL((gatmh_rows_src_hub_kernel<G, H, (H == 4 ? 2 : 4)>), gh, bl, 0, s, a, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, a_r, del, dz, HA); \
+    } while (0)
+        GATMH_ROWS_FORMS(F);
+#undef F
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_src_merge_kernel<G, H>), gm, bl, 0, s, a, HL, z, der, a_l, a_r, del, dz, HA)
+        GATMH_ROWS_FORMS(F);
+#undef F
+        return hipGetLastError();
+    }
     if (bf16) {   // d_o / dog: the shadow rows
         const uint2 *dob = reinterpret_cast<const uint2 *>(d_o), *dogb = reinterpret_cast<const uint2 *>(dog);
 #define F(G, H)                                                                                                                     \

@@ -1,0 +1,20 @@
+// row_chunks.hpp -- rows of an adjacency cut into chunks of consecutive entries (pure host code: dorylus_amd/host/row_chunks.cpp).
+// The plan record is K1's (LongRowsHost; spmm.hip's plan_long_rows fills it for the part of a row beyond LONG_ROW_CLAMP edges, in chunks
+// of LONG_ROW_CHUNK); plan_row_chunks is the general rule -- which rows, from which entry on, in chunks of what size -- and serves the hub
+// rows of the multi-head GAT's row-gather family (gat_mh_rows.hip, dory_gatmh_row_gather_hub_split: the whole row, the caller's size).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+namespace dory {
+
+struct LongRowsHost {                    // plan_long_rows / plan_row_chunks output
+    std::vector<uint32_t> rows;          // the rows that are cut, ascending
+    std::vector<uint32_t> row_chunk_ptr; // rows+1: first chunk of each
+    std::vector<uint32_t> chunks;        // 6 words per chunk: row, flag, e0 (lo, hi), e1 (lo, hi); flag: plan_long_rows 0, plan_row_chunks
+};                                       // 1 on the row's last chunk (else 0)
+// Rows with more than `over` entries (entries = ptr[v + 1] - ptr[v]) are cut: their entries from the `skip`-th on, in order, into
+// consecutive chunks of `chunk` entries, the last one shorter.  A row of exactly `over` entries is not cut.  chunk >= 1, skip <= over.
+void plan_row_chunks(const uint64_t *ptr, uint32_t N, uint64_t over, uint64_t skip, uint64_t chunk, LongRowsHost *out);
+
+}  // namespace dory

@@ -1,0 +1,48 @@
+// row_chunks.cpp -- plan_row_chunks (csrc/row_chunks.hpp) and its C entry point dory_row_chunk_plan (include/dorylus_host.h): the
+// chunk plan of an adjacency's long rows, on the host, without a context or a device.
+#include "../csrc/row_chunks.hpp"
+
+#include "../../include/dorylus_host.h"
+
+namespace dory {
+
+void plan_row_chunks(const uint64_t *ptr, uint32_t N, uint64_t over, uint64_t skip, uint64_t chunk, LongRowsHost *out) {
+    out->rows.clear(); out->row_chunk_ptr.assign(1, 0); out->chunks.clear();
+    for (uint32_t v = 0; v < N; ++v) {
+        const uint64_t beg = ptr[v], end = ptr[v + 1];
+        if (end - beg <= over) continue;
+        out->rows.push_back(v);
+        for (uint64_t e = beg + skip; e < end; e += chunk) {
+            const uint64_t e1 = end - e > chunk ? e + chunk : end;
+            out->chunks.push_back(v);                                  // row
+            out->chunks.push_back(e1 == end ? 1u : 0u);                // the row's last chunk
+            out->chunks.push_back((uint32_t)(e & 0xFFFFFFFFu)); out->chunks.push_back((uint32_t)(e >> 32));
+            out->chunks.push_back((uint32_t)(e1 & 0xFFFFFFFFu)); out->chunks.push_back((uint32_t)(e1 >> 32));
+        }
+        out->row_chunk_ptr.push_back((uint32_t)(out->chunks.size() / 6));
+    }
+}
+
+}  // namespace dory
+
+extern "C" int dory_row_chunk_plan(const uint64_t *ptr, uint32_t rows, uint32_t chunk_entries, uint32_t *hub_rows_out, uint32_t *chunks_out,
+                                   uint32_t *hub_rows, uint32_t *row_first_chunk, uint32_t *chunk_row, uint64_t *chunk_e0,
+                                   uint64_t *chunk_e1) {
+    if (!ptr || chunk_entries == 0) return DORY_ERR_ARG;
+    for (uint32_t v = 0; v < rows; ++v)
+        if (ptr[v] > ptr[v + 1]) return DORY_ERR_ARG;
+    dory::LongRowsHost h;
+    dory::plan_row_chunks(ptr, rows, chunk_entries, 0, chunk_entries, &h);
+    const size_t nr = h.rows.size(), nc = h.chunks.size() / 6;
+    if (hub_rows_out) *hub_rows_out = (uint32_t)nr;
+    if (chunks_out) *chunks_out = (uint32_t)nc;
+    for (size_t i = 0; i < nr && hub_rows; ++i) hub_rows[i] = h.rows[i];
+    for (size_t i = 0; i <= nr && row_first_chunk; ++i) row_first_chunk[i] = h.row_chunk_ptr[i];
+    for (size_t i = 0; i < nc; ++i) {
+        const uint32_t *w = &h.chunks[6 * i];
+        if (chunk_row) chunk_row[i] = w[0];
+        if (chunk_e0) chunk_e0[i] = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+        if (chunk_e1) chunk_e1[i] = (uint64_t)w[4] | ((uint64_t)w[5] << 32);
+    }
+    return DORY_OK;
+}

@@ -575,8 +575,8 @@ int dory_gatmh_bwd_wire_do(dory_ctx *ctx, uint32_t layer, uint32_t *elem_bytes, 
  * nothing on the host: a single-partition epoch in mode 1 can be recorded as an epoch graph like any other.
  * bf16 rows: "gatmh_bf16_gather" >= 1 is refused where the sweep forms do not run, mode 1 included, and the message says so --
  * unless dory_gatmh_row_gather_bf16 (below) is on, which gives this family bf16 forms of its three edge passes.
- * NOT TAKEN: overlap of the interior rows with the forward exchange; hub splitting -- a row's edges are walked by its one lane
- * group, however long the row.
+ * NOT TAKEN: overlap of the interior rows with the forward exchange.  Hub rows: a row's edges are walked by its one lane group,
+ * however long the row, unless dory_gatmh_row_gather_hub_split (below) cuts it.
  * Counters: passes since dory_create, eager calls and recordings (not replays): forward, destination side as an edge pass,
  * destination side as the row-wise kernel, source side; any pointer may be NULL. */
 int dory_gatmh_row_gather(dory_ctx *ctx, int mode);   /* 0 (default) / 1 */
@@ -619,6 +619,45 @@ int dory_gatmh_row_gather_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge
  * "gatmh_bf16_gathers_fwd" / "_src" and dory_gatmh_row_gather_stats count those passes too.  Any pointer may be NULL. */
 int dory_gatmh_row_gather_bf16(dory_ctx *ctx, int on);   /* 0 (default) / 1 */
 int dory_gatmh_row_gather_bf16_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src);
+
+/* ---- hub splitting for the row-gather kernels (opt-in, default off; nothing in the reference) -------------------------------------
+ * In the three edge passes of the family above one lane group walks a row's entries alone, four gathered rows at a time: a
+ * destination with tens of thousands of in-edges (a power-law partition) is one serial chain.  With chunk_entries != 0, wherever
+ * dory_aggregate takes that family -- mode 1 or mode 0's fall-back, gatmh_bwd_phase 0 / 1 / 2, every transport, with or without the
+ * merged exchange, bf16 rows, bf16 halo rows and ghost twins -- a HUB ROW is cut into chunks that run on lane groups of their own.
+ *   entry              an ENTRY of a row is one stored entry of its adjacency: an in-edge of a destination (forward and the
+ *                      destination-side edge pass), an out-edge of a source (source side).  The self edge, which the kernels
+ *                      append as the last entry of the id stream, is NOT counted and belongs to the row's last chunk.
+ *   hub row            a row with MORE than chunk_entries entries.  Its entries are cut, in order, into consecutive chunks of
+ *                      chunk_entries entries; the last chunk is shorter.  A row of exactly chunk_entries entries is not cut.
+ *   a split pass       two launches: (1) the chunks, one lane group each, with the unchanged per-entry arithmetic over their range,
+ *                      each leaving its state in scratch, and in the same launch every row that is no hub row, whole; (2) one lane
+ *                      group per hub row folds its chunks' states IN CHUNK ORDER and closes with the one-pass epilogue.
+ *                        forward: (m_c, den_c, den+_c, acc_c, acc+_c) unnormalised; M = max m_c, sums scaled by exp(m_c - M)
+ *                        destination side: partial (t, a1, a2) against the row's m / den; source side: partial S, S+, T, T+
+ *                      Where the destination side runs the row-wise kernel no edges are walked and nothing changes.
+ * CONTRACT: no atomics -- same input, same bits, run after run.  A row that is not cut keeps the bits it has with the feature off,
+ * in every tensor; "m" keeps them on every row (a maximum is exact).  A row that is cut has its sums in another association and
+ * differs from the one-pass row by rounding.  With no row over chunk_entries in an adjacency its passes launch exactly what they
+ * launch with the feature off.  The bf16 forms (dory_gatmh_row_gather_bf16) are the same bodies over bf16 row chunks: a split bf16
+ * pass equals the split fp32 pass on rows rounded beforehand, bit for bit.
+ * chunk_entries: 0 (default) = off; else a multiple of 64 in 64..1048576.  DORY_ERR_ARG: any other value, a value other than 0 on a
+ * context configured as DORY_GCN / DORY_GAT, a call while an epoch graph is being recorded.  The chunk plan of an adjacency is built when the value is
+ * set (a graph being there) or by the first pass that needs it, kept per adjacency and dropped by dory_graph_upload; the chunk
+ * states live in the context's scratch buffer, which cannot grow inside a recording (DORY_ERR_ARG there: run one eager epoch first).
+ * dory_row_chunk_plan (dorylus_host.h) gives the same plan without a device.
+ * Counters: forward passes, destination-side edge passes and source-side passes that ran split since dory_create (eager calls and
+ * recordings, not replays); hub rows and chunks of the current plan of the in-edges, and of the out-edges (0 while no plan for
+ * the current value is built).  Any pointer may be NULL.
+ * MEASURED (one MI355X, compute only; rank 0 of 8 of an R-MAT graph at Amazon size, largest degree 101 152; the parent's library and
+ * this one alternated over three rounds; profiles/r28_gatmh_row_gather_hubs.txt, tools/gatmh_row_gather_hubs_rate.py): the parent
+ * takes 24-35 ms a pass; at 1 024 every pass takes x0.05-0.15 of that (forward 29.5 -> 3.1 ms at 128-float rows, source side 35.3 ->
+ * 3.4), x0.06-0.15 at 2 048, x0.09-0.18 at 4 096 / 8 192.  RECOMMENDED on power-law partitions: 1 024.  The uniform rank of that size
+ * (nothing cut) stays inside the spread of the rounds, switched off and on.  NOT FASTER, NAMED: switched off, the R-MAT rank's forward
+ * at 1 x 25 is x1.046 of the parent's, the one switched-off line of ten outside the spread. */
+int dory_gatmh_row_gather_hub_split(dory_ctx *ctx, uint32_t chunk_entries);   /* 0 (default) = off */
+int dory_gatmh_row_gather_hub_split_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src, uint64_t *in_hub_rows,
+                                          uint64_t *in_chunks, uint64_t *out_hub_rows, uint64_t *out_chunks);
 
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows

@@ -84,6 +84,16 @@ int dory_partition_wire_order(const dory_partition *p, const int32_t *parts, int
 int dory_halo_send_map(uint32_t local_vtx_cnt, uint32_t num_nodes, const uint32_t *send_counts, const uint32_t *send_lvids,
                        uint32_t *row_ptr, uint32_t *row_slots);
 
+/* The chunk plan of an adjacency's hub rows (pure host code, no context, no device; the plan dory_gatmh_row_gather_hub_split of
+ * dorylus_hip.h builds for the row-gather kernels).  ptr: rows + 1 ascending offsets (column_ptrs or row_ptrs of a partition); an
+ * entry of row v is one of ptr[v] .. ptr[v + 1] - 1.  A row with MORE than chunk_entries entries is a hub row: its entries, in order,
+ * are cut into consecutive chunks of chunk_entries entries, the last one shorter; a row of exactly chunk_entries entries is not cut.
+ * Out: *hub_rows_out, *chunks_out the counts; hub_rows (ascending), row_first_chunk (hub rows + 1 entries: the chunks of hub row i
+ * are row_first_chunk[i] .. row_first_chunk[i + 1] - 1), and per chunk its row and its entries [chunk_e0, chunk_e1).  Every output may
+ * be NULL: call once for the counts, once more with arrays of that size.  DORY_ERR_ARG: ptr NULL or not ascending, chunk_entries 0. */
+int dory_row_chunk_plan(const uint64_t *ptr, uint32_t rows, uint32_t chunk_entries, uint32_t *hub_rows_out, uint32_t *chunks_out,
+                        uint32_t *hub_rows, uint32_t *row_first_chunk, uint32_t *chunk_row, uint64_t *chunk_e0, uint64_t *chunk_e1);
+
 /* upload adjacency (dory_graph_upload) and, when parts is given, both halo plans
  * (dory_halo_plan): recv slots of peer q = ghost slots whose owner is q, ascending.  On a context with option
  * "halo_direct_recv" = 1 the index arrays uploaded are the renumbered copies of dory_partition_wire_order (parts is then
