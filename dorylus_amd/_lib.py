@@ -40,6 +40,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather_bf16", "dory_gatmh_row_gather_bf16_stats",
     "dory_gatmh_bf16_ghosts", "dory_gatmh_bf16_ghosts_stats",
     "dory_gatmh_row_gather_hub_split", "dory_gatmh_row_gather_hub_split_stats",
+    "dory_gatmh_row_gather_overlap", "dory_gatmh_row_gather_overlap_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -184,9 +185,12 @@ def load():
         "dory_gatmh_bf16_ghosts_stats": [vp] + [C.POINTER(u64)] * 7,
         "dory_gatmh_row_gather_hub_split": [vp, u32],
         "dory_gatmh_row_gather_hub_split_stats": [vp] + [C.POINTER(u64)] * 7,
+        "dory_gatmh_row_gather_overlap": [vp, i32],
+        "dory_gatmh_row_gather_overlap_stats": [vp] + [C.POINTER(u64)] * 7,
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_row_chunk_plan": [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), vp, vp, vp, vp, vp],
+        "dory_row_interior_plan": [vp, vp, u32, C.POINTER(u32), C.POINTER(u32), vp, vp],
         "dory_partition_wire_order": [vp, vp, i32, vp, vp],
         "dory_sweep_geometry": [u32, u32, i32, i32, i32, u32, u32, u32, i32, vp],
         "dory_option_spec": [u32, C.POINTER(cp)] + [C.POINTER(t) for t in (i32, C.c_int64, C.c_int64, C.c_int64, i32, i32, i32)],
@@ -285,6 +289,25 @@ def row_chunk_plan(ptr, chunk_entries, lib=None):
     if rc != 0:
         raise DoryError(f"dory_row_chunk_plan failed ({rc})")
     return rows, first, crow, e0, e1
+
+
+def row_interior_plan(ptr, idx, N, lib=None):
+    """(interior, boundary): the rows of a partition's adjacency (ptr[N + 1], idx; an id >= N names a ghost row) whose entries are all
+    local -- a row without entries is one -- and the rows with at least one ghost entry, both ascending (dory_row_interior_plan; no
+    context, no GPU).  The plan Context.gatmh_row_gather_overlap builds per adjacency."""
+    lib = lib or load()
+    ptr, idx = np.ascontiguousarray(ptr, np.uint64), np.ascontiguousarray(idx, np.uint32)
+    if ptr.size != int(N) + 1:
+        raise DoryError(f"row_interior_plan: ptr has {ptr.size} entries for {N} rows")
+    ni, nb = C.c_uint32(), C.c_uint32()
+    rc = lib.dory_row_interior_plan(_ptr(ptr), _ptr(idx), int(N), C.byref(ni), C.byref(nb), None, None)
+    if rc != 0:
+        raise DoryError(f"dory_row_interior_plan failed ({rc})")
+    interior, boundary = np.zeros(ni.value, np.uint32), np.zeros(nb.value, np.uint32)
+    rc = lib.dory_row_interior_plan(_ptr(ptr), _ptr(idx), int(N), None, None, _ptr(interior), _ptr(boundary))
+    if rc != 0:
+        raise DoryError(f"dory_row_interior_plan failed ({rc})")
+    return interior, boundary
 
 
 class Context:
@@ -749,6 +772,22 @@ class Context:
         """dict: fwd / dst_edge_pass / src (passes that ran split since dory_create), in_hub_rows / in_chunks / out_hub_rows /
         out_chunks (the current chunk plans of the in-edges and the out-edges)"""
         return self._stats(self.lib.dory_gatmh_row_gather_hub_split_stats, 7, self.GATMH_HUB_SPLIT_STATS)
+
+    GATMH_ROWS_OVERLAP_STATS = ("fwd_split", "src_split", "fwd_in_flight", "src_in_flight", "in_interior_rows", "out_interior_rows",
+                                "bwd_deferred")
+
+    def gatmh_row_gather_overlap(self, on=1):
+        """the row-gather family runs its interior rows beside the exchange (dory_gatmh_row_gather_overlap): 0 (default) = off; 1 = where
+        an adjacency has interior rows (every entry local: row_interior_plan) and others, the forward and the backward's source side
+        launch the interior rows first -- beside the exchange in flight, if any -- then wait for the ghost rows and launch the rest;
+        every row is computed whole by the same kernel body, so every bit stays"""
+        self._ck(self.lib.dory_gatmh_row_gather_overlap(self.h, int(on)))
+
+    def gatmh_row_gather_overlap_stats(self):
+        """dict: fwd_split / src_split (passes that ran as two launches since dory_create), fwd_in_flight / src_in_flight (those of
+        them with an exchange in flight beside the first), in_interior_rows / out_interior_rows (the current plans of the in-edges
+        and the out-edges), bwd_deferred (backward exchanges issued deferred)"""
+        return self._stats(self.lib.dory_gatmh_row_gather_overlap_stats, 7, self.GATMH_ROWS_OVERLAP_STATS)
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

@@ -874,6 +874,7 @@ int wait_halo(dory_ctx *c) {
         }
         HIPCK(c, hipStreamWaitEvent(c->compute, c->ev_b, 0));
         c->halo_pending = false;
+        if (c->gatmh_scores_pending >= 0) return gatmh_ghost_scores_flush(c);   // (dory_gatmh_row_gather_overlap: left by dory_apply_edge)
     }
     return DORY_OK;
 }
@@ -1021,7 +1022,9 @@ int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, Gatmh
     *send = true;
     return wait_halo(c);   // the previous exchange has finished reading the buffer
 }
-int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor *bgst, bool producer_packed) {
+// defer_last (dory_gatmh_row_gather_overlap): the LAST exchange of the pass -- the merged one, or st's of the two -- is issued deferred where
+// halo_overlap is set (counted); do's, the first of two, never: exchange_rows and the local transport hold ONE pending exchange
+int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor *bgst, bool producer_packed, bool defer_last) {
     const int on = sw_value(c, SW_GATMH_BWD_MERGED_EXCHANGE);
     if (transport_of(c) == Transport::Local)   // every rank ships one row format: checked before anything of this pass is enqueued or counted
         for (uint32_t q = 0; q < c->numNodes; ++q) {
@@ -1033,11 +1036,15 @@ int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor
     if (gatmh_merged_taken(c)) {
         RowPair pair;
         pair.src2 = st; pair.ghost2 = bgst; pair.producer_packed = producer_packed;
-        return exchange_rows(c, DORY_BACKWARD, dO, bgdo, false, &pair);
+        const int rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, defer_last, &pair);
+        if (!rc && defer_last && c->halo_pending) c->gatmh_ovl_deferred++;
+        return rc;
     }
     if (on == 1 && !c->capturing) c->count[CNT_MERGED_SPLIT_FALLBACKS]++;   // (the scatter transport: its own layout; halo_direct_recv: two tensors)
     int rc = exchange_rows(c, DORY_BACKWARD, dO, bgdo, false);   // (dory_gatmh_halo_bf16: do by the rule, st always fp32)
-    return rc ? rc : exchange_rows(c, DORY_BACKWARD, st, bgst, false, nullptr, false);
+    if (!rc) rc = exchange_rows(c, DORY_BACKWARD, st, bgst, defer_last, nullptr, false);
+    if (!rc && defer_last && c->halo_pending) c->gatmh_ovl_deferred++;
+    return rc;
 }
 
 bool fused_pack_target(dory_ctx *c, const Tensor *out, uint32_t M, GemmSend *sd, int *dir) {

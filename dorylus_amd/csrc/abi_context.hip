@@ -239,6 +239,40 @@ int hub_plan_ensure(dory_ctx *c, Adjacency &A) {
     return DORY_OK;
 }
 
+// dory_gatmh_row_gather_overlap: the rows of one adjacency in launch order -- plan_row_interior's interior rows that the hub plan of the
+// context's chunk size does not cut (a row that is cut goes whole to the launch after the wait, with its chunks and the merge), then all
+// other rows.  Built from the pointer and index arrays (read back from the device, as hub_plan_ensure does), cached in the adjacency,
+// dropped with it (free_graph) and rebuilt when the chunk size changes
+int interior_plan_ensure(dory_ctx *c, Adjacency &A) {
+    if (A.rows_split_built && A.rows_hub_chunk == c->gatmh_hub_chunk) return DORY_OK;
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the interior rows' plan would have to be built while recording (run one eager epoch first)");
+    if (A.rows_split) {
+        HIPCK(c, hipDeviceSynchronize());   // (a launch in flight may still read the old list)
+        (void)hipFree(A.rows_split);
+        A.rows_split = nullptr;
+    }
+    A.rows_split_built = false;
+    A.rows_first = A.rows_interior = 0;
+    if (!c->has_graph) return DORY_OK;
+    std::vector<uint64_t> ptr((size_t)c->N + 1, 0);
+    std::vector<uint32_t> idx((size_t)A.nnz), in, bd, order;
+    if (A.ptr) HIPCK(c, hipMemcpy(ptr.data(), A.ptr, ptr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (A.nnz) HIPCK(c, hipMemcpy(idx.data(), A.idx, idx.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (ptr[c->N] > A.nnz) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_overlap: the adjacency's pointers run past its %llu entries", (unsigned long long)A.nnz);
+    plan_row_interior(ptr.data(), idx.data(), c->N, &in, &bd);
+    A.rows_interior = (uint32_t)in.size();
+    const uint64_t chunk = c->gatmh_hub_chunk;
+    std::vector<uint32_t> rest;
+    for (uint32_t v : in) (chunk && ptr[v + 1] - ptr[v] > chunk ? rest : order).push_back(v);   // (plan_row_chunks' rule: more than `chunk` entries)
+    A.rows_first = (uint32_t)order.size();
+    order.resize((size_t)c->N);
+    std::merge(rest.begin(), rest.end(), bd.begin(), bd.end(), order.begin() + A.rows_first);
+    if (c->N) { int rc = upload_array(c, &A.rows_split, order.data(), order.size()); if (rc) return rc; }
+    A.rows_hub_chunk = c->gatmh_hub_chunk;
+    A.rows_split_built = true;
+    return DORY_OK;
+}
+
 }  // namespace dory
 
 using namespace dory;
@@ -306,7 +340,8 @@ static void free_graph(dory_ctx *c) {
     for (Adjacency &A : c->adj) {
         for (void *p : {(void *)A.ptr, (void *)A.idx, (void *)A.val, (void *)A.order, (void *)A.split, (void *)A.edge_split.idx,
                         (void *)A.edge_split.val, (void *)A.edge_split.mid, (void *)A.long_rows.rows, (void *)A.long_rows.row_chunk_ptr,
-                        (void *)A.long_rows.chunks, (void *)A.hub_rows.rows, (void *)A.hub_rows.row_chunk_ptr, (void *)A.hub_rows.chunks})
+                        (void *)A.long_rows.chunks, (void *)A.hub_rows.rows, (void *)A.hub_rows.row_chunk_ptr, (void *)A.hub_rows.chunks,
+                        (void *)A.rows_split})
             if (p) (void)hipFree(p);
         for (BlockedAdj *B : {(BlockedAdj *)&A.blk, (BlockedAdj *)&A.blk16, (BlockedAdj *)&A.swp}) free_blocked(B);
         A = Adjacency{};   // every schedule, layout and flag of the direction at once
@@ -469,6 +504,37 @@ int dory_gatmh_row_gather_hub_split_stats(dory_ctx *c, uint64_t *fwd, uint64_t *
     if (in_chunks) *in_chunks = in ? c->adj[ADJ_IN].hub_rows.nchunks : 0;
     if (out_hub_rows) *out_hub_rows = out ? c->adj[ADJ_OUT].hub_rows.nrows : 0;
     if (out_chunks) *out_chunks = out ? c->adj[ADJ_OUT].hub_rows.nchunks : 0;
+    return DORY_OK;
+}
+
+// ---- dory_gatmh_row_gather_overlap: the row-gather family's interior rows beside the exchange (abi_stages.hip; include/dorylus_hip.h) ----
+int dory_gatmh_row_gather_overlap(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_overlap: value %d is neither 0 nor 1", on);
+    if (on && c->configured && c->gnn != DORY_GATMH)
+        return fail(c, DORY_ERR_ARG, "gatmh_row_gather_overlap: this context is configured as %s; the feature serves the multi-head GAT (DORY_GATMH) only",
+                    c->gnn == DORY_GCN ? "DORY_GCN (K1 runs its local part first itself: halo_overlap)" : "DORY_GAT");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_overlap: not while an epoch graph is being recorded");
+    if ((on == 1) != c->gatmh_rows_overlap) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->gatmh_rows_overlap = on == 1;
+    if (!on || !c->has_graph) return DORY_OK;   // (before dory_graph_upload: the first aggregation plans)
+    for (Adjacency &A : c->adj) {
+        const int rc = interior_plan_ensure(c, A);
+        if (rc) return rc;
+    }
+    return DORY_OK;
+}
+
+int dory_gatmh_row_gather_overlap_stats(dory_ctx *c, uint64_t *fwd_split, uint64_t *src_split, uint64_t *fwd_in_flight, uint64_t *src_in_flight,
+                                        uint64_t *in_interior_rows, uint64_t *out_interior_rows, uint64_t *bwd_deferred) {
+    CHECK_CTX(c);
+    if (fwd_split) *fwd_split = c->gatmh_ovl_fwd;
+    if (src_split) *src_split = c->gatmh_ovl_src;
+    if (fwd_in_flight) *fwd_in_flight = c->gatmh_ovl_fwd_flight;
+    if (src_in_flight) *src_in_flight = c->gatmh_ovl_src_flight;
+    if (in_interior_rows) *in_interior_rows = c->adj[ADJ_IN].rows_split_built ? c->adj[ADJ_IN].rows_interior : 0;
+    if (out_interior_rows) *out_interior_rows = c->adj[ADJ_OUT].rows_split_built ? c->adj[ADJ_OUT].rows_interior : 0;
+    if (bwd_deferred) *bwd_deferred = c->gatmh_ovl_deferred;
     return DORY_OK;
 }
 

@@ -87,6 +87,11 @@ void free_table(std::vector<std::map<std::string, Tensor>> &tab);
 int ensure_scratch(dory_ctx *c, size_t bytes);
 // dory_gatmh_row_gather_hub_split: the adjacency's chunk plan for the context's chunk size, built if it is not the cached one (abi_context.hip)
 int hub_plan_ensure(dory_ctx *c, dory::Adjacency &A);
+// dory_gatmh_row_gather_overlap: the adjacency's rows in launch order (Adjacency::rows_split) for the context's hub chunk size, built if it
+// is not the cached one (abi_context.hip)
+int interior_plan_ensure(dory_ctx *c, dory::Adjacency &A);
+// ... and the ghost sources' scores dory_apply_edge left until the exchange of z has landed: launched by wait_halo (abi_stages.hip)
+int gatmh_ghost_scores_flush(dory_ctx *c);
 // c->partial (K1b's partial rows, the sweeps' gate counters); `what` names it in the refusal inside a recording
 int ensure_partial(dory_ctx *c, size_t bytes, const char *what);
 int ensure_sweep(dory_ctx *c, Adjacency &A, int group);
@@ -125,7 +130,11 @@ int exchange_rows(dory_ctx *c, int dir, Tensor *src, Tensor *ghost, bool defer, 
 // launched -- *send: that kernel may write the merged send rows itself (the merged exchange will be taken, dory_halo_fused_pack is on,
 // the backward plan has its send map, no recording, the send buffer holds them); then *sd is filled in and the previous exchange has
 // finished reading the buffer.  Producer and exchange sit inside one dory_aggregate call: no stamp.
-int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor *bgst, bool producer_packed);
+// defer_last (dory_gatmh_row_gather_overlap, the row-gather family; the sweep and blocked forms pass false): the LAST exchange of the pass
+// -- the merged one, or st's in the two-exchange case -- is issued deferred where option halo_overlap is set; the caller calls wait_halo
+// before it reads bg_do / bg_st and before it returns.  do's exchange, the first of two, is never deferred: exchange_rows and the local
+// transport hold ONE pending exchange.
+int gatmh_bwd_exchange(dory_ctx *c, Tensor *dO, Tensor *bgdo, Tensor *st, Tensor *bgst, bool producer_packed, bool defer_last = false);
 // *bf16 (dory_gatmh_halo_bf16): the do part of those rows is bf16 by the rule of this moment -- the launcher's bf16 send form.
 int gatmh_bwd_send_target(dory_ctx *c, const Tensor *dO, const Tensor *st, GatmhSend *sd, bool *send, bool *bf16);
 uint32_t gatmh_merged_row_max(const dory_ctx *c);

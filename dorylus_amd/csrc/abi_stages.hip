@@ -522,6 +522,21 @@ static int gatmh_hubs_for(dory_ctx *c, Adjacency &A, int pass, uint32_t ld, uint
     return DORY_OK;
 }
 
+// dory_gatmh_row_gather_overlap: the two row lists of a pass of the row-gather family over adjacency A -- `first`: the interior rows the
+// hub plan does not cut (they read no ghost row: launched before the wait for the exchange), `rest`: all others -- or *split == false
+// where either list would be empty (no ghost, every row boundary, N == 0), or the switch is off: the pass launches what it always launched.
+// The plan is built here at first use (not while recording).
+static int gatmh_rows_lists_for(dory_ctx *c, Adjacency &A, bool *split, GatmhRowList *first, GatmhRowList *rest) {
+    *split = false;
+    if (!c->gatmh_rows_overlap || !A.ghosts || !c->N) return DORY_OK;
+    const int rc = interior_plan_ensure(c, A);
+    if (rc || !A.rows_split || !A.rows_first || A.rows_first >= c->N) return rc;
+    *first = GatmhRowList{A.rows_split, A.rows_first, false};
+    *rest = GatmhRowList{A.rows_split + A.rows_first, c->N - A.rows_first, true};
+    *split = true;
+    return DORY_OK;
+}
+
 // The multi-head GAT extension: edge softmax + weighted sum.
 // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
 // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
@@ -529,6 +544,59 @@ static int gatmh_hubs_for(dory_ctx *c, Adjacency &A, int pass, uint32_t ld, uint
 // take any other form the call is refused, never run in fp32
 // opt-in "gatmh_bf16_wide" on top of it: where a pass runs on bf16 rows of 128 floats or more with several heads of 16 / 32 / 64
 // features, its gathers fetch eight features per lane (16 bytes) on 16-lane groups -- the narrow bf16 form's bits
+// which family the forward of a layer takes (aggregate_gatmh_forward's dispatch; dory_apply_edge asks ahead of it, for
+// dory_gatmh_row_gather_overlap): the sweep form, the blocked form, else -- rows_forced or a partitioned run -- the row-gather family
+struct GatmhFwdForm {
+    bool rows_forced, blocked, sweep;
+    int shl;
+};
+static GatmhFwdForm gatmh_fwd_form(dory_ctx *c, const Tensor *z, const Tensor *op, const Tensor *dpos, uint32_t K, uint32_t D) {
+    Adjacency &In = c->adj[ADJ_IN];
+    GatmhFwdForm f;
+    const BlockedAdj &Bf = gatmh_blocked_for(In, z->ld);
+    // dory_gatmh_row_gather = 1: the row-gather family (gat_mh_rows.hip) in place of every other; 0: where a partitioned call
+    // finds neither layout below
+    f.rows_forced = sw_value(c, SW_GATMH_ROW_GATHER) == 1;
+    f.blocked = !f.rows_forced && c->opt[OPT_GATMH_BLOCKED] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
+                (D % 4 == 0 || K == 1) &&
+                (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
+    const DerivedAdj &Sf = In.swp;
+    f.shl = gatmh_sweep_hl(K, D, z->ld);
+    // (the same addressing test the launchers make -- 32-bit byte offsets through the buffer resource -- so that a
+    // partition they would refuse takes the blocked kernels instead of failing, as spmm() does)
+    SpmmArgs sa{};
+    sa.N = c->N; sa.ld = z->ld;
+    f.sweep = !f.rows_forced && c->opt[OPT_GATMH_SWEEP] && c->opt[OPT_SPMM_VARIANT] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
+              f.shl != 0 && op && dpos && sweep_supported(sa, Sf, gatmh_sweep_group(z->ld));
+    return f;
+}
+
+// the scores of the ghost sources of layer l0 from their exchanged z rows (dory_apply_edge; el is all the in-edge side needs)
+static int gatmh_ghost_scores(dory_ctx *c, uint32_t l0) {
+    const uint32_t K = c->heads[l0];
+    NEED(z, l0, "z"); NEED(fgz, l0, "fg_z"); NEED(fgel, l0, "fg_el"); NEED(fger, l0, "fg_er");
+    // dory_gatmh_bf16_ghosts: the exchange left the rows in fg_z's twin alone -- the scores come from the twin, the bits the fp32
+    // kernel gives on the widened rows (the contract of dory_gatmh_halo_bf16: fg_el from rounded rows); nothing is widened
+    if (fgz->twin && fgz->twin_state == DORY_GHOST_TWIN) {
+        HIPCK(c, launch_gatmh_scores_bf16(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->twin, fgz->ld, c->weights[l0]["a_l"].d,
+                                          c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
+        if (!c->capturing) c->count[CNT_GATMH_TWIN_SCORES]++;
+        return DORY_OK;
+    }
+    HIPCK(c, launch_gatmh_scores(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->d, fgz->ld, c->weights[l0]["a_l"].d,
+                                 c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
+    return DORY_OK;
+}
+// dory_gatmh_row_gather_overlap: dory_apply_edge left the ghost sources' scores of a layer to the moment the exchange of z has landed
+// (wait_halo calls this once the compute stream waits for the ghost rows: every reader of fg_el / fg_er calls wait_halo first)
+int gatmh_ghost_scores_flush(dory_ctx *c) {
+    const int l0 = c->gatmh_scores_pending;
+    c->gatmh_scores_pending = -1;
+    if (l0 < 0) return DORY_OK;
+    Timed t(c, "edge", c->compute);
+    return gatmh_ghost_scores(c, (uint32_t)l0);
+}
+
 static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
     Adjacency &In = c->adj[ADJ_IN];
     const uint32_t K = c->heads[fl];
@@ -543,22 +611,16 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
     {
         Timed t(c, "spmm", c->compute);
         const BlockedAdj &Bf = gatmh_blocked_for(In, z->ld);
-        // dory_gatmh_row_gather = 1: the row-gather family (gat_mh_rows.hip) in place of every other; 0: where a partitioned call
-        // finds neither layout below
-        const bool rows_forced = sw_value(c, SW_GATMH_ROW_GATHER) == 1;
-        const bool blocked = !rows_forced && c->opt[OPT_GATMH_BLOCKED] && In.blk.built && !In.blk.na && Bf.nb > 0 &&
-                             (D % 4 == 0 || K == 1) &&
-                             (size_t)Bf.nb * c->N * z->ld * sizeof(float) <= c->partial_bytes;
         AGG_NEED(fgz, fl, "fg_z"); AGG_NEED(fgel, fl, "fg_el");
         const DerivedAdj &Sf = In.swp;
-        const int shl = gatmh_sweep_hl(K, D, z->ld);
         Tensor *op = find(c, fl, "op"), *dpos = find(c, fl, "dpos");
-        // (the same addressing test the launchers make -- 32-bit byte offsets through the buffer resource -- so that a
-        // partition they would refuse takes the blocked kernels instead of failing, as spmm() does)
         SpmmArgs sa{};
         sa.N = c->N; sa.ld = z->ld;
-        const bool sweep = !rows_forced && c->opt[OPT_GATMH_SWEEP] && c->opt[OPT_SPMM_VARIANT] == 2 && Sf.built && !Sf.na && Sf.nb > 0 &&
-                           shl != 0 && op && dpos && sweep_supported(sa, Sf, gatmh_sweep_group(z->ld));
+        const GatmhFwdForm form = gatmh_fwd_form(c, z, op, dpos, K, D);
+        const bool rows_forced = form.rows_forced, blocked = form.blocked, sweep = form.sweep;
+        const int shl = form.shl;
+        // (dory_gatmh_row_gather_overlap: ghost scores dory_apply_edge left for the row-gather family, which this call does not take after all)
+        if (c->gatmh_scores_pending >= 0 && (sweep || blocked || !(rows_forced || c->numNodes > 1))) { int wrc = wait_halo(c); if (wrc) return wrc; }
         const bool bf16 = bfm >= 1;
         // dory_gatmh_row_gather_bf16: where this call takes the row-gather family below, its bf16 form runs instead of the refusal
         const bool rows_bf16 = bf16 && sw_on(c, SW_GATMH_ROW_GATHER_BF16) && !sweep && !blocked && (rows_forced || c->numNodes > 1);
@@ -620,19 +682,37 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                                                   c->opt[OPT_GATMH_EL_ON_THE_FLY] ? c->weights[fl]["a_l"].d : nullptr));
         }
         else if (rows_forced || c->numNodes > 1) {
-            // the row-gather family: the ghost rows have to have landed (overlapping the interior rows with the exchange: DESIGN.md 7)
+            // the row-gather family: the ghost rows have to have landed -- except, with dory_gatmh_row_gather_overlap, for the interior rows
             if (!op || !dpos || !gatmh_rows_ok(K, D, z->ld))
                 return fail(c, DORY_ERR_ARG, "multi-head GAT: the row-gather kernels need op / dpos and K*D <= ld <= 256 (K = %u, D = %u, ld = %u)", K, D, z->ld);
             // bf16 form: z / fg_z from the shadow rows -- the local rows converted now, the ghost rows once their exchange has landed
             Bf16Rows bf;
-            int rc = rows_bf16 ? bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather") : In.ghosts ? ghost_fp32_current(c, fgz) : (int)DORY_OK;
-            if (rc || (rc = wait_halo(c)) || (rc = bf.ghosts_landed())) return rc;
-            if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
+            // dory_gatmh_row_gather_overlap: the interior rows (z / the local shadow rows alone) first, beside the exchange if one is in
+            // flight; then the wait, the ghost rows' conversion or widening, and the rest -- around_halo's schedule, the same arithmetic
+            // with and without an exchange in flight
+            bool split;
+            GatmhRowList first, rest;
+            int rc = gatmh_rows_lists_for(c, In, &split, &first, &rest);
+            if (rc) return rc;
             GatmhHubs hubs;   // dory_gatmh_row_gather_hub_split: the hub rows of the in-edges, if any
             if ((rc = gatmh_hubs_for(c, In, 0, z->ld, el->ld, &hubs))) return rc;
-            HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
-                                               rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
-                                               c->weights[fl]["a_l"].d, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16, &hubs));
+            if (rows_bf16 && (rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
+            const float *a_l = c->weights[fl]["a_l"].d;
+            const bool in_flight = c->halo_pending;
+            auto launch = [&](const GatmhHubs *h, const GatmhRowList *rows) -> int {
+                HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
+                                                   rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
+                                                   a_l, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16, h, rows));
+                return DORY_OK;
+            };
+            rc = around_halo(c, split, rows_bf16 ? &bf : nullptr, [&]() -> int { return launch(&hubs, &first); }, [&]() -> int {
+                // (ghost_fp32_current waits for the exchange itself: after the interior launch)
+                const int r = !rows_bf16 && In.ghosts ? ghost_fp32_current(c, fgz) : (int)DORY_OK;
+                return r ? r : launch(&hubs, split ? &rest : nullptr);
+            });
+            if (rc) return rc;
+            if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
+            if (split) { c->gatmh_ovl_fwd++; if (in_flight) c->gatmh_ovl_fwd_flight++; }
             if (hubs.plan.nchunks) c->gatmh_hub_fwd++;
             if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
             c->count[CNT_GATMH_ROWS_FWD]++;
@@ -666,9 +746,11 @@ struct GatmhBwd {
 
 // ghost destinations of the out-edges: their dO and st rows, between the two phases of a whole backward pass -- two exchanges, or
 // (dory_gatmh_bwd_merged_exchange) one of merged rows, which `producer_packed` says the destination side has written already
-static int gatmh_backward_exchange(dory_ctx *c, const GatmhBwd &T, bool producer_packed = false) {
+// defer_last (dory_gatmh_row_gather_overlap; the row-gather family alone): the last exchange of the pass is issued deferred where
+// halo_overlap allows -- the caller launches what reads no ghost row, then calls wait_halo before anything else
+static int gatmh_backward_exchange(dory_ctx *c, const GatmhBwd &T, bool producer_packed = false, bool defer_last = false) {
     if (T.phase != 0 || c->numNodes <= 1) return DORY_OK;
-    return gatmh_bwd_exchange(c, T.dO, T.bgdo, T.st, T.bgst, producer_packed);
+    return gatmh_bwd_exchange(c, T.dO, T.bgdo, T.st, T.bgst, producer_packed, defer_last);
 }
 
 // The sweep forms (gat_mh_sweep.hip).  Destination side: this layer's forward ran on the skeleton and left the positive-branch
@@ -793,20 +875,35 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         }
     }
     if (T.phase == 1) return DORY_OK;
-    if ((rc = gatmh_backward_exchange(c, T))) return rc;
+    // dory_gatmh_row_gather_overlap: the interior sources (every destination local: do / st alone) run beside the pass's last exchange,
+    // which is then issued deferred (halo_overlap); the wait, bg_do's conversion or widening and the rest follow.  Phase 2: the same two
+    // launches with nothing in flight
+    bool split;
+    GatmhRowList first, rest;
+    if ((rc = gatmh_rows_lists_for(c, Out, &split, &first, &rest))) return rc;
+    if ((rc = gatmh_backward_exchange(c, T, false, split))) return rc;
     {
         Timed t(c, "spmm", c->compute);
-        // (phase 0: the exchange above made the compute stream wait for bg_do; phase 2: the caller moved it before this call)
+        // (phase 0: the exchange above made the compute stream wait for bg_do, or around_halo does; phase 2: the caller moved it before this call)
         Bf16Rows bf;
-        if (src_bf16 && ((rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather")) || (rc = bf.ghosts_landed()))) return rc;
-        if (!src_bf16 && Out.ghosts && (rc = ghost_fp32_current(c, T.bgdo))) return rc;
-        if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
         GatmhHubs hubs;   // dory_gatmh_row_gather_hub_split: the hub rows of the out-edges, if any (the merge has read the states before
         if ((rc = gatmh_hubs_for(c, Out, 2, ld, ldk, &hubs))) return rc;   //  launch_gatmh_dattn below takes the scratch: one stream)
-        HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
-                                       src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
-                                       Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
-                                       c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, src_bf16, &hubs));
+        if (src_bf16 && (rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather"))) return rc;
+        const bool in_flight = c->halo_pending;
+        auto launch = [&](const GatmhHubs *h, const GatmhRowList *rows) -> int {
+            HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
+                                           src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
+                                           Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
+                                           c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, src_bf16, h, rows));
+            return DORY_OK;
+        };
+        rc = around_halo(c, split, src_bf16 ? &bf : nullptr, [&]() -> int { return launch(&hubs, &first); }, [&]() -> int {
+            const int r = !src_bf16 && Out.ghosts ? ghost_fp32_current(c, T.bgdo) : (int)DORY_OK;
+            return r ? r : launch(&hubs, split ? &rest : nullptr);
+        });
+        if (rc) return rc;
+        if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
+        if (split) { c->gatmh_ovl_src++; if (in_flight) c->gatmh_ovl_src_flight++; }
         if (hubs.plan.nchunks) c->gatmh_hub_src++;
         c->count[CNT_GATMH_ROWS_SRC]++;
         if (src_bf16) {
@@ -1135,7 +1232,25 @@ int dory_apply_vertex(dory_ctx *c, uint32_t layer, int dir) {
 
 int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
     CHECK_CTX(c);
-    { int wrc = wait_halo(c); if (wrc) return wrc; }
+    // dory_gatmh_row_gather_overlap: where the forward of this layer will run its interior rows beside the exchange in flight, the exchange
+    // stays in flight here too -- the local scores now, the ghost sources' once it has landed (gatmh_ghost_scores_flush), the same kernels
+    bool keep_flight = false;
+    if (c->gatmh_rows_overlap && c->halo_pending && c->gatmh_scores_pending < 0 && c->prealloc && c->gnn == DORY_GATMH && dir == DORY_FORWARD &&
+        layer >= 1 && layer <= c->L && c->N && c->adj[ADJ_IN].ghosts && (c->adj[ADJ_IN].rows_split_built || !c->capturing)) {
+        const uint32_t l0 = layer - 1, K = c->heads[l0];
+        Tensor *z = find(c, l0, "z"), *op = find(c, l0, "op"), *dpos = find(c, l0, "dpos");
+        if (z && op && dpos && find(c, l0, "fg_z") && find(c, l0, "fg_el") && find(c, l0, "fg_er") && gatmh_rows_ok(K, z->cols / K, z->ld)) {
+            const GatmhFwdForm form = gatmh_fwd_form(c, z, op, dpos, K, z->cols / K);
+            bool split = false;
+            GatmhRowList first, rest;
+            if (!form.sweep && !form.blocked && (form.rows_forced || c->numNodes > 1)) {
+                const int prc = gatmh_rows_lists_for(c, c->adj[ADJ_IN], &split, &first, &rest);
+                if (prc) return prc;
+            }
+            keep_flight = split;
+        }
+    }
+    if (!keep_flight) { int wrc = wait_halo(c); if (wrc) return wrc; }
     if (!c->prealloc || c->gnn == DORY_GCN) {
         if (c->prealloc && c->gnn == DORY_GCN) return DORY_OK;  // applyEdgeGCN is a no-op (gcn_ops.cpp:364-366)
         return fail(c, DORY_ERR_ARG, "apply_edge: preallocate first");
@@ -1149,17 +1264,8 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
         HIPCK(c, launch_gatmh_scores(c->N, K, z->cols / K, z->d, z->ld, c->weights[l0]["a_l"].d, c->weights[l0]["a_r"].d,
                                      el->d, er->d, el->ld, c->compute));
         if (c->adj[ADJ_IN].ghosts) {   // scores of the ghost sources from their exchanged z rows (el is all the in-edge side needs)
-            NEED(fgz, l0, "fg_z"); NEED(fgel, l0, "fg_el"); NEED(fger, l0, "fg_er");
-            // dory_gatmh_bf16_ghosts: the exchange left the rows in fg_z's twin alone -- the scores come from the twin, the bits the fp32
-            // kernel gives on the widened rows (the contract of dory_gatmh_halo_bf16: fg_el from rounded rows); nothing is widened
-            if (fgz->twin && fgz->twin_state == DORY_GHOST_TWIN) {
-                HIPCK(c, launch_gatmh_scores_bf16(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->twin, fgz->ld, c->weights[l0]["a_l"].d,
-                                                  c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
-                if (!c->capturing) c->count[CNT_GATMH_TWIN_SCORES]++;
-                return DORY_OK;
-            }
-            HIPCK(c, launch_gatmh_scores(c->adj[ADJ_IN].ghosts, K, z->cols / K, fgz->d, fgz->ld, c->weights[l0]["a_l"].d,
-                                         c->weights[l0]["a_r"].d, fgel->d, fger->d, fgel->ld, c->compute));
+            if (keep_flight) { c->gatmh_scores_pending = (int)l0; return DORY_OK; }
+            return gatmh_ghost_scores(c, l0);
         }
         return DORY_OK;
     }

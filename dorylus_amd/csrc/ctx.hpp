@@ -216,6 +216,13 @@ struct Adjacency {
     // family of the multi-head GAT; built by hub_plan_ensure when the value is set or at first use, dropped with the adjacency)
     LongRowsDev hub_rows;
     uint32_t hub_chunk = 0;      // the chunk size hub_rows was planned for (0: no plan)
+    // dory_gatmh_row_gather_overlap: the rows in launch order (N entries) -- first the rows_first rows a launch beside an exchange may hold,
+    // ascending: the interior rows of plan_row_interior (every entry < N) that the hub plan of rows_hub_chunk does not cut; then all other
+    // rows, ascending.  Built by interior_plan_ensure when the switch is set or at first use, dropped with the adjacency
+    uint32_t *rows_split = nullptr;
+    uint32_t rows_first = 0, rows_interior = 0;   // (rows_interior: the plan's interior rows, cut or not)
+    uint32_t rows_hub_chunk = 0;
+    bool rows_split_built = false;
     EdgeSplit edge_split;        // K1: local-first copy (GCN partitions with ghosts)
     DerivedAdj blk;              // K1b blocked copy; na: too many source blocks, use K1
     // multi-head GAT contexts with layers on both sides of 128 floats: a second copy, blocked for the 256-B slabs of the narrow
@@ -292,6 +299,11 @@ struct dory_ctx {
     // dory_gatmh_row_gather_hub_split: entries per chunk (0 = off), and the forward / destination-side edge / source-side passes that ran split
     uint32_t gatmh_hub_chunk = 0;
     uint64_t gatmh_hub_fwd = 0, gatmh_hub_dst = 0, gatmh_hub_src = 0;
+    // dory_gatmh_row_gather_overlap: the switch; forward / source-side passes that ran as interior rows + the rest, those of them with an
+    // exchange in flight beside the interior launch, and the backward exchanges issued deferred for it
+    bool gatmh_rows_overlap = false;
+    int gatmh_scores_pending = -1;   // the layer whose ghost sources' scores (fg_el / fg_er) wait for the exchange in flight; -1: none
+    uint64_t gatmh_ovl_fwd = 0, gatmh_ovl_src = 0, gatmh_ovl_fwd_flight = 0, gatmh_ovl_src_flight = 0, gatmh_ovl_deferred = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -715,11 +727,21 @@ struct GatmhHubs {
     float *state = nullptr;
 };
 size_t gatmh_rows_hub_state_floats(int pass, uint32_t ld, uint32_t ldk);
+// dory_gatmh_row_gather_overlap: a launch over n listed rows instead of all N (unit i = row rows[i]; device memory, ids < N).  With a list
+// the forward and the source side run their *_list_kernel: the chunk units of `hubs` (if it has any; its hub rows among the listed ones are
+// skipped and merged as ever), then the listed rows -- each computed whole by the body of the all-N launch, so it keeps its bits.
+struct GatmhRowList {
+    const uint32_t *rows = nullptr;
+    uint32_t n = 0;
+    // false: the launch before the wait -- `hubs` only says which code the listed rows run (the hub kernel's, where the plan has chunks:
+    // what computes them with the switch off); no chunk unit, no merge, no row skipped
+    bool chunks = true;
+};
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
                                      hipStream_t s, bool bf16 = false /* z / zg: their shadow rows (launch_bf16_rows) */,
-                                     const GatmhHubs *hubs = nullptr);
+                                     const GatmhHubs *hubs = nullptr, const GatmhRowList *list = nullptr);
 hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                  const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
@@ -729,7 +751,7 @@ hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
                                  float *del, float *dz, hipStream_t s, bool bf16 = false /* d_o / dog: their shadow rows */,
-                                 const GatmhHubs *hubs = nullptr);
+                                 const GatmhHubs *hubs = nullptr, const GatmhRowList *list = nullptr);
 // row-wise backward (single partition; feature-per-lane or (edge, head, piece)-per-lane kernels by shape)
 hipError_t launch_gatmh_backward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const uint64_t *rowptr, const uint32_t *colidx,

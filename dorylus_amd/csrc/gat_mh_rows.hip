@@ -57,7 +57,19 @@
 // launchers launch exactly the kernels they launched before.  Measured (profiles/r28_gatmh_row_gather_hubs.txt): rank 0 of 8 of an
 // Amazon-size R-MAT graph, largest degree 101 152 -- 24-35 ms a pass one-pass, x0.05-0.15 of that at chunk 1 024; a uniform rank unchanged.
 //
-// Not taken here: a wide (16-byte) bf16 form and overlap of the interior rows with the exchange.
+// Interior rows beside the exchange (dory_gatmh_row_gather_overlap; the *_list_kernel forms below).  The kernels read ghost rows through
+// plain pointers, so a pass used to wait for the exchange before it launched anything.  A row whose every entry is local (row_chunks.hpp:
+// plan_row_interior) reads no ghost row.  With the switch on, the forward and the source side run as two launches of a list form -- the
+// body with its row units named by a list (unit i = row list[i], rows packed densely into lane groups: no all-N launch that skips rows
+// by flag, the family is latency-bound and a wave with one live group of four loses its rows in flight): first the interior rows, then
+// -- after the wait for the ghost rows -- the hub rows' chunks, if any, and all other rows, with the merge launch as ever.  There is a
+// list form of the one-pass kernel and one of the hub kernel (taken where the chunk plan has chunks): the compiler contracts the closing
+// arithmetic of the two differently at four heads per lane, and a listed row has to have the code it has with the switch off.  A row the chunk plan cuts goes whole to the second launch.  Every row is computed whole by the body that
+// computes it in the all-N launch, so every bit stays.  The one-pass, hub and merge kernels are untouched instruction for instruction
+// (the list is a template parameter of RowsWork and a kernel argument of the list kernels alone).  The destination-side edge pass reads
+// fg_z, which landed during the forward: no exchange to hide behind, no list form.  Its measurement: tools/gatmh_row_gather_overlap_rate.py.
+//
+// Not taken here: a wide (16-byte) bf16 form.
 #include "gat_mh.hpp"
 #include "spmm_common.hpp"
 
@@ -110,14 +122,21 @@ struct RowsHubArgs {
 __host__ __device__ __forceinline__ size_t rows_hub_stride(int pass, uint32_t ld, uint32_t ldk) {
     return ((size_t)(pass == 1 ? 0 : 2) * ld + (size_t)(pass == 0 ? 3 : pass == 1 ? 3 : 2) * ldk + 3) & ~(size_t)3;
 }
+// dory_gatmh_row_gather_overlap: the rows of a launch named by a list -- unit i is row rows[i], n units (the interior rows beside
+// an exchange, the boundary rows after it: Adjacency::rows_split)
+struct RowsListArgs {
+    const uint32_t *rows;
+    uint32_t n;
+};
 // What a lane group of a launch does.  HUBS false: row = unit, all of it.  HUBS true: the first H.nchunks units are the chunks of the
 // hub rows (part: a range of the row's entries, the self edge with the last), the rest the rows, of which the hub rows are skipped.
-template <int GROUP, bool HUBS>
+// LIST: the row units are the R.n rows R.rows names, packed densely, not all N (with HUBS: after the chunk units).
+template <int GROUP, bool HUBS, bool LIST>
 struct RowsWork {
     uint32_t row, slot;
     bool ok, part, self;
     uint64_t ce0, cend;
-    __device__ __forceinline__ RowsWork(const GatMhArgs &a, const RowsHubArgs &H) {
+    __device__ __forceinline__ RowsWork(const GatMhArgs &a, const RowsHubArgs &H, const RowsListArgs &R) {
         uint32_t unit = rows_unit<GROUP>();
         part = false; self = true; slot = 0; ce0 = cend = 0;
         if constexpr (HUBS) {
@@ -129,7 +148,9 @@ struct RowsWork {
                 cend = (uint64_t)w[4] | ((uint64_t)w[5] << 32);
             } else unit -= H.nchunks;
         }
-        if (!part) { ok = unit < a.N; row = ok ? unit : 0; }
+        if constexpr (LIST) {
+            if (!part) { ok = unit < R.n; row = ok ? R.rows[unit] : 0; }
+        } else if (!part) { ok = unit < a.N; row = ok ? unit : 0; }
     }
     // the group's entries: [e0, end) of idx, then -- total counts it -- the self edge; false: nothing to walk and nothing to store
     template <class LANE>
@@ -266,11 +287,12 @@ __device__ __forceinline__ void rows_fwd_store(const RowsLane<GROUP, HPQ> &L, co
 // CHUNK: what a lane gathers of a row -- float4 (fp32 rows), or uint2 (four bf16 of the shadow rows, launch_bf16_rows, widened
 // exactly by row_chunk).  Everything after the load is the same arithmetic in the same order, so a bf16 kernel gives its fp32
 // sibling's bits on rows that were rounded beforehand; the bodies below are shared by both, the __global__ kernels only name them.
-template <int GROUP, int HPQ, bool ELFLY, bool HUBS, class CHUNK>
+template <int GROUP, int HPQ, bool ELFLY, bool HUBS, bool LIST, class CHUNK>
 __device__ __forceinline__ void gatmh_rows_forward_body(const GatMhArgs &a, int HL, const CHUNK *z4, const CHUNK *zg4, const float *el,
                                                         const float *elg, const float *er, const float *a_l, float *o, float *op,
-                                                        float *m_out, float *den_out, float *dpos_out, const RowsHubArgs &H) {
-    const RowsWork<GROUP, HUBS> W(a, H);
+                                                        float *m_out, float *den_out, float *dpos_out, const RowsHubArgs &H,
+                                                        const RowsListArgs &R = RowsListArgs{}) {
+    const RowsWork<GROUP, HUBS, LIST> W(a, H, R);
     const RowsLane<GROUP, HPQ> L(a, W.row, W.ok);
     const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
     RowsFwdState<HPQ> S;
@@ -336,7 +358,7 @@ template <int GROUP, int HPQ, bool ELFLY>
 __global__ __launch_bounds__(256) void gatmh_rows_forward_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
                                                                  const float *elg, const float *er, const float *a_l, float *o, float *op,
                                                                  float *m_out, float *den_out, float *dpos_out) {
-    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
                                                       a_l, o, op, m_out, den_out, dpos_out, RowsHubArgs{});
 }
 // the launch of a split pass: the hub rows' chunks, then the rows that are no hub rows (RowsWork)
@@ -344,7 +366,7 @@ template <int GROUP, int HPQ, bool ELFLY>
 __global__ __launch_bounds__(256) void gatmh_rows_forward_hub_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
                                                                      const float *elg, const float *er, const float *a_l, float *o, float *op,
                                                                      float *m_out, float *den_out, float *dpos_out, RowsHubArgs H) {
-    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
                                                      a_l, o, op, m_out, den_out, dpos_out, H);
 }
 template <int GROUP, int HPQ, bool ELFLY>
@@ -352,7 +374,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_forward_hub_bf16_kernel(GatMhA
                                                                           const float *elg, const float *er, const float *a_l, float *o,
                                                                           float *op, float *m_out, float *den_out, float *dpos_out,
                                                                           RowsHubArgs H) {
-    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, H);
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true, false>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, H);
 }
 // one lane group per hub row: the chunk states folded in chunk order against the maximum of the chunk maxima (exp(m_c - M) <= 1: chunks
 // whose maxima lie far apart merge to a factor of zero, never to Inf or NaN -- every chunk has an entry, so every m_c is finite)
@@ -396,7 +418,40 @@ template <int GROUP, int HPQ, bool ELFLY>
 __global__ __launch_bounds__(256) void gatmh_rows_forward_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
                                                                       const float *elg, const float *er, const float *a_l, float *o,
                                                                       float *op, float *m_out, float *den_out, float *dpos_out) {
-    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, RowsHubArgs{});
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false, false>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, RowsHubArgs{});
+}
+// dory_gatmh_row_gather_overlap: the rows of a list -- the interior rows of the in-edges beside the exchange (they read z / the local
+// shadow rows alone), the boundary rows after it; every row by the body above.  Two forms, so that a listed row has the code of the
+// kernel that computes it with the switch off: *_list_kernel is the one-pass kernel over listed rows, *_list_hub_kernel the hub kernel
+// (the hub rows' chunk units first) over listed rows, taken where the adjacency's chunk plan has chunks.
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_list_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                                      const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                                      float *m_out, float *den_out, float *dpos_out, RowsListArgs R) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false, true>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg,
+                                                            er, a_l, o, op, m_out, den_out, dpos_out, RowsHubArgs{}, R);
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_list_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
+                                                                           const float *elg, const float *er, const float *a_l, float *o,
+                                                                           float *op, float *m_out, float *den_out, float *dpos_out,
+                                                                           RowsListArgs R) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, false, true>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, RowsHubArgs{}, R);
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_list_hub_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                                          const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                                          float *m_out, float *den_out, float *dpos_out, RowsHubArgs H,
+                                                                          RowsListArgs R) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true, true>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg,
+                                                           er, a_l, o, op, m_out, den_out, dpos_out, H, R);
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_list_hub_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
+                                                                               const float *elg, const float *er, const float *a_l, float *o,
+                                                                               float *op, float *m_out, float *den_out, float *dpos_out,
+                                                                               RowsHubArgs H, RowsListArgs R) {
+    gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true, true>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, H, R);
 }
 
 // ---- backward, destination side: t[v,k] = sum a*da, der[v,k] = sum a*da*l' - t * sum a*l', st = (er, m, 1/den, t) -------------------
@@ -440,12 +495,12 @@ __device__ __forceinline__ void rows_dst_store(const RowsLane<GROUP, HPQ> &L, co
         }
 }
 
-template <int GROUP, int HPQ, bool ELFLY, bool HUBS, class CHUNK>
+template <int GROUP, int HPQ, bool ELFLY, bool HUBS, bool LIST, class CHUNK>
 __device__ __forceinline__ void gatmh_rows_dst_body(const GatMhArgs &a, int HL, const CHUNK *z4, const CHUNK *zg4, const float *el,
                                                     const float *elg, const float *er, const float *a_l, const float *m_in,
                                                     const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
                                                     uint32_t lds4, const RowsHubArgs &H) {
-    const RowsWork<GROUP, HUBS> W(a, H);
+    const RowsWork<GROUP, HUBS, LIST> W(a, H, RowsListArgs{});
     const RowsLane<GROUP, HPQ> L(a, W.row, W.ok);
     const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
     RowsDstState<HPQ> S;
@@ -511,7 +566,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_kernel(GatMhArgs a, int HL
                                                              const float *elg, const float *er, const float *a_l, const float *m_in,
                                                              const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
                                                              uint32_t lds4) {
-    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, false, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
                                                   m_in, den_in, d_o, t_out, der_out, st4, lds4, RowsHubArgs{});
 }
 template <int GROUP, int HPQ, bool ELFLY>
@@ -519,7 +574,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_hub_kernel(GatMhArgs a, in
                                                                  const float *elg, const float *er, const float *a_l, const float *m_in,
                                                                  const float *den_in, const float *d_o, float *t_out, float *der_out,
                                                                  float4 *st4, uint32_t lds4, RowsHubArgs H) {
-    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, true>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, true, false>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er, a_l,
                                                  m_in, den_in, d_o, t_out, der_out, st4, lds4, H);
 }
 template <int GROUP, int HPQ, bool ELFLY>
@@ -527,7 +582,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_hub_bf16_kernel(GatMhArgs 
                                                                       const float *elg, const float *er, const float *a_l, const float *m_in,
                                                                       const float *den_in, const float *d_o, float *t_out, float *der_out,
                                                                       float4 *st4, uint32_t lds4, RowsHubArgs H) {
-    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, true>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4, H);
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, true, false>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4, H);
 }
 // one lane group per hub row: the chunks' (t, a1, a2) added in chunk order, then the one-pass epilogue
 template <int GROUP, int HPQ>
@@ -566,7 +621,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_bf16_kernel(GatMhArgs a, i
                                                                   const float *elg, const float *er, const float *a_l, const float *m_in,
                                                                   const float *den_in, const float *d_o, float *t_out, float *der_out,
                                                                   float4 *st4, uint32_t lds4) {
-    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, false>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4, RowsHubArgs{});
+    gatmh_rows_dst_body<GROUP, HPQ, ELFLY, false, false>(a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4, RowsHubArgs{});
 }
 
 // ---- backward, source side: rows = sources u (out-edges), entries = destinations v (local: do / st, ghost: bg_do / bg_st) ---------
@@ -634,11 +689,12 @@ __device__ __forceinline__ void rows_src_close(const RowsLane<GROUP, HPQ> &L, co
         if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) del_out[(size_t)L.v * a.ldk + L.hk[s]] = del[s];
 }
 
-template <int GROUP, int HPQ, int NB, bool HUBS, class CHUNK>
+template <int GROUP, int HPQ, int NB, bool HUBS, bool LIST, class CHUNK>
 __device__ __forceinline__ void gatmh_rows_src_body(const GatMhArgs &a, int HL, const float *z, const float *el, const CHUNK *d4,
                                                     const CHUNK *dg4, const float4 *st4, const float4 *stg, uint32_t lds4, const float *der,
-                                                    const float *a_l, const float *a_r, float *del_out, float *dz, const RowsHubArgs &H) {
-    const RowsWork<GROUP, HUBS> W(a, H);
+                                                    const float *a_l, const float *a_r, float *del_out, float *dz, const RowsHubArgs &H,
+                                                    const RowsListArgs &R = RowsListArgs{}) {
+    const RowsWork<GROUP, HUBS, LIST> W(a, H, R);
     const RowsLane<GROUP, HPQ> L(a, W.row, W.ok);
     RowsSrcState<HPQ> S;
 #pragma unroll
@@ -696,7 +752,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_kernel(GatMhArgs a, int HL
                                                              const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
                                                              const float *der, const float *a_l, const float *a_r, float *del_out,
                                                              float *dz) {
-    gatmh_rows_src_body<GROUP, HPQ, NB, false>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
+    gatmh_rows_src_body<GROUP, HPQ, NB, false, false>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
                                                lds4, der, a_l, a_r, del_out, dz, RowsHubArgs{});
 }
 template <int GROUP, int HPQ, int NB>
@@ -704,7 +760,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_hub_kernel(GatMhArgs a, in
                                                                  const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
                                                                  const float *der, const float *a_l, const float *a_r, float *del_out,
                                                                  float *dz, RowsHubArgs H) {
-    gatmh_rows_src_body<GROUP, HPQ, NB, true>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
+    gatmh_rows_src_body<GROUP, HPQ, NB, true, false>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
                                               lds4, der, a_l, a_r, del_out, dz, H);
 }
 template <int GROUP, int HPQ, int NB>
@@ -712,7 +768,7 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_hub_bf16_kernel(GatMhArgs 
                                                                       const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
                                                                       const float *der, const float *a_l, const float *a_r, float *del_out,
                                                                       float *dz, RowsHubArgs H) {
-    gatmh_rows_src_body<GROUP, HPQ, NB, true>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, H);
+    gatmh_rows_src_body<GROUP, HPQ, NB, true, false>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, H);
 }
 // one lane group per hub row: the chunks' sums added in chunk order, then the one-pass closing arithmetic
 template <int GROUP, int HPQ>
@@ -748,7 +804,39 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_bf16_kernel(GatMhArgs a, i
                                                                   const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
                                                                   const float *der, const float *a_l, const float *a_r, float *del_out,
                                                                   float *dz) {
-    gatmh_rows_src_body<GROUP, HPQ, NB, false>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, RowsHubArgs{});
+    gatmh_rows_src_body<GROUP, HPQ, NB, false, false>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, RowsHubArgs{});
+}
+// dory_gatmh_row_gather_overlap: as gatmh_rows_forward_list_kernel, over the out-edges -- the interior sources (every destination local:
+// do / st alone) beside the backward's last exchange, the boundary sources after it
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_list_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
+                                                                  const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                  const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                  float *dz, RowsListArgs R) {
+    gatmh_rows_src_body<GROUP, HPQ, NB, false, true>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4,
+                                                     stg, lds4, der, a_l, a_r, del_out, dz, RowsHubArgs{}, R);
+}
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_list_bf16_kernel(GatMhArgs a, int HL, const float *z, const float *el, const uint2 *dob,
+                                                                       const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                       const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                       float *dz, RowsListArgs R) {
+    gatmh_rows_src_body<GROUP, HPQ, NB, false, true>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, RowsHubArgs{}, R);
+}
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_list_hub_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
+                                                                      const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                      const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                      float *dz, RowsHubArgs H, RowsListArgs R) {
+    gatmh_rows_src_body<GROUP, HPQ, NB, true, true>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4,
+                                                    stg, lds4, der, a_l, a_r, del_out, dz, H, R);
+}
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_list_hub_bf16_kernel(GatMhArgs a, int HL, const float *z, const float *el, const uint2 *dob,
+                                                                           const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                           const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                           float *dz, RowsHubArgs H, RowsListArgs R) {
+    gatmh_rows_src_body<GROUP, HPQ, NB, true, true>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, H, R);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
@@ -786,6 +874,22 @@ static bool gatmh_rows_elfly(int hpq, uint32_t ld) { return hpq > 1 || ((ld >> 2
 
 size_t gatmh_rows_hub_state_floats(int pass, uint32_t ld, uint32_t ldk) { return rows_hub_stride(pass, ld, ldk); }
 // a split pass (hubs with chunks in the plan): the grid of the first launch -- chunk units, then row units -- and of the merge launch
+// dory_gatmh_row_gather_overlap: a launch over a row list -- the listed rows, after the hub rows' chunk units where the plan has any.
+// *hubform: the list-hub form (the plan has chunks: the code the rows run with the switch off); *merge: with the chunk units, and the
+// hub rows' merge launch follows (not for the launch before the wait: no chunk unit, a chunk size no row exceeds)
+static void gatmh_rows_listed(const GatmhHubs *hubs, const GatmhRowList &list, uint32_t rpb, RowsHubArgs *H, RowsListArgs *R, dim3 *gl, dim3 *gm,
+                              bool *hubform, bool *merge) {
+    *hubform = hubs && hubs->plan.nchunks && hubs->state;
+    *merge = *hubform && list.chunks;
+    *H = RowsHubArgs{0, 0, 0xFFFFFFFFu, nullptr, nullptr, nullptr, nullptr};
+    if (*merge) {
+        const LongRowsDev &P = hubs->plan;
+        *H = RowsHubArgs{P.nchunks, P.nrows, hubs->chunk, P.chunks, P.rows, P.row_chunk_ptr, hubs->state};
+        *gm = dim3((P.nrows + rpb - 1) / rpb);
+    }
+    *R = RowsListArgs{list.rows, list.n};
+    *gl = dim3((uint32_t)(((uint64_t)list.n + H->nchunks + rpb - 1) / rpb));
+}
 static bool gatmh_rows_split(const GatmhHubs *hubs, uint32_t N, uint32_t rpb, RowsHubArgs *H, dim3 *gr, dim3 *gm) {
     if (!hubs || !hubs->plan.nchunks || !hubs->state) return false;
     const LongRowsDev &P = hubs->plan;
@@ -798,7 +902,7 @@ static bool gatmh_rows_split(const GatmhHubs *hubs, uint32_t N, uint32_t rpb, Ro
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
-                                     hipStream_t s, bool bf16, const GatmhHubs *hubs) {
+                                     hipStream_t s, bool bf16, const GatmhHubs *hubs, const GatmhRowList *list) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
@@ -808,6 +912,27 @@ hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_
     const bool elfly = gatmh_rows_elfly(hpq, ld);
     RowsHubArgs HA;
     dim3 gh, gm;
+    if (list) {   // dory_gatmh_row_gather_overlap: the listed rows (with the hub rows' chunks and their merge, where the caller hands hubs)
+        RowsListArgs LA;
+        bool hubform, merge;
+        gatmh_rows_listed(hubs, *list, rpb, &HA, &LA, &gh, &gm, &hubform, &merge);
+        if (gh.x == 0) return hipSuccess;
+        const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
+#define F(G, H, E)                                                                                                                  \
+    do {                                                                                                                            \
+        if (hubform && bf16) hipLaunchKernelGGL((gatmh_rows_forward_list_hub_bf16_kernel<G, H, E>), gh, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos, HA, LA); \
+        else if (hubform) hipLaunchKernelGGL((gatmh_rows_forward_list_hub_kernel<G, H, E>), gh, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, o, op, m, den, dpos, HA, LA); \
+        else if (bf16) hipLaunchKernelGGL((gatmh_rows_forward_list_bf16_kernel<G, H, E>), gh, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos, LA); \
+        else hipLaunchKernelGGL((gatmh_rows_forward_list_kernel<G, H, E>), gh, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, o, op, m, den, dpos, LA); \
+    } while (0)
+        GATMH_ROWS_FORMS_EL(F);
+#undef F
+        if (!merge) return hipGetLastError();
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_forward_merge_kernel<G, H>), gm, bl, 0, s, a, o, op, m, den, dpos, HA)
+        GATMH_ROWS_FORMS(F);
+#undef F
+        return hipGetLastError();
+    }
     if (gatmh_rows_split(hubs, N, rpb, &HA, &gh, &gm)) {   // hub rows: their chunks and the other rows, then the merge
         const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
 #define F(G, H, E)                                                                                                                  \
@@ -878,7 +1003,7 @@ hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
 hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
-                                 float *del, float *dz, hipStream_t s, bool bf16, const GatmhHubs *hubs) {
+                                 float *del, float *dz, hipStream_t s, bool bf16, const GatmhHubs *hubs, const GatmhRowList *list) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
@@ -887,6 +1012,27 @@ hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     RowsHubArgs HA;
     dim3 gh, gm;
+    if (list) {   // dory_gatmh_row_gather_overlap: as in launch_gatmh_rows_forward
+        RowsListArgs LA;
+        bool hubform, merge;
+        gatmh_rows_listed(hubs, *list, rpb, &HA, &LA, &gh, &gm, &hubform, &merge);
+        if (gh.x == 0) return hipSuccess;
+        const uint2 *dob = reinterpret_cast<const uint2 *>(d_o), *dogb = reinterpret_cast<const uint2 *>(dog);
+#define F(G, H)                                                                                                                     \
+    do {                                                                                                                            \
+        if (hubform && bf16) hipLaunchKernelGGL((gatmh_rows_src_list_hub_bf16_kernel<G, H, (H == 4 ? 2 : 4)>), gh, bl, 0, s, a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz, HA, LA); \
+        else if (hubform) hipLaunchKernelGGL((gatmh_rows_src_list_hub_kernel<G, H, (H == 4 ? 2 : 4)>), gh, bl, 0, s, a, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, a_r, del, dz, HA, LA); \
+        else if (bf16) hipLaunchKernelGGL((gatmh_rows_src_list_bf16_kernel<G, H, (H == 4 ? 2 : 4)>), gh, bl, 0, s, a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz, LA); \
+        else hipLaunchKernelGGL((gatmh_rows_src_list_kernel<G, H, (H == 4 ? 2 : 4)>), gh, bl, 0, s, a, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, a_r, del, dz, LA); \
+    } while (0)
+        GATMH_ROWS_FORMS(F);
+#undef F
+        if (!merge) return hipGetLastError();
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_src_merge_kernel<G, H>), gm, bl, 0, s, a, HL, z, der, a_l, a_r, del, dz, HA)
+        GATMH_ROWS_FORMS(F);
+#undef F
+        return hipGetLastError();
+    }
     if (gatmh_rows_split(hubs, N, rpb, &HA, &gh, &gm)) {
         const uint2 *dob = reinterpret_cast<const uint2 *>(d_o), *dogb = reinterpret_cast<const uint2 *>(dog);
 #define F(G, H)                                                                                                                     \

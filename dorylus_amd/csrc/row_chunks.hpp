@@ -17,4 +17,11 @@ struct LongRowsHost {                    // plan_long_rows / plan_row_chunks out
 // consecutive chunks of `chunk` entries, the last one shorter.  A row of exactly `over` entries is not cut.  chunk >= 1, skip <= over.
 void plan_row_chunks(const uint64_t *ptr, uint32_t N, uint64_t over, uint64_t skip, uint64_t chunk, LongRowsHost *out);
 
+// The rows of a partition's adjacency by what they read (dory_gatmh_row_gather_overlap; the C entry point: dory_row_interior_plan).  An
+// entry >= N names a ghost row.  interior: every entry of the row is < N -- a row without entries too (its only edge is the self edge);
+// boundary: at least one entry is >= N.  Both ascending; together they are [0, N).  The in-edge adjacency sorts destinations by their
+// sources, the out-edge adjacency sources by their destinations; option halo_direct_recv renumbers the ghosts among themselves, so it
+// changes neither list.
+void plan_row_interior(const uint64_t *ptr, const uint32_t *idx, uint32_t N, std::vector<uint32_t> *interior, std::vector<uint32_t> *boundary);
+
 }  // namespace dory

@@ -1,5 +1,6 @@
 // row_chunks.cpp -- plan_row_chunks (csrc/row_chunks.hpp) and its C entry point dory_row_chunk_plan (include/dorylus_host.h): the
-// chunk plan of an adjacency's long rows, on the host, without a context or a device.
+// chunk plan of an adjacency's long rows, on the host, without a context or a device.  Likewise plan_row_interior /
+// dory_row_interior_plan: the rows that read no ghost row, and the others.
 #include "../csrc/row_chunks.hpp"
 
 #include "../../include/dorylus_host.h"
@@ -23,7 +24,31 @@ void plan_row_chunks(const uint64_t *ptr, uint32_t N, uint64_t over, uint64_t sk
     }
 }
 
+void plan_row_interior(const uint64_t *ptr, const uint32_t *idx, uint32_t N, std::vector<uint32_t> *interior, std::vector<uint32_t> *boundary) {
+    interior->clear(); boundary->clear();
+    for (uint32_t v = 0; v < N; ++v) {
+        bool ghost = false;
+        for (uint64_t e = ptr[v]; e < ptr[v + 1] && !ghost; ++e) ghost = idx[e] >= N;
+        (ghost ? boundary : interior)->push_back(v);
+    }
+}
+
 }  // namespace dory
+
+extern "C" int dory_row_interior_plan(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t *interior_out, uint32_t *boundary_out,
+                                      uint32_t *interior_rows, uint32_t *boundary_rows) {
+    if (!ptr) return DORY_ERR_ARG;
+    for (uint32_t v = 0; v < rows; ++v)
+        if (ptr[v] > ptr[v + 1]) return DORY_ERR_ARG;
+    if (!idx && rows && ptr[rows] > ptr[0]) return DORY_ERR_ARG;
+    std::vector<uint32_t> in, bd;
+    dory::plan_row_interior(ptr, idx, rows, &in, &bd);
+    if (interior_out) *interior_out = (uint32_t)in.size();
+    if (boundary_out) *boundary_out = (uint32_t)bd.size();
+    for (size_t i = 0; i < in.size() && interior_rows; ++i) interior_rows[i] = in[i];
+    for (size_t i = 0; i < bd.size() && boundary_rows; ++i) boundary_rows[i] = bd[i];
+    return DORY_OK;
+}
 
 extern "C" int dory_row_chunk_plan(const uint64_t *ptr, uint32_t rows, uint32_t chunk_entries, uint32_t *hub_rows_out, uint32_t *chunks_out,
                                    uint32_t *hub_rows, uint32_t *row_first_chunk, uint32_t *chunk_row, uint64_t *chunk_e0,

@@ -659,6 +659,42 @@ int dory_gatmh_row_gather_hub_split(dory_ctx *ctx, uint32_t chunk_entries);   /*
 int dory_gatmh_row_gather_hub_split_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src, uint64_t *in_hub_rows,
                                           uint64_t *in_chunks, uint64_t *out_hub_rows, uint64_t *out_chunks);
 
+/* ---- the row-gather family: interior rows beside the exchange (opt-in, default off; nothing in the reference) ----------------
+ * The row-gather kernels read ghost rows through plain pointers, so a pass waits for the exchange that fills them before it
+ * launches anything: with option halo_overlap = 1 the exchange of a rank on this family is fully exposed.  A row whose every
+ * adjacency entry is local needs nothing from the exchange.  With this switch on, a pass over an adjacency that has such rows
+ * and others is two launches:
+ *   interior row       every entry of the row is < local_vtx_cnt; a row without entries is interior (its only edge is the self edge).
+ *                      In-edges: a destination whose sources are all local; out-edges: a source whose destinations are all local.
+ *   boundary row       at least one entry names a ghost row.  dory_row_interior_plan (dorylus_host.h) gives both lists without a device.
+ *   forward            (1) the interior rows, packed densely into lane groups, reading z (or the local shadow rows) alone; (2) the
+ *                      wait for the exchange of z, the ghost rows' conversion or widening; (3) the boundary rows.
+ *   backward, source   the LAST exchange of the pass -- the merged one under dory_gatmh_bwd_merged_exchange, else st's -- is issued
+ *   side (phase 0)     DEFERRED where halo_overlap = 1 (do's, the first of two, never: one exchange can be pending); (1) the interior
+ *                      sources, reading do / st alone; (2) the wait, bg_do's conversion or widening; (3) the boundary sources.  The
+ *                      pending exchange never outlives the dory_aggregate call.  gatmh_bwd_phase = 2: the same two launches.
+ *   not touched        the destination-side edge pass (it reads fg_z, which landed during the forward); the sweep and blocked forms.
+ * The same two launches run whether an exchange is in flight or not (timing families "spmm_beside_halo" / "spmm_local_first").
+ * With dory_gatmh_row_gather_hub_split a row the chunk plan cuts counts as a boundary row: it goes, whole, to the launch after the
+ * wait, with its chunks and the merge.  Where one of the lists is empty -- no ghosts, every row boundary, no vertices -- the pass
+ * launches exactly what it launches with the switch off.
+ * CONTRACT: switch on = switch off, BIT FOR BIT, in every tensor, weight and weight gradient: every row is computed whole by the body
+ * that computes it with the switch off; only the launch that holds it changes.  This holds for every transport, both halo schedules,
+ * gatmh_bwd_phase 0 / 1 / 2, fp32 and bf16 rows, bf16 halo rows and ghost twins, the merged exchange, halo_direct_recv and hub
+ * splitting at any chunk size.  The switch moves no bytes on the wire: the ranks of an in-process group may differ in it.
+ * on: 0 (default) or 1.  DORY_ERR_ARG: any other value, 1 on a context configured as DORY_GCN / DORY_GAT, a call while an epoch
+ * graph is being recorded.  The row lists of an adjacency are built when the switch is set (a graph being there) or by the first
+ * pass that needs them, kept per adjacency, dropped by dory_graph_upload and rebuilt when the hub chunk size changes; they cannot be
+ * built inside a recording (DORY_ERR_ARG there: run one eager epoch first).
+ * Counters, in this order: forward passes and source-side passes that ran as two launches since dory_create (eager calls and
+ * recordings, not replays); of those forward passes, and of those source-side passes, the ones with an exchange in flight beside the
+ * first launch; interior rows of the current plan of the in-edges, and of the out-edges (0 while none is built); backward
+ * exchanges issued deferred.  Any pointer may be NULL. */
+int dory_gatmh_row_gather_overlap(dory_ctx *ctx, int on);   /* 0 (default) = off */
+int dory_gatmh_row_gather_overlap_stats(dory_ctx *ctx, uint64_t *fwd_split, uint64_t *src_split, uint64_t *fwd_in_flight,
+                                        uint64_t *src_in_flight, uint64_t *in_interior_rows, uint64_t *out_interior_rows,
+                                        uint64_t *bwd_deferred);
+
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
  * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels

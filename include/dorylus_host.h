@@ -94,6 +94,16 @@ int dory_halo_send_map(uint32_t local_vtx_cnt, uint32_t num_nodes, const uint32_
 int dory_row_chunk_plan(const uint64_t *ptr, uint32_t rows, uint32_t chunk_entries, uint32_t *hub_rows_out, uint32_t *chunks_out,
                         uint32_t *hub_rows, uint32_t *row_first_chunk, uint32_t *chunk_row, uint64_t *chunk_e0, uint64_t *chunk_e1);
 
+/* The interior rows of a partition's adjacency (pure host code, no context, no device; the plan dory_gatmh_row_gather_overlap of
+ * dorylus_hip.h builds for the row-gather kernels).  ptr as above, idx: the ptr[rows] entries, local ids -- an entry >= rows names a
+ * ghost row.  A row is INTERIOR when every entry is < rows (a row without entries is: its only edge is the self edge) and BOUNDARY
+ * when at least one is >= rows.  With column_ptrs / the in-edges this sorts destinations by their sources, with row_ptrs / the
+ * out-edges sources by their destinations; the ids dory_partition_wire_order renumbers stay >= rows, so the lists do not depend on it.
+ * Out: *interior_out, *boundary_out the counts (their sum is rows); interior_rows, boundary_rows ascending.  Every output may be NULL:
+ * call once for the counts, once more with arrays of that size.  DORY_ERR_ARG: ptr NULL or not ascending, idx NULL with entries. */
+int dory_row_interior_plan(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t *interior_out, uint32_t *boundary_out,
+                           uint32_t *interior_rows, uint32_t *boundary_rows);
+
 /* upload adjacency (dory_graph_upload) and, when parts is given, both halo plans
  * (dory_halo_plan): recv slots of peer q = ghost slots whose owner is q, ascending.  On a context with option
  * "halo_direct_recv" = 1 the index arrays uploaded are the renumbered copies of dory_partition_wire_order (parts is then
