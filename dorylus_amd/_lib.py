@@ -41,6 +41,7 @@ SYMBOLS = [
     "dory_gatmh_bf16_ghosts", "dory_gatmh_bf16_ghosts_stats",
     "dory_gatmh_row_gather_hub_split", "dory_gatmh_row_gather_hub_split_stats",
     "dory_gatmh_row_gather_overlap", "dory_gatmh_row_gather_overlap_stats",
+    "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -187,10 +188,13 @@ def load():
         "dory_gatmh_row_gather_hub_split_stats": [vp] + [C.POINTER(u64)] * 7,
         "dory_gatmh_row_gather_overlap": [vp, i32],
         "dory_gatmh_row_gather_overlap_stats": [vp] + [C.POINTER(u64)] * 7,
+        "dory_gatmh_row_gather_bf16_wide": [vp, i32],
+        "dory_gatmh_row_gather_bf16_wide_stats": [vp] + [C.POINTER(u64)] * 4,
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_row_chunk_plan": [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), vp, vp, vp, vp, vp],
         "dory_row_interior_plan": [vp, vp, u32, C.POINTER(u32), C.POINTER(u32), vp, vp],
+        "dory_gatmh_row_gather_bf16_wide_form": [u32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)],
         "dory_partition_wire_order": [vp, vp, i32, vp, vp],
         "dory_sweep_geometry": [u32, u32, i32, i32, i32, u32, u32, u32, i32, vp],
         "dory_option_spec": [u32, C.POINTER(cp)] + [C.POINTER(t) for t in (i32, C.c_int64, C.c_int64, C.c_int64, i32, i32, i32)],
@@ -308,6 +312,17 @@ def row_interior_plan(ptr, idx, N, lib=None):
     if rc != 0:
         raise DoryError(f"dory_row_interior_plan failed ({rc})")
     return interior, boundary
+
+
+def gatmh_row_gather_bf16_wide_form(K, D, ld, lib=None):
+    """None where a pass of the row-gather family over K heads of D features on rows of ld floats has no wide bf16 form (the narrow
+    form runs), else (lanes_per_row, lanes_per_head, scores_from_row): the rule Context.gatmh_row_gather_bf16_wide applies
+    (dory_gatmh_row_gather_bf16_wide_form; no context, no GPU)"""
+    lib = lib or load()
+    lr, lh, el = C.c_uint32(), C.c_uint32(), C.c_int32()
+    if not lib.dory_gatmh_row_gather_bf16_wide_form(int(K), int(D), int(ld), C.byref(lr), C.byref(lh), C.byref(el)):
+        return None
+    return lr.value, lh.value, bool(el.value)
 
 
 class Context:
@@ -788,6 +803,19 @@ class Context:
         them with an exchange in flight beside the first), in_interior_rows / out_interior_rows (the current plans of the in-edges
         and the out-edges), bwd_deferred (backward exchanges issued deferred)"""
         return self._stats(self.lib.dory_gatmh_row_gather_overlap_stats, 7, self.GATMH_ROWS_OVERLAP_STATS)
+
+    GATMH_ROWS_BF16_WIDE_STATS = ("fwd", "dst_edge_pass", "src", "narrow_while_on")
+
+    def gatmh_row_gather_bf16_wide(self, on=1):
+        """the row-gather family's bf16 passes gather 16 bytes a lane (dory_gatmh_row_gather_bf16_wide): 0 (default) = off; 1 = where
+        gatmh_row_gather_bf16_wide_form has a form for the shape, a bf16 pass keeps eight features a lane on half the lanes per row --
+        the narrow bf16 form's bits in every tensor; inert while gatmh_row_gather_bf16 is off"""
+        self._ck(self.lib.dory_gatmh_row_gather_bf16_wide(self.h, int(on)))
+
+    def gatmh_row_gather_bf16_wide_stats(self):
+        """dict: fwd / dst_edge_pass / src (passes that ran the wide form since dory_create: eager calls and recordings),
+        narrow_while_on (bf16 passes of the family that ran narrow with the switch on)"""
+        return self._stats(self.lib.dory_gatmh_row_gather_bf16_wide_stats, 4, self.GATMH_ROWS_BF16_WIDE_STATS)
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

@@ -538,6 +538,28 @@ int dory_gatmh_row_gather_overlap_stats(dory_ctx *c, uint64_t *fwd_split, uint64
     return DORY_OK;
 }
 
+// ---- dory_gatmh_row_gather_bf16_wide: the row-gather family's bf16 passes gather 16 bytes a lane (gat_mh_rows.hip; include/dorylus_hip.h) ----
+int dory_gatmh_row_gather_bf16_wide(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16_wide: value %d is neither 0 nor 1", on);
+    if (on && c->configured && c->gnn != DORY_GATMH)
+        return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16_wide: this context is configured as %s; the feature serves the multi-head GAT (DORY_GATMH) only",
+                    c->gnn == DORY_GCN ? "DORY_GCN (K1s has its own wide form: gcn_bf16_wide)" : "DORY_GAT");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16_wide: not while an epoch graph is being recorded");
+    if ((on == 1) != c->gatmh_rows_wide) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->gatmh_rows_wide = on == 1;
+    return DORY_OK;
+}
+
+int dory_gatmh_row_gather_bf16_wide_stats(dory_ctx *c, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src, uint64_t *narrow_while_on) {
+    CHECK_CTX(c);
+    if (fwd) *fwd = c->gatmh_rows8_fwd;
+    if (dst_edge_pass) *dst_edge_pass = c->gatmh_rows8_dst;
+    if (src) *src = c->gatmh_rows8_src;
+    if (narrow_while_on) *narrow_while_on = c->gatmh_rows8_narrow;
+    return DORY_OK;
+}
+
 int dory_gatmh_heads(dory_ctx *c, const uint32_t *heads) {
     CHECK_CTX(c);
     if (!c->configured || c->gnn != DORY_GATMH || !heads) return fail(c, DORY_ERR_ARG, "gatmh_heads: configure with DORY_GATMH first");

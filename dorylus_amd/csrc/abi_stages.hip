@@ -537,6 +537,20 @@ static int gatmh_rows_lists_for(dory_ctx *c, Adjacency &A, bool *split, GatmhRow
     return DORY_OK;
 }
 
+// dory_gatmh_row_gather_bf16_wide: what a pass of the row-gather family hands its launcher -- fp32 rows, the shadow rows, or (the switch
+// on, a shape of the wide form, 16-byte aligned shadow rows and twins) the shadow rows gathered 16 bytes a lane.  The wide form gives the
+// narrow form's bits: nothing else of the schedule asks which of the two ran.  bf: after begin() -- the ghost rows' base (shadow rows
+// or twin) is fixed there, before any of them has landed
+static int gatmh_rows_gather_form(dory_ctx *c, bool bf16, uint32_t K, uint32_t D, uint32_t ld, const Bf16Rows &bf) {
+    if (!bf16) return GATMH_ROWS_FP32;
+    return c->gatmh_rows_wide && gatmh_rows_wide_ok(K, D, ld, bf.xl, bf.xg) ? GATMH_ROWS_BF16_WIDE : GATMH_ROWS_BF16;
+}
+// a bf16 pass of the family has run: it was wide, or narrow with the switch on
+static void gatmh_rows_wide_count(dory_ctx *c, int form, uint64_t *wide) {
+    if (form == GATMH_ROWS_BF16_WIDE) ++*wide;
+    else if (c->gatmh_rows_wide) c->gatmh_rows8_narrow++;
+}
+
 // The multi-head GAT extension: edge softmax + weighted sum.
 // opt-in "gatmh_bf16_gather" (no reference counterpart): 1 = the forward edge pass gathers the rows of z / fg_z rounded to
 // bf16, 2 = the backward's source-side pass gathers do / bg_do likewise; scores, statistics, sums and outputs stay fp32.
@@ -699,10 +713,11 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             if (rows_bf16 && (rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
             const float *a_l = c->weights[fl]["a_l"].d;
             const bool in_flight = c->halo_pending;
+            const int rform = gatmh_rows_gather_form(c, rows_bf16, K, D, z->ld, bf);
             auto launch = [&](const GatmhHubs *h, const GatmhRowList *rows) -> int {
                 HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
                                                    rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
-                                                   a_l, o->d, op->d, m->d, den->d, dpos->d, c->compute, rows_bf16, h, rows));
+                                                   a_l, o->d, op->d, m->d, den->d, dpos->d, c->compute, rform, h, rows));
                 return DORY_OK;
             };
             rc = around_halo(c, split, rows_bf16 ? &bf : nullptr, [&]() -> int { return launch(&hubs, &first); }, [&]() -> int {
@@ -720,6 +735,7 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
                 c->gatmh_fwd_rows_bf16[fl] = 1;
                 c->gatmh_bf16_gathers_fwd++;
                 c->count[CNT_GATMH_ROWS_BF16_FWD]++;
+                gatmh_rows_wide_count(c, rform, &c->gatmh_rows8_fwd);
             }
         }
         else
@@ -865,13 +881,14 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
             if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
             GatmhHubs hubs;   // dory_gatmh_row_gather_hub_split: the hub rows of the in-edges, if any
             if ((rc = gatmh_hubs_for(c, In, 1, ld, ldk, &hubs))) return rc;
+            const int rform = gatmh_rows_gather_form(c, dst_bf16, K, D, ld, bf);
             HIPCK(c, launch_gatmh_rows_dst(c->N, K, D, ld, ldk, In.ptr, In.idx, dst_bf16 ? bf.xl : T.z->d,
                                            dst_bf16 ? bf.xg : (In.ghosts ? T.fgz->d : nullptr), T.el->d, In.ghosts ? T.fgel->d : nullptr, T.er->d,
-                                           c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, st4, lds4, c->compute, dst_bf16,
+                                           c->weights[T.fl]["a_l"].d, T.m->d, T.den->d, T.dO->d, T.tt->d, T.der->d, st4, lds4, c->compute, rform,
                                            &hubs));
             if (hubs.plan.nchunks) c->gatmh_hub_dst++;
             c->count[CNT_GATMH_ROWS_DST_EDGE]++;
-            if (dst_bf16) c->count[CNT_GATMH_ROWS_BF16_DST_EDGE]++;
+            if (dst_bf16) { c->count[CNT_GATMH_ROWS_BF16_DST_EDGE]++; gatmh_rows_wide_count(c, rform, &c->gatmh_rows8_dst); }
         }
     }
     if (T.phase == 1) return DORY_OK;
@@ -890,11 +907,12 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         if ((rc = gatmh_hubs_for(c, Out, 2, ld, ldk, &hubs))) return rc;   //  launch_gatmh_dattn below takes the scratch: one stream)
         if (src_bf16 && (rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather"))) return rc;
         const bool in_flight = c->halo_pending;
+        const int rform = gatmh_rows_gather_form(c, src_bf16, K, D, ld, bf);
         auto launch = [&](const GatmhHubs *h, const GatmhRowList *rows) -> int {
             HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
                                            src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
                                            Out.ghosts ? reinterpret_cast<const float4 *>(T.bgst->d) : nullptr, lds4, T.der->d,
-                                           c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, src_bf16, h, rows));
+                                           c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, rform, h, rows));
             return DORY_OK;
         };
         rc = around_halo(c, split, src_bf16 ? &bf : nullptr, [&]() -> int { return launch(&hubs, &first); }, [&]() -> int {
@@ -909,6 +927,7 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         if (src_bf16) {
             c->gatmh_bf16_gathers_src++;
             c->count[CNT_GATMH_ROWS_BF16_SRC]++;
+            gatmh_rows_wide_count(c, rform, &c->gatmh_rows8_src);
         }
     }
     HIPCK(c, launch_gatmh_dattn(c->N, K, D, ld, ldk, T.z->d, T.del->d, T.der->d, c->wgrads[T.fl]["a_l"].d,

@@ -304,6 +304,10 @@ struct dory_ctx {
     bool gatmh_rows_overlap = false;
     int gatmh_scores_pending = -1;   // the layer whose ghost sources' scores (fg_el / fg_er) wait for the exchange in flight; -1: none
     uint64_t gatmh_ovl_fwd = 0, gatmh_ovl_src = 0, gatmh_ovl_fwd_flight = 0, gatmh_ovl_src_flight = 0, gatmh_ovl_deferred = 0;
+    // dory_gatmh_row_gather_bf16_wide: the switch; the forward / destination-side edge / source-side passes that ran the wide bf16 form, and
+    // the bf16 passes of the family that ran narrow with the switch on (shape or alignment)
+    bool gatmh_rows_wide = false;
+    uint64_t gatmh_rows8_fwd = 0, gatmh_rows8_dst = 0, gatmh_rows8_src = 0, gatmh_rows8_narrow = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -737,20 +741,26 @@ struct GatmhRowList {
     // what computes them with the switch off); no chunk unit, no merge, no row skipped
     bool chunks = true;
 };
+// what the three launchers gather: fp32 rows; the shadow rows, four bf16 (8 bytes) per lane and edge; or -- dory_gatmh_row_gather_bf16_wide --
+// the shadow rows, eight bf16 (16 bytes) per lane and edge on half the lanes per row: the narrow bf16 form's bits.  The wide form
+// needs a shape of gatmh_rows8_form (gat_mh_shapes.hpp) and 16-byte aligned rows: gatmh_rows_wide_ok, else the launchers refuse it
+// (hipErrorInvalidValue) and the caller runs the narrow form
+enum GatmhRowsForm { GATMH_ROWS_FP32 = 0, GATMH_ROWS_BF16 = 1, GATMH_ROWS_BF16_WIDE = 2 };
+bool gatmh_rows_wide_ok(uint32_t K, uint32_t D, uint32_t ld, const void *rows, const void *ghost_rows);
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
-                                     hipStream_t s, bool bf16 = false /* z / zg: their shadow rows (launch_bf16_rows) */,
+                                     hipStream_t s, int form = GATMH_ROWS_FP32 /* bf16 forms: z / zg are their shadow rows (launch_bf16_rows) */,
                                      const GatmhHubs *hubs = nullptr, const GatmhRowList *list = nullptr);
 hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                  const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
-                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16 = false /* z / zg: their shadow rows */,
+                                 float4 *st4, uint32_t lds4, hipStream_t s, int form = GATMH_ROWS_FP32 /* bf16 forms: z / zg are their shadow rows */,
                                  const GatmhHubs *hubs = nullptr);
 hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
-                                 float *del, float *dz, hipStream_t s, bool bf16 = false /* d_o / dog: their shadow rows */,
+                                 float *del, float *dz, hipStream_t s, int form = GATMH_ROWS_FP32 /* bf16 forms: d_o / dog are their shadow rows */,
                                  const GatmhHubs *hubs = nullptr, const GatmhRowList *list = nullptr);
 // row-wise backward (single partition; feature-per-lane or (edge, head, piece)-per-lane kernels by shape)
 hipError_t launch_gatmh_backward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,

@@ -3,11 +3,13 @@
 #ifndef DORY_GAT_MH_HPP
 #define DORY_GAT_MH_HPP
 #include "ctx.hpp"
+#include "gat_mh_shapes.hpp"   // gatmh_shape_ok and the row-gather family's shape rules (host code asks them too)
 
 namespace dory {
 
 constexpr float GATMH_SLOPE = 0.2f;
 constexpr int GATMH_MAXC = 4;   // K*D <= 256 (row-wise kernels are instantiated for 1, 2 or 4 chunks of 64 floats)
+static_assert(64 * GATMH_MAXC == 256, "gatmh_shape_ok (gat_mh_shapes.hpp) states the bound as 256");
 
 __device__ __forceinline__ float lrelu02(float x) { return x > 0.f ? x : GATMH_SLOPE * x; }
 // one DPP move inside the VALU (CTRL: a quad_perm, row_half_mirror 0x141, row_mirror 0x140)
@@ -21,13 +23,6 @@ struct GatMhArgs {
     const uint64_t *ptr;   // CSC (forward / dst pass) or CSR (src pass)
     const uint32_t *idx;
 };
-
-// K heads of D features fit the kernels: K*D <= 256, D a power of two <= 64 unless there is a single head
-inline bool gatmh_shape_ok(uint32_t K, uint32_t D) {
-    if (K == 0 || D == 0 || K > 64 || (uint64_t)K * D > 64 * GATMH_MAXC) return false;
-    if (K == 1) return true;
-    return (D & (D - 1)) == 0 && D <= 64;   // per-head reductions are xor-shuffles inside D lanes
-}
 
 }  // namespace dory
 #endif

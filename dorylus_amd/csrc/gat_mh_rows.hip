@@ -69,7 +69,7 @@
 // (the list is a template parameter of RowsWork and a kernel argument of the list kernels alone).  The destination-side edge pass reads
 // fg_z, which landed during the forward: no exchange to hide behind, no list form.  Its measurement: tools/gatmh_row_gather_overlap_rate.py.
 //
-// Not taken here: a wide (16-byte) bf16 form.
+// The wide (16-byte) bf16 form (dory_gatmh_row_gather_bf16_wide): the gatmh_rows8_*_kernel section below.
 #include "gat_mh.hpp"
 #include "spmm_common.hpp"
 
@@ -225,13 +225,22 @@ __device__ __forceinline__ float4 rows_attn4(const RowsLane<GROUP, HPQ> &L, cons
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------
-template <int HPQ>
+// W: float4s per lane -- 1, or 2 in the wide bf16 form (gatmh_rows8_*_kernel below: a lane stands for two lanes of this form and
+// keeps the second one's float4 in the *1 members, x[NB + u] beside x[u]; everything of it is behind `if constexpr (W == 2)`)
+// the wide form's in-lane addition of its two float4s' dot-product chains: the butterfly's offset-1 step, kept off any contraction
+// with the chains' own operations (the narrow form adds after a DPP move)
+__device__ __forceinline__ float rows8_add(float x, float y) {
+#pragma clang fp contract(off)
+    return x + y;
+}
+template <int HPQ, int W = 1>
 struct RowsFwdState {
     float erv[HPQ], mx[HPQ], den[HPQ], denp[HPQ];
     float4 acc, accp;
+    float4 acc1, accp1;   // (W == 2)
     // NB edges at once: the maximum moves once, the sums are rescaled once
     template <int NB>
-    __device__ __forceinline__ void step(const float4 (&x)[NB], const float (&sc)[NB][HPQ]) {
+    __device__ __forceinline__ void step(const float4 (&x)[NB * W], const float (&sc)[NB][HPQ]) {
         float al[NB][HPQ], alp[NB][HPQ], f[HPQ];
 #pragma unroll
         for (int s = 0; s < HPQ; ++s) {
@@ -260,12 +269,21 @@ struct RowsFwdState {
             acc = rows_axpy<HPQ>(al[u], x[u], acc);
             accp = rows_axpy<HPQ>(alp[u], x[u], accp);
         }
+        if constexpr (W == 2) {
+            acc1 = rows_scale<HPQ>(f, acc1);
+            accp1 = rows_scale<HPQ>(f, accp1);
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                acc1 = rows_axpy<HPQ>(al[u], x[NB + u], acc1);
+                accp1 = rows_axpy<HPQ>(alp[u], x[NB + u], accp1);
+            }
+        }
     }
 };
 
 // the one-pass epilogue: normalise and store o, op, m, den, dpos of row L.v (also the hub rows' merge kernel's)
-template <int GROUP, int HPQ>
-__device__ __forceinline__ void rows_fwd_store(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, const RowsFwdState<HPQ> &S, float *o, float *op,
+template <int GROUP, int HPQ, int W>
+__device__ __forceinline__ void rows_fwd_store(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, const RowsFwdState<HPQ, W> &S, float *o, float *op,
                                                float *m_out, float *den_out, float *dpos_out) {
     if (!L.lane_ok) return;
     float idn[HPQ];
@@ -455,15 +473,23 @@ __global__ __launch_bounds__(256) void gatmh_rows_forward_list_hub_bf16_kernel(G
 }
 
 // ---- backward, destination side: t[v,k] = sum a*da, der[v,k] = sum a*da*l' - t * sum a*l', st = (er, m, 1/den, t) -------------------
-template <int HPQ>
+template <int HPQ, int W = 1>
 struct RowsDstState {
     float erv[HPQ], mv[HPQ], idn[HPQ], t[HPQ], a1[HPQ], a2[HPQ];
     float4 g;   // dO[v], padding columns zeroed
+    float4 g1;  // (W == 2)
     template <int NB>
-    __device__ __forceinline__ void step(const float4 (&x)[NB], const float (&sc)[NB][HPQ], int HL) {
+    __device__ __forceinline__ void step(const float4 (&x)[NB * W], const float (&sc)[NB][HPQ], int HL) {
         float prod[NB][HPQ];
 #pragma unroll
         for (int u = 0; u < NB; ++u) rows_dot<HPQ>(g, x[u], prod[u]);
+        if constexpr (W == 2)
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                float p1[HPQ];
+                rows_dot<HPQ>(g1, x[NB + u], p1);
+                prod[u][0] = rows8_add(prod[u][0], p1[0]);
+            }
         if constexpr (HPQ == 1)
 #pragma unroll
             for (int u = 0; u < NB; ++u) prod[u][0] = rows_allreduce(prod[u][0], HL);
@@ -482,8 +508,8 @@ struct RowsDstState {
 };
 
 // the one-pass epilogue of the destination side: t, der, st of row L.v (also the hub rows' merge kernel's)
-template <int GROUP, int HPQ>
-__device__ __forceinline__ void rows_dst_store(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, const RowsDstState<HPQ> &S, float *t_out,
+template <int GROUP, int HPQ, int W>
+__device__ __forceinline__ void rows_dst_store(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, const RowsDstState<HPQ, W> &S, float *t_out,
                                                float *der_out, float4 *st4, uint32_t lds4) {
 #pragma unroll
     for (int s = 0; s < HPQ; ++s)
@@ -625,12 +651,13 @@ __global__ __launch_bounds__(256) void gatmh_rows_dst_bf16_kernel(GatMhArgs a, i
 }
 
 // ---- backward, source side: rows = sources u (out-edges), entries = destinations v (local: do / st, ghost: bg_do / bg_st) ---------
-template <int HPQ>
+template <int HPQ, int W = 1>
 struct RowsSrcState {
     float elu[HPQ], T[HPQ], Tp[HPQ];
     float4 S, Sp;
+    float4 S1, Sp1;   // (W == 2)
     template <int NB>
-    __device__ __forceinline__ void step(const float4 (&x)[NB], const float4 (&rec)[NB][HPQ]) {
+    __device__ __forceinline__ void step(const float4 (&x)[NB * W], const float4 (&rec)[NB][HPQ]) {
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
             float al[HPQ], alp[HPQ];
@@ -645,6 +672,10 @@ struct RowsSrcState {
             }
             S = rows_axpy<HPQ>(al, x[u], S);
             Sp = rows_axpy<HPQ>(alp, x[u], Sp);
+            if constexpr (W == 2) {
+                S1 = rows_axpy<HPQ>(al, x[NB + u], S1);
+                Sp1 = rows_axpy<HPQ>(alp, x[NB + u], Sp1);
+            }
         }
     }
 };
@@ -654,9 +685,11 @@ struct RowsSrcState {
 // in all -- past the 128 that leave four waves per SIMD (what a latency-bound gather lives on; tests/test_gatmh_row_gather_resources.py)
 // the one-pass closing arithmetic of the source side: del and dz of row L.v from its sums (also the hub rows' merge kernel's; every
 // lane of a live group arrives: the head's lanes reduce the dot product)
-template <int GROUP, int HPQ>
-__device__ __forceinline__ void rows_src_close(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, int HL, const RowsSrcState<HPQ> &S, const float *z,
-                                               const float *der, const float *a_l, const float *a_r, float *del_out, float *dz) {
+// (W == 2, the wide bf16 form: L is the lane of its first float4, L1 that of its second -- the same row and head)
+template <int GROUP, int HPQ, int W>
+__device__ __forceinline__ void rows_src_close(const RowsLane<GROUP, HPQ> &L, const GatMhArgs &a, int HL, const RowsSrcState<HPQ, W> &S, const float *z,
+                                               const float *der, const float *a_l, const float *a_r, float *del_out, float *dz,
+                                               const RowsLane<GROUP, HPQ> *L1 = nullptr) {
     // del[u,k] = <Z[u,k,:], 0.2 S + 0.8 S+> - (0.2 T + 0.8 T+)
     const float lo = GATMH_SLOPE, hi = 1.f - GATMH_SLOPE;
     const float4 zz = rows_mask(reinterpret_cast<const float4 *>(z)[(size_t)L.v * L.nchunk + L.col], L.cm);
@@ -664,6 +697,14 @@ __device__ __forceinline__ void rows_src_close(const RowsLane<GROUP, HPQ> &L, co
                                    fmaf(hi, S.Sp.w, lo * S.S.w));
     float dd[HPQ];
     rows_dot<HPQ>(zz, mix, dd);
+    if constexpr (W == 2) {
+        const float4 zz1 = rows_mask(reinterpret_cast<const float4 *>(z)[(size_t)L1->v * L1->nchunk + L1->col], L1->cm);
+        const float4 mix1 = make_float4(fmaf(hi, S.Sp1.x, lo * S.S1.x), fmaf(hi, S.Sp1.y, lo * S.S1.y), fmaf(hi, S.Sp1.z, lo * S.S1.z),
+                                        fmaf(hi, S.Sp1.w, lo * S.S1.w));
+        float d1[HPQ];
+        rows_dot<HPQ>(zz1, mix1, d1);
+        dd[0] = rows8_add(dd[0], d1[0]);
+    }
     if constexpr (HPQ == 1) dd[0] = rows_allreduce(dd[0], HL);
     if (!L.lane_ok) return;
     const uint32_t KD = a.K * a.D;
@@ -687,6 +728,19 @@ __device__ __forceinline__ void rows_src_close(const RowsLane<GROUP, HPQ> &L, co
 #pragma unroll
     for (int s = 0; s < HPQ; ++s)
         if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) del_out[(size_t)L.v * a.ldk + L.hk[s]] = del[s];
+    if constexpr (W == 2) {
+        if (!L1->lane_ok) return;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t f = min(4 * L1->col + c, KD - 1);
+            al4[c] = a_l[f];
+            ar4[c] = a_r[f];
+        }
+        float4 out1 = S.S1;
+        out1 = rows_axpy<HPQ>(del, make_float4(al4[0], al4[1], al4[2], al4[3]), out1);
+        out1 = rows_axpy<HPQ>(dr, make_float4(ar4[0], ar4[1], ar4[2], ar4[3]), out1);
+        reinterpret_cast<float4 *>(dz)[(size_t)L1->v * L1->nchunk + L1->col] = rows_mask(out1, L1->cm);
+    }
 }
 
 template <int GROUP, int HPQ, int NB, bool HUBS, bool LIST, class CHUNK>
@@ -839,10 +893,287 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_list_hub_bf16_kernel(GatMh
     gatmh_rows_src_body<GROUP, HPQ, NB, true, true>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, H, R);
 }
 
+// ---- the wide bf16 form (dory_gatmh_row_gather_bf16_wide; gatmh_rows8_*_kernel) -----------------------------------------------------
+// A lane keeps EIGHT consecutive features: one 16-byte load of eight bf16 per edge, two float4 accumulators wherever the narrow form
+// has one -- the lane stands for the narrow form's lanes 2 li and 2 li + 1 (Rows8Lane::lo / hi), so a row takes 8 / 16 / 32 lanes
+// (gatmh_rows8_form, gat_mh_shapes.hpp), a wave has twice the rows in flight, and the heads' exponentials are computed by half as
+// many lanes.  One head per lane (a single head, or D % 8 == 0).  Everything else is the narrow form's: units, id blocks (a
+// multiple of four entries in both forms: batches, masked tails and the moments the maximum moves coincide), ghost ids, 64-bit
+// addressing, hub chunks and row lists.  The contract is the narrow bf16 kernels' BITS in every tensor:
+//   * the state structs and epilogues above are the narrow form's, W = 2: their `if constexpr (W == 2)` parts repeat, for the second
+//     float4, the calls made for the first -- per column the same fmaf chains in entry order;
+//   * per head, the values are the structs' one scalar chain, run once a lane;
+//   * a dot product is, per float4, the narrow lane's four-term chain (rows_el / rows_dot with nothing reduced);
+//     the two are added in the lane (rows8_add: the butterfly's offset-1 step, a + b where the narrow lanes form a + b and b + a, kept
+//     off any contraction -- the narrow form adds after a DPP move) and reduced by rows_allreduce over half as many lanes, whose
+//     offsets 1, 2, 4 are the narrow form's 2, 4, 8.
+// A hub row's chunk states keep their layout (lane li writes what lanes 2 li and 2 li + 1 write): the narrow merge kernels follow a
+// wide chunk launch.
+// the narrow form's lane that keeps float4 `lane` of the row: RowsLane's values for that place
+template <int GROUP>
+__device__ __forceinline__ RowsLane<GROUP, 1> rows8_half(const GatMhArgs &a, uint32_t rid, bool ok, uint32_t lane) {
+    RowsLane<GROUP, 1> L(a, rid, ok);
+    const uint32_t KD = a.K * a.D;
+    L.li = lane;
+    L.lane_ok = L.row_ok && lane < L.nchunk && 4 * lane < KD;
+    L.col = lane < L.nchunk ? lane : 0;
+    L.hk[0] = min((4 * L.col) / a.D, a.K - 1);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) L.cm[c] = L.lane_ok && 4 * L.col + c < KD;
+    return L;
+}
+template <int GROUP>
+struct Rows8Lane {
+    RowsLane<GROUP, 1> lo, hi;
+    uint32_t li, nchunk8, col8;
+    __device__ __forceinline__ Rows8Lane(const GatMhArgs &a, uint32_t rid, bool ok, uint32_t lane = (uint32_t)((threadIdx.x & 63) % GROUP))
+        : lo(rows8_half<GROUP>(a, rid, ok, 2 * lane)), hi(rows8_half<GROUP>(a, rid, ok, 2 * lane + 1)), li(lane) {
+        nchunk8 = a.ld >> 3;
+        col8 = li < nchunk8 ? li : 0;         // lanes past the row gather column 0 (valid memory) and never store
+    }
+};
+// the source's score of the lane's head from the gathered row: rows_el's value (al0 / al1: a_l's columns of the two float4s)
+__device__ __forceinline__ float rows8_el(const float4 &x0, const float4 &x1, const float4 &al0, const float4 &al1, int HL) {
+    float p0[1], p1[1];
+    rows_el<1>(x0, al0, 1, p0);
+    rows_el<1>(x1, al1, 1, p1);
+    return rows_allreduce(rows8_add(p0[0], p1[0]), HL);
+}
+
+template <int GROUP, bool ELFLY, bool HUBS, bool LIST>
+__device__ __forceinline__ void gatmh_rows8_forward_body(const GatMhArgs &a, int HL, const uint4 *z8, const uint4 *zg8, const float *el,
+                                                         const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                         float *m_out, float *den_out, float *dpos_out, const RowsHubArgs &H,
+                                                         const RowsListArgs &R = RowsListArgs{}) {
+    const RowsWork<GROUP, HUBS, LIST> W(a, H, R);
+    const Rows8Lane<GROUP> L(a, W.row, W.ok);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 al0 = ELFLY ? rows_attn4(L.lo, a, a_l) : zero4, al1 = ELFLY ? rows_attn4(L.hi, a, a_l) : zero4;
+    RowsFwdState<1, 2> S;
+    S.erv[0] = er[(size_t)L.lo.v * a.ldk + L.lo.hk[0]];
+    S.mx[0] = -INFINITY;
+    S.den[0] = S.denp[0] = 0.f;
+    S.acc = S.accp = S.acc1 = S.accp1 = zero4;
+    uint64_t e0, end, total;
+    const bool live = W.entries(a, L.lo, H, e0, end, total);
+    for (uint64_t done = 0; done < total; done += GROUP) {
+        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+        const uint64_t ee = e0 + done + L.li;
+        const uint32_t my_idx = ee < end ? a.idx[ee] : L.lo.v;
+        for (int j = 0; j < n; j += 4) {
+            float4 x[8];      // x[u], x[4 + u]: the two float4s of row u of the batch
+            float sc[4][1];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                const bool loc = s < a.N;
+                const size_t r = loc ? s : s - a.N;
+                row_chunk((loc ? z8 : zg8)[r * L.nchunk8 + L.col8], x[u], x[4 + u]);
+                if constexpr (!ELFLY) sc[u][0] = ((loc ? el : elg) + r * a.ldk)[L.lo.hk[0]];
+            }
+            if constexpr (ELFLY)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) sc[u][0] = rows8_el(x[u], x[4 + u], al0, al1, HL);
+#pragma unroll
+            for (int u = 1; u < 4; ++u) sc[u][0] = j + u < n ? sc[u][0] : -INFINITY;
+            S.template step<4>(x, sc);
+        }
+    }
+    if (!live) return;
+    if constexpr (HUBS)
+        if (W.part) {   // a chunk of a hub row: its state where the narrow form's lanes leave it, for gatmh_rows_forward_merge_kernel
+            if (L.lo.li >= L.lo.nchunk) return;
+            float *sp = H.state + (size_t)W.slot * rows_hub_stride(0, a.ld, a.ldk), *hp = sp + 2 * (size_t)a.ld;
+            reinterpret_cast<float4 *>(sp)[L.lo.col] = S.acc;
+            reinterpret_cast<float4 *>(sp)[L.hi.col] = S.acc1;
+            reinterpret_cast<float4 *>(sp + a.ld)[L.lo.col] = S.accp;
+            reinterpret_cast<float4 *>(sp + a.ld)[L.hi.col] = S.accp1;
+            if (L.lo.leader(a)) {
+                hp[L.lo.hk[0]] = S.mx[0];
+                hp[a.ldk + L.lo.hk[0]] = S.den[0];
+                hp[2 * a.ldk + L.lo.hk[0]] = S.denp[0];
+            }
+            return;
+        }
+    // the narrow epilogue per float4 (the second one's lane is no head's leader: it stores its float4 of o and op alone)
+    rows_fwd_store(L.lo, a, S, o, op, m_out, den_out, dpos_out);
+    RowsFwdState<1> Sh;
+    Sh.mx[0] = S.mx[0]; Sh.den[0] = S.den[0]; Sh.denp[0] = S.denp[0];
+    Sh.acc = S.acc1; Sh.accp = S.accp1;
+    rows_fwd_store(L.hi, a, Sh, o, op, m_out, den_out, dpos_out);
+}
+#define GATMH_ROWS8_FWD_PARAMS                                                                                                        \
+    GatMhArgs a, int HL, const uint4 *zb, const uint4 *zgb, const float *el, const float *elg, const float *er, const float *a_l, float *o, \
+        float *op, float *m_out, float *den_out, float *dpos_out
+#define GATMH_ROWS8_FWD_ARGS a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out
+template <int GROUP, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows8_forward_kernel(GATMH_ROWS8_FWD_PARAMS) {
+    gatmh_rows8_forward_body<GROUP, ELFLY, false, false>(GATMH_ROWS8_FWD_ARGS, RowsHubArgs{});
+}
+template <int GROUP, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows8_forward_hub_kernel(GATMH_ROWS8_FWD_PARAMS, RowsHubArgs H) {
+    gatmh_rows8_forward_body<GROUP, ELFLY, true, false>(GATMH_ROWS8_FWD_ARGS, H);
+}
+template <int GROUP, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows8_forward_list_kernel(GATMH_ROWS8_FWD_PARAMS, RowsListArgs R) {
+    gatmh_rows8_forward_body<GROUP, ELFLY, false, true>(GATMH_ROWS8_FWD_ARGS, RowsHubArgs{}, R);
+}
+template <int GROUP, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows8_forward_list_hub_kernel(GATMH_ROWS8_FWD_PARAMS, RowsHubArgs H, RowsListArgs R) {
+    gatmh_rows8_forward_body<GROUP, ELFLY, true, true>(GATMH_ROWS8_FWD_ARGS, H, R);
+}
+#undef GATMH_ROWS8_FWD_PARAMS
+#undef GATMH_ROWS8_FWD_ARGS
+
+template <int GROUP, bool ELFLY, bool HUBS>
+__device__ __forceinline__ void gatmh_rows8_dst_body(const GatMhArgs &a, int HL, const uint4 *z8, const uint4 *zg8, const float *el,
+                                                     const float *elg, const float *er, const float *a_l, const float *m_in,
+                                                     const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4,
+                                                     uint32_t lds4, const RowsHubArgs &H) {
+    const RowsWork<GROUP, HUBS, false> W(a, H, RowsListArgs{});
+    const Rows8Lane<GROUP> L(a, W.row, W.ok);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 al0 = ELFLY ? rows_attn4(L.lo, a, a_l) : zero4, al1 = ELFLY ? rows_attn4(L.hi, a, a_l) : zero4;
+    RowsDstState<1, 2> S;     // (S.g / S.g1: dO[v]'s two float4s, padding columns zeroed)
+    const size_t vk = (size_t)L.lo.v * a.ldk + L.lo.hk[0];
+    S.erv[0] = er[vk];
+    S.mv[0] = m_in[vk];
+    S.idn[0] = 1.f / den_in[vk];
+    S.t[0] = S.a1[0] = S.a2[0] = 0.f;
+    S.g = rows_mask(reinterpret_cast<const float4 *>(d_o)[(size_t)L.lo.v * L.lo.nchunk + L.lo.col], L.lo.cm);
+    S.g1 = rows_mask(reinterpret_cast<const float4 *>(d_o)[(size_t)L.hi.v * L.hi.nchunk + L.hi.col], L.hi.cm);
+    uint64_t e0, end, total;
+    const bool live = W.entries(a, L.lo, H, e0, end, total);
+    for (uint64_t done = 0; done < total; done += GROUP) {
+        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+        const uint64_t ee = e0 + done + L.li;
+        const uint32_t my_idx = ee < end ? a.idx[ee] : L.lo.v;
+        for (int j = 0; j < n; j += 4) {
+            float4 x[8];
+            float sc[4][1];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                const bool loc = s < a.N;
+                const size_t r = loc ? s : s - a.N;
+                row_chunk((loc ? z8 : zg8)[r * L.nchunk8 + L.col8], x[u], x[4 + u]);
+                if constexpr (!ELFLY) sc[u][0] = ((loc ? el : elg) + r * a.ldk)[L.lo.hk[0]];
+            }
+            if constexpr (ELFLY)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) sc[u][0] = rows8_el(x[u], x[4 + u], al0, al1, HL);
+#pragma unroll
+            for (int u = 1; u < 4; ++u) sc[u][0] = j + u < n ? sc[u][0] : -INFINITY;
+            S.template step<4>(x, sc, HL);
+        }
+    }
+    if (!live) return;
+    if constexpr (HUBS)
+        if (W.part) {   // a chunk of a hub row: its partial (t, a1, a2), for gatmh_rows_dst_merge_kernel
+            float *hp = H.state + (size_t)W.slot * rows_hub_stride(1, a.ld, a.ldk);
+            if (L.lo.leader(a)) {
+                hp[L.lo.hk[0]] = S.t[0];
+                hp[a.ldk + L.lo.hk[0]] = S.a1[0];
+                hp[2 * a.ldk + L.lo.hk[0]] = S.a2[0];
+            }
+            return;
+        }
+    rows_dst_store(L.lo, a, S, t_out, der_out, st4, lds4);
+}
+#define GATMH_ROWS8_DST_PARAMS                                                                                                        \
+    GatMhArgs a, int HL, const uint4 *zb, const uint4 *zgb, const float *el, const float *elg, const float *er, const float *a_l,     \
+        const float *m_in, const float *den_in, const float *d_o, float *t_out, float *der_out, float4 *st4, uint32_t lds4
+#define GATMH_ROWS8_DST_ARGS a, HL, zb, zgb, el, elg, er, a_l, m_in, den_in, d_o, t_out, der_out, st4, lds4
+template <int GROUP, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows8_dst_kernel(GATMH_ROWS8_DST_PARAMS) {
+    gatmh_rows8_dst_body<GROUP, ELFLY, false>(GATMH_ROWS8_DST_ARGS, RowsHubArgs{});
+}
+template <int GROUP, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows8_dst_hub_kernel(GATMH_ROWS8_DST_PARAMS, RowsHubArgs H) {
+    gatmh_rows8_dst_body<GROUP, ELFLY, true>(GATMH_ROWS8_DST_ARGS, H);
+}
+#undef GATMH_ROWS8_DST_PARAMS
+#undef GATMH_ROWS8_DST_ARGS
+
+// the source side: four destination rows in flight (one head per lane: a batch holds four statistics records)
+template <int GROUP, bool HUBS, bool LIST>
+__device__ __forceinline__ void gatmh_rows8_src_body(const GatMhArgs &a, int HL, const float *z, const float *el, const uint4 *d8,
+                                                     const uint4 *dg8, const float4 *st4, const float4 *stg, uint32_t lds4, const float *der,
+                                                     const float *a_l, const float *a_r, float *del_out, float *dz, const RowsHubArgs &H,
+                                                     const RowsListArgs &R = RowsListArgs{}) {
+    constexpr int NB = 4;
+    const RowsWork<GROUP, HUBS, LIST> W(a, H, R);
+    const Rows8Lane<GROUP> L(a, W.row, W.ok);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    RowsSrcState<1, 2> S;
+    S.elu[0] = el[(size_t)L.lo.v * a.ldk + L.lo.hk[0]];
+    S.T[0] = S.Tp[0] = 0.f;
+    S.S = S.Sp = S.S1 = S.Sp1 = zero4;
+    uint64_t e0, end, total;
+    const bool live = W.entries(a, L.lo, H, e0, end, total);
+    for (uint64_t done = 0; done < total; done += GROUP) {
+        const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+        const uint64_t ee = e0 + done + L.li;
+        const uint32_t my_idx = ee < end ? a.idx[ee] : L.lo.v;
+        for (int j = 0; j < n; j += NB) {
+            float4 x[2 * NB], rec[NB][1];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                const bool loc = s < a.N;
+                const size_t r = loc ? s : s - a.N;
+                row_chunk((loc ? d8 : dg8)[r * L.nchunk8 + L.col8], x[u], x[NB + u]);
+                rec[u][0] = ((loc ? st4 : stg) + r * lds4)[L.lo.hk[0]];
+            }
+#pragma unroll
+            for (int u = 1; u < NB; ++u) rec[u][0].x = j + u < n ? rec[u][0].x : -INFINITY;
+            S.template step<NB>(x, rec);
+        }
+    }
+    if (!live) return;
+    if constexpr (HUBS)
+        if (W.part) {   // a chunk of a hub row: its partial sums where the narrow form's lanes leave them, for gatmh_rows_src_merge_kernel
+            if (L.lo.li >= L.lo.nchunk) return;
+            float *sp = H.state + (size_t)W.slot * rows_hub_stride(2, a.ld, a.ldk), *hp = sp + 2 * (size_t)a.ld;
+            reinterpret_cast<float4 *>(sp)[L.lo.col] = S.S;
+            reinterpret_cast<float4 *>(sp)[L.hi.col] = S.S1;
+            reinterpret_cast<float4 *>(sp + a.ld)[L.lo.col] = S.Sp;
+            reinterpret_cast<float4 *>(sp + a.ld)[L.hi.col] = S.Sp1;
+            if (L.lo.leader(a)) {
+                hp[L.lo.hk[0]] = S.T[0];
+                hp[a.ldk + L.lo.hk[0]] = S.Tp[0];
+            }
+            return;
+        }
+    rows_src_close(L.lo, a, HL, S, z, der, a_l, a_r, del_out, dz, &L.hi);
+}
+#define GATMH_ROWS8_SRC_PARAMS                                                                                                        \
+    GatMhArgs a, int HL, const float *z, const float *el, const uint4 *dob, const uint4 *dogb, const float4 *st4, const float4 *stg,  \
+        uint32_t lds4, const float *der, const float *a_l, const float *a_r, float *del_out, float *dz
+#define GATMH_ROWS8_SRC_ARGS a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz
+template <int GROUP>
+__global__ __launch_bounds__(256) void gatmh_rows8_src_kernel(GATMH_ROWS8_SRC_PARAMS) {
+    gatmh_rows8_src_body<GROUP, false, false>(GATMH_ROWS8_SRC_ARGS, RowsHubArgs{});
+}
+template <int GROUP>
+__global__ __launch_bounds__(256) void gatmh_rows8_src_hub_kernel(GATMH_ROWS8_SRC_PARAMS, RowsHubArgs H) {
+    gatmh_rows8_src_body<GROUP, true, false>(GATMH_ROWS8_SRC_ARGS, H);
+}
+template <int GROUP>
+__global__ __launch_bounds__(256) void gatmh_rows8_src_list_kernel(GATMH_ROWS8_SRC_PARAMS, RowsListArgs R) {
+    gatmh_rows8_src_body<GROUP, false, true>(GATMH_ROWS8_SRC_ARGS, RowsHubArgs{}, R);
+}
+template <int GROUP>
+__global__ __launch_bounds__(256) void gatmh_rows8_src_list_hub_kernel(GATMH_ROWS8_SRC_PARAMS, RowsHubArgs H, RowsListArgs R) {
+    gatmh_rows8_src_body<GROUP, true, true>(GATMH_ROWS8_SRC_ARGS, H, R);
+}
+#undef GATMH_ROWS8_SRC_PARAMS
+#undef GATMH_ROWS8_SRC_ARGS
+
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
 // lanes per row and heads per float4 of a shape; false: a shape the model does not allow (gatmh_shape_ok) or rows no float4 tiles
 static bool gatmh_rows_form(uint32_t K, uint32_t D, uint32_t ld, int *group, int *hpq, int *HL) {
-    if (!gatmh_shape_ok(K, D) || (ld & 3) || ld == 0 || ld > 256 || K * D > ld) return false;
+    if (!gatmh_rows_shape_ok(K, D, ld)) return false;
     const uint32_t nchunk = ld >> 2;
     *group = nchunk <= 8 ? 8 : nchunk <= 16 ? 16 : nchunk <= 32 ? 32 : 64;
     *hpq = (K == 1 || (D & 3) == 0) ? 1 : D == 2 ? 2 : 4;     // (K > 1: D is a power of two)
@@ -899,14 +1230,154 @@ static bool gatmh_rows_split(const GatmhHubs *hubs, uint32_t N, uint32_t rpb, Ro
     return true;
 }
 
+// ---- the wide bf16 form's launches: what the launchers below do with GATMH_ROWS_BF16_WIDE.  `group` / HL: the narrow form's, for the
+// hub rows' merge kernels (unchanged: the chunk states have the narrow layout)
+bool gatmh_rows_wide_ok(uint32_t K, uint32_t D, uint32_t ld, const void *rows, const void *ghost_rows) {
+    uint32_t lr, lh;
+    int el;
+    return gatmh_rows_ok(K, D, ld) && gatmh_rows8_form(K, D, ld, &lr, &lh, &el) && !(((uintptr_t)rows | (uintptr_t)ghost_rows) & 15);
+}
+struct Rows8Launch {
+    int g8, hl8;
+    bool elfly;
+    uint32_t rpb8, rpb;
+    dim3 bl{256};
+    // false: not a shape of the wide form, or rows that are not 16-byte aligned (the callers ask gatmh_rows_wide_ok first)
+    bool plan(const GatMhArgs &a, int group, const void *rows, const void *ghost_rows) {
+        uint32_t lr, lh;
+        int el;
+        if (!gatmh_rows_wide_ok(a.K, a.D, a.ld, rows, ghost_rows) || !gatmh_rows8_form(a.K, a.D, a.ld, &lr, &lh, &el)) return false;
+        g8 = (int)lr; hl8 = (int)lh; elfly = el != 0;
+        rpb8 = 4 * (64 / lr); rpb = 4 * (64 / (uint32_t)group);
+        return true;
+    }
+    dim3 merge_grid(uint32_t nrows) const { return dim3((nrows + rpb - 1) / rpb); }
+};
+#define GATMH_ROWS8_FORMS_EL(F)                                                                                                     \
+    do {                                                                                                                            \
+        if (W.elfly) { if (W.g8 == 8) F(8, true); else if (W.g8 == 16) F(16, true); else F(32, true); }                            \
+        else { if (W.g8 == 16) F(16, false); else F(32, false); }                                                                   \
+    } while (0)
+#define GATMH_ROWS8_FORMS(F)                                                                                                        \
+    do { if (W.g8 == 8) F(8); else if (W.g8 == 16) F(16); else F(32); } while (0)
+
+static hipError_t launch_rows8_forward(const GatMhArgs &a, int group, int HL, const float *z, const float *zg, const float *el, const float *elg,
+                                       const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos, hipStream_t s,
+                                       const GatmhHubs *hubs, const GatmhRowList *list) {
+    Rows8Launch W;
+    if (!W.plan(a, group, z, zg)) return hipErrorInvalidValue;
+    const uint4 *zb = reinterpret_cast<const uint4 *>(z), *zgb = reinterpret_cast<const uint4 *>(zg);
+    const int hpq = 1;
+    RowsHubArgs HA;
+    RowsListArgs LA;
+    dim3 gh, gm;
+    bool hubform = false, merge = false;
+    if (list) {
+        gatmh_rows_listed(hubs, *list, W.rpb8, &HA, &LA, &gh, &gm, &hubform, &merge);
+        if (gh.x == 0) return hipSuccess;
+#define F(G, E)                                                                                                                     \
+    do {                                                                                                                            \
+        if (hubform) hipLaunchKernelGGL((gatmh_rows8_forward_list_hub_kernel<G, E>), gh, W.bl, 0, s, a, W.hl8, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos, HA, LA); \
+        else hipLaunchKernelGGL((gatmh_rows8_forward_list_kernel<G, E>), gh, W.bl, 0, s, a, W.hl8, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos, LA); \
+    } while (0)
+        GATMH_ROWS8_FORMS_EL(F);
+#undef F
+    } else if ((merge = gatmh_rows_split(hubs, a.N, W.rpb8, &HA, &gh, &gm))) {
+#define F(G, E) hipLaunchKernelGGL((gatmh_rows8_forward_hub_kernel<G, E>), gh, W.bl, 0, s, a, W.hl8, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos, HA)
+        GATMH_ROWS8_FORMS_EL(F);
+#undef F
+    } else {
+        const dim3 gr((a.N + W.rpb8 - 1) / W.rpb8);
+#define F(G, E) hipLaunchKernelGGL((gatmh_rows8_forward_kernel<G, E>), gr, W.bl, 0, s, a, W.hl8, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos)
+        GATMH_ROWS8_FORMS_EL(F);
+#undef F
+    }
+    if (!merge) return hipGetLastError();
+    gm = W.merge_grid(HA.nrows);
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_forward_merge_kernel<G, H>), gm, W.bl, 0, s, a, o, op, m, den, dpos, HA)
+    GATMH_ROWS_FORMS(F);
+#undef F
+    (void)HL;
+    return hipGetLastError();
+}
+
+static hipError_t launch_rows8_dst(const GatMhArgs &a, int group, const float *z, const float *zg, const float *el, const float *elg,
+                                   const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
+                                   float4 *st4, uint32_t lds4, hipStream_t s, const GatmhHubs *hubs) {
+    Rows8Launch W;
+    if (!W.plan(a, group, z, zg)) return hipErrorInvalidValue;
+    const uint4 *zb = reinterpret_cast<const uint4 *>(z), *zgb = reinterpret_cast<const uint4 *>(zg);
+    const int hpq = 1;
+    RowsHubArgs HA;
+    dim3 gh, gm;
+    if (!gatmh_rows_split(hubs, a.N, W.rpb8, &HA, &gh, &gm)) {
+        const dim3 gr((a.N + W.rpb8 - 1) / W.rpb8);
+#define F(G, E) hipLaunchKernelGGL((gatmh_rows8_dst_kernel<G, E>), gr, W.bl, 0, s, a, W.hl8, zb, zgb, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4)
+        GATMH_ROWS8_FORMS_EL(F);
+#undef F
+        return hipGetLastError();
+    }
+#define F(G, E) hipLaunchKernelGGL((gatmh_rows8_dst_hub_kernel<G, E>), gh, W.bl, 0, s, a, W.hl8, zb, zgb, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4, HA)
+    GATMH_ROWS8_FORMS_EL(F);
+#undef F
+    gm = W.merge_grid(HA.nrows);
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_dst_merge_kernel<G, H>), gm, W.bl, 0, s, a, er, m, den, t, der, st4, lds4, HA)
+    GATMH_ROWS_FORMS(F);
+#undef F
+    return hipGetLastError();
+}
+
+static hipError_t launch_rows8_src(const GatMhArgs &a, int group, int HL, const float *z, const float *el, const float *d_o, const float *dog,
+                                   const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
+                                   float *del, float *dz, hipStream_t s, const GatmhHubs *hubs, const GatmhRowList *list) {
+    Rows8Launch W;
+    if (!W.plan(a, group, d_o, dog)) return hipErrorInvalidValue;
+    const uint4 *dob = reinterpret_cast<const uint4 *>(d_o), *dogb = reinterpret_cast<const uint4 *>(dog);
+    const int hpq = 1;
+    RowsHubArgs HA;
+    RowsListArgs LA;
+    dim3 gh, gm;
+    bool hubform = false, merge = false;
+    if (list) {
+        gatmh_rows_listed(hubs, *list, W.rpb8, &HA, &LA, &gh, &gm, &hubform, &merge);
+        if (gh.x == 0) return hipSuccess;
+#define F(G)                                                                                                                        \
+    do {                                                                                                                            \
+        if (hubform) hipLaunchKernelGGL((gatmh_rows8_src_list_hub_kernel<G>), gh, W.bl, 0, s, a, W.hl8, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz, HA, LA); \
+        else hipLaunchKernelGGL((gatmh_rows8_src_list_kernel<G>), gh, W.bl, 0, s, a, W.hl8, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz, LA); \
+    } while (0)
+        GATMH_ROWS8_FORMS(F);
+#undef F
+    } else if ((merge = gatmh_rows_split(hubs, a.N, W.rpb8, &HA, &gh, &gm))) {
+#define F(G) hipLaunchKernelGGL((gatmh_rows8_src_hub_kernel<G>), gh, W.bl, 0, s, a, W.hl8, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz, HA)
+        GATMH_ROWS8_FORMS(F);
+#undef F
+    } else {
+        const dim3 gr((a.N + W.rpb8 - 1) / W.rpb8);
+#define F(G) hipLaunchKernelGGL((gatmh_rows8_src_kernel<G>), gr, W.bl, 0, s, a, W.hl8, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz)
+        GATMH_ROWS8_FORMS(F);
+#undef F
+    }
+    if (!merge) return hipGetLastError();
+    gm = W.merge_grid(HA.nrows);   // (the narrow merge kernel: the narrow form's lanes per head reduce its closing dot product)
+#define F(G, H) hipLaunchKernelGGL((gatmh_rows_src_merge_kernel<G, H>), gm, W.bl, 0, s, a, HL, z, der, a_l, a_r, del, dz, HA)
+    GATMH_ROWS_FORMS(F);
+#undef F
+    return hipGetLastError();
+}
+#undef GATMH_ROWS8_FORMS
+#undef GATMH_ROWS8_FORMS_EL
+
 hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                      const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                      const float *er, const float *a_l, float *o, float *op, float *m, float *den, float *dpos,
-                                     hipStream_t s, bool bf16, const GatmhHubs *hubs, const GatmhRowList *list) {
+                                     hipStream_t s, int form, const GatmhHubs *hubs, const GatmhRowList *list) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    const bool bf16 = form != GATMH_ROWS_FP32;
     GatMhArgs a{N, K, D, ld, ldk, colptr, rowidx};
+    if (form == GATMH_ROWS_BF16_WIDE) return launch_rows8_forward(a, group, HL, z, zg, el, elg, er, a_l, o, op, m, den, dpos, s, hubs, list);
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     const bool elfly = gatmh_rows_elfly(hpq, ld);
@@ -963,11 +1434,13 @@ hipError_t launch_gatmh_rows_forward(uint32_t N, uint32_t K, uint32_t D, uint32_
 hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const float *z, const float *zg, const float *el, const float *elg,
                                  const float *er, const float *a_l, const float *m, const float *den, const float *d_o, float *t, float *der,
-                                 float4 *st4, uint32_t lds4, hipStream_t s, bool bf16, const GatmhHubs *hubs) {
+                                 float4 *st4, uint32_t lds4, hipStream_t s, int form, const GatmhHubs *hubs) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    const bool bf16 = form != GATMH_ROWS_FP32;
     GatMhArgs a{N, K, D, ld, ldk, colptr, rowidx};
+    if (form == GATMH_ROWS_BF16_WIDE) return launch_rows8_dst(a, group, z, zg, el, elg, er, a_l, m, den, d_o, t, der, st4, lds4, s, hubs);
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     const bool elfly = gatmh_rows_elfly(hpq, ld);
@@ -1003,11 +1476,13 @@ hipError_t launch_gatmh_rows_dst(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
 hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr,
                                  const uint32_t *colidx, const float *z, const float *el, const float *d_o, const float *dog,
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
-                                 float *del, float *dz, hipStream_t s, bool bf16, const GatmhHubs *hubs, const GatmhRowList *list) {
+                                 float *del, float *dz, hipStream_t s, int form, const GatmhHubs *hubs, const GatmhRowList *list) {
     if (N == 0) return hipSuccess;
     int group, hpq, HL;
     if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    const bool bf16 = form != GATMH_ROWS_FP32;
     GatMhArgs a{N, K, D, ld, ldk, rowptr, colidx};
+    if (form == GATMH_ROWS_BF16_WIDE) return launch_rows8_src(a, group, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, a_r, del, dz, s, hubs, list);
     const uint32_t rpb = 4 * (64 / (uint32_t)group);
     const dim3 gr((N + rpb - 1) / rpb), bl(256);
     RowsHubArgs HA;

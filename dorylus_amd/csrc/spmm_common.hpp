@@ -52,6 +52,11 @@ __device__ __forceinline__ float4 bf16_round(const float4 &x) {
 }
 __device__ __forceinline__ float4 row_chunk(const float4 &x) { return x; }
 __device__ __forceinline__ float4 row_chunk(const uint2 &x) { return bf16x4_to_float4(x.x, x.y); }
+// eight bf16 of one 16-byte load: the two float4 a lane of a wide form keeps, each widened as row_chunk(uint2) widens it
+__device__ __forceinline__ void row_chunk(const uint4 &x, float4 &lo, float4 &hi) {
+    lo = bf16x4_to_float4(x.x, x.y);
+    hi = bf16x4_to_float4(x.z, x.w);
+}
 // one row chunk of four features as the kernels load it: a float4, or four bf16 in a uint2
 template <bool BF16> using RowChunk = typename std::conditional<BF16, uint2, float4>::type;
 

@@ -695,6 +695,39 @@ int dory_gatmh_row_gather_overlap_stats(dory_ctx *ctx, uint64_t *fwd_split, uint
                                         uint64_t *src_in_flight, uint64_t *in_interior_rows, uint64_t *out_interior_rows,
                                         uint64_t *bwd_deferred);
 
+/* ---- the row-gather family: 16-byte bf16 row gathers (opt-in, default off; nothing in the reference) -------------------------
+ * The family's bf16 form (dory_gatmh_row_gather_bf16) loads four bf16 -- 8 bytes -- per lane and edge: a 64-float row occupies 16
+ * lanes, and every lane of a head recomputes the head's exponentials.  With this switch on, a bf16 pass of the family runs its WIDE
+ * form where the shape has one: a lane keeps eight consecutive features (one 16-byte load per edge, two float4 accumulators), a row
+ * takes half the lanes -- twice the rows in flight per wave, half the gather, address and broadcast instructions per row, half the
+ * redundant per-head arithmetic.  Kernels gatmh_rows8_{forward,dst,src}[_list][_hub]_kernel (csrc/gat_mh_rows.hip).
+ *   shape rule         dory_gatmh_row_gather_bf16_wide_form (dorylus_host.h): the family covers the shape, 64 <= ld <= 256 (ld a
+ *                      multiple of 8), and K == 1 or D % 8 == 0.  Not taken: ld = 32 (four lanes per row), D = 1 / 2 / 4 with
+ *                      several heads (no wide counterpart of two or four heads per lane).  Lanes per row 8 / 16 / 32.
+ *   which passes       exactly the passes that run the family's bf16 form: the forward and the source side by option
+ *                      gatmh_bf16_gather, the destination-side edge pass of a layer whose forward ran the bf16 form.  Where the shape
+ *                      rule fails, or the shadow rows / the ghost twin handed to the launch are not 16-byte aligned, the narrow form
+ *                      runs as with the switch off, and the pass is counted (narrow_while_on).
+ *   everything else    as it is: shadow rows, ghost twins, hub splitting (the narrow merge kernels fold a wide launch's chunk
+ *                      states: same layout), interior rows beside the exchange, the merged exchange, gatmh_bwd_phase 0 / 1 / 2.
+ * CONTRACT: switch on = switch off, BIT FOR BIT, in every tensor, weight and weight gradient -- hence the fp32 family's bits on rows
+ * rounded beforehand.  Per column the sums are the same fmaf chains in entry order; per head the values are the same scalar chains
+ * over the same batches of four entries; a dot product is the narrow lanes' two four-term chains added inside the lane (the narrow
+ * form's first butterfly step) and then the same butterfly over half as many lanes.
+ * on: 0 (default) or 1.  DORY_ERR_ARG: any other value, 1 on a context configured as DORY_GCN / DORY_GAT, a call while an epoch
+ * graph is being recorded.  1 is legal while dory_gatmh_row_gather_bf16 is off: it is then inert.  Option gatmh_bf16_wide (the
+ * sweeps' wide form) is unrelated.  Counters, in this order: forward passes, destination-side edge passes and source-side passes
+ * that ran the wide form since dory_create (eager calls and recordings, not replays); bf16 passes of the family that ran narrow with
+ * the switch on.  Any pointer may be NULL.
+ * MEASURED (profiles/r29_gatmh_row_gather_bf16_wide.txt; rank 0 of 8 at Amazon size, twins and bf16 wire on, parent / switch off / switch
+ * on alternated over three rounds): uniform rank -- 4 of the 6 passes at 64- / 128-float rows faster outside the spread (x0.89-0.95 a
+ * pass; compute epoch 8 x 16: 15.49 -> 14.93 ms), 2 inside it.  NOT FASTER: every wide pass of the R-MAT rank with
+ * dory_gatmh_row_gather_hub_split(1024) -- forward x1.39-1.41, source side x1.18-1.22, compute epochs x1.19 / x1.11: its passes are the
+ * serial chains of the hub rows' chunks, on which a wide lane does twice the arithmetic per batch.  Leave the switch off on a rank with
+ * hub rows.  Switch off against the parent's library: inside the spread on 23 of 24 lines (the other: x1.006, same instructions). */
+int dory_gatmh_row_gather_bf16_wide(dory_ctx *ctx, int on);   /* 0 (default) = off */
+int dory_gatmh_row_gather_bf16_wide_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src, uint64_t *narrow_while_on);
+
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
  * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels

@@ -198,6 +198,15 @@ int dory_option_check(const char *name, int64_t value, int gnn, int configured, 
  * context of model gnn in that state -- DORY_OK, or DORY_ERR_ARG and in msg (n bytes) its setter's first refusal (a hook's refusal only a context knows). */
 int dory_switch_spec(uint32_t index, const char **name, int *hi, int *refusals, int *waits_halo, int *drops_stamp, int *parent, int *counters);
 int dory_switch_check(const char *name, int value, int gnn, int configured, int prealloc, int recording, int parent_on, char *msg, size_t n);
+/* Shape introspection (tests, tools; no context or device needed): the wide bf16 form of the multi-head GAT's row-gather kernels
+ * (dory_gatmh_row_gather_bf16_wide, dorylus_hip.h) -- dorylus_amd/host/gatmh_rows_wide.cpp, csrc/gat_mh_shapes.hpp.  Returns 1 where a
+ * pass over K heads of D features on rows of ld floats takes the wide form: the family covers the shape (K*D <= ld <= 256, ld a
+ * multiple of 4, a head shape of the model), 64 <= ld and ld a multiple of 8, and K == 1 or D % 8 == 0; else 0 (the narrow form runs).
+ * Then lanes_per_row: 8 / 16 / 32 for ld / 8 <= 8, <= 16, more; lanes_per_head: the lanes a head's dot products are reduced over (the
+ * row's lanes for K == 1, else D / 8); scores_from_row: 1 where the sources' scores are formed from the gathered row (ld / 4 a power of
+ * two), 0 where el / fg_el are gathered.  Any pointer may be NULL; where 0 is returned the outputs are 0. */
+int dory_gatmh_row_gather_bf16_wide_form(uint32_t K, uint32_t D, uint32_t ld, uint32_t *lanes_per_row, uint32_t *lanes_per_head,
+                                         int *scores_from_row);
 
 #ifdef __cplusplus
 }
