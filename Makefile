@@ -11,10 +11,10 @@ LIB  = dorylus_amd/libdorylus_hip.so
 
 all: $(LIB) $(GRAPHSERVER) $(INPUTS) oracle
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/ctx.hpp $(CSRC)/spmm_common.hpp $(CSRC)/sweep_core.hpp $(CSRC)/sweep_geometry.hpp $(CSRC)/options.hpp $(CSRC)/switches.hpp $(CSRC)/row_chunks.hpp $(CSRC)/abi_internal.hpp $(CSRC)/gat_mh.hpp $(CSRC)/gat_mh_shapes.hpp include/dorylus_hip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/ctx.hpp $(CSRC)/spmm_common.hpp $(CSRC)/sweep_core.hpp $(CSRC)/sweep_geometry.hpp $(CSRC)/options.hpp $(CSRC)/switches.hpp $(CSRC)/row_chunks.hpp $(CSRC)/abi_internal.hpp $(CSRC)/gat_mh.hpp $(CSRC)/gat_mh_shapes.hpp $(CSRC)/k1_shapes.hpp include/dorylus_hip.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-dorylus_amd/host/%.o: dorylus_amd/host/%.cpp $(wildcard dorylus_amd/host/*.hpp) $(wildcard include/*.h) $(CSRC)/sweep_geometry.hpp $(CSRC)/options.hpp $(CSRC)/switches.hpp $(CSRC)/row_chunks.hpp $(CSRC)/gat_mh_shapes.hpp
+dorylus_amd/host/%.o: dorylus_amd/host/%.cpp $(wildcard dorylus_amd/host/*.hpp) $(wildcard include/*.h) $(CSRC)/sweep_geometry.hpp $(CSRC)/options.hpp $(CSRC)/switches.hpp $(CSRC)/row_chunks.hpp $(CSRC)/gat_mh_shapes.hpp $(CSRC)/k1_shapes.hpp
 	$(HIPCC) -O3 -std=c++17 -fPIC -fopenmp -Wall -c $< -o $@
 
 $(LIB): $(OBJS) $(HOSTOBJS)

@@ -42,6 +42,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather_hub_split", "dory_gatmh_row_gather_hub_split_stats",
     "dory_gatmh_row_gather_overlap", "dory_gatmh_row_gather_overlap_stats",
     "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
+    "dory_k1_bf16_wide", "dory_k1_bf16_wide_stats", "dory_k1_bf16_wide_form",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -190,6 +191,9 @@ def load():
         "dory_gatmh_row_gather_overlap_stats": [vp] + [C.POINTER(u64)] * 7,
         "dory_gatmh_row_gather_bf16_wide": [vp, i32],
         "dory_gatmh_row_gather_bf16_wide_stats": [vp] + [C.POINTER(u64)] * 4,
+        "dory_k1_bf16_wide": [vp, i32],
+        "dory_k1_bf16_wide_stats": [vp] + [C.POINTER(u64)] * 2,
+        "dory_k1_bf16_wide_form": [u32, u32, C.POINTER(u32), C.POINTER(u32)],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_row_chunk_plan": [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), vp, vp, vp, vp, vp],
@@ -323,6 +327,17 @@ def gatmh_row_gather_bf16_wide_form(K, D, ld, lib=None):
     if not lib.dory_gatmh_row_gather_bf16_wide_form(int(K), int(D), int(ld), C.byref(lr), C.byref(lh), C.byref(el)):
         return None
     return lr.value, lh.value, bool(el.value)
+
+
+def k1_bf16_wide_form(ld, slab=0, lib=None):
+    """None where K1 has no wide bf16 form for rows of ld floats under option spmm_slab = slab (the narrow form runs), else
+    (lanes, chunks): the instantiation of spmm_rows_bf16x8_kernel that Context.k1_bf16_wide selects -- a row pass covers
+    lanes x chunks 16-byte chunks, gridDim.y passes cover the row (dory_k1_bf16_wide_form; no context, no GPU)"""
+    lib = lib or load()
+    g, k = C.c_uint32(), C.c_uint32()
+    if not lib.dory_k1_bf16_wide_form(int(ld), int(slab), C.byref(g), C.byref(k)):
+        return None
+    return g.value, k.value
 
 
 class Context:
@@ -816,6 +831,19 @@ class Context:
         """dict: fwd / dst_edge_pass / src (passes that ran the wide form since dory_create: eager calls and recordings),
         narrow_while_on (bf16 passes of the family that ran narrow with the switch on)"""
         return self._stats(self.lib.dory_gatmh_row_gather_bf16_wide_stats, 4, self.GATMH_ROWS_BF16_WIDE_STATS)
+
+    K1_BF16_WIDE_STATS = ("wide", "narrow_while_on")
+
+    def k1_bf16_wide(self, on=1):
+        """K1's aggregations on bf16 rows gather 16 bytes a lane (dory_k1_bf16_wide; GCN and the GAT prototype): 0 (default) = off;
+        1 = where k1_bf16_wide_form has a form for the row and slab width, every launch of the aggregation keeps eight features a lane
+        and chunk -- the narrow bf16 form's bits in every tensor; inert while no bf16 gather mode is on"""
+        self._ck(self.lib.dory_k1_bf16_wide(self.h, int(on)))
+
+    def k1_bf16_wide_stats(self):
+        """dict: wide (aggregations K1 ran in the wide form since dory_create: eager calls and recordings), narrow_while_on
+        (aggregations on bf16 rows K1 ran narrow with the switch on)"""
+        return self._stats(self.lib.dory_k1_bf16_wide_stats, 2, self.K1_BF16_WIDE_STATS)
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

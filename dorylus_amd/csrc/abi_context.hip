@@ -544,7 +544,8 @@ int dory_gatmh_row_gather_bf16_wide(dory_ctx *c, int on) {
     if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16_wide: value %d is neither 0 nor 1", on);
     if (on && c->configured && c->gnn != DORY_GATMH)
         return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16_wide: this context is configured as %s; the feature serves the multi-head GAT (DORY_GATMH) only",
-                    c->gnn == DORY_GCN ? "DORY_GCN (K1s has its own wide form: gcn_bf16_wide)" : "DORY_GAT");
+                    c->gnn == DORY_GCN ? "DORY_GCN (its wide forms: gcn_bf16_wide for K1s, dory_k1_bf16_wide for K1)"
+                                       : "DORY_GAT (its wide forms: dory_gat_bf16_gather's wide for K1s, dory_k1_bf16_wide for K1)");
     if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_bf16_wide: not while an epoch graph is being recorded");
     if ((on == 1) != c->gatmh_rows_wide) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
     c->gatmh_rows_wide = on == 1;
@@ -557,6 +558,26 @@ int dory_gatmh_row_gather_bf16_wide_stats(dory_ctx *c, uint64_t *fwd, uint64_t *
     if (dst_edge_pass) *dst_edge_pass = c->gatmh_rows8_dst;
     if (src) *src = c->gatmh_rows8_src;
     if (narrow_while_on) *narrow_while_on = c->gatmh_rows8_narrow;
+    return DORY_OK;
+}
+
+// ---- dory_k1_bf16_wide: K1's aggregations on bf16 rows gather 16 bytes a lane (spmm.hip: spmm_rows_bf16x8_kernel; include/dorylus_hip.h) ----
+int dory_k1_bf16_wide(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "k1_bf16_wide: value %d is neither 0 nor 1", on);
+    if (on && c->configured && c->gnn == DORY_GATMH)
+        return fail(c, DORY_ERR_ARG, "k1_bf16_wide: this context is configured as DORY_GATMH (its wide form: dory_gatmh_row_gather_bf16_wide); "
+                                     "the feature serves K1 of DORY_GCN and DORY_GAT only");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "k1_bf16_wide: not while an epoch graph is being recorded");
+    if ((on == 1) != c->k1_bf16_wide) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->k1_bf16_wide = on == 1;
+    return DORY_OK;
+}
+
+int dory_k1_bf16_wide_stats(dory_ctx *c, uint64_t *wide, uint64_t *narrow_while_on) {
+    CHECK_CTX(c);
+    if (wide) *wide = c->k1_rows8_wide;
+    if (narrow_while_on) *narrow_while_on = c->k1_rows8_narrow;
     return DORY_OK;
 }
 

@@ -318,8 +318,18 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
     const bool bf16 = bf.on();
     c->spmm_launches_k1++;
     if (bf16) (c->gnn == DORY_GAT ? c->gat_bf16_gathers_k1 : c->bf16_gathers_k1)++;
+    // dory_k1_bf16_wide: every launch of this aggregation gathers its bf16 rows 16 bytes a lane where the rule has a form for the row
+    // and slab width and the shadow rows and the ghost rows (the twin, or the shadow rows' tail) are 16-byte aligned; else narrow, counted
+    bool wide = false;
+    if (bf16 && c->k1_bf16_wide) {
+        uint32_t lanes, chunks;
+        const int64_t slab = c->opt[OPT_SPMM_SLAB];
+        wide = k1_rows8_form(a.ld, slab > 0 ? (uint32_t)slab : 0u, &lanes, &chunks) &&
+               !((reinterpret_cast<uintptr_t>(a.xl) | reinterpret_cast<uintptr_t>(a.xg)) & 15);
+        (wide ? c->k1_rows8_wide : c->k1_rows8_narrow)++;
+    }
     auto launch = [&](const SpmmArgs &x) -> int {
-        HIPCK(c, launch_spmm(x, (int)c->opt[OPT_SPMM_SLAB], c->compute, bf16));
+        HIPCK(c, launch_spmm(x, (int)c->opt[OPT_SPMM_SLAB], c->compute, bf16, wide));
         return DORY_OK;
     };
     const LongRowsDev &longRows = A.long_rows;

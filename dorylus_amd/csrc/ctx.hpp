@@ -17,6 +17,7 @@
 #include "switches.hpp"
 #include "sweep_geometry.hpp"
 #include "row_chunks.hpp"
+#include "k1_shapes.hpp"
 
 namespace dory {
 
@@ -308,6 +309,10 @@ struct dory_ctx {
     // the bf16 passes of the family that ran narrow with the switch on (shape or alignment)
     bool gatmh_rows_wide = false;
     uint64_t gatmh_rows8_fwd = 0, gatmh_rows8_dst = 0, gatmh_rows8_src = 0, gatmh_rows8_narrow = 0;
+    // dory_k1_bf16_wide: the switch; the aggregations on bf16 rows that K1 ran in its wide form, and those it ran narrow with the switch
+    // on (no form for the row or slab width, rows not 16-byte aligned)
+    bool k1_bf16_wide = false;
+    uint64_t k1_rows8_wide = 0, k1_rows8_narrow = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -443,8 +448,9 @@ struct SpmmArgs {
     const uint32_t *order;  // optional row schedule (longest first) or nullptr
     const uint64_t *ptr_end;// K1: end of every row's edge range (nullptr: ptr[v + 1]); with accumulate == 2 the sum STARTS from out[v]
 };
-// bf16: xl / xg point at bf16 rows of ld elements (launch_bf16_rows; option gcn_bf16_gather), the sums stay fp32
-hipError_t launch_spmm(const SpmmArgs &a, int slab, hipStream_t s, bool bf16 = false);
+// bf16: xl / xg point at bf16 rows of ld elements (launch_bf16_rows; option gcn_bf16_gather), the sums stay fp32; wide: those rows
+// gathered 16 bytes a lane (dory_k1_bf16_wide) -- a form of k1_rows8_form (k1_shapes.hpp) and 16-byte aligned rows, else refused
+hipError_t launch_spmm(const SpmmArgs &a, int slab, hipStream_t s, bool bf16 = false, bool wide = false);
 
 void plan_long_rows(const uint64_t *ptr, uint32_t N, LongRowsHost *out);
 hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float *partial /*nchunks x ld*/, hipStream_t s, bool bf16 = false);

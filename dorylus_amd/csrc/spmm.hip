@@ -140,6 +140,144 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(SpmmArgs a) { spmm_rows_
 template <int GROUP, int CHUNKS>
 __global__ __launch_bounds__(256) void spmm_rows_bf16_kernel(SpmmArgs a) { spmm_rows_body<GROUP, CHUNKS, true>(a); }
 
+// ---- the wide bf16 form (dory_k1_bf16_wide; k1_shapes.hpp: k1_rows8_form) ----------------------------------------------
+// K1's body with a lane owning EIGHT consecutive features per chunk: one 16-byte load of eight bf16 from the shadow rows or the ghost
+// twin per lane, edge and chunk, widened by row_chunk(uint4) into the two float4 a narrow lane pair would hold, two float4 accumulators
+// per chunk; a row takes half the lanes (or half the chunks) of the narrow form.  The entry load and its broadcast, the ghost select,
+// the self term, row_clamp, ptr_end, order / rows, both accumulate modes and the slabs are K1's, in K1's order; per output element the
+// chain of fmaf in edge order is the narrow form's -- same bits on finite rows, whatever BATCH (the edges in flight) is.  A body of its
+// own: the narrow and fp32 instantiations keep their code objects (tests/test_k1_bf16_wide_resources.py).
+template <int GROUP, int CHUNKS, int BATCH>
+__device__ __forceinline__ void spmm_rows8_body(SpmmArgs a) {
+    constexpr int RPW = 64 / GROUP;      // rows per wave
+    constexpr int RPB = 4 * RPW;         // rows per 256-thread block
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int li = lane % GROUP;
+    const int gi = lane / GROUP;
+    const uint32_t rid = blockIdx.x * RPB + wave * RPW + gi;
+    const bool row_ok = rid < (a.rows ? a.rows : a.N);
+    uint32_t v = row_ok ? (a.order ? a.order[rid] : rid) : 0;
+    if constexpr (GROUP == 64) v = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+
+    const uint32_t nchunk = a.ld >> 3;                       // 16-byte chunks (eight bf16; two float4 of out) per row
+    const uint32_t c0 = blockIdx.y * (GROUP * CHUNKS) + li;  // first chunk of this lane
+    bool act[CHUNKS];
+    uint32_t col[CHUNKS];  // inactive lanes gather chunk 0 (valid memory) and never store
+    float4 lo[CHUNKS], hi[CHUNKS];
+#pragma unroll
+    for (int k = 0; k < CHUNKS; ++k) {
+        act[k] = row_ok && (c0 + GROUP * k) < nchunk;
+        col[k] = act[k] ? c0 + GROUP * k : 0;
+        lo[k] = hi[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (a.accumulate == 2) {   // second pass of an edge-split aggregation: go on from the first pass's sum
+        const float4 *o4 = reinterpret_cast<const float4 *>(a.out);
+#pragma unroll
+        for (int k = 0; k < CHUNKS; ++k)
+            if (act[k]) {
+                const size_t o = ((size_t)v * nchunk + col[k]) * 2;
+                lo[k] = o4[o];
+                hi[k] = o4[o + 1];
+            }
+    }
+
+    const uint4 *xl8 = reinterpret_cast<const uint4 *>(a.xl);
+    const uint4 *xg8 = reinterpret_cast<const uint4 *>(a.xg);
+
+    if (a.self_mode != 0) {
+        const float sc = (a.self_mode == 1 && row_ok) ? a.self_scale[v] : 1.f;
+#pragma unroll
+        for (int k = 0; k < CHUNKS; ++k)
+            if (act[k]) {
+                float4 x, y;
+                row_chunk(xl8[(size_t)v * nchunk + col[k]], x, y);
+                lo[k] = make_float4(x.x * sc, x.y * sc, x.z * sc, x.w * sc);
+                hi[k] = make_float4(y.x * sc, y.y * sc, y.z * sc, y.w * sc);
+            }
+    }
+
+    uint64_t e = row_ok ? a.ptr[v] : 0;
+    uint64_t end = row_ok ? (a.ptr_end ? a.ptr_end[v] : a.ptr[v + 1]) : 0;
+    if (a.row_clamp && end - e > a.row_clamp) end = e + a.row_clamp;   // the rest of a long row: spmm_longrow_bf16_kernel (narrow)
+    while (e < end) {
+        const int n = (end - e) < (uint64_t)GROUP ? (int)(end - e) : GROUP;
+        uint32_t my_idx = 0;
+        float my_val = 0.f;
+        if (li < n) {
+            my_idx = a.idx[e + li];
+            my_val = a.val[e + li];
+        }
+        int j = 0;
+        for (; j + BATCH <= n; j += BATCH) {
+            uint4 x[BATCH][CHUNKS];   // raw bf16 in flight, widened as they are summed
+            float w[BATCH];
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u) {
+                const uint32_t s = bcast_u32<GROUP>(my_idx, j + u);
+                w[u] = bcast_f32<GROUP>(my_val, j + u);
+                const uint4 *row = s < a.N ? xl8 + (size_t)s * nchunk
+                                           : xg8 + (size_t)(s - a.N) * nchunk;
+#pragma unroll
+                for (int k = 0; k < CHUNKS; ++k) x[u][k] = row[col[k]];
+            }
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u)
+#pragma unroll
+                for (int k = 0; k < CHUNKS; ++k) {
+                    float4 p, q;
+                    row_chunk(x[u][k], p, q);
+                    lo[k] = fma4(w[u], p, lo[k]);
+                    hi[k] = fma4(w[u], q, hi[k]);
+                }
+        }
+        for (; j < n; ++j) {
+            const uint32_t s = bcast_u32<GROUP>(my_idx, j);
+            const float w = bcast_f32<GROUP>(my_val, j);
+            const uint4 *row = s < a.N ? xl8 + (size_t)s * nchunk
+                                       : xg8 + (size_t)(s - a.N) * nchunk;
+#pragma unroll
+            for (int k = 0; k < CHUNKS; ++k) {
+                float4 p, q;
+                row_chunk(row[col[k]], p, q);
+                lo[k] = fma4(w, p, lo[k]);
+                hi[k] = fma4(w, q, hi[k]);
+            }
+        }
+        e += n;
+    }
+
+    float4 *out4 = reinterpret_cast<float4 *>(a.out);
+#pragma unroll
+    for (int k = 0; k < CHUNKS; ++k)
+        if (act[k]) {
+            const size_t o = ((size_t)v * nchunk + col[k]) * 2;
+            if (a.accumulate == 1) {
+                const float4 p = out4[o], q = out4[o + 1];
+                lo[k].x += p.x; lo[k].y += p.y; lo[k].z += p.z; lo[k].w += p.w;
+                hi[k].x += q.x; hi[k].y += q.y; hi[k].z += q.z; hi[k].w += q.w;
+            }
+            out4[o] = lo[k];
+            out4[o + 1] = hi[k];
+        }
+}
+
+// four edges in flight per lane group, as the narrow form: every instantiation of the rule fits 128 registers with them (the largest,
+// (32, 3): 48 registers of raw bf16 in flight, 24 of sums)
+template <int GROUP, int CHUNKS>
+__global__ __launch_bounds__(256) void spmm_rows_bf16x8_kernel(SpmmArgs a) { spmm_rows8_body<GROUP, CHUNKS, 4>(a); }
+
+template <int GROUP, int CHUNKS>
+static hipError_t launch_t8(const SpmmArgs &a, hipStream_t s) {
+    constexpr int RPB = 4 * (64 / GROUP);
+    const uint32_t nchunk = a.ld >> 3;
+    const uint32_t rows = a.rows ? a.rows : a.N;
+    dim3 grid((rows + RPB - 1) / RPB, (nchunk + GROUP * CHUNKS - 1) / (GROUP * CHUNKS));
+    if (rows == 0 || nchunk == 0) return hipSuccess;
+    hipLaunchKernelGGL((spmm_rows_bf16x8_kernel<GROUP, CHUNKS>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 template <int GROUP, int CHUNKS>
 static hipError_t launch_t(const SpmmArgs &a, hipStream_t s, bool bf16) {
     constexpr int RPB = 4 * (64 / GROUP);
@@ -257,8 +395,28 @@ hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float 
 }
 
 // slab = floats per feature slab (0 = whole row in one pass where it fits 4 chunks per lane).
-hipError_t launch_spmm(const SpmmArgs &a, int slab, hipStream_t s, bool bf16) {
+// wide: the 16-byte form of bf16 rows, for a caller that asked k1_rows8_form and found xl / xg 16-byte aligned (else refused).
+hipError_t launch_spmm(const SpmmArgs &a, int slab, hipStream_t s, bool bf16, bool wide) {
     if (a.ld & 3) return hipErrorInvalidValue;
+    if (wide) {
+        uint32_t lanes = 0, chunks = 0;
+        if (!bf16 || !k1_rows8_form(a.ld, slab > 0 ? (uint32_t)slab : 0u, &lanes, &chunks) ||
+            ((reinterpret_cast<uintptr_t>(a.xl) | reinterpret_cast<uintptr_t>(a.xg)) & 15))
+            return hipErrorInvalidValue;
+        switch (lanes * 4 + chunks) {
+        case 8 * 4 + 1: return launch_t8<8, 1>(a, s);
+        case 16 * 4 + 1: return launch_t8<16, 1>(a, s);
+        case 32 * 4 + 1: return launch_t8<32, 1>(a, s);
+        case 64 * 4 + 1: return launch_t8<64, 1>(a, s);
+#if DORY_K1_WIDE_CH48_16X3
+        case 16 * 4 + 3: return launch_t8<16, 3>(a, s);
+#endif
+        case 32 * 4 + 3: return launch_t8<32, 3>(a, s);
+        case 64 * 4 + 2: return launch_t8<64, 2>(a, s);
+        case 64 * 4 + 3: return launch_t8<64, 3>(a, s);
+        }
+        return hipErrorInvalidValue;
+    }
     uint32_t width = a.ld;                  // floats handled by one block pass
     if (slab > 0 && (uint32_t)slab < width) width = (uint32_t)slab;
     const uint32_t ch = (width + 3) / 4;    // float4 chunks per row pass

@@ -728,6 +728,39 @@ int dory_gatmh_row_gather_overlap_stats(dory_ctx *ctx, uint64_t *fwd_split, uint
 int dory_gatmh_row_gather_bf16_wide(dory_ctx *ctx, int on);   /* 0 (default) = off */
 int dory_gatmh_row_gather_bf16_wide_stats(dory_ctx *ctx, uint64_t *fwd, uint64_t *dst_edge_pass, uint64_t *src, uint64_t *narrow_while_on);
 
+/* ---- K1, the row gather: 16-byte bf16 row gathers (opt-in, default off; nothing in the reference) ---------------------------------
+ * K1 (csrc/spmm.hip) is the aggregation a partitioned rank of a large graph ends up on, and the one family bound by the bytes it
+ * gathers.  On bf16 rows (gcn_bf16_gather; GAT prototype: dory_gat_bf16_gather) it loads four bf16 -- 8 bytes -- per lane, edge and
+ * chunk.  With this switch on, an aggregation on bf16 rows that K1 runs takes its WIDE form where the rule has one: a lane keeps eight
+ * consecutive features per chunk (one 16-byte load from the shadow rows or the ghost twin, two float4 accumulators), a row takes half
+ * the lanes or half the chunks.  Kernel spmm_rows_bf16x8_kernel<lanes, chunks>.
+ *   form rule          dory_k1_bf16_wide_form(ld, slab, &lanes, &chunks): 1 and the instantiation, or 0 (outputs 0; any pointer may be
+ *                      NULL) where ld < 64, ld is no multiple of 8, or option spmm_slab makes a pass narrower than 64 floats.  By
+ *                      ch8 = ceil(width / 8), width = ld or the slab where narrower: <= 8 (8, 1); <= 16 (16, 1); <= 32 (32, 1);
+ *                      <= 64 (64, 1); <= 96 (32, 3); <= 128 (64, 2); <= 192 (64, 3); wider: gridDim.y slabs of (64, 3).  No context,
+ *                      no device needed (dorylus_amd/host/k1_rows_wide.cpp, csrc/k1_shapes.hpp).
+ *   which launches     every launch of the aggregation: the local-first edge-split copy in one launch and in two, the interior /
+ *                      boundary row split, the plain launch, the clamped launch ahead of the long-row kernels.  The long-row kernels
+ *                      themselves stay narrow (a hub chunk is a serial chain; wave-ordered partials do not depend on the lane width).
+ *                      Where the rule has no form, or the shadow rows / the ghost rows handed to the launch are not 16-byte aligned,
+ *                      the narrow form runs as with the switch off, and the aggregation is counted (narrow_while_on).
+ *   everything else    as it is: K1s (its own wide form: gcn_bf16_wide, dory_gat_bf16_gather's `wide`), K1b, the multi-head families.
+ * CONTRACT: switch on = switch off, BIT FOR BIT, in every tensor, weight and weight gradient, on finite inputs: per output element the
+ * same fmaf chain in edge order, from the same start (zero, the self term, or the first pass's sum).
+ * on: 0 (default) or 1.  DORY_ERR_ARG: any other value, 1 on a context configured as DORY_GATMH (dory_gatmh_row_gather_bf16_wide is its
+ * switch), a call while an epoch graph is being recorded.  A change drops a recorded epoch graph.  1 is legal while no bf16 gather mode
+ * is on: it is then inert.  Counters, in this order: aggregations that K1 ran wide since dory_create (eager calls and recordings, not
+ * replays); aggregations on bf16 rows that K1 ran narrow with the switch on.  Any pointer may be NULL.
+ * MEASURED (profiles/r30_k1_bf16_wide.txt; rank 0 of 8 at Amazon size, twins and bf16 wire on, conversion of the local rows included; fp32 /
+ * parent / switch off / switch on alternated over three rounds): narrow against fp32 faster on all 8 lines (x0.56-0.64 on the uniform rank,
+ * x0.80 on the R-MAT rank).  Wide against narrow, uniform rank: 64-float rows x0.962 / x0.964 (backward outside the spread); NOT FASTER: 128
+ * floats x1.023 / x1.017 and 320 floats forward x1.017, all inside the spread (320 backward x0.950, inside it too).  NOT FASTER, outside the
+ * spread: the R-MAT rank, x1.142 / x1.148 -- hub rows' clamped serial chains; leave the switch off on a rank with hub rows.  ld 320 on (16, 3)
+ * against (64, 1): inside the spread, the rule keeps (64, 1).  Switch off against the parent's library: inside the spread on all 8 lines. */
+int dory_k1_bf16_wide(dory_ctx *ctx, int on);   /* 0 (default) = off */
+int dory_k1_bf16_wide_stats(dory_ctx *ctx, uint64_t *wide, uint64_t *narrow_while_on);
+int dory_k1_bf16_wide_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t *chunks);
+
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
  * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels
