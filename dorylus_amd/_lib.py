@@ -41,6 +41,7 @@ SYMBOLS = [
     "dory_gatmh_bf16_ghosts", "dory_gatmh_bf16_ghosts_stats",
     "dory_gatmh_row_gather_hub_split", "dory_gatmh_row_gather_hub_split_stats",
     "dory_gatmh_row_gather_overlap", "dory_gatmh_row_gather_overlap_stats",
+    "dory_gatmh_row_gather_edge_split", "dory_gatmh_row_gather_edge_split_stats",
     "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
     "dory_k1_bf16_wide", "dory_k1_bf16_wide_stats", "dory_k1_bf16_wide_form",
 ]
@@ -189,6 +190,8 @@ def load():
         "dory_gatmh_row_gather_hub_split_stats": [vp] + [C.POINTER(u64)] * 7,
         "dory_gatmh_row_gather_overlap": [vp, i32],
         "dory_gatmh_row_gather_overlap_stats": [vp] + [C.POINTER(u64)] * 7,
+        "dory_gatmh_row_gather_edge_split": [vp, i32],
+        "dory_gatmh_row_gather_edge_split_stats": [vp] + [C.POINTER(u64)] * 8,
         "dory_gatmh_row_gather_bf16_wide": [vp, i32],
         "dory_gatmh_row_gather_bf16_wide_stats": [vp] + [C.POINTER(u64)] * 4,
         "dory_k1_bf16_wide": [vp, i32],
@@ -198,6 +201,7 @@ def load():
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_row_chunk_plan": [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), vp, vp, vp, vp, vp],
         "dory_row_interior_plan": [vp, vp, u32, C.POINTER(u32), C.POINTER(u32), vp, vp],
+        "dory_row_edge_split_plan": [vp, vp, u32, u32, vp, vp],
         "dory_gatmh_row_gather_bf16_wide_form": [u32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)],
         "dory_partition_wire_order": [vp, vp, i32, vp, vp],
         "dory_sweep_geometry": [u32, u32, i32, i32, i32, u32, u32, u32, i32, vp],
@@ -316,6 +320,25 @@ def row_interior_plan(ptr, idx, N, lib=None):
     if rc != 0:
         raise DoryError(f"dory_row_interior_plan failed ({rc})")
     return interior, boundary
+
+
+def row_edge_split_plan(ptr, idx, N, lib=None):
+    """(idx_local_first, mid): the entries of every row of an adjacency (ptr[rows + 1], idx; an id >= N names a ghost row) regrouped
+    -- ids < N first, in their original order, ids >= N after, in their original order -- and per row the position of its first ghost
+    entry, ptr[v + 1] where it has none (dory_row_edge_split_plan; no context, no GPU).  The copy Context.gatmh_row_gather_edge_split
+    builds per adjacency."""
+    lib = lib or load()
+    ptr, idx = np.ascontiguousarray(ptr, np.uint64), np.ascontiguousarray(idx, np.uint32)
+    if ptr.size < 1:
+        raise DoryError("row_edge_split_plan: ptr is empty")
+    rows = ptr.size - 1
+    if rows and int(ptr[rows]) > idx.size:
+        raise DoryError(f"row_edge_split_plan: ptr names {int(ptr[rows])} entries, idx has {idx.size}")
+    out, mid = np.zeros(idx.size, np.uint32), np.zeros(rows, np.uint64)
+    rc = lib.dory_row_edge_split_plan(_ptr(ptr), _ptr(idx), rows, int(N), _ptr(out), _ptr(mid))
+    if rc != 0:
+        raise DoryError(f"dory_row_edge_split_plan failed ({rc})")
+    return out, mid
 
 
 def gatmh_row_gather_bf16_wide_form(K, D, ld, lib=None):
@@ -818,6 +841,24 @@ class Context:
         them with an exchange in flight beside the first), in_interior_rows / out_interior_rows (the current plans of the in-edges
         and the out-edges), bwd_deferred (backward exchanges issued deferred)"""
         return self._stats(self.lib.dory_gatmh_row_gather_overlap_stats, 7, self.GATMH_ROWS_OVERLAP_STATS)
+
+    GATMH_ROWS_EDGE_SPLIT_STATS = ("fwd_split", "src_split", "fwd_in_flight", "src_in_flight", "in_local_entries", "out_local_entries",
+                                   "hub_fallbacks", "wide_not_taken")
+
+    def gatmh_row_gather_edge_split(self, value=1):
+        """the row-gather family walks every row's local entries before its ghost entries (dory_gatmh_row_gather_edge_split): 0 (default)
+        = off; 1 = the forward and the backward's source side run the carry kernels over a local-first copy of the ids
+        (row_edge_split_plan) -- with an exchange in flight the local entries and the self edge first, beside it, the state of the
+        boundary rows parked, then the wait and the ghost entries; with nothing in flight one launch; 2 = always the two launches.
+        The same bits either way; against 0 only m keeps its bits (other association of the sums)"""
+        self._ck(self.lib.dory_gatmh_row_gather_edge_split(self.h, int(value)))
+
+    def gatmh_row_gather_edge_split_stats(self):
+        """dict: fwd_split / src_split (passes that ran the carry kernels since dory_create), fwd_in_flight / src_in_flight (those of
+        them with an exchange in flight beside the first launch), in_local_entries / out_local_entries (the current copies of the
+        in-edges and the out-edges), hub_fallbacks (passes left to the hub chunk plan), wide_not_taken (bf16 passes that ran the
+        narrow carry kernel with gatmh_row_gather_bf16_wide on)"""
+        return self._stats(self.lib.dory_gatmh_row_gather_edge_split_stats, 8, self.GATMH_ROWS_EDGE_SPLIT_STATS)
 
     GATMH_ROWS_BF16_WIDE_STATS = ("fwd", "dst_edge_pass", "src", "narrow_while_on")
 

@@ -273,6 +273,51 @@ int interior_plan_ensure(dory_ctx *c, Adjacency &A) {
     return DORY_OK;
 }
 
+// dory_gatmh_row_gather_edge_split: the local-first copy of one adjacency (RowsEdgeSplit) -- plan_row_edge_split over the pointer and
+// index arrays as they were uploaded (read back from the device, as interior_plan_ensure does: under halo_direct_recv these are the
+// renumbered ids), and the rows that have a ghost entry.  Cached in the adjacency, dropped with it (free_graph)
+int rows_edge_ensure(dory_ctx *c, Adjacency &A) {
+    if (A.rows_edge.built) return DORY_OK;
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the local-first copy of the edges would have to be built while recording (run one eager epoch first)");
+    if (!c->has_graph) return DORY_OK;
+    std::vector<uint64_t> ptr((size_t)c->N + 1, 0), mid((size_t)c->N);
+    std::vector<uint32_t> idx((size_t)A.nnz), lf((size_t)A.nnz), brows;
+    if (A.ptr) HIPCK(c, hipMemcpy(ptr.data(), A.ptr, ptr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (A.nnz) HIPCK(c, hipMemcpy(idx.data(), A.idx, idx.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (ptr[c->N] > A.nnz) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_edge_split: the adjacency's pointers run past its %llu entries", (unsigned long long)A.nnz);
+    for (uint32_t v = 0; v < c->N; ++v)
+        if (ptr[v] > ptr[v + 1]) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_edge_split: the adjacency's pointers do not ascend at row %u", v);
+    plan_row_edge_split(ptr.data(), idx.data(), c->N, c->N, lf.data(), mid.data());
+    RowsEdgeSplit &R = A.rows_edge;
+    R.local = 0;
+    for (uint32_t v = 0; v < c->N; ++v) {
+        R.local += mid[v] - ptr[v];
+        if (mid[v] < ptr[v + 1]) brows.push_back(v);
+    }
+    int rc;
+    if (A.nnz && (rc = upload_array(c, &R.idx, lf.data(), lf.size()))) return rc;
+    if (c->N && (rc = upload_array(c, &R.mid, mid.data(), mid.size()))) return rc;
+    if (!brows.empty() && (rc = upload_array(c, &R.brows, brows.data(), brows.size()))) return rc;
+    R.nbrows = (uint32_t)brows.size();
+    R.built = true;
+    return DORY_OK;
+}
+// ... and the buffer the rows' states wait in between the two launches of a pass: only ever grows, never while recording
+int carry_state_ensure(dory_ctx *c, size_t bytes) {
+    if (bytes <= c->gatmh_carry_bytes) return DORY_OK;
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "epoch graph: the row states of gatmh_row_gather_edge_split would have to grow while recording (run one eager epoch first)");
+    if (c->gatmh_carry_state) {
+        HIPCK(c, hipStreamSynchronize(c->compute));
+        (void)hipFree(c->gatmh_carry_state);
+        c->gatmh_carry_state = nullptr;
+        c->gatmh_carry_bytes = 0;
+        epoch_graph_drop_locked(c);   // (a recorded epoch would write the freed buffer)
+    }
+    HIPCK(c, hipMalloc((void **)&c->gatmh_carry_state, bytes));
+    c->gatmh_carry_bytes = bytes;
+    return DORY_OK;
+}
+
 }  // namespace dory
 
 using namespace dory;
@@ -341,7 +386,7 @@ static void free_graph(dory_ctx *c) {
         for (void *p : {(void *)A.ptr, (void *)A.idx, (void *)A.val, (void *)A.order, (void *)A.split, (void *)A.edge_split.idx,
                         (void *)A.edge_split.val, (void *)A.edge_split.mid, (void *)A.long_rows.rows, (void *)A.long_rows.row_chunk_ptr,
                         (void *)A.long_rows.chunks, (void *)A.hub_rows.rows, (void *)A.hub_rows.row_chunk_ptr, (void *)A.hub_rows.chunks,
-                        (void *)A.rows_split})
+                        (void *)A.rows_split, (void *)A.rows_edge.idx, (void *)A.rows_edge.mid, (void *)A.rows_edge.brows})
             if (p) (void)hipFree(p);
         for (BlockedAdj *B : {(BlockedAdj *)&A.blk, (BlockedAdj *)&A.blk16, (BlockedAdj *)&A.swp}) free_blocked(B);
         A = Adjacency{};   // every schedule, layout and flag of the direction at once
@@ -377,6 +422,7 @@ int dory_destroy(dory_ctx *c) {
     }
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->bf16_rows) (void)hipFree(c->bf16_rows);
+    if (c->gatmh_carry_state) (void)hipFree(c->gatmh_carry_state);
     if (c->partial) (void)hipFree(c->partial);
     if (c->epoch_exec) (void)hipGraphExecDestroy(c->epoch_exec);
     if (c->epoch_graph) (void)hipGraphDestroy(c->epoch_graph);
@@ -535,6 +581,46 @@ int dory_gatmh_row_gather_overlap_stats(dory_ctx *c, uint64_t *fwd_split, uint64
     if (in_interior_rows) *in_interior_rows = c->adj[ADJ_IN].rows_split_built ? c->adj[ADJ_IN].rows_interior : 0;
     if (out_interior_rows) *out_interior_rows = c->adj[ADJ_OUT].rows_split_built ? c->adj[ADJ_OUT].rows_interior : 0;
     if (bwd_deferred) *bwd_deferred = c->gatmh_ovl_deferred;
+    return DORY_OK;
+}
+
+// ---- dory_gatmh_row_gather_edge_split: the row-gather family's local entries beside the exchange (abi_stages.hip; include/dorylus_hip.h) ----
+int dory_gatmh_row_gather_edge_split(dory_ctx *c, int value) {
+    CHECK_CTX(c);
+    if (value < 0 || value > 2) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_edge_split: value %d is neither 0, 1 nor 2", value);
+    if (value && c->configured && c->gnn != DORY_GATMH)
+        return fail(c, DORY_ERR_ARG, "gatmh_row_gather_edge_split: this context is configured as %s; the feature serves the multi-head GAT (DORY_GATMH) only",
+                    c->gnn == DORY_GCN ? "DORY_GCN (K1 runs its local part first itself: halo_overlap)" : "DORY_GAT");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gatmh_row_gather_edge_split: not while an epoch graph is being recorded");
+    if (value != c->gatmh_edge_split) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->gatmh_edge_split = value;
+    if (!value || !c->has_graph) return DORY_OK;   // (before dory_graph_upload: the first aggregation plans)
+    for (Adjacency &A : c->adj) {
+        if (!A.ghosts || !c->N) continue;
+        const int rc = rows_edge_ensure(c, A);
+        if (rc) return rc;
+    }
+    // the states of the widest layer, where the tensors exist already (else: at first use)
+    size_t need = 0;
+    for (uint32_t l = 0; l < c->L && c->prealloc; ++l) {
+        Tensor *z = find(c, l, "z"), *el = find(c, l, "el");
+        if (z && el) need = std::max(need, (size_t)c->N * gatmh_rows_hub_state_floats(0, z->ld, el->ld) * sizeof(float));
+    }
+    return need && (c->adj[ADJ_IN].ghosts || c->adj[ADJ_OUT].ghosts) ? carry_state_ensure(c, need) : (int)DORY_OK;
+}
+
+int dory_gatmh_row_gather_edge_split_stats(dory_ctx *c, uint64_t *fwd_split, uint64_t *src_split, uint64_t *fwd_in_flight, uint64_t *src_in_flight,
+                                           uint64_t *in_local_entries, uint64_t *out_local_entries, uint64_t *hub_fallbacks,
+                                           uint64_t *wide_not_taken) {
+    CHECK_CTX(c);
+    if (fwd_split) *fwd_split = c->gatmh_es_fwd;
+    if (src_split) *src_split = c->gatmh_es_src;
+    if (fwd_in_flight) *fwd_in_flight = c->gatmh_es_fwd_flight;
+    if (src_in_flight) *src_in_flight = c->gatmh_es_src_flight;
+    if (in_local_entries) *in_local_entries = c->adj[ADJ_IN].rows_edge.built ? c->adj[ADJ_IN].rows_edge.local : 0;
+    if (out_local_entries) *out_local_entries = c->adj[ADJ_OUT].rows_edge.built ? c->adj[ADJ_OUT].rows_edge.local : 0;
+    if (hub_fallbacks) *hub_fallbacks = c->gatmh_es_hub_fallbacks;
+    if (wide_not_taken) *wide_not_taken = c->gatmh_es_wide_not_taken;
     return DORY_OK;
 }
 

@@ -90,6 +90,10 @@ int hub_plan_ensure(dory_ctx *c, dory::Adjacency &A);
 // dory_gatmh_row_gather_overlap: the adjacency's rows in launch order (Adjacency::rows_split) for the context's hub chunk size, built if it
 // is not the cached one (abi_context.hip)
 int interior_plan_ensure(dory_ctx *c, dory::Adjacency &A);
+// dory_gatmh_row_gather_edge_split: the adjacency's local-first copy (Adjacency::rows_edge), built if it is not there (never while an
+// epoch graph is recording); the buffer of the rows' states between the two launches of a pass, at least `bytes` large
+int rows_edge_ensure(dory_ctx *c, dory::Adjacency &A);
+int carry_state_ensure(dory_ctx *c, size_t bytes);
 // ... and the ghost sources' scores dory_apply_edge left until the exchange of z has landed: launched by wait_halo (abi_stages.hip)
 int gatmh_ghost_scores_flush(dory_ctx *c);
 // c->partial (K1b's partial rows, the sweeps' gate counters); `what` names it in the refusal inside a recording

@@ -547,6 +547,32 @@ static int gatmh_rows_lists_for(dory_ctx *c, Adjacency &A, bool *split, GatmhRow
     return DORY_OK;
 }
 
+// dory_gatmh_row_gather_edge_split: whether a pass of the row-gather family over adjacency A (the forward: the in-edges; the source
+// side: the out-edges) runs the carry kernels over A's local-first copy, built here at first use (not while recording).  Not taken: the
+// switch off; no ghost, no vertex, no entry (nothing to split); a hub chunk plan with chunks -- counted, where `count` says this is the
+// pass itself and not dory_apply_edge asking ahead of it
+static int gatmh_carry_taken(dory_ctx *c, Adjacency &A, bool count, bool *taken) {
+    *taken = false;
+    if (!c->gatmh_edge_split || !A.ghosts || !c->N || !A.nnz) return DORY_OK;
+    int rc;
+    if (c->gatmh_hub_chunk) {
+        if ((rc = hub_plan_ensure(c, A))) return rc;
+        if (A.hub_rows.nchunks) { if (count) c->gatmh_es_hub_fallbacks++; return DORY_OK; }
+    }
+    if ((rc = rows_edge_ensure(c, A))) return rc;
+    *taken = A.rows_edge.built && A.rows_edge.idx && A.rows_edge.mid;
+    return DORY_OK;
+}
+// ... and what such a pass (0 forward, 2 source side) hands its launcher: the copy and one state slot per row in the context's buffer
+static int gatmh_carry_for(dory_ctx *c, Adjacency &A, int pass, uint32_t ld, uint32_t ldk, bool *taken, GatmhCarry *cy) {
+    int rc = gatmh_carry_taken(c, A, true, taken);
+    if (rc || !*taken) return rc;
+    if ((rc = carry_state_ensure(c, (size_t)c->N * gatmh_rows_hub_state_floats(pass, ld, ldk) * sizeof(float)))) return rc;
+    const RowsEdgeSplit &R = A.rows_edge;
+    *cy = GatmhCarry{R.idx, R.mid, R.brows, R.nbrows, c->gatmh_carry_state};
+    return DORY_OK;
+}
+
 // dory_gatmh_row_gather_bf16_wide: what a pass of the row-gather family hands its launcher -- fp32 rows, the shadow rows, or (the switch
 // on, a shape of the wide form, 16-byte aligned shadow rows and twins) the shadow rows gathered 16 bytes a lane.  The wide form gives the
 // narrow form's bits: nothing else of the schedule asks which of the two ran.  bf: after begin() -- the ghost rows' base (shadow rows
@@ -720,16 +746,35 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             if (rc) return rc;
             GatmhHubs hubs;   // dory_gatmh_row_gather_hub_split: the hub rows of the in-edges, if any
             if ((rc = gatmh_hubs_for(c, In, 0, z->ld, el->ld, &hubs))) return rc;
+            // dory_gatmh_row_gather_edge_split: every row's local entries and self edge first -- beside the exchange, if one is in flight,
+            // the boundary rows' states parked --, the wait, then the ghost entries; with nothing in flight (value 1) one launch of the
+            // same kernel.  Where it takes the pass it decides it: no row lists
+            bool carry;
+            GatmhCarry cy;
+            if ((rc = gatmh_carry_for(c, In, 0, z->ld, el->ld, &carry, &cy))) return rc;
+            if (carry) split = false;
             if (rows_bf16 && (rc = bf.begin(c, *z, fgz, In.ghosts, "gatmh_bf16_gather"))) return rc;
             const float *a_l = c->weights[fl]["a_l"].d;
             const bool in_flight = c->halo_pending;
-            const int rform = gatmh_rows_gather_form(c, rows_bf16, K, D, z->ld, bf);
+            const bool carry_two = carry && (c->gatmh_edge_split == 2 || in_flight);
+            const int rform = carry ? (rows_bf16 ? GATMH_ROWS_BF16 : GATMH_ROWS_FP32) : gatmh_rows_gather_form(c, rows_bf16, K, D, z->ld, bf);
+            auto launch_carry = [&](int walk) -> int {
+                HIPCK(c, launch_gatmh_rows_forward_carry(c->N, K, D, z->ld, el->ld, In.ptr, rows_bf16 ? bf.xl : z->d, rows_bf16 ? bf.xg : fgz->d,
+                                                         el->d, fgel->d, er->d, a_l, o->d, op->d, m->d, den->d, dpos->d, c->compute, rform, cy, walk));
+                return DORY_OK;
+            };
             auto launch = [&](const GatmhHubs *h, const GatmhRowList *rows) -> int {
                 HIPCK(c, launch_gatmh_rows_forward(c->N, K, D, z->ld, el->ld, In.ptr, In.idx, rows_bf16 ? bf.xl : z->d,
                                                    rows_bf16 ? bf.xg : (In.ghosts ? fgz->d : nullptr), el->d, In.ghosts ? fgel->d : nullptr, er->d,
                                                    a_l, o->d, op->d, m->d, den->d, dpos->d, c->compute, rform, h, rows));
                 return DORY_OK;
             };
+            if (carry)
+                rc = around_halo(c, carry_two, rows_bf16 ? &bf : nullptr, [&]() -> int { return launch_carry(GATMH_WALK_FIRST); }, [&]() -> int {
+                    const int r = !rows_bf16 ? ghost_fp32_current(c, fgz) : (int)DORY_OK;
+                    return r ? r : launch_carry(carry_two ? GATMH_WALK_SECOND : GATMH_WALK_BOTH);
+                });
+            else
             rc = around_halo(c, split, rows_bf16 ? &bf : nullptr, [&]() -> int { return launch(&hubs, &first); }, [&]() -> int {
                 // (ghost_fp32_current waits for the exchange itself: after the interior launch)
                 const int r = !rows_bf16 && In.ghosts ? ghost_fp32_current(c, fgz) : (int)DORY_OK;
@@ -738,6 +783,11 @@ static int aggregate_gatmh_forward(dory_ctx *c, uint32_t fl) {
             if (rc) return rc;
             if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
             if (split) { c->gatmh_ovl_fwd++; if (in_flight) c->gatmh_ovl_fwd_flight++; }
+            if (carry) {
+                c->gatmh_es_fwd++;
+                if (carry_two && in_flight) c->gatmh_es_fwd_flight++;
+                if (rows_bf16 && c->gatmh_rows_wide) c->gatmh_es_wide_not_taken++;
+            }
             if (hubs.plan.nchunks) c->gatmh_hub_fwd++;
             if (fl < c->gatmh_fwd_swept.size()) c->gatmh_fwd_swept[fl] = 1;
             c->count[CNT_GATMH_ROWS_FWD]++;
@@ -908,7 +958,13 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
     bool split;
     GatmhRowList first, rest;
     if ((rc = gatmh_rows_lists_for(c, Out, &split, &first, &rest))) return rc;
-    if ((rc = gatmh_backward_exchange(c, T, false, split))) return rc;
+    // dory_gatmh_row_gather_edge_split: every source's local destinations and self edge beside that exchange, the ghost destinations
+    // after the wait; it takes the deferral too, and where it takes the pass it decides it
+    bool carry;
+    GatmhCarry cy;
+    if ((rc = gatmh_carry_for(c, Out, 2, ld, ldk, &carry, &cy))) return rc;
+    if (carry) split = false;
+    if ((rc = gatmh_backward_exchange(c, T, false, split || carry))) return rc;
     {
         Timed t(c, "spmm", c->compute);
         // (phase 0: the exchange above made the compute stream wait for bg_do, or around_halo does; phase 2: the caller moved it before this call)
@@ -917,7 +973,14 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         if ((rc = gatmh_hubs_for(c, Out, 2, ld, ldk, &hubs))) return rc;   //  launch_gatmh_dattn below takes the scratch: one stream)
         if (src_bf16 && (rc = bf.begin(c, *T.dO, T.bgdo, Out.ghosts, "gatmh_bf16_gather"))) return rc;
         const bool in_flight = c->halo_pending;
-        const int rform = gatmh_rows_gather_form(c, src_bf16, K, D, ld, bf);
+        const bool carry_two = carry && (c->gatmh_edge_split == 2 || in_flight);
+        const int rform = carry ? (src_bf16 ? GATMH_ROWS_BF16 : GATMH_ROWS_FP32) : gatmh_rows_gather_form(c, src_bf16, K, D, ld, bf);
+        auto launch_carry = [&](int walk) -> int {
+            HIPCK(c, launch_gatmh_rows_src_carry(c->N, K, D, ld, ldk, Out.ptr, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
+                                                 src_bf16 ? bf.xg : T.bgdo->d, st4, reinterpret_cast<const float4 *>(T.bgst->d), lds4, T.der->d,
+                                                 c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, rform, cy, walk));
+            return DORY_OK;
+        };
         auto launch = [&](const GatmhHubs *h, const GatmhRowList *rows) -> int {
             HIPCK(c, launch_gatmh_rows_src(c->N, K, D, ld, ldk, Out.ptr, Out.idx, T.z->d, T.el->d, src_bf16 ? bf.xl : T.dO->d,
                                            src_bf16 ? bf.xg : (Out.ghosts ? T.bgdo->d : nullptr), st4,
@@ -925,6 +988,12 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
                                            c->weights[T.fl]["a_l"].d, c->weights[T.fl]["a_r"].d, T.del->d, T.dz->d, c->compute, rform, h, rows));
             return DORY_OK;
         };
+        if (carry)
+            rc = around_halo(c, carry_two, src_bf16 ? &bf : nullptr, [&]() -> int { return launch_carry(GATMH_WALK_FIRST); }, [&]() -> int {
+                const int r = !src_bf16 ? ghost_fp32_current(c, T.bgdo) : (int)DORY_OK;
+                return r ? r : launch_carry(carry_two ? GATMH_WALK_SECOND : GATMH_WALK_BOTH);
+            });
+        else
         rc = around_halo(c, split, src_bf16 ? &bf : nullptr, [&]() -> int { return launch(&hubs, &first); }, [&]() -> int {
             const int r = !src_bf16 && Out.ghosts ? ghost_fp32_current(c, T.bgdo) : (int)DORY_OK;
             return r ? r : launch(&hubs, split ? &rest : nullptr);
@@ -932,6 +1001,11 @@ static int gatmh_backward_rows(dory_ctx *c, const GatmhBwd &T, Tensor *op, Tenso
         if (rc) return rc;
         if (bf.from_twin && !c->capturing) c->count[CNT_GATMH_TWIN_READS_ROWS]++;
         if (split) { c->gatmh_ovl_src++; if (in_flight) c->gatmh_ovl_src_flight++; }
+        if (carry) {
+            c->gatmh_es_src++;
+            if (carry_two && in_flight) c->gatmh_es_src_flight++;
+            if (src_bf16 && c->gatmh_rows_wide) c->gatmh_es_wide_not_taken++;
+        }
         if (hubs.plan.nchunks) c->gatmh_hub_src++;
         c->count[CNT_GATMH_ROWS_SRC]++;
         if (src_bf16) {
@@ -1264,19 +1338,24 @@ int dory_apply_edge(dory_ctx *c, uint32_t layer, int dir) {
     // dory_gatmh_row_gather_overlap: where the forward of this layer will run its interior rows beside the exchange in flight, the exchange
     // stays in flight here too -- the local scores now, the ghost sources' once it has landed (gatmh_ghost_scores_flush), the same kernels
     bool keep_flight = false;
-    if (c->gatmh_rows_overlap && c->halo_pending && c->gatmh_scores_pending < 0 && c->prealloc && c->gnn == DORY_GATMH && dir == DORY_FORWARD &&
-        layer >= 1 && layer <= c->L && c->N && c->adj[ADJ_IN].ghosts && (c->adj[ADJ_IN].rows_split_built || !c->capturing)) {
+    // dory_gatmh_row_gather_edge_split: likewise where the forward will run every row's local entries beside the exchange
+    const bool ovl_ready = c->gatmh_rows_overlap && (c->adj[ADJ_IN].rows_split_built || !c->capturing);
+    const bool es_ready = c->gatmh_edge_split && ((c->adj[ADJ_IN].rows_edge.built && c->adj[ADJ_IN].hub_chunk == c->gatmh_hub_chunk) || !c->capturing);
+    if ((ovl_ready || es_ready) && c->halo_pending && c->gatmh_scores_pending < 0 && c->prealloc && c->gnn == DORY_GATMH && dir == DORY_FORWARD &&
+        layer >= 1 && layer <= c->L && c->N && c->adj[ADJ_IN].ghosts) {
         const uint32_t l0 = layer - 1, K = c->heads[l0];
         Tensor *z = find(c, l0, "z"), *op = find(c, l0, "op"), *dpos = find(c, l0, "dpos");
         if (z && op && dpos && find(c, l0, "fg_z") && find(c, l0, "fg_el") && find(c, l0, "fg_er") && gatmh_rows_ok(K, z->cols / K, z->ld)) {
             const GatmhFwdForm form = gatmh_fwd_form(c, z, op, dpos, K, z->cols / K);
             bool split = false;
             GatmhRowList first, rest;
+            bool carry = false;
             if (!form.sweep && !form.blocked && (form.rows_forced || c->numNodes > 1)) {
-                const int prc = gatmh_rows_lists_for(c, c->adj[ADJ_IN], &split, &first, &rest);
+                int prc = ovl_ready ? gatmh_rows_lists_for(c, c->adj[ADJ_IN], &split, &first, &rest) : (int)DORY_OK;
+                if (!prc && es_ready) prc = gatmh_carry_taken(c, c->adj[ADJ_IN], false, &carry);
                 if (prc) return prc;
             }
-            keep_flight = split;
+            keep_flight = split || carry;
         }
     }
     if (!keep_flight) { int wrc = wait_halo(c); if (wrc) return wrc; }

@@ -186,6 +186,16 @@ struct EdgeSplit {
     float *val = nullptr;      // nnz
     uint64_t *mid = nullptr;   // N: first ghost-source edge of the row
 };
+// the row-gather family of the multi-head GAT beside an exchange in flight (dory_gatmh_row_gather_edge_split): the same regrouping
+// (row_chunks.hpp: plan_row_edge_split) and the rows that have a ghost entry at all -- the units of the launch after the wait
+struct RowsEdgeSplit {
+    uint32_t *idx = nullptr;    // nnz: ids, local ones first within every row (stable)
+    uint64_t *mid = nullptr;    // N: the row's first ghost entry (ptr[v + 1]: none)
+    uint32_t *brows = nullptr;  // nbrows: the rows with mid[v] < ptr[v + 1], ascending
+    uint32_t nbrows = 0;
+    uint64_t local = 0;         // entries with a local id
+    bool built = false;
+};
 struct LongRowsDev {
     uint32_t nrows = 0, nchunks = 0;
     uint32_t *rows = nullptr, *row_chunk_ptr = nullptr, *chunks = nullptr;
@@ -225,6 +235,9 @@ struct Adjacency {
     uint32_t rows_hub_chunk = 0;
     bool rows_split_built = false;
     EdgeSplit edge_split;        // K1: local-first copy (GCN partitions with ghosts)
+    // dory_gatmh_row_gather_edge_split: the row-gather family's own local-first copy (no per-edge values: only ids move) -- built from
+    // the ids as uploaded by rows_edge_ensure when the switch is set or at first use, dropped with the adjacency
+    RowsEdgeSplit rows_edge;
     DerivedAdj blk;              // K1b blocked copy; na: too many source blocks, use K1
     // multi-head GAT contexts with layers on both sides of 128 floats: a second copy, blocked for the 256-B slabs of the narrow
     // layers (K1b's windows hold a fixed number of BYTES: 24 blocks of 512-B rows, 16 of 256-B rows at Reddit size)
@@ -305,6 +318,16 @@ struct dory_ctx {
     bool gatmh_rows_overlap = false;
     int gatmh_scores_pending = -1;   // the layer whose ghost sources' scores (fg_el / fg_er) wait for the exchange in flight; -1: none
     uint64_t gatmh_ovl_fwd = 0, gatmh_ovl_src = 0, gatmh_ovl_fwd_flight = 0, gatmh_ovl_src_flight = 0, gatmh_ovl_deferred = 0;
+    // dory_gatmh_row_gather_edge_split: the value (0 off, 1 two launches around an exchange in flight and one otherwise, 2 always two);
+    // forward / source-side passes that ran the carry kernels, those of them with an exchange in flight beside the first launch, passes
+    // left to the hub chunk plan, bf16 passes that ran the narrow carry kernel with dory_gatmh_row_gather_bf16_wide on; and the states
+    // of the rows between the two launches -- a buffer of its own (nothing between the launches may write it: wait_halo's deferred score
+    // kernels, the ghost rows' conversion, an unpack and launch_gatmh_dattn all use other memory), grown outside a recording only
+    int gatmh_edge_split = 0;
+    uint64_t gatmh_es_fwd = 0, gatmh_es_src = 0, gatmh_es_fwd_flight = 0, gatmh_es_src_flight = 0, gatmh_es_hub_fallbacks = 0,
+             gatmh_es_wide_not_taken = 0;
+    float *gatmh_carry_state = nullptr;
+    size_t gatmh_carry_bytes = 0;
     // dory_gatmh_row_gather_bf16_wide: the switch; the forward / destination-side edge / source-side passes that ran the wide bf16 form, and
     // the bf16 passes of the family that ran narrow with the switch on (shape or alignment)
     bool gatmh_rows_wide = false;
@@ -768,6 +791,27 @@ hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
                                  const float4 *st4, const float4 *stg, uint32_t lds4, const float *der, const float *a_l, const float *a_r,
                                  float *del, float *dz, hipStream_t s, int form = GATMH_ROWS_FP32 /* bf16 forms: d_o / dog are their shadow rows */,
                                  const GatmhHubs *hubs = nullptr, const GatmhRowList *list = nullptr);
+// dory_gatmh_row_gather_edge_split: the carry form of the forward and the source side (gatmh_rows_*_carry_kernel).  cy: the adjacency's
+// local-first copy (RowsEdgeSplit) and N slots of gatmh_rows_hub_state_floats(0 forward / 2 source side, ld, ldk) floats; walk: both
+// ranges of every row in one launch, or the local entries + self edge (FIRST: states parked for the rows with ghost entries) and, after
+// the ghost rows have landed, the ghost entries of the boundary rows (SECOND).  BOTH and FIRST + SECOND give the same bits.  form:
+// GATMH_ROWS_FP32 or GATMH_ROWS_BF16 (there is no wide carry form)
+struct GatmhCarry {
+    const uint32_t *idx = nullptr;
+    const uint64_t *mid = nullptr;
+    const uint32_t *rows = nullptr;
+    uint32_t nrows = 0;
+    float *state = nullptr;
+};
+enum GatmhWalk { GATMH_WALK_BOTH = 0, GATMH_WALK_FIRST = 1, GATMH_WALK_SECOND = 2 };
+hipError_t launch_gatmh_rows_forward_carry(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr, const float *z,
+                                           const float *zg, const float *el, const float *elg, const float *er, const float *a_l, float *o,
+                                           float *op, float *m, float *den, float *dpos, hipStream_t s, int form, const GatmhCarry &cy,
+                                           int walk);
+hipError_t launch_gatmh_rows_src_carry(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr, const float *z,
+                                       const float *el, const float *d_o, const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                       const float *der, const float *a_l, const float *a_r, float *del, float *dz, hipStream_t s, int form,
+                                       const GatmhCarry &cy, int walk);
 // row-wise backward (single partition; feature-per-lane or (edge, head, piece)-per-lane kernels by shape)
 hipError_t launch_gatmh_backward(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr,
                                  const uint32_t *rowidx, const uint64_t *rowptr, const uint32_t *colidx,

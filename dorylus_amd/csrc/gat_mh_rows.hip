@@ -69,6 +69,17 @@
 // (the list is a template parameter of RowsWork and a kernel argument of the list kernels alone).  The destination-side edge pass reads
 // fg_z, which landed during the forward: no exchange to hide behind, no list form.  Its measurement: tools/gatmh_row_gather_overlap_rate.py.
 //
+// Local entries beside the exchange (dory_gatmh_row_gather_edge_split; the *_carry_kernel forms below).  On a rank of 8 of a community
+// graph 98 % of the rows have a ghost entry and 85 % of the entries are local: the row lists above hide next to nothing there.  The
+// carry kernels walk a row as two ranges of a local-first copy of the ids (row_chunks.hpp: plan_row_edge_split) -- A: the local entries,
+// then the self edge (a local row: with the part that does not wait); B: the ghost entries -- each with its own masked tail batch, the
+// per-entry arithmetic (the state structs' step) unchanged.  Which ranges a launch walks is a kernel ARGUMENT (RowsCarryArgs::walk):
+// both (state in registers), first (A; a row with ghost entries parks its state in its slot, any other closes), second (the boundary
+// rows, packed densely: state loaded, B, the one-pass epilogue).  One body of machine code for the three walks: one launch and two
+// launches give the same bits by construction -- two kernels instantiated from one body need not (the list forms above).  Against the
+// one-pass kernels only m keeps its bits: the ghost entries move behind the local ones and the self edge between them.  fp32 and narrow
+// bf16, the forms the launchers select for the one-pass kernels; no hub form (a plan with chunks keeps the pass as it was), no wide form.
+//
 // The wide (16-byte) bf16 form (dory_gatmh_row_gather_bf16_wide): the gatmh_rows8_*_kernel section below.
 #include "gat_mh.hpp"
 #include "spmm_common.hpp"
@@ -127,6 +138,19 @@ __host__ __device__ __forceinline__ size_t rows_hub_stride(int pass, uint32_t ld
 struct RowsListArgs {
     const uint32_t *rows;
     uint32_t n;
+};
+// dory_gatmh_row_gather_edge_split: what a carry launch walks of every row.  a.idx is the adjacency's local-first copy (row_chunks.hpp:
+// plan_row_edge_split), mid[v] the position of row v's first ghost entry.  Range A = [ptr[v], mid[v]) and then the self edge (a local
+// row: it goes with the part that does not wait), range B = [mid[v], ptr[v + 1]).  walk BOTH: units = all N rows, A then B, the state in
+// registers; FIRST: all N rows, A alone -- a row with an empty B closes, any other leaves its state in slot v of `state`
+// (rows_hub_stride floats a slot); SECOND: units = the n boundary rows `rows` names, packed densely -- state loaded, B, closed.
+enum { ROWS_WALK_BOTH = 0, ROWS_WALK_FIRST = 1, ROWS_WALK_SECOND = 2 };
+struct RowsCarryArgs {
+    const uint64_t *mid;
+    const uint32_t *rows;
+    uint32_t n;
+    float *state;
+    int walk;
 };
 // What a lane group of a launch does.  HUBS false: row = unit, all of it.  HUBS true: the first H.nchunks units are the chunks of the
 // hub rows (part: a range of the row's entries, the self edge with the last), the rest the rows, of which the hub rows are skipped.
@@ -470,6 +494,104 @@ __global__ __launch_bounds__(256) void gatmh_rows_forward_list_hub_bf16_kernel(G
                                                                                float *op, float *m_out, float *den_out, float *dpos_out,
                                                                                RowsHubArgs H, RowsListArgs R) {
     gatmh_rows_forward_body<GROUP, HPQ, ELFLY, true, true>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, H, R);
+}
+// dory_gatmh_row_gather_edge_split: the carry form -- a row walked as two ranges of the local-first ids (a.idx; C.mid), its state parked
+// between them where the launch says so (RowsCarryArgs::walk: a runtime value, one body of machine code for the three walks).  The
+// batches, the masked tail of each range, the gathers and S.step are the one-pass body's; the epilogue is rows_fwd_store.
+template <int GROUP, int HPQ, bool ELFLY, class CHUNK>
+__device__ __forceinline__ void gatmh_rows_forward_carry_body(const GatMhArgs &a, int HL, const CHUNK *z4, const CHUNK *zg4, const float *el,
+                                                              const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                              float *m_out, float *den_out, float *dpos_out, const RowsCarryArgs &C) {
+    const uint32_t unit = rows_unit<GROUP>();
+    const bool second = C.walk == ROWS_WALK_SECOND;
+    const bool ok = unit < (second ? C.n : a.N);
+    const RowsLane<GROUP, HPQ> L(a, ok ? (second ? C.rows[unit] : unit) : 0, ok);
+    const float4 al4 = ELFLY ? rows_attn4(L, a, a_l) : make_float4(0.f, 0.f, 0.f, 0.f);
+    RowsFwdState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        S.erv[s] = er[(size_t)L.v * a.ldk + L.hk[s]];
+        S.mx[s] = -INFINITY;
+        S.den[s] = S.denp[s] = 0.f;
+    }
+    S.acc = S.accp = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint64_t p0 = L.row_ok ? a.ptr[L.v] : 0, p1 = L.row_ok ? a.ptr[L.v + 1] : 0, md = L.row_ok ? C.mid[L.v] : 0;
+    // the row's slot (one per row): two rows of ld, then (m, den, den+) in runs of ldk -- the layout of a hub chunk's state
+    float *sp = C.state + (size_t)L.v * rows_hub_stride(0, a.ld, a.ldk), *hp = sp + 2 * (size_t)a.ld;
+    if (second && L.row_ok) {   // (every lane takes its column and its heads: what it held when range A ended -- a head's lanes agree)
+        S.acc = reinterpret_cast<const float4 *>(sp)[L.col];
+        S.accp = reinterpret_cast<const float4 *>(sp + a.ld)[L.col];
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) {
+            S.mx[s] = hp[L.hk[s]];
+            S.den[s] = hp[a.ldk + L.hk[s]];
+            S.denp[s] = hp[2 * a.ldk + L.hk[s]];
+        }
+    }
+    // range A: the local entries, then the self edge; range B: the ghost entries.  Each ends with its own masked batch
+    const int r1 = C.walk == ROWS_WALK_FIRST ? 1 : 2;
+    for (int r = second ? 1 : 0; r < r1; ++r) {
+        const uint64_t e0 = r ? md : p0, end = r ? p1 : md;
+        const uint64_t total = L.row_ok ? end - e0 + (r ? 0 : 1) : 0;
+        for (uint64_t done = 0; done < total; done += GROUP) {                     // GROUP == 64: wave-uniform
+            const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+            const uint64_t ee = e0 + done + L.li;
+            const uint32_t my_idx = ee < end ? a.idx[ee] : L.v;
+            for (int j = 0; j < n; j += 4) {
+                float4 x[4];
+                float sc[4][HPQ];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                    const bool loc = s < a.N;
+                    const size_t rr = loc ? s : s - a.N;
+                    x[u] = row_chunk((loc ? z4 : zg4)[rr * L.nchunk + L.col]);
+                    if constexpr (!ELFLY) {
+                        const float *ep = (loc ? el : elg) + rr * a.ldk;
+#pragma unroll
+                        for (int h = 0; h < HPQ; ++h) sc[u][h] = ep[L.hk[h]];
+                    }
+                }
+                if constexpr (ELFLY)
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) rows_el<HPQ>(x[u], al4, HL, sc[u]);
+#pragma unroll
+                for (int u = 1; u < 4; ++u)
+#pragma unroll
+                    for (int h = 0; h < HPQ; ++h) sc[u][h] = j + u < n ? sc[u][h] : -INFINITY;
+                S.template step<4>(x, sc);
+            }
+        }
+    }
+    if (!L.row_ok) return;
+    if (C.walk == ROWS_WALK_FIRST && md < p1) {   // ghost entries to come: the unnormalised state, for the launch after the wait
+        if (L.li >= L.nchunk) return;
+        reinterpret_cast<float4 *>(sp)[L.col] = S.acc;
+        reinterpret_cast<float4 *>(sp + a.ld)[L.col] = S.accp;
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s)
+            if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+                hp[L.hk[s]] = S.mx[s];
+                hp[a.ldk + L.hk[s]] = S.den[s];
+                hp[2 * a.ldk + L.hk[s]] = S.denp[s];
+            }
+        return;
+    }
+    rows_fwd_store(L, a, S, o, op, m_out, den_out, dpos_out);
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_carry_kernel(GatMhArgs a, int HL, const float *z, const float *zg, const float *el,
+                                                                       const float *elg, const float *er, const float *a_l, float *o, float *op,
+                                                                       float *m_out, float *den_out, float *dpos_out, RowsCarryArgs C) {
+    gatmh_rows_forward_carry_body<GROUP, HPQ, ELFLY>(a, HL, reinterpret_cast<const float4 *>(z), reinterpret_cast<const float4 *>(zg), el, elg, er,
+                                                     a_l, o, op, m_out, den_out, dpos_out, C);
+}
+template <int GROUP, int HPQ, bool ELFLY>
+__global__ __launch_bounds__(256) void gatmh_rows_forward_carry_bf16_kernel(GatMhArgs a, int HL, const uint2 *zb, const uint2 *zgb, const float *el,
+                                                                            const float *elg, const float *er, const float *a_l, float *o,
+                                                                            float *op, float *m_out, float *den_out, float *dpos_out,
+                                                                            RowsCarryArgs C) {
+    gatmh_rows_forward_carry_body<GROUP, HPQ, ELFLY>(a, HL, zb, zgb, el, elg, er, a_l, o, op, m_out, den_out, dpos_out, C);
 }
 
 // ---- backward, destination side: t[v,k] = sum a*da, der[v,k] = sum a*da*l' - t * sum a*l', st = (er, m, 1/den, t) -------------------
@@ -891,6 +1013,92 @@ __global__ __launch_bounds__(256) void gatmh_rows_src_list_hub_bf16_kernel(GatMh
                                                                            const float *der, const float *a_l, const float *a_r, float *del_out,
                                                                            float *dz, RowsHubArgs H, RowsListArgs R) {
     gatmh_rows_src_body<GROUP, HPQ, NB, true, true>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, H, R);
+}
+// dory_gatmh_row_gather_edge_split: the carry form of the source side, as gatmh_rows_forward_carry_body -- range A: the local
+// destinations (do / st) and the self edge, range B: the ghost destinations (bg_do / bg_st); the state is (S, S+, T, T+), plain sums
+template <int GROUP, int HPQ, int NB, class CHUNK>
+__device__ __forceinline__ void gatmh_rows_src_carry_body(const GatMhArgs &a, int HL, const float *z, const float *el, const CHUNK *d4,
+                                                          const CHUNK *dg4, const float4 *st4, const float4 *stg, uint32_t lds4, const float *der,
+                                                          const float *a_l, const float *a_r, float *del_out, float *dz, const RowsCarryArgs &C) {
+    const uint32_t unit = rows_unit<GROUP>();
+    const bool second = C.walk == ROWS_WALK_SECOND;
+    const bool ok = unit < (second ? C.n : a.N);
+    const RowsLane<GROUP, HPQ> L(a, ok ? (second ? C.rows[unit] : unit) : 0, ok);
+    RowsSrcState<HPQ> S;
+#pragma unroll
+    for (int s = 0; s < HPQ; ++s) {
+        S.elu[s] = el[(size_t)L.v * a.ldk + L.hk[s]];
+        S.T[s] = S.Tp[s] = 0.f;
+    }
+    S.S = S.Sp = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint64_t p0 = L.row_ok ? a.ptr[L.v] : 0, p1 = L.row_ok ? a.ptr[L.v + 1] : 0, md = L.row_ok ? C.mid[L.v] : 0;
+    float *sp = C.state + (size_t)L.v * rows_hub_stride(2, a.ld, a.ldk), *hp = sp + 2 * (size_t)a.ld;
+    if (second && L.row_ok) {
+        S.S = reinterpret_cast<const float4 *>(sp)[L.col];
+        S.Sp = reinterpret_cast<const float4 *>(sp + a.ld)[L.col];
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s) {
+            S.T[s] = hp[L.hk[s]];
+            S.Tp[s] = hp[a.ldk + L.hk[s]];
+        }
+    }
+    const int r1 = C.walk == ROWS_WALK_FIRST ? 1 : 2;
+    for (int r = second ? 1 : 0; r < r1; ++r) {
+        const uint64_t e0 = r ? md : p0, end = r ? p1 : md;
+        const uint64_t total = L.row_ok ? end - e0 + (r ? 0 : 1) : 0;
+        for (uint64_t done = 0; done < total; done += GROUP) {
+            const int n = (total - done) < (uint64_t)GROUP ? (int)(total - done) : GROUP;
+            const uint64_t ee = e0 + done + L.li;
+            const uint32_t my_idx = ee < end ? a.idx[ee] : L.v;
+            for (int j = 0; j < n; j += NB) {
+                float4 x[NB], rec[NB][HPQ];
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const uint32_t s = bcast_u32<GROUP>(my_idx, min(j + u, n - 1));
+                    const bool loc = s < a.N;
+                    const size_t rr = loc ? s : s - a.N;
+                    x[u] = row_chunk((loc ? d4 : dg4)[rr * L.nchunk + L.col]);
+                    const float4 *rp = (loc ? st4 : stg) + rr * lds4;
+#pragma unroll
+                    for (int h = 0; h < HPQ; ++h) rec[u][h] = rp[L.hk[h]];
+                }
+#pragma unroll
+                for (int u = 1; u < NB; ++u)
+#pragma unroll
+                    for (int h = 0; h < HPQ; ++h) rec[u][h].x = j + u < n ? rec[u][h].x : -INFINITY;
+                S.template step<NB>(x, rec);
+            }
+        }
+    }
+    if (!L.row_ok) return;
+    if (C.walk == ROWS_WALK_FIRST && md < p1) {   // ghost destinations to come: the partial sums, for the launch after the wait
+        if (L.li >= L.nchunk) return;
+        reinterpret_cast<float4 *>(sp)[L.col] = S.S;
+        reinterpret_cast<float4 *>(sp + a.ld)[L.col] = S.Sp;
+#pragma unroll
+        for (int s = 0; s < HPQ; ++s)
+            if (HPQ == 1 ? L.leader(a) : L.head_live(a, s)) {
+                hp[L.hk[s]] = S.T[s];
+                hp[a.ldk + L.hk[s]] = S.Tp[s];
+            }
+        return;
+    }
+    rows_src_close(L, a, HL, S, z, der, a_l, a_r, del_out, dz);
+}
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_carry_kernel(GatMhArgs a, int HL, const float *z, const float *el, const float *d_o,
+                                                                   const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                   const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                   float *dz, RowsCarryArgs C) {
+    gatmh_rows_src_carry_body<GROUP, HPQ, NB>(a, HL, z, el, reinterpret_cast<const float4 *>(d_o), reinterpret_cast<const float4 *>(dog), st4, stg,
+                                              lds4, der, a_l, a_r, del_out, dz, C);
+}
+template <int GROUP, int HPQ, int NB>
+__global__ __launch_bounds__(256) void gatmh_rows_src_carry_bf16_kernel(GatMhArgs a, int HL, const float *z, const float *el, const uint2 *dob,
+                                                                        const uint2 *dogb, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                                                        const float *der, const float *a_l, const float *a_r, float *del_out,
+                                                                        float *dz, RowsCarryArgs C) {
+    gatmh_rows_src_carry_body<GROUP, HPQ, NB>(a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del_out, dz, C);
 }
 
 // ---- the wide bf16 form (dory_gatmh_row_gather_bf16_wide; gatmh_rows8_*_kernel) -----------------------------------------------------
@@ -1534,6 +1742,72 @@ hipError_t launch_gatmh_rows_src(uint32_t N, uint32_t K, uint32_t D, uint32_t ld
 #define F(G, H)                                                                                                                     \
     hipLaunchKernelGGL((gatmh_rows_src_kernel<G, H, (H == 4 ? 2 : 4)>), gr, bl, 0, s, a, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, \
                        a_r, del, dz)
+    GATMH_ROWS_FORMS(F);
+#undef F
+    return hipGetLastError();
+}
+
+// dory_gatmh_row_gather_edge_split: one launch of the carry form -- walk GATMH_WALK_BOTH / _FIRST over all N rows, _SECOND over the
+// boundary rows of the copy (none: nothing to launch).  fp32 rows or the narrow bf16 form; a walk that parks or loads states needs cy.state
+static bool gatmh_rows_carry_args(const GatmhCarry &cy, int walk, uint32_t N, uint32_t rpb, RowsCarryArgs *C, dim3 *g) {
+    if (!cy.idx || !cy.mid || walk < GATMH_WALK_BOTH || walk > GATMH_WALK_SECOND) return false;
+    if (walk != GATMH_WALK_BOTH && !cy.state) return false;
+    if (walk == GATMH_WALK_SECOND && cy.nrows && !cy.rows) return false;
+    *C = RowsCarryArgs{cy.mid, cy.rows, cy.nrows, cy.state,
+                       walk == GATMH_WALK_BOTH ? ROWS_WALK_BOTH : walk == GATMH_WALK_FIRST ? ROWS_WALK_FIRST : ROWS_WALK_SECOND};
+    const uint32_t units = walk == GATMH_WALK_SECOND ? cy.nrows : N;
+    *g = dim3((units + rpb - 1) / rpb);
+    return true;
+}
+hipError_t launch_gatmh_rows_forward_carry(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *colptr, const float *z,
+                                           const float *zg, const float *el, const float *elg, const float *er, const float *a_l, float *o,
+                                           float *op, float *m, float *den, float *dpos, hipStream_t s, int form, const GatmhCarry &cy,
+                                           int walk) {
+    if (N == 0) return hipSuccess;
+    int group, hpq, HL;
+    if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    if (form != GATMH_ROWS_FP32 && form != GATMH_ROWS_BF16) return hipErrorInvalidValue;   // (no wide carry form)
+    const bool bf16 = form == GATMH_ROWS_BF16;
+    GatMhArgs a{N, K, D, ld, ldk, colptr, cy.idx};
+    const uint32_t rpb = 4 * (64 / (uint32_t)group);
+    const dim3 bl(256);
+    const bool elfly = gatmh_rows_elfly(hpq, ld);
+    RowsCarryArgs CA;
+    dim3 gc;
+    if (!gatmh_rows_carry_args(cy, walk, N, rpb, &CA, &gc)) return hipErrorInvalidValue;
+    if (gc.x == 0) return hipSuccess;
+    const uint2 *zb = reinterpret_cast<const uint2 *>(z), *zgb = reinterpret_cast<const uint2 *>(zg);
+#define F(G, H, E)                                                                                                                  \
+    do {                                                                                                                            \
+        if (bf16) hipLaunchKernelGGL((gatmh_rows_forward_carry_bf16_kernel<G, H, E>), gc, bl, 0, s, a, HL, zb, zgb, el, elg, er, a_l, o, op, m, den, dpos, CA); \
+        else hipLaunchKernelGGL((gatmh_rows_forward_carry_kernel<G, H, E>), gc, bl, 0, s, a, HL, z, zg, el, elg, er, a_l, o, op, m, den, dpos, CA); \
+    } while (0)
+    GATMH_ROWS_FORMS_EL(F);
+#undef F
+    return hipGetLastError();
+}
+hipError_t launch_gatmh_rows_src_carry(uint32_t N, uint32_t K, uint32_t D, uint32_t ld, uint32_t ldk, const uint64_t *rowptr, const float *z,
+                                       const float *el, const float *d_o, const float *dog, const float4 *st4, const float4 *stg, uint32_t lds4,
+                                       const float *der, const float *a_l, const float *a_r, float *del, float *dz, hipStream_t s, int form,
+                                       const GatmhCarry &cy, int walk) {
+    if (N == 0) return hipSuccess;
+    int group, hpq, HL;
+    if (!gatmh_rows_form(K, D, ld, &group, &hpq, &HL) || (hpq == 2 && group > 32) || (hpq == 4 && group > 16)) return hipErrorInvalidValue;
+    if (form != GATMH_ROWS_FP32 && form != GATMH_ROWS_BF16) return hipErrorInvalidValue;
+    const bool bf16 = form == GATMH_ROWS_BF16;
+    GatMhArgs a{N, K, D, ld, ldk, rowptr, cy.idx};
+    const uint32_t rpb = 4 * (64 / (uint32_t)group);
+    const dim3 bl(256);
+    RowsCarryArgs CA;
+    dim3 gc;
+    if (!gatmh_rows_carry_args(cy, walk, N, rpb, &CA, &gc)) return hipErrorInvalidValue;
+    if (gc.x == 0) return hipSuccess;
+    const uint2 *dob = reinterpret_cast<const uint2 *>(d_o), *dogb = reinterpret_cast<const uint2 *>(dog);
+#define F(G, H)                                                                                                                     \
+    do {                                                                                                                            \
+        if (bf16) hipLaunchKernelGGL((gatmh_rows_src_carry_bf16_kernel<G, H, (H == 4 ? 2 : 4)>), gc, bl, 0, s, a, HL, z, el, dob, dogb, st4, stg, lds4, der, a_l, a_r, del, dz, CA); \
+        else hipLaunchKernelGGL((gatmh_rows_src_carry_kernel<G, H, (H == 4 ? 2 : 4)>), gc, bl, 0, s, a, HL, z, el, d_o, dog, st4, stg, lds4, der, a_l, a_r, del, dz, CA); \
+    } while (0)
     GATMH_ROWS_FORMS(F);
 #undef F
     return hipGetLastError();

@@ -24,4 +24,10 @@ void plan_row_chunks(const uint64_t *ptr, uint32_t N, uint64_t over, uint64_t sk
 // changes neither list.
 void plan_row_interior(const uint64_t *ptr, const uint32_t *idx, uint32_t N, std::vector<uint32_t> *interior, std::vector<uint32_t> *boundary);
 
+// Every row's entries regrouped local-first (dory_gatmh_row_gather_edge_split; the C entry point: dory_row_edge_split_plan): within
+// [ptr[v], ptr[v + 1]) of idx_out the entries < N come first, in their original order, the entries >= N follow, in their original order
+// (a stable partition; ptr is unchanged, only ids move -- the multi-head GAT's adjacencies carry no per-edge values).  mid_out[v]: the
+// position of the row's first entry >= N, ptr[v + 1] where it has none.  idx_out: as many entries as idx, another array.
+void plan_row_edge_split(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t N, uint32_t *idx_out, uint64_t *mid_out);
+
 }  // namespace dory

@@ -1,6 +1,7 @@
 // row_chunks.cpp -- plan_row_chunks (csrc/row_chunks.hpp) and its C entry point dory_row_chunk_plan (include/dorylus_host.h): the
 // chunk plan of an adjacency's long rows, on the host, without a context or a device.  Likewise plan_row_interior /
-// dory_row_interior_plan: the rows that read no ghost row, and the others.
+// dory_row_interior_plan: the rows that read no ghost row, and the others; plan_row_edge_split / dory_row_edge_split_plan: every
+// row's entries regrouped local ids first.
 #include "../csrc/row_chunks.hpp"
 
 #include "../../include/dorylus_host.h"
@@ -33,7 +34,30 @@ void plan_row_interior(const uint64_t *ptr, const uint32_t *idx, uint32_t N, std
     }
 }
 
+void plan_row_edge_split(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t N, uint32_t *idx_out, uint64_t *mid_out) {
+    for (uint32_t v = 0; v < rows; ++v) {
+        uint64_t w = ptr[v];
+        for (uint64_t e = ptr[v]; e < ptr[v + 1]; ++e)
+            if (idx[e] < N) idx_out[w++] = idx[e];
+        mid_out[v] = w;
+        for (uint64_t e = ptr[v]; e < ptr[v + 1]; ++e)
+            if (idx[e] >= N) idx_out[w++] = idx[e];
+    }
+}
+
 }  // namespace dory
+
+extern "C" int dory_row_edge_split_plan(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t N, uint32_t *idx_out,
+                                        uint64_t *mid_out) {
+    if (!ptr) return DORY_ERR_ARG;
+    for (uint32_t v = 0; v < rows; ++v)
+        if (ptr[v] > ptr[v + 1]) return DORY_ERR_ARG;
+    const bool entries = rows && ptr[rows] > ptr[0];
+    if (entries && (!idx || !idx_out || idx == idx_out)) return DORY_ERR_ARG;
+    if (rows && !mid_out) return DORY_ERR_ARG;
+    dory::plan_row_edge_split(ptr, idx, rows, N, idx_out, mid_out);
+    return DORY_OK;
+}
 
 extern "C" int dory_row_interior_plan(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t *interior_out, uint32_t *boundary_out,
                                       uint32_t *interior_rows, uint32_t *boundary_rows) {

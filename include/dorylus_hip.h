@@ -695,6 +695,56 @@ int dory_gatmh_row_gather_overlap_stats(dory_ctx *ctx, uint64_t *fwd_split, uint
                                         uint64_t *src_in_flight, uint64_t *in_interior_rows, uint64_t *out_interior_rows,
                                         uint64_t *bwd_deferred);
 
+/* ---- the row-gather family: local entries beside the exchange (opt-in, default off; nothing in the reference) -----------------
+ * dory_gatmh_row_gather_overlap hides the exchange behind the interior ROWS only: about none on a uniform rank, a few per cent on a
+ * community rank, where 98 % of the rows have a ghost entry but 85 % of the ENTRIES are local.  With this switch the forward and the
+ * backward's source side walk every row's local entries before its ghost entries -- K1's local-first edge copy (halo_overlap, GCN),
+ * for this family -- and carry the row's state across the wait.  Kernels gatmh_rows_{forward,src}_carry[_bf16]_kernel
+ * (csrc/gat_mh_rows.hip) over a copy of the adjacency's ids regrouped local-first (dory_row_edge_split_plan, dorylus_host.h).
+ *   range A            the row's entries < local_vtx_cnt, in their original order, then the self edge (a local row).
+ *   range B            the row's entries >= local_vtx_cnt (ghost rows), in their original order; no self edge.
+ *                      Each range ends with its own masked batch; the per-entry arithmetic is the one-pass kernels'.
+ *   one launch         ("both") range A, then range B, the state in registers, then the one-pass epilogue.
+ *   two launches       ("first") range A of every row: a row without ghost entries closes, any other leaves its state -- forward
+ *                      (m, den, den+, acc, acc+), source side (S, S+, T, T+) -- in its slot of a buffer the context keeps for this
+ *                      alone; the wait for the exchange, the ghost rows' conversion or widening; ("second") the rows with ghost
+ *                      entries, packed densely into lane groups: state loaded, range B, epilogue.  Which ranges a launch walks is a
+ *                      kernel ARGUMENT: the three walks are one body of machine code.
+ *   value 1            with an exchange in flight when the pass starts: two launches around the wait (timing families
+ *                      "spmm_beside_halo" / "spmm_local_first"); with nothing in flight: one launch, no state traffic.
+ *   value 2            always two launches (tests; what the state round trip costs).
+ *   deferrals          as dory_gatmh_row_gather_overlap's, whether or not that switch is on: dory_apply_edge leaves the ghost
+ *                      sources' scores to the wait; the backward's LAST exchange (the merged one, or st's of two; never do's) is
+ *                      issued deferred under halo_overlap = 1 and never outlives the dory_aggregate call.  Where both switches are on
+ *                      and this one takes a pass, this one decides it.
+ *   not taken          an adjacency whose hub chunk plan (dory_gatmh_row_gather_hub_split) has chunks: the pass runs as with value 0
+ *                      and is counted (hub_fallbacks); an adjacency without ghosts, a rank without vertices: nothing to split, not
+ *                      counted.  The destination-side edge pass (it reads fg_z, landed during the forward), the sweep and blocked
+ *                      forms.  With dory_gatmh_row_gather_bf16_wide on, a bf16 pass that is taken runs the NARROW bf16 carry kernel
+ *                      (there is no wide carry form) and is counted (wide_not_taken).
+ * CONTRACT: one launch = two launches, BIT FOR BIT, in every tensor, weight and weight gradient -- value 1 with nothing in flight,
+ * value 2, value 1 with the exchange in flight.  Against value 0: m keeps its bits on every row (a maximum does not depend on the
+ * order of the entries); every other output changes association (ghost entries behind the local ones, the self edge between them) and
+ * agrees within the family's tolerances.  A bf16 pass equals the fp32 pass on rows rounded beforehand, bit for bit.  Two runs give the
+ * same bits (no atomics).  This holds for dory_gatmh_row_gather modes 0 / 1, gatmh_bwd_phase 0 / 1 / 2, every transport, the merged
+ * exchange, bf16 rows, bf16 halo rows, ghost twins and halo_direct_recv (the copy is built from the ids as uploaded, renumbered or not).
+ * The switch moves no bytes on the wire: the ranks of a group may differ in it.
+ * value: 0 (default), 1 or 2.  DORY_ERR_ARG: any other value, 1 / 2 on a context configured as DORY_GCN / DORY_GAT, a call while an
+ * epoch graph is being recorded.  The copy of an adjacency and the state buffer are built when the switch is set (a graph / the tensors
+ * being there) or by the first pass that needs them, the copy dropped by dory_graph_upload; neither can be built or grown inside a
+ * recording (DORY_ERR_ARG there: run one eager epoch first).
+ * Counters, in this order: forward passes and source-side passes that ran the carry kernels since dory_create (eager calls and
+ * recordings, not replays); of those forward passes, and of those source-side passes, the ones with an exchange in flight beside the
+ * first launch; local entries of the current copy of the in-edges, and of the out-edges (0 while none is built); passes left to the
+ * hub chunk plan; bf16 passes that ran the narrow carry kernel with the wide switch on.  Any pointer may be NULL.
+ * NOT MEASURED YET: tools/gatmh_row_gather_edge_split_rate.py is written (it writes profiles/r31_gatmh_row_gather_edge_split.txt); no
+ * output of it is on record and no gain is claimed.  As arithmetic, two launches cost a 0.9 KB slot written and read per boundary row
+ * (64-float rows, ldk = 32) against 6.4 KB gathered by an fp32 row of 25 edges.  The default stays 0. */
+int dory_gatmh_row_gather_edge_split(dory_ctx *ctx, int value);   /* 0 (default) = off */
+int dory_gatmh_row_gather_edge_split_stats(dory_ctx *ctx, uint64_t *fwd_split, uint64_t *src_split, uint64_t *fwd_in_flight,
+                                           uint64_t *src_in_flight, uint64_t *in_local_entries, uint64_t *out_local_entries,
+                                           uint64_t *hub_fallbacks, uint64_t *wide_not_taken);
+
 /* ---- the row-gather family: 16-byte bf16 row gathers (opt-in, default off; nothing in the reference) -------------------------
  * The family's bf16 form (dory_gatmh_row_gather_bf16) loads four bf16 -- 8 bytes -- per lane and edge: a 64-float row occupies 16
  * lanes, and every lane of a head recomputes the head's exponentials.  With this switch on, a bf16 pass of the family runs its WIDE

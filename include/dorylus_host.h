@@ -104,6 +104,15 @@ int dory_row_chunk_plan(const uint64_t *ptr, uint32_t rows, uint32_t chunk_entri
 int dory_row_interior_plan(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t *interior_out, uint32_t *boundary_out,
                            uint32_t *interior_rows, uint32_t *boundary_rows);
 
+/* Every row's entries regrouped local ids first (pure host code, no context, no device; the copy dory_gatmh_row_gather_edge_split of
+ * dorylus_hip.h builds per adjacency for the row-gather kernels).  ptr, idx as above; N: the ids < N are local, the ids >= N name ghost
+ * rows (the partition's local vertex count; rows is that count too for a partition's adjacency).  Out: idx_out (ptr[rows] entries,
+ * another array than idx) -- within every row the entries < N first, in their original order, then the entries >= N, in their original
+ * order: a stable partition, so every row keeps its ids as a multiset; mid_out (rows entries) -- the position of the row's first ghost
+ * entry, ptr[v + 1] where it has none.  ptr is not changed.  DORY_ERR_ARG: ptr NULL or not ascending, an array NULL that has entries,
+ * idx_out == idx. */
+int dory_row_edge_split_plan(const uint64_t *ptr, const uint32_t *idx, uint32_t rows, uint32_t N, uint32_t *idx_out, uint64_t *mid_out);
+
 /* upload adjacency (dory_graph_upload) and, when parts is given, both halo plans
  * (dory_halo_plan): recv slots of peer q = ghost slots whose owner is q, ascending.  On a context with option
  * "halo_direct_recv" = 1 the index arrays uploaded are the renumbered copies of dory_partition_wire_order (parts is then
