@@ -1016,8 +1016,17 @@ static int download_dense(dory_ctx *c, const Tensor &t, float *host) {
     if (t.ld == t.cols) {
         HIPCK(c, hipMemcpyAsync(host, t.d, t.bytes(), hipMemcpyDeviceToHost, c->compute));
     } else {
-        HIPCK(c, hipMemcpy2DAsync(host, (size_t)t.cols * sizeof(float), t.d, (size_t)t.ld * sizeof(float),
-                                  (size_t)t.cols * sizeof(float), t.rows, hipMemcpyDeviceToHost, c->compute));
+        // padded rows: drop the padding on the device and move one dense block, as upload_dense does the other way round.  A strided
+        // copy into pageable host memory travels row by row where the runtime cannot pin the destination -- minutes for 10^7 rows
+        float *stage = nullptr;
+        const size_t b = (size_t)t.rows * t.cols * sizeof(float);
+        HIPCK(c, hipMalloc((void **)&stage, b));
+        hipError_t e = launch_pad_copy(stage, t.cols, t.d, t.ld, t.rows, t.cols, c->compute);
+        if (e == hipSuccess) e = hipMemcpyAsync(host, stage, b, hipMemcpyDeviceToHost, c->compute);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->compute);
+        (void)hipFree(stage);
+        HIPCK(c, e);
+        return DORY_OK;
     }
     HIPCK(c, hipStreamSynchronize(c->compute));
     return DORY_OK;
