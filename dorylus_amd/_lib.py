@@ -44,6 +44,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather_edge_split", "dory_gatmh_row_gather_edge_split_stats",
     "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
     "dory_k1_bf16_wide", "dory_k1_bf16_wide_stats", "dory_k1_bf16_wide_form",
+    "dory_gemm_bf16", "dory_gemm_bf16_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -151,6 +152,8 @@ def load():
     }
     # bound only if present: DORY_LIB_PATH may name an older build (an A/B run) from before these entry points
     optional = {
+        "dory_gemm_bf16": [vp, i32],
+        "dory_gemm_bf16_stats": [vp] + [C.POINTER(u64)] * 2,
         "dory_halo_wire_ids": [vp, vp, vp, vp],
         "dory_scatter_msgs_layout": [vp, u32, i32, cp, u64, C.POINTER(ScatterMsg), u32, C.POINTER(u32), C.POINTER(u64)],
         "dory_scatter_msgs_pack": [vp, u32, i32, cp, u64, vp],
@@ -885,6 +888,19 @@ class Context:
         """dict: wide (aggregations K1 ran in the wide form since dory_create: eager calls and recordings), narrow_while_on
         (aggregations on bf16 rows K1 ran narrow with the switch on)"""
         return self._stats(self.lib.dory_k1_bf16_wide_stats, 2, self.K1_BF16_WIDE_STATS)
+
+    GEMM_BF16_STATS = ("bf16_launches", "fp32_while_on")
+
+    def gemm_bf16(self, mode=1):
+        """the vertex transforms on the bf16 matrix instruction, operands rounded on their way into LDS, fp32 sums (dory_gemm_bf16;
+        every model): 0 (default) = off; 1 = NN and NT (z, xw, grad); 2 = also TN (the weight gradient).  A product that wants a
+        send form (halo_fused_pack) keeps the fp32 kernel"""
+        self._ck(self.lib.dory_gemm_bf16(self.h, int(mode)))
+
+    def gemm_bf16_stats(self):
+        """dict: bf16_launches (products that ran the bf16 kernel since dory_create: eager calls and recordings), fp32_while_on
+        (products of a form the mode covers that ran the fp32 kernel: send forms)"""
+        return self._stats(self.lib.dory_gemm_bf16_stats, 2, self.GEMM_BF16_STATS)
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

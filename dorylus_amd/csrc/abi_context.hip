@@ -153,12 +153,21 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
     ghost_wrote_fp32(&C);   // (dory_halo_bf16_ghosts: a product written into a ghost tensor -- fgxw@0 -- is fp32 rows)
     ghost_wrote_fp32(C2);
     Timed t(c, "gemm", c->compute);
+    // dory_gemm_bf16: does the mode cover this form (1: NN and NT, 2: TN too)?
+    const bool bf16 = c->gemm_bf16 >= 2 || (c->gemm_bf16 == 1 && !ta);
     if (!sent) {
         fused_note_write(c, &C);
         fused_note_write(c, C2);
+        bool taken = false;
+        if (bf16) HIPCK(c, launch_gemm_bf16(g, c->scratch, c->scratch_bytes, c->compute, &taken));
+        if (taken) {
+            ++c->gemm_bf16_launches;
+            return DORY_OK;
+        }
         HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
         return DORY_OK;
     }
+    if (bf16) ++c->gemm_bf16_fp32;   // (no bf16 send form: the fused halo pack keeps K2's fp32 kernel)
     sd.cols = N;
     bool fused = false;
     HIPCK(c, launch_gemm_send(g, sd, c->scratch, c->scratch_bytes, c->compute, &fused));
@@ -664,6 +673,23 @@ int dory_k1_bf16_wide_stats(dory_ctx *c, uint64_t *wide, uint64_t *narrow_while_
     CHECK_CTX(c);
     if (wide) *wide = c->k1_rows8_wide;
     if (narrow_while_on) *narrow_while_on = c->k1_rows8_narrow;
+    return DORY_OK;
+}
+
+// ---- dory_gemm_bf16: the vertex transforms on the bf16 matrix instruction (gemm_bf16.hip; gemm() above routes; include/dorylus_hip.h) ----
+int dory_gemm_bf16(dory_ctx *c, int mode) {
+    CHECK_CTX(c);
+    if (mode < 0 || mode > 2) return fail(c, DORY_ERR_ARG, "gemm_bf16: mode %d is none of 0 (off), 1 (NN and NT), 2 (TN too)", mode);
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gemm_bf16: not while an epoch graph is being recorded");
+    if (mode != c->gemm_bf16) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other mode's launches)
+    c->gemm_bf16 = mode;
+    return DORY_OK;
+}
+
+int dory_gemm_bf16_stats(dory_ctx *c, uint64_t *bf16_launches, uint64_t *fp32_while_on) {
+    CHECK_CTX(c);
+    if (bf16_launches) *bf16_launches = c->gemm_bf16_launches;
+    if (fp32_while_on) *fp32_while_on = c->gemm_bf16_fp32;
     return DORY_OK;
 }
 

@@ -336,6 +336,10 @@ struct dory_ctx {
     // on (no form for the row or slab width, rows not 16-byte aligned)
     bool k1_bf16_wide = false;
     uint64_t k1_rows8_wide = 0, k1_rows8_narrow = 0;
+    // dory_gemm_bf16: the mode (0 off, 1 NN and NT, 2 also TN); the products that ran the bf16 kernel (gemm_bf16.hip), and those of a
+    // form the mode covers that ran K2's fp32 kernel all the same (a send form: the fused halo pack)
+    int gemm_bf16 = 0;
+    uint64_t gemm_bf16_launches = 0, gemm_bf16_fp32 = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -578,6 +582,13 @@ struct GemmSend {
 // NN and NT with M, K > 0: *fused = true and the rows are in buf; anything else runs as launch_gemm and leaves *fused false
 hipError_t launch_gemm_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *fused);
 size_t gemm_scratch_bytes(uint32_t M, uint32_t N, uint32_t K);
+// K2b (gemm_bf16.hip; dory_gemm_bf16): the same product on v_mfma_f32_32x32x16_bf16, the fp32 operands rounded to bf16 on their
+// way into LDS, fp32 sums; K2's geometry, split plan (gemm_pick_splits) and second-stage sum (launch_splitk_reduce).  *taken =
+// false and nothing launched for what K2's launcher answers without a kernel (M, N or K == 0) or refuses (alignment): the
+// caller then calls launch_gemm
+hipError_t launch_gemm_bf16(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken);
+uint32_t gemm_pick_splits(uint32_t M, uint32_t N, uint32_t K, int bm, int bn);
+hipError_t launch_splitk_reduce(const GemmArgs &g, const float *partial, uint32_t S, hipStream_t s);
 
 // tanh of the transform's epilogue (K2), of the stand-alone activation and of K3's backward -- one function for all three, so
 // that h and the 1 - tanh^2 of the backward pass are the same number.  libm's tanhf is ~40 vector instructions (40 M of the

@@ -509,4 +509,15 @@ hipError_t launch_gemm_send(const GemmArgs &g, const GemmSend &sd, float *scratc
     return launch_gemm_any(g, scratch, scratch_bytes, s, &sd, fused);
 }
 
+// what the bf16 form (gemm_bf16.hip) shares with this file: the split plan and the second-stage sum, as launch_bn uses them
+uint32_t gemm_pick_splits(uint32_t M, uint32_t N, uint32_t K, int bm, int bn) { return pick_splits(M, N, K, bm, bn); }
+hipError_t launch_splitk_reduce(const GemmArgs &g, const float *partial, uint32_t S, hipStream_t s) {
+    const size_t n = (size_t)g.M * g.ldc;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, g.C, partial, g.M, g.N, g.ldc, S,
+                       g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2);
+    return hipGetLastError();
+}
+
 }  // namespace dory

@@ -1,0 +1,292 @@
+// gemm_bf16.hip -- K2b: the vertex transforms on v_mfma_f32_32x32x16_bf16 (opt-in: dory_gemm_bf16, include/dorylus_hip.h).
+//
+// The operands stay fp32 in HBM and are rounded to bf16 (nearest even, v_cvt_pk_bf16_f32) in registers, between the global load
+// and the LDS write; products of two bf16 values are exact in fp32 and the sums are fp32, so a product that runs here equals the
+// fp32-accumulated product of its operands rounded to bf16.  One instruction multiplies 16 k where K2's (gemm.hip,
+// v_mfma_f32_32x32x2_f32) multiplies 2: the 602-wide products leave the matrix unit's floor for the bytes of their operands.
+//
+// Geometry: K2's.  128 x BN block (BN = 128 or 64), 256 threads, each wave a 64x64 (2x2 MFMA tiles) or 32x64 (1x2) register
+// tile, pick_splits's plan and splitk_reduce_kernel (gemm.hip) for the split products; the accumulator layout of the two 32x32
+// instructions is the same, so the store loop is K2's.
+// k-tile: GEMM_BF16_BK = 32 deep -- two 16-KB stages per 128-wide workgroup, K2's LDS footprint (64 compiles as well -- 64 KB, two workgroups
+// per CU -- and has not been measured; 32 is the recorded value).
+// LDS images: both bf16, [i][BK k], a row = BK/8 16-byte pieces (eight consecutive k of one i = one half-wave's fragment of the
+// instruction = one ds_read_b128 per lane), the pieces of row i XOR-ed by (i >> 2) & 3 (BK = 32; (i >> 1) & 7 at 64): the 16
+// lanes ds_read_b128 serves together read one logical piece of 16 consecutive rows, which the swizzle spreads over all 64 banks.
+// The two kinds of source (LDS-DMA cannot round, so the tiles travel through registers):
+//   row-major  elem(k,i) = p[i*ld+k]  (ah in NN; g, W in NT)   a lane takes pieces: two 16-byte loads, 4 cvt_pk, one 16-byte LDS write
+//   k-major    elem(k,i) = p[k*ld+i]  (W in NN; both in TN)    wave w takes the k-group(s) 8w..8w+7: a lane loads BT/64 columns
+//                                                               of eight consecutive k-rows and transposes them in registers
+// Out-of-range rows (row-major) and k-rows (k-major) read zeros through the buffer resource; what a row-major row holds past
+// kend -- padding, or the next split's k -- is cleared in registers in a split's last k-tile only (a uniform branch, as in K2).
+// Pipeline: register-staged, the loads of tile t+1 go out before the MFMAs of tile t and are rounded and written into the other
+// LDS stage after them; ONE barrier per k-tile (a stage is rewritten only after every wave has passed the barrier that follows
+// its last read).
+// Sum order per output element: k-tiles in order, inside a k-tile its 16-deep steps in order, inside a step the instruction's own
+// fixed order -- whatever the grid; the same input gives the same bits.
+// Registers (gfx950; tests/test_gemm_bf16_host.py reads them from the library), no scratch in any form:
+//   128 x 64   NN 92, NT 92, TN 84 vector registers (64 accumulator registers among them)
+//   128 x 128  TN 124 under amdgpu_waves_per_eu(4, 4), the occupancy of K2's 128 x 128 form; NN and NT 140 without that bound (three
+//              waves per SIMD): under it they spill 3-8 registers -- 64 accumulators, 32 of raw rows in flight, 16 of fragments
+#include "ctx.hpp"
+
+namespace dory {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+
+#ifndef GEMM_BF16_BK
+#define GEMM_BF16_BK 32   // k-tile depth (32 or 64)
+#endif
+
+// byte offset of the 16-byte piece q of row r in a [rows][BK] bf16 image
+template <int BK>
+__device__ __forceinline__ uint32_t img_off(uint32_t r, uint32_t q) {
+    constexpr uint32_t PPR = BK / 8;
+    const uint32_t sw = (BK == 32 ? r >> 2 : r >> 1) & (PPR - 1);
+    return r * (BK * 2) + ((q ^ sw) << 4);
+}
+
+__device__ __forceinline__ bf16x8 round8(const float (&f)[8]) {
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (__bf16)f[e];
+    return v;
+}
+
+// One operand's tile: load() requests this thread's share of the current k-tile into registers and moves on, store() rounds it
+// into an LDS image.
+template <int BT, bool KMAJOR, int BK>
+struct RegTile {
+    static constexpr int PPR = BK / 8;                              // 16-byte pieces per image row
+    static constexpr int NP = KMAJOR ? PPR / 4 : BT * PPR / 256;    // row-major: pieces per thread; k-major: k-groups per wave
+    static constexpr int CW = KMAJOR ? BT / 64 : 1;                 // k-major: columns per lane
+    float raw[NP][8][CW];
+    uint32_t voff;       // this thread's byte offset inside the current k-tile's source (constant over the k-loop)
+    uint32_t pstride;    // byte distance between its consecutive pieces / k-groups
+    uint32_t step;       // bytes the source advances per k-tile
+    const char *base;    // source of the current k-tile
+    int64_t left;        // bytes readable from base on (what lies beyond reads zeros)
+
+    __device__ __forceinline__ void init(const float *p, uint32_t ld, uint32_t ext, uint32_t i0, uint32_t k0, uint32_t kend) {
+        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const uint64_t row_b = (uint64_t)ld * 4u;
+        if constexpr (KMAJOR) {
+            base = reinterpret_cast<const char *>(p) + (uint64_t)k0 * row_b + (uint64_t)i0 * 4u;
+            voff = wave * 8u * (uint32_t)row_b + lane * (CW * 4u);
+            pstride = 32u * (uint32_t)row_b;
+            step = BK * (uint32_t)row_b;
+            left = (int64_t)(kend - k0) * (int64_t)row_b - (int64_t)i0 * 4;
+        } else {
+            base = reinterpret_cast<const char *>(p) + (uint64_t)i0 * row_b + (uint64_t)k0 * 4u;
+            voff = (threadIdx.x / PPR) * (uint32_t)row_b + (threadIdx.x % PPR) * 32u;
+            pstride = (256u / PPR) * (uint32_t)row_b;
+            step = BK * 4u;
+            left = (int64_t)(ext - i0) * (int64_t)row_b - (int64_t)k0 * 4;
+        }
+    }
+    __device__ __forceinline__ void load() {
+        const uint32_t n = left <= 0 ? 0u : (left > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)left);
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, n, 0x00020000);
+#pragma unroll
+        for (int pc = 0; pc < NP; ++pc) {
+            const uint32_t o = pc * pstride;   // (uniform: it travels as the instruction's scalar offset, which the range check counts)
+            if constexpr (KMAJOR) {
+                const uint32_t row_b = step / BK;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    if constexpr (CW == 2) {
+                        const f32x2v v = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, o + m * row_b, 0));
+                        raw[pc][m][0] = v[0];
+                        raw[pc][m][CW - 1] = v[1];
+                    } else {
+                        raw[pc][m][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, o + m * row_b, 0));
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + h * 16u, o, 0));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) raw[pc][4 * h + e][0] = v[e];
+                }
+            }
+        }
+        base += step;
+        left -= step;
+    }
+    // krem: the k-rows of the tile that count (>= BK: all of them)
+    __device__ __forceinline__ void store(char *img, uint32_t krem) {
+        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if constexpr (!KMAJOR) {
+            if (krem < (uint32_t)BK) {   // a split's last k-tile: a row holds padding or the next split's k past kend
+                const uint32_t kq = (threadIdx.x % PPR) * 8u;
+#pragma unroll
+                for (int pc = 0; pc < NP; ++pc)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (kq + e >= krem) raw[pc][e][0] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int pc = 0; pc < NP; ++pc) {
+            if constexpr (KMAJOR) {
+#pragma unroll
+                for (int c = 0; c < CW; ++c) {
+                    float f[8];
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) f[m] = raw[pc][m][c];
+                    *reinterpret_cast<bf16x8 *>(img + img_off<BK>(lane * CW + c, pc * 4 + wave)) = round8(f);
+                }
+            } else {
+                float f[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[e] = raw[pc][e][0];
+                *reinterpret_cast<bf16x8 *>(img + img_off<BK>(pc * (256 / PPR) + threadIdx.x / PPR, threadIdx.x % PPR)) = round8(f);
+            }
+        }
+    }
+};
+
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__device__ __forceinline__ void gemm_bf16_body(const GemmArgs &g, uint32_t klen, float *partial, char *smem) {
+    static_assert(WM * WN == 4 && WN * TN * 32 == BN, "tile shape");
+    static_assert(BK == 32 || BK == 64, "image geometry is written for 32- and 64-deep k-tiles");
+    constexpr int BM = WM * TM * 32;
+    constexpr int A_B = BM * BK * 2, STAGE = (BM + BN) * BK * 2;   // bytes
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const uint32_t i0 = blockIdx.x * BM;
+    const uint32_t j0 = blockIdx.y * BN;
+    const uint32_t kbeg = blockIdx.z * klen;
+    const uint32_t kend = min(g.K, kbeg + klen);
+    const int fr = lane & 31, fk = lane >> 5;
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+    RegTile<BM, A_KMAJOR, BK> ta;
+    RegTile<BN, B_KMAJOR, BK> tb;
+    ta.init(g.A, g.lda, g.M, i0, kbeg, kend);
+    tb.init(g.B, g.ldb, g.N, j0, kbeg, kend);
+    const uint32_t T = kbeg < kend ? (kend - kbeg + BK - 1) / BK : 0;
+    if (T) {
+        ta.load();
+        tb.load();
+        ta.store(smem, kend - kbeg);
+        tb.store(smem + A_B, kend - kbeg);
+    }
+    for (uint32_t t = 0; t < T; ++t) {
+        if (t + 1 < T) {   // the next tile's loads travel under this tile's MFMAs
+            ta.load();
+            tb.load();
+        }
+        // everybody's pieces of tile t are in stage t & 1, and nobody still reads the other stage (its MFMAs came before this barrier)
+        __syncthreads();
+        const char *As = smem + (t & 1) * STAGE;
+        const char *Bs = As + A_B;
+#pragma unroll
+        for (int s = 0; s < BK / 16; ++s) {
+            bf16x8 af[TM], bf[TN];
+#pragma unroll
+            for (int a = 0; a < TM; ++a) af[a] = *reinterpret_cast<const bf16x8 *>(As + img_off<BK>((wm * TM + a) * 32 + fr, 2 * s + fk));
+#pragma unroll
+            for (int b = 0; b < TN; ++b) bf[b] = *reinterpret_cast<const bf16x8 *>(Bs + img_off<BK>((wn * TN + b) * 32 + fr, 2 * s + fk));
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TN; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a], bf[b], acc[a][b], 0, 0, 0);
+        }
+        if (t + 1 < T) {
+            char *nx = smem + ((t + 1) & 1) * STAGE;
+            const uint32_t krem = kend - kbeg - (t + 1) * BK;
+            ta.store(nx, krem);
+            tb.store(nx + A_B, krem);
+        }
+    }
+
+    const bool split = gridDim.z > 1;
+    float *C = split ? partial + (size_t)blockIdx.z * g.M * g.ldc : g.C;
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b) {
+            const uint32_t col = j0 + (wn * TN + b) * 32 + fr;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t row = i0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+                if (row < g.M && col < g.N) {
+                    const float v = acc[a][b][r];
+                    C[(size_t)row * g.ldc + col] = v;
+                    if (!split && g.epilogue == EPI_TANH) g.C2[(size_t)row * g.ldc2 + col] = dory_tanh(v);
+                }
+            }
+        }
+}
+
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g, uint32_t klen, float *partial) {
+    __shared__ __attribute__((aligned(1024))) char smem[2 * (WM * TM * 32 + BN) * BK * 2];
+    gemm_bf16_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK>(g, klen, partial, smem);
+}
+// the 128 x 128 TN form at K2's occupancy, four waves per SIMD (NN and NT, whose row-major A tile stages 16 more registers of
+// addresses and raw rows, spill 3-8 registers under that bound and run at three: file header)
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_bf16_kernel_occ4(GemmArgs g, uint32_t klen,
+                                                                                                      float *partial) {
+    __shared__ __attribute__((aligned(1024))) char smem[2 * (WM * TM * 32 + BN) * BK * 2];
+    gemm_bf16_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK>(g, klen, partial, smem);
+}
+
+template <int BN, int WM, int WN, int TM, int TN, int BK>
+static hipError_t launch_bf16_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s) {
+    constexpr int BM = WM * TM * 32;
+    uint32_t S = gemm_pick_splits(g.M, g.N, g.K, BM, BN);
+    if (S > 1 && (size_t)S * g.M * g.ldc * sizeof(float) > scratch_bytes) {
+        S = (uint32_t)(scratch_bytes / ((size_t)g.M * g.ldc * sizeof(float)));
+        if (S < 2) S = 1;
+    }
+    // a split's k-length is rounded to THIS file's k-tile (K2 rounds to 16): the rounding can only lower the split count below
+    // the one pick_splits chose, so the scratch gemm_scratch_bytes sized for K2 still suffices
+    uint32_t klen = (g.K + S - 1) / S;
+    klen = (klen + BK - 1) / BK * BK;
+    S = (g.K + klen - 1) / klen;
+    dim3 grid((g.M + BM - 1) / BM, (g.N + BN - 1) / BN, S);
+    dim3 block(256);
+#define GEMM_BF16_LAUNCH(AK, BKM)                                                                                              \
+    do {                                                                                                                       \
+        if constexpr (BN == 128 && AK)                                                                                         \
+            hipLaunchKernelGGL((gemm_bf16_kernel_occ4<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch); \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((gemm_bf16_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch);      \
+    } while (0)
+    if (!g.ta && !g.tb) GEMM_BF16_LAUNCH(false, true);
+    else if (!g.ta && g.tb) GEMM_BF16_LAUNCH(false, false);
+    else if (g.ta && !g.tb) GEMM_BF16_LAUNCH(true, true);
+    else return hipErrorInvalidValue;
+#undef GEMM_BF16_LAUNCH
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || S == 1) return e;
+    return launch_splitk_reduce(g, scratch, S, s);
+}
+
+// *taken = false and nothing launched where K2's launcher does something else than run a kernel, or refuses: an empty product
+// (K == 0 is its memset) and operands off its 16-byte rule -- the caller then calls launch_gemm, which behaves as ever
+hipError_t launch_gemm_bf16(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken) {
+    *taken = false;
+    if (g.M == 0 || g.N == 0 || g.K == 0 || (g.ta && g.tb)) return hipSuccess;
+    if ((g.lda & 3u) || (g.ldb & 3u) || (reinterpret_cast<uintptr_t>(g.A) & 15u) || (reinterpret_cast<uintptr_t>(g.B) & 15u)) return hipSuccess;
+    *taken = true;
+    if (g.N > 64) return launch_bf16_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
+    return launch_bf16_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
+}
+
+}  // namespace dory

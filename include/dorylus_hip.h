@@ -811,6 +811,30 @@ int dory_k1_bf16_wide(dory_ctx *ctx, int on);   /* 0 (default) = off */
 int dory_k1_bf16_wide_stats(dory_ctx *ctx, uint64_t *wide, uint64_t *narrow_while_on);
 int dory_k1_bf16_wide_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t *chunks);
 
+/* ---- K2b, the vertex transforms on the bf16 matrix instruction (opt-in, default off; nothing in the reference) -----------------
+ * K2 (csrc/gemm.hip) multiplies in fp32, two k per v_mfma_f32_32x32x2_f32; its 602-wide products are bound by that instruction, not
+ * by the bytes they read.  With a mode on, a product the mode covers runs K2b (csrc/gemm_bf16.hip, gemm_bf16_kernel) instead: the
+ * operands stay fp32 in memory -- no shadow tensor, no conversion kernel, no new buffer -- and are rounded to bf16 (nearest even) in
+ * registers on their way into LDS; v_mfma_f32_32x32x16_bf16 multiplies sixteen k per instruction into fp32 sums.  K2's tiles, split-K
+ * plan and deterministic second-stage sum; the tanh epilogue as in K2.
+ *   mode 0 (default)  off: every product runs K2, launch for launch what it ran before this entry point existed.
+ *   mode 1            NN and NT -- the products over feature widths: z = ah W (with h = tanh z), xw = x W, grad = g W^T.
+ *   mode 2            also TN, the weight gradient dW = ah^T g, whose sum runs over all vertices.
+ * Legal on every model (DORY_GCN, DORY_GAT, DORY_GATMH): all of them reach K2 through one helper.
+ * CONTRACT: a product that runs K2b equals the fp32-accumulated product of its operands rounded to bf16: per element at most
+ * (K + splits) 2^-23 sum_k |A^[i,k]| |B^[k,j]| from the exact product of the rounded operands A^, B^; on operands that are exact in
+ * bf16 (small integers) the exact product, bit for bit.  The sum order per element is fixed whatever the grid: the same input gives
+ * the same bits.  Nothing else in the context changes; mode 0 after any other mode gives the bits of a context that never called this.
+ * WHERE K2 STILL RUNS with a mode on: a product that wants a SEND form (dory_halo_fused_pack: the epilogue also writes the rows into the
+ * send buffer) -- there is no bf16 send form, so for those products the two features cancel: the fused pack wins and the product is fp32
+ * (counted: fp32_while_on).  K == 0, M == 0 and operands off K2's 16-byte alignment rule behave as with mode 0.
+ * DORY_ERR_ARG: a mode other than 0, 1, 2; a call while an epoch graph is being recorded.  A change drops a recorded epoch graph.
+ * Counters, in this order: products that ran K2b since dory_create (eager calls and recordings, not replays); products of a form the
+ * mode covers that ran K2's fp32 kernel.  Any pointer may be NULL.
+ * MEASURED: see DESIGN.md section 3 (profiles/r32_gemm_bf16.txt). */
+int dory_gemm_bf16(dory_ctx *ctx, int mode);   /* 0 (default) = off */
+int dory_gemm_bf16_stats(dory_ctx *ctx, uint64_t *bf16_launches, uint64_t *fp32_while_on);
+
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
  * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels
