@@ -44,7 +44,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather_edge_split", "dory_gatmh_row_gather_edge_split_stats",
     "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
     "dory_k1_bf16_wide", "dory_k1_bf16_wide_stats", "dory_k1_bf16_wide_form",
-    "dory_gemm_bf16", "dory_gemm_bf16_stats",
+    "dory_gemm_bf16", "dory_gemm_bf16_stats", "dory_gemm_bf16_split", "dory_gemm_bf16_split_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -154,6 +154,8 @@ def load():
     optional = {
         "dory_gemm_bf16": [vp, i32],
         "dory_gemm_bf16_stats": [vp] + [C.POINTER(u64)] * 2,
+        "dory_gemm_bf16_split": [vp, i32],
+        "dory_gemm_bf16_split_stats": [vp, C.POINTER(u64)],
         "dory_halo_wire_ids": [vp, vp, vp, vp],
         "dory_scatter_msgs_layout": [vp, u32, i32, cp, u64, C.POINTER(ScatterMsg), u32, C.POINTER(u32), C.POINTER(u64)],
         "dory_scatter_msgs_pack": [vp, u32, i32, cp, u64, vp],
@@ -901,6 +903,15 @@ class Context:
         """dict: bf16_launches (products that ran the bf16 kernel since dory_create: eager calls and recordings), fp32_while_on
         (products of a form the mode covers that ran the fp32 kernel: send forms)"""
         return self._stats(self.lib.dory_gemm_bf16_stats, 2, self.GEMM_BF16_STATS)
+
+    def gemm_bf16_split(self, on=1):
+        """the products gemm_bf16's mode covers on two bf16 pieces per operand, three matrix instructions per sixteen k, fp32 sums
+        (dory_gemm_bf16_split; every model): inside the fp32 parity criteria; 0 (default) = off; inert while the mode is 0"""
+        self._ck(self.lib.dory_gemm_bf16_split(self.h, int(on)))
+
+    def gemm_bf16_split_stats(self):
+        """dict: split_launches (products that ran the two-piece kernel since dory_create; each also counts in bf16_launches)"""
+        return self._stats(self.lib.dory_gemm_bf16_split_stats, 1, ("split_launches",))
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

@@ -159,9 +159,10 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
         fused_note_write(c, &C);
         fused_note_write(c, C2);
         bool taken = false;
-        if (bf16) HIPCK(c, launch_gemm_bf16(g, c->scratch, c->scratch_bytes, c->compute, &taken));
+        if (bf16) HIPCK(c, (c->gemm_bf16_split ? launch_gemm_bf16_split : launch_gemm_bf16)(g, c->scratch, c->scratch_bytes, c->compute, &taken));
         if (taken) {
             ++c->gemm_bf16_launches;
+            c->gemm_bf16_split_launches += c->gemm_bf16_split;
             return DORY_OK;
         }
         HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
@@ -690,6 +691,22 @@ int dory_gemm_bf16_stats(dory_ctx *c, uint64_t *bf16_launches, uint64_t *fp32_wh
     CHECK_CTX(c);
     if (bf16_launches) *bf16_launches = c->gemm_bf16_launches;
     if (fp32_while_on) *fp32_while_on = c->gemm_bf16_fp32;
+    return DORY_OK;
+}
+
+// ---- dory_gemm_bf16_split: the products dory_gemm_bf16 covers on two bf16 pieces per operand (gemm_bf16_split.hip; gemm() above routes) ----
+int dory_gemm_bf16_split(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gemm_bf16_split: value %d is neither 0 nor 1", on);
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gemm_bf16_split: not while an epoch graph is being recorded");
+    if ((on == 1) != c->gemm_bf16_split) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->gemm_bf16_split = on == 1;
+    return DORY_OK;
+}
+
+int dory_gemm_bf16_split_stats(dory_ctx *c, uint64_t *split_launches) {
+    CHECK_CTX(c);
+    if (split_launches) *split_launches = c->gemm_bf16_split_launches;
     return DORY_OK;
 }
 

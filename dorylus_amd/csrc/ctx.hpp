@@ -340,6 +340,9 @@ struct dory_ctx {
     // form the mode covers that ran K2's fp32 kernel all the same (a send form: the fused halo pack)
     int gemm_bf16 = 0;
     uint64_t gemm_bf16_launches = 0, gemm_bf16_fp32 = 0;
+    // dory_gemm_bf16_split: the switch (inert at mode 0); those of gemm_bf16_launches that ran the two-piece kernel (gemm_bf16_split.hip)
+    bool gemm_bf16_split = false;
+    uint64_t gemm_bf16_split_launches = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -587,6 +590,9 @@ size_t gemm_scratch_bytes(uint32_t M, uint32_t N, uint32_t K);
 // false and nothing launched for what K2's launcher answers without a kernel (M, N or K == 0) or refuses (alignment): the
 // caller then calls launch_gemm
 hipError_t launch_gemm_bf16(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken);
+// K2c (gemm_bf16_split.hip; dory_gemm_bf16_split): K2b with each operand split into two bf16 pieces in registers and three instructions
+// per 16 k (a_lo b_hi + a_hi b_lo + a_hi b_hi) -- the bf16 matrix unit inside the fp32 parity criteria; *taken as above
+hipError_t launch_gemm_bf16_split(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken);
 uint32_t gemm_pick_splits(uint32_t M, uint32_t N, uint32_t K, int bm, int bn);
 hipError_t launch_splitk_reduce(const GemmArgs &g, const float *partial, uint32_t S, hipStream_t s);
 

@@ -1,0 +1,151 @@
+// gemm_bf16_tile.hpp -- what K2b (gemm_bf16.hip) and K2c (gemm_bf16_split.hip) share: the swizzled [i][BK k] bf16 LDS image, the
+// register-staged loader of one operand's fp32 tile, and the launch plan (split count and k-length) of a 128 x BN product.
+#pragma once
+#include "ctx.hpp"
+
+namespace dory {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+
+#ifndef GEMM_BF16_BK
+#define GEMM_BF16_BK 32   // k-tile depth (32 or 64)
+#endif
+
+// byte offset of the 16-byte piece q of row r in a [rows][BK] bf16 image
+template <int BK>
+__device__ __forceinline__ uint32_t img_off(uint32_t r, uint32_t q) {
+    constexpr uint32_t PPR = BK / 8;
+    const uint32_t sw = (BK == 32 ? r >> 2 : r >> 1) & (PPR - 1);
+    return r * (BK * 2) + ((q ^ sw) << 4);
+}
+
+__device__ __forceinline__ bf16x8 round8(const float (&f)[8]) {
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (__bf16)f[e];
+    return v;
+}
+
+// One operand's tile: load() requests this thread's share of the current k-tile into registers and moves on; pieces() hands the
+// eight consecutive k of every (image row, 16-byte piece) this thread holds to `emit`, store() rounds them into one LDS image.
+template <int BT, bool KMAJOR, int BK>
+struct RegTile {
+    static constexpr int PPR = BK / 8;                              // 16-byte pieces per image row
+    static constexpr int NP = KMAJOR ? PPR / 4 : BT * PPR / 256;    // row-major: pieces per thread; k-major: k-groups per wave
+    static constexpr int CW = KMAJOR ? BT / 64 : 1;                 // k-major: columns per lane
+    float raw[NP][8][CW];
+    uint32_t voff;       // this thread's byte offset inside the current k-tile's source (constant over the k-loop)
+    uint32_t pstride;    // byte distance between its consecutive pieces / k-groups
+    uint32_t step;       // bytes the source advances per k-tile
+    const char *base;    // source of the current k-tile
+    int64_t left;        // bytes readable from base on (what lies beyond reads zeros)
+
+    __device__ __forceinline__ void init(const float *p, uint32_t ld, uint32_t ext, uint32_t i0, uint32_t k0, uint32_t kend) {
+        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const uint64_t row_b = (uint64_t)ld * 4u;
+        if constexpr (KMAJOR) {
+            base = reinterpret_cast<const char *>(p) + (uint64_t)k0 * row_b + (uint64_t)i0 * 4u;
+            voff = wave * 8u * (uint32_t)row_b + lane * (CW * 4u);
+            pstride = 32u * (uint32_t)row_b;
+            step = BK * (uint32_t)row_b;
+            left = (int64_t)(kend - k0) * (int64_t)row_b - (int64_t)i0 * 4;
+        } else {
+            base = reinterpret_cast<const char *>(p) + (uint64_t)i0 * row_b + (uint64_t)k0 * 4u;
+            voff = (threadIdx.x / PPR) * (uint32_t)row_b + (threadIdx.x % PPR) * 32u;
+            pstride = (256u / PPR) * (uint32_t)row_b;
+            step = BK * 4u;
+            left = (int64_t)(ext - i0) * (int64_t)row_b - (int64_t)k0 * 4;
+        }
+    }
+    __device__ __forceinline__ void load() {
+        const uint32_t n = left <= 0 ? 0u : (left > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)left);
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, n, 0x00020000);
+#pragma unroll
+        for (int pc = 0; pc < NP; ++pc) {
+            const uint32_t o = pc * pstride;   // (uniform: it travels as the instruction's scalar offset, which the range check counts)
+            if constexpr (KMAJOR) {
+                const uint32_t row_b = step / BK;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    if constexpr (CW == 2) {
+                        const f32x2v v = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, o + m * row_b, 0));
+                        raw[pc][m][0] = v[0];
+                        raw[pc][m][CW - 1] = v[1];
+                    } else {
+                        raw[pc][m][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, o + m * row_b, 0));
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + h * 16u, o, 0));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) raw[pc][4 * h + e][0] = v[e];
+                }
+            }
+        }
+        base += step;
+        left -= step;
+    }
+    // krem: the k-rows of the tile that count (>= BK: all of them); emit(image row, piece, the piece's eight floats)
+    template <class Emit>
+    __device__ __forceinline__ void pieces(uint32_t krem, Emit &&emit) {
+        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if constexpr (!KMAJOR) {
+            if (krem < (uint32_t)BK) {   // a split's last k-tile: a row holds padding or the next split's k past kend
+                const uint32_t kq = (threadIdx.x % PPR) * 8u;
+#pragma unroll
+                for (int pc = 0; pc < NP; ++pc)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (kq + e >= krem) raw[pc][e][0] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int pc = 0; pc < NP; ++pc) {
+            if constexpr (KMAJOR) {
+#pragma unroll
+                for (int c = 0; c < CW; ++c) {
+                    float f[8];
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) f[m] = raw[pc][m][c];
+                    emit(lane * CW + c, pc * 4 + wave, f);
+                }
+            } else {
+                float f[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[e] = raw[pc][e][0];
+                emit(pc * (256 / PPR) + threadIdx.x / PPR, threadIdx.x % PPR, f);
+            }
+        }
+    }
+    __device__ __forceinline__ void store(char *img, uint32_t krem) {
+        pieces(krem, [&](uint32_t r, uint32_t q, const float (&f)[8]) { *reinterpret_cast<bf16x8 *>(img + img_off<BK>(r, q)) = round8(f); });
+    }
+};
+
+// The grid of a BM x BN product with BK-deep k-tiles: gemm_pick_splits's count within the scratch, then a split's k-length rounded to
+// the k-tile (K2 rounds to 16) -- the rounding can only lower the split count below the one pick_splits chose, so the scratch
+// gemm_scratch_bytes sized for K2 still suffices.  *klen: the k of one split; the grid's z is the split count.
+inline dim3 gemm_bf16_grid(const GemmArgs &g, int BM, int BN, int BK, size_t scratch_bytes, uint32_t *klen) {
+    uint32_t S = gemm_pick_splits(g.M, g.N, g.K, BM, BN);
+    if (S > 1 && (size_t)S * g.M * g.ldc * sizeof(float) > scratch_bytes) {
+        S = (uint32_t)(scratch_bytes / ((size_t)g.M * g.ldc * sizeof(float)));
+        if (S < 2) S = 1;
+    }
+    *klen = (g.K + S - 1) / S;
+    *klen = (*klen + BK - 1) / BK * BK;
+    return dim3((g.M + BM - 1) / BM, (g.N + BN - 1) / BN, (g.K + *klen - 1) / *klen);
+}
+
+// *taken of launch_gemm_bf16 / launch_gemm_bf16_split: false where K2's launcher does something else than run a kernel, or refuses --
+// an empty product (K == 0 is its memset) and operands off its 16-byte rule
+inline bool gemm_bf16_takes(const GemmArgs &g) {
+    if (g.M == 0 || g.N == 0 || g.K == 0 || (g.ta && g.tb)) return false;
+    return !((g.lda & 3u) || (g.ldb & 3u) || (reinterpret_cast<uintptr_t>(g.A) & 15u) || (reinterpret_cast<uintptr_t>(g.B) & 15u));
+}
+
+}  // namespace dory

@@ -835,6 +835,32 @@ int dory_k1_bf16_wide_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t
 int dory_gemm_bf16(dory_ctx *ctx, int mode);   /* 0 (default) = off */
 int dory_gemm_bf16_stats(dory_ctx *ctx, uint64_t *bf16_launches, uint64_t *fp32_while_on);
 
+/* ---- K2c, the bf16 matrix instruction at fp32 parity: two bf16 pieces per operand (opt-in, default off; nothing in the reference) ----
+ * K2b's rounding of an operand to 8 significant bits moves a product by about 2^-9, hundreds of times outside the fp32 parity criteria
+ * (1e-4 relative; tests/helpers.py).  With this switch on, every product that dory_gemm_bf16's mode hands to K2b -- NN and NT at mode 1,
+ * TN too at mode 2 -- runs K2c (csrc/gemm_bf16_split.hip, gemm_bf16x3_kernel) instead: each fp32 operand is split in registers, on its
+ * way into LDS, into hi = bf16(x) and lo = bf16(x - hi), and three v_mfma_f32_32x32x16_bf16 per sixteen k add a_lo b_hi, a_hi b_lo and
+ * a_hi b_hi, in this order, into one fp32 accumulator.  The operands stay fp32 in memory: no shadow tensor, no conversion kernel, no new
+ * buffer.  K2b's tiles, split-K plan and second-stage sum; the tanh epilogue as in K2.
+ * on: 0 (default) or 1.  Inert while dory_gemm_bf16's mode is 0; legal before dory_configure and on every model.
+ * CONTRACT: with A = A_h + A_l + rho_A, A_h = A rounded to bf16 (nearest even), A_l = bf16(A - A_h), and B likewise, a product that runs
+ * K2c is the fp32-accumulated sum of A_l B_h + A_h B_l + A_h B_h.
+ *   exact inputs: where one operand is exact in bf16 and the other exact as hi + lo (every integer of magnitude below 2^16 is), the
+ *     exact product, bit for bit, while the sums stay below 2^24;
+ *   real inputs: with R the exact value of A_l B_h + A_h B_l + A_h B_h and mag = |A_l||B_h| + |A_h||B_l| + |A_h||B_h|, every element
+ *     lies within (3 K + splits) 2^-23 mag[i,j] of R[i,j] (one ulp per addition), and R within 3 2^-16 (|A||B|)[i,j] of the exact
+ *     product of the unrounded operands.
+ * The sum order per element is fixed whatever the grid: the same input gives the same bits.  Mode 0, or the switch off, leaves every
+ * launch as it is without this entry point.
+ * WHERE K2 STILL RUNS: exactly where it does under dory_gemm_bf16 -- a product that wants a SEND form (dory_halo_fused_pack) keeps K2's
+ * fp32 kernel (counted: fp32_while_on of dory_gemm_bf16_stats); K == 0, M == 0, N == 0 and operands off K2's 16-byte rule as with mode 0.
+ * DORY_ERR_ARG: a value other than 0 or 1; a call while an epoch graph is being recorded.  A change drops a recorded epoch graph.
+ * Counter: products that ran K2c since dory_create (eager calls and recordings, not replays); each of them also counts in bf16_launches
+ * of dory_gemm_bf16_stats, whose meaning does not change.  The pointer may be NULL.
+ * MEASURED: see DESIGN.md section 3. */
+int dory_gemm_bf16_split(dory_ctx *ctx, int on);   /* 0 (default) = off */
+int dory_gemm_bf16_split_stats(dory_ctx *ctx, uint64_t *split_launches);
+
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
  * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels

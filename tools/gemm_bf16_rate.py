@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Does the bf16 matrix instruction pay in the vertex transforms (dory_gemm_bf16; csrc/gemm_bf16.hip)?
+"""Does the bf16 matrix instruction pay in the vertex transforms (dory_gemm_bf16; csrc/gemm_bf16.hip), and what does fp32 parity cost on
+it (dory_gemm_bf16_split; csrc/gemm_bf16_split.hip)?
 
-Three arms, alternated over the rounds, every measurement a child process of its own under a time limit (the first that fails or runs
+Four arms, alternated over the rounds, every measurement a child process of its own under a time limit (the first that fails or runs
 out of time ends the run):
   arm `parent`   --parent-lib (a build of the parent commit; without it the arm is left out)
   arm `off`      this tree's library, mode 0
-  arm `bf16`     this tree's library, mode 2
+  arm `bf16`     this tree's library, mode 2, the split off (K2b)
+  arm `split`    this tree's library, mode 2, the split on (K2c)
 PRODUCT lines: the device time (the library's `gemm` timing family, HIP events around K2's launches) of the three products of a
 layer d_in -> d_out over V rows, on a GCN context whose graph is a ring (the vertex stage does not look at it):
   NN  forward of a hidden layer at layer 0 (z = ah W with the tanh epilogue)        TN  backward of layer 0 (dW = ah^T g)
@@ -17,7 +19,8 @@ csrc/gemm.hip's notes use for the narrow products.
 EPOCH lines: the Reddit-size GCN epoch (bench.py's uniform graph and loop) in the default order, transform-first
 (gcn_transform_first = 2) and with the layer-0 aggregate kept (gcn_cache_ah0 = 1).
 RATIO lines: medians with the runs' ranges; `inside the spread` when two medians differ by no more than the larger range.
-GPU box only:  python tools/gemm_bf16_rate.py [--out FILE] [--parent-lib LIB] [--rounds 3] [--step-timeout 240] [--no-epochs] [--no-products]"""
+GPU box only:  python tools/gemm_bf16_rate.py [--out FILE] [--parent-lib LIB] [--rounds 3] [--step-timeout 240] [--no-epochs] [--no-products]
+               [--settings default,cached_ah0]"""
 import argparse
 import os
 import subprocess
@@ -32,7 +35,7 @@ sys.path.insert(0, ROOT)
 SHAPES = [("reddit", 232965, 602, 128), ("reddit", 232965, 128, 41), ("amazon/8", 1178761, 300, 64), ("amazon/8", 1178761, 64, 64),
           ("amazon/8", 1178761, 64, 25), ("friendster/32", 2050261, 256, 48)]
 SETTINGS = {"default": {}, "transform_first": {"gcn_transform_first": 2}, "cached_ah0": {"gcn_cache_ah0": 1}}
-ARMS = ("parent", "off", "bf16")
+ARMS = ("parent", "off", "bf16", "split")
 CALLS = 10
 COPY_TBPS = 5.0
 
@@ -51,6 +54,13 @@ def _timed(ctx, fn):
     return ms / CALLS
 
 
+def _set_arm(ctx, arm):
+    if arm in ("bf16", "split"):
+        ctx.gemm_bf16(2)
+    if arm == "split":
+        ctx.gemm_bf16_split(1)
+
+
 def product_child(arm, name, V, din, dout):
     import dorylus_amd as da
     V, din, dout = int(V), int(din), int(dout)
@@ -64,8 +74,7 @@ def product_child(arm, name, V, din, dout):
         part.upload(ctx, None)
         ctx.preallocate()
         ctx.weights_init_xavier()
-        if arm == "bf16":
-            ctx.gemm_bf16(2)
+        _set_arm(ctx, arm)
         ctx.fill_uniform(layer, "ah", 1, -1.0, 1.0, g["localToGlobal"])
         ctx.fill_uniform(layer, "aTg", 2, -1.0, 1.0, g["localToGlobal"])
         fwd = _timed(ctx, lambda: ctx.apply_vertex(layer, da.FORWARD))
@@ -76,7 +85,8 @@ def product_child(arm, name, V, din, dout):
             ms["NT"] = bwd - ms["TN"]
         if arm != "parent":
             s = ctx.gemm_bf16_stats()
-            assert (s["bf16_launches"] > 0) == (arm == "bf16") and s["fp32_while_on"] == 0, s
+            assert (s["bf16_launches"] > 0) == (arm != "off") and s["fp32_while_on"] == 0, s
+            assert ctx.gemm_bf16_split_stats()["split_launches"] == (s["bf16_launches"] if arm == "split" else 0)
         ctx.close()
     for form, (M, N, K) in (("NN", (V, dout, din)), ("NT", (V, din, dout)), ("TN", (din, dout, V))):
         floor = 4.0 * (M * K + K * N + M * N * (2 if form == "NN" else 1)) / (COPY_TBPS * 1e12) * 1e3
@@ -99,8 +109,7 @@ def epoch_child(arm, setting, path):
         print("# EPOCH reddit transform_first %s: the order is not active on this partition (asymmetric adjacency values): not measured" % arm)
         ctx.close()
         return
-    if arm == "bf16":
-        ctx.gemm_bf16(2)
+    _set_arm(ctx, arm)
     ctx.fill_uniform(0, "x", 1, -1.0, 1.0, g["localToGlobal"])
     ctx.labels_upload(np.random.default_rng(2).integers(0, DIMS[-1], REDDIT_V).astype(np.uint32)[g["localToGlobal"]])
     ctx.weights_init_xavier()
@@ -129,6 +138,7 @@ def main():
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--no-epochs", action="store_true")
     ap.add_argument("--no-products", action="store_true")
+    ap.add_argument("--settings", default=",".join(SETTINGS), help="the EPOCH lines to run")
     ap.add_argument("--child", nargs="+")
     a = ap.parse_args()
     if a.child:
@@ -173,7 +183,7 @@ def main():
             path = os.path.join(tmp, "reddit.part")
             part.save(path)
             part.close()
-            steps += [["epoch", arm, setting, path] for setting in SETTINGS for arm in arms]
+            steps += [["epoch", arm, setting, path] for setting in a.settings.split(",") for arm in arms]
         ok = True
         for rnd in range(a.rounds):
             for s in steps:
@@ -198,6 +208,8 @@ def main():
         if "off" in arms_ and "bf16" in arms_:
             ln = "RATIO %s | " % key + " | ".join("%s_ms %.4f (%.4f..%.4f)" % (k, float(np.median(v)), min(v), max(v)) for k, v in arms_.items())
             ln += (" | floor_ms %s" % floor if floor else "") + " | bf16_over_off %s" % verdict(arms_["bf16"], arms_["off"])
+            if "split" in arms_:
+                ln += " | split_over_off %s | split_over_bf16 %s" % (verdict(arms_["split"], arms_["off"]), verdict(arms_["split"], arms_["bf16"]))
             if "parent" in arms_:
                 ln += " | off_over_parent %s" % verdict(arms_["off"], arms_["parent"])
             say(ln)
