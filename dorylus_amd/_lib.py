@@ -45,6 +45,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
     "dory_k1_bf16_wide", "dory_k1_bf16_wide_stats", "dory_k1_bf16_wide_form",
     "dory_gemm_bf16", "dory_gemm_bf16_stats", "dory_gemm_bf16_split", "dory_gemm_bf16_split_stats",
+    "dory_gemm_bf16_send", "dory_gemm_bf16_send_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -156,6 +157,8 @@ def load():
         "dory_gemm_bf16_stats": [vp] + [C.POINTER(u64)] * 2,
         "dory_gemm_bf16_split": [vp, i32],
         "dory_gemm_bf16_split_stats": [vp, C.POINTER(u64)],
+        "dory_gemm_bf16_send": [vp, i32],
+        "dory_gemm_bf16_send_stats": [vp] + [C.POINTER(u64)] * 2,
         "dory_halo_wire_ids": [vp, vp, vp, vp],
         "dory_scatter_msgs_layout": [vp, u32, i32, cp, u64, C.POINTER(ScatterMsg), u32, C.POINTER(u32), C.POINTER(u64)],
         "dory_scatter_msgs_pack": [vp, u32, i32, cp, u64, vp],
@@ -912,6 +915,17 @@ class Context:
     def gemm_bf16_split_stats(self):
         """dict: split_launches (products that ran the two-piece kernel since dory_create; each also counts in bf16_launches)"""
         return self._stats(self.lib.dory_gemm_bf16_split_stats, 1, ("split_launches",))
+
+    def gemm_bf16_send(self, on=1):
+        """the products gemm_bf16's mode covers that feed a halo exchange keep the bf16 kernel under halo_fused_pack: its own send epilogue
+        writes the send rows (dory_gemm_bf16_send; every model); 0 (default) = off: those products run the fp32 send kernel; inert
+        while the mode is 0 or halo_fused_pack is off"""
+        self._ck(self.lib.dory_gemm_bf16_send(self.h, int(on)))
+
+    def gemm_bf16_send_stats(self):
+        """dict: send_launches (products whose bf16 kernel also wrote the send rows since dory_create; each also counts in
+        bf16_launches), plain_while_on (products with a send target that ran the plain bf16 kernel: the send rule refused)"""
+        return self._stats(self.lib.dory_gemm_bf16_send_stats, 2, ("send_launches", "plain_while_on"))
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

@@ -168,9 +168,27 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
         HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
         return DORY_OK;
     }
-    if (bf16) ++c->gemm_bf16_fp32;   // (no bf16 send form: the fused halo pack keeps K2's fp32 kernel)
     sd.cols = N;
     bool fused = false;
+    if (bf16 && c->gemm_bf16_send) {   // dory_gemm_bf16_send: K2b's / K2c's own send epilogue writes the rows
+        bool taken = false;
+        HIPCK(c, (c->gemm_bf16_split ? launch_gemm_bf16_split_send : launch_gemm_bf16_send)(g, sd, c->scratch, c->scratch_bytes, c->compute, &taken, &fused));
+        if (taken) {
+            ++c->gemm_bf16_launches;
+            c->gemm_bf16_split_launches += c->gemm_bf16_split;
+            if (fused) {
+                ++c->gemm_bf16_send_launches;
+                fused_pack_stamp(c, sent, send_dir, sd);
+            } else {   // (the send rule refused: the plain bf16 kernel ran, the exchange packs)
+                ++c->gemm_bf16_send_plain;
+                if (c->fused_stamp.src == sent) fused_stamp_drop(c);
+            }
+            return DORY_OK;
+        }
+    }
+    // no bf16 send form asked for or taken: the fused halo pack keeps K2's fp32 kernel (with the switch on, an empty product -- an empty
+    // rank's -- is not counted: it launches nothing)
+    if (bf16 && !(c->gemm_bf16_send && (M == 0 || N == 0))) ++c->gemm_bf16_fp32;
     HIPCK(c, launch_gemm_send(g, sd, c->scratch, c->scratch_bytes, c->compute, &fused));
     if (fused) fused_pack_stamp(c, sent, send_dir, sd);
     else if (c->fused_stamp.src == sent) fused_stamp_drop(c);   // (rewritten without its rows in the buffer: K == 0)
@@ -707,6 +725,23 @@ int dory_gemm_bf16_split(dory_ctx *c, int on) {
 int dory_gemm_bf16_split_stats(dory_ctx *c, uint64_t *split_launches) {
     CHECK_CTX(c);
     if (split_launches) *split_launches = c->gemm_bf16_split_launches;
+    return DORY_OK;
+}
+
+// ---- dory_gemm_bf16_send: K2b's and K2c's send epilogues for the products that feed a halo exchange (gemm_bf16_tile.hpp; gemm() above routes) ----
+int dory_gemm_bf16_send(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gemm_bf16_send: value %d is neither 0 nor 1", on);
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gemm_bf16_send: not while an epoch graph is being recorded");
+    if ((on == 1) != c->gemm_bf16_send) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->gemm_bf16_send = on == 1;
+    return DORY_OK;
+}
+
+int dory_gemm_bf16_send_stats(dory_ctx *c, uint64_t *send_launches, uint64_t *plain_while_on) {
+    CHECK_CTX(c);
+    if (send_launches) *send_launches = c->gemm_bf16_send_launches;
+    if (plain_while_on) *plain_while_on = c->gemm_bf16_send_plain;
     return DORY_OK;
 }
 

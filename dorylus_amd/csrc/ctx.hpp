@@ -343,6 +343,10 @@ struct dory_ctx {
     // dory_gemm_bf16_split: the switch (inert at mode 0); those of gemm_bf16_launches that ran the two-piece kernel (gemm_bf16_split.hip)
     bool gemm_bf16_split = false;
     uint64_t gemm_bf16_split_launches = 0;
+    // dory_gemm_bf16_send: the switch (inert at mode 0 and without dory_halo_fused_pack); the products whose bf16 kernel also wrote the send
+    // rows, and those with a send target that ran the plain bf16 kernel because the send rule (gemm_send_applies) refused
+    bool gemm_bf16_send = false;
+    uint64_t gemm_bf16_send_launches = 0, gemm_bf16_send_plain = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -595,6 +599,15 @@ hipError_t launch_gemm_bf16(const GemmArgs &g, float *scratch, size_t scratch_by
 hipError_t launch_gemm_bf16_split(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken);
 uint32_t gemm_pick_splits(uint32_t M, uint32_t N, uint32_t K, int bm, int bn);
 hipError_t launch_splitk_reduce(const GemmArgs &g, const float *partial, uint32_t S, hipStream_t s);
+// The send forms of K2b and K2c (dory_gemm_bf16_send): gemm_send_applies is the one rule by which K2, K2b and K2c decide whether an
+// epilogue writes a product's rows into sd.buf.  *taken as above; *fused = true: the rows are in sd.buf; taken and not fused: the plain
+// bf16 kernel ran.  A split launch sends from launch_splitk_reduce_send (K2's splitk_reduce_send*_kernel).
+bool gemm_send_applies(const GemmArgs &g, const GemmSend &sd);
+hipError_t launch_gemm_bf16_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
+                                 bool *fused);
+hipError_t launch_gemm_bf16_split_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
+                                       bool *fused);
+hipError_t launch_splitk_reduce_send(const GemmArgs &g, const GemmSend &sd, const float *partial, uint32_t S, hipStream_t s);
 
 // tanh of the transform's epilogue (K2), of the stand-alone activation and of K3's backward -- one function for all three, so
 // that h and the 1 - tanh^2 of the backward pass are the same number.  libm's tanhf is ~40 vector instructions (40 M of the

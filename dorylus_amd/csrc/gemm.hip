@@ -489,12 +489,19 @@ static hipError_t launch_bn(const GemmArgs &g, float *scratch, size_t scratch_by
 
 // with sd: the product's rows also go into the send buffer (*fused = true), where a send form exists -- NN and NT with rows and a
 // K to sum over; everything else (TN, the memset of K == 0, M == 0) runs as without and leaves *fused false
+// The send rule of K2, K2b and K2c: does a send form write this product's rows?  NN and NT with rows and a K to sum over, the wire row
+// inside the tensor's row, the tanh rows only of a product that makes them.
+bool gemm_send_applies(const GemmArgs &g, const GemmSend &sd) {
+    if (g.M == 0 || g.N == 0) return false;
+    if (g.ta || g.K == 0 || sd.cols != g.N || sd.w > g.ldc || sd.w > pad_ld(g.N) || (sd.which && g.epilogue != EPI_TANH)) return false;
+    // bf16 rows: whole quads of elements inside the tensor's row (a one-column tensor, ld == 1, has none), columns paired across lanes
+    return !(sd.bf16 && ((sd.w & 3u) || (g.ldc & 1u) || (reinterpret_cast<uintptr_t>(sd.buf) & 7u)));
+}
+
 static hipError_t launch_gemm_any(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd, bool *fused) {
     if (fused) *fused = false;
     if (g.M == 0 || g.N == 0) return hipSuccess;
-    if (sd && (g.ta || g.K == 0 || sd->cols != g.N || sd->w > g.ldc || sd->w > pad_ld(g.N) || (sd->which && g.epilogue != EPI_TANH))) sd = nullptr;
-    // bf16 rows: whole quads of elements inside the tensor's row (a one-column tensor, ld == 1, has none), columns paired across lanes
-    if (sd && sd->bf16 && ((sd->w & 3u) || (g.ldc & 1u) || (reinterpret_cast<uintptr_t>(sd->buf) & 7u))) sd = nullptr;
+    if (sd && !gemm_send_applies(g, *sd)) sd = nullptr;
     // the DMA moves 16-byte pieces: rows must start on 16-byte boundaries (every tensor of the table does: ld is padded to 32 floats)
     if ((g.lda & 3u) || (g.ldb & 3u) || (reinterpret_cast<uintptr_t>(g.A) & 15u) || (reinterpret_cast<uintptr_t>(g.B) & 15u))
         return hipErrorInvalidValue;
@@ -517,6 +524,16 @@ hipError_t launch_splitk_reduce(const GemmArgs &g, const float *partial, uint32_
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, g.C, partial, g.M, g.N, g.ldc, S,
                        g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2);
+    return hipGetLastError();
+}
+// ... and the second-stage sum that also sends (the send forms of K2b and K2c, split launches): the same sums in the same order, the rows
+// in sd's wire format -- the kernels launch_bn runs after a split send launch, under its conditions (gemm_send_applies)
+hipError_t launch_splitk_reduce_send(const GemmArgs &g, const GemmSend &sd, const float *partial, uint32_t S, hipStream_t s) {
+    const size_t n = (size_t)g.M * g.ldc;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(sd.bf16 ? splitk_reduce_send16_kernel : splitk_reduce_send_kernel, dim3(blocks), dim3(256), 0, s, g.C, partial, g.M, g.N, g.ldc,
+                       S, g.epilogue == EPI_TANH ? g.C2 : (float *)nullptr, g.ldc2, sd);
     return hipGetLastError();
 }
 

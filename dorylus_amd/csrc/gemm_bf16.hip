@@ -28,13 +28,18 @@
 //   128 x 64   NN 92, NT 92, TN 84 vector registers (64 accumulator registers among them)
 //   128 x 128  TN 124 under amdgpu_waves_per_eu(4, 4), the occupancy of K2's 128 x 128 form; NN and NT 140 without that bound (three
 //              waves per SIMD): under it they spill 3-8 registers -- 64 accumulators, 32 of raw rows in flight, 16 of fragments
-// The image, the loader (RegTile) and the launch plan live in gemm_bf16_tile.hpp, which K2c (gemm_bf16_split.hip) shares.
+// Send forms (dory_gemm_bf16_send; NN and NT only): the same main loop, then the send epilogue of gemm_bf16_tile.hpp, which keeps the
+// accumulators alive through a second pass over the rows -- no scratch either (tests/test_gemm_bf16_send_host.py):
+//   128 x 64   fp32 wire NN 92, NT 92; bf16 wire NN 92, NT 92
+//   128 x 128  fp32 wire NN 156, NT 156; bf16 wire NN 160, NT 160 -- three waves per SIMD, as the plain NN and NT forms at 140
+// The image, the loader (RegTile), the send epilogue and the launch plan live in gemm_bf16_tile.hpp, which K2c (gemm_bf16_split.hip) shares.
 #include "gemm_bf16_tile.hpp"
 
 namespace dory {
 
-template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
-__device__ __forceinline__ void gemm_bf16_body(const GemmArgs &g, uint32_t klen, float *partial, char *smem) {
+// SEND (dory_gemm_bf16_send): the same main loop, then the send epilogue of gemm_bf16_tile.hpp instead of the store loop; S16: bf16 rows
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK, bool SEND = false, bool S16 = false>
+__device__ __forceinline__ void gemm_bf16_body(const GemmArgs &g, uint32_t klen, float *partial, char *smem, const GemmSend &sd = GemmSend{}) {
     static_assert(WM * WN == 4 && WN * TN * 32 == BN, "tile shape");
     static_assert(BK == 32 || BK == 64, "image geometry is written for 32- and 64-deep k-tiles");
     constexpr int BM = WM * TM * 32;
@@ -98,6 +103,10 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs &g, uint32_t klen,
 
     const bool split = gridDim.z > 1;
     float *C = split ? partial + (size_t)blockIdx.z * g.M * g.ldc : g.C;
+    if constexpr (SEND) {
+        bf16_send_epilogue<TM, TN, S16>(g, sd, acc, C, split, i0 + wm * TM * 32, j0 + wn * TN * 32, fr, fk);
+        return;
+    }
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
@@ -129,8 +138,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     gemm_bf16_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK>(g, klen, partial, smem);
 }
 
+// the send forms (dory_gemm_bf16_send): kernels of their own -- the send descriptor is their extra argument -- so that the ones above
+// keep their names and code objects.  NN and NT only; no occupancy bound at either width (as the plain NN and NT forms)
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) void gemm_bf16_send_kernel(GemmArgs g, uint32_t klen, float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) char smem[2 * (WM * TM * 32 + BN) * BK * 2];
+    gemm_bf16_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, false>(g, klen, partial, smem, sd);
+}
+// ... and with the rows as bf16 (dory_halo_fused_pack_bf16)
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) void gemm_bf16_send16_kernel(GemmArgs g, uint32_t klen, float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) char smem[2 * (WM * TM * 32 + BN) * BK * 2];
+    gemm_bf16_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, true>(g, klen, partial, smem, sd);
+}
+
+// sd: the send form (the caller has asked gemm_send_applies: NN or NT), a split launch's rows leave from the reduce kernel
 template <int BN, int WM, int WN, int TM, int TN, int BK>
-static hipError_t launch_bf16_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s) {
+static hipError_t launch_bf16_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd = nullptr) {
     constexpr int BM = WM * TM * 32;
     uint32_t klen;
     const dim3 grid = gemm_bf16_grid(g, BM, BN, BK, scratch_bytes, &klen);
@@ -143,14 +167,21 @@ static hipError_t launch_bf16_bn(const GemmArgs &g, float *scratch, size_t scrat
         else                                                                                                                   \
             hipLaunchKernelGGL((gemm_bf16_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch);      \
     } while (0)
-    if (!g.ta && !g.tb) GEMM_BF16_LAUNCH(false, true);
+#define GEMM_BF16_LAUNCH_SEND(KERNEL, BKM) hipLaunchKernelGGL((KERNEL<BN, WM, WN, TM, TN, false, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd)
+    if (sd && g.ta) return hipErrorInvalidValue;
+    else if (sd && sd->bf16 && !g.tb) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send16_kernel, true);
+    else if (sd && sd->bf16) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send16_kernel, false);
+    else if (sd && !g.tb) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send_kernel, true);
+    else if (sd) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send_kernel, false);
+    else if (!g.ta && !g.tb) GEMM_BF16_LAUNCH(false, true);
     else if (!g.ta && g.tb) GEMM_BF16_LAUNCH(false, false);
     else if (g.ta && !g.tb) GEMM_BF16_LAUNCH(true, true);
     else return hipErrorInvalidValue;
 #undef GEMM_BF16_LAUNCH
+#undef GEMM_BF16_LAUNCH_SEND
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || S == 1) return e;
-    return launch_splitk_reduce(g, scratch, S, s);
+    return sd ? launch_splitk_reduce_send(g, *sd, scratch, S, s) : launch_splitk_reduce(g, scratch, S, s);
 }
 
 // *taken = false and nothing launched where K2's launcher does something else than run a kernel, or refuses: an empty product
@@ -160,6 +191,19 @@ hipError_t launch_gemm_bf16(const GemmArgs &g, float *scratch, size_t scratch_by
     if (!*taken) return hipSuccess;
     if (g.N > 64) return launch_bf16_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
     return launch_bf16_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
+}
+
+// dory_gemm_bf16_send: *taken as above; *fused = the rows are in sd.buf (gemm_send_applies, K2's own rule); taken and not fused: the
+// plain kernel ran and the exchange packs
+hipError_t launch_gemm_bf16_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
+                                 bool *fused) {
+    *fused = false;
+    *taken = gemm_bf16_takes(g);
+    if (!*taken) return hipSuccess;
+    *fused = gemm_send_applies(g, sd);
+    const GemmSend *p = *fused ? &sd : nullptr;
+    if (g.N > 64) return launch_bf16_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
+    return launch_bf16_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
 }
 
 }  // namespace dory

@@ -25,6 +25,10 @@
 // for waves the LDS cannot hold:
 //   128 x 64   NN 100, NT 98, TN 93 vector registers under amdgpu_waves_per_eu(3, 3) (32 accumulator registers among them)
 //   128 x 128  NN 144, NT 142, TN 134 under amdgpu_waves_per_eu(2, 2) (64 accumulators, 32 of raw rows in flight, 32 of fragments)
+// Send forms (dory_gemm_bf16_send; NN and NT only): the same main loop and occupancy bounds, then the send epilogue of
+// gemm_bf16_tile.hpp -- no scratch either (tests/test_gemm_bf16_send_host.py):
+//   128 x 64   fp32 wire NN 100, NT 98; bf16 wire NN 101, NT 99
+//   128 x 128  fp32 wire NN 144, NT 142; bf16 wire NN 146, NT 144
 #include "gemm_bf16_tile.hpp"
 
 namespace dory {
@@ -45,15 +49,18 @@ __device__ __forceinline__ void split_store(Tile &t, char *hi_img, uint32_t lo_o
     });
 }
 
-template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN == 128 ? 2 : 3, BN == 128 ? 2 : 3)))
-void gemm_bf16x3_kernel(GemmArgs g, uint32_t klen, float *partial) {
+// bytes of LDS a workgroup declares: two stages of [A hi][A lo][B hi][B lo]
+template <int BM, int BN, int BK>
+constexpr int bf16x3_lds() { return 2 * 2 * (BM + BN) * BK * 2; }
+
+// SEND (dory_gemm_bf16_send): the same main loop, then the send epilogue of gemm_bf16_tile.hpp instead of the store loop; S16: bf16 rows
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK, bool SEND = false, bool S16 = false>
+__device__ __forceinline__ void gemm_bf16x3_body(const GemmArgs &g, uint32_t klen, float *partial, char *smem, const GemmSend &sd = GemmSend{}) {
     static_assert(WM * WN == 4 && WN * TN * 32 == BN, "tile shape");
     static_assert(BK == 32 || BK == 64, "image geometry is written for 32- and 64-deep k-tiles");
     constexpr int BM = WM * TM * 32;
     constexpr int IMG_A = BM * BK * 2, IMG_B = BN * BK * 2, STAGE = 2 * (IMG_A + IMG_B);   // bytes
-    static_assert(2 * STAGE <= 64 * 1024, "two stages in the 64 KB a workgroup can declare");
-    __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
+    static_assert(2 * STAGE == bf16x3_lds<BM, BN, BK>() && 2 * STAGE <= 64 * 1024, "two stages in the 64 KB a workgroup can declare");
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -131,6 +138,10 @@ void gemm_bf16x3_kernel(GemmArgs g, uint32_t klen, float *partial) {
 
     const bool split = gridDim.z > 1;
     float *C = split ? partial + (size_t)blockIdx.z * g.M * g.ldc : g.C;
+    if constexpr (SEND) {
+        bf16_send_epilogue<TM, TN, S16>(g, sd, acc, C, split, i0 + wm * TM * 32, j0 + wn * TN * 32, fr, fk);
+        return;
+    }
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
@@ -148,18 +159,48 @@ void gemm_bf16x3_kernel(GemmArgs g, uint32_t klen, float *partial) {
         }
 }
 
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN == 128 ? 2 : 3, BN == 128 ? 2 : 3)))
+void gemm_bf16x3_kernel(GemmArgs g, uint32_t klen, float *partial) {
+    __shared__ __attribute__((aligned(1024))) char smem[bf16x3_lds<WM * TM * 32, BN, BK>()];
+    gemm_bf16x3_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK>(g, klen, partial, smem);
+}
+// the send forms (dory_gemm_bf16_send): kernels of their own -- the send descriptor is their extra argument -- so that the one above
+// keeps its name and code objects; the same occupancy bound, which the LDS sets.  NN and NT only
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN == 128 ? 2 : 3, BN == 128 ? 2 : 3)))
+void gemm_bf16x3_send_kernel(GemmArgs g, uint32_t klen, float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) char smem[bf16x3_lds<WM * TM * 32, BN, BK>()];
+    gemm_bf16x3_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, false>(g, klen, partial, smem, sd);
+}
+// ... and with the rows as bf16 (dory_halo_fused_pack_bf16)
+template <int BN, int WM, int WN, int TM, int TN, bool A_KMAJOR, bool B_KMAJOR, int BK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN == 128 ? 2 : 3, BN == 128 ? 2 : 3)))
+void gemm_bf16x3_send16_kernel(GemmArgs g, uint32_t klen, float *partial, GemmSend sd) {
+    __shared__ __attribute__((aligned(1024))) char smem[bf16x3_lds<WM * TM * 32, BN, BK>()];
+    gemm_bf16x3_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, true>(g, klen, partial, smem, sd);
+}
+
+// sd: the send form (the caller has asked gemm_send_applies: NN or NT), a split launch's rows leave from the reduce kernel
 template <int BN, int WM, int WN, int TM, int TN, int BK>
-static hipError_t launch_bf16x3_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s) {
+static hipError_t launch_bf16x3_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd = nullptr) {
     uint32_t klen;
     const dim3 grid = gemm_bf16_grid(g, WM * TM * 32, BN, BK, scratch_bytes, &klen);
     const dim3 block(256);
-    if (!g.ta && !g.tb) hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, false, true, BK>), grid, block, 0, s, g, klen, scratch);
+#define GEMM_BF16X3_LAUNCH_SEND(KERNEL, BKM) hipLaunchKernelGGL((KERNEL<BN, WM, WN, TM, TN, false, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd)
+    if (sd && g.ta) return hipErrorInvalidValue;
+    else if (sd && sd->bf16 && !g.tb) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send16_kernel, true);
+    else if (sd && sd->bf16) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send16_kernel, false);
+    else if (sd && !g.tb) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send_kernel, true);
+    else if (sd) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send_kernel, false);
+    else if (!g.ta && !g.tb) hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, false, true, BK>), grid, block, 0, s, g, klen, scratch);
     else if (!g.ta && g.tb) hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, false, false, BK>), grid, block, 0, s, g, klen, scratch);
     else if (g.ta && !g.tb) hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, true, true, BK>), grid, block, 0, s, g, klen, scratch);
     else return hipErrorInvalidValue;
+#undef GEMM_BF16X3_LAUNCH_SEND
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || grid.z == 1) return e;
-    return launch_splitk_reduce(g, scratch, grid.z, s);
+    return sd ? launch_splitk_reduce_send(g, *sd, scratch, grid.z, s) : launch_splitk_reduce(g, scratch, grid.z, s);
 }
 
 // *taken as launch_gemm_bf16 sets it
@@ -168,6 +209,18 @@ hipError_t launch_gemm_bf16_split(const GemmArgs &g, float *scratch, size_t scra
     if (!*taken) return hipSuccess;
     if (g.N > 64) return launch_bf16x3_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
     return launch_bf16x3_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
+}
+
+// dory_gemm_bf16_send under K2c: *taken and *fused as launch_gemm_bf16_send sets them
+hipError_t launch_gemm_bf16_split_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
+                                       bool *fused) {
+    *fused = false;
+    *taken = gemm_bf16_takes(g);
+    if (!*taken) return hipSuccess;
+    *fused = gemm_send_applies(g, sd);
+    const GemmSend *p = *fused ? &sd : nullptr;
+    if (g.N > 64) return launch_bf16x3_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
+    return launch_bf16x3_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
 }
 
 }  // namespace dory

@@ -1,5 +1,6 @@
 // gemm_bf16_tile.hpp -- what K2b (gemm_bf16.hip) and K2c (gemm_bf16_split.hip) share: the swizzled [i][BK k] bf16 LDS image, the
-// register-staged loader of one operand's fp32 tile, and the launch plan (split count and k-length) of a 128 x BN product.
+// register-staged loader of one operand's fp32 tile, the send epilogue of their send forms, and the launch plan (split count and k-length)
+// of a 128 x BN product.
 #pragma once
 #include "ctx.hpp"
 
@@ -126,6 +127,71 @@ struct RegTile {
         pieces(krem, [&](uint32_t r, uint32_t q, const float (&f)[8]) { *reinterpret_cast<bf16x8 *>(img + img_off<BK>(r, q)) = round8(f); });
     }
 };
+
+// The SEND epilogue of K2b and K2c (dory_gemm_bf16_send; the send kernels of both files end in this one copy): K2's, whose
+// accumulator layout v_mfma_f32_32x32x16_bf16 shares -- lane (fr, fk) holds column fr of a 32 x 32 tile and, in register r, its row
+// (r & 3) + 8 (r >> 2) + 4 fk.  row0 / col0: the first row and column of this wave's TM x TN tiles.
+// Store loop: C (a split launch: this split's partial) and, with EPI_TANH, C2, exactly as the plain kernels store them; the spent
+// accumulator keeps what travels -- v, tanh(v) when sd.which, zero for rows >= M and columns >= N (the padding of a padded wire row).
+// Second pass (not in a split launch: the reduce kernel sends): row by row; the 32 lanes that hold a row load its slot range once and
+// each slot once for all TN column tiles, and store 128 contiguous bytes per slot and tile (the slot loop inside the store loop cost
+// K2 more than the pack kernel: profiles/r17_halo_fused_pack.txt).
+// S16 (dory_halo_fused_pack_bf16): the rows go out as bf16, byte for byte what gather_rows_bf16_kernel leaves -- at the head of a
+// row's turn, where the whole wave still walks together, a lane takes its right neighbour's column by DPP and leaves the cvt_pk dword
+// of the pair in the accumulator; the even lanes store it (16 lanes x 4 bytes = the 64 contiguous bytes of a row and tile).  sd.w is
+// even, so col + 1 < sd.w for an even col < sd.w.
+template <int TM, int TN, bool S16>
+__device__ __forceinline__ void bf16_send_epilogue(const GemmArgs &g, const GemmSend &sd, f32x16 (&acc)[TM][TN], float *C, bool split,
+                                                   uint32_t row0, uint32_t col0, int fr, int fk) {
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b) {
+            const uint32_t col = col0 + b * 32 + fr;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t row = row0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+                float sv = 0.f;
+                if (row < g.M && col < g.N) {
+                    const float v = acc[a][b][r];
+                    C[(size_t)row * g.ldc + col] = v;
+                    sv = v;
+                    if (!split && g.epilogue == EPI_TANH) {
+                        const float t = dory_tanh(v);
+                        g.C2[(size_t)row * g.ldc2 + col] = t;
+                        if (sd.which) sv = t;
+                    }
+                }
+                acc[a][b][r] = sv;
+            }
+        }
+    if (split) return;
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const uint32_t row = row0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+            if constexpr (S16) {
+#pragma unroll
+                for (int b = 0; b < TN; ++b) acc[a][b][r] = __uint_as_float(pack_bf16x2(acc[a][b][r], lane_right(acc[a][b][r])));
+            }
+            if (row >= g.M) continue;
+            const uint32_t s1 = sd.row_ptr[row + 1];
+            for (uint32_t s = sd.row_ptr[row]; s < s1; ++s) {
+                const size_t at = (size_t)sd.row_slots[s] * sd.w;   // (64-bit: a send buffer may exceed 4 GB)
+#pragma unroll
+                for (int b = 0; b < TN; ++b) {
+                    const uint32_t col = col0 + b * 32 + fr;
+                    if constexpr (S16) {
+                        if (!(fr & 1) && col < sd.w)
+                            *reinterpret_cast<uint32_t *>(reinterpret_cast<uint16_t *>(sd.buf) + at + col) = __float_as_uint(acc[a][b][r]);
+                    } else {
+                        if (col < sd.w) sd.buf[at + col] = acc[a][b][r];
+                    }
+                }
+            }
+        }
+}
 
 // The grid of a BM x BN product with BK-deep k-tiles: gemm_pick_splits's count within the scratch, then a split's k-length rounded to
 // the k-tile (K2 rounds to 16) -- the rounding can only lower the split count below the one pick_splits chose, so the scratch

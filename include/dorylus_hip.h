@@ -826,8 +826,8 @@ int dory_k1_bf16_wide_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t
  * bf16 (small integers) the exact product, bit for bit.  The sum order per element is fixed whatever the grid: the same input gives
  * the same bits.  Nothing else in the context changes; mode 0 after any other mode gives the bits of a context that never called this.
  * WHERE K2 STILL RUNS with a mode on: a product that wants a SEND form (dory_halo_fused_pack: the epilogue also writes the rows into the
- * send buffer) -- there is no bf16 send form, so for those products the two features cancel: the fused pack wins and the product is fp32
- * (counted: fp32_while_on).  K == 0, M == 0 and operands off K2's 16-byte alignment rule behave as with mode 0.
+ * send buffer) -- unless dory_gemm_bf16_send (below) is on, for those products the two features cancel: the fused pack wins and the
+ * product is fp32 (counted: fp32_while_on).  K == 0, M == 0 and operands off K2's 16-byte alignment rule behave as with mode 0.
  * DORY_ERR_ARG: a mode other than 0, 1, 2; a call while an epoch graph is being recorded.  A change drops a recorded epoch graph.
  * Counters, in this order: products that ran K2b since dory_create (eager calls and recordings, not replays); products of a form the
  * mode covers that ran K2's fp32 kernel.  Any pointer may be NULL.
@@ -853,13 +853,39 @@ int dory_gemm_bf16_stats(dory_ctx *ctx, uint64_t *bf16_launches, uint64_t *fp32_
  * The sum order per element is fixed whatever the grid: the same input gives the same bits.  Mode 0, or the switch off, leaves every
  * launch as it is without this entry point.
  * WHERE K2 STILL RUNS: exactly where it does under dory_gemm_bf16 -- a product that wants a SEND form (dory_halo_fused_pack) keeps K2's
- * fp32 kernel (counted: fp32_while_on of dory_gemm_bf16_stats); K == 0, M == 0, N == 0 and operands off K2's 16-byte rule as with mode 0.
+ * fp32 kernel unless dory_gemm_bf16_send (below) is on (counted: fp32_while_on of dory_gemm_bf16_stats); K == 0, M == 0, N == 0 and operands off K2's 16-byte rule as with mode 0.
  * DORY_ERR_ARG: a value other than 0 or 1; a call while an epoch graph is being recorded.  A change drops a recorded epoch graph.
  * Counter: products that ran K2c since dory_create (eager calls and recordings, not replays); each of them also counts in bf16_launches
  * of dory_gemm_bf16_stats, whose meaning does not change.  The pointer may be NULL.
  * MEASURED: see DESIGN.md section 3. */
 int dory_gemm_bf16_split(dory_ctx *ctx, int on);   /* 0 (default) = off */
 int dory_gemm_bf16_split_stats(dory_ctx *ctx, uint64_t *split_launches);
+
+/* ---- send epilogues for K2b and K2c: the bf16 matrix instruction under the fused halo pack (opt-in, default off) ----------------
+ * With dory_halo_fused_pack on, every NN / NT product that is the source of a halo exchange -- GCN h and grad, transform-first xw, the
+ * GAT prototype's z and grad, the 8-head GAT's z -- wants a kernel whose epilogue also writes the send rows, and only K2's fp32 kernels
+ * had one: on a partitioned run dory_gemm_bf16 mode 1 was left with nothing to do.  With this switch on, such a product that the mode
+ * covers runs a send form of K2b (gemm_bf16_send_kernel, gemm_bf16_send16_kernel) or, under dory_gemm_bf16_split, of K2c
+ * (gemm_bf16x3_send_kernel, gemm_bf16x3_send16_kernel): the plain kernel's main loop, then K2's send epilogue on the same accumulator
+ * layout (one copy for both, csrc/gemm_bf16_tile.hpp) -- fp32 wire rows, padded or exact-width, or bf16 rows under
+ * dory_halo_fused_pack_bf16.  A split-K launch sends from K2's splitk_reduce_send*_kernel.  TN never sends.
+ * on: 0 (default) or 1.  Legal before dory_configure and on every model; inert while dory_gemm_bf16's mode is 0 or dory_halo_fused_pack
+ * is off.
+ * CONTRACT: with the switch on, every tensor, weight, gradient and byte on the wire equals, bit for bit, the run with
+ * dory_halo_fused_pack off and the same dory_gemm_bf16 / dory_gemm_bf16_split settings; the exchange launches no pack kernel -- the
+ * statement dory_halo_fused_pack makes for K2.  With the switch 0 every launch and every counter is what it is without this entry point.
+ * WHERE THE ROWS ARE NOT WRITTEN: K2's own send rule decides (one host function for all three kernels): K == 0, a wire row wider than the
+ * tensor's row, the tanh rows of a product without tanh, a bf16 wire row off its alignment -- the plain K2b / K2c kernel runs and the
+ * exchange packs (counted: plain_while_on, and a fallback of dory_halo_fused_pack_stats).  A product K2b does not take (M, N or K == 0,
+ * operands off the 16-byte rule) goes to K2's send launcher as without the switch (counted: fp32_while_on -- except the empty product of
+ * an empty rank, M or N == 0, which launches nothing and is counted nowhere).
+ * DORY_ERR_ARG: a value other than 0 or 1; a call while an epoch graph is being recorded.  A change drops a recorded epoch graph.
+ * Counters, in this order: products whose K2b / K2c kernel also wrote the send rows since dory_create -- each also counts in
+ * bf16_launches (and split_launches under K2c), none in fp32_while_on; products with a send target that ran the plain bf16 kernel.
+ * Any pointer may be NULL.
+ * MEASURED: see DESIGN.md section 3. */
+int dory_gemm_bf16_send(dory_ctx *ctx, int on);   /* 0 (default) = off */
+int dory_gemm_bf16_send_stats(dory_ctx *ctx, uint64_t *send_launches, uint64_t *plain_while_on);
 
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
