@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value $(EXTRA)
 CSRC = dorylus_amd/csrc
-OBJS = $(CSRC)/abi_context.o $(CSRC)/abi_stages.o $(CSRC)/abi_comm.o $(CSRC)/spmm.o $(CSRC)/spmm_blocked.o $(CSRC)/gemm.o $(CSRC)/gemm_bf16.o $(CSRC)/gemm_bf16_split.o $(CSRC)/elementwise.o $(CSRC)/gat_mh.o $(CSRC)/gat_mh_blocked.o $(CSRC)/gat_mh_sweep.o $(CSRC)/gat_mh_rows.o
+OBJS = $(CSRC)/abi_context.o $(CSRC)/abi_stages.o $(CSRC)/abi_comm.o $(CSRC)/spmm.o $(CSRC)/spmm_blocked.o $(CSRC)/gemm.o $(CSRC)/gemm_bf16.o $(CSRC)/gemm_bf16_split.o $(CSRC)/gemm_bf16_resident.o $(CSRC)/elementwise.o $(CSRC)/gat_mh.o $(CSRC)/gat_mh_blocked.o $(CSRC)/gat_mh_sweep.o $(CSRC)/gat_mh_rows.o
 HOSTOBJS = $(patsubst %.cpp,%.o,$(filter-out %_main.cpp,$(wildcard dorylus_amd/host/*.cpp)))
 GRAPHSERVER = dorylus_amd/graphserver
 INPUTS = dorylus_amd/dory-inputs
@@ -15,7 +15,7 @@ $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/ctx.hpp $(CSRC)/spmm_common.hpp $(CSRC)/sweep
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # K2b's and K2c's conversions, K2c's x - hi and the address arithmetic stay on scalar-width fp32 instructions (no v_pk_*_f32 forms)
-$(CSRC)/gemm_bf16.o $(CSRC)/gemm_bf16_split.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+$(CSRC)/gemm_bf16.o $(CSRC)/gemm_bf16_split.o $(CSRC)/gemm_bf16_resident.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 dorylus_amd/host/%.o: dorylus_amd/host/%.cpp $(wildcard dorylus_amd/host/*.hpp) $(wildcard include/*.h) $(CSRC)/sweep_geometry.hpp $(CSRC)/options.hpp $(CSRC)/switches.hpp $(CSRC)/row_chunks.hpp $(CSRC)/gat_mh_shapes.hpp $(CSRC)/k1_shapes.hpp
 	$(HIPCC) -O3 -std=c++17 -fPIC -fopenmp -Wall -c $< -o $@

@@ -45,7 +45,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
     "dory_k1_bf16_wide", "dory_k1_bf16_wide_stats", "dory_k1_bf16_wide_form",
     "dory_gemm_bf16", "dory_gemm_bf16_stats", "dory_gemm_bf16_split", "dory_gemm_bf16_split_stats",
-    "dory_gemm_bf16_send", "dory_gemm_bf16_send_stats",
+    "dory_gemm_bf16_send", "dory_gemm_bf16_send_stats", "dory_gemm_bf16_resident", "dory_gemm_bf16_resident_stats",
 ]
 
 # host transport callbacks (include/dorylus_hip.h)
@@ -159,6 +159,8 @@ def load():
         "dory_gemm_bf16_split_stats": [vp, C.POINTER(u64)],
         "dory_gemm_bf16_send": [vp, i32],
         "dory_gemm_bf16_send_stats": [vp] + [C.POINTER(u64)] * 2,
+        "dory_gemm_bf16_resident": [vp, i32],
+        "dory_gemm_bf16_resident_stats": [vp] + [C.POINTER(u64)] * 3,
         "dory_halo_wire_ids": [vp, vp, vp, vp],
         "dory_scatter_msgs_layout": [vp, u32, i32, cp, u64, C.POINTER(ScatterMsg), u32, C.POINTER(u32), C.POINTER(u64)],
         "dory_scatter_msgs_pack": [vp, u32, i32, cp, u64, vp],
@@ -926,6 +928,17 @@ class Context:
         """dict: send_launches (products whose bf16 kernel also wrote the send rows since dory_create; each also counts in
         bf16_launches), plain_while_on (products with a send target that ran the plain bf16 kernel: the send rule refused)"""
         return self._stats(self.lib.dory_gemm_bf16_send_stats, 2, ("send_launches", "plain_while_on"))
+
+    def gemm_bf16_resident(self, on=1):
+        """the plain bf16 products of a layer-0 constant (x, fg@0, a kept ah@0; h@0 of the GAT models) read a resident bf16 copy of it,
+        made once and kept until the tensor may have changed (dory_gemm_bf16_resident; every model): the same bits as with 0 (default);
+        inert while gemm_bf16's mode does not cover the product"""
+        self._ck(self.lib.dory_gemm_bf16_resident(self.h, int(on)))
+
+    def gemm_bf16_resident_stats(self):
+        """dict: resident_launches (products that read a resident copy since dory_create; each also counts in bf16_launches),
+        conversions (copies made), plain_while_on (products of an eligible operand that ran without one)"""
+        return self._stats(self.lib.dory_gemm_bf16_resident_stats, 3, ("resident_launches", "conversions", "plain_while_on"))
 
     # -- optimiser ---------------------------------------------------------------------------
     def adam_config(self, lr):

@@ -481,7 +481,7 @@ int scatter_deliver(dory_ctx *c, const char *name, const void *const *msgs, cons
         P[i] = {ghost, dr, cnt, lay, m + DORY_WIRE_SCATTER_HDR_SIZE};
     }
     for (const Parsed &q : P) {   // what halo_tensors and dory_halo_exchange drop when these ghost rows change
-        if (q.ghost == find(c, 0, "fg")) c->ah0_valid = false;
+        if (q.ghost == find(c, 0, "fg")) c->layer0_changed();
         if (q.ghost == find(c, q.layer, "fg_z") && q.layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[q.layer] = 0;
         ghost_wrote_fp32(q.ghost);   // (dory_halo_bf16_ghosts: records are fp32; a round writes every ghost row)
     }
@@ -1420,7 +1420,7 @@ int dory_halo_exchange(dory_ctx *c, uint32_t layer, int dir) {
     int rc = halo_tensors(c, layer, dir, &src, &ghost);
     if (rc) return rc;
     // a forward exchange of layer 0 rewrites fg@0 (a peer may have uploaded a new x): a cached ah@0 no longer holds
-    if (layer == 0 && dir == DORY_FORWARD) c->ah0_valid = false;
+    if (layer == 0 && dir == DORY_FORWARD) c->layer0_changed();
     // consumers on the compute stream wait for the ghosts at once, or (halo_overlap) when the first of them needs
     // the ghost rows -- see wait_halo()
     return exchange_rows(c, dir, src, ghost, true);
@@ -1444,6 +1444,7 @@ int dory_halo_unpack(dory_ctx *c, uint32_t layer, int dir, const float *recv_buf
     Tensor *src, *ghost;
     int rc = halo_tensors(c, layer, dir, &src, &ghost);
     if (rc) return rc;
+    if (ghost == find(c, 0, "fg")) c->layer0_changed();   // (dory_gemm_bf16_resident: the copies go only when fg@0 is the tensor written -- not with bgg@0)
     if (!c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack: no plan");
     return split_rows(c, "halo_unpack", false, dir, src, ghost, const_cast<float *>(recv_buf), true);
 }
@@ -1463,6 +1464,7 @@ int dory_halo_unpack_tensor(dory_ctx *c, uint32_t layer, const char *name, int d
     if (layer == 0) c->ah0_valid = false;   // (a caller's transport writing fg@0)
     { int wrc = wait_halo(c); if (wrc) return wrc; }
     Tensor *ghost = name ? find(c, layer, name) : nullptr;
+    if (ghost && ghost == find(c, 0, "fg")) c->layer0_changed();   // (dory_gemm_bf16_resident: as dory_halo_unpack)
     if (!ghost || (dir != 0 && dir != 1) || !c->plan[dir].set) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: no tensor '%s'@%u or no plan", name ? name : "(null)", layer);
     if (ghost->rows != c->adj[dir == DORY_FORWARD ? ADJ_IN : ADJ_OUT].ghosts) return fail(c, DORY_ERR_ARG, "halo_unpack_tensor: '%s' is not a ghost tensor of that direction", name);
     if (!strcmp(name, "fg_z") && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;   // (as halo_tensors: the kept neighbour sum of the old ghost rows no longer holds)
@@ -1766,7 +1768,7 @@ int dory_scatter_msgs_unpack(dory_ctx *c, uint32_t layer, int dir, const char *n
     if (ghost->cols > scatter_msgs_max_cols()) return fail(c, DORY_ERR_ARG, "%s: rows of %u floats (scatter messages carry 1 .. %u)", who, ghost->cols, scatter_msgs_max_cols());
     if (count && (!dev_records || ((uintptr_t)dev_records & 15))) return fail(c, DORY_ERR_ARG, "%s: the records must be 16-byte aligned", who);
     const uint32_t tl = tensor_layer(c, ghost);
-    if (ghost == find(c, 0, "fg")) c->ah0_valid = false;
+    if (ghost == find(c, 0, "fg")) c->layer0_changed();
     if (ghost == find(c, tl, "fg_z") && tl < c->gat_nsum_valid.size()) c->gat_nsum_valid[tl] = 0;
     ghost_wrote_fp32(ghost);   // (dory_halo_bf16_ghosts: records are fp32; a round writes every ghost row)
     HIPCK(c, hipEventRecord(c->ev_a, c->compute));

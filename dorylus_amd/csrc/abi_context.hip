@@ -129,6 +129,73 @@ std::vector<uint32_t> median_source_order(const uint64_t *ptr, const uint32_t *i
     return o;
 }
 
+// ---- dory_gemm_bf16_resident: the resident bf16 copies K2r (gemm_bf16_resident.hip) reads ----
+// the caller has waited for whatever may still read them
+static void gemm_resident_free(dory_ctx *c) {
+    for (auto &r : c->gemm_res) {
+        if (r.buf) (void)hipFree(r.buf);
+        r = dory_ctx::GemmResident{};
+    }
+}
+// a layer-0 tensor gets the caller's values (upload, fill): the kept aggregate may be stale, and with it the copy of ah@0; of the
+// other copies only the written tensor's -- the backward's aTg@0 uploaded between two products leaves the copy of h@0 alone
+static void layer0_tensor_written(dory_ctx *c, const Tensor *t) {
+    c->ah0_valid = false;
+    const Tensor *ah = find(c, 0, "ah");
+    for (auto &r : c->gemm_res) if (r.src == t || r.src == ah) r.valid = false;
+}
+// is A one of the model's layer-0 constants -- x, fg@0 and ah@0 of GCN, h@0 of the GAT models?
+static bool gemm_resident_named(dory_ctx *c, const Tensor &A) {
+    if (!c->prealloc) return false;
+    if (c->gnn == DORY_GCN) return &A == find(c, 0, "x") || &A == find(c, 0, "fg") || &A == find(c, 0, "ah");
+    return &A == find(c, 0, "h");
+}
+// *R = the current resident copy of A for the plain bf16 product g (made now if need be), or null: the product runs what it runs
+// without the switch -- counted, for an operand eligible by name.  Nothing is allocated or converted while an epoch graph records
+// (a replay would read a copy that an upload between two replays cannot reach): recorded products run plain.
+static int gemm_resident_for(dory_ctx *c, const GemmArgs &g, const Tensor &A, bool sends, const uint16_t **R, uint32_t *ldr) {
+    *R = nullptr;
+    if (g.tb || !gemm_resident_named(c, A) || g.M == 0 || g.N == 0 || g.K == 0) return DORY_OK;
+    const bool kept = &A != find(c, 0, "ah") || (c->opt[OPT_GCN_CACHE_AH0] && c->ah0_valid);   // ah@0 is rewritten every epoch otherwise
+    // the copy holds the whole tensor: NN reads M rows of all its columns (the zeros past them are the k-tail), TN K rows of M columns
+    const bool whole = g.ta ? (g.K <= A.rows && g.M <= A.cols) : (g.M <= A.rows && g.K == A.cols);
+    if (c->gemm_bf16_split || sends || !kept || !whole || c->capturing || !gemm_bf16_resident_takes(g)) {
+        ++c->gemm_res_plain;
+        return DORY_OK;
+    }
+    dory_ctx::GemmResident *slot = nullptr;
+    for (auto &r : c->gemm_res) if (r.src == &A) slot = &r;
+    if (!slot) for (auto &r : c->gemm_res) if (!slot && !r.valid) slot = &r;
+    // both slots hold other tensors' current copies: the first goes.  (Three eligible operands taking turns would convert at every
+    // product; no model has them -- x and fg@0 belong to the transform-first order, ah@0 to the other, and the option that chooses
+    // between them drops every copy when it changes)
+    if (!slot) slot = &c->gemm_res[0];
+    const uint32_t ld = gemm_resident_ld(A.cols);
+    const size_t bytes = (size_t)A.rows * ld * sizeof(uint16_t);
+    if (slot->src != &A || slot->ldr != ld || slot->bytes < bytes || !slot->valid) {
+        slot->valid = false;
+        slot->src = &A;
+        slot->ldr = ld;
+        if (slot->bytes < bytes) {
+            if (slot->buf) {   // (earlier products on the compute stream may still read the smaller buffer)
+                HIPCK(c, hipStreamSynchronize(c->compute));
+                (void)hipFree(slot->buf);
+                slot->buf = nullptr;
+                slot->bytes = 0;
+            }
+            HIPCK(c, hipMalloc((void **)&slot->buf, bytes));
+            slot->bytes = bytes;
+        }
+        Timed t(c, "bf16_convert", c->compute);
+        HIPCK(c, launch_gemm_resident_rows(A.d, A.ld, A.rows, A.cols, slot->buf, ld, c->compute));
+        slot->valid = true;
+        ++c->gemm_res_conversions;
+    }
+    *R = slot->buf;
+    *ldr = ld;
+    return DORY_OK;
+}
+
 int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const Tensor &A,
          const Tensor &B, Tensor &C, Tensor *C2) {
     GemmArgs g{};
@@ -152,12 +219,22 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
     if (sent && (rc = wait_halo(c))) return rc;
     ghost_wrote_fp32(&C);   // (dory_halo_bf16_ghosts: a product written into a ghost tensor -- fgxw@0 -- is fp32 rows)
     ghost_wrote_fp32(C2);
-    Timed t(c, "gemm", c->compute);
     // dory_gemm_bf16: does the mode cover this form (1: NN and NT, 2: TN too)?
     const bool bf16 = c->gemm_bf16 >= 2 || (c->gemm_bf16 == 1 && !ta);
+    // dory_gemm_bf16_resident: a plain K2b product of a layer-0 constant reads the operand's resident bf16 copy (K2r)
+    const uint16_t *res = nullptr;
+    uint32_t ldr = 0;
+    if (bf16 && c->gemm_bf16_resident && (rc = gemm_resident_for(c, g, A, sent != nullptr, &res, &ldr))) return rc;
+    Timed t(c, "gemm", c->compute);
     if (!sent) {
         fused_note_write(c, &C);
         fused_note_write(c, C2);
+        if (res) {
+            HIPCK(c, launch_gemm_bf16_resident(g, res, ldr, c->scratch, c->scratch_bytes, c->compute));
+            ++c->gemm_bf16_launches;
+            ++c->gemm_res_launches;
+            return DORY_OK;
+        }
         bool taken = false;
         if (bf16) HIPCK(c, (c->gemm_bf16_split ? launch_gemm_bf16_split : launch_gemm_bf16)(g, c->scratch, c->scratch_bytes, c->compute, &taken));
         if (taken) {
@@ -450,6 +527,7 @@ int dory_destroy(dory_ctx *c) {
     }
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->bf16_rows) (void)hipFree(c->bf16_rows);
+    gemm_resident_free(c);
     if (c->gatmh_carry_state) (void)hipFree(c->gatmh_carry_state);
     if (c->partial) (void)hipFree(c->partial);
     if (c->epoch_exec) (void)hipGraphExecDestroy(c->epoch_exec);
@@ -745,6 +823,28 @@ int dory_gemm_bf16_send_stats(dory_ctx *c, uint64_t *send_launches, uint64_t *pl
     return DORY_OK;
 }
 
+// ---- dory_gemm_bf16_resident: K2r on the resident bf16 copies of the layer-0 A operands (gemm_bf16_resident.hip; gemm() above routes) ----
+int dory_gemm_bf16_resident(dory_ctx *c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) return fail(c, DORY_ERR_ARG, "gemm_bf16_resident: value %d is neither 0 nor 1", on);
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "gemm_bf16_resident: not while an epoch graph is being recorded");
+    if ((on == 1) != c->gemm_bf16_resident) epoch_graph_drop_locked(c);   // (a recorded epoch holds the other value's launches)
+    c->gemm_bf16_resident = on == 1;
+    if (!on && (c->gemm_res[0].buf || c->gemm_res[1].buf)) {   // the copies go once the products that read them have run
+        HIPCK(c, hipStreamSynchronize(c->compute));
+        gemm_resident_free(c);
+    }
+    return DORY_OK;
+}
+
+int dory_gemm_bf16_resident_stats(dory_ctx *c, uint64_t *resident_launches, uint64_t *conversions, uint64_t *plain_while_on) {
+    CHECK_CTX(c);
+    if (resident_launches) *resident_launches = c->gemm_res_launches;
+    if (conversions) *conversions = c->gemm_res_conversions;
+    if (plain_while_on) *plain_while_on = c->gemm_res_plain;
+    return DORY_OK;
+}
+
 int dory_gatmh_heads(dory_ctx *c, const uint32_t *heads) {
     CHECK_CTX(c);
     if (!c->configured || c->gnn != DORY_GATMH || !heads) return fail(c, DORY_ERR_ARG, "gatmh_heads: configure with DORY_GATMH first");
@@ -759,7 +859,7 @@ int dory_graph_upload(dory_ctx *c, uint32_t N, uint32_t Gsrc, uint32_t Gdst, uin
                       uint64_t nnz_out, const uint64_t *row_ptrs, const uint32_t *column_idxs,
                       const float *csr_values, const float *vtx_norms) {
     CHECK_CTX(c);
-    c->ah0_valid = false;
+    c->layer0_changed();
     if (!column_ptrs || !row_ptrs || (N && !vtx_norms) || (nnz_in && (!row_idxs || !csc_values)) ||
         (nnz_out && (!column_idxs || !csr_values)))
         return fail(c, DORY_ERR_ARG, "dory_graph_upload: null array");
@@ -848,10 +948,11 @@ int dory_graph_upload(dory_ctx *c, uint32_t N, uint32_t Gsrc, uint32_t Gdst, uin
 
 int dory_preallocate(dory_ctx *c) {
     CHECK_CTX(c);
-    c->ah0_valid = false;
+    c->layer0_changed();
     if (!c->configured || !c->has_graph) return fail(c, DORY_ERR_ARG, "dory_preallocate: configure and graph_upload first");
     epoch_graph_drop_locked(c);   // a recorded epoch points at the tensors freed below
     HIPCK(c, hipDeviceSynchronize());
+    gemm_resident_free(c);   // (dory_gemm_bf16_resident: the copies shadow the tensors freed below)
     free_table(c->tensors); free_table(c->weights); free_table(c->wgrads); free_table(c->adam_m); free_table(c->adam_v);
     const uint32_t L = c->L, N = c->N;
     Adjacency &In = c->adj[ADJ_IN], &Out = c->adj[ADJ_OUT];
@@ -1067,6 +1168,7 @@ int dory_tensor_info(dory_ctx *c, uint32_t layer, const char *name, uint64_t *ro
         *device_ptr = t->d;
         t->raw_handed = true;
         fused_note_write(c, t);
+        for (auto &r : c->gemm_res) if (r.src == t) r.valid = false;   // (dory_gemm_bf16_resident: the copy is made again at the next product)
     }
     return DORY_OK;
 }
@@ -1158,7 +1260,7 @@ int dory_tensor_upload(dory_ctx *c, uint32_t layer, const char *name, const floa
     { int wrc = wait_halo(c); if (wrc) return wrc; }
     Tensor *t = name ? find(c, layer, name) : nullptr;
     if (!t || !host) return fail(c, DORY_ERR_ARG, "tensor_upload: no tensor '%s' at layer %u", name ? name : "(null)", layer);
-    if (layer == 0) c->ah0_valid = false;                                    // x / fg@0 / ah@0 may have changed
+    if (layer == 0) layer0_tensor_written(c, t);                             // x / fg@0 / ah@0 may have changed
     if (!strcmp(name, "A")) for (auto &f : c->gat_arow_valid) f = 0;          // caller-supplied edge weights: general path
     if (!strcmp(name, "dA") && layer < c->gat_drow_valid.size()) c->gat_drow_valid[layer] = 0;
     if ((!strcmp(name, "z") || !strcmp(name, "fg_z")) && layer < c->gat_nsum_valid.size()) c->gat_nsum_valid[layer] = 0;
@@ -1188,7 +1290,7 @@ int dory_tensor_fill_uniform(dory_ctx *c, uint32_t layer, const char *name, uint
     { int wrc = wait_halo(c); if (wrc) return wrc; }
     Tensor *t = name ? find(c, layer, name) : nullptr;
     if (!t) return fail(c, DORY_ERR_ARG, "tensor_fill: no tensor '%s' at layer %u", name ? name : "(null)", layer);
-    if (layer == 0) c->ah0_valid = false;
+    if (layer == 0) layer0_tensor_written(c, t);
     // (as in dory_tensor_upload: the caller's values replace what the stages kept of the tensor)
     if (!strcmp(name, "A")) for (auto &f : c->gat_arow_valid) f = 0;
     if (!strcmp(name, "dA") && layer < c->gat_drow_valid.size()) c->gat_drow_valid[layer] = 0;
@@ -1424,7 +1526,7 @@ int dory_set_option(dory_ctx *c, const char *key, int64_t value) {
     if (id == OPT_HALO_DIRECT_RECV) c->halo_direct.store((int)value, std::memory_order_release);
     if (id == OPT_GCN_BF16_GATHER) c->gcn_bf16_mode.store((int)value, std::memory_order_release);   // (dory_halo_bf16_rows' rule)
     if (id == OPT_GATMH_BF16_GATHER) c->gatmh_bf16_mode_pub.store((int)value, std::memory_order_release);   // (dory_gatmh_halo_bf16's rule)
-    c->ah0_valid = false;   // (another kernel variant sums in another order: a cached ah@0 is only kept across identical settings)
+    c->layer0_changed();   // (another kernel variant sums in another order: a cached ah@0 is only kept across identical settings)
     return DORY_OK;
 }
 

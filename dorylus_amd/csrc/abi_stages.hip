@@ -464,7 +464,7 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
         // layer 0 is skipped while nothing it reads has been written through this ABI since it was last computed.
         const bool cache = layer == 0 && c->opt[OPT_GCN_CACHE_AH0] && !c->capturing;
         if (cache && c->ah0_valid) { c->ah0_skips++; return DORY_OK; }
-        if (layer == 0) c->ah0_valid = false;
+        if (layer == 0) c->layer0_changed();   // (ah@0 is about to be rewritten: a resident copy of it, dory_gemm_bf16_resident, goes too)
         c->agg_static_ghosts = layer == 0;
         const int rc = spmm(c, In, In.val, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd);
         c->agg_static_ghosts = false;

@@ -347,6 +347,20 @@ struct dory_ctx {
     // rows, and those with a send target that ran the plain bf16 kernel because the send rule (gemm_send_applies) refused
     bool gemm_bf16_send = false;
     uint64_t gemm_bf16_send_launches = 0, gemm_bf16_send_plain = 0;
+    // dory_gemm_bf16_resident: the switch (inert at mode 0); the resident bf16 copies of the layer-0 A operands K2r reads (at most two: x
+    // and fg@0 can both be live) -- the tensor shadowed, rows x ldr bf16 made on the compute stream at the first product that wants it and
+    // current while `valid` -- and the products that ran K2r, the copies made, and the products of an eligible operand that ran K2b / K2c
+    // / K2 all the same (abi_context.hip: gemm_resident_for).  layer0_changed() is what every writer of a layer-0 constant calls.
+    struct GemmResident {
+        const dory::Tensor *src = nullptr;
+        uint16_t *buf = nullptr;
+        size_t bytes = 0;
+        uint32_t ldr = 0;
+        bool valid = false;
+    };
+    bool gemm_bf16_resident = false;
+    GemmResident gemm_res[2];
+    uint64_t gemm_res_launches = 0, gemm_res_conversions = 0, gemm_res_plain = 0;
     float *partial = nullptr;
     size_t partial_bytes = 0;
 
@@ -354,6 +368,11 @@ struct dory_ctx {
     bool prealloc = false;
     bool ah0_valid = false;      // option gcn_cache_ah0: ah@0 holds the aggregate of the current x / fg@0 / adjacency
     uint64_t ah0_skips = 0;      // layer-0 aggregations answered from it
+    // x / fg@0 / ah@0 / h@0 may have changed (or, for ah@0, are about to): the kept aggregate and K2r's resident copies no longer hold
+    void layer0_changed() {
+        ah0_valid = false;
+        for (GemmResident &r : gemm_res) r.valid = false;
+    }
     // options gcn_bf16_gather / gatmh_bf16_gather: the bf16 copy of the rows an aggregation reads ((N + ghosts) x ld, rewritten
     // by every pass that uses it, never kept across calls), and the passes that ran on it per kernel family
     uint16_t *bf16_rows = nullptr;
@@ -608,6 +627,14 @@ hipError_t launch_gemm_bf16_send(const GemmArgs &g, const GemmSend &sd, float *s
 hipError_t launch_gemm_bf16_split_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
                                        bool *fused);
 hipError_t launch_splitk_reduce_send(const GemmArgs &g, const GemmSend &sd, const float *partial, uint32_t S, hipStream_t s);
+// K2r (gemm_bf16_resident.hip; dory_gemm_bf16_resident): K2b's NN and TN with A read from R, the resident bf16 copy of the tensor behind
+// g.A -- rows x ldr, ldr = cols rounded up to 32 elements, zeros in [cols, ldr), made by launch_gemm_resident_rows (nearest even).  NN's
+// A tile travels by LDS-DMA, TN's through registers as bf16; K2b's plan, sum order and bits.  gemm_bf16_resident_takes: NN or TN, and K2b's
+// own rule (a product its launcher would run) -- to be asked before a copy is made for the product
+bool gemm_bf16_resident_takes(const GemmArgs &g);
+inline uint32_t gemm_resident_ld(uint32_t cols) { return (cols + 31u) & ~31u; }
+hipError_t launch_gemm_resident_rows(const float *x, uint32_t ld, uint64_t rows, uint32_t cols, uint16_t *y, uint32_t ldr, hipStream_t s);
+hipError_t launch_gemm_bf16_resident(const GemmArgs &g, const uint16_t *R, uint32_t ldr, float *scratch, size_t scratch_bytes, hipStream_t s);
 
 // tanh of the transform's epilogue (K2), of the stand-alone activation and of K3's backward -- one function for all three, so
 // that h and the 1 - tanh^2 of the backward pass are the same number.  libm's tanhf is ~40 vector instructions (40 M of the

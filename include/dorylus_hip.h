@@ -887,6 +887,38 @@ int dory_gemm_bf16_split_stats(dory_ctx *ctx, uint64_t *split_launches);
 int dory_gemm_bf16_send(dory_ctx *ctx, int on);   /* 0 (default) = off */
 int dory_gemm_bf16_send_stats(dory_ctx *ctx, uint64_t *send_launches, uint64_t *plain_while_on);
 
+/* ---- K2r: a resident bf16 operand for the layer-0 products of K2b (opt-in, default off; nothing in the reference) -----------------
+ * HAZARD, RAW POINTERS: with the switch on, a write to x, fg@0, ah@0 or h@0 through a device pointer that dory_tensor_info handed
+ * out EARLIER is not seen by the products that follow -- they read the copy.  dory_tensor_info drops the tensor's copy at the moment
+ * it hands the pointer out, and at no later time: a caller that writes through a raw pointer calls dory_tensor_info for that tensor
+ * again after every such write (or uses dory_tensor_upload), or leaves the switch off.  With the switch off such writes are honoured
+ * as ever.
+ * The A operand of the layer-0 NN and TN products is the same matrix every epoch: x and fg@0 of a transform-first GCN, ah@0 of a GCN
+ * under option gcn_cache_ah0 while the kept aggregate holds, h@0 of the GAT prototype and of the 8-head GAT.  K2b reads it as fp32 and
+ * rounds it to bf16 in registers, twice per epoch.  With this switch on the context keeps a bf16 copy of such an operand (rows x ldr,
+ * ldr = cols rounded up to 32 elements, zeros in [cols, ldr); nearest even, the rounding of K2b and of the shadow rows), made on the
+ * compute stream at the first product that wants it, and those products run K2r (csrc/gemm_bf16_resident.hip): K2b's geometry, split
+ * plan, LDS image and MFMA loop with the A tile of NN travelling global -> LDS by LDS-DMA and the A tile of TN transposed from bf16
+ * dwords -- half the operand's bytes, no conversion, no registers for the NN tile.
+ * on: 0 (default) or 1.  Legal before dory_configure and on every model; inert while dory_gemm_bf16's mode does not cover the product.
+ * CONTRACT: switch on = switch off, bit for bit, in every tensor, weight and weight gradient (K2r sums in K2b's order).
+ * WHICH PRODUCTS: those gemm() would hand to K2b's plain kernel (NN under mode 1 and 2, TN under mode 2) whose A operand is one of
+ * the tensors above.  An eligible operand's product runs what it runs without the switch, and is counted in plain_while_on, under
+ * dory_gemm_bf16_split (a hi + lo pair is as many bytes as fp32), where it wants a send form, for ah@0 without gcn_cache_ah0 or while
+ * the kept aggregate does not hold, off K2's 16-byte rule, and while an epoch graph records (nothing is allocated or converted then,
+ * and a replay could not see a later upload).  NT never qualifies: its A is a gradient.
+ * THE COPY is dropped (and made again by the next product: conversions) by everything that may change the tensor through this ABI --
+ * a layer-0 dory_tensor_upload / dory_tensor_fill_uniform, dory_graph_upload, dory_preallocate, every transport's write of fg@0, a
+ * change of kernel variant, a new aggregation into ah@0 -- and by dory_tensor_info handing out the tensor's device pointer: a caller
+ * that writes through a raw pointer asks for it again after writing.  At most two copies live per context; their memory is freed by
+ * switching off, by dory_preallocate and by dory_destroy.
+ * DORY_ERR_ARG: a value other than 0 or 1; a call while an epoch graph is being recorded.  A change drops a recorded epoch graph.
+ * Counters, in this order: products that ran K2r since dory_create (each also counts in bf16_launches), copies made, products of an
+ * eligible operand that did not run K2r with the switch on.  Any pointer may be NULL.
+ * MEASURED: see DESIGN.md section 3. */
+int dory_gemm_bf16_resident(dory_ctx *ctx, int on);   /* 0 (default) = off */
+int dory_gemm_bf16_resident_stats(dory_ctx *ctx, uint64_t *resident_launches, uint64_t *conversions, uint64_t *plain_while_on);
+
 /* ---- bf16 ghost twins: bf16 halo rows land where they are read (opt-in, default off; nothing in the reference) -------------
  * With dory_halo_bf16_rows alone a bf16 row is widened into the fp32 ghost tensor on arrival and rounded back into the shadow rows
  * by the aggregation that reads it: two conversions that cancel (the argument above), 1536 bytes of memory traffic and two kernels
