@@ -44,6 +44,7 @@ SYMBOLS = [
     "dory_gatmh_row_gather_edge_split", "dory_gatmh_row_gather_edge_split_stats",
     "dory_gatmh_row_gather_bf16_wide", "dory_gatmh_row_gather_bf16_wide_stats",
     "dory_k1_bf16_wide", "dory_k1_bf16_wide_stats", "dory_k1_bf16_wide_form",
+    "dory_k1_fp8_gather", "dory_k1_fp8_gather_stats", "dory_k1_fp8_gather_download", "dory_k1_fp8_form", "dory_k1_fp8_rows",
     "dory_gemm_bf16", "dory_gemm_bf16_stats", "dory_gemm_bf16_split", "dory_gemm_bf16_split_stats",
     "dory_gemm_bf16_send", "dory_gemm_bf16_send_stats", "dory_gemm_bf16_resident", "dory_gemm_bf16_resident_stats",
 ]
@@ -207,6 +208,11 @@ def load():
         "dory_k1_bf16_wide": [vp, i32],
         "dory_k1_bf16_wide_stats": [vp] + [C.POINTER(u64)] * 2,
         "dory_k1_bf16_wide_form": [u32, u32, C.POINTER(u32), C.POINTER(u32)],
+        "dory_k1_fp8_gather": [vp, i32],
+        "dory_k1_fp8_gather_stats": [vp] + [C.POINTER(u64)] * 4,
+        "dory_k1_fp8_gather_download": [vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u32)],
+        "dory_k1_fp8_form": [u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
+        "dory_k1_fp8_rows": [vp, u64, u32, u32, vp, vp],
         # include/dorylus_host.h
         "dory_halo_send_map": [u32, u32, vp, vp, vp, vp],
         "dory_row_chunk_plan": [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), vp, vp, vp, vp, vp],
@@ -371,6 +377,33 @@ def k1_bf16_wide_form(ld, slab=0, lib=None):
     if not lib.dory_k1_bf16_wide_form(int(ld), int(slab), C.byref(g), C.byref(k)):
         return None
     return g.value, k.value
+
+
+def k1_fp8_form(ld, slab=0, lib=None):
+    """None where K1 has no fp8 form for rows of ld floats under option spmm_slab = slab (the aggregation runs as with the mode off),
+    else (lanes, chunks, bytes_per_lane): the instantiation of k1_fp8_rows_kernel that Context.k1_fp8_gather selects -- a row pass
+    covers lanes x chunks loads of 16 or 8 E4M3, gridDim.y passes cover the row (dory_k1_fp8_form; no context, no GPU)"""
+    lib = lib or load()
+    g, k, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    if not lib.dory_k1_fp8_form(int(ld), int(slab), C.byref(g), C.byref(k), C.byref(b)):
+        return None
+    return g.value, k.value, b.value
+
+
+def k1_fp8_rows(rows, ld=None, lib=None):
+    """the number format of Context.k1_fp8_gather on the host (dory_k1_fp8_rows; no context, no GPU): rows (n, cols) float32 ->
+    (q, e): q (n, ld) uint8, the rows as E4M3 bytes (zero bytes in [cols, ld); ld defaults to cols), e (n,) uint8, the rows' biased
+    power-of-two exponents; element j of row i stands for q[i, j] as float8_e4m3fn times 2 ** (e[i] - 127)"""
+    lib = lib or load()
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("k1_fp8_rows: rows must be two-dimensional")
+    n, cols = x.shape
+    ld = cols if ld is None else int(ld)
+    q, e = np.zeros((n, ld), np.uint8), np.zeros(n, np.uint8)
+    if lib.dory_k1_fp8_rows(_ptr(x), n, cols, ld, _ptr(q), _ptr(e)) != 0:
+        raise DoryError(f"k1_fp8_rows: ld = {ld} is under cols = {cols}")
+    return q, e
 
 
 class Context:
@@ -895,6 +928,29 @@ class Context:
         """dict: wide (aggregations K1 ran in the wide form since dory_create: eager calls and recordings), narrow_while_on
         (aggregations on bf16 rows K1 ran narrow with the switch on)"""
         return self._stats(self.lib.dory_k1_bf16_wide_stats, 2, self.K1_BF16_WIDE_STATS)
+
+    K1_FP8_GATHER_STATS = ("fp8", "other_family", "no_form", "rows_converted")
+
+    def k1_fp8_gather(self, mode=1):
+        """K1's GCN aggregations gather rows rounded to E4M3 with one power-of-two scale per row, a quarter of the fp32 bytes, fp32
+        sums in the fp32 order (dory_k1_fp8_gather): 0 (default) = off; 1 = the forward aggregations; 2 = forward and backward.  Takes
+        effect where the aggregation reaches K1 and k1_fp8_form has a form; not together with gcn_bf16_gather"""
+        self._ck(self.lib.dory_k1_fp8_gather(self.h, int(mode)))
+
+    def k1_fp8_gather_stats(self):
+        """dict: fp8 (aggregations K1 ran on fp8 rows since dory_create: eager calls and recordings), other_family (aggregations the
+        mode covers that K1s or K1b ran), no_form (those K1 ran without a form for the row width), rows_converted"""
+        return self._stats(self.lib.dory_k1_fp8_gather_stats, 4, self.K1_FP8_GATHER_STATS)
+
+    def k1_fp8_gather_download(self):
+        """the shadow rows of the last aggregation on fp8 rows, [N local rows ; ghost rows]: (q (rows, ld) uint8, e (rows,) uint8), as
+        k1_fp8_rows gives them; two empty arrays before the first one"""
+        n, ld = C.c_uint64(0), C.c_uint32(0)
+        self._ck(self.lib.dory_k1_fp8_gather_download(self.h, 0, None, None, C.byref(n), C.byref(ld)))
+        q, e = np.zeros((n.value, ld.value), np.uint8), np.zeros(n.value, np.uint8)
+        if n.value:
+            self._ck(self.lib.dory_k1_fp8_gather_download(self.h, n.value, _ptr(q), _ptr(e), C.byref(n), C.byref(ld)))
+        return q, e
 
     GEMM_BF16_STATS = ("bf16_launches", "fp32_while_on")
 

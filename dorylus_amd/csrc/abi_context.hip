@@ -527,6 +527,7 @@ int dory_destroy(dory_ctx *c) {
     }
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->bf16_rows) (void)hipFree(c->bf16_rows);
+    if (c->fp8_rows) (void)hipFree(c->fp8_rows);
     gemm_resident_free(c);
     if (c->gatmh_carry_state) (void)hipFree(c->gatmh_carry_state);
     if (c->partial) (void)hipFree(c->partial);
@@ -770,6 +771,44 @@ int dory_k1_bf16_wide_stats(dory_ctx *c, uint64_t *wide, uint64_t *narrow_while_
     CHECK_CTX(c);
     if (wide) *wide = c->k1_rows8_wide;
     if (narrow_while_on) *narrow_while_on = c->k1_rows8_narrow;
+    return DORY_OK;
+}
+
+// ---- dory_k1_fp8_gather: K1's GCN aggregations gather fp8 rows (spmm_fp8.hip; abi_stages.hip: Fp8Rows, spmm_k1; include/dorylus_hip.h) ----
+int dory_k1_fp8_gather(dory_ctx *c, int mode) {
+    CHECK_CTX(c);
+    if (mode < 0 || mode > 2) return fail(c, DORY_ERR_ARG, "k1_fp8_gather: mode %d is none of 0 (off), 1 (forward), 2 (forward and backward)", mode);
+    if (mode && c->configured && c->gnn != DORY_GCN)
+        return fail(c, DORY_ERR_ARG, "k1_fp8_gather: this context is configured as %s; the feature serves K1 of DORY_GCN only",
+                    c->gnn == DORY_GAT ? "DORY_GAT" : "DORY_GATMH");
+    if (c->capturing) return fail(c, DORY_ERR_ARG, "k1_fp8_gather: not while an epoch graph is being recorded");
+    if (mode != c->k1_fp8_mode) {
+        epoch_graph_drop_locked(c);   // (a recorded epoch holds the other mode's launches)
+        c->ah0_valid = false;         // (option gcn_cache_ah0: a kept ah@0 is the other mode's aggregate)
+    }
+    c->k1_fp8_mode = mode;
+    return DORY_OK;
+}
+
+int dory_k1_fp8_gather_stats(dory_ctx *c, uint64_t *fp8_aggregations, uint64_t *other_family, uint64_t *no_form, uint64_t *rows_converted) {
+    CHECK_CTX(c);
+    if (fp8_aggregations) *fp8_aggregations = c->k1_fp8_aggs;
+    if (other_family) *other_family = c->k1_fp8_other;
+    if (no_form) *no_form = c->k1_fp8_no_form;
+    if (rows_converted) *rows_converted = c->k1_fp8_converted;
+    return DORY_OK;
+}
+
+int dory_k1_fp8_gather_download(dory_ctx *c, uint64_t cap_rows, uint8_t *q, uint8_t *e, uint64_t *rows, uint32_t *ld) {
+    CHECK_CTX(c);
+    const uint64_t n = c->fp8_last_rows;
+    if (rows) *rows = n;
+    if (ld) *ld = c->fp8_last_ld;
+    if (!n || cap_rows < n || !q || !e) return DORY_OK;
+    const size_t qbytes = (size_t)n * c->fp8_last_ld;
+    HIPCK(c, hipStreamSynchronize(c->compute));
+    HIPCK(c, hipMemcpy(q, c->fp8_rows, qbytes, hipMemcpyDeviceToHost));
+    HIPCK(c, hipMemcpy(e, c->fp8_rows + ((qbytes + 15) & ~(size_t)15), n, hipMemcpyDeviceToHost));
     return DORY_OK;
 }
 

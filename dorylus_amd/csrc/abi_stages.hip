@@ -160,19 +160,66 @@ struct Bf16Rows {
     int ghosts_landed() { return ghost ? bf16_convert(c, *ghost, c->N) : DORY_OK; }
 };
 
+// dory_k1_fp8_gather: one aggregation's use of the fp8 shadow buffer (spmm_fp8.hip), managed as Bf16Rows manages its own: begin()
+// sizes it -- [(N + ghosts) x ld bytes of E4M3 | 16-byte aligned: one exponent byte per row], only ever grown, never inside a
+// recording -- and converts the N local rows; ghosts_landed() converts the ghost rows once the exchange that writes them has landed.
+struct Fp8Rows {
+    dory_ctx *c = nullptr;
+    const Tensor *ghost = nullptr;
+    K1Fp8Src src{nullptr, nullptr};
+    int convert(const Tensor &t, uint64_t first_row) {
+        if (!t.rows) return DORY_OK;
+        Timed tc(c, "fp8_convert", c->compute);
+        HIPCK(c, launch_fp8_rows(t.d, const_cast<uint8_t *>(src.q) + first_row * t.ld, const_cast<uint8_t *>(src.e) + first_row, t.rows, t.ld, c->compute));
+        c->k1_fp8_converted += t.rows;
+        return DORY_OK;
+    }
+    int begin(dory_ctx *ctx, const Tensor &rows, const Tensor *ghost_rows, uint64_t nghost) {
+        const uint64_t total = (uint64_t)ctx->N + nghost;
+        const size_t qbytes = ((size_t)total * rows.ld + 15) & ~(size_t)15, need = qbytes + total;
+        if (need > ctx->fp8_rows_bytes) {
+            if (ctx->capturing) return fail(ctx, DORY_ERR_ARG, "epoch graph: the fp8 rows of dory_k1_fp8_gather would have to grow while recording");
+            if (ctx->fp8_rows) {
+                HIPCK(ctx, hipStreamSynchronize(ctx->compute));
+                (void)hipFree(ctx->fp8_rows);
+                ctx->fp8_rows = nullptr;
+                ctx->fp8_rows_bytes = 0;
+                epoch_graph_drop_locked(ctx);   // (a recorded epoch would read the freed buffer)
+            }
+            HIPCK(ctx, hipMalloc((void **)&ctx->fp8_rows, need));
+            ctx->fp8_rows_bytes = need;
+        }
+        c = ctx;
+        ghost = nghost ? ghost_rows : nullptr;
+        src = K1Fp8Src{c->fp8_rows, c->fp8_rows + qbytes};
+        c->fp8_last_rows = total;
+        c->fp8_last_ld = rows.ld;
+        Tensor local = rows;
+        local.rows = c->N;
+        return convert(local, 0);
+    }
+    bool on() const { return c != nullptr; }
+    int ghosts_landed() { return ghost ? convert(*ghost, c->N) : (int)DORY_OK; }
+};
+
 // The schedule every kernel family of spmm() follows around a halo exchange: what does not read the ghost rows is launched
 // `first`, timed as "spmm_beside_halo" (under an exchange in flight; "spmm_local_first": the same split with nothing in
-// flight), then the compute stream waits for the ghosts (and rounds them, for an aggregation on bf16 rows), then `rest` runs.
-// Not split: the wait, then `rest` alone.  bf == nullptr: an aggregation on fp32 rows (K1b has no other).
-template <class First, class Rest>
-static int around_halo(dory_ctx *c, bool split, Bf16Rows *bf, First first, Rest rest) {
+// flight), then the compute stream waits for the ghosts, `landed` runs (what has to be made of the ghost rows before a kernel reads
+// them: the rounding of an aggregation on bf16 or fp8 rows), then `rest` runs.  Not split: the wait, `landed`, then `rest` alone.
+template <class Landed, class First, class Rest>
+static int around_halo_then(dory_ctx *c, bool split, Landed landed, First first, Rest rest) {
     int rc;
     if (split) {
         Timed tb(c, c->halo_pending ? "spmm_beside_halo" : "spmm_local_first", c->compute);
         if ((rc = first())) return rc;
     }
-    if ((rc = wait_halo(c)) || (bf && (rc = bf->ghosts_landed()))) return rc;
+    if ((rc = wait_halo(c)) || (rc = landed())) return rc;
     return rest();
+}
+// ... with the hook of an aggregation on bf16 rows; bf == nullptr: an aggregation on fp32 rows (K1b has no other)
+template <class First, class Rest>
+static int around_halo(dory_ctx *c, bool split, Bf16Rows *bf, First first, Rest rest) {
+    return around_halo_then(c, split, [&]() -> int { return bf ? bf->ghosts_landed() : (int)DORY_OK; }, first, rest);
 }
 
 // What a launch sequence on the sweep skeleton (K1s, the 8-head GAT's edge passes) needs beside its tensors, decided once per
@@ -313,10 +360,25 @@ static int spmm_k1b(dory_ctx *c, Adjacency &A, const SpmmArgs &a, const float *r
 }
 
 // K1: the row gather with per-edge values (spmm.hip), whatever the graph.
-static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
+// f8l (dory_k1_fp8_gather; nullptr: not asked for): the tensor of the local rows, f8g that of the ghost rows -- the aggregation
+// gathers their fp8 shadow rows where k1_fp8_form has a form for the row and slab width; else as without, counted.
+static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf, const Tensor *f8l = nullptr, const Tensor *f8g = nullptr) {
     if (!a.val) return fail(c, DORY_ERR_ARG, "spmm: no edge values");
     const bool bf16 = bf.on();
     c->spmm_launches_k1++;
+    Fp8Rows f8;
+    if (f8l && !bf16) {
+        uint32_t lanes, chunks, bytes;
+        const int64_t slab = c->opt[OPT_SPMM_SLAB];
+        if (!k1_fp8_form(a.ld, slab > 0 ? (uint32_t)slab : 0u, &lanes, &chunks, &bytes)) {
+            c->k1_fp8_no_form++;
+        } else {
+            int rc = f8.begin(c, *f8l, f8g, a.xg ? f8g->rows : 0);
+            if (rc) return rc;
+            c->k1_fp8_aggs++;
+        }
+    }
+    const bool fp8 = f8.on();
     if (bf16) (c->gnn == DORY_GAT ? c->gat_bf16_gathers_k1 : c->bf16_gathers_k1)++;
     // dory_k1_bf16_wide: every launch of this aggregation gathers its bf16 rows 16 bytes a lane where the rule has a form for the row
     // and slab width and the shadow rows and the ghost rows (the twin, or the shadow rows' tail) are 16-byte aligned; else narrow, counted
@@ -329,8 +391,13 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
         (wide ? c->k1_rows8_wide : c->k1_rows8_narrow)++;
     }
     auto launch = [&](const SpmmArgs &x) -> int {
-        HIPCK(c, launch_spmm(x, (int)c->opt[OPT_SPMM_SLAB], c->compute, bf16, wide));
+        if (fp8) HIPCK(c, launch_k1_fp8(x, f8.src, (int)c->opt[OPT_SPMM_SLAB], c->compute));
+        else HIPCK(c, launch_spmm(x, (int)c->opt[OPT_SPMM_SLAB], c->compute, bf16, wide));
         return DORY_OK;
+    };
+    auto landed = [&]() -> int {   // the ghost rows have landed: round them, for an aggregation on bf16 or fp8 rows
+        const int rc = bf.ghosts_landed();
+        return rc ? rc : f8.ghosts_landed();
     };
     const LongRowsDev &longRows = A.long_rows;
     if (longRows.nchunks) {   // hubs: K1 stops after LONG_ROW_CLAMP edges of a row, workgroup-per-chunk kernels do the rest
@@ -358,8 +425,8 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
         p2.accumulate = 2;
         const bool boundary = !A.split || A.n_interior < c->N;   // rows without a ghost source are done
         if (A.split && boundary) { p2.order = A.split + A.n_interior; p2.rows = c->N - A.n_interior; }
-        return around_halo(c, in_flight, &bf, [&] { return launch(p1); },
-                           [&] { return !in_flight ? launch(a) : boundary ? launch(p2) : (int)DORY_OK; });
+        return around_halo_then(c, in_flight, landed, [&] { return launch(p1); },
+                                [&] { return !in_flight ? launch(a) : boundary ? launch(p2) : (int)DORY_OK; });
     }
     // (other cases -- GAT's per-epoch edge values, hub rows: the rows whose sources are all local run first, the rows that read
     // ghost rows after the comm stream's event)
@@ -372,10 +439,13 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
         boundary.order = A.split + A.n_interior;
         boundary.rows = c->N - A.n_interior;
     }
-    return around_halo(c, split_rows, &bf, [&] { return launch(interior); }, [&]() -> int {
+    return around_halo_then(c, split_rows, landed, [&] { return launch(interior); }, [&]() -> int {
         if (split_rows) return launch(boundary);
         int rc = launch(a);
-        if (!rc && longRows.nchunks) HIPCK(c, launch_spmm_long_rows(a, longRows, c->scratch, c->compute, bf16));
+        if (!rc && longRows.nchunks) {
+            if (fp8) HIPCK(c, launch_k1_fp8_long_rows(a, f8.src, longRows, c->scratch, c->compute));
+            else HIPCK(c, launch_spmm_long_rows(a, longRows, c->scratch, c->compute, bf16));
+        }
         return rc;
     });
 }
@@ -389,12 +459,15 @@ static int spmm_k1(dory_ctx *c, Adjacency &A, SpmmArgs a, Bf16Rows &bf) {
 // K1s and K1 have bf16 forms, K1b has none: where fp32 would take K1b, bf16 takes K1.  row_scale on bf16 rows: the GAT
 // prototype's unit-weight forms of K1s only.  bf_out (optional): the aggregation's shadow rows, for a caller that reads the
 // rounded self rows once more (they stay until the next aggregation on bf16 rows).
+// fp8 (dory_k1_fp8_gather; never together with bf16): where the aggregation reaches K1, every row read is rounded to E4M3 with one
+// scale per row first (spmm_k1); K1s and K1b run it as without.
 static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tensor &xl, Tensor *xg, Tensor &out,
-                uint32_t F, int accumulate, const float *row_scale = nullptr, bool bf16 = false, Bf16Rows *bf_out = nullptr) {
+                uint32_t F, int accumulate, const float *row_scale = nullptr, bool bf16 = false, Bf16Rows *bf_out = nullptr, bool fp8 = false) {
     if (xl.ld != out.ld || (xg && xg->rows && xg->ld != xl.ld) || xl.cols != F)
         return fail(c, DORY_ERR_ARG, "spmm: tensor shapes disagree (F=%u ld %u/%u)", F, xl.ld, out.ld);
     if (bf16 && ((row_scale && c->gnn != DORY_GAT) || xl.rows < c->N))
         return fail(c, DORY_ERR_ARG, "spmm: bf16 rows need edge weights (but on a GAT context) and N rows");
+    if (fp8 && (bf16 || row_scale || xl.rows < c->N)) return fail(c, DORY_ERR_ARG, "spmm: fp8 rows need edge weights, N rows and no bf16 rows");
     c->last_spmm_unit = false;
     // dory_halo_bf16_ghosts: an aggregation on fp32 rows of a ghost tensor whose twin alone is current (the gather mode changed after
     // the exchange) gets the twin widened first; one on bf16 rows reads the twin itself (Bf16Rows::begin)
@@ -422,7 +495,8 @@ static int spmm(dory_ctx *c, Adjacency &A, const float *val, int self_mode, Tens
     int rc = SPMM_NOT_MINE;
     if (layouts && c->opt[OPT_SPMM_VARIANT] == 2) rc = spmm_k1s(c, A, a, row_scale, bf);
     if (rc == SPMM_NOT_MINE && layouts && c->opt[OPT_SPMM_VARIANT] >= 1 && !bf16) rc = spmm_k1b(c, A, a, row_scale);
-    if (rc == SPMM_NOT_MINE) rc = spmm_k1(c, A, a, bf);
+    if (rc != SPMM_NOT_MINE && fp8) c->k1_fp8_other++;   // (K1s or K1b took it: as with the mode off, counted)
+    if (rc == SPMM_NOT_MINE) rc = spmm_k1(c, A, a, bf, fp8 ? &xl : nullptr, xg);
     if (bf_out) *bf_out = bf;
     return rc;
 }
@@ -441,6 +515,11 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
         return fail(c, DORY_ERR_ARG, "aggregate: gcn_bf16_gather = %lld with spmm_variant = 1 (K1b has no bf16 form: spmm_variant 0 or 2)",
                     (long long)bfm);
     const bool bf_fwd = bfm >= 1, bf_bwd = bfm >= 2;
+    // opt-in dory_k1_fp8_gather: 1 = the forward aggregations that reach K1 read fp8 rows, 2 = the backward ones too
+    if (bfm && c->k1_fp8_mode)
+        return fail(c, DORY_ERR_ARG, "aggregate: gcn_bf16_gather = %lld with dory_k1_fp8_gather = %d (one rounding of the rows or the other: set one of them to 0)",
+                    (long long)bfm, c->k1_fp8_mode);
+    const bool f8_fwd = c->k1_fp8_mode >= 1, f8_bwd = c->k1_fp8_mode >= 2;
     if (dir == DORY_FORWARD) {
         if (layer >= c->L) return fail(c, DORY_ERR_ARG, "aggregate: layer %u out of range", layer);
         Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
@@ -456,7 +535,7 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
                 if (!rc && In.ghosts) rc = gemm(c, 0, 0, In.ghosts, c->dims[1], c->dims[0], *fg, W, *fgxw);
                 if (rc) return rc;
             }   // deeper layers: apply_vertex(l-1) left xw@l, the forward exchange of layer l its ghost rows
-            return spmm(c, In, In.val, 1, *xw, fgxw, *z, c->dims[layer + 1], 0, nullptr, bf_fwd);
+            return spmm(c, In, In.val, 1, *xw, fgxw, *z, c->dims[layer + 1], 0, nullptr, bf_fwd, nullptr, f8_fwd);
         }
         // Opt-in "gcn_cache_ah0" (no reference counterpart; the reference recomputes it every epoch and so does the
         // default here): in full-graph training ah@0 = A_hat [x ; fg@0] is a constant of the run -- x and fg@0 come
@@ -466,7 +545,7 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
         if (cache && c->ah0_valid) { c->ah0_skips++; return DORY_OK; }
         if (layer == 0) c->layer0_changed();   // (ah@0 is about to be rewritten: a resident copy of it, dory_gemm_bf16_resident, goes too)
         c->agg_static_ghosts = layer == 0;
-        const int rc = spmm(c, In, In.val, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd);
+        const int rc = spmm(c, In, In.val, 1, *in, fg, *ah, c->dims[layer], 0, nullptr, bf_fwd, nullptr, f8_fwd);
         c->agg_static_ghosts = false;
         if (cache) c->ah0_valid = rc == DORY_OK;
         return rc;
@@ -476,7 +555,7 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
         Tensor *in = layer == 0 ? find(c, 0, "x") : find(c, layer - 1, "h");
         if (!in) return fail(c, DORY_ERR_ARG, "aggregate: input tensor missing");
         const uint32_t Fin = c->dims[layer], Fout = c->dims[layer + 1];
-        int rc = spmm(c, Out, Out.val, 1, *g, bgg, *u, Fout, 0, nullptr, bf_bwd);
+        int rc = spmm(c, Out, Out.val, 1, *g, bgg, *u, Fout, 0, nullptr, bf_bwd, nullptr, f8_bwd);
         if (rc) return rc;
         if ((rc = gemm(c, 1, 0, Fin, Fout, c->N, *in, *u, c->wgrads[layer]["w"]))) return rc;
         if (layer == 0) return DORY_OK;
@@ -487,7 +566,7 @@ static int aggregate_gcn(dory_ctx *c, uint32_t layer, int dir) {
     AGG_NEED(grad, layer, "grad");
     AGG_NEED(bg, layer - 1, "bg");
     AGG_NEED(aTg, layer - 1, "aTg");
-    return spmm(c, Out, Out.val, 1, *grad, bg, *aTg, c->dims[layer], 0, nullptr, bf_bwd);
+    return spmm(c, Out, Out.val, 1, *grad, bg, *aTg, c->dims[layer], 0, nullptr, bf_bwd, nullptr, f8_bwd);
 }
 
 // What the two edge passes of the multi-head GAT on the sweep skeleton do alike (forward: the layout of the in-edges; source side of

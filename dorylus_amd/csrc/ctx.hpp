@@ -336,6 +336,16 @@ struct dory_ctx {
     // on (no form for the row or slab width, rows not 16-byte aligned)
     bool k1_bf16_wide = false;
     uint64_t k1_rows8_wide = 0, k1_rows8_narrow = 0;
+    // dory_k1_fp8_gather: the mode (0 off, 1 forward, 2 forward and backward); the shadow buffer of the rows one aggregation reads
+    // ((N + ghosts) x ld bytes of E4M3, then one exponent byte per row; rewritten by every aggregation that uses it, only grows); what
+    // the last aggregation left there; the aggregations K1 ran on fp8 rows, those the mode covers that another family ran or that had
+    // no form, and the rows converted
+    int k1_fp8_mode = 0;
+    uint8_t *fp8_rows = nullptr;
+    size_t fp8_rows_bytes = 0;
+    uint64_t fp8_last_rows = 0;
+    uint32_t fp8_last_ld = 0;
+    uint64_t k1_fp8_aggs = 0, k1_fp8_other = 0, k1_fp8_no_form = 0, k1_fp8_converted = 0;
     // dory_gemm_bf16: the mode (0 off, 1 NN and NT, 2 also TN); the products that ran the bf16 kernel (gemm_bf16.hip), and those of a
     // form the mode covers that ran K2's fp32 kernel all the same (a send form: the fused halo pack)
     int gemm_bf16 = 0;
@@ -507,6 +517,18 @@ hipError_t launch_spmm(const SpmmArgs &a, int slab, hipStream_t s, bool bf16 = f
 
 void plan_long_rows(const uint64_t *ptr, uint32_t N, LongRowsHost *out);
 hipError_t launch_spmm_long_rows(const SpmmArgs &a, const LongRowsDev &L, float *partial /*nchunks x ld*/, hipStream_t s, bool bf16 = false);
+
+// K1 on fp8 rows (spmm_fp8.hip; dory_k1_fp8_gather).  The rows a launch gathers: (N + ghosts) rows of ld bytes of E4M3 -- a source id
+// addresses its row, local or ghost -- and one biased exponent byte per row; xl / xg of the SpmmArgs are not read.
+struct K1Fp8Src {
+    const uint8_t *q;
+    const uint8_t *e;
+};
+// rows x ld floats -> rows x ld bytes and rows exponent bytes (include/dorylus_hip.h: the number format); ld a multiple of 16
+hipError_t launch_fp8_rows(const float *x, uint8_t *q, uint8_t *e, uint64_t rows, uint32_t ld, hipStream_t s);
+// a form of k1_fp8_form (k1_shapes.hpp) and 16-byte aligned rows, else refused
+hipError_t launch_k1_fp8(const SpmmArgs &a, const K1Fp8Src &r, int slab, hipStream_t s);
+hipError_t launch_k1_fp8_long_rows(const SpmmArgs &a, const K1Fp8Src &r, const LongRowsDev &L, float *partial /*nchunks x ld*/, hipStream_t s);
 
 hipError_t build_blocked(const uint64_t *ptr, const uint32_t *idx, const float *val, uint32_t N, uint32_t NG,
                          uint64_t nnz, uint32_t want_nb /*0 = auto*/, uint32_t row_bytes, BlockedAdj *out,

@@ -1,5 +1,6 @@
 // k1_shapes.hpp -- the form rule of K1's wide bf16 row gather (spmm.hip: spmm_rows_bf16x8_kernel; dory_k1_bf16_wide) as launch_spmm
-// applies it, for host code without a device too (plain C++, no HIP; include/dorylus_hip.h: dory_k1_bf16_wide_form).
+// applies it, for host code without a device too (plain C++, no HIP; include/dorylus_hip.h: dory_k1_bf16_wide_form); and the form rule
+// of K1 on fp8 rows (spmm_fp8.hip: k1_fp8_rows_kernel; dory_k1_fp8_gather, dory_k1_fp8_form) as launch_k1_fp8 applies it.
 #ifndef DORY_K1_SHAPES_HPP
 #define DORY_K1_SHAPES_HPP
 #include <cstdint>
@@ -35,6 +36,36 @@ inline bool k1_rows8_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t 
     else { g = 64; k = 3; }
     *lanes = g;
     *chunks = k;
+    return true;
+}
+
+// The forms of K1 on fp8 rows (spmm_fp8.hip: k1_fp8_rows_kernel<lanes, chunks, bytes>; dory_k1_fp8_gather): a row is ld BYTES of E4M3.
+// The width of one block pass is launch_spmm's, as above.  No form -- the aggregation runs as with the mode off -- where ld < 64 (a
+// 32-float row is four 8-byte chunks), where ld is no multiple of 16, or where a pass is under 64 floats wide.  Rows and passes of 128
+// floats or more: a lane keeps SIXTEEN consecutive features per chunk (one 16-byte load), the shape by ch16 = ceil(width / 16); rows
+// wider than 64 x 2 chunks (2048 floats) take gridDim.y slabs of (64, 2).  Narrower (ld 64 and 96; a slab of 64 .. 127 floats): eight
+// features per lane (one 8-byte load) on (8, 1) / (16, 1).
+inline bool k1_fp8_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t *chunks, uint32_t *bytes_per_lane) {
+    if (ld < 64 || (ld & 15)) return false;
+    uint32_t width = ld;
+    if (slab > 0 && slab < width) width = slab;
+    if (width < 64) return false;
+    uint32_t g, k = 1, b;
+    if (width >= 128) {
+        b = 16;
+        const uint32_t ch16 = (width + 15) / 16;
+        if (ch16 <= 8) g = 8;
+        else if (ch16 <= 16) g = 16;
+        else if (ch16 <= 32) g = 32;
+        else if (ch16 <= 64) g = 64;
+        else { g = 64; k = 2; }
+    } else {
+        b = 8;
+        g = (width + 7) / 8 <= 8 ? 8 : 16;
+    }
+    *lanes = g;
+    *chunks = k;
+    *bytes_per_lane = b;
     return true;
 }
 

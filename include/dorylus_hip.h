@@ -811,6 +811,52 @@ int dory_k1_bf16_wide(dory_ctx *ctx, int on);   /* 0 (default) = off */
 int dory_k1_bf16_wide_stats(dory_ctx *ctx, uint64_t *wide, uint64_t *narrow_while_on);
 int dory_k1_bf16_wide_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t *chunks);
 
+/* ---- K1, the row gather: fp8 (E4M3, one scale per row) row gathers (opt-in, default off; nothing in the reference) -----------------
+ * K1 is bound by the bytes it gathers; bf16 rows halved them (gcn_bf16_gather).  With a mode on, a GCN aggregation that K1 runs reads
+ * rows of a QUARTER of the fp32 bytes: every row it reads -- self row, local and ghost rows -- is rounded into a shadow buffer of ld
+ * bytes and one exponent byte per row, and gathered from there (csrc/spmm_fp8.hip).  Edge values, norm, the sums and every tensor and
+ * weight stay fp32; halo rows stay fp32 on the wire; the sums run in the fp32 path's order.
+ * THE NUMBER FORMAT.  A row is all ld floats of a tensor row.  With amax its largest magnitude,
+ *     e   = clamp(floor(log2 amax) - 7, DORY_K1_FP8_EXP_MIN, DORY_K1_FP8_EXP_MAX); e = 0 for an all-zero row;
+ *     q_j = x_j 2^-e (exact), held to +-448, rounded to nearest even to OCP E4M3 (float8_e4m3fn), subnormals included;
+ * the row is the ld bytes q and the byte e + 127 (as E8M0).  Unclamped, the scaled maximum lies in [128, 256): rounding reaches 256 at
+ * most, nothing saturates, and every element moves by at most 2^-4 of amax.  The clamp to [-117, 119] keeps every dequantised value
+ * q_j 2^e a NORMAL fp32 or zero (2^-9 2^-117 = 2^-126 .. 448 2^119 < 2^128), so q 2^e is exact whatever the denormal mode.  It bites
+ * only outside 2^-110 <= amax < 2^127: a smaller row keeps e = -117 and loses its low bits (below 2^-126 nothing is left), a larger one
+ * keeps e = 119 and its elements of 448 2^119 or more are held there.  Rows with a non-finite value are outside the contract.
+ *   dory_k1_fp8_rows   the definition, as a host function without a device: n rows of `cols` floats (dense, row stride cols) become n rows
+ *                      of ld bytes (q_out; [cols, ld) are zero bytes, as a tensor's padding is) and n exponent bytes (e_out).  ld >= cols.
+ *                      The conversion kernel (fp8_rows_kernel) gives these bytes.
+ *   dory_k1_fp8_form   the form rule (csrc/k1_shapes.hpp: k1_fp8_form; no context, no device): 1 and the instantiation
+ *                      k1_fp8_rows_kernel<lanes, chunks, bytes_per_lane>, or 0 (outputs 0; any pointer may be NULL) where ld < 64, ld is
+ *                      no multiple of 16, or option spmm_slab makes a pass narrower than 64 floats.  width = ld or the slab where
+ *                      narrower.  width >= 128: 16 bytes (sixteen features) per lane, by ch = ceil(width / 16): <= 8 (8, 1); <= 16
+ *                      (16, 1); <= 32 (32, 1); <= 64 (64, 1); <= 128 (64, 2); wider: gridDim.y slabs of (64, 2).  width < 128 (ld 64, 96):
+ *                      8 bytes per lane on (8, 1) / (16, 1).
+ *   mode               0 (default) off; 1 the forward aggregations; 2 forward and backward.
+ *   where it runs      where the aggregation reaches K1: spmm_variant = 0, or K1s / K1b leaving it to K1.  Every launch of it: the
+ *                      local-first edge split in one launch and in two, the interior / boundary row split, the plain launch, the
+ *                      clamped launch and the long-row kernels (k1_fp8_longrow_kernel).  The local rows are converted at the start of
+ *                      the aggregation, the ghost rows once the exchange that writes them has landed; nothing is kept across calls.
+ *   not taken          an aggregation K1s or K1b runs, and a row width without a form (ld = 32), run as with mode 0 and are counted.
+ * CONTRACT: an aggregation on fp8 rows equals, BIT FOR BIT, the mode-0 aggregation of a context whose local and ghost rows were
+ * uploaded dequantised (q 2^e): per output element the same fmaf chain in edge order from the same start.
+ * DORY_ERR_ARG: a mode other than 0, 1, 2; a non-zero mode on a context configured as anything but DORY_GCN; a call while an epoch
+ * graph is being recorded.  A change drops a recorded epoch graph.  dory_aggregate refuses a non-zero mode together with
+ * gcn_bf16_gather != 0 (one rounding or the other).  The shadow buffer only grows, and never inside a recording.
+ * Counters, in this order: aggregations K1 ran on fp8 rows since dory_create (eager calls and recordings, not replays); aggregations
+ * the mode covers that K1s or K1b ran; aggregations the mode covers that K1 ran without a form; rows converted.  Any pointer may be NULL.
+ * dory_k1_fp8_gather_download: the shadow rows of the LAST aggregation on fp8 rows, for tests -- *rows and *ld are always written;
+ * where cap_rows >= *rows the bytes (q: *rows x *ld) and exponents (e: *rows) are copied to the host.
+ * MEASURED: see DESIGN.md section 3 (profiles/r36_k1_fp8_gather.txt). */
+#define DORY_K1_FP8_EXP_MIN (-117)
+#define DORY_K1_FP8_EXP_MAX 119
+int dory_k1_fp8_gather(dory_ctx *ctx, int mode);   /* 0 (default) = off */
+int dory_k1_fp8_gather_stats(dory_ctx *ctx, uint64_t *fp8_aggregations, uint64_t *other_family, uint64_t *no_form, uint64_t *rows_converted);
+int dory_k1_fp8_gather_download(dory_ctx *ctx, uint64_t cap_rows, uint8_t *q, uint8_t *e, uint64_t *rows, uint32_t *ld);
+int dory_k1_fp8_form(uint32_t ld, uint32_t slab, uint32_t *lanes, uint32_t *chunks, uint32_t *bytes_per_lane);
+int dory_k1_fp8_rows(const float *rows, uint64_t n, uint32_t cols, uint32_t ld, uint8_t *q_out, uint8_t *e_out);
+
 /* ---- K2b, the vertex transforms on the bf16 matrix instruction (opt-in, default off; nothing in the reference) -----------------
  * K2 (csrc/gemm.hip) multiplies in fp32, two k per v_mfma_f32_32x32x2_f32; its 602-wide products are bound by that instruction, not
  * by the bytes they read.  With a mode on, a product the mode covers runs K2b (csrc/gemm_bf16.hip, gemm_bf16_kernel) instead: the
