@@ -235,33 +235,28 @@ int gemm(dory_ctx *c, int ta, int tb, uint32_t M, uint32_t N, uint32_t K, const 
             ++c->gemm_res_launches;
             return DORY_OK;
         }
-        bool taken = false;
-        if (bf16) HIPCK(c, (c->gemm_bf16_split ? launch_gemm_bf16_split : launch_gemm_bf16)(g, c->scratch, c->scratch_bytes, c->compute, &taken));
-        if (taken) {
-            ++c->gemm_bf16_launches;
-            c->gemm_bf16_split_launches += c->gemm_bf16_split;
-            return DORY_OK;
-        }
-        HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
-        return DORY_OK;
     }
     sd.cols = N;
-    bool fused = false;
-    if (bf16 && c->gemm_bf16_send) {   // dory_gemm_bf16_send: K2b's / K2c's own send epilogue writes the rows
-        bool taken = false;
-        HIPCK(c, (c->gemm_bf16_split ? launch_gemm_bf16_split_send : launch_gemm_bf16_send)(g, sd, c->scratch, c->scratch_bytes, c->compute, &taken, &fused));
-        if (taken) {
-            ++c->gemm_bf16_launches;
-            c->gemm_bf16_split_launches += c->gemm_bf16_split;
-            if (fused) {
-                ++c->gemm_bf16_send_launches;
-                fused_pack_stamp(c, sent, send_dir, sd);
-            } else {   // (the send rule refused: the plain bf16 kernel ran, the exchange packs)
-                ++c->gemm_bf16_send_plain;
-                if (c->fused_stamp.src == sent) fused_stamp_drop(c);
-            }
-            return DORY_OK;
+    bool taken = false, fused = false;
+    // K2b / K2c; with a send target only under dory_gemm_bf16_send, where their own send epilogue writes the rows
+    if (bf16 && (!sent || c->gemm_bf16_send))
+        HIPCK(c, launch_gemm_bf16(g, c->gemm_bf16_split ? GEMM_BF16_SPLIT : GEMM_BF16_ROUNDED, sent ? &sd : nullptr, c->scratch, c->scratch_bytes,
+                                  c->compute, &taken, &fused));
+    if (taken) {
+        ++c->gemm_bf16_launches;
+        c->gemm_bf16_split_launches += c->gemm_bf16_split;
+        if (fused) {
+            ++c->gemm_bf16_send_launches;
+            fused_pack_stamp(c, sent, send_dir, sd);
+        } else if (sent) {   // (the send rule refused: the plain bf16 kernel ran, the exchange packs)
+            ++c->gemm_bf16_send_plain;
+            if (c->fused_stamp.src == sent) fused_stamp_drop(c);
         }
+        return DORY_OK;
+    }
+    if (!sent) {
+        HIPCK(c, launch_gemm(g, c->scratch, c->scratch_bytes, c->compute));
+        return DORY_OK;
     }
     // no bf16 send form asked for or taken: the fused halo pack keeps K2's fp32 kernel (with the switch on, an empty product -- an empty
     // rank's -- is not counted: it launches nothing)

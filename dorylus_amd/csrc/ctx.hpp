@@ -633,21 +633,18 @@ size_t gemm_scratch_bytes(uint32_t M, uint32_t N, uint32_t K);
 // K2b (gemm_bf16.hip; dory_gemm_bf16): the same product on v_mfma_f32_32x32x16_bf16, the fp32 operands rounded to bf16 on their
 // way into LDS, fp32 sums; K2's geometry, split plan (gemm_pick_splits) and second-stage sum (launch_splitk_reduce).  *taken =
 // false and nothing launched for what K2's launcher answers without a kernel (M, N or K == 0) or refuses (alignment): the
-// caller then calls launch_gemm
-hipError_t launch_gemm_bf16(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken);
-// K2c (gemm_bf16_split.hip; dory_gemm_bf16_split): K2b with each operand split into two bf16 pieces in registers and three instructions
-// per 16 k (a_lo b_hi + a_hi b_lo + a_hi b_hi) -- the bf16 matrix unit inside the fp32 parity criteria; *taken as above
-hipError_t launch_gemm_bf16_split(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken);
+// caller then calls launch_gemm (with a send target: launch_gemm_send).
+// K2c (gemm_bf16_split.hip; dory_gemm_bf16_split), kind GEMM_BF16_SPLIT: K2b with each operand split into two bf16 pieces in registers
+// and three instructions per 16 k (a_lo b_hi + a_hi b_lo + a_hi b_hi) -- the bf16 matrix unit inside the fp32 parity criteria.
+// sd, or null: the send forms of both (dory_gemm_bf16_send).  gemm_send_applies is the one rule by which K2, K2b and K2c decide whether
+// an epilogue writes a product's rows into sd->buf: *fused = true: the rows are there; taken and not fused: the plain bf16 kernel ran.
+// A split launch sends from launch_splitk_reduce_send (K2's splitk_reduce_send*_kernel).
+enum GemmBf16Kind { GEMM_BF16_ROUNDED = 0, GEMM_BF16_SPLIT = 1 };
+hipError_t launch_gemm_bf16(const GemmArgs &g, GemmBf16Kind kind, const GemmSend *sd, float *scratch, size_t scratch_bytes, hipStream_t s,
+                            bool *taken, bool *fused);
 uint32_t gemm_pick_splits(uint32_t M, uint32_t N, uint32_t K, int bm, int bn);
 hipError_t launch_splitk_reduce(const GemmArgs &g, const float *partial, uint32_t S, hipStream_t s);
-// The send forms of K2b and K2c (dory_gemm_bf16_send): gemm_send_applies is the one rule by which K2, K2b and K2c decide whether an
-// epilogue writes a product's rows into sd.buf.  *taken as above; *fused = true: the rows are in sd.buf; taken and not fused: the plain
-// bf16 kernel ran.  A split launch sends from launch_splitk_reduce_send (K2's splitk_reduce_send*_kernel).
 bool gemm_send_applies(const GemmArgs &g, const GemmSend &sd);
-hipError_t launch_gemm_bf16_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
-                                 bool *fused);
-hipError_t launch_gemm_bf16_split_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
-                                       bool *fused);
 hipError_t launch_splitk_reduce_send(const GemmArgs &g, const GemmSend &sd, const float *partial, uint32_t S, hipStream_t s);
 // K2r (gemm_bf16_resident.hip; dory_gemm_bf16_resident): K2b's NN and TN with A read from R, the resident bf16 copy of the tensor behind
 // g.A -- rows x ldr, ldr = cols rounded up to 32 elements, zeros in [cols, ldr), made by launch_gemm_resident_rows (nearest even).  NN's

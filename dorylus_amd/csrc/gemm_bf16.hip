@@ -152,58 +152,36 @@ __global__ __launch_bounds__(256) void gemm_bf16_send16_kernel(GemmArgs g, uint3
     gemm_bf16_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, true>(g, klen, partial, smem, sd);
 }
 
-// sd: the send form (the caller has asked gemm_send_applies: NN or NT), a split launch's rows leave from the reduce kernel
-template <int BN, int WM, int WN, int TM, int TN, int BK>
-static hipError_t launch_bf16_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd = nullptr) {
-    constexpr int BM = WM * TM * 32;
-    uint32_t klen;
-    const dim3 grid = gemm_bf16_grid(g, BM, BN, BK, scratch_bytes, &klen);
-    const uint32_t S = grid.z;
-    dim3 block(256);
-#define GEMM_BF16_LAUNCH(AK, BKM)                                                                                              \
-    do {                                                                                                                       \
-        if constexpr (BN == 128 && AK)                                                                                         \
-            hipLaunchKernelGGL((gemm_bf16_kernel_occ4<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((gemm_bf16_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch);      \
-    } while (0)
-#define GEMM_BF16_LAUNCH_SEND(KERNEL, BKM) hipLaunchKernelGGL((KERNEL<BN, WM, WN, TM, TN, false, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd)
-    if (sd && g.ta) return hipErrorInvalidValue;
-    else if (sd && sd->bf16 && !g.tb) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send16_kernel, true);
-    else if (sd && sd->bf16) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send16_kernel, false);
-    else if (sd && !g.tb) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send_kernel, true);
-    else if (sd) GEMM_BF16_LAUNCH_SEND(gemm_bf16_send_kernel, false);
-    else if (!g.ta && !g.tb) GEMM_BF16_LAUNCH(false, true);
-    else if (!g.ta && g.tb) GEMM_BF16_LAUNCH(false, false);
-    else if (g.ta && !g.tb) GEMM_BF16_LAUNCH(true, true);
-    else return hipErrorInvalidValue;
-#undef GEMM_BF16_LAUNCH
-#undef GEMM_BF16_LAUNCH_SEND
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || S == 1) return e;
-    return sd ? launch_splitk_reduce_send(g, *sd, scratch, S, s) : launch_splitk_reduce(g, scratch, S, s);
-}
+// the kernel of a form, for launch_mfma16 (gemm_bf16_tile.hpp); TN never sends
+struct K2bKernels {
+    template <int BN, int WM, int WN, int TM, int TN, int BK, bool AK, bool BKM>
+    void launch(dim3 grid, hipStream_t s, const GemmArgs &g, uint32_t klen, float *scratch, const GemmSend *sd) const {
+        const dim3 block(256);
+        if (!sd) {
+            if constexpr (BN == 128 && AK)
+                hipLaunchKernelGGL((gemm_bf16_kernel_occ4<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch);
+            else
+                hipLaunchKernelGGL((gemm_bf16_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch);
+        } else if constexpr (!AK) {
+            if (sd->bf16) hipLaunchKernelGGL((gemm_bf16_send16_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd);
+            else hipLaunchKernelGGL((gemm_bf16_send_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd);
+        }
+    }
+};
 
-// *taken = false and nothing launched where K2's launcher does something else than run a kernel, or refuses: an empty product
-// (K == 0 is its memset) and operands off its 16-byte rule -- the caller then calls launch_gemm, which behaves as ever
-hipError_t launch_gemm_bf16(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken) {
-    *taken = gemm_bf16_takes(g);
-    if (!*taken) return hipSuccess;
-    if (g.N > 64) return launch_bf16_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
-    return launch_bf16_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
-}
-
-// dory_gemm_bf16_send: *taken as above; *fused = the rows are in sd.buf (gemm_send_applies, K2's own rule); taken and not fused: the
-// plain kernel ran and the exchange packs
-hipError_t launch_gemm_bf16_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
-                                 bool *fused) {
+// K2b (kind GEMM_BF16_ROUNDED) or K2c (GEMM_BF16_SPLIT).  *taken = false and nothing launched where K2's launcher does something else
+// than run a kernel, or refuses: an empty product (K == 0 is its memset) and operands off its 16-byte rule -- the caller then calls
+// launch_gemm or launch_gemm_send, which behave as ever.  With sd (dory_gemm_bf16_send): *fused = the rows are in sd->buf
+// (gemm_send_applies, K2's own rule); taken and not fused: the plain kernel ran and the exchange packs
+hipError_t launch_gemm_bf16(const GemmArgs &g, GemmBf16Kind kind, const GemmSend *sd, float *scratch, size_t scratch_bytes, hipStream_t s,
+                            bool *taken, bool *fused) {
     *fused = false;
     *taken = gemm_bf16_takes(g);
     if (!*taken) return hipSuccess;
-    *fused = gemm_send_applies(g, sd);
-    const GemmSend *p = *fused ? &sd : nullptr;
-    if (g.N > 64) return launch_bf16_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
-    return launch_bf16_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
+    *fused = sd && gemm_send_applies(g, *sd);
+    if (!*fused) sd = nullptr;
+    if (kind == GEMM_BF16_SPLIT) return launch_gemm_bf16x3(g, scratch, scratch_bytes, s, sd);
+    return launch_mfma16(K2bKernels{}, g, scratch, scratch_bytes, s, sd);
 }
 
 }  // namespace dory

@@ -251,27 +251,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     gemm_res_body<BN, WM, WN, TM, TN, A_KMAJOR, BK>(g, R, ldr, klen, partial, smem);
 }
 
-template <int BN, int WM, int WN, int TM, int TN, int BK>
-static hipError_t launch_res_bn(const GemmArgs &g, const uint16_t *R, uint32_t ldr, float *scratch, size_t scratch_bytes, hipStream_t s) {
-    constexpr int BM = WM * TM * 32;
-    uint32_t klen;
-    const dim3 grid = gemm_bf16_grid(g, BM, BN, BK, scratch_bytes, &klen);   // K2b's plan: the same splits, the same bits
-    const uint32_t S = grid.z;
-    dim3 block(256);
-#define GEMM_RES_LAUNCH(AK)                                                                                                          \
-    do {                                                                                                                             \
-        if constexpr (BN == 128)                                                                                                     \
-            hipLaunchKernelGGL((gemm_bf16_resident_kernel_occ4<BN, WM, WN, TM, TN, AK, BK>), grid, block, 0, s, g, R, ldr, klen, scratch); \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((gemm_bf16_resident_kernel<BN, WM, WN, TM, TN, AK, BK>), grid, block, 0, s, g, R, ldr, klen, scratch);      \
-    } while (0)
-    if (g.ta) GEMM_RES_LAUNCH(true);
-    else GEMM_RES_LAUNCH(false);
-#undef GEMM_RES_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || S == 1) return e;
-    return launch_splitk_reduce(g, scratch, S, s);
-}
+// the kernel of a form, for launch_mfma16 (gemm_bf16_tile.hpp)
+struct K2rKernels {
+    const uint16_t *R;
+    uint32_t ldr;
+    template <int BN, int WM, int WN, int TM, int TN, int BK, bool AK, bool BKM>
+    void launch(dim3 grid, hipStream_t s, const GemmArgs &g, uint32_t klen, float *scratch, const GemmSend *) const {
+        const dim3 block(256);
+        if constexpr (BKM) {   // (NN and TN only: gemm_bf16_resident_takes)
+            if constexpr (BN == 128)
+                hipLaunchKernelGGL((gemm_bf16_resident_kernel_occ4<BN, WM, WN, TM, TN, AK, BK>), grid, block, 0, s, g, R, ldr, klen, scratch);
+            else
+                hipLaunchKernelGGL((gemm_bf16_resident_kernel<BN, WM, WN, TM, TN, AK, BK>), grid, block, 0, s, g, R, ldr, klen, scratch);
+        }
+    }
+};
 
 bool gemm_bf16_resident_takes(const GemmArgs &g) { return !g.tb && gemm_bf16_takes(g); }
 
@@ -279,8 +273,7 @@ bool gemm_bf16_resident_takes(const GemmArgs &g) { return !g.tb && gemm_bf16_tak
 // g.M rows of g.K <= ldr columns, TN g.K rows of g.M columns; the caller has asked gemm_bf16_resident_takes(g).
 hipError_t launch_gemm_bf16_resident(const GemmArgs &g, const uint16_t *R, uint32_t ldr, float *scratch, size_t scratch_bytes, hipStream_t s) {
     if (!gemm_bf16_resident_takes(g) || !R || (ldr & 31u) || (!g.ta && g.K > ldr)) return hipErrorInvalidValue;
-    if (g.N > 64) return launch_res_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, R, ldr, scratch, scratch_bytes, s);
-    return launch_res_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, R, ldr, scratch, scratch_bytes, s);
+    return launch_mfma16(K2rKernels{R, ldr}, g, scratch, scratch_bytes, s, nullptr);   // K2b's plan: the same splits, the same bits
 }
 
 }  // namespace dory

@@ -181,46 +181,22 @@ void gemm_bf16x3_send16_kernel(GemmArgs g, uint32_t klen, float *partial, GemmSe
     gemm_bf16x3_body<BN, WM, WN, TM, TN, A_KMAJOR, B_KMAJOR, BK, true, true>(g, klen, partial, smem, sd);
 }
 
-// sd: the send form (the caller has asked gemm_send_applies: NN or NT), a split launch's rows leave from the reduce kernel
-template <int BN, int WM, int WN, int TM, int TN, int BK>
-static hipError_t launch_bf16x3_bn(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd = nullptr) {
-    uint32_t klen;
-    const dim3 grid = gemm_bf16_grid(g, WM * TM * 32, BN, BK, scratch_bytes, &klen);
-    const dim3 block(256);
-#define GEMM_BF16X3_LAUNCH_SEND(KERNEL, BKM) hipLaunchKernelGGL((KERNEL<BN, WM, WN, TM, TN, false, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd)
-    if (sd && g.ta) return hipErrorInvalidValue;
-    else if (sd && sd->bf16 && !g.tb) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send16_kernel, true);
-    else if (sd && sd->bf16) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send16_kernel, false);
-    else if (sd && !g.tb) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send_kernel, true);
-    else if (sd) GEMM_BF16X3_LAUNCH_SEND(gemm_bf16x3_send_kernel, false);
-    else if (!g.ta && !g.tb) hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, false, true, BK>), grid, block, 0, s, g, klen, scratch);
-    else if (!g.ta && g.tb) hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, false, false, BK>), grid, block, 0, s, g, klen, scratch);
-    else if (g.ta && !g.tb) hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, true, true, BK>), grid, block, 0, s, g, klen, scratch);
-    else return hipErrorInvalidValue;
-#undef GEMM_BF16X3_LAUNCH_SEND
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || grid.z == 1) return e;
-    return sd ? launch_splitk_reduce_send(g, *sd, scratch, grid.z, s) : launch_splitk_reduce(g, scratch, grid.z, s);
-}
+// the kernel of a form, for launch_mfma16 (gemm_bf16_tile.hpp); TN never sends
+struct K2cKernels {
+    template <int BN, int WM, int WN, int TM, int TN, int BK, bool AK, bool BKM>
+    void launch(dim3 grid, hipStream_t s, const GemmArgs &g, uint32_t klen, float *scratch, const GemmSend *sd) const {
+        const dim3 block(256);
+        if (!sd) {
+            hipLaunchKernelGGL((gemm_bf16x3_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch);
+        } else if constexpr (!AK) {
+            if (sd->bf16) hipLaunchKernelGGL((gemm_bf16x3_send16_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd);
+            else hipLaunchKernelGGL((gemm_bf16x3_send_kernel<BN, WM, WN, TM, TN, AK, BKM, BK>), grid, block, 0, s, g, klen, scratch, *sd);
+        }
+    }
+};
 
-// *taken as launch_gemm_bf16 sets it
-hipError_t launch_gemm_bf16_split(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken) {
-    *taken = gemm_bf16_takes(g);
-    if (!*taken) return hipSuccess;
-    if (g.N > 64) return launch_bf16x3_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
-    return launch_bf16x3_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s);
-}
-
-// dory_gemm_bf16_send under K2c: *taken and *fused as launch_gemm_bf16_send sets them
-hipError_t launch_gemm_bf16_split_send(const GemmArgs &g, const GemmSend &sd, float *scratch, size_t scratch_bytes, hipStream_t s, bool *taken,
-                                       bool *fused) {
-    *fused = false;
-    *taken = gemm_bf16_takes(g);
-    if (!*taken) return hipSuccess;
-    *fused = gemm_send_applies(g, sd);
-    const GemmSend *p = *fused ? &sd : nullptr;
-    if (g.N > 64) return launch_bf16x3_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
-    return launch_bf16x3_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(g, scratch, scratch_bytes, s, p);
+hipError_t launch_gemm_bf16x3(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd) {
+    return launch_mfma16(K2cKernels{}, g, scratch, scratch_bytes, s, sd);
 }
 
 }  // namespace dory

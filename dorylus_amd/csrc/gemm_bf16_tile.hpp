@@ -1,6 +1,7 @@
 // gemm_bf16_tile.hpp -- what K2b (gemm_bf16.hip) and K2c (gemm_bf16_split.hip) share: the swizzled [i][BK k] bf16 LDS image, the
-// register-staged loader of one operand's fp32 tile, the send epilogue of their send forms, and the launch plan (split count and k-length)
-// of a 128 x BN product.
+// register-staged loader of one operand's fp32 tile, the send epilogue of their send forms, and -- with K2r (gemm_bf16_resident.hip) --
+// the launch plan (split count and k-length) of a 128 x BN product and the launch ladder (launch_mfma16).
+// (The device text of the family stays per file: profiles/r37_gemm_family_isa.txt lists the merges that changed a kernel's instructions.)
 #pragma once
 #include "ctx.hpp"
 
@@ -207,11 +208,37 @@ inline dim3 gemm_bf16_grid(const GemmArgs &g, int BM, int BN, int BK, size_t scr
     return dim3((g.M + BM - 1) / BM, (g.N + BN - 1) / BN, (g.K + *klen - 1) / *klen);
 }
 
-// *taken of launch_gemm_bf16 / launch_gemm_bf16_split: false where K2's launcher does something else than run a kernel, or refuses --
-// an empty product (K == 0 is its memset) and operands off its 16-byte rule
+// *taken of launch_gemm_bf16: false where K2's launcher does something else than run a kernel, or refuses -- an empty product
+// (K == 0 is its memset) and operands off its 16-byte rule
 inline bool gemm_bf16_takes(const GemmArgs &g) {
     if (g.M == 0 || g.N == 0 || g.K == 0 || (g.ta && g.tb)) return false;
     return !((g.lda & 3u) || (g.ldb & 3u) || (reinterpret_cast<uintptr_t>(g.A) & 15u) || (reinterpret_cast<uintptr_t>(g.B) & 15u));
 }
+
+// The launch ladder of K2b, K2c and K2r.  kernels.launch<BN, WM, WN, TM, TN, BK, A_KMAJOR, B_KMAJOR>(grid, s, g, klen, scratch, sd)
+// launches the file's kernel of that form -- the send form with sd (the caller has asked gemm_send_applies: NN or NT) -- and
+// instantiates nothing for a form the file does not have.  A split launch is followed by K2's second-stage sum, from which a split
+// send launch's rows leave.
+template <int BN, int WM, int WN, int TM, int TN, int BK, class Kernels>
+hipError_t launch_mfma16_bn(const Kernels &kernels, const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd) {
+    if ((g.ta && g.tb) || (sd && g.ta)) return hipErrorInvalidValue;
+    uint32_t klen;
+    const dim3 grid = gemm_bf16_grid(g, WM * TM * 32, BN, BK, scratch_bytes, &klen);
+    if (g.ta) kernels.template launch<BN, WM, WN, TM, TN, BK, true, true>(grid, s, g, klen, scratch, sd);
+    else if (g.tb) kernels.template launch<BN, WM, WN, TM, TN, BK, false, false>(grid, s, g, klen, scratch, sd);
+    else kernels.template launch<BN, WM, WN, TM, TN, BK, false, true>(grid, s, g, klen, scratch, sd);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || grid.z == 1) return e;
+    return sd ? launch_splitk_reduce_send(g, *sd, scratch, grid.z, s) : launch_splitk_reduce(g, scratch, grid.z, s);
+}
+// ... in K2's two shapes: the wide one above 64 columns
+template <class Kernels>
+hipError_t launch_mfma16(const Kernels &kernels, const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd) {
+    if (g.N > 64) return launch_mfma16_bn<128, 2, 2, 2, 2, GEMM_BF16_BK>(kernels, g, scratch, scratch_bytes, s, sd);
+    return launch_mfma16_bn<64, 4, 1, 1, 2, GEMM_BF16_BK>(kernels, g, scratch, scratch_bytes, s, sd);
+}
+
+// K2c's side of launch_gemm_bf16 (its kernels are in gemm_bf16_split.hip's translation unit)
+hipError_t launch_gemm_bf16x3(const GemmArgs &g, float *scratch, size_t scratch_bytes, hipStream_t s, const GemmSend *sd);
 
 }  // namespace dory
